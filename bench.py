@@ -13,19 +13,23 @@ and keyframes are created at the reference's rate (every ~25 frames).
 3584 sequences per GPU in 14 sequence groups of 256 (weak scaling: the same per rank; 2048 in 8
 groups: about 6 % fewer frames/s at half the time per step, profiles/r03_seqs_sweep.txt).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
-Rank 0 prints ONE JSON line (contract of the driver). The timed region (exactly K
-steps between barrier + synchronize) is repeated `--repeats` times on the running
-sequences and `value` is the median repeat; all repeats are listed. `roofline`
+Rank 0 prints ONE JSON line (contract of the driver). A plain run sets up, warms up,
+times exactly K steps (between barrier + synchronize; `--repeats R` measures R such
+regions in a row and `value` is the median) and prints the line. `roofline`
 describes the stage with the largest measured launch time (HIP events on the
-stream the kernel runs on), `cpu_baseline` the CPU oracle timed on this box's
-host cores (one thread, and all cores) on a bounded sample; rank 0, N=1 only.
-The all-cores leg runs two sequences of EVERY sequence group and its poses are
-compared frame by frame with the HIP trajectories of those sequences (`parity`).
+stream the kernel runs on, recorded in the timed steps). `--dump-outputs DIR`
+writes what the last timed step computed as DIR/<name>.npy (dump_outputs).
+`--full` adds the legs beside the headline figure, rank 0 and N=1 only: the
+fast-solver, single-sequence, host-input and small C3 legs, and `cpu_baseline`, the
+CPU oracle timed on this box's host cores (one thread, and all cores) on a bounded
+sample. The all-cores leg runs two sequences of EVERY sequence group and its poses
+are compared frame by frame with the HIP trajectories of those sequences (`parity`).
 """
 import argparse
+import ctypes as C
 import json
 import os
 import sys
@@ -46,7 +50,7 @@ import numpy as np
 import torch
 
 from stereo_svo_slam_amd import multi_seq, synth
-from stereo_svo_slam_amd.stereo_slam import StereoSlamBatch
+from stereo_svo_slam_amd.stereo_slam import KP_INFO_DTYPE, StereoSlamBatch
 
 HBM_PEAK_GBS = 8000.0   # MI355X HBM3E spec peak, /opt/skills/guides/MI355X_MICROARCH.md
 VALU_PEAK = 1024 * 2.4e9 / 2      # wave64 VALU instructions / s of the chip: 1024 SIMD-32 units, 2 cycles each (same guide)
@@ -105,7 +109,9 @@ def render_loops(cfg_name, loop_ids, n_frames, device, scale=MOTION_SCALE):
     scenes = {}
     lefts, rights = [], []
     for lid in loop_ids:
-        sc = scenes.setdefault(lid % 8, synth.Scene(lid % 8, device))
+        if lid % 8 not in scenes:                   # (a Scene is seeded by its id: built once per id)
+            scenes[lid % 8] = synth.Scene(lid % 8, device)
+        sc = scenes[lid % 8]
         poses = synth.loop_trajectory(n_frames, lid, scale * n_frames / LOOP_FRAMES)
         seeds = 7919 * (lid + 1) + 2 * np.arange(n_frames)
         lefts.append(synth.render_frames_gpu(sc, cfg, poses, False, 1.0, seeds))
@@ -224,14 +230,32 @@ def load_profile_json(name):
         return None
 
 
-def run_batch(cfg, lefts, rights, plan, B, K, Wm, reps, device, world, coll_dev, fast, borrow, prewarm):
-    """The timed legs of one ctx of B sequences: returns (slam, seconds per repeat, totals before / after)."""
+def step_packer(lefts, rights, plan, borrow):
+    """packs_for(slam, n): the svo_submit_images arguments of steps 0..n-1 (slam.pack_images), step k
+    showing frame (offset + k) % nF of every sequence's loop at time stamp k / 20. The image pointers
+    of a step depend on k % nF alone, so they are packed once per phase of the loop and each step gets
+    a copy of its phase's pack with its own time stamps (element 3 of the tuple): the set-up time does
+    not grow with the step count."""
     nF = lefts[0].shape[0]
+    lv = [list(x.unbind(0)) for x in lefts]          # [H, W] views of every rendered frame, made once
+    rv = [list(x.unbind(0)) for x in rights]
 
     def packs_for(slam, n):
-        return [slam.pack_images([lefts[plan[s][0]][frame_index(k, nF, plan[s][1])] for s in range(slam.n)],
-                                 [rights[plan[s][0]][frame_index(k, nF, plan[s][1])] for s in range(slam.n)],
-                                 [k / 20.0] * slam.n, borrow=borrow) for k in range(n)]
+        phases, out = {}, []
+        for k in range(n):
+            if k % nF not in phases:
+                phases[k % nF] = slam.pack_images([lv[plan[s][0]][frame_index(k, nF, plan[s][1])] for s in range(slam.n)],
+                                                  [rv[plan[s][0]][frame_index(k, nF, plan[s][1])] for s in range(slam.n)],
+                                                  [k / 20.0] * slam.n, borrow=borrow)
+            pk = phases[k % nF]
+            out.append(pk[:3] + ((C.c_float * slam.n)(*[k / 20.0] * slam.n),) + pk[4:])
+        return out
+    return packs_for
+
+
+def run_batch(cfg, lefts, rights, plan, B, K, Wm, reps, device, world, coll_dev, fast, borrow, prewarm):
+    """The timed legs of one ctx of B sequences: returns (slam, seconds per repeat, totals before / after)."""
+    packs_for = step_packer(lefts, rights, plan, borrow)
 
     # clocks: a fresh box starts with the GPU in a low power state. Untimed, on a throw-away ctx:
     # the same frames until `prewarm` seconds have passed (only sustained load matters here)
@@ -275,14 +299,61 @@ def stage_table(t0, t1):
     return launches, stage_ms, {STAGES[i]: float(per_launch_ms[i]) for i in range(8)}
 
 
+DUMP_BYTES = 60 * 10**6         # --dump-outputs stays under 64 MB in all
+DUMP_SEED = 0
+KP_FIELDS = ("level", "type", "keyframe_id", "keypoint_index", "outlier_count", "inlier_count", "score",
+             "kf_inv_depth", "kf_variance")
+
+
+def dump_outputs(slam, out_dir):
+    """What a caller of the timed path holds after its last step (get_frame / the keyframe decision of
+    every sequence), one float32 .npy per array: pose [B, 6] and is_keyframe [B] of every sequence; the
+    current frame's keypoints concatenated over the sequences (kps2d [n, 2], kps3d [n, 3], kp_<field> [n]
+    of the keypoint record, kp_flags = the three ignore flags as bits 0-2), kp_sequence [n] naming each
+    keypoint's ctx sequence. Should the keypoints not fit DUMP_BYTES, those of a fixed seeded sample of
+    sequences are written (pose and is_keyframe stay complete)."""
+    os.makedirs(out_dir, exist_ok=True)
+    B = slam.n
+    out = {"pose": np.stack([slam.pose(s) for s in range(B)]).astype(np.float32),
+           "is_keyframe": np.array([slam.stats(s).is_keyframe for s in range(B)], np.float32)}
+    budget = DUMP_BYTES - sum(a.nbytes for a in out.values())
+    per_kp = 4 * (2 + 3 + len(KP_FIELDS) + 2)
+    frames = {}
+    for s in np.random.default_rng(DUMP_SEED).permutation(B):
+        f = slam.get_frame(int(s))
+        if len(f.kps2d) * per_kp > budget:
+            break
+        budget -= len(f.kps2d) * per_kp
+        frames[int(s)] = f
+    seqs = sorted(frames)
+    info = np.concatenate([frames[s].info for s in seqs]) if seqs else np.zeros(0, KP_INFO_DTYPE)
+    out["kp_sequence"] = np.concatenate([np.full(len(frames[s].kps2d), s) for s in seqs] or [np.zeros(0)])
+    out["kps2d"] = np.concatenate([frames[s].kps2d for s in seqs] or [np.zeros((0, 2))])
+    out["kps3d"] = np.concatenate([frames[s].kps3d for s in seqs] or [np.zeros((0, 3))])
+    for name in KP_FIELDS:
+        out["kp_" + name] = info[name]
+    out["kp_flags"] = (info["ignore_during_refinement"] * 1 + info["ignore_completely"] * 2 +
+                       info["ignore_temporary"] * 4)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=80)
     ap.add_argument("--warmup", type=int, default=8)
-    ap.add_argument("--repeats", type=int, default=3,
+    ap.add_argument("--repeats", type=int, default=1,
                     help="the timed region of exactly --steps steps is measured this many times in a row; "
                          "value = median")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline figure: fast-solver, single-sequence, host-input "
+                         "and small C3 legs (off with --no-extras) and the CPU oracle baseline with its parity "
+                         "check (off with --no-cpu-baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed (pose, keyframe decision and "
+                         "keypoints of rank 0's sequences; the keypoints of a seeded sample of sequences should they "
+                         "exceed 60 MB) as float32 DIR/<name>.npy")
     ap.add_argument("--config", default="euroc", choices=sorted(synth.CONFIGS))
     ap.add_argument("--seqs", type=int, default=None,
                     help="sequences per GPU (default 3584 = fourteen groups of 256 on their own streams; hd: 512 = eight groups of 64)")
@@ -297,9 +368,9 @@ def main():
     ap.add_argument("--copy-input", action="store_true",
                     help="SVO_MEM_DEVICE: the ctx copies every device-resident frame into its own image set "
                          "(default: SVO_MEM_DEVICE_BORROW, frames used in place)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU oracle leg")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the fast-solver, single-sequence, host-input and C3 legs (profiling runs)")
+                    help="with --full: skip the fast-solver, single-sequence, host-input and C3 legs")
     ap.add_argument("--c3-seqs", type=int, default=64, help="sequences of the small C3 (1920x1080) leg; 0: skip")
     ap.add_argument("--prewarm", type=float, default=1.5,
                     help="seconds of untimed load on a throw-away ctx before the warm-up steps (clock ramp)")
@@ -309,6 +380,8 @@ def main():
     ap.add_argument("--share-gpu", action="store_true", help="all ranks use cuda:0 (rehearsal only)")
     args = ap.parse_args()
     t_start = time.perf_counter()
+    extras = args.full and not args.no_extras
+    cpu_leg = args.full and not args.no_cpu_baseline
 
     rank, local_rank, world = multi_seq.init_distributed(args.backend)
     if world != max(args.gpus, 1) and world > 1:
@@ -343,6 +416,8 @@ def main():
                     n_kps=t1.keypoints - t0.keypoints,
                     n_grad=t1.gn_gradient_calls - t0.gn_gradient_calls,
                     n_cost=t1.gn_cost_calls - t0.gn_cost_calls)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(slam, args.dump_outputs)
 
     # one small exchange at the end: per-sequence summaries (id, frames, final pose)
     seq_ids = multi_seq.sequence_ids(rank, world, B)
@@ -431,15 +506,16 @@ def main():
     if same_cfg(pmc) and pmc.get("issue_activity"):
         issue = dict(pmc["issue_activity"], source=f"profiles/{PMC_PROFILE}: sum of SQ_ACTIVE_INST_ANY over the kernels of a step x 4 / "
                                                     "(step time x 2.4 GHz x 1024 SIMDs), an earlier counter run of this command (replayed)")
-    sample, sample_groups = group_sample(B, G)
-    gpu_traj = {s: np.asarray(slam.get_trajectory(s)) for s in sample}
+    if cpu_leg and world == 1:
+        sample, sample_groups = group_sample(B, G)
+        gpu_traj = {s: np.asarray(slam.get_trajectory(s)) for s in sample}
     # fps over tracked (non-keyframe) frames: the keyframe kernels' share of the groups' event time taken out
     kf_share = float(stage_ms[7] / max(stage_ms.sum(), 1e-9))
     tracked_only = (counters["frames"] - counters["keyframes"]) / max(counters["frames"], 1) * fps / max(1.0 - kf_share, 1e-9)
     slam.close()
 
     single = host_input = fast_leg = c3 = None
-    if not args.no_extras and world == 1 and not args.fast:
+    if extras and world == 1 and not args.fast:
         # the same workload with svo_ctx_set_fast_solver(1): what the approximate solver would buy
         fs = StereoSlamBatch(cfg, cfg["width"], cfg["height"], B, device.index)
         fs.set_fast_solver(True)
@@ -450,7 +526,7 @@ def main():
                             "mode on smooth motion, iteration traces not the reference's; never `value`"}
         fs.close()
         del fp
-    if not args.no_extras and world == 1:
+    if extras and world == 1:
         # latency leg: one sequence alone, frame by frame (svo_new_images returns when the frame is done)
         one = StereoSlamBatch(cfg, cfg["width"], cfg["height"], 1, device.index)
         one.enable_timing(True)
@@ -500,10 +576,10 @@ def main():
         del hl, hr, hp
 
     cpu = None
-    if not args.no_cpu_baseline and world == 1:
+    if cpu_leg and world == 1:
         cpu = cpu_baseline(cfg, lefts, rights, plan, n_steps, sample, sample_groups, gpu_trajectories=gpu_traj)
 
-    if not args.no_extras and world == 1 and not hd and args.c3_seqs > 0:
+    if extras and world == 1 and not hd and args.c3_seqs > 0:
         # a small run of BASELINE config 3 (1920x1080, ~2000 patches, 5-level SIA pyramid) so that the
         # driver's line carries it; the full-size C3 run is `bench.py --config hd` (profiles/)
         del lefts, rights

@@ -232,6 +232,85 @@ def test_bench_loop_plan_and_group_sample():
     assert seqs == [0, 4, 7, 1, 5, 8] and groups == [0, 1, 2, 0, 1, 2]
 
 
+def _ctxless_batch(n, h, w):
+    """A StereoSlamBatch without a ctx: enough for pack_images (host tensors, no GPU)."""
+    from stereo_svo_slam_amd.stereo_slam import StereoSlamBatch
+    b = StereoSlamBatch.__new__(StereoSlamBatch)
+    b._ctx, b.n, b.height, b.width = None, n, h, w
+    return b
+
+
+def test_bench_step_packer_matches_packing_every_step():
+    """bench.step_packer packs the image pointers once per phase of the loop: every step's arguments
+    equal those of packing that step's frames directly (pointers, stride, time stamps, memory mode),
+    past the wrap of the loop too."""
+    sys.path.insert(0, ROOT)
+    import bench
+    nF, H, W = 5, 6, 8
+    lefts = [torch.randint(0, 255, (nF, H, W), dtype=torch.uint8) for _ in range(3)]
+    rights = [torch.randint(0, 255, (nF, H, W), dtype=torch.uint8) for _ in range(3)]
+    plan = bench.loop_plan(7, 3, nF)
+    slam = _ctxless_batch(7, H, W)
+    packs = bench.step_packer(lefts, rights, plan, True)(slam, 13)
+    assert len(packs) == 13
+    for k, got in enumerate(packs):
+        want = slam.pack_images([lefts[plan[s][0]][bench.frame_index(k, nF, plan[s][1])] for s in range(7)],
+                                [rights[plan[s][0]][bench.frame_index(k, nF, plan[s][1])] for s in range(7)],
+                                [k / 20.0] * 7, borrow=True)
+        assert list(got[0]) == list(want[0]) and list(got[1]) == list(want[1])
+        assert got[2] == want[2] and list(got[3]) == list(want[3]) and got[5] == want[5]
+
+
+def test_bench_dump_outputs(tmp_path, monkeypatch):
+    """bench.dump_outputs writes the last step's pose, keyframe decision and keypoints of every
+    sequence as float32 .npy files; over the size limit, the keypoints of a fixed sample of whole
+    sequences (pose and keyframe decision stay complete)."""
+    sys.path.insert(0, ROOT)
+    import bench
+    from stereo_svo_slam_amd.stereo_slam import KP_INFO_DTYPE, Frame
+
+    class FakeSlam:
+        n = 6
+
+        def pose(self, s):
+            return np.arange(6, dtype=np.float32) + 10 * s
+
+        def stats(self, s):
+            return type("St", (), {"is_keyframe": int(s % 2)})()
+
+        def get_frame(self, s):
+            m = s + 1
+            info = np.zeros(m, KP_INFO_DTYPE)
+            info["level"] = s
+            info["kf_inv_depth"] = 0.5 * s
+            info["ignore_completely"] = 1
+            k2 = np.full((m, 2), s, np.float32)
+            return Frame(self.pose(s), k2, np.full((m, 3), -s, np.float32), info)
+
+    bench.dump_outputs(FakeSlam(), str(tmp_path / "all"))
+    ld = lambda d, name: np.load(tmp_path / d / (name + ".npy"))
+    assert ld("all", "pose").dtype == np.float32 and ld("all", "pose").shape == (6, 6)
+    assert ld("all", "is_keyframe").tolist() == [0, 1, 0, 1, 0, 1]
+    seq = ld("all", "kp_sequence")
+    assert seq.tolist() == [s for s in range(6) for _ in range(s + 1)]
+    assert np.array_equal(ld("all", "kps2d")[:, 0], seq) and np.array_equal(ld("all", "kps3d")[:, 2], -seq)
+    assert np.array_equal(ld("all", "kp_level"), seq) and np.array_equal(ld("all", "kp_kf_inv_depth"), 0.5 * seq)
+    assert set(ld("all", "kp_flags").tolist()) == {2.0}
+    for f in os.listdir(tmp_path / "all"):
+        assert np.load(tmp_path / "all" / f).dtype == np.float32
+
+    per_kp = 4 * (2 + 3 + len(bench.KP_FIELDS) + 2)
+    monkeypatch.setattr(bench, "DUMP_BYTES", 6 * 7 * 4 + 9 * per_kp)
+    bench.dump_outputs(FakeSlam(), str(tmp_path / "a"))
+    bench.dump_outputs(FakeSlam(), str(tmp_path / "b"))
+    assert ld("a", "pose").shape == (6, 6)
+    seq = ld("a", "kp_sequence")
+    assert 0 < len(seq) <= 9 and np.array_equal(seq, np.sort(seq))
+    for s in set(seq.tolist()):                       # whole sequences only
+        assert (seq == s).sum() == s + 1
+    assert np.array_equal(seq, ld("b", "kp_sequence"))
+
+
 def test_loop_trajectory_is_closed_and_smooth():
     p = synth.loop_trajectory(192, 3, 0.75)
     assert p.shape == (192, 6)
