@@ -812,21 +812,21 @@ static int sia_img_bytes(const svo_camera_settings& cam, int width, int height) 
 }
 
 template <int WAVES, int MODE>
-static bool sia_launch_shape(const SiaArgs* d_args, int batch, int img, int cap, size_t lds, hipStream_t stream) {
+static LaunchStatus sia_launch_shape(const SiaArgs* d_args, int batch, int img, int cap, size_t lds, hipStream_t stream) {
     static LdsLimit limit;
-    if (raise_lds_limit(limit, reinterpret_cast<const void*>(sia_gn_kernel<WAVES, MODE>), (int)SIA_LDS_BUDGET) != hipSuccess)
-        return false;
+    const hipError_t e = raise_lds_limit(limit, reinterpret_cast<const void*>(sia_gn_kernel<WAVES, MODE>), (int)SIA_LDS_BUDGET);
+    if (e != hipSuccess) return {true, e};
     hipLaunchKernelGGL((sia_gn_kernel<WAVES, MODE>), dim3(batch), dim3(64 * WAVES), lds, stream, d_args, img, cap);
-    return true;
+    return {true, hipSuccess};
 }
 
 // Workgroup shape of a launch: `batch` sequences of at most n_bound keypoints, one keypoint per
 // lane and pass: as many waves as 64-keypoint passes, at most 4. A few sequences keep everything
 // in LDS (MODE 0: records 256 B per keypoint + the finest level image), a batch only the cost
 // records (MODE 1); sets that do not fit (1920x1080, ~1700 keypoints) read records, per-keypoint
-// values and image taps from L2 (MODE 2). Returns false if n_bound exceeds the workspaces.
-bool launch_sia(const SiaArgs* d_args, int batch, const svo_camera_settings& cam, int width,
-                int height, int n_bound, int rec_cap, int exact, hipStream_t stream) {
+// values and image taps from L2 (MODE 2). Does not fit if n_bound exceeds the workspaces.
+LaunchStatus launch_sia(const SiaArgs* d_args, int batch, const svo_camera_settings& cam, int width,
+                        int height, int n_bound, int rec_cap, int exact, hipStream_t stream) {
     const int nb = std::max(n_bound, 1);
     const int n_lv = cam.max_pyramid_levels - cam.min_pyramid_level_pose_estimation;
     const int img = sia_img_bytes(cam, width, height);
@@ -843,11 +843,6 @@ bool launch_sia(const SiaArgs* d_args, int batch, const svo_camera_settings& cam
     // 192: with keyframes at the reference's rate the sets reach ~160, and the two-wave shape costs every sequence
     // of the launch a second wave — 5.7 against 4.8 ms per launch in the round-3 profile)
     if (batched) { mode = 2; waves = nb <= 192 ? 1 : nb <= 384 ? 2 : 4; }
-    // (experiments: SVO_SIA_MODE = 0 / 1 / 2 and SVO_SIA_WAVES = 1 / 2 / 4 force the shape of batched launches)
-    static const int env_mode = getenv("SVO_SIA_MODE") ? atoi(getenv("SVO_SIA_MODE")) : -1;
-    static const int env_waves = getenv("SVO_SIA_WAVES") ? atoi(getenv("SVO_SIA_WAVES")) : 0;
-    if (batched && env_mode >= 0 && env_mode <= 2) mode = env_mode;
-    if (batched && (env_waves == 1 || env_waves == 2 || env_waves == 4)) waves = env_waves;
     int T = 64 * waves;
     int cap = (nb + T - 1) / T * T;                   // every lane of every pass owns a slot
     size_t lds = sia_lds_layout(img, cap, T, exact != 0, mode).total;
@@ -860,14 +855,14 @@ bool launch_sia(const SiaArgs* d_args, int batch, const svo_camera_settings& cam
         cap = (nb + T - 1) / T * T;
         lds = sia_lds_layout(img, cap, T, exact != 0, mode).total;
     }
-    if (lds > SIA_LDS_BUDGET || cap > rec_cap) return false;
+    if (lds > SIA_LDS_BUDGET || cap > rec_cap) return {false, hipSuccess};
     hipLaunchKernelGGL(sia_prep_kernel, dim3((((nb + 3) & ~3) * 16 + 63) / 64, n_lv, batch), dim3(64), 0, stream, d_args);
 #define SIA_CASE(W, M) if (waves == W && mode == M) return sia_launch_shape<W, M>(d_args, batch, img, cap, lds, stream);
     SIA_CASE(1, 0) SIA_CASE(2, 0) SIA_CASE(4, 0)
     SIA_CASE(1, 1) SIA_CASE(2, 1) SIA_CASE(4, 1)
     SIA_CASE(1, 2) SIA_CASE(2, 2) SIA_CASE(4, 2)
 #undef SIA_CASE
-    return false;
+    return {false, hipSuccess};
 }
 
 size_t sia_rec_ws_floats(const svo_camera_settings& cam, int rec_cap) {

@@ -1,0 +1,23 @@
+// svo_group.hpp — one group of sequences (svo_group.hip) as svo_ctx.hip drives it.
+#pragma once
+
+#include <cstdint>
+#include <memory>
+
+#include "../../include/svo_hip.h"
+
+struct svo_group;
+struct GroupDelete { void operator()(svo_group* g) const; };   // synchronises the group's stream, then frees all
+using Group = std::unique_ptr<svo_group, GroupDelete>;
+
+int grp_create(const svo_camera_settings* cam, int width, int height, int n_sequences, int device, Group* out);
+// one frame of every sequence whose two images are not NULL; after a failure the group rejects further frames
+int grp_new_images(svo_group* g, const uint8_t* const* left, const uint8_t* const* right, int stride,
+                   const float* time_stamps, int mem);
+void grp_set_exact_pinv(svo_group* g, int on);
+void grp_enable_timing(svo_group* g, int on);
+svo_totals grp_totals(const svo_group* g);
+
+// implemented by svo_ctx.hip: the group of ctx sequence `seq` and its index there, once every queue of the ctx
+// has drained, with the ctx's device current (the per-sequence getters of svo_group.hip start here)
+int ctx_seq(svo_ctx* ctx, int seq, svo_group** g, int* local);

@@ -3,7 +3,7 @@ bench.py for each (SVO_HIP_LIB override). Usage: variant_bench.py "name:-DX=1 -D
 import json, os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "stereo-svo-slam_amd", "csrc")
-srcs = [os.path.join(CSRC, f) for f in "svo_capi.hip svo_ctx.hip pyramid.hip sia.hip klt.hip reproj.hip depth.hip keyframe.hip".split()]
+srcs = [os.path.join(CSRC, f) for f in "svo_capi.hip svo_ctx.hip svo_group.hip pyramid.hip sia.hip klt.hip reproj.hip depth.hip keyframe.hip".split()]
 extra = os.environ.get("BENCH_ARGS", "--seqs 64 --steps 30 --warmup 3 --no-cpu-baseline").split()
 for spec in sys.argv[1:]:
     name, flags = spec.split(":", 1)
