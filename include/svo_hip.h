@@ -222,6 +222,27 @@ int svo_ctx_enable_timing(svo_ctx *ctx, int on);
 int svo_ctx_set_fast_solver(svo_ctx *ctx, int on);  /* see svo_handle_set_fast_solver; default 0 */
 int svo_ctx_set_exact_pinv(svo_ctx *ctx, int on);   /* older name: set_fast_solver(!on) */
 
+/* The workgroup shapes the sparse alignment and the reprojection GN ran: one entry per distinct
+ * (kernel, waves, mode, cap), with the number of group launches that used it, summed over the ctx's
+ * groups since svo_ctx_create. Counted on the host where the shape is chosen. */
+enum { SVO_KERNEL_SIA_GN = 0,       /* sia_gn_kernel<waves, mode>                                 */
+       SVO_KERNEL_REPROJ_GN = 1 };  /* reproj_gn_kernel<waves> (mode 0)                           */
+typedef struct svo_launch_shape {
+    int32_t kernel;             /* SVO_KERNEL_*                                                   */
+    int32_t waves;              /* wavefronts (64 lanes) per sequence                            */
+    int32_t mode;               /* alignment: 0 records + image in LDS, 1 cost records in LDS,
+                                   2 records and image taps from L2                               */
+    int32_t cap;                /* keypoint slots per sequence                                    */
+    int64_t launches;
+} svo_launch_shape;
+/* writes min(max, distinct shapes) entries (sorted by kernel, waves, mode, cap); *n = distinct shapes */
+int svo_ctx_get_launch_shapes(svo_ctx *ctx, svo_launch_shape *out, int max, int *n);
+/* the shapes a launch of `batch` sequences of at most n_bound keypoints would run, without a GPU:
+ * out[0] the alignment (SVO_KERNEL_SIA_GN, workspaces of rec_cap keypoints, exact = reference-order
+ * mode), out[1] the reprojection GN; launches = 1 if the keypoints fit the kernel, else 0 */
+int svo_pick_launch_shapes(const svo_camera_settings *cam, int width, int height, int batch, int n_bound,
+                           int rec_cap, int exact, svo_launch_shape out[2]);
+
 #ifdef __cplusplus
 }
 #endif

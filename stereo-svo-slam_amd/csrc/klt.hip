@@ -21,6 +21,7 @@
 // the window drifts out of the search tile. All window sums are exact integers,
 // so the result does not depend on the reduction order.
 #include "svo_kernels.hpp"
+#include "klt_bounds.hpp"
 #include <cstring>
 #include <utility>
 
@@ -227,7 +228,7 @@ __device__ inline LkWeights lk_weights(float fa, float fb) {
 template <int LS, int MAXROWS>
 __device__ inline void stage_tile(uint8_t* tile, const ImgView& im, int x0, int y0, int nq, int rows) {
     const int tid = threadIdx.x;
-    const bool fast = x0 >= 0 && y0 >= 0 && x0 + 4 * nq <= im.w && y0 + rows <= im.h &&
+    const bool fast = klt_rect_in_image(x0, y0, 4 * nq, rows, im.w, im.h) &&
                       (((reinterpret_cast<uintptr_t>(im.data) | (uintptr_t)im.stride) & 3) == 0);
     if (fast) {
         constexpr int RPP = KLT_THREADS / 16;                        // rows per pass, 16 dword lanes per row
@@ -268,7 +269,7 @@ __device__ inline void stage_tile(uint8_t* tile, const ImgView& im, int x0, int 
 // dword's first pixel comes from the neighbouring lane); else byte by byte with BORDER_REFLECT_101.
 // The in-image case in two halves, so that a caller can have the loads in flight while it does something else.
 __device__ inline bool tile_in_image(const ImgView& im, int x0, int y0, int nq, int rows) {
-    return x0 >= 0 && y0 >= 0 && x0 + 4 * nq <= im.w && y0 + rows <= im.h &&
+    return klt_rect_in_image(x0, y0, 4 * nq, rows, im.w, im.h) &&
            (((reinterpret_cast<uintptr_t>(im.data) | (uintptr_t)im.stride) & 3) == 0);
 }
 template <class GEO>
@@ -472,9 +473,11 @@ __device__ __forceinline__ void klt_track_body(const KltArgs* __restrict__ args)
             hq0 = hd[0]; hq1 = hd[1];
 #pragma unroll
             for (int q = 0; q < KltTmpl<NPAIR>::TQ; q++) tq[q] = rec[q * 64 + tid];
-            const int px = cv_floor(nextx - halfWin), py = cv_floor(nexty - halfWin);      // where iteration 0 will look
+            // where iteration 0 will look, if it looks at all (its own range test, before the float-to-int conversion)
+            const bool look = klt_corner_in_range(nextx - halfWin, nexty - halfWin, win, J.w, J.h);
+            const int px = look ? cv_floor(nextx - halfWin) : 0, py = look ? cv_floor(nexty - halfWin) : 0;
             const int qx0 = (px - KLT_MARGIN) & ~3, qy0 = py - KLT_MARGIN;
-            if (tile_in_image(J, qx0, qy0, TW >> 2, TJ)) {
+            if (look && tile_in_image(J, qx0, qy0, TW >> 2, TJ)) {
                 tile_j2_load<GEO>(pre, J, qx0, qy0, TW >> 2, TJ);
                 tx0 = qx0; ty0 = qy0; tile_regs = true;
             }
@@ -499,10 +502,10 @@ __device__ __forceinline__ void klt_track_body(const KltArgs* __restrict__ args)
         asm volatile("" : "+v"(lc_b), "+v"(y0_b));
         const ImgView I = kfp->lk[level];            // (the keyframe's image: only a template that is built needs it)
         prevx -= halfWin; prevy -= halfWin;
-        const int iprevx = cv_floor(prevx), iprevy = cv_floor(prevy);
-        if (iprevx < -win || iprevx >= I.w || iprevy < -win || iprevy >= I.h) {
+        if (!klt_corner_in_range(prevx, prevy, win, I.w, I.h)) {
             lstate = KLT_OUTSIDE;
         } else {
+        const int iprevx = cv_floor(prevx), iprevy = cv_floor(prevy);
         wt = lk_weights(prevx - iprevx, prevy - iprevy);
 
         __syncthreads();
@@ -658,11 +661,11 @@ __device__ __forceinline__ void klt_track_body(const KltArgs* __restrict__ args)
 #endif
         for (int j = 0; j < SVO_KLT_MAXIT; j++) {
             KLT_COUNT(10, 1);
-            const int inextx = cv_floor(nextx), inexty = cv_floor(nexty);
-            if (inextx < -win || inextx >= J.w || inexty < -win || inexty >= J.h) {
+            if (!klt_corner_in_range(nextx, nexty, win, J.w, J.h)) {
                 if (level == 0) status = 0;
                 break;
             }
+            const int inextx = cv_floor(nextx), inexty = cv_floor(nexty);
             if (!have_tile || inextx < tx0 || inexty < ty0 || inextx + DW > tx0 + TW || inexty + DW > ty0 + TJ)
                 load_tile(inextx, inexty);
             wt = lk_weights(nextx - inextx, nexty - inexty);
@@ -708,11 +711,11 @@ __device__ __forceinline__ void klt_track_body(const KltArgs* __restrict__ args)
 
         if (status && level == 0) {
             const float npx = nx - halfWin, npy = ny - halfWin;
-            const int inx = cv_floor(npx), iny = cv_floor(npy);
-            if (inx < -win || inx >= J.w || iny < -win || iny >= J.h) {
+            if (!klt_corner_in_range(npx, npy, win, J.w, J.h)) {
                 status = 0;
                 continue;
             }
+            const int inx = cv_floor(npx), iny = cv_floor(npy);
             if (!have_tile || inx < tx0 || iny < ty0 || inx + DW > tx0 + TW || iny + DW > ty0 + TJ)
                 load_tile(inx, iny);
             wt = lk_weights(npx - inx, npy - iny);

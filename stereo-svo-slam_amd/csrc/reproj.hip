@@ -279,22 +279,27 @@ void launch_project(const float* pose, const svo_kp3d* kps3d, int n, const svo_c
 // n_bound: upper bound of the keypoint counts of the launch (sizes the LDS copy of the keypoints:
 // 24 B each). One wave per sequence up to 128 keypoints, four beyond. Does not fit when the
 // keypoints do not fit LDS (more than ~5000).
-LaunchStatus launch_reproj(const ReprojArgs* d_args, int batch, int n_bound, hipStream_t stream) {
+LaunchShape reproj_pick_shape(int batch, int n_bound) {
     // a batch of sequences: one wave each up to 256 keypoints (four staging steps): the four-wave shape took
     // 2.0 against 0.8 ms per launch in the round-3 profile, for every sequence of a launch whose largest set passed 128
     const int T = n_bound <= (batch >= 32 ? 256 : 128) ? 64 : 256;
     const int cap = (std::max(n_bound, 1) + T - 1) / T * T;          // whole staging steps
     const size_t lds = (size_t)cap * 6 * sizeof(float);
-    if (lds > 120 * 1024) return {false, hipSuccess};
+    return {lds <= 120 * 1024, T / 64, 0, cap, lds};
+}
+
+LaunchStatus launch_reproj(const ReprojArgs* d_args, int batch, int n_bound, hipStream_t stream) {
+    const LaunchShape sh = reproj_pick_shape(batch, n_bound);
+    if (!sh.fits) return {sh, hipSuccess};
     static LdsLimit limit1, limit4;
     hipError_t e = raise_lds_limit(limit1, reinterpret_cast<const void*>(reproj_gn_kernel<1>), 120 * 1024);
     if (e == hipSuccess) e = raise_lds_limit(limit4, reinterpret_cast<const void*>(reproj_gn_kernel<4>), 120 * 1024);
-    if (e != hipSuccess) return {true, e};
-    if (T == 64)
-        hipLaunchKernelGGL(reproj_gn_kernel<1>, dim3(batch), dim3(64), lds, stream, d_args, cap);
+    if (e != hipSuccess) return {sh, e};
+    if (sh.waves == 1)
+        hipLaunchKernelGGL(reproj_gn_kernel<1>, dim3(batch), dim3(64), sh.lds, stream, d_args, sh.cap);
     else
-        hipLaunchKernelGGL(reproj_gn_kernel<4>, dim3(batch), dim3(256), lds, stream, d_args, cap);
-    return {true, hipSuccess};
+        hipLaunchKernelGGL(reproj_gn_kernel<4>, dim3(batch), dim3(256), sh.lds, stream, d_args, sh.cap);
+    return {sh, hipSuccess};
 }
 
 }  // namespace svo

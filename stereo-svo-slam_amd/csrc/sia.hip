@@ -812,12 +812,12 @@ static int sia_img_bytes(const svo_camera_settings& cam, int width, int height) 
 }
 
 template <int WAVES, int MODE>
-static LaunchStatus sia_launch_shape(const SiaArgs* d_args, int batch, int img, int cap, size_t lds, hipStream_t stream) {
+static LaunchStatus sia_launch_shape(const SiaArgs* d_args, int batch, int img, const LaunchShape& sh, hipStream_t stream) {
     static LdsLimit limit;
     const hipError_t e = raise_lds_limit(limit, reinterpret_cast<const void*>(sia_gn_kernel<WAVES, MODE>), (int)SIA_LDS_BUDGET);
-    if (e != hipSuccess) return {true, e};
-    hipLaunchKernelGGL((sia_gn_kernel<WAVES, MODE>), dim3(batch), dim3(64 * WAVES), lds, stream, d_args, img, cap);
-    return {true, hipSuccess};
+    if (e != hipSuccess) return {sh, e};
+    hipLaunchKernelGGL((sia_gn_kernel<WAVES, MODE>), dim3(batch), dim3(64 * WAVES), sh.lds, stream, d_args, img, sh.cap);
+    return {sh, hipSuccess};
 }
 
 // Workgroup shape of a launch: `batch` sequences of at most n_bound keypoints, one keypoint per
@@ -825,10 +825,9 @@ static LaunchStatus sia_launch_shape(const SiaArgs* d_args, int batch, int img, 
 // in LDS (MODE 0: records 256 B per keypoint + the finest level image), a batch only the cost
 // records (MODE 1); sets that do not fit (1920x1080, ~1700 keypoints) read records, per-keypoint
 // values and image taps from L2 (MODE 2). Does not fit if n_bound exceeds the workspaces.
-LaunchStatus launch_sia(const SiaArgs* d_args, int batch, const svo_camera_settings& cam, int width,
-                        int height, int n_bound, int rec_cap, int exact, hipStream_t stream) {
+LaunchShape sia_pick_shape(int batch, const svo_camera_settings& cam, int width, int height, int n_bound, int rec_cap,
+                           int exact) {
     const int nb = std::max(n_bound, 1);
-    const int n_lv = cam.max_pyramid_levels - cam.min_pyramid_level_pose_estimation;
     const int img = sia_img_bytes(cam, width, height);
     // A batch of sequences: records, per-keypoint values and image taps from L2 (MODE 2) and one
     // wave per 128 keypoints, i.e. ~38 KB of LDS per sequence (the staging area of the ordered
@@ -855,14 +854,23 @@ LaunchStatus launch_sia(const SiaArgs* d_args, int batch, const svo_camera_setti
         cap = (nb + T - 1) / T * T;
         lds = sia_lds_layout(img, cap, T, exact != 0, mode).total;
     }
-    if (lds > SIA_LDS_BUDGET || cap > rec_cap) return {false, hipSuccess};
+    return {lds <= SIA_LDS_BUDGET && cap <= rec_cap, waves, mode, cap, lds};
+}
+
+LaunchStatus launch_sia(const SiaArgs* d_args, int batch, const svo_camera_settings& cam, int width,
+                        int height, int n_bound, int rec_cap, int exact, hipStream_t stream) {
+    const LaunchShape sh = sia_pick_shape(batch, cam, width, height, n_bound, rec_cap, exact);
+    if (!sh.fits) return {sh, hipSuccess};
+    const int nb = std::max(n_bound, 1);
+    const int n_lv = cam.max_pyramid_levels - cam.min_pyramid_level_pose_estimation;
+    const int img = sia_img_bytes(cam, width, height);
     hipLaunchKernelGGL(sia_prep_kernel, dim3((((nb + 3) & ~3) * 16 + 63) / 64, n_lv, batch), dim3(64), 0, stream, d_args);
-#define SIA_CASE(W, M) if (waves == W && mode == M) return sia_launch_shape<W, M>(d_args, batch, img, cap, lds, stream);
+#define SIA_CASE(W, M) if (sh.waves == W && sh.mode == M) return sia_launch_shape<W, M>(d_args, batch, img, sh, stream);
     SIA_CASE(1, 0) SIA_CASE(2, 0) SIA_CASE(4, 0)
     SIA_CASE(1, 1) SIA_CASE(2, 1) SIA_CASE(4, 1)
     SIA_CASE(1, 2) SIA_CASE(2, 2) SIA_CASE(4, 2)
 #undef SIA_CASE
-    return {false, hipSuccess};
+    return {{false, sh.waves, sh.mode, sh.cap, sh.lds}, hipSuccess};
 }
 
 size_t sia_rec_ws_floats(const svo_camera_settings& cam, int rec_cap) {

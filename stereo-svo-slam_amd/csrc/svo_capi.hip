@@ -234,7 +234,7 @@ extern "C" int svo_sparse_align(svo_handle* h, const svo_image* prev_pyr, const 
     const LaunchStatus sia_launch =
         launch_sia(d, 1, *cam, cur_pyr[0].width, cur_pyr[0].height, n, h->rec_cap, h->exact_pinv, h->stream);
     HIP_TRY(sia_launch.err);
-    if (!sia_launch.fits) return svo_set_error(SVO_ERR_CAPACITY, "svo_sparse_align: %d keypoints exceed the workspaces", n);
+    if (!sia_launch.shape.fits) return svo_set_error(SVO_ERR_CAPACITY, "svo_sparse_align: %d keypoints exceed the workspaces", n);
     HIP_TRY(hipGetLastError());
     return SVO_OK;
 }
@@ -292,7 +292,7 @@ extern "C" int svo_reproj_gn(svo_handle* h, svo_kp2d* kps2d, const svo_kp3d* kps
     if (rc) return rc;
     const LaunchStatus reproj_launch = launch_reproj(d, 1, n, h->stream);
     HIP_TRY(reproj_launch.err);
-    if (!reproj_launch.fits) return svo_set_error(SVO_ERR_CAPACITY, "svo_reproj_gn: %d keypoints do not fit LDS", n);
+    if (!reproj_launch.shape.fits) return svo_set_error(SVO_ERR_CAPACITY, "svo_reproj_gn: %d keypoints do not fit LDS", n);
     HIP_TRY(hipGetLastError());
     return SVO_OK;
 }
@@ -351,5 +351,16 @@ extern "C" int svo_depth_filter_update(svo_handle* h, const svo_kp2d* kps2d, svo
     if (rc) return rc;
     launch_filter(d, 1, n, h->stream);
     HIP_TRY(hipGetLastError());
+    return SVO_OK;
+}
+
+extern "C" int svo_pick_launch_shapes(const svo_camera_settings* cam, int width, int height, int batch, int n_bound,
+                                      int rec_cap, int exact, svo_launch_shape out[2]) {
+    if (!cam || !out || width < 1 || height < 1 || batch < 1)
+        return svo_set_error(SVO_ERR_INVALID, "svo_pick_launch_shapes: bad arguments");
+    const LaunchShape s = sia_pick_shape(batch, *cam, width, height, n_bound, rec_cap, exact);
+    const LaunchShape r = reproj_pick_shape(batch, n_bound);
+    out[0] = {SVO_KERNEL_SIA_GN, s.waves, s.mode, s.cap, s.fits ? 1 : 0};
+    out[1] = {SVO_KERNEL_REPROJ_GN, r.waves, r.mode, r.cap, r.fits ? 1 : 0};
     return SVO_OK;
 }

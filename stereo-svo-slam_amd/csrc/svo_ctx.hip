@@ -260,3 +260,27 @@ extern "C" int svo_get_totals(svo_ctx* c, svo_totals* out) {
     out->n_groups = (int)c->workers.size();
     return SVO_OK;
 }
+
+extern "C" int svo_ctx_get_launch_shapes(svo_ctx* c, svo_launch_shape* out, int max, int* n) {
+    if (!c || !n || max < 0 || (max > 0 && !out)) return svo_set_error(SVO_ERR_INVALID, "svo_ctx_get_launch_shapes: bad arguments");
+    const int rc = ctx_drain(c);
+    if (rc) return rc;
+    std::vector<svo_launch_shape> all;
+    for (auto& w : c->workers)
+        for (const svo_launch_shape& e : grp_launch_shapes(w->g.get())) {
+            auto it = std::find_if(all.begin(), all.end(), [&e](const svo_launch_shape& a) {
+                return a.kernel == e.kernel && a.waves == e.waves && a.mode == e.mode && a.cap == e.cap;
+            });
+            if (it == all.end()) all.push_back(e);
+            else it->launches += e.launches;
+        }
+    std::sort(all.begin(), all.end(), [](const svo_launch_shape& a, const svo_launch_shape& b) {
+        if (a.kernel != b.kernel) return a.kernel < b.kernel;
+        if (a.waves != b.waves) return a.waves < b.waves;
+        if (a.mode != b.mode) return a.mode < b.mode;
+        return a.cap < b.cap;
+    });
+    *n = (int)all.size();
+    for (int i = 0; i < std::min(max, *n); i++) out[i] = all[i];
+    return SVO_OK;
+}

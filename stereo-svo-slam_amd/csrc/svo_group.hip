@@ -266,6 +266,7 @@ struct svo_group {
     int tmpl_kf = 0, tmpl_cap = 0;
     size_t tmpl_block_bytes = 0, tmpl_valid_bytes = 0;
     svo_totals totals;
+    std::vector<svo_launch_shape> launch_shapes;   // distinct shapes of launch_sia / launch_reproj and their launches
     bool retire_kf_images = true;    // SVO_KEEP_KEYFRAME_IMAGES=1: keep every keyframe's image set (the reference's behaviour)
     int image_sets = 0;              // image sets allocated so far
     double host_ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // SVO_HOST_TIMING diagnostic: host phases of a step
@@ -635,6 +636,8 @@ svo_totals grp_totals(const svo_group* c) {
     return t;
 }
 
+const std::vector<svo_launch_shape>& grp_launch_shapes(const svo_group* c) { return c->launch_shapes; }
+
 namespace {
 
 // motion + 12-state filter + trajectory of the last frame (stereo_slam.cpp:250-270).
@@ -850,6 +853,16 @@ void pack_tracking_args(svo_group* c, const Step& st) {
     }
 }
 
+// one more launch of `kernel` (SVO_KERNEL_*) in shape `sh`
+void count_launch(svo_group* c, int kernel, const LaunchShape& sh) {
+    for (svo_launch_shape& e : c->launch_shapes)
+        if (e.kernel == kernel && e.waves == sh.waves && e.mode == sh.mode && e.cap == sh.cap) {
+            e.launches++;
+            return;
+        }
+    c->launch_shapes.push_back({kernel, sh.waves, sh.mode, sh.cap, 1});
+}
+
 // the arguments upload, the pyramids and (after the first frame) the tracked frame's kernels; the
 // inside-counters go back to the host for the keyframe decision
 int launch_tracking(svo_group* c, const Step& s) {
@@ -872,8 +885,9 @@ int launch_tracking(svo_group* c, const Step& s) {
     const LaunchStatus sia_launch =
         launch_sia(a.sia.d, M, c->cam, c->width, c->height, grid_n, c->rec_cap, c->exact_pinv, st);
     HIP_TRY(sia_launch.err);
-    if (!sia_launch.fits)
+    if (!sia_launch.shape.fits)
         return svo_set_error(SVO_ERR_CAPACITY, "sparse alignment: %d keypoints exceed the workspaces", grid_n);
+    count_launch(c, SVO_KERNEL_SIA_GN, sia_launch.shape);
     HIP_TRY(hipGetLastError());
     HIP_TRY(mark(c, 3));
     launch_klt(a.klt.d, M, grid_n, c->cam.window_size_opt_flow, st);
@@ -881,8 +895,9 @@ int launch_tracking(svo_group* c, const Step& s) {
     HIP_TRY(mark(c, 4));
     const LaunchStatus reproj_launch = launch_reproj(a.reproj.d, M, grid_n, st);
     HIP_TRY(reproj_launch.err);
-    if (!reproj_launch.fits)
+    if (!reproj_launch.shape.fits)
         return svo_set_error(SVO_ERR_CAPACITY, "reprojection GN: %d keypoints do not fit LDS", grid_n);
+    count_launch(c, SVO_KERNEL_REPROJ_GN, reproj_launch.shape);
     HIP_TRY(hipGetLastError());
     HIP_TRY(mark(c, 5));
     launch_ssd(a.ssd.d, M, grid_n, c->cam.window_size_depth_calculator, c->cam.search_y, st);

@@ -3,6 +3,7 @@
 
 #include <cstdint>
 #include <memory>
+#include <vector>
 
 #include "../../include/svo_hip.h"
 
@@ -17,6 +18,7 @@ int grp_new_images(svo_group* g, const uint8_t* const* left, const uint8_t* cons
 void grp_set_exact_pinv(svo_group* g, int on);
 void grp_enable_timing(svo_group* g, int on);
 svo_totals grp_totals(const svo_group* g);
+const std::vector<svo_launch_shape>& grp_launch_shapes(const svo_group* g);   // (svo_ctx_get_launch_shapes)
 
 // implemented by svo_ctx.hip: the group of ctx sequence `seq` and its index there, once every queue of the ctx
 // has drained, with the ctx's device current (the per-sequence getters of svo_group.hip start here)

@@ -71,14 +71,25 @@ struct SiaArgs {
     int exact_pinv;               // 1: reference-order normal equations + the reference's SVD pseudo-inverse (parity mode)
     PoseMats* mats_out;           // optional: rotation matrices of pose_out, for the kernels that project with it
 };
-// What launch_sia / launch_reproj report: whether the keypoints fit the kernel's workspaces (false: nothing
-// was launched), and the error of raising the kernel's LDS limit (the launch itself: hipGetLastError())
-struct LaunchStatus {
+// The workgroup shape of an alignment or reprojection-GN launch, a pure host decision (sia_pick_shape,
+// reproj_pick_shape): sia_gn_kernel<waves, mode> / reproj_gn_kernel<waves> (mode 0) with `cap` keypoint
+// slots per sequence and `lds` bytes of dynamic LDS. fits == false: the keypoints exceed the kernel's
+// workspaces, nothing is launched.
+struct LaunchShape {
     bool fits;
+    int waves, mode, cap;
+    size_t lds;
+};
+// What launch_sia / launch_reproj report: the shape they chose (shape.fits == false: nothing was launched),
+// and the error of raising the kernel's LDS limit (the launch itself: hipGetLastError())
+struct LaunchStatus {
+    LaunchShape shape;
     hipError_t err;
 };
 // n_bound: upper bound of the keypoint counts of the launch's sequences (chooses the workgroup
 // shape); rec_cap: SiaArgs::rec_cap of every block; exact: the value of SiaArgs::exact_pinv in every block (sizes the LDS staging).
+LaunchShape sia_pick_shape(int batch, const svo_camera_settings& cam, int width, int height, int n_bound, int rec_cap,
+                           int exact);
 LaunchStatus launch_sia(const SiaArgs* d_args, int batch, const svo_camera_settings& cam, int width,
                         int height, int n_bound, int rec_cap, int exact, hipStream_t stream);
 size_t sia_rec_ws_floats(const svo_camera_settings& cam, int rec_cap);   // size of SiaArgs::rec_ws
@@ -142,6 +153,7 @@ struct ReprojArgs {
     int exact_pinv;
     int* zero_out;                // or null: set to 0 (the inside counter filter_update_kernel adds to)
 };
+LaunchShape reproj_pick_shape(int batch, int n_bound);
 LaunchStatus launch_reproj(const ReprojArgs* d_args, int batch, int n_bound, hipStream_t stream);
 
 // project_keypoints (src/lib/transform_keypoints.cpp:11-48) as a stage of its own (the tracker

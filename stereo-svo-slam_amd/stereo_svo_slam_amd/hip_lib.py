@@ -28,6 +28,7 @@ SYMBOLS = (
     "svo_handle_set_fast_solver", "svo_ctx_set_fast_solver",
     "svo_device_malloc", "svo_device_free", "svo_copy_to_device", "svo_copy_to_host",
     "svo_copy_image_to_device", "svo_project_keypoints",
+    "svo_ctx_get_launch_shapes", "svo_pick_launch_shapes",
 )
 
 

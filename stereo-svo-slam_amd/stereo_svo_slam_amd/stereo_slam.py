@@ -48,6 +48,30 @@ class Totals(C.Structure):
                 ("launches", C.c_int64), ("n_groups", C.c_int32), ("image_sets", C.c_int32)]
 
 
+class LaunchShape(C.Structure):
+    """svo_launch_shape (include/svo_hip.h)."""
+    _fields_ = [("kernel", C.c_int32), ("waves", C.c_int32), ("mode", C.c_int32), ("cap", C.c_int32),
+                ("launches", C.c_int64)]
+
+
+KERNEL_NAMES = ("sia_gn_kernel", "reproj_gn_kernel")     # svo_launch_shape.kernel
+
+
+def _shape_key(e):
+    """(kernel name, waves, mode, cap) of a svo_launch_shape"""
+    return (KERNEL_NAMES[e.kernel], e.waves, e.mode, e.cap)
+
+
+def pick_launch_shapes(cfg, batch, n_bound, rec_cap=1 << 20, exact=True):
+    """svo_pick_launch_shapes: the (kernel, waves, mode, cap) the alignment and the reprojection GN
+    launch for `batch` sequences of at most n_bound keypoints of camera preset `cfg` (a host decision:
+    no GPU needed); None for a kernel whose workspaces the keypoints exceed."""
+    out = (LaunchShape * 2)()
+    _check(lib().svo_pick_launch_shapes(C.byref(CameraSettings.from_dict(cfg)), cfg["width"], cfg["height"],
+                                        batch, n_bound, rec_cap, int(exact), out))
+    return tuple(_shape_key(e) if e.launches else None for e in out)
+
+
 class Frame:
     """Frame / KeyFrame (src/include/stereo_slam_types.hpp:117-131) without images."""
 
@@ -167,6 +191,15 @@ class StereoSlamBatch:
         t = Totals()
         _check(lib().svo_get_totals(self._ctx, C.byref(t)))
         return t
+
+    def launch_shapes(self):
+        """svo_ctx_get_launch_shapes: {(kernel name, waves, mode, cap): launches} of the alignment
+        and reprojection-GN kernels, summed over the groups since creation."""
+        n = C.c_int(0)
+        _check(lib().svo_ctx_get_launch_shapes(self._ctx, None, 0, C.byref(n)))
+        out = (LaunchShape * max(n.value, 1))()
+        _check(lib().svo_ctx_get_launch_shapes(self._ctx, out, n.value, C.byref(n)))
+        return {_shape_key(e): e.launches for e in out[:n.value]}
 
     def pose(self, seq=0):
         p = np.zeros(6, np.float32)

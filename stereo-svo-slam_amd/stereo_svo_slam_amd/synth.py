@@ -300,10 +300,12 @@ def render_frames_gpu(scene, cfg, poses, right=False, noise_sigma=1.0, noise_see
     return out
 
 
-def make_sequence_gpu(config="euroc", n_frames=10, seed=0, device="cuda", noise_sigma=1.0, motion_scale=1.0):
+def make_sequence_gpu(config="euroc", n_frames=10, seed=0, device="cuda", noise_sigma=1.0, motion_scale=1.0,
+                      overrides=None):
     """make_sequence with the fused renderer (same scene and path, its own noise): returns
-    (cfg, lefts [n,H,W] uint8 CUDA tensor, rights, poses, timestamps)."""
-    cfg = dict(CONFIGS[config])
+    (cfg, lefts [n,H,W] uint8 CUDA tensor, rights, poses, timestamps). overrides: camera settings
+    that replace the preset's (e.g. a denser keypoint grid)."""
+    cfg = dict(CONFIGS[config], **(overrides or {}))
     scene = Scene(seed, device)
     poses = trajectory(n_frames, seed, motion_scale)
     seeds = 7919 * (seed + 1) + 2 * np.arange(n_frames)
@@ -313,10 +315,11 @@ def make_sequence_gpu(config="euroc", n_frames=10, seed=0, device="cuda", noise_
 
 
 def make_sequence(config="euroc", n_frames=10, seed=0, device="cpu", noise_sigma=1.0,
-                  motion_scale=1.0):
+                  motion_scale=1.0, overrides=None):
     """Returns (cfg, lefts, rights, poses, timestamps); lefts/rights are lists
-    of uint8 torch tensors on `device`; poses float32 [n,6] ground truth."""
-    cfg = dict(CONFIGS[config])
+    of uint8 torch tensors on `device`; poses float32 [n,6] ground truth. overrides: camera
+    settings that replace the preset's (e.g. a denser keypoint grid)."""
+    cfg = dict(CONFIGS[config], **(overrides or {}))
     scene = Scene(seed, device)
     poses = trajectory(n_frames, seed, motion_scale)
     lefts, rights = [], []

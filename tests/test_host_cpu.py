@@ -177,6 +177,75 @@ def test_cpp_facade_builds_and_fails_loudly_without_gpu(tmp_path):
         assert r.returncode == 3 and "no HIP device" in r.stdout, (r.returncode, r.stdout, r.stderr)
 
 
+def test_klt_bounds_predicates_at_the_int_and_float_corners(tmp_path):
+    """The KLT kernel's range tests (csrc/klt_bounds.hpp) built for the host: the window-corner test
+    rejects NaN, +-inf and coordinates beyond int like the reference's x86 (int)floorf, and is the
+    reference's test on every other value; the tile-rectangle test does not wrap next to INT_MAX."""
+    import shutil
+    import subprocess
+    csrc = os.path.join(ROOT, "stereo-svo-slam_amd", "csrc")
+    gxx = shutil.which("g++")
+    assert gxx
+    exe = str(tmp_path / "klt_bounds_check")
+    subprocess.check_call([gxx, "-std=c++17", "-O2", "-Wall", "-I" + csrc,
+                           os.path.join(ROOT, "tests", "cpp", "klt_bounds_check.cpp"), "-o", exe])
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0 and "klt bounds ok" in r.stdout, r.stdout[-3000:]
+
+
+# The workgroup shapes the GPU tests of tests/test_tracker_gpu.py claim to reach: (camera preset,
+# sequences per launch, largest keypoint set) -> (alignment, reprojection GN), each as (kernel, waves,
+# mode, cap). If a threshold of sia_pick_shape / reproj_pick_shape moves, this table fails first.
+SHAPE_TABLE = [
+    ("euroc", 1, 60, ("sia_gn_kernel", 1, 0, 64), ("reproj_gn_kernel", 1, 0, 64)),
+    ("euroc", 1, 128, ("sia_gn_kernel", 2, 0, 128), ("reproj_gn_kernel", 1, 0, 128)),
+    ("euroc", 1, 160, ("sia_gn_kernel", 4, 1, 256), ("reproj_gn_kernel", 4, 0, 256)),
+    ("euroc", 36, 60, ("sia_gn_kernel", 1, 2, 64), ("reproj_gn_kernel", 1, 0, 64)),
+    ("euroc", 36, 128, ("sia_gn_kernel", 1, 2, 128), ("reproj_gn_kernel", 1, 0, 128)),
+    ("euroc", 36, 160, ("sia_gn_kernel", 1, 2, 192), ("reproj_gn_kernel", 1, 0, 192)),
+    ("euroc", 36, 192, ("sia_gn_kernel", 1, 2, 192), ("reproj_gn_kernel", 1, 0, 192)),
+    ("euroc", 36, 250, ("sia_gn_kernel", 2, 2, 256), ("reproj_gn_kernel", 1, 0, 256)),
+    ("euroc", 36, 300, ("sia_gn_kernel", 2, 2, 384), ("reproj_gn_kernel", 4, 0, 512)),
+    ("euroc", 36, 385, ("sia_gn_kernel", 4, 2, 512), ("reproj_gn_kernel", 4, 0, 512)),
+    ("euroc", 31, 160, ("sia_gn_kernel", 4, 1, 256), ("reproj_gn_kernel", 4, 0, 256)),
+    ("hd", 1, 2000, ("sia_gn_kernel", 4, 2, 2048), ("reproj_gn_kernel", 4, 0, 2048)),
+    ("hd", 32, 2000, ("sia_gn_kernel", 4, 2, 2048), ("reproj_gn_kernel", 4, 0, 2048)),
+    ("tiny", 1, 50, ("sia_gn_kernel", 1, 0, 64), ("reproj_gn_kernel", 1, 0, 64)),
+    ("tiny", 34, 50, ("sia_gn_kernel", 1, 2, 64), ("reproj_gn_kernel", 1, 0, 64)),
+]
+
+
+@pytest.mark.parametrize("config,batch,n_bound,sia,reproj", SHAPE_TABLE)
+def test_launch_shape_table(config, batch, n_bound, sia, reproj):
+    from stereo_svo_slam_amd import synth
+    from stereo_svo_slam_amd.stereo_slam import pick_launch_shapes
+    cfg = dict(synth.CONFIGS[config])
+    assert pick_launch_shapes(cfg, batch, n_bound) == (sia, reproj)
+
+
+def test_launch_shape_edges():
+    """The shape changes exactly at its thresholds: 32 sequences per launch (MODE 2, one wave up to 192
+    keypoints, reprojection one wave up to 256), 64 / 128 / 192 / 384 keypoints; the fast solver stages
+    nothing, so it keeps MODE 0 where the reference-order mode needs MODE 1; a set beyond the
+    workspaces does not fit."""
+    from stereo_svo_slam_amd import synth
+    from stereo_svo_slam_amd.stereo_slam import pick_launch_shapes
+    e = dict(synth.CONFIGS["euroc"])
+    sia = lambda b, n, **kw: pick_launch_shapes(e, b, n, **kw)[0]
+    rp = lambda b, n: pick_launch_shapes(e, b, n)[1]
+    assert sia(31, 100) == ("sia_gn_kernel", 2, 0, 128) and sia(32, 100) == ("sia_gn_kernel", 1, 2, 128)
+    assert [sia(32, n)[1:] for n in (64, 65, 128, 129, 192, 193, 384, 385)] == \
+        [(1, 2, 64), (1, 2, 128), (1, 2, 128), (1, 2, 192), (1, 2, 192), (2, 2, 256), (2, 2, 384), (4, 2, 512)]
+    assert [sia(1, n)[1:] for n in (64, 65, 128, 129, 256, 257)] == \
+        [(1, 0, 64), (2, 0, 128), (2, 0, 128), (4, 1, 256), (4, 1, 256), (4, 1, 512)]
+    assert sia(1, 160, exact=False) == ("sia_gn_kernel", 4, 0, 256)
+    assert [rp(31, n)[1:] for n in (128, 129)] == [(1, 0, 128), (4, 0, 256)]
+    assert [rp(32, n)[1:] for n in (64, 65, 129, 193, 256, 257)] == \
+        [(1, 0, 64), (1, 0, 128), (1, 0, 192), (1, 0, 256), (1, 0, 256), (4, 0, 512)]
+    assert pick_launch_shapes(e, 36, 600, rec_cap=512)[0] is None        # 600 keypoints: cap 768 > rec_cap
+    assert pick_launch_shapes(e, 1, 5200)[1] is None                      # the reprojection's LDS copy: 120 KB
+
+
 def test_timed_steps_runs_finish_fn_inside_the_timed_region():
     """Queued steps (svo_submit_images) are drained by finish_fn before the clock stops: once after
     the warm-up steps and once after the timed ones."""

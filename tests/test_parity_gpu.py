@@ -153,6 +153,58 @@ def test_klt_small_image_fewer_levels(H):
     _klt_case(H, img, img2, pts, pts.copy(), 21)
 
 
+def _odd_points(w, h, win, normal):
+    """prev_pts / init pairs at the edges of the kernel's range tests: coordinates that saturate a float-to-int
+    conversion (+-1e10, +-inf, +-3e9), NaN, window corners just inside and just outside [-win, w) x [-win, h),
+    each paired with an ordinary point and with another odd one, mixed with ordinary points."""
+    half = (win - 1) * 0.5
+    odd = [1e10, -1e10, np.inf, -np.inf, np.nan, 3e9, -3e9]
+    edges_x = [c + half for c in (-win - 0.25, -win - 1e-3, -win, -win + 0.25, w - 1e-3, w - 0.25, w, w + 0.25)]
+    edges_y = [c + half for c in (-win - 0.25, -win, h - 1e-3, h, h + 0.25)]
+    prev, init = [], []
+    cx, cy = normal[0]
+    for v in odd:
+        for a, b in (((v, cy), (cx, cy)), ((cx, v), (cx, cy)), ((cx, cy), (v, cy)), ((cx, cy), (cx, v)),
+                     ((v, v), (v, v)), ((v, cy), (cx, v))):
+            prev.append(a); init.append(b)
+    for ex in edges_x:
+        prev.append((ex, cy)); init.append((ex, cy))
+        prev.append((cx, cy)); init.append((ex, cy))
+    for ey in edges_y:
+        prev.append((cx, ey)); init.append((cx, ey))
+        prev.append((cx, cy)); init.append((cx, ey))
+    for i, (x, y) in enumerate(normal):                   # ordinary points between the odd ones
+        prev.insert(2 * i, (x, y)); init.insert(2 * i, (x + 0.7, y - 0.4))
+    return np.array(prev, np.float32), np.array(init, np.float32)
+
+
+@pytest.mark.parametrize("win", [21, 31])
+def test_klt_coordinates_out_of_int_range(H, win):
+    """The stage entry with points whose coordinates are NaN, infinite, beyond int, or whose window corner
+    lies just inside / outside the tracked range: status, positions (bit patterns, NaN included) and errors
+    equal the oracle's. The stage path builds its templates without the cache and tests the range before
+    every window load, so none of these coordinates reaches a load; a NaN point is lost (status 0), as in
+    the reference, whose (int)floorf(NaN) is INT_MIN."""
+    sc = util.scenario("euroc", 3, 1, 1)
+    prev_img, cur_img = sc["L"][0], sc["L"][2]
+    h, w = prev_img.shape
+    prev_pts, init = _odd_points(w, h, win, [tuple(p) for p in sc["kps2d"][:40]])
+    pl, cl = O.build_lk_pyramid(prev_img, win), O.build_lk_pyramid(cur_img, win)
+    ref_pts, ref_st, ref_err = O.klt_track(pl, cl, prev_pts, init.copy(), win)
+    gp, gc = H.build_lk_pyramid(dev(prev_img), win), H.build_lk_pyramid(dev(cur_img), win)
+    cur_pts = dev(init.copy())
+    _, st, err = H.klt_track(gp, gc, dev(prev_pts), cur_pts, win)
+    st, err, pts = st.cpu().numpy(), err.cpu().numpy(), cur_pts.cpu().numpy()
+    assert np.array_equal(st, ref_st), np.nonzero(st != ref_st)
+    assert np.array_equal(pts.view(np.uint32), ref_pts.view(np.uint32)), \
+        np.nonzero(np.any(pts.view(np.uint32) != ref_pts.view(np.uint32), axis=1))
+    assert np.array_equal(err.view(np.uint32), ref_err.view(np.uint32))
+    # the odd points are lost, the ordinary ones between them mostly tracked
+    odd = ~np.all(np.isfinite(prev_pts) & np.isfinite(init) & (np.abs(prev_pts) < 1e9) & (np.abs(init) < 1e9), axis=1)
+    assert odd.sum() >= 40 and not ref_st[odd].any()
+    assert ref_st[:80:2].sum() >= 30
+
+
 # ------------------------------------------------------------------------ A
 def _sia_inputs(sc, frame):
     cfg = sc["cfg"]

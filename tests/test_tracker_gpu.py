@@ -225,37 +225,178 @@ def test_batched_launch_shapes_equal_single(monkeypatch):
     batch.close()
 
 
-def test_batched_c2_shape_in_groups_equals_the_oracle(monkeypatch):
-    """The launch shape the headline number runs (sia_gn_kernel<1,2>: one wave per sequence, records and
-    image taps from L2; several sequence groups on their own streams; frames used in place, queued
-    with svo_submit_images) at the C2 size, pinned to the oracle DIRECTLY: 66 `euroc` sequences in 3
-    groups, 5 frames; every sequence's pose, keypoints, flags, counters and trajectory equal the
-    oracle's bit for bit."""
-    n_seq, n_frames = 66, 5
-    monkeypatch.setenv("SVO_GROUPS", "3")
-    rendered = [synth.make_sequence_gpu("euroc", n_frames, 100 + s, motion_scale=1.5) for s in range(n_seq)]
-    cfg = rendered[0][0]
+def _oracle_frames(rendered, cfg):
+    """The oracle over every rendered sequence, frame by frame, in a thread pool (the oracle's ctypes calls
+    release the GIL): per sequence a list of (keyframe made, kps2d, kps3d, info, pose, stats) per frame."""
+    from concurrent.futures import ThreadPoolExecutor
+    cam = util.oracle_camera(cfg)
+    host = [(r[1].cpu().numpy() if torch.is_tensor(r[1]) else np.stack([x.numpy() for x in r[1]]),
+             r[2].cpu().numpy() if torch.is_tensor(r[2]) else np.stack([x.numpy() for x in r[2]]),
+             r[4]) for r in rendered]
+
+    def one(seq):
+        L, R, ts = seq
+        ref = O.Slam(cam)
+        out = []
+        for k in range(len(ts)):
+            made = ref.new_image(L[k], R[k], float(ts[k]))
+            ok2, ok3, oinfo = ref.keypoints()
+            out.append((made, ok2, ok3, oinfo, ref.pose().copy(), ref.stats()))
+        ref.close()
+        return out
+
+    with ThreadPoolExecutor(min(16, len(host))) as ex:
+        return list(ex.map(one, host))
+
+
+def _batch_against_oracle(rendered, cfg, oracle, n_groups, fast=False):
+    """All sequences in one ctx of n_groups groups, borrowed device frames queued with svo_submit_images, one
+    frame set at a time. Every sequence on every frame: keyframe decision, feature index lists, flags, counters,
+    score, and (reference-order mode) pose, keypoints and GN traces bit for bit; the fast solver: pose within
+    1e-4, keypoints within the _compare_frame bounds. Returns the ctx's launch shapes."""
+    n_seq, n_frames = len(rendered), len(rendered[0][4])
     batch = StereoSlamBatch(cfg, cfg["width"], cfg["height"], n_seq)
-    assert batch.groups() == 3
+    assert batch.groups() == n_groups
+    if fast:
+        batch.set_fast_solver(True)
     torch.cuda.synchronize()
     packs = [batch.pack_images([r[1][k] for r in rendered], [r[2][k] for r in rendered],
                                [float(r[4][k]) for r in rendered], borrow=True) for k in range(n_frames)]
-    for pk in packs:
-        batch.submit_packed(pk)
-    batch.wait()
-    cam = util.oracle_camera(cfg)
-    for i, r in enumerate(rendered):
-        ref = O.Slam(cam)
-        L, R = r[1].cpu().numpy(), r[2].cpu().numpy()
-        traj = []
-        for k in range(n_frames):
-            ref.new_image(L[k], R[k], float(r[4][k]))
-            traj.append(ref.pose().copy())
-        ok2, ok3, oinfo = ref.keypoints()
-        _compare_frame(f"euroc batch seq {i}", batch.get_frame(i), ok2, ok3, oinfo, ref.pose(), tol=0.0)
-        assert np.array_equal(batch.get_trajectory(i), np.array(traj)), i
-        assert _same_trace(batch.stats(i), ref.stats(), cfg), i
+    tol = 1e-4 if fast else 0.0
+    for k in range(n_frames):
+        batch.submit_packed(packs[k])
+        batch.wait()
+        for i in range(n_seq):
+            made, ok2, ok3, oinfo, pose, ost = oracle[i][k]
+            st = batch.stats(i)
+            assert st.is_keyframe == made, f"seq {i} frame {k}: keyframe decision"
+            _compare_frame(f"seq {i} frame {k}", batch.get_frame(i), ok2, ok3, oinfo, pose, tol)
+            if k > 0 and not fast:
+                assert _same_trace(st, ost, cfg), f"seq {i} frame {k}: GN trace differs from the oracle's"
+    for i in range(n_seq):
+        traj = np.array([f[4] for f in oracle[i]])
+        if fast:
+            assert np.max(np.abs(batch.get_trajectory(i) - traj)) < 1e-4, i
+        else:
+            assert np.array_equal(batch.get_trajectory(i), traj), i
+        assert batch.num_keyframes(i) == sum(f[0] for f in oracle[i]), i
+    shapes = batch.launch_shapes()
     batch.close()
+    return shapes
+
+
+def _sia_shapes(shapes):
+    return {k[1:]: v for k, v in shapes.items() if k[0] == "sia_gn_kernel"}
+
+
+def _reproj_shapes(shapes):
+    return {k[1:]: v for k, v in shapes.items() if k[0] == "reproj_gn_kernel"}
+
+
+# C2 in the shape of the headline run: 72 `euroc` sequences in 2 groups of 36, 10 frames at 8x the motion,
+# so that keyframes fire inside the run (the sets pass 128 keypoints) after frames whose sets all stay below
+C2_BATCH = dict(n_seq=72, groups=2, n_frames=10, motion_scale=8.0)
+
+
+@pytest.fixture(scope="module")
+def c2_batch():
+    """rendered sequences and the oracle's frames of the C2 batched run (shared by the exact and fast legs)"""
+    p = C2_BATCH
+    rendered = [synth.make_sequence_gpu("euroc", p["n_frames"], 100 + s, motion_scale=p["motion_scale"])
+                for s in range(p["n_seq"])]
+    cfg = rendered[0][0]
+    oracle = _oracle_frames(rendered, cfg)
+    per_group = p["n_seq"] // p["groups"]
+    for g in range(p["groups"]):          # a keyframe inside the run in every group
+        assert any(f[0] for o in oracle[g * per_group:(g + 1) * per_group] for f in o[1:]), g
+    return rendered, cfg, oracle
+
+
+def test_batched_c2_shape_in_groups_equals_the_oracle(monkeypatch, c2_batch):
+    """The launch shape the headline number runs, pinned to the oracle DIRECTLY: 72 `euroc` sequences in
+    2 groups of 36 (sia_gn_kernel<1,2>: one wave per sequence, records and image taps from L2, with cap 128
+    and 192, i.e. two and three staging chunks; reproj_gn_kernel<1> with cap 192: three staging steps),
+    several groups on their own streams, borrowed device frames queued with svo_submit_images. Every
+    sequence's pose, keypoints, flags, counters, GN traces and trajectory equal the oracle's bit for bit
+    on every frame."""
+    rendered, cfg, oracle = c2_batch
+    monkeypatch.setenv("SVO_GROUPS", str(C2_BATCH["groups"]))
+    shapes = _batch_against_oracle(rendered, cfg, oracle, C2_BATCH["groups"])
+    sia, rp = _sia_shapes(shapes), _reproj_shapes(shapes)
+    print("C2 batched launch shapes:", shapes)
+    assert set(sia) <= {(1, 2, 64), (1, 2, 128), (1, 2, 192)}, sia
+    assert (1, 2, 128) in sia and (1, 2, 192) in sia, sia
+    assert all(w == 1 for w, _, _ in rp) and any(cap >= 192 for _, _, cap in rp), rp
+
+
+def test_batched_c2_fast_solver_stays_with_the_oracle(monkeypatch):
+    """The batched C2 shape with the fast solver (tree sums whose order depends on the wave count): 72
+    `euroc` sequences in 2 groups at the motion of the earlier form of the C2 test, 6 frames; every pose
+    within 1e-4 m / rad of the oracle's, feature index lists equal, on every frame. (The 8x motion of the
+    reference-order test above is beyond the fast solver's bound in any shape: one of its sequences ends
+    3e-4 away from the oracle in a ctx of its own too. That run pins the reference-order mode only.)"""
+    monkeypatch.setenv("SVO_GROUPS", "2")
+    rendered = [synth.make_sequence_gpu("euroc", 6, 100 + s, motion_scale=1.5) for s in range(72)]
+    cfg = rendered[0][0]
+    shapes = _batch_against_oracle(rendered, cfg, _oracle_frames(rendered, cfg), 2, fast=True)
+    sia = _sia_shapes(shapes)
+    print("C2 batched launch shapes, fast solver:", shapes)
+    assert sia and all(w == 1 and m == 2 for w, m, _ in sia) and (1, 2, 128) in sia, sia
+
+
+def test_batched_two_wave_alignment_equals_the_oracle(monkeypatch):
+    """sia_gn_kernel<2,2> (a batched launch whose largest set has 193-384 keypoints) and reproj_gn_kernel<4>
+    in a batched launch: 36 `euroc` sequences with a 32 x 32 pixel keypoint grid (345 cells), 3 frames,
+    one group; bit for bit against the oracle on every frame."""
+    monkeypatch.setenv("SVO_GROUPS", "1")
+    rendered = [synth.make_sequence_gpu("euroc", 3, 300 + s, motion_scale=1.5,
+                                        overrides=dict(grid_width=32, grid_height=32)) for s in range(36)]
+    cfg = rendered[0][0]
+    shapes = _batch_against_oracle(rendered, cfg, _oracle_frames(rendered, cfg), 1)
+    print("C2 dense-grid launch shapes:", shapes)
+    sia, rp = _sia_shapes(shapes), _reproj_shapes(shapes)
+    assert sia and all(w == 2 and m == 2 for w, m, _ in sia), sia
+    assert rp and all(w == 4 for w, _, _ in rp), rp
+
+
+def test_batched_c3_equals_the_oracle(monkeypatch):
+    """C3 (1920x1080, ~2000 keypoints) in a batched launch: 32 `hd` sequences in one group, 2 frames;
+    sia_gn_kernel<4,2> and reproj_gn_kernel<4> at C3's caps (1536-2048 keypoints), bit for bit against the oracle."""
+    monkeypatch.setenv("SVO_GROUPS", "1")
+    rendered = [synth.make_sequence_gpu("hd", 2, 400 + s) for s in range(32)]
+    cfg = rendered[0][0]
+    shapes = _batch_against_oracle(rendered, cfg, _oracle_frames(rendered, cfg), 1)
+    print("C3 batched launch shapes:", shapes)
+    sia, rp = _sia_shapes(shapes), _reproj_shapes(shapes)
+    assert sia and all(w == 4 and m == 2 and cap >= 1536 for w, m, cap in sia), sia
+    assert rp and all(w == 4 and cap >= 1536 for w, _, cap in rp), rp
+
+
+def test_shape_switch_when_sequences_finish(monkeypatch):
+    """34 `tiny` sequences of unequal length in one group: while 34 are active the alignment runs
+    sia_gn_kernel<1,2>; once 30 have finished, the 4 that remain run sia_gn_kernel<1,0>. Every sequence
+    ends with the oracle's pose, keypoints, flags, counters, trajectory and GN traces."""
+    from stereo_svo_slam_amd import multi_seq
+    monkeypatch.setenv("SVO_GROUPS", "1")
+    lengths = [3] * 30 + [8] * 4
+    seqs = [synth.make_sequence("tiny", n, 500 + s, device="cpu", motion_scale=2.0) for s, n in enumerate(lengths)]
+    cfg = seqs[0][0]
+    seqs = [(c, L, R, p, np.arange(len(L), dtype=np.float32) / 20.0) for c, L, R, p, _ in seqs]   # play_unequal's times
+    oracle = _oracle_frames(seqs, cfg)
+    batch = StereoSlamBatch(cfg, cfg["width"], cfg["height"], len(lengths))
+    assert batch.groups() == 1
+    done = multi_seq.play_unequal(batch, lambda s, k: (seqs[s][1][k].numpy(), seqs[s][2][k].numpy()), lengths)
+    assert done == sum(lengths)
+    for s, n in enumerate(lengths):
+        made, ok2, ok3, oinfo, pose, ost = oracle[s][-1]
+        _compare_frame(f"seq {s}", batch.get_frame(s), ok2, ok3, oinfo, pose, tol=0.0)
+        assert _same_trace(batch.stats(s), ost, cfg), s
+        assert np.array_equal(batch.get_trajectory(s), np.array([f[4] for f in oracle[s]])), s
+        assert batch.num_keyframes(s) == sum(f[0] for f in oracle[s]), s
+    sia = _sia_shapes(batch.launch_shapes())
+    batch.close()
+    print("unequal lengths launch shapes:", sia)
+    assert sia.get((1, 2, 64), 0) == 2 and sia.get((1, 0, 64), 0) == 5, sia
 
 
 def test_groups_and_pipelined_submit_equal_lockstep(monkeypatch):
