@@ -243,6 +243,14 @@ int svo_ctx_get_launch_shapes(svo_ctx *ctx, svo_launch_shape *out, int max, int 
 int svo_pick_launch_shapes(const svo_camera_settings *cam, int width, int height, int batch, int n_bound,
                            int rec_cap, int exact, svo_launch_shape out[2]);
 
+/* ---- diagnostics (tests, not the tracking path) ----
+ * n pseudo-inverses of 6x6 float systems H_dev[n][36] (row major, device) through the Jacobi SVD of
+ * the Gauss-Newton solves: impl 0 = the sequential reference (one system per lane), 1 = the
+ * lane-parallel solver of the kernels (one system per wavefront). out_dev[n][114] receives, per
+ * system, Hinv[36], W[6], Vt[36] and U^T[36] (the scaled rows of At); sweeps_dev[n] the Jacobi
+ * sweeps run (1..30). Both impls give the same bits. */
+int svo_pinv6_check(svo_handle *h, const float *H_dev, int n, float *out_dev, int32_t *sweeps_dev, int impl);
+
 #ifdef __cplusplus
 }
 #endif

@@ -621,14 +621,7 @@ struct Sia {
             for (int q = 0; q < 6; q++) grad[q] = LDSCF(sums)[WAVES * 32 + q];
             __syncthreads();                             // (sums is written again by the next call)
         } else {
-#ifdef SVO_SVD_ONE_LANE
-        // experiment: the solve under an exec mask of one lane (less switching power), result broadcast
-        if (lane == 0) gn_solve6(H, b, delta, exact);
-#pragma unroll
-        for (int q = 0; q < 6; q++) delta[q] = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(delta[q])));
-#else
         gn_solve6(H, b, delta, exact);
-#endif
         exponential_map(delta, pg);
         mat33f_vec(pm.R, pg, grad);                  // pose_estimator.cpp:495-497
         mat33f_vec(pm.R, pg + 3, grad + 3);

@@ -364,3 +364,45 @@ extern "C" int svo_pick_launch_shapes(const svo_camera_settings* cam, int width,
     out[1] = {SVO_KERNEL_REPROJ_GN, r.waves, r.mode, r.cap, r.fits ? 1 : 0};
     return SVO_OK;
 }
+
+// ------------------------------------------------------------------ diagnostics
+// svo_pinv6_check: IMPL 0 runs jacobi_svd6_reg on one system per lane, IMPL 1 jacobi_svd6_lanes on one
+// system per wavefront (H loaded alike by all 64 lanes: the wave-uniform input of the kernels' solves).
+template <int IMPL>
+__global__ void __launch_bounds__(64) pinv6_check_kernel(const float* H, int n, float* out, int32_t* sweeps) {
+    const long sys = IMPL == 0 ? (long)blockIdx.x * 64 + threadIdx.x : (long)blockIdx.x;
+    if (sys >= n) return;   // IMPL 1: never taken (one workgroup per system), the wave stays converged
+    const float* h = H + sys * 36;
+    float At[6][6], W[6], Vt[6][6], Hinv[36];
+#pragma unroll
+    for (int i = 0; i < 6; i++)
+#pragma unroll
+        for (int j = 0; j < 6; j++) At[i][j] = h[j * 6 + i];
+    const int sw = IMPL == 0 ? jacobi_svd6_reg(At, W, Vt) : jacobi_svd6_lanes(At, W, Vt);
+    svd6_pinv(At, W, Vt, Hinv);
+    if (IMPL == 1 && threadIdx.x != 0) return;
+    float* o = out + sys * 114;
+#pragma unroll
+    for (int i = 0; i < 36; i++) o[i] = Hinv[i];
+#pragma unroll
+    for (int i = 0; i < 6; i++) o[36 + i] = W[i];
+#pragma unroll
+    for (int i = 0; i < 6; i++)
+#pragma unroll
+        for (int k = 0; k < 6; k++) { o[42 + i * 6 + k] = Vt[i][k]; o[78 + i * 6 + k] = At[i][k]; }
+    sweeps[sys] = sw;
+}
+
+extern "C" int svo_pinv6_check(svo_handle* h, const float* H_dev, int n, float* out_dev, int32_t* sweeps_dev,
+                               int impl) {
+    CHECK_H(h);
+    if (n < 0 || (n > 0 && (!H_dev || !out_dev || !sweeps_dev)) || (impl != 0 && impl != 1))
+        return svo_set_error(SVO_ERR_INVALID, "svo_pinv6_check: bad arguments");
+    if (n == 0) return SVO_OK;
+    if (impl == 0)
+        pinv6_check_kernel<0><<<(n + 63) / 64, 64, 0, h->stream>>>(H_dev, n, out_dev, sweeps_dev);
+    else
+        pinv6_check_kernel<1><<<n, 64, 0, h->stream>>>(H_dev, n, out_dev, sweeps_dev);
+    HIP_TRY(hipGetLastError());
+    return SVO_OK;
+}

@@ -373,13 +373,53 @@ __host__ __device__ inline void jacobi_svd(float (&At)[N][M], float (&W)[N], flo
     }
 }
 
+// Tail of the 6x6 Jacobi SVDs below, after the sweeps: singular values from the rotated rows,
+// selection sort (largest first), rows of At scaled to unit length.
+__device__ inline void svd6_finish(float (&At)[6][6], float (&W)[6], float (&Vt)[6][6]) {
+    double Wd[6];
+#pragma unroll
+    for (int i = 0; i < 6; i++) {
+        double sd = 0;
+#pragma unroll
+        for (int k = 0; k < 6; k++) { const float t = At[i][k]; sd = __builtin_fma((double)t, (double)t, sd); }
+        Wd[i] = sqrt(sd);
+    }
+    // selection sort, largest first: row i <-> the first maximum of rows i..5
+#pragma unroll
+    for (int i = 0; i < 5; i++) {
+        int j = i;
+        double wj = Wd[i];
+#pragma unroll
+        for (int k = i + 1; k < 6; k++)
+            if (wj < Wd[k]) { j = k; wj = Wd[k]; }
+#pragma unroll
+        for (int k = i + 1; k < 6; k++)
+            if (j == k) {
+                const double tw = Wd[i]; Wd[i] = Wd[k]; Wd[k] = tw;
+#pragma unroll
+                for (int q = 0; q < 6; q++) { const float t = At[i][q]; At[i][q] = At[k][q]; At[k][q] = t; }
+#pragma unroll
+                for (int q = 0; q < 6; q++) { const float t = Vt[i][q]; Vt[i][q] = Vt[k][q]; Vt[k][q] = t; }
+            }
+    }
+#pragma unroll
+    for (int i = 0; i < 6; i++) {
+        W[i] = (float)Wd[i];
+        const double sd = Wd[i];
+        const float s = (float)(sd > (double)FLT_MIN ? 1 / sd : 0.);
+#pragma unroll
+        for (int k = 0; k < 6; k++) At[i][k] *= s;
+    }
+}
+
 // The same one-sided Jacobi SVD for the 6x6 systems of the Gauss-Newton kernels, written so
 // that every array index is a compile-time constant (all loops over rows / columns / pairs are
 // unrolled, the selection sort swaps under predicates): At, Vt and W live in registers instead of
 // scratch memory. Same operations in the same order as jacobi_svd<6,6>: same bits.
 // (The product of two floats is exact in double, so fma(x, y, acc) == acc + x * y bit for bit: the
 // sums of squares and the dot products below use one instruction per term.)
-__device__ inline void jacobi_svd6_reg(float (&At)[6][6], float (&W)[6], float (&Vt)[6][6]) {
+// Sequential reference of jacobi_svd6_lanes (svo_pinv6_check only); returns the sweeps run.
+__device__ inline int jacobi_svd6_reg(float (&At)[6][6], float (&W)[6], float (&Vt)[6][6]) {
     const float eps = FLT_EPSILON * 2;
     double Wd[6];
 #pragma unroll
@@ -391,6 +431,7 @@ __device__ inline void jacobi_svd6_reg(float (&At)[6][6], float (&W)[6], float (
 #pragma unroll
         for (int k = 0; k < 6; k++) Vt[i][k] = (i == k) ? 1.f : 0.f;
     }
+    int sweeps = 30;
     for (int iter = 0; iter < 30; iter++) {
         bool changed = false;
 #pragma unroll
@@ -435,52 +476,151 @@ __device__ inline void jacobi_svd6_reg(float (&At)[6][6], float (&W)[6], float (
                     }
                 }
             }
-        if (!changed) break;
+        if (!changed) { sweeps = iter + 1; break; }
     }
-#pragma unroll
-    for (int i = 0; i < 6; i++) {
-        double sd = 0;
-#pragma unroll
-        for (int k = 0; k < 6; k++) { const float t = At[i][k]; sd = __builtin_fma((double)t, (double)t, sd); }
-        Wd[i] = sqrt(sd);
-    }
-    // selection sort, largest first: row i <-> the first maximum of rows i..5
-#pragma unroll
-    for (int i = 0; i < 5; i++) {
-        int j = i;
-        double wj = Wd[i];
-#pragma unroll
-        for (int k = i + 1; k < 6; k++)
-            if (wj < Wd[k]) { j = k; wj = Wd[k]; }
-#pragma unroll
-        for (int k = i + 1; k < 6; k++)
-            if (j == k) {
-                const double tw = Wd[i]; Wd[i] = Wd[k]; Wd[k] = tw;
-#pragma unroll
-                for (int q = 0; q < 6; q++) { const float t = At[i][q]; At[i][q] = At[k][q]; At[k][q] = t; }
-#pragma unroll
-                for (int q = 0; q < 6; q++) { const float t = Vt[i][q]; Vt[i][q] = Vt[k][q]; Vt[k][q] = t; }
-            }
-    }
-#pragma unroll
-    for (int i = 0; i < 6; i++) {
-        W[i] = (float)Wd[i];
-        const double sd = Wd[i];
-        const float s = (float)(sd > (double)FLT_MIN ? 1 / sd : 0.);
-#pragma unroll
-        for (int k = 0; k < 6; k++) At[i][k] *= s;
-    }
+    svd6_finish(At, W, Vt);
+    return sweeps;
 }
 
-// Matx66f::inv(DECOMP_SVD): zeros when sigma_max < FLT_EPSILON or
-// sigma_min / sigma_max == 0, else V diag(1/w) U^T with the SVBkSb threshold.
-__device__ inline void inv_svd6(const float H[36], float Hinv[36]) {
-    float At[6][6], Vt[6][6], W[6];
+// Schedule of jacobi_svd6_lanes, generated by tools/svd_schedule.py (and checked against it by
+// tests/test_svd_schedule_cpu.py). Position q of the 6-round body pairs row r with row
+// (kSvdPartner[q] >> 4r) & 7 (itself: idle this round); bit r of kSvdLag[q] marks a pair of the
+// previous sweep (t - 1 in body iteration t), the other pairs belong to sweep t.
+// SVD-SCHEDULE-BEGIN
+constexpr uint32_t kSvdPartner[6] = {0x76234501u, 0x76345012u, 0x76450123u, 0x76501234u, 0x76012345u, 0x76123450u};
+constexpr uint32_t kSvdLag[6] = {0x3Cu, 0x28u, 0x30u, 0x00u, 0x00u, 0x00u};
+// SVD-SCHEDULE-END
+
+// jacobi_svd6_reg with the rotations of disjoint row pairs in parallel lanes: the same bits out
+// for every input, fewer dependent steps. Lane r (r = lane & 7 < 6) owns row r of At and Vt and its
+// Wd[r]; lanes with r = 6, 7 idle.
+//
+// Why the bits are the same. A rotation of rows (i, j) reads and writes only rows i and j of At and
+// Vt, Wd[i] and Wd[j], and sets the `changed` flag. Two rotations on disjoint row pairs therefore
+// commute exactly, and any order of the pairs that keeps, for every row, the reference's order of
+// the pairs touching it (a topological order of the row-dependency graph of the cyclic sweep
+// (0,1) (0,2) .. (0,5) (1,2) .. (4,5), sweep after sweep) gives every pair the same operands as the
+// sequential loop. kSvdPartner / kSvdLag are that order scheduled as early as possible: sweep t
+// runs in positions 1-6 of body iteration t and its last three pairs, (2,5) (3,4) / (3,5) / (4,5),
+// in positions 1-3 of iteration t + 1, beside the first pairs of sweep t + 1. 6 rounds per sweep
+// instead of 15.
+// Within a pair both lanes compute p, the skip test, beta, gamma, c and s with the reference's
+// operations on the same operands (a = Wd of the low row, b = Wd of the high row; fma(x, y, acc)
+// with an exact product does not depend on the order of x and y), so both decide and round alike.
+// The low lane writes c*own + s*partner (the reference's t0), the high lane c*own + (-s)*partner,
+// which is the reference's t1 = -s*Ai + c*Aj with the addition commuted (-ffp-contract=off: no fma).
+//
+// Stopping. Iteration 0 masks its sweep -1 pairs, which leaves sweep 0 scheduled as early as
+// possible. After position 3 of iteration t >= 1 sweep t - 1 is complete; the reference stops after
+// it if it rotated nothing, and so does this loop. The pairs of sweep t that already ran by then,
+// (0,1) (0,2) (0,3) (1,2), include every earlier pair of sweep t on their rows, and they were no-ops:
+// sweep t - 1 left every row as it found it, so each of them saw the operands its sweep t - 1 twin
+// saw (inductively, in dependency order, the pairs before it having skipped as well) and skipped alike.
+// The reference runs at most 30 sweeps (iter < 30): pairs of sweep 30 are masked and the loop stops
+// after position 3 of iteration 30. Returns the sweep count of the reference loop.
+//
+// Precondition: the wave is converged (all 64 lanes active) and At holds the same values in every
+// lane; At, W and Vt come back wave-uniform (v_readlane), through the same svd6_finish.
+__device__ inline int jacobi_svd6_lanes(float (&At)[6][6], float (&W)[6], float (&Vt)[6][6]) {
+    const float eps = FLT_EPSILON * 2;
+    const int lane = (int)__lane_id();
+    const int r = lane & 7;
+    float a[6], v[6];
+#pragma unroll
+    for (int k = 0; k < 6; k++) {
+        float x = 0.f;
+#pragma unroll
+        for (int i = 0; i < 6; i++) x = (r == i) ? At[i][k] : x;
+        a[k] = x;
+        v[k] = (r == k) ? 1.f : 0.f;
+    }
+    double wd = 0;
+#pragma unroll
+    for (int k = 0; k < 6; k++) wd = __builtin_fma((double)a[k], (double)a[k], wd);
+
+    // per position: the partner lane's byte address for ds_bpermute, this lane's role, its sweep lag
+    int addr[6];
+    bool pair[6], low[6], lag[6];
+#pragma unroll
+    for (int q = 0; q < 6; q++) {
+        const int pr = (int)((kSvdPartner[q] >> (4 * r)) & 7u);
+        addr[q] = ((lane & ~7) | pr) << 2;
+        pair[q] = pr != r;
+        low[q] = r < pr;
+        lag[q] = ((kSvdLag[q] >> r) & 1u) != 0;
+    }
+
+    bool chg_prev = false, chg_cur = false;   // rotations of sweep t - 1 / sweep t seen by this lane
+    auto round = [&](int q, int t) {
+        // the partner's row: 14 dwords fetched in one batch
+        float pa[6], pv[6];
+#pragma unroll
+        for (int k = 0; k < 6; k++) pa[k] = __int_as_float(__builtin_amdgcn_ds_bpermute(addr[q], __float_as_int(a[k])));
+#pragma unroll
+        for (int k = 0; k < 6; k++) pv[k] = __int_as_float(__builtin_amdgcn_ds_bpermute(addr[q], __float_as_int(v[k])));
+        const int wlo = __builtin_amdgcn_ds_bpermute(addr[q], (int)__double2loint(wd));
+        const int whi = __builtin_amdgcn_ds_bpermute(addr[q], (int)__double2hiint(wd));
+        const double wp = __hiloint2double(whi, wlo);
+        const int sweep = t - (lag[q] ? 1 : 0);
+        const bool live = pair[q] && sweep >= 0 && sweep < 30;
+        double wa = low[q] ? wd : wp, p = 0, wb = low[q] ? wp : wd;
+#pragma unroll
+        for (int k = 0; k < 6; k++) p = __builtin_fma((double)a[k], (double)pa[k], p);
+        const double pp = p * p, ee = ((double)eps * (double)eps) * (wa * wb);
+        bool rotate = pp > ee * (1 + 1e-9);
+        if (!rotate && !(pp < ee * (1 - 1e-9))) rotate = !(fabs(p) <= eps * sqrt(wa * wb));
+        rotate = rotate && live;
+        if (rotate) {
+            p *= 2;
+            const double beta = wa - wb, gamma = svo_hypot(p, beta);
+            const bool neg = beta < 0;
+            const double num = neg ? (gamma - beta) * 0.5 : (gamma + beta);
+            const double den = neg ? gamma : gamma * 2;
+            const float r1 = (float)sqrt(num / den);
+            const float r2 = (float)(p / (gamma * r1 * 2));
+            const float c = neg ? r2 : r1, s = neg ? r1 : r2;
+            const float se = low[q] ? s : -s;
+            double w = 0;
+#pragma unroll
+            for (int k = 0; k < 6; k++) {
+                const float t0 = c * a[k] + se * pa[k];
+                a[k] = t0;
+                w = __builtin_fma((double)t0, (double)t0, w);
+            }
+            wd = w;
+#pragma unroll
+            for (int k = 0; k < 6; k++) v[k] = c * v[k] + se * pv[k];
+        }
+        if (lag[q]) chg_prev = chg_prev || rotate;
+        else chg_cur = chg_cur || rotate;
+    };
+
+    int t = 0;
+    for (;; t++) {
+        round(0, t);
+        round(1, t);
+        round(2, t);
+        if (t == 30 || (t >= 1 && __builtin_amdgcn_ballot_w64(chg_prev) == 0)) break;
+        round(3, t);
+        round(4, t);
+        round(5, t);
+        chg_prev = chg_cur;
+        chg_cur = false;
+    }
 #pragma unroll
     for (int i = 0; i < 6; i++)
 #pragma unroll
-        for (int j = 0; j < 6; j++) At[i][j] = H[j * 6 + i];
-    jacobi_svd6_reg(At, W, Vt);
+        for (int k = 0; k < 6; k++) {
+            At[i][k] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(a[k]), i));
+            Vt[i][k] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v[k]), i));
+        }
+    svd6_finish(At, W, Vt);
+    return t;
+}
+
+// pinv(H) from its SVD: V diag(1/w) U^T with the SVBkSb threshold; zeros unless ok.
+__device__ inline void svd6_pinv(const float (&At)[6][6], const float (&W)[6], const float (&Vt)[6][6],
+                                  float Hinv[36]) {
 #pragma unroll
     for (int i = 0; i < 36; i++) Hinv[i] = 0;
     double threshold = 0;
@@ -508,6 +648,19 @@ __device__ inline void inv_svd6(const float H[36], float Hinv[36]) {
 #pragma unroll
         for (int i = 0; i < 36; i++) Hinv[i] = 0;
     }
+}
+
+// Matx66f::inv(DECOMP_SVD): zeros when sigma_max < FLT_EPSILON or
+// sigma_min / sigma_max == 0, else V diag(1/w) U^T with the SVBkSb threshold.
+// Called by a converged wave with H wave-uniform (jacobi_svd6_lanes).
+__device__ inline void inv_svd6(const float H[36], float Hinv[36]) {
+    float At[6][6], Vt[6][6], W[6];
+#pragma unroll
+    for (int i = 0; i < 6; i++)
+#pragma unroll
+        for (int j = 0; j < 6; j++) At[i][j] = H[j * 6 + i];
+    jacobi_svd6_lanes(At, W, Vt);
+    svd6_pinv(At, W, Vt, Hinv);
 }
 
 // delta = pinv(H) b for the Gauss-Newton steps (pose_estimator.cpp:405,484;

@@ -28,7 +28,7 @@ SYMBOLS = (
     "svo_handle_set_fast_solver", "svo_ctx_set_fast_solver",
     "svo_device_malloc", "svo_device_free", "svo_copy_to_device", "svo_copy_to_host",
     "svo_copy_image_to_device", "svo_project_keypoints",
-    "svo_ctx_get_launch_shapes", "svo_pick_launch_shapes",
+    "svo_ctx_get_launch_shapes", "svo_pick_launch_shapes", "svo_pinv6_check",
 )
 
 
@@ -202,6 +202,16 @@ class Handle:
         return cur_pts, status, err
 
     # -- B1 + B3 ----------------------------------------------------------
+    def pinv6_check(self, H, impl):
+        """Diagnostic: pinv of n 6x6 systems H[n, 36] (float32, device) through the solvers' Jacobi
+        SVD, impl 0 = sequential reference, 1 = lane-parallel. Returns (out[n, 114] float32 =
+        Hinv, W, Vt, U^T per system, sweeps[n] int32)."""
+        n = H.shape[0]
+        out = torch.empty((n, 114), dtype=torch.float32, device=H.device)
+        sweeps = torch.empty(n, dtype=torch.int32, device=H.device)
+        _check(lib().svo_pinv6_check(self._h, _ptr(H), n, _ptr(out), _ptr(sweeps), int(impl)))
+        return out, sweeps
+
     def reproj_gn(self, kps2d, kps3d, flags, cam, pose_in, tracked=None, err=None):
         dev = kps2d.device
         n = kps2d.shape[0]
