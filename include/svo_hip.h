@@ -250,6 +250,12 @@ int svo_pick_launch_shapes(const svo_camera_settings *cam, int width, int height
  * system, Hinv[36], W[6], Vt[36] and U^T[36] (the scaled rows of At); sweeps_dev[n] the Jacobi
  * sweeps run (1..30). Both impls give the same bits. */
 int svo_pinv6_check(svo_handle *h, const float *H_dev, int n, float *out_dev, int32_t *sweeps_dev, int impl);
+/* Diagnostic: the exact Gauss-Newton solve delta = pinv(H) b of n systems (H_dev[n][36],
+ * b_dev[n][6]), one wavefront each: impl 0 = the round-4 solve (wave-uniform finish, pseudo-inverse
+ * and step), 1 = the lane-resident solve of the kernels. out_dev[n][120] receives Hinv[36], W[6],
+ * Vt[36], U^T[36] and delta[6]; sweeps_dev[n] the Jacobi sweeps run. Both impls give the same bits. */
+int svo_solve6_check(svo_handle *h, const float *H_dev, const float *b_dev, int n, float *out_dev,
+                     int32_t *sweeps_dev, int impl);
 
 #ifdef __cplusplus
 }

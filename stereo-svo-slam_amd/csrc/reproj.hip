@@ -148,8 +148,11 @@ __device__ void reproj_gradient(const ReprojArgs& a, const RpKps& kp, int n, con
     rp_sync<WAVES>();
     if (tid < 27) ((SVO_LDS(float)*)sh.sums)[tid] = acc;
     rp_sync<WAVES>();
-    float H[36], e[6], twist[6];
-    {
+    float twist[6];
+    if (a.exact_pinv != 0) {
+        gn_solve6_sums((const SVO_LDS(float)*)sh.sums, twist);   // lane-resident, rows read from the sums
+    } else {
+        float H[36], e[6];
         int idx = 0;
 #pragma unroll
         for (int r = 0; r < 6; r++)
@@ -160,8 +163,8 @@ __device__ void reproj_gradient(const ReprojArgs& a, const RpKps& kp, int n, con
             }
 #pragma unroll
         for (int r = 0; r < 6; r++) e[r] = ((const SVO_LDS(float)*)sh.sums)[21 + r];
+        gn_solve6(H, e, twist, false);
     }
-    gn_solve6(H, e, twist, a.exact_pinv != 0);
     exponential_map(twist, grad);                  // not rotated (pose_refinement.cpp:398-411)
 }
 

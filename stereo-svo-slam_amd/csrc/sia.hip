@@ -566,7 +566,6 @@ struct Sia {
 
         SIA_T(g1);
         float* sums = reinterpret_cast<float*>(dyn + lay.sums);        // [WAVES][32]
-        float H[36], b[6];
         if (!exact) {
 #pragma unroll
             for (int q = 0; q < 27; q++) acc[q] = wave_sum_dpp(acc[q]);
@@ -589,25 +588,40 @@ struct Sia {
             sia_sync<WAVES>();
             if (wave == 0 && lane < 27) LDSF(sums)[lane] = eacc;
             sia_sync<WAVES>();
-#pragma unroll
-            for (int q = 0; q < 27; q++) acc[q] = LDSCF(sums)[q];
-        }
-        {
-            int q = 0;
-#pragma unroll
-            for (int r = 0; r < 6; r++)
-#pragma unroll
-                for (int c = r; c < 6; c++) { H[r * 6 + c] = acc[q]; H[c * 6 + r] = acc[q]; q++; }
-#pragma unroll
-            for (int r = 0; r < 6; r++) b[r] = acc[21 + r];
         }
         SIA_T(g2);
         float delta[6], pg[6];
+        // exact: lane-resident solve straight from the sums (they stay in LDS until the next call);
+        // fast: LDL^T on the wave-uniform H
+        auto solve = [&]() {
+            if (exact) {
+                const int r = lane & 7;
+                float ra[6], rv[6];
+#pragma unroll
+                for (int k = 0; k < 6; k++) ra[k] = r < 6 ? LDSCF(sums)[h6_tri(min(r, k), max(r, k))] : 0.f;
+                const float b_j = LDSCF(sums)[21 + (lane < 36 ? lane : 35) % 6];
+                svd6_sweeps_lanes(ra, rv);
+                SIA_T(s1);
+                svd6_tail_lanes(ra, rv, b_j, delta);
+                SIA_T(s2);
+                SIA_ADD(10, s1, g2); SIA_ADD(11, s2, s1);
+            } else {
+                float H[36], b[6];
+                int q = 0;
+#pragma unroll
+                for (int r = 0; r < 6; r++)
+#pragma unroll
+                    for (int c = r; c < 6; c++) { H[r * 6 + c] = acc[q]; H[c * 6 + r] = acc[q]; q++; }
+#pragma unroll
+                for (int r = 0; r < 6; r++) b[r] = acc[21 + r];
+                gn_solve6(H, b, delta, false);
+            }
+        };
         if (WAVES > 2) {
             // four waves: wave 0 solves, the others wait at the barrier (the same 6x6 SVD in every wave would
             // only take VALU time from the kernels of the other sequence groups)
             if (wave == 0) {
-                gn_solve6(H, b, delta, exact);
+                solve();
                 exponential_map(delta, pg);
                 mat33f_vec(pm.R, pg, grad);
                 mat33f_vec(pm.R, pg + 3, grad + 3);
@@ -621,7 +635,7 @@ struct Sia {
             for (int q = 0; q < 6; q++) grad[q] = LDSCF(sums)[WAVES * 32 + q];
             __syncthreads();                             // (sums is written again by the next call)
         } else {
-        gn_solve6(H, b, delta, exact);
+        solve();
         exponential_map(delta, pg);
         mat33f_vec(pm.R, pg, grad);                  // pose_estimator.cpp:495-497
         mat33f_vec(pm.R, pg + 3, grad + 3);
@@ -630,8 +644,13 @@ struct Sia {
         SIA_ADD(5, g1, g0); SIA_ADD(6, g2, g1); SIA_ADD(7, g3, g2); SIA_ADD(8, 1, 0);
 #ifndef SVO_SIA_STAMPS
         if (dbg && tid == 0) {
-            for (int q = 0; q < 36; q++) dbg[q] = H[q];
-            for (int q = 0; q < 6; q++) { dbg[36 + q] = b[q]; dbg[42 + q] = grad[q]; }
+            int q = 0;
+            for (int r = 0; r < 6; r++)
+                for (int c = r; c < 6; c++, q++) {
+                    const float v = exact ? LDSCF(sums)[q] : acc[q];
+                    dbg[r * 6 + c] = v; dbg[c * 6 + r] = v;
+                }
+            for (int r = 0; r < 6; r++) { dbg[36 + r] = exact ? LDSCF(sums)[21 + r] : acc[21 + r]; dbg[42 + r] = grad[r]; }
         }
 #else
         (void)dbg;

@@ -406,3 +406,80 @@ extern "C" int svo_pinv6_check(svo_handle* h, const float* H_dev, int n, float* 
     HIP_TRY(hipGetLastError());
     return SVO_OK;
 }
+
+// svo_solve6_check: the exact Gauss-Newton solve delta = pinv(H) b, one system per wavefront (H and b loaded
+// alike by all 64 lanes). IMPL 0 is the round-4 solve: jacobi_svd6_lanes, then svd6_pinv and delta = Hinv b
+// on wave-uniform values. IMPL 1 is the kernels' solve: svd6_sweeps_lanes + svd6_tail_lanes, every element
+// in its own lane. Output per system (120 floats): Hinv, W, Vt, U^T, delta.
+template <int IMPL>
+__global__ void __launch_bounds__(64) solve6_check_kernel(const float* H, const float* B, int n, float* out,
+                                                          int32_t* sweeps) {
+    const long sys = (long)blockIdx.x;
+    if (sys >= n) return;   // never taken (one workgroup per system): the wave stays converged
+    const float* h = H + sys * 36;
+    const float* b = B + sys * 6;
+    float* o = out + sys * 120;
+    const int lane = threadIdx.x;
+    if constexpr (IMPL == 0) {
+        float At[6][6], W[6], Vt[6][6], Hinv[36], delta[6];
+#pragma unroll
+        for (int i = 0; i < 6; i++)
+#pragma unroll
+            for (int j = 0; j < 6; j++) At[i][j] = h[j * 6 + i];
+        const int sw = jacobi_svd6_lanes(At, W, Vt);
+        svd6_pinv(At, W, Vt, Hinv);
+#pragma unroll
+        for (int r = 0; r < 6; r++) {
+            float sacc = 0;
+#pragma unroll
+            for (int c = 0; c < 6; c++) sacc += Hinv[r * 6 + c] * b[c];
+            delta[r] = sacc;
+        }
+        if (lane != 0) return;
+#pragma unroll
+        for (int i = 0; i < 36; i++) o[i] = Hinv[i];
+#pragma unroll
+        for (int i = 0; i < 6; i++) o[36 + i] = W[i];
+#pragma unroll
+        for (int i = 0; i < 6; i++)
+#pragma unroll
+            for (int k = 0; k < 6; k++) { o[42 + i * 6 + k] = Vt[i][k]; o[78 + i * 6 + k] = At[i][k]; }
+#pragma unroll
+        for (int i = 0; i < 6; i++) o[114 + i] = delta[i];
+        sweeps[sys] = sw;
+    } else {
+        const int r = lane & 7;
+        float a[6], v[6], delta[6];
+#pragma unroll
+        for (int k = 0; k < 6; k++) a[k] = r < 6 ? h[k * 6 + r] : 0.f;
+        const float b_j = b[(lane < 36 ? lane : 35) % 6];
+        const int sw = svd6_sweeps_lanes(a, v);
+        Solve6Lane e;
+        svd6_tail_lanes(a, v, b_j, delta, &e);
+        if (lane < 36) {
+            o[lane] = e.hinv;
+            o[42 + lane] = e.vt;
+            o[78 + lane] = e.ut;
+            if (lane % 6 == 0) o[36 + lane / 6] = e.w;
+        }
+        if (lane == 0) {
+#pragma unroll
+            for (int i = 0; i < 6; i++) o[114 + i] = delta[i];
+            sweeps[sys] = sw;
+        }
+    }
+}
+
+extern "C" int svo_solve6_check(svo_handle* h, const float* H_dev, const float* b_dev, int n, float* out_dev,
+                                int32_t* sweeps_dev, int impl) {
+    CHECK_H(h);
+    if (n < 0 || (n > 0 && (!H_dev || !b_dev || !out_dev || !sweeps_dev)) || (impl != 0 && impl != 1))
+        return svo_set_error(SVO_ERR_INVALID, "svo_solve6_check: bad arguments");
+    if (n == 0) return SVO_OK;
+    if (impl == 0)
+        solve6_check_kernel<0><<<n, 64, 0, h->stream>>>(H_dev, b_dev, n, out_dev, sweeps_dev);
+    else
+        solve6_check_kernel<1><<<n, 64, 0, h->stream>>>(H_dev, b_dev, n, out_dev, sweeps_dev);
+    HIP_TRY(hipGetLastError());
+    return SVO_OK;
+}

@@ -519,21 +519,14 @@ constexpr uint32_t kSvdLag[6] = {0x3Cu, 0x28u, 0x30u, 0x00u, 0x00u, 0x00u};
 // The reference runs at most 30 sweeps (iter < 30): pairs of sweep 30 are masked and the loop stops
 // after position 3 of iteration 30. Returns the sweep count of the reference loop.
 //
-// Precondition: the wave is converged (all 64 lanes active) and At holds the same values in every
-// lane; At, W and Vt come back wave-uniform (v_readlane), through the same svd6_finish.
-__device__ inline int jacobi_svd6_lanes(float (&At)[6][6], float (&W)[6], float (&Vt)[6][6]) {
+// Precondition: the wave is converged (all 64 lanes active). In: a = row r of At (r = 6, 7: zeros).
+// Out: a, v = rows r of the rotated At and of Vt, before the sort and the scaling.
+__device__ inline int svd6_sweeps_lanes(float (&a)[6], float (&v)[6]) {
     const float eps = FLT_EPSILON * 2;
     const int lane = (int)__lane_id();
     const int r = lane & 7;
-    float a[6], v[6];
 #pragma unroll
-    for (int k = 0; k < 6; k++) {
-        float x = 0.f;
-#pragma unroll
-        for (int i = 0; i < 6; i++) x = (r == i) ? At[i][k] : x;
-        a[k] = x;
-        v[k] = (r == k) ? 1.f : 0.f;
-    }
+    for (int k = 0; k < 6; k++) v[k] = (r == k) ? 1.f : 0.f;
     double wd = 0;
 #pragma unroll
     for (int k = 0; k < 6; k++) wd = __builtin_fma((double)a[k], (double)a[k], wd);
@@ -607,6 +600,23 @@ __device__ inline int jacobi_svd6_lanes(float (&At)[6][6], float (&W)[6], float 
         chg_prev = chg_cur;
         chg_cur = false;
     }
+    return t;
+}
+
+// The round-4 form of the solve's SVD (svo_pinv6_check, svo_solve6_check impl 0 only): the sweeps in
+// lanes, then At, W and Vt wave-uniform (v_readlane) through svd6_finish. Precondition: the wave is
+// converged and At holds the same values in every lane.
+__device__ inline int jacobi_svd6_lanes(float (&At)[6][6], float (&W)[6], float (&Vt)[6][6]) {
+    const int r = (int)__lane_id() & 7;
+    float a[6], v[6];
+#pragma unroll
+    for (int k = 0; k < 6; k++) {
+        float x = 0.f;
+#pragma unroll
+        for (int i = 0; i < 6; i++) x = (r == i) ? At[i][k] : x;
+        a[k] = x;
+    }
+    const int t = svd6_sweeps_lanes(a, v);
 #pragma unroll
     for (int i = 0; i < 6; i++)
 #pragma unroll
@@ -618,7 +628,8 @@ __device__ inline int jacobi_svd6_lanes(float (&At)[6][6], float (&W)[6], float 
     return t;
 }
 
-// pinv(H) from its SVD: V diag(1/w) U^T with the SVBkSb threshold; zeros unless ok.
+// pinv(H) from its SVD (Matx66f::inv(DECOMP_SVD)): V diag(1/w) U^T with the SVBkSb threshold; zeros
+// when sigma_max < FLT_EPSILON or sigma_min / sigma_max == 0.
 __device__ inline void svd6_pinv(const float (&At)[6][6], const float (&W)[6], const float (&Vt)[6][6],
                                   float Hinv[36]) {
 #pragma unroll
@@ -650,17 +661,139 @@ __device__ inline void svd6_pinv(const float (&At)[6][6], const float (&W)[6], c
     }
 }
 
-// Matx66f::inv(DECOMP_SVD): zeros when sigma_max < FLT_EPSILON or
-// sigma_min / sigma_max == 0, else V diag(1/w) U^T with the SVBkSb threshold.
-// Called by a converged wave with H wave-uniform (jacobi_svd6_lanes).
-__device__ inline void inv_svd6(const float H[36], float Hinv[36]) {
-    float At[6][6], Vt[6][6], W[6];
+// Per-lane outputs of svd6_tail_lanes for svo_solve6_check: lane L = 6i + j < 36 holds Hinv(i, j),
+// U^T(i, j), Vt(i, j) and W[i].
+struct Solve6Lane {
+    float hinv, ut, vt, w;
+};
+
+// What follows the sweeps of the exact solve — svd6_finish, svd6_pinv and delta = Hinv b of the
+// round-4 solve (jacobi_svd6_lanes + svd6_pinv + the product in gn_solve6) — with the elements in
+// lanes instead of wave-uniform registers. In: a, v from svd6_sweeps_lanes (row r = lane & 7 < 6);
+// bf(j) = b[j]. Out: delta wave-uniform. Precondition: the wave is converged.
+//
+// Why the bits are the same. Every element below is computed by one lane with the reference's
+// operations on the reference's operands in the reference's order; only where the operands live changes.
+// - Wd: lane r sums its own row's squares (k order, fma with exact products) and takes the square root.
+// - The sort: the six Wd are read back wave-uniform and the selection sort runs on them with the
+//   reference's compares ("first maximum of rows i..5", the same swaps, ties and NaNs included) while
+//   an index array follows the swaps: src[i] is the row that ends at position i. The sort moves rows
+//   whole, so sorted row i is unsorted row src[i], element by element.
+// - Lane L = 6i + j takes U^T(i, j), Vt(i, j) from row src[i] (one ds_bpermute each, from lane 8j + src[i],
+//   which picked element j of its row) and scales U^T(i, j) by the reference's s_i, from Wd sorted.
+// - The pseudo-inverse: threshold is the ordered sum of the wave-uniform W. Lane 6i + j holds
+//   buffer[j] = U^T(i, j) * (1 / W[i]) of row i, the reference's double. Lane (r, j) runs its own chain
+//   Hinv(r, j) = (float)(Hinv(r, j) + Vt(i, r) * buffer[j]) over i = 0..5 in order, taking Vt(i, r) from
+//   lane 6i + r and buffer[j] from lane 6i + j, and skips row i under the same wave-uniform test
+//   fabs(W[i]) <= threshold. The `ok` test zeroes it as before.
+// - The step: lane L forms Hinv(r, j) * b[j] (the product of sacc += Hinv * b, -ffp-contract=off), lane r
+//   adds the six products of its row to 0 in j order, and delta[r] is read back wave-uniform.
+__device__ inline void svd6_tail_lanes(const float (&a)[6], const float (&v)[6], float b_j, float delta[6],
+                                       Solve6Lane* out = nullptr) {
+    const int lane = (int)__lane_id();
+    double sd = 0;
 #pragma unroll
-    for (int i = 0; i < 6; i++)
+    for (int k = 0; k < 6; k++) sd = __builtin_fma((double)a[k], (double)a[k], sd);
+    const double wr = sqrt(sd);
+    double w[6];
+    int src[6];
 #pragma unroll
-        for (int j = 0; j < 6; j++) At[i][j] = H[j * 6 + i];
-    jacobi_svd6_lanes(At, W, Vt);
-    svd6_pinv(At, W, Vt, Hinv);
+    for (int i = 0; i < 6; i++) {
+        w[i] = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(wr), i),
+                                __builtin_amdgcn_readlane(__double2loint(wr), i));
+        src[i] = i;
+    }
+#pragma unroll
+    for (int i = 0; i < 5; i++) {
+        int j = i;
+        double wj = w[i];
+#pragma unroll
+        for (int k = i + 1; k < 6; k++)
+            if (wj < w[k]) { j = k; wj = w[k]; }
+#pragma unroll
+        for (int k = i + 1; k < 6; k++)
+            if (j == k) {
+                const double tw = w[i]; w[i] = w[k]; w[k] = tw;
+                const int ts = src[i]; src[i] = src[k]; src[k] = ts;
+            }
+    }
+    // lane L = 6i + j (lanes past 35 mirror lane 35)
+    const int L = lane < 36 ? lane : 35;
+    const int i = L / 6, j = L - 6 * i;
+    // (elements picked with bit masks: a chain of selects between the elements of an array is folded into
+    // one load at a lane-dependent index, which moves the array to scratch memory)
+    int si = 0, wlo = 0, whi = 0;
+#pragma unroll
+    for (int q = 0; q < 6; q++) {
+        const int m = -(int)(i == q);
+        si |= m & src[q];
+        wlo |= m & __double2loint(w[q]);
+        whi |= m & __double2hiint(w[q]);
+    }
+    const double wi = __hiloint2double(whi, wlo);
+    // lane 8g + r offers element g of its row r; lane L reads element j of row src[i]
+    const int g = lane >> 3;
+    int agb = 0, vgb = 0;
+#pragma unroll
+    for (int k = 0; k < 6; k++) {
+        const int m = -(int)(g == k);
+        agb |= m & __float_as_int(a[k]);
+        vgb |= m & __float_as_int(v[k]);
+    }
+    const int from = (8 * j + si) << 2;
+    float ut = __int_as_float(__builtin_amdgcn_ds_bpermute(from, agb));
+    const float vt = __int_as_float(__builtin_amdgcn_ds_bpermute(from, vgb));
+    const float wf = (float)wi;
+    const float sc = (float)(wi > (double)FLT_MIN ? 1 / wi : 0.);
+    ut *= sc;
+
+    float W[6];
+#pragma unroll
+    for (int q = 0; q < 6; q++) W[q] = (float)w[q];
+    double threshold = 0;
+#pragma unroll
+    for (int q = 0; q < 6; q++) threshold += W[q];
+    threshold *= (float)(DBL_EPSILON * 2);
+    const double buf = ut * (1 / (double)wf);
+    const int blo = __double2loint(buf), bhi = __double2hiint(buf);
+    float h = 0;
+#pragma unroll
+    for (int q = 0; q < 6; q++) {
+        const int fb = (6 * q + j) << 2, fv = (6 * q + i) << 2;
+        const double bq = __hiloint2double(__builtin_amdgcn_ds_bpermute(fb, bhi), __builtin_amdgcn_ds_bpermute(fb, blo));
+        const float sv = __int_as_float(__builtin_amdgcn_ds_bpermute(fv, __float_as_int(vt)));
+        const double wq = W[q];
+        if (!(fabs(wq) <= threshold)) h = (float)(h + sv * bq);
+    }
+    const bool ok = W[0] >= FLT_EPSILON ? (W[5] / W[0] != 0) : false;
+    if (!ok) h = 0;
+    if (out) *out = Solve6Lane{h, ut, vt, wf};
+
+    const float p = h * b_j;
+    const int rr = lane < 6 ? lane : 0;
+    float sacc = 0;
+#pragma unroll
+    for (int c = 0; c < 6; c++) sacc += __int_as_float(__builtin_amdgcn_ds_bpermute((6 * rr + c) << 2, __float_as_int(p)));
+#pragma unroll
+    for (int q = 0; q < 6; q++) delta[q] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(sacc), q));
+}
+
+// Index of H(r, c), r <= c, among the 21 upper-triangle sums (row-major, as the accumulators store them).
+__device__ inline int h6_tri(int r, int c) { return r * (11 - r) / 2 + c; }
+
+// The exact solve delta = pinv(H) b straight from the accumulators: sums[0..20] the upper triangle of the
+// symmetric H, sums[21..26] b (LDS). Lane r = lane & 7 < 6 reads row r of H (= row r of At), lane L < 36
+// b[L % 6]; no wave-uniform H. Precondition: the wave is converged. Returns the sweeps run.
+__device__ inline int gn_solve6_sums(const SVO_LDS(float)* sums, float delta[6]) {
+    const int lane = (int)__lane_id();
+    const int r = lane & 7;
+    float a[6], v[6];
+#pragma unroll
+    for (int k = 0; k < 6; k++) a[k] = r < 6 ? sums[h6_tri(min(r, k), max(r, k))] : 0.f;
+    const float b_j = sums[21 + (lane < 36 ? lane : 35) % 6];
+    const int sw = svd6_sweeps_lanes(a, v);
+    svd6_tail_lanes(a, v, b_j, delta);
+    return sw;
 }
 
 // delta = pinv(H) b for the Gauss-Newton steps (pose_estimator.cpp:405,484;
@@ -715,15 +848,23 @@ __device__ inline void gn_solve6(const float H[36], const float b[6], float delt
             return;
         }
     }
-    float Hinv[36];
-    inv_svd6(H, Hinv);
+    // the exact solve in lanes: lane r takes row r of At = H^T, lane L < 36 b[L % 6] (bit masks: see
+    // svd6_tail_lanes)
+    const int lane = (int)__lane_id();
+    const int r = lane & 7, jb = (lane < 36 ? lane : 35) % 6;
+    float a[6], v[6];
+    int bb = 0;
 #pragma unroll
-    for (int r = 0; r < 6; r++) {
-        float sacc = 0;
+    for (int k = 0; k < 6; k++) {
+        int x = 0;
 #pragma unroll
-        for (int c = 0; c < 6; c++) sacc += Hinv[r * 6 + c] * b[c];
-        delta[r] = sacc;
+        for (int i = 0; i < 6; i++) x |= -(int)(r == i) & __float_as_int(H[k * 6 + i]);
+        a[k] = __int_as_float(x);
+        bb |= -(int)(jb == k) & __float_as_int(b[k]);
     }
+    const float b_j = __int_as_float(bb);
+    svd6_sweeps_lanes(a, v);
+    svd6_tail_lanes(a, v, b_j, delta);
 }
 
 // cv::solve(A[3x2], b, x, DECOMP_SVD), src/lib/depth_filter.cpp:194-200

@@ -29,6 +29,7 @@ SYMBOLS = (
     "svo_device_malloc", "svo_device_free", "svo_copy_to_device", "svo_copy_to_host",
     "svo_copy_image_to_device", "svo_project_keypoints",
     "svo_ctx_get_launch_shapes", "svo_pick_launch_shapes", "svo_pinv6_check",
+    "svo_solve6_check",
 )
 
 
@@ -210,6 +211,16 @@ class Handle:
         out = torch.empty((n, 114), dtype=torch.float32, device=H.device)
         sweeps = torch.empty(n, dtype=torch.int32, device=H.device)
         _check(lib().svo_pinv6_check(self._h, _ptr(H), n, _ptr(out), _ptr(sweeps), int(impl)))
+        return out, sweeps
+
+    def solve6_check(self, H, b, impl):
+        """Diagnostic: the exact Gauss-Newton solve delta = pinv(H) b of n systems H[n, 36], b[n, 6]
+        (float32, device), impl 0 = round-4 solve (wave-uniform finish), 1 = lane-resident solve of the
+        kernels. Returns (out[n, 120] float32 = Hinv, W, Vt, U^T, delta per system, sweeps[n] int32)."""
+        n = H.shape[0]
+        out = torch.empty((n, 120), dtype=torch.float32, device=H.device)
+        sweeps = torch.empty(n, dtype=torch.int32, device=H.device)
+        _check(lib().svo_solve6_check(self._h, _ptr(H), _ptr(b), n, _ptr(out), _ptr(sweeps), int(impl)))
         return out, sweeps
 
     def reproj_gn(self, kps2d, kps3d, flags, cam, pose_in, tracked=None, err=None):

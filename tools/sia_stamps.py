@@ -2,6 +2,8 @@
 (tools/build_variants.sh stamps -> build_ab/libsvo_hip_stamps.so) and prints where one
 sparse-alignment launch spends its cycles (s_memtime on thread 0), for a lone sequence
 (workgroup shape by keypoint count) and, with `batch`, for the one-wave shape of batched launches.
+"grad: solve" is split into "solve: sweeps" (rows in, Jacobi sweeps) and "solve: tail+step" (singular
+values, sort, pseudo-inverse, delta); what is left of it is exponential_map and the rotation.
 Usage: sia_stamps.py [config] [exact]"""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -28,8 +30,9 @@ s = dbg.cpu().numpy()[:12]
 tr = hip_lib.trace_to_numpy(trace)
 ng = sum(int(t["n_gradient"]) for t in tr); nc = sum(int(t["n_cost"]) for t in tr)
 names = ["levels: image + records", "cost: pose_mats", "cost: keypoints", "cost: ordered sum", "n_cost",
-         "grad: pose+keypoints", "grad: reduce", "grad: solve", "n_grad", "kernel_total"]
+         "grad: pose+keypoints", "grad: reduce", "grad: solve", "n_grad", "kernel_total",
+         "solve: sweeps", "solve: tail+step"]
 print(f"{config}: n = {len(sc['kps2d'])}, exact = {exact}, n_grad {ng}, n_cost {nc}")
 for n_, v in zip(names, s):
-    per = v / max(s[4], 1) if n_.startswith("cost") else (v / max(s[8], 1) if n_.startswith("grad") else v)
+    per = v / max(s[4], 1) if n_.startswith("cost") else (v / max(s[8], 1) if n_.startswith(("grad", "solve")) else v)
     print(f"{n_:26s} total {v:12.0f}  per call {per:10.0f} cycles (100 MHz ticks x clock ratio)")
