@@ -75,6 +75,14 @@ int svo_build_pyramid(svo_handle *h, int n_levels, svo_image *levels);
  * levels[l>=1] receive pyrDown of the previous level; *n_out = usable levels. */
 int svo_build_lk_pyramid(svo_handle *h, int max_levels, int win, svo_image *levels, int *n_out);
 
+/* R   cv::remap(src, dst, map_x, map_y, INTER_LINEAR), BORDER_CONSTANT 0   src/app/euroc_input.cpp:69-70
+ * n images that share one map: src[i] (any size) -> dst[i] (dst width x height = the map's size, same for all i);
+ * map_x / map_y: device, dst width x height floats, dense rows. Bit-exact to OpenCV's fixed-point remap
+ * (INTER_BITS 5: positions rounded half to even to 1/32 pixel, 15-bit weights; a map entry that is not
+ * finite or whose |value * 32| >= 2^31 gives 0). Sources up to 16383 pixels a side. */
+int svo_remap_linear(svo_handle *h, int n, const svo_image *src, svo_image *dst,
+                     const float *map_x, const float *map_y);
+
 /* A   PoseEstimator::estimate_pose(guess, out) src/include/pose_estimator.hpp:19-27,
  *                                              src/lib/pose_estimator.cpp:115-130
  * prev_pyr/cur_pyr: cam->max_pyramid_levels halfSample levels (host array of
@@ -135,7 +143,8 @@ typedef struct svo_ctx svo_ctx;
 /* SVO_MEM_DEVICE_BORROW: device images that the ctx uses IN PLACE as level 0 of its pyramids and
  * as the right image — no copy, like the reference, whose level 0 is a shallow alias of the caller's
  * cv::Mat (src/lib/stereo_slam.cpp:115). The caller keeps every image valid and unchanged while a
- * frame or keyframe of the ctx refers to it (the safe choice: until svo_ctx_destroy). */
+ * frame or keyframe of the ctx refers to it (the safe choice: until svo_ctx_destroy). With
+ * rectification on (svo_ctx_set_rectification) the images are only read during their step. */
 enum { SVO_MEM_HOST = 0, SVO_MEM_DEVICE = 1, SVO_MEM_DEVICE_BORROW = 2 };
 
 /* StereoSlam::StereoSlam(const CameraSettings&)         src/lib/stereo_slam.cpp:29-41 */
@@ -163,6 +172,17 @@ int svo_submit_images(svo_ctx *ctx, const uint8_t *const *left, const uint8_t *c
                       int stride, const float *time_stamps, int mem);
 int svo_wait(svo_ctx *ctx);
 int svo_ctx_get_groups(svo_ctx *ctx, int *n_groups);
+/* EurocInput's rectification (maps :48-49, remap :69-70) inside the tracker: from the next frame on, the
+ * images given to svo_new_image(s) / svo_submit_images are RAW images of the ctx size, remapped on the
+ * device before the pyramids. left_* rectify the library's left image (the reference's M1r/M2r: cam1 with
+ * RIGHT.*), right_* its right image (M1l/M2l). Each map: width x height floats, dense rows, host
+ * (SVO_MEM_HOST) or device (SVO_MEM_DEVICE) memory; copied. All four NULL: off. Waits for queued frames.
+ * The arithmetic is svo_remap_linear's. Every sequence of the ctx shares the maps (one camera rig); they
+ * apply to every frame of every active sequence, keyframes and the first frame included. With
+ * SVO_MEM_DEVICE_BORROW and rectification on, the raw frames are read once and level 0 is the ctx's own
+ * rectified image: the caller may reuse the raw buffers once the step is done (after svo_wait). */
+int svo_ctx_set_rectification(svo_ctx *ctx, const float *left_map_x, const float *left_map_y,
+                              const float *right_map_x, const float *right_map_y, int mem);
 /* n_sequences == 1, host memory: the exact shape of StereoSlam::new_image */
 int svo_new_image(svo_ctx *ctx, const uint8_t *left, int left_stride, const uint8_t *right,
                   int right_stride, int width, int height, float time_stamp);

@@ -1,0 +1,232 @@
+// rectify.hip — the input stage of EurocInput::read (src/app/euroc_input.cpp:69-70):
+// cv::remap(raw, out, M1, M2, INTER_LINEAR) with BORDER_CONSTANT 0 on 8-bit images and CV_32FC1 maps,
+// bit-exact to OpenCV's fixed-point path (RemapInvoker + remapBilinear, INTER_BITS = 5,
+// INTER_REMAP_COEF_BITS = 15). Per output pixel, m = (map_x, map_y):
+//
+//  * m non-finite or |m*32| >= 2^31: 0 (cvRound gives INT_MIN there: outside every image);
+//  * X = round_half_even(mx*32), Y likewise (the product is exact); sx = X >> 5, sy = Y >> 5 (floor),
+//    fx = X & 31, fy = Y & 31;
+//  * taps v00 = src[sy][sx], v01 = src[sy][sx+1], v10 = src[sy+1][sx], v11 = src[sy+1][sx+1], 0 outside
+//    the image; weights 32(32-fx)(32-fy), 32 fx(32-fy), 32(32-fx)fy, 32 fx fy (sum 2^15);
+//  * out = (sum w v + 2^14) >> 15 = (sum' + 512) >> 10 over the products without the factor 32.
+//    OpenCV's int16 table stores 32767 for the weight 2^15 of an integer position and moves the
+//    remainder to another tap; the result is still v00 there (the difference is below 2^14).
+//
+// Two kernels:
+//  * remap_prep_kernel (once per map): float maps -> fixed point in 64x64 output tiles, with the
+//    non-finite / range rule applied explicitly (a plain float->int conversion is undefined in C++ for
+//    those and gives 0 for NaN on the GPU), plus per tile the bounding box of the source taps;
+//  * remap_linear_kernel (per frame): one workgroup per (output tile, REMAP_SPB images, side). The
+//    tile's map entries are loaded once (16 B per lane) and reused for every image of the workgroup.
+//    Where the tile's source box, clipped to the image, fits REMAP_LDS_BYTES it is staged in LDS with
+//    dword loads and the four taps are gathered from there; otherwise (random or extreme maps) they are
+//    gathered from global memory. Four output pixels of a row per lane, stored as one dword.
+//
+// Every address a tap forms lies inside the source image (or the staged box, which is inside it): the
+// tests are on clamped int16 positions (|x|, |y| <= 16384), so nothing can wrap.
+#include "svo_kernels.hpp"
+
+#include <climits>
+
+namespace svo {
+
+constexpr int REMAP_THREADS = 256;
+constexpr int REMAP_SPB = 16;              // images per workgroup of remap_linear_kernel (map entries read once for them)
+constexpr int REMAP_LDS_BYTES = 12288;     // staged source box (EuRoC: at most 68 x 68 of a 64 x 64 tile)
+constexpr int REMAP_ENTRIES = REMAP_TILE * REMAP_TILE;
+
+static_assert(REMAP_THREADS == 16 * 16, "a lane covers 4 columns of 4 rows (16 lanes per 64-pixel row)");
+
+size_t remap_map_bytes(int w, int h) {
+    const size_t tiles = (size_t)((w + REMAP_TILE - 1) / REMAP_TILE) * ((h + REMAP_TILE - 1) / REMAP_TILE);
+    auto al = [](size_t b) { return (b + 255) / 256 * 256; };
+    return al(tiles * REMAP_ENTRIES * 4) + al(tiles * REMAP_ENTRIES * 2) + al(tiles * sizeof(int4));
+}
+
+RemapMap remap_map_view(void* base, int w, int h) {
+    RemapMap m;
+    m.w = w; m.h = h;
+    m.tiles_x = (w + REMAP_TILE - 1) / REMAP_TILE;
+    m.tiles_y = (h + REMAP_TILE - 1) / REMAP_TILE;
+    const size_t tiles = (size_t)m.tiles_x * m.tiles_y;
+    auto al = [](size_t b) { return (b + 255) / 256 * 256; };
+    uint8_t* p = static_cast<uint8_t*>(base);
+    m.xy = reinterpret_cast<const uint32_t*>(p);
+    m.frac = reinterpret_cast<const uint16_t*>(p + al(tiles * REMAP_ENTRIES * 4));
+    m.box = reinterpret_cast<const int4*>(p + al(tiles * REMAP_ENTRIES * 4) + al(tiles * REMAP_ENTRIES * 2));
+    return m;
+}
+
+// one coordinate: X = round_half_even(m * 32) where |m * 32| < 2^31 (false for NaN and inf)
+__device__ __forceinline__ int fix5(float m, bool& ok) {
+    const float v = m * 32.0f;
+    ok = fabsf(v) < 2147483648.0f;
+    return ok ? (int)__builtin_rintf(v) : 0;
+}
+
+__global__ __launch_bounds__(REMAP_THREADS) void remap_prep_kernel(const float* __restrict__ map_x,
+                                                                   const float* __restrict__ map_y, RemapMap m) {
+    __shared__ int s_box[4];
+    const int t = blockIdx.x;
+    const int tx = t % m.tiles_x, ty = t / m.tiles_x;
+    const int lane = threadIdx.x;
+    const int c4 = (lane & 15) * 4, r0 = lane >> 4;
+    if (lane == 0) { s_box[0] = INT_MAX; s_box[1] = INT_MIN; s_box[2] = INT_MAX; s_box[3] = INT_MIN; }
+    __syncthreads();
+    int bx0 = INT_MAX, bx1 = INT_MIN, by0 = INT_MAX, by1 = INT_MIN;
+    SVO_GP(const float) gx = G(map_x);
+    SVO_GP(const float) gy = G(map_y);
+    SVO_GP(uint4) oxy = (SVO_GP(uint4))G(const_cast<uint32_t*>(m.xy) + (size_t)t * REMAP_ENTRIES);
+    SVO_GP(uint2) ofr = (SVO_GP(uint2))G(const_cast<uint16_t*>(m.frac) + (size_t)t * REMAP_ENTRIES);
+    for (int k = 0; k < 4; k++) {
+        const int r = r0 + 16 * k, y = ty * REMAP_TILE + r;
+        uint32_t e[4], f[4];
+        for (int j = 0; j < 4; j++) {
+            const int x = tx * REMAP_TILE + c4 + j;
+            int sx = -2, sy = -2, fr = 0;
+            if (x < m.w && y < m.h) {
+                bool okx, oky;
+                const int X = fix5(gx[(size_t)y * m.w + x], okx);
+                const int Y = fix5(gy[(size_t)y * m.w + x], oky);
+                if (okx && oky) {
+                    sx = min(max(X >> 5, -2), REMAP_MAX_SRC);
+                    sy = min(max(Y >> 5, -2), REMAP_MAX_SRC);
+                    fr = (X & 31) | (Y & 31) << 5;
+                }
+            }
+            // taps sx, sx + 1 (sy, sy + 1) can fall inside an image of at most REMAP_MAX_SRC a side
+            if (sx >= -1 && sx < REMAP_MAX_SRC && sy >= -1 && sy < REMAP_MAX_SRC) {
+                bx0 = min(bx0, max(sx, 0)); bx1 = max(bx1, sx + 1);
+                by0 = min(by0, max(sy, 0)); by1 = max(by1, sy + 1);
+            }
+            e[j] = ((uint32_t)sx & 0xffffu) | (uint32_t)sy << 16;
+            f[j] = (uint32_t)fr;
+        }
+        oxy[r * 16 + (lane & 15)] = make_uint4(e[0], e[1], e[2], e[3]);
+        ofr[r * 16 + (lane & 15)] = make_uint2(f[0] | f[1] << 16, f[2] | f[3] << 16);
+    }
+    if (bx0 != INT_MAX) {
+        atomicMin(&s_box[0], bx0); atomicMax(&s_box[1], bx1);
+        atomicMin(&s_box[2], by0); atomicMax(&s_box[3], by1);
+    }
+    __syncthreads();
+    if (lane == 0) {
+        int4* ob = const_cast<int4*>(m.box) + t;
+        *G(ob) = s_box[0] == INT_MAX ? make_int4(0, -1, 0, -1) : make_int4(s_box[0], s_box[1], s_box[2], s_box[3]);
+    }
+}
+
+// the 16 output pixels of a lane (4 rows r0 + 16k, 4 columns c4 .. c4+3) of one image, a row of 4 at a
+// time: tap(x, y) -> 0..255, store(k, 4 pixels). The scheduling barrier keeps the rows apart (hoisting all
+// 64 taps costs more registers than the occupancy allows).
+template <typename Tap, typename Store>
+__device__ __forceinline__ void remap_gather(const uint32_t (&xy)[16], const uint32_t (&fr)[8], Tap tap, Store store) {
+    for (int k = 0; k < 4; k++) {
+        uint32_t packed = 0;
+        for (int j = 0; j < 4; j++) {
+            const uint32_t e = xy[4 * k + j];
+            const uint32_t f = (fr[2 * k + (j >> 1)] >> (16 * (j & 1))) & 0xffffu;
+            const int sx = (int)(int16_t)(e & 0xffffu), sy = (int)e >> 16;
+            const int fx = (int)(f & 31u), fy = (int)(f >> 5) & 31;
+            const int v00 = tap(sx, sy), v01 = tap(sx + 1, sy), v10 = tap(sx, sy + 1), v11 = tap(sx + 1, sy + 1);
+            const int s = v00 * (32 - fx) * (32 - fy) + v01 * fx * (32 - fy) + v10 * (32 - fx) * fy + v11 * fx * fy;
+            packed |= (uint32_t)((s + 512) >> 10) << (8 * j);
+        }
+        store(k, packed);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
+
+__global__ __launch_bounds__(REMAP_THREADS) void remap_linear_kernel(RemapLaunch a) {
+    __shared__ uint32_t s_src[REMAP_LDS_BYTES / 4];
+    const int side = blockIdx.z;
+    const RemapMap m = side ? a.map[1] : a.map[0];
+    const int t = blockIdx.x;
+    const int tx = t % m.tiles_x, ty = t / m.tiles_x;
+    const int lane = threadIdx.x;
+    const int c4 = (lane & 15) * 4, r0 = lane >> 4;
+    // the tile's map entries: once for every image of the workgroup
+    uint32_t xy[16], fr[8];
+    SVO_GP(const uint4) pxy = (SVO_GP(const uint4))G(m.xy + (size_t)t * REMAP_ENTRIES);
+    SVO_GP(const uint2) pfr = (SVO_GP(const uint2))G(m.frac + (size_t)t * REMAP_ENTRIES);
+    for (int k = 0; k < 4; k++) {
+        const uint4 v = pxy[(r0 + 16 * k) * 16 + (lane & 15)];
+        const uint2 f = pfr[(r0 + 16 * k) * 16 + (lane & 15)];
+        xy[4 * k] = v.x; xy[4 * k + 1] = v.y; xy[4 * k + 2] = v.z; xy[4 * k + 3] = v.w;
+        fr[2 * k] = f.x; fr[2 * k + 1] = f.y;
+    }
+    const int4 box = *G(m.box + t);
+    const int i0 = blockIdx.y * REMAP_SPB, i1 = min(a.n, i0 + REMAP_SPB);
+    for (int i = i0; i < i1; i++) {
+        // (the entries pass through an empty asm per image: otherwise the decoded positions and weights of
+        // all 16 pixels are hoisted out of the image loop, 256 VGPRs instead of the ~60 the kernel needs)
+        for (int j = 0; j < 16; j++) asm volatile("" : "+v"(xy[j]));
+        for (int j = 0; j < 8; j++) asm volatile("" : "+v"(fr[j]));
+        const RemapImg im = G(a.img)[side * a.n + i];
+        const ImgView src = im.src, dst = im.dst;
+        // the tile's source box on this image (x0, y0 >= 0 already)
+        const int bx0 = box.x, bx1 = min(box.y, src.w - 1), by0 = box.z, by1 = min(box.w, src.h - 1);
+        const bool empty = bx1 < bx0 || by1 < by0;
+        const int xs = bx0 & ~3;                                   // staged from a dword boundary
+        const int nd = empty ? 0 : ((bx1 - xs) >> 2) + 1;          // dwords per staged row
+        const int rows = empty ? 0 : by1 - by0 + 1;
+        const bool dal = ((reinterpret_cast<uintptr_t>(dst.data) | (uintptr_t)dst.stride) & 3) == 0;
+        const int X = tx * REMAP_TILE + c4;
+        auto store = [&](int k, uint32_t v) {
+            const int Y = ty * REMAP_TILE + r0 + 16 * k;
+            if (Y >= dst.h || X >= dst.w) return;
+            SVO_GP(uint8_t) drow = dst.gw() + (size_t)Y * dst.stride;
+            if (dal && X + 3 < dst.w) {
+                *(SVO_GP(uint32_t))(drow + X) = v;
+            } else {
+                for (int j = 0; j < 4; j++)
+                    if (X + j < dst.w) drow[X + j] = (uint8_t)(v >> (8 * j));
+            }
+        };
+        if ((long long)rows * nd * 4 <= REMAP_LDS_BYTES) {
+            __syncthreads();                                       // the previous image's gather is done
+            const bool al = ((reinterpret_cast<uintptr_t>(src.data) | (uintptr_t)src.stride) & 3) == 0;
+            SVO_GP(const uint8_t) sp = src.g();
+            for (int idx = lane; idx < rows * nd; idx += REMAP_THREADS) {
+                const int r = idx / nd, d = idx - r * nd;
+                const int col = xs + 4 * d;                        // 0 <= col <= bx1 < src.w
+                SVO_GP(const uint8_t) row = sp + (size_t)(by0 + r) * src.stride;
+                uint32_t v;
+                if (al && col + 3 < src.w) {
+                    v = *(SVO_GP(const uint32_t))(row + col);
+                } else {
+                    v = 0;
+                    for (int j = 0; j < 4; j++)
+                        if (col + j < src.w) v |= (uint32_t)row[col + j] << (8 * j);
+                }
+                s_src[idx] = v;
+            }
+            __syncthreads();
+            const SVO_LDS(uint8_t)* lds = (const SVO_LDS(uint8_t)*)s_src;
+            const int pitch = nd * 4;
+            const unsigned bw = (unsigned)(bx1 - bx0), bh = (unsigned)(by1 - by0);
+            remap_gather(xy, fr, [&](int x, int y) -> int {
+                const bool in = !empty && (unsigned)(x - bx0) <= bw && (unsigned)(y - by0) <= bh;
+                return in ? (int)lds[(y - by0) * pitch + (x - xs)] : 0;
+            }, store);
+        } else {
+            SVO_GP(const uint8_t) sp = src.g();
+            remap_gather(xy, fr, [&](int x, int y) -> int {
+                const bool in = (unsigned)x < (unsigned)src.w && (unsigned)y < (unsigned)src.h;
+                return in ? (int)sp[(size_t)y * src.stride + x] : 0;
+            }, store);
+        }
+    }
+}
+
+void launch_remap_prep(const float* map_x, const float* map_y, const RemapMap& m, hipStream_t stream) {
+    hipLaunchKernelGGL(remap_prep_kernel, dim3(m.tiles_x * m.tiles_y), dim3(REMAP_THREADS), 0, stream, map_x, map_y, m);
+}
+
+void launch_remap(const RemapLaunch& a, int n_sides, hipStream_t stream) {
+    const RemapMap& m = a.map[0];
+    dim3 grid(m.tiles_x * m.tiles_y, (a.n + REMAP_SPB - 1) / REMAP_SPB, n_sides);
+    hipLaunchKernelGGL(remap_linear_kernel, grid, dim3(REMAP_THREADS), 0, stream, a);
+}
+
+}  // namespace svo

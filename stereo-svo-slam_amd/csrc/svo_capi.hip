@@ -8,6 +8,7 @@
 #include <cstring>
 #include <memory>
 #include <new>
+#include <vector>
 
 #include "svo_host.hpp"
 #include "svo_kernels.hpp"
@@ -25,6 +26,8 @@ struct svo_handle {
     int rec_cap;
     DevPtr<KfDev> kf_one;           // 1-entry keyframe table for svo_klt_track
     int exact_pinv = 1;             // reference-order Gauss-Newton by default
+    DevPtr<uint8_t> remap_ws;       // svo_remap_linear: the map in the kernel's form + the image table
+    size_t remap_ws_bytes = 0;
 };
 
 extern "C" const char* svo_last_error(void) { return svo_error_text; }
@@ -165,6 +168,45 @@ extern "C" int svo_build_pyramid(svo_handle* h, int n_levels, svo_image* levels)
     int rc = stage(h, pa, &d);
     if (rc) return rc;
     if (n_levels > 1) launch_pyr_fused(d, 1, levels[0].width, levels[0].height, false, pyr_stream_rows(pa), h->stream);
+    HIP_TRY(hipGetLastError());
+    return SVO_OK;
+}
+
+extern "C" int svo_remap_linear(svo_handle* h, int n, const svo_image* src, svo_image* dst, const float* map_x,
+                                const float* map_y) {
+    CHECK_H(h);
+    if (n < 1 || !src || !dst || !map_x || !map_y)
+        return svo_set_error(SVO_ERR_INVALID, "svo_remap_linear: bad arguments");
+    const int w = dst[0].width, hgt = dst[0].height;
+    if (w < 1 || hgt < 1) return svo_set_error(SVO_ERR_INVALID, "svo_remap_linear: empty map");
+    for (int i = 0; i < n; i++) {
+        if (!src[i].data || !dst[i].data || dst[i].width != w || dst[i].height != hgt || dst[i].stride < w)
+            return svo_set_error(SVO_ERR_INVALID, "svo_remap_linear: image %d: every dst is the map's size", i);
+        if (src[i].width < 1 || src[i].height < 1 || src[i].width > REMAP_MAX_SRC || src[i].height > REMAP_MAX_SRC ||
+            src[i].stride < src[i].width)
+            return svo_set_error(SVO_ERR_INVALID, "svo_remap_linear: image %d: source of 1..%d pixels a side", i, REMAP_MAX_SRC);
+    }
+    const size_t map_bytes = remap_map_bytes(w, hgt);
+    const size_t need = map_bytes + sizeof(RemapImg) * (size_t)n;
+    if (need > h->remap_ws_bytes) {
+        HIP_TRY(hipStreamSynchronize(h->stream));      // (the old workspace may still be read)
+        h->remap_ws.reset();
+        h->remap_ws_bytes = 0;
+        HIP_TRY(dev_malloc(h->remap_ws, need));
+        h->remap_ws_bytes = need;
+    }
+    std::vector<RemapImg> imgs(n);
+    for (int i = 0; i < n; i++) imgs[i] = RemapImg{make_view(src[i]), make_view(dst[i])};
+    RemapImg* d_img = reinterpret_cast<RemapImg*>(h->remap_ws.get() + map_bytes);
+    HIP_TRY(hipMemcpyAsync(d_img, imgs.data(), sizeof(RemapImg) * (size_t)n, hipMemcpyHostToDevice, h->stream));
+    RemapLaunch a;
+    std::memset(&a, 0, sizeof(a));
+    a.map[0] = a.map[1] = remap_map_view(h->remap_ws.get(), w, hgt);
+    launch_remap_prep(map_x, map_y, a.map[0], h->stream);
+    HIP_TRY(hipGetLastError());
+    a.img = d_img;
+    a.n = n;
+    launch_remap(a, 1, h->stream);
     HIP_TRY(hipGetLastError());
     return SVO_OK;
 }

@@ -18,6 +18,7 @@
 
 #include "svo_group.hpp"
 #include "svo_host.hpp"
+#include "svo_kernels.hpp"
 
 // svo_ctx: the public object. Its sequences are split over 1..G groups; a group owns a
 // HIP stream, its argument blocks and (G > 1) a host thread that drives it, so the groups
@@ -49,6 +50,9 @@ struct svo_ctx {
     // latched here, the other groups drop what is still queued, and later submits are rejected.
     std::atomic<bool> failed{false};
     std::vector<std::unique_ptr<Worker>> workers;
+    // svo_ctx_set_rectification: one read-only map set for every group (left, right), or none
+    svo::DevPtr<uint8_t> rect_mem;
+    svo::RemapMap rect[2];
 };
 
 namespace {
@@ -168,6 +172,7 @@ extern "C" int svo_ctx_destroy(svo_ctx* c) {
         }
         w->g.reset();
     }
+    c->rect_mem.reset();                          // (after the groups that read it)
     delete c;
     return SVO_OK;
 }
@@ -222,6 +227,51 @@ extern "C" int svo_new_image(svo_ctx* c, const uint8_t* left, int left_stride, c
     if (width != c->width || height != c->height || left_stride != right_stride)
         return svo_set_error(SVO_ERR_INVALID, "svo_new_image: image size / stride mismatch");
     return grp_new_images(c->workers[0]->g.get(), &left, &right, left_stride, &time_stamp, SVO_MEM_HOST);
+}
+
+extern "C" int svo_ctx_set_rectification(svo_ctx* c, const float* left_map_x, const float* left_map_y,
+                                         const float* right_map_x, const float* right_map_y, int mem) {
+    const float* maps[4] = {left_map_x, left_map_y, right_map_x, right_map_y};
+    const int given = (int)std::count_if(maps, maps + 4, [](const float* p) { return p != nullptr; });
+    if (!c || (given != 0 && given != 4) || (mem != SVO_MEM_HOST && mem != SVO_MEM_DEVICE))
+        return svo_set_error(SVO_ERR_INVALID, "svo_ctx_set_rectification: give all four maps or none, mem host or device");
+    const int rc = ctx_drain(c);                  // (the groups are idle from here on: no frame reads the old maps)
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    if (given == 0) {
+        for (auto& w : c->workers) grp_set_rectification(w->g.get(), nullptr);
+        c->rect_mem.reset();
+        return SVO_OK;
+    }
+    // the new set is built completely before it replaces the old one: a failure leaves the old setting
+    const size_t map_bytes = svo::remap_map_bytes(c->width, c->height);
+    const size_t plane = sizeof(float) * (size_t)c->width * c->height;
+    svo::DevPtr<uint8_t> mem_new;
+    HIP_TRY(svo::dev_malloc(mem_new, 2 * map_bytes + (mem == SVO_MEM_HOST ? 4 * plane : 0)));
+    svo::Stream st;                               // (uploads and conversion ordered on one stream of their own)
+    HIP_TRY(svo::make_stream(st));
+    const float* dev_maps[4];
+    for (int i = 0; i < 4; i++) {
+        if (mem == SVO_MEM_HOST) {
+            float* d = reinterpret_cast<float*>(mem_new.get() + 2 * map_bytes + i * plane);
+            HIP_TRY(hipMemcpyAsync(d, maps[i], plane, hipMemcpyHostToDevice, st.get()));
+            dev_maps[i] = d;
+        } else {
+            dev_maps[i] = maps[i];
+        }
+    }
+    svo::RemapMap rect[2];
+    for (int side = 0; side < 2; side++) {
+        rect[side] = svo::remap_map_view(mem_new.get() + side * map_bytes, c->width, c->height);
+        svo::launch_remap_prep(dev_maps[2 * side], dev_maps[2 * side + 1], rect[side], st.get());
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipStreamSynchronize(st.get()));
+    c->rect[0] = rect[0];
+    c->rect[1] = rect[1];
+    c->rect_mem = std::move(mem_new);             // (frees the previous set)
+    for (auto& w : c->workers) grp_set_rectification(w->g.get(), c->rect);
+    return SVO_OK;
 }
 
 extern "C" int svo_ctx_set_exact_pinv(svo_ctx* c, int on);

@@ -254,6 +254,11 @@ struct svo_group {
     // host-resident input frames land here first (2 x B frames; runs of contiguous frames as one
     // copy) and are then ingested like device-resident ones
     uint8_t* d_stage_in = nullptr; size_t stage_frame_bytes = 0;
+    // rectification (svo_ctx_set_rectification): the ctx's two maps, or null; the image table of its launch
+    // (left images of the active sequences, then their right images) in a pinned block and its device mirror
+    const RemapMap* rect = nullptr;
+    ArgArray<RemapImg> remap_img;
+    PinnedPtr<RemapImg> remap_img_host;
     bool timing = false;
     bool failed = false;
     int exact_pinv = 1;          // reference-order Gauss-Newton unless svo_ctx_set_fast_solver(ctx, 1)
@@ -622,12 +627,16 @@ int grp_create(const svo_camera_settings* cam, int width, int height, int n_sequ
         if ((rc = alloc_sequence(c, c->seqs[s], s))) return rc;
     if ((rc = grow_kf_slabs(c, std::max(2 * n_sequences, 32)))) return rc;   // the first keyframes never allocate
     if ((rc = alloc_template_cache(c))) return rc;
+    HIP_TRY(pinned_malloc(c->remap_img_host, sizeof(RemapImg) * 2 * (size_t)n_sequences));
+    c->remap_img.h = c->remap_img_host.get();
+    if ((rc = dev_alloc(c, &c->remap_img.d, 2 * (size_t)n_sequences))) return rc;
     HIP_TRY(hipDeviceSynchronize());
     *out = std::move(g);
     return SVO_OK;
 }
 
 void grp_set_exact_pinv(svo_group* c, int on) { c->exact_pinv = on != 0; }
+void grp_set_rectification(svo_group* c, const RemapMap* maps) { c->rect = maps; }
 void grp_enable_timing(svo_group* c, int on) { c->timing = on != 0; }
 
 svo_totals grp_totals(const svo_group* c) {
@@ -756,7 +765,19 @@ int pack_pyramids(svo_group* c, Step& s) {
         ImageSet* is = q.cur_set;
         PyrArgs& hs = clear(c->args.pyr.h[j]);
         hs.n_levels = c->cam.max_pyramid_levels;
-        if (s.mem == SVO_MEM_DEVICE_BORROW) {
+        if (c->rect) {
+            // rectification: the raw frames (in place, or from the staging buffer) are remapped into the
+            // set's own level 0 and right image, then the pyramids are built from there (no ingest)
+            is->left[0] = is->own_left0;
+            is->right = is->own_right;
+            const bool host = s.mem == SVO_MEM_HOST;
+            const uint8_t* src_l = host ? c->d_stage_in + (size_t)seq * c->stage_frame_bytes : s.left[seq];
+            const uint8_t* src_r = host ? c->d_stage_in + (size_t)(c->B + seq) * c->stage_frame_bytes : s.right[seq];
+            const int M = (int)s.act.size();
+            c->remap_img.h[j] = RemapImg{ImgView{src_l, c->width, c->height, s.stride}, is->own_left0};
+            c->remap_img.h[M + j] = RemapImg{ImgView{src_r, c->width, c->height, s.stride}, is->own_right};
+            hs.src_left = is->left[0];
+        } else if (s.mem == SVO_MEM_DEVICE_BORROW) {
             // level 0 of both pyramids and the right image ARE the caller's images (like the
             // reference's shallow cv::Mat alias, stereo_slam.cpp:115): nothing is copied
             is->left[0] = ImgView{s.left[seq], c->width, c->height, s.stride};
@@ -870,7 +891,16 @@ int launch_tracking(svo_group* c, const Step& s) {
     hipStream_t st = c->stream.get();
     const int M = (int)s.act.size();
     HIP_TRY(hipMemcpyAsync(a.dev, a.host.get(), s.first ? a.bytes : a.frame_bytes, hipMemcpyHostToDevice, st));
-    launch_pyr_fused(a.pyr.d, M, c->width, c->height, s.mem != SVO_MEM_DEVICE_BORROW, std::max(s.pyr_stream, 0), st);
+    if (c->rect) {
+        HIP_TRY(hipMemcpyAsync(c->remap_img.d, c->remap_img.h, sizeof(RemapImg) * 2 * M, hipMemcpyHostToDevice, st));
+        RemapLaunch ra;
+        ra.map[0] = c->rect[0]; ra.map[1] = c->rect[1];
+        ra.img = c->remap_img.d; ra.n = M;
+        launch_remap(ra, 2, st);
+        HIP_TRY(hipGetLastError());
+    }
+    launch_pyr_fused(a.pyr.d, M, c->width, c->height, !c->rect && s.mem != SVO_MEM_DEVICE_BORROW,
+                     std::max(s.pyr_stream, 0), st);
     HIP_TRY(hipGetLastError());   // (every launch is checked on its own: a later success must not mask a failure)
     if (s.first) return SVO_OK;
     HIP_TRY(mark(c, 1));

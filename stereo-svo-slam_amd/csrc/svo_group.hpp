@@ -7,6 +7,7 @@
 
 #include "../../include/svo_hip.h"
 
+namespace svo { struct RemapMap; }
 struct svo_group;
 struct GroupDelete { void operator()(svo_group* g) const; };   // synchronises the group's stream, then frees all
 using Group = std::unique_ptr<svo_group, GroupDelete>;
@@ -16,6 +17,9 @@ int grp_create(const svo_camera_settings* cam, int width, int height, int n_sequ
 int grp_new_images(svo_group* g, const uint8_t* const* left, const uint8_t* const* right, int stride,
                    const float* time_stamps, int mem);
 void grp_set_exact_pinv(svo_group* g, int on);
+// rectification of every frame from the next one on: maps[0] the left image's, maps[1] the right image's
+// (owned by the ctx, device memory that stays valid while set); nullptr: off
+void grp_set_rectification(svo_group* g, const svo::RemapMap* maps);
 void grp_enable_timing(svo_group* g, int on);
 svo_totals grp_totals(const svo_group* g);
 const std::vector<svo_launch_shape>& grp_launch_shapes(const svo_group* g);   // (svo_ctx_get_launch_shapes)

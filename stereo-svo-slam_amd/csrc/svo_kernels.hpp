@@ -49,6 +49,39 @@ struct PyrArgs {
 void launch_pyr_fused(const PyrArgs* d_args, int batch, int w, int h, bool right_blocks, int stream_rows, hipStream_t stream);
 int pyr_stream_rows(const PyrArgs& host_args);
 
+// ------------------------------------------------------------ rectification (rectify.hip)
+// cv::remap(src, dst, map_x, map_y, INTER_LINEAR), BORDER_CONSTANT 0, 8-bit (src/app/euroc_input.cpp:69-70)
+// in OpenCV's fixed point. A map in the kernels' form: per output pixel, in 64x64 tiles (tile-major, a
+// tile's 4096 entries row by row), the integer source position (sx, sy) as two int16 in one dword and
+// the 5-bit fractions fx | fy << 5; (sx, sy) are clamped to [-2, REMAP_MAX_SRC] (no tap of a clamped
+// entry can fall inside an image of at most REMAP_MAX_SRC pixels a side) and entries without a source
+// (non-finite, |m*32| >= 2^31, tile padding) are (-2, -2). box[t] = x0, x1, y0, y1: the bounding box of
+// every tap of tile t that can fall inside an image (x0, y0 >= 0; x1 < x0: none).
+constexpr int REMAP_TILE = 64;
+constexpr int REMAP_MAX_SRC = 16383;
+struct RemapMap {
+    const uint32_t* xy;
+    const uint16_t* frac;
+    const int4* box;
+    int w, h, tiles_x, tiles_y;
+};
+struct RemapImg {
+    ImgView src, dst;             // dst: w x h of the map
+};
+// `n` images per side; side s of image i: img[s * n + i] through map[s]
+struct RemapLaunch {
+    RemapMap map[2];
+    const RemapImg* img;
+    int n;
+};
+// device bytes of a w x h map in the kernels' form, and its views on `base` (256-byte aligned)
+size_t remap_map_bytes(int w, int h);
+RemapMap remap_map_view(void* base, int w, int h);
+// float maps (device, dense rows of w floats) -> the kernels' form in `m` (its storage, written)
+void launch_remap_prep(const float* map_x, const float* map_y, const RemapMap& m, hipStream_t stream);
+// n_sides = 1: map[0] and img[0..n); 2: both sides in one launch
+void launch_remap(const RemapLaunch& a, int n_sides, hipStream_t stream);
+
 // ------------------------------------------------- sparse image alignment
 struct SiaArgs {
     ImgView prev[SVO_MAX_PYRAMID_LEVELS];

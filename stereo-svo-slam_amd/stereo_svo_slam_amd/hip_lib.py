@@ -29,7 +29,7 @@ SYMBOLS = (
     "svo_device_malloc", "svo_device_free", "svo_copy_to_device", "svo_copy_to_host",
     "svo_copy_image_to_device", "svo_project_keypoints",
     "svo_ctx_get_launch_shapes", "svo_pick_launch_shapes", "svo_pinv6_check",
-    "svo_solve6_check",
+    "svo_solve6_check", "svo_remap_linear", "svo_ctx_set_rectification",
 )
 
 
@@ -152,6 +152,19 @@ class Handle:
         arr = _imgs(levels)
         _check(lib().svo_build_pyramid(self._h, n_levels, arr))
         return levels
+
+    # -- R ----------------------------------------------------------------
+    def remap_linear(self, srcs, map_x, map_y):
+        """cv::remap(src, dst, map_x, map_y, INTER_LINEAR), constant 0 border (src/app/euroc_input.cpp:69-70)
+        of every uint8 device image in `srcs` through one map (float32 [H, W] device tensors): a list of
+        uint8 [H, W] device tensors, bit-exact to OpenCV's fixed-point remap."""
+        assert map_x.shape == map_y.shape and map_x.dim() == 2
+        assert map_x.dtype == torch.float32 and map_y.dtype == torch.float32
+        h, w = map_x.shape
+        map_x, map_y = map_x.contiguous(), map_y.contiguous()
+        outs = [torch.empty((h, w), dtype=torch.uint8, device=map_x.device) for _ in srcs]
+        _check(lib().svo_remap_linear(self._h, len(srcs), _imgs(srcs), _imgs(outs), _ptr(map_x), _ptr(map_y)))
+        return outs
 
     # -- P2 ---------------------------------------------------------------
     def build_lk_pyramid(self, img, win, max_levels=3):

@@ -7,6 +7,7 @@ Host bookkeeping only; every frame goes through StereoSlam.new_image (libsvo_hip
 
     python -m stereo_svo_slam_amd.replay --synthetic euroc --frames 100 -t traj.csv
     python -m stereo_svo_slam_amd.replay --settings EuRoC.yaml --euroc /data/MH_02_easy/mav0/ -t traj.csv
+    python -m stereo_svo_slam_amd.replay --settings EuRoC.yaml --euroc /data/MH_02_easy/mav0/ --gpu-rectify
     python -m stereo_svo_slam_amd.replay --settings Blender.yaml --sbs 'frames/%06d.png' -t traj.csv
     python -m stereo_svo_slam_amd.replay --settings EuRoC.yaml --pairs 'seq/%06d_left.png,seq/%06d_right.png'
 
@@ -121,9 +122,11 @@ class EurocInput:
     """EurocInput (src/app/euroc_input.cpp): `image_path` is the mav0/ directory. cam0/data.csv lists
     time stamps [ns] and file names; the library's `right` image is cam0 rectified with the LEFT.*
     calibration of the settings file, `left` is cam1 rectified with RIGHT.* (:69-70, :100-101); time
-    stamps are seconds since the first frame as float (:104-110)."""
+    stamps are seconds since the first frame as float (:104-110). raw=True: read() hands out the
+    unrectified frames, for the tracker to rectify on the GPU with gpu_maps()."""
 
-    def __init__(self, image_path, settings):
+    def __init__(self, image_path, settings, raw=False):
+        self.raw = raw
         self.right_images, self.left_images, self.timestamps = [], [], []
         t0 = None
         with open(os.path.join(image_path, "cam0", "data.csv")) as fh:
@@ -152,10 +155,17 @@ class EurocInput:
     def read(self, k):
         """(left, right, time_stamp) in the library's naming."""
         cam0, cam1 = _gray(self.right_images[k]), _gray(self.left_images[k])
-        if self.maps_l is not None:
+        if self.maps_l is not None and not self.raw:
             cam0 = remap_linear(cam0, *self.maps_l)      # right <- remap(cam0, M1l, M2l)
             cam1 = remap_linear(cam1, *self.maps_r)      # left  <- remap(cam1, M1r, M2r)
         return cam1, cam0, float(self.timestamps[k])
+
+    def gpu_maps(self):
+        """(left maps, right maps) in the library's naming for StereoSlam.set_rectification: the library's
+        left image is cam1 (RIGHT.* calibration, M1r/M2r), its right image cam0 (LEFT.*, M1l/M2l)."""
+        if self.maps_l is None:
+            raise ValueError("the settings file has no LEFT.* / RIGHT.* rectification matrices")
+        return self.maps_r, self.maps_l
 
 
 class SideBySideInput:
@@ -253,12 +263,15 @@ def error_report(test_rows, reference_rows):
 class Replay:
     """process_image loop: only the time inside new_image is accumulated (slam_app.cpp:186-190)."""
 
-    def __init__(self, settings, device=0, time_trace=False, fast=False):
-        """fast=False keeps the library default: the reference-order Gauss-Newton (bit-exact traces)."""
+    def __init__(self, settings, device=0, time_trace=False, fast=False, rectify_maps=None):
+        """fast=False keeps the library default: the reference-order Gauss-Newton (bit-exact traces).
+        rectify_maps = (left maps, right maps): the frames fed are raw and are rectified on the GPU."""
         self.settings = settings
         self.slam = StereoSlam(settings, device=device)
         if fast:
             self.slam.set_fast_solver(True)
+        if rectify_maps is not None:
+            self.slam.set_rectification(*rectify_maps)
         self.cumulative = []
         self._t = 0.0
         self.time_trace = time_trace
@@ -323,6 +336,8 @@ def main(argv=None):
     ap.add_argument("--fast", action="store_true",
                     help="svo_ctx_set_fast_solver(1): tree sums + LDL^T instead of the default reference-order Gauss-Newton")
     ap.add_argument("--exact", action="store_true", help="no-op (the reference-order mode is the default)")
+    ap.add_argument("--gpu-rectify", action="store_true",
+                    help="--euroc: hand the raw frames to the library and rectify them on the GPU (bit-exact cv::remap)")
     ap.add_argument("--frames", type=int, default=100)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--rate", type=float, default=20.0, help="frames per second of the time stamps")
@@ -331,6 +346,7 @@ def main(argv=None):
     args = ap.parse_args(argv)
 
     gt = None
+    rect = None
     data = os.environ.get("SVO_DATA")
     if data and not (args.synthetic or args.pairs or args.euroc or args.sbs):
         if os.path.exists(os.path.join(data, "cam0", "data.csv")):
@@ -339,7 +355,9 @@ def main(argv=None):
             args.sbs = os.path.join(data, "%06d.png")
     if args.euroc and args.settings:
         settings = read_settings(args.settings)
-        src = EurocInput(args.euroc, args.settings)
+        src = EurocInput(args.euroc, args.settings, raw=args.gpu_rectify)
+        if args.gpu_rectify:
+            rect = src.gpu_maps()
         n = min(args.frames, len(src))
         frames = (src.read(k) for k in range(n))
     elif args.sbs and args.settings:
@@ -355,7 +373,9 @@ def main(argv=None):
         frames = ((*_load_pair(args.pairs, k), k / args.rate) for k in range(args.frames))
     else:
         ap.error("give --synthetic, or --settings with --euroc / --sbs / --pairs (or $SVO_DATA)")
-    rp = Replay(settings, args.device, args.time_trace, args.fast)
+    if args.gpu_rectify and rect is None:
+        ap.error("--gpu-rectify needs --euroc with --settings")
+    rp = Replay(settings, args.device, args.time_trace, args.fast, rectify_maps=rect)
     for left, right, t in frames:
         rp.feed(left, right, t)
     rows = rp.rows()

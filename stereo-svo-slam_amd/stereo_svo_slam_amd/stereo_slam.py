@@ -116,6 +116,40 @@ class StereoSlamBatch:
     def set_exact_pinv(self, on=True):
         self.set_fast_solver(not on)
 
+    def set_rectification(self, left_maps, right_maps):
+        """svo_ctx_set_rectification: from the next frame on the images are RAW and are remapped on the GPU
+        (cv::remap INTER_LINEAR, constant 0 border, bit-exact) before tracking. left_maps / right_maps:
+        (map_x, map_y) of the library's left / right image, float32 [H, W] numpy arrays or CUDA tensors
+        (EurocInput: left <- RIGHT.* calibration, right <- LEFT.*); None, None turns it off."""
+        if left_maps is None and right_maps is None:
+            self._rect = None
+        else:
+            maps = [*left_maps, *right_maps]
+            on_dev = isinstance(maps[0], torch.Tensor)
+            if on_dev:
+                maps = [m.to(dtype=torch.float32).contiguous() for m in maps]
+            else:
+                maps = [np.ascontiguousarray(m, np.float32) for m in maps]
+            self._rect = (maps, on_dev)
+        if self._ctx:                      # (StereoSlam creates its ctx with the first image)
+            self._apply_rectification()
+
+    def _apply_rectification(self):
+        rect = getattr(self, "_rect", None)
+        if rect is None:
+            _check(lib().svo_ctx_set_rectification(self._ctx, None, None, None, None, 0))
+            return
+        maps, on_dev = rect
+        for m in maps:
+            assert tuple(m.shape) == (self.height, self.width), "a rectification map has the ctx size"
+        if on_dev:
+            assert all(m.is_cuda and m.device == self.device for m in maps), "maps on the ctx's GPU"
+            torch.cuda.current_stream(self.device).synchronize()
+            ptrs = [C.c_void_p(m.data_ptr()) for m in maps]
+        else:
+            ptrs = [m.ctypes.data_as(C.c_void_p) for m in maps]
+        _check(lib().svo_ctx_set_rectification(self._ctx, *ptrs, 1 if on_dev else 0))
+
     def enable_timing(self, on=True):
         self._timing = bool(on)
         if self._ctx:                      # (StereoSlam creates its ctx with the first image)
@@ -279,4 +313,6 @@ class StereoSlam(StereoSlamBatch):
                 self.set_fast_solver(True)
             if getattr(self, "_timing", False):
                 self.enable_timing(True)
+            if getattr(self, "_rect", None) is not None:
+                self._apply_rectification()
         self.new_images([left], [right], [time_stamp])
