@@ -131,6 +131,33 @@ int svo_depth_filter_update(svo_handle *h, const svo_kp2d *kps2d, svo_kp3d *kps3
                             float *kf_inv_depth, float *kf_variance,
                             int do_outlier_check, int do_update);
 
+/* F2  CornerDetector::detect_keypoints and detect_keypoints_on_each_level
+ *                                              src/lib/corner_detector.cpp:13-79,
+ *                                              src/lib/depth_calculator.cpp:11-35
+ * One keypoint per grid cell on each of n_levels images (1..SVO_MAX_PYRAMID_LEVELS; host array of views
+ * onto device memory: any width, height, stride >= width and base address); level l uses cells of
+ * (grid_width >> l) x (grid_height >> l). The launch is the tracker's (same kernel shape, same argument
+ * block). cells[l * max_cells + c] (device) receives cell c of level l, cells in row-major order;
+ * counts[l] (device, n_levels ints) the level's cell count: (width / cell width) * (height / cell height).
+ * max_cells >= every level's cell count (svo_detect_shape has the tracker's value for halved levels).
+ * SVO_ERR_INVALID for what has no value in the reference: a level-0 cell outside 4..96 x 4..64
+ * (svo_ctx_create rejects it too), a level whose shifted cell size is 0 (the reference's cell loop does
+ * not end) or whose height is below its cell height (the reference reads past the last row). */
+typedef struct svo_det_cell {
+    float   x, y;               /* pixel of the level                                              */
+    float   score;              /* FAST score or saturated Sobel dx response                       */
+    int32_t type;               /* SVO_KP_FAST / SVO_KP_EDGELET                                    */
+} svo_det_cell;
+int svo_detect_keypoints(svo_handle *h, int n_levels, const svo_image *levels, int grid_width,
+                         int grid_height, int max_cells, svo_det_cell *cells, int32_t *counts);
+/* the shape such a launch runs, without a GPU, for levels that halve from width x height (level l:
+ * width >> l, height >> l): *max_cells = the largest cell count of a level (at least 1: the tracker's
+ * value), *cell_width / *cell_height = the largest cell of the kernel shape chosen, *list_capacity = the
+ * FAST corners of one cell + 1 px that the shape keeps for its score pass (more are scored where they are
+ * found). Any out pointer may be NULL. Same SVO_ERR_INVALID cases as svo_detect_keypoints. */
+int svo_detect_shape(int width, int height, int n_levels, int grid_width, int grid_height,
+                     int *max_cells, int *cell_width, int *cell_height, int *list_capacity);
+
 /* ---- whole tracker: StereoSlam (src/include/stereo_slam.hpp:27-79) --------
  * One svo_ctx owns `n_sequences` independent StereoSlam instances; the sequences of
  * a group share every kernel launch (sequence = a grid dimension);

@@ -343,11 +343,17 @@ __global__ __launch_bounds__(256) void kf_detect_kernel(const DetectArgs* __rest
     }
 }
 
+constexpr DetectShape DET_SMALL = {56, 48, 1024}, DET_LARGE = {DET_MAX_CW, DET_MAX_CH, 2048};
+
+DetectShape detect_pick_shape(int grid_w, int grid_h) {
+    return grid_w <= DET_SMALL.cell_w && grid_h <= DET_SMALL.cell_h ? DET_SMALL : DET_LARGE;
+}
+
 void launch_detect(const DetectArgs* d_args, int batch, int max_cells, int n_levels, int grid_w, int grid_h, hipStream_t stream) {
-    if (grid_w <= 56 && grid_h <= 48)
-        hipLaunchKernelGGL((kf_detect_kernel<56, 48, 1024>), dim3(max_cells, n_levels, batch), dim3(256), 0, stream, d_args);
+    if (detect_pick_shape(grid_w, grid_h).cell_w == DET_SMALL.cell_w)
+        hipLaunchKernelGGL((kf_detect_kernel<DET_SMALL.cell_w, DET_SMALL.cell_h, DET_SMALL.list>), dim3(max_cells, n_levels, batch), dim3(256), 0, stream, d_args);
     else
-        hipLaunchKernelGGL((kf_detect_kernel<DET_MAX_CW, DET_MAX_CH, 2048>), dim3(max_cells, n_levels, batch), dim3(256), 0, stream, d_args);
+        hipLaunchKernelGGL((kf_detect_kernel<DET_LARGE.cell_w, DET_LARGE.cell_h, DET_LARGE.list>), dim3(max_cells, n_levels, batch), dim3(256), 0, stream, d_args);
 }
 
 // --------------------------------------------------------- select + merge

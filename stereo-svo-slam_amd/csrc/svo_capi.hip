@@ -12,6 +12,7 @@
 
 #include "svo_host.hpp"
 #include "svo_kernels.hpp"
+#include "svo_tracker.hpp"
 
 using namespace svo;
 
@@ -392,6 +393,77 @@ extern "C" int svo_depth_filter_update(svo_handle* h, const svo_kp2d* kps2d, svo
     rc = stage(h, fa, &d);
     if (rc) return rc;
     launch_filter(d, 1, n, h->stream);
+    HIP_TRY(hipGetLastError());
+    return SVO_OK;
+}
+
+// what CornerDetector::detect_keypoints has no value for: see include/svo_hip.h
+static int check_detect_levels(const char* who, int n_levels, int grid_width, int grid_height) {
+    if (n_levels < 1 || n_levels > SVO_MAX_PYRAMID_LEVELS)
+        return svo_set_error(SVO_ERR_INVALID, "%s: n_levels must be 1..%d", who, SVO_MAX_PYRAMID_LEVELS);
+    if (grid_width < 4 || grid_height < 4 || grid_width > 96 || grid_height > 64)
+        return svo_set_error(SVO_ERR_INVALID, "%s: grid cell must be within 4..96 x 4..64", who);
+    if ((grid_width >> (n_levels - 1)) == 0 || (grid_height >> (n_levels - 1)) == 0)
+        return svo_set_error(SVO_ERR_INVALID, "%s: the cell of level %d is empty", who, n_levels - 1);
+    return SVO_OK;
+}
+static int detect_level_cells(const char* who, int l, int width, int height, int grid_width, int grid_height, int* cells) {
+    const int gw = grid_width >> l, gh = grid_height >> l;
+    if (width < 1 || height < gh)
+        return svo_set_error(SVO_ERR_INVALID, "%s: level %d (%d x %d) is lower than its cell (%d x %d)", who, l, width, height, gw, gh);
+    *cells = (width / gw) * (height / gh);
+    return SVO_OK;
+}
+
+extern "C" int svo_detect_shape(int width, int height, int n_levels, int grid_width, int grid_height, int* max_cells,
+                                int* cell_width, int* cell_height, int* list_capacity) {
+    int rc = check_detect_levels("svo_detect_shape", n_levels, grid_width, grid_height);
+    if (rc) return rc;
+    int most = 1;
+    for (int l = 0; l < n_levels; l++) {
+        int nc;
+        if ((rc = detect_level_cells("svo_detect_shape", l, width >> l, height >> l, grid_width, grid_height, &nc))) return rc;
+        most = std::max(most, nc);
+    }
+    const DetectShape s = detect_pick_shape(grid_width, grid_height);
+    if (max_cells) *max_cells = most;
+    if (cell_width) *cell_width = s.cell_w;
+    if (cell_height) *cell_height = s.cell_h;
+    if (list_capacity) *list_capacity = s.list;
+    return SVO_OK;
+}
+
+static_assert(sizeof(svo_det_cell) == sizeof(DetCell) && offsetof(svo_det_cell, score) == offsetof(DetCell, score) &&
+              offsetof(svo_det_cell, type) == offsetof(DetCell, type), "svo_det_cell is the kernel's DetCell");
+
+extern "C" int svo_detect_keypoints(svo_handle* h, int n_levels, const svo_image* levels, int grid_width, int grid_height,
+                                    int max_cells, svo_det_cell* cells, int32_t* counts) {
+    CHECK_H(h);
+    if (!levels || !cells || !counts || max_cells < 1)
+        return svo_set_error(SVO_ERR_INVALID, "svo_detect_keypoints: bad arguments");
+    int rc = check_detect_levels("svo_detect_keypoints", n_levels, grid_width, grid_height);
+    if (rc) return rc;
+    DetectArgs da;
+    memset(&da, 0, sizeof(da));
+    for (int l = 0; l < n_levels; l++) {
+        if (!levels[l].data || levels[l].stride < levels[l].width)
+            return svo_set_error(SVO_ERR_INVALID, "svo_detect_keypoints: level %d: no data or stride < width", l);
+        int nc;
+        if ((rc = detect_level_cells("svo_detect_keypoints", l, levels[l].width, levels[l].height, grid_width, grid_height, &nc)))
+            return rc;
+        if (nc > max_cells)
+            return svo_set_error(SVO_ERR_CAPACITY, "svo_detect_keypoints: level %d has %d cells, max_cells = %d", l, nc, max_cells);
+        da.level[l] = make_view(levels[l]);
+    }
+    da.n_levels = n_levels; da.grid_w = grid_width; da.grid_h = grid_height;
+    da.out = reinterpret_cast<DetCell*>(cells); da.n_out = counts; da.max_cells = max_cells;
+    // (a level narrower than its cell has no cells and no workgroup that writes its count: the tracker clears the
+    // counters in the compaction kernel that precedes the detection)
+    HIP_TRY(hipMemsetAsync(counts, 0, sizeof(int32_t) * (size_t)n_levels, h->stream));
+    DetectArgs* d;
+    rc = stage(h, da, &d);
+    if (rc) return rc;
+    launch_detect(d, 1, max_cells, n_levels, grid_width, grid_height, h->stream);
     HIP_TRY(hipGetLastError());
     return SVO_OK;
 }

@@ -300,13 +300,19 @@ T& clear(T& x) {
     return x;
 }
 
-// `count` elements of T (at least one byte's worth), owned by the group; `zero`: cleared first
+// `count` elements of T (at least one byte's worth), owned by the group; `zero`: cleared first. The clearing is
+// complete on return: hipMemset of device memory only enqueues on the null stream, which the group's
+// non-blocking stream does not wait for, and the staging buffer of host frames is allocated and filled in
+// the same step (a first host frame arrived with patches of it zeroed, about once in a hundred ctxs).
 template <typename T>
 int dev_alloc(svo_group* c, T** p, size_t count, bool zero = true) {
     const size_t bytes = sizeof(T) * std::max<size_t>(count, 1);
     DevPtr<void> q;
     HIP_TRY(dev_malloc(q, bytes));
-    if (zero) HIP_TRY(hipMemset(q.get(), 0, bytes));
+    if (zero) {
+        HIP_TRY(hipMemsetAsync(q.get(), 0, bytes, nullptr));
+        HIP_TRY(hipStreamSynchronize(nullptr));
+    }
     *p = static_cast<T*>(q.get());
     c->dev_mem.push_back(std::move(q));
     return SVO_OK;

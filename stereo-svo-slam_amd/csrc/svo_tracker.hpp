@@ -53,6 +53,9 @@ struct DetectArgs {
 };
 // grid_w x grid_h: the level-0 cell of the launch's sequences (chooses the kernel shape)
 void launch_detect(const DetectArgs* d_args, int batch, int max_cells, int n_levels, int grid_w, int grid_h, hipStream_t stream);
+// the kernel shape launch_detect runs for that cell: its largest cell and the corners (of a cell + 1 px) its LDS list holds
+struct DetectShape { int cell_w, cell_h, list; };
+DetectShape detect_pick_shape(int grid_w, int grid_h);
 
 struct MergeArgs {
     svo_camera_settings cam;

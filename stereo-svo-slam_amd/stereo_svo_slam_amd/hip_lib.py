@@ -30,6 +30,7 @@ SYMBOLS = (
     "svo_copy_image_to_device", "svo_project_keypoints",
     "svo_ctx_get_launch_shapes", "svo_pick_launch_shapes", "svo_pinv6_check",
     "svo_solve6_check", "svo_remap_linear", "svo_ctx_set_rectification",
+    "svo_detect_keypoints", "svo_detect_shape",
 )
 
 
@@ -66,6 +67,10 @@ GN_TRACE_DTYPE = np.dtype([("level", "<i4"), ("n_gradient", "<i4"), ("n_cost", "
 assert GN_TRACE_DTYPE.itemsize == 52
 
 
+DET_CELL_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("score", "<f4"), ("type", "<i4")])
+assert DET_CELL_DTYPE.itemsize == 16
+
+
 def lib():
     """Load libsvo_hip.so; fail loudly when it has not been built."""
     global _LIB
@@ -94,6 +99,14 @@ def _ptr(t):
 def _img(t):
     assert t.dtype == torch.uint8 and t.dim() == 2 and t.is_cuda and t.stride(1) == 1
     return Image(t.data_ptr(), t.shape[1], t.shape[0], t.stride(0))
+
+
+def detect_shape(width, height, n_levels, grid_width, grid_height):
+    """svo_detect_shape (host only): (max_cells, cell_width, cell_height, list_capacity) of the detection
+    launch for levels that halve from width x height."""
+    out = [C.c_int(0) for _ in range(4)]
+    _check(lib().svo_detect_shape(width, height, n_levels, grid_width, grid_height, *[C.byref(o) for o in out]))
+    return tuple(o.value for o in out)
 
 
 def _imgs(ts, n=None):
@@ -152,6 +165,23 @@ class Handle:
         arr = _imgs(levels)
         _check(lib().svo_build_pyramid(self._h, n_levels, arr))
         return levels
+
+    # -- F2 ---------------------------------------------------------------
+    def detect_keypoints(self, levels, grid_width, grid_height, max_cells=None):
+        """CornerDetector::detect_keypoints on every level (uint8 device tensors or views with unit column
+        stride; level l uses the cell (grid_width >> l) x (grid_height >> l)). Returns (cells, counts):
+        cells [n_levels, max_cells] device bytes viewed as DET_CELL_DTYPE by detect_to_numpy, counts [n_levels]
+        int32 device."""
+        n = len(levels)
+        if max_cells is None:
+            max_cells = max([1] + [(t.shape[1] // max(grid_width >> l, 1)) * (t.shape[0] // max(grid_height >> l, 1))
+                                   for l, t in enumerate(levels)])
+        dev = levels[0].device
+        cells = torch.zeros((n, max_cells, DET_CELL_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+        counts = torch.full((n,), -1, dtype=torch.int32, device=dev)
+        _check(lib().svo_detect_keypoints(self._h, n, _imgs(levels), grid_width, grid_height, max_cells,
+                                          _ptr(cells), _ptr(counts)))
+        return cells, counts
 
     # -- R ----------------------------------------------------------------
     def remap_linear(self, srcs, map_x, map_y):
@@ -264,6 +294,12 @@ class Handle:
             self._h, _ptr(kps2d), _ptr(kps3d), _ptr(flags), n, C.byref(cam), _ptr(frame_pose),
             _ptr(disparity), _ptr(ref3d), _ptr(ref2d), _ptr(kf_pose), _ptr(outlier), _ptr(inlier),
             _ptr(kf_x), _ptr(kf_p), do_outlier_check, do_update))
+
+
+def detect_to_numpy(cells, counts):
+    """Per level the structured array (DET_CELL_DTYPE) of its cells, from Handle.detect_keypoints' outputs."""
+    c = cells.cpu().numpy().view(DET_CELL_DTYPE)[..., 0]
+    return [c[l, :k].copy() for l, k in enumerate(counts.cpu().numpy())]
 
 
 def trace_to_numpy(t):

@@ -246,6 +246,24 @@ def test_launch_shape_edges():
     assert pick_launch_shapes(e, 1, 5200)[1] is None                      # the reprojection's LDS copy: 120 KB
 
 
+def test_detect_shape_and_what_it_rejects():
+    """svo_detect_shape (host only): the tracker's cell maximum over halved levels, the kernel shape's largest
+    cell and corner list; no value for cells outside 4..96 x 4..64, an empty shifted cell, a level lower than
+    its cell"""
+    ds = hip_lib.detect_shape
+    assert ds(752, 480, 3, 54, 48) == (140, 56, 48, 1024)          # (level 2: 14 x 10 cells of 13 x 12)
+    assert ds(752, 480, 2, 56, 48) == (130, 56, 48, 1024)
+    assert ds(752, 480, 2, 57, 48)[1:] == ds(752, 480, 2, 56, 49)[1:] == (96, 64, 2048)
+    assert ds(752, 480, 2, 75, 48) == (100, 96, 64, 2048) and ds(752, 480, 3, 96, 64) == (49, 96, 64, 2048)
+    assert ds(320, 240, 2, 4, 4)[0] == 4800 and ds(16, 16, 3, 4, 4)[0] == 16
+    assert ds(15, 16, 1, 16, 16)[0] == 1                       # no cell at all: the tracker's minimum of 1
+    for bad in ((752, 480, 1, 3, 48), (752, 480, 1, 54, 3), (752, 480, 1, 97, 48), (752, 480, 1, 54, 65),
+                (752, 480, 4, 4, 4), (752, 480, 0, 54, 48), (752, 480, 9, 54, 48), (752, 47, 1, 54, 48),
+                (64, 33, 2, 8, 34)):
+        with pytest.raises(hip_lib.SvoError):
+            ds(*bad)
+
+
 def test_timed_steps_runs_finish_fn_inside_the_timed_region():
     """Queued steps (svo_submit_images) are drained by finish_fn before the clock stops: once after
     the warm-up steps and once after the timed ones."""

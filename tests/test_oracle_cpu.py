@@ -308,3 +308,102 @@ def test_golden_sequence():
         assert np.array_equal(slam.pose(), s[f"f{k}_pose"])
         assert np.array_equal(k2, s[f"f{k}_kps2d"]) and np.array_equal(k3, s[f"f{k}_kps3d"])
         assert np.array_equal(info, s[f"f{k}_info"])
+
+
+# ------------------------------------------------- the keyframe path's detector
+def test_numpy_fast_statement_against_brute_force():
+    """tests/keyframe_cases.py states FAST in closed form (largest over the arcs of the smallest difference);
+    here it meets the arc test tried threshold by threshold, on small patches of the crafted textures"""
+    import keyframe_cases as K
+    ring = K.RING
+
+    def is_corner(img, y, x, t):
+        d = [int(img[y, x]) - int(img[y + dy, x + dx]) for dx, dy in ring]
+        return any(all(d[(s + i) % 16] > t for i in range(9)) or all(d[(s + i) % 16] < -t for i in range(9))
+                   for s in range(16))
+
+    corners = 0
+    for name in ("noise", "saturated", "lowc7", "bowls", "half_lr", "dots4"):
+        img = K.texture(name, 22, 26)
+        raw = np.zeros(img.shape, np.uint8)
+        for y in range(3, 19):
+            for x in range(3, 23):
+                t = 5
+                while t < 255 and is_corner(img, y, x, t + 1):
+                    t += 1
+                raw[y, x] = t if t >= 6 else 0
+        assert np.array_equal(K.fast_raw(img), raw), name
+        corners += int((raw > 0).sum())
+    assert corners > 100
+
+
+@pytest.mark.parametrize("grid", [(40, 40), (16, 16), (5, 7)])
+def test_detect_keypoints_against_numpy_statement(grid):
+    """O.detect_keypoints against corner_detector.cpp:27-78 written with numpy (closed-form FAST, scipy Sobel,
+    explicit cell loops) on every crafted texture, ties for the best score included"""
+    import keyframe_cases as K
+    gw, gh = grid
+    fast_ties = edge_ties = types = 0
+    for name in K.TEXTURES:
+        img = K.texture(name, 120, 160, gw, gh)
+        nms, edge = K.fast_nms(K.fast_raw(img)), K.sobel_u8(img)
+        assert np.array_equal(O.fast_score_nms(img, 6), nms), name
+        assert np.array_equal(O.sobel_x_u8(img), edge), name
+        kps, score, typ = O.detect_keypoints(img, gw, gh, 0)
+        rk, rs, rt = K.detect_ref(img, gw, gh, nms, edge)
+        assert len(kps) == (160 // gw) * (120 // gh)
+        assert np.array_equal(kps, rk) and np.array_equal(score, rs) and np.array_equal(typ, rt), name
+        fast_ties += len(K.tie_cells(nms, gw, gh))
+        edge_ties += sum(1 for j, i in K.tie_cells(edge, gw, gh) if nms[j * gh:(j + 1) * gh, i * gw:(i + 1) * gw].max() == 0)
+        types |= (1 << K.FAST if (typ == K.FAST).any() else 0) | (1 << K.EDGELET if (typ == K.EDGELET).any() else 0)
+    assert types == 3
+    if grid == (40, 40):                       # cells whose first best pixel depends on the scan order
+        assert fast_ties > 0 and edge_ties > 0
+
+
+def test_detect_keypoints_on_other_sizes_against_numpy_statement():
+    import keyframe_cases as K
+    for (w, h), (gw, gh) in (((203, 131), (43, 27)), ((16, 16), (4, 4)), ((16, 16), (16, 16)), ((113, 97), (54, 48)),
+                             ((99, 64), (96, 64)), ((7, 9), (5, 7))):
+        for name in ("noise", "binary", "const77", "checker7", "half_tb"):
+            img = K.texture(name, h, w, gw, gh)
+            for a, b in zip(O.detect_keypoints(img, gw, gh, 0), K.detect_ref(img, gw, gh)):
+                assert np.array_equal(a, b), (w, h, gw, gh, name)
+
+
+# first frame of O.Slam on crafted images (right = left rolled by 7 px): corners in the densest cell + 1 px
+# (numpy), keypoints kept, cells, [FAST, edgelet], keypoints per level. Recorded from this oracle: they say
+# when the oracle moves, and how far simple textures are from what a rendered frame reaches.
+FIRST_FRAME_ANSWERS = [
+    ("euroc", {}, "noise", 1047, 121, 130, [121, 0], [121, 0, 0]),
+    ("euroc", {}, "bowls", 1652, 99, 130, [99, 0], [99, 0, 0]),
+    ("euroc", {}, "const77", 0, 96, 130, [0, 96], [0, 0, 96]),
+    ("euroc", {}, "half_lr", 1033, 115, 130, [102, 13], [66, 0, 49]),
+    ("blender", {}, "noise", 1431, 93, 100, [93, 0], [93, 0, 0]),
+    ("blender", {}, "bowls", 2288, 90, 100, [90, 0], [90, 0, 0]),
+    ("euroc", {"grid_width": 96, "grid_height": 64}, "noise", 2376, 47, 49, [47, 0], [47, 0, 0]),
+    ("euroc", {"grid_width": 96, "grid_height": 64}, "bowls", 3812, 20, 49, [20, 0], [20, 0, 0]),
+    ("tiny", {}, "const77", 0, 0, 48, [0, 0], [0, 0, 0]),
+    ("tiny", {}, "ramp_x", 0, 0, 48, [0, 0], [0, 0, 0]),
+    ("tiny", {}, "stripes_x", 0, 0, 48, [0, 0], [0, 0, 0]),
+    ("tiny", {}, "checker7", 0, 17, 48, [7, 10], [0, 17, 0]),
+    ("tiny", {"grid_width": 4, "grid_height": 4}, "noise", 21, 2624, 4800, [2512, 112], [2534, 90, 0]),
+]
+
+
+@pytest.mark.parametrize("config,over,name,densest,n_kps,n_cells,types,levels", FIRST_FRAME_ANSWERS,
+                         ids=[f"{a[0]}-{a[1].get('grid_width', '')}-{a[2]}" for a in FIRST_FRAME_ANSWERS])
+def test_first_frame_known_answers(config, over, name, densest, n_kps, n_cells, types, levels):
+    import keyframe_cases as K
+    cfg = dict(synth.CONFIGS[config])
+    cfg.update(over)
+    gw, gh, w, h = cfg["grid_width"], cfg["grid_height"], cfg["width"], cfg["height"]
+    img = K.texture(name, h, w, gw, gh)
+    assert int(K.corners_per_cell(img, gw, gh).max()) == densest
+    slam = O.Slam(util.oracle_camera(cfg))
+    assert slam.new_image(img, np.roll(img, 7, axis=1), 0.0) == 1 and slam.num_keyframes() == 1
+    k2, k3, info = slam.keypoints()
+    assert (len(k2), (w // gw) * (h // gh)) == (n_kps, n_cells)
+    assert np.bincount(info["type"], minlength=2).tolist() == types
+    assert np.bincount(info["level"], minlength=3).tolist() == levels
+    assert np.array_equal(slam.pose(), np.zeros(6, np.float32))

@@ -39,3 +39,33 @@ def flags_of(info):
 def real_pair():
     d = np.load(__import__("os").path.join(GOLDEN, "stereo_pair.npz"))
     return d["left"], d["right"]
+
+
+# ---- frame comparison of the whole-tracker tests (HIP ctx against oracle_py.Slam)
+INT_FIELDS = ("level", "type", "keyframe_id", "keypoint_index", "ignore_during_refinement",
+              "ignore_completely", "ignore_temporary", "outlier_count", "inlier_count")
+
+
+def compare_frame(tag, gpu_frame, ok2, ok3, oinfo, pose_ref, tol=1e-4):
+    assert len(gpu_frame.kps2d) == len(ok2), f"{tag}: keypoint count {len(gpu_frame.kps2d)} vs {len(ok2)}"
+    for f in INT_FIELDS:                                   # feature index lists: bit exact
+        assert np.array_equal(gpu_frame.info[f], oinfo[f]), f"{tag}: info.{f}"
+    assert np.array_equal(gpu_frame.info["score"], oinfo["score"]), f"{tag}: score"
+    if tol == 0.0:                                           # reference-order mode: the oracle's floats
+        assert np.array_equal(gpu_frame.pose, pose_ref), (tag, gpu_frame.pose, pose_ref)
+        assert np.array_equal(gpu_frame.kps2d, ok2) and np.array_equal(gpu_frame.kps3d, ok3), tag
+        return
+    assert np.max(np.abs(gpu_frame.pose - pose_ref)) < tol, (tag, gpu_frame.pose, pose_ref)
+    if len(ok2):
+        assert np.max(np.abs(gpu_frame.kps2d - ok2)) < 5e-2, f"{tag}: kps2d"
+        assert np.max(np.abs(gpu_frame.kps3d - ok3)) < 5e-3, f"{tag}: kps3d"
+
+
+def same_trace(a, b, cfg):
+    """GN control flow of one frame: gradient / cost / accepted counts per alignment level and
+    of the reprojection GN, HIP (svo_frame_stats) against the oracle."""
+    pairs = [(a.sia_trace[lv], b.sia_trace[lv])
+             for lv in range(cfg["min_pyramid_level_pose_estimation"], cfg["max_pyramid_levels"])]
+    pairs.append((a.reproj_trace, b.reproj_trace))
+    return all((x.n_gradient, x.n_cost, x.n_accepted, x.exit_small) ==
+               (y.n_gradient, y.n_cost, y.n_accepted, y.exit_small) for x, y in pairs)
