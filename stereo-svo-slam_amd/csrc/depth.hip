@@ -5,8 +5,8 @@
 //    and the identical loop of DepthCalculator::calculate_depth
 //    (depth_calculator.cpp:200-240). One workgroup per keypoint; template and
 //    search region live in LDS; exact int32 SSD (cv::matchTemplate TM_SQDIFF),
-//    first-minimum argmin in row-major order (cv::minMaxLoc) and the
-//    tie-averaged column of :313-323.
+//    first minimum of the float map in row-major order (cv::minMaxLoc) and
+//    the tie-averaged column of :313-323.
 //  * filter_update_kernel (C2, D1, D3): outlier_check (:52-128),
 //    update_kps3d (:130-257), the flag/write-back loop of
 //    StereoSlam::new_image (src/lib/stereo_slam.cpp:205-229) and the counter
@@ -82,7 +82,9 @@ typedef int ssd_v4i __attribute__((ext_vector_type(4)));
 //    Any k-order inside the instruction is fine as long as A and B agree: lane l holds bytes
 //    16*(l>>4) .. +15 of its row / column for both operands.
 //  * sum_w R^2: sliding window sums, columns first (one thread per region column), then rows.
-//  * argmin (first minimum in row-major order) and the tie-averaged column of :313-323 as before.
+//  * argmin: cv::minMaxLoc runs on matchTemplate's CV_32F result, so it is the first minimum in row-major
+//    order of the map ROUNDED TO FLOAT (two integers above 2^24 that round to one float tie, and the earlier
+//    wins); the key is (bits of (float)SSD, index). Then the tie-averaged column of :313-323.
 // SSD_MAX_WIN / SSD_MAX_MH: what the LDS is sized for. The window kernels of a step share each CU's 160 KB with
 // the alignment kernel's 38 KB per wavefront, and what fits is what runs: the shape for windows up to 31 and
 // search_y up to 6 (every configuration of the reference) takes 14.9 KB instead of 18.2.
@@ -253,10 +255,12 @@ __global__ __launch_bounds__(SSD_THREADS) void ssd_disparity_kernel(const SsdArg
     const int nm = mw * mh;
     unsigned long long best = ~0ull;
     for (int o = tid; o < nm; o += SSD_THREADS) {
-        const unsigned long long key = ((unsigned long long)(unsigned)s_m[o] << 32) | (unsigned)o;
+        const unsigned long long key = ((unsigned long long)__float_as_uint((float)s_m[o]) << 32) | (unsigned)o;
         best = key < best ? key : best;
     }
-    // first minimum in row-major order == smallest (value, index) key
+    // first minimum of the FLOAT map in row-major order == smallest (float bits, index) key: an SSD is not
+    // negative, and non-negative floats order like their bit patterns. Above 2^24 different integers round to
+    // one float, and cv::minMaxLoc sees the floats: the earlier position wins, not the smaller integer.
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) {
         const unsigned long long other = __shfl_xor(best, o, 64);
@@ -266,10 +270,9 @@ __global__ __launch_bounds__(SSD_THREADS) void ssd_disparity_kernel(const SsdArg
     __syncthreads();
     best = s_key[0];
     for (int w = 1; w < SSD_THREADS / 64; w++) best = s_key[w] < best ? s_key[w] : best;
-    const int min_int = (int)(best >> 32);
     const int min_o = (int)(best & 0xffffffffu);
     const int minx = min_o % mw, miny = min_o / mw;
-    const float minVal = (float)min_int;
+    const float minVal = __uint_as_float((unsigned)(best >> 32));
 
     int sumj = 0, cnt = 0;
     // o / mw without an integer division: exact for o * mw < 2^20 (the map has at most 65 x 17 entries)

@@ -12,6 +12,7 @@ from scipy.spatial.transform import Rotation
 import oracle_py as O
 from stereo_svo_slam_amd import synth
 import util
+import window_cases
 
 
 def crc(a):
@@ -173,21 +174,9 @@ def test_ssd_disparity_brute_force():
     kps = np.float32([[30.4, 30.9], [3, 3], [88, 58], [45, 10]])
     win, sx, sy = 11, 12, 2
     got = O.ssd_disparity(left, right, kps, win, sx, sy, 1)
-    wb, wa = win // 2, (win + 1) // 2
-    for i, (kx, ky) in enumerate(kps):
-        x, y = int(kx), int(ky)
-        x11, x12 = max(0, x - wb), min(89, x + wa)
-        y11, y12 = max(0, y - wb), min(60, y + wa)
-        x22 = min(89, x + wa + sx)
-        y21, y22 = max(0, y - wb - sy), min(59, y + wa + sy)
-        t = left[y11:y12, x11:x12].astype(np.int64)
-        roi = right[y21:y22, x11:x22].astype(np.int64)
-        mh, mw = roi.shape[0] - t.shape[0] + 1, roi.shape[1] - t.shape[1] + 1
-        m = np.array([[((roi[k:k + t.shape[0], j:j + t.shape[1]] - t) ** 2).sum() for j in range(mw)]
-                      for k in range(mh)]).astype(np.float32)
-        ky0, kx0 = np.unravel_index(np.argmin(m), m.shape)
-        sel = [j for j in range(kx0, mw) for k in range(ky0, mh) if m[k, j] <= m[ky0, kx0]]
-        assert got[i] == max(0.5, np.float32(sum(sel)) / len(sel))
+    ref = window_cases.ssd_ref(left, right, kps, win, sx, sy, 1)     # brute-force int64 map, first float minimum
+    for i in range(len(kps)):
+        assert got[i] == ref["disparity"][i]
     assert got[0] == 5.0
 
 
