@@ -289,6 +289,9 @@ int svo_ctx_get_launch_shapes(svo_ctx *ctx, svo_launch_shape *out, int max, int 
  * mode), out[1] the reprojection GN; launches = 1 if the keypoints fit the kernel, else 0 */
 int svo_pick_launch_shapes(const svo_camera_settings *cam, int width, int height, int batch, int n_bound,
                            int rec_cap, int exact, svo_launch_shape out[2]);
+/* the dynamic LDS (bytes per workgroup) the alignment kernel of that launch asks for (out[0] above) */
+int svo_pick_sia_lds_bytes(const svo_camera_settings *cam, int width, int height, int batch, int n_bound,
+                           int rec_cap, int exact, int64_t *lds_bytes);
 
 /* ---- diagnostics (tests, not the tracking path) ----
  * n pseudo-inverses of 6x6 float systems H_dev[n][36] (row major, device) through the Jacobi SVD of

@@ -25,8 +25,10 @@
 //     (:112-117; v_readlane adds for one wave, an LDS pass otherwise): the stop test |dcost| < 1
 //     is exact. The normal equations have two forms: the DEFAULT accumulates hessian += row^T row
 //     and residual -= row * diff row by row in storage order (:399-403, :472-477) — 64 keypoints
-//     stage their rows in LDS, 27 accumulator lanes walk them, four keypoints per trip (with four
-//     waves: wave 0 only adds while the others compute and stage the next keypoints, two buffers) —
+//     stage their rows in LDS, 27 accumulator lanes walk them, four keypoints per trip (the batched
+//     one-wave shape: 32 keypoints, every lane staging half of a keypoint's rows, two per trip — 18 KB of
+//     LDS and under 256 registers; with four waves: wave 0 only adds while the others compute and stage
+//     the next keypoints, two buffers) —
 //     and inverts by the Jacobi SVD, so the whole iteration trace is the reference's; the fast solver
 //     (svo_*_set_fast_solver) builds sum_kp J^T (sum_px g g^T) J with a wave reduction and solves
 //     by LDL^T.
@@ -75,16 +77,20 @@ __device__ inline float patch_sum_lds(const LevelImg<BIG>& im, float cx, float c
 // Dynamic LDS of one workgroup (byte offsets). cap = keypoint capacity (multiple of 64),
 // T = threads. Per keypoint: 9 floats (point, last projection, sum g g^T, active) and the
 // 64 per-pixel records, all struct-of-arrays with the keypoint index fastest (conflict free).
-#ifndef SVO_SIA_STG
-#define SVO_SIA_STG 64
+// keypoints whose rows are staged at a time in reference-order mode: 64 (one per lane), except in the batched
+// one-wave shape (T == 64, MODE 2), where LDS is what the window kernels of the other sequence groups wait for:
+// 32-keypoint chunks, every lane staging half of a keypoint's rows (18 instead of 36 KB per sequence)
+// (diagnostic builds: -DSVO_SIA_STG1=64 keeps 64 there, tools/build_variants.sh)
+#ifndef SVO_SIA_STG1
+#define SVO_SIA_STG1 32
 #endif
-// keypoints whose rows are staged at a time in reference-order mode: 64; the one-wave shape can be built with 32
-// (-DSVO_SIA_STG=32: 18 instead of 36 KB of LDS per sequence, two staging rounds per pass)
-__host__ __device__ constexpr int sia_stg(int T) { return T == 64 ? SVO_SIA_STG : 64; }
+__host__ __device__ constexpr int sia_stg(int T, int mode) { return T == 64 && mode == 2 ? SVO_SIA_STG1 : 64; }
+// keypoints per trip of the ordered accumulation (their LDS reads are in flight together: 32 registers each). Two
+// keep the batched one-wave shape within 256 registers, i.e. two of its waves or one and KLT waves on a SIMD
 #ifndef SVO_SIA_ACC_U
-#define SVO_SIA_ACC_U 4
+#define SVO_SIA_ACC_U 2
 #endif
-constexpr int SIA_ACC_U = SVO_SIA_ACC_U;   // keypoints per trip of the ordered accumulation (their LDS reads are in flight together)    // keypoints whose rows are staged at a time in reference-order mode
+__host__ __device__ constexpr int sia_acc_u(int T, int mode) { return T == 64 && mode == 2 ? SVO_SIA_ACC_U : 4; }
 enum { KF_PX = 0, KF_PY, KF_PZ, KF_QX, KF_QY, KF_GXX, KF_GXY, KF_GYY, KF_ACT, KF_COUNT };
 enum { REC_I1 = 0, REC_PS = 1, REC_G0 = 2, REC_G1 = 3 };
 struct SiaLds {
@@ -99,7 +105,7 @@ __host__ __device__ inline SiaLds sia_lds_layout(int img_bytes, int cap, int T, 
     l.rec = off;   off += mode == 2 ? 0 : (size_t)(mode == 1 ? 16 : 64) * cap * 4;
     l.sums = off;  off += (size_t)(T / 64) * 32 * 4 + 32;              // [WAVES][32] + the step wave 0 hands to the others
     // 7 planes of SIA_STG keypoints' rows (20 floats each); several waves per sequence fill two of them in turn
-    l.stage = off; off += exact ? (size_t)(T > 128 ? 2 : 1) * 7 * (sia_stg(T) * 20 + 4) * 4 : 0;
+    l.stage = off; off += exact ? (size_t)(T > 128 ? 2 : 1) * 7 * (sia_stg(T, mode) * 20 + 4) * 4 : 0;
     l.pipe = off;  off += exact && T > 128 ? 16 : 0;                   // hand-over counters of the two buffers
     l.total = off;
     return l;
@@ -214,7 +220,7 @@ __global__ __launch_bounds__(64) void sia_prep_kernel(const SiaArgs* __restrict_
 //     short of — and keypoint sets / level images that do not fit LDS, the 1920x1080 configuration
 //     with ~1700 keypoints and a 480x270 finest level): per-keypoint values in the HBM workspace
 //     SiaArgs::kp_ws, records and image taps from L2; LDS holds only the staging area of the
-//     ordered accumulation (~38 KB).
+//     ordered accumulation (18 KB with one wave per sequence, 36 KB with two, 72 KB with four).
 template <int WAVES, int MODE>
 struct Sia {
     static constexpr bool BIG = MODE == 2;
@@ -361,7 +367,9 @@ struct Sia {
         float eacc = 0;
         const float wlim = (float)(cur.w - 2), hlim = (float)(cur.h - 2);
         constexpr int KS = 20;                       // floats per keypoint in a staging plane (16 + pad: no write conflicts)
-        constexpr int SIA_STG = sia_stg(T);
+        constexpr int SIA_STG = sia_stg(T, MODE);
+        constexpr int SIA_ACC_U = sia_acc_u(T, MODE);
+        static_assert(SIA_STG % SIA_ACC_U == 0, "a trip of the accumulation stays inside the staged chunk");
         constexpr int PS = SIA_STG * KS + 4;         // plane stride: the 7 planes start on different banks
         float* stage = reinterpret_cast<float*>(dyn + lay.stage);      // [7][PS], index slot*KS + px
 
@@ -455,6 +463,35 @@ struct Sia {
                 // residual -= row * diff (:472-477) == residual += row * (-diff), exactly
                 *(SVO_LDS(v4f)*)(LDSF(stg) + 6 * PS + slot * KS + p4 * 4) =
                     v4f{-d[p4 * 4], -d[p4 * 4 + 1], -d[p4 * 4 + 2], -d[p4 * 4 + 3]};
+            }
+        };
+        // the same rows for pixel rows 2h and 2h+1 only (32-keypoint chunks: two lanes share a keypoint). Eight
+        // consecutive lanes, the group of a ds_write_b128, have one h and consecutive slots: their 16-byte pieces start
+        // at banks 20 slot + const (mod 32) = eight different multiples of 4, conflict free as in stage_kp. The 27
+        // readers of a ds_read_b128 read one offset of planes that start 644 floats = 4 banks (mod 64) apart.
+        auto stage_half = [&](float* stg, int slot, int h, int i, bool active, const float (&J)[12], const float (&d)[8]) {
+            float g0[8], g1[8];
+#pragma unroll
+            for (int e = 0; e < 8; e++) {
+                g0[e] = active ? rec_ld(REC_G0, h * 8 + e, i) : 0.f;
+                g1[e] = active ? rec_ld(REC_G1, h * 8 + e, i) : 0.f;
+            }
+#pragma unroll
+            for (int p = 0; p < 2; p++) {
+                const int o = slot * KS + (2 * h + p) * 4;
+#pragma unroll
+                for (int q = 0; q < 6; q++) {
+                    v4f row;
+#pragma unroll
+                    for (int e = 0; e < 4; e++) {
+                        float sum = 0;
+                        sum += g0[p * 4 + e] * J[q];
+                        sum += g1[p * 4 + e] * J[6 + q];
+                        row[e] = sum;
+                    }
+                    *(SVO_LDS(v4f)*)(LDSF(stg) + q * PS + o) = row;
+                }
+                *(SVO_LDS(v4f)*)(LDSF(stg) + 6 * PS + o) = v4f{-d[p * 4], -d[p * 4 + 1], -d[p * 4 + 2], -d[p * 4 + 3]};
             }
         };
         // hessian += row^T row (lanes 0..20), residual += row * (-diff) (lanes 21..26) over the m keypoints of a
@@ -554,12 +591,42 @@ struct Sia {
             } else {
                 // SIA_STG keypoints at a time stage the rows of gradient_times_jacobians (:376-388) and the
                 // diffs, keypoint-major; wave 0 adds them in storage order.
-                for (int sub = 0; sub < T / SIA_STG; sub++) {
-                    sia_sync<WAVES>();                      // the previous keypoints have been consumed
-                    if ((tid / SIA_STG) == sub) stage_kp(stage, tid % SIA_STG, i, active, J, d);
-                    sia_sync<WAVES>();
-                    if (wave == 0 && lane < 27)
-                        accumulate_chunk(stage, min(SIA_STG, n - (i0 + sub * SIA_STG)));   // keypoints of this chunk, in index order
+                if constexpr (SIA_STG == 32) {
+                    // the pass's 64 keypoints in two chunks of 32, all 64 lanes staging in both: lane L stages
+                    // pixel rows 2h, 2h+1 (h = L >> 5) of keypoint 32 s + (L & 31). v_permlane32_swap trades the
+                    // upper lanes of its first operand for the lower lanes of its second: of (J, J) it leaves
+                    // J of lane L & 31 and J of lane 32 + (L & 31), of (d[e], d[8 + e]) the residuals of the
+                    // pixel rows this lane stages in chunk 0 and in chunk 1. Each chunk swaps for itself and keeps
+                    // its half (21 swaps, 21 selects): one exchange for both chunks would hold the second chunk's
+                    // 21 values through the first and put the kernel over 256 registers.
+                    static_assert(WAVES == 1, "the two chunks of a pass trade their operands inside one wave");
+                    auto swap32 = [](float lo, float hi, bool second) {
+                        const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(lo), __float_as_uint(hi), false, false);
+                        return __uint_as_float(second ? r[1] : r[0]);
+                    };
+#pragma unroll 1
+                    for (int s = 0; s < 2; s++) {
+                        const int c0 = i0 + 32 * s;                 // (wave-uniform)
+                        if (c0 >= n) break;                         // nothing of this chunk would be added
+                        float Jh[12], dh[8];
+#pragma unroll
+                        for (int q = 0; q < 12; q++) Jh[q] = swap32(J[q], J[q], s != 0);
+#pragma unroll
+                        for (int e = 0; e < 8; e++) dh[e] = swap32(d[e], d[8 + e], s != 0);
+                        const bool act = swap32(active ? 1.f : 0.f, active ? 1.f : 0.f, s != 0) != 0.f;
+                        sia_sync<WAVES>();                          // the previous keypoints have been consumed
+                        stage_half(stage, lane & 31, lane >> 5, c0 + (lane & 31), act, Jh, dh);
+                        sia_sync<WAVES>();
+                        if (lane < 27) accumulate_chunk(stage, min(32, n - c0));
+                    }
+                } else {
+                    for (int sub = 0; sub < T / SIA_STG; sub++) {
+                        sia_sync<WAVES>();                      // the previous keypoints have been consumed
+                        if ((tid / SIA_STG) == sub) stage_kp(stage, tid % SIA_STG, i, active, J, d);
+                        sia_sync<WAVES>();
+                        if (wave == 0 && lane < 27)
+                            accumulate_chunk(stage, min(SIA_STG, n - (i0 + sub * SIA_STG)));   // keypoints of this chunk, in index order
+                    }
                 }
             }
         }
@@ -842,8 +909,9 @@ LaunchShape sia_pick_shape(int batch, const svo_camera_settings& cam, int width,
     const int nb = std::max(n_bound, 1);
     const int img = sia_img_bytes(cam, width, height);
     // A batch of sequences: records, per-keypoint values and image taps from L2 (MODE 2) and one
-    // wave per 128 keypoints, i.e. ~38 KB of LDS per sequence (the staging area of the ordered
-    // accumulation) instead of 74-96 KB. With six and more sequence groups in flight LDS is what the
+    // wave up to 192 keypoints, i.e. 18 KB of LDS per sequence (the staging area of the ordered
+    // accumulation, 32 keypoints at a time; 36 KB in 64-keypoint chunks before) instead of 74-96 KB.
+    // With six and more sequence groups in flight LDS is what the
     // window kernels (SSD 17 KB, pyramid 15 KB, KLT 10 KB per workgroup) run short of: 1536 sequences
     // in 6 groups, frames/s: MODE 0 174 K, MODE 1 184 K, MODE 2 two waves 200 K, one wave 206 K.
     // (at most 4 waves: with 8 a wave may only hold 256 registers and the kernel spills ~80 into scratch)

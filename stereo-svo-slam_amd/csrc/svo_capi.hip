@@ -479,6 +479,14 @@ extern "C" int svo_pick_launch_shapes(const svo_camera_settings* cam, int width,
     return SVO_OK;
 }
 
+extern "C" int svo_pick_sia_lds_bytes(const svo_camera_settings* cam, int width, int height, int batch, int n_bound,
+                                      int rec_cap, int exact, int64_t* lds_bytes) {
+    if (!cam || !lds_bytes || width < 1 || height < 1 || batch < 1)
+        return svo_set_error(SVO_ERR_INVALID, "svo_pick_sia_lds_bytes: bad arguments");
+    *lds_bytes = (int64_t)sia_pick_shape(batch, *cam, width, height, n_bound, rec_cap, exact).lds;
+    return SVO_OK;
+}
+
 // ------------------------------------------------------------------ diagnostics
 // svo_pinv6_check: IMPL 0 runs jacobi_svd6_reg on one system per lane, IMPL 1 jacobi_svd6_lanes on one
 // system per wavefront (H loaded alike by all 64 lanes: the wave-uniform input of the kernels' solves).

@@ -28,7 +28,7 @@ SYMBOLS = (
     "svo_handle_set_fast_solver", "svo_ctx_set_fast_solver",
     "svo_device_malloc", "svo_device_free", "svo_copy_to_device", "svo_copy_to_host",
     "svo_copy_image_to_device", "svo_project_keypoints",
-    "svo_ctx_get_launch_shapes", "svo_pick_launch_shapes", "svo_pinv6_check",
+    "svo_ctx_get_launch_shapes", "svo_pick_launch_shapes", "svo_pick_sia_lds_bytes", "svo_pinv6_check",
     "svo_solve6_check", "svo_remap_linear", "svo_ctx_set_rectification",
     "svo_detect_keypoints", "svo_detect_shape",
 )

@@ -72,6 +72,15 @@ def pick_launch_shapes(cfg, batch, n_bound, rec_cap=1 << 20, exact=True):
     return tuple(_shape_key(e) if e.launches else None for e in out)
 
 
+def pick_sia_lds_bytes(cfg, batch, n_bound, rec_cap=1 << 20, exact=True):
+    """svo_pick_sia_lds_bytes: the dynamic LDS per workgroup of the alignment launch pick_launch_shapes
+    describes (a host decision: no GPU needed)."""
+    out = C.c_int64(0)
+    _check(lib().svo_pick_sia_lds_bytes(C.byref(CameraSettings.from_dict(cfg)), cfg["width"], cfg["height"],
+                                        batch, n_bound, rec_cap, int(exact), C.byref(out)))
+    return out.value
+
+
 class Frame:
     """Frame / KeyFrame (src/include/stereo_slam_types.hpp:117-131) without images."""
 

@@ -2,6 +2,9 @@
 # Diagnostic builds of libsvo_hip into build_ab/ (git-ignored; travels to the GPU box):
 #   build_variants.sh stamps            -> build_ab/libsvo_hip_stamps.so  (-DSVO_SIA_STAMPS)
 #   build_variants.sh <tag> <flags...>  -> build_ab/libsvo_hip_<tag>.so   (extra hipcc flags)
+# sia_gn_kernel<1,2> (sia.hip): -DSVO_SIA_STG1=64 stages 64 keypoints at a time (36 KB of LDS),
+#   -DSVO_SIA_ACC_U=4 adds four keypoints per trip (over 256 registers), -DSVO_SIA_OCC=n caps the registers.
+# Run it in a checkout of the commit to compare against for that commit's library; never while a source is being edited.
 set -e
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
 CSRC=$ROOT/stereo-svo-slam_amd/csrc
@@ -9,7 +12,7 @@ TAG=$1; shift
 FLAGS="$@"
 [ "$TAG" = stamps ] && FLAGS="-DSVO_SIA_STAMPS $FLAGS"
 mkdir -p $ROOT/build_ab/$TAG
-for f in svo_capi svo_ctx svo_group pyramid sia klt reproj depth keyframe; do
+for f in svo_capi svo_ctx svo_group rectify pyramid sia klt reproj depth keyframe; do
   /opt/rocm/bin/hipcc -O3 --offload-arch=gfx950 -ffp-contract=off -fPIC -std=c++17 $FLAGS -c $CSRC/$f.hip -o $ROOT/build_ab/$TAG/$f.o &
 done
 wait
