@@ -170,7 +170,9 @@ typedef struct svo_ctx svo_ctx;
 /* SVO_MEM_DEVICE_BORROW: device images that the ctx uses IN PLACE as level 0 of its pyramids and
  * as the right image — no copy, like the reference, whose level 0 is a shallow alias of the caller's
  * cv::Mat (src/lib/stereo_slam.cpp:115). The caller keeps every image valid and unchanged while a
- * frame or keyframe of the ctx refers to it (the safe choice: until svo_ctx_destroy). With
+ * frame or keyframe of the ctx refers to it: until its sequence ends. Once svo_ctx_restart_sequences
+ * has been processed for a slot (after svo_wait) no frame of the ended sequence is read again and the
+ * caller may reuse or free them; otherwise until svo_ctx_destroy. With
  * rectification on (svo_ctx_set_rectification) the images are only read during their step. */
 enum { SVO_MEM_HOST = 0, SVO_MEM_DEVICE = 1, SVO_MEM_DEVICE_BORROW = 2 };
 
@@ -185,7 +187,8 @@ int svo_ctx_destroy(svo_ctx *ctx);
  * The images are copied; the caller may reuse its buffers on return. Returns
  * after the frame is complete (like the reference). A sequence whose two pointers are
  * NULL sits the step out with its state untouched (sequences of one ctx may have different
- * lengths); the very first step needs every sequence. */
+ * lengths). Every slot of a fresh ctx is EMPTY: a slot starts its sequence with the first frame
+ * it is given, at whatever step (see svo_ctx_restart_sequences). */
 int svo_new_images(svo_ctx *ctx, const uint8_t *const *left, const uint8_t *const *right,
                    int stride, const float *time_stamps, int mem);
 /* Pipelined form (no counterpart in the reference, whose new_image is synchronous): svo_submit_images() queues one frame set (same arguments; the images,
@@ -199,6 +202,42 @@ int svo_submit_images(svo_ctx *ctx, const uint8_t *const *left, const uint8_t *c
                       int stride, const float *time_stamps, int mem);
 int svo_wait(svo_ctx *ctx);
 int svo_ctx_get_groups(svo_ctx *ctx, int *n_groups);
+/* Sequence lifecycle (the reference's user constructs a new StereoSlam per sequence, src/app/main.cpp).
+ * The named slots end their current sequence. Ordered with the frame sets: it takes effect after every
+ * frame set submitted before it and before every one submitted after it; it does not wait. From then
+ * on a slot is EMPTY: NULL images keep it empty, and the next frame it is given is frame 0 of a new
+ * sequence, exactly like the first frame of a fresh ctx (zero pose, keyframe 0 from that frame, new
+ * pose filter, frame_id 0, keyframe ids from 0, colour LCG reseeded, empty trajectory). The getters
+ * describe the slot's current run; on an empty slot they return what a fresh ctx returns. Ending a
+ * sequence gives its image sets and keyframe storage back to the ctx (svo_ctx_get_memory), so a slot
+ * can run any number of sequences in bounded memory.
+ * An empty slot named here is left alone. Bad index: SVO_ERR_INVALID, nothing queued. A failed ctx
+ * rejects it like svo_submit_images. */
+int svo_ctx_restart_sequences(svo_ctx *ctx, const int *seqs, int n);
+/* When a restart ends a non-empty run, the ctx keeps a host record of it (24 B per frame for the
+ * trajectory) until svo_drop_finished_runs. Like every getter these wait for the queues. */
+typedef struct svo_run_info {
+    int32_t seq, run;           /* slot, and the ordinal of the run in that slot (0, 1, ...)        */
+    int32_t frames, keyframes;
+    float   last_time_stamp;
+    float   pose[6];            /* final filtered pose                                              */
+} svo_run_info;
+/* *n = kept records of the slot, oldest first */
+int svo_get_finished_runs(svo_ctx *ctx, int seq, int *n);
+/* record i of the slot; copies min(*n_poses, cap) poses of its trajectory. info / trajectory / n_poses may be NULL */
+int svo_get_finished_run(svo_ctx *ctx, int seq, int i, svo_run_info *info, svo_pose *trajectory,
+                         int cap, int *n_poses);
+/* forgets the records of the slot; seq < 0: of every slot */
+int svo_drop_finished_runs(svo_ctx *ctx, int seq);
+/* device memory of the ctx. Image sets and keyframe slabs are allocated in chunks when a free list runs dry and
+ * return to it when a keyframe's images are retired or a sequence ends. */
+typedef struct svo_memory {
+    int64_t device_bytes;       /* every device allocation of the ctx's groups                      */
+    int64_t klt_cache_bytes;    /* of which the KLT template cache                                  */
+    int32_t image_sets, image_sets_free;          /* pyramids of one frame: made so far / not in use */
+    int32_t keyframe_slabs, keyframe_slabs_free;  /* keypoint storage of one keyframe                */
+} svo_memory;
+int svo_ctx_get_memory(svo_ctx *ctx, svo_memory *out);
 /* EurocInput's rectification (maps :48-49, remap :69-70) inside the tracker: from the next frame on, the
  * images given to svo_new_image(s) / svo_submit_images are RAW images of the ctx size, remapped on the
  * device before the pyramids. left_* rectify the library's left image (the reference's M1r/M2r: cam1 with

@@ -69,7 +69,7 @@ __global__ __launch_bounds__(1024) void compact_kernel(const CompactArgs* __rest
     __shared__ unsigned s_live[2];
     const int tid = threadIdx.x;
     if (tid == 0) { s_min_kf = INT_MAX; s_live[0] = s_live[1] = 0u; }   // (the scan's barriers stand between this and the atomics below)
-    const int n = *G(a.src.n);
+    const int n = a.start ? 0 : *G(a.src.n);
     const int per = (n + (int)blockDim.x - 1) / (int)blockDim.x;
     const int i0 = tid * per, i1 = min(n, i0 + per);
     int cnt = 0;
@@ -103,7 +103,10 @@ __global__ __launch_bounds__(1024) void compact_kernel(const CompactArgs* __rest
             min_kf = min(min_kf, G(a.src.kf_id)[i]);
         }
     }
-    if (tid == 0) *G(a.dst.n) = total;
+    if (tid == 0) {
+        *G(a.dst.n) = total;
+        if (a.start) *G(a.src.n) = 0;
+    }
     if (a.min_kf) {                            // (uniform) which keyframes the frame's keypoints still refer to
         if (min_kf != INT_MAX) atomicMin(&s_min_kf, min_kf);
         __syncthreads();
@@ -118,6 +121,8 @@ __global__ __launch_bounds__(1024) void compact_kernel(const CompactArgs* __rest
     }
     if (a.zero)
         for (int i = tid; i < a.zero_count; i += blockDim.x) G(a.zero)[i] = 0;
+    if (a.zero_res)
+        for (int i = tid; i < a.zero_res_count; i += blockDim.x) G(a.zero_res)[i] = 0;
 }
 
 // Small sets run with 256 threads: a 16-wave workgroup only starts on a CU that has drained, and
@@ -462,7 +467,7 @@ __global__ __launch_bounds__(256) void kf_init_kernel(const KfInitArgs* __restri
         for (int i = tid; i < a.tmpl_valid_bytes / 4; i += 256) ((SVO_GP(uint32_t))a.record.tmpl_valid)[i] = 0u;
     __syncthreads();
     const float fx = a.cam.fx, fy = a.cam.fy, cx = a.cam.cx, cy = a.cam.cy, baseline = a.cam.baseline;
-    const uint32_t lcg0 = *G(a.color_lcg);
+    const uint32_t lcg0 = a.first_frame ? SVO_COLOR_LCG_SEED : *G(a.color_lcg);
     for (int i = old_count + tid; i < n; i += 256) {
         const svo_kp2d kp = G(a.kps.kps2d)[i];
         const float disparity = G(a.disparity)[i];

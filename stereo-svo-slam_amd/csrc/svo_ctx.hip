@@ -28,10 +28,12 @@
 // the other. svo_submit_images() queues a frame set on every group and returns;
 // svo_wait() drains the queues. svo_new_images() = submit + wait.
 struct svo_ctx {
+    // one entry of a group's queue: a frame set, or (restart non-empty) the end of some of its sequences
     struct Job {
         std::vector<const uint8_t*> left, right;
         std::vector<float> ts;
-        int stride, mem;
+        int stride = 0, mem = 0;
+        std::vector<int> restart;        // indices in the group
     };
     struct Worker {
         Group g;
@@ -57,9 +59,14 @@ struct svo_ctx {
 
 namespace {
 
+// the job joins the group's queue (one group: it runs here, on the caller's thread)
+void worker_submit(svo_ctx::Worker& w, svo_ctx::Job&& job);
+
 void worker_run_job(svo_ctx::Worker& w, const svo_ctx::Job& job) {
     if (w.err != SVO_OK || w.ctx_failed->load()) return;   // after a failure (any group) the queues are dropped
-    const int rc = grp_new_images(w.g.get(), job.left.data(), job.right.data(), job.stride, job.ts.data(), job.mem);
+    const int rc = !job.restart.empty()
+                       ? grp_restart_sequences(w.g.get(), job.restart.data(), (int)job.restart.size())
+                       : grp_new_images(w.g.get(), job.left.data(), job.right.data(), job.stride, job.ts.data(), job.mem);
     if (rc != SVO_OK) {
         w.err = rc;
         w.msg = svo_last_error();
@@ -84,6 +91,18 @@ void worker_loop(svo_ctx::Worker* w) {
             w->busy = false;
             if (w->jobs.empty()) w->cv_idle.notify_all();
         }
+    }
+}
+
+void worker_submit(svo_ctx::Worker& w, svo_ctx::Job&& job) {
+    if (w.th.joinable()) {
+        {
+            std::lock_guard<std::mutex> lk(w.m);
+            w.jobs.push_back(std::move(job));
+        }
+        w.cv.notify_one();
+    } else {
+        worker_run_job(w, job);
     }
 }
 
@@ -197,15 +216,51 @@ extern "C" int svo_submit_images(svo_ctx* c, const uint8_t* const* left, const u
         job.right.assign(right + w.first, right + w.first + w.count);
         job.ts.assign(time_stamps + w.first, time_stamps + w.first + w.count);
         job.stride = stride; job.mem = mem;
-        if (w.th.joinable()) {
-            {
-                std::lock_guard<std::mutex> lk(w.m);
-                w.jobs.push_back(std::move(job));
-            }
-            w.cv.notify_one();
-        } else {
-            worker_run_job(w, job);              // single group: runs on the caller's thread
-        }
+        worker_submit(w, std::move(job));
+    }
+    return SVO_OK;
+}
+
+extern "C" int svo_ctx_restart_sequences(svo_ctx* c, const int* seqs, int n) {
+    if (!c || n < 0 || (n > 0 && !seqs)) return svo_set_error(SVO_ERR_INVALID, "svo_ctx_restart_sequences: bad arguments");
+    for (int i = 0; i < n; i++)
+        if (seqs[i] < 0 || seqs[i] >= c->B)
+            return svo_set_error(SVO_ERR_INVALID, "svo_ctx_restart_sequences: sequence %d out of range", seqs[i]);
+    if (c->failed.load()) {                      // (as svo_submit_images)
+        const int rc = ctx_drain(c);
+        return rc ? rc : svo_set_error(SVO_ERR_INVALID, "svo_ctx_restart_sequences: an earlier frame of this ctx failed; create a new ctx");
+    }
+    for (auto& wp : c->workers) {
+        svo_ctx::Worker& w = *wp;
+        svo_ctx::Job job;
+        for (int i = 0; i < n; i++)
+            if (seqs[i] >= w.first && seqs[i] < w.first + w.count) job.restart.push_back(seqs[i] - w.first);
+        if (!job.restart.empty()) worker_submit(w, std::move(job));
+    }
+    return SVO_OK;
+}
+
+extern "C" int svo_drop_finished_runs(svo_ctx* c, int seq) {
+    if (!c || seq >= c->B) return svo_set_error(SVO_ERR_INVALID, "bad ctx / sequence index");
+    const int rc = ctx_drain(c);
+    if (rc) return rc;
+    for (auto& w : c->workers) {
+        if (seq < 0) grp_drop_finished_runs(w->g.get(), -1);
+        else if (seq >= w->first && seq < w->first + w->count) grp_drop_finished_runs(w->g.get(), seq - w->first);
+    }
+    return SVO_OK;
+}
+
+extern "C" int svo_ctx_get_memory(svo_ctx* c, svo_memory* out) {
+    if (!c || !out) return svo_set_error(SVO_ERR_INVALID, "svo_ctx_get_memory: bad arguments");
+    const int rc = ctx_drain(c);
+    if (rc) return rc;
+    std::memset(out, 0, sizeof(*out));
+    for (auto& w : c->workers) {
+        const svo_memory m = grp_memory(w->g.get());
+        out->device_bytes += m.device_bytes; out->klt_cache_bytes += m.klt_cache_bytes;
+        out->image_sets += m.image_sets; out->image_sets_free += m.image_sets_free;
+        out->keyframe_slabs += m.keyframe_slabs; out->keyframe_slabs_free += m.keyframe_slabs_free;
     }
     return SVO_OK;
 }

@@ -191,7 +191,8 @@ struct Seq {
     ImageSet* prev_set = nullptr;
     // host state
     PoseFilter kf;
-    int frame_id = -1;
+    int frame_id = -1;               // -1: the slot is EMPTY (no sequence yet, or ended: end_sequence); its next frame is frame 0
+    int run = 0;                     // ordinal of the slot's current (or next) sequence
     double ts = 0;
     float pose[6] = {0, 0, 0, 0, 0, 0};
     std::vector<svo_pose> trajectory;
@@ -201,6 +202,12 @@ struct Seq {
     bool pending = false;
     float pending_pose[6] = {0, 0, 0, 0, 0, 0};
     double pending_ts = 0;
+};
+
+// what stays of a sequence that svo_ctx_restart_sequences ended (host memory only)
+struct FinishedRun {
+    svo_run_info info;               // (info.seq: index in the group)
+    std::vector<svo_pose> trajectory;
 };
 
 // one kernel's argument blocks: slot i of the pinned array `h` goes up to slot i of the device array `d`
@@ -265,6 +272,9 @@ struct svo_group {
     Event ev[10];
     SetLayout set_layout;
     std::vector<uint8_t*> kf_slabs;   // free per-keyframe keypoint storage (allocated in chunks)
+    int kf_slab_count = 0;            // ... of so many slabs allocated so far
+    size_t device_bytes = 0;          // sum of dev_mem
+    std::vector<FinishedRun> finished;   // ended sequences, oldest first (svo_get_finished_run)
     std::vector<uint8_t*> set_slabs;  // free image-set storage (allocated in chunks)
     // KLT template cache (klt.hip): the templates of a keyframe's keypoints stay in HBM while the keyframe is one
     // of the last tmpl_kf of its sequence (0: off)
@@ -315,6 +325,7 @@ int dev_alloc(svo_group* c, T** p, size_t count, bool zero = true) {
     }
     *p = static_cast<T*>(q.get());
     c->dev_mem.push_back(std::move(q));
+    c->device_bytes += bytes;
     return SVO_OK;
 }
 
@@ -409,10 +420,12 @@ int grow_kf_slabs(svo_group* c, int count) {
     const int rc = dev_alloc(c, &base, sb * count, false);
     if (rc) return rc;
     for (int i = count - 1; i >= 0; i--) c->kf_slabs.push_back(base + sb * i);
+    c->kf_slab_count += count;
     return SVO_OK;
 }
 
-// the keypoint arrays of a keyframe in one slab of kf_slab_bytes
+// the keypoint arrays of a keyframe in one slab of kf_slab_bytes (kps3d is the slab's first array: its address
+// is the slab's, which end_sequence gives back)
 KpsDev carve_kps(uint8_t* base, size_t cap) {
     KpsDev k;
     std::memset(&k, 0, sizeof(k));
@@ -569,8 +582,6 @@ int alloc_sequence(svo_group* c, Seq& q, int s) {
     alloc(&q.sel, cells); alloc(&q.sel_level, cells); alloc(&q.sel_cell, cells); alloc(&q.occupied, c->merge_cells);
     alloc(&q.color_lcg, 1);
     if (rc) return rc;
-    const uint32_t lcg = 12345u;
-    HIP_TRY(hipMemcpy(q.color_lcg, &lcg, sizeof(lcg), hipMemcpyHostToDevice));
     q.kf.init();
     std::memset(&q.stats, 0, sizeof(q.stats));
     for (int i = 0; i < 4; i++)         // pre-allocate a few image sets
@@ -692,8 +703,9 @@ struct Step {
     const uint8_t* const* right;
     int stride, mem;
     const float* time_stamps;
-    bool first;                  // the group's first frame: every sequence makes a keyframe
-    std::vector<int> act;        // the sequences that take part, in slot order
+    std::vector<int> act;        // the sequences that take part, in slot order: they get pyramids
+    std::vector<int> trk;        // of these, the ones with a previous frame: they run the tracked frame's kernels
+    std::vector<int> start;      // [B] 1: this is frame 0 of the sequence (the slot was empty): no tracking, a keyframe
     std::vector<int> need;       // [B] 1: the sequence makes a keyframe in this step
     int pyr_stream = -1;         // row block of the row-streaming pyramid kernel, 0: some frame does not fit it
     float stage_ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -710,18 +722,23 @@ void lap(svo_group* c, Step& s, int phase) {
     s.lap_start = now;
 }
 
-// Sequences whose image pointers are NULL sit this step out (their state is untouched): a ctx
-// can hold sequences of different lengths. The others are packed into the first M slots of
-// every argument array, so the launches cover exactly them.
+// Sequences whose image pointers are NULL sit this step out (their state is untouched; an empty slot stays
+// empty): a ctx can hold sequences of different lengths. An empty slot that gets a frame starts a sequence
+// with it. The sequences of a launch are packed into the first slots of its argument arrays, so every
+// launch covers exactly the sequences it is for.
 int select_sequences(svo_group* c, Step& s) {
     s.act.reserve(c->B);
+    s.trk.reserve(c->B);
+    s.start.assign(c->B, 0);
     s.need.assign(c->B, 0);
     for (int q = 0; q < c->B; q++)
-        if (s.left[q] && s.right[q]) s.act.push_back(q);
-        else if ((s.left[q] != nullptr) != (s.right[q] != nullptr))
+        if (s.left[q] && s.right[q]) {
+            s.act.push_back(q);
+            if (c->seqs[q].frame_id < 0) s.start[q] = 1;
+            else s.trk.push_back(q);
+        } else if ((s.left[q] != nullptr) != (s.right[q] != nullptr)) {
             return svo_set_error(SVO_ERR_INVALID, "svo_new_images: sequence %d has only one image", q);
-    if (s.first && (int)s.act.size() != c->B)
-        return svo_set_error(SVO_ERR_INVALID, "svo_new_images: the first frame needs every sequence");
+        }
     return SVO_OK;
 }
 
@@ -832,11 +849,11 @@ void pack_ssd(svo_group* c, const Seq& q, int slot, int clamp_half, const int* f
     sa.first = 0; sa.first_ptr = first_ptr;
 }
 
-// arguments of the tracked frame's kernels: active sequence j in slot j
+// arguments of the tracked frame's kernels: tracked sequence j in slot j
 void pack_tracking_args(svo_group* c, const Step& st) {
     ArgBlocks& a = c->args;
-    for (int slot = 0; slot < (int)st.act.size(); slot++) {
-        const int s = st.act[slot];
+    for (int slot = 0; slot < (int)st.trk.size(); slot++) {
+        const int s = st.trk[slot];
         Seq& q = c->seqs[s];
         FrameResult* dr = c->d_res + s;
         // predicted pose = kf.statePre (stereo_slam.cpp:183-192)
@@ -890,13 +907,13 @@ void count_launch(svo_group* c, int kernel, const LaunchShape& sh) {
     c->launch_shapes.push_back({kernel, sh.waves, sh.mode, sh.cap, 1});
 }
 
-// the arguments upload, the pyramids and (after the first frame) the tracked frame's kernels; the
-// inside-counters go back to the host for the keyframe decision
+// the arguments upload, the pyramids of every sequence with a frame and the tracked frame's kernels for those
+// that have a previous one; their inside-counters go back to the host for the keyframe decision
 int launch_tracking(svo_group* c, const Step& s) {
     const ArgBlocks& a = c->args;
     hipStream_t st = c->stream.get();
-    const int M = (int)s.act.size();
-    HIP_TRY(hipMemcpyAsync(a.dev, a.host.get(), s.first ? a.bytes : a.frame_bytes, hipMemcpyHostToDevice, st));
+    const int M = (int)s.act.size(), T = (int)s.trk.size();
+    HIP_TRY(hipMemcpyAsync(a.dev, a.host.get(), a.frame_bytes, hipMemcpyHostToDevice, st));
     if (c->rect) {
         HIP_TRY(hipMemcpyAsync(c->remap_img.d, c->remap_img.h, sizeof(RemapImg) * 2 * M, hipMemcpyHostToDevice, st));
         RemapLaunch ra;
@@ -908,38 +925,41 @@ int launch_tracking(svo_group* c, const Step& s) {
     launch_pyr_fused(a.pyr.d, M, c->width, c->height, !c->rect && s.mem != SVO_MEM_DEVICE_BORROW,
                      std::max(s.pyr_stream, 0), st);
     HIP_TRY(hipGetLastError());   // (every launch is checked on its own: a later success must not mask a failure)
-    if (s.first) return SVO_OK;
     HIP_TRY(mark(c, 1));
-    launch_compact(a.compact.d, M, c->cap, st);
+    if (T == 0) {                 // only starting sequences: the stages of a tracked frame are empty
+        for (int i = 2; i <= 7; i++) HIP_TRY(mark(c, i));
+        return SVO_OK;
+    }
+    launch_compact(a.compact.d, T, c->cap, st);
     HIP_TRY(hipGetLastError());
     HIP_TRY(mark(c, 2));
     // the compaction can only shrink a sequence's keypoint set, so last frame's counts bound the
     // grids and the alignment kernel's LDS working set
     int grid_n = 1;
-    for (int seq : s.act) grid_n = std::max(grid_n, c->seqs[seq].n_host);
+    for (int seq : s.trk) grid_n = std::max(grid_n, c->seqs[seq].n_host);
     grid_n = std::min(grid_n, c->cap);
     const LaunchStatus sia_launch =
-        launch_sia(a.sia.d, M, c->cam, c->width, c->height, grid_n, c->rec_cap, c->exact_pinv, st);
+        launch_sia(a.sia.d, T, c->cam, c->width, c->height, grid_n, c->rec_cap, c->exact_pinv, st);
     HIP_TRY(sia_launch.err);
     if (!sia_launch.shape.fits)
         return svo_set_error(SVO_ERR_CAPACITY, "sparse alignment: %d keypoints exceed the workspaces", grid_n);
     count_launch(c, SVO_KERNEL_SIA_GN, sia_launch.shape);
     HIP_TRY(hipGetLastError());
     HIP_TRY(mark(c, 3));
-    launch_klt(a.klt.d, M, grid_n, c->cam.window_size_opt_flow, st);
+    launch_klt(a.klt.d, T, grid_n, c->cam.window_size_opt_flow, st);
     HIP_TRY(hipGetLastError());
     HIP_TRY(mark(c, 4));
-    const LaunchStatus reproj_launch = launch_reproj(a.reproj.d, M, grid_n, st);
+    const LaunchStatus reproj_launch = launch_reproj(a.reproj.d, T, grid_n, st);
     HIP_TRY(reproj_launch.err);
     if (!reproj_launch.shape.fits)
         return svo_set_error(SVO_ERR_CAPACITY, "reprojection GN: %d keypoints do not fit LDS", grid_n);
     count_launch(c, SVO_KERNEL_REPROJ_GN, reproj_launch.shape);
     HIP_TRY(hipGetLastError());
     HIP_TRY(mark(c, 5));
-    launch_ssd(a.ssd.d, M, grid_n, c->cam.window_size_depth_calculator, c->cam.search_y, st);
+    launch_ssd(a.ssd.d, T, grid_n, c->cam.window_size_depth_calculator, c->cam.search_y, st);
     HIP_TRY(hipGetLastError());
     HIP_TRY(mark(c, 6));
-    launch_filter(a.filter.d, M, grid_n, st);
+    launch_filter(a.filter.d, T, grid_n, st);
     HIP_TRY(hipGetLastError());
     HIP_TRY(mark(c, 7));
     HIP_TRY(hipMemcpyAsync(c->h_inside, c->d_inside, sizeof(int) * c->B, hipMemcpyDeviceToHost, st));
@@ -958,6 +978,12 @@ int pack_keyframe_args(svo_group* c, int slot, int s, bool first_frame) {
     CompactArgs& ca = pack_compact(c, q, slot, 1);
     ca.width = c->width; ca.height = c->height;
     ca.zero = q.n_det; ca.zero_count = SVO_MAX_PYRAMID_LEVELS;      // (detection counters: cleared by the compaction kernel)
+    if (first_frame) {
+        // a sequence starts: no keypoints, and the slot's result block as a fresh ctx has it (no stream
+        // operation of its own per starting sequence)
+        ca.start = 1;
+        ca.zero_res = reinterpret_cast<int*>(dr); ca.zero_res_count = (int)(sizeof(FrameResult) / sizeof(int));
+    }
     DetectArgs& da = clear(a.detect.h[slot]);
     for (int l = 0; l < c->cam.max_pyramid_levels; l++) da.level[l] = q.cur_set->left[l];
     da.n_levels = c->det_levels; da.grid_w = c->cam.grid_width; da.grid_h = c->cam.grid_height;
@@ -988,7 +1014,7 @@ int enqueue_keyframes(svo_group* c, const Step& s) {
     int m = 0;
     for (int seq = 0; seq < c->B; seq++) {
         if (!s.need[seq]) continue;
-        const int rc = pack_keyframe_args(c, m++, seq, s.first);
+        const int rc = pack_keyframe_args(c, m++, seq, s.start[seq] != 0);
         if (rc) return rc;
     }
     if (m == 0) return SVO_OK;
@@ -1009,21 +1035,13 @@ int enqueue_keyframes(svo_group* c, const Step& s) {
     return SVO_OK;
 }
 
-// which sequences make a keyframe (the first frame: all of them) and their launches
+// which sequences make a keyframe (every one that starts, stereo_slam.cpp:141-160) and their launches
 int decide_keyframes(svo_group* c, Step& s) {
-    if (s.first) {
-        for (int seq = 0; seq < c->B; seq++) {
-            s.need[seq] = 1;
-            HIP_TRY(hipMemsetAsync(c->seqs[seq].d_n, 0, sizeof(int) * 2, c->stream.get()));
-        }
-        HIP_TRY(hipMemsetAsync(c->d_res, 0, sizeof(FrameResult) * c->B, c->stream.get()));
-        return enqueue_keyframes(c, s);
-    }
     // KeyFrameManager::keyframe_needed (keyframe_manager.cpp:66-72)
     const int max_keypoints = (c->width / c->cam.grid_width) * (c->height / c->cam.grid_height);
     bool any = false;
     for (int seq : s.act) {
-        s.need[seq] = (double)c->h_inside[seq] < 0.66 * max_keypoints ? 1 : 0;
+        s.need[seq] = s.start[seq] || (double)c->h_inside[seq] < 0.66 * max_keypoints ? 1 : 0;
         any = any || s.need[seq];
     }
     return any ? enqueue_keyframes(c, s) : SVO_OK;
@@ -1033,11 +1051,7 @@ int read_stage_times(svo_group* c, Step& s) {
     HIP_TRY(mark(c, 8));
     if (!c->timing) return SVO_OK;
     HIP_TRY(hipEventSynchronize(c->ev[8].get()));
-    if (!s.first) {
-        for (int i = 0; i < 8; i++) (void)hipEventElapsedTime(&s.stage_ms[i], c->ev[i].get(), c->ev[i + 1].get());
-    } else {
-        (void)hipEventElapsedTime(&s.stage_ms[7], c->ev[0].get(), c->ev[8].get());
-    }
+    for (int i = 0; i < 8; i++) (void)hipEventElapsedTime(&s.stage_ms[i], c->ev[i].get(), c->ev[i + 1].get());
     return SVO_OK;
 }
 
@@ -1049,7 +1063,7 @@ int read_stage_times(svo_group* c, Step& s) {
 // instead of growing with every keyframe (the reference keeps them all). Nothing else of a keyframe goes:
 // its keypoint arrays, pose and table record stay for the depth filter and the getters.
 void retire_keyframe_images(svo_group* c, const Step& s) {
-    for (int seq : s.act) {
+    for (int seq : s.trk) {
         Seq& q = c->seqs[seq];
         const FrameResult& r = c->h_res[seq];
         const int newest = (int)q.kfs.size() - 1;                  // (never the newest: a keyframe made in this frame)
@@ -1068,8 +1082,9 @@ int book_frame(svo_group* c, Step& s) {
         Seq& q = c->seqs[seq];
         const FrameResult& r = c->h_res[seq];
         const double ts = (double)s.time_stamps[seq];
+        const bool first = s.start[seq] != 0;
         q.frame_id++;
-        if (s.first) {
+        if (first) {
             std::memset(q.pose, 0, sizeof(q.pose));
             q.ts = ts;
             q.trajectory.push_back(svo_pose{});         // (the zero pose)
@@ -1081,13 +1096,13 @@ int book_frame(svo_group* c, Step& s) {
         if (s.need[seq]) {
             KfHost& k = q.kfs.back();
             k.n = r.kf_n;
-            if (s.first) std::memset(k.pose, 0, sizeof(k.pose));
+            if (first) std::memset(k.pose, 0, sizeof(k.pose));
             else std::memcpy(k.pose, r.pose_refined, sizeof(k.pose));
         }
         q.n_host = c->h_n[2 * seq + q.cur];
         svo_frame_stats& st = clear(q.stats);
         st.frame_id = q.frame_id; st.is_keyframe = s.need[seq]; st.n_keypoints = q.n_host;
-        st.n_keyframes = (int)q.kfs.size(); st.inside_count = s.first ? 0 : c->h_inside[seq]; st.overflow = r.overflow;
+        st.n_keyframes = (int)q.kfs.size(); st.inside_count = first ? 0 : c->h_inside[seq]; st.overflow = r.overflow;
         std::memcpy(st.pose_sia, r.pose_sia, sizeof(st.pose_sia));
         std::memcpy(st.pose_refined, r.pose_refined, sizeof(st.pose_refined));
         st.sia_cost = r.sia_cost; st.reproj_cost = r.reproj_cost; st.sia_ms = s.stage_ms[2];
@@ -1097,7 +1112,7 @@ int book_frame(svo_group* c, Step& s) {
         c->totals.frames++;
         c->totals.keyframes += s.need[seq];
         c->totals.keypoints += q.n_host;
-        if (!s.first)
+        if (!first)
             for (int l = 0; l < SVO_MAX_PYRAMID_LEVELS; l++) {
                 c->totals.gn_gradient_calls += r.sia_trace[l].n_gradient;
                 c->totals.gn_cost_calls += r.sia_trace[l].n_cost;
@@ -1124,23 +1139,21 @@ int step(svo_group* c, Step& s) {
     HIP_TRY(mark(c, 0));
     if (s.mem == SVO_MEM_HOST && (rc = stage_host_frames(c, s))) return rc;
     if ((rc = pack_pyramids(c, s))) return rc;
-    if (!s.first) pack_tracking_args(c, s);
+    pack_tracking_args(c, s);
     lap(c, s, 0);
     if ((rc = launch_tracking(c, s))) return rc;
-    if (!s.first) {
-        lap(c, s, 1);
-        flush_pending(c);                 // previous frame's pose filter, overlapped with the kernels
-        lap(c, s, 2);
-        HIP_TRY(hipStreamSynchronize(c->stream.get()));
-        lap(c, s, 3);
-    }
+    lap(c, s, 1);
+    flush_pending(c);                     // previous frame's pose filter, overlapped with the kernels
+    lap(c, s, 2);
+    if (!s.trk.empty()) HIP_TRY(hipStreamSynchronize(c->stream.get()));   // the inside-counters
+    lap(c, s, 3);
     if ((rc = decide_keyframes(c, s))) return rc;
     lap(c, s, 4);
     HIP_TRY(hipMemcpyAsync(c->h_res, c->d_res, c->readback_bytes, hipMemcpyDeviceToHost, c->stream.get()));
     HIP_TRY(hipStreamSynchronize(c->stream.get()));   // results + counts
     lap(c, s, 5);
     if ((rc = read_stage_times(c, s))) return rc;
-    if (!s.first && c->retire_kf_images) retire_keyframe_images(c, s);
+    if (c->retire_kf_images) retire_keyframe_images(c, s);
     return book_frame(c, s);
 }
 
@@ -1156,10 +1169,74 @@ int grp_new_images(svo_group* c, const uint8_t* const* left, const uint8_t* cons
         return svo_set_error(SVO_ERR_INVALID, "svo_new_images: an earlier frame of this ctx failed; create a new ctx");
     Step s;
     s.left = left; s.right = right; s.stride = stride; s.mem = mem; s.time_stamps = time_stamps;
-    s.first = c->seqs[0].frame_id < 0;
     const int rc = step(c, s);
     if (rc != SVO_OK) c->failed = true;
     return rc;
+}
+
+// ------------------------------------------------------------------ the end of a sequence
+
+namespace {
+
+// The sequence of the slot ends (between two steps of the group: its stream is idle). Its image sets and
+// keyframe keypoint slabs go back to their free lists, its host state becomes that of a fresh ctx, and a host
+// record of the run stays. Nothing is cleared on the device: the slot's next frame is frame 0 of a new
+// sequence, whose kernels reset what they read (compact_kernel: keypoint counts and result block,
+// kf_init_kernel: colour generator, table record and "stored" flags of keyframe 0). Records and template-cache
+// blocks of the old run's keyframes stay behind in the table, but a keypoint only refers to a keyframe id that
+// its own run has created, and creating it rewrites both.
+void end_sequence(svo_group* c, int s) {
+    Seq& q = c->seqs[s];
+    if (q.frame_id < 0) return;              // empty: nothing to end
+    flush_one(q);
+    FinishedRun f;
+    clear(f.info);
+    f.info.seq = s; f.info.run = q.run; f.info.frames = q.frame_id + 1; f.info.keyframes = (int)q.kfs.size();
+    f.info.last_time_stamp = (float)q.ts;
+    std::memcpy(f.info.pose, q.pose, sizeof(f.info.pose));
+    f.trajectory = std::move(q.trajectory);
+    c->finished.push_back(std::move(f));
+    for (KfHost& k : q.kfs) {
+        release_set(q, k.set);
+        c->kf_slabs.push_back(reinterpret_cast<uint8_t*>(k.kps.kps3d));
+    }
+    release_set(q, q.cur_set);
+    release_set(q, q.prev_set);
+    q.kfs.clear();
+    q.kfs_retired = 0;
+    q.trajectory.clear();
+    q.cur = 0; q.n_host = 0; q.frame_id = -1; q.ts = 0; q.run++;
+    std::memset(q.pose, 0, sizeof(q.pose));
+    q.kf.init();
+    clear(q.stats);
+}
+
+}  // namespace
+
+int grp_restart_sequences(svo_group* c, const int* seqs, int n) {
+    if (c->failed)
+        return svo_set_error(SVO_ERR_INVALID, "svo_ctx_restart_sequences: an earlier frame of this ctx failed; create a new ctx");
+    for (int i = 0; i < n; i++) end_sequence(c, seqs[i]);
+    return SVO_OK;
+}
+
+void grp_drop_finished_runs(svo_group* c, int seq) {
+    if (seq < 0) { c->finished.clear(); return; }
+    c->finished.erase(std::remove_if(c->finished.begin(), c->finished.end(),
+                                     [seq](const FinishedRun& f) { return f.info.seq == seq; }),
+                      c->finished.end());
+}
+
+svo_memory grp_memory(const svo_group* c) {
+    svo_memory m;
+    clear(m);
+    m.device_bytes = (int64_t)c->device_bytes;
+    m.klt_cache_bytes = (int64_t)((size_t)c->B * c->tmpl_kf * (c->tmpl_block_bytes + c->tmpl_valid_bytes));
+    m.image_sets = c->image_sets;
+    for (const Seq& q : c->seqs) m.image_sets_free += (int)q.free_sets.size();
+    m.keyframe_slabs = c->kf_slab_count;
+    m.keyframe_slabs_free = (int)c->kf_slabs.size();
+    return m;
 }
 
 // ------------------------------------------------------------------ per-sequence getters of the C ABI
@@ -1252,4 +1329,27 @@ extern "C" int svo_get_frame_stats(svo_ctx* ctx, int seq, svo_frame_stats* out) 
     if (const int rc = ctx_seq(ctx, seq, &c, &s)) return rc;
     if (out) *out = c->seqs[s].stats;
     return SVO_OK;
+}
+
+extern "C" int svo_get_finished_runs(svo_ctx* ctx, int seq, int* n) {
+    svo_group* c; int s;
+    if (const int rc = ctx_seq(ctx, seq, &c, &s)) return rc;
+    if (n) *n = (int)std::count_if(c->finished.begin(), c->finished.end(), [s](const FinishedRun& f) { return f.info.seq == s; });
+    return SVO_OK;
+}
+
+extern "C" int svo_get_finished_run(svo_ctx* ctx, int seq, int i, svo_run_info* info, svo_pose* trajectory,
+                                    int cap, int* n_poses) {
+    svo_group* c; int s;
+    if (const int rc = ctx_seq(ctx, seq, &c, &s)) return rc;
+    int k = 0;
+    for (const FinishedRun& f : c->finished) {
+        if (f.info.seq != s || k++ != i) continue;
+        if (info) { *info = f.info; info->seq = seq; }
+        if (n_poses) *n_poses = (int)f.trajectory.size();
+        const int m = std::min<int>(cap, (int)f.trajectory.size());
+        if (trajectory && m > 0) std::memcpy(trajectory, f.trajectory.data(), sizeof(svo_pose) * m);
+        return SVO_OK;
+    }
+    return svo_set_error(SVO_ERR_INVALID, "sequence %d has no finished run %d", seq, i);
 }

@@ -16,6 +16,11 @@ int grp_create(const svo_camera_settings* cam, int width, int height, int n_sequ
 // one frame of every sequence whose two images are not NULL; after a failure the group rejects further frames
 int grp_new_images(svo_group* g, const uint8_t* const* left, const uint8_t* const* right, int stride,
                    const float* time_stamps, int mem);
+// the named sequences (indices in the group) end; their slots are empty until their next frame. Runs between two
+// steps of the group, on the thread that drives it. A failed group rejects it.
+int grp_restart_sequences(svo_group* g, const int* seqs, int n);
+void grp_drop_finished_runs(svo_group* g, int seq);   // seq < 0: of every sequence of the group
+svo_memory grp_memory(const svo_group* g);
 void grp_set_exact_pinv(svo_group* g, int on);
 // rectification of every frame from the next one on: maps[0] the left image's, maps[1] the right image's
 // (owned by the ctx, device memory that stays valid while set); nullptr: off

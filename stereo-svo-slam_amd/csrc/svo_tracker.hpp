@@ -32,6 +32,9 @@ struct CompactArgs {
     const int* enable; // optional device predicate
     int* zero;         // optional: zero_count ints set to 0 (the detection counters of the keyframe that follows)
     int zero_count;
+    int start;         // 1: the first frame of a sequence: both keypoint sets are empty whatever their counts say (src.n is cleared too)
+    int* zero_res;     // optional: zero_res_count ints set to 0 (the result block of a sequence that starts)
+    int zero_res_count;
     int* min_kf;       // optional: [3] smallest origin-keyframe id among the keypoints kept (INT_MAX: none kept), then a 64-bit
                        // mask (low word first): bit j set = some kept keypoint comes from keyframe min + j (younger ones: not reported)
 };
@@ -75,13 +78,15 @@ struct MergeArgs {
 };
 void launch_select_merge(const MergeArgs* d_args, int batch, int max_cells, hipStream_t stream);
 
+constexpr uint32_t SVO_COLOR_LCG_SEED = 12345u;   // state of a sequence's colour generator before its first keypoint
+
 struct KfInitArgs {
     svo_camera_settings cam;
     KpsDev kps;
     const int* old_count;
     const float* disparity;
     const float* frame_pose;
-    int first_frame;
+    int first_frame;   // 1: frame 0 of a sequence: zero pose, no temporary flags, colour LCG reseeded (SVO_COLOR_LCG_SEED)
     int new_kf_id;
     KfDev* kfs;
     uint32_t* color_lcg;

@@ -31,6 +31,8 @@ SYMBOLS = (
     "svo_ctx_get_launch_shapes", "svo_pick_launch_shapes", "svo_pick_sia_lds_bytes", "svo_pinv6_check",
     "svo_solve6_check", "svo_remap_linear", "svo_ctx_set_rectification",
     "svo_detect_keypoints", "svo_detect_shape",
+    "svo_ctx_restart_sequences", "svo_get_finished_runs", "svo_get_finished_run",
+    "svo_drop_finished_runs", "svo_ctx_get_memory",
 )
 
 

@@ -77,6 +77,90 @@ def play_unequal(slam, frames_of, lengths, time_of=lambda k: k / 20.0):
     return done
 
 
+def queue_schedule(lengths, n_slots, order=None):
+    """Sequences played back to back on the slots of one ctx: a slot whose sequence has ended takes the next
+    sequence of `order` at the very next step (order=None: longest first, the index as tie-break: the order
+    of assign_longest_first). Returns one list per step of (slot, sequence, frame index), in slot order;
+    sequences without frames are never scheduled. No GPU involved."""
+    if order is None:
+        order = sorted(range(len(lengths)), key=lambda i: (-lengths[i], i))
+    waiting = [i for i in order if lengths[i] > 0]
+    waiting.reverse()                       # (pop() takes the next one)
+    playing = [None] * n_slots              # per slot: [sequence, next frame]
+    steps = []
+    while True:
+        step = []
+        for slot in range(n_slots):
+            if playing[slot] is None and waiting:
+                playing[slot] = [waiting.pop(), 0]
+            if playing[slot] is None:
+                continue
+            seq, k = playing[slot]
+            step.append((slot, seq, k))
+            playing[slot] = [seq, k + 1] if k + 1 < lengths[seq] else None
+        if not step:
+            return steps
+        steps.append(step)
+
+
+def _queue_steps(n, frames_of, lengths, time_of, order):
+    """queue_schedule as calls on a ctx of n slots: [(slots to restart before the step, lefts, rights, time
+    stamps)] with None for slots without a frame, {sequence: (slot, run ordinal in that slot)}, sequence-frames.
+    A slot is restarted before the first frame of every sequence but its first."""
+    runs_started = [0] * n
+    where, steps, frames = {}, [], 0
+    for step in queue_schedule(lengths, n, order):
+        L, R, ts = [None] * n, [None] * n, [0.0] * n
+        restart = []
+        for slot, seq, k in step:
+            if k == 0:
+                if runs_started[slot] > 0:
+                    restart.append(slot)
+                where[seq] = (slot, runs_started[slot])
+                runs_started[slot] += 1
+            L[slot], R[slot] = frames_of(seq, k)
+            ts[slot] = time_of(seq, k)
+        steps.append((restart, L, R, ts))
+        frames += len(step)
+    return steps, where, frames
+
+
+def pack_queue(slam, frames_of, lengths, time_of=lambda s, k: k / 20.0, order=None, borrow=False):
+    """The steps of a pipelined play_queue built ahead (keeps Python out of a timed loop): a list of (slots to
+    restart before the step, packed frame set of slam.pack_images), then where and frames as play_queue
+    returns them."""
+    steps, where, frames = _queue_steps(slam.n, frames_of, lengths, time_of, order)
+    return [(restart, slam.pack_images(L, R, ts, borrow=borrow)) for restart, L, R, ts in steps], where, frames
+
+
+def submit_queue(slam, steps):
+    """Queue the steps of pack_queue on the ctx (restarts and frame sets in order); nothing is waited for."""
+    for restart, packed in steps:
+        if restart:
+            slam.restart(restart)
+        slam.submit_packed(packed)
+
+
+def play_queue(slam, frames_of, lengths, time_of=lambda s, k: k / 20.0, order=None, pipelined=False, borrow=False):
+    """Drive a ctx through queue_schedule(lengths, slam.n, order): a slot is restarted before the first frame
+    of every sequence but its first, slots without a frame get None, time stamps are per sequence
+    (time_of(sequence, frame index)). frames_of(sequence, k) -> (left, right). pipelined: every frame set and
+    restart is queued (svo_submit_images; torch frames, with borrow used in place) and waited for once at the
+    end; otherwise one new_images call per step. Returns ({sequence: (slot, run ordinal in that slot)},
+    number of sequence-frames)."""
+    if pipelined:
+        steps, where, frames = pack_queue(slam, frames_of, lengths, time_of, order, borrow)
+        submit_queue(slam, steps)
+        slam.wait()
+        return where, frames
+    steps, where, frames = _queue_steps(slam.n, frames_of, lengths, time_of, order)
+    for restart, L, R, ts in steps:
+        if restart:
+            slam.restart(restart)
+        slam.new_images(L, R, ts)
+    return where, frames
+
+
 def _sync(device):
     if device is not None and device.type == "cuda":
         torch.cuda.synchronize(device)

@@ -54,6 +54,19 @@ class LaunchShape(C.Structure):
                 ("launches", C.c_int64)]
 
 
+class RunInfo(C.Structure):
+    """svo_run_info (include/svo_hip.h): what stays of a sequence that a restart ended."""
+    _fields_ = [("seq", C.c_int32), ("run", C.c_int32), ("frames", C.c_int32), ("keyframes", C.c_int32),
+                ("last_time_stamp", C.c_float), ("pose", C.c_float * 6)]
+
+
+class Memory(C.Structure):
+    """svo_memory (include/svo_hip.h)."""
+    _fields_ = [("device_bytes", C.c_int64), ("klt_cache_bytes", C.c_int64),
+                ("image_sets", C.c_int32), ("image_sets_free", C.c_int32),
+                ("keyframe_slabs", C.c_int32), ("keyframe_slabs_free", C.c_int32)]
+
+
 KERNEL_NAMES = ("sia_gn_kernel", "reproj_gn_kernel")     # svo_launch_shape.kernel
 
 
@@ -167,8 +180,10 @@ class StereoSlamBatch:
     def new_images(self, lefts, rights, time_stamps):
         """lefts/rights: per sequence a uint8 [H, W] numpy array (host) or torch CUDA tensor; None for
         a sequence that has no frame at this step (it sits the step out: sequences of a ctx may have
-        different lengths)."""
+        different lengths; an empty slot starts its sequence with the first frame it gets)."""
         assert len(lefts) == self.n and len(rights) == self.n
+        if all(x is None for x in lefts):
+            return
         on_dev = isinstance(next(x for x in lefts if x is not None), torch.Tensor)
         ptrs_l = (C.c_void_p * self.n)()
         ptrs_r = (C.c_void_p * self.n)()
@@ -224,6 +239,34 @@ class StereoSlamBatch:
 
     def wait(self):
         _check(lib().svo_wait(self._ctx))
+
+    def restart(self, seqs):
+        """svo_ctx_restart_sequences: the named slots end their sequences (ordered with the submitted frame
+        sets, does not wait); the next frame a slot gets is frame 0 of a new sequence."""
+        seqs = [int(s) for s in ([seqs] if np.isscalar(seqs) else seqs)]
+        arr = (C.c_int * max(len(seqs), 1))(*seqs)
+        _check(lib().svo_ctx_restart_sequences(self._ctx, arr, len(seqs)))
+
+    def finished_runs(self, seq):
+        """The kept records of the slot's ended sequences, oldest first: [(RunInfo, trajectory[n, 6])]."""
+        n = C.c_int(0)
+        _check(lib().svo_get_finished_runs(self._ctx, seq, C.byref(n)))
+        out = []
+        for i in range(n.value):
+            info, m = RunInfo(), C.c_int(0)
+            _check(lib().svo_get_finished_run(self._ctx, seq, i, C.byref(info), None, 0, C.byref(m)))
+            traj = np.zeros((m.value, 6), np.float32)
+            _check(lib().svo_get_finished_run(self._ctx, seq, i, None, traj.ctypes.data_as(C.c_void_p), m.value, None))
+            out.append((info, traj))
+        return out
+
+    def drop_finished_runs(self, seq=-1):
+        _check(lib().svo_drop_finished_runs(self._ctx, seq))
+
+    def memory(self):
+        m = Memory()
+        _check(lib().svo_ctx_get_memory(self._ctx, C.byref(m)))
+        return m
 
     def groups(self):
         n = C.c_int(0)
