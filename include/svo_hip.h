@@ -83,6 +83,44 @@ int svo_build_lk_pyramid(svo_handle *h, int max_levels, int win, svo_image *leve
 int svo_remap_linear(svo_handle *h, int n, const svo_image *src, svo_image *dst,
                      const float *map_x, const float *map_y);
 
+/* I   the per-pixel step of the reference's ImageInput classes before StereoSlam::new_image: cvtColor(BGR2GRAY)
+ *     and the halves of a side-by-side frame (src/app/video_input.cpp:29-36), extractChannel of a 3-channel
+ *     frame (src/app/econ_input.cpp:102-103). The arithmetic:
+ *       gray  Y = (3735 B + 19235 G + 9798 R + 2^14) >> 15   (OpenCV 4.x RGB2Gray<uchar>: 15-bit weights, CV_DESCALE)
+ *       channel extract: byte k of an interleaved 3-channel pixel
+ *       side by side, output width W: right = columns 0 .. W-1, left = columns W .. 2W-1 of the frame
+ * An input format says how the buffers of one sequence become its left and right 8-bit images. */
+enum { SVO_INPUT_GRAY_PAIR = 0,   /* default: left[s], right[s] are two 8-bit images                                 */
+       SVO_INPUT_BGR_PAIR  = 1,   /* two 3-channel images, B,G,R order                                               */
+       SVO_INPUT_RGB_PAIR  = 2,   /* ... R,G,B order                                                                 */
+       SVO_INPUT_SBS_GRAY  = 3,   /* ONE buffer per sequence, >= 2W pixels per row: right = left half, left = right half */
+       SVO_INPUT_SBS_BGR   = 4,
+       SVO_INPUT_SBS_RGB   = 5,
+       SVO_INPUT_CH3_ECON  = 6 }; /* ONE W x H x 3 buffer: right = channel 1, left = channel 2                      */
+enum { SVO_INGEST_COPY = 0,       /* the output byte is byte `channel` of the source pixel                           */
+       SVO_INGEST_GRAY = 1 };     /* (weight[0] c0 + weight[1] c1 + weight[2] c2 + 2^14) >> 15 of its three bytes     */
+typedef struct svo_input_side {
+    int32_t buffer;             /* which buffer of the sequence: 0 = left[s] (src_a), 1 = right[s] (src_b)          */
+    int32_t start_column;       /* column of the buffer that becomes column 0 of the image                          */
+    int32_t op, channel;        /* SVO_INGEST_*                                                                      */
+    int32_t weight[3];
+} svo_input_side;
+typedef struct svo_input_layout {
+    int32_t buffers;            /* per sequence: 1 or 2                                                              */
+    int32_t channels;           /* bytes per pixel: 1 or 3                                                           */
+    int32_t min_row_pixels;     /* pixels a buffer row holds at least (its stride: >= min_row_pixels * channels)     */
+    svo_input_side left, right;
+} svo_input_layout;
+/* the layout of `format` for images of `width` pixels; needs no GPU. Unknown format or width < 1: SVO_ERR_INVALID */
+int svo_input_format_info(int format, int width, svo_input_layout *out);
+/* n buffers src_a[i] (and src_b[i] for the pair formats; otherwise src_b is ignored and may be NULL) into n left
+ * and n right 8-bit images. Every left[i] / right[i] has the size of left[0] (W x H, any W, H >= 1, stride >= W);
+ * a source has at least min_row_pixels x H pixels of `channels` bytes (svo_image.width / height in pixels, stride in
+ * bytes >= width * channels). Any base address and stride: rows that are dword aligned (source) and 16-byte
+ * aligned (output) take the wide path, the rest goes byte by byte; nothing outside the rows given is read or written. */
+int svo_convert_frames(svo_handle *h, int format, int n, const svo_image *src_a, const svo_image *src_b,
+                       svo_image *left, svo_image *right);
+
 /* A   PoseEstimator::estimate_pose(guess, out) src/include/pose_estimator.hpp:19-27,
  *                                              src/lib/pose_estimator.cpp:115-130
  * prev_pyr/cur_pyr: cam->max_pyramid_levels halfSample levels (host array of
@@ -173,7 +211,10 @@ typedef struct svo_ctx svo_ctx;
  * frame or keyframe of the ctx refers to it: until its sequence ends. Once svo_ctx_restart_sequences
  * has been processed for a slot (after svo_wait) no frame of the ended sequence is read again and the
  * caller may reuse or free them; otherwise until svo_ctx_destroy. With
- * rectification on (svo_ctx_set_rectification) the images are only read during their step. */
+ * rectification on (svo_ctx_set_rectification) or an input format that converts (svo_ctx_set_input_format: every one
+ * but GRAY_PAIR and SBS_GRAY) the buffers are only read during their step and level 0 is the ctx's own image: they may
+ * be reused after svo_wait. SVO_INPUT_SBS_GRAY without rectification uses the two halves of the frame in place
+ * (nothing is converted or copied): the lifetime rule above holds for the frame. */
 enum { SVO_MEM_HOST = 0, SVO_MEM_DEVICE = 1, SVO_MEM_DEVICE_BORROW = 2 };
 
 /* StereoSlam::StereoSlam(const CameraSettings&)         src/lib/stereo_slam.cpp:29-41 */
@@ -249,6 +290,17 @@ int svo_ctx_get_memory(svo_ctx *ctx, svo_memory *out);
  * rectified image: the caller may reuse the raw buffers once the step is done (after svo_wait). */
 int svo_ctx_set_rectification(svo_ctx *ctx, const float *left_map_x, const float *left_map_y,
                               const float *right_map_x, const float *right_map_y, int mem);
+/* The input format of the frames given to svo_new_image(s) / svo_submit_images from the next frame on, for every
+ * active slot (a slot's first frame and keyframes included); may be switched between frames. Waits for queued
+ * frames. Default SVO_INPUT_GRAY_PAIR: with it no launch, copy or allocation is added. The formats with ONE buffer
+ * per sequence take it in left[s]; right[s] (and the `right` array itself) is ignored and may be NULL; a NULL
+ * left[s] sits the step out. `stride` is the buffer's row pitch in bytes (>= min_row_pixels * channels of
+ * svo_input_format_info for the ctx width). svo_new_image follows the same rule: right and right_stride are ignored,
+ * width and height stay the ctx's. All three memory modes work with every format; host buffers go through the
+ * staging buffer (one slot per sequence for the one-buffer formats). With rectification also on the order is
+ * format -> remap -> pyramids, as EurocInput would do on colour images. A bad format: SVO_ERR_INVALID, the ctx
+ * keeps its setting. */
+int svo_ctx_set_input_format(svo_ctx *ctx, int format);
 /* n_sequences == 1, host memory: the exact shape of StereoSlam::new_image */
 int svo_new_image(svo_ctx *ctx, const uint8_t *left, int left_stride, const uint8_t *right,
                   int right_stride, int width, int height, float time_stamp);

@@ -5,6 +5,8 @@
 // device every call fails with SVO_ERR_NO_DEVICE.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <climits>
 #include <cstring>
 #include <memory>
 #include <new>
@@ -29,6 +31,8 @@ struct svo_handle {
     int exact_pinv = 1;             // reference-order Gauss-Newton by default
     DevPtr<uint8_t> remap_ws;       // svo_remap_linear: the map in the kernel's form + the image table
     size_t remap_ws_bytes = 0;
+    DevPtr<IngestImg> ingest_ws;    // svo_convert_frames: the image table
+    size_t ingest_ws_count = 0;
 };
 
 extern "C" const char* svo_last_error(void) { return svo_error_text; }
@@ -209,6 +213,63 @@ extern "C" int svo_remap_linear(svo_handle* h, int n, const svo_image* src, svo_
     a.n = n;
     launch_remap(a, 1, h->stream);
     HIP_TRY(hipGetLastError());
+    return SVO_OK;
+}
+
+extern "C" int svo_input_format_info(int format, int width, svo_input_layout* out) {
+    const IngestFormat* f = ingest_format(format);
+    if (!f || width < 1 || !out) return svo_set_error(SVO_ERR_INVALID, "svo_input_format_info: unknown format %d, width %d", format, width);
+    std::memset(out, 0, sizeof(*out));
+    out->buffers = f->buffers; out->channels = f->channels; out->min_row_pixels = ingest_row_pixels(*f, width);
+    const IngestSide* sides[2] = {&f->left, &f->right};
+    svo_input_side* outs[2] = {&out->left, &out->right};
+    for (int i = 0; i < 2; i++) {
+        outs[i]->buffer = sides[i]->buffer; outs[i]->start_column = sides[i]->start * width;
+        outs[i]->op = sides[i]->op; outs[i]->channel = sides[i]->channel;
+        for (int k = 0; k < 3; k++) outs[i]->weight[k] = sides[i]->weight[k];
+    }
+    return SVO_OK;
+}
+
+extern "C" int svo_convert_frames(svo_handle* h, int format, int n, const svo_image* src_a, const svo_image* src_b,
+                                  svo_image* left, svo_image* right) {
+    CHECK_H(h);
+    const IngestFormat* f = ingest_format(format);
+    if (!f || n < 1 || !src_a || !left || !right || (f->buffers == 2 && !src_b))
+        return svo_set_error(SVO_ERR_INVALID, "svo_convert_frames: bad arguments");
+    const int w = left[0].width, hgt = left[0].height;
+    if (w < 1 || hgt < 1) return svo_set_error(SVO_ERR_INVALID, "svo_convert_frames: empty output");
+    const int row_px = ingest_row_pixels(*f, w);
+    if ((long long)row_px * f->channels > INT_MAX) return svo_set_error(SVO_ERR_INVALID, "svo_convert_frames: row too long");
+    for (int i = 0; i < n; i++) {
+        for (const svo_image* d : {&left[i], &right[i]})
+            if (!d->data || d->width != w || d->height != hgt || d->stride < w)
+                return svo_set_error(SVO_ERR_INVALID, "svo_convert_frames: image %d: every output has the size of left[0]", i);
+        for (int b = 0; b < f->buffers; b++) {
+            const svo_image& s = b ? src_b[i] : src_a[i];
+            if (!s.data || s.width < row_px || s.height < hgt || (long long)s.stride < (long long)s.width * f->channels)
+                return svo_set_error(SVO_ERR_INVALID, "svo_convert_frames: image %d: a source of at least %d x %d pixels, stride >= its row", i, row_px, hgt);
+        }
+    }
+    if ((size_t)2 * n > h->ingest_ws_count) {
+        HIP_TRY(hipStreamSynchronize(h->stream));      // (the old table may still be read)
+        h->ingest_ws.reset();
+        h->ingest_ws_count = 0;
+        HIP_TRY(dev_malloc(h->ingest_ws, sizeof(IngestImg) * 2 * (size_t)n));
+        h->ingest_ws_count = (size_t)2 * n;
+    }
+    std::vector<IngestImg> imgs((size_t)2 * n);
+    for (int i = 0; i < n; i++)
+        for (int side = 0; side < 2; side++) {
+            const svo_image& s = (side ? f->right : f->left).buffer ? src_b[i] : src_a[i];
+            imgs[(size_t)side * n + i] = ingest_image(*f, side, s.data, s.stride, make_view(side ? right[i] : left[i]));
+        }
+    HIP_TRY(hipMemcpyAsync(h->ingest_ws.get(), imgs.data(), sizeof(IngestImg) * imgs.size(), hipMemcpyHostToDevice, h->stream));
+    const int total = 2 * n, per_launch = 32768;
+    for (int i0 = 0; i0 < total; i0 += per_launch) {
+        launch_ingest(h->ingest_ws.get() + i0, std::min(per_launch, total - i0), w, hgt, h->stream);
+        HIP_TRY(hipGetLastError());
+    }
     return SVO_OK;
 }
 

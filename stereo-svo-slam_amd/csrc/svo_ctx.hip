@@ -55,6 +55,8 @@ struct svo_ctx {
     // svo_ctx_set_rectification: one read-only map set for every group (left, right), or none
     svo::DevPtr<uint8_t> rect_mem;
     svo::RemapMap rect[2];
+    int input_format = SVO_INPUT_GRAY_PAIR;      // svo_ctx_set_input_format (every group has the same)
+    bool one_buffer() const { return svo::ingest_format(input_format)->buffers == 1; }
 };
 
 namespace {
@@ -66,7 +68,8 @@ void worker_run_job(svo_ctx::Worker& w, const svo_ctx::Job& job) {
     if (w.err != SVO_OK || w.ctx_failed->load()) return;   // after a failure (any group) the queues are dropped
     const int rc = !job.restart.empty()
                        ? grp_restart_sequences(w.g.get(), job.restart.data(), (int)job.restart.size())
-                       : grp_new_images(w.g.get(), job.left.data(), job.right.data(), job.stride, job.ts.data(), job.mem);
+                       : grp_new_images(w.g.get(), job.left.data(), job.right.empty() ? nullptr : job.right.data(), job.stride,
+                                        job.ts.data(), job.mem);
     if (rc != SVO_OK) {
         w.err = rc;
         w.msg = svo_last_error();
@@ -204,7 +207,11 @@ extern "C" int svo_ctx_get_groups(svo_ctx* c, int* n_groups) {
 
 extern "C" int svo_submit_images(svo_ctx* c, const uint8_t* const* left, const uint8_t* const* right,
                                  int stride, const float* time_stamps, int mem) {
-    if (!c || !left || !right || !time_stamps) return svo_set_error(SVO_ERR_INVALID, "svo_submit_images: bad arguments");
+    if (!c || !left || !time_stamps || (!right && !c->one_buffer()))
+        return svo_set_error(SVO_ERR_INVALID, "svo_submit_images: bad arguments");
+    const svo::IngestFormat& f = *svo::ingest_format(c->input_format);
+    if ((long long)stride < (long long)svo::ingest_row_pixels(f, c->width) * f.channels)   // (nothing is queued: the ctx stays usable)
+        return svo_set_error(SVO_ERR_INVALID, "svo_submit_images: stride %d is below the row's bytes", stride);
     if (c->failed.load()) {                      // nothing is queued on any group once one of them has failed
         const int rc = ctx_drain(c);             // (the first call after the failure reports its cause)
         return rc ? rc : svo_set_error(SVO_ERR_INVALID, "svo_submit_images: an earlier frame of this ctx failed; create a new ctx");
@@ -213,7 +220,7 @@ extern "C" int svo_submit_images(svo_ctx* c, const uint8_t* const* left, const u
         svo_ctx::Worker& w = *wp;
         svo_ctx::Job job;
         job.left.assign(left + w.first, left + w.first + w.count);
-        job.right.assign(right + w.first, right + w.first + w.count);
+        if (right && !c->one_buffer()) job.right.assign(right + w.first, right + w.first + w.count);   // (else: ignored)
         job.ts.assign(time_stamps + w.first, time_stamps + w.first + w.count);
         job.stride = stride; job.mem = mem;
         worker_submit(w, std::move(job));
@@ -279,9 +286,25 @@ extern "C" int svo_new_images(svo_ctx* c, const uint8_t* const* left, const uint
 extern "C" int svo_new_image(svo_ctx* c, const uint8_t* left, int left_stride, const uint8_t* right,
                              int right_stride, int width, int height, float time_stamp) {
     if (!c || c->B != 1) return svo_set_error(SVO_ERR_INVALID, "svo_new_image needs a 1-sequence ctx");
-    if (width != c->width || height != c->height || left_stride != right_stride)
+    if (width != c->width || height != c->height || (!c->one_buffer() && left_stride != right_stride))
         return svo_set_error(SVO_ERR_INVALID, "svo_new_image: image size / stride mismatch");
     return grp_new_images(c->workers[0]->g.get(), &left, &right, left_stride, &time_stamp, SVO_MEM_HOST);
+}
+
+extern "C" int svo_ctx_set_input_format(svo_ctx* c, int format) {
+    if (!c || !svo::ingest_format(format))
+        return svo_set_error(SVO_ERR_INVALID, "svo_ctx_set_input_format: unknown format %d", format);
+    const int rc = ctx_drain(c);                  // (the groups are idle from here on)
+    if (rc) return rc;
+    // a group that cannot get its image table keeps the old format, and so does the ctx: the groups before it go back
+    for (size_t i = 0; i < c->workers.size(); i++) {
+        const int e = grp_set_input_format(c->workers[i]->g.get(), format);
+        if (e == SVO_OK) continue;
+        for (size_t k = 0; k < i; k++) (void)grp_set_input_format(c->workers[k]->g.get(), c->input_format);
+        return e;
+    }
+    c->input_format = format;
+    return SVO_OK;
 }
 
 extern "C" int svo_ctx_set_rectification(svo_ctx* c, const float* left_map_x, const float* left_map_y,

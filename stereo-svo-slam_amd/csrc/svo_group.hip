@@ -266,6 +266,15 @@ struct svo_group {
     const RemapMap* rect = nullptr;
     ArgArray<RemapImg> remap_img;
     PinnedPtr<RemapImg> remap_img_host;
+    // input format (svo_ctx_set_input_format). fmt: its row of ingest.hip's table. A format that converts launches
+    // ingest_kernel over ingest_img (left images of the active sequences, then their right images: pinned block and
+    // device mirror, made when the first such format is set); with rectification on too it writes the raw gray
+    // planes d_raw_gray (2 x B of raw_plane_bytes, made on first use) that the remap reads.
+    int input_format = SVO_INPUT_GRAY_PAIR;
+    const IngestFormat* fmt = nullptr;
+    ArgArray<IngestImg> ingest_img;
+    PinnedPtr<IngestImg> ingest_img_host;
+    uint8_t* d_raw_gray = nullptr; size_t raw_plane_bytes = 0;
     bool timing = false;
     bool failed = false;
     int exact_pinv = 1;          // reference-order Gauss-Newton unless svo_ctx_set_fast_solver(ctx, 1)
@@ -632,6 +641,7 @@ int grp_create(const svo_camera_settings* cam, int width, int height, int n_sequ
     Group g(new (std::nothrow) svo_group());
     svo_group* c = g.get();
     if (!c) return svo_set_error(SVO_ERR_INVALID, "out of host memory");
+    c->fmt = ingest_format(SVO_INPUT_GRAY_PAIR);
     c->device = device; c->B = n_sequences; c->width = width; c->height = height; c->cam = *cam;
     std::memset(&c->totals, 0, sizeof(c->totals));
     HIP_TRY(make_stream(c->stream));
@@ -655,6 +665,27 @@ int grp_create(const svo_camera_settings* cam, int width, int height, int n_sequ
 void grp_set_exact_pinv(svo_group* c, int on) { c->exact_pinv = on != 0; }
 void grp_set_rectification(svo_group* c, const RemapMap* maps) { c->rect = maps; }
 void grp_enable_timing(svo_group* c, int on) { c->timing = on != 0; }
+
+namespace {
+// does the format need ingest_kernel? GRAY_PAIR is the tracker's own input; SBS_GRAY is GRAY_PAIR at base + W and base
+bool converts(int format) { return format != SVO_INPUT_GRAY_PAIR && format != SVO_INPUT_SBS_GRAY; }
+}  // namespace
+
+int grp_set_input_format(svo_group* c, int format) {
+    if (converts(format) && !c->ingest_img.d) {
+        HIP_TRY(hipSetDevice(c->device));
+        PinnedPtr<IngestImg> host;
+        HIP_TRY(pinned_malloc(host, sizeof(IngestImg) * 2 * (size_t)c->B));
+        IngestImg* dev = nullptr;
+        if (const int rc = dev_alloc(c, &dev, 2 * (size_t)c->B)) return rc;
+        c->ingest_img_host = std::move(host);
+        c->ingest_img.h = c->ingest_img_host.get();
+        c->ingest_img.d = dev;
+    }
+    c->input_format = format;
+    c->fmt = ingest_format(format);
+    return SVO_OK;
+}
 
 svo_totals grp_totals(const svo_group* c) {
     svo_totals t = c->totals;
@@ -731,21 +762,24 @@ int select_sequences(svo_group* c, Step& s) {
     s.trk.reserve(c->B);
     s.start.assign(c->B, 0);
     s.need.assign(c->B, 0);
+    const bool one_buffer = c->fmt->buffers == 1;
     for (int q = 0; q < c->B; q++)
-        if (s.left[q] && s.right[q]) {
+        if (s.left[q] && (one_buffer || s.right[q])) {
             s.act.push_back(q);
             if (c->seqs[q].frame_id < 0) s.start[q] = 1;
             else s.trk.push_back(q);
-        } else if ((s.left[q] != nullptr) != (s.right[q] != nullptr)) {
+        } else if (!one_buffer && (s.left[q] != nullptr) != (s.right[q] != nullptr)) {
             return svo_set_error(SVO_ERR_INVALID, "svo_new_images: sequence %d has only one image", q);
         }
     return SVO_OK;
 }
 
-// host-resident frames into the staging buffer: slots 0..B-1 left frames, B..2B-1 right frames
+// host-resident frames into the staging buffer: slots 0..B-1 left frames, B..2B-1 right frames (a one-buffer
+// input format: slots 0..B-1, one side only)
 int stage_host_frames(svo_group* c, const Step& s) {
     const int B = c->B;
-    const size_t used = (size_t)(c->height - 1) * s.stride + c->width;      // bytes of one frame that are read
+    const size_t row_bytes = (size_t)ingest_row_pixels(*c->fmt, c->width) * c->fmt->channels;
+    const size_t used = (size_t)(c->height - 1) * s.stride + row_bytes;     // bytes of one frame that are read
     const size_t fb = align_up((size_t)c->height * s.stride, 256);
     if (fb > c->stage_frame_bytes) {
         HIP_TRY(hipStreamSynchronize(c->stream.get()));
@@ -756,7 +790,7 @@ int stage_host_frames(svo_group* c, const Step& s) {
     // host frames that follow each other at exactly one frame's distance (one [B][H][stride] block per
     // side) go as ONE 2D copy: a "row" is a whole frame
     const size_t spacing = (size_t)c->height * s.stride;
-    for (int side = 0; side < 2; side++) {
+    for (int side = 0; side < c->fmt->buffers; side++) {
         const uint8_t* const* src = side ? s.right : s.left;
         int s0 = 0;
         while (s0 < B) {
@@ -778,6 +812,11 @@ int stage_host_frames(svo_group* c, const Step& s) {
 
 // every active sequence takes a fresh image set; its pyramid arguments
 int pack_pyramids(svo_group* c, Step& s) {
+    if (converts(c->input_format) && c->rect && !c->d_raw_gray) {
+        c->raw_plane_bytes = align_up(align_up((size_t)c->width, 64) * c->height, 256);
+        const int rc = dev_alloc(c, &c->d_raw_gray, c->raw_plane_bytes * 2 * c->B, false);
+        if (rc) return rc;
+    }
     for (int j = 0; j < (int)s.act.size(); j++) {
         const int seq = s.act[j];
         Seq& q = c->seqs[seq];
@@ -788,32 +827,50 @@ int pack_pyramids(svo_group* c, Step& s) {
         ImageSet* is = q.cur_set;
         PyrArgs& hs = clear(c->args.pyr.h[j]);
         hs.n_levels = c->cam.max_pyramid_levels;
-        if (c->rect) {
+        // the sequence's buffers on the device (in place, or in the staging buffer), and its two gray images in them
+        const bool host = s.mem == SVO_MEM_HOST;
+        const uint8_t* buf[2];
+        buf[0] = host ? c->d_stage_in + (size_t)seq * c->stage_frame_bytes : s.left[seq];
+        buf[1] = c->fmt->buffers == 1 ? buf[0] : host ? c->d_stage_in + (size_t)(c->B + seq) * c->stage_frame_bytes : s.right[seq];
+        const uint8_t* src_l = buf[c->fmt->left.buffer] + (size_t)c->fmt->left.start * c->width;    // (gray formats; unused
+        const uint8_t* src_r = buf[c->fmt->right.buffer] + (size_t)c->fmt->right.start * c->width;  //  when the format converts)
+        const int M = (int)s.act.size();
+        if (converts(c->input_format)) {
+            // the ingest launch makes the gray images: straight into the set's own level 0 and right image, or,
+            // with rectification on, into the group's raw planes, which the remap then reads (dense rows of the
+            // aligned width). The pyramids are built from the set's own images (no ingest of theirs).
+            is->left[0] = is->own_left0;
+            is->right = is->own_right;
+            ImgView gray_l = is->own_left0, gray_r = is->own_right;
+            if (c->rect) {
+                const int pitch = (int)align_up((size_t)c->width, 64);
+                gray_l = ImgView{c->d_raw_gray + (size_t)seq * c->raw_plane_bytes, c->width, c->height, pitch};
+                gray_r = ImgView{c->d_raw_gray + (size_t)(c->B + seq) * c->raw_plane_bytes, c->width, c->height, pitch};
+                c->remap_img.h[j] = RemapImg{gray_l, is->own_left0};
+                c->remap_img.h[M + j] = RemapImg{gray_r, is->own_right};
+            }
+            c->ingest_img.h[j] = ingest_image(*c->fmt, 0, buf[c->fmt->left.buffer], s.stride, gray_l);
+            c->ingest_img.h[M + j] = ingest_image(*c->fmt, 1, buf[c->fmt->right.buffer], s.stride, gray_r);
+            hs.src_left = is->left[0];
+        } else if (c->rect) {
             // rectification: the raw frames (in place, or from the staging buffer) are remapped into the
             // set's own level 0 and right image, then the pyramids are built from there (no ingest)
             is->left[0] = is->own_left0;
             is->right = is->own_right;
-            const bool host = s.mem == SVO_MEM_HOST;
-            const uint8_t* src_l = host ? c->d_stage_in + (size_t)seq * c->stage_frame_bytes : s.left[seq];
-            const uint8_t* src_r = host ? c->d_stage_in + (size_t)(c->B + seq) * c->stage_frame_bytes : s.right[seq];
-            const int M = (int)s.act.size();
             c->remap_img.h[j] = RemapImg{ImgView{src_l, c->width, c->height, s.stride}, is->own_left0};
             c->remap_img.h[M + j] = RemapImg{ImgView{src_r, c->width, c->height, s.stride}, is->own_right};
             hs.src_left = is->left[0];
         } else if (s.mem == SVO_MEM_DEVICE_BORROW) {
             // level 0 of both pyramids and the right image ARE the caller's images (like the
             // reference's shallow cv::Mat alias, stereo_slam.cpp:115): nothing is copied
-            is->left[0] = ImgView{s.left[seq], c->width, c->height, s.stride};
-            is->right = ImgView{s.right[seq], c->width, c->height, s.stride};
+            is->left[0] = ImgView{src_l, c->width, c->height, s.stride};
+            is->right = ImgView{src_r, c->width, c->height, s.stride};
             hs.src_left = is->left[0];
         } else {
             // frames are ingested by the pyramid kernel itself (one launch for all sequences instead of
             // 2 copies per sequence); host-resident ones come through the staging buffer
             is->left[0] = is->own_left0;
             is->right = is->own_right;
-            const bool dev = s.mem == SVO_MEM_DEVICE;
-            const uint8_t* src_l = dev ? s.left[seq] : c->d_stage_in + (size_t)seq * c->stage_frame_bytes;
-            const uint8_t* src_r = dev ? s.right[seq] : c->d_stage_in + (size_t)(c->B + seq) * c->stage_frame_bytes;
             hs.src_left = ImgView{src_l, c->width, c->height, s.stride};
             hs.src_right = ImgView{src_r, c->width, c->height, s.stride};
             hs.dst_right = is->right;
@@ -914,6 +971,15 @@ int launch_tracking(svo_group* c, const Step& s) {
     hipStream_t st = c->stream.get();
     const int M = (int)s.act.size(), T = (int)s.trk.size();
     HIP_TRY(hipMemcpyAsync(a.dev, a.host.get(), a.frame_bytes, hipMemcpyHostToDevice, st));
+    const bool ingest = converts(c->input_format);
+    if (ingest) {
+        // both sides of every active sequence in one launch (chunks of the grid's z limit)
+        HIP_TRY(hipMemcpyAsync(c->ingest_img.d, c->ingest_img.h, sizeof(IngestImg) * 2 * M, hipMemcpyHostToDevice, st));
+        for (int i0 = 0; i0 < 2 * M; i0 += 32768) {
+            launch_ingest(c->ingest_img.d + i0, std::min(32768, 2 * M - i0), c->width, c->height, st);
+            HIP_TRY(hipGetLastError());
+        }
+    }
     if (c->rect) {
         HIP_TRY(hipMemcpyAsync(c->remap_img.d, c->remap_img.h, sizeof(RemapImg) * 2 * M, hipMemcpyHostToDevice, st));
         RemapLaunch ra;
@@ -922,7 +988,7 @@ int launch_tracking(svo_group* c, const Step& s) {
         launch_remap(ra, 2, st);
         HIP_TRY(hipGetLastError());
     }
-    launch_pyr_fused(a.pyr.d, M, c->width, c->height, !c->rect && s.mem != SVO_MEM_DEVICE_BORROW,
+    launch_pyr_fused(a.pyr.d, M, c->width, c->height, !c->rect && !ingest && s.mem != SVO_MEM_DEVICE_BORROW,
                      std::max(s.pyr_stream, 0), st);
     HIP_TRY(hipGetLastError());   // (every launch is checked on its own: a later success must not mask a failure)
     HIP_TRY(mark(c, 1));
@@ -1163,7 +1229,8 @@ int step(svo_group* c, Step& s) {
 // frame ids: the group is marked failed and rejects further frames instead of tracking on.
 int grp_new_images(svo_group* c, const uint8_t* const* left, const uint8_t* const* right, int stride,
                    const float* time_stamps, int mem) {
-    if (!c || !left || !right || !time_stamps || stride < c->width)
+    if (!c || !left || (!right && c->fmt->buffers == 2) || !time_stamps ||
+        (long long)stride < (long long)ingest_row_pixels(*c->fmt, c->width) * c->fmt->channels)
         return svo_set_error(SVO_ERR_INVALID, "svo_new_images: bad arguments");
     if (c->failed)
         return svo_set_error(SVO_ERR_INVALID, "svo_new_images: an earlier frame of this ctx failed; create a new ctx");

@@ -13,7 +13,8 @@ struct GroupDelete { void operator()(svo_group* g) const; };   // synchronises t
 using Group = std::unique_ptr<svo_group, GroupDelete>;
 
 int grp_create(const svo_camera_settings* cam, int width, int height, int n_sequences, int device, Group* out);
-// one frame of every sequence whose two images are not NULL; after a failure the group rejects further frames
+// one frame of every sequence whose two images are not NULL (a one-buffer input format: whose left[s] is not NULL;
+// right may then be null); after a failure the group rejects further frames
 int grp_new_images(svo_group* g, const uint8_t* const* left, const uint8_t* const* right, int stride,
                    const float* time_stamps, int mem);
 // the named sequences (indices in the group) end; their slots are empty until their next frame. Runs between two
@@ -25,6 +26,9 @@ void grp_set_exact_pinv(svo_group* g, int on);
 // rectification of every frame from the next one on: maps[0] the left image's, maps[1] the right image's
 // (owned by the ctx, device memory that stays valid while set); nullptr: off
 void grp_set_rectification(svo_group* g, const svo::RemapMap* maps);
+// the input format (SVO_INPUT_*, a valid one) of every frame from the next one on. A format that converts gets its
+// image table here, the first time: a failure leaves the group's setting as it was.
+int grp_set_input_format(svo_group* g, int format);
 void grp_enable_timing(svo_group* g, int on);
 svo_totals grp_totals(const svo_group* g);
 const std::vector<svo_launch_shape>& grp_launch_shapes(const svo_group* g);   // (svo_ctx_get_launch_shapes)

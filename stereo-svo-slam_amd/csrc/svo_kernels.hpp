@@ -82,6 +82,36 @@ void launch_remap_prep(const float* map_x, const float* map_y, const RemapMap& m
 // n_sides = 1: map[0] and img[0..n); 2: both sides in one launch
 void launch_remap(const RemapLaunch& a, int n_sides, hipStream_t stream);
 
+// ------------------------------------------------------------ input formats (ingest.hip)
+// The per-pixel step of the reference's ImageInput classes: gray from colour (cvtColor's 15-bit fixed point),
+// channel extract, and the halves of a side-by-side frame. One output image of the launch:
+enum { INGEST_COPY = 0, INGEST_GRAY = 1 };
+struct IngestImg {
+    ImgView src;                  // the caller's buffer: data, pitch; w x h = the OUTPUT size
+    ImgView dst;                  // w x h
+    int step;                     // bytes per source pixel: 1 or 3
+    int col0;                     // source column of output column 0
+    int op;                       // INGEST_COPY: byte `channel` of the pixel; INGEST_GRAY: (sum weight[i] * byte i + 2^14) >> 15
+    int channel;
+    int weight[3];
+};
+// one side of an input format: which of the sequence's buffers (0 = left[s], 1 = right[s]), the start column in
+// units of the output width, the operation
+struct IngestSide {
+    int buffer, start, op, channel;
+    int weight[3];
+};
+struct IngestFormat {
+    int buffers, channels;        // buffers per sequence (1 or 2), bytes per pixel (1 or 3)
+    IngestSide left, right;
+};
+const IngestFormat* ingest_format(int format);             // SVO_INPUT_*; null: no such format
+int ingest_row_pixels(const IngestFormat& f, int w);       // pixels a buffer row holds at least, for outputs of width w
+// the table entry of one side (0 left, 1 right) read from `buffer` (pitch `stride`) into dst
+IngestImg ingest_image(const IngestFormat& f, int side, const uint8_t* buffer, int stride, const ImgView& dst);
+// n output images of w x h (every dst of the table), n <= 65535
+void launch_ingest(const IngestImg* d_imgs, int n, int w, int h, hipStream_t stream);
+
 // ------------------------------------------------- sparse image alignment
 struct SiaArgs {
     ImgView prev[SVO_MAX_PYRAMID_LEVELS];

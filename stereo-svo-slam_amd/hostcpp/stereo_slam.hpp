@@ -21,17 +21,37 @@ public:
     // svo_ctx_set_fast_solver: off (default) = the reference's Gauss-Newton arithmetic, bit for bit
     void set_fast_solver(bool on) { fast = on; if (ctx) check(svo_ctx_set_fast_solver(ctx, on ? 1 : 0)); }
 
+    // svo_ctx_set_input_format: the frames of new_image are buffers of that format (SVO_INPUT_*) from the next one
+    // on, converted to gray and split on the GPU (what VideoInput / EconInput do before new_image in the reference)
+    void set_input_format(int fmt) {
+        svo_input_layout info;
+        check(svo_input_format_info(fmt, 1, &info));
+        format = fmt;
+        if (ctx) check(svo_ctx_set_input_format(ctx, fmt));
+    }
+
     // void new_image(const cv::Mat& left, const cv::Mat& right, const float time_stamp)
     void new_image(const Image8& left, const Image8& right, const float time_stamp) {
-        if (!ctx) {
-            check(svo_ctx_create(&camera_settings, left.cols, left.rows, 1, device, &ctx));
-            if (fast) check(svo_ctx_set_fast_solver(ctx, 1));
-        }
+        create(left.cols, left.rows);
         check(svo_new_image(ctx, left.data, left.step, right.data, right.step, left.cols, left.rows,
                             time_stamp));
         last_ts = time_stamp;
     }
+    // one buffer per frame (SVO_INPUT_SBS_*: cols = 2 x the image width; SVO_INPUT_CH3_ECON): pixels of `channels` bytes
+    void new_image(const Image8& frame, int channels, const float time_stamp) {
+        svo_input_layout info;
+        check(svo_input_format_info(format, 1, &info));
+        if (info.buffers != 1 || info.channels != channels) throw std::runtime_error("new_image(frame): the input format takes other buffers");
+        create(frame.cols / info.min_row_pixels, frame.rows);
+        check(svo_new_image(ctx, frame.data, frame.step, nullptr, 0, frame.cols / info.min_row_pixels, frame.rows, time_stamp));
+        last_ts = time_stamp;
+    }
+    void new_image(const Image8C3& frame, const float time_stamp) { new_image(Image8{frame.data, frame.cols, frame.rows, frame.step}, 3, time_stamp); }
 #ifdef SVO_FACADE_HAVE_OPENCV
+    void new_image(const cv::Mat& frame, const float time_stamp) {
+        CV_Assert(frame.type() == CV_8U || frame.type() == CV_8UC3);
+        new_image(Image8{frame.data, frame.cols, frame.rows, (int)frame.step}, frame.channels(), time_stamp);
+    }
     void new_image(const cv::Mat& left, const cv::Mat& right, const float time_stamp) {
         new_image(view_of(left), view_of(right), time_stamp);
     }
@@ -80,6 +100,12 @@ public:
     }
 
 private:
+    void create(int width, int height) {
+        if (ctx) return;
+        check(svo_ctx_create(&camera_settings, width, height, 1, device, &ctx));
+        if (fast) check(svo_ctx_set_fast_solver(ctx, 1));
+        if (format != SVO_INPUT_GRAY_PAIR) check(svo_ctx_set_input_format(ctx, format));
+    }
     void read_keyframe(int id, KeyFrame& kf) {
         int n = 0;
         Pose p{};
@@ -95,6 +121,7 @@ private:
     svo_ctx* ctx = nullptr;
     double last_ts = 0;
     bool fast = false;
+    int format = SVO_INPUT_GRAY_PAIR;
 };
 
 }  // namespace svo_amd

@@ -132,6 +132,10 @@ struct Image8 {            // CV_8U single channel view in host memory
     const uint8_t* data;
     int cols, rows, step;
 };
+struct Image8C3 {          // CV_8UC3 view in host memory: interleaved 3-byte pixels, step in bytes
+    const uint8_t* data;
+    int cols, rows, step;
+};
 #ifdef SVO_FACADE_HAVE_OPENCV
 inline Image8 view_of(const cv::Mat& m) {
     CV_Assert(m.type() == CV_8U);

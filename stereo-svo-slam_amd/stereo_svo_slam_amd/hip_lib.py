@@ -33,7 +33,13 @@ SYMBOLS = (
     "svo_detect_keypoints", "svo_detect_shape",
     "svo_ctx_restart_sequences", "svo_get_finished_runs", "svo_get_finished_run",
     "svo_drop_finished_runs", "svo_ctx_get_memory",
+    "svo_input_format_info", "svo_convert_frames", "svo_ctx_set_input_format",
 )
+
+# svo_ctx_set_input_format / svo_convert_frames: how the buffers of a sequence become its two gray images
+INPUT_GRAY_PAIR, INPUT_BGR_PAIR, INPUT_RGB_PAIR, INPUT_SBS_GRAY, INPUT_SBS_BGR, INPUT_SBS_RGB, INPUT_CH3_ECON = range(7)
+INPUT_FORMATS = ("gray_pair", "bgr_pair", "rgb_pair", "sbs_gray", "sbs_bgr", "sbs_rgb", "ch3_econ")
+INGEST_COPY, INGEST_GRAY = 0, 1
 
 
 class SvoError(RuntimeError):
@@ -61,6 +67,18 @@ class CameraSettings(C.Structure):
 class Image(C.Structure):
     _fields_ = [("data", C.c_void_p), ("width", C.c_int32), ("height", C.c_int32),
                 ("stride", C.c_int32)]
+
+
+class InputSide(C.Structure):
+    """svo_input_side (include/svo_hip.h)."""
+    _fields_ = [("buffer", C.c_int32), ("start_column", C.c_int32), ("op", C.c_int32), ("channel", C.c_int32),
+                ("weight", C.c_int32 * 3)]
+
+
+class InputLayout(C.Structure):
+    """svo_input_layout (include/svo_hip.h)."""
+    _fields_ = [("buffers", C.c_int32), ("channels", C.c_int32), ("min_row_pixels", C.c_int32),
+                ("left", InputSide), ("right", InputSide)]
 
 
 GN_TRACE_DTYPE = np.dtype([("level", "<i4"), ("n_gradient", "<i4"), ("n_cost", "<i4"),
@@ -109,6 +127,22 @@ def detect_shape(width, height, n_levels, grid_width, grid_height):
     out = [C.c_int(0) for _ in range(4)]
     _check(lib().svo_detect_shape(width, height, n_levels, grid_width, grid_height, *[C.byref(o) for o in out]))
     return tuple(o.value for o in out)
+
+
+def input_format_info(fmt, width):
+    """svo_input_format_info (host only): the InputLayout of input format `fmt` for images of `width` pixels."""
+    out = InputLayout()
+    _check(lib().svo_input_format_info(int(fmt), int(width), C.byref(out)))
+    return out
+
+
+def _raw_img(t, channels):
+    """a uint8 device buffer [H, W] (one byte per pixel) or [H, W, 3] (interleaved) as an svo_image: width and
+    height in pixels, stride in bytes"""
+    assert t.dtype == torch.uint8 and t.is_cuda and t.dim() == (3 if channels == 3 else 2) and t.stride(-1) == 1
+    if channels == 3:
+        assert t.shape[2] == 3 and t.stride(1) == 3
+    return Image(t.data_ptr(), t.shape[1], t.shape[0], t.stride(0))
 
 
 def _imgs(ts, n=None):
@@ -197,6 +231,24 @@ class Handle:
         outs = [torch.empty((h, w), dtype=torch.uint8, device=map_x.device) for _ in srcs]
         _check(lib().svo_remap_linear(self._h, len(srcs), _imgs(srcs), _imgs(outs), _ptr(map_x), _ptr(map_y)))
         return outs
+
+    # -- I ----------------------------------------------------------------
+    def convert_frames(self, fmt, src_a, src_b, width=None, lefts=None, rights=None):
+        """svo_convert_frames: the buffers src_a[i] (and src_b[i] for the pair formats, else None) of input format
+        `fmt` (uint8 device tensors, [H, W'] or [H, W', 3], unit stride inside a row) into gray images: two lists
+        (left, right) of uint8 [H, width] device tensors (made here unless lefts / rights are given). width: of the
+        images (default: of the buffer, halved for the side-by-side formats)."""
+        info = input_format_info(fmt, 1)
+        if width is None:
+            width = src_a[0].shape[1] // info.min_row_pixels
+        n, hgt = len(src_a), src_a[0].shape[0]
+        if lefts is None:
+            lefts = [torch.empty((hgt, width), dtype=torch.uint8, device=src_a[0].device) for _ in range(n)]
+            rights = [torch.empty((hgt, width), dtype=torch.uint8, device=src_a[0].device) for _ in range(n)]
+        arr_a = (Image * n)(*[_raw_img(t, info.channels) for t in src_a])
+        arr_b = (Image * n)(*[_raw_img(t, info.channels) for t in src_b]) if info.buffers == 2 else None
+        _check(lib().svo_convert_frames(self._h, int(fmt), n, arr_a, arr_b, _imgs(lefts), _imgs(rights)))
+        return lefts, rights
 
     # -- P2 ---------------------------------------------------------------
     def build_lk_pyramid(self, img, win, max_levels=3):

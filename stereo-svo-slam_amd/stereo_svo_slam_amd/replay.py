@@ -9,10 +9,15 @@ Host bookkeeping only; every frame goes through StereoSlam.new_image (libsvo_hip
     python -m stereo_svo_slam_amd.replay --settings EuRoC.yaml --euroc /data/MH_02_easy/mav0/ -t traj.csv
     python -m stereo_svo_slam_amd.replay --settings EuRoC.yaml --euroc /data/MH_02_easy/mav0/ --gpu-rectify
     python -m stereo_svo_slam_amd.replay --settings Blender.yaml --sbs 'frames/%06d.png' -t traj.csv
+    python -m stereo_svo_slam_amd.replay --settings Blender.yaml --sbs 'frames/%06d.png' --gpu-ingest
+    python -m stereo_svo_slam_amd.replay --settings Econ.yaml --interleaved 'frames/%06d.png' --gpu-ingest
     python -m stereo_svo_slam_amd.replay --settings EuRoC.yaml --pairs 'seq/%06d_left.png,seq/%06d_right.png'
 
 Inputs follow the reference's conventions (the library's `left` is the physically RIGHT camera):
-EurocInput (src/app/euroc_input.cpp:48-70,100-105), VideoInput (src/app/video_input.cpp:35-36).
+EurocInput (src/app/euroc_input.cpp:48-70,100-105), VideoInput (src/app/video_input.cpp:29-36), EconInput
+(src/app/econ_input.cpp:102-106). Colour frames become gray with cvtColor's arithmetic (bgr2gray), on the host or,
+with --gpu-ingest, inside the library from the raw frame (svo_ctx_set_input_format): both give the same CSV, and
+frames that are gray already give the CSV they gave before colour frames were converted this way.
 With $SVO_DATA set (a EuRoC `mav0/` directory, or a directory of side-by-side frames) and no
 explicit input that data is used; otherwise the seeded synthetic sequence.
 """
@@ -113,9 +118,29 @@ def remap_linear(img, map_x, map_y):
     return np.clip(np.rint(v), 0, 255).astype(np.uint8)
 
 
-def _gray(path):
+def bgr2gray(img, order="bgr"):
+    """cv::cvtColor(BGR2GRAY / RGB2GRAY) of a uint8 [..., 3] array, OpenCV 4.x's 15-bit fixed point:
+    Y = (3735 B + 19235 G + 9798 R + 2^14) >> 15 (the weights sum to 2^15: R = G = B = v gives v)."""
+    c = np.asarray(img).astype(np.uint32)
+    b, r = (c[..., 0], c[..., 2]) if order == "bgr" else (c[..., 2], c[..., 0])
+    return ((3735 * b + 19235 * c[..., 1] + 9798 * r + (1 << 14)) >> 15).astype(np.uint8)
+
+
+def _load(path):
+    """a decoded frame as the reference's cv::imread / VideoCapture hands it out: uint8 [H, W] for a gray file,
+    [H, W, 3] in B, G, R order for a colour one (palette and alpha files are decoded to colour first)"""
     from PIL import Image
-    return np.ascontiguousarray(np.array(Image.open(path).convert("L")))
+    im = Image.open(path)
+    if im.mode == "L":
+        return np.ascontiguousarray(np.array(im))
+    if im.mode in ("1", "I", "I;16", "F", "LA"):
+        return np.ascontiguousarray(np.array(im.convert("L")))
+    return np.ascontiguousarray(np.array(im.convert("RGB"))[..., ::-1])
+
+
+def _gray(path):
+    img = _load(path)
+    return img if img.ndim == 2 else np.ascontiguousarray(bgr2gray(img))
 
 
 class EurocInput:
@@ -170,21 +195,53 @@ class EurocInput:
 
 class SideBySideInput:
     """VideoInput (src/app/video_input.cpp:25-45) on decoded frames: every image holds both cameras
-    side by side; `right` is the LEFT half, `left` the RIGHT half; time stamps advance by 1/fps from
-    1/fps."""
+    side by side; colour frames become gray first (cvtColor(BGR2GRAY), :29-31: bgr2gray); `right` is the LEFT
+    half, `left` the RIGHT half; time stamps advance by 1/fps from 1/fps. raw=True: read() hands out the undivided
+    frame ([H, 2W] gray or [H, 2W, 3] B, G, R) as `left` and None as `right`, for the library to convert and split
+    (input_format())."""
 
-    def __init__(self, pattern, n_frames, fps=30.0):
-        self.pattern, self.n, self.fps = pattern, n_frames, fps
+    def __init__(self, pattern, n_frames, fps=30.0, raw=False):
+        self.pattern, self.n, self.fps, self.raw = pattern, n_frames, fps, raw
 
     def __len__(self):
         return self.n
 
+    def input_format(self, k=0):
+        """the library's input format name for the raw frames (by the channels of frame k)"""
+        return "sbs_gray" if _load(self.pattern % k).ndim == 2 else "sbs_bgr"
+
     def read(self, k):
+        if self.raw:
+            return _load(self.pattern % k), None, (k + 1) / self.fps
         img = _gray(self.pattern % k)
         w = img.shape[1] // 2
         right = np.ascontiguousarray(img[:, :w])
         left = np.ascontiguousarray(img[:, w:2 * w])
         return left, right, (k + 1) / self.fps
+
+
+class InterleavedInput:
+    """EconInput (src/app/econ_input.cpp:102-106) on decoded frames: every image is one 3-channel frame whose
+    channel 1 is the `right` image and channel 2 the `left` one; time stamps advance by 1/fps from 1/fps.
+    raw=True: read() hands out the frame itself ([H, W, 3]) as `left` and None as `right` (input format ch3_econ).
+    The channels are those of the stored file read in B, G, R order."""
+
+    def __init__(self, pattern, n_frames, fps=30.0, raw=False):
+        self.pattern, self.n, self.fps, self.raw = pattern, n_frames, fps, raw
+
+    def __len__(self):
+        return self.n
+
+    def input_format(self, k=0):
+        return "ch3_econ"
+
+    def read(self, k):
+        img = _load(self.pattern % k)
+        if img.ndim != 3:
+            raise ValueError("InterleavedInput needs 3-channel frames")
+        if self.raw:
+            return img, None, (k + 1) / self.fps
+        return np.ascontiguousarray(img[..., 2]), np.ascontiguousarray(img[..., 1]), (k + 1) / self.fps
 
 
 # END_MEASUREMENT names of the reference (src/lib/stereo_slam.cpp:66-86,140,227,235;
@@ -263,15 +320,18 @@ def error_report(test_rows, reference_rows):
 class Replay:
     """process_image loop: only the time inside new_image is accumulated (slam_app.cpp:186-190)."""
 
-    def __init__(self, settings, device=0, time_trace=False, fast=False, rectify_maps=None):
+    def __init__(self, settings, device=0, time_trace=False, fast=False, rectify_maps=None, input_format=None):
         """fast=False keeps the library default: the reference-order Gauss-Newton (bit-exact traces).
-        rectify_maps = (left maps, right maps): the frames fed are raw and are rectified on the GPU."""
+        rectify_maps = (left maps, right maps): the frames fed are raw and are rectified on the GPU.
+        input_format: the frames fed are raw buffers of that format (StereoSlam.set_input_format)."""
         self.settings = settings
         self.slam = StereoSlam(settings, device=device)
         if fast:
             self.slam.set_fast_solver(True)
         if rectify_maps is not None:
             self.slam.set_rectification(*rectify_maps)
+        if input_format is not None:
+            self.slam.set_input_format(input_format)
         self.cumulative = []
         self._t = 0.0
         self.time_trace = time_trace
@@ -319,10 +379,8 @@ class Replay:
 
 
 def _load_pair(pattern, k):
-    from PIL import Image
     lp, rp = pattern.split(",")
-    load = lambda p: np.ascontiguousarray(np.array(Image.open(p % k).convert("L")))
-    return load(lp), load(rp)
+    return _gray(lp % k), _gray(rp % k)
 
 
 def main(argv=None):
@@ -338,6 +396,9 @@ def main(argv=None):
     ap.add_argument("--exact", action="store_true", help="no-op (the reference-order mode is the default)")
     ap.add_argument("--gpu-rectify", action="store_true",
                     help="--euroc: hand the raw frames to the library and rectify them on the GPU (bit-exact cv::remap)")
+    ap.add_argument("--interleaved", help="'frames/%%06d.png' 3-channel frames: EconInput conventions (right = channel 1, left = channel 2)")
+    ap.add_argument("--gpu-ingest", action="store_true",
+                    help="--sbs / --interleaved: hand the raw frames to the library, which converts and splits them on the GPU")
     ap.add_argument("--frames", type=int, default=100)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--rate", type=float, default=20.0, help="frames per second of the time stamps")
@@ -348,7 +409,8 @@ def main(argv=None):
     gt = None
     rect = None
     data = os.environ.get("SVO_DATA")
-    if data and not (args.synthetic or args.pairs or args.euroc or args.sbs):
+    fmt = None
+    if data and not (args.synthetic or args.pairs or args.euroc or args.sbs or args.interleaved):
         if os.path.exists(os.path.join(data, "cam0", "data.csv")):
             args.euroc = data
         else:
@@ -362,7 +424,13 @@ def main(argv=None):
         frames = (src.read(k) for k in range(n))
     elif args.sbs and args.settings:
         settings = read_settings(args.settings)
-        src = SideBySideInput(args.sbs, args.frames, args.rate)
+        src = SideBySideInput(args.sbs, args.frames, args.rate, raw=args.gpu_ingest)
+        fmt = src.input_format() if args.gpu_ingest else None
+        frames = (src.read(k) for k in range(args.frames))
+    elif args.interleaved and args.settings:
+        settings = read_settings(args.settings)
+        src = InterleavedInput(args.interleaved, args.frames, args.rate, raw=args.gpu_ingest)
+        fmt = src.input_format() if args.gpu_ingest else None
         frames = (src.read(k) for k in range(args.frames))
     elif args.synthetic:
         cfg, L, R, gt, ts = synth.make_sequence(args.synthetic, args.frames, args.seed, device="cpu")
@@ -372,10 +440,12 @@ def main(argv=None):
         settings = read_settings(args.settings)
         frames = ((*_load_pair(args.pairs, k), k / args.rate) for k in range(args.frames))
     else:
-        ap.error("give --synthetic, or --settings with --euroc / --sbs / --pairs (or $SVO_DATA)")
+        ap.error("give --synthetic, or --settings with --euroc / --sbs / --interleaved / --pairs (or $SVO_DATA)")
     if args.gpu_rectify and rect is None:
         ap.error("--gpu-rectify needs --euroc with --settings")
-    rp = Replay(settings, args.device, args.time_trace, args.fast, rectify_maps=rect)
+    if args.gpu_ingest and fmt is None:
+        ap.error("--gpu-ingest needs --sbs or --interleaved with --settings")
+    rp = Replay(settings, args.device, args.time_trace, args.fast, rectify_maps=rect, input_format=fmt)
     for left, right, t in frames:
         rp.feed(left, right, t)
     rows = rp.rows()

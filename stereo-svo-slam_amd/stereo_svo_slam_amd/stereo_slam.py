@@ -172,6 +172,36 @@ class StereoSlamBatch:
             ptrs = [m.ctypes.data_as(C.c_void_p) for m in maps]
         _check(lib().svo_ctx_set_rectification(self._ctx, *ptrs, 1 if on_dev else 0))
 
+    def set_input_format(self, fmt):
+        """svo_ctx_set_input_format: from the next frame on the frames are buffers of input format `fmt`
+        (hip_lib.INPUT_*, or its name in hip_lib.INPUT_FORMATS) and become gray images on the GPU (cvtColor's
+        15-bit fixed point, channel extract, the halves of a side-by-side frame). The pair formats take
+        [H, W, 3] lefts and rights; the one-buffer formats take ONE list of [H, >= 2W] (sbs_gray),
+        [H, >= 2W, 3] (sbs_bgr / sbs_rgb) or [H, W, 3] (ch3_econ) frames as `lefts` (rights: None)."""
+        if isinstance(fmt, str):
+            fmt = hip_lib.INPUT_FORMATS.index(fmt)
+        hip_lib.input_format_info(fmt, self.width or 1)      # (raises for an unknown format)
+        self._format = int(fmt)
+        if self._ctx:                      # (StereoSlam creates its ctx with the first image)
+            _check(lib().svo_ctx_set_input_format(self._ctx, self._format))
+
+    def _frame_layout(self):
+        """(buffers per sequence, the shape a buffer has at least, bytes per pixel) of the input format in force"""
+        if not getattr(self, "_format", 0):        # (the default asks the library nothing)
+            return 2, (self.height, self.width), 1
+        info = hip_lib.input_format_info(self._format, self.width)
+        shape = (self.height, info.min_row_pixels) + ((3,) if info.channels == 3 else ())
+        return info.buffers, shape, info.channels
+
+    @staticmethod
+    def _fits(arr, shape, channels):
+        """a frame buffer: the rows and channels of `shape`, at least its columns, pixels and channels dense"""
+        sh = tuple(arr.shape)
+        if len(sh) != len(shape) or sh[0] != shape[0] or sh[1] < shape[1] or sh[2:] != shape[2:]:
+            return False
+        strides = arr.stride() if isinstance(arr, torch.Tensor) else arr.strides
+        return strides[-1] == 1 and (channels == 1 or strides[1] == 3)
+
     def enable_timing(self, on=True):
         self._timing = bool(on)
         if self._ctx:                      # (StereoSlam creates its ctx with the first image)
@@ -181,7 +211,8 @@ class StereoSlamBatch:
         """lefts/rights: per sequence a uint8 [H, W] numpy array (host) or torch CUDA tensor; None for
         a sequence that has no frame at this step (it sits the step out: sequences of a ctx may have
         different lengths; an empty slot starts its sequence with the first frame it gets)."""
-        assert len(lefts) == self.n and len(rights) == self.n
+        buffers, shape, channels = self._frame_layout()
+        assert len(lefts) == self.n and (buffers == 1 or len(rights) == self.n)
         if all(x is None for x in lefts):
             return
         on_dev = isinstance(next(x for x in lefts if x is not None), torch.Tensor)
@@ -192,14 +223,14 @@ class StereoSlamBatch:
         for s in range(self.n):
             if lefts[s] is None:
                 continue
-            for arr, dst in ((lefts[s], ptrs_l), (rights[s], ptrs_r)):
+            for arr, dst in ((lefts[s], ptrs_l), (rights[s], ptrs_r))[:buffers]:
                 if on_dev:
-                    assert arr.is_cuda and arr.dtype == torch.uint8 and arr.stride(1) == 1
+                    assert arr.is_cuda and arr.dtype == torch.uint8
                     st, p = arr.stride(0), arr.data_ptr()
                 else:
                     arr = np.ascontiguousarray(arr, dtype=np.uint8)
                     st, p = arr.strides[0], arr.ctypes.data
-                assert tuple(arr.shape) == (self.height, self.width)
+                assert self._fits(arr, shape, channels), (tuple(arr.shape), shape)
                 assert stride is None or stride == st
                 stride = st
                 keep.append(arr)
@@ -213,7 +244,9 @@ class StereoSlamBatch:
         """Pre-build the argument arrays of one step (keeps Python out of a timed loop); pass the
         result to new_images_packed / submit_packed. The frames are torch uint8 tensors, all on
         the GPU (SVO_MEM_DEVICE; with borrow=True SVO_MEM_DEVICE_BORROW: used in place, the caller
-        keeps them alive and unchanged) or all in host memory (SVO_MEM_HOST; pinned for full PCIe rate)."""
+        keeps them alive and unchanged) or all in host memory (SVO_MEM_HOST; pinned for full PCIe rate).
+        With a one-buffer input format (set_input_format) `lefts` holds the frames and `rights` is ignored."""
+        buffers, shape, channels = self._frame_layout()
         ptrs_l = (C.c_void_p * self.n)()
         ptrs_r = (C.c_void_p * self.n)()
         some = next(x for x in lefts if x is not None)
@@ -222,9 +255,9 @@ class StereoSlamBatch:
         for s in range(self.n):
             if lefts[s] is None:                            # the sequence sits this step out
                 continue
-            for arr, dst in ((lefts[s], ptrs_l), (rights[s], ptrs_r)):
-                assert arr.is_cuda == on_dev and arr.dtype == torch.uint8 and arr.stride(1) == 1
-                assert tuple(arr.shape) == (self.height, self.width) and arr.stride(0) == stride
+            for arr, dst in ((lefts[s], ptrs_l), (rights[s], ptrs_r))[:buffers]:
+                assert arr.is_cuda == on_dev and arr.dtype == torch.uint8
+                assert self._fits(arr, shape, channels) and arr.stride(0) == stride, (tuple(arr.shape), shape)
                 dst[s] = arr.data_ptr()
         ts = (C.c_float * self.n)(*[float(t) for t in time_stamps])
         return ptrs_l, ptrs_r, stride, ts, (lefts, rights), (2 if borrow else 1) if on_dev else 0
@@ -356,11 +389,23 @@ class StereoSlam(StereoSlamBatch):
         if width is not None:
             super().__init__(camera_settings, width, height, 1, device)
 
-    def new_image(self, left, right, time_stamp):
+    def set_input_format(self, fmt):
+        if self._ctx is None:              # (kept until the first frame makes the ctx)
+            self._format = hip_lib.INPUT_FORMATS.index(fmt) if isinstance(fmt, str) else int(fmt)
+            hip_lib.input_format_info(self._format, 1)
+        else:
+            super().set_input_format(fmt)
+
+    def new_image(self, left, right=None, time_stamp=0.0):
+        """one frame; with a one-buffer input format `left` is the frame and `right` is ignored"""
         if self._ctx is None:   # the reference learns the image size from the first frame
             cam, device = self._pending
-            h, w = left.shape
+            h, w = left.shape[:2]
+            if getattr(self, "_format", 0):
+                w //= hip_lib.input_format_info(self._format, 1).min_row_pixels   # (side by side: half the frame)
             super().__init__(cam, w, h, 1, device)
+            if getattr(self, "_format", 0):
+                super().set_input_format(self._format)
             if getattr(self, "_fast", False):
                 self.set_fast_solver(True)
             if getattr(self, "_timing", False):
