@@ -321,6 +321,65 @@ int svo_update_pose(svo_ctx *ctx, int seq, const float pose[6], const float spee
                     const float pose_var[6], const float speed_var[6], double dt,
                     float filtered[6]);
 
+/* ---- bulk export: the state of many slots in one ordered launch ------------
+ * The reference reads its state one object at a time (get_frame / get_keyframes, src/lib/stereo_slam.cpp:273-289),
+ * and so do the getters above: each waits for every queue of the ctx and makes twelve blocking copies per slot.
+ * An export is the batched form: the groups that own a named slot pack the slots' keypoints into the getters'
+ * records (svo_kp2d, svo_kp3d, svo_kp_info, byte for byte; svo_kp_info._pad is 0) with one kernel launch each and
+ * deliver them into host or device memory; the host writes one svo_export_segment per named slot.
+ *
+ * Named slots: seqs == NULL names every slot in order (n is ignored); otherwise segment i describes slot seqs[i].
+ * Placement: with R = svo_export_capacity's records per slot, group g packs its named slots densely, in named
+ * order, from record (named slots of earlier groups) * R on; every segment's `first` is rounded up to a multiple
+ * of 4, so a segment starts 16-byte aligned in all three arrays (given 16-byte aligned arrays; others work, more
+ * slowly; 4-byte alignment is required). Records outside the segments are not written by the kernel: neither the
+ * up to 3 records of padding between two segments nor the space between two groups. (Host mode copies a group's
+ * used prefix, first segment to last, in one piece per array: there the padding records between the group's
+ * segments receive unspecified bytes; the space after a group's last segment stays untouched.)
+ * An empty slot (never started, or restarted) gives n = 0, frame_id = -1 and a zero pose. */
+enum { SVO_EXPORT_FRAMES = 0,          /* the current frame of each named slot (what svo_get_frame_keypoints + svo_get_pose return) */
+       SVO_EXPORT_LAST_KEYFRAMES = 1 };/* the newest keyframe of each named slot (svo_get_keyframe(seq, count-1)) */
+
+typedef struct svo_export_segment {   /* 64 bytes, one per named slot, written by the host */
+    int32_t seq, run;                 /* slot and ordinal of its run (svo_run_info.run)                    */
+    int32_t frame_id;                 /* of the slot's current frame; -1: empty slot                        */
+    int32_t keyframe_id;              /* LAST_KEYFRAMES: id exported (-1: the slot has none); FRAMES: -1   */
+    int32_t is_keyframe;              /* svo_frame_stats.is_keyframe of the current frame                   */
+    int32_t n;                        /* keypoints exported                                                 */
+    int64_t first;                    /* they are records [first, first + n) of every array; multiple of 4 */
+    float   pose[6];                  /* FRAMES: svo_get_pose; LAST_KEYFRAMES: the keyframe's pose          */
+    float   time_stamp;               /* of the slot's current frame                                        */
+    int32_t _pad;
+} svo_export_segment;
+
+typedef struct svo_export_dst {
+    svo_export_segment *segments;     /* HOST memory always, >= n entries                                   */
+    svo_kp2d *kps2d; svo_kp3d *kps3d; svo_kp_info *info;   /* host or device (mem); any may be NULL: skipped */
+    int64_t capacity;                 /* records each non-NULL array holds                                  */
+} svo_export_dst;
+
+/* records one slot can take at most (the group's keypoint capacity: 2 * grid cells + 128, rounded up to a
+ * multiple of 64), without a GPU. Settings svo_ctx_create rejects: SVO_ERR_INVALID */
+int svo_export_capacity(const svo_camera_settings *cam, int width, int height, int *records_per_sequence);
+/* Queued like a frame set: it sees every frame set and restart submitted before it and none submitted after it,
+ * and it does not wait for other groups (only groups that own a named slot get work). dst (copied), the segments
+ * and the arrays stay valid until svo_wait, after which everything is delivered. mem: SVO_MEM_HOST or
+ * SVO_MEM_DEVICE, of the three arrays. Rejected with nothing queued: an index out of range or named twice, a bad
+ * `what` or `mem`, a misaligned array (SVO_ERR_INVALID); dst->capacity < named slots * R while an array is given
+ * (SVO_ERR_CAPACITY: the bound, not the counts, so that it can be checked here); a failed ctx, like
+ * svo_submit_images. Host mode goes through a device staging block of (slots of the group) * R * 64 bytes per
+ * group, made by the group's first host-mode export (svo_memory.device_bytes) and one copy per array; a ctx that
+ * never exports pays nothing. An export that fails on the device side (a HIP error, e.g. no memory for the staging
+ * block) is reported by svo_wait and fails the ctx like a frame that fails: what is still queued is dropped. */
+int svo_submit_export(svo_ctx *ctx, int what, const int *seqs, int n, const svo_export_dst *dst, int mem);
+int svo_export(svo_ctx *ctx, int what, const int *seqs, int n, const svo_export_dst *dst, int mem); /* submit + wait */
+/* stage entry: n_sets SoA keypoint sets (host array of views onto device memory, sets[i].n valid entries;
+ * every array 4-byte aligned) into AoS records at first[i] (host array, >= 0); kps2d / kps3d / info are device
+ * memory, any may be NULL. The tracker's launch: keypoints [0, n) of a set are read, records [first, first + n)
+ * written, nothing else. */
+int svo_pack_keypoints(svo_handle *h, int n_sets, const svo_keypoints *sets, const int64_t *first,
+                       svo_kp2d *kps2d, svo_kp3d *kps3d, svo_kp_info *info);
+
 /* per-frame diagnostics of the last svo_new_images call */
 typedef struct svo_frame_stats {
     int32_t frame_id;

@@ -33,6 +33,8 @@ struct svo_handle {
     size_t remap_ws_bytes = 0;
     DevPtr<IngestImg> ingest_ws;    // svo_convert_frames: the image table
     size_t ingest_ws_count = 0;
+    DevPtr<ExportTile> export_ws;   // svo_pack_keypoints: the tile table
+    size_t export_ws_count = 0;
 };
 
 extern "C" const char* svo_last_error(void) { return svo_error_text; }
@@ -270,6 +272,45 @@ extern "C" int svo_convert_frames(svo_handle* h, int format, int n, const svo_im
         launch_ingest(h->ingest_ws.get() + i0, std::min(per_launch, total - i0), w, hgt, h->stream);
         HIP_TRY(hipGetLastError());
     }
+    return SVO_OK;
+}
+
+extern "C" int svo_pack_keypoints(svo_handle* h, int n_sets, const svo_keypoints* sets, const int64_t* first,
+                                  svo_kp2d* kps2d, svo_kp3d* kps3d, svo_kp_info* info) {
+    CHECK_H(h);
+    if (n_sets < 0 || (n_sets > 0 && (!sets || !first)))
+        return svo_set_error(SVO_ERR_INVALID, "svo_pack_keypoints: bad arguments");
+    for (const void* p : {(const void*)kps2d, (const void*)kps3d, (const void*)info})
+        if ((uintptr_t)p & 3) return svo_set_error(SVO_ERR_INVALID, "svo_pack_keypoints: an output array is not 4-byte aligned");
+    std::vector<ExportTile> tiles;
+    for (int i = 0; i < n_sets; i++) {
+        const svo_keypoints& k = sets[i];
+        if (k.n < 0 || first[i] < 0) return svo_set_error(SVO_ERR_INVALID, "svo_pack_keypoints: set %d: n and first must be >= 0", i);
+        if (k.n == 0) continue;
+        KpsDev d;
+        d.kps2d = k.kps2d; d.kps3d = k.kps3d; d.flags = k.flags; d.kf_id = k.keyframe_id; d.kp_index = k.keypoint_index;
+        d.outl = k.outlier_count; d.inl = k.inlier_count; d.kfx = k.kf_inv_depth; d.kfP = k.kf_variance;
+        d.score = k.score; d.level_type = k.level_type; d.color = k.color; d.n = nullptr;
+        for (const void* p : {(const void*)d.kps2d, (const void*)d.kps3d, (const void*)d.flags, (const void*)d.kf_id,
+                              (const void*)d.kp_index, (const void*)d.outl, (const void*)d.inl, (const void*)d.kfx,
+                              (const void*)d.kfP, (const void*)d.score, (const void*)d.level_type, (const void*)d.color})
+            if (!p || ((uintptr_t)p & 3))
+                return svo_set_error(SVO_ERR_INVALID, "svo_pack_keypoints: set %d: every array is device memory, 4-byte aligned", i);
+        for (int start = 0; start < k.n; start += EXPORT_TILE)
+            tiles.push_back(export_tile(d, start, std::min(EXPORT_TILE, k.n - start), first[i]));
+    }
+    if (tiles.empty() || (!kps2d && !kps3d && !info)) return SVO_OK;
+    if (tiles.size() > (size_t)INT_MAX) return svo_set_error(SVO_ERR_INVALID, "svo_pack_keypoints: too many keypoints");
+    if (tiles.size() > h->export_ws_count) {
+        HIP_TRY(hipStreamSynchronize(h->stream));      // (the old table may still be read)
+        h->export_ws.reset();
+        h->export_ws_count = 0;
+        HIP_TRY(dev_malloc(h->export_ws, sizeof(ExportTile) * tiles.size()));
+        h->export_ws_count = tiles.size();
+    }
+    HIP_TRY(hipMemcpyAsync(h->export_ws.get(), tiles.data(), sizeof(ExportTile) * tiles.size(), hipMemcpyHostToDevice, h->stream));
+    launch_export(h->export_ws.get(), (int)tiles.size(), kps2d, kps3d, info, h->stream);
+    HIP_TRY(hipGetLastError());
     return SVO_OK;
 }
 

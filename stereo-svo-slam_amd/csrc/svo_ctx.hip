@@ -26,14 +26,25 @@
 // its argument blocks, the other group's kernels keep the GPU busy, and the latency-bound
 // single-workgroup-per-sequence alignment kernel of one group overlaps the window kernels of
 // the other. svo_submit_images() queues a frame set on every group and returns;
-// svo_wait() drains the queues. svo_new_images() = submit + wait.
+// svo_wait() drains the queues. svo_new_images() = submit + wait. Restarts (svo_ctx_restart_sequences) and
+// exports (svo_submit_export) are entries of the same queues, so they are ordered with the frame sets.
 struct svo_ctx {
-    // one entry of a group's queue: a frame set, or (restart non-empty) the end of some of its sequences
+    // the group's share of an svo_submit_export: its named slots (indices in the group) in named order, the
+    // segment each one fills, and the record of the caller's arrays the group packs from
+    struct Export {
+        int what = 0, mem = 0;
+        std::vector<int> seqs, seg;
+        int64_t base = 0;
+        svo_export_dst dst{};
+    };
+    // one entry of a group's queue: a frame set, or (restart non-empty) the end of some of its sequences, or
+    // (exp.seqs non-empty) an export
     struct Job {
         std::vector<const uint8_t*> left, right;
         std::vector<float> ts;
         int stride = 0, mem = 0;
         std::vector<int> restart;        // indices in the group
+        Export exp;
     };
     struct Worker {
         Group g;
@@ -66,7 +77,10 @@ void worker_submit(svo_ctx::Worker& w, svo_ctx::Job&& job);
 
 void worker_run_job(svo_ctx::Worker& w, const svo_ctx::Job& job) {
     if (w.err != SVO_OK || w.ctx_failed->load()) return;   // after a failure (any group) the queues are dropped
-    const int rc = !job.restart.empty()
+    const svo_ctx::Export& e = job.exp;
+    const int rc = !e.seqs.empty()
+                       ? grp_export(w.g.get(), e.what, e.mem, e.seqs.data(), e.seg.data(), (int)e.seqs.size(), w.first, e.base, &e.dst)
+                   : !job.restart.empty()
                        ? grp_restart_sequences(w.g.get(), job.restart.data(), (int)job.restart.size())
                        : grp_new_images(w.g.get(), job.left.data(), job.right.empty() ? nullptr : job.right.data(), job.stride,
                                         job.ts.data(), job.mem);
@@ -245,6 +259,50 @@ extern "C" int svo_ctx_restart_sequences(svo_ctx* c, const int* seqs, int n) {
         if (!job.restart.empty()) worker_submit(w, std::move(job));
     }
     return SVO_OK;
+}
+
+extern "C" int svo_submit_export(svo_ctx* c, int what, const int* seqs, int n, const svo_export_dst* dst, int mem) {
+    if (!c || !dst || !dst->segments || (what != SVO_EXPORT_FRAMES && what != SVO_EXPORT_LAST_KEYFRAMES) ||
+        (mem != SVO_MEM_HOST && mem != SVO_MEM_DEVICE) || (seqs && n < 0))
+        return svo_set_error(SVO_ERR_INVALID, "svo_submit_export: bad arguments (what %d, mem %d)", what, mem);
+    if (!seqs) n = c->B;
+    std::vector<char> named(c->B, 0);
+    for (int i = 0; i < n; i++) {
+        const int s = seqs ? seqs[i] : i;
+        if (s < 0 || s >= c->B || named[s])
+            return svo_set_error(SVO_ERR_INVALID, "svo_submit_export: sequence %d is out of range or named twice", s);
+        named[s] = 1;
+    }
+    for (const void* p : {(const void*)dst->kps2d, (const void*)dst->kps3d, (const void*)dst->info})
+        if ((uintptr_t)p & 3) return svo_set_error(SVO_ERR_INVALID, "svo_submit_export: an array is not 4-byte aligned");
+    const int64_t per_seq = grp_capacity(c->workers[0]->g.get());     // (the same in every group)
+    if ((dst->kps2d || dst->kps3d || dst->info) && dst->capacity < n * per_seq)
+        return svo_set_error(SVO_ERR_CAPACITY, "svo_submit_export: %d slots need arrays of %lld records, capacity %lld", n,
+                             (long long)(n * per_seq), (long long)dst->capacity);
+    if (c->failed.load()) {                      // (as svo_submit_images)
+        const int rc = ctx_drain(c);
+        return rc ? rc : svo_set_error(SVO_ERR_INVALID, "svo_submit_export: an earlier frame of this ctx failed; create a new ctx");
+    }
+    int64_t before = 0;                          // named slots of the groups so far
+    for (auto& wp : c->workers) {
+        svo_ctx::Worker& w = *wp;
+        svo_ctx::Job job;
+        svo_ctx::Export& e = job.exp;
+        for (int i = 0; i < n; i++) {
+            const int s = seqs ? seqs[i] : i;
+            if (s >= w.first && s < w.first + w.count) { e.seqs.push_back(s - w.first); e.seg.push_back(i); }
+        }
+        if (e.seqs.empty()) continue;
+        e.what = what; e.mem = mem; e.dst = *dst; e.base = before * per_seq;
+        before += (int64_t)e.seqs.size();
+        worker_submit(w, std::move(job));
+    }
+    return SVO_OK;
+}
+
+extern "C" int svo_export(svo_ctx* c, int what, const int* seqs, int n, const svo_export_dst* dst, int mem) {
+    const int rc = svo_submit_export(c, what, seqs, n, dst, mem);
+    return rc ? rc : svo_wait(c);
 }
 
 extern "C" int svo_drop_finished_runs(svo_ctx* c, int seq) {

@@ -1,6 +1,6 @@
 // svo_group.hip — one group of the tracker behind the C ABI: StereoSlam::new_image
 // (src/lib/stereo_slam.cpp:123-271) for B sequences together, one kernel launch per stage, on the
-// group's own stream: creation, the step as its phases, and the per-sequence getters of the C ABI.
+// group's own stream: creation, the step as its phases, the bulk export, and the per-sequence getters of the C ABI.
 // svo_ctx.hip spreads a ctx's sequences over groups.
 //
 // Host side = bookkeeping only: image-set pool, argument blocks, the 12-state
@@ -275,6 +275,9 @@ struct svo_group {
     ArgArray<IngestImg> ingest_img;
     PinnedPtr<IngestImg> ingest_img_host;
     uint8_t* d_raw_gray = nullptr; size_t raw_plane_bytes = 0;
+    // bulk export (grp_export) in host mode: B * cap records of each of the three arrays (kps2d | kps3d | info),
+    // made by the first such export
+    uint8_t* d_export = nullptr;
     bool timing = false;
     bool failed = false;
     int exact_pinv = 1;          // reference-order Gauss-Newton unless svo_ctx_set_fast_solver(ctx, 1)
@@ -512,12 +515,17 @@ int check_settings(const svo_camera_settings* cam, int width, int height, int n_
     return SVO_OK;
 }
 
+// keypoints a sequence can hold: the frame's plus a keyframe's new ones, and some room
+int keypoint_capacity(const svo_camera_settings& cam, int width, int height) {
+    const int cells = (width / cam.grid_width) * (height / cam.grid_height);
+    return (int)align_up((size_t)(2 * cells + 128), 64);
+}
+
 // capacities and level counts that follow from the settings
 void size_group(svo_group* c) {
     const svo_camera_settings& cam = c->cam;
     const int width = c->width, height = c->height;
-    const int cells = (width / cam.grid_width) * (height / cam.grid_height);
-    c->cap = (int)align_up((size_t)(2 * cells + 128), 64);
+    c->cap = keypoint_capacity(cam, width, height);
     c->rec_cap = (int)align_up((size_t)c->cap, 512);   // whole passes of the widest alignment workgroup
     c->max_kf = 4096;
     if (const char* e = std::getenv("SVO_KEEP_KEYFRAME_IMAGES")) c->retire_kf_images = std::atoi(e) == 0;
@@ -1304,6 +1312,94 @@ svo_memory grp_memory(const svo_group* c) {
     m.keyframe_slabs = c->kf_slab_count;
     m.keyframe_slabs_free = (int)c->kf_slabs.size();
     return m;
+}
+
+// ------------------------------------------------------------------ bulk export
+
+extern "C" int svo_export_capacity(const svo_camera_settings* cam, int width, int height, int* records_per_sequence) {
+    if (!records_per_sequence) return svo_set_error(SVO_ERR_INVALID, "svo_export_capacity: bad arguments");
+    if (const int rc = check_settings(cam, width, height, 1)) return rc;
+    *records_per_sequence = keypoint_capacity(*cam, width, height);
+    return SVO_OK;
+}
+
+int grp_capacity(const svo_group* c) { return c->cap; }
+
+// The named slots of the group as segments and records (svo_submit_export). The counts are the host's own
+// (Seq::n_host, KfHost::n), so the tile table is built here; it goes up through the group's argument blocks, pinned
+// and device: between two steps the stream is idle and nothing in them is live (every step fills and uploads what
+// its launches read), so an export allocates no table of its own. One launch unless the table outgrows the
+// blocks. Host mode packs into the staging block and copies the used prefix of each array out.
+int grp_export(svo_group* c, int what, int mem, const int* seqs, const int* seg, int n, int seq0, int64_t base,
+               const svo_export_dst* dst) {
+    if (c->failed)
+        return svo_set_error(SVO_ERR_INVALID, "svo_submit_export: an earlier frame of this ctx failed; create a new ctx");
+    HIP_TRY(hipSetDevice(c->device));
+    flush_pending(c);
+    hipStream_t st = c->stream.get();
+    const bool host = mem == SVO_MEM_HOST;
+    svo_kp2d* o2 = dst->kps2d ? dst->kps2d + base : nullptr;
+    svo_kp3d* o3 = dst->kps3d ? dst->kps3d + base : nullptr;
+    svo_kp_info* oi = dst->info ? dst->info + base : nullptr;
+    const bool any = o2 || o3 || oi;
+    if (host && any) {
+        const size_t records = (size_t)c->B * c->cap;
+        if (!c->d_export)
+            if (const int rc = dev_alloc(c, &c->d_export, records * (sizeof(svo_kp2d) + sizeof(svo_kp3d) + sizeof(svo_kp_info)))) return rc;
+        if (o2) o2 = reinterpret_cast<svo_kp2d*>(c->d_export);
+        if (o3) o3 = reinterpret_cast<svo_kp3d*>(c->d_export + records * sizeof(svo_kp2d));
+        if (oi) oi = reinterpret_cast<svo_kp_info*>(c->d_export + records * (sizeof(svo_kp2d) + sizeof(svo_kp3d)));
+    }
+    ExportTile* h_tiles = reinterpret_cast<ExportTile*>(c->args.host.get());
+    ExportTile* d_tiles = reinterpret_cast<ExportTile*>(c->args.dev);
+    size_t table_cap = c->args.bytes / sizeof(ExportTile);
+    if (const char* e = std::getenv("SVO_EXPORT_TABLE_TILES"))     // diagnostic: a smaller table (tests reach the chunked launches)
+        table_cap = std::max<size_t>(1, std::min<size_t>(table_cap, (size_t)std::atoll(e)));
+    size_t m = 0;
+    // the tiles so far; `more`: the pinned table is filled again, so the upload must be over
+    auto launch = [&](bool more) -> int {
+        if (m == 0) return SVO_OK;
+        HIP_TRY(hipMemcpyAsync(d_tiles, h_tiles, sizeof(ExportTile) * m, hipMemcpyHostToDevice, st));
+        launch_export(d_tiles, (int)m, o2, o3, oi, st);
+        HIP_TRY(hipGetLastError());
+        if (more) HIP_TRY(hipStreamSynchronize(st));
+        m = 0;
+        return SVO_OK;
+    };
+    int64_t used = 0;                        // records of the group so far
+    for (int i = 0; i < n; i++) {
+        const Seq& q = c->seqs[seqs[i]];
+        svo_export_segment& e = clear(dst->segments[seg[i]]);
+        e.seq = seq0 + seqs[i]; e.run = q.run; e.frame_id = q.frame_id; e.keyframe_id = -1;
+        e.is_keyframe = q.stats.is_keyframe; e.time_stamp = (float)q.ts;
+        const KpsDev* src = &q.kps[q.cur];
+        if (what == SVO_EXPORT_FRAMES) {
+            e.n = q.n_host;
+            std::memcpy(e.pose, q.pose, sizeof(e.pose));
+        } else if (!q.kfs.empty()) {
+            const KfHost& k = q.kfs.back();
+            e.keyframe_id = (int)q.kfs.size() - 1;
+            e.n = k.n;
+            std::memcpy(e.pose, k.pose, sizeof(e.pose));
+            src = &k.kps;
+        }
+        used = (int64_t)align_up((size_t)used, 4);
+        e.first = base + used;
+        for (int start = 0; any && start < e.n; start += EXPORT_TILE) {
+            if (m == table_cap)
+                if (const int rc = launch(true)) return rc;
+            h_tiles[m++] = export_tile(*src, start, std::min(EXPORT_TILE, e.n - start), used);
+        }
+        used += e.n;
+    }
+    if (const int rc = launch(false)) return rc;
+    if (host && used > 0) {
+        if (o2) HIP_TRY(hipMemcpyAsync(dst->kps2d + base, o2, sizeof(svo_kp2d) * used, hipMemcpyDeviceToHost, st));
+        if (o3) HIP_TRY(hipMemcpyAsync(dst->kps3d + base, o3, sizeof(svo_kp3d) * used, hipMemcpyDeviceToHost, st));
+        if (oi) HIP_TRY(hipMemcpyAsync(dst->info + base, oi, sizeof(svo_kp_info) * used, hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(hipStreamSynchronize(st));       // delivered: svo_wait means that
+    return SVO_OK;
 }
 
 // ------------------------------------------------------------------ per-sequence getters of the C ABI

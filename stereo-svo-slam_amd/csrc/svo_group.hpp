@@ -20,6 +20,13 @@ int grp_new_images(svo_group* g, const uint8_t* const* left, const uint8_t* cons
 // the named sequences (indices in the group) end; their slots are empty until their next frame. Runs between two
 // steps of the group, on the thread that drives it. A failed group rejects it.
 int grp_restart_sequences(svo_group* g, const int* seqs, int n);
+// One group's share of svo_submit_export, between two steps of the group, on the thread that drives it:
+// seqs[i] (index in the group; ctx slot seq0 + seqs[i]) is segment seg[i] of dst->segments; the group's records
+// start at record `base` of the caller's arrays (host or device memory: mem). Delivered on return. A failed group
+// rejects it.
+int grp_export(svo_group* g, int what, int mem, const int* seqs, const int* seg, int n, int seq0, int64_t base,
+               const svo_export_dst* dst);
+int grp_capacity(const svo_group* g);                 // keypoint records a sequence can hold (svo_export_capacity)
 void grp_drop_finished_runs(svo_group* g, int seq);   // seq < 0: of every sequence of the group
 svo_memory grp_memory(const svo_group* g);
 void grp_set_exact_pinv(svo_group* g, int on);

@@ -100,4 +100,24 @@ struct KfInitArgs {
 };
 void launch_kf_init(const KfInitArgs* d_args, int batch, hipStream_t stream);
 
+// ------------------------------------------------------------ bulk export (export.hip)
+// One tile of a keypoint set on its way into the records of the C ABI: at most EXPORT_TILE keypoints, one
+// workgroup. The source arrays point at the tile's first keypoint (kps2d / kps3d as dwords; the ten 4-byte planes
+// in the order flags, outlier count, inlier count, keyframe id, keypoint index, 1/z, variance, score,
+// level | type << 8, colour); `first` is the record of every output array that keypoint goes to.
+constexpr int EXPORT_TILE = 256;
+constexpr int EXPORT_PLANES = 10;
+struct ExportTile {
+    const uint32_t* kps2d;
+    const uint32_t* kps3d;
+    const uint32_t* plane[EXPORT_PLANES];
+    int64_t first;
+    int count, pad_;
+};
+// keypoints [start, start + count) of the set, to records first + start ... (count <= EXPORT_TILE)
+ExportTile export_tile(const KpsDev& k, int start, int count, int64_t first);
+// every output array: device memory or null (skipped); nothing is launched for no tiles or no arrays
+void launch_export(const ExportTile* d_tiles, int n_tiles, svo_kp2d* kps2d, svo_kp3d* kps3d, svo_kp_info* info,
+                   hipStream_t stream);
+
 }  // namespace svo

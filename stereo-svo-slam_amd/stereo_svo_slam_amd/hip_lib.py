@@ -34,12 +34,17 @@ SYMBOLS = (
     "svo_ctx_restart_sequences", "svo_get_finished_runs", "svo_get_finished_run",
     "svo_drop_finished_runs", "svo_ctx_get_memory",
     "svo_input_format_info", "svo_convert_frames", "svo_ctx_set_input_format",
+    "svo_export_capacity", "svo_submit_export", "svo_export", "svo_pack_keypoints",
 )
 
 # svo_ctx_set_input_format / svo_convert_frames: how the buffers of a sequence become its two gray images
 INPUT_GRAY_PAIR, INPUT_BGR_PAIR, INPUT_RGB_PAIR, INPUT_SBS_GRAY, INPUT_SBS_BGR, INPUT_SBS_RGB, INPUT_CH3_ECON = range(7)
 INPUT_FORMATS = ("gray_pair", "bgr_pair", "rgb_pair", "sbs_gray", "sbs_bgr", "sbs_rgb", "ch3_econ")
 INGEST_COPY, INGEST_GRAY = 0, 1
+# svo_submit_export: what is exported, and where the arrays live
+EXPORT_FRAMES, EXPORT_LAST_KEYFRAMES = 0, 1
+EXPORT_WHAT = ("frames", "last_keyframes")
+MEM_HOST, MEM_DEVICE = 0, 1
 
 
 class SvoError(RuntimeError):
@@ -91,6 +96,26 @@ DET_CELL_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("score", "<f4"), ("type"
 assert DET_CELL_DTYPE.itemsize == 16
 
 
+# svo_export_segment (include/svo_hip.h): one per named slot of an export
+EXPORT_SEGMENT_DTYPE = np.dtype([("seq", "<i4"), ("run", "<i4"), ("frame_id", "<i4"), ("keyframe_id", "<i4"),
+                                 ("is_keyframe", "<i4"), ("n", "<i4"), ("first", "<i8"), ("pose", "<f4", (6,)),
+                                 ("time_stamp", "<f4"), ("_pad", "<i4")])
+assert EXPORT_SEGMENT_DTYPE.itemsize == 64
+
+
+class ExportDst(C.Structure):
+    """svo_export_dst (include/svo_hip.h)."""
+    _fields_ = [("segments", C.c_void_p), ("kps2d", C.c_void_p), ("kps3d", C.c_void_p), ("info", C.c_void_p),
+                ("capacity", C.c_int64)]
+
+
+class Keypoints(C.Structure):
+    """svo_keypoints (include/svo_types.h): an SoA keypoint set, views onto device memory."""
+    _fields_ = [("n", C.c_int32)] + [(name, C.c_void_p) for name in (
+        "kps2d", "kps3d", "flags", "keyframe_id", "keypoint_index", "outlier_count", "inlier_count",
+        "kf_inv_depth", "kf_variance", "score", "level_type", "color")]
+
+
 def lib():
     """Load libsvo_hip.so; fail loudly when it has not been built."""
     global _LIB
@@ -127,6 +152,13 @@ def detect_shape(width, height, n_levels, grid_width, grid_height):
     out = [C.c_int(0) for _ in range(4)]
     _check(lib().svo_detect_shape(width, height, n_levels, grid_width, grid_height, *[C.byref(o) for o in out]))
     return tuple(o.value for o in out)
+
+
+def export_capacity(cam, width, height):
+    """svo_export_capacity (host only): the records one slot of an export can take at most."""
+    out = C.c_int(0)
+    _check(lib().svo_export_capacity(C.byref(cam), int(width), int(height), C.byref(out)))
+    return out.value
 
 
 def input_format_info(fmt, width):
@@ -249,6 +281,19 @@ class Handle:
         arr_b = (Image * n)(*[_raw_img(t, info.channels) for t in src_b]) if info.buffers == 2 else None
         _check(lib().svo_convert_frames(self._h, int(fmt), n, arr_a, arr_b, _imgs(lefts), _imgs(rights)))
         return lefts, rights
+
+    # -- export -----------------------------------------------------------
+    def pack_keypoints(self, sets, first, kps2d=None, kps3d=None, info=None):
+        """svo_pack_keypoints: SoA keypoint sets into AoS records. sets: a list of (n, {field of svo_keypoints:
+        device tensor or raw device address}); first[i]: the record set i starts at; kps2d / kps3d / info: device
+        tensors that receive the records (None: skipped)."""
+        arr = (Keypoints * max(len(sets), 1))()
+        for i, (n, fields) in enumerate(sets):
+            arr[i].n = int(n)
+            for name, v in fields.items():
+                setattr(arr[i], name, v.data_ptr() if isinstance(v, torch.Tensor) else int(v))
+        firsts = (C.c_int64 * max(len(sets), 1))(*[int(f) for f in first])
+        _check(lib().svo_pack_keypoints(self._h, len(sets), arr, firsts, _ptr(kps2d), _ptr(kps3d), _ptr(info)))
 
     # -- P2 ---------------------------------------------------------------
     def build_lk_pyramid(self, img, win, max_levels=3):

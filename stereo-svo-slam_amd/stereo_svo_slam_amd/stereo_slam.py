@@ -104,6 +104,78 @@ class Frame:
         self.info = info
 
 
+class Export:
+    """One svo_submit_export: keeps the buffers the library writes alive. After wait(): `segments`
+    (hip_lib.EXPORT_SEGMENT_DTYPE, one per named slot) and the record arrays kps2d [capacity, 2] float32,
+    kps3d [capacity, 3] float32 and info — numpy views of pinned memory (info: KP_INFO_DTYPE [capacity]) in host
+    mode, torch tensors on the ctx's device (info: uint8 [capacity, 44]) in device mode; None for a field that
+    was not asked for. Slot i's keypoints are records [segments[i].first, + segments[i].n) of every array."""
+
+    def __init__(self, slam, what, seqs, device, fields):
+        self._slam = slam
+        self.what, self.device_mode = what, bool(device)
+        self.seqs = None if seqs is None else [int(s) for s in seqs]
+        n = slam.n if seqs is None else len(self.seqs)
+        self.capacity = n * slam.export_capacity()
+        self._seg = torch.zeros(max(n, 1) * hip_lib.EXPORT_SEGMENT_DTYPE.itemsize, dtype=torch.uint8)
+        self.segments = self._seg.numpy().view(hip_lib.EXPORT_SEGMENT_DTYPE)[:n]
+        shapes = {"kps2d": ((self.capacity, 2), torch.float32), "kps3d": ((self.capacity, 3), torch.float32),
+                  "info": ((self.capacity, KP_INFO_DTYPE.itemsize), torch.uint8)}
+        assert set(fields) <= set(shapes), fields
+        self._bufs = {}
+        for name in fields:
+            shape, dtype = shapes[name]
+            self._bufs[name] = (torch.empty(shape, dtype=dtype, device=slam.device) if device
+                                else torch.empty(shape, dtype=dtype, pin_memory=True))
+        self._dst = hip_lib.ExportDst(self._seg.data_ptr(), *[
+            self._bufs[name].data_ptr() if name in self._bufs else None for name in ("kps2d", "kps3d", "info")],
+            self.capacity)
+        self._seq_arr = None if seqs is None else (C.c_int * max(n, 1))(*self.seqs)
+        self._n = n
+
+    def _field(self, name):
+        t = self._bufs.get(name)
+        if t is None or self.device_mode:
+            return t
+        a = t.numpy()
+        return a.view(KP_INFO_DTYPE)[:, 0] if name == "info" else a
+
+    kps2d = property(lambda self: self._field("kps2d"))
+    kps3d = property(lambda self: self._field("kps3d"))
+    info = property(lambda self: self._field("info"))
+
+    def submit(self):
+        """queue the export (again: the same slots into the same buffers, once the previous one is delivered)"""
+        slam = self._slam
+        if self.device_mode:
+            torch.cuda.current_stream(slam.device).synchronize()     # (nothing of the caller's is still using the tensors)
+        _check(lib().svo_submit_export(slam._ctx, self.what, self._seq_arr, self._n, C.byref(self._dst),
+                                       hip_lib.MEM_DEVICE if self.device_mode else hip_lib.MEM_HOST))
+        return self
+
+    def wait(self):
+        self._slam.wait()
+        return self
+
+    def frame(self, i):
+        """segment i as a Frame (what get_frame / get_keyframe return); a field that was not exported is None.
+        Device mode copies the segment's records to the host."""
+        e = self.segments[i]
+        lo, hi = int(e["first"]), int(e["first"]) + int(e["n"])
+        out = []
+        for name in ("kps2d", "kps3d", "info"):
+            a = self._field(name)
+            if a is not None:
+                a = a[lo:hi]
+                if self.device_mode:
+                    a = a.cpu().numpy()
+                    if name == "info":
+                        a = a.view(KP_INFO_DTYPE)[:, 0]
+                a = a.copy()
+            out.append(a)
+        return Frame(np.array(e["pose"], np.float32), *out)
+
+
 class StereoSlamBatch:
     def __init__(self, camera_settings, width, height, n_sequences=1, device=0):
         if isinstance(camera_settings, dict):
@@ -272,6 +344,25 @@ class StereoSlamBatch:
 
     def wait(self):
         _check(lib().svo_wait(self._ctx))
+
+    def export_capacity(self):
+        """svo_export_capacity: the records one slot of an export can take at most."""
+        return hip_lib.export_capacity(self.cam, self.width, self.height)
+
+    def submit_export(self, what="frames", seqs=None, device=False, fields=("kps2d", "kps3d", "info")):
+        """svo_submit_export: queue the export of the current frames (what="frames") or newest keyframes
+        ("last_keyframes") of the slots `seqs` (None: all, in order) behind the frame sets and restarts submitted
+        so far; nothing is waited for. Returns an Export, valid after its wait() (or the ctx's); its submit()
+        queues the same export again into the same buffers."""
+        if isinstance(what, str):
+            what = hip_lib.EXPORT_WHAT.index(what)
+        return Export(self, int(what), seqs, device, fields).submit()
+
+    def export_frames(self, seqs=None, device=False, fields=("kps2d", "kps3d", "info")):
+        return self.submit_export("frames", seqs, device, fields).wait()
+
+    def export_last_keyframes(self, seqs=None, device=False, fields=("kps2d", "kps3d", "info")):
+        return self.submit_export("last_keyframes", seqs, device, fields).wait()
 
     def restart(self, seqs):
         """svo_ctx_restart_sequences: the named slots end their sequences (ordered with the submitted frame
