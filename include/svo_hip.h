@@ -380,6 +380,128 @@ int svo_export(svo_ctx *ctx, int what, const int *seqs, int n, const svo_export_
 int svo_pack_keypoints(svo_handle *h, int n_sets, const svo_keypoints *sets, const int64_t *first,
                        svo_kp2d *kps2d, svo_kp3d *kps3d, svo_kp_info *info);
 
+/* ---- snapshots: the sequence state of a slot saved, loaded, moved between ctxs ------------
+ * The reference has no checkpoint or resume (a StereoSlam lives and dies with its process). A snapshot is
+ * everything the next frame of a slot depends on and everything its getters return, so that a sequence saved
+ * after frame k and loaded into any slot of any compatible ctx (another process, GPU, group layout, solver mode,
+ * input format, memory mode, template-ring size) gives from frame k+1 on exactly the frames of the uninterrupted
+ * run. It has two parts:
+ *
+ * HOST PART (host memory always; little endian, every field 4-byte aligned, sections in this order, no gaps):
+ *   header      struct svo_snapshot_info (160 bytes)
+ *   pose filter the 12-state filter: statePre[12], statePost[12], then A, H, Q, R, errorCovPre, errorCovPost,
+ *               gain, 144 floats each, row major (4128 bytes)
+ *   frame       double time_stamp; float pose[6] (the filtered pose: svo_get_pose); svo_frame_stats: 616 bytes
+ *   trajectory  n_trajectory x svo_pose
+ *   keyframes   n_keyframes x svo_snapshot_keyframe
+ *   directory   n_planes x svo_snapshot_plane: where every plane lies in the data part, in this order:
+ *                 the current keypoint set: kps2d, kps3d, flags, keyframe_id, keypoint_index, outlier_count,
+ *                   inlier_count, kf_inv_depth, kf_variance, score, level_type, color (12 planes of one row,
+ *                   n_keypoints entries each); the colour generator's word (4 bytes); the keypoint count as the
+ *                   device holds it (4 bytes)
+ *                 per keyframe, retired ones included: the same 12 planes with the keyframe's n entries
+ *                 per image set: left pyramid levels 0 .. pyramid_levels-1 (level l: (width >> l) x (height >> l)),
+ *                   the right image, LK levels 1 .. lk_levels-1 (halved rounding up); rows = the image's,
+ *                   row_bytes = its width
+ *               Image set 0 is the current frame's; the others are those of the live keyframes in keyframe order,
+ *               each stored once (a keyframe made on the current frame refers to set 0).
+ * DATA PART (host or device memory: mem): the planes, rows dense (pitch = row_bytes), each at its directory
+ *   offset (save puts them at multiples of 16; the bytes between planes are not written). No pointers anywhere.
+ *
+ * Not part of a snapshot: the slot's run ordinal and finished-run records, the counters of svo_totals: frames count where
+ * they ran, the KLT template cache (a loaded slot's cache starts empty; results do not depend on it), the previous
+ * frame's images (no later frame reads them), and every setting of the ctx. */
+#define SVO_SNAPSHOT_MAGIC   0x534f5653u            /* "SVOS" */
+#define SVO_SNAPSHOT_VERSION 1
+#define SVO_SNAPSHOT_BYTE_ORDER 0x01020304u
+enum { SVO_SNAPSHOT_COMPLETE = 0,
+       SVO_SNAPSHOT_TOO_SMALL = 1 };  /* a capacity was too small when the save ran: only the header was written */
+
+/* the header of a host part; also what svo_snapshot_info returns. (A struct tag only, no typedef: the function
+ * of the same name.) */
+struct svo_snapshot_info {
+    uint32_t magic, version, byte_order;
+    uint32_t status;                   /* SVO_SNAPSHOT_*                                                    */
+    int64_t  host_bytes, data_bytes;   /* sizes of the two parts (TOO_SMALL: the sizes needed)              */
+    svo_camera_settings cam;
+    int32_t  width, height;
+    int32_t  capacity;                 /* keypoints a slot can hold (svo_export_capacity)                   */
+    int32_t  pyramid_levels, lk_levels;
+    int32_t  frame_id;                 /* -1: the slot was empty (every count below is 0)                   */
+    int32_t  n_keypoints;              /* of the current frame                                              */
+    int32_t  n_trajectory;             /* frame_id + 1                                                      */
+    int32_t  n_keyframes, keyframes_retired;   /* keyframes [0, retired) have given their images back        */
+    int32_t  n_image_sets;
+    int32_t  n_planes;                 /* 14 + 12 n_keyframes + n_image_sets (pyramid_levels + lk_levels)   */
+    int32_t  _reserved;                /* 0                                                                 */
+};
+typedef struct svo_snapshot_keyframe {
+    float   pose[6];
+    int32_t n;                         /* its keypoints                                                     */
+    int32_t image_set;                 /* which saved image set it uses; -1: retired                        */
+} svo_snapshot_keyframe;
+typedef struct svo_snapshot_plane {
+    int64_t offset;                    /* in the data part                                                  */
+    int32_t row_bytes, rows;           /* extent: rows x row_bytes bytes from there                         */
+} svo_snapshot_plane;
+
+/* the buffers of one snapshot. save: capacities in, written; load: the sizes of what is given, read. */
+typedef struct svo_snapshot {
+    void   *host;  int64_t host_capacity;     /* host part: host memory                                      */
+    void   *data;  int64_t data_capacity;     /* data part: host (SVO_MEM_HOST) or device (SVO_MEM_DEVICE)   */
+} svo_snapshot;
+
+/* the sizes a save of the slot would need right now; a getter: waits for the queues */
+int svo_snapshot_size(svo_ctx *ctx, int seq, int64_t *host_bytes, int64_t *data_bytes);
+/* Save: snaps[i] receives slot seqs[i]. Queued like an export: it sees every frame set, restart and load submitted
+ * before it and none submitted after; only the groups that own a named slot get work and no other group is
+ * drained; the buffers stay valid until svo_wait, after which everything is delivered. The slot is not changed
+ * (its deferred pose-filter update is flushed first, as the getters do). Level 0 and the right image are copied
+ * even when they alias the caller's frames (SVO_MEM_DEVICE_BORROW, SBS_GRAY in place). An empty slot gives a valid
+ * snapshot (frame_id -1). A capacity too small for the state when the save runs: only the header is written, with
+ * the sizes needed and status SVO_SNAPSHOT_TOO_SMALL; nothing else is touched, the ctx does not fail and svo_wait
+ * returns SVO_OK. Rejected with nothing queued (SVO_ERR_INVALID): an index out of range or named twice, a bad
+ * mem, a null host part or host_capacity < sizeof(struct svo_snapshot_info), a null data part with
+ * data_capacity > 0; a failed ctx, like svo_submit_images.
+ * Host mode goes through one device staging block per group, made on first use and grown when outgrown
+ * (svo_memory.device_bytes), and one copy per snapshot. A ctx that never saves or loads allocates nothing more
+ * and adds no launch or copy to a step. */
+int svo_submit_save(svo_ctx *ctx, const int *seqs, int n, svo_snapshot *snaps, int mem);
+int svo_save_sequences(svo_ctx *ctx, const int *seqs, int n, svo_snapshot *snaps, int mem);   /* submit + wait */
+/* Load: slot seqs[i] takes on snaps[i] (host_capacity / data_capacity: the bytes given). Queued like a save. The
+ * slot first ends its current sequence exactly as svo_ctx_restart_sequences does (a finished-run record if it was
+ * running), then takes the saved state into image sets and keyframe storage from the ctx's own free lists; the
+ * images are the sets' own copies. Every getter then returns for the slot what it returned at the source when
+ * the save ran; the slot keeps its own run ordinal. Loading an empty snapshot is a restart.
+ * Compatibility: camera settings, width, height and capacity must equal the ctx's byte for byte; solver mode,
+ * input format, rectification, memory mode, group count, slot index, template-ring size and device are free.
+ * The host part is parsed and checked completely here, on the host, before anything is queued or changed: magic,
+ * version, byte order, status, compatibility, every count against the capacity, every directory entry against
+ * the extent its plane must have and the data part's size, the sizes against what was passed. A bad snapshot, an
+ * index out of range or named twice, a bad mem: SVO_ERR_INVALID, nothing queued, every slot untouched, the ctx
+ * usable. (The host part is copied at submit time: only the data part must stay valid until svo_wait.)
+ * The DATA part is trusted as frames are: its bytes become keypoints and images unchecked. */
+int svo_submit_load(svo_ctx *ctx, const int *seqs, int n, const svo_snapshot *snaps, int mem);
+int svo_load_sequences(svo_ctx *ctx, const int *seqs, int n, const svo_snapshot *snaps, int mem);   /* submit + wait */
+/* validates a host part (everything svo_submit_load checks but the compatibility with a ctx) and returns its
+ * header; needs no GPU. A header-only part (SVO_SNAPSHOT_TOO_SMALL) of >= sizeof(struct svo_snapshot_info)
+ * bytes is valid here (and rejected by a load). */
+int svo_snapshot_info(const void *host_part, int64_t bytes, struct svo_snapshot_info *out);
+/* stage entry of the copy kernel: n 2-D byte segments, device to device, in the tracker's launch (chunked when
+ * the diagnostic SVO_SNAPSHOT_TABLE_TILES bounds the tile table). Of a segment exactly
+ * [src + r * src_pitch, + row_bytes) is read for r in [0, rows) and the matching destination bytes are written;
+ * rows or row_bytes of 0: nothing. Any addresses: 16 bytes per lane where source, destination and pitches allow,
+ * dwords where 4-byte alignment allows, bytes otherwise. Negative sizes or pitches, a null pointer of a non-empty
+ * segment, rows > 1 with dst_pitch < row_bytes: SVO_ERR_INVALID. Segments must not overlap each other's
+ * destinations. */
+typedef struct svo_copy_segment {
+    const void *src;
+    void       *dst;
+    int64_t     row_bytes, rows;
+    int64_t     src_pitch, dst_pitch;
+} svo_copy_segment;
+int svo_copy_segments(svo_handle *h, int n, const svo_copy_segment *segs);
+
 /* per-frame diagnostics of the last svo_new_images call */
 typedef struct svo_frame_stats {
     int32_t frame_id;

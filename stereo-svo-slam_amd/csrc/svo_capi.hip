@@ -7,6 +7,7 @@
 
 #include <algorithm>
 #include <climits>
+#include <cstdlib>
 #include <cstring>
 #include <memory>
 #include <new>
@@ -35,6 +36,8 @@ struct svo_handle {
     size_t ingest_ws_count = 0;
     DevPtr<ExportTile> export_ws;   // svo_pack_keypoints: the tile table
     size_t export_ws_count = 0;
+    DevPtr<CopyTile> copy_ws;       // svo_copy_segments: the tile table
+    size_t copy_ws_count = 0;
 };
 
 extern "C" const char* svo_last_error(void) { return svo_error_text; }
@@ -311,6 +314,40 @@ extern "C" int svo_pack_keypoints(svo_handle* h, int n_sets, const svo_keypoints
     HIP_TRY(hipMemcpyAsync(h->export_ws.get(), tiles.data(), sizeof(ExportTile) * tiles.size(), hipMemcpyHostToDevice, h->stream));
     launch_export(h->export_ws.get(), (int)tiles.size(), kps2d, kps3d, info, h->stream);
     HIP_TRY(hipGetLastError());
+    return SVO_OK;
+}
+
+extern "C" int svo_copy_segments(svo_handle* h, int n, const svo_copy_segment* segs) {
+    CHECK_H(h);
+    if (n < 0 || (n > 0 && !segs)) return svo_set_error(SVO_ERR_INVALID, "svo_copy_segments: bad arguments");
+    std::vector<CopyTile> tiles;
+    for (int i = 0; i < n; i++) {
+        const svo_copy_segment& g = segs[i];
+        if (g.row_bytes < 0 || g.rows < 0 || g.src_pitch < 0 || g.dst_pitch < 0 || (g.rows > 1 && g.dst_pitch < g.row_bytes))
+            return svo_set_error(SVO_ERR_INVALID, "svo_copy_segments: segment %d: negative size or pitch, or destination rows that overlap", i);
+        if (g.row_bytes == 0 || g.rows == 0) continue;
+        if (!g.src || !g.dst) return svo_set_error(SVO_ERR_INVALID, "svo_copy_segments: segment %d: null pointer", i);
+        cut_copy_tiles(g.src, g.dst, g.row_bytes, g.rows, g.src_pitch, g.dst_pitch, tiles);
+    }
+    if (tiles.empty()) return SVO_OK;
+    size_t chunk = std::min<size_t>(tiles.size(), (size_t)INT_MAX);
+    if (const char* e = getenv("SVO_SNAPSHOT_TABLE_TILES"))     // diagnostic: a smaller table (tests reach the chunked launches)
+        chunk = std::max<size_t>(1, std::min<size_t>(chunk, (size_t)atoll(e)));
+    if (chunk > h->copy_ws_count) {
+        HIP_TRY(hipStreamSynchronize(h->stream));      // (the old table may still be read)
+        h->copy_ws.reset();
+        h->copy_ws_count = 0;
+        HIP_TRY(dev_malloc(h->copy_ws, sizeof(CopyTile) * chunk));
+        h->copy_ws_count = chunk;
+    }
+    for (size_t t0 = 0; t0 < tiles.size(); t0 += chunk) {
+        const size_t m = std::min(chunk, tiles.size() - t0);
+        if (t0 > 0) HIP_TRY(hipStreamSynchronize(h->stream));   // (the table is filled again)
+        HIP_TRY(hipMemcpyAsync(h->copy_ws.get(), tiles.data() + t0, sizeof(CopyTile) * m, hipMemcpyHostToDevice, h->stream));
+        launch_copy_tiles(h->copy_ws.get(), (int)m, h->stream);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipStreamSynchronize(h->stream));          // (the table's upload read `tiles`)
     return SVO_OK;
 }
 

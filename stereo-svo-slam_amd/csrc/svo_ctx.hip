@@ -26,8 +26,9 @@
 // its argument blocks, the other group's kernels keep the GPU busy, and the latency-bound
 // single-workgroup-per-sequence alignment kernel of one group overlaps the window kernels of
 // the other. svo_submit_images() queues a frame set on every group and returns;
-// svo_wait() drains the queues. svo_new_images() = submit + wait. Restarts (svo_ctx_restart_sequences) and
-// exports (svo_submit_export) are entries of the same queues, so they are ordered with the frame sets.
+// svo_wait() drains the queues. svo_new_images() = submit + wait. Restarts (svo_ctx_restart_sequences),
+// exports (svo_submit_export), saves and loads (svo_submit_save / svo_submit_load) are entries of the same queues,
+// so they are ordered with the frame sets.
 struct svo_ctx {
     // the group's share of an svo_submit_export: its named slots (indices in the group) in named order, the
     // segment each one fills, and the record of the caller's arrays the group packs from
@@ -37,14 +38,22 @@ struct svo_ctx {
         int64_t base = 0;
         svo_export_dst dst{};
     };
+    // the group's share of an svo_submit_save (snaps) or svo_submit_load (loads): its named slots, indices in the group
+    struct Snapshots {
+        int mem = 0;
+        std::vector<int> seqs;
+        std::vector<svo_snapshot> snaps;
+        std::vector<SnapshotLoad> loads;
+    };
     // one entry of a group's queue: a frame set, or (restart non-empty) the end of some of its sequences, or
-    // (exp.seqs non-empty) an export
+    // (exp.seqs non-empty) an export, or (snap.seqs / snap.loads non-empty) a save / a load
     struct Job {
         std::vector<const uint8_t*> left, right;
         std::vector<float> ts;
         int stride = 0, mem = 0;
         std::vector<int> restart;        // indices in the group
         Export exp;
+        Snapshots snap;
     };
     struct Worker {
         Group g;
@@ -78,7 +87,12 @@ void worker_submit(svo_ctx::Worker& w, svo_ctx::Job&& job);
 void worker_run_job(svo_ctx::Worker& w, const svo_ctx::Job& job) {
     if (w.err != SVO_OK || w.ctx_failed->load()) return;   // after a failure (any group) the queues are dropped
     const svo_ctx::Export& e = job.exp;
-    const int rc = !e.seqs.empty()
+    const svo_ctx::Snapshots& sn = job.snap;
+    const int rc = !sn.loads.empty()
+                       ? grp_load(w.g.get(), sn.loads.data(), (int)sn.loads.size(), sn.mem)
+                   : !sn.seqs.empty()
+                       ? grp_save(w.g.get(), sn.seqs.data(), (int)sn.seqs.size(), sn.snaps.data(), sn.mem)
+                   : !e.seqs.empty()
                        ? grp_export(w.g.get(), e.what, e.mem, e.seqs.data(), e.seg.data(), (int)e.seqs.size(), w.first, e.base, &e.dst)
                    : !job.restart.empty()
                        ? grp_restart_sequences(w.g.get(), job.restart.data(), (int)job.restart.size())
@@ -303,6 +317,91 @@ extern "C" int svo_submit_export(svo_ctx* c, int what, const int* seqs, int n, c
 extern "C" int svo_export(svo_ctx* c, int what, const int* seqs, int n, const svo_export_dst* dst, int mem) {
     const int rc = svo_submit_export(c, what, seqs, n, dst, mem);
     return rc ? rc : svo_wait(c);
+}
+
+namespace {
+
+// what svo_submit_save and svo_submit_load check alike, before anything is queued
+int check_snapshot_call(svo_ctx* c, const char* name, const int* seqs, int n, const svo_snapshot* snaps, int mem) {
+    if (!c || n < 0 || (n > 0 && (!seqs || !snaps)) || (mem != SVO_MEM_HOST && mem != SVO_MEM_DEVICE))
+        return svo_set_error(SVO_ERR_INVALID, "%s: bad arguments (mem %d)", name, mem);
+    std::vector<char> named(c->B, 0);
+    for (int i = 0; i < n; i++) {
+        if (seqs[i] < 0 || seqs[i] >= c->B || named[seqs[i]])
+            return svo_set_error(SVO_ERR_INVALID, "%s: sequence %d is out of range or named twice", name, seqs[i]);
+        named[seqs[i]] = 1;
+    }
+    return SVO_OK;
+}
+
+int reject_failed(svo_ctx* c, const char* name) {      // (as svo_submit_images)
+    const int rc = ctx_drain(c);
+    return rc ? rc : svo_set_error(SVO_ERR_INVALID, "%s: an earlier frame of this ctx failed; create a new ctx", name);
+}
+
+}  // namespace
+
+extern "C" int svo_submit_save(svo_ctx* c, const int* seqs, int n, svo_snapshot* snaps, int mem) {
+    if (const int rc = check_snapshot_call(c, "svo_submit_save", seqs, n, snaps, mem)) return rc;
+    for (int i = 0; i < n; i++)
+        if (!snaps[i].host || snaps[i].host_capacity < (int64_t)sizeof(struct svo_snapshot_info) || snaps[i].data_capacity < 0 ||
+            (!snaps[i].data && snaps[i].data_capacity > 0))
+            return svo_set_error(SVO_ERR_INVALID, "svo_submit_save: snapshot %d: the host part needs room for its header, the data part its memory", i);
+    if (c->failed.load()) return reject_failed(c, "svo_submit_save");
+    for (auto& wp : c->workers) {
+        svo_ctx::Worker& w = *wp;
+        svo_ctx::Job job;
+        for (int i = 0; i < n; i++)
+            if (seqs[i] >= w.first && seqs[i] < w.first + w.count) {
+                job.snap.seqs.push_back(seqs[i] - w.first);
+                job.snap.snaps.push_back(snaps[i]);
+            }
+        if (job.snap.seqs.empty()) continue;
+        job.snap.mem = mem;
+        worker_submit(w, std::move(job));
+    }
+    return SVO_OK;
+}
+
+extern "C" int svo_save_sequences(svo_ctx* c, const int* seqs, int n, svo_snapshot* snaps, int mem) {
+    const int rc = svo_submit_save(c, seqs, n, snaps, mem);
+    return rc ? rc : svo_wait(c);
+}
+
+extern "C" int svo_submit_load(svo_ctx* c, const int* seqs, int n, const svo_snapshot* snaps, int mem) {
+    if (const int rc = check_snapshot_call(c, "svo_submit_load", seqs, n, snaps, mem)) return rc;
+    // every snapshot is parsed and checked before any group gets work
+    std::vector<SnapshotLoad> loads((size_t)n);
+    for (int i = 0; i < n; i++) {
+        loads[i].seq = seqs[i];
+        loads[i].data = snaps[i].data;
+        if (const int rc = grp_check_snapshot(c->workers[0]->g.get(), &snaps[i], &loads[i].host)) return rc;   // (every group has the same settings)
+    }
+    if (c->failed.load()) return reject_failed(c, "svo_submit_load");
+    for (auto& wp : c->workers) {
+        svo_ctx::Worker& w = *wp;
+        svo_ctx::Job job;
+        for (int i = 0; i < n; i++)
+            if (seqs[i] >= w.first && seqs[i] < w.first + w.count) {
+                loads[i].seq -= w.first;
+                job.snap.loads.push_back(std::move(loads[i]));
+            }
+        if (job.snap.loads.empty()) continue;
+        job.snap.mem = mem;
+        worker_submit(w, std::move(job));
+    }
+    return SVO_OK;
+}
+
+extern "C" int svo_load_sequences(svo_ctx* c, const int* seqs, int n, const svo_snapshot* snaps, int mem) {
+    const int rc = svo_submit_load(c, seqs, n, snaps, mem);
+    return rc ? rc : svo_wait(c);
+}
+
+extern "C" int svo_snapshot_size(svo_ctx* ctx, int seq, int64_t* host_bytes, int64_t* data_bytes) {
+    svo_group* g; int s;
+    if (const int rc = ctx_seq(ctx, seq, &g, &s)) return rc;
+    return grp_snapshot_size(g, s, host_bytes, data_bytes);
 }
 
 extern "C" int svo_drop_finished_runs(svo_ctx* c, int seq) {

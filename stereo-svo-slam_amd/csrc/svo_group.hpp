@@ -26,6 +26,19 @@ int grp_restart_sequences(svo_group* g, const int* seqs, int n);
 // rejects it.
 int grp_export(svo_group* g, int what, int mem, const int* seqs, const int* seg, int n, int seq0, int64_t base,
                const svo_export_dst* dst);
+// Snapshots (svo_submit_save / svo_submit_load). grp_check_snapshot: everything svo_submit_load checks of one
+// snapshot, on the caller's thread (it reads only what never changes in a group); *host_copy receives the checked
+// host part. grp_save / grp_load: one group's share, between two steps of the group, on the thread that drives it;
+// seqs / loads[i].seq are indices in the group; delivered on return. A failed group rejects them.
+struct SnapshotLoad {
+    int seq;
+    std::vector<uint8_t> host;        // the checked host part
+    const void* data;                 // the data part (host or device memory: mem)
+};
+int grp_check_snapshot(const svo_group* g, const svo_snapshot* snap, std::vector<uint8_t>* host_copy);
+int grp_save(svo_group* g, const int* seqs, int n, const svo_snapshot* snaps, int mem);
+int grp_load(svo_group* g, const SnapshotLoad* loads, int n, int mem);
+int grp_snapshot_size(svo_group* g, int seq, int64_t* host_bytes, int64_t* data_bytes);   // (the queues have drained)
 int grp_capacity(const svo_group* g);                 // keypoint records a sequence can hold (svo_export_capacity)
 void grp_drop_finished_runs(svo_group* g, int seq);   // seq < 0: of every sequence of the group
 svo_memory grp_memory(const svo_group* g);

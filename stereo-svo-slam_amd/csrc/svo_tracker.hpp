@@ -2,6 +2,8 @@
 // argument blocks of the bookkeeping / keyframe kernels (keyframe.hip).
 #pragma once
 
+#include <vector>
+
 #include "svo_kernels.hpp"
 
 namespace svo {
@@ -119,5 +121,20 @@ ExportTile export_tile(const KpsDev& k, int start, int count, int64_t first);
 // every output array: device memory or null (skipped); nothing is launched for no tiles or no arrays
 void launch_export(const ExportTile* d_tiles, int n_tiles, svo_kp2d* kps2d, svo_kp3d* kps3d, svo_kp_info* info,
                    hipStream_t stream);
+
+// ------------------------------------------------------------ segment copies (snapshot.hip)
+// One tile of a 2-D byte segment: `rows` rows of `row_bytes` bytes, one workgroup. rows * row_bytes is at most
+// COPY_TILE_BYTES (a single row piece: row_bytes is).
+constexpr int COPY_TILE_BYTES = 32768;
+struct CopyTile {
+    const uint8_t* src;
+    uint8_t* dst;
+    int64_t src_pitch, dst_pitch;
+    int row_bytes, rows;
+};
+// the tiles of one segment, appended to `out` (none for rows or row_bytes of 0)
+void cut_copy_tiles(const void* src, void* dst, int64_t row_bytes, int64_t rows, int64_t src_pitch, int64_t dst_pitch,
+                    std::vector<CopyTile>& out);
+void launch_copy_tiles(const CopyTile* d_tiles, int n_tiles, hipStream_t stream);
 
 }  // namespace svo

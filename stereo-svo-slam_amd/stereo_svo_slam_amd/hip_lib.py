@@ -35,6 +35,8 @@ SYMBOLS = (
     "svo_drop_finished_runs", "svo_ctx_get_memory",
     "svo_input_format_info", "svo_convert_frames", "svo_ctx_set_input_format",
     "svo_export_capacity", "svo_submit_export", "svo_export", "svo_pack_keypoints",
+    "svo_snapshot_size", "svo_submit_save", "svo_save_sequences", "svo_submit_load", "svo_load_sequences",
+    "svo_snapshot_info", "svo_copy_segments",
 )
 
 # svo_ctx_set_input_format / svo_convert_frames: how the buffers of a sequence become its two gray images
@@ -116,6 +118,30 @@ class Keypoints(C.Structure):
         "kf_inv_depth", "kf_variance", "score", "level_type", "color")]
 
 
+class SnapshotInfo(C.Structure):
+    """struct svo_snapshot_info (include/svo_hip.h): the header of a snapshot's host part."""
+    _fields_ = [("magic", C.c_uint32), ("version", C.c_uint32), ("byte_order", C.c_uint32), ("status", C.c_uint32),
+                ("host_bytes", C.c_int64), ("data_bytes", C.c_int64), ("cam", CameraSettings)] + \
+               [(n, C.c_int32) for n in
+                ("width", "height", "capacity", "pyramid_levels", "lk_levels", "frame_id", "n_keypoints",
+                 "n_trajectory", "n_keyframes", "keyframes_retired", "n_image_sets", "n_planes", "_reserved")]
+
+
+assert C.sizeof(SnapshotInfo) == 160
+SNAPSHOT_COMPLETE, SNAPSHOT_TOO_SMALL = 0, 1
+
+
+class SnapshotBuffers(C.Structure):
+    """svo_snapshot (include/svo_hip.h): the two buffers of one snapshot."""
+    _fields_ = [("host", C.c_void_p), ("host_capacity", C.c_int64), ("data", C.c_void_p), ("data_capacity", C.c_int64)]
+
+
+class CopySegment(C.Structure):
+    """svo_copy_segment (include/svo_hip.h)."""
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("row_bytes", C.c_int64), ("rows", C.c_int64),
+                ("src_pitch", C.c_int64), ("dst_pitch", C.c_int64)]
+
+
 def lib():
     """Load libsvo_hip.so; fail loudly when it has not been built."""
     global _LIB
@@ -159,6 +185,15 @@ def export_capacity(cam, width, height):
     out = C.c_int(0)
     _check(lib().svo_export_capacity(C.byref(cam), int(width), int(height), C.byref(out)))
     return out.value
+
+
+def snapshot_info(host_part):
+    """svo_snapshot_info (host only): checks the host part of a snapshot (bytes-like) and returns its header;
+    SvoError for a bad one."""
+    buf = bytes(host_part)
+    out = SnapshotInfo()
+    _check(lib().svo_snapshot_info(buf, len(buf), C.byref(out)))
+    return out
 
 
 def input_format_info(fmt, width):
@@ -294,6 +329,12 @@ class Handle:
                 setattr(arr[i], name, v.data_ptr() if isinstance(v, torch.Tensor) else int(v))
         firsts = (C.c_int64 * max(len(sets), 1))(*[int(f) for f in first])
         _check(lib().svo_pack_keypoints(self._h, len(sets), arr, firsts, _ptr(kps2d), _ptr(kps3d), _ptr(info)))
+
+    def copy_segments(self, segs):
+        """svo_copy_segments: 2-D byte segments, device to device. segs: (src address, dst address, row_bytes,
+        rows, src_pitch, dst_pitch) each. Complete on return."""
+        arr = (CopySegment * max(len(segs), 1))(*[CopySegment(*[int(x) for x in g]) for g in segs])
+        _check(lib().svo_copy_segments(self._h, len(segs), arr))
 
     # -- P2 ---------------------------------------------------------------
     def build_lk_pyramid(self, img, win, max_levels=3):

@@ -161,6 +161,19 @@ def play_queue(slam, frames_of, lengths, time_of=lambda s, k: k / 20.0, order=No
     return where, frames
 
 
+def move(src, src_slots, dst, dst_slots):
+    """Move sequences between two ctxs (or two slots of one): a device-mode save of src's slots, their restart,
+    then the load into dst's slots (any slot count, group layout or GPU of the same process: the data parts go
+    through a copy to dst's device when it differs). Waits for both ctxs. Returns the Snapshots (in dst's memory)."""
+    from .stereo_slam import Snapshot
+    snaps = src.save(src_slots, device=True)
+    src.restart(src_slots)
+    if dst.device != src.device:
+        snaps = [Snapshot(s.host, s.data.to(dst.device)) for s in snaps]
+    dst.load(dst_slots, snaps)
+    return snaps
+
+
 def _sync(device):
     if device is not None and device.type == "cuda":
         torch.cuda.synchronize(device)

@@ -176,6 +176,55 @@ class Export:
         return Frame(np.array(e["pose"], np.float32), *out)
 
 
+class Snapshot:
+    """The sequence state of one slot (svo_submit_save / svo_submit_load): `host` (numpy uint8, the host part) and
+    `data` (the data part: numpy uint8, or a torch uint8 tensor on the ctx's device in device mode). Valid after
+    the wait() that follows its save. `info`: the checked header (hip_lib.SnapshotInfo). tobytes() / frombytes():
+    one self-contained blob for a file."""
+
+    def __init__(self, host, data):
+        self.host, self.data = host, data
+
+    @property
+    def device_mode(self):
+        return isinstance(self.data, torch.Tensor)
+
+    @property
+    def info(self):
+        return hip_lib.snapshot_info(self.host)
+
+    def trimmed(self):
+        """the two parts cut to the sizes the header states (a save is given capacities)"""
+        i = self.info
+        return Snapshot(self.host[:i.host_bytes], self.data[:i.data_bytes])
+
+    def tobytes(self):
+        """host part, then data part (their sizes are in the header)"""
+        t = self.trimmed()
+        data = t.data.cpu().numpy() if t.device_mode else t.data
+        return t.host.tobytes() + data.tobytes()
+
+    @classmethod
+    def frombytes(cls, blob, device=None):
+        """from tobytes(); device: a torch device for a device-mode snapshot (default: host mode)"""
+        i = hip_lib.snapshot_info(blob)
+        if i.status != hip_lib.SNAPSHOT_COMPLETE or len(blob) < i.host_bytes + i.data_bytes:
+            raise SvoError("snapshot: incomplete")
+        a = np.frombuffer(blob, np.uint8)
+        host, data = a[:i.host_bytes].copy(), a[i.host_bytes:i.host_bytes + i.data_bytes].copy()
+        return cls(host, torch.from_numpy(data).to(device) if device is not None else data)
+
+    def _buffers(self):
+        if self.device_mode:
+            assert self.data.is_cuda and self.data.dtype == torch.uint8 and self.data.is_contiguous()
+            data, n = self.data.data_ptr(), self.data.numel()
+        else:
+            assert self.data.dtype == np.uint8 and self.data.flags.c_contiguous
+            data, n = self.data.ctypes.data, self.data.size
+        assert self.host.dtype == np.uint8 and self.host.flags.c_contiguous
+        return hip_lib.SnapshotBuffers(self.host.ctypes.data, self.host.size, data if n else None, n)
+
+
 class StereoSlamBatch:
     def __init__(self, camera_settings, width, height, n_sequences=1, device=0):
         if isinstance(camera_settings, dict):
@@ -363,6 +412,58 @@ class StereoSlamBatch:
 
     def export_last_keyframes(self, seqs=None, device=False, fields=("kps2d", "kps3d", "info")):
         return self.submit_export("last_keyframes", seqs, device, fields).wait()
+
+    def snapshot_size(self, seq):
+        """svo_snapshot_size: (host_bytes, data_bytes) a save of the slot needs right now (waits)."""
+        hb, db = C.c_int64(0), C.c_int64(0)
+        _check(lib().svo_snapshot_size(self._ctx, int(seq), C.byref(hb), C.byref(db)))
+        return hb.value, db.value
+
+    def _snapshot_call(self, fn, seqs, snaps):
+        seqs = [int(s) for s in seqs]
+        assert len(seqs) == len(snaps)
+        device = [s.device_mode for s in snaps]
+        assert all(device) or not any(device), "snapshots of one call are all in host or all in device memory"
+        if any(device):
+            torch.cuda.current_stream(self.device).synchronize()     # (nothing of the caller's is still using the tensors)
+        arr = (hip_lib.SnapshotBuffers * max(len(seqs), 1))(*[s._buffers() for s in snaps])
+        _check(fn(self._ctx, (C.c_int * max(len(seqs), 1))(*seqs), len(seqs), arr,
+                  hip_lib.MEM_DEVICE if any(device) else hip_lib.MEM_HOST))
+
+    def new_snapshot(self, host_bytes, data_bytes, device=False):
+        """zeroed buffers for a save (zeroed: the bytes between the planes of a device-mode data part are not
+        written)"""
+        return Snapshot(np.zeros(host_bytes, np.uint8),
+                        torch.zeros(data_bytes, dtype=torch.uint8, device=self.device) if device
+                        else np.zeros(data_bytes, np.uint8))
+
+    def submit_save(self, seqs=None, device=False, snapshots=None):
+        """svo_submit_save: queue the save of the slots `seqs` (None: all) behind what was submitted so far.
+        Returns the Snapshots, valid after wait(). snapshots: buffers to save into (new_snapshot), with room for
+        what the frames still queued may add; nothing is waited for then, and a save whose capacity turns out too
+        small gives a header-only snapshot (info.status == SNAPSHOT_TOO_SMALL, with the sizes needed). Default:
+        made here with the sizes the slots need, after a wait for the queues."""
+        seqs = list(range(self.n)) if seqs is None else [int(s) for s in seqs]
+        if snapshots is None:
+            snapshots = [self.new_snapshot(*self.snapshot_size(s), device) for s in seqs]
+        self._snapshot_call(lib().svo_submit_save, seqs, snapshots)
+        return snapshots
+
+    def save(self, seqs=None, device=False):
+        """submit_save + wait: the Snapshots of the slots `seqs` (None: all)"""
+        snaps = self.submit_save(seqs, device)
+        self.wait()
+        return snaps
+
+    def submit_load(self, seqs, snapshots):
+        """svo_submit_load: queue the load of snapshots[i] into slot seqs[i]; the slot's current sequence ends as
+        with restart(). A bad snapshot raises SvoError here and nothing is queued. The data parts stay alive and
+        unchanged until wait()."""
+        self._snapshot_call(lib().svo_submit_load, seqs, list(snapshots))
+
+    def load(self, seqs, snapshots):
+        self.submit_load(seqs, snapshots)
+        self.wait()
 
     def restart(self, seqs):
         """svo_ctx_restart_sequences: the named slots end their sequences (ordered with the submitted frame
