@@ -205,9 +205,29 @@ __global__ __launch_bounds__(64) void sia_prep_kernel(const SiaArgs* __restrict_
 #ifdef SVO_SIA_STAMPS
 #define SIA_T(v) const long long v = __builtin_readcyclecounter()
 #define SIA_ADD(i, t1, t0) st[i] += (t1) - (t0)
+// time until everything asked of vector memory has arrived. SIA_WAIT_PRE / SIA_WAIT_CHAIN: the points of the batched
+// loads and of the chain of dependent loads (-DSVO_SIA_PRELOAD=0) where a pass needs what it asked for
+#define SIA_WAIT(i) do { SIA_T(w0_); asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); SIA_T(w1_); SIA_ADD(i, w1_, w0_); } while (0)
+#define SIA_WAIT_PRE(i) do { if constexpr (PRE) SIA_WAIT(i); } while (0)
+#define SIA_WAIT_CHAIN(i) do { if constexpr (BIG && !PRE) SIA_WAIT(i); } while (0)
+constexpr int SIA_N_STAMPS = 20;
+constexpr int SIA_STAMP_RING = 4096;          // rows of the batched launches' stamps: the last 4096 sequences that finished
+__device__ float g_sia_stamps[SIA_STAMP_RING][SIA_N_STAMPS];
+__device__ unsigned g_sia_stamp_rows;
 #else
 #define SIA_T(v)
 #define SIA_ADD(i, t1, t0)
+#define SIA_WAIT(i) do { } while (0)
+#define SIA_WAIT_PRE(i) do { } while (0)
+#define SIA_WAIT_CHAIN(i) do { } while (0)
+#endif
+// (diagnostic builds: -DSVO_SIA_PRELOAD=0 keeps MODE 2's loads where they are used, one behind the other, as before
+// round 7, -DSVO_SIA_QREG=0 hands the projections from cost() to get_gradient through kp_ws; tools/build_variants.sh)
+#ifndef SVO_SIA_PRELOAD
+#define SVO_SIA_PRELOAD 1
+#endif
+#ifndef SVO_SIA_QREG
+#define SVO_SIA_QREG 1
 #endif
 
 // MODE — where the working set of a sequence lives (same arithmetic, same order in all three):
@@ -220,13 +240,25 @@ __global__ __launch_bounds__(64) void sia_prep_kernel(const SiaArgs* __restrict_
 //     short of — and keypoint sets / level images that do not fit LDS, the 1920x1080 configuration
 //     with ~1700 keypoints and a 480x270 finest level): per-keypoint values in the HBM workspace
 //     SiaArgs::kp_ws, records and image taps from L2; LDS holds only the staging area of the
-//     ordered accumulation (18 KB with one wave per sequence, 36 KB with two, 72 KB with four).
+//     ordered accumulation (18 KB with one wave per sequence, 36 KB with two, 72 KB with four). A pass asks
+//     for everything it reads of its keypoint at once (PRE) instead of one load behind the branch on the other:
+//     a sequence is one serial chain of passes, and every round trip to L2 on it is time the launch lasts.
 template <int WAVES, int MODE>
 struct Sia {
     static constexpr bool BIG = MODE == 2;
     static constexpr int T = 64 * WAVES;
+    // MODE 2 reads its operands from L2: a pass asks for all of them at once, a pass of cost() a pass ahead
+    static constexpr bool PRE = BIG && SVO_SIA_PRELOAD != 0;
+    // (a pass ahead with one wave, whose chain of passes is what a launch lasts; several waves per sequence ask at the
+    // top of the pass itself: a second set of operands in flight puts the four-wave shape over 256 registers)
+    static constexpr bool AHEAD = PRE && WAVES == 1;
+    // ... and with one wave a keypoint has the same lane in cost() and in get_gradient: the projection stays in
+    // registers (the one-wave MODE 2 shape has at most QPASSES passes, sia_pick_shape)
+    static constexpr bool QREG = PRE && WAVES == 1 && SVO_SIA_QREG != 0;
+    static constexpr int QPASSES = 3;
+    float qx[QPASSES] = {0, 0, 0}, qy[QPASSES] = {0, 0, 0};
 #ifdef SVO_SIA_STAMPS
-    long long st[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    long long st[SIA_N_STAMPS] = {};
 #endif
 
     const SiaArgs& a;
@@ -288,9 +320,39 @@ struct Sia {
         }
     }
 
+    // MODE 2 (PRE): what a pass of cost() reads of keypoint i before it can project: one batch of 20 independent
+    // loads, whatever the slot holds (every i < cap lies inside kp_ws [KF_COUNT][cap] and the rows of rec_ws, rec_cap
+    // >= cap). An inactive or padded slot's values are dropped by the tests that dropped them when they were loaded
+    // one behind the other, each behind the branch on the one before.
+    struct CostOps {
+        float act, p[3], i1[16];
+    };
+    __device__ inline void cost_ops_ld(int i, CostOps& o) const {
+        o.act = kpf_ld(KF_ACT, i);
+        o.p[0] = kpf_ld(KF_PX, i); o.p[1] = kpf_ld(KF_PY, i); o.p[2] = kpf_ld(KF_PZ, i);
+#pragma unroll
+        for (int px = 0; px < 16; px++) o.i1[px] = rec_ld(REC_I1, px, i);
+    }
+    // QREG: the projection of the keypoint this lane owns in pass k (k is wave-uniform)
+    __device__ inline void q_put(int k, float x, float y) {
+#pragma unroll
+        for (int j = 0; j < QPASSES; j++)
+            if (k == j) { qx[j] = x; qy[j] = y; }
+    }
+    __device__ inline void q_get(int k, float& x, float& y) const {
+        x = qx[0]; y = qy[0];
+#pragma unroll
+        for (int j = 1; j < QPASSES; j++)
+            if (k == j) { x = qx[j]; y = qy[j]; }
+    }
+
     // ---- do_calc: project + get_total_intensity_diff
     __device__ float cost(const float pose[6]) {
         SIA_T(c0);
+        CostOps nxt;
+        if constexpr (PRE) {
+            if (AHEAD && (int)threadIdx.x < npad) cost_ops_ld(threadIdx.x, nxt);     // the first pass's: behind pose_mats
+        }
         PoseMats pm;
         pose_mats(pose, pm);
         SIA_T(c1);
@@ -300,14 +362,36 @@ struct Sia {
         float* buf = reinterpret_cast<float*>(dyn + lay.tbuf) + par * cap;
         par ^= 1;
         float total = 0;
-        for (int i = threadIdx.x; i < npad; i += T) {     // (passes beyond the sequence's own keypoints would add exact zeros)
+        int pass = 0;
+        for (int i = threadIdx.x; i < npad; i += T, pass++) {     // (passes beyond the sequence's own keypoints would add exact zeros)
+            CostOps ops;
+            if constexpr (PRE) {
+                if constexpr (AHEAD) {
+                    // this pass's operands were asked for a pass ago; the next pass's travel behind this pass
+                    ops = nxt;
+                    SIA_WAIT_PRE(12);
+                    if (i + T < npad) cost_ops_ld(i + T, nxt);
+                } else {
+                    cost_ops_ld(i, ops);
+                    asm volatile("" ::: "memory");      // (keeps the loads out of the branches below, as in compute_kp)
+                    SIA_WAIT_PRE(12);
+                }
+            }
+            SIA_ADD(17, 1, 0);
             float v = 0;
-            if (kpf_ld(KF_ACT, i) != 0.f) {
-                const svo_kp2d q = project_point(pm.Rd, pm.t, camd, svo_kp3d{kpf_ld(KF_PX, i), kpf_ld(KF_PY, i), kpf_ld(KF_PZ, i)});
-                kpf_st(KF_QX, i, q.x); kpf_st(KF_QY, i, q.y);
+            const bool active = (PRE ? ops.act : kpf_ld(KF_ACT, i)) != 0.f;
+            SIA_WAIT_CHAIN(12);
+            if (active) {
+                const svo_kp3d P = PRE ? svo_kp3d{ops.p[0], ops.p[1], ops.p[2]}
+                                       : svo_kp3d{kpf_ld(KF_PX, i), kpf_ld(KF_PY, i), kpf_ld(KF_PZ, i)};
+                SIA_WAIT_CHAIN(12);
+                const svo_kp2d q = project_point(pm.Rd, pm.t, camd, P);
+                if constexpr (QREG) q_put(pass, q.x, q.y);
+                else { kpf_st(KF_QX, i, q.x); kpf_st(KF_QY, i, q.y); }
                 const float s2x = q.x - half_size, s2y = q.y - half_size;
                 const float f2x = floorf(s2x), f2y = floorf(s2y);
-                const float i1_0 = rec_ld(REC_I1, 0, i);
+                const float i1_0 = PRE ? ops.i1[0] : rec_ld(REC_I1, 0, i);
+                SIA_WAIT_CHAIN(12);
                 // (absurd projections are kept out of the int conversion)
                 if (i1_0 == i1_0 && f2x >= 0.f && f2y >= 0.f && f2x < 65536.f && f2y < 65536.f) {
                     const int ip2x = (int)f2x, ip2y = (int)f2y;
@@ -321,6 +405,15 @@ struct Sia {
                         for (int r = 0; r < 5; r++)
 #pragma unroll
                             for (int c = 0; c < 5; c++) b[r][c] = cur.at(o + r * cur.stride + c);
+#ifdef SVO_SIA_STAMPS
+                        float i1s[16];          // (the chain's other 15 records leave with the taps, as the compiler has them)
+#pragma unroll
+                        for (int px = 0; px < 16; px++) i1s[px] = PRE ? ops.i1[px] : rec_ld(REC_I1, px, i);
+                        if constexpr (BIG) SIA_WAIT(13);
+#define SIA_I1(px) i1s[px]
+#else
+#define SIA_I1(px) (PRE ? ops.i1[px] : rec_ld(REC_I1, px, i))
+#endif
 #pragma unroll
                         for (int px = 0; px < 16; px++) {
                             const int r = px >> 2, c = px & 3;
@@ -329,8 +422,9 @@ struct Sia {
                             i2 += m1 * b[r][c + 1];
                             i2 += m2 * b[r + 1][c];
                             i2 += m3 * b[r + 1][c + 1];
-                            v += fabsf(rec_ld(REC_I1, px, i) - i2);
+                            v += fabsf(SIA_I1(px) - i2);
                         }
+#undef SIA_I1
                     }
                 }
             }
@@ -374,33 +468,60 @@ struct Sia {
         float* stage = reinterpret_cast<float*>(dyn + lay.stage);      // [7][PS], index slot*KS + px
 
         // J (2x6) and the 16 residuals of keypoint i (a lane's work of one pass)
-        auto compute_kp = [&](int i, float (&J)[12], float (&d)[16], bool& active) {
+        auto compute_kp = [&](int i, [[maybe_unused]] int pass, float (&J)[12], float (&d)[16], bool& active) {
 #pragma unroll
             for (int q = 0; q < 12; q++) J[q] = 0;
-            active = kpf_ld(KF_ACT, i) != 0.f;
-            if (active) {
-                float X[3] = {kpf_ld(KF_PX, i) - pm.t[0], kpf_ld(KF_PY, i) - pm.t[1], kpf_ld(KF_PZ, i) - pm.t[2]};
-                mat33f_vec(pm.Ri, X, X);
-                pose_jacobian(fx, fy, X[0], X[1], X[2], J);
+            // MODE 2 (PRE): everything the pass reads of keypoint i apart from the image taps in one batch of 20 or 22
+            // loads, as in cost(): the point and the reference patch sums no longer wait for the active flag to arrive,
+            // and with QREG the image taps below leave with them.
+            // (The compiler would move loads that only the active branch uses back into it; the empty asm keeps them.)
+            float kact, kp[3], kq[2], kps[16];
+            if constexpr (PRE) {
+                kact = kpf_ld(KF_ACT, i);
+                if constexpr (QREG) q_get(pass, kq[0], kq[1]);
+                else { kq[0] = kpf_ld(KF_QX, i); kq[1] = kpf_ld(KF_QY, i); }
+                kp[0] = kpf_ld(KF_PX, i); kp[1] = kpf_ld(KF_PY, i); kp[2] = kpf_ld(KF_PZ, i);
+#pragma unroll
+                for (int px = 0; px < 16; px++) kps[px] = rec_ld(REC_PS, px, i);
+                asm volatile("" ::: "memory");
+                if constexpr (!QREG) SIA_WAIT_PRE(14);
             }
+            SIA_ADD(18, 1, 0);
+            active = (PRE ? kact : kpf_ld(KF_ACT, i)) != 0.f;
+            SIA_WAIT_CHAIN(14);
+            auto jacobian = [&]() {
+                if (active) {
+                    float X[3] = {(PRE ? kp[0] : kpf_ld(KF_PX, i)) - pm.t[0], (PRE ? kp[1] : kpf_ld(KF_PY, i)) - pm.t[1],
+                                  (PRE ? kp[2] : kpf_ld(KF_PZ, i)) - pm.t[2]};
+                    SIA_WAIT_CHAIN(14);
+                    mat33f_vec(pm.Ri, X, X);
+                    pose_jacobian(fx, fy, X[0], X[1], X[2], J);
+                }
+            };
+            if constexpr (!QREG) jacobian();        // (QREG: below, once the image taps have been asked for)
             // residuals: the same walk over the patch as above, from the projection. The 16 patch sums
             // read a 6x6 block of the current image: it is loaded up front (36 independent reads,
             // clamped to the image) and every patch sum whose taps start where the walk says they
             // should — all of them, unless a float increment rounds across an integer — takes its 3x3
             // taps from the block; the others read the image directly.
             {
-                const float kx0 = kpf_ld(KF_QX, i) - 2.f, ky0 = kpf_ld(KF_QY, i) - 2.f;
+                const float kx0 = (PRE ? kq[0] : kpf_ld(KF_QX, i)) - 2.f, ky0 = (PRE ? kq[1] : kpf_ld(KF_QY, i)) - 2.f;
+                SIA_WAIT_CHAIN(14);
                 const int bx = (int)fminf(fmaxf(floorf(kx0 - 0.5f), -8.f), 65536.f);
                 const int by = (int)fminf(fmaxf(floorf(ky0 - 0.5f), -8.f), 65536.f);
                 float blk[6][6];
-                if (active) {
+                // (QREG: the taps do not wait for the active flag either. Their addresses are clamped to the image
+                // whatever the projection holds, and an inactive keypoint's are never used)
+                if (QREG || active) {
 #pragma unroll
                     for (int r = 0; r < 6; r++) {
                         const int ro = min(max(by + r, 0), cur.h - 1) * cur.stride;
 #pragma unroll
                         for (int c = 0; c < 6; c++) blk[r][c] = cur.at(ro + min(max(bx + c, 0), cur.w - 1));
                     }
+                    if constexpr (BIG) SIA_WAIT(15);        // (with QREG: the taps and the batch above together)
                 }
+                if constexpr (QREG) jacobian();
                 float kx = kx0, ky = ky0;
 #pragma unroll
                 for (int r = 0; r < 4; r++) {
@@ -409,7 +530,8 @@ struct Sia {
                         const int px = r * 4 + c;
                         float dd = 0;
                         if (active) {
-                            const float psr = rec_ld(REC_PS, px, i);
+                            const float psr = PRE ? kps[px] : rec_ld(REC_PS, px, i);
+                            SIA_WAIT_CHAIN(14);
                             // (kx - 1.0) < 0 || (ky - 1.0) < 0 || (kx + 2.0) > cols || (ky + 2.0) > rows of :449-454:
                             // the double sums are exact, so these float compares decide the same way
                             if (psr == psr &&                   // reference pixel inside (:449-451)
@@ -476,6 +598,7 @@ struct Sia {
                 g0[e] = active ? rec_ld(REC_G0, h * 8 + e, i) : 0.f;
                 g1[e] = active ? rec_ld(REC_G1, h * 8 + e, i) : 0.f;
             }
+            SIA_WAIT(16);
 #pragma unroll
             for (int p = 0; p < 2; p++) {
                 const int o = slot * KS + (2 * h + p) * 4;
@@ -551,7 +674,7 @@ struct Sia {
                     bool active;
 #pragma unroll
                     for (int q = 0; q < 12; q++) J[q] = 0;
-                    compute_kp(i, J, d, active);
+                    compute_kp(i, 0, J, d, active);
                     const int bsel = c & 1, k = c >> 1;
                     while (__hip_atomic_load(&cnt[2 + bsel], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < k) __builtin_amdgcn_s_sleep(1);
                     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
@@ -567,7 +690,7 @@ struct Sia {
             bool active;
 #pragma unroll
             for (int q = 0; q < 12; q++) J[q] = 0;
-            compute_kp(i, J, d, active);
+            compute_kp(i, i0 / T, J, d, active);
             if (!exact) {
                 float s0 = 0, s1 = 0, Gxx = 0, Gxy = 0, Gyy = 0;
                 if (active) {                               // (slots past the keypoints hold no records)
@@ -843,9 +966,12 @@ struct Sia {
             }
         }
 #ifdef SVO_SIA_STAMPS
-        if (tid == 0 && a.dbg_H) {
+        if (tid == 0) {
             st[9] = __builtin_readcyclecounter() - k0;
-            for (int j = 0; j < 12; j++) G(a.dbg_H)[j] = (float)st[j];
+            st[19] = n;
+            // a lone launch hands its stamps back through dbg_H; the sequences of a batch take the next row of the ring
+            float* out = a.dbg_H ? a.dbg_H : g_sia_stamps[atomicAdd(&g_sia_stamp_rows, 1u) % SIA_STAMP_RING];
+            for (int j = 0; j < SIA_N_STAMPS; j++) G(out)[j] = (float)st[j];
         }
 #endif
         if (tid == 0) {
@@ -895,6 +1021,8 @@ static LaunchStatus sia_launch_shape(const SiaArgs* d_args, int batch, int img, 
     static LdsLimit limit;
     const hipError_t e = raise_lds_limit(limit, reinterpret_cast<const void*>(sia_gn_kernel<WAVES, MODE>), (int)SIA_LDS_BUDGET);
     if (e != hipSuccess) return {sh, e};
+    // (one wave keeps a projection per pass in registers, QREG)
+    if (WAVES == 1 && MODE == 2 && sh.cap > 64 * Sia<WAVES, MODE>::QPASSES) return {{false, sh.waves, sh.mode, sh.cap, sh.lds}, hipSuccess};
     hipLaunchKernelGGL((sia_gn_kernel<WAVES, MODE>), dim3(batch), dim3(64 * WAVES), sh.lds, stream, d_args, img, sh.cap);
     return {sh, hipSuccess};
 }
@@ -952,6 +1080,19 @@ LaunchStatus launch_sia(const SiaArgs* d_args, int batch, const svo_camera_setti
 #undef SIA_CASE
     return {{false, sh.waves, sh.mode, sh.cap, sh.lds}, hipSuccess};
 }
+
+#ifdef SVO_SIA_STAMPS
+}  // namespace svo
+// diagnostic builds only (tools/sia_stamps.py batch): the ring of the batched launches' stamps, [SIA_STAMP_RING][SIA_N_STAMPS]
+// floats, and how many rows have been written since the library was loaded
+extern "C" int svo_sia_stamps_read(float* out, unsigned* rows_written) {
+    if (hipDeviceSynchronize() != hipSuccess) return -1;
+    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(svo::g_sia_stamps), sizeof(float) * svo::SIA_STAMP_RING * svo::SIA_N_STAMPS) != hipSuccess) return -1;
+    if (hipMemcpyFromSymbol(rows_written, HIP_SYMBOL(svo::g_sia_stamp_rows), sizeof(unsigned)) != hipSuccess) return -1;
+    return 0;
+}
+namespace svo {
+#endif
 
 size_t sia_rec_ws_floats(const svo_camera_settings& cam, int rec_cap) {
     return (size_t)(cam.max_pyramid_levels - cam.min_pyramid_level_pose_estimation) * SIA_REC_ROWS * rec_cap;
