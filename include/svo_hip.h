@@ -578,6 +578,29 @@ int svo_pinv6_check(svo_handle *h, const float *H_dev, int n, float *out_dev, in
  * Vt[36], U^T[36] and delta[6]; sweeps_dev[n] the Jacobi sweeps run. Both impls give the same bits. */
 int svo_solve6_check(svo_handle *h, const float *H_dev, const float *b_dev, int n, float *out_dev,
                      int32_t *sweeps_dev, int impl);
+/* Diagnostic: the reprojection refinement (svo_reproj_gn) of `batch` sequences in one launch, the way the
+ * tracker launches it. Every keypoint array holds the sequences `stride` entries apart (sequence b starts at
+ * b * stride); n_dev[batch] (device) the counts, each 0..n_bound, n_bound <= stride; pose_in / pose_out
+ * [batch][6], cost [batch], trace [batch] (cost, trace, tracked + err may be NULL); zero_out [batch] or NULL:
+ * every sequence's word is set to 0 (the tracker's inside counter). *waves and *cap receive the wavefronts
+ * per sequence and the staged keypoint capacity that the launch chose for (batch, n_bound). Complete on return. */
+int svo_reproj_gn_batch(svo_handle *h, int batch, int stride, const int32_t *n_dev, int n_bound, svo_kp2d *kps2d,
+                        const svo_kp3d *kps3d, uint32_t *flags, const svo_camera_settings *cam,
+                        const svo_kp2d *tracked, const float *err, const float *pose_in, float *pose_out,
+                        float *cost, svo_gn_trace *trace, int32_t *zero_out, int *waves, int *cap);
+/* Diagnostic: the depth filter update (svo_depth_filter_update) of `batch` sequences in one launch, with explicit
+ * references, laid out as above (kf_pose [batch * stride][6], frame_pose [batch][6]). do_flags: the counter
+ * rules of StereoSlam::new_image (src/lib/stereo_slam.cpp:212-216) are applied to `flags`; do_reproject: kps2d
+ * receives project_keypoints(frame_pose, kps3d) and inside_count[b] (or NULL; the caller zeroes it) is
+ * increased by the keypoints of sequence b that KeyFrameManager::keyframe_needed counts in a width x height
+ * image. Without a switch its outputs are not written. Complete on return. */
+int svo_filter_update_batch(svo_handle *h, int batch, int stride, const int32_t *n_dev, int n_bound, svo_kp2d *kps2d,
+                            svo_kp3d *kps3d, uint32_t *flags, const svo_camera_settings *cam,
+                            const float *frame_pose, const float *disparity, const svo_kp3d *ref3d,
+                            const svo_kp2d *ref2d, const float *kf_pose, int32_t *outlier_count,
+                            int32_t *inlier_count, float *kf_inv_depth, float *kf_variance,
+                            int do_outlier_check, int do_update, int do_flags, int do_reproject, int width,
+                            int height, int32_t *inside_count);
 
 #ifdef __cplusplus
 }

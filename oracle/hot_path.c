@@ -682,13 +682,15 @@ static float reproj_do_calc(const svo_kp2d *kps2d, const svo_kp3d *kps3d, const 
     return tot;
 }
 
-/* PoseRefinerCallback::get_gradient — src/lib/pose_refinement.cpp:350-412 */
-static void reproj_get_gradient(const svo_kp2d *kps2d, const svo_kp3d *kps3d,
-                                const uint32_t *flags, int n, const svo_camera_settings *cam,
-                                const float pose[6], svo_kp2d *proj, float grad[6])
+/* the loop of PoseRefinerCallback::get_gradient — src/lib/pose_refinement.cpp:350-396: the 36 sums of
+ * `hessian += J^T J` and the 6 of `err += J^T diff`, in keypoint order */
+void svo_o_reproj_normal(const svo_kp2d *kps2d, const svo_kp3d *kps3d, const uint32_t *flags, int n,
+                         const svo_camera_settings *cam, const float pose[6], float H[36], float err[6])
 {
+    svo_kp2d *proj = (svo_kp2d *)malloc(sizeof(svo_kp2d) * (size_t)(n > 0 ? n : 1));
     svo_o_project_keypoints(pose, kps3d, n, cam, proj);
-    float err[6] = { 0 }, H[36] = { 0 };
+    memset(H, 0, sizeof(float) * 36);
+    memset(err, 0, sizeof(float) * 6);
     float rot[9], inv_rot[9];
     svo_o_pose_matrices(pose, rot, inv_rot);
     const float fx = cam->fx, fy = cam->fy;
@@ -715,6 +717,16 @@ static void reproj_get_gradient(const svo_kp2d *kps2d, const svo_kp3d *kps3d,
             err[a] += s;
         }
     }
+    free(proj);
+}
+
+/* PoseRefinerCallback::get_gradient — src/lib/pose_refinement.cpp:350-412 */
+static void reproj_get_gradient(const svo_kp2d *kps2d, const svo_kp3d *kps3d,
+                                const uint32_t *flags, int n, const svo_camera_settings *cam,
+                                const float pose[6], float grad[6])
+{
+    float err[6], H[36];
+    svo_o_reproj_normal(kps2d, kps3d, flags, n, cam, pose, H, err);
     float Hinv[36], twist[6];
     svo_o_inv_svd(H, 6, Hinv);
     for (int a = 0; a < 6; a++) {
@@ -740,7 +752,7 @@ float svo_o_reproj_gn(const svo_kp2d *kps2d, const svo_kp3d *kps3d, const uint32
     int i;
     for (i = 0; i < maxIter; i++) {
         float gradient[6];
-        reproj_get_gradient(kps2d, kps3d, flags, n, cam, x0, proj, gradient);
+        reproj_get_gradient(kps2d, kps3d, flags, n, cam, x0, gradient);
         n_grad++;
         float k = 1.0f;
         for (; i < maxIter; i++) {
@@ -850,7 +862,7 @@ void svo_o_outlier_check(const svo_kp2d *kps2d, const float *disparity, int n,
     svo_o_pose_matrices(frame_pose, rot, inv_rot);
     for (int i = 0; i < n; i++) {
         const float d = disparity[i];
-        const float _z = baseline / (d > 0.5f ? d : 0.5f);
+        const float _z = baseline / (d < 0.5f ? 0.5f : d);   /* std::max<float>(d, 0.5): (a < b) ? b : a, a NaN stays */
         const float _x = (kps2d[i].x - cx) / fx * _z;
         const float _y = (kps2d[i].y - cy) / fy * _z;
         float p[3] = { _x, _y, _z };
@@ -928,4 +940,26 @@ void svo_o_update_kps3d(const svo_kp2d *kps2d, svo_kp3d *kps3d, const uint32_t *
         kps3d[i].y = c1[1] + cp[1];
         kps3d[i].z = c1[2] + cp[2];
     }
+}
+
+/* the two counter rules of StereoSlam::new_image — src/lib/stereo_slam.cpp:212-216 */
+void svo_o_filter_flags(uint32_t *flags, const int32_t *outlier_count, const int32_t *inlier_count, int n)
+{
+    for (int i = 0; i < n; i++) {
+        if (outlier_count[i] > inlier_count[i]) flags[i] |= SVO_IGNORE_COMPLETELY;
+        if (inlier_count[i] > outlier_count[i]) flags[i] &= ~(uint32_t)SVO_IGNORE_TEMPORARY;
+    }
+}
+
+/* the counter of KeyFrameManager::keyframe_needed — src/lib/keyframe_manager.cpp:53-62 */
+int svo_o_inside_count(const svo_kp2d *kps2d, const uint32_t *flags, int n, int image_width, int image_height)
+{
+    int inside = 0;
+    for (int i = 0; i < n; i++) {
+        const svo_kp2d kp = kps2d[i];
+        if (kp.x > 0 && kp.y > 0 && kp.x < image_width && kp.y < image_height &&
+            !(flags[i] & SVO_IGNORE_COMPLETELY))
+            inside++;
+    }
+    return inside;
 }

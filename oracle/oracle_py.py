@@ -271,6 +271,18 @@ def reproj_gn(kps2d, kps3d, flags, cam, pose_in):
     return out, cost, tr.as_dict()
 
 
+def reproj_normal(kps2d, kps3d, flags, cam, pose):
+    """the sums of one get_gradient call: (H[36], err[6])"""
+    kps2d = _f32(kps2d)
+    kps3d = _f32(kps3d)
+    flags = np.ascontiguousarray(flags, dtype=np.uint32)
+    pose = _f32(pose)
+    H = np.zeros(36, np.float32)
+    e = np.zeros(6, np.float32)
+    lib().svo_o_reproj_normal(_p(kps2d), _p(kps3d), _p(flags), kps2d.shape[0], C.byref(cam), _p(pose), _p(H), _p(e))
+    return H, e
+
+
 def ssd_disparity(left, right, kps2d, win, search_x, search_y, clamp_half=1):
     kps2d = _f32(kps2d)
     n = kps2d.shape[0]
@@ -307,6 +319,20 @@ def update_kps3d(kps2d, kps3d, flags, cam, frame_pose, ref2d, kf_pose, outlier, 
     lib().svo_o_update_kps3d(_p(kps2d), _p(kps3d), _p(flags), kps2d.shape[0], C.byref(cam),
                              _p(frame_pose), _p(ref2d), _p(kf_pose), _p(outlier), _p(kf_x), _p(kf_p))
     return kps3d, outlier, kf_x, kf_p
+
+
+def filter_flags(flags, outlier, inlier):
+    flags = np.ascontiguousarray(flags, dtype=np.uint32).copy()
+    outlier = np.ascontiguousarray(outlier, dtype=np.int32)
+    inlier = np.ascontiguousarray(inlier, dtype=np.int32)
+    lib().svo_o_filter_flags(_p(flags), _p(outlier), _p(inlier), flags.shape[0])
+    return flags
+
+
+def inside_count(kps2d, flags, width, height):
+    kps2d = _f32(kps2d)
+    flags = np.ascontiguousarray(flags, dtype=np.uint32)
+    return lib().svo_o_inside_count(_p(kps2d), _p(flags), kps2d.shape[0], int(width), int(height))
 
 
 def fast_score_nms(img, threshold=6):

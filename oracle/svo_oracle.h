@@ -101,6 +101,10 @@ float svo_o_reproj_gn(const svo_kp2d *kps2d, const svo_kp3d *kps3d, const uint32
                       int n, const svo_camera_settings *cam,
                       const float pose_in[6], float pose_out[6], svo_gn_trace *trace);
 
+/* the 36 + 6 sums of one get_gradient call (pose_refinement.cpp:350-396) exposed for unit parity */
+void svo_o_reproj_normal(const svo_kp2d *kps2d, const svo_kp3d *kps3d, const uint32_t *flags, int n,
+                         const svo_camera_settings *cam, const float pose[6], float H[36], float err[6]);
+
 /* C1: DepthFilter::calculate_disparities, src/lib/depth_filter.cpp:259-327
  * (clamp_half=1) and the same loop in DepthCalculator::calculate_depth,
  * src/lib/depth_calculator.cpp:200-240 (clamp_half=0: no max(0.5,.), no OOB skip). */
@@ -120,6 +124,11 @@ void svo_o_update_kps3d(const svo_kp2d *kps2d, svo_kp3d *kps3d, const uint32_t *
                         const svo_camera_settings *cam, const float frame_pose[6],
                         const svo_kp2d *ref2d, const float *kf_pose /* n*6 */,
                         int32_t *outlier_count, float *kf_inv_depth, float *kf_variance);
+
+/* D3: the counter rules of StereoSlam::new_image, src/lib/stereo_slam.cpp:212-216, on the SVO_IGNORE_* bits, and
+ * the counter of KeyFrameManager::keyframe_needed, src/lib/keyframe_manager.cpp:53-62 (tracker.c calls both) */
+void svo_o_filter_flags(uint32_t *flags, const int32_t *outlier_count, const int32_t *inlier_count, int n);
+int  svo_o_inside_count(const svo_kp2d *kps2d, const uint32_t *flags, int n, int image_width, int image_height);
 
 /* ---- whole StereoSlam restatement (tracker.c) --------------------------- */
 typedef struct svo_o_slam svo_o_slam;

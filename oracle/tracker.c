@@ -580,13 +580,10 @@ static keyframe_t *create_keyframe(svo_o_slam *s, frame_t *f)
 static int keyframe_needed(const svo_o_slam *s, const frame_t *f)
 {
     const int image_width = f->im->left[0].width, image_height = f->im->left[0].height;
-    int inside = 0;
-    for (int i = 0; i < f->kps.n; i++) {
-        const svo_kp2d kp = f->kps.kps2d[i];
-        if (kp.x > 0 && kp.y > 0 && kp.x < image_width && kp.y < image_height &&
-            !f->kps.info[i].ignore_completely)
-            inside++;
-    }
+    uint32_t *fl = (uint32_t *)malloc(sizeof(uint32_t) * (size_t)(f->kps.n + 1));
+    for (int i = 0; i < f->kps.n; i++) fl[i] = f->kps.info[i].ignore_completely ? SVO_IGNORE_COMPLETELY : 0;
+    const int inside = svo_o_inside_count(f->kps.kps2d, fl, f->kps.n, image_width, image_height);
+    free(fl);
     const int max_keypoints = (image_width / s->cam.grid_width) * (image_height / s->cam.grid_height);
     return inside < 0.66 * max_keypoints;
 }
@@ -764,8 +761,10 @@ int svo_o_slam_new_image(svo_o_slam *s, const uint8_t *left, const uint8_t *righ
             in->outlier_count = outl[i]; in->inlier_count = inl[i];
             in->kf_inv_depth = kx[i]; in->kf_variance = kP[i];
             keyframe_t *kf = &s->keyframes[in->keyframe_id];
-            if (in->outlier_count > in->inlier_count) in->ignore_completely = 1;
-            if (in->inlier_count > in->outlier_count) in->ignore_temporary = 0;
+            uint32_t fb = (in->ignore_completely ? SVO_IGNORE_COMPLETELY : 0) | (in->ignore_temporary ? SVO_IGNORE_TEMPORARY : 0);
+            svo_o_filter_flags(&fb, &in->outlier_count, &in->inlier_count, 1);
+            in->ignore_completely = (fb & SVO_IGNORE_COMPLETELY) != 0;
+            in->ignore_temporary = (fb & SVO_IGNORE_TEMPORARY) != 0;
             kf->kps.kps3d[in->keypoint_index] = updated[i];
             f->kps.kps3d[i] = updated[i];
             svo_kp_info *ki = &kf->kps.info[in->keypoint_index];

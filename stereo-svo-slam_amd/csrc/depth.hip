@@ -351,7 +351,7 @@ __global__ __launch_bounds__(64) void filter_update_kernel(const FilterArgs* __r
 
         if (a.do_outlier_check) {   // depth_filter.cpp:52-128
             const float d = G(a.disparity)[i];
-            const float _z = baseline / fmaxf(d, 0.5f);
+            const float _z = baseline / (d < 0.5f ? 0.5f : d);   // std::max<float>(d, 0.5) is (a < b) ? b : a: a NaN stays (fmaxf drops it)
             const float _x = (kp2.x - cx) / fx * _z;
             const float _y = (kp2.y - cy) / fy * _z;
             float pw[3] = {_x, _y, _z};

@@ -668,6 +668,112 @@ extern "C" int svo_pinv6_check(svo_handle* h, const float* H_dev, int n, float* 
     return SVO_OK;
 }
 
+// svo_reproj_gn_batch / svo_filter_update_batch: launch_reproj and launch_filter with a batch of sequences, the way
+// the tracker calls them, on caller-made arrays. The counts are read back and checked before the launch (a
+// diagnostic may wait): a count beyond n_bound or the stride would make a block read its neighbour's arrays.
+static int check_batch_counts(const char* who, int batch, int stride, const int32_t* n_dev, int n_bound) {
+    if (batch < 1 || batch > 4096 || !n_dev || n_bound < 0 || stride < n_bound)
+        return svo_set_error(SVO_ERR_INVALID, "%s: need 1 <= batch <= 4096, n_dev and 0 <= n_bound <= stride", who);
+    std::vector<int32_t> n((size_t)batch);
+    HIP_TRY(hipMemcpy(n.data(), n_dev, sizeof(int32_t) * (size_t)batch, hipMemcpyDeviceToHost));
+    for (int b = 0; b < batch; b++)
+        if (n[(size_t)b] < 0 || n[(size_t)b] > n_bound)
+            return svo_set_error(SVO_ERR_INVALID, "%s: n_dev[%d] = %d is outside 0..n_bound = %d", who, b, n[(size_t)b], n_bound);
+    return SVO_OK;
+}
+
+template <typename T>
+static int stage_blocks(svo_handle* h, const std::vector<T>& host, T** dev) {
+    const size_t bytes = (sizeof(T) * host.size() + 255) & ~(size_t)255;
+    if (bytes > h->ring_cap) return svo_set_error(SVO_ERR_CAPACITY, "argument blocks do not fit the ring");
+    if (h->ring_off + bytes > h->ring_cap) {
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        h->ring_off = 0;
+    }
+    T* d = reinterpret_cast<T*>(h->ring.get() + h->ring_off);
+    h->ring_off += bytes;
+    HIP_TRY(hipMemcpyAsync(d, host.data(), sizeof(T) * host.size(), hipMemcpyHostToDevice, h->stream));
+    *dev = d;
+    return SVO_OK;
+}
+
+extern "C" int svo_reproj_gn_batch(svo_handle* h, int batch, int stride, const int32_t* n_dev, int n_bound, svo_kp2d* kps2d,
+                                   const svo_kp3d* kps3d, uint32_t* flags, const svo_camera_settings* cam,
+                                   const svo_kp2d* tracked, const float* err, const float* pose_in, float* pose_out,
+                                   float* cost, svo_gn_trace* trace, int32_t* zero_out, int* waves, int* cap) {
+    CHECK_H(h);
+    if (!cam || !pose_in || !pose_out || (n_bound > 0 && (!kps2d || !kps3d || !flags)) || (!tracked != !err))
+        return svo_set_error(SVO_ERR_INVALID, "svo_reproj_gn_batch: bad arguments");
+    int rc = check_batch_counts("svo_reproj_gn_batch", batch, stride, n_dev, n_bound);
+    if (rc) return rc;
+    std::vector<ReprojArgs> blocks((size_t)batch);
+    for (int b = 0; b < batch; b++) {
+        ReprojArgs& ra = blocks[(size_t)b];
+        const size_t o = (size_t)b * (size_t)stride;
+        memset(&ra, 0, sizeof(ra));
+        ra.cam = *cam;
+        ra.n_ptr = n_dev + b;
+        ra.kps2d = kps2d + o; ra.kps3d = kps3d + o; ra.flags = flags + o;
+        ra.tracked = tracked ? tracked + o : nullptr; ra.err = err ? err + o : nullptr;
+        ra.pose_in = pose_in + 6 * (size_t)b; ra.pose_out = pose_out + 6 * (size_t)b;
+        ra.cost_out = cost ? cost + b : nullptr; ra.trace = trace ? trace + b : nullptr;
+        ra.exact_pinv = h->exact_pinv;
+        ra.zero_out = zero_out ? zero_out + b : nullptr;
+    }
+    ReprojArgs* d;
+    rc = stage_blocks(h, blocks, &d);
+    if (rc) return rc;
+    const LaunchStatus st = launch_reproj(d, batch, n_bound, h->stream);
+    HIP_TRY(st.err);
+    if (waves) *waves = st.shape.waves;
+    if (cap) *cap = st.shape.cap;
+    if (!st.shape.fits) return svo_set_error(SVO_ERR_CAPACITY, "svo_reproj_gn_batch: %d keypoints do not fit LDS", n_bound);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return SVO_OK;
+}
+
+extern "C" int svo_filter_update_batch(svo_handle* h, int batch, int stride, const int32_t* n_dev, int n_bound, svo_kp2d* kps2d,
+                                       svo_kp3d* kps3d, uint32_t* flags, const svo_camera_settings* cam,
+                                       const float* frame_pose, const float* disparity, const svo_kp3d* ref3d,
+                                       const svo_kp2d* ref2d, const float* kf_pose, int32_t* outlier_count,
+                                       int32_t* inlier_count, float* kf_inv_depth, float* kf_variance,
+                                       int do_outlier_check, int do_update, int do_flags, int do_reproject, int width,
+                                       int height, int32_t* inside_count) {
+    CHECK_H(h);
+    if (!cam || !frame_pose || !kf_pose || !kps2d || !kps3d || !flags || !outlier_count || !inlier_count ||
+        !kf_inv_depth || !kf_variance || (do_outlier_check && !disparity))
+        return svo_set_error(SVO_ERR_INVALID, "svo_filter_update_batch: bad arguments");
+    int rc = check_batch_counts("svo_filter_update_batch", batch, stride, n_dev, n_bound);
+    if (rc) return rc;
+    std::vector<FilterArgs> blocks((size_t)batch);
+    for (int b = 0; b < batch; b++) {
+        FilterArgs& fa = blocks[(size_t)b];
+        const size_t o = (size_t)b * (size_t)stride;
+        memset(&fa, 0, sizeof(fa));
+        fa.cam = *cam;
+        fa.n_ptr = n_dev + b;
+        fa.frame_pose = frame_pose + 6 * (size_t)b;
+        fa.kps2d = kps2d + o; fa.kps3d = kps3d + o; fa.flags = flags + o;
+        fa.outlier_count = outlier_count + o; fa.inlier_count = inlier_count + o;
+        fa.kf_inv_depth = kf_inv_depth + o; fa.kf_variance = kf_variance + o;
+        fa.disparity = disparity ? disparity + o : nullptr;
+        fa.ref3d = ref3d ? ref3d + o : nullptr; fa.ref2d = ref2d ? ref2d + o : nullptr;
+        fa.kf_pose = kf_pose + 6 * o;
+        fa.do_outlier_check = do_outlier_check; fa.do_update = do_update;
+        fa.do_flags = do_flags; fa.do_reproject = do_reproject;
+        fa.width = width; fa.height = height;
+        fa.inside_count = inside_count ? inside_count + b : nullptr;
+    }
+    FilterArgs* d;
+    rc = stage_blocks(h, blocks, &d);
+    if (rc) return rc;
+    launch_filter(d, batch, n_bound, h->stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return SVO_OK;
+}
+
 // svo_solve6_check: the exact Gauss-Newton solve delta = pinv(H) b, one system per wavefront (H and b loaded
 // alike by all 64 lanes). IMPL 0 is the round-4 solve: jacobi_svd6_lanes, then svd6_pinv and delta = Hinv b
 // on wave-uniform values. IMPL 1 is the kernels' solve: svd6_sweeps_lanes + svd6_tail_lanes, every element

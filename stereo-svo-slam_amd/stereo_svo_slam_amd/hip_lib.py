@@ -37,6 +37,7 @@ SYMBOLS = (
     "svo_export_capacity", "svo_submit_export", "svo_export", "svo_pack_keypoints",
     "svo_snapshot_size", "svo_submit_save", "svo_save_sequences", "svo_submit_load", "svo_load_sequences",
     "svo_snapshot_info", "svo_copy_segments",
+    "svo_reproj_gn_batch", "svo_filter_update_batch",
 )
 
 # svo_ctx_set_input_format / svo_convert_frames: how the buffers of a sequence become its two gray images
@@ -417,6 +418,22 @@ class Handle:
                                    _ptr(cost), _ptr(trace)))
         return pose_out, cost, trace
 
+    def reproj_gn_batch(self, n, n_bound, kps2d, kps3d, flags, cam, pose_in, tracked=None, err=None, zero_out=None):
+        """Diagnostic: svo_reproj_gn of len(n) sequences in one launch. n: int32 [batch] device; the keypoint
+        arrays are [batch, stride, ..] device tensors (kps2d and flags are updated in place). Returns (pose_out
+        [batch, 6], cost [batch], trace [batch] bytes, waves, cap)."""
+        batch, stride = kps2d.shape[0], kps2d.shape[1]
+        dev = kps2d.device
+        pose_out = torch.zeros((batch, 6), dtype=torch.float32, device=dev)
+        cost = torch.zeros(batch, dtype=torch.float32, device=dev)
+        trace = torch.zeros((batch, GN_TRACE_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+        waves, cap = C.c_int(0), C.c_int(0)
+        _check(lib().svo_reproj_gn_batch(self._h, batch, stride, _ptr(n), int(n_bound), _ptr(kps2d), _ptr(kps3d),
+                                         _ptr(flags), C.byref(cam), _ptr(tracked), _ptr(err), _ptr(pose_in),
+                                         _ptr(pose_out), _ptr(cost), _ptr(trace), _ptr(zero_out), C.byref(waves),
+                                         C.byref(cap)))
+        return pose_out, cost, trace, waves.value, cap.value
+
     # -- C1 ---------------------------------------------------------------
     def ssd_disparity(self, left, right, kps2d, win, search_x, search_y, clamp_half=1):
         n = kps2d.shape[0]
@@ -434,6 +451,19 @@ class Handle:
             self._h, _ptr(kps2d), _ptr(kps3d), _ptr(flags), n, C.byref(cam), _ptr(frame_pose),
             _ptr(disparity), _ptr(ref3d), _ptr(ref2d), _ptr(kf_pose), _ptr(outlier), _ptr(inlier),
             _ptr(kf_x), _ptr(kf_p), do_outlier_check, do_update))
+
+    def filter_update_batch(self, n, n_bound, kps2d, kps3d, flags, cam, frame_pose, disparity, ref3d, ref2d, kf_pose,
+                            outlier, inlier, kf_x, kf_p, do_outlier_check, do_update, do_flags, do_reproject, width,
+                            height, inside_count):
+        """Diagnostic: svo_depth_filter_update of len(n) sequences in one launch, with the flag write-back, the
+        reprojection and the inside counter of the tracker's launch. The keypoint arrays are [batch, stride, ..]
+        device tensors, updated in place; inside_count int32 [batch], zeroed by the caller."""
+        batch, stride = kps2d.shape[0], kps2d.shape[1]
+        _check(lib().svo_filter_update_batch(
+            self._h, batch, stride, _ptr(n), int(n_bound), _ptr(kps2d), _ptr(kps3d), _ptr(flags), C.byref(cam),
+            _ptr(frame_pose), _ptr(disparity), _ptr(ref3d), _ptr(ref2d), _ptr(kf_pose), _ptr(outlier), _ptr(inlier),
+            _ptr(kf_x), _ptr(kf_p), int(do_outlier_check), int(do_update), int(do_flags), int(do_reproject),
+            int(width), int(height), _ptr(inside_count)))
 
 
 def detect_to_numpy(cells, counts):
