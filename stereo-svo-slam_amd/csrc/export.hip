@@ -1,7 +1,7 @@
 // export.hip — SoA keypoint sets into the AoS records of the C ABI (svo_kp2d, svo_kp3d, svo_kp_info), many sets
 // in one launch. The reference hands its state out one object at a time (StereoSlam::get_frame / get_keyframes,
 // src/lib/stereo_slam.cpp:273-289: a Frame carries vector<KeyPoint2d>, vector<KeyPoint3d> and
-// vector<KeyPointInformation>); the per-sequence getters of svo_group.hip restate that with twelve blocking
+// vector<KeyPointInformation>); the per-sequence getters of svo_ctx.hip restate that with twelve blocking
 // copies per sequence and a host loop. This is the bulk form: the records are built on the GPU, byte for byte
 // the getters' (a cleared record, then its fields: `_pad` is 0).
 //

@@ -1,5 +1,5 @@
 // snapshot.hip — many 2-D byte segments copied device to device in one launch: the data path of saving and
-// loading a slot's sequence state (svo_submit_save / svo_submit_load, svo_group.hip) and of svo_copy_segments.
+// loading a slot's sequence state (svo_submit_save / svo_submit_load, svo_group_snapshot.hip) and of svo_copy_segments.
 // The reference has no checkpoint or resume; a snapshot's data part is the image pyramids of the live
 // keyframes, the keypoint arrays of the frame and of every keyframe and two words, scattered over image sets,
 // keyframe slabs and per-sequence arrays on one side and packed behind offsets on the other. One kernel does both

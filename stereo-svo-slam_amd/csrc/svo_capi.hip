@@ -330,9 +330,8 @@ extern "C" int svo_copy_segments(svo_handle* h, int n, const svo_copy_segment* s
         cut_copy_tiles(g.src, g.dst, g.row_bytes, g.rows, g.src_pitch, g.dst_pitch, tiles);
     }
     if (tiles.empty()) return SVO_OK;
-    size_t chunk = std::min<size_t>(tiles.size(), (size_t)INT_MAX);
-    if (const char* e = getenv("SVO_SNAPSHOT_TABLE_TILES"))     // diagnostic: a smaller table (tests reach the chunked launches)
-        chunk = std::max<size_t>(1, std::min<size_t>(chunk, (size_t)atoll(e)));
+    // (SVO_SNAPSHOT_TABLE_TILES: a smaller table, so that tests reach the chunked launches)
+    const size_t chunk = table_tiles("SVO_SNAPSHOT_TABLE_TILES", std::min<size_t>(tiles.size(), (size_t)INT_MAX));
     if (chunk > h->copy_ws_count) {
         HIP_TRY(hipStreamSynchronize(h->stream));      // (the old table may still be read)
         h->copy_ws.reset();
@@ -340,14 +339,12 @@ extern "C" int svo_copy_segments(svo_handle* h, int n, const svo_copy_segment* s
         HIP_TRY(dev_malloc(h->copy_ws, sizeof(CopyTile) * chunk));
         h->copy_ws_count = chunk;
     }
-    for (size_t t0 = 0; t0 < tiles.size(); t0 += chunk) {
-        const size_t m = std::min(chunk, tiles.size() - t0);
-        if (t0 > 0) HIP_TRY(hipStreamSynchronize(h->stream));   // (the table is filled again)
-        HIP_TRY(hipMemcpyAsync(h->copy_ws.get(), tiles.data() + t0, sizeof(CopyTile) * m, hipMemcpyHostToDevice, h->stream));
-        launch_copy_tiles(h->copy_ws.get(), (int)m, h->stream);
-        HIP_TRY(hipGetLastError());
-    }
-    HIP_TRY(hipStreamSynchronize(h->stream));          // (the table's upload read `tiles`)
+    std::vector<CopyTile> host(chunk);
+    TileTable table{host.data(), h->copy_ws.get(), chunk, h->stream, &launch_copy_tiles};
+    for (const CopyTile& t : tiles)
+        if (const int rc = table.add(t)) return rc;
+    if (const int rc = table.launch(false)) return rc;
+    HIP_TRY(hipStreamSynchronize(h->stream));          // (the table's upload read `host`)
     return SVO_OK;
 }
 

@@ -1,6 +1,7 @@
-// svo_ctx.hip — the public svo_ctx of the C ABI: a set of sequence groups (svo_group.hip), each
+// svo_ctx.hip — the public svo_ctx of the C ABI: a set of sequence groups (svo_group.hpp), each
 // on its own stream and host thread, with a queue of submitted frame sets, and the extern "C"
-// entry points of the ctx (the per-sequence getters are in svo_group.hip, behind ctx_seq).
+// entry points of the ctx. The per-sequence getters at the end read a group's state directly
+// (svo_group_state.hpp); everything else drives the groups through svo_group.hpp.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -17,6 +18,7 @@
 #include <vector>
 
 #include "svo_group.hpp"
+#include "svo_group_state.hpp"
 #include "svo_host.hpp"
 #include "svo_kernels.hpp"
 
@@ -154,8 +156,8 @@ int ctx_drain(svo_ctx* c) {
     return rc;
 }
 
-}  // namespace
-
+// the group of ctx sequence `seq` and its index there, once every queue of the ctx has drained, with the ctx's
+// device current (the per-sequence getters start here)
 int ctx_seq(svo_ctx* c, int seq, svo_group** g, int* local) {
     if (!c || seq < 0 || seq >= c->B) return svo_set_error(SVO_ERR_INVALID, "bad ctx / sequence index");
     const int rc = ctx_drain(c);
@@ -169,6 +171,8 @@ int ctx_seq(svo_ctx* c, int seq, svo_group** g, int* local) {
     HIP_TRY(hipSetDevice(c->device));
     return SVO_OK;
 }
+
+}  // namespace
 
 extern "C" int svo_ctx_create(const svo_camera_settings* cam, int width, int height, int n_sequences,
                               int device, svo_ctx** out) {
@@ -568,4 +572,120 @@ extern "C" int svo_ctx_get_launch_shapes(svo_ctx* c, svo_launch_shape* out, int 
     *n = (int)all.size();
     for (int i = 0; i < std::min(max, *n); i++) out[i] = all[i];
     return SVO_OK;
+}
+
+// ------------------------------------------------------------------ per-sequence getters of the C ABI
+// (each one starts at ctx_seq: the queues have drained, so the group's state is read between two steps)
+
+static int fetch_info(int n, const svo::KpsDev& k, svo_kp2d* kps2d, svo_kp3d* kps3d, svo_kp_info* info) {
+    if (n <= 0) return SVO_OK;
+    if (kps2d) HIP_TRY(hipMemcpy(kps2d, k.kps2d, sizeof(svo_kp2d) * n, hipMemcpyDeviceToHost));
+    if (kps3d) HIP_TRY(hipMemcpy(kps3d, k.kps3d, sizeof(svo_kp3d) * n, hipMemcpyDeviceToHost));
+    if (!info) return SVO_OK;
+    std::vector<uint32_t> fl(n), col(n);
+    std::vector<int> kf(n), ki(n), ou(n), in(n), lt(n);
+    std::vector<float> kx(n), kP(n), sc(n);
+    const struct { void* dst; const void* src; } arrays[] = {
+        {fl.data(), k.flags}, {ou.data(), k.outl}, {in.data(), k.inl}, {kf.data(), k.kf_id}, {ki.data(), k.kp_index},
+        {kx.data(), k.kfx}, {kP.data(), k.kfP}, {sc.data(), k.score}, {lt.data(), k.level_type}, {col.data(), k.color}};
+    for (const auto& a : arrays) HIP_TRY(hipMemcpy(a.dst, a.src, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));   // (all 4-byte)
+    for (int i = 0; i < n; i++) {
+        svo_kp_info& o = svo::clear(info[i]);
+        o.score = sc[i]; o.level = lt[i] & 0xff; o.type = (lt[i] >> 8) & 0xff;
+        o.keyframe_id = kf[i]; o.keypoint_index = ki[i];
+        o.color[0] = col[i] & 0xff; o.color[1] = (col[i] >> 8) & 0xff; o.color[2] = (col[i] >> 16) & 0xff;
+        o.ignore_during_refinement = (fl[i] & SVO_IGNORE_DURING_REFINEMENT) != 0;
+        o.ignore_completely = (fl[i] & SVO_IGNORE_COMPLETELY) != 0;
+        o.ignore_temporary = (fl[i] & SVO_IGNORE_TEMPORARY) != 0;
+        o.outlier_count = ou[i]; o.inlier_count = in[i];
+        o.kf_inv_depth = kx[i]; o.kf_variance = kP[i];
+    }
+    return SVO_OK;
+}
+
+extern "C" int svo_get_pose(svo_ctx* ctx, int seq, float pose[6]) {
+    svo_group* c; int s;
+    if (const int rc = ctx_seq(ctx, seq, &c, &s)) return rc;
+    svo::flush_pending(c);
+    std::memcpy(pose, c->seqs[s].pose, sizeof(float) * 6);
+    return SVO_OK;
+}
+
+extern "C" int svo_get_frame_keypoints(svo_ctx* ctx, int seq, svo_kp2d* kps2d, svo_kp3d* kps3d,
+                                       svo_kp_info* info, int cap, int* n) {
+    svo_group* c; int s;
+    if (const int rc = ctx_seq(ctx, seq, &c, &s)) return rc;
+    const svo::Seq& q = c->seqs[s];
+    if (n) *n = q.n_host;
+    return fetch_info(std::min(cap, q.n_host), q.kps[q.cur], kps2d, kps3d, info);
+}
+
+extern "C" int svo_get_keyframe_count(svo_ctx* ctx, int seq, int* count) {
+    svo_group* c; int s;
+    if (const int rc = ctx_seq(ctx, seq, &c, &s)) return rc;
+    if (count) *count = (int)c->seqs[s].kfs.size();
+    return SVO_OK;
+}
+
+extern "C" int svo_get_keyframe(svo_ctx* ctx, int seq, int id, svo_kp2d* kps2d, svo_kp3d* kps3d,
+                                svo_kp_info* info, float pose[6], int cap, int* n) {
+    svo_group* c; int s;
+    if (const int rc = ctx_seq(ctx, seq, &c, &s)) return rc;
+    const svo::Seq& q = c->seqs[s];
+    if (id < 0 || id >= (int)q.kfs.size()) return svo_set_error(SVO_ERR_INVALID, "keyframe %d does not exist", id);
+    const svo::KfHost& k = q.kfs[id];
+    if (n) *n = k.n;
+    if (pose) std::memcpy(pose, k.pose, sizeof(float) * 6);
+    return fetch_info(std::min(cap, k.n), k.kps, kps2d, kps3d, info);
+}
+
+extern "C" int svo_get_trajectory(svo_ctx* ctx, int seq, svo_pose* out, int cap, int* n) {
+    svo_group* c; int s;
+    if (const int rc = ctx_seq(ctx, seq, &c, &s)) return rc;
+    svo::flush_pending(c);
+    const svo::Seq& q = c->seqs[s];
+    if (n) *n = (int)q.trajectory.size();
+    const int m = std::min<int>(cap, (int)q.trajectory.size());
+    if (out && m > 0) std::memcpy(out, q.trajectory.data(), sizeof(svo_pose) * m);
+    return SVO_OK;
+}
+
+extern "C" int svo_update_pose(svo_ctx* ctx, int seq, const float pose[6], const float speed[6],
+                               const float pose_var[6], const float speed_var[6], double dt,
+                               float filtered[6]) {
+    svo_group* c; int s;
+    if (const int rc = ctx_seq(ctx, seq, &c, &s)) return rc;
+    svo::flush_pending(c);
+    c->seqs[s].kf.update(pose, speed, pose_var, speed_var, dt, filtered);
+    return SVO_OK;
+}
+
+extern "C" int svo_get_frame_stats(svo_ctx* ctx, int seq, svo_frame_stats* out) {
+    svo_group* c; int s;
+    if (const int rc = ctx_seq(ctx, seq, &c, &s)) return rc;
+    if (out) *out = c->seqs[s].stats;
+    return SVO_OK;
+}
+
+extern "C" int svo_get_finished_runs(svo_ctx* ctx, int seq, int* n) {
+    svo_group* c; int s;
+    if (const int rc = ctx_seq(ctx, seq, &c, &s)) return rc;
+    if (n) *n = (int)std::count_if(c->finished.begin(), c->finished.end(), [s](const svo::FinishedRun& f) { return f.info.seq == s; });
+    return SVO_OK;
+}
+
+extern "C" int svo_get_finished_run(svo_ctx* ctx, int seq, int i, svo_run_info* info, svo_pose* trajectory,
+                                    int cap, int* n_poses) {
+    svo_group* c; int s;
+    if (const int rc = ctx_seq(ctx, seq, &c, &s)) return rc;
+    int k = 0;
+    for (const svo::FinishedRun& f : c->finished) {
+        if (f.info.seq != s || k++ != i) continue;
+        if (info) { *info = f.info; info->seq = seq; }
+        if (n_poses) *n_poses = (int)f.trajectory.size();
+        const int m = std::min<int>(cap, (int)f.trajectory.size());
+        if (trajectory && m > 0) std::memcpy(trajectory, f.trajectory.data(), sizeof(svo_pose) * m);
+        return SVO_OK;
+    }
+    return svo_set_error(SVO_ERR_INVALID, "sequence %d has no finished run %d", seq, i);
 }

@@ -1,4 +1,6 @@
-// svo_group.hpp — one group of sequences (svo_group.hip) as svo_ctx.hip drives it.
+// svo_group.hpp — one group of sequences as svo_ctx.hip drives it: the opaque interface of svo_group.hip (creation,
+// settings, restarts), svo_group_step.hip (grp_new_images), svo_group_export.hip (grp_export, grp_capacity) and
+// svo_group_snapshot.hip (grp_check_snapshot, grp_save, grp_load, grp_snapshot_size).
 #pragma once
 
 #include <cstdint>
@@ -52,7 +54,3 @@ int grp_set_input_format(svo_group* g, int format);
 void grp_enable_timing(svo_group* g, int on);
 svo_totals grp_totals(const svo_group* g);
 const std::vector<svo_launch_shape>& grp_launch_shapes(const svo_group* g);   // (svo_ctx_get_launch_shapes)
-
-// implemented by svo_ctx.hip: the group of ctx sequence `seq` and its index there, once every queue of the ctx
-// has drained, with the ctx's device current (the per-sequence getters of svo_group.hip start here)
-int ctx_seq(svo_ctx* ctx, int seq, svo_group** g, int* local);

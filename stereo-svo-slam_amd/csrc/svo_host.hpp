@@ -1,12 +1,14 @@
-// svo_host.hpp — what the host files of the C ABI share (svo_capi.hip, svo_ctx.hip, svo_group.hip):
-// the thread-local error text, HIP_TRY, and owners of HIP resources, so that every early return of
-// a creation path frees what was made before it.
+// svo_host.hpp — what the host files of the C ABI share (svo_capi.hip, svo_ctx.hip, svo_group*.hip):
+// the thread-local error text, HIP_TRY, owners of HIP resources, so that every early return of
+// a creation path frees what was made before it, and the chunked upload of a tile table.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdarg>
 #include <cstdio>
+#include <cstdlib>
 #include <memory>
 #include <type_traits>
 
@@ -76,5 +78,42 @@ inline hipError_t make_event(Event& ev) {
     ev.reset(h);
     return e;
 }
+
+// a diagnostic *_TABLE_TILES override: a table of at most so many tiles (at least one), so that tests reach the
+// chunked launches
+inline size_t table_tiles(const char* env, size_t cap) {
+    if (const char* e = std::getenv(env)) cap = std::max<size_t>(1, std::min<size_t>(cap, (size_t)std::atoll(e)));
+    return cap;
+}
+
+// A table of at most `cap` tiles, filled on the host (h) and uploaded to its device mirror (d) for
+// run(d, tiles, stream): one launch, unless there are more tiles than the table holds.
+template <typename Tile, typename Launch>
+struct TileTable {
+    Tile* h;
+    Tile* d;
+    size_t cap;
+    hipStream_t stream;
+    Launch run;
+    size_t m = 0;
+    // the tiles so far; `more`: the host table is filled again, so the upload must be over
+    int launch(bool more) {
+        if (m == 0) return SVO_OK;
+        HIP_TRY(hipMemcpyAsync(d, h, sizeof(Tile) * m, hipMemcpyHostToDevice, stream));
+        run(d, (int)m, stream);
+        HIP_TRY(hipGetLastError());
+        if (more) HIP_TRY(hipStreamSynchronize(stream));
+        m = 0;
+        return SVO_OK;
+    }
+    int add(const Tile& t) {
+        if (m == cap)
+            if (const int rc = launch(true)) return rc;
+        h[m++] = t;
+        return SVO_OK;
+    }
+};
+template <typename Tile, typename Launch>
+TileTable(Tile*, Tile*, size_t, hipStream_t, Launch) -> TileTable<Tile, Launch>;
 
 }  // namespace svo

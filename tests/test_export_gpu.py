@@ -441,9 +441,11 @@ def test_many_slots_exporting_every_step_track_like_a_twin(monkeypatch):
     batch = StereoSlamBatch(cfg, cfg["width"], cfg["height"], n_slots)
     twin = StereoSlamBatch(cfg, cfg["width"], cfg["height"], n_slots)
     assert batch.groups() == 3
+    queued = []                                  # (an Export owns the buffers its queued export writes: kept until the wait)
     for k in range(steps):
         batch.submit_packed(batch.pack_images(*sets[k]))
         frames, keyframes = batch.submit_export("frames"), batch.submit_export("last_keyframes", device=True)
+        queued.append((frames, keyframes))
         twin.new_images(*sets[k])
     batch.wait()
     a, b = _getter_state(batch), _getter_state(twin)
