@@ -316,10 +316,45 @@ int svo_get_keyframe(svo_ctx *ctx, int seq, int id, svo_kp2d *kps2d, svo_kp3d *k
                      svo_kp_info *info, float pose[6], int cap, int *n);
 /* get_trajectory (src/lib/stereo_slam.cpp:291-294) */
 int svo_get_trajectory(svo_ctx *ctx, int seq, svo_pose *out, int cap, int *n);
-/* StereoSlam::update_pose (12-state Kalman)             src/lib/stereo_slam.cpp:296-359 */
+/* StereoSlam::update_pose (12-state Kalman)             src/lib/stereo_slam.cpp:296-359
+ * The one-slot form: waits for every queue of the ctx and runs the filter on the calling thread. On an empty or
+ * restarted slot it works on a fresh filter. */
 int svo_update_pose(svo_ctx *ctx, int seq, const float pose[6], const float speed[6],
                     const float pose_var[6], const float speed_var[6], double dt,
                     float filtered[6]);
+
+/* ---- batched pose-filter updates: the IMU loop of many slots as one queued job per group -------------------------
+ * The batched, queued form of svo_update_pose: counts[i] samples for slot seqs[i] (seqs == NULL: slot i, n is then
+ * the ctx's slots; a count of 0 leaves the slot untouched). `samples` holds the samples of seqs[0] first, in the
+ * order they are applied, then those of seqs[1], and so on. Every group that owns a named slot with a positive count
+ * gets one entry in its queue, behind the frame sets, restarts, exports, saves and loads submitted so far; nothing
+ * is waited for and no group waits for another. The group's worker applies the pending update of its last frame
+ * (as svo_get_pose does), uploads the filter states and samples of its named slots in one copy, runs the filter of
+ * all of them in ONE kernel launch (pose_filter.hip), downloads the states in one copy and stores them: every byte
+ * of a slot's filter equals what the same svo_update_pose calls in the same order leave, for finite inputs (others:
+ * the call terminates, the values are unspecified). The slot's pose, time stamp and trajectory are not touched.
+ * SVO_POSE_SAMPLE_CHAIN: the sample measures the filtered pose of the slot's previous sample of this call, the
+ * slot's first sample the slot's current pose (svo_get_pose; zeros on an empty slot): SlamApp::update_pose_from_imu
+ * (src/app/slam_app.cpp:111-135) of one frame interval is one call without a round trip.
+ * seqs, counts and samples are copied at submit time; filtered ([sum of counts][6], sample order, may be NULL) is
+ * written by the groups' workers and valid after svo_wait.
+ * A slot out of range or named twice, a negative count, an unknown flag bit, NULL samples with a positive total:
+ * SVO_ERR_INVALID, nothing queued, the ctx stays usable. Device and pinned buffers are made by a group's first such
+ * job (counted in svo_ctx_get_memory) and grow when a job needs more. */
+int svo_submit_pose_updates(svo_ctx *ctx, const int *seqs, const int *counts, int n,
+                            const svo_pose_sample *samples, float *filtered);
+int svo_update_poses(svo_ctx *ctx, const int *seqs, const int *counts, int n,
+                     const svo_pose_sample *samples, float *filtered);   /* submit + wait */
+/* stage entry of the filter kernel: n_states filter states, every array in device memory, on the handle's stream.
+ * state_in: per state statePost[12] | errorCovPost[144] (156 floats); state b runs samples [first[b], first[b + 1])
+ * (first: n_states + 1 offsets, clamped to [0, n_samples)) in order, with A = I + dt, H = I, Q = 100 I of the
+ * tracker's filter and R = diag(pose_var, speed_var); start_pose [n_states][6]: what a chained first sample measures.
+ * state_out: per state statePre[12] | statePost[12] | errorCovPre[144] | errorCovPost[144] | gain[144] (456 floats)
+ * after its last sample; filtered [n_samples][6] (may be NULL). A state without samples is neither read nor written,
+ * and neither is anything outside the named ranges. samples: 8-byte aligned, the others 4-byte. */
+int svo_pose_filter_batch(svo_handle *h, int n_states, const float *state_in, const float *start_pose,
+                          const int *first, int n_samples, const svo_pose_sample *samples, float *state_out,
+                          float *filtered);
 
 /* ---- bulk export: the state of many slots in one ordered launch ------------
  * The reference reads its state one object at a time (get_frame / get_keyframes, src/lib/stereo_slam.cpp:273-289),

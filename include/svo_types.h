@@ -110,6 +110,18 @@ typedef struct svo_gn_trace {
     float   pose[6];        /* pose at the end of the level                  */
 } svo_gn_trace;
 
+/* One StereoSlam::update_pose call (src/lib/stereo_slam.cpp:296-359) as an element of svo_submit_pose_updates /
+ * svo_pose_filter_batch: the measured pose and speed, their variances (the diagonal of R) and the time step.
+ * 112 bytes. */
+enum { SVO_POSE_SAMPLE_CHAIN = 1u << 0 };   /* the measured pose is the filtered pose of the slot's previous sample
+                                               of the call (first sample: the slot's current pose); pose[] is ignored */
+typedef struct svo_pose_sample {
+    float    pose[6], speed[6], pose_var[6], speed_var[6];
+    double   dt;
+    uint32_t flags;           /* SVO_POSE_SAMPLE_CHAIN or 0; other bits: rejected */
+    uint32_t _pad;
+} svo_pose_sample;
+
 #define SVO_MAX_PYRAMID_LEVELS 8
 #define SVO_LK_LEVELS 3        /* maxLevel = 2, src/lib/optical_flow.cpp:42   */
 

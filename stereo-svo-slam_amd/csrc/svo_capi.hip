@@ -348,6 +348,21 @@ extern "C" int svo_copy_segments(svo_handle* h, int n, const svo_copy_segment* s
     return SVO_OK;
 }
 
+extern "C" int svo_pose_filter_batch(svo_handle* h, int n_states, const float* state_in, const float* start_pose,
+                                     const int* first, int n_samples, const svo_pose_sample* samples, float* state_out,
+                                     float* filtered) {
+    CHECK_H(h);
+    if (n_states < 0 || n_samples < 0 || (n_states > 0 && (!state_in || !start_pose || !first || !state_out)) ||
+        (n_samples > 0 && !samples))
+        return svo_set_error(SVO_ERR_INVALID, "svo_pose_filter_batch: bad arguments");
+    if (((uintptr_t)samples & 7) || (((uintptr_t)state_in | (uintptr_t)start_pose | (uintptr_t)first | (uintptr_t)state_out | (uintptr_t)filtered) & 3))
+        return svo_set_error(SVO_ERR_INVALID, "svo_pose_filter_batch: the samples are 8-byte aligned, every other array 4-byte aligned");
+    if (n_states == 0 || n_samples == 0) return SVO_OK;
+    launch_pose_filter(PoseFilterArgs{n_states, n_samples, state_in, start_pose, first, samples, state_out, filtered}, h->stream);
+    HIP_TRY(hipGetLastError());
+    return SVO_OK;
+}
+
 extern "C" int svo_build_lk_pyramid(svo_handle* h, int max_levels, int win, svo_image* levels,
                                     int* n_out) {
     CHECK_H(h);

@@ -29,8 +29,8 @@
 // single-workgroup-per-sequence alignment kernel of one group overlaps the window kernels of
 // the other. svo_submit_images() queues a frame set on every group and returns;
 // svo_wait() drains the queues. svo_new_images() = submit + wait. Restarts (svo_ctx_restart_sequences),
-// exports (svo_submit_export), saves and loads (svo_submit_save / svo_submit_load) are entries of the same queues,
-// so they are ordered with the frame sets.
+// exports (svo_submit_export), saves and loads (svo_submit_save / svo_submit_load) and pose-filter updates
+// (svo_submit_pose_updates) are entries of the same queues, so they are ordered with the frame sets.
 struct svo_ctx {
     // the group's share of an svo_submit_export: its named slots (indices in the group) in named order, the
     // segment each one fills, and the record of the caller's arrays the group packs from
@@ -47,8 +47,16 @@ struct svo_ctx {
         std::vector<svo_snapshot> snaps;
         std::vector<SnapshotLoad> loads;
     };
+    // the group's share of an svo_submit_pose_updates: its named slots with a positive count (indices in the group),
+    // their samples in that order, and where each slot's filtered poses go (the caller's memory, or null)
+    struct PoseUpdates {
+        std::vector<int> seqs, counts;
+        std::vector<svo_pose_sample> samples;
+        std::vector<float*> filtered;
+    };
     // one entry of a group's queue: a frame set, or (restart non-empty) the end of some of its sequences, or
-    // (exp.seqs non-empty) an export, or (snap.seqs / snap.loads non-empty) a save / a load
+    // (exp.seqs non-empty) an export, or (snap.seqs / snap.loads non-empty) a save / a load, or (pose.seqs non-empty)
+    // pose-filter updates
     struct Job {
         std::vector<const uint8_t*> left, right;
         std::vector<float> ts;
@@ -56,6 +64,7 @@ struct svo_ctx {
         std::vector<int> restart;        // indices in the group
         Export exp;
         Snapshots snap;
+        PoseUpdates pose;
     };
     struct Worker {
         Group g;
@@ -90,7 +99,10 @@ void worker_run_job(svo_ctx::Worker& w, const svo_ctx::Job& job) {
     if (w.err != SVO_OK || w.ctx_failed->load()) return;   // after a failure (any group) the queues are dropped
     const svo_ctx::Export& e = job.exp;
     const svo_ctx::Snapshots& sn = job.snap;
-    const int rc = !sn.loads.empty()
+    const svo_ctx::PoseUpdates& pu = job.pose;
+    const int rc = !pu.seqs.empty()
+                       ? grp_pose_updates(w.g.get(), pu.seqs.data(), pu.counts.data(), (int)pu.seqs.size(), pu.samples.data(), pu.filtered.data())
+                   : !sn.loads.empty()
                        ? grp_load(w.g.get(), sn.loads.data(), (int)sn.loads.size(), sn.mem)
                    : !sn.seqs.empty()
                        ? grp_save(w.g.get(), sn.seqs.data(), (int)sn.seqs.size(), sn.snaps.data(), sn.mem)
@@ -399,6 +411,50 @@ extern "C" int svo_submit_load(svo_ctx* c, const int* seqs, int n, const svo_sna
 
 extern "C" int svo_load_sequences(svo_ctx* c, const int* seqs, int n, const svo_snapshot* snaps, int mem) {
     const int rc = svo_submit_load(c, seqs, n, snaps, mem);
+    return rc ? rc : svo_wait(c);
+}
+
+extern "C" int svo_submit_pose_updates(svo_ctx* c, const int* seqs, const int* counts, int n, const svo_pose_sample* samples,
+                                       float* filtered) {
+    if (!c || !counts || (seqs && n < 0)) return svo_set_error(SVO_ERR_INVALID, "svo_submit_pose_updates: bad arguments");
+    if (!seqs) n = c->B;
+    std::vector<char> named(c->B, 0);
+    std::vector<int64_t> first((size_t)n + 1, 0);     // sample offsets of the named slots
+    for (int i = 0; i < n; i++) {
+        const int s = seqs ? seqs[i] : i;
+        if (s < 0 || s >= c->B || named[s])
+            return svo_set_error(SVO_ERR_INVALID, "svo_submit_pose_updates: sequence %d is out of range or named twice", s);
+        named[s] = 1;
+        if (counts[i] < 0) return svo_set_error(SVO_ERR_INVALID, "svo_submit_pose_updates: sequence %d: negative count", s);
+        first[i + 1] = first[i] + counts[i];
+    }
+    const int64_t total = first[n];
+    if (total > (1 << 24)) return svo_set_error(SVO_ERR_INVALID, "svo_submit_pose_updates: %lld samples in one call", (long long)total);
+    if (total > 0 && !samples) return svo_set_error(SVO_ERR_INVALID, "svo_submit_pose_updates: no samples");
+    for (int64_t k = 0; k < total; k++)
+        if (samples[k].flags & ~(uint32_t)SVO_POSE_SAMPLE_CHAIN)
+            return svo_set_error(SVO_ERR_INVALID, "svo_submit_pose_updates: sample %lld: unknown flag bits 0x%x", (long long)k, samples[k].flags);
+    if (c->failed.load()) return reject_failed(c, "svo_submit_pose_updates");
+    for (auto& wp : c->workers) {
+        svo_ctx::Worker& w = *wp;
+        svo_ctx::Job job;
+        svo_ctx::PoseUpdates& u = job.pose;
+        for (int i = 0; i < n; i++) {
+            const int s = seqs ? seqs[i] : i;
+            if (counts[i] == 0 || s < w.first || s >= w.first + w.count) continue;
+            u.seqs.push_back(s - w.first);
+            u.counts.push_back(counts[i]);
+            u.samples.insert(u.samples.end(), samples + first[i], samples + first[i + 1]);
+            u.filtered.push_back(filtered ? filtered + first[i] * 6 : nullptr);
+        }
+        if (!u.seqs.empty()) worker_submit(w, std::move(job));
+    }
+    return SVO_OK;
+}
+
+extern "C" int svo_update_poses(svo_ctx* c, const int* seqs, const int* counts, int n, const svo_pose_sample* samples,
+                                float* filtered) {
+    const int rc = svo_submit_pose_updates(c, seqs, counts, n, samples, filtered);
     return rc ? rc : svo_wait(c);
 }
 

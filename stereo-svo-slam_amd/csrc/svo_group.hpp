@@ -1,6 +1,7 @@
 // svo_group.hpp — one group of sequences as svo_ctx.hip drives it: the opaque interface of svo_group.hip (creation,
-// settings, restarts), svo_group_step.hip (grp_new_images), svo_group_export.hip (grp_export, grp_capacity) and
-// svo_group_snapshot.hip (grp_check_snapshot, grp_save, grp_load, grp_snapshot_size).
+// settings, restarts), svo_group_step.hip (grp_new_images), svo_group_export.hip (grp_export, grp_capacity),
+// svo_group_snapshot.hip (grp_check_snapshot, grp_save, grp_load, grp_snapshot_size) and svo_group_pose.hip
+// (grp_pose_updates).
 #pragma once
 
 #include <cstdint>
@@ -41,6 +42,11 @@ int grp_check_snapshot(const svo_group* g, const svo_snapshot* snap, std::vector
 int grp_save(svo_group* g, const int* seqs, int n, const svo_snapshot* snaps, int mem);
 int grp_load(svo_group* g, const SnapshotLoad* loads, int n, int mem);
 int grp_snapshot_size(svo_group* g, int seq, int64_t* host_bytes, int64_t* data_bytes);   // (the queues have drained)
+// One group's share of svo_submit_pose_updates (svo_group_pose.hip), between two steps of the group, on the thread
+// that drives it: counts[i] > 0 samples for slot seqs[i] (index in the group), `samples` in that order; filtered[i]:
+// host memory for the slot's counts[i] filtered poses, or null. Delivered on return. A failed group rejects it.
+int grp_pose_updates(svo_group* g, const int* seqs, const int* counts, int n, const svo_pose_sample* samples,
+                     float* const* filtered);
 int grp_capacity(const svo_group* g);                 // keypoint records a sequence can hold (svo_export_capacity)
 void grp_drop_finished_runs(svo_group* g, int seq);   // seq < 0: of every sequence of the group
 svo_memory grp_memory(const svo_group* g);

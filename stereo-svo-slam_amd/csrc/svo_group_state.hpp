@@ -1,6 +1,7 @@
 // svo_group_state.hpp — the state of one sequence group, internal to the group: only its translation units
 // (svo_group.hip: storage, creation, settings, the end of a sequence; svo_group_step.hip: the step;
-// svo_group_export.hip: the bulk export; svo_group_snapshot.hip: save and load) and the per-sequence getters of
+// svo_group_export.hip: the bulk export; svo_group_snapshot.hip: save and load; svo_group_pose.hip: the batched
+// pose-filter updates) and the per-sequence getters of
 // svo_ctx.hip include it. Everyone else drives a group through the opaque interface of svo_group.hpp.
 //
 // Host side = bookkeeping only: image-set pool, argument blocks, the 12-state
@@ -275,6 +276,11 @@ struct svo_group {
     // snapshots (grp_save / grp_load) in host mode: the data parts of one call, made by the first such call and
     // replaced when outgrown
     uint8_t* d_snap = nullptr; size_t snap_bytes = 0;
+    // batched pose-filter updates (grp_pose_updates): the upload block (samples | filter states | start poses |
+    // sample offsets) and behind it the download block (filter states | filtered poses) of one job, device and pinned,
+    // made by the first such job and replaced when outgrown
+    uint8_t* d_pose = nullptr; size_t pose_up_bytes = 0, pose_down_bytes = 0;
+    svo::PinnedPtr<uint8_t> pose_host;
     bool timing = false;
     bool failed = false;
     int exact_pinv = 1;          // reference-order Gauss-Newton unless svo_ctx_set_fast_solver(ctx, 1)

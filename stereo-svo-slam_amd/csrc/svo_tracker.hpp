@@ -137,4 +137,24 @@ void cut_copy_tiles(const void* src, void* dst, int64_t row_bytes, int64_t rows,
                     std::vector<CopyTile>& out);
 void launch_copy_tiles(const CopyTile* d_tiles, int n_tiles, hipStream_t stream);
 
+// ------------------------------------------------------------ batched pose filter (pose_filter.hip)
+// n_states filter states, one lane each, POSE_FILTER_LANES per workgroup. State b runs samples
+// [first[b], first[b + 1]) (clamped to [0, n_samples)) in order; a state without samples is neither read nor written.
+// All pointers: device memory. state_in: statePost[12] | errorCovPost[144] per state; state_out: statePre[12] |
+// statePost[12] | errorCovPre[144] | errorCovPost[144] | gain[144] per state (after the state's last sample);
+// start_pose: [n_states][6], what a chained first sample measures; filtered: [n_samples][6] or null.
+constexpr int POSE_FILTER_LANES = 64;
+constexpr int POSE_FILTER_IN_FLOATS = 12 + 144;
+constexpr int POSE_FILTER_OUT_FLOATS = 2 * 12 + 3 * 144;
+struct PoseFilterArgs {
+    int n_states, n_samples;
+    const float* state_in;
+    const float* start_pose;
+    const int* first;             // [n_states + 1]
+    const svo_pose_sample* samples;
+    float* state_out;
+    float* filtered;
+};
+void launch_pose_filter(const PoseFilterArgs& a, hipStream_t stream);
+
 }  // namespace svo

@@ -38,6 +38,7 @@ SYMBOLS = (
     "svo_snapshot_size", "svo_submit_save", "svo_save_sequences", "svo_submit_load", "svo_load_sequences",
     "svo_snapshot_info", "svo_copy_segments",
     "svo_reproj_gn_batch", "svo_filter_update_batch",
+    "svo_submit_pose_updates", "svo_update_poses", "svo_pose_filter_batch",
 )
 
 # svo_ctx_set_input_format / svo_convert_frames: how the buffers of a sequence become its two gray images
@@ -143,6 +144,16 @@ class CopySegment(C.Structure):
                 ("src_pitch", C.c_int64), ("dst_pitch", C.c_int64)]
 
 
+# svo_pose_sample (include/svo_types.h): one StereoSlam::update_pose call of svo_submit_pose_updates
+POSE_SAMPLE_DTYPE = np.dtype([("pose", "<f4", (6,)), ("speed", "<f4", (6,)), ("pose_var", "<f4", (6,)),
+                              ("speed_var", "<f4", (6,)), ("dt", "<f8"), ("flags", "<u4"), ("_pad", "<u4")])
+assert POSE_SAMPLE_DTYPE.itemsize == 112
+POSE_SAMPLE_CHAIN = 1
+# svo_pose_filter_batch: floats of a filter state going in (statePost | errorCovPost) and coming out
+# (statePre | statePost | errorCovPre | errorCovPost | gain)
+POSE_FILTER_IN_FLOATS, POSE_FILTER_OUT_FLOATS = 156, 456
+
+
 def lib():
     """Load libsvo_hip.so; fail loudly when it has not been built."""
     global _LIB
@@ -153,6 +164,10 @@ def lib():
                 "g.build()'` (hipcc --offload-arch=gfx950). There is no CPU fallback.")
         _LIB = C.CDLL(LIB_PATH)
         _LIB.svo_last_error.restype = C.c_char_p
+        for name in ("svo_submit_pose_updates", "svo_update_poses"):
+            getattr(_LIB, name).argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        _LIB.svo_pose_filter_batch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                               C.c_void_p, C.c_void_p, C.c_void_p]
     return _LIB
 
 
@@ -336,6 +351,23 @@ class Handle:
         rows, src_pitch, dst_pitch) each. Complete on return."""
         arr = (CopySegment * max(len(segs), 1))(*[CopySegment(*[int(x) for x in g]) for g in segs])
         _check(lib().svo_copy_segments(self._h, len(segs), arr))
+
+    # -- pose filter --------------------------------------------------------
+    def pose_filter_batch(self, state_in, start_pose, first, samples, state_out, filtered=None):
+        """svo_pose_filter_batch: the 12-state pose filter of len(state_in) states in one launch. Device tensors:
+        state_in float32 [B, 156] (statePost | errorCovPost), start_pose float32 [B, 6], first int32 [B + 1]
+        (sample offsets), samples uint8 [total, 112] (POSE_SAMPLE_DTYPE records), state_out float32 [B, 456]
+        (statePre | statePost | errorCovPre | errorCovPost | gain; written for states with samples only), filtered
+        float32 [total, 6] or None."""
+        b, total = state_in.shape[0], samples.shape[0]
+        assert state_in.shape == (b, POSE_FILTER_IN_FLOATS) and state_out.shape == (b, POSE_FILTER_OUT_FLOATS)
+        assert start_pose.shape == (b, 6) and first.shape == (b + 1,) and first.dtype == torch.int32
+        assert samples.dtype == torch.uint8 and samples.shape == (total, POSE_SAMPLE_DTYPE.itemsize)
+        assert filtered is None or filtered.shape == (total, 6)
+        for t in (state_in, start_pose, state_out, filtered):
+            assert t is None or t.dtype == torch.float32
+        _check(lib().svo_pose_filter_batch(self._h, b, _ptr(state_in), _ptr(start_pose), _ptr(first), total,
+                                           _ptr(samples), _ptr(state_out), _ptr(filtered)))
 
     # -- P2 ---------------------------------------------------------------
     def build_lk_pyramid(self, img, win, max_levels=3):

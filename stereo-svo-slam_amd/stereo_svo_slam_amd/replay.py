@@ -320,11 +320,15 @@ def error_report(test_rows, reference_rows):
 class Replay:
     """process_image loop: only the time inside new_image is accumulated (slam_app.cpp:186-190)."""
 
-    def __init__(self, settings, device=0, time_trace=False, fast=False, rectify_maps=None, input_format=None):
+    def __init__(self, settings, device=0, time_trace=False, fast=False, rectify_maps=None, input_format=None,
+                 gpu_imu=False):
         """fast=False keeps the library default: the reference-order Gauss-Newton (bit-exact traces).
         rectify_maps = (left maps, right maps): the frames fed are raw and are rectified on the GPU.
-        input_format: the frames fed are raw buffers of that format (StereoSlam.set_input_format)."""
+        input_format: the frames fed are raw buffers of that format (StereoSlam.set_input_format).
+        gpu_imu: update_pose_from_imu is one svo_update_poses (the filter kernel) instead of a loop of
+        svo_update_pose calls: the same bits."""
         self.settings = settings
+        self.gpu_imu = gpu_imu
         self.slam = StereoSlam(settings, device=device)
         if fast:
             self.slam.set_fast_solver(True)
@@ -348,6 +352,9 @@ class Replay:
         act through the filter's state)."""
         if self.slam._ctx is None:                # (the ctx is created by the first frame)
             return None
+        if self.gpu_imu:
+            out = self.slam.update_poses_from_gyro([gyro_deg_s], dt)
+            return out[-1] if len(out) else np.asarray(self.slam.pose(), np.float32)
         gyro = np.asarray(gyro_deg_s, np.float32).reshape(-1, 3)
         pose_variance = np.full(6, 1000.0, np.float32)
         speed_variance = np.array([100.0, 100.0, 100.0, 0.1, 0.1, 0.1], np.float32)
@@ -399,6 +406,10 @@ def main(argv=None):
     ap.add_argument("--interleaved", help="'frames/%%06d.png' 3-channel frames: EconInput conventions (right = channel 1, left = channel 2)")
     ap.add_argument("--gpu-ingest", action="store_true",
                     help="--sbs / --interleaved: hand the raw frames to the library, which converts and splits them on the GPU")
+    ap.add_argument("--gyro", help="text file, one row 'frame gx gy gz' per IMU sample (degrees per second), rows in time "
+                                   "order: the samples of frame k feed the pose filter before frame k (update_pose_from_imu)")
+    ap.add_argument("--gpu-imu", action="store_true",
+                    help="--gyro: one svo_update_poses per frame interval (the filter kernel) instead of one svo_update_pose per sample")
     ap.add_argument("--frames", type=int, default=100)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--rate", type=float, default=20.0, help="frames per second of the time stamps")
@@ -445,9 +456,12 @@ def main(argv=None):
         ap.error("--gpu-rectify needs --euroc with --settings")
     if args.gpu_ingest and fmt is None:
         ap.error("--gpu-ingest needs --sbs or --interleaved with --settings")
-    rp = Replay(settings, args.device, args.time_trace, args.fast, rectify_maps=rect, input_format=fmt)
-    for left, right, t in frames:
-        rp.feed(left, right, t)
+    if args.gpu_imu and not args.gyro:
+        ap.error("--gpu-imu needs --gyro")
+    gyro = np.loadtxt(args.gyro, ndmin=2) if args.gyro else None
+    rp = Replay(settings, args.device, args.time_trace, args.fast, rectify_maps=rect, input_format=fmt, gpu_imu=args.gpu_imu)
+    for k, (left, right, t) in enumerate(frames):
+        rp.feed(left, right, t, None if gyro is None else gyro[gyro[:, 0] == k, 1:4])
     rows = rp.rows()
     print(f"frames {rows.shape[0]}  Average FPS: {fps_from_csv_rows(rows):.2f}  "
           f"keyframes {rp.slam.num_keyframes()}")

@@ -13,7 +13,7 @@ import numpy as np
 import torch
 
 from . import hip_lib
-from .hip_lib import CameraSettings, SvoError, _check, lib
+from .hip_lib import POSE_SAMPLE_CHAIN, POSE_SAMPLE_DTYPE, CameraSettings, SvoError, _check, lib
 
 KP_INFO_DTYPE = np.dtype([
     ("score", "<f4"), ("level", "<i4"), ("type", "<i4"), ("keyframe_id", "<i4"),
@@ -569,6 +569,60 @@ class StereoSlamBatch:
         arrs = [np.ascontiguousarray(a, np.float32) for a in (pose, speed, pose_variance, speed_variance)]
         _check(lib().svo_update_pose(self._ctx, seq, *[a.ctypes.data_as(C.c_void_p) for a in arrs],
                                      C.c_double(dt), out.ctypes.data_as(C.c_void_p)))
+        return out
+
+
+    # -- batched pose-filter updates ----------------------------------------
+    IMU_RATE = 104.0                              # samples per second of the Econ camera's IMU thread (slam_app.cpp:127)
+
+    def submit_pose_updates(self, seqs, samples_per_seq):
+        """svo_submit_pose_updates: queue the pose-filter updates of the slots `seqs` (None: all, in order) behind
+        what was submitted so far; nothing is waited for. samples_per_seq[i]: the POSE_SAMPLE_DTYPE records of slot
+        seqs[i] in the order they are applied (an empty array or None: the slot is left alone). Returns the filtered
+        poses, float32 [total, 6] in sample order, valid after wait()."""
+        seqs = None if seqs is None else [int(s) for s in seqs]
+        n = self.n if seqs is None else len(seqs)
+        assert len(samples_per_seq) == n
+        per = [np.zeros(0, POSE_SAMPLE_DTYPE) if a is None else np.ascontiguousarray(a, POSE_SAMPLE_DTYPE).reshape(-1)
+               for a in samples_per_seq]
+        counts = (C.c_int * max(n, 1))(*[len(a) for a in per])
+        samples = np.concatenate(per) if per else np.zeros(0, POSE_SAMPLE_DTYPE)
+        filtered = np.zeros((len(samples), 6), np.float32)
+        seq_arr = None if seqs is None else (C.c_int * max(n, 1))(*seqs)
+        _check(lib().svo_submit_pose_updates(self._ctx, seq_arr, counts, n, samples.ctypes.data if len(samples) else None,
+                                             filtered.ctypes.data if len(samples) else None))
+        return filtered                            # (the worker writes into it: the caller keeps it until wait())
+
+    def update_poses(self, seqs, samples_per_seq):
+        """submit_pose_updates + wait: the filtered poses [total, 6]"""
+        out = self.submit_pose_updates(seqs, samples_per_seq)
+        self.wait()
+        return out
+
+    @classmethod
+    def gyro_samples(cls, gyro_deg_s, dt):
+        """SlamApp::update_pose_from_imu (slam_app.cpp:111-135) of one frame interval as chained samples: at most
+        IMU_RATE * dt of the gyro rates ([n, 3] degrees per second, x y z) as the speed measurement with the app's
+        variances, each one update of 1 / IMU_RATE (the double)"""
+        gyro = np.asarray(gyro_deg_s, np.float32).reshape(-1, 3)
+        n = min(len(gyro), int(np.float32(cls.IMU_RATE) * np.float32(dt)))     # std::min<size_t>(size, f * dt): truncated
+        out = np.zeros(n, POSE_SAMPLE_DTYPE)
+        out["speed"][:, 3:] = (gyro[:n].astype(np.float64) / 180.0 * np.pi).astype(np.float32)
+        out["pose_var"] = 1000.0
+        out["speed_var"] = np.array([100.0, 100.0, 100.0, 0.1, 0.1, 0.1], np.float32)
+        out["dt"] = 1.0 / cls.IMU_RATE
+        out["flags"] = POSE_SAMPLE_CHAIN
+        return out
+
+    def submit_poses_from_gyro(self, gyro_per_seq, dt, seqs=None):
+        """gyro_samples of every named slot (gyro_per_seq[i]: [n_i, 3] or None) as one submit_pose_updates"""
+        return self.submit_pose_updates(seqs, [None if g is None else self.gyro_samples(g, dt) for g in gyro_per_seq])
+
+    def update_poses_from_gyro(self, gyro_per_seq, dt, seqs=None):
+        """the app's IMU loop between two frames for many slots in one call, without a round trip per sample:
+        submit_poses_from_gyro + wait. Returns the filtered poses [total, 6]."""
+        out = self.submit_poses_from_gyro(gyro_per_seq, dt, seqs)
+        self.wait()
         return out
 
 
