@@ -126,7 +126,10 @@ int svo_convert_frames(svo_handle *h, int format, int n, const svo_image *src_a,
  * prev_pyr/cur_pyr: cam->max_pyramid_levels halfSample levels (host array of
  * views onto device memory). pose_guess/pose_out/cost/trace: device memory;
  * trace = [SVO_MAX_PYRAMID_LEVELS] svo_gn_trace or NULL.
- * dbg (optional, device, 48 floats): H, b, step of the first get_gradient on dbg_level. */
+ * dbg (optional, device, 48 floats): H, b, step of the first get_gradient on dbg_level.
+ * One departure from the reference: a keypoint whose Jacobian has an entry that is not finite (a point in the
+ * camera plane of the pose) takes no part in H and b. The reference does the same while none of its patch pixels
+ * passes the gradient bounds, and otherwise returns NaN. */
 int svo_sparse_align(svo_handle *h, const svo_image *prev_pyr, const svo_image *cur_pyr,
                      const svo_kp2d *kps2d, const svo_kp3d *kps3d, const uint32_t *flags, int n,
                      const svo_camera_settings *cam, const float *pose_guess, float *pose_out,
@@ -623,6 +626,19 @@ int svo_reproj_gn_batch(svo_handle *h, int batch, int stride, const int32_t *n_d
                         const svo_kp3d *kps3d, uint32_t *flags, const svo_camera_settings *cam,
                         const svo_kp2d *tracked, const float *err, const float *pose_in, float *pose_out,
                         float *cost, svo_gn_trace *trace, int32_t *zero_out, int *waves, int *cap);
+/* Diagnostic: the sparse image alignment (svo_sparse_align) of `batch` sequences in one launch, the way the tracker
+ * launches it. The keypoint arrays are laid out as above (n_dev[batch] device, each 0..n_bound, n_bound <= stride);
+ * prev_pyr / cur_pyr: HOST arrays [batch][cam->max_pyramid_levels] of views onto device memory, every sequence its
+ * own images, all of one width x height per level; pose_guess / pose_out [batch][6], cost [batch] or NULL, trace
+ * [batch][SVO_MAX_PYRAMID_LEVELS] or NULL, dbg [batch][48] or NULL (H, b, step of the first get_gradient on
+ * dbg_level). For the call every sequence gets record and per-keypoint workspaces of its own, and ws_fill is written
+ * over all of them before the launch: what the kernel reads of a workspace slot that it did not write is this
+ * pattern. *waves, *mode and *cap receive the shape the launch chose for (batch, n_bound). Complete on return. */
+int svo_sparse_align_batch(svo_handle *h, int batch, int stride, const int32_t *n_dev, int n_bound,
+                           const svo_kp2d *kps2d, const svo_kp3d *kps3d, const uint32_t *flags,
+                           const svo_image *prev_pyr, const svo_image *cur_pyr, const svo_camera_settings *cam,
+                           const float *pose_guess, int dbg_level, uint32_t ws_fill, float *pose_out, float *cost,
+                           svo_gn_trace *trace, float *dbg, int *waves, int *mode, int *cap);
 /* Diagnostic: the depth filter update (svo_depth_filter_update) of `batch` sequences in one launch, with explicit
  * references, laid out as above (kf_pose [batch * stride][6], frame_pose [batch][6]). do_flags: the counter
  * rules of StereoSlam::new_image (src/lib/stereo_slam.cpp:212-216) are applied to `flags`; do_reproject: kps2d

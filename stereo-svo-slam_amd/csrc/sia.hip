@@ -496,6 +496,18 @@ struct Sia {
                     SIA_WAIT_CHAIN(14);
                     mat33f_vec(pm.Ri, X, X);
                     pose_jacobian(fx, fy, X[0], X[1], X[2], J);
+                    // A point in the camera plane (z == 0, or z * z underflows) has an infinite Jacobian. Where none of
+                    // its patch pixels passes the gradient bounds the reference still has exact zero rows (:351-356),
+                    // and the zero gradient records here would turn into 0 * inf: a keypoint with an entry of J that is
+                    // not finite takes no part in H and b. (This departs from the reference where such a keypoint has
+                    // a patch pixel inside: there the reference's H is NaN, and this kernel's stays finite.)
+                    bool finite = true;
+#pragma unroll
+                    for (int q = 0; q < 12; q++) finite = finite && fabsf(J[q]) <= 3.4028235e38f;
+                    if (!finite) {
+#pragma unroll
+                        for (int q = 0; q < 12; q++) J[q] = 0;
+                    }
                 }
             };
             if constexpr (!QREG) jacobian();        // (QREG: below, once the image taps have been asked for)

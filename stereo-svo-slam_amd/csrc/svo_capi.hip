@@ -745,6 +745,87 @@ extern "C" int svo_reproj_gn_batch(svo_handle* h, int batch, int stride, const i
     return SVO_OK;
 }
 
+// svo_sparse_align_batch: launch_sia with a batch of sequences, the way the tracker calls it, on caller-made
+// arrays. Every sequence gets record and per-keypoint workspaces of its own for the call ([levels used][68][rec_cap]
+// and [9][rec_cap] floats, rec_cap the multiple of 256 that covers the launch's cap), filled with ws_fill first: what
+// a kernel reads of a slot that nothing wrote is the caller's pattern.
+extern "C" int svo_sparse_align_batch(svo_handle* h, int batch, int stride, const int32_t* n_dev, int n_bound,
+                                      const svo_kp2d* kps2d, const svo_kp3d* kps3d, const uint32_t* flags,
+                                      const svo_image* prev_pyr, const svo_image* cur_pyr,
+                                      const svo_camera_settings* cam, const float* pose_guess, int dbg_level,
+                                      uint32_t ws_fill, float* pose_out, float* cost, svo_gn_trace* trace, float* dbg,
+                                      int* waves, int* mode, int* cap) {
+    CHECK_H(h);
+    if (!cam || !prev_pyr || !cur_pyr || !pose_guess || !pose_out || (n_bound > 0 && (!kps2d || !kps3d)))
+        return svo_set_error(SVO_ERR_INVALID, "svo_sparse_align_batch: bad arguments");
+    if (cam->max_pyramid_levels < 1 || cam->max_pyramid_levels > 7 || cam->min_pyramid_level_pose_estimation < 0 ||
+        cam->min_pyramid_level_pose_estimation >= cam->max_pyramid_levels)
+        return svo_set_error(SVO_ERR_INVALID, "svo_sparse_align_batch: max_pyramid_levels must be 1..7, min below it");
+    if (cam->window_size_pose_estimator != 4)
+        return svo_set_error(SVO_ERR_INVALID, "svo_sparse_align_batch: window_size_pose_estimator must be 4");
+    int rc = check_batch_counts("svo_sparse_align_batch", batch, stride, n_dev, n_bound);
+    if (rc) return rc;
+    const int levels = cam->max_pyramid_levels;
+    const int width = cur_pyr[0].width, height = cur_pyr[0].height;      // (level 0 gives the size even where it is not used)
+    if (width < 1 || height < 1) return svo_set_error(SVO_ERR_INVALID, "svo_sparse_align_batch: cur_pyr[0] has no size");
+    for (int b = 0; b < batch; b++)
+        for (int l = cam->min_pyramid_level_pose_estimation; l < levels; l++) {
+            const svo_image& p = prev_pyr[(size_t)b * levels + l];
+            const svo_image& c = cur_pyr[(size_t)b * levels + l];
+            if (!p.data || !c.data || p.width != (width >> l) || c.width != (width >> l) || p.height != (height >> l) ||
+                c.height != (height >> l) || p.stride < p.width || c.stride < c.width)
+                return svo_set_error(SVO_ERR_INVALID, "svo_sparse_align_batch: sequence %d level %d: every sequence needs "
+                                     "images of one size, %d x %d at level 0", b, l, width, height);
+        }
+    const LaunchShape want = sia_pick_shape(batch, *cam, width, height, n_bound, INT_MAX, h->exact_pinv);
+    if (waves) *waves = want.waves;
+    if (mode) *mode = want.mode;
+    if (cap) *cap = want.cap;
+    if (!want.fits || want.cap > INT_MAX - 255)
+        return svo_set_error(SVO_ERR_CAPACITY, "svo_sparse_align_batch: %d keypoints exceed the kernel's LDS", n_bound);
+    const int rec_cap = (want.cap + 255) / 256 * 256;
+    const size_t rec_floats = sia_rec_ws_floats(*cam, rec_cap), kp_floats = (size_t)9 * rec_cap;
+    DevPtr<float> ws;
+    HIP_TRY(dev_malloc(ws, sizeof(float) * (rec_floats + kp_floats) * (size_t)batch));
+    HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(ws.get()), (int)ws_fill,
+                              (rec_floats + kp_floats) * (size_t)batch, h->stream));
+    std::vector<SiaArgs> blocks((size_t)batch);
+    for (int b = 0; b < batch; b++) {
+        SiaArgs& sa = blocks[(size_t)b];
+        const size_t o = (size_t)b * (size_t)stride;
+        memset(&sa, 0, sizeof(sa));
+        for (int l = cam->min_pyramid_level_pose_estimation; l < levels; l++) {      // (the levels checked above: the others are not read)
+            sa.prev[l] = make_view(prev_pyr[(size_t)b * levels + l]);
+            sa.cur[l] = make_view(cur_pyr[(size_t)b * levels + l]);
+        }
+        sa.cam = *cam;
+        sa.n_ptr = n_dev + b;
+        sa.kps2d = kps2d ? kps2d + o : nullptr; sa.kps3d = kps3d ? kps3d + o : nullptr;
+        sa.flags = flags ? flags + o : nullptr;
+        sa.pose_guess = pose_guess + 6 * (size_t)b; sa.pose_out = pose_out + 6 * (size_t)b;
+        sa.cost_out = cost ? cost + b : nullptr;
+        sa.trace = trace ? trace + (size_t)b * SVO_MAX_PYRAMID_LEVELS : nullptr;
+        sa.rec_ws = ws.get() + (size_t)b * (rec_floats + kp_floats);
+        sa.kp_ws = sa.rec_ws + rec_floats;
+        sa.rec_cap = rec_cap;
+        sa.dbg_H = dbg ? dbg + 48 * (size_t)b : nullptr; sa.dbg_level = dbg_level;
+        sa.cap = stride;
+        sa.exact_pinv = h->exact_pinv;
+    }
+    SiaArgs* d;
+    rc = stage_blocks(h, blocks, &d);
+    if (rc) return rc;
+    const LaunchStatus st = launch_sia(d, batch, *cam, width, height, n_bound, rec_cap, h->exact_pinv, h->stream);
+    HIP_TRY(st.err);
+    if (!st.shape.fits) {
+        (void)hipStreamSynchronize(h->stream);
+        return svo_set_error(SVO_ERR_CAPACITY, "svo_sparse_align_batch: %d keypoints exceed the kernel's LDS or registers", n_bound);
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return SVO_OK;            // (ws is freed here: the launch is complete)
+}
+
 extern "C" int svo_filter_update_batch(svo_handle* h, int batch, int stride, const int32_t* n_dev, int n_bound, svo_kp2d* kps2d,
                                        svo_kp3d* kps3d, uint32_t* flags, const svo_camera_settings* cam,
                                        const float* frame_pose, const float* disparity, const svo_kp3d* ref3d,

@@ -37,7 +37,7 @@ SYMBOLS = (
     "svo_export_capacity", "svo_submit_export", "svo_export", "svo_pack_keypoints",
     "svo_snapshot_size", "svo_submit_save", "svo_save_sequences", "svo_submit_load", "svo_load_sequences",
     "svo_snapshot_info", "svo_copy_segments",
-    "svo_reproj_gn_batch", "svo_filter_update_batch",
+    "svo_reproj_gn_batch", "svo_filter_update_batch", "svo_sparse_align_batch",
     "svo_submit_pose_updates", "svo_update_poses", "svo_pose_filter_batch",
 )
 
@@ -397,6 +397,33 @@ class Handle:
             n, C.byref(cam), _ptr(pose_guess), _ptr(pose_out), _ptr(cost), _ptr(trace), _ptr(dbg),
             dbg_level))
         return pose_out, cost, trace, dbg
+
+    def sparse_align_batch(self, n, n_bound, kps2d, kps3d, flags, prev_pyrs, cur_pyrs, cam, pose_guess, dbg_level=-1,
+                           ws_fill=0, outputs=None):
+        """Diagnostic: svo_sparse_align of len(n) sequences in one launch. n: int32 [batch] device; the keypoint
+        arrays are [batch, stride, ..] device tensors; prev_pyrs / cur_pyrs: per sequence the list of its level
+        images (uint8 device tensors or views with unit column stride); pose_guess [batch, 6]. outputs: (pose_out
+        [batch, 6], cost [batch], trace [batch, 8 * 52] bytes, dbg [batch, 48] or None) to write into, made here if
+        None. Returns (pose_out, cost, trace, dbg, (waves, mode, cap))."""
+        batch, stride = kps2d.shape[0], kps2d.shape[1]
+        dev = kps2d.device
+        levels = cam.max_pyramid_levels
+        if outputs is None:
+            outputs = (torch.zeros((batch, 6), dtype=torch.float32, device=dev),
+                       torch.zeros(batch, dtype=torch.float32, device=dev),
+                       torch.zeros((batch, 8 * GN_TRACE_DTYPE.itemsize), dtype=torch.uint8, device=dev),
+                       torch.zeros((batch, 48), dtype=torch.float32, device=dev) if dbg_level >= 0 else None)
+        pose_out, cost, trace, dbg = outputs
+        pp, cp = (Image * (batch * levels))(), (Image * (batch * levels))()
+        for b in range(batch):
+            for l in range(levels):
+                pp[b * levels + l], cp[b * levels + l] = _img(prev_pyrs[b][l]), _img(cur_pyrs[b][l])
+        waves, mode, cap = C.c_int(0), C.c_int(0), C.c_int(0)
+        _check(lib().svo_sparse_align_batch(self._h, batch, stride, _ptr(n), int(n_bound), _ptr(kps2d), _ptr(kps3d),
+                                            _ptr(flags), pp, cp, C.byref(cam), _ptr(pose_guess), int(dbg_level),
+                                            C.c_uint32(ws_fill), _ptr(pose_out), _ptr(cost), _ptr(trace), _ptr(dbg),
+                                            C.byref(waves), C.byref(mode), C.byref(cap)))
+        return pose_out, cost, trace, dbg, (waves.value, mode.value, cap.value)
 
     # -- A3 ---------------------------------------------------------------
     def project_keypoints(self, pose, kps3d, cam):
