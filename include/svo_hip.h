@@ -418,6 +418,113 @@ int svo_export(svo_ctx *ctx, int what, const int *seqs, int n, const svo_export_
 int svo_pack_keypoints(svo_handle *h, int n_sets, const svo_keypoints *sets, const int64_t *first,
                        svo_kp2d *kps2d, svo_kp3d *kps3d, svo_kp_info *info);
 
+/* ---- map export: every keyframe of many slots as one compacted point cloud ------------
+ * The reference's viewer protocol (`keyframes` / `get`, src/app/svo_slam_backend.cpp:18-110) sends EVERY keyframe of
+ * the tracker: pose, kps3d and colours. svo_get_keyframe per id restates that with twelve blocking copies per
+ * keyframe; svo_submit_export covers the newest keyframe only. A map export is the batched form for the whole map:
+ * the groups that own a named slot write the keypoints of the slot's keyframes that pass a filter as 16-byte points,
+ * densely, with map.hip's two kernels, and the host writes one svo_map_segment per named slot and one
+ * svo_map_keyframe per exported keyframe.
+ *
+ * Filter: a keyframe copies the surviving points of earlier keyframes (merge_keypoints,
+ * src/lib/depth_calculator.cpp:88-130), which keep their origin keyframe_id, while the depth filter writes refined
+ * kps3d and flags back to the ORIGIN keyframe only (src/lib/stereo_slam.cpp:205-226): the copies in later keyframes
+ * go stale. own_only keeps a point only in its origin keyframe, drop_flags / min_inliers select by quality. Only the
+ * device holds these planes, so the compaction runs there.
+ *
+ * Order: a slot's kept points lie densely from region.first_point on: keyframes in ascending id, inside a keyframe
+ * in ascending keypoint index. Stable: two runs give the same bytes.
+ *
+ * Polling: keyframes below svo_map_segment.keyframes_retired are no longer tracked, no write-back reaches them and
+ * their points are final. A poller can pass from_keyframe = keyframes_retired of its last poll and keep what it has
+ * of the keyframes below. */
+typedef struct svo_map_point {      /* 16 bytes */
+    float   x, y, z;                /* kps3d, bits unchanged (world frame)                                  */
+    uint8_t color[3];               /* r, g, b                                                              */
+    uint8_t flags;                  /* SVO_IGNORE_* bits of the keypoint (other bits of its flags word: not kept) */
+} svo_map_point;
+
+typedef struct svo_map_filter {     /* all zero (or a NULL filter): every keypoint of every keyframe        */
+    uint32_t drop_flags;            /* dropped if (flags & drop_flags) != 0; SVO_IGNORE_* bits only         */
+    int32_t  own_only;              /* != 0: dropped if keyframe_id != id of the keyframe that holds it     */
+    int32_t  min_inliers;           /* dropped if inlier_count < min_inliers (signed)                       */
+    int32_t  _reserved;             /* 0, else SVO_ERR_INVALID                                              */
+} svo_map_filter;
+
+typedef struct svo_map_keyframe {   /* 48 bytes, host, one per exported keyframe                            */
+    int32_t id, n_total, n, _pad;   /* its keypoints / those kept                                           */
+    int64_t first;                  /* kept points are records [first, first + n) of `points`               */
+    float   pose[6];
+} svo_map_keyframe;
+
+enum { SVO_MAP_COMPLETE = 0,
+       SVO_MAP_TOO_SMALL = 1 };     /* a capacity of the slot's region was too small when the job ran: only its segment was written */
+
+typedef struct svo_map_segment {    /* 64 bytes, host, one per named slot                                   */
+    int32_t seq, run;               /* slot and ordinal of its run (svo_run_info.run)                       */
+    int32_t frame_id;               /* of the slot's current frame; -1: empty slot (every count is 0)       */
+    int32_t status;                 /* SVO_MAP_*                                                            */
+    int32_t n_keyframes, keyframes_retired;   /* of the slot when the job ran                               */
+    int32_t from_keyframe, n_exported;        /* keyframes [from_keyframe, from_keyframe + n_exported): the region's
+                                                 from_keyframe; n_exported = max(0, n_keyframes - from_keyframe) */
+    int64_t n_points;               /* points kept (TOO_SMALL: 0)                                           */
+    int64_t points_bound;           /* keypoints of the exported keyframes: the sum of their n_total        */
+    float   time_stamp;             /* of the slot's current frame                                          */
+    int32_t _pad[3];
+} svo_map_segment;
+
+typedef struct svo_map_region {     /* where one named slot goes: the caller places every slot itself       */
+    int64_t first_point;            /* its points are records [first_point, first_point + n_points) of dst->points */
+    int64_t point_capacity;         /* records it may take: >= points_bound, or the slot comes back TOO_SMALL */
+    int64_t first_keyframe_entry;   /* its keyframes are entries [first_keyframe_entry, + n_exported) of dst->keyframes */
+    int32_t keyframe_capacity;      /* entries it may take: >= n_exported, or TOO_SMALL                     */
+    int32_t from_keyframe;          /* >= 0; beyond the slot's count: nothing exported                      */
+} svo_map_region;
+
+typedef struct svo_map_dst {
+    svo_map_segment  *segments;     /* HOST memory always, one per named slot                               */
+    svo_map_keyframe *keyframes;    /* HOST memory always; NULL: every keyframe_capacity is 0               */
+    svo_map_point    *points;       /* host or device (mem), 16-byte aligned; NULL: every point_capacity is 0 */
+} svo_map_dst;
+
+/* what an export of the slot from keyframe from_keyframe on would need right now: *keyframes = n_exported,
+ * *points_bound = the sum of their keypoint counts (either may be NULL). A getter: waits for the queues. */
+int svo_map_size(svo_ctx *ctx, int seq, int from_keyframe, int *keyframes, int64_t *points_bound);
+/* Queued exactly as svo_submit_export is (seqs == NULL names every slot in order, n is ignored; segment i and
+ * regions[i] belong to slot seqs[i]): it sees every frame set, restart, load and pose update submitted before it and
+ * none submitted after; only the groups that own a named slot get work and no group waits for another; the slot is
+ * not changed (its deferred pose-filter update is flushed first). regions, filter and dst are copied; segments,
+ * keyframes and points stay valid until svo_wait, after which everything is delivered. Regions must not overlap.
+ * Sizes: keyframe counts grow while frames are queued, so they are only known when the job runs. A slot with
+ * n_exported > keyframe_capacity or points_bound > point_capacity gets status SVO_MAP_TOO_SMALL: its segment carries
+ * the counts needed, nothing else of the slot is written, the other slots are delivered, the ctx does not fail and
+ * svo_wait returns SVO_OK (the rule of snapshots). The check is on the bound, never on the kept count, so it is made
+ * before any launch and the kernels cannot overrun a region. Of a region exactly records [first_point, first_point
+ * + n_points) and entries [first_keyframe_entry, + n_exported) are written.
+ * Rejected with SVO_ERR_INVALID and nothing queued: a slot out of range or named twice, a bad mem (SVO_MEM_HOST or
+ * SVO_MEM_DEVICE, of `points`), NULL segments, NULL keyframes or points together with a positive capacity, a
+ * negative region field, a misaligned points, drop_flags bits that are no SVO_IGNORE_* bit, _reserved != 0; a
+ * failed ctx, as in svo_submit_images.
+ * Every group keeps a small block of counts (per keyframe and tile of a job) and, in host mode, a staging block of
+ * points: made by the group's first (host-mode) map export, grown when outgrown, counted in svo_ctx_get_memory. Host
+ * mode copies each named slot's kept prefix out in one piece; the per-keyframe kept counts come back in one copy per
+ * group. A ctx that never exports a map allocates, launches and copies nothing more. */
+int svo_submit_export_map(svo_ctx *ctx, const int *seqs, int n, const svo_map_region *regions,
+                          const svo_map_filter *filter, const svo_map_dst *dst, int mem);
+int svo_export_map(svo_ctx *ctx, const int *seqs, int n, const svo_map_region *regions,
+                   const svo_map_filter *filter, const svo_map_dst *dst, int mem);   /* submit + wait */
+/* stage entry of the two kernels: region r holds the SoA sets [set_begin[r], set_begin[r + 1]) (set_begin: host,
+ * n_regions + 1 entries from 0 on, ascending; sets: host array of views onto device memory, of which kps3d, flags,
+ * keyframe_id, inlier_count and color are read: 4-byte aligned); own_id[s] (host): the keyframe id set s is held
+ * by; first[r] (host, >= 0): the record region r starts at. The kept points of a region leave densely from
+ * points[first[r]] on, in set order and keypoint order (points: device, 16-byte aligned, or NULL: only counts);
+ * counts[s] (device, one per set, or NULL) receives the points kept of set s. The tracker's launches (chunked when
+ * the diagnostic SVO_MAP_TABLE_TILES bounds the tile table): keypoints [0, n) of the five planes of a set are read,
+ * records [first[r], + kept of r) and every counts[s] written, nothing else. Complete on return. */
+int svo_pack_map_points(svo_handle *h, int n_regions, const int32_t *set_begin, const svo_keypoints *sets,
+                        const int32_t *own_id, const int64_t *first, const svo_map_filter *filter,
+                        svo_map_point *points, int32_t *counts);
+
 /* ---- snapshots: the sequence state of a slot saved, loaded, moved between ctxs ------------
  * The reference has no checkpoint or resume (a StereoSlam lives and dies with its process). A snapshot is
  * everything the next frame of a slot depends on and everything its getters return, so that a sequence saved

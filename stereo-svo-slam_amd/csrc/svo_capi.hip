@@ -38,6 +38,8 @@ struct svo_handle {
     size_t export_ws_count = 0;
     DevPtr<CopyTile> copy_ws;       // svo_copy_segments: the tile table
     size_t copy_ws_count = 0;
+    DevPtr<uint8_t> map_ws;         // svo_pack_map_points: the tile counts of a call, then the tile table
+    size_t map_ws_bytes = 0;
 };
 
 extern "C" const char* svo_last_error(void) { return svo_error_text; }
@@ -314,6 +316,58 @@ extern "C" int svo_pack_keypoints(svo_handle* h, int n_sets, const svo_keypoints
     HIP_TRY(hipMemcpyAsync(h->export_ws.get(), tiles.data(), sizeof(ExportTile) * tiles.size(), hipMemcpyHostToDevice, h->stream));
     launch_export(h->export_ws.get(), (int)tiles.size(), kps2d, kps3d, info, h->stream);
     HIP_TRY(hipGetLastError());
+    return SVO_OK;
+}
+
+extern "C" int svo_pack_map_points(svo_handle* h, int n_regions, const int32_t* set_begin, const svo_keypoints* sets,
+                                   const int32_t* own_id, const int64_t* first, const svo_map_filter* filter,
+                                   svo_map_point* points, int32_t* counts) {
+    CHECK_H(h);
+    if (n_regions < 0 || (n_regions > 0 && (!set_begin || !first || set_begin[0] != 0)))
+        return svo_set_error(SVO_ERR_INVALID, "svo_pack_map_points: bad arguments");
+    const svo_map_filter f = filter ? *filter : svo_map_filter{0, 0, 0, 0};
+    if ((f.drop_flags & ~(uint32_t)(SVO_IGNORE_DURING_REFINEMENT | SVO_IGNORE_COMPLETELY | SVO_IGNORE_TEMPORARY)) || f._reserved != 0)
+        return svo_set_error(SVO_ERR_INVALID, "svo_pack_map_points: drop_flags 0x%x has unknown bits, or _reserved is not 0", f.drop_flags);
+    if (((uintptr_t)points & 15) || ((uintptr_t)counts & 3))
+        return svo_set_error(SVO_ERR_INVALID, "svo_pack_map_points: points must be 16-byte aligned, counts 4-byte");
+    std::vector<MapTile> tiles;
+    for (int r = 0; r < n_regions; r++) {
+        if (set_begin[r + 1] < set_begin[r] || first[r] < 0)
+            return svo_set_error(SVO_ERR_INVALID, "svo_pack_map_points: region %d: set_begin must ascend, first must be >= 0", r);
+        if (set_begin[r + 1] > set_begin[r] && (!sets || !own_id)) return svo_set_error(SVO_ERR_INVALID, "svo_pack_map_points: no sets");
+        const int region_tile = (int)tiles.size();
+        for (int s = set_begin[r]; s < set_begin[r + 1]; s++) {
+            const svo_keypoints& k = sets[s];
+            if (k.n < 0) return svo_set_error(SVO_ERR_INVALID, "svo_pack_map_points: set %d: n must be >= 0", s);
+            KpsDev d{};
+            d.kps3d = k.kps3d; d.flags = k.flags; d.kf_id = k.keyframe_id; d.inl = k.inlier_count; d.color = k.color;
+            for (const void* p : {(const void*)d.kps3d, (const void*)d.flags, (const void*)d.kf_id, (const void*)d.inl, (const void*)d.color})
+                if ((k.n > 0 && !p) || ((uintptr_t)p & 3))
+                    return svo_set_error(SVO_ERR_INVALID, "svo_pack_map_points: set %d: kps3d, flags, keyframe_id, inlier_count and color are device memory, 4-byte aligned", s);
+            map_tiles(d, k.n, own_id[s], s, first[r], region_tile, tiles);
+            if (tiles.size() > (size_t)INT_MAX / 2) return svo_set_error(SVO_ERR_INVALID, "svo_pack_map_points: too many keypoints");
+        }
+    }
+    if (tiles.empty() || (!points && !counts)) return SVO_OK;
+    // (SVO_MAP_TABLE_TILES: a smaller table, so that tests reach the chunked launches)
+    const size_t chunk = table_tiles("SVO_MAP_TABLE_TILES", tiles.size());
+    const size_t counts_bytes = (sizeof(int) * tiles.size() + 15) / 16 * 16;
+    const size_t bytes = counts_bytes + sizeof(MapTile) * chunk;
+    if (bytes > h->map_ws_bytes) {
+        HIP_TRY(hipStreamSynchronize(h->stream));      // (the old block may still be read)
+        h->map_ws.reset();
+        h->map_ws_bytes = 0;
+        HIP_TRY(dev_malloc(h->map_ws, bytes));
+        h->map_ws_bytes = bytes;
+    }
+    int* tile_counts = reinterpret_cast<int*>(h->map_ws.get());
+    std::vector<MapTile> host(chunk);
+    TileTable table{host.data(), reinterpret_cast<MapTile*>(h->map_ws.get() + counts_bytes), chunk, h->stream,
+                    [&](const MapTile* d, int m, hipStream_t s) { launch_map(d, m, f, points, tile_counts, counts, s); }};
+    for (const MapTile& t : tiles)
+        if (const int rc = table.add(t)) return rc;
+    if (const int rc = table.launch(false)) return rc;
+    HIP_TRY(hipStreamSynchronize(h->stream));          // (the table's upload read `host`)
     return SVO_OK;
 }
 

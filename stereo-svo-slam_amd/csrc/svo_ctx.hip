@@ -29,7 +29,7 @@
 // single-workgroup-per-sequence alignment kernel of one group overlaps the window kernels of
 // the other. svo_submit_images() queues a frame set on every group and returns;
 // svo_wait() drains the queues. svo_new_images() = submit + wait. Restarts (svo_ctx_restart_sequences),
-// exports (svo_submit_export), saves and loads (svo_submit_save / svo_submit_load) and pose-filter updates
+// exports (svo_submit_export, svo_submit_export_map), saves and loads (svo_submit_save / svo_submit_load) and pose-filter updates
 // (svo_submit_pose_updates) are entries of the same queues, so they are ordered with the frame sets.
 struct svo_ctx {
     // the group's share of an svo_submit_export: its named slots (indices in the group) in named order, the
@@ -39,6 +39,15 @@ struct svo_ctx {
         std::vector<int> seqs, seg;
         int64_t base = 0;
         svo_export_dst dst{};
+    };
+    // the group's share of an svo_submit_export_map: its named slots (indices in the group) in named order, the
+    // segment each one fills and the region it goes to
+    struct MapExport {
+        int mem = 0;
+        std::vector<int> seqs, seg;
+        std::vector<svo_map_region> regions;
+        svo_map_filter filter{};
+        svo_map_dst dst{};
     };
     // the group's share of an svo_submit_save (snaps) or svo_submit_load (loads): its named slots, indices in the group
     struct Snapshots {
@@ -56,7 +65,7 @@ struct svo_ctx {
     };
     // one entry of a group's queue: a frame set, or (restart non-empty) the end of some of its sequences, or
     // (exp.seqs non-empty) an export, or (snap.seqs / snap.loads non-empty) a save / a load, or (pose.seqs non-empty)
-    // pose-filter updates
+    // pose-filter updates, or (map.seqs non-empty) a map export
     struct Job {
         std::vector<const uint8_t*> left, right;
         std::vector<float> ts;
@@ -65,6 +74,7 @@ struct svo_ctx {
         Export exp;
         Snapshots snap;
         PoseUpdates pose;
+        MapExport map;
     };
     struct Worker {
         Group g;
@@ -100,7 +110,10 @@ void worker_run_job(svo_ctx::Worker& w, const svo_ctx::Job& job) {
     const svo_ctx::Export& e = job.exp;
     const svo_ctx::Snapshots& sn = job.snap;
     const svo_ctx::PoseUpdates& pu = job.pose;
-    const int rc = !pu.seqs.empty()
+    const svo_ctx::MapExport& mp = job.map;
+    const int rc = !mp.seqs.empty()
+                       ? grp_export_map(w.g.get(), mp.mem, mp.seqs.data(), mp.seg.data(), mp.regions.data(), (int)mp.seqs.size(), w.first, &mp.filter, &mp.dst)
+                   : !pu.seqs.empty()
                        ? grp_pose_updates(w.g.get(), pu.seqs.data(), pu.counts.data(), (int)pu.seqs.size(), pu.samples.data(), pu.filtered.data())
                    : !sn.loads.empty()
                        ? grp_load(w.g.get(), sn.loads.data(), (int)sn.loads.size(), sn.mem)
@@ -356,6 +369,58 @@ int reject_failed(svo_ctx* c, const char* name) {      // (as svo_submit_images)
 }
 
 }  // namespace
+
+extern "C" int svo_submit_export_map(svo_ctx* c, const int* seqs, int n, const svo_map_region* regions,
+                                     const svo_map_filter* filter, const svo_map_dst* dst, int mem) {
+    if (!c || !dst || !dst->segments || (mem != SVO_MEM_HOST && mem != SVO_MEM_DEVICE) || (seqs && n < 0))
+        return svo_set_error(SVO_ERR_INVALID, "svo_submit_export_map: bad arguments (mem %d)", mem);
+    if (!seqs) n = c->B;
+    if (n > 0 && !regions) return svo_set_error(SVO_ERR_INVALID, "svo_submit_export_map: no regions");
+    const svo_map_filter f = filter ? *filter : svo_map_filter{0, 0, 0, 0};
+    if ((f.drop_flags & ~(uint32_t)(SVO_IGNORE_DURING_REFINEMENT | SVO_IGNORE_COMPLETELY | SVO_IGNORE_TEMPORARY)) || f._reserved != 0)
+        return svo_set_error(SVO_ERR_INVALID, "svo_submit_export_map: drop_flags 0x%x has unknown bits, or _reserved is not 0", f.drop_flags);
+    if ((uintptr_t)dst->points & 15) return svo_set_error(SVO_ERR_INVALID, "svo_submit_export_map: points is not 16-byte aligned");
+    std::vector<char> named(c->B, 0);
+    for (int i = 0; i < n; i++) {
+        const int s = seqs ? seqs[i] : i;
+        if (s < 0 || s >= c->B || named[s])
+            return svo_set_error(SVO_ERR_INVALID, "svo_submit_export_map: sequence %d is out of range or named twice", s);
+        named[s] = 1;
+        const svo_map_region& r = regions[i];
+        if (r.first_point < 0 || r.point_capacity < 0 || r.first_keyframe_entry < 0 || r.keyframe_capacity < 0 || r.from_keyframe < 0)
+            return svo_set_error(SVO_ERR_INVALID, "svo_submit_export_map: region %d has a negative field", i);
+        if ((r.point_capacity > 0 && !dst->points) || (r.keyframe_capacity > 0 && !dst->keyframes))
+            return svo_set_error(SVO_ERR_INVALID, "svo_submit_export_map: region %d has a capacity, but its array is NULL", i);
+    }
+    if (c->failed.load()) return reject_failed(c, "svo_submit_export_map");
+    for (auto& wp : c->workers) {
+        svo_ctx::Worker& w = *wp;
+        svo_ctx::Job job;
+        svo_ctx::MapExport& e = job.map;
+        for (int i = 0; i < n; i++) {
+            const int s = seqs ? seqs[i] : i;
+            if (s >= w.first && s < w.first + w.count) { e.seqs.push_back(s - w.first); e.seg.push_back(i); e.regions.push_back(regions[i]); }
+        }
+        if (e.seqs.empty()) continue;
+        e.mem = mem; e.filter = f; e.dst = *dst;
+        worker_submit(w, std::move(job));
+    }
+    return SVO_OK;
+}
+
+extern "C" int svo_export_map(svo_ctx* c, const int* seqs, int n, const svo_map_region* regions, const svo_map_filter* filter,
+                              const svo_map_dst* dst, int mem) {
+    const int rc = svo_submit_export_map(c, seqs, n, regions, filter, dst, mem);
+    return rc ? rc : svo_wait(c);
+}
+
+extern "C" int svo_map_size(svo_ctx* ctx, int seq, int from_keyframe, int* keyframes, int64_t* points_bound) {
+    if (from_keyframe < 0) return svo_set_error(SVO_ERR_INVALID, "svo_map_size: from_keyframe %d", from_keyframe);
+    svo_group* g; int s;
+    if (const int rc = ctx_seq(ctx, seq, &g, &s)) return rc;
+    grp_map_size(g, s, from_keyframe, keyframes, points_bound);
+    return SVO_OK;
+}
 
 extern "C" int svo_submit_save(svo_ctx* c, const int* seqs, int n, svo_snapshot* snaps, int mem) {
     if (const int rc = check_snapshot_call(c, "svo_submit_save", seqs, n, snaps, mem)) return rc;

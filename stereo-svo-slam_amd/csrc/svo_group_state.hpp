@@ -1,7 +1,7 @@
 // svo_group_state.hpp — the state of one sequence group, internal to the group: only its translation units
 // (svo_group.hip: storage, creation, settings, the end of a sequence; svo_group_step.hip: the step;
-// svo_group_export.hip: the bulk export; svo_group_snapshot.hip: save and load; svo_group_pose.hip: the batched
-// pose-filter updates) and the per-sequence getters of
+// svo_group_export.hip: the bulk export; svo_group_map.hip: the map export; svo_group_snapshot.hip: save and load;
+// svo_group_pose.hip: the batched pose-filter updates) and the per-sequence getters of
 // svo_ctx.hip include it. Everyone else drives a group through the opaque interface of svo_group.hpp.
 //
 // Host side = bookkeeping only: image-set pool, argument blocks, the 12-state
@@ -276,6 +276,12 @@ struct svo_group {
     // snapshots (grp_save / grp_load) in host mode: the data parts of one call, made by the first such call and
     // replaced when outgrown
     uint8_t* d_snap = nullptr; size_t snap_bytes = 0;
+    // map export (grp_export_map): the kept counts of one job (map_counts ints: per exported keyframe, then per tile)
+    // and the pinned mirror that its per-keyframe part comes back into, made by the group's first map export; in host
+    // mode the staging block of map_points points, made by the first host-mode one. Replaced when outgrown.
+    int* d_map_counts = nullptr; size_t map_counts = 0;
+    svo::PinnedPtr<int> map_counts_host;
+    svo_map_point* d_map_points = nullptr; size_t map_points = 0;
     // batched pose-filter updates (grp_pose_updates): the upload block (samples | filter states | start poses |
     // sample offsets) and behind it the download block (filter states | filtered poses) of one job, device and pinned,
     // made by the first such job and replaced when outgrown

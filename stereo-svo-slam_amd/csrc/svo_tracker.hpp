@@ -4,6 +4,7 @@
 
 #include <vector>
 
+#include "../../include/svo_hip.h"
 #include "svo_kernels.hpp"
 
 namespace svo {
@@ -121,6 +122,35 @@ ExportTile export_tile(const KpsDev& k, int start, int count, int64_t first);
 // every output array: device memory or null (skipped); nothing is launched for no tiles or no arrays
 void launch_export(const ExportTile* d_tiles, int n_tiles, svo_kp2d* kps2d, svo_kp3d* kps3d, svo_kp_info* info,
                    hipStream_t stream);
+
+// ------------------------------------------------------------ map export (map.hip)
+// One tile of a keyframe's keypoint set on its way into the compacted points of a region: at most MAP_TILE
+// keypoints, one workgroup. The planes point at the tile's first keypoint (kps3d as dwords). The tiles of a call
+// are numbered in the order they are added (index): those of a region are consecutive, those of a set too, and
+// tile_counts[index] receives the tile's kept points. A set without keypoints still has one tile (count 0), so that
+// every set's count is written.
+constexpr int MAP_TILE = 256;
+struct MapTile {
+    const uint32_t* kps3d;
+    const uint32_t* flags;
+    const int* kf_id;
+    const int* inl;
+    const uint32_t* color;
+    int64_t first;         // record of `points` the tile's region starts at
+    int count;             // keypoints of the tile
+    int own_id;            // id of the keyframe that holds the set
+    int index;             // of the tile in the call
+    int region_tile;       // index of the first tile of its region
+    int set_tile;          // index of the first tile of its set
+    int set;               // >= 0: the tile is the last of set `set` (set_counts[set] is written); -1: it is not
+};
+// appends the tiles of keypoints [0, n) of set `set` of a region whose first tile has index region_tile
+void map_tiles(const KpsDev& k, int n, int own_id, int set, int64_t first, int region_tile, std::vector<MapTile>& out);
+// A chunk of a call's tiles, in index order and after every earlier chunk on the same stream: the count launch
+// writes tile_counts[index] of the chunk's tiles, the write launch sums the counts of a tile's region before it,
+// writes the kept points (points: device, 16-byte aligned, or null: none) and set_counts (or null).
+void launch_map(const MapTile* d_tiles, int n_tiles, const svo_map_filter& filter, svo_map_point* points,
+                int* tile_counts, int* set_counts, hipStream_t stream);
 
 // ------------------------------------------------------------ segment copies (snapshot.hip)
 // One tile of a 2-D byte segment: `rows` rows of `row_bytes` bytes, one workgroup. rows * row_bytes is at most

@@ -39,6 +39,7 @@ SYMBOLS = (
     "svo_snapshot_info", "svo_copy_segments",
     "svo_reproj_gn_batch", "svo_filter_update_batch", "svo_sparse_align_batch",
     "svo_submit_pose_updates", "svo_update_poses", "svo_pose_filter_batch",
+    "svo_map_size", "svo_submit_export_map", "svo_export_map", "svo_pack_map_points",
 )
 
 # svo_ctx_set_input_format / svo_convert_frames: how the buffers of a sequence become its two gray images
@@ -111,6 +112,41 @@ class ExportDst(C.Structure):
     """svo_export_dst (include/svo_hip.h)."""
     _fields_ = [("segments", C.c_void_p), ("kps2d", C.c_void_p), ("kps3d", C.c_void_p), ("info", C.c_void_p),
                 ("capacity", C.c_int64)]
+
+
+# map export (svo_submit_export_map, include/svo_hip.h): a point, a keyframe entry, a segment (one per named slot)
+MAP_POINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("color", "u1", (3,)), ("flags", "u1")])
+MAP_KEYFRAME_DTYPE = np.dtype([("id", "<i4"), ("n_total", "<i4"), ("n", "<i4"), ("_pad", "<i4"), ("first", "<i8"),
+                               ("pose", "<f4", (6,))])
+MAP_SEGMENT_DTYPE = np.dtype([("seq", "<i4"), ("run", "<i4"), ("frame_id", "<i4"), ("status", "<i4"),
+                              ("n_keyframes", "<i4"), ("keyframes_retired", "<i4"), ("from_keyframe", "<i4"),
+                              ("n_exported", "<i4"), ("n_points", "<i8"), ("points_bound", "<i8"),
+                              ("time_stamp", "<f4"), ("_pad", "<i4", (3,))])
+# svo_map_region as a numpy record, so that a call's regions are one array
+MAP_REGION_DTYPE = np.dtype([("first_point", "<i8"), ("point_capacity", "<i8"), ("first_keyframe_entry", "<i8"),
+                             ("keyframe_capacity", "<i4"), ("from_keyframe", "<i4")])
+assert (MAP_POINT_DTYPE.itemsize, MAP_KEYFRAME_DTYPE.itemsize, MAP_SEGMENT_DTYPE.itemsize,
+        MAP_REGION_DTYPE.itemsize) == (16, 48, 64, 32)
+MAP_COMPLETE, MAP_TOO_SMALL = 0, 1
+IGNORE_DURING_REFINEMENT, IGNORE_COMPLETELY, IGNORE_TEMPORARY = 1, 2, 4
+
+
+class MapFilter(C.Structure):
+    """svo_map_filter (include/svo_hip.h): all zero keeps every keypoint of every keyframe."""
+    _fields_ = [("drop_flags", C.c_uint32), ("own_only", C.c_int32), ("min_inliers", C.c_int32),
+                ("_reserved", C.c_int32)]
+
+
+class MapDst(C.Structure):
+    """svo_map_dst (include/svo_hip.h)."""
+    _fields_ = [("segments", C.c_void_p), ("keyframes", C.c_void_p), ("points", C.c_void_p)]
+
+
+def map_filter(f):
+    """a MapFilter from None (keep everything), a MapFilter or a dict of its fields"""
+    if f is None:
+        return MapFilter()
+    return f if isinstance(f, MapFilter) else MapFilter(**f)
 
 
 class Keypoints(C.Structure):
@@ -345,6 +381,24 @@ class Handle:
                 setattr(arr[i], name, v.data_ptr() if isinstance(v, torch.Tensor) else int(v))
         firsts = (C.c_int64 * max(len(sets), 1))(*[int(f) for f in first])
         _check(lib().svo_pack_keypoints(self._h, len(sets), arr, firsts, _ptr(kps2d), _ptr(kps3d), _ptr(info)))
+
+    def pack_map_points(self, regions, first, filter=None, points=None, counts=None):
+        """svo_pack_map_points: the keypoints of SoA sets that pass `filter` (map_filter's forms) as dense 16-byte
+        points. regions: per region a list of (n, own keyframe id, {field of svo_keypoints: device tensor or raw
+        device address}) sets; first[r]: the record region r starts at; points: uint8 [records, 16] device tensor
+        or None (counts only); counts: int32 [sets] device tensor (the kept points of every set, in call order) or
+        None. Complete on return."""
+        sets = [s for r in regions for s in r]
+        arr = (Keypoints * max(len(sets), 1))()
+        for i, (n, _, fields) in enumerate(sets):
+            arr[i].n = int(n)
+            for name, v in fields.items():
+                setattr(arr[i], name, v.data_ptr() if isinstance(v, torch.Tensor) else int(v))
+        begin = (C.c_int32 * (len(regions) + 1))(*np.cumsum([0] + [len(r) for r in regions]).tolist())
+        own = (C.c_int32 * max(len(sets), 1))(*[int(s[1]) for s in sets])
+        firsts = (C.c_int64 * max(len(regions), 1))(*[int(f) for f in first])
+        _check(lib().svo_pack_map_points(self._h, len(regions), begin, arr, own, firsts, C.byref(map_filter(filter)),
+                                         _ptr(points), _ptr(counts)))
 
     def copy_segments(self, segs):
         """svo_copy_segments: 2-D byte segments, device to device. segs: (src address, dst address, row_bytes,

@@ -176,6 +176,99 @@ class Export:
         return Frame(np.array(e["pose"], np.float32), *out)
 
 
+class MapExport:
+    """One svo_submit_export_map: owns the buffers the library writes. `regions` (hip_lib.MAP_REGION_DTYPE, one per
+    named slot: where the slot goes and from which keyframe on) are laid out here, densely in named order, from the
+    capacities given, unless an array of them is passed. After wait(): `segments` (hip_lib.MAP_SEGMENT_DTYPE, one
+    per named slot), keyframes(i), points(i) and points_of_keyframe(i, k). The points are a numpy view
+    (hip_lib.MAP_POINT_DTYPE) of pinned memory in host mode, `points_buffer` a uint8 [capacity, 16] tensor on the
+    ctx's device in device mode (points(i) then copies the slot's records to the host)."""
+
+    def __init__(self, slam, seqs=None, from_keyframe=None, filter=None, device=False, point_capacity=0,
+                 keyframe_capacity=0, regions=None):
+        self._slam = slam
+        self.device_mode = bool(device)
+        self.seqs = list(range(slam.n)) if seqs is None else [int(s) for s in seqs]
+        n = self._n = len(self.seqs)
+        self.filter = hip_lib.map_filter(filter)
+        self.regions = np.zeros(max(n, 1), hip_lib.MAP_REGION_DTYPE)[:n]
+        if regions is not None:
+            self.regions[:] = regions
+        else:
+            self.regions["from_keyframe"] = 0 if from_keyframe is None else from_keyframe
+            self.regions["point_capacity"] = point_capacity
+            self.regions["keyframe_capacity"] = keyframe_capacity
+            self._place()
+        self._seq_arr = (C.c_int * max(n, 1))(*self.seqs)
+        self._seg = np.zeros(max(n, 1), hip_lib.MAP_SEGMENT_DTYPE)
+        self.segments = self._seg[:n]
+        self._allocate()
+
+    def _place(self):
+        """every slot behind the one named before it"""
+        r = self.regions
+        r["first_point"] = np.cumsum(r["point_capacity"]) - r["point_capacity"]
+        r["first_keyframe_entry"] = np.cumsum(r["keyframe_capacity"]) - r["keyframe_capacity"]
+
+    def _allocate(self):
+        r = self.regions
+        self.capacity = int((r["first_point"] + r["point_capacity"]).max()) if self._n else 0
+        entries = int((r["first_keyframe_entry"] + r["keyframe_capacity"]).max()) if self._n else 0
+        self._kfs = np.zeros(max(entries, 1), hip_lib.MAP_KEYFRAME_DTYPE)
+        shape = (max(self.capacity, 1), hip_lib.MAP_POINT_DTYPE.itemsize)
+        self.points_buffer = (torch.empty(shape, dtype=torch.uint8, device=self._slam.device) if self.device_mode
+                              else torch.empty(shape, dtype=torch.uint8, pin_memory=True))
+        self._dst = hip_lib.MapDst(self._seg.ctypes.data, self._kfs.ctypes.data if entries else None,
+                                   self.points_buffer.data_ptr() if self.capacity else None)
+
+    def submit(self):
+        """queue the export (again: the same slots into the same buffers, once the previous one is delivered)"""
+        slam = self._slam
+        if self.device_mode:
+            torch.cuda.current_stream(slam.device).synchronize()     # (nothing of the caller's is still using the tensor)
+        _check(lib().svo_submit_export_map(slam._ctx, self._seq_arr, self._n, self.regions.ctypes.data_as(C.c_void_p),
+                                           C.byref(self.filter), C.byref(self._dst),
+                                           hip_lib.MEM_DEVICE if self.device_mode else hip_lib.MEM_HOST))
+        return self
+
+    def wait(self):
+        self._slam.wait()
+        return self
+
+    def grow(self):
+        """after wait(): every slot that came back MAP_TOO_SMALL gets the capacities its segment asks for, the regions
+        are laid out again and new buffers made. False: every slot was delivered and nothing changed."""
+        small = self.segments["status"] == hip_lib.MAP_TOO_SMALL
+        if not small.any():
+            return False
+        r = self.regions
+        r["point_capacity"] = np.where(small, np.maximum(r["point_capacity"], self.segments["points_bound"]), r["point_capacity"])
+        r["keyframe_capacity"] = np.where(small, np.maximum(r["keyframe_capacity"], self.segments["n_exported"]), r["keyframe_capacity"])
+        self._place()
+        self._allocate()
+        return True
+
+    def keyframes(self, i):
+        """the svo_map_keyframe entries (hip_lib.MAP_KEYFRAME_DTYPE) of named slot i; none for a slot that was not delivered"""
+        e, r = self.segments[i], self.regions[i]
+        n = int(e["n_exported"]) if e["status"] == hip_lib.MAP_COMPLETE else 0
+        return self._kfs[int(r["first_keyframe_entry"]):int(r["first_keyframe_entry"]) + n]
+
+    def _records(self, lo, n):
+        a = self.points_buffer[lo:lo + n]
+        a = a.cpu().numpy() if self.device_mode else a.numpy()
+        return a.view(hip_lib.MAP_POINT_DTYPE)[:, 0]
+
+    def points(self, i):
+        """the kept points of named slot i (hip_lib.MAP_POINT_DTYPE), keyframe after keyframe"""
+        return self._records(int(self.regions[i]["first_point"]), int(self.segments[i]["n_points"]))
+
+    def points_of_keyframe(self, i, k):
+        """the kept points of the k-th exported keyframe of named slot i"""
+        kf = self.keyframes(i)[k]
+        return self._records(int(kf["first"]), int(kf["n"]))
+
+
 class Snapshot:
     """The sequence state of one slot (svo_submit_save / svo_submit_load): `host` (numpy uint8, the host part) and
     `data` (the data part: numpy uint8, or a torch uint8 tensor on the ctx's device in device mode). Valid after
@@ -412,6 +505,40 @@ class StereoSlamBatch:
 
     def export_last_keyframes(self, seqs=None, device=False, fields=("kps2d", "kps3d", "info")):
         return self.submit_export("last_keyframes", seqs, device, fields).wait()
+
+    def map_size(self, seq, from_keyframe=0):
+        """svo_map_size: (keyframes, points_bound) an export of the slot's map from `from_keyframe` on needs right
+        now (waits)."""
+        k, p = C.c_int(0), C.c_int64(0)
+        _check(lib().svo_map_size(self._ctx, int(seq), int(from_keyframe), C.byref(k), C.byref(p)))
+        return k.value, p.value
+
+    def submit_map(self, seqs=None, from_keyframe=None, filter=None, device=False, point_capacity=None,
+                   keyframe_capacity=None, regions=None):
+        """svo_submit_export_map: queue the export of every keyframe (from `from_keyframe` on: None = 0, an int, or
+        one per slot) of the slots `seqs` (None: all, in order) as compacted points behind what was submitted so
+        far. filter: None (everything), a hip_lib.MapFilter or a dict of its fields. Returns a MapExport, valid
+        after its wait(). point_capacity / keyframe_capacity (an int or one per slot): room for what the frames
+        still queued may add, nothing is waited for then and a slot that outgrew them comes back MAP_TOO_SMALL;
+        default: what the slots need right now (map_size: waits for the queues). regions: a
+        hip_lib.MAP_REGION_DTYPE array that places every slot itself."""
+        if regions is None and (point_capacity is None or keyframe_capacity is None):
+            named = list(range(self.n)) if seqs is None else [int(s) for s in seqs]
+            frm = np.broadcast_to(0 if from_keyframe is None else from_keyframe, (len(named),))
+            sizes = [self.map_size(s, f) for s, f in zip(named, frm)]
+            if keyframe_capacity is None:
+                keyframe_capacity = [k for k, _ in sizes]
+            if point_capacity is None:
+                point_capacity = [p for _, p in sizes]
+        return MapExport(self, seqs, from_keyframe, filter, device, point_capacity, keyframe_capacity, regions).submit()
+
+    def export_map(self, seqs=None, from_keyframe=None, filter=None, device=False):
+        """the map of the slots `seqs`: regions sized from map_size, submit + wait; a slot that came back
+        MAP_TOO_SMALL gets the capacities its segment asks for and the export runs once more."""
+        m = self.submit_map(seqs, from_keyframe, filter, device).wait()
+        if m.grow():
+            m.submit().wait()
+        return m
 
     def snapshot_size(self, seq):
         """svo_snapshot_size: (host_bytes, data_bytes) a save of the slot needs right now (waits)."""

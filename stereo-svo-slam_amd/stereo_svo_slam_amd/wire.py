@@ -41,6 +41,22 @@ def keyframes_message(slam, seq=0):
     return json.dumps(out, separators=(",", ":"))
 
 
+def keyframes_messages(slam, seqs=None):
+    """keyframes_message of many slots (None: all) of a StereoSlamBatch from ONE unfiltered map export
+    (svo_submit_export_map) instead of a getter round trip per keyframe: the same texts, character for character."""
+    m = slam.export_map(seqs)
+    texts = []
+    for i in range(len(m.segments)):
+        out = []
+        for k, kf in enumerate(m.keyframes(i)):
+            pts = m.points_of_keyframe(i, k)
+            out.append({"pose": _pose_object(kf["pose"]),
+                        "keypoints": [{"x": float(p["x"]), "y": float(p["y"]), "z": float(p["z"])} for p in pts],
+                        "colors": [{"r": int(c[0]), "g": int(c[1]), "b": int(c[2])} for c in pts["color"]]})
+        texts.append(json.dumps(out, separators=(",", ":")))
+    return texts
+
+
 def pose_message(slam, seq=0):
     return json.dumps({"pose": _pose_object(slam.pose(seq))}, separators=(",", ":"))
 
