@@ -525,6 +525,106 @@ int svo_pack_map_points(svo_handle *h, int n_regions, const int32_t *set_begin, 
                         const int32_t *own_id, const int64_t *first, const svo_map_filter *filter,
                         svo_map_point *points, int32_t *counts);
 
+/* ---- views: the images of frames and newest keyframes of many slots in one queued job ------------
+ * The reference hands images to its caller: Frame and KeyFrame carry stereo_image (src/include/stereo_slam_types.hpp:120),
+ * and its consumers read frame.stereo_image.left[0]: the test app's window (draw_frame, src/app/main.cpp:40-118: the
+ * last keyframe and the current frame, a marker per keypoint) and the AR demo's video surface
+ * (src/ar-app/opencvimageprovider.cpp:33,59). Here the gray images are made on the device (input formats,
+ * rectification, pyramids) and only a snapshot moved them out. A view job is the batched reader: the groups that own a
+ * named slot render one image per slot with one kernel launch each (view.hip) and deliver it into host or device
+ * memory; the host writes one svo_view_segment per named slot. Two forms: the plain gray plane, or gray expanded to
+ * RGB with one marker per keypoint, composed on the device, where keypoints, colours and flags live.
+ *
+ * Layout: rows are dense, pitch = cols * bytes per pixel; image_bytes = rows * pitch rounded up to a multiple of 256;
+ * named slot i of a job goes to offset = i * image_bytes of dst->pixels, whatever group owns it. Of a slot exactly
+ * rows * pitch bytes from its offset on are written; a slot whose status is SVO_VIEW_NONE writes only its segment.
+ *
+ * Markers: the project's own statement of cv::drawMarker(img, p, color, type, size) at thickness 1 as draw_frame
+ * calls it, for the two marker types the app uses; both are axis-aligned runs of pixels. Not restated: the text
+ * overlay (putText) and the x2 cv::resize of the app's window.
+ *   centre  c = (trunc(x * 2^-level), trunc(y * 2^-level)), truncated toward zero (Point(float, float)); a keypoint
+ *           whose scaled coordinate is not finite or has magnitude >= 2^15 draws nothing
+ *   size    s = size_temporary if the keypoint has SVO_IGNORE_TEMPORARY, else size (the app: 10 / 20 for a frame, 10
+ *           for a keyframe)
+ *   cross   type SVO_KP_FAST: the pixels (cx - s/2 .. cx + s/2, cy) and (cx, cy - s/2 .. cy + s/2); integer
+ *           division, ends inclusive
+ *   square  any other type: with s' = (int)(s * 0.8), the border of [cx - s'/2, cx + s'/2] x [cy - s'/2, cy + s'/2]
+ *   colour  bytes r, g, b of the keypoint's colour into channels 0, 1, 2 (the app draws Scalar(r, g, b) into a
+ *           GRAY2RGB image); every other pixel is (g, g, g); the fourth byte of RGBA is 255
+ *   order   keypoints are drawn in ascending index and a later one overwrites: a pixel takes the colour of the
+ *           highest-index keypoint that is not dropped and whose marker covers it
+ *   pixels outside the image are dropped. */
+enum { SVO_PLANE_LEFT = 0, SVO_PLANE_RIGHT = 1 };
+enum { SVO_PIXEL_GRAY8 = 0, SVO_PIXEL_RGB8 = 1, SVO_PIXEL_RGBA8 = 2 };   /* 1, 3, 4 bytes per pixel; A = 255 */
+enum { SVO_VIEW_OK = 0,
+       SVO_VIEW_NONE = 1 };         /* an empty slot, no keyframe yet, or the keyframe has given its image set back */
+
+typedef struct svo_view_style {     /* what one job draws; copied at submit                                 */
+    int32_t  plane;                 /* SVO_PLANE_*                                                          */
+    int32_t  level;                 /* LEFT: pyramid level 0 .. max_pyramid_levels - 1 ((width >> level) x (height >> level));
+                                       RIGHT: 0                                                             */
+    int32_t  pixel;                 /* SVO_PIXEL_*                                                          */
+    int32_t  markers;               /* 0: the plane only; 1: and one marker per keypoint (LEFT and RGB8 / RGBA8 only) */
+    uint32_t drop_flags;            /* keypoints with (flags & drop_flags) != 0 get no marker; SVO_IGNORE_* bits only */
+    int32_t  size, size_temporary;  /* marker size without / with SVO_IGNORE_TEMPORARY, 0 .. 64             */
+    int32_t  _reserved;             /* 0                                                                    */
+} svo_view_style;
+
+typedef struct svo_view_segment {   /* 64 bytes, host, one per named slot                                   */
+    int32_t seq, run;               /* slot and ordinal of its run (svo_run_info.run)                       */
+    int32_t frame_id;               /* of the slot's current frame; -1: empty slot                          */
+    int32_t keyframe_id;            /* LAST_KEYFRAMES: the keyframe shown (-1: the slot has none); FRAMES: -1 */
+    int32_t status;                 /* SVO_VIEW_*                                                           */
+    int32_t n;                      /* keypoints of the set the markers come from                           */
+    int64_t offset;                 /* the image is bytes [offset, offset + rows * pitch) of dst->pixels    */
+    float   pose[6];                /* FRAMES: svo_get_pose; LAST_KEYFRAMES: the keyframe's pose            */
+    float   time_stamp;             /* of the slot's current frame                                          */
+    int32_t _pad;
+} svo_view_segment;
+
+typedef struct svo_view_dst {
+    svo_view_segment *segments;     /* HOST memory always, >= n entries                                     */
+    uint8_t *pixels;                /* host or device (mem); 4-byte aligned (16-byte aligned: the wide stores) */
+    int64_t capacity;               /* bytes `pixels` holds                                                 */
+} svo_view_dst;
+
+/* the shape of one image of a job with that style in a ctx of these settings, without a GPU (any out pointer may be
+ * NULL). Settings svo_ctx_create rejects, or a style a job rejects: SVO_ERR_INVALID */
+int svo_view_size(const svo_camera_settings *cam, int width, int height, const svo_view_style *style,
+                  int *cols, int *rows, int64_t *pitch, int64_t *image_bytes);
+/* what: SVO_EXPORT_FRAMES (the image set of the slot's current frame; a slot that sat steps out shows its last frame;
+ * under SVO_MEM_DEVICE_BORROW level 0 and the right image are the caller's buffers, which the validity rule above
+ * keeps alive) or SVO_EXPORT_LAST_KEYFRAMES (the image set and keypoints of the newest keyframe; once it has given its
+ * images back the status is SVO_VIEW_NONE). Queued exactly as svo_submit_export is (seqs == NULL names every slot in
+ * order, n is ignored): the job sees every frame set, restart, load and pose update submitted before it and none
+ * submitted after, only groups that own a named slot get work, no group waits for another, the slot is not changed
+ * (its deferred pose-filter update is flushed first). style and dst are copied; segments and pixels stay valid until
+ * svo_wait, after which everything is delivered. mem: SVO_MEM_HOST or SVO_MEM_DEVICE, of `pixels`.
+ * Rejected with SVO_ERR_INVALID and nothing queued: a slot out of range or named twice; a bad what, mem, plane, level,
+ * pixel or size; markers with RIGHT or with GRAY8; drop_flags bits that are no SVO_IGNORE_* bit; _reserved != 0; NULL
+ * segments; pixels NULL or not 4-byte aligned; a failed ctx, as in svo_submit_images. SVO_ERR_CAPACITY: dst->capacity
+ * < named slots * image_bytes (the bound, so it is checked here).
+ * Host mode: a group renders its named slots densely into a device staging block, made by the group's first host-mode
+ * view job and replaced when outgrown (svo_memory.device_bytes), and copies each run of consecutive named slots out
+ * in one piece. Device mode writes in place and allocates nothing. A ctx that never asks for a view allocates,
+ * launches and copies nothing more. */
+int svo_submit_export_views(svo_ctx *ctx, int what, const int *seqs, int n, const svo_view_style *style,
+                            const svo_view_dst *dst, int mem);
+int svo_export_views(svo_ctx *ctx, int what, const int *seqs, int n, const svo_view_style *style,
+                     const svo_view_dst *dst, int mem);   /* submit + wait */
+/* stage entry of the kernel: n images in the tracker's launch (chunked when the diagnostic SVO_VIEW_TABLE_TILES bounds
+ * the tile table). src[i].image: the gray plane (device memory, any base address, stride >= width; its width x height
+ * is the output's cols x rows); src[i].kps: the set the markers come from, of which kps2d, flags, level_type and color
+ * are read (device, 4-byte aligned; ignored without style->markers). Image i goes to pixels + offset[i] (host array,
+ * >= 0, multiples of 4; pixels: device, 4-byte aligned), rows dense. style->plane is not used and style->level (0 ..
+ * SVO_MAX_PYRAMID_LEVELS - 1) only scales the keypoints. Exactly the images' bytes are written. Complete on return. */
+typedef struct svo_view_src {
+    svo_image     image;
+    svo_keypoints kps;
+} svo_view_src;
+int svo_render_views(svo_handle *h, int n, const svo_view_src *src, const int64_t *offset,
+                     const svo_view_style *style, uint8_t *pixels);
+
 /* ---- snapshots: the sequence state of a slot saved, loaded, moved between ctxs ------------
  * The reference has no checkpoint or resume (a StereoSlam lives and dies with its process). A snapshot is
  * everything the next frame of a slot depends on and everything its getters return, so that a sequence saved

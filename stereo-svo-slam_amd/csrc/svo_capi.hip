@@ -40,6 +40,8 @@ struct svo_handle {
     size_t copy_ws_count = 0;
     DevPtr<uint8_t> map_ws;         // svo_pack_map_points: the tile counts of a call, then the tile table
     size_t map_ws_bytes = 0;
+    DevPtr<ViewTile> view_ws;       // svo_render_views: the tile table
+    size_t view_ws_count = 0;
 };
 
 extern "C" const char* svo_last_error(void) { return svo_error_text; }
@@ -365,6 +367,50 @@ extern "C" int svo_pack_map_points(svo_handle* h, int n_regions, const int32_t* 
     TileTable table{host.data(), reinterpret_cast<MapTile*>(h->map_ws.get() + counts_bytes), chunk, h->stream,
                     [&](const MapTile* d, int m, hipStream_t s) { launch_map(d, m, f, points, tile_counts, counts, s); }};
     for (const MapTile& t : tiles)
+        if (const int rc = table.add(t)) return rc;
+    if (const int rc = table.launch(false)) return rc;
+    HIP_TRY(hipStreamSynchronize(h->stream));          // (the table's upload read `host`)
+    return SVO_OK;
+}
+
+extern "C" int svo_render_views(svo_handle* h, int n, const svo_view_src* src, const int64_t* offset, const svo_view_style* style,
+                                uint8_t* pixels) {
+    CHECK_H(h);
+    if (n < 0 || (n > 0 && (!src || !offset))) return svo_set_error(SVO_ERR_INVALID, "svo_render_views: bad arguments");
+    if (const int rc = view_check_style(style, SVO_MAX_PYRAMID_LEVELS, "svo_render_views")) return rc;
+    if (!pixels || ((uintptr_t)pixels & 3)) return svo_set_error(SVO_ERR_INVALID, "svo_render_views: pixels is NULL or not 4-byte aligned");
+    std::vector<ViewTile> tiles;
+    for (int i = 0; i < n; i++) {
+        const svo_image& im = src[i].image;
+        const svo_keypoints& k = src[i].kps;
+        if (!im.data || im.width < 1 || im.height < 1 || im.stride < im.width || im.width > (1 << 15) || im.height > (1 << 15))
+            return svo_set_error(SVO_ERR_INVALID, "svo_render_views: image %d: a device plane of 1 .. 32768 pixels a side, stride >= width", i);
+        if (offset[i] < 0 || (offset[i] & 3)) return svo_set_error(SVO_ERR_INVALID, "svo_render_views: image %d: offset must be >= 0 and a multiple of 4", i);
+        KpsDev d{};
+        if (style->markers) {
+            if (k.n < 0) return svo_set_error(SVO_ERR_INVALID, "svo_render_views: image %d: n must be >= 0", i);
+            d.kps2d = k.kps2d; d.flags = k.flags; d.level_type = k.level_type; d.color = k.color;
+            for (const void* p : {(const void*)d.kps2d, (const void*)d.flags, (const void*)d.level_type, (const void*)d.color})
+                if ((k.n > 0 && !p) || ((uintptr_t)p & 3))
+                    return svo_set_error(SVO_ERR_INVALID, "svo_render_views: image %d: kps2d, flags, level_type and color are device memory, 4-byte aligned", i);
+        }
+        view_tiles(make_view(im), pixels + offset[i], style->markers ? &d : nullptr, k.n, tiles);
+    }
+    if (tiles.empty()) return SVO_OK;
+    // (SVO_VIEW_TABLE_TILES: a smaller table, so that tests reach the chunked launches)
+    const size_t chunk = table_tiles("SVO_VIEW_TABLE_TILES", std::min<size_t>(tiles.size(), (size_t)INT_MAX));
+    if (chunk > h->view_ws_count) {
+        HIP_TRY(hipStreamSynchronize(h->stream));      // (the old table may still be read)
+        h->view_ws.reset();
+        h->view_ws_count = 0;
+        HIP_TRY(dev_malloc(h->view_ws, sizeof(ViewTile) * chunk));
+        h->view_ws_count = chunk;
+    }
+    const ViewParams params = view_params(*style);
+    std::vector<ViewTile> host(chunk);
+    TileTable table{host.data(), h->view_ws.get(), chunk, h->stream,
+                    [&](const ViewTile* d, int m, hipStream_t s) { launch_view(d, m, params, s); }};
+    for (const ViewTile& t : tiles)
         if (const int rc = table.add(t)) return rc;
     if (const int rc = table.launch(false)) return rc;
     HIP_TRY(hipStreamSynchronize(h->stream));          // (the table's upload read `host`)

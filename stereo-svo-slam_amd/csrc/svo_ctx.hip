@@ -29,7 +29,7 @@
 // single-workgroup-per-sequence alignment kernel of one group overlaps the window kernels of
 // the other. svo_submit_images() queues a frame set on every group and returns;
 // svo_wait() drains the queues. svo_new_images() = submit + wait. Restarts (svo_ctx_restart_sequences),
-// exports (svo_submit_export, svo_submit_export_map), saves and loads (svo_submit_save / svo_submit_load) and pose-filter updates
+// exports (svo_submit_export, svo_submit_export_map, svo_submit_export_views), saves and loads (svo_submit_save / svo_submit_load) and pose-filter updates
 // (svo_submit_pose_updates) are entries of the same queues, so they are ordered with the frame sets.
 struct svo_ctx {
     // the group's share of an svo_submit_export: its named slots (indices in the group) in named order, the
@@ -49,6 +49,14 @@ struct svo_ctx {
         svo_map_filter filter{};
         svo_map_dst dst{};
     };
+    // the group's share of an svo_submit_export_views: its named slots (indices in the group) in named order and the
+    // segment (and image) of the job each one fills
+    struct ViewExport {
+        int what = 0, mem = 0;
+        std::vector<int> seqs, seg;
+        svo_view_style style{};
+        svo_view_dst dst{};
+    };
     // the group's share of an svo_submit_save (snaps) or svo_submit_load (loads): its named slots, indices in the group
     struct Snapshots {
         int mem = 0;
@@ -65,7 +73,7 @@ struct svo_ctx {
     };
     // one entry of a group's queue: a frame set, or (restart non-empty) the end of some of its sequences, or
     // (exp.seqs non-empty) an export, or (snap.seqs / snap.loads non-empty) a save / a load, or (pose.seqs non-empty)
-    // pose-filter updates, or (map.seqs non-empty) a map export
+    // pose-filter updates, or (map.seqs non-empty) a map export, or (view.seqs non-empty) a view job
     struct Job {
         std::vector<const uint8_t*> left, right;
         std::vector<float> ts;
@@ -75,6 +83,7 @@ struct svo_ctx {
         Snapshots snap;
         PoseUpdates pose;
         MapExport map;
+        ViewExport view;
     };
     struct Worker {
         Group g;
@@ -111,7 +120,10 @@ void worker_run_job(svo_ctx::Worker& w, const svo_ctx::Job& job) {
     const svo_ctx::Snapshots& sn = job.snap;
     const svo_ctx::PoseUpdates& pu = job.pose;
     const svo_ctx::MapExport& mp = job.map;
-    const int rc = !mp.seqs.empty()
+    const svo_ctx::ViewExport& vw = job.view;
+    const int rc = !vw.seqs.empty()
+                       ? grp_export_views(w.g.get(), vw.what, vw.mem, vw.seqs.data(), vw.seg.data(), (int)vw.seqs.size(), w.first, &vw.style, &vw.dst)
+                   : !mp.seqs.empty()
                        ? grp_export_map(w.g.get(), mp.mem, mp.seqs.data(), mp.seg.data(), mp.regions.data(), (int)mp.seqs.size(), w.first, &mp.filter, &mp.dst)
                    : !pu.seqs.empty()
                        ? grp_pose_updates(w.g.get(), pu.seqs.data(), pu.counts.data(), (int)pu.seqs.size(), pu.samples.data(), pu.filtered.data())
@@ -411,6 +423,49 @@ extern "C" int svo_submit_export_map(svo_ctx* c, const int* seqs, int n, const s
 extern "C" int svo_export_map(svo_ctx* c, const int* seqs, int n, const svo_map_region* regions, const svo_map_filter* filter,
                               const svo_map_dst* dst, int mem) {
     const int rc = svo_submit_export_map(c, seqs, n, regions, filter, dst, mem);
+    return rc ? rc : svo_wait(c);
+}
+
+extern "C" int svo_submit_export_views(svo_ctx* c, int what, const int* seqs, int n, const svo_view_style* style,
+                                       const svo_view_dst* dst, int mem) {
+    if (!c || !dst || !dst->segments || (what != SVO_EXPORT_FRAMES && what != SVO_EXPORT_LAST_KEYFRAMES) ||
+        (mem != SVO_MEM_HOST && mem != SVO_MEM_DEVICE) || (seqs && n < 0))
+        return svo_set_error(SVO_ERR_INVALID, "svo_submit_export_views: bad arguments (what %d, mem %d)", what, mem);
+    const svo_group* g0 = c->workers[0]->g.get();                    // (every group has the same settings)
+    if (const int rc = grp_check_view_style(g0, style)) return rc;
+    if (!dst->pixels || ((uintptr_t)dst->pixels & 3))
+        return svo_set_error(SVO_ERR_INVALID, "svo_submit_export_views: pixels is NULL or not 4-byte aligned");
+    if (!seqs) n = c->B;
+    std::vector<char> named(c->B, 0);
+    for (int i = 0; i < n; i++) {
+        const int s = seqs ? seqs[i] : i;
+        if (s < 0 || s >= c->B || named[s])
+            return svo_set_error(SVO_ERR_INVALID, "svo_submit_export_views: sequence %d is out of range or named twice", s);
+        named[s] = 1;
+    }
+    const int64_t image_bytes = grp_view_bytes(g0, style);
+    if (dst->capacity < n * image_bytes)
+        return svo_set_error(SVO_ERR_CAPACITY, "svo_submit_export_views: %d slots need %lld bytes, capacity %lld", n,
+                             (long long)(n * image_bytes), (long long)dst->capacity);
+    if (c->failed.load()) return reject_failed(c, "svo_submit_export_views");
+    for (auto& wp : c->workers) {
+        svo_ctx::Worker& w = *wp;
+        svo_ctx::Job job;
+        svo_ctx::ViewExport& e = job.view;
+        for (int i = 0; i < n; i++) {
+            const int s = seqs ? seqs[i] : i;
+            if (s >= w.first && s < w.first + w.count) { e.seqs.push_back(s - w.first); e.seg.push_back(i); }
+        }
+        if (e.seqs.empty()) continue;
+        e.what = what; e.mem = mem; e.style = *style; e.dst = *dst;
+        worker_submit(w, std::move(job));
+    }
+    return SVO_OK;
+}
+
+extern "C" int svo_export_views(svo_ctx* c, int what, const int* seqs, int n, const svo_view_style* style,
+                                const svo_view_dst* dst, int mem) {
+    const int rc = svo_submit_export_views(c, what, seqs, n, style, dst, mem);
     return rc ? rc : svo_wait(c);
 }
 

@@ -1,6 +1,6 @@
 // svo_group.hpp — one group of sequences as svo_ctx.hip drives it: the opaque interface of svo_group.hip (creation,
 // settings, restarts), svo_group_step.hip (grp_new_images), svo_group_export.hip (grp_export, grp_capacity),
-// svo_group_map.hip (grp_export_map, grp_map_size),
+// svo_group_map.hip (grp_export_map, grp_map_size), svo_group_view.hip (grp_export_views, grp_view_bytes),
 // svo_group_snapshot.hip (grp_check_snapshot, grp_save, grp_load, grp_snapshot_size) and svo_group_pose.hip
 // (grp_pose_updates).
 #pragma once
@@ -35,6 +35,16 @@ int grp_export(svo_group* g, int what, int mem, const int* seqs, const int* seg,
 // regions[i] says (host or device points: mem). Delivered on return. A failed group rejects it.
 int grp_export_map(svo_group* g, int mem, const int* seqs, const int* seg, const svo_map_region* regions, int n, int seq0,
                    const svo_map_filter* filter, const svo_map_dst* dst);
+// One group's share of svo_submit_export_views (svo_group_view.hip), between two steps of the group, on the thread that
+// drives it: slot seqs[i] (index in the group; ctx slot seq0 + seqs[i]) fills dst->segments[seg[i]] and its image goes
+// to byte seg[i] * image_bytes of dst->pixels (host or device memory: mem). style: checked (grp_check_view_style).
+// Delivered on return. A failed group rejects it.
+int grp_export_views(svo_group* g, int what, int mem, const int* seqs, const int* seg, int n, int seq0,
+                     const svo_view_style* style, const svo_view_dst* dst);
+// what svo_submit_export_views checks of a style, and the image_bytes of a checked one (they read only what never
+// changes in a group)
+int grp_check_view_style(const svo_group* g, const svo_view_style* style);
+int64_t grp_view_bytes(const svo_group* g, const svo_view_style* style);
 // what svo_map_size reports of a slot (the queues have drained)
 void grp_map_size(const svo_group* g, int seq, int from_keyframe, int* keyframes, int64_t* points_bound);
 // Snapshots (svo_submit_save / svo_submit_load). grp_check_snapshot: everything svo_submit_load checks of one

@@ -1,6 +1,7 @@
 // svo_group_state.hpp — the state of one sequence group, internal to the group: only its translation units
 // (svo_group.hip: storage, creation, settings, the end of a sequence; svo_group_step.hip: the step;
-// svo_group_export.hip: the bulk export; svo_group_map.hip: the map export; svo_group_snapshot.hip: save and load;
+// svo_group_export.hip: the bulk export; svo_group_map.hip: the map export; svo_group_view.hip: the views;
+// svo_group_snapshot.hip: save and load;
 // svo_group_pose.hip: the batched pose-filter updates) and the per-sequence getters of
 // svo_ctx.hip include it. Everyone else drives a group through the opaque interface of svo_group.hpp.
 //
@@ -282,6 +283,9 @@ struct svo_group {
     int* d_map_counts = nullptr; size_t map_counts = 0;
     svo::PinnedPtr<int> map_counts_host;
     svo_map_point* d_map_points = nullptr; size_t map_points = 0;
+    // views (grp_export_views) in host mode: the images of one job, made by the first such job and replaced when
+    // outgrown
+    uint8_t* d_view = nullptr; size_t view_bytes = 0;
     // batched pose-filter updates (grp_pose_updates): the upload block (samples | filter states | start poses |
     // sample offsets) and behind it the download block (filter states | filtered poses) of one job, device and pinned,
     // made by the first such job and replaced when outgrown

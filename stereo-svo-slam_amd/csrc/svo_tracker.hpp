@@ -167,6 +167,36 @@ void cut_copy_tiles(const void* src, void* dst, int64_t row_bytes, int64_t rows,
                     std::vector<CopyTile>& out);
 void launch_copy_tiles(const CopyTile* d_tiles, int n_tiles, hipStream_t stream);
 
+// ------------------------------------------------------------ views (view.hip)
+// One tile of an output image: at most VIEW_TILE_W x VIEW_TILE_H pixels at (x0, y0) of a w x h image, one
+// workgroup. src: the gray plane (any base, src_stride >= w); dst: the image, rows dense (w * bytes per pixel);
+// the four keypoint planes of the set the markers come from (n = 0: none, the planes may be null).
+constexpr int VIEW_TILE_W = 64, VIEW_TILE_H = 16;
+struct ViewTile {
+    const uint8_t* src;
+    uint8_t* dst;
+    const svo_kp2d* kps2d;
+    const uint32_t* flags;
+    const int* level_type;
+    const uint32_t* color;
+    int src_stride, w, h;
+    int x0, y0;
+    int n;
+};
+// what a launch draws, from a checked svo_view_style: bytes per pixel, and per marker size (0: size, 1:
+// size_temporary) the half extents of a cross (s / 2) and of a square ((int)(s * 0.8) / 2)
+struct ViewParams {
+    int level, bpp, markers;
+    uint32_t drop_flags;
+    int half_cross[2], half_square[2];
+};
+// what a view job and the stage entry check of a style alike (levels: 0 .. max_levels - 1 of the left plane)
+int view_check_style(const svo_view_style* style, int max_levels, const char* who);
+ViewParams view_params(const svo_view_style& style);
+// the tiles of one image, appended to `out` (kps null: no markers)
+void view_tiles(const ImgView& src, uint8_t* dst, const KpsDev* kps, int n, std::vector<ViewTile>& out);
+void launch_view(const ViewTile* d_tiles, int n_tiles, const ViewParams& p, hipStream_t stream);
+
 // ------------------------------------------------------------ batched pose filter (pose_filter.hip)
 // n_states filter states, one lane each, POSE_FILTER_LANES per workgroup. State b runs samples
 // [first[b], first[b + 1]) (clamped to [0, n_samples)) in order; a state without samples is neither read nor written.

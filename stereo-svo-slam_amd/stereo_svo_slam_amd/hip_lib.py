@@ -40,6 +40,7 @@ SYMBOLS = (
     "svo_reproj_gn_batch", "svo_filter_update_batch", "svo_sparse_align_batch",
     "svo_submit_pose_updates", "svo_update_poses", "svo_pose_filter_batch",
     "svo_map_size", "svo_submit_export_map", "svo_export_map", "svo_pack_map_points",
+    "svo_view_size", "svo_submit_export_views", "svo_export_views", "svo_render_views",
 )
 
 # svo_ctx_set_input_format / svo_convert_frames: how the buffers of a sequence become its two gray images
@@ -149,11 +150,65 @@ def map_filter(f):
     return f if isinstance(f, MapFilter) else MapFilter(**f)
 
 
+# views (svo_submit_export_views, include/svo_hip.h): the plane, the pixel format, a segment (one per named slot)
+PLANE_LEFT, PLANE_RIGHT = 0, 1
+PLANES = ("left", "right")
+PIXEL_GRAY8, PIXEL_RGB8, PIXEL_RGBA8 = 0, 1, 2
+PIXELS = ("gray8", "rgb8", "rgba8")
+PIXEL_BYTES = (1, 3, 4)
+VIEW_OK, VIEW_NONE = 0, 1
+VIEW_SEGMENT_DTYPE = np.dtype([("seq", "<i4"), ("run", "<i4"), ("frame_id", "<i4"), ("keyframe_id", "<i4"),
+                               ("status", "<i4"), ("n", "<i4"), ("offset", "<i8"), ("pose", "<f4", (6,)),
+                               ("time_stamp", "<f4"), ("_pad", "<i4")])
+assert VIEW_SEGMENT_DTYPE.itemsize == 64
+
+
+class ViewStyle(C.Structure):
+    """svo_view_style (include/svo_hip.h): what one view job draws."""
+    _fields_ = [("plane", C.c_int32), ("level", C.c_int32), ("pixel", C.c_int32), ("markers", C.c_int32),
+                ("drop_flags", C.c_uint32), ("size", C.c_int32), ("size_temporary", C.c_int32),
+                ("_reserved", C.c_int32)]
+
+
+class ViewDst(C.Structure):
+    """svo_view_dst (include/svo_hip.h)."""
+    _fields_ = [("segments", C.c_void_p), ("pixels", C.c_void_p), ("capacity", C.c_int64)]
+
+
+def view_style(what=EXPORT_FRAMES, plane=PLANE_LEFT, level=0, pixel=PIXEL_GRAY8, markers=False, drop_flags=None,
+               size=None, size_temporary=None):
+    """a ViewStyle; plane and pixel may be names (PLANES, PIXELS). The defaults of the marker fields follow the
+    reference app's window: a frame drops IGNORE_COMPLETELY keypoints and draws 20 / 10 (10 with IGNORE_TEMPORARY),
+    a keyframe drops nothing and draws 10 / 10."""
+    if isinstance(plane, str):
+        plane = PLANES.index(plane)
+    if isinstance(pixel, str):
+        pixel = PIXELS.index(pixel)
+    frames = int(what) == EXPORT_FRAMES
+    return ViewStyle(int(plane), int(level), int(pixel), int(bool(markers)),
+                     (IGNORE_COMPLETELY if frames else 0) if drop_flags is None else int(drop_flags),
+                     (20 if frames else 10) if size is None else int(size),
+                     10 if size_temporary is None else int(size_temporary), 0)
+
+
+def view_size(cam, width, height, style):
+    """svo_view_size (host only): (cols, rows, pitch, image_bytes) of one image of a view job with `style`."""
+    cols, rows, pitch, nbytes = C.c_int(0), C.c_int(0), C.c_int64(0), C.c_int64(0)
+    _check(lib().svo_view_size(C.byref(cam), int(width), int(height), C.byref(style), C.byref(cols), C.byref(rows),
+                               C.byref(pitch), C.byref(nbytes)))
+    return cols.value, rows.value, pitch.value, nbytes.value
+
+
 class Keypoints(C.Structure):
     """svo_keypoints (include/svo_types.h): an SoA keypoint set, views onto device memory."""
     _fields_ = [("n", C.c_int32)] + [(name, C.c_void_p) for name in (
         "kps2d", "kps3d", "flags", "keyframe_id", "keypoint_index", "outlier_count", "inlier_count",
         "kf_inv_depth", "kf_variance", "score", "level_type", "color")]
+
+
+class ViewSrc(C.Structure):
+    """svo_view_src (include/svo_hip.h): one image of svo_render_views."""
+    _fields_ = [("image", Image), ("kps", Keypoints)]
 
 
 class SnapshotInfo(C.Structure):
@@ -399,6 +454,23 @@ class Handle:
         firsts = (C.c_int64 * max(len(regions), 1))(*[int(f) for f in first])
         _check(lib().svo_pack_map_points(self._h, len(regions), begin, arr, own, firsts, C.byref(map_filter(filter)),
                                          _ptr(points), _ptr(counts)))
+
+    def render_views(self, srcs, offsets, style, pixels):
+        """svo_render_views: gray planes as images of `style` (a ViewStyle) with a marker per keypoint. srcs: per
+        image ((data address or uint8 device tensor [H, W]), width, height, stride) and (n, {field of svo_keypoints:
+        device tensor or raw device address}) or None; offsets[i]: the byte of `pixels` (a uint8 device tensor, or a
+        raw device address) image i starts at. Complete on return."""
+        arr = (ViewSrc * max(len(srcs), 1))()
+        for i, (img, kps) in enumerate(srcs):
+            data, w, h, stride = img
+            arr[i].image = Image(data.data_ptr() if isinstance(data, torch.Tensor) else int(data), int(w), int(h), int(stride))
+            if kps is not None:
+                arr[i].kps.n = int(kps[0])
+                for name, v in kps[1].items():
+                    setattr(arr[i].kps, name, v.data_ptr() if isinstance(v, torch.Tensor) else int(v))
+        offs = (C.c_int64 * max(len(srcs), 1))(*[int(o) for o in offsets])
+        p = pixels.data_ptr() if isinstance(pixels, torch.Tensor) else int(pixels)
+        _check(lib().svo_render_views(self._h, len(srcs), arr, offs, C.byref(style), C.c_void_p(p)))
 
     def copy_segments(self, segs):
         """svo_copy_segments: 2-D byte segments, device to device. segs: (src address, dst address, row_bytes,

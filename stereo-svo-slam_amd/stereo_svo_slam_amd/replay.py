@@ -12,12 +12,17 @@ Host bookkeeping only; every frame goes through StereoSlam.new_image (libsvo_hip
     python -m stereo_svo_slam_amd.replay --settings Blender.yaml --sbs 'frames/%06d.png' --gpu-ingest
     python -m stereo_svo_slam_amd.replay --settings Econ.yaml --interleaved 'frames/%06d.png' --gpu-ingest
     python -m stereo_svo_slam_amd.replay --settings EuRoC.yaml --pairs 'seq/%06d_left.png,seq/%06d_right.png'
+    python -m stereo_svo_slam_amd.replay --synthetic tiny --frames 20 --dump-views views/
 
 Inputs follow the reference's conventions (the library's `left` is the physically RIGHT camera):
 EurocInput (src/app/euroc_input.cpp:48-70,100-105), VideoInput (src/app/video_input.cpp:29-36), EconInput
 (src/app/econ_input.cpp:102-106). Colour frames become gray with cvtColor's arithmetic (bgr2gray), on the host or,
 with --gpu-ingest, inside the library from the raw frame (svo_ctx_set_input_format): both give the same CSV, and
 frames that are gray already give the CSV they gave before colour frames were converted this way.
+--dump-views DIR writes per frame the two halves of the reference app's window (draw_frame, src/app/main.cpp:40-118)
+as binary PPM files, DIR/000000_keyframe.ppm (the last keyframe, a marker per keypoint) and DIR/000000_frame.ppm (the
+current frame): the gray image the tracker worked on, which with --gpu-rectify / --gpu-ingest only the GPU has seen.
+The text overlay and the x2 resize of the window are not drawn.
 With $SVO_DATA set (a EuRoC `mav0/` directory, or a directory of side-by-side frames) and no
 explicit input that data is used; otherwise the seeded synthetic sequence.
 """
@@ -317,17 +322,41 @@ def error_report(test_rows, reference_rows):
     return dict(max=d.max(0)[1:].tolist(), mean=d.mean(0)[1:].tolist(), fps=fps_from_csv_rows(t))
 
 
+def write_ppm(path, img):
+    """a uint8 [H, W, 3] R, G, B image as a binary PPM (P6)"""
+    img = np.ascontiguousarray(img, np.uint8)
+    assert img.ndim == 3 and img.shape[2] == 3
+    with open(path, "wb") as fh:
+        fh.write(b"P6\n%d %d\n255\n" % (img.shape[1], img.shape[0]))
+        fh.write(img.tobytes())
+
+
+def read_ppm(path):
+    """a binary PPM (P6, maxval 255, as write_ppm writes it) as uint8 [H, W, 3]"""
+    with open(path, "rb") as fh:
+        raw = fh.read()
+    magic, dims, maxval, body = raw.split(b"\n", 3)
+    w, h = (int(v) for v in dims.split())
+    assert magic == b"P6" and maxval == b"255" and len(body) == w * h * 3
+    return np.frombuffer(body, np.uint8).reshape(h, w, 3)
+
+
 class Replay:
     """process_image loop: only the time inside new_image is accumulated (slam_app.cpp:186-190)."""
 
     def __init__(self, settings, device=0, time_trace=False, fast=False, rectify_maps=None, input_format=None,
-                 gpu_imu=False):
+                 gpu_imu=False, dump_views=None):
         """fast=False keeps the library default: the reference-order Gauss-Newton (bit-exact traces).
         rectify_maps = (left maps, right maps): the frames fed are raw and are rectified on the GPU.
         input_format: the frames fed are raw buffers of that format (StereoSlam.set_input_format).
         gpu_imu: update_pose_from_imu is one svo_update_poses (the filter kernel) instead of a loop of
-        svo_update_pose calls: the same bits."""
+        svo_update_pose calls: the same bits.
+        dump_views: a directory that receives, per frame, the last keyframe and the current frame with a marker per
+        keypoint as the reference app's window shows them (write_ppm), outside the timed region."""
         self.settings = settings
+        self.dump_views = dump_views
+        if dump_views:
+            os.makedirs(dump_views, exist_ok=True)
         self.gpu_imu = gpu_imu
         self.slam = StereoSlam(settings, device=device)
         if fast:
@@ -374,6 +403,12 @@ class Replay:
         self.slam.new_image(left, right, time_stamp)
         self._t += time.perf_counter() - t0
         self.cumulative.append(self._t)
+        if self.dump_views:
+            k = len(self.cumulative) - 1
+            for what, name in (("last_keyframes", "keyframe"), ("frames", "frame")):
+                img = self.slam.get_image(what, pixel="rgb8", markers=True)
+                if img is not None:
+                    write_ppm(os.path.join(self.dump_views, f"{k:06d}_{name}.ppm"), img)
         if self.time_trace:                       # like PRINT_TIME_TRACE of the reference
             print("\n".join(time_trace_lines(self.slam.stats())))
 
@@ -410,6 +445,9 @@ def main(argv=None):
                                    "order: the samples of frame k feed the pose filter before frame k (update_pose_from_imu)")
     ap.add_argument("--gpu-imu", action="store_true",
                     help="--gyro: one svo_update_poses per frame interval (the filter kernel) instead of one svo_update_pose per sample")
+    ap.add_argument("--dump-views", metavar="DIR",
+                    help="write per frame DIR/NNNNNN_keyframe.ppm and DIR/NNNNNN_frame.ppm: the last keyframe and the current "
+                         "frame as the reference app's window draws them (gray as RGB, a marker per keypoint)")
     ap.add_argument("--frames", type=int, default=100)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--rate", type=float, default=20.0, help="frames per second of the time stamps")
@@ -459,7 +497,8 @@ def main(argv=None):
     if args.gpu_imu and not args.gyro:
         ap.error("--gpu-imu needs --gyro")
     gyro = np.loadtxt(args.gyro, ndmin=2) if args.gyro else None
-    rp = Replay(settings, args.device, args.time_trace, args.fast, rectify_maps=rect, input_format=fmt, gpu_imu=args.gpu_imu)
+    rp = Replay(settings, args.device, args.time_trace, args.fast, rectify_maps=rect, input_format=fmt, gpu_imu=args.gpu_imu,
+                dump_views=args.dump_views)
     for k, (left, right, t) in enumerate(frames):
         rp.feed(left, right, t, None if gyro is None else gyro[gyro[:, 0] == k, 1:4])
     rows = rp.rows()

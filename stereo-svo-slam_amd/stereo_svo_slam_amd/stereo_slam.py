@@ -269,6 +269,56 @@ class MapExport:
         return self._records(int(kf["first"]), int(kf["n"]))
 
 
+class Views:
+    """One svo_submit_export_views: owns the buffers the library writes. After wait(): `segments`
+    (hip_lib.VIEW_SEGMENT_DTYPE, one per named slot) and image(i); `pixels` is the whole buffer, a numpy uint8 view of
+    pinned memory in host mode, a torch uint8 tensor on the ctx's device in device mode. cols, rows, pitch,
+    image_bytes: the shape of every image of the job (svo_view_size); channels: 1, 3 or 4."""
+
+    def __init__(self, slam, what, seqs, style, device):
+        self._slam = slam
+        self.what, self.style, self.device_mode = int(what), style, bool(device)
+        self.seqs = None if seqs is None else [int(s) for s in seqs]
+        n = self._n = slam.n if seqs is None else len(self.seqs)
+        self.cols, self.rows, self.pitch, self.image_bytes = slam.view_size(style)
+        self.channels = hip_lib.PIXEL_BYTES[style.pixel]
+        self.capacity = n * self.image_bytes
+        self._seg = np.zeros(max(n, 1), hip_lib.VIEW_SEGMENT_DTYPE)
+        self.segments = self._seg[:n]
+        self._buf = (torch.zeros(max(self.capacity, 4), dtype=torch.uint8, device=slam.device) if device
+                     else torch.zeros(max(self.capacity, 4), dtype=torch.uint8, pin_memory=True))
+        self._dst = hip_lib.ViewDst(self._seg.ctypes.data, self._buf.data_ptr(), self.capacity)
+        self._seq_arr = None if seqs is None else (C.c_int * max(n, 1))(*self.seqs)
+
+    @property
+    def pixels(self):
+        return self._buf if self.device_mode else self._buf.numpy()
+
+    def submit(self):
+        """queue the job (again: the same slots into the same buffers, once the previous one is delivered)"""
+        slam = self._slam
+        if self.device_mode:
+            torch.cuda.current_stream(slam.device).synchronize()     # (nothing of the caller's is still using the tensor)
+        _check(lib().svo_submit_export_views(slam._ctx, self.what, self._seq_arr, self._n, C.byref(self.style),
+                                             C.byref(self._dst), hip_lib.MEM_DEVICE if self.device_mode else hip_lib.MEM_HOST))
+        return self
+
+    def wait(self):
+        self._slam.wait()
+        return self
+
+    def image(self, i):
+        """the image of named slot i: [rows, cols] (gray8) or [rows, cols, 3 | 4], a view of `pixels` (numpy in host
+        mode, a torch tensor in device mode); None for a slot whose status is VIEW_NONE"""
+        e = self.segments[i]
+        if int(e["status"]) != hip_lib.VIEW_OK:
+            return None
+        lo = int(e["offset"])
+        a = self.pixels[lo:lo + self.rows * self.pitch]
+        shape = (self.rows, self.cols) + ((self.channels,) if self.channels > 1 else ())
+        return a.reshape(shape)
+
+
 class Snapshot:
     """The sequence state of one slot (svo_submit_save / svo_submit_load): `host` (numpy uint8, the host part) and
     `data` (the data part: numpy uint8, or a torch uint8 tensor on the ctx's device in device mode). Valid after
@@ -540,6 +590,28 @@ class StereoSlamBatch:
             m.submit().wait()
         return m
 
+    def view_size(self, style):
+        """svo_view_size: (cols, rows, pitch, image_bytes) of one image of a view job with `style` in this ctx"""
+        return hip_lib.view_size(self.cam, self.width, self.height, style)
+
+    def submit_views(self, what="frames", seqs=None, plane="left", level=0, pixel="gray8", markers=False,
+                     drop_flags=None, size=None, size_temporary=None, device=False, style=None):
+        """svo_submit_export_views: queue a view of the current frames (what="frames") or newest keyframes
+        ("last_keyframes") of the slots `seqs` (None: all, in order) behind what was submitted so far; nothing is
+        waited for. plane "left" (level 0 .. max_pyramid_levels - 1) or "right"; pixel "gray8", "rgb8" or "rgba8";
+        markers: one marker per keypoint as the reference app's window draws them (hip_lib.view_style has the
+        defaults of drop_flags and the two sizes); style: a hip_lib.ViewStyle instead of all these. Returns a Views,
+        valid after its wait() (or the ctx's); its submit() queues the same job again into the same buffers."""
+        if isinstance(what, str):
+            what = hip_lib.EXPORT_WHAT.index(what)
+        if style is None:
+            style = hip_lib.view_style(what, plane, level, pixel, markers, drop_flags, size, size_temporary)
+        return Views(self, what, seqs, style, device).submit()
+
+    def export_views(self, what="frames", seqs=None, **kw):
+        """submit_views + wait"""
+        return self.submit_views(what, seqs, **kw).wait()
+
     def snapshot_size(self, seq):
         """svo_snapshot_size: (host_bytes, data_bytes) a save of the slot needs right now (waits)."""
         hb, db = C.c_int64(0), C.c_int64(0)
@@ -786,3 +858,12 @@ class StereoSlam(StereoSlamBatch):
             if getattr(self, "_rect", None) is not None:
                 self._apply_rectification()
         self.new_images([left], [right], [time_stamp])
+
+    def get_image(self, what="frames", **kw):
+        """the image of the current frame (or, what="last_keyframes", of the newest keyframe) as a numpy array
+        (export_views of the one slot: plane, level, pixel, markers, ...); None when there is none"""
+        if self._ctx is None:
+            return None
+        kw["device"] = False
+        img = self.export_views(what, None, **kw).image(0)
+        return None if img is None else img.copy()
