@@ -625,6 +625,156 @@ typedef struct svo_view_src {
 int svo_render_views(svo_handle *h, int n, const svo_view_src *src, const int64_t *offset,
                      const svo_view_style *style, uint8_t *pixels);
 
+/* ---- scene: the viewer's 3-D picture of the maps of many slots in one queued job ------------
+ * The reference's second window is its 3-D viewer (src/qt-viewer/PointCloudViewer.qml, src/python/pointcloudviewer.py):
+ * every keyframe's points as depth-tested squares of fixed size on white, the trajectory as a red line strip, a blue
+ * wire frustum per keyframe and a green one at the current pose, seen through a perspective camera with front / top /
+ * side presets. A scene job is that picture for many slots: the groups that own a named slot render one image per
+ * slot with one kernel launch each (scene.hip) from the keyframe planes on the device and from line records the host
+ * builds from the trajectory and the poses, and deliver it into host or device memory; the host writes one
+ * svo_scene_segment per named slot.
+ *
+ * The picture is the project's own statement of the viewer's scene, not GL's rasteriser (which is not specified to
+ * the bit). All arithmetic is float32 in the order written, without contraction; integer parts are exact.
+ *   camera   svo_scene_camera: V = view[12], the rows of a 3x4 world -> camera matrix (camera frame as the tracker's:
+ *            x right, y down, z forward), and f, cx, cy, near
+ *   T(x,y,z) c_k = ((V[4k] * x + V[4k+1] * y) + V[4k+2] * z) + V[4k+3],  k = 0, 1, 2
+ *   point    (class 3) dropped unless every c_k is finite and c_2 >= near.  u = (f * c_0) / c_2 + cx,
+ *            v = (f * c_1) / c_2 + cy; dropped unless |u| < 2^15 and |v| < 2^15.  px = floor(u), py = floor(v); it
+ *            covers the s x s pixels [px - (s-1)/2, px - (s-1)/2 + s - 1] x [py - (s-1)/2, py - (s-1)/2 + s - 1]
+ *            (integer division), s = point_size; its depth is c_2, its colour the keypoint's r, g, b (the QML swaps r
+ *            and b; that quirk is not restated)
+ *   line     A -> B (classes 0 .. 2), a = T(A), b = T(B): dropped if any coordinate is not finite or both a_2 and
+ *            b_2 < near. If exactly one end, say a, has a_2 < near: t = (near - a_2) / (b_2 - a_2),
+ *            a_k := a_k + t * (b_k - a_k) for k = 0, 1, a_2 := near (the same with the roles swapped when b is the
+ *            near end); dropped if the result is not finite. Both ends are projected as a point is; the line is
+ *            dropped if either end fails the 2^15 rule. X = floor(u), Y = floor(v), dx = X1 - X0, dy = Y1 - Y0,
+ *            n = max(|dx|, |dy|). Pixel i = 0 .. n is (X0 + rdiv(i * dx, n), Y0 + rdiv(i * dy, n)) with
+ *            rdiv(p, n) = floor((2 p + n) / (2 n)) in int64; n = 0: the single pixel (X0, Y0). Its depth is
+ *            z_i = z0 + (z1 - z0) * ((float)i / (float)n), z0 for n = 0: linear on the screen, NOT
+ *            perspective-correct. One pixel wide.
+ *   pixel    every element that covers it offers the 64-bit key  bits(depth) << 32 | cls << 24 | r << 16 | g << 8 | b;
+ *            the pixel shows r, g, b of the SMALLEST key: the nearest element wins; at equal depth a line beats a
+ *            point and the current-pose frustum beats everything; inside a class the smaller colour word wins. The
+ *            result depends on no drawing order and two runs give the same bytes. A pixel nobody covers shows
+ *            `background`; the fourth byte of RGBA is 255. Pixels outside the image are dropped.
+ * Elements of a slot, each drawn only if its bit of style.show is set:
+ *   POINTS      the keypoints of keyframes from_keyframe .. that pass style.filter (a svo_map_filter, with exactly
+ *               the meaning map export gives it)
+ *   TRAJECTORY  class 2, trajectory_rgb: the lines between consecutive positions of svo_get_trajectory;
+ *               trajectory_tail = k > 0 draws the newest k poses only (k - 1 lines)
+ *   KEYFRAMES   class 1, keyframe_rgb: a frustum per keyframe from from_keyframe on
+ *   POSE        class 0, pose_rgb: a frustum at svo_get_pose
+ * Frustum of a pose (t, r): camera-frame vertices 0, (-w, h, d), (-w, -h, d), (w, -h, d), (w, h, d); the 8 edges of
+ * the QML's index buffer (0-1, 0-2, 0-3, 0-4, 1-2, 2-3, 3-4, 4-1); w, h, d from the style (the viewer: 0.1, 0.08,
+ * 0.07). World vertex: ((R[3k] * vx + R[3k+1] * vy) + R[3k+2] * vz) + t_k, R the float `rot` of
+ * PoseManager::set_pose (Rodrigues in double with the sin / cos of svo_libm.h, rounded to float). The QML orients
+ * its frusta with fromEulerAngles; the tracker's Rodrigues is used instead.
+ * Layout, as for the views: rows are dense, pitch = cols * bytes per pixel; image_bytes = rows * pitch rounded up to
+ * a multiple of 256; named slot i of a job goes to offset = i * image_bytes of dst->pixels; of a slot exactly
+ * rows * pitch bytes are written; a slot whose status is SVO_SCENE_NONE writes only its segment.
+ * Not drawn: text, anti-aliasing, line widths; there is no orbit controller and no fitting of the camera to a map. */
+enum { SVO_SCENE_POINTS = 1, SVO_SCENE_TRAJECTORY = 2, SVO_SCENE_KEYFRAMES = 4, SVO_SCENE_POSE = 8 };   /* style.show */
+enum { SVO_SCENE_CLASS_POSE = 0, SVO_SCENE_CLASS_KEYFRAME = 1, SVO_SCENE_CLASS_TRAJECTORY = 2, SVO_SCENE_CLASS_POINT = 3 };
+enum { SVO_SCENE_OK = 0,
+       SVO_SCENE_NONE = 1 };          /* an empty slot */
+
+typedef struct svo_scene_camera {     /* 64 bytes */
+    float view[12];                   /* rows of the 3x4 world -> camera matrix                              */
+    float f, cx, cy;                  /* focal length and principal point, pixels                            */
+    float near;                       /* elements nearer than this are dropped / clipped                     */
+} svo_scene_camera;                   /* rejected: an entry that is not finite, f <= 0, near <= 0            */
+
+typedef struct svo_scene_style {      /* what one job draws; copied at submit                                */
+    int32_t  cols, rows;              /* of every image: 1 .. 4096                                           */
+    int32_t  pixel;                   /* SVO_PIXEL_RGB8 or SVO_PIXEL_RGBA8                                   */
+    int32_t  point_size;              /* 1 .. 16                                                             */
+    uint32_t background, trajectory_rgb, keyframe_rgb, pose_rgb;   /* r << 16 | g << 8 | b; the top byte 0   */
+    float    frustum_w, frustum_h, frustum_d;   /* finite                                                   */
+    uint32_t show;                    /* SVO_SCENE_* bits                                                    */
+    int32_t  from_keyframe;           /* >= 0: points and frusta of keyframes from this one on               */
+    int32_t  trajectory_tail;         /* 0: the whole trajectory; k > 0: its newest k poses                  */
+    svo_map_filter filter;            /* which keypoints are points                                          */
+    int32_t  _reserved;               /* 0                                                                   */
+} svo_scene_style;
+
+typedef struct svo_scene_line {       /* 32 bytes: one line of the stage entry                               */
+    float    a[3], b[3];              /* world                                                               */
+    uint32_t cls_rgb;                 /* cls << 24 | r << 16 | g << 8 | b, cls 0 .. 2                        */
+    uint32_t _pad;                    /* 0                                                                   */
+} svo_scene_line;
+
+typedef struct svo_scene_segment {    /* 64 bytes, host, one per named slot                                  */
+    int32_t  seq, run;                /* slot and ordinal of its run (svo_run_info.run)                      */
+    int32_t  frame_id;                /* of the slot's current frame; -1: empty slot                         */
+    uint16_t status;                  /* SVO_SCENE_*                                                         */
+    uint16_t n_keyframes;             /* of the slot when the job ran (a sequence has at most 4096)          */
+    int32_t  from_keyframe;           /* the style's                                                         */
+    int32_t  n_keypoints;             /* keypoints considered: those of keyframes from_keyframe .. (0 without POINTS) */
+    int32_t  n_poses;                 /* trajectory poses drawn (0 without TRAJECTORY)                       */
+    float    time_stamp;              /* of the slot's current frame                                         */
+    int64_t  offset;                  /* the image is bytes [offset, offset + rows * pitch) of dst->pixels   */
+    float    pose[6];                 /* svo_get_pose                                                        */
+} svo_scene_segment;
+
+typedef struct svo_scene_dst {
+    svo_scene_segment *segments;      /* HOST memory always, >= n entries                                    */
+    uint8_t *pixels;                  /* host or device (mem); 4-byte aligned (16-byte aligned: the wide stores) */
+    int64_t capacity;                 /* bytes `pixels` holds                                                */
+} svo_scene_dst;
+
+/* pitch and image_bytes of one image of a job with that style, without a GPU (either may be NULL). A style a job
+ * rejects: SVO_ERR_INVALID */
+int svo_scene_size(const svo_scene_style *style, int64_t *pitch, int64_t *image_bytes);
+/* a camera at `eye` looking at `centre`, without a GPU: z_c = normalize(centre - eye), x_c = normalize(cross(-up,
+ * z_c)), y_c = cross(z_c, x_c); row k of view = (axis_k, -axis_k . eye); f = (rows / 2) / tan(fov_y / 2), cx =
+ * cols / 2, cy = rows / 2; computed in double, stored as float. The viewer's presets (fov 45, near 0.1): front eye
+ * (0, 0, -1) up (0, -1, 0), top eye (0, -5, 0) up (0, 0, 1), side eye (-5, 0, 0) up (0, -1, 0), centre 0.
+ * SVO_ERR_INVALID: an argument that is not finite, eye == centre, up parallel to the viewing direction, fov_y not
+ * within (0, 180), cols or rows < 1, near <= 0, or a result a job rejects. */
+int svo_scene_look_at(const float eye[3], const float centre[3], const float up[3], float fov_y_deg, int cols, int rows,
+                      float near, svo_scene_camera *camera);
+/* the 8 world lines (a, b) of the frustum of `pose` with dims = (w, h, d), in the order of the index buffer, without
+ * a GPU */
+int svo_scene_frustum(const float pose[6], const float dims[3], float out[8][6]);
+/* Queued exactly as svo_submit_export_views is (seqs == NULL names every slot in order, n is ignored): the job sees
+ * every frame set, restart, load and pose update submitted before it and none submitted after, only groups that own a
+ * named slot get work, no group waits for another, the slot is not changed (its deferred pose-filter update is
+ * flushed first). cameras: ONE PER NAMED SLOT, cameras[i] belongs to seqs[i] (pass the same camera n times for one
+ * view of all). style, cameras and dst are copied; segments and pixels stay valid until svo_wait, after which
+ * everything is delivered. mem: SVO_MEM_HOST or SVO_MEM_DEVICE, of `pixels`.
+ * Rejected with SVO_ERR_INVALID and nothing queued: a slot out of range or named twice; a bad mem; a style or a
+ * camera out of the ranges above (GRAY8, unknown show bits, a colour with a top byte, filter bits that are no
+ * SVO_IGNORE_* bit, _reserved != 0, ...); NULL cameras or segments; pixels NULL or not 4-byte aligned; a failed ctx,
+ * as in svo_submit_images. SVO_ERR_CAPACITY: dst->capacity < named slots * image_bytes.
+ * The host builds the trajectory and frustum lines of the group's named slots (svo_scene_frustum) and uploads them
+ * with the table of keyframe sets in one copy per group, into an input block made by the group's first scene job and
+ * replaced when outgrown. Host mode: a group renders its named slots densely into a device staging block (likewise)
+ * and copies each run of consecutive named slots out in one piece. Device mode writes in place. Both blocks count in
+ * svo_ctx_get_memory (svo_memory.device_bytes). A ctx that never asks for a scene allocates, launches and copies
+ * nothing more. */
+int svo_submit_export_scenes(svo_ctx *ctx, const int *seqs, int n, const svo_scene_style *style,
+                             const svo_scene_camera *cameras, const svo_scene_dst *dst, int mem);
+int svo_export_scenes(svo_ctx *ctx, const int *seqs, int n, const svo_scene_style *style,
+                      const svo_scene_camera *cameras, const svo_scene_dst *dst, int mem);   /* submit + wait */
+/* stage entry of the kernel: n images in the tracker's launch (chunked when the diagnostic SVO_SCENE_TABLE_TILES
+ * bounds the tile table). Image i is src[i].cols x src[i].rows (1 .. 4096 each; style->cols and rows are not used)
+ * and shows, through cameras[i], the n_sets SoA keyframe sets src[i].sets (host array of views onto device memory, of
+ * which kps3d, flags, keyframe_id, inlier_count and color are read: 4-byte aligned; own_id[s], host: the keyframe id
+ * set s is held by, as svo_pack_map_points takes them) filtered by style->filter as points of style->point_size, and
+ * the n_lines lines src[i].lines (device memory, 16-byte aligned). style->show, from_keyframe, trajectory_tail, the
+ * three line colours and the frustum are not used. Image i goes to pixels + offset[i] (host array, >= 0, multiples
+ * of 4; pixels: device, 4-byte aligned), rows dense. Exactly the images' bytes are written. Complete on return. */
+typedef struct svo_scene_src {
+    int32_t cols, rows;
+    int32_t n_sets, n_lines;
+    const svo_keypoints *sets;
+    const int32_t *own_id;
+    const svo_scene_line *lines;
+} svo_scene_src;
+int svo_render_scene(svo_handle *h, int n, const svo_scene_src *src, const svo_scene_camera *cameras,
+                     const int64_t *offset, const svo_scene_style *style, uint8_t *pixels);
+
 /* ---- snapshots: the sequence state of a slot saved, loaded, moved between ctxs ------------
  * The reference has no checkpoint or resume (a StereoSlam lives and dies with its process). A snapshot is
  * everything the next frame of a slot depends on and everything its getters return, so that a sequence saved

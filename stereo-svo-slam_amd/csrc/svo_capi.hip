@@ -42,6 +42,8 @@ struct svo_handle {
     size_t map_ws_bytes = 0;
     DevPtr<ViewTile> view_ws;       // svo_render_views: the tile table
     size_t view_ws_count = 0;
+    DevPtr<uint8_t> scene_ws;       // svo_render_scene: the sets and image records of a call, then the tile table
+    size_t scene_ws_bytes = 0;
 };
 
 extern "C" const char* svo_last_error(void) { return svo_error_text; }
@@ -414,6 +416,75 @@ extern "C" int svo_render_views(svo_handle* h, int n, const svo_view_src* src, c
         if (const int rc = table.add(t)) return rc;
     if (const int rc = table.launch(false)) return rc;
     HIP_TRY(hipStreamSynchronize(h->stream));          // (the table's upload read `host`)
+    return SVO_OK;
+}
+
+extern "C" int svo_render_scene(svo_handle* h, int n, const svo_scene_src* src, const svo_scene_camera* cameras,
+                                const int64_t* offset, const svo_scene_style* style, uint8_t* pixels) {
+    CHECK_H(h);
+    if (n < 0 || (n > 0 && (!src || !cameras || !offset))) return svo_set_error(SVO_ERR_INVALID, "svo_render_scene: bad arguments");
+    if (const int rc = scene_check_style(style, "svo_render_scene")) return rc;
+    if (!pixels || ((uintptr_t)pixels & 3)) return svo_set_error(SVO_ERR_INVALID, "svo_render_scene: pixels is NULL or not 4-byte aligned");
+    std::vector<SceneSet> sets;
+    std::vector<SceneImage> images;
+    std::vector<size_t> set0;
+    std::vector<SceneTile> tiles;
+    for (int i = 0; i < n; i++) {
+        const svo_scene_src& s = src[i];
+        if (s.cols < 1 || s.cols > 4096 || s.rows < 1 || s.rows > 4096)
+            return svo_set_error(SVO_ERR_INVALID, "svo_render_scene: image %d: %d x %d is not within 1 .. 4096 a side", i, s.cols, s.rows);
+        if (offset[i] < 0 || (offset[i] & 3)) return svo_set_error(SVO_ERR_INVALID, "svo_render_scene: image %d: offset must be >= 0 and a multiple of 4", i);
+        if (const int rc = scene_check_camera(&cameras[i], "svo_render_scene", i)) return rc;
+        if (s.n_sets < 0 || s.n_lines < 0 || (s.n_sets > 0 && (!s.sets || !s.own_id)) || (s.n_lines > 0 && !s.lines) || ((uintptr_t)s.lines & 15))
+            return svo_set_error(SVO_ERR_INVALID, "svo_render_scene: image %d: sets, own_id or lines missing, or lines not 16-byte aligned", i);
+        set0.push_back(sets.size());
+        for (int j = 0; j < s.n_sets; j++) {
+            const svo_keypoints& k = s.sets[j];
+            if (k.n < 0) return svo_set_error(SVO_ERR_INVALID, "svo_render_scene: image %d: set %d: n must be >= 0", i, j);
+            KpsDev d{};
+            d.kps3d = k.kps3d; d.flags = k.flags; d.kf_id = k.keyframe_id; d.inl = k.inlier_count; d.color = k.color;
+            for (const void* p : {(const void*)d.kps3d, (const void*)d.flags, (const void*)d.kf_id, (const void*)d.inl, (const void*)d.color})
+                if ((k.n > 0 && !p) || ((uintptr_t)p & 3))
+                    return svo_set_error(SVO_ERR_INVALID, "svo_render_scene: image %d: set %d: kps3d, flags, keyframe_id, inlier_count and color are device memory, 4-byte aligned", i, j);
+            sets.push_back(scene_set(d, k.n, s.own_id[j]));
+        }
+        SceneImage im;
+        im.cam = cameras[i];
+        im.dst = pixels + offset[i];
+        im.sets = nullptr; im.lines = s.lines;             // (the sets are placed below, once the block is there)
+        im.n_sets = s.n_sets; im.n_lines = s.n_lines;
+        im.w = s.cols; im.h = s.rows;
+        scene_tiles(i, s.cols, s.rows, tiles);
+        images.push_back(im);
+    }
+    if (tiles.empty()) return SVO_OK;
+    // (SVO_SCENE_TABLE_TILES: a smaller table, so that tests reach the chunked launches)
+    const size_t chunk = table_tiles("SVO_SCENE_TABLE_TILES", std::min<size_t>(tiles.size(), (size_t)INT_MAX));
+    const size_t sets_bytes = (sizeof(SceneSet) * sets.size() + 15) / 16 * 16;
+    const size_t images_bytes = (sizeof(SceneImage) * images.size() + 15) / 16 * 16;
+    const size_t bytes = sets_bytes + images_bytes + sizeof(SceneTile) * chunk;
+    if (bytes > h->scene_ws_bytes) {
+        HIP_TRY(hipStreamSynchronize(h->stream));      // (the old block may still be read)
+        h->scene_ws.reset();
+        h->scene_ws_bytes = 0;
+        HIP_TRY(dev_malloc(h->scene_ws, bytes));
+        h->scene_ws_bytes = bytes;
+    }
+    const SceneSet* d_sets = reinterpret_cast<const SceneSet*>(h->scene_ws.get());
+    const SceneImage* d_images = reinterpret_cast<const SceneImage*>(h->scene_ws.get() + sets_bytes);
+    for (size_t i = 0; i < images.size(); i++) images[i].sets = d_sets + set0[i];
+    if (!sets.empty()) HIP_TRY(hipMemcpyAsync(h->scene_ws.get(), sets.data(), sizeof(SceneSet) * sets.size(), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->scene_ws.get() + sets_bytes, images.data(), sizeof(SceneImage) * images.size(), hipMemcpyHostToDevice, h->stream));
+    const SceneParams params = scene_params(*style);
+    std::vector<SceneTile> host(chunk);
+    TileTable table{host.data(), reinterpret_cast<SceneTile*>(h->scene_ws.get() + sets_bytes + images_bytes), chunk, h->stream,
+                    [&](const SceneTile* d, int m, hipStream_t s) { launch_scene(d, m, d_images, params, s); }};
+    int rc = SVO_OK;
+    for (size_t i = 0; i < tiles.size() && !rc; i++) rc = table.add(tiles[i]);
+    if (!rc) rc = table.launch(false);
+    const hipError_t e = hipStreamSynchronize(h->stream);   // (on every path: the uploads read host memory of this call)
+    if (rc) return rc;
+    HIP_TRY(e);
     return SVO_OK;
 }
 

@@ -29,7 +29,7 @@
 // single-workgroup-per-sequence alignment kernel of one group overlaps the window kernels of
 // the other. svo_submit_images() queues a frame set on every group and returns;
 // svo_wait() drains the queues. svo_new_images() = submit + wait. Restarts (svo_ctx_restart_sequences),
-// exports (svo_submit_export, svo_submit_export_map, svo_submit_export_views), saves and loads (svo_submit_save / svo_submit_load) and pose-filter updates
+// exports (svo_submit_export, svo_submit_export_map, svo_submit_export_views, svo_submit_export_scenes), saves and loads (svo_submit_save / svo_submit_load) and pose-filter updates
 // (svo_submit_pose_updates) are entries of the same queues, so they are ordered with the frame sets.
 struct svo_ctx {
     // the group's share of an svo_submit_export: its named slots (indices in the group) in named order, the
@@ -57,6 +57,15 @@ struct svo_ctx {
         svo_view_style style{};
         svo_view_dst dst{};
     };
+    // the group's share of an svo_submit_export_scenes: its named slots (indices in the group) in named order, the
+    // camera of each and the segment (and image) of the job each one fills
+    struct SceneExport {
+        int mem = 0;
+        std::vector<int> seqs, seg;
+        std::vector<svo_scene_camera> cameras;
+        svo_scene_style style{};
+        svo_scene_dst dst{};
+    };
     // the group's share of an svo_submit_save (snaps) or svo_submit_load (loads): its named slots, indices in the group
     struct Snapshots {
         int mem = 0;
@@ -73,7 +82,8 @@ struct svo_ctx {
     };
     // one entry of a group's queue: a frame set, or (restart non-empty) the end of some of its sequences, or
     // (exp.seqs non-empty) an export, or (snap.seqs / snap.loads non-empty) a save / a load, or (pose.seqs non-empty)
-    // pose-filter updates, or (map.seqs non-empty) a map export, or (view.seqs non-empty) a view job
+    // pose-filter updates, or (map.seqs non-empty) a map export, or (view.seqs non-empty) a view job, or (scene.seqs
+    // non-empty) a scene job
     struct Job {
         std::vector<const uint8_t*> left, right;
         std::vector<float> ts;
@@ -84,6 +94,7 @@ struct svo_ctx {
         PoseUpdates pose;
         MapExport map;
         ViewExport view;
+        SceneExport scene;
     };
     struct Worker {
         Group g;
@@ -121,7 +132,10 @@ void worker_run_job(svo_ctx::Worker& w, const svo_ctx::Job& job) {
     const svo_ctx::PoseUpdates& pu = job.pose;
     const svo_ctx::MapExport& mp = job.map;
     const svo_ctx::ViewExport& vw = job.view;
-    const int rc = !vw.seqs.empty()
+    const svo_ctx::SceneExport& sc = job.scene;
+    const int rc = !sc.seqs.empty()
+                       ? grp_export_scenes(w.g.get(), sc.mem, sc.seqs.data(), sc.seg.data(), (int)sc.seqs.size(), w.first, &sc.style, sc.cameras.data(), &sc.dst)
+                   : !vw.seqs.empty()
                        ? grp_export_views(w.g.get(), vw.what, vw.mem, vw.seqs.data(), vw.seg.data(), (int)vw.seqs.size(), w.first, &vw.style, &vw.dst)
                    : !mp.seqs.empty()
                        ? grp_export_map(w.g.get(), mp.mem, mp.seqs.data(), mp.seg.data(), mp.regions.data(), (int)mp.seqs.size(), w.first, &mp.filter, &mp.dst)
@@ -466,6 +480,48 @@ extern "C" int svo_submit_export_views(svo_ctx* c, int what, const int* seqs, in
 extern "C" int svo_export_views(svo_ctx* c, int what, const int* seqs, int n, const svo_view_style* style,
                                 const svo_view_dst* dst, int mem) {
     const int rc = svo_submit_export_views(c, what, seqs, n, style, dst, mem);
+    return rc ? rc : svo_wait(c);
+}
+
+extern "C" int svo_submit_export_scenes(svo_ctx* c, const int* seqs, int n, const svo_scene_style* style,
+                                        const svo_scene_camera* cameras, const svo_scene_dst* dst, int mem) {
+    if (!c || !dst || !dst->segments || !cameras || (mem != SVO_MEM_HOST && mem != SVO_MEM_DEVICE) || (seqs && n < 0))
+        return svo_set_error(SVO_ERR_INVALID, "svo_submit_export_scenes: bad arguments (mem %d)", mem);
+    if (const int rc = svo::scene_check_style(style, "svo_submit_export_scenes")) return rc;
+    if (!dst->pixels || ((uintptr_t)dst->pixels & 3))
+        return svo_set_error(SVO_ERR_INVALID, "svo_submit_export_scenes: pixels is NULL or not 4-byte aligned");
+    if (!seqs) n = c->B;
+    std::vector<char> named(c->B, 0);
+    for (int i = 0; i < n; i++) {
+        const int s = seqs ? seqs[i] : i;
+        if (s < 0 || s >= c->B || named[s])
+            return svo_set_error(SVO_ERR_INVALID, "svo_submit_export_scenes: sequence %d is out of range or named twice", s);
+        named[s] = 1;
+        if (const int rc = svo::scene_check_camera(&cameras[i], "svo_submit_export_scenes", i)) return rc;
+    }
+    const int64_t image_bytes = grp_scene_bytes(style);
+    if (dst->capacity < n * image_bytes)
+        return svo_set_error(SVO_ERR_CAPACITY, "svo_submit_export_scenes: %d slots need %lld bytes, capacity %lld", n,
+                             (long long)(n * image_bytes), (long long)dst->capacity);
+    if (c->failed.load()) return reject_failed(c, "svo_submit_export_scenes");
+    for (auto& wp : c->workers) {
+        svo_ctx::Worker& w = *wp;
+        svo_ctx::Job job;
+        svo_ctx::SceneExport& e = job.scene;
+        for (int i = 0; i < n; i++) {
+            const int s = seqs ? seqs[i] : i;
+            if (s >= w.first && s < w.first + w.count) { e.seqs.push_back(s - w.first); e.seg.push_back(i); e.cameras.push_back(cameras[i]); }
+        }
+        if (e.seqs.empty()) continue;
+        e.mem = mem; e.style = *style; e.dst = *dst;
+        worker_submit(w, std::move(job));
+    }
+    return SVO_OK;
+}
+
+extern "C" int svo_export_scenes(svo_ctx* c, const int* seqs, int n, const svo_scene_style* style,
+                                 const svo_scene_camera* cameras, const svo_scene_dst* dst, int mem) {
+    const int rc = svo_submit_export_scenes(c, seqs, n, style, cameras, dst, mem);
     return rc ? rc : svo_wait(c);
 }
 

@@ -167,7 +167,7 @@ __device__ inline float ordered_wave_sum(float v, float s) {
 // cv::Rodrigues (vector -> matrix) in double: PoseManager::set_pose,
 // src/lib/pose_manager.cpp:15-16, and inside cv::projectPoints,
 // src/lib/transform_keypoints.cpp:45. R(-r) is exactly the transpose.
-__device__ inline void rodrigues_d(const float r[3], double R[9]) {
+__host__ __device__ inline void rodrigues_d(const float r[3], double R[9]) {
     double rx = r[0], ry = r[1], rz = r[2];
     const double theta = sqrt(rx * rx + ry * ry + rz * rz);
     if (theta < DBL_EPSILON) {

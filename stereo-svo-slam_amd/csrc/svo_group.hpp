@@ -1,6 +1,7 @@
 // svo_group.hpp — one group of sequences as svo_ctx.hip drives it: the opaque interface of svo_group.hip (creation,
 // settings, restarts), svo_group_step.hip (grp_new_images), svo_group_export.hip (grp_export, grp_capacity),
 // svo_group_map.hip (grp_export_map, grp_map_size), svo_group_view.hip (grp_export_views, grp_view_bytes),
+// svo_group_scene.hip (grp_export_scenes, grp_scene_bytes),
 // svo_group_snapshot.hip (grp_check_snapshot, grp_save, grp_load, grp_snapshot_size) and svo_group_pose.hip
 // (grp_pose_updates).
 #pragma once
@@ -45,6 +46,13 @@ int grp_export_views(svo_group* g, int what, int mem, const int* seqs, const int
 // changes in a group)
 int grp_check_view_style(const svo_group* g, const svo_view_style* style);
 int64_t grp_view_bytes(const svo_group* g, const svo_view_style* style);
+// One group's share of svo_submit_export_scenes (svo_group_scene.hip), between two steps of the group, on the thread
+// that drives it: slot seqs[i] (index in the group; ctx slot seq0 + seqs[i]) seen through cameras[i] fills
+// dst->segments[seg[i]] and its image goes to byte seg[i] * image_bytes of dst->pixels (host or device memory: mem).
+// style and cameras: checked (scene_check_style, scene_check_camera). Delivered on return. A failed group rejects it.
+int grp_export_scenes(svo_group* g, int mem, const int* seqs, const int* seg, int n, int seq0, const svo_scene_style* style,
+                      const svo_scene_camera* cameras, const svo_scene_dst* dst);
+int64_t grp_scene_bytes(const svo_scene_style* style);   // the image_bytes of a checked style
 // what svo_map_size reports of a slot (the queues have drained)
 void grp_map_size(const svo_group* g, int seq, int from_keyframe, int* keyframes, int64_t* points_bound);
 // Snapshots (svo_submit_save / svo_submit_load). grp_check_snapshot: everything svo_submit_load checks of one

@@ -1,0 +1,248 @@
+// svo_group_scene.hip — the scene job of a sequence group (svo_submit_export_scenes): the viewer's 3-D picture of the
+// maps of its named slots (keyframe points, trajectory, frusta), rendered by scene.hip's kernel, as segments and
+// pixels; and the host-only entry points svo_scene_size, svo_scene_look_at, svo_scene_frustum. The state is
+// svo_group_state.hpp.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+
+#include "svo_group_state.hpp"
+
+using namespace svo;
+
+namespace {
+
+// the input block (device and its pinned mirror) holds `bytes`; a grown one replaces the old
+int reserve_scene_in(svo_group* c, size_t bytes) {
+    if (bytes <= c->scene_in_bytes) return SVO_OK;
+    HIP_TRY(hipStreamSynchronize(c->stream.get()));
+    bytes = align_up(bytes, 4096);
+    if (c->d_scene_in) dev_release(c, c->d_scene_in, c->scene_in_bytes);
+    c->d_scene_in = nullptr; c->scene_in_bytes = 0;
+    c->scene_in_host.reset();
+    HIP_TRY(pinned_malloc(c->scene_in_host, bytes));
+    if (const int rc = dev_alloc(c, &c->d_scene_in, bytes, false)) return rc;
+    c->scene_in_bytes = bytes;
+    return SVO_OK;
+}
+
+// the host-mode staging block holds `bytes`
+int reserve_scene(svo_group* c, size_t bytes) {
+    if (bytes <= c->scene_bytes) return SVO_OK;
+    HIP_TRY(hipStreamSynchronize(c->stream.get()));
+    if (c->d_scene) dev_release(c, c->d_scene, c->scene_bytes);
+    c->d_scene = nullptr; c->scene_bytes = 0;
+    if (const int rc = dev_alloc(c, &c->d_scene, bytes, false)) return rc;
+    c->scene_bytes = bytes;
+    return SVO_OK;
+}
+
+bool finite3(const float v[3]) { return std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]); }
+
+void cross(const double a[3], const double b[3], double o[3]) {
+    o[0] = a[1] * b[2] - a[2] * b[1];
+    o[1] = a[2] * b[0] - a[0] * b[2];
+    o[2] = a[0] * b[1] - a[1] * b[0];
+}
+
+// v / |v|; false for a vector without a direction
+bool normalize(double v[3]) {
+    const double l = std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
+    if (!(l > 0) || !std::isfinite(l)) return false;
+    for (int k = 0; k < 3; k++) v[k] /= l;
+    return true;
+}
+
+}  // namespace
+
+extern "C" int svo_scene_size(const svo_scene_style* style, int64_t* pitch, int64_t* image_bytes) {
+    if (const int rc = scene_check_style(style, "svo_scene_size")) return rc;
+    scene_shape(*style, style->cols, style->rows, pitch, image_bytes);
+    return SVO_OK;
+}
+
+extern "C" int svo_scene_look_at(const float eye[3], const float centre[3], const float up[3], float fov_y_deg, int cols,
+                                 int rows, float near, svo_scene_camera* camera) {
+    if (!eye || !centre || !up || !camera || !finite3(eye) || !finite3(centre) || !finite3(up) || !(fov_y_deg > 0) ||
+        !(fov_y_deg < 180) || cols < 1 || rows < 1 || !(near > 0) || !std::isfinite(near))
+        return svo_set_error(SVO_ERR_INVALID, "svo_scene_look_at: bad arguments");
+    double axis[3][3];                                     // x_c, y_c, z_c
+    const double neg_up[3] = {-(double)up[0], -(double)up[1], -(double)up[2]};
+    for (int k = 0; k < 3; k++) axis[2][k] = (double)centre[k] - (double)eye[k];
+    if (!normalize(axis[2])) return svo_set_error(SVO_ERR_INVALID, "svo_scene_look_at: eye and centre coincide");
+    cross(neg_up, axis[2], axis[0]);
+    if (!normalize(axis[0])) return svo_set_error(SVO_ERR_INVALID, "svo_scene_look_at: up is parallel to the viewing direction");
+    cross(axis[2], axis[0], axis[1]);
+    svo_scene_camera cam;
+    for (int k = 0; k < 3; k++) {
+        for (int j = 0; j < 3; j++) cam.view[4 * k + j] = (float)(axis[k][j] + 0.0);   // (+ 0.0: no negative zero)
+        cam.view[4 * k + 3] = (float)(-((axis[k][0] * eye[0] + axis[k][1] * eye[1]) + axis[k][2] * eye[2]) + 0.0);
+    }
+    const double half = (double)fov_y_deg * (3.14159265358979323846 / 180.0) * 0.5;
+    cam.f = (float)((rows * 0.5) / std::tan(half));
+    cam.cx = (float)(cols * 0.5);
+    cam.cy = (float)(rows * 0.5);
+    cam.near = near;
+    if (const int rc = scene_check_camera(&cam, "svo_scene_look_at", 0)) return rc;
+    *camera = cam;
+    return SVO_OK;
+}
+
+extern "C" int svo_scene_frustum(const float pose[6], const float dims[3], float out[8][6]) {
+    if (!pose || !dims || !out) return svo_set_error(SVO_ERR_INVALID, "svo_scene_frustum: bad arguments");
+    double Rd[9];
+    rodrigues_d(pose + 3, Rd);
+    float R[9];
+    for (int k = 0; k < 9; k++) R[k] = (float)Rd[k];
+    const float w = dims[0], h = dims[1], d = dims[2];
+    const float v[5][3] = {{0, 0, 0}, {-w, h, d}, {-w, -h, d}, {w, -h, d}, {w, h, d}};
+    float world[5][3];
+    for (int i = 0; i < 5; i++)
+        for (int k = 0; k < 3; k++)
+            world[i][k] = ((R[3 * k] * v[i][0] + R[3 * k + 1] * v[i][1]) + R[3 * k + 2] * v[i][2]) + pose[k];
+    static const int edge[8][2] = {{0, 1}, {0, 2}, {0, 3}, {0, 4}, {1, 2}, {2, 3}, {3, 4}, {4, 1}};
+    for (int e = 0; e < 8; e++) {
+        std::memcpy(out[e], world[edge[e][0]], sizeof(float) * 3);
+        std::memcpy(out[e] + 3, world[edge[e][1]], sizeof(float) * 3);
+    }
+    return SVO_OK;
+}
+
+namespace svo {
+
+void scene_frustum_lines(const float pose[6], const float dims[3], uint32_t cls_rgb, std::vector<svo_scene_line>& out) {
+    float e[8][6];
+    svo_scene_frustum(pose, dims, e);
+    for (int i = 0; i < 8; i++) {
+        svo_scene_line l;
+        std::memcpy(l.a, e[i], sizeof(l.a));
+        std::memcpy(l.b, e[i] + 3, sizeof(l.b));
+        l.cls_rgb = cls_rgb; l._pad = 0;
+        out.push_back(l);
+    }
+}
+
+}  // namespace svo
+
+int64_t grp_scene_bytes(const svo_scene_style* style) {
+    int64_t bytes = 0;
+    scene_shape(*style, style->cols, style->rows, nullptr, &bytes);
+    return bytes;
+}
+
+// The named slots of the group as segments and images (svo_submit_export_scenes); cameras[i] belongs to seqs[i].
+// Named slot seg[i] of the job goes to byte seg[i] * image_bytes of the caller's pixels; in host mode the group
+// renders its i-th named slot at byte i * image_bytes of its staging block and copies every run of slots that are
+// consecutive in both (and delivered) out as the views do. The lines of every slot (trajectory, keyframe frusta, the
+// pose's frustum), the table of its keyframe sets and the image records are built in the pinned input block and go
+// up in one copy; the tile table goes through the group's argument blocks (group_tile_table), one launch unless it
+// outgrows them.
+int grp_export_scenes(svo_group* c, int mem, const int* seqs, const int* seg, int n, int seq0, const svo_scene_style* style,
+                      const svo_scene_camera* cameras, const svo_scene_dst* dst) {
+    if (c->failed)
+        return svo_set_error(SVO_ERR_INVALID, "svo_submit_export_scenes: an earlier frame of this ctx failed; create a new ctx");
+    HIP_TRY(hipSetDevice(c->device));
+    flush_pending(c);
+    hipStream_t st = c->stream.get();
+    const bool host = mem == SVO_MEM_HOST;
+    const int cols = style->cols, rows = style->rows;
+    int64_t pitch, image_bytes;
+    scene_shape(*style, cols, rows, &pitch, &image_bytes);
+    const int64_t used = (int64_t)rows * pitch;          // bytes of an image
+    const float dims[3] = {style->frustum_w, style->frustum_h, style->frustum_d};
+    std::vector<svo_scene_line> lines;
+    std::vector<SceneSet> sets;
+    std::vector<SceneImage> images;
+    std::vector<SceneTile> tiles;
+    std::vector<char> shown((size_t)n, 0);
+    struct Placed { int i; size_t set0, line0; };        // a delivered slot: its first set and line of the job
+    std::vector<Placed> placed;
+    for (int i = 0; i < n; i++) {
+        const Seq& q = c->seqs[seqs[i]];
+        svo_scene_segment& e = clear(dst->segments[seg[i]]);
+        e.seq = seq0 + seqs[i]; e.run = q.run; e.frame_id = q.frame_id; e.status = SVO_SCENE_NONE;
+        e.n_keyframes = (uint16_t)q.kfs.size(); e.from_keyframe = style->from_keyframe;
+        e.time_stamp = (float)q.ts; e.offset = (int64_t)seg[i] * image_bytes;
+        std::memcpy(e.pose, q.pose, sizeof(e.pose));
+        if (q.frame_id < 0) continue;
+        e.status = SVO_SCENE_OK;
+        shown[i] = 1;
+        SceneImage im;
+        im.cam = cameras[i];
+        im.dst = nullptr; im.sets = nullptr; im.lines = nullptr;   // (placed below, once the blocks are there)
+        im.w = cols; im.h = rows;
+        const size_t set0 = sets.size(), line0 = lines.size();
+        placed.push_back({i, set0, line0});
+        const size_t kf0 = std::min<size_t>((size_t)style->from_keyframe, q.kfs.size());
+        if (style->show & SVO_SCENE_POINTS)
+            for (size_t k = kf0; k < q.kfs.size(); k++) {
+                sets.push_back(scene_set(q.kfs[k].kps, q.kfs[k].n, (int)k));
+                e.n_keypoints += q.kfs[k].n;
+            }
+        if (style->show & SVO_SCENE_TRAJECTORY) {
+            const size_t np = q.trajectory.size();
+            const size_t first = style->trajectory_tail > 0 && np > (size_t)style->trajectory_tail ? np - (size_t)style->trajectory_tail : 0;
+            e.n_poses = (int)(np - first);
+            for (size_t j = first; j + 1 < np; j++) {
+                const svo_pose &a = q.trajectory[j], &b = q.trajectory[j + 1];
+                lines.push_back(svo_scene_line{{a.x, a.y, a.z}, {b.x, b.y, b.z}, (uint32_t)SVO_SCENE_CLASS_TRAJECTORY << 24 | style->trajectory_rgb, 0});
+            }
+        }
+        if (style->show & SVO_SCENE_KEYFRAMES)
+            for (size_t k = kf0; k < q.kfs.size(); k++)
+                scene_frustum_lines(q.kfs[k].pose, dims, (uint32_t)SVO_SCENE_CLASS_KEYFRAME << 24 | style->keyframe_rgb, lines);
+        if (style->show & SVO_SCENE_POSE)
+            scene_frustum_lines(q.pose, dims, (uint32_t)SVO_SCENE_CLASS_POSE << 24 | style->pose_rgb, lines);
+        im.n_sets = (int)(sets.size() - set0); im.n_lines = (int)(lines.size() - line0);
+        scene_tiles((int)images.size(), cols, rows, tiles);
+        images.push_back(im);
+    }
+    if (!images.empty()) {
+        if (host)
+            if (const int rc = reserve_scene(c, (size_t)n * (size_t)image_bytes)) return rc;
+        // the input block: lines | sets | images
+        const size_t lines_bytes = sizeof(svo_scene_line) * lines.size(), sets_bytes = sizeof(SceneSet) * sets.size();
+        const size_t in_bytes = lines_bytes + sets_bytes + sizeof(SceneImage) * images.size();
+        if (const int rc = reserve_scene_in(c, in_bytes)) return rc;
+        const svo_scene_line* d_lines = reinterpret_cast<const svo_scene_line*>(c->d_scene_in);
+        const SceneSet* d_sets = reinterpret_cast<const SceneSet*>(c->d_scene_in + lines_bytes);
+        const SceneImage* d_images = reinterpret_cast<const SceneImage*>(c->d_scene_in + lines_bytes + sets_bytes);
+        for (size_t k = 0; k < placed.size(); k++) {
+            const Placed& pl = placed[k];
+            images[k].dst = host ? c->d_scene + (int64_t)pl.i * image_bytes : dst->pixels + (int64_t)seg[pl.i] * image_bytes;
+            images[k].sets = d_sets + pl.set0;
+            images[k].lines = d_lines + pl.line0;
+        }
+        uint8_t* h = c->scene_in_host.get();
+        if (lines_bytes) std::memcpy(h, lines.data(), lines_bytes);
+        if (sets_bytes) std::memcpy(h + lines_bytes, sets.data(), sets_bytes);
+        std::memcpy(h + lines_bytes + sets_bytes, images.data(), sizeof(SceneImage) * images.size());
+        HIP_TRY(hipMemcpyAsync(c->d_scene_in, h, in_bytes, hipMemcpyHostToDevice, st));
+        const SceneParams params = scene_params(*style);
+        // (SVO_SCENE_TABLE_TILES: a smaller table, so that tests reach the chunked launches)
+        auto table = group_tile_table<SceneTile>(c, "SVO_SCENE_TABLE_TILES", [&](const SceneTile* d, int m, hipStream_t s) {
+            launch_scene(d, m, d_images, params, s);
+        });
+        for (const SceneTile& t : tiles)
+            if (const int rc = table.add(t)) return rc;
+        if (const int rc = table.launch(false)) return rc;
+    }
+    for (int i = 0; host && i < n;) {
+        if (!shown[i]) { i++; continue; }
+        int j = i + 1;
+        while (j < n && shown[j] && seg[j] == seg[j - 1] + 1) j++;
+        uint8_t* to = dst->pixels + (int64_t)seg[i] * image_bytes;
+        const uint8_t* from = c->d_scene + (int64_t)i * image_bytes;
+        if (used == image_bytes)
+            HIP_TRY(hipMemcpyAsync(to, from, (size_t)((j - i) * image_bytes), hipMemcpyDeviceToHost, st));
+        else if (j - i == 1)
+            HIP_TRY(hipMemcpyAsync(to, from, (size_t)used, hipMemcpyDeviceToHost, st));
+        else
+            HIP_TRY(hipMemcpy2DAsync(to, (size_t)image_bytes, from, (size_t)image_bytes, (size_t)used, (size_t)(j - i), hipMemcpyDeviceToHost, st));
+        i = j;
+    }
+    HIP_TRY(hipStreamSynchronize(st));       // delivered: svo_wait means that
+    return SVO_OK;
+}

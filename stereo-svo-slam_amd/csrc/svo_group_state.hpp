@@ -1,6 +1,7 @@
 // svo_group_state.hpp — the state of one sequence group, internal to the group: only its translation units
 // (svo_group.hip: storage, creation, settings, the end of a sequence; svo_group_step.hip: the step;
 // svo_group_export.hip: the bulk export; svo_group_map.hip: the map export; svo_group_view.hip: the views;
+// svo_group_scene.hip: the scenes;
 // svo_group_snapshot.hip: save and load;
 // svo_group_pose.hip: the batched pose-filter updates) and the per-sequence getters of
 // svo_ctx.hip include it. Everyone else drives a group through the opaque interface of svo_group.hpp.
@@ -286,6 +287,12 @@ struct svo_group {
     // views (grp_export_views) in host mode: the images of one job, made by the first such job and replaced when
     // outgrown
     uint8_t* d_view = nullptr; size_t view_bytes = 0;
+    // scenes (grp_export_scenes): the input block of one job (lines | keyframe sets | image records) and its pinned
+    // mirror, made by the group's first scene job; in host mode the images of one job, made by the first host-mode
+    // one. Replaced when outgrown.
+    uint8_t* d_scene_in = nullptr; size_t scene_in_bytes = 0;
+    svo::PinnedPtr<uint8_t> scene_in_host;
+    uint8_t* d_scene = nullptr; size_t scene_bytes = 0;
     // batched pose-filter updates (grp_pose_updates): the upload block (samples | filter states | start poses |
     // sample offsets) and behind it the download block (filter states | filtered poses) of one job, device and pinned,
     // made by the first such job and replaced when outgrown

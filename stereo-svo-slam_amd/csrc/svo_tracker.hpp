@@ -197,6 +197,50 @@ ViewParams view_params(const svo_view_style& style);
 void view_tiles(const ImgView& src, uint8_t* dst, const KpsDev* kps, int n, std::vector<ViewTile>& out);
 void launch_view(const ViewTile* d_tiles, int n_tiles, const ViewParams& p, hipStream_t stream);
 
+// ------------------------------------------------------------ scene (scene.hip)
+// One keyframe set of an image: the five planes the points come from (4-byte aligned), its keypoints and the id of
+// the keyframe that holds it
+struct SceneSet {
+    const uint32_t* kps3d;
+    const uint32_t* flags;
+    const int* kf_id;
+    const int* inl;
+    const uint32_t* color;
+    int n, own_id;
+};
+// One output image: w x h pixels at dst, rows dense, seen through cam; its sets and lines (device tables)
+struct SceneImage {
+    svo_scene_camera cam;
+    uint8_t* dst;
+    const SceneSet* sets;
+    const svo_scene_line* lines;
+    int n_sets, n_lines;
+    int w, h;
+};
+// One tile of an image: at most SCENE_TILE_W x SCENE_TILE_H pixels at (x0, y0), one workgroup
+constexpr int SCENE_TILE_W = 64, SCENE_TILE_H = 16;
+struct SceneTile {
+    int image, x0, y0, _pad;
+};
+// what a launch draws, from a checked svo_scene_style
+struct SceneParams {
+    int bpp, point_size;
+    uint32_t background;
+    svo_map_filter filter;
+};
+// what a scene job, svo_scene_size and the stage entry check alike
+int scene_check_style(const svo_scene_style* style, const char* who);
+int scene_check_camera(const svo_scene_camera* cam, const char* who, int i);
+SceneParams scene_params(const svo_scene_style& style);
+// pitch and image_bytes of a cols x rows image of a checked style
+void scene_shape(const svo_scene_style& style, int cols, int rows, int64_t* pitch, int64_t* image_bytes);
+SceneSet scene_set(const KpsDev& k, int n, int own_id);
+// the tiles of image `image` (w x h), appended to `out`
+void scene_tiles(int image, int w, int h, std::vector<SceneTile>& out);
+// the 8 world lines of a frustum (svo_scene_frustum) as records of class cls and colour rgb, appended to `out`
+void scene_frustum_lines(const float pose[6], const float dims[3], uint32_t cls_rgb, std::vector<svo_scene_line>& out);
+void launch_scene(const SceneTile* d_tiles, int n_tiles, const SceneImage* d_images, const SceneParams& p, hipStream_t stream);
+
 // ------------------------------------------------------------ batched pose filter (pose_filter.hip)
 // n_states filter states, one lane each, POSE_FILTER_LANES per workgroup. State b runs samples
 // [first[b], first[b + 1]) (clamped to [0, n_samples)) in order; a state without samples is neither read nor written.

@@ -41,6 +41,8 @@ SYMBOLS = (
     "svo_submit_pose_updates", "svo_update_poses", "svo_pose_filter_batch",
     "svo_map_size", "svo_submit_export_map", "svo_export_map", "svo_pack_map_points",
     "svo_view_size", "svo_submit_export_views", "svo_export_views", "svo_render_views",
+    "svo_scene_size", "svo_scene_look_at", "svo_scene_frustum", "svo_submit_export_scenes", "svo_export_scenes",
+    "svo_render_scene",
 )
 
 # svo_ctx_set_input_format / svo_convert_frames: how the buffers of a sequence become its two gray images
@@ -211,6 +213,94 @@ class ViewSrc(C.Structure):
     _fields_ = [("image", Image), ("kps", Keypoints)]
 
 
+# scenes (svo_submit_export_scenes, include/svo_hip.h): what is shown, the classes of the key, a line of the stage
+# entry, a segment (one per named slot)
+SCENE_POINTS, SCENE_TRAJECTORY, SCENE_KEYFRAMES, SCENE_POSE = 1, 2, 4, 8
+SCENE_ALL = 15
+SCENE_CLASS_POSE, SCENE_CLASS_KEYFRAME, SCENE_CLASS_TRAJECTORY, SCENE_CLASS_POINT = range(4)
+SCENE_OK, SCENE_NONE = 0, 1
+SCENE_LINE_DTYPE = np.dtype([("a", "<f4", (3,)), ("b", "<f4", (3,)), ("cls_rgb", "<u4"), ("_pad", "<u4")])
+SCENE_SEGMENT_DTYPE = np.dtype([("seq", "<i4"), ("run", "<i4"), ("frame_id", "<i4"), ("status", "<u2"),
+                                ("n_keyframes", "<u2"), ("from_keyframe", "<i4"), ("n_keypoints", "<i4"),
+                                ("n_poses", "<i4"), ("time_stamp", "<f4"), ("offset", "<i8"), ("pose", "<f4", (6,))])
+assert (SCENE_LINE_DTYPE.itemsize, SCENE_SEGMENT_DTYPE.itemsize) == (32, 64)
+# the viewer's camera presets (src/qt-viewer/PointCloudViewer.qml:19-39, 95-96): (eye, centre, up), 45 degrees, 0.1
+SCENE_FRONT = ((0.0, 0.0, -1.0), (0.0, 0.0, 0.0), (0.0, -1.0, 0.0))
+SCENE_TOP = ((0.0, -5.0, 0.0), (0.0, 0.0, 0.0), (0.0, 0.0, 1.0))
+SCENE_SIDE = ((-5.0, 0.0, 0.0), (0.0, 0.0, 0.0), (0.0, -1.0, 0.0))
+SCENE_PRESETS = dict(front=SCENE_FRONT, top=SCENE_TOP, side=SCENE_SIDE)
+SCENE_FOV_Y, SCENE_NEAR = 45.0, 0.1
+
+
+class SceneCamera(C.Structure):
+    """svo_scene_camera (include/svo_hip.h): the rows of the 3x4 world -> camera matrix, f, cx, cy, near."""
+    _fields_ = [("view", C.c_float * 12), ("f", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("near", C.c_float)]
+
+
+class SceneStyle(C.Structure):
+    """svo_scene_style (include/svo_hip.h): what one scene job draws; colours are r << 16 | g << 8 | b."""
+    _fields_ = [("cols", C.c_int32), ("rows", C.c_int32), ("pixel", C.c_int32), ("point_size", C.c_int32),
+                ("background", C.c_uint32), ("trajectory_rgb", C.c_uint32), ("keyframe_rgb", C.c_uint32),
+                ("pose_rgb", C.c_uint32), ("frustum_w", C.c_float), ("frustum_h", C.c_float), ("frustum_d", C.c_float),
+                ("show", C.c_uint32), ("from_keyframe", C.c_int32), ("trajectory_tail", C.c_int32),
+                ("filter", MapFilter), ("_reserved", C.c_int32)]
+
+
+class SceneDst(C.Structure):
+    """svo_scene_dst (include/svo_hip.h)."""
+    _fields_ = [("segments", C.c_void_p), ("pixels", C.c_void_p), ("capacity", C.c_int64)]
+
+
+class SceneSrc(C.Structure):
+    """svo_scene_src (include/svo_hip.h): one image of svo_render_scene."""
+    _fields_ = [("cols", C.c_int32), ("rows", C.c_int32), ("n_sets", C.c_int32), ("n_lines", C.c_int32),
+                ("sets", C.c_void_p), ("own_id", C.c_void_p), ("lines", C.c_void_p)]
+
+
+assert (C.sizeof(SceneCamera), C.sizeof(SceneStyle)) == (64, 76)
+
+
+def scene_style(cols=256, rows=256, pixel=PIXEL_RGB8, point_size=3, background=0xffffff, trajectory_rgb=0xff0000,
+                keyframe_rgb=0x0000ff, pose_rgb=0x00ff00, frustum=(0.1, 0.08, 0.07), show=SCENE_ALL, from_keyframe=0,
+                trajectory_tail=0, filter=None):
+    """a SceneStyle; the defaults are the viewer's (white, red trajectory, blue keyframes, a green current pose, its
+    frustum). pixel may be a name (PIXELS); filter: None, a MapFilter or a dict of its fields"""
+    if isinstance(pixel, str):
+        pixel = PIXELS.index(pixel)
+    return SceneStyle(int(cols), int(rows), int(pixel), int(point_size), int(background), int(trajectory_rgb),
+                      int(keyframe_rgb), int(pose_rgb), float(frustum[0]), float(frustum[1]), float(frustum[2]),
+                      int(show), int(from_keyframe), int(trajectory_tail), map_filter(filter), 0)
+
+
+def scene_size(style):
+    """svo_scene_size (host only): (pitch, image_bytes) of one image of a scene job with `style`."""
+    pitch, nbytes = C.c_int64(0), C.c_int64(0)
+    _check(lib().svo_scene_size(C.byref(style), C.byref(pitch), C.byref(nbytes)))
+    return pitch.value, nbytes.value
+
+
+def scene_look_at(eye, centre, up, fov_y_deg=SCENE_FOV_Y, cols=256, rows=256, near=SCENE_NEAR):
+    """svo_scene_look_at (host only): the SceneCamera at `eye` looking at `centre` for a cols x rows image."""
+    v3 = lambda v: (C.c_float * 3)(*[float(x) for x in v])
+    out = SceneCamera()
+    _check(lib().svo_scene_look_at(v3(eye), v3(centre), v3(up), float(fov_y_deg), int(cols), int(rows), float(near),
+                                   C.byref(out)))
+    return out
+
+
+def scene_preset(name, cols=256, rows=256):
+    """the viewer's "front", "top" or "side" camera for a cols x rows image"""
+    return scene_look_at(*SCENE_PRESETS[name], SCENE_FOV_Y, cols, rows, SCENE_NEAR)
+
+
+def scene_frustum(pose, dims=(0.1, 0.08, 0.07)):
+    """svo_scene_frustum (host only): float32 [8, 6], the world lines (a, b) of the frustum of `pose`."""
+    out = np.zeros((8, 6), np.float32)
+    _check(lib().svo_scene_frustum((C.c_float * 6)(*[float(x) for x in pose]), (C.c_float * 3)(*[float(x) for x in dims]),
+                                   out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
 class SnapshotInfo(C.Structure):
     """struct svo_snapshot_info (include/svo_hip.h): the header of a snapshot's host part."""
     _fields_ = [("magic", C.c_uint32), ("version", C.c_uint32), ("byte_order", C.c_uint32), ("status", C.c_uint32),
@@ -257,6 +347,8 @@ def lib():
         _LIB.svo_last_error.restype = C.c_char_p
         for name in ("svo_submit_pose_updates", "svo_update_poses"):
             getattr(_LIB, name).argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        _LIB.svo_scene_look_at.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_int, C.c_float,
+                                           C.c_void_p]
         _LIB.svo_pose_filter_batch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                                C.c_void_p, C.c_void_p, C.c_void_p]
     return _LIB
@@ -471,6 +563,41 @@ class Handle:
         offs = (C.c_int64 * max(len(srcs), 1))(*[int(o) for o in offsets])
         p = pixels.data_ptr() if isinstance(pixels, torch.Tensor) else int(pixels)
         _check(lib().svo_render_views(self._h, len(srcs), arr, offs, C.byref(style), C.c_void_p(p)))
+
+    def render_scene(self, srcs, cameras, offsets, style, pixels):
+        """svo_render_scene: the viewer's scene of keyframe sets and lines as images of `style` (a SceneStyle). srcs:
+        per image (cols, rows, sets, lines) with sets a list of (n, own_id, {field of svo_keypoints: device tensor or
+        raw device address}) and lines a device tensor holding SCENE_LINE_DTYPE records (16-byte aligned) or None;
+        cameras: a SceneCamera per image; offsets[i]: the byte of `pixels` (a uint8 device tensor, or a raw device
+        address) image i starts at. Complete on return."""
+        self.render_scene_packed(self.pack_scene(srcs, cameras, offsets), style, pixels)
+
+    def pack_scene(self, srcs, cameras, offsets):
+        """the argument arrays of render_scene, built once (keeps Python out of a timed call); pass the result to
+        render_scene_packed. The device tensors of `srcs` must stay alive."""
+        n = len(srcs)
+        arr = (SceneSrc * max(n, 1))()
+        cams = (SceneCamera * max(n, 1))(*cameras)
+        keep = []
+        for i, (cols, rows, sets, lines) in enumerate(srcs):
+            ks = (Keypoints * max(len(sets), 1))()
+            own = (C.c_int32 * max(len(sets), 1))()
+            for j, (m, own_id, planes) in enumerate(sets):
+                ks[j].n, own[j] = int(m), int(own_id)
+                for name, v in planes.items():
+                    setattr(ks[j], name, v.data_ptr() if isinstance(v, torch.Tensor) else int(v))
+            keep += [ks, own]
+            n_lines = 0 if lines is None else lines.numel() * lines.element_size() // SCENE_LINE_DTYPE.itemsize
+            arr[i] = SceneSrc(int(cols), int(rows), len(sets), n_lines, C.cast(ks, C.c_void_p), C.cast(own, C.c_void_p),
+                              lines.data_ptr() if n_lines else None)
+        offs = (C.c_int64 * max(n, 1))(*[int(o) for o in offsets])
+        return n, arr, cams, offs, keep
+
+    def render_scene_packed(self, packed, style, pixels):
+        """svo_render_scene of the arrays of pack_scene"""
+        n, arr, cams, offs, _ = packed
+        p = pixels.data_ptr() if isinstance(pixels, torch.Tensor) else int(pixels)
+        _check(lib().svo_render_scene(self._h, n, arr, cams, offs, C.byref(style), C.c_void_p(p)))
 
     def copy_segments(self, segs):
         """svo_copy_segments: 2-D byte segments, device to device. segs: (src address, dst address, row_bytes,

@@ -13,6 +13,7 @@ Host bookkeeping only; every frame goes through StereoSlam.new_image (libsvo_hip
     python -m stereo_svo_slam_amd.replay --settings Econ.yaml --interleaved 'frames/%06d.png' --gpu-ingest
     python -m stereo_svo_slam_amd.replay --settings EuRoC.yaml --pairs 'seq/%06d_left.png,seq/%06d_right.png'
     python -m stereo_svo_slam_amd.replay --synthetic tiny --frames 20 --dump-views views/
+    python -m stereo_svo_slam_amd.replay --synthetic tiny --frames 20 --dump-scene scene/
 
 Inputs follow the reference's conventions (the library's `left` is the physically RIGHT camera):
 EurocInput (src/app/euroc_input.cpp:48-70,100-105), VideoInput (src/app/video_input.cpp:29-36), EconInput
@@ -23,6 +24,8 @@ frames that are gray already give the CSV they gave before colour frames were co
 as binary PPM files, DIR/000000_keyframe.ppm (the last keyframe, a marker per keypoint) and DIR/000000_frame.ppm (the
 current frame): the gray image the tracker worked on, which with --gpu-rectify / --gpu-ingest only the GPU has seen.
 The text overlay and the x2 resize of the window are not drawn.
+--dump-scene DIR writes per frame DIR/000000_scene.ppm: the 3-D viewer's picture of the map so far
+(src/qt-viewer/PointCloudViewer.qml: points, trajectory, frusta) through its front camera.
 With $SVO_DATA set (a EuRoC `mav0/` directory, or a directory of side-by-side frames) and no
 explicit input that data is used; otherwise the seeded synthetic sequence.
 """
@@ -345,18 +348,20 @@ class Replay:
     """process_image loop: only the time inside new_image is accumulated (slam_app.cpp:186-190)."""
 
     def __init__(self, settings, device=0, time_trace=False, fast=False, rectify_maps=None, input_format=None,
-                 gpu_imu=False, dump_views=None):
+                 gpu_imu=False, dump_views=None, dump_scene=None):
         """fast=False keeps the library default: the reference-order Gauss-Newton (bit-exact traces).
         rectify_maps = (left maps, right maps): the frames fed are raw and are rectified on the GPU.
         input_format: the frames fed are raw buffers of that format (StereoSlam.set_input_format).
         gpu_imu: update_pose_from_imu is one svo_update_poses (the filter kernel) instead of a loop of
         svo_update_pose calls: the same bits.
         dump_views: a directory that receives, per frame, the last keyframe and the current frame with a marker per
-        keypoint as the reference app's window shows them (write_ppm), outside the timed region."""
+        keypoint as the reference app's window shows them (write_ppm), outside the timed region.
+        dump_scene: a directory that receives, per frame, the 3-D viewer's picture of the map (get_scene), likewise."""
         self.settings = settings
-        self.dump_views = dump_views
-        if dump_views:
-            os.makedirs(dump_views, exist_ok=True)
+        self.dump_views, self.dump_scene = dump_views, dump_scene
+        for d in (dump_views, dump_scene):
+            if d:
+                os.makedirs(d, exist_ok=True)
         self.gpu_imu = gpu_imu
         self.slam = StereoSlam(settings, device=device)
         if fast:
@@ -409,6 +414,10 @@ class Replay:
                 img = self.slam.get_image(what, pixel="rgb8", markers=True)
                 if img is not None:
                     write_ppm(os.path.join(self.dump_views, f"{k:06d}_{name}.ppm"), img)
+        if self.dump_scene:
+            img = self.slam.get_scene("front", pixel="rgb8")
+            if img is not None:
+                write_ppm(os.path.join(self.dump_scene, f"{len(self.cumulative) - 1:06d}_scene.ppm"), img)
         if self.time_trace:                       # like PRINT_TIME_TRACE of the reference
             print("\n".join(time_trace_lines(self.slam.stats())))
 
@@ -448,6 +457,9 @@ def main(argv=None):
     ap.add_argument("--dump-views", metavar="DIR",
                     help="write per frame DIR/NNNNNN_keyframe.ppm and DIR/NNNNNN_frame.ppm: the last keyframe and the current "
                          "frame as the reference app's window draws them (gray as RGB, a marker per keypoint)")
+    ap.add_argument("--dump-scene", metavar="DIR",
+                    help="write per frame DIR/NNNNNN_scene.ppm: the 3-D viewer's picture of the map so far (keyframe points, "
+                         "trajectory, a frustum per keyframe and at the current pose) through its front camera")
     ap.add_argument("--frames", type=int, default=100)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--rate", type=float, default=20.0, help="frames per second of the time stamps")
@@ -498,7 +510,7 @@ def main(argv=None):
         ap.error("--gpu-imu needs --gyro")
     gyro = np.loadtxt(args.gyro, ndmin=2) if args.gyro else None
     rp = Replay(settings, args.device, args.time_trace, args.fast, rectify_maps=rect, input_format=fmt, gpu_imu=args.gpu_imu,
-                dump_views=args.dump_views)
+                dump_views=args.dump_views, dump_scene=args.dump_scene)
     for k, (left, right, t) in enumerate(frames):
         rp.feed(left, right, t, None if gyro is None else gyro[gyro[:, 0] == k, 1:4])
     rows = rp.rows()

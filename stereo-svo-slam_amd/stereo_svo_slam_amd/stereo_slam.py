@@ -319,6 +319,60 @@ class Views:
         return a.reshape(shape)
 
 
+class Scenes:
+    """One svo_submit_export_scenes: owns the buffers the library writes. After wait(): `segments`
+    (hip_lib.SCENE_SEGMENT_DTYPE, one per named slot) and image(i); `pixels` is the whole buffer, a numpy uint8 view
+    of pinned memory in host mode, a torch uint8 tensor on the ctx's device in device mode. cols, rows, pitch,
+    image_bytes: the shape of every image of the job (svo_scene_size); channels: 3 or 4."""
+
+    def __init__(self, slam, seqs, style, cameras, device):
+        self._slam = slam
+        self.style, self.device_mode = style, bool(device)
+        self.seqs = None if seqs is None else [int(s) for s in seqs]
+        n = self._n = slam.n if seqs is None else len(self.seqs)
+        self.cols, self.rows = style.cols, style.rows
+        self.pitch, self.image_bytes = hip_lib.scene_size(style)
+        self.channels = hip_lib.PIXEL_BYTES[style.pixel]
+        self.capacity = n * self.image_bytes
+        if isinstance(cameras, hip_lib.SceneCamera):
+            cameras = [cameras] * n                       # one view of all
+        if len(cameras) != n:
+            raise ValueError(f"{len(cameras)} cameras for {n} named slots: one per named slot, or a single one for all")
+        self._cams = (hip_lib.SceneCamera * max(n, 1))(*cameras)
+        self._seg = np.zeros(max(n, 1), hip_lib.SCENE_SEGMENT_DTYPE)
+        self.segments = self._seg[:n]
+        self._buf = (torch.zeros(max(self.capacity, 4), dtype=torch.uint8, device=slam.device) if device
+                     else torch.zeros(max(self.capacity, 4), dtype=torch.uint8, pin_memory=True))
+        self._dst = hip_lib.SceneDst(self._seg.ctypes.data, self._buf.data_ptr(), self.capacity)
+        self._seq_arr = None if seqs is None else (C.c_int * max(n, 1))(*self.seqs)
+
+    @property
+    def pixels(self):
+        return self._buf if self.device_mode else self._buf.numpy()
+
+    def submit(self):
+        """queue the job (again: the same slots into the same buffers, once the previous one is delivered)"""
+        slam = self._slam
+        if self.device_mode:
+            torch.cuda.current_stream(slam.device).synchronize()     # (nothing of the caller's is still using the tensor)
+        _check(lib().svo_submit_export_scenes(slam._ctx, self._seq_arr, self._n, C.byref(self.style), self._cams,
+                                              C.byref(self._dst), hip_lib.MEM_DEVICE if self.device_mode else hip_lib.MEM_HOST))
+        return self
+
+    def wait(self):
+        self._slam.wait()
+        return self
+
+    def image(self, i):
+        """the image of named slot i: [rows, cols, 3 | 4], a view of `pixels` (numpy in host mode, a torch tensor in
+        device mode); None for a slot whose status is SCENE_NONE"""
+        e = self.segments[i]
+        if int(e["status"]) != hip_lib.SCENE_OK:
+            return None
+        lo = int(e["offset"])
+        return self.pixels[lo:lo + self.rows * self.pitch].reshape(self.rows, self.cols, self.channels)
+
+
 class Snapshot:
     """The sequence state of one slot (svo_submit_save / svo_submit_load): `host` (numpy uint8, the host part) and
     `data` (the data part: numpy uint8, or a torch uint8 tensor on the ctx's device in device mode). Valid after
@@ -612,6 +666,23 @@ class StereoSlamBatch:
         """submit_views + wait"""
         return self.submit_views(what, seqs, **kw).wait()
 
+    def submit_scenes(self, seqs=None, camera="front", device=False, style=None, **kw):
+        """svo_submit_export_scenes: queue the viewer's 3-D picture (keyframe points, trajectory, a frustum per
+        keyframe and at the current pose) of the slots `seqs` (None: all, in order) behind what was submitted so far;
+        nothing is waited for. camera: a preset name ("front", "top", "side"), one hip_lib.SceneCamera for all, or a
+        list with one per named slot; style: a hip_lib.SceneStyle, or its fields as keywords (hip_lib.scene_style:
+        cols, rows, pixel, point_size, colours, show, from_keyframe, trajectory_tail, filter). Returns a Scenes,
+        valid after its wait() (or the ctx's); its submit() queues the same job again into the same buffers."""
+        if style is None:
+            style = hip_lib.scene_style(**kw)
+        if isinstance(camera, str):
+            camera = hip_lib.scene_preset(camera, style.cols, style.rows)
+        return Scenes(self, seqs, style, camera, device).submit()
+
+    def export_scenes(self, seqs=None, **kw):
+        """submit_scenes + wait"""
+        return self.submit_scenes(seqs, **kw).wait()
+
     def snapshot_size(self, seq):
         """svo_snapshot_size: (host_bytes, data_bytes) a save of the slot needs right now (waits)."""
         hb, db = C.c_int64(0), C.c_int64(0)
@@ -866,4 +937,13 @@ class StereoSlam(StereoSlamBatch):
             return None
         kw["device"] = False
         img = self.export_views(what, None, **kw).image(0)
+        return None if img is None else img.copy()
+
+    def get_scene(self, camera="front", **kw):
+        """the viewer's 3-D picture of the map as a numpy array [rows, cols, 3 | 4] (export_scenes of the one slot:
+        camera, cols, rows, pixel, show, ...); None before the first frame"""
+        if self._ctx is None:
+            return None
+        kw["device"] = False
+        img = self.export_scenes(None, camera=camera, **kw).image(0)
         return None if img is None else img.copy()
