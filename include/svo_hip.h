@@ -83,6 +83,14 @@ int svo_build_lk_pyramid(svo_handle *h, int max_levels, int win, svo_image *leve
 int svo_remap_linear(svo_handle *h, int n, const svo_image *src, svo_image *dst,
                      const float *map_x, const float *map_y);
 
+/* R'  the same remap with a map per image (camera rigs): n_maps maps of one size (map_x[m] / map_y[m]: device, dst width x
+ * height floats, dense rows; host arrays of pointers), image i through map map_of_image[i] in [0, n_maps), in any order;
+ * a map that no image uses is allowed (it is checked, not read). The arithmetic is svo_remap_linear's. The images are
+ * sorted by map, and images that share a map share its loads as in svo_remap_linear. SVO_ERR_INVALID: n_maps < 1, an
+ * index out of range, a NULL map, dst images of mixed sizes; the handle stays usable. */
+int svo_remap_linear_multi(svo_handle *h, int n, const svo_image *src, svo_image *dst, int n_maps,
+                           const float *const *map_x, const float *const *map_y, const int *map_of_image);
+
 /* I   the per-pixel step of the reference's ImageInput classes before StereoSlam::new_image: cvtColor(BGR2GRAY)
  *     and the halves of a side-by-side frame (src/app/video_input.cpp:29-36), extractChannel of a 3-channel
  *     frame (src/app/econ_input.cpp:102-103). The arithmetic:
@@ -287,12 +295,46 @@ int svo_ctx_get_memory(svo_ctx *ctx, svo_memory *out);
  * device before the pyramids. left_* rectify the library's left image (the reference's M1r/M2r: cam1 with
  * RIGHT.*), right_* its right image (M1l/M2l). Each map: width x height floats, dense rows, host
  * (SVO_MEM_HOST) or device (SVO_MEM_DEVICE) memory; copied. All four NULL: off. Waits for queued frames.
- * The arithmetic is svo_remap_linear's. Every sequence of the ctx shares the maps (one camera rig); they
- * apply to every frame of every active sequence, keyframes and the first frame included. With
+ * The arithmetic is svo_remap_linear's. These are the maps of rig 0: every slot that is not bound to another rig
+ * (svo_ctx_assign_rigs) shares them; they apply to every frame of those slots, keyframes and the first frame included. With
  * SVO_MEM_DEVICE_BORROW and rectification on, the raw frames are read once and level 0 is the ctx's own
  * rectified image: the caller may reuse the raw buffers once the step is done (after svo_wait). */
 int svo_ctx_set_rectification(svo_ctx *ctx, const float *left_map_x, const float *left_map_y,
                               const float *right_map_x, const float *right_map_y, int mem);
+/* ---- camera rigs: slots of one ctx with their own intrinsics and rectification maps ------------------------------
+ * A rig is what differs between two units of one camera model: the ten float settings and, optionally, the four
+ * rectification maps (all four or none; ctx size, dense rows, host or device memory: mem; copied, as in
+ * svo_ctx_set_rectification). The integer settings, the image size and the input format stay the ctx's: they choose
+ * launch shapes and storage. Rig 0 always exists: the settings given to svo_ctx_create and whatever
+ * svo_ctx_set_rectification holds. Every slot starts bound to rig 0, and a ctx that never adds a rig behaves and
+ * launches as one without this interface. The slots of a group still share every launch: the kernels read the
+ * intrinsics from the slot's argument block, and the remap takes a map per image when the images of a step do not
+ * share one (svo_remap_linear_multi's kernel; slots whose rig has no maps are used as given in the same step, in
+ * place with SVO_MEM_DEVICE_BORROW: the lifetime rule above then holds per slot). A rig's maps take
+ * 2 x (6 B per pixel of the 64-aligned ctx size) of device memory. Maps are not part of a snapshot. */
+typedef struct svo_rig {            /* 80 bytes */
+    float baseline, fx, fy, cx, cy, k1, k2, k3, p1, p2;   /* as in svo_camera_settings; finite, fx, fy > 0 */
+    const float *left_map_x, *left_map_y, *right_map_x, *right_map_y;   /* all four or all NULL */
+    int32_t mem;                    /* of the maps: SVO_MEM_HOST / SVO_MEM_DEVICE */
+    int32_t _reserved;              /* 0 */
+} svo_rig;
+/* adds n rigs; ids[i] >= 1 receives the id of rigs[i]. Waits for queued work. A value that is not finite, fx or
+ * fy <= 0, some but not all maps, a bad mem: SVO_ERR_INVALID, nothing added. */
+int svo_ctx_add_rigs(svo_ctx *ctx, const svo_rig *rigs, int n, int *ids);
+/* removes the named rigs and frees their maps. Waits for queued work. Rig 0, an unknown id, or a rig that a slot is
+ * bound to: SVO_ERR_INVALID, nothing removed, the ctx carries on. */
+int svo_ctx_remove_rigs(svo_ctx *ctx, const int *ids, int n);
+/* binds slot seqs[i] to rig rigs[i]. Ordered with the frame sets exactly like svo_ctx_restart_sequences, and like it
+ * it ends the slot's sequence if it has one (the run goes to the finished runs, its storage back to the free lists):
+ * the slot's next frame is frame 0 of a new sequence under that rig, so a calibration never changes inside a
+ * sequence. The binding survives later restarts. Does not wait. A bad slot or an unknown rig: SVO_ERR_INVALID,
+ * nothing queued. A failed ctx rejects it like svo_submit_images. */
+int svo_ctx_assign_rigs(svo_ctx *ctx, const int *seqs, const int *rigs, int n);
+/* the rig the slot is bound to and the full settings it tracks with (either may be NULL). Waits like every getter. */
+int svo_ctx_get_slot_rig(svo_ctx *ctx, int seq, int *rig, svo_camera_settings *cam);
+/* *n = rigs of the ctx, rig 0 included; *map_bytes = device bytes of the maps of the added rigs (also counted in
+ * svo_memory.device_bytes). Either may be NULL. Waits. */
+int svo_ctx_get_rigs(svo_ctx *ctx, int *n, int64_t *map_bytes);
 /* The input format of the frames given to svo_new_image(s) / svo_submit_images from the next frame on, for every
  * active slot (a slot's first frame and keyframes included); may be switched between frames. Waits for queued
  * frames. Default SVO_INPUT_GRAY_PAIR: with it no launch, copy or allocation is added. The formats with ONE buffer
@@ -868,8 +910,10 @@ int svo_save_sequences(svo_ctx *ctx, const int *seqs, int n, svo_snapshot *snaps
  * running), then takes the saved state into image sets and keyframe storage from the ctx's own free lists; the
  * images are the sets' own copies. Every getter then returns for the slot what it returned at the source when
  * the save ran; the slot keeps its own run ordinal. Loading an empty snapshot is a restart.
- * Compatibility: camera settings, width, height and capacity must equal the ctx's byte for byte; solver mode,
- * input format, rectification, memory mode, group count, slot index, template-ring size and device are free.
+ * Compatibility: width, height and capacity must equal the ctx's, and the camera settings those of the target slot
+ * (the header has the settings of the saved slot's rig; the target's: its rig as of this call, svo_ctx_assign_rigs
+ * included) byte for byte; solver mode, input format, rectification maps, rig ids, memory mode, group count, slot
+ * index, template-ring size and device are free.
  * The host part is parsed and checked completely here, on the host, before anything is queued or changed: magic,
  * version, byte order, status, compatibility, every count against the capacity, every directory entry against
  * the extent its plane must have and the data part's size, the sizes against what was passed. A bad snapshot, an

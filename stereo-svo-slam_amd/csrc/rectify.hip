@@ -12,7 +12,7 @@
 //    OpenCV's int16 table stores 32767 for the weight 2^15 of an integer position and moves the
 //    remainder to another tap; the result is still v00 there (the difference is below 2^14).
 //
-// Two kernels:
+// The kernels:
 //  * remap_prep_kernel (once per map): float maps -> fixed point in 64x64 output tiles, with the
 //    non-finite / range rule applied explicitly (a plain float->int conversion is undefined in C++ for
 //    those and gives 0 for NaN on the GPU), plus per tile the bounding box of the source taps;
@@ -21,11 +21,16 @@
 //    Where the tile's source box, clipped to the image, fits REMAP_LDS_BYTES it is staged in LDS with
 //    dword loads and the four taps are gathered from there; otherwise (random or extreme maps) they are
 //    gathered from global memory. Four output pixels of a row per lane, stored as one dword.
+//  * remap_linear_multi_kernel (per frame, when the images of a launch do not share one map: camera rigs):
+//    the same per-image work, one workgroup per (output tile, chunk, side), where the host has sorted the
+//    images by map and cut every run of equal maps into chunks of at most REMAP_SPB images; and
+//    remap_linear_single_kernel, its form without the image loop for launches whose every chunk is one image.
 //
 // Every address a tap forms lies inside the source image (or the staged box, which is inside it): the
 // tests are on clamped int16 positions (|x|, |y| <= 16384), so nothing can wrap.
 #include "svo_kernels.hpp"
 
+#include <algorithm>
 #include <climits>
 
 namespace svo {
@@ -219,6 +224,135 @@ __global__ __launch_bounds__(REMAP_THREADS) void remap_linear_kernel(RemapLaunch
     }
 }
 
+// ---- a map per image. remap_linear_kernel above stays as it was measured; the forms below restate its
+// per-image work as functions of the tile's entries
+
+// the tile's map entries as a lane holds them: 16 positions, 16 fractions (two per dword), the tile's source box
+struct RemapTile {
+    uint32_t xy[16], fr[8];
+    int4 box;
+};
+
+__device__ __forceinline__ void remap_load_tile(const RemapMap& m, int t, int lane, RemapTile& e) {
+    const int r0 = lane >> 4;
+    SVO_GP(const uint4) pxy = (SVO_GP(const uint4))G(m.xy + (size_t)t * REMAP_ENTRIES);
+    SVO_GP(const uint2) pfr = (SVO_GP(const uint2))G(m.frac + (size_t)t * REMAP_ENTRIES);
+    for (int k = 0; k < 4; k++) {
+        const uint4 v = pxy[(r0 + 16 * k) * 16 + (lane & 15)];
+        const uint2 f = pfr[(r0 + 16 * k) * 16 + (lane & 15)];
+        e.xy[4 * k] = v.x; e.xy[4 * k + 1] = v.y; e.xy[4 * k + 2] = v.z; e.xy[4 * k + 3] = v.w;
+        e.fr[2 * k] = f.x; e.fr[2 * k + 1] = f.y;
+    }
+    e.box = *G(m.box + t);
+}
+
+// output tile (tx, ty) of one image through the entries `e`: the LDS box path where the tile's source box fits,
+// else the global gather (both kernels below)
+__device__ __forceinline__ void remap_image(const RemapTile& e, const RemapImg& im, int tx, int ty, int lane, uint32_t* s_src) {
+    const int c4 = (lane & 15) * 4, r0 = lane >> 4;
+    const int4 box = e.box;
+    const ImgView src = im.src, dst = im.dst;
+    // the tile's source box on this image (x0, y0 >= 0 already)
+    const int bx0 = box.x, bx1 = min(box.y, src.w - 1), by0 = box.z, by1 = min(box.w, src.h - 1);
+    const bool empty = bx1 < bx0 || by1 < by0;
+    const int xs = bx0 & ~3;                                   // staged from a dword boundary
+    const int nd = empty ? 0 : ((bx1 - xs) >> 2) + 1;          // dwords per staged row
+    const int rows = empty ? 0 : by1 - by0 + 1;
+    const bool dal = ((reinterpret_cast<uintptr_t>(dst.data) | (uintptr_t)dst.stride) & 3) == 0;
+    const int X = tx * REMAP_TILE + c4;
+    auto store = [&](int k, uint32_t v) {
+        const int Y = ty * REMAP_TILE + r0 + 16 * k;
+        if (Y >= dst.h || X >= dst.w) return;
+        SVO_GP(uint8_t) drow = dst.gw() + (size_t)Y * dst.stride;
+        if (dal && X + 3 < dst.w) {
+            *(SVO_GP(uint32_t))(drow + X) = v;
+        } else {
+            for (int j = 0; j < 4; j++)
+                if (X + j < dst.w) drow[X + j] = (uint8_t)(v >> (8 * j));
+        }
+    };
+    if ((long long)rows * nd * 4 <= REMAP_LDS_BYTES) {
+        __syncthreads();                                       // the previous image's gather is done
+        const bool al = ((reinterpret_cast<uintptr_t>(src.data) | (uintptr_t)src.stride) & 3) == 0;
+        SVO_GP(const uint8_t) sp = src.g();
+        for (int idx = lane; idx < rows * nd; idx += REMAP_THREADS) {
+            const int r = idx / nd, d = idx - r * nd;
+            const int col = xs + 4 * d;                        // 0 <= col <= bx1 < src.w
+            SVO_GP(const uint8_t) row = sp + (size_t)(by0 + r) * src.stride;
+            uint32_t v;
+            if (al && col + 3 < src.w) {
+                v = *(SVO_GP(const uint32_t))(row + col);
+            } else {
+                v = 0;
+                for (int j = 0; j < 4; j++)
+                    if (col + j < src.w) v |= (uint32_t)row[col + j] << (8 * j);
+            }
+            s_src[idx] = v;
+        }
+        __syncthreads();
+        const SVO_LDS(uint8_t)* lds = (const SVO_LDS(uint8_t)*)s_src;
+        const int pitch = nd * 4;
+        const unsigned bw = (unsigned)(bx1 - bx0), bh = (unsigned)(by1 - by0);
+        remap_gather(e.xy, e.fr, [&](int x, int y) -> int {
+            const bool in = !empty && (unsigned)(x - bx0) <= bw && (unsigned)(y - by0) <= bh;
+            return in ? (int)lds[(y - by0) * pitch + (x - xs)] : 0;
+        }, store);
+    } else {
+        SVO_GP(const uint8_t) sp = src.g();
+        remap_gather(e.xy, e.fr, [&](int x, int y) -> int {
+            const bool in = (unsigned)x < (unsigned)src.w && (unsigned)y < (unsigned)src.h;
+            return in ? (int)sp[(size_t)y * src.stride + x] : 0;
+        }, store);
+    }
+}
+
+// (the entries pass through an empty asm per image of a loop: otherwise the decoded positions and weights of
+// all 16 pixels are hoisted out of the image loop, 256 VGPRs instead of the ~60 the kernel needs)
+__device__ __forceinline__ void remap_pin_tile(RemapTile& e) {
+    for (int j = 0; j < 16; j++) asm volatile("" : "+v"(e.xy[j]));
+    for (int j = 0; j < 8; j++) asm volatile("" : "+v"(e.fr[j]));
+}
+
+// A map per image: workgroup (output tile, chunk blockIdx.y of the table, side). A chunk is at most REMAP_SPB
+// images of one run (images that share a map), so they still share the tile's map loads. LOOP = false: every
+// chunk of the launch is one image (a map of its own per image): no image loop, nothing kept live across one.
+template <bool LOOP>
+__device__ __forceinline__ void remap_multi(const RemapMultiLaunch& a, uint32_t* s_src) {
+    const int side = blockIdx.z;
+    const RemapChunk ch = G(a.chunks)[blockIdx.y];
+    RemapMap m = a.shape;                                      // the launch's maps differ in their storage only
+    const uint8_t* base = side ? ch.map[1] : ch.map[0];
+    m.xy = reinterpret_cast<const uint32_t*>(base);
+    m.frac = reinterpret_cast<const uint16_t*>(base + a.frac_offset);
+    m.box = reinterpret_cast<const int4*>(base + a.box_offset);
+    const int t = blockIdx.x;
+    const int tx = t % m.tiles_x, ty = t / m.tiles_x;
+    const int lane = threadIdx.x;
+    RemapTile e;
+    remap_load_tile(m, t, lane, e);
+    if (LOOP) {
+        const int i1 = min(a.n, ch.first + min(ch.count, REMAP_SPB));
+        for (int i = max(ch.first, 0); i < i1; i++) {
+            remap_pin_tile(e);
+            const RemapImg im = G(a.img)[side * a.n + i];
+            remap_image(e, im, tx, ty, lane, s_src);
+        }
+    } else if (ch.first >= 0 && ch.first < a.n) {
+        const RemapImg im = G(a.img)[side * a.n + ch.first];
+        remap_image(e, im, tx, ty, lane, s_src);
+    }
+}
+
+__global__ __launch_bounds__(REMAP_THREADS) void remap_linear_multi_kernel(RemapMultiLaunch a) {
+    __shared__ uint32_t s_src[REMAP_LDS_BYTES / 4];
+    remap_multi<true>(a, s_src);
+}
+
+__global__ __launch_bounds__(REMAP_THREADS) void remap_linear_single_kernel(RemapMultiLaunch a) {
+    __shared__ uint32_t s_src[REMAP_LDS_BYTES / 4];
+    remap_multi<false>(a, s_src);
+}
+
 void launch_remap_prep(const float* map_x, const float* map_y, const RemapMap& m, hipStream_t stream) {
     hipLaunchKernelGGL(remap_prep_kernel, dim3(m.tiles_x * m.tiles_y), dim3(REMAP_THREADS), 0, stream, map_x, map_y, m);
 }
@@ -227,6 +361,31 @@ void launch_remap(const RemapLaunch& a, int n_sides, hipStream_t stream) {
     const RemapMap& m = a.map[0];
     dim3 grid(m.tiles_x * m.tiles_y, (a.n + REMAP_SPB - 1) / REMAP_SPB, n_sides);
     hipLaunchKernelGGL(remap_linear_kernel, grid, dim3(REMAP_THREADS), 0, stream, a);
+}
+
+int remap_chunks(const int* map_of_image, int n, std::vector<int>& order, std::vector<RemapChunkSpan>& chunks) {
+    order.resize((size_t)n);
+    for (int i = 0; i < n; i++) order[i] = i;
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return map_of_image[a] < map_of_image[b]; });
+    chunks.clear();
+    int longest = 0;
+    for (int i0 = 0; i0 < n;) {
+        int i1 = i0 + 1;
+        while (i1 < n && map_of_image[order[i1]] == map_of_image[order[i0]]) i1++;
+        longest = std::max(longest, i1 - i0);
+        for (int k = i0; k < i1; k += REMAP_SPB) chunks.push_back({map_of_image[order[i0]], k, std::min(REMAP_SPB, i1 - k)});
+        i0 = i1;
+    }
+    return longest;
+}
+
+void launch_remap_multi(RemapMultiLaunch a, int w, int h, int n_chunks, bool single_images, int n_sides, hipStream_t stream) {
+    a.shape = remap_map_view(nullptr, w, h);
+    a.frac_offset = reinterpret_cast<uintptr_t>(a.shape.frac);   // (views on a null base: the offsets in a map's storage)
+    a.box_offset = reinterpret_cast<uintptr_t>(a.shape.box);
+    dim3 grid(a.shape.tiles_x * a.shape.tiles_y, n_chunks, n_sides);
+    if (single_images) hipLaunchKernelGGL(remap_linear_single_kernel, grid, dim3(REMAP_THREADS), 0, stream, a);
+    else hipLaunchKernelGGL(remap_linear_multi_kernel, grid, dim3(REMAP_THREADS), 0, stream, a);
 }
 
 }  // namespace svo

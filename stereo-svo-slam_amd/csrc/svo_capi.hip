@@ -227,6 +227,69 @@ extern "C" int svo_remap_linear(svo_handle* h, int n, const svo_image* src, svo_
     return SVO_OK;
 }
 
+extern "C" int svo_remap_linear_multi(svo_handle* h, int n, const svo_image* src, svo_image* dst, int n_maps,
+                                      const float* const* map_x, const float* const* map_y, const int* map_of_image) {
+    CHECK_H(h);
+    if (n < 1 || n_maps < 1 || !src || !dst || !map_x || !map_y || !map_of_image)
+        return svo_set_error(SVO_ERR_INVALID, "svo_remap_linear_multi: bad arguments");
+    const int w = dst[0].width, hgt = dst[0].height;
+    if (w < 1 || hgt < 1) return svo_set_error(SVO_ERR_INVALID, "svo_remap_linear_multi: empty map");
+    for (int m = 0; m < n_maps; m++)
+        if (!map_x[m] || !map_y[m]) return svo_set_error(SVO_ERR_INVALID, "svo_remap_linear_multi: map %d is NULL", m);
+    for (int i = 0; i < n; i++) {
+        if (map_of_image[i] < 0 || map_of_image[i] >= n_maps)
+            return svo_set_error(SVO_ERR_INVALID, "svo_remap_linear_multi: image %d: map %d of %d", i, map_of_image[i], n_maps);
+        if (!src[i].data || !dst[i].data || dst[i].width != w || dst[i].height != hgt || dst[i].stride < w)
+            return svo_set_error(SVO_ERR_INVALID, "svo_remap_linear_multi: image %d: every dst is the maps' size", i);
+        if (src[i].width < 1 || src[i].height < 1 || src[i].width > REMAP_MAX_SRC || src[i].height > REMAP_MAX_SRC ||
+            src[i].stride < src[i].width)
+            return svo_set_error(SVO_ERR_INVALID, "svo_remap_linear_multi: image %d: source of 1..%d pixels a side", i, REMAP_MAX_SRC);
+    }
+    // the images in map order, and the chunks of that order
+    std::vector<int> order;
+    std::vector<RemapChunkSpan> spans;
+    const int longest = remap_chunks(map_of_image, n, order, spans);
+    if (spans.size() > 65535) return svo_set_error(SVO_ERR_INVALID, "svo_remap_linear_multi: more than 65535 chunks in one call");
+    // workspace: the maps that have an image, in the kernels' form | image table | chunk table
+    std::vector<int> slot_of_map((size_t)n_maps, -1);
+    int used = 0;
+    for (const RemapChunkSpan& c : spans)
+        if (slot_of_map[c.map] < 0) slot_of_map[c.map] = used++;
+    const size_t map_bytes = remap_map_bytes(w, hgt);
+    const size_t img_bytes = (sizeof(RemapImg) * (size_t)n + 255) / 256 * 256;
+    const size_t need = map_bytes * used + img_bytes + sizeof(RemapChunk) * spans.size();
+    if (need > h->remap_ws_bytes) {
+        HIP_TRY(hipStreamSynchronize(h->stream));      // (the old workspace may still be read)
+        h->remap_ws.reset();
+        h->remap_ws_bytes = 0;
+        HIP_TRY(dev_malloc(h->remap_ws, need));
+        h->remap_ws_bytes = need;
+    }
+    uint8_t* ws = h->remap_ws.get();
+    std::vector<RemapImg> imgs((size_t)n);
+    for (int k = 0; k < n; k++) imgs[k] = RemapImg{make_view(src[order[k]]), make_view(dst[order[k]])};
+    std::vector<RemapChunk> chunks(spans.size());
+    for (size_t k = 0; k < spans.size(); k++) {
+        const uint8_t* base = ws + map_bytes * slot_of_map[spans[k].map];
+        chunks[k] = RemapChunk{{base, base}, spans[k].first, spans[k].count};
+    }
+    RemapImg* d_img = reinterpret_cast<RemapImg*>(ws + map_bytes * used);
+    RemapChunk* d_chunks = reinterpret_cast<RemapChunk*>(ws + map_bytes * used + img_bytes);
+    HIP_TRY(hipMemcpyAsync(d_img, imgs.data(), sizeof(RemapImg) * (size_t)n, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(d_chunks, chunks.data(), sizeof(RemapChunk) * chunks.size(), hipMemcpyHostToDevice, h->stream));
+    for (int m = 0; m < n_maps; m++) {
+        if (slot_of_map[m] < 0) continue;
+        launch_remap_prep(map_x[m], map_y[m], remap_map_view(ws + map_bytes * slot_of_map[m], w, hgt), h->stream);
+        HIP_TRY(hipGetLastError());
+    }
+    RemapMultiLaunch a;
+    std::memset(&a, 0, sizeof(a));
+    a.chunks = d_chunks; a.img = d_img; a.n = n;
+    launch_remap_multi(a, w, hgt, (int)chunks.size(), longest == 1, 1, h->stream);
+    HIP_TRY(hipGetLastError());
+    return SVO_OK;
+}
+
 extern "C" int svo_input_format_info(int format, int width, svo_input_layout* out) {
     const IngestFormat* f = ingest_format(format);
     if (!f || width < 1 || !out) return svo_set_error(SVO_ERR_INVALID, "svo_input_format_info: unknown format %d, width %d", format, width);

@@ -6,6 +6,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cmath>
 #include <condition_variable>
 #include <cstdlib>
 #include <cstring>
@@ -83,12 +84,14 @@ struct svo_ctx {
     // one entry of a group's queue: a frame set, or (restart non-empty) the end of some of its sequences, or
     // (exp.seqs non-empty) an export, or (snap.seqs / snap.loads non-empty) a save / a load, or (pose.seqs non-empty)
     // pose-filter updates, or (map.seqs non-empty) a map export, or (view.seqs non-empty) a view job, or (scene.seqs
-    // non-empty) a scene job
+    // non-empty) a scene job, or (assign non-empty) a rig assignment
     struct Job {
         std::vector<const uint8_t*> left, right;
         std::vector<float> ts;
         int stride = 0, mem = 0;
         std::vector<int> restart;        // indices in the group
+        std::vector<int> assign;         // indices in the group, and what each is bound to
+        std::vector<RigBinding> bindings;
         Export exp;
         Snapshots snap;
         PoseUpdates pose;
@@ -117,6 +120,22 @@ struct svo_ctx {
     svo::DevPtr<uint8_t> rect_mem;
     svo::RemapMap rect[2];
     int input_format = SVO_INPUT_GRAY_PAIR;      // svo_ctx_set_input_format (every group has the same)
+    // camera rigs (svo_ctx_add_rigs): rigs[id]; rigs[0] is the ctx's own settings (its maps: rect_mem). A removed
+    // rig leaves an unused entry, so ids stay what they were. slot_rig: what each slot is bound to once everything
+    // submitted so far has run (svo_ctx_assign_rigs records it at submit time).
+    struct Rig {
+        bool used = false;
+        svo_camera_settings cam{};
+        svo::DevPtr<uint8_t> maps;               // left map | right map, or null
+    };
+    std::vector<Rig> rigs;
+    std::vector<int> slot_rig;
+    size_t rig_map_bytes() const {
+        size_t b = 0;
+        for (size_t i = 1; i < rigs.size(); i++)
+            if (rigs[i].used && rigs[i].maps) b += 2 * svo::remap_map_bytes(width, height);
+        return b;
+    }
     bool one_buffer() const { return svo::ingest_format(input_format)->buffers == 1; }
 };
 
@@ -147,6 +166,8 @@ void worker_run_job(svo_ctx::Worker& w, const svo_ctx::Job& job) {
                        ? grp_save(w.g.get(), sn.seqs.data(), (int)sn.seqs.size(), sn.snaps.data(), sn.mem)
                    : !e.seqs.empty()
                        ? grp_export(w.g.get(), e.what, e.mem, e.seqs.data(), e.seg.data(), (int)e.seqs.size(), w.first, e.base, &e.dst)
+                   : !job.assign.empty()
+                       ? grp_assign_rigs(w.g.get(), job.assign.data(), job.bindings.data(), (int)job.assign.size())
                    : !job.restart.empty()
                        ? grp_restart_sequences(w.g.get(), job.restart.data(), (int)job.restart.size())
                        : grp_new_images(w.g.get(), job.left.data(), job.right.empty() ? nullptr : job.right.data(), job.stride,
@@ -247,6 +268,9 @@ extern "C" int svo_ctx_create(const svo_camera_settings* cam, int width, int hei
     std::unique_ptr<svo_ctx> c(new (std::nothrow) svo_ctx());
     if (!c) return svo_set_error(SVO_ERR_INVALID, "out of host memory");
     c->B = n_sequences; c->device = device; c->width = width; c->height = height;
+    c->rigs.resize(1);
+    c->rigs[0].used = true; c->rigs[0].cam = *cam;
+    c->slot_rig.assign(n_sequences, 0);
     int first = 0;
     for (int g = 0; g < G; g++) {
         const int count = n_sequences / G + (g < n_sequences % G ? 1 : 0);
@@ -277,7 +301,7 @@ extern "C" int svo_ctx_destroy(svo_ctx* c) {
         }
         w->g.reset();
     }
-    c->rect_mem.reset();                          // (after the groups that read it)
+    c->rect_mem.reset();                          // (after the groups that read it; the rigs' maps go with the ctx)
     delete c;
     return SVO_OK;
 }
@@ -567,7 +591,8 @@ extern "C" int svo_submit_load(svo_ctx* c, const int* seqs, int n, const svo_sna
     for (int i = 0; i < n; i++) {
         loads[i].seq = seqs[i];
         loads[i].data = snaps[i].data;
-        if (const int rc = grp_check_snapshot(c->workers[0]->g.get(), &snaps[i], &loads[i].host)) return rc;   // (every group has the same settings)
+        if (const int rc = grp_check_snapshot(c->workers[0]->g.get(), &c->rigs[c->slot_rig[seqs[i]]].cam, &snaps[i], &loads[i].host))
+            return rc;                           // (every group has the same size and capacity; the settings: the slot's rig's)
     }
     if (c->failed.load()) return reject_failed(c, "svo_submit_load");
     for (auto& wp : c->workers) {
@@ -662,6 +687,7 @@ extern "C" int svo_ctx_get_memory(svo_ctx* c, svo_memory* out) {
         out->image_sets += m.image_sets; out->image_sets_free += m.image_sets_free;
         out->keyframe_slabs += m.keyframe_slabs; out->keyframe_slabs_free += m.keyframe_slabs_free;
     }
+    out->device_bytes += (int64_t)c->rig_map_bytes();
     return SVO_OK;
 }
 
@@ -742,6 +768,137 @@ extern "C" int svo_ctx_set_rectification(svo_ctx* c, const float* left_map_x, co
     c->rect[1] = rect[1];
     c->rect_mem = std::move(mem_new);             // (frees the previous set)
     for (auto& w : c->workers) grp_set_rectification(w->g.get(), c->rect);
+    return SVO_OK;
+}
+
+// ------------------------------------------------------------------ camera rigs
+
+namespace {
+
+// the four float maps of a rig (host or device memory) into the kernels' form: left map | right map in `out`
+int build_rig_maps(svo_ctx* c, const float* const maps[4], int mem, svo::DevPtr<uint8_t>& out) {
+    const size_t map_bytes = svo::remap_map_bytes(c->width, c->height);
+    const size_t plane = sizeof(float) * (size_t)c->width * c->height;
+    svo::DevPtr<uint8_t> mem_new, stage;
+    HIP_TRY(svo::dev_malloc(mem_new, 2 * map_bytes));
+    if (mem == SVO_MEM_HOST) HIP_TRY(svo::dev_malloc(stage, 4 * plane));
+    svo::Stream st;                               // (uploads and conversion ordered on one stream of their own)
+    HIP_TRY(svo::make_stream(st));
+    const float* dev_maps[4];
+    for (int i = 0; i < 4; i++) {
+        dev_maps[i] = maps[i];
+        if (mem != SVO_MEM_HOST) continue;
+        float* d = reinterpret_cast<float*>(stage.get() + i * plane);
+        HIP_TRY(hipMemcpyAsync(d, maps[i], plane, hipMemcpyHostToDevice, st.get()));
+        dev_maps[i] = d;
+    }
+    for (int side = 0; side < 2; side++) {
+        svo::launch_remap_prep(dev_maps[2 * side], dev_maps[2 * side + 1],
+                               svo::remap_map_view(mem_new.get() + side * map_bytes, c->width, c->height), st.get());
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipStreamSynchronize(st.get()));
+    out = std::move(mem_new);
+    return SVO_OK;
+}
+
+bool rig_exists(const svo_ctx* c, int id) { return id >= 0 && id < (int)c->rigs.size() && c->rigs[id].used; }
+
+}  // namespace
+
+extern "C" int svo_ctx_add_rigs(svo_ctx* c, const svo_rig* rigs, int n, int* ids) {
+    if (!c || n < 0 || (n > 0 && (!rigs || !ids))) return svo_set_error(SVO_ERR_INVALID, "svo_ctx_add_rigs: bad arguments");
+    for (int i = 0; i < n; i++) {
+        const svo_rig& r = rigs[i];
+        const float v[10] = {r.baseline, r.fx, r.fy, r.cx, r.cy, r.k1, r.k2, r.k3, r.p1, r.p2};
+        for (float x : v)
+            if (!std::isfinite(x)) return svo_set_error(SVO_ERR_INVALID, "svo_ctx_add_rigs: rig %d has a value that is not finite", i);
+        if (!(r.fx > 0) || !(r.fy > 0)) return svo_set_error(SVO_ERR_INVALID, "svo_ctx_add_rigs: rig %d: fx and fy must be positive", i);
+        const int given = (r.left_map_x != nullptr) + (r.left_map_y != nullptr) + (r.right_map_x != nullptr) + (r.right_map_y != nullptr);
+        if ((given != 0 && given != 4) || (given == 4 && r.mem != SVO_MEM_HOST && r.mem != SVO_MEM_DEVICE) || r._reserved != 0)
+            return svo_set_error(SVO_ERR_INVALID, "svo_ctx_add_rigs: rig %d: give all four maps or none, mem host or device, _reserved 0", i);
+    }
+    const int rc = ctx_drain(c);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    // every rig is built before any is added: a failure adds nothing
+    std::vector<svo_ctx::Rig> made((size_t)n);
+    for (int i = 0; i < n; i++) {
+        const svo_rig& r = rigs[i];
+        svo_camera_settings& s = made[i].cam;
+        s = c->rigs[0].cam;                          // (the integer settings stay the ctx's)
+        s.baseline = r.baseline; s.fx = r.fx; s.fy = r.fy; s.cx = r.cx; s.cy = r.cy;
+        s.k1 = r.k1; s.k2 = r.k2; s.k3 = r.k3; s.p1 = r.p1; s.p2 = r.p2;
+        made[i].used = true;
+        if (!r.left_map_x) continue;
+        const float* const maps[4] = {r.left_map_x, r.left_map_y, r.right_map_x, r.right_map_y};
+        if (const int e = build_rig_maps(c, maps, r.mem, made[i].maps)) return e;
+    }
+    for (int i = 0; i < n; i++) {
+        ids[i] = (int)c->rigs.size();
+        c->rigs.push_back(std::move(made[i]));
+    }
+    return SVO_OK;
+}
+
+extern "C" int svo_ctx_remove_rigs(svo_ctx* c, const int* ids, int n) {
+    if (!c || n < 0 || (n > 0 && !ids)) return svo_set_error(SVO_ERR_INVALID, "svo_ctx_remove_rigs: bad arguments");
+    const int rc = ctx_drain(c);                  // (the groups are idle from here on: no frame reads the maps)
+    if (rc) return rc;
+    for (int i = 0; i < n; i++) {
+        if (ids[i] == 0 || !rig_exists(c, ids[i]))
+            return svo_set_error(SVO_ERR_INVALID, "svo_ctx_remove_rigs: rig %d is rig 0 or does not exist", ids[i]);
+        if (std::find(c->slot_rig.begin(), c->slot_rig.end(), ids[i]) != c->slot_rig.end())
+            return svo_set_error(SVO_ERR_INVALID, "svo_ctx_remove_rigs: a slot is bound to rig %d", ids[i]);
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    for (int i = 0; i < n; i++) {
+        c->rigs[ids[i]].used = false;
+        c->rigs[ids[i]].maps.reset();
+    }
+    return SVO_OK;
+}
+
+extern "C" int svo_ctx_assign_rigs(svo_ctx* c, const int* seqs, const int* rigs, int n) {
+    if (!c || n < 0 || (n > 0 && (!seqs || !rigs))) return svo_set_error(SVO_ERR_INVALID, "svo_ctx_assign_rigs: bad arguments");
+    for (int i = 0; i < n; i++) {
+        if (seqs[i] < 0 || seqs[i] >= c->B)
+            return svo_set_error(SVO_ERR_INVALID, "svo_ctx_assign_rigs: sequence %d out of range", seqs[i]);
+        if (!rig_exists(c, rigs[i])) return svo_set_error(SVO_ERR_INVALID, "svo_ctx_assign_rigs: rig %d does not exist", rigs[i]);
+    }
+    if (c->failed.load()) return reject_failed(c, "svo_ctx_assign_rigs");
+    const size_t map_bytes = svo::remap_map_bytes(c->width, c->height);
+    for (auto& wp : c->workers) {
+        svo_ctx::Worker& w = *wp;
+        svo_ctx::Job job;
+        for (int i = 0; i < n; i++) {
+            if (seqs[i] < w.first || seqs[i] >= w.first + w.count) continue;
+            const svo_ctx::Rig& r = c->rigs[rigs[i]];
+            const uint8_t* base = r.maps.get();
+            job.assign.push_back(seqs[i] - w.first);
+            job.bindings.push_back(RigBinding{rigs[i], r.cam, {base, base ? base + map_bytes : nullptr}});
+        }
+        if (!job.assign.empty()) worker_submit(w, std::move(job));
+    }
+    for (int i = 0; i < n; i++) c->slot_rig[seqs[i]] = rigs[i];
+    return SVO_OK;
+}
+
+extern "C" int svo_ctx_get_slot_rig(svo_ctx* c, int seq, int* rig, svo_camera_settings* cam) {
+    if (!c || seq < 0 || seq >= c->B) return svo_set_error(SVO_ERR_INVALID, "bad ctx / sequence index");
+    const int rc = ctx_drain(c);
+    if (rc) return rc;
+    if (rig) *rig = c->slot_rig[seq];
+    if (cam) *cam = c->rigs[c->slot_rig[seq]].cam;
+    return SVO_OK;
+}
+
+extern "C" int svo_ctx_get_rigs(svo_ctx* c, int* n, int64_t* map_bytes) {
+    if (!c) return svo_set_error(SVO_ERR_INVALID, "svo_ctx_get_rigs: bad ctx");
+    const int rc = ctx_drain(c);
+    if (rc) return rc;
+    if (n) *n = (int)std::count_if(c->rigs.begin(), c->rigs.end(), [](const svo_ctx::Rig& r) { return r.used; });
+    if (map_bytes) *map_bytes = (int64_t)c->rig_map_bytes();
     return SVO_OK;
 }
 

@@ -258,7 +258,9 @@ static int alloc_blocks(svo_group* c) {
     size_t off = 0;
     auto size = [&](auto& arr) { off += align_up(sizeof(typename std::decay_t<decltype(arr)>::type) * B, 256); };
     a.frame_arrays(size);
-    a.frame_bytes = off;                  // everything a tracked frame uploads; the rest is keyframe-only
+    a.frame_bytes = off;                  // everything a tracked frame uploads; the rest is keyframe-only ...
+    a.rig_arrays(size);
+    a.frame_rig_bytes = off;              // ... but for the chunk table of a step whose slots remap through different maps
     a.keyframe_arrays(size);
     a.bytes = off;
     HIP_TRY(pinned_malloc(a.host, a.bytes));
@@ -273,6 +275,7 @@ static int alloc_blocks(svo_group* c) {
         off += align_up(sizeof(T) * B, 256);
     };
     a.frame_arrays(place);
+    a.rig_arrays(place);
     a.keyframe_arrays(place);
 
     const size_t res_bytes = sizeof(FrameResult) * B, n_bytes = sizeof(int) * 2 * B, in_bytes = sizeof(int) * B;
@@ -373,6 +376,7 @@ int grp_create(const svo_camera_settings* cam, int width, int height, int n_sequ
     if ((rc = alloc_blocks(c))) return rc;
     for (Event& e : c->ev) HIP_TRY(make_event(e));
     c->seqs.resize(n_sequences);
+    for (Seq& q : c->seqs) q.cam = c->cam;                      // (rig 0)
     if ((rc = grow_set_slabs(c, 4 * n_sequences))) return rc;   // the first four image sets of every sequence: one allocation
     for (int s = 0; s < n_sequences; s++)
         if ((rc = alloc_sequence(c, c->seqs[s], s))) return rc;
@@ -478,6 +482,19 @@ int grp_restart_sequences(svo_group* c, const int* seqs, int n) {
     if (c->failed)
         return svo_set_error(SVO_ERR_INVALID, "svo_ctx_restart_sequences: an earlier frame of this ctx failed; create a new ctx");
     for (int i = 0; i < n; i++) end_sequence(c, seqs[i]);
+    return SVO_OK;
+}
+
+int grp_assign_rigs(svo_group* c, const int* seqs, const RigBinding* b, int n) {
+    if (c->failed)
+        return svo_set_error(SVO_ERR_INVALID, "svo_ctx_assign_rigs: an earlier frame of this ctx failed; create a new ctx");
+    for (int i = 0; i < n; i++) {
+        end_sequence(c, seqs[i]);
+        Seq& q = c->seqs[seqs[i]];
+        q.rig = b[i].rig; q.cam = b[i].cam;
+        q.rig_maps[0] = b[i].rig ? b[i].maps[0] : nullptr;
+        q.rig_maps[1] = b[i].rig ? b[i].maps[1] : nullptr;
+    }
     return SVO_OK;
 }
 

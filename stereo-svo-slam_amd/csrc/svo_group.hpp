@@ -25,6 +25,16 @@ int grp_new_images(svo_group* g, const uint8_t* const* left, const uint8_t* cons
 // the named sequences (indices in the group) end; their slots are empty until their next frame. Runs between two
 // steps of the group, on the thread that drives it. A failed group rejects it.
 int grp_restart_sequences(svo_group* g, const int* seqs, int n);
+// One group's share of svo_ctx_assign_rigs, between two steps of the group, on the thread that drives it: slot seqs[i]
+// (index in the group) ends its sequence like a restart and is bound to b[i]: the rig's id, the full settings of its
+// sequences from now on, and the storage of its left and right maps (owned by the ctx, valid while a slot is bound;
+// null: none; rig 0: ignored, its maps are grp_set_rectification's). A failed group rejects it.
+struct RigBinding {
+    int rig;
+    svo_camera_settings cam;
+    const uint8_t* maps[2];
+};
+int grp_assign_rigs(svo_group* g, const int* seqs, const RigBinding* b, int n);
 // One group's share of svo_submit_export, between two steps of the group, on the thread that drives it:
 // seqs[i] (index in the group; ctx slot seq0 + seqs[i]) is segment seg[i] of dst->segments; the group's records
 // start at record `base` of the caller's arrays (host or device memory: mem). Delivered on return. A failed group
@@ -56,15 +66,16 @@ int64_t grp_scene_bytes(const svo_scene_style* style);   // the image_bytes of a
 // what svo_map_size reports of a slot (the queues have drained)
 void grp_map_size(const svo_group* g, int seq, int from_keyframe, int* keyframes, int64_t* points_bound);
 // Snapshots (svo_submit_save / svo_submit_load). grp_check_snapshot: everything svo_submit_load checks of one
-// snapshot, on the caller's thread (it reads only what never changes in a group); *host_copy receives the checked
-// host part. grp_save / grp_load: one group's share, between two steps of the group, on the thread that drives it;
+// snapshot, on the caller's thread (it reads only what never changes in a group; slot_cam: the settings of the
+// target slot's rig); *host_copy receives the checked host part. grp_save / grp_load: one group's share, between two steps of the group, on the thread that drives it;
 // seqs / loads[i].seq are indices in the group; delivered on return. A failed group rejects them.
 struct SnapshotLoad {
     int seq;
     std::vector<uint8_t> host;        // the checked host part
     const void* data;                 // the data part (host or device memory: mem)
 };
-int grp_check_snapshot(const svo_group* g, const svo_snapshot* snap, std::vector<uint8_t>* host_copy);
+int grp_check_snapshot(const svo_group* g, const svo_camera_settings* slot_cam, const svo_snapshot* snap,
+                       std::vector<uint8_t>* host_copy);
 int grp_save(svo_group* g, const int* seqs, int n, const svo_snapshot* snaps, int mem);
 int grp_load(svo_group* g, const SnapshotLoad* loads, int n, int mem);
 int grp_snapshot_size(svo_group* g, int seq, int64_t* host_bytes, int64_t* data_bytes);   // (the queues have drained)

@@ -150,7 +150,7 @@ struct SavePlan {
 void plan_snapshot(const svo_group* c, const Seq& q, SavePlan& p) {
     SnapHeader& h = clear(p.h);
     h.magic = SVO_SNAPSHOT_MAGIC; h.version = SVO_SNAPSHOT_VERSION; h.byte_order = SVO_SNAPSHOT_BYTE_ORDER;
-    h.cam = c->cam; h.width = c->width; h.height = c->height; h.capacity = c->cap;
+    h.cam = q.cam; h.width = c->width; h.height = c->height; h.capacity = c->cap;
     h.pyramid_levels = c->cam.max_pyramid_levels; h.lk_levels = c->n_lk;
     h.frame_id = q.frame_id;
     if (q.frame_id >= 0) {
@@ -241,12 +241,13 @@ int grp_snapshot_size(svo_group* c, int s, int64_t* host_bytes, int64_t* data_by
     return SVO_OK;
 }
 
-int grp_check_snapshot(const svo_group* c, const svo_snapshot* snap, std::vector<uint8_t>* host_copy) {
+int grp_check_snapshot(const svo_group* c, const svo_camera_settings* slot_cam, const svo_snapshot* snap,
+                       std::vector<uint8_t>* host_copy) {
     if (const int rc = check_snapshot(snap->host, snap->host_capacity, *host_copy)) return rc;
     const SnapHeader& h = *reinterpret_cast<const SnapHeader*>(host_copy->data());
     if (h.status != SVO_SNAPSHOT_COMPLETE) SNAP_BAD("only the header was saved (a capacity was too small)");
-    if (std::memcmp(&h.cam, &c->cam, sizeof(h.cam)) != 0 || h.width != c->width || h.height != c->height || h.capacity != c->cap)
-        SNAP_BAD("camera settings, size or capacity differ from the ctx's");
+    if (std::memcmp(&h.cam, slot_cam, sizeof(h.cam)) != 0 || h.width != c->width || h.height != c->height || h.capacity != c->cap)
+        SNAP_BAD("camera settings, size or capacity differ from the target slot's");
     if (snap->data_capacity < h.data_bytes || (h.data_bytes > 0 && !snap->data))
         SNAP_BAD("the data part has %lld bytes of %lld", (long long)snap->data_capacity, (long long)h.data_bytes);
     return SVO_OK;

@@ -186,6 +186,12 @@ struct Seq {
     std::vector<ImageSet*> free_sets;
     ImageSet* cur_set = nullptr;
     ImageSet* prev_set = nullptr;
+    // the camera rig the slot is bound to (grp_assign_rigs; 0: the ctx's own), the settings its sequences track with
+    // (the ctx's integer settings, the rig's floats), and for rig >= 1 the storage of its left and right
+    // rectification maps (owned by the ctx; null: the rig has none). Rig 0 rectifies through svo_group::rect.
+    int rig = 0;
+    svo_camera_settings cam{};
+    const uint8_t* rig_maps[2] = {nullptr, nullptr};
     // host state
     PoseFilter kf;
     int frame_id = -1;               // -1: the slot is EMPTY (no sequence yet, or ended: end_sequence); its next frame is frame 0
@@ -216,7 +222,8 @@ struct ArgArray {
 };
 
 // every kernel's argument array, carved in this order out of one pinned block and one device block: the
-// tracked-frame arrays first, so that a tracked frame uploads them as one prefix copy (frame_bytes)
+// tracked-frame arrays first, so that a tracked frame uploads them as one prefix copy (frame_bytes), and right behind
+// them the chunk table of a multi-map remap, which a step that has one uploads in the same copy (frame_rig_bytes)
 struct ArgBlocks {
     ArgArray<PyrArgs> pyr;
     ArgArray<CompactArgs> compact;
@@ -226,16 +233,18 @@ struct ArgBlocks {
     ArgArray<SsdArgs> ssd;
     ArgArray<FilterArgs> filter;
     ArgArray<float[8]> guess;        // per sequence: the predicted pose
+    ArgArray<RemapChunk> remap_chunk;    // the chunks of a step's multi-map remap (slots on different rigs)
     ArgArray<DetectArgs> detect;
     ArgArray<MergeArgs> merge;
     ArgArray<KfInitArgs> kf_init;
     ArgArray<int> enable;            // (reserved)
     ArgArray<KfDev> kf_record;       // per sequence: staging of its newest keyframe's record
     template <typename F> void frame_arrays(F f) { f(pyr); f(compact); f(sia); f(klt); f(reproj); f(ssd); f(filter); f(guess); }
+    template <typename F> void rig_arrays(F f) { f(remap_chunk); }
     template <typename F> void keyframe_arrays(F f) { f(detect); f(merge); f(kf_init); f(enable); f(kf_record); }
     PinnedPtr<uint8_t> host;
     uint8_t* dev = nullptr;
-    size_t frame_bytes = 0, bytes = 0;
+    size_t frame_bytes = 0, frame_rig_bytes = 0, bytes = 0;
 };
 
 }  // namespace svo
@@ -258,8 +267,9 @@ struct svo_group {
     // host-resident input frames land here first (2 x B frames; runs of contiguous frames as one
     // copy) and are then ingested like device-resident ones
     uint8_t* d_stage_in = nullptr; size_t stage_frame_bytes = 0;
-    // rectification (svo_ctx_set_rectification): the ctx's two maps, or null; the image table of its launch
-    // (left images of the active sequences, then their right images) in a pinned block and its device mirror
+    // rectification (svo_ctx_set_rectification): the two maps of rig 0, or null (a slot on another rig: Seq::rig_maps);
+    // the image table of the remap launch (left images of the active sequences that remap, then their right images:
+    // in slot order while they share their maps, else sorted by map) in a pinned block and its device mirror
     const svo::RemapMap* rect = nullptr;
     svo::ArgArray<svo::RemapImg> remap_img;
     svo::PinnedPtr<svo::RemapImg> remap_img_host;

@@ -26,6 +26,14 @@ struct Step {
     std::vector<int> start;      // [B] 1: this is frame 0 of the sequence (the slot was empty): no tracking, a keyframe
     std::vector<int> need;       // [B] 1: the sequence makes a keyframe in this step
     int pyr_stream = -1;         // row block of the row-streaming pyramid kernel, 0: some frame does not fit it
+    // rectification: the active sequences whose rig has maps, in slot order (the storage of their two maps, their
+    // left and right table entries); once packed: do they all share their maps (then the single-map launch), else
+    // the chunks of the multi-map launch and whether every chunk is one image
+    struct Remap { const uint8_t* map[2]; RemapImg left, right; };
+    std::vector<Remap> remap;
+    bool remap_shared = true, remap_single = false;
+    int remap_chunks = 0;
+    bool copy_right = false;     // some sequence's right image is copied by the pyramid launch
     float stage_ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     std::chrono::steady_clock::time_point t0, lap_start;
 };
@@ -97,9 +105,50 @@ int stage_host_frames(svo_group* c, const Step& s) {
     return SVO_OK;
 }
 
+// the storage of the two maps that rectify the slot's frames (its rig's; rig 0: the ctx's), or nulls
+void slot_maps(const svo_group* c, const Seq& q, const uint8_t* maps[2]) {
+    for (int side = 0; side < 2; side++)
+        maps[side] = q.rig ? q.rig_maps[side] : c->rect ? reinterpret_cast<const uint8_t*>(c->rect[side].xy) : nullptr;
+}
+
+// the image table of the step's remap launch, and for maps that differ its chunk table
+void pack_remap(svo_group* c, Step& s) {
+    const int R = (int)s.remap.size();
+    for (const Step::Remap& r : s.remap)
+        s.remap_shared = s.remap_shared && r.map[0] == s.remap[0].map[0] && r.map[1] == s.remap[0].map[1];
+    std::vector<int> order((size_t)R);
+    for (int k = 0; k < R; k++) order[k] = k;
+    if (!s.remap_shared) {
+        // a rig's two maps are one allocation: the left map's address names the rig
+        std::vector<const uint8_t*> rigs;
+        for (const Step::Remap& r : s.remap) rigs.push_back(r.map[0]);
+        std::sort(rigs.begin(), rigs.end());
+        rigs.erase(std::unique(rigs.begin(), rigs.end()), rigs.end());
+        std::vector<int> map_of((size_t)R);
+        for (int k = 0; k < R; k++) map_of[k] = (int)(std::lower_bound(rigs.begin(), rigs.end(), s.remap[k].map[0]) - rigs.begin());
+        std::vector<RemapChunkSpan> spans;
+        s.remap_single = remap_chunks(map_of.data(), R, order, spans) == 1;
+        s.remap_chunks = (int)spans.size();                    // (<= R <= B: the table's size)
+        for (int k = 0; k < s.remap_chunks; k++) {
+            const Step::Remap& r = s.remap[order[spans[k].first]];
+            c->args.remap_chunk.h[k] = RemapChunk{{r.map[0], r.map[1]}, spans[k].first, spans[k].count};
+        }
+    }
+    for (int k = 0; k < R; k++) {
+        c->remap_img.h[k] = s.remap[order[k]].left;
+        c->remap_img.h[R + k] = s.remap[order[k]].right;
+    }
+}
+
 // every active sequence takes a fresh image set; its pyramid arguments
 int pack_pyramids(svo_group* c, Step& s) {
-    if (converts(c->input_format) && c->rect && !c->d_raw_gray) {
+    bool any_rect = false;
+    for (int seq : s.act) {
+        const uint8_t* maps[2];
+        slot_maps(c, c->seqs[seq], maps);
+        any_rect = any_rect || maps[0] != nullptr;
+    }
+    if (converts(c->input_format) && any_rect && !c->d_raw_gray) {
         c->raw_plane_bytes = align_up(align_up((size_t)c->width, 64) * c->height, 256);
         const int rc = dev_alloc(c, &c->d_raw_gray, c->raw_plane_bytes * 2 * c->B, false);
         if (rc) return rc;
@@ -122,6 +171,9 @@ int pack_pyramids(svo_group* c, Step& s) {
         const uint8_t* src_l = buf[c->fmt->left.buffer] + (size_t)c->fmt->left.start * c->width;    // (gray formats; unused
         const uint8_t* src_r = buf[c->fmt->right.buffer] + (size_t)c->fmt->right.start * c->width;  //  when the format converts)
         const int M = (int)s.act.size();
+        const uint8_t* maps[2];
+        slot_maps(c, q, maps);
+        const bool rect = maps[0] != nullptr;
         if (converts(c->input_format)) {
             // the ingest launch makes the gray images: straight into the set's own level 0 and right image, or,
             // with rectification on, into the group's raw planes, which the remap then reads (dense rows of the
@@ -129,23 +181,22 @@ int pack_pyramids(svo_group* c, Step& s) {
             is->left[0] = is->own_left0;
             is->right = is->own_right;
             ImgView gray_l = is->own_left0, gray_r = is->own_right;
-            if (c->rect) {
+            if (rect) {
                 const int pitch = (int)align_up((size_t)c->width, 64);
                 gray_l = ImgView{c->d_raw_gray + (size_t)seq * c->raw_plane_bytes, c->width, c->height, pitch};
                 gray_r = ImgView{c->d_raw_gray + (size_t)(c->B + seq) * c->raw_plane_bytes, c->width, c->height, pitch};
-                c->remap_img.h[j] = RemapImg{gray_l, is->own_left0};
-                c->remap_img.h[M + j] = RemapImg{gray_r, is->own_right};
+                s.remap.push_back({{maps[0], maps[1]}, RemapImg{gray_l, is->own_left0}, RemapImg{gray_r, is->own_right}});
             }
             c->ingest_img.h[j] = ingest_image(*c->fmt, 0, buf[c->fmt->left.buffer], s.stride, gray_l);
             c->ingest_img.h[M + j] = ingest_image(*c->fmt, 1, buf[c->fmt->right.buffer], s.stride, gray_r);
             hs.src_left = is->left[0];
-        } else if (c->rect) {
+        } else if (rect) {
             // rectification: the raw frames (in place, or from the staging buffer) are remapped into the
             // set's own level 0 and right image, then the pyramids are built from there (no ingest)
             is->left[0] = is->own_left0;
             is->right = is->own_right;
-            c->remap_img.h[j] = RemapImg{ImgView{src_l, c->width, c->height, s.stride}, is->own_left0};
-            c->remap_img.h[M + j] = RemapImg{ImgView{src_r, c->width, c->height, s.stride}, is->own_right};
+            s.remap.push_back({{maps[0], maps[1]}, RemapImg{ImgView{src_l, c->width, c->height, s.stride}, is->own_left0},
+                               RemapImg{ImgView{src_r, c->width, c->height, s.stride}, is->own_right}});
             hs.src_left = is->left[0];
         } else if (s.mem == SVO_MEM_DEVICE_BORROW) {
             // level 0 of both pyramids and the right image ARE the caller's images (like the
@@ -161,6 +212,7 @@ int pack_pyramids(svo_group* c, Step& s) {
             hs.src_left = ImgView{src_l, c->width, c->height, s.stride};
             hs.src_right = ImgView{src_r, c->width, c->height, s.stride};
             hs.dst_right = is->right;
+            s.copy_right = true;
         }
         is->lk[0] = is->left[0];
         for (int l = 0; l < hs.n_levels; l++) hs.level[l] = is->left[l];
@@ -169,6 +221,7 @@ int pack_pyramids(svo_group* c, Step& s) {
         const int rows = pyr_stream_rows(hs);
         s.pyr_stream = (s.pyr_stream == 0 || rows == 0) ? 0 : std::max(s.pyr_stream, rows);
     }
+    if (!s.remap.empty()) pack_remap(c, s);
     return SVO_OK;
 }
 
@@ -210,7 +263,7 @@ void pack_tracking_args(svo_group* c, const Step& st) {
             sa.prev[l] = q.prev_set->left[l];
             sa.cur[l] = q.cur_set->left[l];
         }
-        sa.cam = c->cam; sa.n_ptr = k.n; sa.kps2d = k.kps2d; sa.kps3d = k.kps3d; sa.flags = k.flags;
+        sa.cam = q.cam; sa.n_ptr = k.n; sa.kps2d = k.kps2d; sa.kps3d = k.kps3d; sa.flags = k.flags;
         sa.pose_guess = a.guess.d[s]; sa.pose_out = dr->pose_sia; sa.cost_out = &dr->sia_cost;
         sa.trace = dr->sia_trace; sa.kp_ws = q.sia_kpws;
         sa.rec_ws = q.sia_rec; sa.rec_cap = c->rec_cap;
@@ -222,16 +275,16 @@ void pack_tracking_args(svo_group* c, const Step& st) {
         ka.n_ptr = k.n; ka.prev_pts = nullptr; ka.cur_pts = q.tracked; ka.status = q.klt_status;
         ka.err = q.klt_err; ka.win = c->cam.window_size_opt_flow;
         ka.proj_pose = dr->pose_sia; ka.proj_mats = q.sia_mats; ka.kps3d = k.kps3d; ka.proj_out = k.kps2d;
-        ka.kp_index = k.kp_index; ka.ref_out = nullptr; ka.cam = c->cam;
+        ka.kp_index = k.kp_index; ka.ref_out = nullptr; ka.cam = q.cam;
         ReprojArgs& ra = clear(a.reproj.h[slot]);
-        ra.cam = c->cam; ra.n_ptr = k.n; ra.kps2d = k.kps2d; ra.kps3d = k.kps3d; ra.flags = k.flags;
+        ra.cam = q.cam; ra.n_ptr = k.n; ra.kps2d = k.kps2d; ra.kps3d = k.kps3d; ra.flags = k.flags;
         ra.tracked = q.tracked; ra.err = q.klt_err; ra.pose_in = dr->pose_sia;
         ra.pose_out = dr->pose_refined; ra.cost_out = &dr->reproj_cost; ra.trace = &dr->reproj_trace;
         ra.exact_pinv = c->exact_pinv;
         ra.zero_out = c->d_inside + s;      // filter_update_kernel adds to it
         pack_ssd(c, q, slot, 1, nullptr);
         FilterArgs& fa = clear(a.filter.h[slot]);
-        fa.cam = c->cam; fa.n_ptr = k.n; fa.frame_pose = dr->pose_refined;
+        fa.cam = q.cam; fa.n_ptr = k.n; fa.frame_pose = dr->pose_refined;
         fa.kps2d = k.kps2d; fa.kps3d = k.kps3d; fa.flags = k.flags;
         fa.outlier_count = k.outl; fa.inlier_count = k.inl; fa.kf_inv_depth = k.kfx;
         fa.kf_variance = k.kfP; fa.disparity = q.disparity;
@@ -257,7 +310,7 @@ int launch_tracking(svo_group* c, const Step& s) {
     const ArgBlocks& a = c->args;
     hipStream_t st = c->stream.get();
     const int M = (int)s.act.size(), T = (int)s.trk.size();
-    HIP_TRY(hipMemcpyAsync(a.dev, a.host.get(), a.frame_bytes, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(a.dev, a.host.get(), s.remap_chunks ? a.frame_rig_bytes : a.frame_bytes, hipMemcpyHostToDevice, st));
     const bool ingest = converts(c->input_format);
     if (ingest) {
         // both sides of every active sequence in one launch (chunks of the grid's z limit)
@@ -267,16 +320,25 @@ int launch_tracking(svo_group* c, const Step& s) {
             HIP_TRY(hipGetLastError());
         }
     }
-    if (c->rect) {
-        HIP_TRY(hipMemcpyAsync(c->remap_img.d, c->remap_img.h, sizeof(RemapImg) * 2 * M, hipMemcpyHostToDevice, st));
-        RemapLaunch ra;
-        ra.map[0] = c->rect[0]; ra.map[1] = c->rect[1];
-        ra.img = c->remap_img.d; ra.n = M;
-        launch_remap(ra, 2, st);
+    if (const int R = (int)s.remap.size()) {
+        // both sides of every sequence that is rectified in one launch: the single-map kernel while they share their
+        // maps (rig 0 only, or one rig for all of them), else a map per chunk (its table went up with the arguments)
+        HIP_TRY(hipMemcpyAsync(c->remap_img.d, c->remap_img.h, sizeof(RemapImg) * 2 * R, hipMemcpyHostToDevice, st));
+        if (s.remap_shared) {
+            RemapLaunch ra;
+            for (int side = 0; side < 2; side++)
+                ra.map[side] = remap_map_view(const_cast<uint8_t*>(s.remap[0].map[side]), c->width, c->height);
+            ra.img = c->remap_img.d; ra.n = R;
+            launch_remap(ra, 2, st);
+        } else {
+            RemapMultiLaunch ra;
+            clear(ra);
+            ra.chunks = a.remap_chunk.d; ra.img = c->remap_img.d; ra.n = R;
+            launch_remap_multi(ra, c->width, c->height, s.remap_chunks, s.remap_single, 2, st);
+        }
         HIP_TRY(hipGetLastError());
     }
-    launch_pyr_fused(a.pyr.d, M, c->width, c->height, !c->rect && !ingest && s.mem != SVO_MEM_DEVICE_BORROW,
-                     std::max(s.pyr_stream, 0), st);
+    launch_pyr_fused(a.pyr.d, M, c->width, c->height, s.copy_right, std::max(s.pyr_stream, 0), st);
     HIP_TRY(hipGetLastError());   // (every launch is checked on its own: a later success must not mask a failure)
     HIP_TRY(mark(c, 1));
     if (T == 0) {                 // only starting sequences: the stages of a tracked frame are empty
@@ -291,6 +353,9 @@ int launch_tracking(svo_group* c, const Step& s) {
     int grid_n = 1;
     for (int seq : s.trk) grid_n = std::max(grid_n, c->seqs[seq].n_host);
     grid_n = std::min(grid_n, c->cap);
+    // (the launchers take the ctx's settings: launch_sia and sia_pick_shape read max_pyramid_levels and
+    // min_pyramid_level_pose_estimation, launch_klt, launch_ssd and launch_detect are given windows, search ranges and
+    // grid sizes: integer settings only, which no rig changes. A slot's intrinsics are in its argument blocks.)
     const LaunchStatus sia_launch =
         launch_sia(a.sia.d, T, c->cam, c->width, c->height, grid_n, c->rec_cap, c->exact_pinv, st);
     HIP_TRY(sia_launch.err);
@@ -355,14 +420,14 @@ int pack_keyframe_args(svo_group* c, int slot, int s, bool first_frame) {
     da.n_levels = c->det_levels; da.grid_w = c->cam.grid_width; da.grid_h = c->cam.grid_height;
     da.out = q.det; da.n_out = q.n_det; da.max_cells = c->max_cells;
     MergeArgs& ma = clear(a.merge.h[slot]);
-    ma.cam = c->cam; ma.width = c->width; ma.height = c->height;
+    ma.cam = q.cam; ma.width = c->width; ma.height = c->height;
     ma.det = q.det; ma.n_det = q.n_det; ma.n_levels = c->det_levels; ma.max_cells = c->max_cells;
     ma.kps = q.kps[q.cur]; ma.cap = c->cap;
     ma.sel = q.sel; ma.sel_level = q.sel_level; ma.sel_cell = q.sel_cell; ma.occupied = q.occupied;
     ma.old_count = &dr->old_count; ma.overflow = &dr->overflow;
     pack_ssd(c, q, slot, 0, &dr->old_count);
     KfInitArgs& ia = clear(a.kf_init.h[slot]);
-    ia.cam = c->cam; ia.kps = q.kps[q.cur]; ia.old_count = &dr->old_count;
+    ia.cam = q.cam; ia.kps = q.kps[q.cur]; ia.old_count = &dr->old_count;
     ia.disparity = q.disparity; ia.frame_pose = dr->pose_refined;
     ia.first_frame = first_frame ? 1 : 0; ia.new_kf_id = id; ia.kfs = q.d_kfs;
     ia.color_lcg = q.color_lcg; ia.n_out = &dr->kf_n;

@@ -7,6 +7,7 @@
 
 #include <hip/hip_runtime.h>
 #include <mutex>
+#include <vector>
 
 #include "svo_device.hpp"
 
@@ -81,6 +82,27 @@ RemapMap remap_map_view(void* base, int w, int h);
 void launch_remap_prep(const float* map_x, const float* map_y, const RemapMap& m, hipStream_t stream);
 // n_sides = 1: map[0] and img[0..n); 2: both sides in one launch
 void launch_remap(const RemapLaunch& a, int n_sides, hipStream_t stream);
+// A map per image (camera rigs). The images of a launch are ordered by map; a chunk is at most 16 images
+// img[s * n + first .. first + count) of one run of equal maps, through the maps whose storage (the `base` of
+// remap_map_view) is map[s]. Every map of a launch has the same size.
+struct RemapChunk {
+    const uint8_t* map[2];
+    int first, count;
+};
+struct RemapMultiLaunch {
+    const RemapChunk* chunks;     // device, one per blockIdx.y
+    const RemapImg* img;
+    int n;                        // images per side
+    RemapMap shape;               // (filled by launch_remap_multi: sizes of a w x h map ...
+    size_t frac_offset, box_offset;   // ... and where its parts lie in its storage)
+};
+// images 0..n) sorted by map_of_image (stable) into `order`, and the chunks of that order as (map, first position in
+// `order`, count); returns the longest run
+struct RemapChunkSpan { int map, first, count; };
+int remap_chunks(const int* map_of_image, int n, std::vector<int>& order, std::vector<RemapChunkSpan>& chunks);
+// n_chunks <= 65535 chunks of maps of w x h; single_images: every chunk is one image (the kernel form without an
+// image loop); n_sides as launch_remap
+void launch_remap_multi(RemapMultiLaunch a, int w, int h, int n_chunks, bool single_images, int n_sides, hipStream_t stream);
 
 // ------------------------------------------------------------ input formats (ingest.hip)
 // The per-pixel step of the reference's ImageInput classes: gray from colour (cvtColor's 15-bit fixed point),

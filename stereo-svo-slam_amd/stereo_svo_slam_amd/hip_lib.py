@@ -43,6 +43,8 @@ SYMBOLS = (
     "svo_view_size", "svo_submit_export_views", "svo_export_views", "svo_render_views",
     "svo_scene_size", "svo_scene_look_at", "svo_scene_frustum", "svo_submit_export_scenes", "svo_export_scenes",
     "svo_render_scene",
+    "svo_remap_linear_multi", "svo_ctx_add_rigs", "svo_ctx_remove_rigs", "svo_ctx_assign_rigs", "svo_ctx_get_slot_rig",
+    "svo_ctx_get_rigs",
 )
 
 # svo_ctx_set_input_format / svo_convert_frames: how the buffers of a sequence become its two gray images
@@ -75,6 +77,25 @@ class CameraSettings(C.Structure):
         for name, _ in cls._fields_:
             setattr(cam, name, d[name])
         return cam
+
+
+RIG_FLOATS = ("baseline", "fx", "fy", "cx", "cy", "k1", "k2", "k3", "p1", "p2")
+
+
+class Rig(C.Structure):
+    """svo_rig (include/svo_hip.h): what differs between two units of one camera model."""
+    _fields_ = [(n, C.c_float) for n in RIG_FLOATS] + \
+               [(n, C.c_void_p) for n in ("left_map_x", "left_map_y", "right_map_x", "right_map_y")] + \
+               [("mem", C.c_int32), ("_reserved", C.c_int32)]
+
+    @classmethod
+    def from_dict(cls, d):
+        """the ten float settings of a camera-settings dict or CameraSettings (no maps)"""
+        get = d.__getitem__ if isinstance(d, dict) else lambda n: getattr(d, n)
+        return cls(**{n: get(n) for n in RIG_FLOATS})
+
+
+assert C.sizeof(Rig) == 80
 
 
 class Image(C.Structure):
@@ -496,6 +517,24 @@ class Handle:
         map_x, map_y = map_x.contiguous(), map_y.contiguous()
         outs = [torch.empty((h, w), dtype=torch.uint8, device=map_x.device) for _ in srcs]
         _check(lib().svo_remap_linear(self._h, len(srcs), _imgs(srcs), _imgs(outs), _ptr(map_x), _ptr(map_y)))
+        return outs
+
+    def remap_linear_multi(self, srcs, maps_x, maps_y, map_of_image):
+        """svo_remap_linear_multi: image i of `srcs` through map map_of_image[i] of maps_x / maps_y (lists of float32
+        [H, W] device tensors of one size), in any order; a list of uint8 [H, W] device tensors. The arithmetic is
+        remap_linear's."""
+        assert len(maps_x) == len(maps_y) and len(map_of_image) == len(srcs)
+        maps_x = [m.contiguous() for m in maps_x]
+        maps_y = [m.contiguous() for m in maps_y]
+        h, w = maps_x[0].shape
+        for m in maps_x + maps_y:
+            assert m.dtype == torch.float32 and tuple(m.shape) == (h, w) and m.is_cuda
+        outs = [torch.empty((h, w), dtype=torch.uint8, device=maps_x[0].device) for _ in srcs]
+        n_maps = len(maps_x)
+        px = (C.c_void_p * n_maps)(*[m.data_ptr() for m in maps_x])
+        py = (C.c_void_p * n_maps)(*[m.data_ptr() for m in maps_y])
+        idx = (C.c_int * max(len(srcs), 1))(*[int(i) for i in map_of_image])
+        _check(lib().svo_remap_linear_multi(self._h, len(srcs), _imgs(srcs), _imgs(outs), n_maps, px, py, idx))
         return outs
 
     # -- I ----------------------------------------------------------------

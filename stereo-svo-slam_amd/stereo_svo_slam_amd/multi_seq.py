@@ -77,11 +77,29 @@ def play_unequal(slam, frames_of, lengths, time_of=lambda k: k / 20.0):
     return done
 
 
-def queue_schedule(lengths, n_slots, order=None):
+def queue_schedule(lengths, n_slots, order=None, rigs=None):
     """Sequences played back to back on the slots of one ctx: a slot whose sequence has ended takes the next
     sequence of `order` at the very next step (order=None: longest first, the index as tie-break: the order
     of assign_longest_first). Returns one list per step of (slot, sequence, frame index), in slot order;
-    sequences without frames are never scheduled. No GPU involved."""
+    sequences without frames are never scheduled. No GPU involved.
+    rigs: the camera rig (svo_ctx_add_rigs id, 0: the ctx's own) of every sequence. The same schedule (a rig costs
+    no step), its entries (slot, sequence, frame index, rig, how): a freed slot takes the next sequence together with
+    its rig, and `how` says what the ctx is asked before a sequence's first frame: "assign" where the rig differs
+    from the one the slot is bound to (every slot starts on rig 0), "restart" where it is the same and the slot has
+    played before, None otherwise and for every later frame."""
+    if rigs is not None:
+        bound, played = [0] * n_slots, [False] * n_slots
+        steps = []
+        for step in queue_schedule(lengths, n_slots, order):
+            out = []
+            for slot, seq, k in step:
+                how = None
+                if k == 0:
+                    how = "assign" if rigs[seq] != bound[slot] else "restart" if played[slot] else None
+                    bound[slot], played[slot] = rigs[seq], True
+                out.append((slot, seq, k, rigs[seq], how))
+            steps.append(out)
+        return steps
     if order is None:
         order = sorted(range(len(lengths)), key=lambda i: (-lengths[i], i))
     waiting = [i for i in order if lengths[i] > 0]
@@ -103,60 +121,72 @@ def queue_schedule(lengths, n_slots, order=None):
         steps.append(step)
 
 
-def _queue_steps(n, frames_of, lengths, time_of, order):
+def _queue_steps(n, frames_of, lengths, time_of, order, rigs=None):
     """queue_schedule as calls on a ctx of n slots: [(slots to restart before the step, lefts, rights, time
     stamps)] with None for slots without a frame, {sequence: (slot, run ordinal in that slot)}, sequence-frames.
-    A slot is restarted before the first frame of every sequence but its first."""
+    A slot is restarted before the first frame of every sequence but its first. With rigs (one per sequence) a step
+    has a fifth entry, (slots, rigs) to assign before it: a slot whose next sequence is on another rig is assigned
+    instead of restarted (the assignment ends its sequence too)."""
     runs_started = [0] * n
     where, steps, frames = {}, [], 0
-    for step in queue_schedule(lengths, n, order):
+    for step in queue_schedule(lengths, n, order, rigs if rigs is not None else [0] * len(lengths)):
         L, R, ts = [None] * n, [None] * n, [0.0] * n
-        restart = []
-        for slot, seq, k in step:
+        restart, assign = [], ([], [])
+        for slot, seq, k, rig, how in step:
             if k == 0:
-                if runs_started[slot] > 0:
+                if how == "restart":
                     restart.append(slot)
+                elif how == "assign":
+                    assign[0].append(slot); assign[1].append(rig)
                 where[seq] = (slot, runs_started[slot])
                 runs_started[slot] += 1
             L[slot], R[slot] = frames_of(seq, k)
             ts[slot] = time_of(seq, k)
-        steps.append((restart, L, R, ts))
+        steps.append((restart, L, R, ts) if rigs is None else (restart, L, R, ts, assign))
         frames += len(step)
     return steps, where, frames
 
 
-def pack_queue(slam, frames_of, lengths, time_of=lambda s, k: k / 20.0, order=None, borrow=False):
+def pack_queue(slam, frames_of, lengths, time_of=lambda s, k: k / 20.0, order=None, borrow=False, rigs=None):
     """The steps of a pipelined play_queue built ahead (keeps Python out of a timed loop): a list of (slots to
-    restart before the step, packed frame set of slam.pack_images), then where and frames as play_queue
-    returns them."""
-    steps, where, frames = _queue_steps(slam.n, frames_of, lengths, time_of, order)
-    return [(restart, slam.pack_images(L, R, ts, borrow=borrow)) for restart, L, R, ts in steps], where, frames
+    restart before the step, packed frame set of slam.pack_images[, (slots, rigs) to assign before the step: with
+    rigs]), then where and frames as play_queue returns them."""
+    steps, where, frames = _queue_steps(slam.n, frames_of, lengths, time_of, order, rigs)
+    return [(st[0], slam.pack_images(st[1], st[2], st[3], borrow=borrow)) + tuple(st[4:]) for st in steps], where, frames
 
 
 def submit_queue(slam, steps):
-    """Queue the steps of pack_queue on the ctx (restarts and frame sets in order); nothing is waited for."""
-    for restart, packed in steps:
+    """Queue the steps of pack_queue on the ctx (restarts, rig assignments and frame sets in order); nothing is
+    waited for."""
+    for restart, packed, *assign in steps:
         if restart:
             slam.restart(restart)
+        if assign and assign[0][0]:
+            slam.assign_rigs(*assign[0])
         slam.submit_packed(packed)
 
 
-def play_queue(slam, frames_of, lengths, time_of=lambda s, k: k / 20.0, order=None, pipelined=False, borrow=False):
+def play_queue(slam, frames_of, lengths, time_of=lambda s, k: k / 20.0, order=None, pipelined=False, borrow=False,
+               rigs=None):
     """Drive a ctx through queue_schedule(lengths, slam.n, order): a slot is restarted before the first frame
     of every sequence but its first, slots without a frame get None, time stamps are per sequence
     (time_of(sequence, frame index)). frames_of(sequence, k) -> (left, right). pipelined: every frame set and
     restart is queued (svo_submit_images; torch frames, with borrow used in place) and waited for once at the
-    end; otherwise one new_images call per step. Returns ({sequence: (slot, run ordinal in that slot)},
+    end; otherwise one new_images call per step. rigs: the camera rig (an id of slam.add_rigs, 0: the ctx's own) of
+    every sequence; a freed slot takes the next sequence together with its rig (slam.assign_rigs instead of the
+    restart where the rig differs from the slot's). Returns ({sequence: (slot, run ordinal in that slot)},
     number of sequence-frames)."""
     if pipelined:
-        steps, where, frames = pack_queue(slam, frames_of, lengths, time_of, order, borrow)
+        steps, where, frames = pack_queue(slam, frames_of, lengths, time_of, order, borrow, rigs)
         submit_queue(slam, steps)
         slam.wait()
         return where, frames
-    steps, where, frames = _queue_steps(slam.n, frames_of, lengths, time_of, order)
-    for restart, L, R, ts in steps:
+    steps, where, frames = _queue_steps(slam.n, frames_of, lengths, time_of, order, rigs)
+    for restart, L, R, ts, *assign in steps:
         if restart:
             slam.restart(restart)
+        if assign and assign[0][0]:
+            slam.assign_rigs(*assign[0])
         slam.new_images(L, R, ts)
     return where, frames
 
@@ -164,12 +194,19 @@ def play_queue(slam, frames_of, lengths, time_of=lambda s, k: k / 20.0, order=No
 def move(src, src_slots, dst, dst_slots):
     """Move sequences between two ctxs (or two slots of one): a device-mode save of src's slots, their restart,
     then the load into dst's slots (any slot count, group layout or GPU of the same process: the data parts go
-    through a copy to dst's device when it differs). Waits for both ctxs. Returns the Snapshots (in dst's memory)."""
+    through a copy to dst's device when it differs). Waits for both ctxs. Returns the Snapshots (in dst's memory).
+    A slot's camera settings travel with it: a target slot that tracks with other settings is first bound to a rig
+    of dst with the source slot's settings (added to dst if it has none). Rectification maps are not part of a
+    snapshot and do not travel: such a rig of dst has none."""
     from .stereo_slam import Snapshot
     snaps = src.save(src_slots, device=True)
     src.restart(src_slots)
     if dst.device != src.device:
         snaps = [Snapshot(s.host, s.data.to(dst.device)) for s in snaps]
+    for s_slot, d_slot in zip(src_slots, dst_slots):
+        cam = src.slot_rig(s_slot)[1]
+        if bytes(dst.slot_rig(d_slot)[1]) != bytes(cam):
+            dst.assign_rigs([d_slot], [dst.find_rig(cam, add=True)])
     dst.load(dst_slots, snaps)
     return snaps
 

@@ -742,6 +742,79 @@ class StereoSlamBatch:
         arr = (C.c_int * max(len(seqs), 1))(*seqs)
         _check(lib().svo_ctx_restart_sequences(self._ctx, arr, len(seqs)))
 
+    # -- camera rigs ---------------------------------------------------------------------------------------
+    def add_rigs(self, rigs):
+        """svo_ctx_add_rigs: every rig is a dict (or CameraSettings) with the ten float settings baseline, fx, fy, cx,
+        cy, k1, k2, k3, p1, p2, and optionally (dict only) "left_maps" and "right_maps": (map_x, map_y) of the
+        library's left / right image as in set_rectification, float32 [H, W] numpy arrays or CUDA tensors (both or
+        neither). Waits for queued work. Returns the ids (>= 1; rig 0 is the ctx's own settings and
+        set_rectification's maps)."""
+        arr = (hip_lib.Rig * max(len(rigs), 1))()
+        keep = []
+        for i, r in enumerate(rigs):
+            arr[i] = hip_lib.Rig.from_dict(r)
+            maps = [*r["left_maps"], *r["right_maps"]] if isinstance(r, dict) and r.get("left_maps") is not None else None
+            if maps is None:
+                continue
+            on_dev = isinstance(maps[0], torch.Tensor)
+            maps = [m.to(dtype=torch.float32).contiguous() if on_dev else np.ascontiguousarray(m, np.float32) for m in maps]
+            for m in maps:
+                assert tuple(m.shape) == (self.height, self.width), "a rectification map has the ctx size"
+            keep.append(maps)
+            ptrs = [m.data_ptr() if on_dev else m.ctypes.data for m in maps]
+            arr[i].left_map_x, arr[i].left_map_y, arr[i].right_map_x, arr[i].right_map_y = ptrs
+            arr[i].mem = hip_lib.MEM_DEVICE if on_dev else hip_lib.MEM_HOST
+        if any(isinstance(m[0], torch.Tensor) for m in keep):
+            torch.cuda.current_stream(self.device).synchronize()
+        ids = (C.c_int * max(len(rigs), 1))()
+        _check(lib().svo_ctx_add_rigs(self._ctx, arr, len(rigs), ids))
+        for i in range(len(rigs)):                # (find_rig: the full settings of every rig added here)
+            cam = CameraSettings.from_buffer_copy(self.cam)
+            for name in hip_lib.RIG_FLOATS:
+                setattr(cam, name, getattr(arr[i], name))
+            self._rig_settings()[ids[i]] = bytes(cam)
+        return list(ids[:len(rigs)])
+
+    def _rig_settings(self):
+        if getattr(self, "_rig_cams", None) is None:
+            self._rig_cams = {0: bytes(self.cam)}
+        return self._rig_cams
+
+    def remove_rigs(self, ids):
+        """svo_ctx_remove_rigs: waits; SvoError (nothing removed) for rig 0 or while a slot is bound to one of them"""
+        ids = [int(i) for i in ([ids] if np.isscalar(ids) else ids)]
+        _check(lib().svo_ctx_remove_rigs(self._ctx, (C.c_int * max(len(ids), 1))(*ids), len(ids)))
+        for i in ids:
+            self._rig_settings().pop(i, None)
+
+    def assign_rigs(self, seqs, rigs):
+        """svo_ctx_assign_rigs: slot seqs[i] ends its sequence like restart() and is bound to rig rigs[i] (ordered with
+        the submitted frame sets, does not wait); its next frame is frame 0 of a new sequence under that rig."""
+        seqs, rigs = [int(s) for s in seqs], [int(r) for r in rigs]
+        assert len(seqs) == len(rigs)
+        n = len(seqs)
+        _check(lib().svo_ctx_assign_rigs(self._ctx, (C.c_int * max(n, 1))(*seqs), (C.c_int * max(n, 1))(*rigs), n))
+
+    def slot_rig(self, seq):
+        """svo_ctx_get_slot_rig: (rig id, CameraSettings the slot tracks with)"""
+        rig, cam = C.c_int(0), CameraSettings()
+        _check(lib().svo_ctx_get_slot_rig(self._ctx, seq, C.byref(rig), C.byref(cam)))
+        return rig.value, cam
+
+    def rigs(self):
+        """svo_ctx_get_rigs: (rigs of the ctx, rig 0 included; device bytes of the added rigs' maps)"""
+        n, b = C.c_int(0), C.c_int64(0)
+        _check(lib().svo_ctx_get_rigs(self._ctx, C.byref(n), C.byref(b)))
+        return n.value, b.value
+
+    def find_rig(self, cam, add=False):
+        """the id of a rig this object has added (or rig 0) whose settings equal `cam` (CameraSettings) byte for byte;
+        add: a rig without maps is added when there is none. None otherwise."""
+        for rid, b in self._rig_settings().items():
+            if b == bytes(cam):
+                return rid
+        return self.add_rigs([cam])[0] if add else None
+
     def finished_runs(self, seq):
         """The kept records of the slot's ended sequences, oldest first: [(RunInfo, trajectory[n, 6])]."""
         n = C.c_int(0)
