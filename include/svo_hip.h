@@ -1053,6 +1053,58 @@ int svo_filter_update_batch(svo_handle *h, int batch, int stride, const int32_t 
                             int32_t *inlier_count, float *kf_inv_depth, float *kf_variance,
                             int do_outlier_check, int do_update, int do_flags, int do_reproject, int width,
                             int height, int32_t *inside_count);
+/* Diagnostic: the KLT launch as the tracker makes it (svo_klt_track is the stage form: explicit start and reference
+ * positions, no template cache). One launch of grid (n_bound, batch) over `batch` sequences; per sequence (HOST
+ * array seqs[batch], every pointer in it device memory unless said otherwise):
+ *   the start position of point i is project_keypoints(pose, kps3d[i]) with the sequence's own camera settings,
+ *   computed in the kernel, from the rotation matrices of a one-thread launch (use_mats != 0) or from the pose alone;
+ *   the reference position is kfs[kf_id[i]].kps2d[kp_index[i]] (kf_id NULL: keyframe 0 for every point);
+ *   the template of (point, level) is read from / written to the keyframe's cache record (kp_index[i], level) when
+ *   the keyframe has a cache (tmpl != NULL), the cache was made for this window (tmpl_win == win) and
+ *   kp_index[i] < tmpl_cap; otherwise it is built and not kept.
+ * The cache memory is the caller's: tmpl holds [tmpl_cap][SVO_LK_LEVELS] records laid out as svo_klt_cache_layout
+ * says, tmpl_valid [tmpl_cap][SVO_LK_LEVELS] bytes (0: not stored yet; the kernel sets 1 when it stores a record).
+ * tmpl_bytes / tmpl_valid_bytes are the sizes of the two blocks; the call is refused if a cache that the launch
+ * would use is smaller than tmpl_cap records. The entry keeps nothing between calls.
+ * Outputs per point: tracked, status, err (INFINITY where status is 0), proj_out (the projection), ref_out (the
+ * gathered reference, or NULL). Entries [n, n_bound) of the outputs are not written. Before the launch the counts
+ * (0 <= *n <= n_bound), kf_id (0 <= id < n_kfs) and kp_index (0 <= index < that keyframe's n_kps) are read back
+ * and checked. win 3..35. Complete on return. */
+typedef struct svo_klt_keyframe {
+    svo_image lk[SVO_LK_LEVELS];    /* the keyframe's LK pyramid, views onto device memory                     */
+    int32_t n_lk;                   /* 1..SVO_LK_LEVELS                                                          */
+    int32_t n_kps;                  /* entries of kps2d                                                          */
+    const svo_kp2d *kps2d;
+    void *tmpl;                     /* or NULL: no cache                                                         */
+    uint8_t *tmpl_valid;            /* or NULL with tmpl NULL                                                    */
+    int64_t tmpl_bytes, tmpl_valid_bytes;
+    int32_t tmpl_cap, tmpl_win;
+} svo_klt_keyframe;
+typedef struct svo_klt_sequence {
+    const svo_klt_keyframe *kfs;    /* HOST array                                                                */
+    int32_t n_kfs;                  /* 1..8                                                                      */
+    int32_t n_cur;                  /* 1..SVO_LK_LEVELS                                                          */
+    svo_image cur[SVO_LK_LEVELS];   /* the current frame's LK pyramid                                            */
+    const int32_t *n;               /* [1] the number of points                                                  */
+    const int32_t *kf_id;           /* [n] or NULL                                                               */
+    const int32_t *kp_index;        /* [n]                                                                       */
+    const svo_kp3d *kps3d;          /* [n]                                                                       */
+    const float *pose;              /* [6]                                                                       */
+    svo_camera_settings cam;
+    svo_kp2d *tracked;              /* [n_bound] outputs ...                                                     */
+    uint8_t *status;
+    float *err;
+    svo_kp2d *proj_out;
+    svo_kp2d *ref_out;              /* ... or NULL                                                               */
+} svo_klt_sequence;
+int svo_klt_track_batch(svo_handle *h, int batch, const svo_klt_sequence *seqs, int n_bound, int win, int use_mats);
+/* Host only: the layout of a keyframe's KLT template cache for window `win` (3..35). A cache of tmpl_cap keypoints
+ * is tmpl_cap * *levels records of *record_bytes each, record (k, level) at ((k * *levels) + level) * *record_bytes,
+ * and tmpl_cap * *levels flag bytes in the same order. A record is the template proper (one wavefront's 64 lanes x
+ * 16 bytes per load, lane-major) and, at *header_offset, a header of *header_bytes: int32 state (0 reference window
+ * outside the image, 1 flat, 2 trackable; only a trackable record's body is written), float A11, A12, A22,
+ * double cI1, cI2. */
+int svo_klt_cache_layout(int win, int64_t *record_bytes, int64_t *header_offset, int64_t *header_bytes, int *levels);
 
 #ifdef __cplusplus
 }

@@ -212,6 +212,10 @@ struct KltTmpl {
     static constexpr int TQ = (3 * NPAIR + 3) / 4;
     static constexpr int BYTES = TQ * 64 * 16 + 64;
 };
+static_assert(KLT_THREADS == 64, "the cached template is addressed rec[q * 64 + tid] and sized for one wavefront per "
+                                 "keypoint (KltTmpl::BYTES): with more threads a keypoint's lanes would write into its header "
+                                 "and the next record");
+static_assert(sizeof(KltTmplHeader) <= 64, "the header's room behind the template");
 // the four 14-bit bilinear weights of calcOpticalFlowPyrLK for the fractions (fa, fb)
 __device__ inline LkWeights lk_weights(float fa, float fb) {
     const int W_BITS = 14;
@@ -784,6 +788,11 @@ namespace svo {
 size_t klt_template_bytes(int win) {
     return win + 1 <= 32 ? KltTmpl<8>::BYTES : KltTmpl<18>::BYTES;
 }
+// where a record's KltTmplHeader lies (behind the TQ x 64 uint4 of the template), and its size
+size_t klt_template_header_offset(int win) {
+    return (win + 1 <= 32 ? KltTmpl<8>::TQ : KltTmpl<18>::TQ) * 64 * 16;
+}
+size_t klt_template_header_bytes() { return sizeof(KltTmplHeader); }
 
 void launch_klt(const KltArgs* d_args, int batch, int max_n, int win, hipStream_t stream) {
     if (max_n <= 0) return;

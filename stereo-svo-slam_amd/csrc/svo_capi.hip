@@ -1177,3 +1177,116 @@ extern "C" int svo_solve6_check(svo_handle* h, const float* H_dev, const float* 
     HIP_TRY(hipGetLastError());
     return SVO_OK;
 }
+
+// svo_klt_track_batch: launch_klt with a batch of sequences, its argument blocks filled the way pack_tracking_args
+// (svo_group_step.hip) fills them: the fused projection through proj_mats or proj_pose, the reference position
+// gathered from the keyframe table, the keyframe's template cache. The table, the cache blocks and every array are
+// the caller's; the counts and the two index arrays are read back and checked before the launch (a diagnostic may
+// wait): an index beyond a keyframe's arrays would make a workgroup read or write a neighbour's memory.
+__global__ void klt_pose_mats_kernel(const float* const* poses, PoseMats* out) {
+    pose_mats(poses[blockIdx.x], out[blockIdx.x]);
+}
+
+static_assert(sizeof(svo_klt_keyframe) == 128 && sizeof(svo_klt_sequence) == 248, "the layouts the Python binding restates");
+static bool klt_bad_view(const svo_image& v) { return !v.data || v.width < 1 || v.height < 1 || v.stride < v.width; }
+
+extern "C" int svo_klt_track_batch(svo_handle* h, int batch, const svo_klt_sequence* seqs, int n_bound, int win,
+                                   int use_mats) {
+    CHECK_H(h);
+    if (batch < 1 || batch > 4096 || !seqs || n_bound < 0)
+        return svo_set_error(SVO_ERR_INVALID, "svo_klt_track_batch: need 1 <= batch <= 4096, seqs and n_bound >= 0");
+    if (win < 3 || win > 35) return svo_set_error(SVO_ERR_INVALID, "svo_klt_track_batch: window must be 3..35");
+    HIP_TRY(hipStreamSynchronize(h->stream));      // (the caller's arrays are read back below)
+    const size_t rec_bytes = klt_template_bytes(win);
+    std::vector<KfDev> table;
+    std::vector<size_t> first_kf((size_t)batch);
+    std::vector<int32_t> idx, ids;
+    for (int b = 0; b < batch; b++) {
+        const svo_klt_sequence& s = seqs[b];
+        if (!s.kfs || s.n_kfs < 1 || s.n_kfs > 8 || s.n_cur < 1 || s.n_cur > SVO_LK_LEVELS || !s.n || !s.pose ||
+            (n_bound > 0 && (!s.kp_index || !s.kps3d || !s.tracked || !s.status || !s.err || !s.proj_out)))
+            return svo_set_error(SVO_ERR_INVALID, "svo_klt_track_batch: sequence %d: bad arguments", b);
+        for (int l = 0; l < s.n_cur; l++)
+            if (klt_bad_view(s.cur[l])) return svo_set_error(SVO_ERR_INVALID, "svo_klt_track_batch: sequence %d: current level %d", b, l);
+        first_kf[(size_t)b] = table.size();
+        for (int k = 0; k < s.n_kfs; k++) {
+            const svo_klt_keyframe& f = s.kfs[k];
+            if (f.n_lk < 1 || f.n_lk > SVO_LK_LEVELS || f.n_kps < 0 || (f.n_kps > 0 && !f.kps2d))
+                return svo_set_error(SVO_ERR_INVALID, "svo_klt_track_batch: sequence %d keyframe %d: bad arguments", b, k);
+            for (int l = 0; l < f.n_lk; l++)
+                if (klt_bad_view(f.lk[l]))
+                    return svo_set_error(SVO_ERR_INVALID, "svo_klt_track_batch: sequence %d keyframe %d: level %d", b, k, l);
+            if (f.tmpl && f.tmpl_win == win) {       // a cache that the kernel will use
+                const int64_t recs = (int64_t)f.tmpl_cap * SVO_LK_LEVELS;
+                if (f.tmpl_cap < 0 || !f.tmpl_valid || f.tmpl_valid_bytes < recs || f.tmpl_bytes < recs * (int64_t)rec_bytes ||
+                    (reinterpret_cast<uintptr_t>(f.tmpl) & 15))
+                    return svo_set_error(SVO_ERR_INVALID, "svo_klt_track_batch: sequence %d keyframe %d: the cache needs %lld "
+                                         "records of %zu bytes, 16-byte aligned, and as many flags", b, k, (long long)recs, rec_bytes);
+            }
+            KfDev kf;
+            memset(&kf, 0, sizeof(kf));
+            kf.n_lk = f.n_lk;
+            for (int l = 0; l < f.n_lk; l++) kf.lk[l] = make_view(f.lk[l]);
+            kf.kps2d = const_cast<svo_kp2d*>(f.kps2d);
+            kf.n = f.n_kps;
+            kf.tmpl = f.tmpl; kf.tmpl_valid = f.tmpl_valid; kf.tmpl_cap = f.tmpl_cap; kf.tmpl_win = f.tmpl_win;
+            table.push_back(kf);
+        }
+        int32_t n = 0;
+        HIP_TRY(hipMemcpy(&n, s.n, sizeof(n), hipMemcpyDeviceToHost));
+        if (n < 0 || n > n_bound)
+            return svo_set_error(SVO_ERR_INVALID, "svo_klt_track_batch: sequence %d: n = %d is outside 0..n_bound = %d", b, n, n_bound);
+        idx.resize((size_t)n); ids.assign((size_t)n, 0);
+        if (n > 0) {
+            HIP_TRY(hipMemcpy(idx.data(), s.kp_index, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost));
+            if (s.kf_id) HIP_TRY(hipMemcpy(ids.data(), s.kf_id, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost));
+        }
+        for (int i = 0; i < n; i++)
+            if (ids[(size_t)i] < 0 || ids[(size_t)i] >= s.n_kfs || idx[(size_t)i] < 0 || idx[(size_t)i] >= s.kfs[ids[(size_t)i]].n_kps)
+                return svo_set_error(SVO_ERR_INVALID, "svo_klt_track_batch: sequence %d point %d: keyframe %d, index %d", b, i,
+                                     ids[(size_t)i], idx[(size_t)i]);
+    }
+    KfDev* d_table;
+    int rc = stage_blocks(h, table, &d_table);
+    if (rc) return rc;
+    DevPtr<PoseMats> mats;
+    if (use_mats) {
+        std::vector<const float*> poses((size_t)batch);
+        for (int b = 0; b < batch; b++) poses[(size_t)b] = seqs[b].pose;
+        const float** d_poses;
+        rc = stage_blocks(h, poses, &d_poses);
+        if (rc) return rc;
+        HIP_TRY(dev_malloc(mats, sizeof(PoseMats) * (size_t)batch));
+        klt_pose_mats_kernel<<<batch, 1, 0, h->stream>>>(d_poses, mats.get());
+        HIP_TRY(hipGetLastError());
+    }
+    std::vector<KltArgs> blocks((size_t)batch);
+    for (int b = 0; b < batch; b++) {
+        const svo_klt_sequence& s = seqs[b];
+        KltArgs& ka = blocks[(size_t)b];
+        memset(&ka, 0, sizeof(ka));
+        ka.kfs = d_table + first_kf[(size_t)b]; ka.kf_id = s.kf_id; ka.n_cur = s.n_cur;
+        for (int l = 0; l < s.n_cur; l++) ka.cur[l] = make_view(s.cur[l]);
+        ka.n_ptr = s.n; ka.prev_pts = nullptr; ka.cur_pts = s.tracked; ka.status = s.status;
+        ka.err = s.err; ka.win = win;
+        ka.proj_pose = s.pose; ka.proj_mats = use_mats ? mats.get() + b : nullptr; ka.kps3d = s.kps3d; ka.proj_out = s.proj_out;
+        ka.kp_index = s.kp_index; ka.ref_out = s.ref_out; ka.cam = s.cam;
+    }
+    KltArgs* d;
+    rc = stage_blocks(h, blocks, &d);
+    if (rc) { (void)hipStreamSynchronize(h->stream); return rc; }
+    launch_klt(d, batch, n_bound, win, h->stream);
+    const hipError_t launched = hipGetLastError();
+    HIP_TRY(hipStreamSynchronize(h->stream));      // (mats is freed on return: the launch is complete)
+    HIP_TRY(launched);
+    return SVO_OK;
+}
+
+extern "C" int svo_klt_cache_layout(int win, int64_t* record_bytes, int64_t* header_offset, int64_t* header_bytes, int* levels) {
+    if (win < 3 || win > 35) return svo_set_error(SVO_ERR_INVALID, "svo_klt_cache_layout: window must be 3..35");
+    if (record_bytes) *record_bytes = (int64_t)klt_template_bytes(win);
+    if (header_offset) *header_offset = (int64_t)klt_template_header_offset(win);
+    if (header_bytes) *header_bytes = (int64_t)klt_template_header_bytes();
+    if (levels) *levels = SVO_LK_LEVELS;
+    return SVO_OK;
+}

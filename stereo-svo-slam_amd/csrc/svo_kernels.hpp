@@ -221,6 +221,8 @@ struct KltArgs {
 };
 void launch_klt(const KltArgs* d_args, int batch, int max_n, int win, hipStream_t stream);
 size_t klt_template_bytes(int win);
+size_t klt_template_header_offset(int win);      // of the header (state, A11, A12, A22, cI1, cI2) within a record
+size_t klt_template_header_bytes();
 
 // ------------------------------------------- merge + reprojection GN (B1,B3)
 struct ReprojArgs {

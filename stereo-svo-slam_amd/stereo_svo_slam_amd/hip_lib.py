@@ -45,6 +45,7 @@ SYMBOLS = (
     "svo_render_scene",
     "svo_remap_linear_multi", "svo_ctx_add_rigs", "svo_ctx_remove_rigs", "svo_ctx_assign_rigs", "svo_ctx_get_slot_rig",
     "svo_ctx_get_rigs",
+    "svo_klt_track_batch", "svo_klt_cache_layout",
 )
 
 # svo_ctx_set_input_format / svo_convert_frames: how the buffers of a sequence become its two gray images
@@ -101,6 +102,24 @@ assert C.sizeof(Rig) == 80
 class Image(C.Structure):
     _fields_ = [("data", C.c_void_p), ("width", C.c_int32), ("height", C.c_int32),
                 ("stride", C.c_int32)]
+
+
+class KltKeyframe(C.Structure):
+    """svo_klt_keyframe (include/svo_hip.h): one keyframe of svo_klt_track_batch."""
+    _fields_ = [("lk", Image * 3), ("n_lk", C.c_int32), ("n_kps", C.c_int32), ("kps2d", C.c_void_p),
+                ("tmpl", C.c_void_p), ("tmpl_valid", C.c_void_p), ("tmpl_bytes", C.c_int64),
+                ("tmpl_valid_bytes", C.c_int64), ("tmpl_cap", C.c_int32), ("tmpl_win", C.c_int32)]
+
+
+class KltSequence(C.Structure):
+    """svo_klt_sequence (include/svo_hip.h): one sequence of svo_klt_track_batch."""
+    _fields_ = [("kfs", C.POINTER(KltKeyframe)), ("n_kfs", C.c_int32), ("n_cur", C.c_int32), ("cur", Image * 3),
+                ("n", C.c_void_p), ("kf_id", C.c_void_p), ("kp_index", C.c_void_p), ("kps3d", C.c_void_p),
+                ("pose", C.c_void_p), ("cam", CameraSettings)] + \
+               [(n, C.c_void_p) for n in ("tracked", "status", "err", "proj_out", "ref_out")]
+
+
+assert (C.sizeof(KltKeyframe), C.sizeof(KltSequence)) == (128, 248)
 
 
 class InputSide(C.Structure):
@@ -398,6 +417,14 @@ def detect_shape(width, height, n_levels, grid_width, grid_height):
     out = [C.c_int(0) for _ in range(4)]
     _check(lib().svo_detect_shape(width, height, n_levels, grid_width, grid_height, *[C.byref(o) for o in out]))
     return tuple(o.value for o in out)
+
+
+def klt_cache_layout(win):
+    """svo_klt_cache_layout (host only): (record_bytes, header_offset, header_bytes, levels) of a keyframe's KLT
+    template cache for window `win`."""
+    rec, off, hb, lv = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_int(0)
+    _check(lib().svo_klt_cache_layout(int(win), C.byref(rec), C.byref(off), C.byref(hb), C.byref(lv)))
+    return rec.value, off.value, hb.value, lv.value
 
 
 def export_capacity(cam, width, height):
@@ -736,6 +763,39 @@ class Handle:
         _check(lib().svo_klt_track(self._h, _imgs(prev_lk), _imgs(cur_lk), nl, _ptr(prev_pts),
                                    _ptr(cur_pts), n, win, _ptr(status), _ptr(err)))
         return cur_pts, status, err
+
+    def klt_track_batch(self, seqs, n_bound, win, use_mats):
+        """Diagnostic: svo_klt_track_batch, the KLT launch as the tracker makes it, over len(seqs) sequences. A
+        sequence is a dict of device tensors: kfs (list of keyframes: dict(lk=[levels], kps2d float32 [m, 2],
+        tmpl / valid uint8 tensors or None, tmpl_cap, tmpl_win)), cur ([levels]), n (int32 [1]), kf_id (int32 [n]
+        or None), kp_index (int32 [n]), kps3d (float32 [n, 3]), pose (float32 [6]), cam (CameraSettings), and the
+        outputs tracked, status, err, proj_out, ref_out (or None), which are written in place. Complete on return."""
+        arr = (KltSequence * len(seqs))()
+        keep = []
+        for b, s in enumerate(seqs):
+            kfs = (KltKeyframe * len(s["kfs"]))()
+            keep.append(kfs)
+            for k, f in enumerate(s["kfs"]):
+                for l, im in enumerate(f["lk"]):
+                    kfs[k].lk[l] = _img(im)
+                tm, va = f.get("tmpl"), f.get("valid")
+                kfs[k].n_lk, kfs[k].n_kps, kfs[k].kps2d = len(f["lk"]), f["kps2d"].shape[0], _ptr(f["kps2d"])
+                kfs[k].tmpl, kfs[k].tmpl_valid = _ptr(tm), _ptr(va)
+                kfs[k].tmpl_bytes = 0 if tm is None else tm.numel() * tm.element_size()
+                kfs[k].tmpl_valid_bytes = 0 if va is None else va.numel() * va.element_size()
+                kfs[k].tmpl_cap, kfs[k].tmpl_win = int(f.get("tmpl_cap", 0)), int(f.get("tmpl_win", 0))
+            a = arr[b]
+            a.kfs, a.n_kfs, a.n_cur = kfs, len(s["kfs"]), len(s["cur"])
+            for l, im in enumerate(s["cur"]):
+                a.cur[l] = _img(im)
+            assert s["n"].dtype == torch.int32 and s["kp_index"].dtype == torch.int32
+            assert s.get("kf_id") is None or s["kf_id"].dtype == torch.int32
+            a.n, a.kf_id, a.kp_index, a.kps3d, a.pose = (_ptr(s["n"]), _ptr(s.get("kf_id")), _ptr(s["kp_index"]),
+                                                         _ptr(s["kps3d"]), _ptr(s["pose"]))
+            a.cam = s["cam"]
+            a.tracked, a.status, a.err, a.proj_out, a.ref_out = (_ptr(s["tracked"]), _ptr(s["status"]), _ptr(s["err"]),
+                                                                 _ptr(s["proj_out"]), _ptr(s.get("ref_out")))
+        _check(lib().svo_klt_track_batch(self._h, len(seqs), arr, int(n_bound), int(win), int(bool(use_mats))))
 
     # -- B1 + B3 ----------------------------------------------------------
     def pinv6_check(self, H, impl):

@@ -460,6 +460,56 @@ def test_klt_template_cache_changes_nothing(monkeypatch):
             assert all(np.array_equal(x, y) for x, y in zip(a, b)), (k, i)
 
 
+@pytest.mark.parametrize("win", [21, 35])
+def test_klt_ring_of_three_slots_changes_nothing(monkeypatch, win):
+    """The same sequence in three slots of one group whose keyframe ids, and so their places in the template ring,
+    differ at every step: slot 1 is restarted after 5 frames and slot 2 after 11, then each runs all 36 frames. With
+    the ring off (SVO_KLT_CACHE_KF=0), a ring of one keyframe and a ring of two (every slot makes four keyframes, so
+    either ring wraps, at a different step in every slot), in both kernel shapes (window 21: 32 columns, 35: 36
+    columns): every frame of every slot is the oracle's and the ring-off run's."""
+    n_frames, delays = 36, (0, 5, 11)
+    cfg, L, R, poses, ts = synth.make_sequence("tiny", n_frames, 2, device="cpu", motion_scale=4.0,
+                                               overrides={"window_size_opt_flow": win})
+    L, R = [x.numpy() for x in L], [x.numpy() for x in R]
+    ref = O.Slam(util.oracle_camera(cfg))
+    oracle = []
+    for i in range(n_frames):
+        ref.new_image(L[i], R[i], float(ts[i]))
+        k2, k3, info = ref.keypoints()
+        oracle.append((k2, k3, info, ref.pose()))
+    n_kf = ref.num_keyframes()
+    assert n_kf >= 3, "the sequence stopped making keyframes: the rings never wrap"
+    base = None
+    for ring in ("0", "1", "2"):
+        monkeypatch.setenv("SVO_KLT_CACHE_KF", ring)
+        ctx = StereoSlamBatch(cfg, cfg["width"], cfg["height"], 3)
+        assert ctx.groups() == 1
+        frames = [[None] * n_frames for _ in delays]
+        for step in range(n_frames + max(delays)):
+            again = [s for s, d in enumerate(delays) if d and step == d]
+            if again:
+                ctx.restart(again)
+            # (a slot plays the sequence from step 0; its restart makes it begin again)
+            at = [step - d if step >= d else step for d in delays]
+            live = [k < n_frames for k in at]
+            ctx.new_images([L[k] if ok else None for k, ok in zip(at, live)], [R[k] if ok else None for k, ok in zip(at, live)],
+                           [float(ts[min(k, n_frames - 1)]) for k in at])
+            for s, (k, ok) in enumerate(zip(at, live)):
+                if ok and step >= delays[s]:
+                    f = ctx.get_frame(s)
+                    k2, k3, info, pose = oracle[k]
+                    _compare_frame(f"window {win} ring {ring} slot {s} frame {k}", f, k2, k3, info, pose, 0.0)
+                    frames[s][k] = (f.pose.copy(), f.kps2d.copy(), f.kps3d.copy(), f.info.copy())
+        for s in range(len(delays)):
+            assert ctx.num_keyframes(s) == n_kf, (ring, s, ctx.num_keyframes(s))
+        ctx.close()
+        if base is None:
+            base = frames[0]
+        for s in range(len(delays)):
+            for k in range(n_frames):
+                assert all(np.array_equal(x, y) for x, y in zip(base[k], frames[s][k])), (win, ring, s, k)
+
+
 def test_update_pose_matches_oracle():
     cfg = dict(synth.CONFIGS["tiny"])
     gpu = StereoSlamBatch(cfg, cfg["width"], cfg["height"], 1)

@@ -203,7 +203,8 @@ def _bilinear(pad, ix, iy, win, wts, shift):
 def klt_ref(prev_levels, cur_levels, prev_pts, init, win):
     """(pts [n, 2] float32, status [n] uint8, err [n] float32, info). info: labels [n][level] (None for a
     level that was not entered), sums [n, levels, 5] int64 (largest |A11|, |A12|, |A22|, |b1|, |b2| met; A12
-    signed in a12 [n, levels]), moved [n, levels, 2] float32 (position after the level minus before it)."""
+    signed in a12 [n, levels]), moved [n, levels, 2] float32 (position after the level minus before it), ci
+    [n, levels, 2] int64 (sum I Ix, sum I Iy over the reference window: constants of a level's template)."""
     nl = min(len(prev_levels), len(cur_levels))
     n = len(prev_pts)
     half = F(win - 1) * F(0.5)
@@ -218,6 +219,7 @@ def klt_ref(prev_levels, cur_levels, prev_pts, init, win):
     labels = [[None] * nl for _ in range(n)]
     sums = np.zeros((n, nl, 5), np.int64)
     a12 = np.zeros((n, nl), np.int64)
+    ci = np.zeros((n, nl, 2), np.int64)
     moved = np.zeros((n, nl, 2), F)
     for i in range(n):
         for level in range(nl - 1, -1, -1):
@@ -245,6 +247,7 @@ def klt_ref(prev_levels, cur_levels, prev_pts, init, win):
             iA11, iA12, iA22 = int((Ix * Ix).sum()), int((Ix * Iy).sum()), int((Iy * Iy).sum())
             sums[i, level, :3] = abs(iA11), abs(iA12), abs(iA22)
             a12[i, level] = iA12
+            ci[i, level] = int((Iw * Ix).sum()), int((Iw * Iy).sum())
             A11, A12, A22 = F(iA11) * scale20, F(iA12) * scale20, F(iA22) * scale20
             Dt = A11 * A22 - A12 * A12
             dif = A11 - A22
@@ -284,7 +287,8 @@ def klt_ref(prev_levels, cur_levels, prev_pts, init, win):
                     label = "backed_off"
                     break
                 pdx, pdy = dx, dy
-            moved[i, level] = pts[i] - start
+            with np.errstate(invalid="ignore"):                 # (an infinite start stays where it is)
+                moved[i, level] = pts[i] - start
             if status[i] and level == 0:
                 npx, npy = pts[i, 0] - half, pts[i, 1] - half
                 inx, iny = _floor(npx), _floor(npy)
@@ -297,7 +301,7 @@ def klt_ref(prev_levels, cur_levels, prev_pts, init, win):
                     err[i] = F(int(np.abs(diff).sum())) * F(1) / F(32 * win * win)   # (< 2^24: the float sum is exact)
             labels[i][level] = label
     err[status == 0] = np.inf
-    return pts, status, err, dict(labels=labels, sums=sums, a12=a12, moved=moved)
+    return pts, status, err, dict(labels=labels, sums=sums, a12=a12, moved=moved, ci=ci)
 
 
 # ------------------------------------------------------------------ case lists
