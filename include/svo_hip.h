@@ -91,6 +91,34 @@ int svo_remap_linear(svo_handle *h, int n, const svo_image *src, svo_image *dst,
 int svo_remap_linear_multi(svo_handle *h, int n, const svo_image *src, svo_image *dst, int n_maps,
                            const float *const *map_x, const float *const *map_y, const int *map_of_image);
 
+/* M   cv::initUndistortRectifyMap(K, D, R, P, size, CV_32F, map_x, map_y)   src/app/euroc_input.cpp:24-49
+ * One camera's calibration as EurocInput reads it from the settings file: K, R row-major 3x3, P the left 3x3 of the
+ * file's 3x4 projection, D = k1, k2, p1, p2, k3, k4, k5, k6 (zeros where the model has fewer). The maps are plain
+ * IEEE binary64 arithmetic, every operation rounded on its own (no fused multiply-add), in exactly this association:
+ *   M[r][c] = (P[r][0]*R[0][c] + P[r][1]*R[1][c]) + P[r][2]*R[2][c];   a..i = M row-major
+ *   c00 = e*i - f*h;  c01 = f*g - d*i;  c02 = d*h - e*g;  det = (a*c00 + b*c01) + c*c02;  t = 1.0/det
+ *   ir = { c00*t, (c*h-b*i)*t, (b*f-c*e)*t,  c01*t, (a*i-c*g)*t, (c*d-a*f)*t,  c02*t, (b*g-a*h)*t, (a*e-b*d)*t }
+ *   pixel (column j, row i):  X = j*ir[0] + (i*ir[1] + ir[2]);  Y = j*ir[3] + (i*ir[4] + ir[5]);
+ *                             W = j*ir[6] + (i*ir[7] + ir[8]);  iw = 1.0/W;  x = X*iw;  y = Y*iw
+ *   x2 = x*x;  y2 = y*y;  r2 = x2 + y2;  _2xy = (2*x)*y
+ *   kr = (1 + ((k3*r2 + k2)*r2 + k1)*r2) / (1 + ((k6*r2 + k5)*r2 + k4)*r2)
+ *   xd = (x*kr + p1*_2xy) + p2*(r2 + 2*x2);   yd = (y*kr + p1*(r2 + 2*y2)) + p2*_2xy
+ *   map_x = (float)(K[0]*xd + K[2]);  map_y = (float)(K[4]*yd + K[5])        (round to nearest even)
+ * Values that are not finite propagate as IEEE says (W = 0 on a horizon line); the remap treats them as outside.
+ * (OpenCV's scalar loop accumulates X += ir[0] along a row, its AVX2 path does not: this direct form is the
+ * library's statement; on the EuRoC calibrations at 752 x 480 all three give the same float bits.) */
+typedef struct svo_camera_calibration {   /* 280 bytes: K at 0, D at 72, R at 136, P at 208 */
+    double K[9], D[8], R[9], P[9];
+} svo_camera_calibration;
+/* ir of the statement above; host only (works without a GPU). The one place that validates a calibration, used by
+ * every entry that takes one: SVO_ERR_INVALID (ir untouched) when an input is not finite or det is 0 or not finite. */
+int svo_rectify_inverse(const svo_camera_calibration *cal, double ir[9]);
+/* the maps of n cameras (cal: host array) in ONE launch: map_x[c] / map_y[c] (host arrays of device pointers) receive
+ * width x height floats each, dense rows; any width, height >= 1. A calibration svo_rectify_inverse rejects, a NULL
+ * plane, n < 0, or 2^23 or more (64 x 64 tile, camera) pairs: SVO_ERR_INVALID, nothing launched. */
+int svo_build_rectify_maps(svo_handle *h, int n, const svo_camera_calibration *cal, int width, int height,
+                           float *const *map_x, float *const *map_y);
+
 /* I   the per-pixel step of the reference's ImageInput classes before StereoSlam::new_image: cvtColor(BGR2GRAY)
  *     and the halves of a side-by-side frame (src/app/video_input.cpp:29-36), extractChannel of a 3-channel
  *     frame (src/app/econ_input.cpp:102-103). The arithmetic:
@@ -335,6 +363,19 @@ int svo_ctx_get_slot_rig(svo_ctx *ctx, int seq, int *rig, svo_camera_settings *c
 /* *n = rigs of the ctx, rig 0 included; *map_bytes = device bytes of the maps of the added rigs (also counted in
  * svo_memory.device_bytes). Either may be NULL. Waits. */
 int svo_ctx_get_rigs(svo_ctx *ctx, int *n, int64_t *map_bytes);
+/* EurocInput's whole rectification set-up (src/app/euroc_input.cpp:24-49) inside the ctx: rigs whose maps come from
+ * calibrations instead of float planes. rigs[i] carries the ten float settings as svo_ctx_add_rigs validates them;
+ * its four map pointers must be NULL. left[i] / right[i]: the cameras behind the library's left / right image
+ * (EurocInput: left <- RIGHT.*, right <- LEFT.*), validated by svo_rectify_inverse. One launch builds all 2n maps
+ * straight in the remap kernels' fixed-point form (svo_build_rectify_maps' float -> remap_prep's entries, fused): no
+ * float plane is allocated, uploaded or read, a rig costs its 2 x map bytes and nothing transient. The rigs are the
+ * rigs svo_ctx_add_rigs makes from svo_build_rectify_maps' planes, byte for byte. Waits for queued work; every rig
+ * is built before any is added: SVO_ERR_INVALID (map pointers set, a rejected calibration, n < 0, ...) adds nothing. */
+int svo_ctx_add_rigs_calibrated(svo_ctx *ctx, const svo_rig *rigs, const svo_camera_calibration *left,
+                                const svo_camera_calibration *right, int n, int *ids);
+/* the same for rig 0, with svo_ctx_set_rectification's rules: both NULL turns rectification off; one NULL or a
+ * rejected calibration: SVO_ERR_INVALID, the old maps stay. */
+int svo_ctx_set_calibration(svo_ctx *ctx, const svo_camera_calibration *left, const svo_camera_calibration *right);
 /* The input format of the frames given to svo_new_image(s) / svo_submit_images from the next frame on, for every
  * active slot (a slot's first frame and keyframes included); may be switched between frames. Waits for queued
  * frames. Default SVO_INPUT_GRAY_PAIR: with it no launch, copy or allocation is added. The formats with ONE buffer

@@ -32,6 +32,7 @@
 
 #include <algorithm>
 #include <climits>
+#include <cmath>
 
 namespace svo {
 
@@ -351,6 +352,152 @@ __global__ __launch_bounds__(REMAP_THREADS) void remap_linear_multi_kernel(Remap
 __global__ __launch_bounds__(REMAP_THREADS) void remap_linear_single_kernel(RemapMultiLaunch a) {
     __shared__ uint32_t s_src[REMAP_LDS_BYTES / 4];
     remap_multi<false>(a, s_src);
+}
+
+// ---- maps from calibrations: cv::initUndistortRectifyMap (src/app/euroc_input.cpp:48-49), the f64 statement of
+// include/svo_hip.h. One workgroup per (output tile, camera), a lane's 16 pixels as in remap_prep_kernel, a row of 4
+// at a time (the scheduling barrier keeps the f64 temporaries of the rows apart). The camera's block is uniform per
+// workgroup and only read: it comes through the constant address space (scalar loads into SGPRs). -ffp-contract=off
+// keeps every product and sum rounded on its own, and f64 division is correctly rounded: the floats are the
+// statement's, bit for bit.
+//  * FUSED = false (svo_build_rectify_maps): the two floats are stored, a row of 4 as one 16-byte store where the
+//    row pitch and the plane's address allow;
+//  * FUSED = true (svo_ctx_add_rigs_calibrated, svo_ctx_set_calibration): the float goes straight through what
+//    remap_prep_kernel does with it: fix5, the packed entries, the tile's source box. No float plane exists.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define SVO_KP(T) __attribute__((address_space(4))) T*
+#else
+#define SVO_KP(T) T*
+#endif
+
+template <bool FUSED>
+__global__ __launch_bounds__(REMAP_THREADS) void rig_maps_kernel(const RigCam* __restrict__ cams, RemapMap m,
+                                                                 size_t frac_offset, size_t box_offset) {
+    __shared__ int s_box[4];
+    const int tiles = m.tiles_x * m.tiles_y;
+    const int cam = blockIdx.x / tiles, t = blockIdx.x - cam * tiles;
+    const int tx = t % m.tiles_x, ty = t / m.tiles_x;
+    const int lane = threadIdx.x;
+    const int c4 = (lane & 15) * 4, r0 = lane >> 4;
+    const RigCam c = ((SVO_KP(const RigCam))cams)[cam];
+    if (FUSED) {
+        if (lane == 0) { s_box[0] = INT_MAX; s_box[1] = INT_MIN; s_box[2] = INT_MAX; s_box[3] = INT_MIN; }
+        __syncthreads();
+    }
+    int bx0 = INT_MAX, bx1 = INT_MIN, by0 = INT_MAX, by1 = INT_MIN;
+    SVO_GP(float) gx = G(c.map_x);
+    SVO_GP(float) gy = G(c.map_y);
+    SVO_GP(uint4) oxy = (SVO_GP(uint4))G(reinterpret_cast<uint32_t*>(c.fixed) + (size_t)t * REMAP_ENTRIES);
+    SVO_GP(uint2) ofr = (SVO_GP(uint2))G(reinterpret_cast<uint16_t*>(c.fixed + frac_offset) + (size_t)t * REMAP_ENTRIES);
+    const bool vec = (m.w & 3) == 0 && ((reinterpret_cast<uintptr_t>(c.map_x) | reinterpret_cast<uintptr_t>(c.map_y)) & 15) == 0;
+    const int x0 = tx * REMAP_TILE + c4;
+    for (int k = 0; k < 4; k++) {
+        const int r = r0 + 16 * k, y = ty * REMAP_TILE + r;
+        const double i = (double)y;
+        const double rowX = i * c.ir[1] + c.ir[2], rowY = i * c.ir[4] + c.ir[5], rowW = i * c.ir[7] + c.ir[8];
+        float mx[4], my[4];
+        for (int j = 0; j < 4; j++) {
+            const double col = (double)(x0 + j);
+            const double X = col * c.ir[0] + rowX, Y = col * c.ir[3] + rowY, W = col * c.ir[6] + rowW;
+            const double iw = 1.0 / W;
+            const double x = X * iw, yy = Y * iw;
+            const double x2 = x * x, y2 = yy * yy, r2 = x2 + y2, _2xy = (2 * x) * yy;
+            const double kr = (1 + ((c.k3 * r2 + c.k2) * r2 + c.k1) * r2) / (1 + ((c.k6 * r2 + c.k5) * r2 + c.k4) * r2);
+            const double xd = (x * kr + c.p1 * _2xy) + c.p2 * (r2 + 2 * x2);
+            const double yd = (yy * kr + c.p1 * (r2 + 2 * y2)) + c.p2 * _2xy;
+            mx[j] = (float)(c.fx * xd + c.u0);
+            my[j] = (float)(c.fy * yd + c.v0);
+        }
+        if (!FUSED) {
+            if (y < m.h && x0 < m.w) {
+                const size_t o = (size_t)y * m.w + x0;
+                if (vec && x0 + 3 < m.w) {
+                    *(SVO_GP(float4))(gx + o) = make_float4(mx[0], mx[1], mx[2], mx[3]);
+                    *(SVO_GP(float4))(gy + o) = make_float4(my[0], my[1], my[2], my[3]);
+                } else {
+                    for (int j = 0; j < 4; j++)
+                        if (x0 + j < m.w) { gx[o + j] = mx[j]; gy[o + j] = my[j]; }
+                }
+            }
+        } else {
+            // (remap_prep_kernel's entry of the float it would have read)
+            uint32_t e[4], f[4];
+            for (int j = 0; j < 4; j++) {
+                int sx = -2, sy = -2, fr = 0;
+                if (x0 + j < m.w && y < m.h) {
+                    bool okx, oky;
+                    const int X = fix5(mx[j], okx);
+                    const int Y = fix5(my[j], oky);
+                    if (okx && oky) {
+                        sx = min(max(X >> 5, -2), REMAP_MAX_SRC);
+                        sy = min(max(Y >> 5, -2), REMAP_MAX_SRC);
+                        fr = (X & 31) | (Y & 31) << 5;
+                    }
+                }
+                if (sx >= -1 && sx < REMAP_MAX_SRC && sy >= -1 && sy < REMAP_MAX_SRC) {
+                    bx0 = min(bx0, max(sx, 0)); bx1 = max(bx1, sx + 1);
+                    by0 = min(by0, max(sy, 0)); by1 = max(by1, sy + 1);
+                }
+                e[j] = ((uint32_t)sx & 0xffffu) | (uint32_t)sy << 16;
+                f[j] = (uint32_t)fr;
+            }
+            oxy[r * 16 + (lane & 15)] = make_uint4(e[0], e[1], e[2], e[3]);
+            ofr[r * 16 + (lane & 15)] = make_uint2(f[0] | f[1] << 16, f[2] | f[3] << 16);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    if (FUSED) {
+        if (bx0 != INT_MAX) {
+            atomicMin(&s_box[0], bx0); atomicMax(&s_box[1], bx1);
+            atomicMin(&s_box[2], by0); atomicMax(&s_box[3], by1);
+        }
+        __syncthreads();
+        if (lane == 0) {
+            int4* ob = reinterpret_cast<int4*>(c.fixed + box_offset) + t;
+            *G(ob) = s_box[0] == INT_MAX ? make_int4(0, -1, 0, -1) : make_int4(s_box[0], s_box[1], s_box[2], s_box[3]);
+        }
+    }
+}
+
+bool rectify_inverse(const svo_camera_calibration& cal, double ir[9]) {
+    const double* all[4] = {cal.K, cal.D, cal.R, cal.P};
+    const int len[4] = {9, 8, 9, 9};
+    for (int q = 0; q < 4; q++)
+        for (int k = 0; k < len[q]; k++)
+            if (!std::isfinite(all[q][k])) return false;
+    const double *P = cal.P, *R = cal.R;
+    double M[9];
+    for (int r = 0; r < 3; r++)
+        for (int cc = 0; cc < 3; cc++) M[3 * r + cc] = (P[3 * r] * R[cc] + P[3 * r + 1] * R[3 + cc]) + P[3 * r + 2] * R[6 + cc];
+    const double a = M[0], b = M[1], c = M[2], d = M[3], e = M[4], f = M[5], g = M[6], h = M[7], i = M[8];
+    const double c00 = e * i - f * h, c01 = f * g - d * i, c02 = d * h - e * g;
+    const double det = (a * c00 + b * c01) + c * c02;
+    if (det == 0 || !std::isfinite(det)) return false;
+    const double t = 1.0 / det;
+    const double out[9] = {c00 * t, (c * h - b * i) * t, (b * f - c * e) * t,
+                           c01 * t, (a * i - c * g) * t, (c * d - a * f) * t,
+                           c02 * t, (b * g - a * h) * t, (a * e - b * d) * t};
+    std::copy(out, out + 9, ir);
+    return true;
+}
+
+bool rig_camera(const svo_camera_calibration& cal, RigCam& out) {
+    if (!rectify_inverse(cal, out.ir)) return false;
+    out.fx = cal.K[0]; out.fy = cal.K[4]; out.u0 = cal.K[2]; out.v0 = cal.K[5];
+    out.k1 = cal.D[0]; out.k2 = cal.D[1]; out.p1 = cal.D[2]; out.p2 = cal.D[3];
+    out.k3 = cal.D[4]; out.k4 = cal.D[5]; out.k5 = cal.D[6]; out.k6 = cal.D[7];
+    out.map_x = out.map_y = nullptr;
+    out.fixed = nullptr;
+    return true;
+}
+
+void launch_rig_maps(const RigCam* d_cams, int n, int w, int h, bool fused, hipStream_t stream) {
+    if (n <= 0) return;
+    const RemapMap m = remap_map_view(nullptr, w, h);            // (a view on a null base: the offsets in a map's storage)
+    const size_t frac_offset = reinterpret_cast<uintptr_t>(m.frac), box_offset = reinterpret_cast<uintptr_t>(m.box);
+    const dim3 grid((unsigned)(m.tiles_x * m.tiles_y) * (unsigned)n);
+    if (fused) hipLaunchKernelGGL(rig_maps_kernel<true>, grid, dim3(REMAP_THREADS), 0, stream, d_cams, m, frac_offset, box_offset);
+    else hipLaunchKernelGGL(rig_maps_kernel<false>, grid, dim3(REMAP_THREADS), 0, stream, d_cams, m, frac_offset, box_offset);
 }
 
 void launch_remap_prep(const float* map_x, const float* map_y, const RemapMap& m, hipStream_t stream) {

@@ -32,6 +32,8 @@ struct svo_handle {
     int exact_pinv = 1;             // reference-order Gauss-Newton by default
     DevPtr<uint8_t> remap_ws;       // svo_remap_linear: the map in the kernel's form + the image table
     size_t remap_ws_bytes = 0;
+    DevPtr<RigCam> rigcam_ws;       // svo_build_rectify_maps: the camera table
+    size_t rigcam_ws_count = 0;
     DevPtr<IngestImg> ingest_ws;    // svo_convert_frames: the image table
     size_t ingest_ws_count = 0;
     DevPtr<ExportTile> export_ws;   // svo_pack_keypoints: the tile table
@@ -223,6 +225,43 @@ extern "C" int svo_remap_linear(svo_handle* h, int n, const svo_image* src, svo_
     a.img = d_img;
     a.n = n;
     launch_remap(a, 1, h->stream);
+    HIP_TRY(hipGetLastError());
+    return SVO_OK;
+}
+
+extern "C" int svo_rectify_inverse(const svo_camera_calibration* cal, double ir[9]) {
+    if (!cal || !ir) return svo_set_error(SVO_ERR_INVALID, "svo_rectify_inverse: bad arguments");
+    if (!rectify_inverse(*cal, ir))
+        return svo_set_error(SVO_ERR_INVALID, "svo_rectify_inverse: a value is not finite, or P R has no inverse");
+    return SVO_OK;
+}
+
+extern "C" int svo_build_rectify_maps(svo_handle* h, int n, const svo_camera_calibration* cal, int width, int height,
+                                      float* const* map_x, float* const* map_y) {
+    CHECK_H(h);
+    if (n < 0 || width < 1 || height < 1 || (n > 0 && (!cal || !map_x || !map_y)))
+        return svo_set_error(SVO_ERR_INVALID, "svo_build_rectify_maps: bad arguments");
+    const long long tiles = (long long)((width + REMAP_TILE - 1) / REMAP_TILE) * ((height + REMAP_TILE - 1) / REMAP_TILE);
+    if (tiles * n >= RIG_MAX_WORKGROUPS)
+        return svo_set_error(SVO_ERR_INVALID, "svo_build_rectify_maps: %d cameras of %d x %d are too many for one call", n, width, height);
+    std::vector<RigCam> cams((size_t)n);
+    for (int i = 0; i < n; i++) {
+        if (!map_x[i] || !map_y[i]) return svo_set_error(SVO_ERR_INVALID, "svo_build_rectify_maps: camera %d: a plane is NULL", i);
+        if (!rig_camera(cal[i], cams[i]))
+            return svo_set_error(SVO_ERR_INVALID, "svo_build_rectify_maps: camera %d: a value is not finite, or P R has no inverse", i);
+        cams[i].map_x = map_x[i];
+        cams[i].map_y = map_y[i];
+    }
+    if (n == 0) return SVO_OK;
+    if ((size_t)n > h->rigcam_ws_count) {
+        HIP_TRY(hipStreamSynchronize(h->stream));     // (an earlier call may still read the table)
+        h->rigcam_ws.reset();
+        h->rigcam_ws_count = 0;
+        HIP_TRY(dev_malloc(h->rigcam_ws, sizeof(RigCam) * (size_t)n));
+        h->rigcam_ws_count = (size_t)n;
+    }
+    HIP_TRY(hipMemcpyAsync(h->rigcam_ws.get(), cams.data(), sizeof(RigCam) * (size_t)n, hipMemcpyHostToDevice, h->stream));
+    launch_rig_maps(h->rigcam_ws.get(), n, width, height, false, h->stream);
     HIP_TRY(hipGetLastError());
     return SVO_OK;
 }

@@ -9,6 +9,7 @@
 #include <mutex>
 #include <vector>
 
+#include "../../include/svo_hip.h"
 #include "svo_device.hpp"
 
 namespace svo {
@@ -103,6 +104,26 @@ int remap_chunks(const int* map_of_image, int n, std::vector<int>& order, std::v
 // n_chunks <= 65535 chunks of maps of w x h; single_images: every chunk is one image (the kernel form without an
 // image loop); n_sides as launch_remap
 void launch_remap_multi(RemapMultiLaunch a, int w, int h, int n_chunks, bool single_images, int n_sides, hipStream_t stream);
+
+// Maps from calibrations: cv::initUndistortRectifyMap (src/app/euroc_input.cpp:48-49) in the f64 statement of
+// include/svo_hip.h. One camera of a launch: what the kernel reads (uniform per workgroup, only read) and where
+// its output goes: two dense float planes (stage form), or the storage of a map in the kernels' form (fused form).
+struct RigCam {
+    double ir[9];                 // inverse of P R
+    double fx, fy, u0, v0;        // of K
+    double k1, k2, p1, p2, k3, k4, k5, k6;
+    float* map_x;                 // stage form
+    float* map_y;
+    uint8_t* fixed;               // fused form: the `base` of remap_map_view
+};
+// ir of the statement (host); false: an input is not finite, or det is 0 or not finite (ir untouched)
+bool rectify_inverse(const svo_camera_calibration& cal, double ir[9]);
+// the kernel's block of a validated calibration (outputs null); false as rectify_inverse
+bool rig_camera(const svo_camera_calibration& cal, RigCam& out);
+// n cameras (device table) of w x h in one launch: one workgroup per (64 x 64 tile, camera); tiles * n < RIG_MAX_WORKGROUPS.
+// fused = false: the float planes; true: fix5, the packed entries and the tile boxes remap_prep_kernel writes from them
+constexpr long long RIG_MAX_WORKGROUPS = 1ll << 23;   // (2^31 lanes in a launch)
+void launch_rig_maps(const RigCam* d_cams, int n, int w, int h, bool fused, hipStream_t stream);
 
 // ------------------------------------------------------------ input formats (ingest.hip)
 // The per-pixel step of the reference's ImageInput classes: gray from colour (cvtColor's 15-bit fixed point),

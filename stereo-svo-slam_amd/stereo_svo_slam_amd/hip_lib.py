@@ -46,6 +46,7 @@ SYMBOLS = (
     "svo_remap_linear_multi", "svo_ctx_add_rigs", "svo_ctx_remove_rigs", "svo_ctx_assign_rigs", "svo_ctx_get_slot_rig",
     "svo_ctx_get_rigs",
     "svo_klt_track_batch", "svo_klt_cache_layout",
+    "svo_rectify_inverse", "svo_build_rectify_maps", "svo_ctx_add_rigs_calibrated", "svo_ctx_set_calibration",
 )
 
 # svo_ctx_set_input_format / svo_convert_frames: how the buffers of a sequence become its two gray images
@@ -97,6 +98,33 @@ class Rig(C.Structure):
 
 
 assert C.sizeof(Rig) == 80
+
+
+class CameraCalibration(C.Structure):
+    """svo_camera_calibration (include/svo_hip.h): K, D, R, P of one camera as EurocInput reads them
+    (src/app/euroc_input.cpp:24-49); D = k1, k2, p1, p2, k3, k4, k5, k6."""
+    _fields_ = [("K", C.c_double * 9), ("D", C.c_double * 8), ("R", C.c_double * 9), ("P", C.c_double * 9)]
+
+    @classmethod
+    def from_mats(cls, K, D, R, P):
+        """K 3x3; D of 4, 5 or 8 coefficients (the rest 0; more raises); R 3x3 or None (identity); P 3x3, or the
+        3x4 of a settings file (its left 3x3 is used)"""
+        K, P = np.asarray(K, np.float64), np.asarray(P, np.float64)
+        D = np.asarray(D, np.float64).ravel()
+        R = np.eye(3) if R is None else np.asarray(R, np.float64)
+        if K.shape != (3, 3) or R.shape != (3, 3) or P.shape not in ((3, 3), (3, 4)):
+            raise ValueError(f"K, R are 3x3 and P is 3x3 or 3x4, not {K.shape}, {R.shape}, {P.shape}")
+        if D.size not in (4, 5, 8):
+            raise ValueError(f"D has 4, 5 or 8 coefficients, not {D.size}")
+        cal = cls()
+        cal.K[:] = K.ravel().tolist()
+        cal.D[:] = D.tolist() + [0.0] * (8 - D.size)
+        cal.R[:] = R.ravel().tolist()
+        cal.P[:] = P[:, :3].ravel().tolist()
+        return cal
+
+
+assert C.sizeof(CameraCalibration) == 280
 
 
 class Image(C.Structure):
@@ -427,6 +455,14 @@ def klt_cache_layout(win):
     return rec.value, off.value, hb.value, lv.value
 
 
+def rectify_inverse(cal):
+    """svo_rectify_inverse (host only): ir[9] of the calibration, the inverse of P R in the arithmetic of the maps;
+    SvoError for a calibration the library rejects."""
+    ir = (C.c_double * 9)()
+    _check(lib().svo_rectify_inverse(C.byref(cal), ir))
+    return np.array(ir, np.float64)
+
+
 def export_capacity(cam, width, height):
     """svo_export_capacity (host only): the records one slot of an export can take at most."""
     out = C.c_int(0)
@@ -563,6 +599,24 @@ class Handle:
         idx = (C.c_int * max(len(srcs), 1))(*[int(i) for i in map_of_image])
         _check(lib().svo_remap_linear_multi(self._h, len(srcs), _imgs(srcs), _imgs(outs), n_maps, px, py, idx))
         return outs
+
+    # -- M ----------------------------------------------------------------
+    def build_rectify_maps(self, cals, width, height, out=None):
+        """svo_build_rectify_maps: cv::initUndistortRectifyMap (src/app/euroc_input.cpp:48-49) of every
+        CameraCalibration in `cals` in one launch: a list of (map_x, map_y) float32 [height, width] device tensors
+        (out: such a list to write into)."""
+        n = len(cals)
+        if out is None:
+            out = [tuple(torch.empty((height, width), dtype=torch.float32, device=self.device) for _ in range(2))
+                   for _ in range(n)]
+        for mx, my in out:
+            for m in (mx, my):
+                assert m.dtype == torch.float32 and tuple(m.shape) == (height, width) and m.is_cuda and m.is_contiguous()
+        arr = (CameraCalibration * max(n, 1))(*cals)
+        px = (C.c_void_p * max(n, 1))(*[m[0].data_ptr() for m in out])
+        py = (C.c_void_p * max(n, 1))(*[m[1].data_ptr() for m in out])
+        _check(lib().svo_build_rectify_maps(self._h, n, arr, int(width), int(height), px, py))
+        return out
 
     # -- I ----------------------------------------------------------------
     def convert_frames(self, fmt, src_a, src_b, width=None, lefts=None, rights=None):

@@ -8,6 +8,7 @@ Host bookkeeping only; every frame goes through StereoSlam.new_image (libsvo_hip
     python -m stereo_svo_slam_amd.replay --synthetic euroc --frames 100 -t traj.csv
     python -m stereo_svo_slam_amd.replay --settings EuRoC.yaml --euroc /data/MH_02_easy/mav0/ -t traj.csv
     python -m stereo_svo_slam_amd.replay --settings EuRoC.yaml --euroc /data/MH_02_easy/mav0/ --gpu-rectify
+    python -m stereo_svo_slam_amd.replay --settings EuRoC.yaml --euroc /data/MH_02_easy/mav0/ --gpu-maps
     python -m stereo_svo_slam_amd.replay --settings Blender.yaml --sbs 'frames/%06d.png' -t traj.csv
     python -m stereo_svo_slam_amd.replay --settings Blender.yaml --sbs 'frames/%06d.png' --gpu-ingest
     python -m stereo_svo_slam_amd.replay --settings Econ.yaml --interleaved 'frames/%06d.png' --gpu-ingest
@@ -156,9 +157,10 @@ class EurocInput:
     time stamps [ns] and file names; the library's `right` image is cam0 rectified with the LEFT.*
     calibration of the settings file, `left` is cam1 rectified with RIGHT.* (:69-70, :100-101); time
     stamps are seconds since the first frame as float (:104-110). raw=True: read() hands out the
-    unrectified frames, for the tracker to rectify on the GPU with gpu_maps()."""
+    unrectified frames, for the tracker to rectify on the GPU with gpu_maps() or gpu_calibration().
+    host_maps=False: the float maps are not computed here (gpu_calibration() needs none)."""
 
-    def __init__(self, image_path, settings, raw=False):
+    def __init__(self, image_path, settings, raw=False, host_maps=True):
         self.raw = raw
         self.right_images, self.left_images, self.timestamps = [], [], []
         t0 = None
@@ -176,7 +178,8 @@ class EurocInput:
         self.maps_l = self.maps_r = None
         mats = {k: read_matrix(settings, k) for k in ("LEFT.K", "LEFT.D", "LEFT.R", "LEFT.P",
                                                      "RIGHT.K", "RIGHT.D", "RIGHT.R", "RIGHT.P")}
-        if all(v is not None for v in mats.values()):
+        self.mats = mats if all(v is not None for v in mats.values()) else None
+        if self.mats is not None and host_maps:
             size_l = (int(read_scalar(settings, "LEFT.width")), int(read_scalar(settings, "LEFT.height")))
             size_r = (int(read_scalar(settings, "RIGHT.width")), int(read_scalar(settings, "RIGHT.height")))
             self.maps_l = undistort_rectify_map(mats["LEFT.K"], mats["LEFT.D"], mats["LEFT.R"], mats["LEFT.P"], size_l)
@@ -199,6 +202,15 @@ class EurocInput:
         if self.maps_l is None:
             raise ValueError("the settings file has no LEFT.* / RIGHT.* rectification matrices")
         return self.maps_r, self.maps_l
+
+    def gpu_calibration(self):
+        """(left, right) CameraCalibrations in the library's naming for StereoSlam.set_calibration, as gpu_maps():
+        left from RIGHT.*, right from LEFT.*. The library builds the maps of gpu_maps() from them on the GPU."""
+        if self.mats is None:
+            raise ValueError("the settings file has no LEFT.* / RIGHT.* rectification matrices")
+        from .hip_lib import CameraCalibration
+        left, right = (CameraCalibration.from_mats(*(self.mats[f"{side}.{k}"] for k in "KDRP")) for side in ("RIGHT", "LEFT"))
+        return left, right
 
 
 class SideBySideInput:
@@ -348,9 +360,10 @@ class Replay:
     """process_image loop: only the time inside new_image is accumulated (slam_app.cpp:186-190)."""
 
     def __init__(self, settings, device=0, time_trace=False, fast=False, rectify_maps=None, input_format=None,
-                 gpu_imu=False, dump_views=None, dump_scene=None):
+                 gpu_imu=False, dump_views=None, dump_scene=None, calibration=None):
         """fast=False keeps the library default: the reference-order Gauss-Newton (bit-exact traces).
         rectify_maps = (left maps, right maps): the frames fed are raw and are rectified on the GPU.
+        calibration = (left, right) CameraCalibrations: the same, with the maps built on the GPU as well.
         input_format: the frames fed are raw buffers of that format (StereoSlam.set_input_format).
         gpu_imu: update_pose_from_imu is one svo_update_poses (the filter kernel) instead of a loop of
         svo_update_pose calls: the same bits.
@@ -368,6 +381,8 @@ class Replay:
             self.slam.set_fast_solver(True)
         if rectify_maps is not None:
             self.slam.set_rectification(*rectify_maps)
+        if calibration is not None:
+            self.slam.set_calibration(*calibration)
         if input_format is not None:
             self.slam.set_input_format(input_format)
         self.cumulative = []
@@ -447,6 +462,9 @@ def main(argv=None):
     ap.add_argument("--exact", action="store_true", help="no-op (the reference-order mode is the default)")
     ap.add_argument("--gpu-rectify", action="store_true",
                     help="--euroc: hand the raw frames to the library and rectify them on the GPU (bit-exact cv::remap)")
+    ap.add_argument("--gpu-maps", action="store_true",
+                    help="--euroc: as --gpu-rectify, and the rectification maps are built on the GPU from the LEFT.* / RIGHT.* "
+                         "calibrations of the settings file (initUndistortRectifyMap; no float map on the host)")
     ap.add_argument("--interleaved", help="'frames/%%06d.png' 3-channel frames: EconInput conventions (right = channel 1, left = channel 2)")
     ap.add_argument("--gpu-ingest", action="store_true",
                     help="--sbs / --interleaved: hand the raw frames to the library, which converts and splits them on the GPU")
@@ -468,7 +486,7 @@ def main(argv=None):
     args = ap.parse_args(argv)
 
     gt = None
-    rect = None
+    rect = cal = None
     data = os.environ.get("SVO_DATA")
     fmt = None
     if data and not (args.synthetic or args.pairs or args.euroc or args.sbs or args.interleaved):
@@ -478,8 +496,10 @@ def main(argv=None):
             args.sbs = os.path.join(data, "%06d.png")
     if args.euroc and args.settings:
         settings = read_settings(args.settings)
-        src = EurocInput(args.euroc, args.settings, raw=args.gpu_rectify)
-        if args.gpu_rectify:
+        src = EurocInput(args.euroc, args.settings, raw=args.gpu_rectify or args.gpu_maps, host_maps=not args.gpu_maps)
+        if args.gpu_maps:
+            cal = src.gpu_calibration()
+        elif args.gpu_rectify:
             rect = src.gpu_maps()
         n = min(args.frames, len(src))
         frames = (src.read(k) for k in range(n))
@@ -502,15 +522,17 @@ def main(argv=None):
         frames = ((*_load_pair(args.pairs, k), k / args.rate) for k in range(args.frames))
     else:
         ap.error("give --synthetic, or --settings with --euroc / --sbs / --interleaved / --pairs (or $SVO_DATA)")
-    if args.gpu_rectify and rect is None:
+    if args.gpu_rectify and rect is None and cal is None:
         ap.error("--gpu-rectify needs --euroc with --settings")
+    if args.gpu_maps and cal is None:
+        ap.error("--gpu-maps needs --euroc with --settings")
     if args.gpu_ingest and fmt is None:
         ap.error("--gpu-ingest needs --sbs or --interleaved with --settings")
     if args.gpu_imu and not args.gyro:
         ap.error("--gpu-imu needs --gyro")
     gyro = np.loadtxt(args.gyro, ndmin=2) if args.gyro else None
     rp = Replay(settings, args.device, args.time_trace, args.fast, rectify_maps=rect, input_format=fmt, gpu_imu=args.gpu_imu,
-                dump_views=args.dump_views, dump_scene=args.dump_scene)
+                dump_views=args.dump_views, dump_scene=args.dump_scene, calibration=cal)
     for k, (left, right, t) in enumerate(frames):
         rp.feed(left, right, t, None if gyro is None else gyro[gyro[:, 0] == k, 1:4])
     rows = rp.rows()

@@ -479,6 +479,9 @@ class StereoSlamBatch:
         if rect is None:
             _check(lib().svo_ctx_set_rectification(self._ctx, None, None, None, None, 0))
             return
+        if isinstance(rect[0], hip_lib.CameraCalibration):
+            _check(lib().svo_ctx_set_calibration(self._ctx, C.byref(rect[0]), C.byref(rect[1])))
+            return
         maps, on_dev = rect
         for m in maps:
             assert tuple(m.shape) == (self.height, self.width), "a rectification map has the ctx size"
@@ -489,6 +492,28 @@ class StereoSlamBatch:
         else:
             ptrs = [m.ctypes.data_as(C.c_void_p) for m in maps]
         _check(lib().svo_ctx_set_rectification(self._ctx, *ptrs, 1 if on_dev else 0))
+
+    def set_calibration(self, left, right):
+        """svo_ctx_set_calibration: set_rectification with the maps of two CameraCalibrations (the cameras behind the
+        library's left / right image; EurocInput: left <- RIGHT.*, right <- LEFT.*), built on the GPU straight in the
+        remap's fixed-point form; None, None turns rectification off."""
+        if (left is None) != (right is None):
+            raise ValueError("give both calibrations or none")
+        self._rect = None if left is None else (left, right)
+        if self._ctx:                      # (StereoSlam creates its ctx with the first image)
+            self._apply_rectification()
+
+    @staticmethod
+    def build_rectify_maps(cals, width, height, device=0):
+        """svo_build_rectify_maps: [(map_x, map_y)] float32 [height, width] CUDA tensors, one pair per
+        CameraCalibration, all in one launch (the float maps set_rectification / add_rigs take)"""
+        h = hip_lib.Handle(device, 1)
+        try:
+            out = h.build_rectify_maps(cals, width, height)
+            h.synchronize()
+        finally:
+            h.close()
+        return out
 
     def set_input_format(self, fmt):
         """svo_ctx_set_input_format: from the next frame on the frames are buffers of input format `fmt`
@@ -744,16 +769,27 @@ class StereoSlamBatch:
 
     # -- camera rigs ---------------------------------------------------------------------------------------
     def add_rigs(self, rigs):
-        """svo_ctx_add_rigs: every rig is a dict (or CameraSettings) with the ten float settings baseline, fx, fy, cx,
-        cy, k1, k2, k3, p1, p2, and optionally (dict only) "left_maps" and "right_maps": (map_x, map_y) of the
-        library's left / right image as in set_rectification, float32 [H, W] numpy arrays or CUDA tensors (both or
-        neither). Waits for queued work. Returns the ids (>= 1; rig 0 is the ctx's own settings and
-        set_rectification's maps)."""
+        """svo_ctx_add_rigs / svo_ctx_add_rigs_calibrated: every rig is a dict (or CameraSettings) with the ten float
+        settings baseline, fx, fy, cx, cy, k1, k2, k3, p1, p2, and optionally (dict only) its rectification in one of
+        two forms: "left_maps" and "right_maps", (map_x, map_y) of the library's left / right image as in
+        set_rectification, float32 [H, W] numpy arrays or CUDA tensors (both or neither); or "left_calibration" and
+        "right_calibration", two CameraCalibrations as in set_calibration (both or neither; not with maps). A list
+        may mix the forms: each form goes to its entry in one call. Waits for queued work. Returns the ids in the
+        order of `rigs` (>= 1; rig 0 is the ctx's own settings and set_rectification's maps)."""
         arr = (hip_lib.Rig * max(len(rigs), 1))()
-        keep = []
+        keep, cals = [], {}
         for i, r in enumerate(rigs):
             arr[i] = hip_lib.Rig.from_dict(r)
-            maps = [*r["left_maps"], *r["right_maps"]] if isinstance(r, dict) and r.get("left_maps") is not None else None
+            is_dict = isinstance(r, dict)
+            cal = (r.get("left_calibration"), r.get("right_calibration")) if is_dict else (None, None)
+            maps = [*r["left_maps"], *r["right_maps"]] if is_dict and r.get("left_maps") is not None else None
+            if (cal[0] is None) != (cal[1] is None):
+                raise ValueError(f"rig {i}: give both calibrations or none")
+            if cal[0] is not None:
+                if maps is not None or r.get("right_maps") is not None:
+                    raise ValueError(f"rig {i}: calibrations or maps, not both")
+                cals[i] = cal
+                continue
             if maps is None:
                 continue
             on_dev = isinstance(maps[0], torch.Tensor)
@@ -766,14 +802,35 @@ class StereoSlamBatch:
             arr[i].mem = hip_lib.MEM_DEVICE if on_dev else hip_lib.MEM_HOST
         if any(isinstance(m[0], torch.Tensor) for m in keep):
             torch.cuda.current_stream(self.device).synchronize()
-        ids = (C.c_int * max(len(rigs), 1))()
-        _check(lib().svo_ctx_add_rigs(self._ctx, arr, len(rigs), ids))
+        plain = [i for i in range(len(rigs)) if i not in cals]
+        out = [None] * len(rigs)
+        added = []
+        try:
+            for idx, calibrated in ((plain, False), (sorted(cals), True)):
+                if not idx and (calibrated or cals):
+                    continue
+                n = len(idx)
+                sub = (hip_lib.Rig * max(n, 1))(*[arr[i] for i in idx])
+                ids = (C.c_int * max(n, 1))()
+                if calibrated:
+                    left = (hip_lib.CameraCalibration * n)(*[cals[i][0] for i in idx])
+                    right = (hip_lib.CameraCalibration * n)(*[cals[i][1] for i in idx])
+                    _check(lib().svo_ctx_add_rigs_calibrated(self._ctx, sub, left, right, n, ids))
+                else:
+                    _check(lib().svo_ctx_add_rigs(self._ctx, sub, n, ids))
+                for k, i in enumerate(idx):
+                    out[i] = ids[k]
+                added += list(ids[:n])
+        except SvoError:
+            if added:                             # (a mixed list is all or nothing, like each entry)
+                _check(lib().svo_ctx_remove_rigs(self._ctx, (C.c_int * len(added))(*added), len(added)))
+            raise
         for i in range(len(rigs)):                # (find_rig: the full settings of every rig added here)
             cam = CameraSettings.from_buffer_copy(self.cam)
             for name in hip_lib.RIG_FLOATS:
                 setattr(cam, name, getattr(arr[i], name))
-            self._rig_settings()[ids[i]] = bytes(cam)
-        return list(ids[:len(rigs)])
+            self._rig_settings()[out[i]] = bytes(cam)
+        return out
 
     def _rig_settings(self):
         if getattr(self, "_rig_cams", None) is None:
