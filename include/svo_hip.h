@@ -318,6 +318,40 @@ typedef struct svo_memory {
     int32_t keyframe_slabs, keyframe_slabs_free;  /* keypoint storage of one keyframe                */
 } svo_memory;
 int svo_ctx_get_memory(svo_ctx *ctx, svo_memory *out);
+/* ---- trimming: a sequence that runs without end -------------------------------------------------------------------
+ * A keyframe is RETIRED once no keypoint of the current frame originates from it (its image set goes back then). Its
+ * points are final from there on: neither the tracker nor the depth filter touches it again, the keypoints of every
+ * later frame have an origin id at or above the retired count, and write-back goes to origin keyframes only. A
+ * retired keyframe still holds its keypoint storage (15 dwords per keypoint of capacity) and a record of the slot's
+ * keyframe table, which has room for `table` RESIDENT keyframes (4096; the diagnostic SVO_KEYFRAME_TABLE, a power of
+ * two 4 .. 4096, makes it smaller; a bad value: the default). Trimming drops a prefix of the retired keyframes: their
+ * storage returns to the ctx (svo_memory.keyframe_slabs_free) and their table records become free for new keyframes.
+ * It cannot change any frame. Ids never move: keyframe ids, svo_get_keyframe_count, svo_run_info.keyframes and the
+ * keypoints' keyframe_id stay absolute and keep counting up; the resident keyframes of a slot are [first, count), with
+ * first <= retired <= count - 1, and a new keyframe fails with SVO_ERR_CAPACITY only when count - first == table.
+ * A restart, the end of a sequence and a load free the resident keyframes; first returns to 0 with the ids.
+ * Not trimmed: the host trajectory, 24 B per frame and slot (about 1.7 MB per hour and slot at 20 Hz).
+ *
+ * svo_submit_trim_keyframes: each named slot drops its keyframes with id < min(below[i], retired) as of when the job
+ * runs (below == NULL: everything retired; seqs == NULL names every slot in order, n is ignored). Queued exactly like
+ * a restart: behind every frame set, restart, load and export submitted before it and ahead of what follows; it does
+ * not wait, and only the groups that own a named slot get work. Nothing to drop, or an empty slot, is not an error.
+ * Host bookkeeping only: no launch, no copy. Rejected with SVO_ERR_INVALID and nothing queued: a slot out of range or
+ * named twice; a failed ctx, as in svo_submit_images. */
+int svo_submit_trim_keyframes(svo_ctx *ctx, const int *seqs, const int *below, int n);
+int svo_trim_keyframes(svo_ctx *ctx, const int *seqs, const int *below, int n);   /* submit + wait */
+/* keep = -1 (the default): a slot never trims on its own. keep >= 0: after each step a slot with retired - first >
+ * keep is trimmed to first = retired - keep. A setter: waits for the queues. With SVO_KEEP_KEYFRAME_IMAGES=1 nothing
+ * retires and so nothing is trimmed. keep < -1: SVO_ERR_INVALID. */
+int svo_ctx_set_keyframe_window(svo_ctx *ctx, int keep);
+typedef struct svo_keyframe_range {   /* 16 bytes */
+    int32_t first;                    /* the oldest resident keyframe (0 until the slot is trimmed)                   */
+    int32_t retired;                  /* keyframes below it are final and may be trimmed                              */
+    int32_t count;                    /* svo_get_keyframe_count: ids [first, count) are resident                      */
+    int32_t table;                    /* resident keyframes a slot can hold                                           */
+} svo_keyframe_range;
+/* a getter: waits for the queues. An empty slot: {0, 0, 0, table}. */
+int svo_get_keyframe_range(svo_ctx *ctx, int seq, svo_keyframe_range *out);
 /* EurocInput's rectification (maps :48-49, remap :69-70) inside the tracker: from the next frame on, the
  * images given to svo_new_image(s) / svo_submit_images are RAW images of the ctx size, remapped on the
  * device before the pyramids. left_* rectify the library's left image (the reference's M1r/M2r: cam1 with
@@ -396,7 +430,8 @@ int svo_get_pose(svo_ctx *ctx, int seq, float pose[6]);
 /* Frame::kps of the current frame; returns the count in *n (copies min(n, cap)) */
 int svo_get_frame_keypoints(svo_ctx *ctx, int seq, svo_kp2d *kps2d, svo_kp3d *kps3d,
                             svo_kp_info *info, int cap, int *n);
-/* get_keyframes / get_keyframe (src/lib/stereo_slam.cpp:273-289) */
+/* get_keyframes / get_keyframe (src/lib/stereo_slam.cpp:273-289). The count is the number of ids given out; an id
+ * below svo_keyframe_range.first: SVO_ERR_INVALID, "keyframe %d was trimmed" */
 int svo_get_keyframe_count(svo_ctx *ctx, int seq, int *count);
 int svo_get_keyframe(svo_ctx *ctx, int seq, int id, svo_kp2d *kps2d, svo_kp3d *kps3d,
                      svo_kp_info *info, float pose[6], int cap, int *n);
@@ -520,7 +555,10 @@ int svo_pack_keypoints(svo_handle *h, int n_sets, const svo_keypoints *sets, con
  *
  * Polling: keyframes below svo_map_segment.keyframes_retired are no longer tracked, no write-back reaches them and
  * their points are final. A poller can pass from_keyframe = keyframes_retired of its last poll and keep what it has
- * of the keyframes below. */
+ * of the keyframes below. Once that export is delivered it may trim them (svo_submit_trim_keyframes with below = the
+ * from_keyframe it passed): they were final when the previous export ran, so the copies it holds are. The keyframes
+ * in [from_keyframe, the newly reported keyframes_retired) become final in this export: it keeps those copies and
+ * passes the new count next time. A trimmed slot exports from max(from_keyframe, first_keyframe) on. */
 typedef struct svo_map_point {      /* 16 bytes */
     float   x, y, z;                /* kps3d, bits unchanged (world frame)                                  */
     uint8_t color[3];               /* r, g, b                                                              */
@@ -548,12 +586,16 @@ typedef struct svo_map_segment {    /* 64 bytes, host, one per named slot       
     int32_t frame_id;               /* of the slot's current frame; -1: empty slot (every count is 0)       */
     int32_t status;                 /* SVO_MAP_*                                                            */
     int32_t n_keyframes, keyframes_retired;   /* of the slot when the job ran                               */
-    int32_t from_keyframe, n_exported;        /* keyframes [from_keyframe, from_keyframe + n_exported): the region's
-                                                 from_keyframe; n_exported = max(0, n_keyframes - from_keyframe) */
+    int32_t from_keyframe, n_exported;        /* keyframes [from_keyframe, from_keyframe + n_exported): from_keyframe =
+                                                 max(the region's, first_keyframe); n_exported = max(0, n_keyframes -
+                                                 from_keyframe) */
     int64_t n_points;               /* points kept (TOO_SMALL: 0)                                           */
     int64_t points_bound;           /* keypoints of the exported keyframes: the sum of their n_total        */
     float   time_stamp;             /* of the slot's current frame                                          */
-    int32_t _pad[3];
+    union {
+        int32_t first_keyframe;     /* the slot's oldest resident keyframe (svo_keyframe_range.first; 0: untrimmed): */
+        int32_t _pad[3];            /* _pad[0] of earlier versions; _pad[1], _pad[2]: 0                             */
+    };
 } svo_map_segment;
 
 typedef struct svo_map_region {     /* where one named slot goes: the caller places every slot itself       */
@@ -561,7 +603,8 @@ typedef struct svo_map_region {     /* where one named slot goes: the caller pla
     int64_t point_capacity;         /* records it may take: >= points_bound, or the slot comes back TOO_SMALL */
     int64_t first_keyframe_entry;   /* its keyframes are entries [first_keyframe_entry, + n_exported) of dst->keyframes */
     int32_t keyframe_capacity;      /* entries it may take: >= n_exported, or TOO_SMALL                     */
-    int32_t from_keyframe;          /* >= 0; beyond the slot's count: nothing exported                      */
+    int32_t from_keyframe;          /* >= 0; beyond the slot's count: nothing exported; below its first resident
+                                       keyframe: from that one on                                            */
 } svo_map_region;
 
 typedef struct svo_map_dst {
@@ -570,7 +613,8 @@ typedef struct svo_map_dst {
     svo_map_point    *points;       /* host or device (mem), 16-byte aligned; NULL: every point_capacity is 0 */
 } svo_map_dst;
 
-/* what an export of the slot from keyframe from_keyframe on would need right now: *keyframes = n_exported,
+/* what an export of the slot from keyframe from_keyframe on (a trimmed slot: from its first resident keyframe, if that
+ * is later) would need right now: *keyframes = n_exported,
  * *points_bound = the sum of their keypoint counts (either may be NULL). A getter: waits for the queues. */
 int svo_map_size(svo_ctx *ctx, int seq, int from_keyframe, int *keyframes, int64_t *points_bound);
 /* Queued exactly as svo_submit_export is (seqs == NULL names every slot in order, n is ignored; segment i and
@@ -775,7 +819,7 @@ typedef struct svo_scene_style {      /* what one job draws; copied at submit   
     uint32_t background, trajectory_rgb, keyframe_rgb, pose_rgb;   /* r << 16 | g << 8 | b; the top byte 0   */
     float    frustum_w, frustum_h, frustum_d;   /* finite                                                   */
     uint32_t show;                    /* SVO_SCENE_* bits                                                    */
-    int32_t  from_keyframe;           /* >= 0: points and frusta of keyframes from this one on               */
+    int32_t  from_keyframe;           /* >= 0: points and frusta of the resident keyframes from this one on  */
     int32_t  trajectory_tail;         /* 0: the whole trajectory; k > 0: its newest k poses                  */
     svo_map_filter filter;            /* which keypoints are points                                          */
     int32_t  _reserved;               /* 0                                                                   */
@@ -791,7 +835,7 @@ typedef struct svo_scene_segment {    /* 64 bytes, host, one per named slot     
     int32_t  seq, run;                /* slot and ordinal of its run (svo_run_info.run)                      */
     int32_t  frame_id;                /* of the slot's current frame; -1: empty slot                         */
     uint16_t status;                  /* SVO_SCENE_*                                                         */
-    uint16_t n_keyframes;             /* of the slot when the job ran (a sequence has at most 4096)          */
+    uint16_t n_keyframes;             /* of the slot when the job ran, its low 16 bits (ids outlive a trimmed table)  */
     int32_t  from_keyframe;           /* the style's                                                         */
     int32_t  n_keypoints;             /* keypoints considered: those of keyframes from_keyframe .. (0 without POINTS) */
     int32_t  n_poses;                 /* trajectory poses drawn (0 without TRAJECTORY)                       */
@@ -871,13 +915,13 @@ int svo_render_scene(svo_handle *h, int n, const svo_scene_src *src, const svo_s
  *               gain, 144 floats each, row major (4128 bytes)
  *   frame       double time_stamp; float pose[6] (the filtered pose: svo_get_pose); svo_frame_stats: 616 bytes
  *   trajectory  n_trajectory x svo_pose
- *   keyframes   n_keyframes x svo_snapshot_keyframe
+ *   keyframes   (n_keyframes - first_keyframe) x svo_snapshot_keyframe: the resident keyframes, oldest first
  *   directory   n_planes x svo_snapshot_plane: where every plane lies in the data part, in this order:
  *                 the current keypoint set: kps2d, kps3d, flags, keyframe_id, keypoint_index, outlier_count,
  *                   inlier_count, kf_inv_depth, kf_variance, score, level_type, color (12 planes of one row,
  *                   n_keypoints entries each); the colour generator's word (4 bytes); the keypoint count as the
  *                   device holds it (4 bytes)
- *                 per keyframe, retired ones included: the same 12 planes with the keyframe's n entries
+ *                 per resident keyframe, retired ones included: the same 12 planes with the keyframe's n entries
  *                 per image set: left pyramid levels 0 .. pyramid_levels-1 (level l: (width >> l) x (height >> l)),
  *                   the right image, LK levels 1 .. lk_levels-1 (halved rounding up); rows = the image's,
  *                   row_bytes = its width
@@ -910,8 +954,10 @@ struct svo_snapshot_info {
     int32_t  n_trajectory;             /* frame_id + 1                                                      */
     int32_t  n_keyframes, keyframes_retired;   /* keyframes [0, retired) have given their images back        */
     int32_t  n_image_sets;
-    int32_t  n_planes;                 /* 14 + 12 n_keyframes + n_image_sets (pyramid_levels + lk_levels)   */
-    int32_t  _reserved;                /* 0                                                                 */
+    int32_t  n_planes;                 /* 14 + 12 (n_keyframes - first_keyframe) + n_image_sets (pyramid_levels + lk_levels) */
+    int32_t  first_keyframe;           /* keyframes below it were trimmed and are not in the snapshot: 0 <= first_keyframe
+                                          <= keyframes_retired, n_keyframes - first_keyframe <= 4096 (0: untrimmed, the
+                                          snapshot of earlier versions byte for byte)                        */
 };
 typedef struct svo_snapshot_keyframe {
     float   pose[6];
@@ -954,7 +1000,8 @@ int svo_save_sequences(svo_ctx *ctx, const int *seqs, int n, svo_snapshot *snaps
  * Compatibility: width, height and capacity must equal the ctx's, and the camera settings those of the target slot
  * (the header has the settings of the saved slot's rig; the target's: its rig as of this call, svo_ctx_assign_rigs
  * included) byte for byte; solver mode, input format, rectification maps, rig ids, memory mode, group count, slot
- * index, template-ring size and device are free.
+ * index, template-ring size and device are free; the resident keyframes (n_keyframes - first_keyframe) must fit the
+ * ctx's keyframe table (svo_keyframe_range.table), else SVO_ERR_INVALID here, nothing queued or changed.
  * The host part is parsed and checked completely here, on the host, before anything is queued or changed: magic,
  * version, byte order, status, compatibility, every count against the capacity, every directory entry against
  * the extent its plane must have and the data part's size, the sizes against what was passed. A bad snapshot, an

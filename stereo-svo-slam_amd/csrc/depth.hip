@@ -331,7 +331,7 @@ __global__ __launch_bounds__(64) void filter_update_kernel(const FilterArgs* __r
         SVO_GP(KfDev) kf = nullptr;
         int kidx = 0;
         if (a.kfs) {
-            kf = &G(a.kfs)[G(a.kf_id)[i]];
+            kf = &G(a.kfs)[G(a.kf_id)[i] & a.kf_mask];             // (the table is a ring over the ids)
             kidx = G(a.kp_index)[i];
             for (int q = 0; q < 6; q++) kfp[q] = kf->pose[q];
             r3 = G(kf->kps3d)[kidx];

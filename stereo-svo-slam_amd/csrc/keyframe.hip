@@ -460,8 +460,8 @@ __global__ __launch_bounds__(256) void kf_init_kernel(const KfInitArgs* __restri
     for (int i = 0; i < 6; i++) pose[i] = a.first_frame ? 0.f : G(a.frame_pose)[i];
     if (tid == 0) {
         pose_mats(pose, pm);
-        G(a.kfs)[a.new_kf_id] = a.record;                       // the keyframe table entry (pointers; n and pose below)
-        if (a.evict_id >= 0) G(a.kfs)[a.evict_id].tmpl = nullptr;   // its template cache block now belongs to the new keyframe
+        G(a.kfs)[a.new_kf_id & a.kf_mask] = a.record;                     // the keyframe table entry (pointers; n and pose below)
+        if (a.evict_id >= 0) G(a.kfs)[a.evict_id & a.kf_mask].tmpl = nullptr;   // its template cache block now belongs to the new keyframe
     }
     if (a.record.tmpl_valid)
         for (int i = tid; i < a.tmpl_valid_bytes / 4; i += 256) ((SVO_GP(uint32_t))a.record.tmpl_valid)[i] = 0u;
@@ -514,7 +514,7 @@ __global__ __launch_bounds__(256) void kf_init_kernel(const KfInitArgs* __restri
     __syncthreads();
     not_temp = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
     if (tid == 0) {
-        SVO_GP(KfDev) kfw = G(a.kfs) + a.new_kf_id;
+        SVO_GP(KfDev) kfw = G(a.kfs) + (a.new_kf_id & a.kf_mask);
         kfw->n = n;
         for (int i = 0; i < 6; i++) kfw->pose[i] = pose[i];
         uint32_t st = lcg0;

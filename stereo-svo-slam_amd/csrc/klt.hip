@@ -382,7 +382,7 @@ __device__ __forceinline__ void klt_track_body(const KltArgs* __restrict__ args)
     // the struct lands in scratch memory — 216 B per lane written and read back per keypoint, 0.7 GB
     // of HBM writes per 256-sequence launch — because lk[] is indexed with the run-time level.)
     const int kfid = __builtin_amdgcn_readfirstlane(a.kf_id ? G(a.kf_id)[kp] : 0);
-    SVO_GP(const KfDev) kfp = G(a.kfs) + kfid;
+    SVO_GP(const KfDev) kfp = G(a.kfs) + (kfid & a.kf_mask);     // (the table is a ring over the ids)
 
     svo_kp2d ref;
     float nx, ny;

@@ -722,7 +722,7 @@ extern "C" int svo_klt_track(svo_handle* h, const svo_image* prev_lk, const svo_
     if (rc) return rc;
     KltArgs ka;
     memset(&ka, 0, sizeof(ka));
-    ka.kfs = d_kf;
+    ka.kfs = d_kf; ka.kf_mask = -1;
     ka.n_cur = n_levels;
     for (int l = 0; l < n_levels; l++) ka.cur[l] = make_view(cur_lk[l]);
     int* d_n;
@@ -1304,7 +1304,7 @@ extern "C" int svo_klt_track_batch(svo_handle* h, int batch, const svo_klt_seque
         const svo_klt_sequence& s = seqs[b];
         KltArgs& ka = blocks[(size_t)b];
         memset(&ka, 0, sizeof(ka));
-        ka.kfs = d_table + first_kf[(size_t)b]; ka.kf_id = s.kf_id; ka.n_cur = s.n_cur;
+        ka.kfs = d_table + first_kf[(size_t)b]; ka.kf_mask = -1; ka.kf_id = s.kf_id; ka.n_cur = s.n_cur;
         for (int l = 0; l < s.n_cur; l++) ka.cur[l] = make_view(s.cur[l]);
         ka.n_ptr = s.n; ka.prev_pts = nullptr; ka.cur_pts = s.tracked; ka.status = s.status;
         ka.err = s.err; ka.win = win;

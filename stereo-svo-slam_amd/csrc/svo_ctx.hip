@@ -6,6 +6,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <climits>
 #include <cmath>
 #include <condition_variable>
 #include <cstdlib>
@@ -84,12 +85,13 @@ struct svo_ctx {
     // one entry of a group's queue: a frame set, or (restart non-empty) the end of some of its sequences, or
     // (exp.seqs non-empty) an export, or (snap.seqs / snap.loads non-empty) a save / a load, or (pose.seqs non-empty)
     // pose-filter updates, or (map.seqs non-empty) a map export, or (view.seqs non-empty) a view job, or (scene.seqs
-    // non-empty) a scene job, or (assign non-empty) a rig assignment
+    // non-empty) a scene job, or (assign non-empty) a rig assignment, or (trim non-empty) a trim of keyframes
     struct Job {
         std::vector<const uint8_t*> left, right;
         std::vector<float> ts;
         int stride = 0, mem = 0;
         std::vector<int> restart;        // indices in the group
+        std::vector<int> trim, trim_below;   // indices in the group, and the id each one's keyframes go below
         std::vector<int> assign;         // indices in the group, and what each is bound to
         std::vector<RigBinding> bindings;
         Export exp;
@@ -168,6 +170,8 @@ void worker_run_job(svo_ctx::Worker& w, const svo_ctx::Job& job) {
                        ? grp_export(w.g.get(), e.what, e.mem, e.seqs.data(), e.seg.data(), (int)e.seqs.size(), w.first, e.base, &e.dst)
                    : !job.assign.empty()
                        ? grp_assign_rigs(w.g.get(), job.assign.data(), job.bindings.data(), (int)job.assign.size())
+                   : !job.trim.empty()
+                       ? grp_trim_keyframes(w.g.get(), job.trim.data(), job.trim_below.data(), (int)job.trim.size())
                    : !job.restart.empty()
                        ? grp_restart_sequences(w.g.get(), job.restart.data(), (int)job.restart.size())
                        : grp_new_images(w.g.get(), job.left.data(), job.right.empty() ? nullptr : job.right.data(), job.stride,
@@ -351,6 +355,54 @@ extern "C" int svo_ctx_restart_sequences(svo_ctx* c, const int* seqs, int n) {
             if (seqs[i] >= w.first && seqs[i] < w.first + w.count) job.restart.push_back(seqs[i] - w.first);
         if (!job.restart.empty()) worker_submit(w, std::move(job));
     }
+    return SVO_OK;
+}
+
+extern "C" int svo_submit_trim_keyframes(svo_ctx* c, const int* seqs, const int* below, int n) {
+    if (!c || (seqs && n < 0)) return svo_set_error(SVO_ERR_INVALID, "svo_submit_trim_keyframes: bad arguments");
+    if (!seqs) n = c->B;
+    std::vector<char> named(c->B, 0);
+    for (int i = 0; i < n; i++) {
+        const int s = seqs ? seqs[i] : i;
+        if (s < 0 || s >= c->B || named[s])
+            return svo_set_error(SVO_ERR_INVALID, "svo_submit_trim_keyframes: sequence %d is out of range or named twice", s);
+        named[s] = 1;
+    }
+    if (c->failed.load()) {                      // (as svo_submit_images)
+        const int rc = ctx_drain(c);
+        return rc ? rc : svo_set_error(SVO_ERR_INVALID, "svo_submit_trim_keyframes: an earlier frame of this ctx failed; create a new ctx");
+    }
+    for (auto& wp : c->workers) {
+        svo_ctx::Worker& w = *wp;
+        svo_ctx::Job job;
+        for (int i = 0; i < n; i++) {
+            const int s = seqs ? seqs[i] : i;
+            if (s < w.first || s >= w.first + w.count) continue;
+            job.trim.push_back(s - w.first);
+            job.trim_below.push_back(below ? below[i] : INT_MAX);     // (NULL: everything retired)
+        }
+        if (!job.trim.empty()) worker_submit(w, std::move(job));
+    }
+    return SVO_OK;
+}
+
+extern "C" int svo_trim_keyframes(svo_ctx* c, const int* seqs, const int* below, int n) {
+    const int rc = svo_submit_trim_keyframes(c, seqs, below, n);
+    return rc ? rc : svo_wait(c);
+}
+
+extern "C" int svo_ctx_set_keyframe_window(svo_ctx* c, int keep) {
+    if (!c || keep < -1) return svo_set_error(SVO_ERR_INVALID, "svo_ctx_set_keyframe_window: bad ctx, or keep %d below -1", keep);
+    const int rc = ctx_drain(c);
+    if (!rc)
+        for (auto& w : c->workers) grp_set_keyframe_window(w->g.get(), keep);
+    return rc;
+}
+
+extern "C" int svo_get_keyframe_range(svo_ctx* ctx, int seq, svo_keyframe_range* out) {
+    svo_group* g; int s;
+    if (const int rc = ctx_seq(ctx, seq, &g, &s)) return rc;
+    if (out) *out = grp_keyframe_range(g, s);
     return SVO_OK;
 }
 
@@ -1124,6 +1176,7 @@ extern "C" int svo_get_keyframe(svo_ctx* ctx, int seq, int id, svo_kp2d* kps2d, 
     if (const int rc = ctx_seq(ctx, seq, &c, &s)) return rc;
     const svo::Seq& q = c->seqs[s];
     if (id < 0 || id >= (int)q.kfs.size()) return svo_set_error(SVO_ERR_INVALID, "keyframe %d does not exist", id);
+    if (id < q.kfs.first()) return svo_set_error(SVO_ERR_INVALID, "keyframe %d was trimmed", id);
     const svo::KfHost& k = q.kfs[id];
     if (n) *n = k.n;
     if (pose) std::memcpy(pose, k.pose, sizeof(float) * 6);

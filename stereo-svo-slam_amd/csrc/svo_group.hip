@@ -235,7 +235,13 @@ static void size_group(svo_group* c) {
     const int width = c->width, height = c->height;
     c->cap = keypoint_capacity(cam, width, height);
     c->rec_cap = (int)align_up((size_t)c->cap, 512);   // whole passes of the widest alignment workgroup
+    // the keyframe table of a sequence: a ring, so a power of two. SVO_KEYFRAME_TABLE (4 .. MAX_KEYFRAMES) is a
+    // diagnostic: tests reach the table's end in seconds with it. Anything else: the default.
     c->max_kf = MAX_KEYFRAMES;
+    if (const char* e = std::getenv("SVO_KEYFRAME_TABLE")) {
+        const int t = std::atoi(e);
+        if (t >= 4 && t <= MAX_KEYFRAMES && (t & (t - 1)) == 0) c->max_kf = t;
+    }
     if (const char* e = std::getenv("SVO_KEEP_KEYFRAME_IMAGES")) c->retire_kf_images = std::atoi(e) == 0;
     c->n_lk = usable_lk_levels(cam, width, height);
     c->det_levels = cam.max_pyramid_levels / 2;
@@ -450,6 +456,7 @@ void flush_pending(svo_group* c) {
 // kf_init_kernel: colour generator, table record and "stored" flags of keyframe 0). Records and template-cache
 // blocks of the old run's keyframes stay behind in the table, but a keypoint only refers to a keyframe id that
 // its own run has created, and creating it rewrites both.
+// (Trimmed keyframes gave their slabs back when they went: the resident ones are all that is left to free.)
 void end_sequence(svo_group* c, int s) {
     Seq& q = c->seqs[s];
     if (q.frame_id < 0) return;              // empty: nothing to end
@@ -476,7 +483,36 @@ void end_sequence(svo_group* c, int s) {
     clear(q.stats);
 }
 
+// The slot's keyframes below min(below, kfs_retired) go (between two steps of the group): host bookkeeping only. Such
+// a keyframe is retired, so no keypoint of the frame originates from it, neither the tracker nor the depth filter reads
+// or writes it again and its image set is back already; its keypoint slab returns to the free list, its host entry
+// goes, and its record stays behind in the table ring until a new keyframe takes the slot.
+void trim_keyframes(svo_group* c, Seq& q, int below) {
+    const int to = std::min(below, q.kfs_retired);
+    if (to <= q.kfs.first()) return;
+    for (int id = q.kfs.first(); id < to; id++) {
+        KfHost& k = q.kfs[(size_t)id];
+        release_set(q, k.set);               // (null already)
+        c->kf_slabs.push_back(reinterpret_cast<uint8_t*>(k.kps.kps3d));
+    }
+    q.kfs.drop_below(to);
+}
+
 }  // namespace svo
+
+int grp_trim_keyframes(svo_group* c, const int* seqs, const int* below, int n) {
+    if (c->failed)
+        return svo_set_error(SVO_ERR_INVALID, "svo_submit_trim_keyframes: an earlier frame of this ctx failed; create a new ctx");
+    for (int i = 0; i < n; i++) trim_keyframes(c, c->seqs[seqs[i]], below[i]);
+    return SVO_OK;
+}
+
+void grp_set_keyframe_window(svo_group* c, int keep) { c->kf_window = keep; }
+
+svo_keyframe_range grp_keyframe_range(const svo_group* c, int seq) {
+    const Seq& q = c->seqs[seq];
+    return svo_keyframe_range{q.kfs.first(), q.kfs_retired, (int)q.kfs.size(), c->max_kf};
+}
 
 int grp_restart_sequences(svo_group* c, const int* seqs, int n) {
     if (c->failed)

@@ -25,6 +25,11 @@ int grp_new_images(svo_group* g, const uint8_t* const* left, const uint8_t* cons
 // the named sequences (indices in the group) end; their slots are empty until their next frame. Runs between two
 // steps of the group, on the thread that drives it. A failed group rejects it.
 int grp_restart_sequences(svo_group* g, const int* seqs, int n);
+// One group's share of svo_submit_trim_keyframes, between two steps of the group, on the thread that drives it: slot
+// seqs[i] (index in the group) drops its keyframes below min(below[i], its retired count). A failed group rejects it.
+int grp_trim_keyframes(svo_group* g, const int* seqs, const int* below, int n);
+void grp_set_keyframe_window(svo_group* g, int keep);                 // svo_ctx_set_keyframe_window (the queues have drained)
+svo_keyframe_range grp_keyframe_range(const svo_group* g, int seq);   // (the queues have drained)
 // One group's share of svo_ctx_assign_rigs, between two steps of the group, on the thread that drives it: slot seqs[i]
 // (index in the group) ends its sequence like a restart and is bound to b[i]: the rig's id, the full settings of its
 // sequences from now on, and the storage of its left and right maps (owned by the ctx, valid while a slot is bound;
@@ -64,7 +69,7 @@ int grp_export_scenes(svo_group* g, int mem, const int* seqs, const int* seg, in
                       const svo_scene_camera* cameras, const svo_scene_dst* dst);
 int64_t grp_scene_bytes(const svo_scene_style* style);   // the image_bytes of a checked style
 // what svo_map_size reports of a slot (the queues have drained)
-void grp_map_size(const svo_group* g, int seq, int from_keyframe, int* keyframes, int64_t* points_bound);
+void grp_map_size(const svo_group* g, int seq, int from_keyframe, int* keyframes, int64_t* points_bound, int* from = nullptr);
 // Snapshots (svo_submit_save / svo_submit_load). grp_check_snapshot: everything svo_submit_load checks of one
 // snapshot, on the caller's thread (it reads only what never changes in a group; slot_cam: the settings of the
 // target slot's rig); *host_copy receives the checked host part. grp_save / grp_load: one group's share, between two steps of the group, on the thread that drives it;

@@ -39,12 +39,15 @@ int reserve_map_points(svo_group* c, size_t points) {
 
 }  // namespace
 
-void grp_map_size(const svo_group* c, int seq, int from_keyframe, int* keyframes, int64_t* points_bound) {
+// (a trimmed slot: from its first resident keyframe on, if that is later; *from receives the effective start)
+void grp_map_size(const svo_group* c, int seq, int from_keyframe, int* keyframes, int64_t* points_bound, int* from) {
     const Seq& q = c->seqs[seq];
+    from_keyframe = std::max(from_keyframe, q.kfs.first());
     int64_t bound = 0;
     for (size_t k = (size_t)from_keyframe; k < q.kfs.size(); k++) bound += q.kfs[k].n;
     if (keyframes) *keyframes = (int)std::max<int64_t>(0, (int64_t)q.kfs.size() - from_keyframe);
     if (points_bound) *points_bound = bound;
+    if (from) *from = from_keyframe;
 }
 
 // The named slots of the group as segments, keyframe entries and points (svo_submit_export_map). The keypoint counts
@@ -70,8 +73,8 @@ int grp_export_map(svo_group* c, int mem, const int* seqs, const int* seg, const
         const svo_map_region& r = regions[i];
         svo_map_segment& e = clear(dst->segments[seg[i]]);
         e.seq = seq0 + seqs[i]; e.run = q.run; e.frame_id = q.frame_id; e.time_stamp = (float)q.ts;
-        e.n_keyframes = (int)q.kfs.size(); e.keyframes_retired = q.kfs_retired; e.from_keyframe = r.from_keyframe;
-        grp_map_size(c, seqs[i], r.from_keyframe, &e.n_exported, &e.points_bound);
+        e.n_keyframes = (int)q.kfs.size(); e.keyframes_retired = q.kfs_retired; e.first_keyframe = q.kfs.first();
+        grp_map_size(c, seqs[i], r.from_keyframe, &e.n_exported, &e.points_bound, &e.from_keyframe);
         if (e.n_exported > r.keyframe_capacity || e.points_bound > r.point_capacity) {
             e.status = SVO_MAP_TOO_SMALL;
             continue;
@@ -79,7 +82,7 @@ int grp_export_map(svo_group* c, int mem, const int* seqs, const int* seg, const
         if (e.n_exported == 0) continue;
         placed.push_back({i, sets, staged});
         const int region_tile = (int)tiles.size();
-        for (int k = r.from_keyframe; k < e.n_keyframes; k++)
+        for (int k = e.from_keyframe; k < e.n_keyframes; k++)
             map_tiles(q.kfs[k].kps, q.kfs[k].n, k, sets++, host ? staged : r.first_point, region_tile, tiles);
         staged += e.points_bound;
     }
@@ -108,9 +111,9 @@ int grp_export_map(svo_group* c, int mem, const int* seqs, const int* seg, const
         svo_map_segment& e = dst->segments[seg[p.i]];
         int64_t at = 0;
         for (int j = 0; j < e.n_exported; j++) {
-            const KfHost& k = q.kfs[r.from_keyframe + j];
+            const KfHost& k = q.kfs[e.from_keyframe + j];
             svo_map_keyframe& o = clear(dst->keyframes[r.first_keyframe_entry + j]);
-            o.id = r.from_keyframe + j; o.n_total = k.n; o.n = kept[p.set0 + j];
+            o.id = e.from_keyframe + j; o.n_total = k.n; o.n = kept[p.set0 + j];
             o.first = r.first_point + at;
             std::memcpy(o.pose, k.pose, sizeof(o.pose));
             at += o.n;

@@ -175,7 +175,8 @@ int grp_export_scenes(svo_group* c, int mem, const int* seqs, const int* seg, in
         im.w = cols; im.h = rows;
         const size_t set0 = sets.size(), line0 = lines.size();
         placed.push_back({i, set0, line0});
-        const size_t kf0 = std::min<size_t>((size_t)style->from_keyframe, q.kfs.size());
+        // (the resident keyframes: a trimmed one has neither points nor a frustum)
+        const size_t kf0 = std::min<size_t>(std::max<size_t>((size_t)style->from_keyframe, (size_t)q.kfs.first()), q.kfs.size());
         if (style->show & SVO_SCENE_POINTS)
             for (size_t k = kf0; k < q.kfs.size(); k++) {
                 sets.push_back(scene_set(q.kfs[k].kps, q.kfs[k].n, (int)k));

@@ -38,7 +38,7 @@ std::vector<PlaneDim> snapshot_plane_dims(const SnapHeader& h, const svo_snapsho
     for (int i = 0; i < KP_PLANES; i++) v.push_back({KP_PLANE_ELEM[i] * h.n_keypoints, 1});
     v.push_back({4, 1});
     v.push_back({4, 1});
-    for (int k = 0; k < h.n_keyframes; k++)
+    for (int k = 0; k < h.n_keyframes - h.first_keyframe; k++)     // (kfs: the resident ones)
         for (int i = 0; i < KP_PLANES; i++) v.push_back({KP_PLANE_ELEM[i] * kfs[k].n, 1});
     for (int s = 0; s < h.n_image_sets; s++) {
         for (int l = 0; l < h.pyramid_levels; l++) v.push_back({h.width >> l, h.height >> l});
@@ -52,12 +52,12 @@ std::vector<PlaneDim> snapshot_plane_dims(const SnapHeader& h, const svo_snapsho
 }
 
 int64_t snapshot_plane_count(const SnapHeader& h) {
-    return FIXED_PLANES + (int64_t)KP_PLANES * h.n_keyframes + (int64_t)h.n_image_sets * (h.pyramid_levels + h.lk_levels);
+    return FIXED_PLANES + (int64_t)KP_PLANES * (h.n_keyframes - h.first_keyframe) + (int64_t)h.n_image_sets * (h.pyramid_levels + h.lk_levels);
 }
 
 int64_t snapshot_host_bytes(const SnapHeader& h) {
     return (int64_t)(sizeof(SnapHeader) + sizeof(PoseFilter) + SNAP_FRAME_BYTES) + (int64_t)sizeof(svo_pose) * h.n_trajectory +
-           (int64_t)sizeof(svo_snapshot_keyframe) * h.n_keyframes + (int64_t)sizeof(svo_snapshot_plane) * h.n_planes;
+           (int64_t)sizeof(svo_snapshot_keyframe) * (h.n_keyframes - h.first_keyframe) + (int64_t)sizeof(svo_snapshot_plane) * h.n_planes;
 }
 
 // the sections of a checked host part (an aligned private copy)
@@ -66,7 +66,7 @@ struct SnapView {
     const PoseFilter* filter;
     const uint8_t* frame;
     const svo_pose* trajectory;
-    const svo_snapshot_keyframe* kfs;
+    const svo_snapshot_keyframe* kfs;      // the resident keyframes: kfs[k] is keyframe first_keyframe + k
     const svo_snapshot_plane* dir;
 };
 
@@ -81,7 +81,7 @@ SnapView snapshot_view(const uint8_t* p) {
     v.trajectory = reinterpret_cast<const svo_pose*>(p);
     p += sizeof(svo_pose) * (size_t)v.h->n_trajectory;
     v.kfs = reinterpret_cast<const svo_snapshot_keyframe*>(p);
-    p += sizeof(svo_snapshot_keyframe) * (size_t)v.h->n_keyframes;
+    p += sizeof(svo_snapshot_keyframe) * (size_t)(v.h->n_keyframes - v.h->first_keyframe);
     v.dir = reinterpret_cast<const svo_snapshot_plane*>(p);
     return v;
 }
@@ -97,16 +97,18 @@ int check_snapshot(const void* host_part, int64_t bytes, std::vector<uint8_t>& c
     if (h.version != SVO_SNAPSHOT_VERSION) SNAP_BAD("version %u, this library reads version %d", h.version, SVO_SNAPSHOT_VERSION);
     if (h.byte_order != SVO_SNAPSHOT_BYTE_ORDER) SNAP_BAD("not little endian");
     if (h.status != SVO_SNAPSHOT_COMPLETE && h.status != SVO_SNAPSHOT_TOO_SMALL) SNAP_BAD("bad status %u", h.status);
-    if (h._reserved != 0) SNAP_BAD("reserved field is not 0");
     if (h.width < 16 || h.height < 16 || check_settings(&h.cam, h.width, h.height, 1) != SVO_OK) SNAP_BAD("bad camera settings or size");
     if (h.capacity != keypoint_capacity(h.cam, h.width, h.height)) SNAP_BAD("capacity %d does not follow from the settings", h.capacity);
     if (h.pyramid_levels != h.cam.max_pyramid_levels || h.lk_levels != usable_lk_levels(h.cam, h.width, h.height))
         SNAP_BAD("level counts do not follow from the settings");
     if (h.frame_id < -1 || h.n_trajectory != h.frame_id + 1) SNAP_BAD("frame id %d with %d poses", h.frame_id, h.n_trajectory);
     if (h.n_keypoints < 0 || h.n_keypoints > h.capacity) SNAP_BAD("%d keypoints, capacity %d", h.n_keypoints, h.capacity);
-    if (h.n_keyframes < 0 || h.n_keyframes > MAX_KEYFRAMES) SNAP_BAD("%d keyframes", h.n_keyframes);
-    if (h.n_image_sets < 0 || h.n_image_sets > h.n_keyframes + 1) SNAP_BAD("%d image sets for %d keyframes", h.n_image_sets, h.n_keyframes);
+    if (h.n_keyframes < 0) SNAP_BAD("%d keyframes", h.n_keyframes);
     if (h.keyframes_retired < 0 || h.keyframes_retired > std::max(h.n_keyframes - 1, 0)) SNAP_BAD("%d keyframes retired of %d", h.keyframes_retired, h.n_keyframes);
+    if (h.first_keyframe < 0 || h.first_keyframe > h.keyframes_retired) SNAP_BAD("first keyframe %d, %d retired", h.first_keyframe, h.keyframes_retired);
+    const int resident = h.n_keyframes - h.first_keyframe;
+    if (resident > MAX_KEYFRAMES) SNAP_BAD("%d resident keyframes", resident);
+    if (h.n_image_sets < 0 || h.n_image_sets > resident + 1) SNAP_BAD("%d image sets for %d keyframes", h.n_image_sets, resident);
     if (h.frame_id < 0 ? (h.n_keypoints || h.n_keyframes || h.n_image_sets) : (h.n_keyframes < 1 || h.n_image_sets < 1))
         SNAP_BAD("counts do not fit frame id %d", h.frame_id);
     if ((int64_t)h.n_planes != snapshot_plane_count(h)) SNAP_BAD("%d planes", h.n_planes);
@@ -119,8 +121,8 @@ int check_snapshot(const void* host_part, int64_t bytes, std::vector<uint8_t>& c
     copy.assign(static_cast<const uint8_t*>(host_part), static_cast<const uint8_t*>(host_part) + h.host_bytes);
     const SnapView v = snapshot_view(copy.data());
     std::vector<int> refs((size_t)h.n_image_sets, 0);
-    for (int k = 0; k < h.n_keyframes; k++) {
-        const svo_snapshot_keyframe& kf = v.kfs[k];
+    for (int k = h.first_keyframe; k < h.n_keyframes; k++) {
+        const svo_snapshot_keyframe& kf = v.kfs[k - h.first_keyframe];
         if (kf.n < 0 || kf.n > h.capacity) SNAP_BAD("keyframe %d: %d keypoints, capacity %d", k, kf.n, h.capacity);
         if (kf.image_set < -1 || kf.image_set >= h.n_image_sets || (k < h.keyframes_retired && kf.image_set != -1))
             SNAP_BAD("keyframe %d: image set %d", k, kf.image_set);
@@ -155,7 +157,7 @@ void plan_snapshot(const svo_group* c, const Seq& q, SavePlan& p) {
     h.frame_id = q.frame_id;
     if (q.frame_id >= 0) {
         h.n_keypoints = q.n_host; h.n_trajectory = (int)q.trajectory.size();
-        h.n_keyframes = (int)q.kfs.size(); h.keyframes_retired = q.kfs_retired;
+        h.n_keyframes = (int)q.kfs.size(); h.keyframes_retired = q.kfs_retired; h.first_keyframe = q.kfs.first();
         p.sets.push_back(q.cur_set);
         for (const KfHost& k : q.kfs) {
             svo_snapshot_keyframe r;
@@ -248,6 +250,8 @@ int grp_check_snapshot(const svo_group* c, const svo_camera_settings* slot_cam, 
     if (h.status != SVO_SNAPSHOT_COMPLETE) SNAP_BAD("only the header was saved (a capacity was too small)");
     if (std::memcmp(&h.cam, slot_cam, sizeof(h.cam)) != 0 || h.width != c->width || h.height != c->height || h.capacity != c->cap)
         SNAP_BAD("camera settings, size or capacity differ from the target slot's");
+    if (h.n_keyframes - h.first_keyframe > c->max_kf)
+        SNAP_BAD("%d resident keyframes, the ctx's keyframe table holds %d", h.n_keyframes - h.first_keyframe, c->max_kf);
     if (snap->data_capacity < h.data_bytes || (h.data_bytes > 0 && !snap->data))
         SNAP_BAD("the data part has %lld bytes of %lld", (long long)snap->data_capacity, (long long)h.data_bytes);
     return SVO_OK;
@@ -350,7 +354,8 @@ int grp_load(svo_group* c, const SnapshotLoad* loads, int n, int mem) {
         }
         q.cur_set = sets[0];
         q.cur_set->refs = 1;
-        for (int k = 0; k < h.n_keyframes; k++) {
+        q.kfs.clear(h.first_keyframe);           // (the ids go on from the saved slot's)
+        for (int k = 0; k < h.n_keyframes - h.first_keyframe; k++) {
             KfHost kf{};
             if (const int rc = take_kf_slab(c, &kf.kps)) return rc;
             std::memcpy(kf.pose, v.kfs[k].pose, sizeof(kf.pose));
@@ -371,18 +376,26 @@ int grp_load(svo_group* c, const SnapshotLoad* loads, int n, int mem) {
         q.frame_id = h.frame_id; q.n_host = h.n_keypoints; q.pending = false;
         // the keyframe table. Template cache: the keyframes a fresh run would hold ring blocks for get theirs with
         // the "stored" flags cleared, the others have none (as after their eviction)
+        // The records of the resident keyframes, in table order: rec[j] is ring slot j
         std::vector<KfDev>& rec = records[i];
-        rec.resize((size_t)h.n_keyframes);
-        for (int k = 0; k < h.n_keyframes; k++) {
-            fill_kf_record(c, q, k, q.kfs[k], rec[k]);
-            std::memcpy(rec[k].pose, q.kfs[k].pose, sizeof(rec[k].pose));
-            rec[k].n = q.kfs[k].n;
+        const int resident = q.kfs.resident(), mask = c->max_kf - 1;
+        rec.resize((size_t)std::min(c->max_kf, h.n_keyframes));     // (slots [0, that) cover every resident id's)
+        for (int k = h.first_keyframe; k < h.n_keyframes; k++) {
+            KfDev& d = rec[(size_t)(k & mask)];
+            fill_kf_record(c, q, k, q.kfs[k], d);
+            std::memcpy(d.pose, q.kfs[k].pose, sizeof(d.pose));
+            d.n = q.kfs[k].n;
             if (c->tmpl_kf > 0) {
-                if (k < h.n_keyframes - c->tmpl_kf) rec[k].tmpl = nullptr;
-                else HIP_TRY(hipMemsetAsync(rec[k].tmpl_valid, 0, c->tmpl_valid_bytes, st));
+                if (k < h.n_keyframes - c->tmpl_kf) d.tmpl = nullptr;
+                else HIP_TRY(hipMemsetAsync(d.tmpl_valid, 0, c->tmpl_valid_bytes, st));
             }
         }
-        HIP_TRY(hipMemcpyAsync(q.d_kfs, rec.data(), sizeof(KfDev) * rec.size(), hipMemcpyHostToDevice, st));
+        // (one copy while the resident ids do not wrap, else the two ends of the table)
+        const int s0 = h.first_keyframe & mask;
+        const int run0 = std::min(resident, c->max_kf - s0);
+        HIP_TRY(hipMemcpyAsync(q.d_kfs + s0, rec.data() + s0, sizeof(KfDev) * (size_t)run0, hipMemcpyHostToDevice, st));
+        if (resident > run0)
+            HIP_TRY(hipMemcpyAsync(q.d_kfs, rec.data(), sizeof(KfDev) * (size_t)(resident - run0), hipMemcpyHostToDevice, st));
         // the data part -> device
         const uint8_t* base = static_cast<const uint8_t*>(loads[i].data);
         if (host && h.data_bytes > 0) {

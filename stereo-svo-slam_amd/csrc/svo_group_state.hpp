@@ -17,7 +17,7 @@
 //                 keyframe's set stay resident (288 GB: ~1 MB per 752x480 set).
 //   keypoints   : two SoA sets (KpsDev) ping-ponged by the order-preserving
 //                 compactions; per-point scratch (tracked, err, disparity).
-//   keyframes   : table of KfDev records + per-keyframe SoA copies.
+//   keyframes   : table of KfDev records (a ring over the resident ids) + per-keyframe SoA copies.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -163,6 +163,34 @@ struct KfHost {
     KpsDev kps;                 // device arrays, carved out of one slab (kps.n: unused)
 };
 
+// The keyframes of a sequence by id. Ids keep counting up over the whole run; [first(), size()) are resident and
+// the ones below were trimmed (drop_below). Every host index by id goes through here, so nothing else knows the
+// offset; a range-for visits the resident ones, oldest first.
+class KfList {
+  public:
+    int first() const { return first_; }
+    size_t size() const { return (size_t)first_ + v_.size(); }       // ids given out so far (not: resident keyframes)
+    int resident() const { return (int)v_.size(); }
+    bool empty() const { return v_.empty(); }                        // (a run with keyframes has a resident one: the newest)
+    KfHost& operator[](size_t id) { return v_[id - (size_t)first_]; }
+    const KfHost& operator[](size_t id) const { return v_[id - (size_t)first_]; }
+    KfHost& back() { return v_.back(); }
+    const KfHost& back() const { return v_.back(); }
+    void push_back(const KfHost& k) { v_.push_back(k); }
+    std::vector<KfHost>::iterator begin() { return v_.begin(); }
+    std::vector<KfHost>::iterator end() { return v_.end(); }
+    std::vector<KfHost>::const_iterator begin() const { return v_.begin(); }
+    std::vector<KfHost>::const_iterator end() const { return v_.end(); }
+    void drop_below(int id) {                                        // first() <= id <= size()
+        v_.erase(v_.begin(), v_.begin() + (id - first_));
+        first_ = id;
+    }
+    void clear(int first = 0) { v_.clear(); first_ = first; }        // no keyframes; the next one gets id `first`
+  private:
+    std::vector<KfHost> v_;
+    int first_ = 0;
+};
+
 struct Seq {
     KpsDev kps[2];
     int cur = 0;
@@ -176,8 +204,8 @@ struct Seq {
     PoseMats* sia_mats = nullptr;    // rotation matrices of the aligned pose (sia_gn_kernel -> klt_track_kernel)
     uint8_t* tmpl_base = nullptr;    // KLT template cache: tmpl_kf blocks (a ring over the sequence's keyframes)
     uint8_t* tmpl_valid = nullptr;   // their "stored" flags
-    KfDev* d_kfs = nullptr;
-    std::vector<KfHost> kfs;
+    KfDev* d_kfs = nullptr;          // the keyframe table: a ring of svo_group::max_kf records, keyframe id in slot id & (max_kf - 1)
+    KfList kfs;                      // kfs.first() <= kfs_retired <= kfs.size() - 1 (while there is a keyframe)
     int kfs_retired = 0;             // keyframes [0, kfs_retired) have given their image sets back
     DetCell* det = nullptr; int* n_det = nullptr;
     DetCell* sel = nullptr; int* sel_level = nullptr; int* sel_cell = nullptr; int* occupied = nullptr;
@@ -325,6 +353,7 @@ struct svo_group {
     svo_totals totals;
     std::vector<svo_launch_shape> launch_shapes;   // distinct shapes of launch_sia / launch_reproj and their launches
     bool retire_kf_images = true;    // SVO_KEEP_KEYFRAME_IMAGES=1: keep every keyframe's image set (the reference's behaviour)
+    int kf_window = -1;              // svo_ctx_set_keyframe_window: retired keyframes a slot keeps after a step (-1: all of them)
     int image_sets = 0;              // image sets allocated so far
     double host_ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // SVO_HOST_TIMING diagnostic: host phases of a step
     long host_steps = 0;
@@ -360,7 +389,7 @@ int dev_alloc(svo_group* c, T** p, size_t count, bool zero = true) {
 // does the format need ingest_kernel? GRAY_PAIR is the tracker's own input; SBS_GRAY is GRAY_PAIR at base + W and base
 inline bool converts(int format) { return format != SVO_INPUT_GRAY_PAIR && format != SVO_INPUT_SBS_GRAY; }
 
-constexpr int MAX_KEYFRAMES = 4096;   // of one sequence (the keyframe table)
+constexpr int MAX_KEYFRAMES = 4096;   // resident ones of one sequence (the keyframe table's default and largest size)
 
 // The tile table of an export, a save or a load (TileTable, svo_host.hpp) goes up through the group's argument
 // blocks, pinned and device: between two steps the stream is idle and nothing in them is live (every step fills and
@@ -382,6 +411,7 @@ void fill_kf_record(const svo_group* c, const Seq& q, int id, const KfHost& k, K
 void flush_one(Seq& q);
 void flush_pending(svo_group* c);
 void end_sequence(svo_group* c, int s);
+void trim_keyframes(svo_group* c, Seq& q, int below);                  // drops the slot's keyframes below min(below, kfs_retired)
 int check_settings(const svo_camera_settings* cam, int width, int height, int n_sequences);
 int keypoint_capacity(const svo_camera_settings& cam, int width, int height);
 int usable_lk_levels(const svo_camera_settings& cam, int width, int height);

@@ -270,7 +270,7 @@ void pack_tracking_args(svo_group* c, const Step& st) {
         sa.mats_out = q.sia_mats;
         sa.dbg_H = nullptr; sa.dbg_level = -1; sa.cap = c->cap; sa.exact_pinv = c->exact_pinv;
         KltArgs& ka = clear(a.klt.h[slot]);
-        ka.kfs = q.d_kfs; ka.kf_id = k.kf_id; ka.n_cur = c->n_lk;
+        ka.kfs = q.d_kfs; ka.kf_mask = c->max_kf - 1; ka.kf_id = k.kf_id; ka.n_cur = c->n_lk;
         for (int l = 0; l < c->n_lk; l++) ka.cur[l] = q.cur_set->lk[l];
         ka.n_ptr = k.n; ka.prev_pts = nullptr; ka.cur_pts = q.tracked; ka.status = q.klt_status;
         ka.err = q.klt_err; ka.win = c->cam.window_size_opt_flow;
@@ -288,7 +288,7 @@ void pack_tracking_args(svo_group* c, const Step& st) {
         fa.kps2d = k.kps2d; fa.kps3d = k.kps3d; fa.flags = k.flags;
         fa.outlier_count = k.outl; fa.inlier_count = k.inl; fa.kf_inv_depth = k.kfx;
         fa.kf_variance = k.kfP; fa.disparity = q.disparity;
-        fa.kfs = q.d_kfs; fa.kf_id = k.kf_id; fa.kp_index = k.kp_index;
+        fa.kfs = q.d_kfs; fa.kf_mask = c->max_kf - 1; fa.kf_id = k.kf_id; fa.kp_index = k.kp_index;
         fa.do_outlier_check = 1; fa.do_update = 1; fa.do_flags = 1; fa.do_reproject = 1;
         fa.width = c->width; fa.height = c->height; fa.inside_count = c->d_inside + s;
     }
@@ -387,7 +387,8 @@ int launch_tracking(svo_group* c, const Step& s) {
 // keyframe `id` of sequence s on its current image set; its record goes to the pinned staging slot of s
 // (it reaches the device inside the KfInitArgs block: no copy per keyframe)
 int new_keyframe_storage(svo_group* c, Seq& q, int s, int id) {
-    if (id >= c->max_kf) return svo_set_error(SVO_ERR_CAPACITY, "more than %d keyframes", c->max_kf);
+    if (id - q.kfs.first() >= c->max_kf)     // (the ring slot of `id` still belongs to keyframe id - max_kf)
+        return svo_set_error(SVO_ERR_CAPACITY, "more than %d resident keyframes (svo_trim_keyframes makes room)", c->max_kf);
     KfHost k{};
     if (const int rc = take_kf_slab(c, &k.kps)) return rc;
     k.set = q.cur_set;
@@ -429,11 +430,12 @@ int pack_keyframe_args(svo_group* c, int slot, int s, bool first_frame) {
     KfInitArgs& ia = clear(a.kf_init.h[slot]);
     ia.cam = q.cam; ia.kps = q.kps[q.cur]; ia.old_count = &dr->old_count;
     ia.disparity = q.disparity; ia.frame_pose = dr->pose_refined;
-    ia.first_frame = first_frame ? 1 : 0; ia.new_kf_id = id; ia.kfs = q.d_kfs;
+    ia.first_frame = first_frame ? 1 : 0; ia.new_kf_id = id; ia.kfs = q.d_kfs; ia.kf_mask = c->max_kf - 1;
     ia.color_lcg = q.color_lcg; ia.n_out = &dr->kf_n;
     ia.record = a.kf_record.h[s];
     ia.tmpl_valid_bytes = (int)c->tmpl_valid_bytes;
-    ia.evict_id = (c->tmpl_kf > 0 && id >= c->tmpl_kf) ? id - c->tmpl_kf : -1;
+    // (a trimmed keyframe has no record to take the block away from: its ring slot may be the new keyframe's own)
+    ia.evict_id = (c->tmpl_kf > 0 && id - c->tmpl_kf >= q.kfs.first()) ? id - c->tmpl_kf : -1;
     return SVO_OK;
 }
 
@@ -492,7 +494,8 @@ int read_stage_times(svo_group* c, Step& s) {
 // those whose bit is set in r.live_kf: the others hand their image sets back to the sequence's free
 // list, so memory stays bounded by the keyframes still in use
 // instead of growing with every keyframe (the reference keeps them all). Nothing else of a keyframe goes:
-// its keypoint arrays, pose and table record stay for the depth filter and the getters.
+// its keypoint arrays, pose and table record stay for the depth filter and the getters, until the keyframe is
+// trimmed (trim_keyframes).
 void retire_keyframe_images(svo_group* c, const Step& s) {
     for (int seq : s.trk) {
         Seq& q = c->seqs[seq];
@@ -585,6 +588,11 @@ int step(svo_group* c, Step& s) {
     lap(c, s, 5);
     if ((rc = read_stage_times(c, s))) return rc;
     if (c->retire_kf_images) retire_keyframe_images(c, s);
+    if (c->kf_window >= 0)                // svo_ctx_set_keyframe_window: host bookkeeping only
+        for (int seq : s.trk) {
+            Seq& q = c->seqs[seq];
+            if (q.kfs_retired - q.kfs.first() > c->kf_window) trim_keyframes(c, q, q.kfs_retired - c->kf_window);
+        }
     return book_frame(c, s);
 }
 

@@ -221,7 +221,7 @@ struct KfDev {                    // one keyframe as the device sees it
 };
 
 struct KltArgs {
-    const KfDev* kfs;             // keyframe table
+    const KfDev* kfs;             // keyframe table: keyframe id in record id & kf_mask
     const int* kf_id;             // [n] origin keyframe of each point (null: all 0)
     ImgView cur[SVO_LK_LEVELS];
     int n_cur;
@@ -231,6 +231,7 @@ struct KltArgs {
     uint8_t* status;              // [n]
     float* err;                   // [n]
     int win;
+    int kf_mask;                  // table records - 1 of a ring (the tracker's); -1: the table is indexed by id as it is
     // optional fused projection (tracker path): cur_pts = project(pose, kps3d) first
     const float* proj_pose;       // [6] or null
     const PoseMats* proj_mats;    // optional: pose_mats(proj_pose) computed once per sequence (sia_gn_kernel)
@@ -300,9 +301,10 @@ struct FilterArgs {
     const svo_kp2d* ref2d;
     const float* kf_pose;         // [n*6]
     // ... or the keyframe table (tracker): gathers refs and writes results back
-    KfDev* kfs;
+    KfDev* kfs;                   // (keyframe id in record id & kf_mask, as KltArgs)
     const int* kf_id;
     const int* kp_index;
+    int kf_mask;
     int do_outlier_check, do_update, do_flags, do_reproject;
     int width, height;
     int* inside_count;            // keyframe_needed numerator (or null)

@@ -91,12 +91,13 @@ struct KfInitArgs {
     const float* frame_pose;
     int first_frame;   // 1: frame 0 of a sequence: zero pose, no temporary flags, colour LCG reseeded (SVO_COLOR_LCG_SEED)
     int new_kf_id;
+    int kf_mask;       // the table is a ring: keyframe id in record id & kf_mask
     KfDev* kfs;
     uint32_t* color_lcg;
     int* n_out;
     const int* enable;
     // the record of the new keyframe (written to kfs[new_kf_id] by the kernel: no copy of its own per keyframe),
-    // the "stored" flags of its template cache block (cleared here) and the keyframe that loses the block (-1: none)
+    // the "stored" flags of its template cache block (cleared here) and the keyframe that loses the block (-1: none, or no longer in the table)
     KfDev record;
     int tmpl_valid_bytes;
     int evict_id;

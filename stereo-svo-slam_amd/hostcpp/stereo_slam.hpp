@@ -81,8 +81,10 @@ public:
     void get_keyframes(std::vector<KeyFrame>& keyframes) {
         int count = 0;
         check(svo_get_keyframe_count(ctx, 0, &count));
-        keyframes.resize(count);
-        for (int i = 0; i < count; i++) read_keyframe(i, keyframes[i]);
+        svo_keyframe_range range{};                      // (the resident ones: [first, count) once the slot was trimmed)
+        check(svo_get_keyframe_range(ctx, 0, &range));
+        keyframes.resize(count - range.first);
+        for (int i = range.first; i < count; i++) read_keyframe(i, keyframes[i - range.first]);
     }
     void get_trajectory(std::vector<Pose>& trajectory) {
         int n = 0;

@@ -47,6 +47,7 @@ SYMBOLS = (
     "svo_ctx_get_rigs",
     "svo_klt_track_batch", "svo_klt_cache_layout",
     "svo_rectify_inverse", "svo_build_rectify_maps", "svo_ctx_add_rigs_calibrated", "svo_ctx_set_calibration",
+    "svo_submit_trim_keyframes", "svo_trim_keyframes", "svo_ctx_set_keyframe_window", "svo_get_keyframe_range",
 )
 
 # svo_ctx_set_input_format / svo_convert_frames: how the buffers of a sequence become its two gray images
@@ -192,13 +193,19 @@ MAP_KEYFRAME_DTYPE = np.dtype([("id", "<i4"), ("n_total", "<i4"), ("n", "<i4"), 
 MAP_SEGMENT_DTYPE = np.dtype([("seq", "<i4"), ("run", "<i4"), ("frame_id", "<i4"), ("status", "<i4"),
                               ("n_keyframes", "<i4"), ("keyframes_retired", "<i4"), ("from_keyframe", "<i4"),
                               ("n_exported", "<i4"), ("n_points", "<i8"), ("points_bound", "<i8"),
-                              ("time_stamp", "<f4"), ("_pad", "<i4", (3,))])
+                              ("time_stamp", "<f4"), ("_pad", "<i4", (3,))])      # (_pad[0]: first_keyframe)
 # svo_map_region as a numpy record, so that a call's regions are one array
 MAP_REGION_DTYPE = np.dtype([("first_point", "<i8"), ("point_capacity", "<i8"), ("first_keyframe_entry", "<i8"),
                              ("keyframe_capacity", "<i4"), ("from_keyframe", "<i4")])
 assert (MAP_POINT_DTYPE.itemsize, MAP_KEYFRAME_DTYPE.itemsize, MAP_SEGMENT_DTYPE.itemsize,
         MAP_REGION_DTYPE.itemsize) == (16, 48, 64, 32)
 MAP_COMPLETE, MAP_TOO_SMALL = 0, 1
+
+
+def map_first_keyframe(segment):
+    """svo_map_segment.first_keyframe of a MAP_SEGMENT_DTYPE record: the slot's oldest resident keyframe (the C union
+    member over _pad[0])"""
+    return int(segment["_pad"][0])
 IGNORE_DURING_REFINEMENT, IGNORE_COMPLETELY, IGNORE_TEMPORARY = 1, 2, 4
 
 
@@ -378,7 +385,25 @@ class SnapshotInfo(C.Structure):
                  "n_trajectory", "n_keyframes", "keyframes_retired", "n_image_sets", "n_planes", "_reserved")]
 
 
+    @property
+    def first_keyframe(self):
+        """the oldest keyframe in the snapshot: the ones below were trimmed (the C field of that name)"""
+        return self._reserved
+
+
 assert C.sizeof(SnapshotInfo) == 160
+
+
+class KeyframeRange(C.Structure):
+    """svo_keyframe_range (include/svo_hip.h): keyframes [first, count) of a slot are resident, those below `retired`
+    are final; `table`: resident keyframes a slot can hold."""
+    _fields_ = [(n, C.c_int32) for n in ("first", "retired", "count", "table")]
+
+    def __repr__(self):
+        return f"KeyframeRange(first={self.first}, retired={self.retired}, count={self.count}, table={self.table})"
+
+
+assert C.sizeof(KeyframeRange) == 16
 SNAPSHOT_COMPLETE, SNAPSHOT_TOO_SMALL = 0, 1
 
 

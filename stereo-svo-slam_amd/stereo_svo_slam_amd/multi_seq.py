@@ -167,15 +167,21 @@ def submit_queue(slam, steps):
 
 
 def play_queue(slam, frames_of, lengths, time_of=lambda s, k: k / 20.0, order=None, pipelined=False, borrow=False,
-               rigs=None):
+               rigs=None, keyframe_window=None):
     """Drive a ctx through queue_schedule(lengths, slam.n, order): a slot is restarted before the first frame
     of every sequence but its first, slots without a frame get None, time stamps are per sequence
     (time_of(sequence, frame index)). frames_of(sequence, k) -> (left, right). pipelined: every frame set and
     restart is queued (svo_submit_images; torch frames, with borrow used in place) and waited for once at the
     end; otherwise one new_images call per step. rigs: the camera rig (an id of slam.add_rigs, 0: the ctx's own) of
     every sequence; a freed slot takes the next sequence together with its rig (slam.assign_rigs instead of the
-    restart where the rig differs from the slot's). Returns ({sequence: (slot, run ordinal in that slot)},
+    restart where the rig differs from the slot's). keyframe_window: None leaves the ctx's setting alone, else
+    slam.set_keyframe_window(keyframe_window) before the first step (an int >= -1: the retired keyframes a slot keeps, so
+    that sequences of any length play in bounded memory). Returns ({sequence: (slot, run ordinal in that slot)},
     number of sequence-frames)."""
+    if keyframe_window is not None:
+        if int(keyframe_window) != keyframe_window or keyframe_window < -1:
+            raise ValueError(f"keyframe_window {keyframe_window!r}: an int >= -1 (or None)")
+        slam.set_keyframe_window(int(keyframe_window))
     if pipelined:
         steps, where, frames = pack_queue(slam, frames_of, lengths, time_of, order, borrow, rigs)
         submit_queue(slam, steps)

@@ -360,7 +360,7 @@ class Replay:
     """process_image loop: only the time inside new_image is accumulated (slam_app.cpp:186-190)."""
 
     def __init__(self, settings, device=0, time_trace=False, fast=False, rectify_maps=None, input_format=None,
-                 gpu_imu=False, dump_views=None, dump_scene=None, calibration=None):
+                 gpu_imu=False, dump_views=None, dump_scene=None, calibration=None, keyframe_window=None):
         """fast=False keeps the library default: the reference-order Gauss-Newton (bit-exact traces).
         rectify_maps = (left maps, right maps): the frames fed are raw and are rectified on the GPU.
         calibration = (left, right) CameraCalibrations: the same, with the maps built on the GPU as well.
@@ -369,7 +369,8 @@ class Replay:
         svo_update_pose calls: the same bits.
         dump_views: a directory that receives, per frame, the last keyframe and the current frame with a marker per
         keypoint as the reference app's window shows them (write_ppm), outside the timed region.
-        dump_scene: a directory that receives, per frame, the 3-D viewer's picture of the map (get_scene), likewise."""
+        dump_scene: a directory that receives, per frame, the 3-D viewer's picture of the map (get_scene), likewise.
+        keyframe_window: the retired keyframes the tracker keeps (StereoSlamBatch.set_keyframe_window); None: all."""
         self.settings = settings
         self.dump_views, self.dump_scene = dump_views, dump_scene
         for d in (dump_views, dump_scene):
@@ -385,6 +386,8 @@ class Replay:
             self.slam.set_calibration(*calibration)
         if input_format is not None:
             self.slam.set_input_format(input_format)
+        if keyframe_window is not None:
+            self.slam.set_keyframe_window(keyframe_window)
         self.cumulative = []
         self._t = 0.0
         self.time_trace = time_trace
@@ -449,7 +452,14 @@ def _load_pair(pattern, k):
     return _gray(lp % k), _gray(rp % k)
 
 
-def main(argv=None):
+def _keyframe_window(text):
+    k = int(text)
+    if k < 0:
+        raise argparse.ArgumentTypeError("a count >= 0")
+    return k
+
+
+def build_parser():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--settings", help="cv::FileStorage YAML with the Camera.* keys")
     ap.add_argument("--synthetic", choices=sorted(synth.CONFIGS), help="seeded synthetic sequence")
@@ -483,6 +493,14 @@ def main(argv=None):
     ap.add_argument("--rate", type=float, default=20.0, help="frames per second of the time stamps")
     ap.add_argument("-t", "--trajectory", help="output CSV")
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--keyframe-window", metavar="K", type=_keyframe_window, default=None,
+                    help="keep only K retired keyframes (svo_ctx_set_keyframe_window): a replay of any length runs in "
+                         "bounded device memory; the poses do not change. Default: keep every keyframe")
+    return ap
+
+
+def main(argv=None):
+    ap = build_parser()
     args = ap.parse_args(argv)
 
     gt = None
@@ -532,7 +550,8 @@ def main(argv=None):
         ap.error("--gpu-imu needs --gyro")
     gyro = np.loadtxt(args.gyro, ndmin=2) if args.gyro else None
     rp = Replay(settings, args.device, args.time_trace, args.fast, rectify_maps=rect, input_format=fmt, gpu_imu=args.gpu_imu,
-                dump_views=args.dump_views, dump_scene=args.dump_scene, calibration=cal)
+                dump_views=args.dump_views, dump_scene=args.dump_scene, calibration=cal,
+                keyframe_window=args.keyframe_window)
     for k, (left, right, t) in enumerate(frames):
         rp.feed(left, right, t, None if gyro is None else gyro[gyro[:, 0] == k, 1:4])
     rows = rp.rows()

@@ -254,6 +254,10 @@ class MapExport:
         n = int(e["n_exported"]) if e["status"] == hip_lib.MAP_COMPLETE else 0
         return self._kfs[int(r["first_keyframe_entry"]):int(r["first_keyframe_entry"]) + n]
 
+    def first_keyframe(self, i):
+        """svo_map_segment.first_keyframe of named slot i: its oldest resident keyframe when the job ran"""
+        return hip_lib.map_first_keyframe(self.segments[i])
+
     def _records(self, lo, n):
         a = self.points_buffer[lo:lo + n]
         a = a.cpu().numpy() if self.device_mode else a.numpy()
@@ -767,6 +771,32 @@ class StereoSlamBatch:
         arr = (C.c_int * max(len(seqs), 1))(*seqs)
         _check(lib().svo_ctx_restart_sequences(self._ctx, arr, len(seqs)))
 
+    # -- trimming retired keyframes ------------------------------------------------------------------------
+    def trim_keyframes(self, seqs=None, below=None, wait=True):
+        """svo_submit_trim_keyframes: the slots `seqs` (None: all, in order) drop their keyframes with an id below
+        min(below, retired) (below: None = everything retired, an int, or one per slot), ordered with the submitted
+        frame sets like restart(). wait=False: queued only. Ids never move; the storage returns to the ctx."""
+        if seqs is not None:
+            seqs = [int(s) for s in ([seqs] if np.isscalar(seqs) else seqs)]
+        n = self.n if seqs is None else len(seqs)
+        arr = None if seqs is None else (C.c_int * max(n, 1))(*seqs)
+        lim = None
+        if below is not None:
+            lim = (C.c_int * max(n, 1))(*[int(b) for b in np.broadcast_to(below, (n,))])
+        fn = lib().svo_trim_keyframes if wait else lib().svo_submit_trim_keyframes
+        _check(fn(self._ctx, arr, lim, n))
+
+    def set_keyframe_window(self, keep):
+        """svo_ctx_set_keyframe_window: keep >= 0: after each step a slot keeps at most `keep` retired keyframes;
+        -1 (the default): slots never trim on their own. Waits for the queues."""
+        _check(lib().svo_ctx_set_keyframe_window(self._ctx, int(keep)))
+
+    def keyframe_range(self, seq=0):
+        """svo_get_keyframe_range: a hip_lib.KeyframeRange (first, retired, count, table) of the slot (waits)."""
+        r = hip_lib.KeyframeRange()
+        _check(lib().svo_get_keyframe_range(self._ctx, int(seq), C.byref(r)))
+        return r
+
     # -- camera rigs ---------------------------------------------------------------------------------------
     def add_rigs(self, rigs):
         """svo_ctx_add_rigs / svo_ctx_add_rigs_calibrated: every rig is a dict (or CameraSettings) with the ten float
@@ -954,7 +984,8 @@ class StereoSlamBatch:
         return Frame(pose, k2, k3, info)
 
     def get_keyframes(self, seq=0):
-        return [self.get_keyframe(i, seq) for i in range(self.num_keyframes(seq))]
+        """the resident keyframes, oldest first: ids keyframe_range(seq).first .. num_keyframes(seq) - 1"""
+        return [self.get_keyframe(i, seq) for i in range(self.keyframe_range(seq).first, self.num_keyframes(seq))]
 
     def get_trajectory(self, seq=0):
         n = C.c_int(0)
@@ -1042,6 +1073,12 @@ class StereoSlam(StereoSlamBatch):
         else:
             super().set_input_format(fmt)
 
+    def set_keyframe_window(self, keep):
+        if self._ctx is None:              # (kept until the first frame makes the ctx)
+            self._window = int(keep)
+        else:
+            super().set_keyframe_window(keep)
+
     def new_image(self, left, right=None, time_stamp=0.0):
         """one frame; with a one-buffer input format `left` is the frame and `right` is ignored"""
         if self._ctx is None:   # the reference learns the image size from the first frame
@@ -1058,6 +1095,8 @@ class StereoSlam(StereoSlamBatch):
                 self.enable_timing(True)
             if getattr(self, "_rect", None) is not None:
                 self._apply_rectification()
+            if getattr(self, "_window", -1) >= 0:
+                super().set_keyframe_window(self._window)
         self.new_images([left], [right], [time_stamp])
 
     def get_image(self, what="frames", **kw):
