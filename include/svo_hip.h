@@ -1194,6 +1194,115 @@ int svo_klt_track_batch(svo_handle *h, int batch, const svo_klt_sequence *seqs, 
  * double cI1, cI2. */
 int svo_klt_cache_layout(int win, int64_t *record_bytes, int64_t *header_offset, int64_t *header_bytes, int *levels);
 
+/* Diagnostics: the four bookkeeping launches of the keyframe path as the tracker makes them, on caller-made arrays.
+ * Each entry takes a HOST array seqs[batch] (1 <= batch <= 4096) whose pointers are device memory, fills one
+ * argument block per sequence the way the tracker's step fills it, launches once through the tracker's launcher,
+ * and is complete on return; it keeps nothing between calls. The counts and indices a kernel would index with are
+ * read back and checked before the launch (a diagnostic may wait).
+ *
+ * A keypoint set as the tracker holds it: twelve planes and a count, all device memory. */
+typedef struct svo_kps_planes {
+    svo_kp2d *kps2d;
+    svo_kp3d *kps3d;
+    uint32_t *flags;                /* SVO_IGNORE_* bits                                                         */
+    int32_t  *kf_id, *kp_index, *outlier_count, *inlier_count;
+    float    *kf_inv_depth, *kf_variance, *score;
+    int32_t  *level_type;           /* level | type << 8                                                         */
+    uint32_t *color;                /* r | g << 8 | b << 16                                                      */
+    int32_t  *n;                    /* [1]                                                                       */
+} svo_kps_planes;
+/* Host only: the workgroup sizes the compaction launch of sets of `cap` keypoints and the select + merge launch of
+ * `max_cells` candidates run with, and the bytes of "stored" flags a ctx gives a keyframe's template cache of
+ * tmpl_cap keypoints (any of the outputs may be NULL). */
+int svo_keyframe_launch_info(int cap, int max_cells, int tmpl_cap, int *compact_threads, int *merge_threads,
+                             int64_t *tmpl_valid_bytes);
+/* compact_kernel: src -> dst, order preserving, all twelve planes; *dst.n = the number kept.
+ *   mode 0  remove_outliers (src/lib/stereo_slam.cpp:43-56): SVO_IGNORE_COMPLETELY goes
+ *   mode 1  find_bad_keypoints (src/lib/depth_calculator.cpp:67-86) in a width x height image
+ *   start   1: a sequence starts: nothing is copied, *dst.n = *src.n = 0 whatever *src.n held
+ *   zero, zero_res: (or NULL) zero_count / zero_res_count words set to 0
+ *   min_kf  (or NULL; mode 0 only, the entry refuses it with mode 1) [3]: the smallest kf_id among the keypoints kept
+ *           (INT_MAX: none), then a 64-bit mask, low word first: bit j = a kept keypoint has kf_id min + j
+ *   enable  (or NULL) [1]: 0 = the sequence's workgroup does nothing at all
+ * Every plane holds `cap` entries; *src.n must be 0..cap unless start is set. *threads (or NULL) receives the
+ * workgroup size launch_compact chose for cap. */
+typedef struct svo_compact_sequence {
+    svo_kps_planes src, dst;
+    int32_t mode, width, height, start;
+    const int32_t *enable;
+    int32_t *zero, *zero_res, *min_kf;
+    int32_t zero_count, zero_res_count;
+} svo_compact_sequence;
+int svo_compact_batch(svo_handle *h, int batch, const svo_compact_sequence *seqs, int cap, int *threads);
+/* kf_select_merge_kernel: select_best_keypoints (src/lib/depth_calculator.cpp:37-65) over det[n_levels][max_cells]
+ * with counts n_det[n_levels], then merge_keypoints (:88-130, grid arguments swapped as :179-180 does) into kps:
+ * kps2d, score and level_type of the appended entries are written, *kps.n grows, clamped at cap with *overflow = 1
+ * (it is not written otherwise); *old_count = the count before. sel, sel_level, sel_cell [max_cells] and occupied
+ * [occupied_count >= the merge grid's cells] are workspaces. Checked: 0 <= n_det[i] <= max_cells, 0 <= *kps.n <= cap.
+ * *threads: the workgroup size launch_select_merge chose for max_cells. */
+typedef struct svo_merge_sequence {
+    svo_camera_settings cam;
+    int32_t width, height;
+    const svo_det_cell *det;
+    const int32_t *n_det;
+    svo_kps_planes kps;
+    svo_det_cell *sel;
+    int32_t *sel_level, *sel_cell, *occupied;
+    int32_t *old_count, *overflow;
+    const int32_t *enable;
+    int32_t occupied_count, pad_;
+} svo_merge_sequence;
+int svo_keyframe_merge_batch(svo_handle *h, int batch, const svo_merge_sequence *seqs, int n_levels, int max_cells,
+                             int cap, int *threads);
+/* kf_init_kernel: the depth and filter initialisation of keypoints [*old_count, *kps.n) (src/lib/depth_calculator.cpp:
+ * 241-289, colours from the sequence's LCG state *color_lcg), the copy of the whole set and the pose into the new
+ * keyframe's record (src/lib/keyframe_manager.cpp:15-32), and the ignore_temporary rules of src/lib/stereo_slam.cpp:
+ * 157-159 and :237-245. kfs: the keyframe table, (kf_mask + 1) records of svo_keyframe_record_layout bytes, a ring:
+ * record new_kf_id & kf_mask is written (planes = `record`, whose n is not used; tmpl, tmpl_valid, tmpl_cap,
+ * tmpl_win; n and pose), record evict_id & kf_mask (evict_id >= 0) loses its tmpl pointer. tmpl_valid_bytes (a
+ * multiple of 4) bytes at tmpl_valid are cleared. first_frame: zero pose (frame_pose is not read), LCG reseeded, no
+ * keypoint stays temporary. *n_out = *kps.n. The planes of kps and record hold `cap` entries. Checked:
+ * 0 <= *old_count <= *kps.n <= cap. */
+typedef struct svo_kf_init_sequence {
+    svo_camera_settings cam;
+    int32_t first_frame, new_kf_id, kf_mask, evict_id;
+    svo_kps_planes kps, record;
+    const int32_t *old_count;
+    const float *disparity, *frame_pose;
+    void *kfs;
+    int64_t kfs_bytes;
+    uint32_t *color_lcg;
+    int32_t *n_out;
+    const int32_t *enable;
+    void *tmpl;
+    uint8_t *tmpl_valid;
+    int32_t tmpl_valid_bytes, tmpl_cap, tmpl_win, pad_;
+} svo_kf_init_sequence;
+int svo_keyframe_init_batch(svo_handle *h, int batch, const svo_kf_init_sequence *seqs, int cap);
+/* Host only: bytes of a keyframe table record and the offsets in it of its count (int32), pose (float[6]), template
+ * cache pointer, "stored" flags pointer, tmpl_cap and tmpl_win (int32), and of the twelve plane pointers in the order
+ * of the planes structure above. Any output may be NULL. */
+int svo_keyframe_record_layout(int64_t *record_bytes, int64_t *n_offset, int64_t *pose_offset, int64_t *tmpl_offset,
+                               int64_t *tmpl_valid_offset, int64_t *tmpl_cap_offset, int64_t *tmpl_win_offset,
+                               int64_t plane_offsets[12]);
+/* ssd_disparity_kernel as the tracker launches it: grid (n_bound, batch); sequence b handles keypoints
+ * first + *first_ptr + 0 .. n_bound - 1 that lie below *n (first_ptr NULL: + 0); every other entry of disparity stays.
+ * `win` and `search_y` choose the kernel shape (the tracker passes its settings); a sequence's own win, search_x
+ * and search_y must not exceed win, 64 and search_y. kps2d and disparity hold `cap` entries. Checked: 0 <= *n <= cap,
+ * and first, *first_ptr and n_bound each within 0..2^29 (their sum stays an int). *max_win: the largest window of the kernel shape launch_ssd chose (31 or 35). */
+typedef struct svo_ssd_sequence {
+    svo_image left, right;
+    const int32_t *n;
+    const svo_kp2d *kps2d;
+    float *disparity;
+    int32_t win, search_x, search_y, clamp_half;
+    int32_t first, cap;
+    const int32_t *first_ptr;
+    const int32_t *enable;
+} svo_ssd_sequence;
+int svo_ssd_disparity_batch(svo_handle *h, int batch, const svo_ssd_sequence *seqs, int n_bound, int win, int search_y,
+                            int *max_win);
+
 #ifdef __cplusplus
 }
 #endif

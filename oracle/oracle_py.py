@@ -360,6 +360,70 @@ def detect_keypoints(img, grid_w, grid_h, level=0):
     return kps[:n], score[:n], typ[:n]
 
 
+# ------------------------------------------------- keyframe path bookkeeping
+def remove_outliers(flags):
+    """indices that remove_outliers keeps"""
+    flags = np.ascontiguousarray(flags, dtype=np.uint32)
+    kept = np.zeros(flags.shape[0] + 1, np.int32)
+    m = lib().svo_o_remove_outliers(_p(flags), flags.shape[0], _p(kept))
+    return kept[:m].copy()
+
+
+def find_bad_keypoints(kps2d, flags, width, height):
+    """indices that find_bad_keypoints keeps"""
+    kps2d = _f32(kps2d).reshape(-1, 2)
+    flags = np.ascontiguousarray(flags, dtype=np.uint32)
+    kept = np.zeros(flags.shape[0] + 1, np.int32)
+    m = lib().svo_o_find_bad_keypoints(_p(kps2d), _p(flags), flags.shape[0], int(width), int(height), _p(kept))
+    return kept[:m].copy()
+
+
+def select_best_keypoints(levels):
+    """levels: per level (kps [n, 2] float32, score [n] float32, type [n] int32). Returns (sel [n0, 2], score,
+    type, level)."""
+    nl = len(levels)
+    ks = [_f32(l[0]).reshape(-1, 2) for l in levels]
+    ss = [_f32(l[1]) for l in levels]
+    ts = [np.ascontiguousarray(l[2], dtype=np.int32) for l in levels]
+    n = np.array([k.shape[0] for k in ks] + [0], np.int32)
+    pp = lambda arrs: (C.c_void_p * max(nl, 1))(*[a.ctypes.data for a in arrs])
+    n0 = int(n[0]) if nl else 0
+    sel, sc = np.zeros((n0 + 1, 2), np.float32), np.zeros(n0 + 1, np.float32)
+    ty, lv = np.zeros(n0 + 1, np.int32), np.zeros(n0 + 1, np.int32)
+    lib().svo_o_select_best_keypoints(nl, pp(ks), pp(ss), pp(ts), _p(n), _p(sel), _p(sc), _p(ty), _p(lv))
+    return sel[:n0], sc[:n0], ty[:n0], lv[:n0]
+
+
+def merge_keypoints(old_kps, cand, image_width, image_height, grid_height, grid_width):
+    """merge_keypoints with ITS argument names; the candidates appended, in order"""
+    old_kps = _f32(old_kps).reshape(-1, 2)
+    cand = _f32(cand).reshape(-1, 2)
+    picked = np.zeros(cand.shape[0] + 1, np.int32)
+    m = lib().svo_o_merge_keypoints(_p(old_kps), old_kps.shape[0], _p(cand), cand.shape[0], int(image_width),
+                                    int(image_height), int(grid_height), int(grid_width), _p(picked))
+    return picked[:m].copy()
+
+
+def depth_init(cam, pose, kps2d, disparity, first, keyframe_id, lcg):
+    """keypoints [first, n): (kps3d [n, 3], info [n], lcg afterwards); entries below `first` are zero"""
+    kps2d = _f32(kps2d).reshape(-1, 2)
+    disparity = _f32(disparity)
+    pose = _f32(pose)
+    n = kps2d.shape[0]
+    k3 = np.zeros((n + 1, 3), np.float32)
+    info = np.zeros(n + 1, KP_INFO_DTYPE)
+    st = C.c_uint32(int(lcg))
+    lib().svo_o_depth_init(C.byref(cam), _p(pose), _p(kps2d), _p(disparity), int(first), n, int(keyframe_id),
+                           C.byref(st), _p(k3), _p(info))
+    return k3[:n], info[:n], st.value
+
+
+def backup_rule(flags):
+    flags = np.ascontiguousarray(flags, dtype=np.uint32).copy()
+    cleared = lib().svo_o_backup_rule(_p(flags), flags.shape[0])
+    return flags, cleared
+
+
 # ------------------------------------------------------------------- tracker
 class Slam:
     """Oracle restatement of StereoSlam (src/include/stereo_slam.hpp:27-79)."""

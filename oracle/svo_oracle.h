@@ -175,6 +175,31 @@ int  svo_o_detect_keypoints(const uint8_t *img, int w, int h, int stride,
                             int grid_w, int grid_h, int level,
                             svo_kp2d *kps, float *score, int32_t *type, int cap);
 
+
+/* the keyframe path's bookkeeping on plain arrays, exposed for unit parity (tracker.c calls every one itself) */
+/* remove_outliers, src/lib/stereo_slam.cpp:43-56, and find_bad_keypoints, src/lib/depth_calculator.cpp:67-86, on
+ * the SVO_IGNORE_* bits: kept[0..return) are the indices that stay, ascending */
+int  svo_o_remove_outliers(const uint32_t *flags, int n, int32_t *kept);
+int  svo_o_find_bad_keypoints(const svo_kp2d *kps2d, const uint32_t *flags, int n, int width, int height,
+                              int32_t *kept);
+/* select_best_keypoints, src/lib/depth_calculator.cpp:37-65: level i holds n[i] candidates; n[0] are selected
+ * (entry j of level i >= 1 takes part while j < n[i]) */
+void svo_o_select_best_keypoints(int n_levels, const svo_kp2d *const *kps, const float *const *score,
+                                 const int32_t *const *type, const int32_t *n, svo_kp2d *sel, float *sel_score,
+                                 int32_t *sel_type, int32_t *sel_level);
+/* merge_keypoints, src/lib/depth_calculator.cpp:88-130, unbounded, with ITS argument names (calculate_depth passes
+ * camera grid_width as grid_height and the reverse): picked[0..return) are the candidates appended, in order;
+ * picked holds n_cand entries */
+int  svo_o_merge_keypoints(const svo_kp2d *old_kps, int n_old, const svo_kp2d *cand, int n_cand, int image_width,
+                           int image_height, int grid_height, int grid_width, int32_t *picked);
+/* the per-point initialisation of calculate_depth, src/lib/depth_calculator.cpp:241-289, for keypoints [first, n):
+ * kps3d and info of those are written (score, level, type stay); *lcg is the colour generator's state */
+void svo_o_depth_init(const svo_camera_settings *cam, const float pose[6], const svo_kp2d *kps2d,
+                      const float *disparity, int first, int n, int keyframe_id, uint32_t *lcg, svo_kp3d *kps3d,
+                      svo_kp_info *info);
+/* the backup rule of src/lib/stereo_slam.cpp:237-245 on the SVO_IGNORE_TEMPORARY bit; returns 1 if it cleared */
+int  svo_o_backup_rule(uint32_t *flags, int n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -61,14 +61,6 @@ static void kps_free(kps_t *k)
     memset(k, 0, sizeof(*k));
 }
 
-static void kps_erase(kps_t *k, int i)
-{
-    memmove(k->kps2d + i, k->kps2d + i + 1, sizeof(svo_kp2d) * (size_t)(k->n - i - 1));
-    memmove(k->kps3d + i, k->kps3d + i + 1, sizeof(svo_kp3d) * (size_t)(k->n - i - 1));
-    memmove(k->info + i, k->info + i + 1, sizeof(svo_kp_info) * (size_t)(k->n - i - 1));
-    k->n--;
-}
-
 static uint32_t info_flags(const svo_kp_info *f)
 {
     return (f->ignore_during_refinement ? SVO_IGNORE_DURING_REFINEMENT : 0) |
@@ -421,25 +413,164 @@ int svo_o_detect_keypoints(const uint8_t *img, int w, int h, int stride, int gri
     return n;
 }
 
-/* find_bad_keypoints — src/lib/depth_calculator.cpp:67-86 */
+/* remove_outliers — src/lib/stereo_slam.cpp:43-56: the indices that stay, in order */
+int svo_o_remove_outliers(const uint32_t *flags, int n, int32_t *kept)
+{
+    int m = 0;
+    for (int i = 0; i < n; i++) {
+        if (flags[i] & SVO_IGNORE_COMPLETELY) continue;
+        kept[m++] = i;
+    }
+    return m;
+}
+
+/* find_bad_keypoints — src/lib/depth_calculator.cpp:67-86: the indices that stay, in order */
+int svo_o_find_bad_keypoints(const svo_kp2d *kps2d, const uint32_t *flags, int n, int width, int height,
+                             int32_t *kept)
+{
+    int m = 0;
+    for (int i = 0; i < n; i++) {
+        const svo_kp2d kp = kps2d[i];
+        if (kp.x < 0 || kp.y < 0 || kp.x > width || kp.y > height ||
+            (flags[i] & SVO_IGNORE_COMPLETELY) || (flags[i] & SVO_IGNORE_DURING_REFINEMENT))
+            continue;
+        kept[m++] = i;
+    }
+    return m;
+}
+
+/* the keypoints kept[0..m) of k, moved to the front (kept ascending) */
+static void kps_gather(kps_t *k, const int32_t *kept, int m)
+{
+    for (int q = 0; q < m; q++) {
+        k->kps2d[q] = k->kps2d[kept[q]];
+        k->kps3d[q] = k->kps3d[kept[q]];
+        k->info[q] = k->info[kept[q]];
+    }
+    k->n = m;
+}
+
 static void find_bad_keypoints(frame_t *f)
 {
-    const int width = f->im->left[0].width, height = f->im->left[0].height;
-    for (int i = 0; i < f->kps.n; i++) {
-        const svo_kp2d kp = f->kps.kps2d[i];
-        if (kp.x < 0 || kp.y < 0 || kp.x > width || kp.y > height ||
-            f->kps.info[i].ignore_completely || f->kps.info[i].ignore_during_refinement) {
-            kps_erase(&f->kps, i);
-            i--;
+    const int width = f->im->left[0].width, height = f->im->left[0].height, n = f->kps.n;
+    uint32_t *flags = (uint32_t *)malloc(sizeof(uint32_t) * (size_t)(n + 1));
+    int32_t *kept = (int32_t *)malloc(sizeof(int32_t) * (size_t)(n + 1));
+    for (int i = 0; i < n; i++) flags[i] = info_flags(&f->kps.info[i]);
+    kps_gather(&f->kps, kept, svo_o_find_bad_keypoints(f->kps.kps2d, flags, n, width, height, kept));
+    free(flags); free(kept);
+}
+
+/* select_best_keypoints — src/lib/depth_calculator.cpp:37-65 (index j is used on every level as is) */
+void svo_o_select_best_keypoints(int n_levels, const svo_kp2d *const *kps, const float *const *score,
+                                 const int32_t *const *type, const int32_t *n, svo_kp2d *sel, float *sel_score,
+                                 int32_t *sel_type, int32_t *sel_level)
+{
+    const int nsel = n_levels > 0 ? n[0] : 0;
+    for (int j = 0; j < nsel; j++) { sel[j] = kps[0][j]; sel_score[j] = score[0][j]; sel_type[j] = type[0][j]; sel_level[j] = 0; }
+    for (int i = 1; i < n_levels; i++)
+        for (int j = 0; j < nsel; j++) {
+            if (j >= n[i]) continue; /* the reference would read out of bounds here */
+            if (sel_type[j] == SVO_KP_FAST && type[i][j] == SVO_KP_EDGELET) continue;
+            if (sel_type[j] == type[i][j] && sel_score[j] > score[i][j]) continue;
+            sel[j] = kps[i][j];
+            sel[j].x *= (1 << i);
+            sel[j].y *= (1 << i);
+            sel_score[j] = score[i][j]; sel_type[j] = type[i][j]; sel_level[j] = i;
+        }
+}
+
+/* merge_keypoints — src/lib/depth_calculator.cpp:88-130 (the caller swaps the grid arguments, :179-180): the
+ * candidates appended to the list, in order, as indices; the list grows inside the loop as the reference's does */
+int svo_o_merge_keypoints(const svo_kp2d *old_kps, int n_old, const svo_kp2d *cand, int n_cand, int image_width,
+                          int image_height, int grid_height, int grid_width, int32_t *picked)
+{
+    svo_kp2d *list = (svo_kp2d *)malloc(sizeof(svo_kp2d) * (size_t)(n_old + n_cand + 1));
+    int n = n_old;
+    memcpy(list, old_kps, sizeof(svo_kp2d) * (size_t)n_old);
+    for (int x = 0; x < image_width; x += grid_width) {
+        const int left = x, right = left + grid_width;
+        for (int y = 0; y < image_height; y += grid_height) {
+            const int top = y, bottom = y + grid_height;
+            int match = 0;
+            for (int i = 0; i < n; i++) {
+                const svo_kp2d kp = list[i];
+                if (kp.x > left && kp.x < right && kp.y > top && kp.y < bottom) { match = 1; break; }
+            }
+            if (!match)
+                for (int i = 0; i < n_cand; i++) {
+                    const svo_kp2d kp = cand[i];
+                    if (kp.x > left && kp.x < right && kp.y > top && kp.y < bottom) {
+                        picked[n - n_old] = i;       /* (strictly inside one cell only: at most once each) */
+                        list[n++] = kp;
+                    }
+                }
         }
     }
+    free(list);
+    return n - n_old;
+}
+
+/* the per-point initialisation of DepthCalculator::calculate_depth — src/lib/depth_calculator.cpp:241-289, for
+ * keypoints [first, n); rand() is the oracle's LCG (*lcg is advanced once per point) */
+void svo_o_depth_init(const svo_camera_settings *cam, const float pose[6], const svo_kp2d *kps2d,
+                      const float *disparity, int first, int n, int keyframe_id, uint32_t *lcg, svo_kp3d *kps3d,
+                      svo_kp_info *info)
+{
+    const float fx = cam->fx, fy = cam->fy, cx = cam->cx, cy = cam->cy, baseline = cam->baseline;
+    float rot[9], inv_rot[9];
+    svo_o_pose_matrices(pose, rot, inv_rot);
+    for (int i = first; i < n; i++) {
+        const svo_kp2d kp = kps2d[i];
+        const float d = disparity[i];
+        const float _z = baseline / (0.5f < d ? d : 0.5f);   /* std::max<float>(0.5, d): a NaN d gives 0.5 */
+        const float _x = (kp.x - cx) / fx * _z;
+        const float _y = (kp.y - cy) / fy * _z;
+        const float loc[3] = { _x, _y, _z };
+        float g[3];
+        for (int r = 0; r < 3; r++) {
+            float sum = 0;
+            for (int k = 0; k < 3; k++) sum += rot[r * 3 + k] * loc[k];
+            g[r] = sum;
+        }
+        kps3d[i].x = g[0] + pose[0];
+        kps3d[i].y = g[1] + pose[1];
+        kps3d[i].z = g[2] + pose[2];
+
+        *lcg = *lcg * 1664525u + 1013904223u;
+        const uint32_t color = *lcg >> 8;
+        svo_kp_info *in = &info[i];
+        in->color[0] = (color >> 0) & 0xFF;
+        in->color[1] = (color >> 8) & 0xFF;
+        in->color[2] = (color >> 16) & 0xFF;
+        in->keyframe_id = (int32_t)keyframe_id;
+        in->keypoint_index = i;
+        in->ignore_completely = 0;
+        in->ignore_temporary = 1;
+        in->ignore_during_refinement = 0;
+        in->inlier_count = 0;
+        in->outlier_count = 0;
+        const float deviation = (float)(0.5 / (double)(baseline / fx));
+        in->kf_variance = deviation * deviation;
+        in->kf_inv_depth = 1 / _z;
+    }
+}
+
+/* the backup rule of StereoSlam::new_image — src/lib/stereo_slam.cpp:237-245: with fewer than n / 4 keypoints that
+ * are not temporary, every keypoint loses the bit; returns 1 if it did */
+int svo_o_backup_rule(uint32_t *flags, int n)
+{
+    int cnt = 0;
+    for (int i = 0; i < n; i++)
+        if (!(flags[i] & SVO_IGNORE_TEMPORARY)) cnt++;
+    if (!((size_t)cnt < (size_t)n / 4)) return 0;
+    for (int i = 0; i < n; i++) flags[i] &= ~(uint32_t)SVO_IGNORE_TEMPORARY;
+    return 1;
 }
 
 /* DepthCalculator::calculate_depth — src/lib/depth_calculator.cpp:132-392 */
 static void calculate_depth(svo_o_slam *s, frame_t *f)
 {
     const svo_camera_settings *cam = &s->cam;
-    const float fx = cam->fx, fy = cam->fy, cx = cam->cx, cy = cam->cy, baseline = cam->baseline;
 
     find_bad_keypoints(f);
 
@@ -466,92 +597,35 @@ static void calculate_depth(svo_o_slam *s, frame_t *f)
     float *ss = (float *)malloc(sizeof(float) * (size_t)(nsel + 1));
     int32_t *st = (int32_t *)malloc(sizeof(int32_t) * (size_t)(nsel + 1));
     int32_t *sl = (int32_t *)malloc(sizeof(int32_t) * (size_t)(nsel + 1));
-    for (int j = 0; j < nsel; j++) { sk[j] = pk[0][j]; ss[j] = ps[0][j]; st[j] = pt[0][j]; sl[j] = 0; }
-    for (int i = 1; i < nlev; i++)
-        for (int j = 0; j < nsel; j++) {
-            if (j >= pn[i]) continue; /* the reference would read out of bounds here */
-            if (st[j] == SVO_KP_FAST && pt[i][j] == SVO_KP_EDGELET) continue;
-            if (st[j] == pt[i][j] && ss[j] > ps[i][j]) continue;
-            sk[j] = pk[i][j];
-            sk[j].x *= (1 << i);
-            sk[j].y *= (1 << i);
-            ss[j] = ps[i][j]; st[j] = pt[i][j]; sl[j] = i;
-        }
+    svo_o_select_best_keypoints(nlev, (const svo_kp2d *const *)pk, (const float *const *)ps,
+                                (const int32_t *const *)pt, pn, sk, ss, st, sl);
 
     const int old_count = f->kps.n;
 
     /* merge_keypoints — :88-130, called with grid_width/grid_height swapped (:179-180) */
     {
-        const int m_grid_height = cam->grid_width, m_grid_width = cam->grid_height;
-        const int image_width = f->im->left[0].width, image_height = f->im->left[0].height;
-        for (int x = 0; x < image_width; x += m_grid_width) {
-            const int left = x, right = left + m_grid_width;
-            for (int y = 0; y < image_height; y += m_grid_height) {
-                const int top = y, bottom = y + m_grid_height;
-                int match = 0;
-                for (int i = 0; i < f->kps.n; i++) {
-                    const svo_kp2d kp = f->kps.kps2d[i];
-                    if (kp.x > left && kp.x < right && kp.y > top && kp.y < bottom) { match = 1; break; }
-                }
-                if (!match)
-                    for (int i = 0; i < nsel; i++) {
-                        const svo_kp2d kp = sk[i];
-                        if (kp.x > left && kp.x < right && kp.y > top && kp.y < bottom) {
-                            kps_reserve(&f->kps, f->kps.n + 1);
-                            const int q = f->kps.n++;
-                            f->kps.kps2d[q] = kp;
-                            memset(&f->kps.info[q], 0, sizeof(svo_kp_info));
-                            f->kps.info[q].score = ss[i];
-                            f->kps.info[q].type = st[i];
-                            f->kps.info[q].level = sl[i];
-                            f->kps.kps3d[q].x = f->kps.kps3d[q].y = f->kps.kps3d[q].z = 0;
-                        }
-                    }
-            }
+        int32_t *picked = (int32_t *)malloc(sizeof(int32_t) * (size_t)(nsel + 1));
+        const int n_add = svo_o_merge_keypoints(f->kps.kps2d, f->kps.n, sk, nsel, f->im->left[0].width,
+                                                f->im->left[0].height, cam->grid_width, cam->grid_height, picked);
+        kps_reserve(&f->kps, f->kps.n + n_add);
+        for (int k = 0; k < n_add; k++) {
+            const int i = picked[k], q = f->kps.n++;
+            f->kps.kps2d[q] = sk[i];
+            memset(&f->kps.info[q], 0, sizeof(svo_kp_info));
+            f->kps.info[q].score = ss[i];
+            f->kps.info[q].type = st[i];
+            f->kps.info[q].level = sl[i];
+            f->kps.kps3d[q].x = f->kps.kps3d[q].y = f->kps.kps3d[q].z = 0;
         }
+        free(picked);
     }
-
-    float rot[9], inv_rot[9];
-    svo_o_pose_matrices(f->pose, rot, inv_rot);
 
     const int n_new = f->kps.n - old_count;
-    float *disp = (float *)malloc(sizeof(float) * (size_t)(n_new + 1));
+    float *disp = (float *)malloc(sizeof(float) * (size_t)(f->kps.n + 1));
     svo_o_ssd_disparity(&f->im->left[0], &f->im->right0, f->kps.kps2d + old_count, n_new,
-                        cam->window_size_depth_calculator, cam->search_x, cam->search_y, 0, disp);
-    for (int i = old_count; i < f->kps.n; i++) {
-        const svo_kp2d kp = f->kps.kps2d[i];
-        const float disparity = disp[i - old_count];
-        const float _z = baseline / (0.5f > disparity ? 0.5f : disparity);
-        const float _x = (kp.x - cx) / fx * _z;
-        const float _y = (kp.y - cy) / fy * _z;
-        const float loc[3] = { _x, _y, _z };
-        float g[3];
-        for (int r = 0; r < 3; r++) {
-            float sum = 0;
-            for (int k = 0; k < 3; k++) sum += rot[r * 3 + k] * loc[k];
-            g[r] = sum;
-        }
-        f->kps.kps3d[i].x = g[0] + f->pose[0];
-        f->kps.kps3d[i].y = g[1] + f->pose[1];
-        f->kps.kps3d[i].z = g[2] + f->pose[2];
-
-        s->color_lcg = s->color_lcg * 1664525u + 1013904223u;
-        const uint32_t color = s->color_lcg >> 8;
-        svo_kp_info *in = &f->kps.info[i];
-        in->color[0] = (color >> 0) & 0xFF;
-        in->color[1] = (color >> 8) & 0xFF;
-        in->color[2] = (color >> 16) & 0xFF;
-        in->keyframe_id = (int32_t)s->keyframe_count;
-        in->keypoint_index = i;
-        in->ignore_completely = 0;
-        in->ignore_temporary = 1;
-        in->ignore_during_refinement = 0;
-        in->inlier_count = 0;
-        in->outlier_count = 0;
-        const float deviation = (float)(0.5 / (double)(baseline / fx));
-        in->kf_variance = deviation * deviation;
-        in->kf_inv_depth = 1 / _z;
-    }
+                        cam->window_size_depth_calculator, cam->search_x, cam->search_y, 0, disp + old_count);
+    svo_o_depth_init(cam, f->pose, f->kps.kps2d, disp, old_count, f->kps.n, (int)s->keyframe_count, &s->color_lcg,
+                     f->kps.kps3d, f->kps.info);
     free(disp);
     for (int l = 0; l < nlev; l++) { free(pk[l]); free(ps[l]); free(pt[l]); }
     free(sk); free(ss); free(st); free(sl);
@@ -656,15 +730,12 @@ int svo_o_slam_new_image(svo_o_slam *s, const uint8_t *left, const uint8_t *righ
 
         /* remove_outliers — :43-56 */
         {
-            int m = 0;
-            for (int i = 0; i < prev->kps.n; i++) {
-                if (prev->kps.info[i].ignore_completely) continue;
-                prev->kps.kps2d[m] = prev->kps.kps2d[i];
-                prev->kps.kps3d[m] = prev->kps.kps3d[i];
-                prev->kps.info[m] = prev->kps.info[i];
-                m++;
-            }
-            prev->kps.n = m;
+            const int n0 = prev->kps.n;
+            uint32_t *fl0 = (uint32_t *)malloc(sizeof(uint32_t) * (size_t)(n0 + 1));
+            int32_t *kept = (int32_t *)malloc(sizeof(int32_t) * (size_t)(n0 + 1));
+            for (int i = 0; i < n0; i++) fl0[i] = info_flags(&prev->kps.info[i]);
+            kps_gather(&prev->kps, kept, svo_o_remove_outliers(fl0, n0, kept));
+            free(fl0); free(kept);
         }
         const int n = prev->kps.n;
         stx->n_tracked = n;
@@ -781,11 +852,11 @@ int svo_o_slam_new_image(svo_o_slam *s, const uint8_t *left, const uint8_t *righ
             create_keyframe(s, f);
             stx->t_keyframe = now_s() - t0;
             made_keyframe = 1;
-            int cnt = 0;
-            for (int i = 0; i < f->kps.n; i++)
-                if (!f->kps.info[i].ignore_temporary) cnt++;
-            if ((size_t)cnt < (size_t)f->kps.n / 4)
+            uint32_t *fb = (uint32_t *)malloc(sizeof(uint32_t) * (size_t)(f->kps.n + 1));
+            for (int i = 0; i < f->kps.n; i++) fb[i] = info_flags(&f->kps.info[i]);
+            if (svo_o_backup_rule(fb, f->kps.n))
                 for (int i = 0; i < f->kps.n; i++) f->kps.info[i].ignore_temporary = 0;
+            free(fb);
         }
         free(flags); free(tracked); free(refpts); free(gref); free(gcur); free(gidx);
         free(err); free(gerr); free(gstatus); free(disp); free(ref3d); free(kfpose);

@@ -294,9 +294,11 @@ __global__ __launch_bounds__(SSD_THREADS) void ssd_disparity_kernel(const SsdArg
     }
 }
 
+int ssd_pick_max_win(int win, int search_y) { return win <= 31 && 2 * search_y + 1 <= 13 ? 31 : SSD_WIN_ALL; }
+
 void launch_ssd(const SsdArgs* d_args, int batch, int max_n, int win, int search_y, hipStream_t stream) {
     if (max_n <= 0) return;
-    if (win <= 31 && 2 * search_y + 1 <= 13)
+    if (ssd_pick_max_win(win, search_y) == 31)
         hipLaunchKernelGGL((ssd_disparity_kernel<31, 13>), dim3(max_n, batch), dim3(SSD_THREADS), 0, stream, d_args);
     else
         hipLaunchKernelGGL((ssd_disparity_kernel<SSD_WIN_ALL, SSD_MH_ALL>), dim3(max_n, batch), dim3(SSD_THREADS), 0, stream, d_args);

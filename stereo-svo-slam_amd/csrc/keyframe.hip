@@ -127,10 +127,12 @@ __global__ __launch_bounds__(1024) void compact_kernel(const CompactArgs* __rest
 
 // Small sets run with 256 threads: a 16-wave workgroup only starts on a CU that has drained, and
 // next to the other sequence groups' window kernels it waited ~0.4 ms for one (HIP events).
-void launch_compact(const CompactArgs* d_args, int batch, int cap, hipStream_t stream) {
+int compact_pick_threads(int cap) {
     static const int env_threads = getenv("SVO_COMPACT_THREADS") ? atoi(getenv("SVO_COMPACT_THREADS")) : 0;   // (experiments)
-    const int threads = env_threads >= 64 && env_threads <= 1024 && env_threads % 64 == 0 ? env_threads : (cap <= 1024 ? 256 : 1024);
-    hipLaunchKernelGGL(compact_kernel, dim3(batch), dim3(threads), 0, stream, d_args);
+    return env_threads >= 64 && env_threads <= 1024 && env_threads % 64 == 0 ? env_threads : (cap <= 1024 ? 256 : 1024);
+}
+void launch_compact(const CompactArgs* d_args, int batch, int cap, hipStream_t stream) {
+    hipLaunchKernelGGL(compact_kernel, dim3(batch), dim3(compact_pick_threads(cap)), 0, stream, d_args);
 }
 
 // --------------------------------------------------------------- detection
@@ -442,10 +444,12 @@ __global__ __launch_bounds__(1024) void kf_select_merge_kernel(const MergeArgs* 
     }
 }
 
-void launch_select_merge(const MergeArgs* d_args, int batch, int max_cells, hipStream_t stream) {
+int select_merge_pick_threads(int max_cells) {
     static const int env_threads = getenv("SVO_MERGE_THREADS") ? atoi(getenv("SVO_MERGE_THREADS")) : 0;   // (experiments)
-    const int threads = env_threads >= 64 && env_threads <= 1024 && env_threads % 64 == 0 ? env_threads : (max_cells <= 512 ? 256 : 1024);
-    hipLaunchKernelGGL(kf_select_merge_kernel, dim3(batch), dim3(threads), 0, stream, d_args);
+    return env_threads >= 64 && env_threads <= 1024 && env_threads % 64 == 0 ? env_threads : (max_cells <= 512 ? 256 : 1024);
+}
+void launch_select_merge(const MergeArgs* d_args, int batch, int max_cells, hipStream_t stream) {
+    hipLaunchKernelGGL(kf_select_merge_kernel, dim3(batch), dim3(select_merge_pick_threads(max_cells)), 0, stream, d_args);
 }
 
 // ------------------------------------------------------------------- init

@@ -1329,3 +1329,237 @@ extern "C" int svo_klt_cache_layout(int win, int64_t* record_bytes, int64_t* hea
     if (levels) *levels = SVO_LK_LEVELS;
     return SVO_OK;
 }
+
+// svo_compact_batch, svo_keyframe_merge_batch, svo_keyframe_init_batch, svo_ssd_disparity_batch: the four bookkeeping
+// launches of the keyframe path with their argument blocks filled the way pack_compact, pack_keyframe_args and
+// pack_ssd (svo_group_step.hip) fill them, through the tracker's launchers, over the caller's memory. What a kernel
+// indexes with is read back and checked first (a diagnostic may wait): a count beyond the capacity would make a
+// workgroup read or write a neighbour's memory.
+static_assert(sizeof(svo_kps_planes) == 104 && sizeof(svo_compact_sequence) == 264 && sizeof(svo_merge_sequence) == 272 &&
+              sizeof(svo_kf_init_sequence) == 400 && sizeof(svo_ssd_sequence) == 112, "the layouts the Python binding restates");
+
+static KpsDev kps_dev(const svo_kps_planes& p) {
+    KpsDev k;
+    k.kps2d = p.kps2d; k.kps3d = p.kps3d; k.flags = p.flags; k.kf_id = p.kf_id; k.kp_index = p.kp_index;
+    k.outl = p.outlier_count; k.inl = p.inlier_count; k.kfx = p.kf_inv_depth; k.kfP = p.kf_variance;
+    k.score = p.score; k.level_type = p.level_type; k.color = p.color; k.n = p.n;
+    return k;
+}
+static bool planes_missing(const svo_kps_planes& p, bool need_n) {
+    return !p.kps2d || !p.kps3d || !p.flags || !p.kf_id || !p.kp_index || !p.outlier_count || !p.inlier_count ||
+           !p.kf_inv_depth || !p.kf_variance || !p.score || !p.level_type || !p.color || (need_n && !p.n);
+}
+static int read_i32(const int32_t* dev, int count, int32_t* out) {
+    HIP_TRY(hipMemcpy(out, dev, sizeof(int32_t) * (size_t)count, hipMemcpyDeviceToHost));
+    return SVO_OK;
+}
+// launch done: the first error of the launch or the wait
+static int finish_launch(svo_handle* h) {
+    const hipError_t launched = hipGetLastError();
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(launched);
+    return SVO_OK;
+}
+
+extern "C" int svo_keyframe_launch_info(int cap, int max_cells, int tmpl_cap, int* compact_threads, int* merge_threads,
+                                        int64_t* tmpl_valid_bytes) {
+    if (cap < 1 || max_cells < 1 || tmpl_cap < 0)
+        return svo_set_error(SVO_ERR_INVALID, "svo_keyframe_launch_info: need cap >= 1, max_cells >= 1, tmpl_cap >= 0");
+    if (compact_threads) *compact_threads = compact_pick_threads(cap);
+    if (merge_threads) *merge_threads = select_merge_pick_threads(max_cells);
+    if (tmpl_valid_bytes) *tmpl_valid_bytes = (int64_t)kf_tmpl_valid_bytes(tmpl_cap);
+    return SVO_OK;
+}
+
+extern "C" int svo_compact_batch(svo_handle* h, int batch, const svo_compact_sequence* seqs, int cap, int* threads) {
+    CHECK_H(h);
+    if (batch < 1 || batch > 4096 || !seqs || cap < 1)
+        return svo_set_error(SVO_ERR_INVALID, "svo_compact_batch: need 1 <= batch <= 4096, seqs and cap >= 1");
+    HIP_TRY(hipStreamSynchronize(h->stream));      // (the caller's counts are read back below)
+    std::vector<CompactArgs> blocks((size_t)batch);
+    for (int b = 0; b < batch; b++) {
+        const svo_compact_sequence& s = seqs[b];
+        if (planes_missing(s.src, true) || planes_missing(s.dst, true) || (s.mode != 0 && s.mode != 1) ||
+            (s.start != 0 && s.start != 1) || s.zero_count < 0 || s.zero_res_count < 0 || (s.zero_count > 0 && !s.zero) ||
+            (s.zero_res_count > 0 && !s.zero_res))
+            return svo_set_error(SVO_ERR_INVALID, "svo_compact_batch: sequence %d: bad arguments", b);
+        if (s.min_kf && s.mode != 0)
+            return svo_set_error(SVO_ERR_INVALID, "svo_compact_batch: sequence %d: min_kf is defined for mode 0 only", b);
+        if (!s.start) {
+            int32_t n = 0;
+            if (const int rc = read_i32(s.src.n, 1, &n)) return rc;
+            if (n < 0 || n > cap)
+                return svo_set_error(SVO_ERR_INVALID, "svo_compact_batch: sequence %d: n = %d is outside 0..cap = %d", b, n, cap);
+        }
+        CompactArgs& ca = blocks[(size_t)b];
+        memset(&ca, 0, sizeof(ca));
+        ca.src = kps_dev(s.src); ca.dst = kps_dev(s.dst); ca.mode = s.mode;
+        ca.width = s.width; ca.height = s.height;
+        ca.enable = s.enable;
+        ca.zero = s.zero; ca.zero_count = s.zero_count;
+        ca.start = s.start;
+        ca.zero_res = s.zero_res; ca.zero_res_count = s.zero_res_count;
+        ca.min_kf = s.min_kf;
+    }
+    CompactArgs* d;
+    const int rc = stage_blocks(h, blocks, &d);
+    if (rc) return rc;
+    if (threads) *threads = compact_pick_threads(cap);
+    launch_compact(d, batch, cap, h->stream);
+    return finish_launch(h);
+}
+
+extern "C" int svo_keyframe_merge_batch(svo_handle* h, int batch, const svo_merge_sequence* seqs, int n_levels,
+                                        int max_cells, int cap, int* threads) {
+    CHECK_H(h);
+    if (batch < 1 || batch > 4096 || !seqs || n_levels < 1 || n_levels > SVO_MAX_PYRAMID_LEVELS || max_cells < 1 || cap < 1)
+        return svo_set_error(SVO_ERR_INVALID, "svo_keyframe_merge_batch: need 1 <= batch <= 4096, seqs, n_levels 1..%d, "
+                             "max_cells >= 1 and cap >= 1", SVO_MAX_PYRAMID_LEVELS);
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    std::vector<MergeArgs> blocks((size_t)batch);
+    for (int b = 0; b < batch; b++) {
+        const svo_merge_sequence& s = seqs[b];
+        if (planes_missing(s.kps, true) || !s.det || !s.n_det || !s.sel || !s.sel_level || !s.sel_cell || !s.occupied ||
+            !s.old_count || !s.overflow || s.width < 1 || s.height < 1 || s.cam.grid_width < 1 || s.cam.grid_height < 1)
+            return svo_set_error(SVO_ERR_INVALID, "svo_keyframe_merge_batch: sequence %d: bad arguments", b);
+        // (the kernel's grid: cells of grid_height x grid_width, the swap of depth_calculator.cpp:179-180)
+        const int64_t cells = ((int64_t)(s.width + s.cam.grid_height - 1) / s.cam.grid_height) *
+                              ((int64_t)(s.height + s.cam.grid_width - 1) / s.cam.grid_width);
+        if (cells > s.occupied_count)
+            return svo_set_error(SVO_ERR_INVALID, "svo_keyframe_merge_batch: sequence %d: %lld merge cells, occupied holds %d", b,
+                                 (long long)cells, s.occupied_count);
+        int32_t nd[SVO_MAX_PYRAMID_LEVELS], n = 0;
+        if (const int rc = read_i32(s.n_det, n_levels, nd)) return rc;
+        if (const int rc = read_i32(s.kps.n, 1, &n)) return rc;
+        for (int l = 0; l < n_levels; l++)
+            if (nd[l] < 0 || nd[l] > max_cells)
+                return svo_set_error(SVO_ERR_INVALID, "svo_keyframe_merge_batch: sequence %d: n_det[%d] = %d is outside "
+                                     "0..max_cells = %d", b, l, nd[l], max_cells);
+        if (n < 0 || n > cap)
+            return svo_set_error(SVO_ERR_INVALID, "svo_keyframe_merge_batch: sequence %d: n = %d is outside 0..cap = %d", b, n, cap);
+        MergeArgs& ma = blocks[(size_t)b];
+        memset(&ma, 0, sizeof(ma));
+        ma.cam = s.cam; ma.width = s.width; ma.height = s.height;
+        ma.det = reinterpret_cast<const DetCell*>(s.det); ma.n_det = s.n_det; ma.n_levels = n_levels; ma.max_cells = max_cells;
+        ma.kps = kps_dev(s.kps); ma.cap = cap;
+        ma.sel = reinterpret_cast<DetCell*>(s.sel); ma.sel_level = s.sel_level; ma.sel_cell = s.sel_cell; ma.occupied = s.occupied;
+        ma.old_count = s.old_count; ma.overflow = s.overflow;
+        ma.enable = s.enable;
+    }
+    MergeArgs* d;
+    const int rc = stage_blocks(h, blocks, &d);
+    if (rc) return rc;
+    if (threads) *threads = select_merge_pick_threads(max_cells);
+    launch_select_merge(d, batch, max_cells, h->stream);
+    return finish_launch(h);
+}
+
+extern "C" int svo_keyframe_record_layout(int64_t* record_bytes, int64_t* n_offset, int64_t* pose_offset, int64_t* tmpl_offset,
+                                          int64_t* tmpl_valid_offset, int64_t* tmpl_cap_offset, int64_t* tmpl_win_offset,
+                                          int64_t plane_offsets[12]) {
+    if (record_bytes) *record_bytes = (int64_t)sizeof(KfDev);
+    if (n_offset) *n_offset = (int64_t)offsetof(KfDev, n);
+    if (pose_offset) *pose_offset = (int64_t)offsetof(KfDev, pose);
+    if (tmpl_offset) *tmpl_offset = (int64_t)offsetof(KfDev, tmpl);
+    if (tmpl_valid_offset) *tmpl_valid_offset = (int64_t)offsetof(KfDev, tmpl_valid);
+    if (tmpl_cap_offset) *tmpl_cap_offset = (int64_t)offsetof(KfDev, tmpl_cap);
+    if (tmpl_win_offset) *tmpl_win_offset = (int64_t)offsetof(KfDev, tmpl_win);
+    if (plane_offsets) {       // in the order of svo_kps_planes
+        const size_t o[12] = {offsetof(KfDev, kps2d), offsetof(KfDev, kps3d), offsetof(KfDev, flags), offsetof(KfDev, kf_id),
+                              offsetof(KfDev, kp_index), offsetof(KfDev, outlier_count), offsetof(KfDev, inlier_count),
+                              offsetof(KfDev, kfx), offsetof(KfDev, kfP), offsetof(KfDev, score), offsetof(KfDev, level_type),
+                              offsetof(KfDev, color)};
+        for (int i = 0; i < 12; i++) plane_offsets[i] = (int64_t)o[i];
+    }
+    return SVO_OK;
+}
+
+extern "C" int svo_keyframe_init_batch(svo_handle* h, int batch, const svo_kf_init_sequence* seqs, int cap) {
+    CHECK_H(h);
+    if (batch < 1 || batch > 4096 || !seqs || cap < 1)
+        return svo_set_error(SVO_ERR_INVALID, "svo_keyframe_init_batch: need 1 <= batch <= 4096, seqs and cap >= 1");
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    std::vector<KfInitArgs> blocks((size_t)batch);
+    for (int b = 0; b < batch; b++) {
+        const svo_kf_init_sequence& s = seqs[b];
+        if (planes_missing(s.kps, true) || planes_missing(s.record, false) || !s.old_count || !s.disparity || !s.kfs ||
+            !s.color_lcg || !s.n_out || (!s.first_frame && !s.frame_pose) || (s.first_frame != 0 && s.first_frame != 1) ||
+            s.new_kf_id < 0 || s.evict_id < -1)
+            return svo_set_error(SVO_ERR_INVALID, "svo_keyframe_init_batch: sequence %d: bad arguments", b);
+        if (s.kf_mask < 0 || s.kf_mask > (1 << 20) || ((s.kf_mask + 1) & s.kf_mask) != 0 ||
+            (int64_t)(s.kf_mask + 1) * (int64_t)sizeof(KfDev) > s.kfs_bytes || (reinterpret_cast<uintptr_t>(s.kfs) & 7))
+            return svo_set_error(SVO_ERR_INVALID, "svo_keyframe_init_batch: sequence %d: the table needs kf_mask + 1 = a power "
+                                 "of two records of %zu bytes, 8-byte aligned", b, sizeof(KfDev));
+        if (s.tmpl_valid_bytes < 0 || s.tmpl_valid_bytes % 4 != 0 || (s.tmpl_valid_bytes > 0 && !s.tmpl_valid) ||
+            (reinterpret_cast<uintptr_t>(s.tmpl_valid) & 3))
+            return svo_set_error(SVO_ERR_INVALID, "svo_keyframe_init_batch: sequence %d: tmpl_valid must be 4-byte aligned and "
+                                 "tmpl_valid_bytes a multiple of 4", b);
+        int32_t n = 0, old_count = 0;
+        if (const int rc = read_i32(s.kps.n, 1, &n)) return rc;
+        if (const int rc = read_i32(s.old_count, 1, &old_count)) return rc;
+        if (n < 0 || n > cap || old_count < 0 || old_count > n)
+            return svo_set_error(SVO_ERR_INVALID, "svo_keyframe_init_batch: sequence %d: need 0 <= old_count = %d <= n = %d <= "
+                                 "cap = %d", b, old_count, n, cap);
+        KfInitArgs& ia = blocks[(size_t)b];
+        memset(&ia, 0, sizeof(ia));
+        ia.cam = s.cam; ia.kps = kps_dev(s.kps); ia.old_count = s.old_count;
+        ia.disparity = s.disparity; ia.frame_pose = s.frame_pose;
+        ia.first_frame = s.first_frame; ia.new_kf_id = s.new_kf_id; ia.kfs = static_cast<KfDev*>(s.kfs); ia.kf_mask = s.kf_mask;
+        ia.color_lcg = s.color_lcg; ia.n_out = s.n_out;
+        ia.enable = s.enable;
+        KfDev& r = ia.record;          // (as fill_kf_record makes it, without images: no kernel of this entry reads them)
+        r.kps2d = s.record.kps2d; r.kps3d = s.record.kps3d; r.flags = s.record.flags;
+        r.outlier_count = s.record.outlier_count; r.inlier_count = s.record.inlier_count;
+        r.kf_id = s.record.kf_id; r.kp_index = s.record.kp_index; r.score = s.record.score;
+        r.level_type = s.record.level_type; r.color = s.record.color; r.kfx = s.record.kf_inv_depth; r.kfP = s.record.kf_variance;
+        r.tmpl = s.tmpl; r.tmpl_valid = s.tmpl_valid; r.tmpl_cap = s.tmpl_cap; r.tmpl_win = s.tmpl_win;
+        ia.tmpl_valid_bytes = s.tmpl_valid_bytes;
+        ia.evict_id = s.evict_id;
+    }
+    KfInitArgs* d;
+    const int rc = stage_blocks(h, blocks, &d);
+    if (rc) return rc;
+    launch_kf_init(d, batch, h->stream);
+    return finish_launch(h);
+}
+
+extern "C" int svo_ssd_disparity_batch(svo_handle* h, int batch, const svo_ssd_sequence* seqs, int n_bound, int win,
+                                       int search_y, int* max_win) {
+    CHECK_H(h);
+    constexpr int kMaxIndex = 1 << 29;             // first, *first_ptr and n_bound: their sum stays an int
+    if (batch < 1 || batch > 4096 || !seqs || n_bound < 0 || n_bound > kMaxIndex)
+        return svo_set_error(SVO_ERR_INVALID, "svo_ssd_disparity_batch: need 1 <= batch <= 4096, seqs and 0 <= n_bound <= 2^29");
+    if (win < 1 || win > 35 || search_y < 0 || search_y > 8)
+        return svo_set_error(SVO_ERR_INVALID, "svo_ssd_disparity_batch: win<=35, search_y<=8 supported");
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    std::vector<SsdArgs> blocks((size_t)batch);
+    for (int b = 0; b < batch; b++) {
+        const svo_ssd_sequence& s = seqs[b];
+        if (klt_bad_view(s.left) || klt_bad_view(s.right) || !s.n || s.cap < 0 || (s.cap > 0 && (!s.kps2d || !s.disparity)) ||
+            s.first < 0 || s.first > kMaxIndex)
+            return svo_set_error(SVO_ERR_INVALID, "svo_ssd_disparity_batch: sequence %d: bad arguments", b);
+        if (s.win < 1 || s.win > win || s.search_x < 0 || s.search_x > 64 || s.search_y < 0 || s.search_y > search_y)
+            return svo_set_error(SVO_ERR_INVALID, "svo_ssd_disparity_batch: sequence %d: win %d, search_x %d, search_y %d exceed "
+                                 "the launch's %d, 64, %d", b, s.win, s.search_x, s.search_y, win, search_y);
+        int32_t n = 0, first = 0;
+        if (const int rc = read_i32(s.n, 1, &n)) return rc;
+        if (s.first_ptr)
+            if (const int rc = read_i32(s.first_ptr, 1, &first)) return rc;
+        if (n < 0 || n > s.cap || first < 0 || first > kMaxIndex)
+            return svo_set_error(SVO_ERR_INVALID, "svo_ssd_disparity_batch: sequence %d: n = %d is outside 0..cap = %d, or "
+                                 "*first_ptr = %d is outside 0..2^29", b, n, s.cap, first);
+        SsdArgs& sa = blocks[(size_t)b];
+        memset(&sa, 0, sizeof(sa));
+        sa.left = make_view(s.left); sa.right = make_view(s.right);
+        sa.n_ptr = s.n; sa.kps2d = s.kps2d; sa.disparity = s.disparity;
+        sa.win = s.win; sa.search_x = s.search_x; sa.search_y = s.search_y; sa.clamp_half = s.clamp_half;
+        sa.first = s.first; sa.first_ptr = s.first_ptr;
+        sa.enable = s.enable;
+    }
+    SsdArgs* d;
+    const int rc = stage_blocks(h, blocks, &d);
+    if (rc) return rc;
+    if (max_win) *max_win = ssd_pick_max_win(win, search_y);
+    launch_ssd(d, batch, n_bound, win, search_y, h->stream);
+    return finish_launch(h);
+}

@@ -331,7 +331,7 @@ static int alloc_template_cache(svo_group* c) {
     c->tmpl_block_bytes = align_up((size_t)c->tmpl_cap * SVO_LK_LEVELS * klt_template_bytes(c->cam.window_size_opt_flow), 256);
     int K = c->tmpl_block_bytes <= ((size_t)8 << 20) ? 8 : 4;
     if (const char* e = std::getenv("SVO_KLT_CACHE_KF")) K = std::max(0, std::min(std::atoi(e), 64));
-    c->tmpl_valid_bytes = align_up((size_t)c->tmpl_cap * SVO_LK_LEVELS, 256);
+    c->tmpl_valid_bytes = kf_tmpl_valid_bytes(c->tmpl_cap);
     size_t free_b = 0, total_b = 0;
     HIP_TRY(hipMemGetInfo(&free_b, &total_b));
     while (K > 0 && (size_t)B * K * c->tmpl_block_bytes > free_b / 3) K--;

@@ -283,6 +283,7 @@ struct SsdArgs {
 };
 // win / search_y: the largest SsdArgs::win / search_y of the launch (choose the LDS size of the kernel)
 void launch_ssd(const SsdArgs* d_args, int batch, int max_n, int win, int search_y, hipStream_t stream);
+int ssd_pick_max_win(int win, int search_y);       // the largest window of the kernel shape of that launch (31 or 35)
 
 struct FilterArgs {
     svo_camera_settings cam;

@@ -42,6 +42,7 @@ struct CompactArgs {
                        // mask (low word first): bit j set = some kept keypoint comes from keyframe min + j (younger ones: not reported)
 };
 void launch_compact(const CompactArgs* d_args, int batch, int cap, hipStream_t stream);
+int compact_pick_threads(int cap);                 // the workgroup size of that launch
 
 struct DetCell {
     float x, y, score;
@@ -80,6 +81,7 @@ struct MergeArgs {
     const int* enable;
 };
 void launch_select_merge(const MergeArgs* d_args, int batch, int max_cells, hipStream_t stream);
+int select_merge_pick_threads(int max_cells);      // the workgroup size of that launch
 
 constexpr uint32_t SVO_COLOR_LCG_SEED = 12345u;   // state of a sequence's colour generator before its first keypoint
 
@@ -103,6 +105,8 @@ struct KfInitArgs {
     int evict_id;
 };
 void launch_kf_init(const KfInitArgs* d_args, int batch, hipStream_t stream);
+// bytes of "stored" flags of a template cache block of tmpl_cap keypoints (kf_init_kernel clears them as dwords)
+inline size_t kf_tmpl_valid_bytes(int tmpl_cap) { return ((size_t)tmpl_cap * SVO_LK_LEVELS + 255) / 256 * 256; }
 
 // ------------------------------------------------------------ bulk export (export.hip)
 // One tile of a keypoint set on its way into the records of the C ABI: at most EXPORT_TILE keypoints, one

@@ -48,6 +48,8 @@ SYMBOLS = (
     "svo_klt_track_batch", "svo_klt_cache_layout",
     "svo_rectify_inverse", "svo_build_rectify_maps", "svo_ctx_add_rigs_calibrated", "svo_ctx_set_calibration",
     "svo_submit_trim_keyframes", "svo_trim_keyframes", "svo_ctx_set_keyframe_window", "svo_get_keyframe_range",
+    "svo_keyframe_launch_info", "svo_compact_batch", "svo_keyframe_merge_batch", "svo_keyframe_init_batch",
+    "svo_keyframe_record_layout", "svo_ssd_disparity_batch",
 )
 
 # svo_ctx_set_input_format / svo_convert_frames: how the buffers of a sequence become its two gray images
@@ -149,6 +151,74 @@ class KltSequence(C.Structure):
 
 
 assert (C.sizeof(KltKeyframe), C.sizeof(KltSequence)) == (128, 248)
+
+
+KPS_PLANES = ("kps2d", "kps3d", "flags", "kf_id", "kp_index", "outlier_count", "inlier_count", "kf_inv_depth",
+              "kf_variance", "score", "level_type", "color", "n")
+
+
+class KpsPlanes(C.Structure):
+    """svo_kps_planes: the twelve planes of a keypoint set and its count, device addresses"""
+    _fields_ = [(name, C.c_void_p) for name in KPS_PLANES]
+
+
+class CompactSequence(C.Structure):
+    _fields_ = [("src", KpsPlanes), ("dst", KpsPlanes), ("mode", C.c_int32), ("width", C.c_int32), ("height", C.c_int32),
+                ("start", C.c_int32), ("enable", C.c_void_p), ("zero", C.c_void_p), ("zero_res", C.c_void_p),
+                ("min_kf", C.c_void_p), ("zero_count", C.c_int32), ("zero_res_count", C.c_int32)]
+
+
+class MergeSequence(C.Structure):
+    _fields_ = [("cam", CameraSettings), ("width", C.c_int32), ("height", C.c_int32), ("det", C.c_void_p),
+                ("n_det", C.c_void_p), ("kps", KpsPlanes), ("sel", C.c_void_p), ("sel_level", C.c_void_p),
+                ("sel_cell", C.c_void_p), ("occupied", C.c_void_p), ("old_count", C.c_void_p), ("overflow", C.c_void_p),
+                ("enable", C.c_void_p), ("occupied_count", C.c_int32), ("pad_", C.c_int32)]
+
+
+class KfInitSequence(C.Structure):
+    _fields_ = [("cam", CameraSettings), ("first_frame", C.c_int32), ("new_kf_id", C.c_int32), ("kf_mask", C.c_int32),
+                ("evict_id", C.c_int32), ("kps", KpsPlanes), ("record", KpsPlanes), ("old_count", C.c_void_p),
+                ("disparity", C.c_void_p), ("frame_pose", C.c_void_p), ("kfs", C.c_void_p), ("kfs_bytes", C.c_int64),
+                ("color_lcg", C.c_void_p), ("n_out", C.c_void_p), ("enable", C.c_void_p), ("tmpl", C.c_void_p),
+                ("tmpl_valid", C.c_void_p), ("tmpl_valid_bytes", C.c_int32), ("tmpl_cap", C.c_int32),
+                ("tmpl_win", C.c_int32), ("pad_", C.c_int32)]
+
+
+class SsdSequence(C.Structure):
+    _fields_ = [("left", Image), ("right", Image), ("n", C.c_void_p), ("kps2d", C.c_void_p), ("disparity", C.c_void_p),
+                ("win", C.c_int32), ("search_x", C.c_int32), ("search_y", C.c_int32), ("clamp_half", C.c_int32),
+                ("first", C.c_int32), ("cap", C.c_int32), ("first_ptr", C.c_void_p), ("enable", C.c_void_p)]
+
+
+assert (C.sizeof(KpsPlanes), C.sizeof(CompactSequence), C.sizeof(MergeSequence), C.sizeof(KfInitSequence),
+        C.sizeof(SsdSequence)) == (104, 264, 272, 400, 112)
+
+
+def _addr(x):
+    """a device address from a tensor, an integer or None"""
+    if x is None:
+        return None
+    if isinstance(x, int):
+        return C.c_void_p(x)
+    assert x.is_cuda
+    return C.c_void_p(x.data_ptr())
+
+
+def _fill(struct, d, skip=()):
+    """the fields of a ctypes structure from a dict: addresses for pointer fields, nested dicts for nested
+    structures, values as they are otherwise; a missing key is NULL / 0"""
+    for name, typ in struct._fields_:
+        if name in skip or name not in d or d[name] is None:
+            continue
+        v = d[name]
+        if typ is C.c_void_p:
+            setattr(struct, name, _addr(v))
+        elif typ is KpsPlanes:
+            _fill(getattr(struct, name), v)
+        elif typ in (C.c_int32, C.c_int64):
+            setattr(struct, name, int(v))
+        else:
+            setattr(struct, name, v)
 
 
 class InputSide(C.Structure):
@@ -478,6 +548,26 @@ def klt_cache_layout(win):
     rec, off, hb, lv = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_int(0)
     _check(lib().svo_klt_cache_layout(int(win), C.byref(rec), C.byref(off), C.byref(hb), C.byref(lv)))
     return rec.value, off.value, hb.value, lv.value
+
+
+def keyframe_launch_info(cap, max_cells, tmpl_cap):
+    """svo_keyframe_launch_info (host only): (threads of the compaction launch for sets of `cap`, threads of the
+    select + merge launch for `max_cells`, bytes of "stored" flags of a template cache of tmpl_cap keypoints)"""
+    a, b, v = C.c_int(0), C.c_int(0), C.c_int64(0)
+    _check(lib().svo_keyframe_launch_info(int(cap), int(max_cells), int(tmpl_cap), C.byref(a), C.byref(b), C.byref(v)))
+    return a.value, b.value, v.value
+
+
+def keyframe_record_layout():
+    """svo_keyframe_record_layout (host only): dict of a keyframe table record's size (`bytes`) and the offsets of
+    n, pose, tmpl, tmpl_valid, tmpl_cap, tmpl_win and `planes` (name -> offset of that plane's pointer)"""
+    names = ("bytes", "n", "pose", "tmpl", "tmpl_valid", "tmpl_cap", "tmpl_win")
+    out = [C.c_int64(0) for _ in names]
+    planes = (C.c_int64 * 12)()
+    _check(lib().svo_keyframe_record_layout(*[C.byref(o) for o in out], planes))
+    d = {k: o.value for k, o in zip(names, out)}
+    d["planes"] = dict(zip(KPS_PLANES[:12], planes))
+    return d
 
 
 def rectify_inverse(cal):
@@ -954,6 +1044,49 @@ class Handle:
             _ptr(frame_pose), _ptr(disparity), _ptr(ref3d), _ptr(ref2d), _ptr(kf_pose), _ptr(outlier), _ptr(inlier),
             _ptr(kf_x), _ptr(kf_p), int(do_outlier_check), int(do_update), int(do_flags), int(do_reproject),
             int(width), int(height), _ptr(inside_count)))
+
+
+    # -- keyframe path bookkeeping -------------------------------------------
+    def compact_batch(self, seqs, cap):
+        """Diagnostic: svo_compact_batch over len(seqs) sequences, each a dict with the fields of
+        svo_compact_sequence (src / dst: dicts of the planes KPS_PLANES; addresses as device tensors or integers).
+        Returns the workgroup size of the launch. Complete on return."""
+        arr = (CompactSequence * len(seqs))()
+        for a, s in zip(arr, seqs):
+            _fill(a, s)
+        threads = C.c_int(0)
+        _check(lib().svo_compact_batch(self._h, len(seqs), arr, int(cap), C.byref(threads)))
+        return threads.value
+
+    def keyframe_merge_batch(self, seqs, n_levels, max_cells, cap):
+        """Diagnostic: svo_keyframe_merge_batch; seqs: dicts with the fields of svo_merge_sequence (cam: CameraSettings).
+        Returns the workgroup size of the launch."""
+        arr = (MergeSequence * len(seqs))()
+        for a, s in zip(arr, seqs):
+            _fill(a, s)
+        threads = C.c_int(0)
+        _check(lib().svo_keyframe_merge_batch(self._h, len(seqs), arr, int(n_levels), int(max_cells), int(cap),
+                                              C.byref(threads)))
+        return threads.value
+
+    def keyframe_init_batch(self, seqs, cap):
+        """Diagnostic: svo_keyframe_init_batch; seqs: dicts with the fields of svo_kf_init_sequence."""
+        arr = (KfInitSequence * len(seqs))()
+        for a, s in zip(arr, seqs):
+            _fill(a, s)
+        _check(lib().svo_keyframe_init_batch(self._h, len(seqs), arr, int(cap)))
+
+    def ssd_disparity_batch(self, seqs, n_bound, win, search_y):
+        """Diagnostic: svo_ssd_disparity_batch; seqs: dicts with the fields of svo_ssd_sequence (left / right: uint8
+        device tensors or views). Returns the largest window of the kernel shape the launch chose."""
+        arr = (SsdSequence * len(seqs))()
+        for a, s in zip(arr, seqs):
+            _fill(a, s, skip=("left", "right"))
+            a.left, a.right = _img(s["left"]), _img(s["right"])
+        max_win = C.c_int(0)
+        _check(lib().svo_ssd_disparity_batch(self._h, len(seqs), arr, int(n_bound), int(win), int(search_y),
+                                             C.byref(max_win)))
+        return max_win.value
 
 
 def detect_to_numpy(cells, counts):
