@@ -1128,6 +1128,19 @@ int svo_sparse_align_batch(svo_handle *h, int batch, int stride, const int32_t *
                            const svo_image *prev_pyr, const svo_image *cur_pyr, const svo_camera_settings *cam,
                            const float *pose_guess, int dbg_level, uint32_t ws_fill, float *pose_out, float *cost,
                            svo_gn_trace *trace, float *dbg, int *waves, int *mode, int *cap);
+/* The same launch, and mats_out[batch] (device, 8-byte aligned) receives per sequence the block of rotation matrices
+ * of its pose_out that the alignment kernel leaves for the tracker's KLT launch to project with. */
+int svo_sparse_align_batch_mats(svo_handle *h, int batch, int stride, const int32_t *n_dev, int n_bound,
+                                const svo_kp2d *kps2d, const svo_kp3d *kps3d, const uint32_t *flags,
+                                const svo_image *prev_pyr, const svo_image *cur_pyr, const svo_camera_settings *cam,
+                                const float *pose_guess, int dbg_level, uint32_t ws_fill, float *pose_out, float *cost,
+                                svo_gn_trace *trace, float *dbg, int *waves, int *mode, int *cap, void *mats_out);
+/* Host only: bytes of one such block and the offsets in it of Rd (double[9], cv::Rodrigues of the pose's rotation
+ * vector r, row major), R (float[9], Rd rounded: PoseManager::get_rotation_matrix), Ri (float[9], cv::Rodrigues of -r
+ * rounded: get_inv_rotation_matrix, src/lib/pose_manager.cpp:9-17) and t (float[3], the translation). Bytes outside
+ * the four members are padding and hold nothing. Any output may be NULL. */
+int svo_pose_mats_layout(int64_t *block_bytes, int64_t *rd_offset, int64_t *r_offset, int64_t *ri_offset,
+                         int64_t *t_offset);
 /* Diagnostic: the depth filter update (svo_depth_filter_update) of `batch` sequences in one launch, with explicit
  * references, laid out as above (kf_pose [batch * stride][6], frame_pose [batch][6]). do_flags: the counter
  * rules of StereoSlam::new_image (src/lib/stereo_slam.cpp:212-216) are applied to `flags`; do_reproject: kps2d
@@ -1302,6 +1315,48 @@ typedef struct svo_ssd_sequence {
 } svo_ssd_sequence;
 int svo_ssd_disparity_batch(svo_handle *h, int batch, const svo_ssd_sequence *seqs, int n_bound, int win, int search_y,
                             int *max_win);
+
+/* Diagnostic: the depth filter update as the tracker launches it for a tracked frame (svo_filter_update_batch is the
+ * stage form: explicit references, nothing written outside the frame's arrays). Keypoint i of sequence b comes from
+ * keyframe record kf_id[i] & kf_mask of the sequence's table (kf_mask = table - 1, table a power of two: a ring over
+ * the ids, the tracker's form; kf_mask = -1: record kf_id[i] as it is), point kp_index[i] of it. The kernel
+ *   gathers that record's pose, kps3d (the reference of DepthFilter::outlier_check) and kps2d (of update_kps3d),
+ *   runs outlier_check and update_kps3d (src/lib/depth_filter.cpp:40-50) on the frame's own arrays, and
+ *   with do_flags writes back into the keyframe as the loop of StereoSlam::new_image does
+ *   (src/lib/stereo_slam.cpp:196-229): kps3d, outlier_count, inlier_count, and the flags merged: the keyframe keeps its
+ *   own SVO_IGNORE_DURING_REFINEMENT bit and takes SVO_IGNORE_TEMPORARY and SVO_IGNORE_COMPLETELY from the frame;
+ *   with do_reproject kps2d receives the projection and *inside_count (or NULL) is INCREASED by the keypoints that
+ *   KeyFrameManager::keyframe_needed counts in a width x height image (src/lib/keyframe_manager.cpp:55-64).
+ * Per sequence (HOST array seqs[batch]; every pointer device memory unless said otherwise): kps, the frame's set
+ * (score, level_type and color are not used and may be NULL; the arrays hold at least *kps.n entries); kfs, a HOST
+ * array of `table` keyframes, each its pose and five arrays of n entries (n 0: a vacant record, the arrays may be
+ * NULL); records, `table` records of svo_keyframe_record_layout bytes that the entry fills before the launch (pose,
+ * n and the five array pointers; everything else 0). Before anything is written the counts (0 <= *kps.n <= n_bound),
+ * kf_id (>= 0, its record < table) and kp_index (0 <= index < that keyframe's n) are read back and checked. The pairs
+ * (record, kp_index) of a sequence must be distinct, as they are in the reference (not checked: two keypoints of one
+ * pair would race for the keyframe's entry). One launch of grid (ceil(n_bound / 64), batch), filled by the filling of
+ * the tracker's step. Complete on return. */
+typedef struct svo_filter_keyframe {
+    float pose[6];
+    svo_kp2d *kps2d;
+    svo_kp3d *kps3d;
+    uint32_t *flags;
+    int32_t *outlier_count, *inlier_count;
+    int32_t n, pad_;
+} svo_filter_keyframe;
+typedef struct svo_filter_table_sequence {
+    svo_camera_settings cam;
+    svo_kps_planes kps;
+    const float *frame_pose;        /* [6]                                                                        */
+    const float *disparity;         /* [n] (NULL without do_outlier_check)                                        */
+    const svo_filter_keyframe *kfs; /* HOST array [table]                                                         */
+    void *records;
+    int64_t records_bytes;
+    int32_t table, kf_mask, width, height;
+    int32_t *inside_count;          /* [1] or NULL                                                                */
+} svo_filter_table_sequence;
+int svo_filter_update_table_batch(svo_handle *h, int batch, const svo_filter_table_sequence *seqs, int n_bound,
+                                  int do_outlier_check, int do_update, int do_flags, int do_reproject);
 
 #ifdef __cplusplus
 }

@@ -335,6 +335,41 @@ def inside_count(kps2d, flags, width, height):
     return lib().svo_o_inside_count(_p(kps2d), _p(flags), kps2d.shape[0], int(width), int(height))
 
 
+class KfSlab(C.Structure):
+    """svo_o_kf_slab (svo_oracle.h): one keyframe record of svo_o_filter_table"""
+    _fields_ = [("pose", C.c_float * 6)] + \
+               [(n, C.c_void_p) for n in ("kps2d", "kps3d", "flags", "outlier_count", "inlier_count")] + [("n", C.c_int32)]
+
+
+def filter_table(frame, kf_id, kp_index, table, kf_mask, disparity, frame_pose, cam, switches, width, height):
+    """svo_o_filter_table. frame: dict(kps2d, kps3d, flags, outlier, inlier, kf_inv_depth, kf_variance); table: one
+    dict(pose, kps2d, kps3d, flags, outlier, inlier) per record. Nothing given is changed: returns (frame, table,
+    inside) as new dicts of the same keys."""
+    typ = dict(kps2d=np.float32, kps3d=np.float32, flags=np.uint32, outlier=np.int32, inlier=np.int32,
+               kf_inv_depth=np.float32, kf_variance=np.float32, pose=np.float32)
+    fr = {k: np.array(frame[k], dtype=typ[k], order="C") for k in typ if k != "pose"}
+    tb = [{k: np.array(rec[k], dtype=typ[k], order="C") for k in ("pose", "kps2d", "kps3d", "flags", "outlier", "inlier")}
+          for rec in table]
+    slabs = (KfSlab * max(len(tb), 1))()
+    for s, rec in zip(slabs, tb):
+        s.pose[:] = rec["pose"].tolist()
+        s.kps2d, s.kps3d, s.flags = _p(rec["kps2d"]), _p(rec["kps3d"]), _p(rec["flags"])
+        s.outlier_count, s.inlier_count, s.n = _p(rec["outlier"]), _p(rec["inlier"]), len(rec["flags"])
+    kf_id = np.ascontiguousarray(kf_id, dtype=np.int32)
+    kp_index = np.ascontiguousarray(kp_index, dtype=np.int32)
+    n = len(kf_id)
+    assert all(len(fr[k]) == n for k in fr) and len(kp_index) == n
+    rec_of = kf_id & np.int32(kf_mask)
+    assert n == 0 or (rec_of.min() >= 0 and rec_of.max() < len(tb))
+    assert all(0 <= kp_index[i] < len(tb[rec_of[i]]["flags"]) for i in range(n))
+    disparity, frame_pose = _f32(disparity), _f32(frame_pose)
+    inside = lib().svo_o_filter_table(
+        _p(fr["kps2d"]), _p(fr["kps3d"]), _p(fr["flags"]), _p(fr["outlier"]), _p(fr["inlier"]), _p(fr["kf_inv_depth"]),
+        _p(fr["kf_variance"]), _p(kf_id), _p(kp_index), n, slabs, int(kf_mask), _p(disparity), _p(frame_pose),
+        C.byref(cam), *[int(s) for s in switches], int(width), int(height))
+    return fr, tb, inside
+
+
 def fast_score_nms(img, threshold=6):
     h, w = img.shape
     out = np.zeros((h, w), np.uint8)

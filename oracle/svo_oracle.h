@@ -130,6 +130,29 @@ void svo_o_update_kps3d(const svo_kp2d *kps2d, svo_kp3d *kps3d, const uint32_t *
 void svo_o_filter_flags(uint32_t *flags, const int32_t *outlier_count, const int32_t *inlier_count, int n);
 int  svo_o_inside_count(const svo_kp2d *kps2d, const uint32_t *flags, int n, int image_width, int image_height);
 
+/* C2 + D1 + D3 over a keyframe table: the depth filter of a tracked frame as StereoSlam::new_image runs it
+ * (src/lib/stereo_slam.cpp:196-229 with DepthFilter::update_depth, src/lib/depth_filter.cpp:40-50), on plain arrays.
+ * Keypoint i of the frame comes from keyframe record kfs[kf_id[i] & kf_mask] (kf_mask -1: the id as it is), point
+ * kp_index[i] there: that record's pose, kps3d (the outlier check's reference) and kps2d (the update's) are gathered
+ * for every keypoint first; then, each under its switch, svo_o_outlier_check, svo_o_update_kps3d (which starts from
+ * the FRAME's kps3d), svo_o_filter_flags with the write-back into the keyframe (:205-226: kps3d, the two counters,
+ * ignore_temporary and ignore_completely; the keyframe's own ignore_during_refinement stays), and the reprojection
+ * of :228-229 with the counter of keyframe_needed (src/lib/keyframe_manager.cpp:55-64) in a width x height image,
+ * which is returned (0 without do_reproject). Without do_flags no keyframe array is written. */
+typedef struct svo_o_kf_slab {
+    float pose[6];
+    svo_kp2d *kps2d;
+    svo_kp3d *kps3d;
+    uint32_t *flags;
+    int32_t *outlier_count, *inlier_count;
+    int32_t n;
+} svo_o_kf_slab;
+int  svo_o_filter_table(svo_kp2d *kps2d, svo_kp3d *kps3d, uint32_t *flags, int32_t *outlier_count,
+                        int32_t *inlier_count, float *kf_inv_depth, float *kf_variance, const int32_t *kf_id,
+                        const int32_t *kp_index, int n, const svo_o_kf_slab *kfs, int kf_mask, const float *disparity,
+                        const float frame_pose[6], const svo_camera_settings *cam, int do_outlier_check,
+                        int do_update, int do_flags, int do_reproject, int width, int height);
+
 /* ---- whole StereoSlam restatement (tracker.c) --------------------------- */
 typedef struct svo_o_slam svo_o_slam;
 svo_o_slam *svo_o_slam_create(const svo_camera_settings *cam);

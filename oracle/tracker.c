@@ -697,6 +697,51 @@ static void traj_push(svo_o_slam *s, const float pose[6])
     memcpy(&s->trajectory[s->n_traj++], pose, sizeof(svo_pose));
 }
 
+/* The depth filter of a tracked frame over a keyframe table (svo_oracle.h): DepthFilter::update_depth —
+ * src/lib/depth_filter.cpp:40-50 — the write-back of src/lib/stereo_slam.cpp:205-226 and the reprojection of
+ * :228-229. svo_o_slam_new_image runs exactly this. */
+int svo_o_filter_table(svo_kp2d *kps2d, svo_kp3d *kps3d, uint32_t *flags, int32_t *outlier_count,
+                       int32_t *inlier_count, float *kf_inv_depth, float *kf_variance, const int32_t *kf_id,
+                       const int32_t *kp_index, int n, const svo_o_kf_slab *kfs, int kf_mask, const float *disparity,
+                       const float frame_pose[6], const svo_camera_settings *cam, int do_outlier_check,
+                       int do_update, int do_flags, int do_reproject, int width, int height)
+{
+    svo_kp3d *ref3d = (svo_kp3d *)malloc(sizeof(svo_kp3d) * (size_t)(n + 1));
+    svo_kp2d *ref2d = (svo_kp2d *)malloc(sizeof(svo_kp2d) * (size_t)(n + 1));
+    float *kfpose = (float *)malloc(sizeof(float) * 6 * (size_t)(n + 1));
+    for (int i = 0; i < n; i++) {
+        const svo_o_kf_slab *kf = &kfs[kf_id[i] & kf_mask];
+        ref3d[i] = kf->kps3d[kp_index[i]];
+        ref2d[i] = kf->kps2d[kp_index[i]];
+        memcpy(kfpose + (size_t)i * 6, kf->pose, sizeof(float) * 6);
+    }
+    if (do_outlier_check)
+        svo_o_outlier_check(kps2d, disparity, n, cam, frame_pose, ref3d, kfpose, outlier_count, inlier_count);
+    if (do_update)
+        svo_o_update_kps3d(kps2d, kps3d, flags, n, cam, frame_pose, ref2d, kfpose, outlier_count, kf_inv_depth,
+                           kf_variance);
+    if (do_flags) {
+        /* write back — src/lib/stereo_slam.cpp:205-226 */
+        svo_o_filter_flags(flags, outlier_count, inlier_count, n);
+        for (int i = 0; i < n; i++) {
+            const svo_o_kf_slab *kf = &kfs[kf_id[i] & kf_mask];
+            const int k = kp_index[i];
+            kf->kps3d[k] = kps3d[i];
+            kf->flags[k] = (kf->flags[k] & SVO_IGNORE_DURING_REFINEMENT) |
+                           (flags[i] & (SVO_IGNORE_TEMPORARY | SVO_IGNORE_COMPLETELY));
+            kf->inlier_count[k] = inlier_count[i];
+            kf->outlier_count[k] = outlier_count[i];
+        }
+    }
+    int inside = 0;
+    if (do_reproject) {
+        svo_o_project_keypoints(frame_pose, kps3d, n, cam, kps2d);
+        inside = svo_o_inside_count(kps2d, flags, n, width, height);
+    }
+    free(ref3d); free(ref2d); free(kfpose);
+    return inside;
+}
+
 /* StereoSlam::new_image — src/lib/stereo_slam.cpp:123-271 */
 int svo_o_slam_new_image(svo_o_slam *s, const uint8_t *left, const uint8_t *right, int width,
                          int height, float time_stamp)
@@ -805,47 +850,59 @@ int svo_o_slam_new_image(svo_o_slam *s, const uint8_t *left, const uint8_t *righ
                             cam->window_size_depth_calculator, cam->search_x, cam->search_y, 1, disp);
         stx->t_disparity = now_s() - t0;
         t0 = now_s();
-        svo_kp3d *ref3d = (svo_kp3d *)malloc(sizeof(svo_kp3d) * (size_t)(n + 1));
-        float *kfpose = (float *)malloc(sizeof(float) * 6 * (size_t)(n + 1));
+        /* the frame's info as planes, and every keyframe's kps and info as a slab of the table (the reference
+         * indexes its keyframes by id: kf_mask -1) */
         int32_t *outl = (int32_t *)malloc(sizeof(int32_t) * (size_t)(n + 1));
         int32_t *inl = (int32_t *)malloc(sizeof(int32_t) * (size_t)(n + 1));
+        int32_t *kfid = (int32_t *)malloc(sizeof(int32_t) * (size_t)(n + 1));
+        int32_t *kpidx = (int32_t *)malloc(sizeof(int32_t) * (size_t)(n + 1));
         float *kx = (float *)malloc(sizeof(float) * (size_t)(n + 1));
         float *kP = (float *)malloc(sizeof(float) * (size_t)(n + 1));
         for (int i = 0; i < n; i++) {
             const svo_kp_info *in = &f->kps.info[i];
-            const keyframe_t *kf = &s->keyframes[in->keyframe_id];
-            ref3d[i] = kf->kps.kps3d[in->keypoint_index];
-            memcpy(kfpose + (size_t)i * 6, kf->pose, sizeof(float) * 6);
+            kfid[i] = in->keyframe_id; kpidx[i] = in->keypoint_index;
             outl[i] = in->outlier_count; inl[i] = in->inlier_count;
             kx[i] = in->kf_inv_depth; kP[i] = in->kf_variance;
         }
-        svo_o_outlier_check(f->kps.kps2d, disp, n, cam, f->pose, ref3d, kfpose, outl, inl);
-        svo_kp3d *updated = (svo_kp3d *)malloc(sizeof(svo_kp3d) * (size_t)(n + 1));
-        memcpy(updated, f->kps.kps3d, sizeof(svo_kp3d) * (size_t)n);
-        svo_o_update_kps3d(f->kps.kps2d, updated, flags, n, cam, f->pose, refpts, kfpose, outl, kx, kP);
-
-        /* write back — src/lib/stereo_slam.cpp:205-226 */
+        size_t kf_points = 0;
+        for (int k = 0; k < s->n_keyframes; k++) kf_points += (size_t)s->keyframes[k].kps.n;
+        svo_o_kf_slab *slabs = (svo_o_kf_slab *)malloc(sizeof(svo_o_kf_slab) * (size_t)(s->n_keyframes + 1));
+        uint32_t *kf_flags = (uint32_t *)malloc(sizeof(uint32_t) * (kf_points + 1));
+        int32_t *kf_outl = (int32_t *)malloc(sizeof(int32_t) * (kf_points + 1));
+        int32_t *kf_inl = (int32_t *)malloc(sizeof(int32_t) * (kf_points + 1));
+        for (int k = 0, o = 0; k < s->n_keyframes; k++) {
+            keyframe_t *kf = &s->keyframes[k];
+            svo_o_kf_slab *sl = &slabs[k];
+            memcpy(sl->pose, kf->pose, sizeof(sl->pose));
+            sl->kps2d = kf->kps.kps2d; sl->kps3d = kf->kps.kps3d; sl->n = kf->kps.n;
+            sl->flags = kf_flags + o; sl->outlier_count = kf_outl + o; sl->inlier_count = kf_inl + o;
+            for (int j = 0; j < kf->kps.n; j++) {
+                sl->flags[j] = info_flags(&kf->kps.info[j]);
+                sl->outlier_count[j] = kf->kps.info[j].outlier_count;
+                sl->inlier_count[j] = kf->kps.info[j].inlier_count;
+            }
+            o += kf->kps.n;
+        }
+        svo_o_filter_table(f->kps.kps2d, f->kps.kps3d, flags, outl, inl, kx, kP, kfid, kpidx, n, slabs, -1, disp,
+                           f->pose, cam, 1, 1, 1, 1, width, height);
         for (int i = 0; i < n; i++) {
             svo_kp_info *in = &f->kps.info[i];
             in->ignore_during_refinement = (flags[i] & SVO_IGNORE_DURING_REFINEMENT) != 0;
             in->ignore_completely = (flags[i] & SVO_IGNORE_COMPLETELY) != 0;
+            in->ignore_temporary = (flags[i] & SVO_IGNORE_TEMPORARY) != 0;
             in->outlier_count = outl[i]; in->inlier_count = inl[i];
             in->kf_inv_depth = kx[i]; in->kf_variance = kP[i];
-            keyframe_t *kf = &s->keyframes[in->keyframe_id];
-            uint32_t fb = (in->ignore_completely ? SVO_IGNORE_COMPLETELY : 0) | (in->ignore_temporary ? SVO_IGNORE_TEMPORARY : 0);
-            svo_o_filter_flags(&fb, &in->outlier_count, &in->inlier_count, 1);
-            in->ignore_completely = (fb & SVO_IGNORE_COMPLETELY) != 0;
-            in->ignore_temporary = (fb & SVO_IGNORE_TEMPORARY) != 0;
-            kf->kps.kps3d[in->keypoint_index] = updated[i];
-            f->kps.kps3d[i] = updated[i];
-            svo_kp_info *ki = &kf->kps.info[in->keypoint_index];
-            ki->ignore_temporary = in->ignore_temporary;
-            ki->ignore_completely = in->ignore_completely;
-            ki->inlier_count = in->inlier_count;
-            ki->outlier_count = in->outlier_count;
         }
+        for (int k = 0; k < s->n_keyframes; k++)
+            for (int j = 0; j < s->keyframes[k].kps.n; j++) {
+                svo_kp_info *ki = &s->keyframes[k].kps.info[j];
+                ki->ignore_during_refinement = (slabs[k].flags[j] & SVO_IGNORE_DURING_REFINEMENT) != 0;
+                ki->ignore_completely = (slabs[k].flags[j] & SVO_IGNORE_COMPLETELY) != 0;
+                ki->ignore_temporary = (slabs[k].flags[j] & SVO_IGNORE_TEMPORARY) != 0;
+                ki->outlier_count = slabs[k].outlier_count[j];
+                ki->inlier_count = slabs[k].inlier_count[j];
+            }
         stx->t_filter = now_s() - t0;
-        svo_o_project_keypoints(f->pose, f->kps.kps3d, n, cam, f->kps.kps2d);
 
         if (keyframe_needed(s, f)) {
             t0 = now_s();
@@ -859,8 +916,8 @@ int svo_o_slam_new_image(svo_o_slam *s, const uint8_t *left, const uint8_t *righ
             free(fb);
         }
         free(flags); free(tracked); free(refpts); free(gref); free(gcur); free(gidx);
-        free(err); free(gerr); free(gstatus); free(disp); free(ref3d); free(kfpose);
-        free(outl); free(inl); free(kx); free(kP); free(updated);
+        free(err); free(gerr); free(gstatus); free(disp); free(outl); free(inl); free(kx); free(kP);
+        free(kfid); free(kpidx); free(slabs); free(kf_flags); free(kf_outl); free(kf_inl);
     }
 
     if (prev) {

@@ -1022,12 +1022,14 @@ extern "C" int svo_reproj_gn_batch(svo_handle* h, int batch, int stride, const i
 // arrays. Every sequence gets record and per-keypoint workspaces of its own for the call ([levels used][68][rec_cap]
 // and [9][rec_cap] floats, rec_cap the multiple of 256 that covers the launch's cap), filled with ws_fill first: what
 // a kernel reads of a slot that nothing wrote is the caller's pattern.
-extern "C" int svo_sparse_align_batch(svo_handle* h, int batch, int stride, const int32_t* n_dev, int n_bound,
-                                      const svo_kp2d* kps2d, const svo_kp3d* kps3d, const uint32_t* flags,
-                                      const svo_image* prev_pyr, const svo_image* cur_pyr,
-                                      const svo_camera_settings* cam, const float* pose_guess, int dbg_level,
-                                      uint32_t ws_fill, float* pose_out, float* cost, svo_gn_trace* trace, float* dbg,
-                                      int* waves, int* mode, int* cap) {
+// mats_out: null, or [batch] blocks of sizeof(PoseMats) (svo_pose_mats_layout), SiaArgs::mats_out of every sequence:
+// what the tracker's KLT launch projects with (svo_sparse_align_batch_mats)
+static int sparse_align_batch(svo_handle* h, int batch, int stride, const int32_t* n_dev, int n_bound,
+                              const svo_kp2d* kps2d, const svo_kp3d* kps3d, const uint32_t* flags,
+                              const svo_image* prev_pyr, const svo_image* cur_pyr,
+                              const svo_camera_settings* cam, const float* pose_guess, int dbg_level,
+                              uint32_t ws_fill, float* pose_out, float* cost, svo_gn_trace* trace, float* dbg,
+                              int* waves, int* mode, int* cap, PoseMats* mats_out) {
     CHECK_H(h);
     if (!cam || !prev_pyr || !cur_pyr || !pose_guess || !pose_out || (n_bound > 0 && (!kps2d || !kps3d)))
         return svo_set_error(SVO_ERR_INVALID, "svo_sparse_align_batch: bad arguments");
@@ -1084,6 +1086,7 @@ extern "C" int svo_sparse_align_batch(svo_handle* h, int batch, int stride, cons
         sa.dbg_H = dbg ? dbg + 48 * (size_t)b : nullptr; sa.dbg_level = dbg_level;
         sa.cap = stride;
         sa.exact_pinv = h->exact_pinv;
+        sa.mats_out = mats_out ? mats_out + b : nullptr;
     }
     SiaArgs* d;
     rc = stage_blocks(h, blocks, &d);
@@ -1097,6 +1100,39 @@ extern "C" int svo_sparse_align_batch(svo_handle* h, int batch, int stride, cons
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(h->stream));
     return SVO_OK;            // (ws is freed here: the launch is complete)
+}
+
+extern "C" int svo_sparse_align_batch(svo_handle* h, int batch, int stride, const int32_t* n_dev, int n_bound,
+                                      const svo_kp2d* kps2d, const svo_kp3d* kps3d, const uint32_t* flags,
+                                      const svo_image* prev_pyr, const svo_image* cur_pyr,
+                                      const svo_camera_settings* cam, const float* pose_guess, int dbg_level,
+                                      uint32_t ws_fill, float* pose_out, float* cost, svo_gn_trace* trace, float* dbg,
+                                      int* waves, int* mode, int* cap) {
+    return sparse_align_batch(h, batch, stride, n_dev, n_bound, kps2d, kps3d, flags, prev_pyr, cur_pyr, cam, pose_guess,
+                              dbg_level, ws_fill, pose_out, cost, trace, dbg, waves, mode, cap, nullptr);
+}
+
+extern "C" int svo_sparse_align_batch_mats(svo_handle* h, int batch, int stride, const int32_t* n_dev, int n_bound,
+                                           const svo_kp2d* kps2d, const svo_kp3d* kps3d, const uint32_t* flags,
+                                           const svo_image* prev_pyr, const svo_image* cur_pyr,
+                                           const svo_camera_settings* cam, const float* pose_guess, int dbg_level,
+                                           uint32_t ws_fill, float* pose_out, float* cost, svo_gn_trace* trace, float* dbg,
+                                           int* waves, int* mode, int* cap, void* mats_out) {
+    if (!mats_out || (reinterpret_cast<uintptr_t>(mats_out) & (alignof(PoseMats) - 1)))
+        return svo_set_error(SVO_ERR_INVALID, "svo_sparse_align_batch_mats: mats_out must be %zu-byte aligned device memory",
+                             alignof(PoseMats));
+    return sparse_align_batch(h, batch, stride, n_dev, n_bound, kps2d, kps3d, flags, prev_pyr, cur_pyr, cam, pose_guess,
+                              dbg_level, ws_fill, pose_out, cost, trace, dbg, waves, mode, cap, static_cast<PoseMats*>(mats_out));
+}
+
+extern "C" int svo_pose_mats_layout(int64_t* block_bytes, int64_t* rd_offset, int64_t* r_offset, int64_t* ri_offset,
+                                    int64_t* t_offset) {
+    if (block_bytes) *block_bytes = (int64_t)sizeof(PoseMats);
+    if (rd_offset) *rd_offset = (int64_t)offsetof(PoseMats, Rd);
+    if (r_offset) *r_offset = (int64_t)offsetof(PoseMats, R);
+    if (ri_offset) *ri_offset = (int64_t)offsetof(PoseMats, Ri);
+    if (t_offset) *t_offset = (int64_t)offsetof(PoseMats, t);
+    return SVO_OK;
 }
 
 extern "C" int svo_filter_update_batch(svo_handle* h, int batch, int stride, const int32_t* n_dev, int n_bound, svo_kp2d* kps2d,
@@ -1561,5 +1597,79 @@ extern "C" int svo_ssd_disparity_batch(svo_handle* h, int batch, const svo_ssd_s
     if (rc) return rc;
     if (max_win) *max_win = ssd_pick_max_win(win, search_y);
     launch_ssd(d, batch, n_bound, win, search_y, h->stream);
+    return finish_launch(h);
+}
+
+// svo_filter_update_table_batch: launch_filter in the form the tracker makes it (FilterArgs::kfs set: references
+// gathered from the keyframe table, results written back into the keyframes), the argument blocks filled by the
+// filling of pack_tracking_args itself (fill_filter_table_args). The entry makes the table's records from the
+// caller's per-keyframe arrays and puts them into the caller's device memory; everything a lane would index with is
+// read back and checked first (a diagnostic may wait).
+static_assert(sizeof(svo_filter_keyframe) == 72 && sizeof(svo_filter_table_sequence) == 248, "the layouts the Python binding restates");
+
+extern "C" int svo_filter_update_table_batch(svo_handle* h, int batch, const svo_filter_table_sequence* seqs, int n_bound,
+                                             int do_outlier_check, int do_update, int do_flags, int do_reproject) {
+    CHECK_H(h);
+    if (batch < 1 || batch > 4096 || !seqs || n_bound < 0)
+        return svo_set_error(SVO_ERR_INVALID, "svo_filter_update_table_batch: need 1 <= batch <= 4096, seqs and n_bound >= 0");
+    HIP_TRY(hipStreamSynchronize(h->stream));      // (the caller's counts and indices are read back below)
+    std::vector<std::vector<KfDev>> tables((size_t)batch);
+    std::vector<int32_t> ids, idx;
+    for (int b = 0; b < batch; b++) {
+        const svo_filter_table_sequence& s = seqs[b];
+        const svo_kps_planes& p = s.kps;
+        if (!s.kfs || !s.records || !s.frame_pose || !p.n || !p.kps2d || !p.kps3d || !p.flags || !p.kf_id || !p.kp_index ||
+            !p.outlier_count || !p.inlier_count || !p.kf_inv_depth || !p.kf_variance || (do_outlier_check && !s.disparity))
+            return svo_set_error(SVO_ERR_INVALID, "svo_filter_update_table_batch: sequence %d: bad arguments", b);
+        const bool ring = s.kf_mask != -1;
+        if (s.table < 1 || s.table > 4096 || (ring && ((s.table & (s.table - 1)) != 0 || s.kf_mask != s.table - 1)) ||
+            (int64_t)s.table * (int64_t)sizeof(KfDev) > s.records_bytes || (reinterpret_cast<uintptr_t>(s.records) & 7))
+            return svo_set_error(SVO_ERR_INVALID, "svo_filter_update_table_batch: sequence %d: the table needs 1..4096 records "
+                                 "of %zu bytes, 8-byte aligned; a ring (kf_mask != -1) a power of two of them and kf_mask = "
+                                 "table - 1", b, sizeof(KfDev));
+        std::vector<KfDev>& rec = tables[(size_t)b];
+        rec.resize((size_t)s.table);
+        for (int k = 0; k < s.table; k++) {
+            const svo_filter_keyframe& f = s.kfs[k];
+            if (f.n < 0 || (f.n > 0 && (!f.kps2d || !f.kps3d || !f.flags || !f.outlier_count || !f.inlier_count)))
+                return svo_set_error(SVO_ERR_INVALID, "svo_filter_update_table_batch: sequence %d keyframe %d: bad arguments", b, k);
+            KfDev& d = rec[(size_t)k];          // (as fill_kf_record makes it, without images and cache: this kernel reads neither)
+            memset(&d, 0, sizeof(d));
+            memcpy(d.pose, f.pose, sizeof(d.pose));
+            d.kps2d = f.kps2d; d.kps3d = f.kps3d; d.flags = f.flags;
+            d.outlier_count = f.outlier_count; d.inlier_count = f.inlier_count;
+            d.n = f.n;
+        }
+        int32_t n = 0;
+        if (const int rc = read_i32(p.n, 1, &n)) return rc;
+        if (n < 0 || n > n_bound)
+            return svo_set_error(SVO_ERR_INVALID, "svo_filter_update_table_batch: sequence %d: n = %d is outside 0..n_bound = %d",
+                                 b, n, n_bound);
+        ids.resize((size_t)n); idx.resize((size_t)n);
+        if (n > 0) {
+            if (const int rc = read_i32(p.kf_id, n, ids.data())) return rc;
+            if (const int rc = read_i32(p.kp_index, n, idx.data())) return rc;
+        }
+        for (int i = 0; i < n; i++) {
+            const int slot = ids[(size_t)i] & s.kf_mask;
+            if (ids[(size_t)i] < 0 || slot >= s.table || idx[(size_t)i] < 0 || idx[(size_t)i] >= s.kfs[slot].n)
+                return svo_set_error(SVO_ERR_INVALID, "svo_filter_update_table_batch: sequence %d point %d: keyframe %d, index %d",
+                                     b, i, ids[(size_t)i], idx[(size_t)i]);
+        }
+    }
+    std::vector<FilterArgs> blocks((size_t)batch);
+    for (int b = 0; b < batch; b++) {
+        const svo_filter_table_sequence& s = seqs[b];
+        HIP_TRY(hipMemcpy(s.records, tables[(size_t)b].data(), sizeof(KfDev) * (size_t)s.table, hipMemcpyHostToDevice));
+        FilterArgs& fa = blocks[(size_t)b];
+        memset(&fa, 0, sizeof(fa));
+        fill_filter_table_args(fa, s.cam, kps_dev(s.kps), s.frame_pose, s.disparity, static_cast<KfDev*>(s.records), s.kf_mask,
+                               s.width, s.height, s.inside_count);
+        fa.do_outlier_check = do_outlier_check; fa.do_update = do_update; fa.do_flags = do_flags; fa.do_reproject = do_reproject;
+    }
+    FilterArgs* d;
+    const int rc = stage_blocks(h, blocks, &d);
+    if (rc) return rc;
+    launch_filter(d, batch, n_bound, h->stream);
     return finish_launch(h);
 }

@@ -283,14 +283,8 @@ void pack_tracking_args(svo_group* c, const Step& st) {
         ra.exact_pinv = c->exact_pinv;
         ra.zero_out = c->d_inside + s;      // filter_update_kernel adds to it
         pack_ssd(c, q, slot, 1, nullptr);
-        FilterArgs& fa = clear(a.filter.h[slot]);
-        fa.cam = q.cam; fa.n_ptr = k.n; fa.frame_pose = dr->pose_refined;
-        fa.kps2d = k.kps2d; fa.kps3d = k.kps3d; fa.flags = k.flags;
-        fa.outlier_count = k.outl; fa.inlier_count = k.inl; fa.kf_inv_depth = k.kfx;
-        fa.kf_variance = k.kfP; fa.disparity = q.disparity;
-        fa.kfs = q.d_kfs; fa.kf_mask = c->max_kf - 1; fa.kf_id = k.kf_id; fa.kp_index = k.kp_index;
-        fa.do_outlier_check = 1; fa.do_update = 1; fa.do_flags = 1; fa.do_reproject = 1;
-        fa.width = c->width; fa.height = c->height; fa.inside_count = c->d_inside + s;
+        fill_filter_table_args(clear(a.filter.h[slot]), q.cam, k, dr->pose_refined, q.disparity, q.d_kfs, c->max_kf - 1,
+                               c->width, c->height, c->d_inside + s);
     }
 }
 

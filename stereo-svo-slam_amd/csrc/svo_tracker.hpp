@@ -28,6 +28,22 @@ struct KpsDev {
     int* n;
 };
 
+// The depth filter's argument block in its tracker form (filter_update_kernel with FilterArgs::kfs set): the frame's
+// keypoint set, its refined pose and disparities, the sequence's keyframe table (a ring of kf_mask + 1 records over the
+// ids; -1: indexed by id as it is) and its inside counter, all four stages on. One filling for the tracker's step
+// (pack_tracking_args) and for the diagnostic entry svo_filter_update_table_batch. `fa` must be cleared.
+inline void fill_filter_table_args(FilterArgs& fa, const svo_camera_settings& cam, const KpsDev& k, const float* frame_pose,
+                                   const float* disparity, KfDev* kfs, int kf_mask, int width, int height,
+                                   int* inside_count) {
+    fa.cam = cam; fa.n_ptr = k.n; fa.frame_pose = frame_pose;
+    fa.kps2d = k.kps2d; fa.kps3d = k.kps3d; fa.flags = k.flags;
+    fa.outlier_count = k.outl; fa.inlier_count = k.inl; fa.kf_inv_depth = k.kfx;
+    fa.kf_variance = k.kfP; fa.disparity = disparity;
+    fa.kfs = kfs; fa.kf_mask = kf_mask; fa.kf_id = k.kf_id; fa.kp_index = k.kp_index;
+    fa.do_outlier_check = 1; fa.do_update = 1; fa.do_flags = 1; fa.do_reproject = 1;
+    fa.width = width; fa.height = height; fa.inside_count = inside_count;
+}
+
 struct CompactArgs {
     KpsDev src, dst;
     int mode;          // 0: remove_outliers, 1: find_bad_keypoints

@@ -50,6 +50,7 @@ SYMBOLS = (
     "svo_submit_trim_keyframes", "svo_trim_keyframes", "svo_ctx_set_keyframe_window", "svo_get_keyframe_range",
     "svo_keyframe_launch_info", "svo_compact_batch", "svo_keyframe_merge_batch", "svo_keyframe_init_batch",
     "svo_keyframe_record_layout", "svo_ssd_disparity_batch",
+    "svo_sparse_align_batch_mats", "svo_pose_mats_layout", "svo_filter_update_table_batch",
 )
 
 # svo_ctx_set_input_format / svo_convert_frames: how the buffers of a sequence become its two gray images
@@ -190,8 +191,23 @@ class SsdSequence(C.Structure):
                 ("first", C.c_int32), ("cap", C.c_int32), ("first_ptr", C.c_void_p), ("enable", C.c_void_p)]
 
 
+class FilterKeyframe(C.Structure):
+    """svo_filter_keyframe (include/svo_hip.h): one keyframe of svo_filter_update_table_batch."""
+    _fields_ = [("pose", C.c_float * 6)] + \
+               [(n, C.c_void_p) for n in ("kps2d", "kps3d", "flags", "outlier_count", "inlier_count")] + \
+               [("n", C.c_int32), ("pad_", C.c_int32)]
+
+
+class FilterTableSequence(C.Structure):
+    """svo_filter_table_sequence (include/svo_hip.h): one sequence of svo_filter_update_table_batch."""
+    _fields_ = [("cam", CameraSettings), ("kps", KpsPlanes), ("frame_pose", C.c_void_p), ("disparity", C.c_void_p),
+                ("kfs", C.POINTER(FilterKeyframe)), ("records", C.c_void_p), ("records_bytes", C.c_int64),
+                ("table", C.c_int32), ("kf_mask", C.c_int32), ("width", C.c_int32), ("height", C.c_int32),
+                ("inside_count", C.c_void_p)]
+
+
 assert (C.sizeof(KpsPlanes), C.sizeof(CompactSequence), C.sizeof(MergeSequence), C.sizeof(KfInitSequence),
-        C.sizeof(SsdSequence)) == (104, 264, 272, 400, 112)
+        C.sizeof(SsdSequence), C.sizeof(FilterKeyframe), C.sizeof(FilterTableSequence)) == (104, 264, 272, 400, 112, 72, 248)
 
 
 def _addr(x):
@@ -570,6 +586,15 @@ def keyframe_record_layout():
     return d
 
 
+def pose_mats_layout():
+    """svo_pose_mats_layout (host only): dict of the size (`bytes`) of the block of rotation matrices that the
+    alignment kernel leaves for the KLT launch, and of its members name -> (offset, numpy dtype, count): Rd, R, Ri, t"""
+    out = [C.c_int64(0) for _ in range(5)]
+    _check(lib().svo_pose_mats_layout(*[C.byref(o) for o in out]))
+    size, rd, r, ri, t = (o.value for o in out)
+    return dict(bytes=size, Rd=(rd, np.float64, 9), R=(r, np.float32, 9), Ri=(ri, np.float32, 9), t=(t, np.float32, 3))
+
+
 def rectify_inverse(cal):
     """svo_rectify_inverse (host only): ir[9] of the calibration, the inverse of P R in the arithmetic of the maps;
     SvoError for a calibration the library rejects."""
@@ -887,12 +912,14 @@ class Handle:
         return pose_out, cost, trace, dbg
 
     def sparse_align_batch(self, n, n_bound, kps2d, kps3d, flags, prev_pyrs, cur_pyrs, cam, pose_guess, dbg_level=-1,
-                           ws_fill=0, outputs=None):
+                           ws_fill=0, outputs=None, mats_out=None):
         """Diagnostic: svo_sparse_align of len(n) sequences in one launch. n: int32 [batch] device; the keypoint
         arrays are [batch, stride, ..] device tensors; prev_pyrs / cur_pyrs: per sequence the list of its level
         images (uint8 device tensors or views with unit column stride); pose_guess [batch, 6]. outputs: (pose_out
         [batch, 6], cost [batch], trace [batch, 8 * 52] bytes, dbg [batch, 48] or None) to write into, made here if
-        None. Returns (pose_out, cost, trace, dbg, (waves, mode, cap))."""
+        None. mats_out: None, or a device tensor of at least batch blocks of pose_mats_layout()["bytes"] that receives
+        every sequence's block of rotation matrices (svo_sparse_align_batch_mats). Returns (pose_out, cost, trace, dbg,
+        (waves, mode, cap))."""
         batch, stride = kps2d.shape[0], kps2d.shape[1]
         dev = kps2d.device
         levels = cam.max_pyramid_levels
@@ -907,10 +934,14 @@ class Handle:
             for l in range(levels):
                 pp[b * levels + l], cp[b * levels + l] = _img(prev_pyrs[b][l]), _img(cur_pyrs[b][l])
         waves, mode, cap = C.c_int(0), C.c_int(0), C.c_int(0)
-        _check(lib().svo_sparse_align_batch(self._h, batch, stride, _ptr(n), int(n_bound), _ptr(kps2d), _ptr(kps3d),
-                                            _ptr(flags), pp, cp, C.byref(cam), _ptr(pose_guess), int(dbg_level),
-                                            C.c_uint32(ws_fill), _ptr(pose_out), _ptr(cost), _ptr(trace), _ptr(dbg),
-                                            C.byref(waves), C.byref(mode), C.byref(cap)))
+        args = (self._h, batch, stride, _ptr(n), int(n_bound), _ptr(kps2d), _ptr(kps3d), _ptr(flags), pp, cp, C.byref(cam),
+                _ptr(pose_guess), int(dbg_level), C.c_uint32(ws_fill), _ptr(pose_out), _ptr(cost), _ptr(trace), _ptr(dbg),
+                C.byref(waves), C.byref(mode), C.byref(cap))
+        if mats_out is None:
+            _check(lib().svo_sparse_align_batch(*args))
+        else:
+            assert mats_out.numel() * mats_out.element_size() >= batch * pose_mats_layout()["bytes"]
+            _check(lib().svo_sparse_align_batch_mats(*args, _ptr(mats_out)))
         return pose_out, cost, trace, dbg, (waves.value, mode.value, cap.value)
 
     # -- A3 ---------------------------------------------------------------
@@ -1045,6 +1076,25 @@ class Handle:
             _ptr(kf_x), _ptr(kf_p), int(do_outlier_check), int(do_update), int(do_flags), int(do_reproject),
             int(width), int(height), _ptr(inside_count)))
 
+    def filter_update_table_batch(self, seqs, n_bound, do_outlier_check=1, do_update=1, do_flags=1, do_reproject=1):
+        """Diagnostic: svo_filter_update_table_batch, the depth filter launch as the tracker makes it for a tracked
+        frame, over len(seqs) sequences. A sequence is a dict with the fields of svo_filter_table_sequence: cam
+        (CameraSettings), kps (dict of the planes KPS_PLANES), frame_pose, disparity, kfs (a list of `table` dicts with
+        the fields of svo_filter_keyframe; pose: six numbers), records / records_bytes, kf_mask, width, height,
+        inside_count; addresses as device tensors or integers. The frame's and the keyframes' arrays are updated in
+        place. Complete on return."""
+        arr = (FilterTableSequence * len(seqs))()
+        keep = []
+        for a, s in zip(arr, seqs):
+            kfs = (FilterKeyframe * max(len(s["kfs"]), 1))()
+            keep.append(kfs)
+            for k, f in zip(kfs, s["kfs"]):
+                _fill(k, f, skip=("pose",))
+                k.pose[:] = [float(v) for v in f["pose"]]
+            _fill(a, s, skip=("kfs", "table"))
+            a.kfs, a.table = kfs, int(s.get("table", len(s["kfs"])))
+        _check(lib().svo_filter_update_table_batch(self._h, len(seqs), arr, int(n_bound), int(do_outlier_check),
+                                                   int(do_update), int(do_flags), int(do_reproject)))
 
     # -- keyframe path bookkeeping -------------------------------------------
     def compact_batch(self, seqs, cap):

@@ -211,9 +211,34 @@ def cached_oracle(name, n):
     return oracle_align(c, n)
 
 
+MATS_FILL = 0x5A
+
+
+def check_mats(got, what):
+    """the block of rotation matrices the alignment kernel leaves for the tracker's KLT launch to project with
+    (SiaArgs::mats_out) is that of the pose it returns, byte for byte: Rd = cv::Rodrigues(r) in double, R = Rd
+    rounded to float, Ri = cv::Rodrigues(-r) rounded to float, t the translation. Padding is whatever the layout
+    entry leaves out."""
+    L = hip_lib.pose_mats_layout()
+    pose = np.asarray(got["pose"], F)
+    want = dict(Rd=O.rodrigues(pose[3:6]).reshape(9), R=O.rodrigues(pose[3:6]).astype(F).reshape(9),
+                Ri=O.rodrigues(-pose[3:6]).astype(F).reshape(9), t=pose[:3])
+    covered = 0
+    for name in ("Rd", "R", "Ri", "t"):
+        off, dtype, count = L[name]
+        w = np.ascontiguousarray(want[name], dtype)
+        assert w.size == count
+        block = got["mats"][off:off + w.nbytes]
+        assert block.tobytes() == w.tobytes(), f"{what}: {name} of mats_out: {block.view(dtype)} against {w}"
+        covered += w.nbytes
+    assert covered <= L["bytes"] < covered + 8 and len(got["mats"]) == L["bytes"]
+
+
 def run_batch(H, plan, n_bound, ws_fill, dbg_level=-1, exact=True, views=None):
-    """svo_sparse_align_batch on a plan [(set, n)]: per sequence dict(pose, cost, trace, dbg), and the shape"""
+    """svo_sparse_align_batch on a plan [(set, n)]: per sequence dict(pose, cost, trace, dbg, mats), and the shape"""
     batch, stride = len(plan), n_bound + PAD
+    mats_bytes = hip_lib.pose_mats_layout()["bytes"]
+    mats = torch.full((batch + 1, mats_bytes), MATS_FILL, dtype=torch.uint8, device="cuda")
     cam = AC.scenes()[plan[0][0]["scene"]]["cam"]
     arrays = [poisoned(c, n, stride) for c, n in plan]
     k2, k3, fl = (dev(np.stack([a[k] for a in arrays])) for k in range(3))
@@ -226,18 +251,37 @@ def run_batch(H, plan, n_bound, ws_fill, dbg_level=-1, exact=True, views=None):
         *_, shape = H.sparse_align_batch(
             dev(np.array([n for _, n in plan], np.int32)), n_bound, k2, k3, fl, [p[0] for p in pyr], [p[1] for p in pyr],
             hcam(cam), dev(np.stack([c["guess"] for c, _ in plan])), dbg_level, ws_fill,
-            outputs=(pose[:batch], cost[:batch], trace[:batch], dbg[:batch] if dbg_level >= 0 else None))
+            outputs=(pose[:batch], cost[:batch], trace[:batch], dbg[:batch] if dbg_level >= 0 else None), mats_out=mats)
     finally:
         H.set_exact_pinv(True)
     pose, cost, dbg, trace = pose.cpu().numpy(), cost.cpu().numpy(), dbg.cpu().numpy(), trace.cpu().numpy()
+    mats = mats.cpu().numpy()
+    assert np.all(mats[batch] == MATS_FILL), "mats_out behind the last sequence"
     assert np.all(pose[batch] == GUARD_F) and cost[batch] == GUARD_F and np.all(dbg[batch] == GUARD_F)
     assert np.all(trace[batch] == GUARD_B)
     used = list(levels_of(cam))
     assert np.all(trace.reshape(batch + 1, 8, -1)[:, [l for l in range(8) if l not in used]] == GUARD_B)
     if dbg_level < 0:
         assert np.all(dbg == GUARD_F)
-    return [dict(pose=pose[b], cost=cost[b], trace=trace[b].view(hip_lib.GN_TRACE_DTYPE), dbg=dbg[b])
+    return [dict(pose=pose[b], cost=cost[b], trace=trace[b].view(hip_lib.GN_TRACE_DTYPE), dbg=dbg[b], mats=mats[b])
             for b in range(batch)], shape
+
+
+def test_mats_out_of_every_case_alone(H):
+    """a batch of one takes the lone shapes: every named case (those without a keypoint, without an active keypoint
+    and without a valid patch included), the composites on both sides of every lone shape switch, both solvers"""
+    stated = AC.results()
+    quiet = set()
+    for exact in (True, False):
+        for c in AC.cases() + ([AC.composite(scene, n) for scene, n in AC.lone_plan()] if exact else []):
+            n = len(c["kps2d"])
+            (got,), _ = run_batch(H, [(c, n)], max(n, 1), FILLS[0], exact=exact)
+            check_mats(got, f"{c['name']} exact {exact}")
+            if exact:
+                same(got["pose"], np.asarray(oracle_align(c)["pose"], F), f"{c['name']}: pose of the batch of one")
+                if c["name"] in stated:
+                    quiet |= stated[c["name"]]["labels"] & {"n_zero", "no_active_keypoint", "rank_deficient", "zero_step"}
+    assert {"n_zero", "no_active_keypoint"} <= quiet, quiet
 
 
 @pytest.mark.parametrize("n_bound", AC.BATCH_BOUNDS)
@@ -255,6 +299,8 @@ def test_batched_shapes(H, n_bound):
         ref = cached_oracle(c["name"], n)
         check_exact(runs[0][b], ref, cam, what)
         check_dbg(runs[0][b]["dbg"], oracle_gradient(c, n, cam, top, c["guess"]), what)
+        for run in runs:
+            check_mats(run[b], what)
         for key in ("pose", "cost", "dbg"):
             same(runs[1][b][key], runs[0][b][key], f"{what}: {key} with the other workspace pattern")
         assert runs[1][b]["trace"].tobytes() == runs[0][b]["trace"].tobytes(), what
@@ -273,6 +319,7 @@ def test_batched_fast_solver(H):
     for b, (c, n) in enumerate(plan):
         ref = cached_oracle(c["name"], n)
         same(got[b]["trace"][top]["initial_cost"], F(ref["trace"][top]["initial_cost"]), f"{c['name']}[:{n}]: first cost")
+        check_mats(got[b], f"{c['name']}[:{n}] with the fast solver")
         whole = n == len(c["kps2d"])
         if whole and c["name"] in held:
             check_fast(got[b]["dbg"], oracle_gradient(c, n, cam, top, c["guess"]), c["name"])
