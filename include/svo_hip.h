@@ -902,6 +902,172 @@ typedef struct svo_scene_src {
 int svo_render_scene(svo_handle *h, int n, const svo_scene_src *src, const svo_scene_camera *cameras,
                      const int64_t *offset, const svo_scene_style *style, uint8_t *pixels);
 
+/* ---- ar: lit meshes over the camera image of many slots in one queued job ------------
+ * The reference's third program is its AR demo (src/ar-app/): the left image of the current frame as the video
+ * surface (opencvimageprovider.cpp:33,59), a camera at the tracked pose (slam.cpp:19-40, AnimatedEntity.qml:12-36)
+ * whose frustum comes from the pinhole intrinsics (AnimatedEntity.qml:15-22), and an entity fixed in the world
+ * (AnimatedEntity.qml:51-59, ObjectEntity.qml: a mesh and a directional light). An ar job is that picture for many
+ * slots: the groups that own a named slot draw the job's mesh instances, flat shaded and depth tested, over the left
+ * level-0 plane of each slot's current frame with two kernel launches each (ar.hip) and deliver one image per slot
+ * into host or device memory; the host writes one svo_ar_segment per named slot.
+ *
+ * The picture is the project's own statement, not GL's rasteriser. All arithmetic is float32 in the order written,
+ * without contraction; integer parts are exact (int64 where said).
+ *   output     one image per named slot, W x H of the ctx (level 0), SVO_PIXEL_RGB8 or SVO_PIXEL_RGBA8. Layout as for
+ *              views and scenes: rows dense, pitch = W * bytes per pixel; image_bytes = H * pitch rounded up to a
+ *              multiple of 256; named slot i of a job at offset = i * image_bytes of dst->pixels; of a slot exactly
+ *              H * pitch bytes are written; the fourth byte of RGBA is 255; a slot whose status is SVO_AR_NONE writes
+ *              only its segment
+ *   background the left level-0 plane of the slot's current frame: the plane a view job with what = FRAMES, plane =
+ *              LEFT, level = 0 shows (under SVO_MEM_DEVICE_BORROW the caller's buffer, as for views). A pixel no
+ *              triangle covers shows (g, g, g)
+ *   camera     svo_ar_camera: V = view[12], the rows of the 3x4 world -> camera matrix, and fx, fy, cx, cy. Of a slot
+ *              (svo_ar_camera_of_pose): with (t, r) = svo_get_pose and R the float `rot` of PoseManager::set_pose
+ *              (Rodrigues in double with the sin / cos of svo_libm.h, rounded to float: the R of the scene's frusta),
+ *              view[4k + j] = R[3j + k] (row k of R transposed) and
+ *              view[4k + 3] = -(((R[k] * t_0) + (R[3 + k] * t_1)) + (R[6 + k] * t_2)); this is the mapping of
+ *              project_keypoints (src/lib/transform_keypoints.cpp:23-45: subtract the translation, rotate by -r) up
+ *              to float rounding; fx, fy, cx, cy are the intrinsics of the slot's rig. The distortion coefficients
+ *              are NOT applied (the tracked plane is rectified): straight edges stay straight
+ *   vertex     (x, y, z) of instance M = model[12]: world w_k = ((M[4k] * x + M[4k+1] * y) + M[4k+2] * z) + M[4k+3];
+ *              camera c_k = ((V[4k] * w_0 + V[4k+1] * w_1) + V[4k+2] * w_2) + V[4k+3] (the scene's T);
+ *              u = (fx * c_0) / c_2 + cx, v = (fy * c_1) / c_2 + cy
+ *   triangle   vertices 0, 1, 2 of a mesh triangle. Dropped when a vertex index is outside [0, n_vertices) (the job
+ *              rejects such a mesh at submit; the stage entry cannot read device memory on the host), when any w_k or
+ *              c_k of a vertex is not finite, when any vertex has c_2 < near (NO clipping against the near plane:
+ *              tessellate objects that come close), or when any |u| or |v| is not < 2^15. Otherwise
+ *              X = (int)floorf(u * 16), Y = (int)floorf(v * 16): 4 sub-pixel bits, |X|, |Y| < 2^19
+ *   coverage   in int64 at the pixel centre P = (16 px + 8, 16 py + 8):
+ *              E_0 = (X2 - X1)(Py - Y1) - (Y2 - Y1)(Px - X1), E_1 the same for the edge 2 -> 0, E_2 for 0 -> 1;
+ *              A = E_0 + E_1 + E_2 = (X1 - X0)(Y2 - Y0) - (Y1 - Y0)(X2 - X0), twice the area, the same at every
+ *              pixel. A == 0: dropped. A < 0: E_0, E_1, E_2 and A are negated (both faces are drawn). The pixel is
+ *              covered iff every E_k >= 0: inclusive, so two triangles that share an edge leave no hole; the key
+ *              settles the pixels both cover
+ *   depth      l_k = (float)E_k / (float)A (int64 -> float, round to nearest even); z = (l_0 * c2_0 + l_1 * c2_1) +
+ *              l_2 * c2_2 with c2_k the c_2 of vertex k: linear on the screen like the scene's lines, NOT
+ *              perspective-correct. z > 0, so its bits order as the values do
+ *   colour     flat per triangle, in world space: e1 = w1 - w0, e2 = w2 - w0,
+ *              n = (e1_y * e2_z - e1_z * e2_y, e1_z * e2_x - e1_x * e2_z, e1_x * e2_y - e1_y * e2_x),
+ *              q = (n_x * n_x + n_y * n_y) + n_z * n_z, d = (n_x * L_x + n_y * L_y) + n_z * L_z with L = style.light,
+ *              t = fabsf(d) / sqrtf(q); s = 0 when q == 0 or t is a NaN, else t when t < 1, else 1;
+ *              shade = ambient + (1 - ambient) * s; channel c' = min(255, (int)(c * shade + 0.5f)) for c = r, g, b
+ *              of the mesh's per-triangle rgb if it has one, else of the instance's rgb. L is used as given (not
+ *              normalised): a unit vector gives Lambert's |cos|
+ *   pixel      every covering triangle offers the 64-bit key  bits(z) << 32 | r' << 16 | g' << 8 | b'; the pixel
+ *              shows r', g', b' of the SMALLEST key. No drawing order enters: two runs give the same bytes.
+ * Not drawn: near clipping, textures, smooth shading, spot lights, transparency, anti-aliasing, lens distortion, the
+ * scene's points and frusta. */
+enum { SVO_AR_OK = 0,
+       SVO_AR_NONE = 1 };             /* an empty slot */
+enum { SVO_AR_MAX_TRIANGLES = 65536 };   /* instanced triangles of one image (slot) at most */
+
+typedef struct svo_ar_camera {        /* 64 bytes */
+    float view[12];                   /* rows of the 3x4 world -> camera matrix                              */
+    float fx, fy, cx, cy;             /* pinhole intrinsics, pixels                                          */
+} svo_ar_camera;                      /* rejected: an entry that is not finite, fx <= 0 or fy <= 0           */
+
+typedef struct svo_ar_mesh {          /* 40 bytes; HOST memory, copied at submit                             */
+    const float   *vertices;          /* n_vertices x (x, y, z)                                              */
+    const int32_t *triangles;         /* n_triangles x 3 vertex indices, each 0 .. n_vertices - 1            */
+    const uint32_t *rgb;              /* n_triangles colours r << 16 | g << 8 | b, or NULL: the instance's   */
+    int32_t n_vertices, n_triangles;  /* >= 0                                                                */
+    int64_t _reserved;                /* 0                                                                   */
+} svo_ar_mesh;
+
+typedef struct svo_ar_instance {      /* 64 bytes */
+    float    model[12];               /* rows of the 3x4 mesh -> world matrix, finite                        */
+    int32_t  mesh;                    /* index into the job's meshes                                         */
+    uint32_t rgb;                     /* r << 16 | g << 8 | b; the top byte 0                                */
+    int32_t  _reserved[2];            /* 0                                                                   */
+} svo_ar_instance;
+
+typedef struct svo_ar_style {         /* 32 bytes; what one job draws; copied at submit                      */
+    int32_t pixel;                    /* SVO_PIXEL_RGB8 or SVO_PIXEL_RGBA8                                   */
+    float   light[3];                 /* L, world, finite (the demo: 0, 0, 1)                                */
+    float   ambient;                  /* 0 .. 1                                                              */
+    float   near;                     /* > 0, finite (the demo: 0.01)                                        */
+    int32_t _reserved[2];             /* 0                                                                   */
+} svo_ar_style;
+
+typedef struct svo_ar_segment {       /* 64 bytes, host, one per named slot                                  */
+    int32_t  seq, run;                /* slot and ordinal of its run (svo_run_info.run)                      */
+    int32_t  frame_id;                /* of the slot's current frame; -1: empty slot                         */
+    uint16_t status;                  /* SVO_AR_*                                                            */
+    uint16_t _pad;
+    int32_t  n_instances;             /* instances the slot shows                                            */
+    int32_t  n_triangles;             /* triangles offered: the sum of their meshes' (0 with SVO_AR_NONE)    */
+    float    time_stamp;              /* of the slot's current frame                                         */
+    int32_t  _pad2;
+    int64_t  offset;                  /* the image is bytes [offset, offset + H * pitch) of dst->pixels      */
+    float    pose[6];                 /* svo_get_pose                                                        */
+} svo_ar_segment;
+
+typedef struct svo_ar_dst {
+    svo_ar_segment *segments;         /* HOST memory always, >= n entries                                    */
+    uint8_t *pixels;                  /* host or device (mem); 4-byte aligned (16-byte aligned: the wide stores) */
+    int64_t capacity;                 /* bytes `pixels` holds                                                */
+} svo_ar_dst;
+
+/* pitch and image_bytes of one image of a job with that style in a ctx of these settings, without a GPU (either may
+ * be NULL). Settings svo_ctx_create rejects, or a style a job rejects: SVO_ERR_INVALID */
+int svo_ar_size(const svo_camera_settings *cam, int width, int height, const svo_ar_style *style, int64_t *pitch,
+                int64_t *image_bytes);
+/* the camera of a slot at `pose` (t, r) with the intrinsics of `cam`, as stated above, without a GPU */
+int svo_ar_camera_of_pose(const float pose[6], const svo_camera_settings *cam, svo_ar_camera *camera);
+/* Queued exactly as svo_submit_export_scenes is (seqs == NULL names every slot in order, n is ignored): the job sees
+ * every frame set, restart, load and pose update submitted before it and none submitted after, only groups that own a
+ * named slot get work, no group waits for another, the slot is not changed (its deferred pose-filter update is
+ * flushed first). first == NULL: every named slot shows instances [0, n_instances) (the demo: one object, seen by
+ * all); else first[n + 1] (seqs == NULL: n = the ctx's slots) gives named slot i the instances [first[i],
+ * first[i + 1]). style, meshes (with everything they point to), instances and first are copied at submit; segments
+ * and pixels stay valid until svo_wait, after which everything is delivered. mem: SVO_MEM_HOST or SVO_MEM_DEVICE, of
+ * `pixels`.
+ * Rejected with SVO_ERR_INVALID and nothing queued: a slot out of range or named twice; a bad mem or pixel (GRAY8);
+ * a light, ambient, near or model entry that is not finite; ambient outside 0 .. 1; near <= 0; an instance colour or
+ * a mesh colour with a top byte; an instance's mesh outside [0, n_meshes); a vertex index outside [0, n_vertices); a
+ * negative count; a `first` that starts below 0, does not ascend or does not end at n_instances; NULL where
+ * data is needed (segments, pixels, meshes with n_meshes > 0, instances with n_instances > 0, the arrays of a mesh
+ * with a positive count); pixels not 4-byte aligned; _reserved != 0; a failed ctx, as in svo_submit_images.
+ * SVO_ERR_CAPACITY: dst->capacity < named slots * image_bytes, or a slot with more than SVO_AR_MAX_TRIANGLES
+ * instanced triangles.
+ * Per job and group one pinned input block (meshes, instance records, image records, the work list of the first
+ * launch) goes up in one copy. The first launch sets every (image, triangle) up once into a screen record (64 bytes)
+ * of a device block; the second walks the records per tile. The input block, the record block and, in host mode, a
+ * staging block for the images are made by the group's first ar job, replaced when outgrown and counted in
+ * svo_ctx_get_memory (svo_memory.device_bytes). Host mode copies each run of consecutive named slots out in one
+ * piece; device mode writes in place. A ctx that never asks for an ar picture allocates, launches and copies nothing
+ * more. */
+int svo_submit_export_ar(svo_ctx *ctx, const int *seqs, int n, const svo_ar_style *style, const svo_ar_mesh *meshes,
+                         int n_meshes, const svo_ar_instance *instances, const int *first, int n_instances,
+                         const svo_ar_dst *dst, int mem);
+int svo_export_ar(svo_ctx *ctx, const int *seqs, int n, const svo_ar_style *style, const svo_ar_mesh *meshes,
+                  int n_meshes, const svo_ar_instance *instances, const int *first, int n_instances,
+                  const svo_ar_dst *dst, int mem);   /* submit + wait */
+/* stage entry of the kernels: n images in the tracker's two launches (the second chunked when the diagnostic
+ * SVO_AR_TABLE_TILES bounds the tile table). src[i].image: the background plane (device memory, any base address,
+ * stride >= width, 1 .. 32768 pixels a side; its width x height is the output's). src[i].draws: HOST array of
+ * n_draws instanced meshes whose vertices, triangles and rgb (or NULL) are DEVICE memory, 4-byte aligned; a triangle
+ * with a vertex index out of range is dropped and the top byte of a colour in `rgb` is ignored. At most SVO_AR_MAX_TRIANGLES triangles per image (SVO_ERR_CAPACITY).
+ * Image i is seen through cameras[i] and goes to pixels + offset[i] (host array, >= 0, multiples of 4; pixels:
+ * device, 4-byte aligned), rows dense. Exactly the images' bytes are written. Complete on return. */
+typedef struct svo_ar_draw {          /* 88 bytes */
+    float    model[12];
+    const float   *vertices;
+    const int32_t *triangles;
+    const uint32_t *rgb;
+    int32_t  n_vertices, n_triangles;
+    uint32_t rgb_all;                 /* the instance's colour                                               */
+    int32_t  _reserved;               /* 0                                                                   */
+} svo_ar_draw;
+typedef struct svo_ar_src {
+    svo_image image;
+    const svo_ar_draw *draws;
+    int32_t n_draws;
+    int32_t _reserved;                /* 0                                                                   */
+} svo_ar_src;
+int svo_render_ar(svo_handle *h, int n, const svo_ar_src *src, const svo_ar_camera *cameras, const int64_t *offset,
+                  const svo_ar_style *style, uint8_t *pixels);
+
 /* ---- snapshots: the sequence state of a slot saved, loaded, moved between ctxs ------------
  * The reference has no checkpoint or resume (a StereoSlam lives and dies with its process). A snapshot is
  * everything the next frame of a slot depends on and everything its getters return, so that a sequence saved

@@ -1,10 +1,11 @@
 // svo_capi_tables.hip — the stage-level entries that take many images, sets or segments and build a table for one
-// launch: rectification and remap, frame ingest, keypoint and map export, the viewer's images and scenes, segment
+// launch: rectification and remap, frame ingest, keypoint and map export, the viewer's images and scenes, the AR picture, segment
 // copies, the pose filter. Every entry keeps a grow-only workspace of its own in the handle (svo_handle.hpp).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <climits>
+#include <cmath>
 #include <cstring>
 #include <vector>
 
@@ -349,6 +350,86 @@ extern "C" int svo_render_scene(svo_handle* h, int n, const svo_scene_src* src, 
     const SceneParams params = scene_params(*style);
     return launch_tiles(h, tiles, reinterpret_cast<SceneTile*>(h->scene_ws.ptr.get() + sets_bytes + images_bytes), chunk,
                         [&](const SceneTile* d, int m, hipStream_t s) { launch_scene(d, m, d_images, params, s); });
+}
+
+extern "C" int svo_render_ar(svo_handle* h, int n, const svo_ar_src* src, const svo_ar_camera* cameras, const int64_t* offset,
+                             const svo_ar_style* style, uint8_t* pixels) {
+    CHECK_H(h);
+    if (n < 0 || (n > 0 && (!src || !cameras || !offset))) return svo_set_error(SVO_ERR_INVALID, "svo_render_ar: bad arguments");
+    if (const int rc = ar_check_style(style, "svo_render_ar")) return rc;
+    if (!pixels || ((uintptr_t)pixels & 3)) return svo_set_error(SVO_ERR_INVALID, "svo_render_ar: pixels is NULL or not 4-byte aligned");
+    std::vector<svo_ar_draw> draws;
+    std::vector<ArImage> images;
+    std::vector<size_t> draw0, rec0;
+    std::vector<ArSetup> setup;
+    std::vector<ArTile> tiles;
+    size_t records = 0;
+    for (int i = 0; i < n; i++) {
+        const svo_ar_src& s = src[i];
+        const svo_image& im = s.image;
+        if (!im.data || im.width < 1 || im.height < 1 || im.stride < im.width || im.width > (1 << 15) || im.height > (1 << 15))
+            return svo_set_error(SVO_ERR_INVALID, "svo_render_ar: image %d: a device plane of 1 .. 32768 pixels a side, stride >= width", i);
+        if (offset[i] < 0 || (offset[i] & 3)) return svo_set_error(SVO_ERR_INVALID, "svo_render_ar: image %d: offset must be >= 0 and a multiple of 4", i);
+        if (const int rc = ar_check_camera(&cameras[i], "svo_render_ar", i)) return rc;
+        if (s.n_draws < 0 || (s.n_draws > 0 && !s.draws) || s._reserved != 0)
+            return svo_set_error(SVO_ERR_INVALID, "svo_render_ar: image %d: draws missing, or _reserved is not 0", i);
+        int64_t tri = 0;
+        for (int j = 0; j < s.n_draws; j++) {
+            const svo_ar_draw& d = s.draws[j];
+            bool finite = true;
+            for (float v : d.model) finite = finite && std::isfinite(v);
+            if (!finite || d.n_vertices < 0 || d.n_triangles < 0 || (d.n_triangles > 0 && (!d.triangles || (d.n_vertices > 0 && !d.vertices))) ||
+                (((uintptr_t)d.vertices | (uintptr_t)d.triangles | (uintptr_t)d.rgb) & 3) || (d.rgb_all >> 24) || d._reserved != 0)
+                return svo_set_error(SVO_ERR_INVALID, "svo_render_ar: image %d: draw %d: a model entry that is not finite, a negative count, arrays missing or not 4-byte aligned, a colour with a top byte, or _reserved is not 0", i, j);
+            tri += d.n_triangles;
+        }
+        if (tri > SVO_AR_MAX_TRIANGLES)
+            return svo_set_error(SVO_ERR_CAPACITY, "svo_render_ar: image %d: %lld triangles, at most %d", i, (long long)tri, (int)SVO_AR_MAX_TRIANGLES);
+        draw0.push_back(draws.size());
+        rec0.push_back(records);
+        draws.insert(draws.end(), s.draws, s.draws + s.n_draws);
+        ArImage a;
+        a.cam = cameras[i];
+        a.src = im.data; a.dst = pixels + offset[i];
+        a.draws = nullptr; a.records = nullptr;            // (placed below, once the block is there)
+        a.src_stride = im.stride; a.w = im.width; a.h = im.height;
+        a.n_records = ar_work(i, im.width, im.height, s.draws, s.n_draws, setup, tiles);
+        records += (size_t)a.n_records;
+        images.push_back(a);
+    }
+    if (tiles.empty()) return SVO_OK;
+    // (SVO_AR_TABLE_TILES: a smaller table, so that tests reach the chunked launches)
+    const size_t chunk = table_tiles("SVO_AR_TABLE_TILES", std::min<size_t>(tiles.size(), (size_t)INT_MAX));
+    auto pad = [](size_t b) { return (b + 15) / 16 * 16; };
+    const size_t draws_bytes = pad(sizeof(svo_ar_draw) * draws.size()), images_bytes = pad(sizeof(ArImage) * images.size());
+    const size_t setup_bytes = pad(sizeof(ArSetup) * setup.size()), records_bytes = sizeof(ArRecord) * records;
+    const size_t bytes = draws_bytes + images_bytes + setup_bytes + records_bytes + sizeof(ArTile) * chunk;
+    if (const int rc = h->ar_ws.reserve(bytes, h->stream)) return rc;
+    uint8_t* base = h->ar_ws.ptr.get();
+    const svo_ar_draw* d_draws = reinterpret_cast<const svo_ar_draw*>(base);
+    const ArImage* d_images = reinterpret_cast<const ArImage*>(base + draws_bytes);
+    const ArSetup* d_setup = reinterpret_cast<const ArSetup*>(base + draws_bytes + images_bytes);
+    ArRecord* d_records = reinterpret_cast<ArRecord*>(base + draws_bytes + images_bytes + setup_bytes);
+    for (size_t i = 0; i < images.size(); i++) { images[i].draws = d_draws + draw0[i]; images[i].records = d_records + rec0[i]; }
+    const ArParams params = ar_params(*style);
+    int rc = SVO_OK;
+    auto up = [&](const void* dst, const void* from, size_t b) {
+        if (rc == SVO_OK && b > 0 && hipMemcpyAsync(const_cast<void*>(dst), from, b, hipMemcpyHostToDevice, h->stream) != hipSuccess)
+            rc = svo_set_error(SVO_ERR_HIP, "svo_render_ar: an upload failed");
+    };
+    up(d_draws, draws.data(), sizeof(svo_ar_draw) * draws.size());
+    up(d_images, images.data(), sizeof(ArImage) * images.size());
+    up(d_setup, setup.data(), sizeof(ArSetup) * setup.size());
+    if (rc == SVO_OK) {
+        launch_ar_setup(d_setup, (int)setup.size(), d_images, params, h->stream);
+        if (hipGetLastError() != hipSuccess) rc = svo_set_error(SVO_ERR_HIP, "svo_render_ar: the first launch failed");
+    }
+    if (rc != SVO_OK) {                                    // (the uploads read host memory of this call)
+        (void)hipStreamSynchronize(h->stream);
+        return rc;
+    }
+    return launch_tiles(h, tiles, reinterpret_cast<ArTile*>(base + draws_bytes + images_bytes + setup_bytes + records_bytes), chunk,
+                        [&](const ArTile* d, int m, hipStream_t s) { launch_ar(d, m, d_images, params, s); });
 }
 
 extern "C" int svo_copy_segments(svo_handle* h, int n, const svo_copy_segment* segs) {

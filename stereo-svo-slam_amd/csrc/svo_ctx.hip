@@ -31,7 +31,7 @@
 // single-workgroup-per-sequence alignment kernel of one group overlaps the window kernels of
 // the other. svo_submit_images() queues a frame set on every group and returns;
 // svo_wait() drains the queues. svo_new_images() = submit + wait. Restarts (svo_ctx_restart_sequences),
-// exports (svo_submit_export, svo_submit_export_map, svo_submit_export_views, svo_submit_export_scenes), saves and loads (svo_submit_save / svo_submit_load) and pose-filter updates
+// exports (svo_submit_export, svo_submit_export_map, svo_submit_export_views, svo_submit_export_scenes, svo_submit_export_ar), saves and loads (svo_submit_save / svo_submit_load) and pose-filter updates
 // (svo_submit_pose_updates) are entries of the same queues, so they are ordered with the frame sets.
 struct svo_ctx {
     // the group's share of an svo_submit_export: its named slots (indices in the group) in named order, the
@@ -68,6 +68,15 @@ struct svo_ctx {
         svo_scene_style style{};
         svo_scene_dst dst{};
     };
+    // the group's share of an svo_submit_export_ar: its named slots (indices in the group) in named order, the
+    // instances [inst0, inst1) of the job each one shows, the segment (and image) of the job each one fills, and
+    // the job's copied arrays, which the groups share
+    struct ArExport {
+        int mem = 0;
+        std::vector<int> seqs, seg, inst0, inst1;
+        std::shared_ptr<const ArJob> job;
+        svo_ar_dst dst{};
+    };
     // the group's share of an svo_submit_save (snaps) or svo_submit_load (loads): its named slots, indices in the group
     struct Snapshots {
         int mem = 0;
@@ -85,7 +94,7 @@ struct svo_ctx {
     // one entry of a group's queue: a frame set, or (restart non-empty) the end of some of its sequences, or
     // (exp.seqs non-empty) an export, or (snap.seqs / snap.loads non-empty) a save / a load, or (pose.seqs non-empty)
     // pose-filter updates, or (map.seqs non-empty) a map export, or (view.seqs non-empty) a view job, or (scene.seqs
-    // non-empty) a scene job, or (assign non-empty) a rig assignment, or (trim non-empty) a trim of keyframes
+    // non-empty) a scene job, or (ar.seqs non-empty) an ar job, or (assign non-empty) a rig assignment, or (trim non-empty) a trim of keyframes
     struct Job {
         std::vector<const uint8_t*> left, right;
         std::vector<float> ts;
@@ -100,6 +109,7 @@ struct svo_ctx {
         MapExport map;
         ViewExport view;
         SceneExport scene;
+        ArExport ar;
     };
     struct Worker {
         Group g;
@@ -154,7 +164,10 @@ void worker_run_job(svo_ctx::Worker& w, const svo_ctx::Job& job) {
     const svo_ctx::MapExport& mp = job.map;
     const svo_ctx::ViewExport& vw = job.view;
     const svo_ctx::SceneExport& sc = job.scene;
-    const int rc = !sc.seqs.empty()
+    const svo_ctx::ArExport& ar = job.ar;
+    const int rc = !ar.seqs.empty()
+                       ? grp_export_ar(w.g.get(), ar.mem, ar.seqs.data(), ar.seg.data(), ar.inst0.data(), ar.inst1.data(), (int)ar.seqs.size(), w.first, ar.job.get(), &ar.dst)
+                   : !sc.seqs.empty()
                        ? grp_export_scenes(w.g.get(), sc.mem, sc.seqs.data(), sc.seg.data(), (int)sc.seqs.size(), w.first, &sc.style, sc.cameras.data(), &sc.dst)
                    : !vw.seqs.empty()
                        ? grp_export_views(w.g.get(), vw.what, vw.mem, vw.seqs.data(), vw.seg.data(), (int)vw.seqs.size(), w.first, &vw.style, &vw.dst)
@@ -598,6 +611,86 @@ extern "C" int svo_submit_export_scenes(svo_ctx* c, const int* seqs, int n, cons
 extern "C" int svo_export_scenes(svo_ctx* c, const int* seqs, int n, const svo_scene_style* style,
                                  const svo_scene_camera* cameras, const svo_scene_dst* dst, int mem) {
     const int rc = svo_submit_export_scenes(c, seqs, n, style, cameras, dst, mem);
+    return rc ? rc : svo_wait(c);
+}
+
+extern "C" int svo_submit_export_ar(svo_ctx* c, const int* seqs, int n, const svo_ar_style* style, const svo_ar_mesh* meshes,
+                                    int n_meshes, const svo_ar_instance* instances, const int* first, int n_instances,
+                                    const svo_ar_dst* dst, int mem) {
+    const char* who = "svo_submit_export_ar";
+    if (!c || !dst || !dst->segments || (mem != SVO_MEM_HOST && mem != SVO_MEM_DEVICE) || (seqs && n < 0) || n_meshes < 0 ||
+        n_instances < 0 || (n_meshes > 0 && !meshes) || (n_instances > 0 && !instances))
+        return svo_set_error(SVO_ERR_INVALID, "%s: bad arguments (mem %d, %d meshes, %d instances)", who, mem, n_meshes, n_instances);
+    if (const int rc = svo::ar_check_style(style, who)) return rc;
+    if (!dst->pixels || ((uintptr_t)dst->pixels & 3)) return svo_set_error(SVO_ERR_INVALID, "%s: pixels is NULL or not 4-byte aligned", who);
+    if (!seqs) n = c->B;
+    std::vector<char> named(c->B, 0);
+    for (int i = 0; i < n; i++) {
+        const int s = seqs ? seqs[i] : i;
+        if (s < 0 || s >= c->B || named[s]) return svo_set_error(SVO_ERR_INVALID, "%s: sequence %d is out of range or named twice", who, s);
+        named[s] = 1;
+    }
+    if (first) {
+        if (first[0] < 0 || first[n] != n_instances)
+            return svo_set_error(SVO_ERR_INVALID, "%s: first starts at %d and ends at %d, not at >= 0 and %d", who, first[0], first[n], n_instances);
+        for (int i = 0; i < n; i++)
+            if (first[i + 1] < first[i]) return svo_set_error(SVO_ERR_INVALID, "%s: first does not ascend at %d", who, i);
+    }
+    auto job = std::make_shared<ArJob>();
+    job->style = *style;
+    for (int m = 0; m < n_meshes; m++) {
+        const svo_ar_mesh& me = meshes[m];
+        if (me.n_vertices < 0 || me.n_triangles < 0 || me._reserved != 0 || (me.n_vertices > 0 && !me.vertices) || (me.n_triangles > 0 && !me.triangles))
+            return svo_set_error(SVO_ERR_INVALID, "%s: mesh %d: a negative count, a missing array, or _reserved is not 0", who, m);
+        for (int64_t k = 0; k < (int64_t)me.n_triangles * 3; k++)
+            if (me.triangles[k] < 0 || me.triangles[k] >= me.n_vertices)
+                return svo_set_error(SVO_ERR_INVALID, "%s: mesh %d: triangle %lld names vertex %d of %d", who, m, (long long)(k / 3), me.triangles[k], me.n_vertices);
+        for (int k = 0; me.rgb && k < me.n_triangles; k++)
+            if (me.rgb[k] >> 24) return svo_set_error(SVO_ERR_INVALID, "%s: mesh %d: a colour is r << 16 | g << 8 | b", who, m);
+        job->meshes.push_back(ArJob::Mesh{job->vertices.size() / 3, job->triangles.size() / 3, job->rgb.size(), me.n_vertices, me.n_triangles, me.rgb != nullptr});
+        job->vertices.insert(job->vertices.end(), me.vertices, me.vertices + (size_t)me.n_vertices * 3);
+        job->triangles.insert(job->triangles.end(), me.triangles, me.triangles + (size_t)me.n_triangles * 3);
+        if (me.rgb) job->rgb.insert(job->rgb.end(), me.rgb, me.rgb + me.n_triangles);
+    }
+    std::vector<int64_t> tri_before((size_t)n_instances + 1, 0);     // triangles of the instances before each
+    for (int k = 0; k < n_instances; k++) {
+        const svo_ar_instance& in = instances[k];
+        bool finite = true;
+        for (float v : in.model) finite = finite && std::isfinite(v);
+        if (!finite || in.mesh < 0 || in.mesh >= n_meshes || (in.rgb >> 24) || in._reserved[0] != 0 || in._reserved[1] != 0)
+            return svo_set_error(SVO_ERR_INVALID, "%s: instance %d: a model entry that is not finite, mesh %d of %d, a colour with a top byte, or a _reserved that is not 0", who, k, in.mesh, n_meshes);
+        tri_before[(size_t)k + 1] = tri_before[(size_t)k] + meshes[in.mesh].n_triangles;
+    }
+    job->instances.assign(instances, instances + n_instances);
+    for (int i = 0; i < n; i++) {
+        const int64_t tri = first ? tri_before[(size_t)first[i + 1]] - tri_before[(size_t)first[i]] : tri_before[(size_t)n_instances];
+        if (tri > SVO_AR_MAX_TRIANGLES)
+            return svo_set_error(SVO_ERR_CAPACITY, "%s: named slot %d shows %lld triangles, at most %d", who, i, (long long)tri, (int)SVO_AR_MAX_TRIANGLES);
+    }
+    const int64_t image_bytes = grp_ar_bytes(c->workers[0]->g.get(), style);   // (every group has the same size)
+    if (dst->capacity < n * image_bytes)
+        return svo_set_error(SVO_ERR_CAPACITY, "%s: %d slots need %lld bytes, capacity %lld", who, n, (long long)(n * image_bytes), (long long)dst->capacity);
+    if (c->failed.load()) return reject_failed(c, who);
+    for (auto& wp : c->workers) {
+        svo_ctx::Worker& w = *wp;
+        svo_ctx::Job jb;
+        svo_ctx::ArExport& e = jb.ar;
+        for (int i = 0; i < n; i++) {
+            const int s = seqs ? seqs[i] : i;
+            if (s < w.first || s >= w.first + w.count) continue;
+            e.seqs.push_back(s - w.first); e.seg.push_back(i);
+            e.inst0.push_back(first ? first[i] : 0); e.inst1.push_back(first ? first[i + 1] : n_instances);
+        }
+        if (e.seqs.empty()) continue;
+        e.mem = mem; e.job = job; e.dst = *dst;
+        worker_submit(w, std::move(jb));
+    }
+    return SVO_OK;
+}
+
+extern "C" int svo_export_ar(svo_ctx* c, const int* seqs, int n, const svo_ar_style* style, const svo_ar_mesh* meshes, int n_meshes,
+                             const svo_ar_instance* instances, const int* first, int n_instances, const svo_ar_dst* dst, int mem) {
+    const int rc = svo_submit_export_ar(c, seqs, n, style, meshes, n_meshes, instances, first, n_instances, dst, mem);
     return rc ? rc : svo_wait(c);
 }
 

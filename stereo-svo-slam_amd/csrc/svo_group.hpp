@@ -1,7 +1,7 @@
 // svo_group.hpp — one group of sequences as svo_ctx.hip drives it: the opaque interface of svo_group.hip (creation,
 // settings, restarts), svo_group_step.hip (grp_new_images), svo_group_export.hip (grp_export, grp_capacity),
 // svo_group_map.hip (grp_export_map, grp_map_size), svo_group_view.hip (grp_export_views, grp_view_bytes),
-// svo_group_scene.hip (grp_export_scenes, grp_scene_bytes),
+// svo_group_scene.hip (grp_export_scenes, grp_scene_bytes), svo_group_ar.hip (grp_export_ar, grp_ar_bytes),
 // svo_group_snapshot.hip (grp_check_snapshot, grp_save, grp_load, grp_snapshot_size) and svo_group_pose.hip
 // (grp_pose_updates).
 #pragma once
@@ -68,6 +68,25 @@ int64_t grp_view_bytes(const svo_group* g, const svo_view_style* style);
 int grp_export_scenes(svo_group* g, int mem, const int* seqs, const int* seg, int n, int seq0, const svo_scene_style* style,
                       const svo_scene_camera* cameras, const svo_scene_dst* dst);
 int64_t grp_scene_bytes(const svo_scene_style* style);   // the image_bytes of a checked style
+// What svo_submit_export_ar copied of its caller's arrays, checked; the jobs of all groups share one (read only).
+// The meshes lie back to back: mesh m has vertices [v0, v0 + n_vertices) (3 floats each), triangles [t0, t0 +
+// n_triangles) (3 indices each) and, with has_rgb, the colours [c0, c0 + n_triangles).
+struct ArJob {
+    svo_ar_style style{};
+    struct Mesh { size_t v0, t0, c0; int n_vertices, n_triangles; bool has_rgb; };
+    std::vector<Mesh> meshes;
+    std::vector<float> vertices;
+    std::vector<int32_t> triangles;
+    std::vector<uint32_t> rgb;
+    std::vector<svo_ar_instance> instances;
+};
+// One group's share of svo_submit_export_ar (svo_group_ar.hip), between two steps of the group, on the thread that
+// drives it: slot seqs[i] (index in the group; ctx slot seq0 + seqs[i]) shows the instances [inst0[i], inst1[i]) of
+// `job`, fills dst->segments[seg[i]] and its image goes to byte seg[i] * image_bytes of dst->pixels (host or device
+// memory: mem). Delivered on return. A failed group rejects it.
+int grp_export_ar(svo_group* g, int mem, const int* seqs, const int* seg, const int* inst0, const int* inst1, int n, int seq0,
+                  const ArJob* job, const svo_ar_dst* dst);
+int64_t grp_ar_bytes(const svo_group* g, const svo_ar_style* style);   // the image_bytes of a checked style
 // what svo_map_size reports of a slot (the queues have drained)
 void grp_map_size(const svo_group* g, int seq, int from_keyframe, int* keyframes, int64_t* points_bound, int* from = nullptr);
 // Snapshots (svo_submit_save / svo_submit_load). grp_check_snapshot: everything svo_submit_load checks of one

@@ -1,0 +1,202 @@
+// svo_group_ar.hip — the ar job of a sequence group (svo_submit_export_ar): the AR demo's picture of its named slots
+// (the job's mesh instances, lit and depth tested, over the left level-0 plane of each slot's current frame, seen
+// from the slot's pose through its rig's intrinsics), rendered by ar.hip's two kernels, as segments and pixels; and
+// the host-only entry points svo_ar_size and svo_ar_camera_of_pose. The state is svo_group_state.hpp.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+
+#include "svo_group_state.hpp"
+
+using namespace svo;
+
+namespace {
+
+// the input block (device and its pinned mirror) holds `bytes`; a grown one replaces the old
+int reserve_ar_in(svo_group* c, size_t bytes) {
+    if (bytes <= c->ar_in_bytes) return SVO_OK;
+    HIP_TRY(hipStreamSynchronize(c->stream.get()));
+    bytes = align_up(bytes, 4096);
+    if (c->d_ar_in) dev_release(c, c->d_ar_in, c->ar_in_bytes);
+    c->d_ar_in = nullptr; c->ar_in_bytes = 0;
+    c->ar_in_host.reset();
+    HIP_TRY(pinned_malloc(c->ar_in_host, bytes));
+    if (const int rc = dev_alloc(c, &c->d_ar_in, bytes, false)) return rc;
+    c->ar_in_bytes = bytes;
+    return SVO_OK;
+}
+
+// *block (of *have bytes) holds `bytes`: the screen records, or the host-mode staging block
+int reserve_ar_block(svo_group* c, uint8_t** block, size_t* have, size_t bytes) {
+    if (bytes <= *have) return SVO_OK;
+    HIP_TRY(hipStreamSynchronize(c->stream.get()));
+    if (*block) dev_release(c, *block, *have);
+    *block = nullptr; *have = 0;
+    if (const int rc = dev_alloc(c, block, bytes, false)) return rc;
+    *have = bytes;
+    return SVO_OK;
+}
+
+size_t pad16(size_t b) { return (b + 15) / 16 * 16; }
+
+}  // namespace
+
+extern "C" int svo_ar_size(const svo_camera_settings* cam, int width, int height, const svo_ar_style* style, int64_t* pitch,
+                           int64_t* image_bytes) {
+    if (const int rc = check_settings(cam, width, height, 1)) return rc;
+    if (const int rc = ar_check_style(style, "svo_ar_size")) return rc;
+    ar_shape(*style, width, height, pitch, image_bytes);
+    return SVO_OK;
+}
+
+extern "C" int svo_ar_camera_of_pose(const float pose[6], const svo_camera_settings* cam, svo_ar_camera* camera) {
+    if (!pose || !cam || !camera) return svo_set_error(SVO_ERR_INVALID, "svo_ar_camera_of_pose: bad arguments");
+    double Rd[9];
+    rodrigues_d(pose + 3, Rd);
+    float R[9];
+    for (int k = 0; k < 9; k++) R[k] = (float)Rd[k];
+    for (int k = 0; k < 3; k++) {
+        for (int j = 0; j < 3; j++) camera->view[4 * k + j] = R[3 * j + k];
+        camera->view[4 * k + 3] = -(((R[k] * pose[0]) + (R[3 + k] * pose[1])) + (R[6 + k] * pose[2]));
+    }
+    camera->fx = cam->fx; camera->fy = cam->fy; camera->cx = cam->cx; camera->cy = cam->cy;
+    return SVO_OK;
+}
+
+int64_t grp_ar_bytes(const svo_group* c, const svo_ar_style* style) {
+    int64_t bytes = 0;
+    ar_shape(*style, c->width, c->height, nullptr, &bytes);
+    return bytes;
+}
+
+// The named slots of the group as segments and images (svo_submit_export_ar); slot seqs[i] shows the job's instances
+// [inst0[i], inst1[i]). Named slot seg[i] of the job goes to byte seg[i] * image_bytes of the caller's pixels; in host
+// mode the group renders its i-th named slot at byte i * image_bytes of its staging block and copies every run of
+// slots that are consecutive in both (and delivered) out as the views do. The input block holds the job's meshes
+// once (vertices | triangles | colours), then a draw per (slot, instance), the image records and the work list of
+// the first launch; it goes up in one copy. The tile table goes through the group's argument blocks
+// (group_tile_table), one launch unless it outgrows them.
+int grp_export_ar(svo_group* c, int mem, const int* seqs, const int* seg, const int* inst0, const int* inst1, int n, int seq0,
+                  const ArJob* job, const svo_ar_dst* dst) {
+    if (c->failed)
+        return svo_set_error(SVO_ERR_INVALID, "svo_submit_export_ar: an earlier frame of this ctx failed; create a new ctx");
+    HIP_TRY(hipSetDevice(c->device));
+    flush_pending(c);
+    hipStream_t st = c->stream.get();
+    const bool host = mem == SVO_MEM_HOST;
+    const int cols = c->width, rows = c->height;
+    int64_t pitch, image_bytes;
+    ar_shape(job->style, cols, rows, &pitch, &image_bytes);
+    const int64_t used = (int64_t)rows * pitch;          // bytes of an image
+    std::vector<svo_ar_draw> draws;
+    std::vector<int> draw_mesh;                          // the job's mesh of each draw
+    std::vector<ArImage> images;
+    std::vector<ArSetup> setup;
+    std::vector<ArTile> tiles;
+    std::vector<char> shown((size_t)n, 0);
+    struct Placed { int i; size_t draw0, rec0; };        // a delivered slot: its first draw and record of the job
+    std::vector<Placed> placed;
+    size_t records = 0;
+    for (int i = 0; i < n; i++) {
+        const Seq& q = c->seqs[seqs[i]];
+        svo_ar_segment& e = clear(dst->segments[seg[i]]);
+        e.seq = seq0 + seqs[i]; e.run = q.run; e.frame_id = q.frame_id; e.status = SVO_AR_NONE;
+        e.n_instances = inst1[i] - inst0[i];
+        e.time_stamp = (float)q.ts; e.offset = (int64_t)seg[i] * image_bytes;
+        std::memcpy(e.pose, q.pose, sizeof(e.pose));
+        if (q.frame_id < 0 || !q.cur_set) continue;
+        const ImgView& src = q.cur_set->left[0];
+        if (src.w != cols || src.h != rows)
+            return svo_set_error(SVO_ERR_INVALID, "svo_submit_export_ar: level 0 is %d x %d, not %d x %d", src.w, src.h, cols, rows);
+        e.status = SVO_AR_OK;
+        shown[i] = 1;
+        placed.push_back({i, draws.size(), records});
+        for (int k = inst0[i]; k < inst1[i]; k++) {
+            const svo_ar_instance& in = job->instances[(size_t)k];
+            const ArJob::Mesh& m = job->meshes[(size_t)in.mesh];
+            svo_ar_draw d;
+            std::memcpy(d.model, in.model, sizeof(d.model));
+            d.vertices = nullptr; d.triangles = nullptr; d.rgb = nullptr;   // (placed below, once the block is there)
+            d.n_vertices = m.n_vertices; d.n_triangles = m.n_triangles;
+            d.rgb_all = in.rgb; d._reserved = 0;
+            draws.push_back(d);
+            draw_mesh.push_back(in.mesh);
+        }
+        ArImage im;
+        svo_ar_camera_of_pose(q.pose, &q.cam, &im.cam);
+        im.src = src.data; im.dst = nullptr; im.draws = nullptr; im.records = nullptr;   // (placed below, once the blocks are there)
+        im.src_stride = src.stride; im.w = cols; im.h = rows;
+        const size_t d0 = placed.back().draw0;
+        im.n_records = ar_work((int)images.size(), cols, rows, draws.data() + d0, (int)(draws.size() - d0), setup, tiles);
+        e.n_triangles = im.n_records;
+        records += (size_t)im.n_records;
+        images.push_back(im);
+    }
+    if (!images.empty()) {
+        if (host)
+            if (const int rc = reserve_ar_block(c, &c->d_ar, &c->ar_bytes, (size_t)n * (size_t)image_bytes)) return rc;
+        if (const int rc = reserve_ar_block(c, &c->d_ar_rec, &c->ar_rec_bytes, sizeof(ArRecord) * records)) return rc;
+        // the input block: vertices | triangles | colours | draws | images | work list
+        const size_t v_bytes = pad16(sizeof(float) * job->vertices.size()), t_bytes = pad16(sizeof(int32_t) * job->triangles.size());
+        const size_t c_bytes = pad16(sizeof(uint32_t) * job->rgb.size()), d_bytes = pad16(sizeof(svo_ar_draw) * draws.size());
+        const size_t i_bytes = pad16(sizeof(ArImage) * images.size()), s_bytes = sizeof(ArSetup) * setup.size();
+        const size_t in_bytes = v_bytes + t_bytes + c_bytes + d_bytes + i_bytes + s_bytes;
+        if (const int rc = reserve_ar_in(c, in_bytes)) return rc;
+        uint8_t* dev = c->d_ar_in;
+        const float* d_vertices = reinterpret_cast<const float*>(dev);
+        const int32_t* d_triangles = reinterpret_cast<const int32_t*>(dev + v_bytes);
+        const uint32_t* d_rgb = reinterpret_cast<const uint32_t*>(dev + v_bytes + t_bytes);
+        const svo_ar_draw* d_draws = reinterpret_cast<const svo_ar_draw*>(dev + v_bytes + t_bytes + c_bytes);
+        const ArImage* d_images = reinterpret_cast<const ArImage*>(dev + v_bytes + t_bytes + c_bytes + d_bytes);
+        const ArSetup* d_setup = reinterpret_cast<const ArSetup*>(dev + v_bytes + t_bytes + c_bytes + d_bytes + i_bytes);
+        for (size_t k = 0; k < draws.size(); k++) {
+            const ArJob::Mesh& m = job->meshes[(size_t)draw_mesh[k]];
+            draws[k].vertices = d_vertices + m.v0 * 3;
+            draws[k].triangles = d_triangles + m.t0 * 3;
+            if (m.has_rgb) draws[k].rgb = d_rgb + m.c0;
+        }
+        for (size_t k = 0; k < placed.size(); k++) {
+            const Placed& pl = placed[k];
+            images[k].dst = host ? c->d_ar + (int64_t)pl.i * image_bytes : dst->pixels + (int64_t)seg[pl.i] * image_bytes;
+            images[k].draws = d_draws + pl.draw0;
+            images[k].records = reinterpret_cast<ArRecord*>(c->d_ar_rec) + pl.rec0;
+        }
+        uint8_t* h = c->ar_in_host.get();
+        auto put = [&](size_t at, const void* from, size_t b) { if (b) std::memcpy(h + at, from, b); };
+        put(0, job->vertices.data(), sizeof(float) * job->vertices.size());
+        put(v_bytes, job->triangles.data(), sizeof(int32_t) * job->triangles.size());
+        put(v_bytes + t_bytes, job->rgb.data(), sizeof(uint32_t) * job->rgb.size());
+        put(v_bytes + t_bytes + c_bytes, draws.data(), sizeof(svo_ar_draw) * draws.size());
+        put(v_bytes + t_bytes + c_bytes + d_bytes, images.data(), sizeof(ArImage) * images.size());
+        put(v_bytes + t_bytes + c_bytes + d_bytes + i_bytes, setup.data(), s_bytes);
+        HIP_TRY(hipMemcpyAsync(dev, h, in_bytes, hipMemcpyHostToDevice, st));
+        const ArParams params = ar_params(job->style);
+        launch_ar_setup(d_setup, (int)setup.size(), d_images, params, st);
+        HIP_TRY(hipGetLastError());
+        // (SVO_AR_TABLE_TILES: a smaller table, so that tests reach the chunked launches)
+        auto table = group_tile_table<ArTile>(c, "SVO_AR_TABLE_TILES", [&](const ArTile* d, int m, hipStream_t s) {
+            launch_ar(d, m, d_images, params, s);
+        });
+        for (const ArTile& t : tiles)
+            if (const int rc = table.add(t)) return rc;
+        if (const int rc = table.launch(false)) return rc;
+    }
+    for (int i = 0; host && i < n;) {
+        if (!shown[i]) { i++; continue; }
+        int j = i + 1;
+        while (j < n && shown[j] && seg[j] == seg[j - 1] + 1) j++;
+        uint8_t* to = dst->pixels + (int64_t)seg[i] * image_bytes;
+        const uint8_t* from = c->d_ar + (int64_t)i * image_bytes;
+        if (used == image_bytes)
+            HIP_TRY(hipMemcpyAsync(to, from, (size_t)((j - i) * image_bytes), hipMemcpyDeviceToHost, st));
+        else if (j - i == 1)
+            HIP_TRY(hipMemcpyAsync(to, from, (size_t)used, hipMemcpyDeviceToHost, st));
+        else
+            HIP_TRY(hipMemcpy2DAsync(to, (size_t)image_bytes, from, (size_t)image_bytes, (size_t)used, (size_t)(j - i), hipMemcpyDeviceToHost, st));
+        i = j;
+    }
+    HIP_TRY(hipStreamSynchronize(st));       // delivered: svo_wait means that
+    return SVO_OK;
+}

@@ -1,7 +1,7 @@
 // svo_group_state.hpp — the state of one sequence group, internal to the group: only its translation units
 // (svo_group.hip: storage, creation, settings, the end of a sequence; svo_group_step.hip: the step;
 // svo_group_export.hip: the bulk export; svo_group_map.hip: the map export; svo_group_view.hip: the views;
-// svo_group_scene.hip: the scenes;
+// svo_group_scene.hip: the scenes; svo_group_ar.hip: the ar pictures;
 // svo_group_snapshot.hip: save and load;
 // svo_group_pose.hip: the batched pose-filter updates) and the per-sequence getters of
 // svo_ctx.hip include it. Everyone else drives a group through the opaque interface of svo_group.hpp.
@@ -331,6 +331,13 @@ struct svo_group {
     uint8_t* d_scene_in = nullptr; size_t scene_in_bytes = 0;
     svo::PinnedPtr<uint8_t> scene_in_host;
     uint8_t* d_scene = nullptr; size_t scene_bytes = 0;
+    // ar pictures (grp_export_ar): the input block of one job (meshes | draws | image records | work list) and its
+    // pinned mirror and the screen records of one job, made by the group's first ar job; in host mode the images of
+    // one job, made by the first host-mode one. Replaced when outgrown.
+    uint8_t* d_ar_in = nullptr; size_t ar_in_bytes = 0;
+    svo::PinnedPtr<uint8_t> ar_in_host;
+    uint8_t* d_ar_rec = nullptr; size_t ar_rec_bytes = 0;
+    uint8_t* d_ar = nullptr; size_t ar_bytes = 0;
     // batched pose-filter updates (grp_pose_updates): the upload block (samples | filter states | start poses |
     // sample offsets) and behind it the download block (filter states | filtered poses) of one job, device and pinned,
     // made by the first such job and replaced when outgrown

@@ -262,6 +262,56 @@ void scene_tiles(int image, int w, int h, std::vector<SceneTile>& out);
 void scene_frustum_lines(const float pose[6], const float dims[3], uint32_t cls_rgb, std::vector<svo_scene_line>& out);
 void launch_scene(const SceneTile* d_tiles, int n_tiles, const SceneImage* d_images, const SceneParams& p, hipStream_t stream);
 
+// ------------------------------------------------------------ ar (ar.hip)
+// The screen record of one (image, triangle), written by the first launch and walked by the second: the snapped
+// vertices (4 sub-pixel bits), the camera depth of each, the shaded colour r << 16 | g << 8 | b and the pixels whose
+// centres can lie inside, clipped to the image (bx0 > bx1: dropped, or nothing to draw). Four 16-byte words.
+struct ArRecord {
+    int X0, Y0, X1, Y1;
+    int X2, Y2; float z0, z1;
+    float z2; uint32_t rgb; int _pad[2];
+    int bx0, by0, bx1, by1;
+};
+// One output image: the background plane (any base, src_stride >= w), the w x h image at dst (rows dense), seen
+// through cam; its draws (device table; everything they point to is device memory) and its n_records records, the
+// triangles of draw 0 first
+struct ArImage {
+    svo_ar_camera cam;
+    const uint8_t* src;
+    uint8_t* dst;
+    const svo_ar_draw* draws;
+    ArRecord* records;
+    int src_stride, w, h, n_records;
+};
+// One workgroup of the first launch: triangles [t0, t0 + AR_THREADS) of draw `draw` of image `image`, whose records
+// start at rec0
+constexpr int AR_THREADS = 256;
+struct ArSetup {
+    int image, draw, t0, rec0;
+};
+// One tile of an image: at most AR_TILE_W x AR_TILE_H pixels at (x0, y0), one workgroup of the second launch
+constexpr int AR_TILE_W = 64, AR_TILE_H = 16;
+struct ArTile {
+    int image, x0, y0, _pad;
+};
+// what the launches draw, from a checked svo_ar_style
+struct ArParams {
+    int bpp;
+    float light[3];
+    float ambient, near;
+};
+// what an ar job, svo_ar_size and the stage entry check alike
+int ar_check_style(const svo_ar_style* style, const char* who);
+int ar_check_camera(const svo_ar_camera* cam, const char* who, int i);
+ArParams ar_params(const svo_ar_style& style);
+// pitch and image_bytes of a cols x rows image of a checked style
+void ar_shape(const svo_ar_style& style, int cols, int rows, int64_t* pitch, int64_t* image_bytes);
+// the work of image `image`: its tiles (w x h) and the first launch's items of its draws, appended; returns the
+// image's records
+int ar_work(int image, int w, int h, const svo_ar_draw* draws, int n_draws, std::vector<ArSetup>& setup, std::vector<ArTile>& tiles);
+void launch_ar_setup(const ArSetup* d_setup, int n_setup, const ArImage* d_images, const ArParams& p, hipStream_t stream);
+void launch_ar(const ArTile* d_tiles, int n_tiles, const ArImage* d_images, const ArParams& p, hipStream_t stream);
+
 // ------------------------------------------------------------ batched pose filter (pose_filter.hip)
 // n_states filter states, one lane each, POSE_FILTER_LANES per workgroup. State b runs samples
 // [first[b], first[b + 1]) (clamped to [0, n_samples)) in order; a state without samples is neither read nor written.

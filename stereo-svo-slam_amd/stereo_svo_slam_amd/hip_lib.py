@@ -43,6 +43,7 @@ SYMBOLS = (
     "svo_view_size", "svo_submit_export_views", "svo_export_views", "svo_render_views",
     "svo_scene_size", "svo_scene_look_at", "svo_scene_frustum", "svo_submit_export_scenes", "svo_export_scenes",
     "svo_render_scene",
+    "svo_ar_size", "svo_ar_camera_of_pose", "svo_submit_export_ar", "svo_export_ar", "svo_render_ar",
     "svo_remap_linear_multi", "svo_ctx_add_rigs", "svo_ctx_remove_rigs", "svo_ctx_assign_rigs", "svo_ctx_get_slot_rig",
     "svo_ctx_get_rigs",
     "svo_klt_track_batch", "svo_klt_cache_layout",
@@ -462,6 +463,105 @@ def scene_frustum(pose, dims=(0.1, 0.08, 0.07)):
     return out
 
 
+# ar pictures (svo_submit_export_ar, include/svo_hip.h): lit meshes over each slot's camera image
+AR_OK, AR_NONE = 0, 1
+AR_MAX_TRIANGLES = 65536
+AR_SEGMENT_DTYPE = np.dtype([("seq", "<i4"), ("run", "<i4"), ("frame_id", "<i4"), ("status", "<u2"), ("_pad", "<u2"),
+                             ("n_instances", "<i4"), ("n_triangles", "<i4"), ("time_stamp", "<f4"), ("_pad2", "<i4"),
+                             ("offset", "<i8"), ("pose", "<f4", (6,))])
+assert AR_SEGMENT_DTYPE.itemsize == 64
+# the demo (src/ar-app/): near plane 0.01, a directional light along +z, the object half a metre in front of the
+# first camera (AnimatedEntity.qml:56). The demo's light has no ambient term of its own (Qt3D's phong default adds
+# a small one); 0.25 is this binding's choice, so that a face turned away from the light keeps a visible colour.
+AR_NEAR, AR_LIGHT, AR_AMBIENT, AR_AT = 0.01, (0.0, 0.0, 1.0), 0.25, (0.0, 0.0, 0.5)
+
+
+class ArCamera(C.Structure):
+    """svo_ar_camera (include/svo_hip.h): the rows of the 3x4 world -> camera matrix, fx, fy, cx, cy."""
+    _fields_ = [("view", C.c_float * 12), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float)]
+
+
+class ArMesh(C.Structure):
+    """svo_ar_mesh (include/svo_hip.h): host arrays of one mesh."""
+    _fields_ = [("vertices", C.c_void_p), ("triangles", C.c_void_p), ("rgb", C.c_void_p), ("n_vertices", C.c_int32),
+                ("n_triangles", C.c_int32), ("_reserved", C.c_int64)]
+
+
+class ArInstance(C.Structure):
+    """svo_ar_instance (include/svo_hip.h): a mesh placed in the world."""
+    _fields_ = [("model", C.c_float * 12), ("mesh", C.c_int32), ("rgb", C.c_uint32), ("_reserved", C.c_int32 * 2)]
+
+
+class ArStyle(C.Structure):
+    """svo_ar_style (include/svo_hip.h)."""
+    _fields_ = [("pixel", C.c_int32), ("light", C.c_float * 3), ("ambient", C.c_float), ("near", C.c_float),
+                ("_reserved", C.c_int32 * 2)]
+
+
+class ArDst(C.Structure):
+    """svo_ar_dst (include/svo_hip.h)."""
+    _fields_ = [("segments", C.c_void_p), ("pixels", C.c_void_p), ("capacity", C.c_int64)]
+
+
+class ArDraw(C.Structure):
+    """svo_ar_draw (include/svo_hip.h): an instanced mesh in device memory, of svo_render_ar."""
+    _fields_ = [("model", C.c_float * 12), ("vertices", C.c_void_p), ("triangles", C.c_void_p), ("rgb", C.c_void_p),
+                ("n_vertices", C.c_int32), ("n_triangles", C.c_int32), ("rgb_all", C.c_uint32), ("_reserved", C.c_int32)]
+
+
+class ArSrc(C.Structure):
+    """svo_ar_src (include/svo_hip.h): one image of svo_render_ar."""
+    _fields_ = [("image", Image), ("draws", C.c_void_p), ("n_draws", C.c_int32), ("_reserved", C.c_int32)]
+
+
+assert (C.sizeof(ArCamera), C.sizeof(ArMesh), C.sizeof(ArInstance), C.sizeof(ArStyle), C.sizeof(ArDraw)) == (64, 40, 64, 32, 88)
+
+
+def ar_style(pixel=PIXEL_RGB8, light=AR_LIGHT, ambient=AR_AMBIENT, near=AR_NEAR):
+    """an ArStyle; the defaults are the demo's near plane (0.01) and light (0, 0, 1), and ambient = 0.25 (this
+    binding's choice: the demo states none). pixel may be a name (PIXELS)"""
+    if isinstance(pixel, str):
+        pixel = PIXELS.index(pixel)
+    return ArStyle(int(pixel), (C.c_float * 3)(*[float(x) for x in light]), float(ambient), float(near))
+
+
+def ar_size(cam, width, height, style):
+    """svo_ar_size (host only): (pitch, image_bytes) of one image of an ar job in a ctx of these settings."""
+    pitch, nbytes = C.c_int64(0), C.c_int64(0)
+    _check(lib().svo_ar_size(C.byref(cam), int(width), int(height), C.byref(style), C.byref(pitch), C.byref(nbytes)))
+    return pitch.value, nbytes.value
+
+
+def ar_camera_of_pose(pose, cam):
+    """svo_ar_camera_of_pose (host only): the ArCamera of a slot at `pose` (t, r) with the intrinsics of `cam`."""
+    out = ArCamera()
+    _check(lib().svo_ar_camera_of_pose((C.c_float * 6)(*[float(x) for x in pose]), C.byref(cam), C.byref(out)))
+    return out
+
+
+def ar_model(at=(0.0, 0.0, 0.0), scale=1.0, rot=None):
+    """float32 [12]: the rows of the 3x4 mesh -> world matrix `scale * rot` (rot: 3x3, default identity) then + at"""
+    m = np.zeros((3, 4), np.float32)
+    m[:, :3] = (np.eye(3) if rot is None else np.asarray(rot, np.float64)) * float(scale)
+    m[:, 3] = at
+    return m.ravel()
+
+
+def ar_box(size=1.0):
+    """the stock object: an axis-aligned cube of edge `size` about the origin as (vertices float32 [8, 3], triangles
+    int32 [12, 3]), two triangles a face"""
+    h = 0.5 * float(size)
+    v = np.array([[x, y, z] for z in (-h, h) for y in (-h, h) for x in (-h, h)], np.float32)
+    t = np.array([[0, 1, 3], [0, 3, 2], [4, 7, 5], [4, 6, 7], [0, 5, 1], [0, 4, 5],
+                  [2, 3, 7], [2, 7, 6], [0, 2, 6], [0, 6, 4], [1, 5, 7], [1, 7, 3]], np.int32)
+    return v, t
+
+
+def ar_instance(model, mesh=0, rgb=0xc08040):
+    """an ArInstance of mesh index `mesh` at `model` (12 floats, ar_model) with colour r << 16 | g << 8 | b"""
+    return ArInstance((C.c_float * 12)(*[float(x) for x in np.asarray(model).ravel()]), int(mesh), int(rgb))
+
+
 class SnapshotInfo(C.Structure):
     """struct svo_snapshot_info (include/svo_hip.h): the header of a snapshot's host part."""
     _fields_ = [("magic", C.c_uint32), ("version", C.c_uint32), ("byte_order", C.c_uint32), ("status", C.c_uint32),
@@ -858,6 +958,40 @@ class Handle:
         n, arr, cams, offs, _ = packed
         p = pixels.data_ptr() if isinstance(pixels, torch.Tensor) else int(pixels)
         _check(lib().svo_render_scene(self._h, n, arr, cams, offs, C.byref(style), C.c_void_p(p)))
+
+    def render_ar(self, srcs, cameras, offsets, style, pixels):
+        """svo_render_ar: lit meshes over gray planes as images of `style` (an ArStyle). srcs: per image
+        ((data address or uint8 device tensor, width, height, stride), draws) with draws a list of (model of 12
+        floats, vertices float32 device tensor [V, 3], triangles int32 device tensor [T, 3], rgb uint32 / int32 device
+        tensor [T] or None, the instance's colour); cameras: an ArCamera per image; offsets[i]: the byte of `pixels`
+        (a uint8 device tensor, or a raw device address) image i starts at. Complete on return."""
+        self.render_ar_packed(self.pack_ar(srcs, cameras, offsets), style, pixels)
+
+    def pack_ar(self, srcs, cameras, offsets):
+        """the argument arrays of render_ar, built once (keeps Python out of a timed call); pass the result to
+        render_ar_packed. The device tensors of `srcs` must stay alive."""
+        n = len(srcs)
+        arr = (ArSrc * max(n, 1))()
+        cams = (ArCamera * max(n, 1))(*cameras)
+        keep = []
+        for i, (img, draws) in enumerate(srcs):
+            data, w, h, stride = img
+            ds = (ArDraw * max(len(draws), 1))()
+            for j, (model, vertices, triangles, rgb, rgb_all) in enumerate(draws):
+                ds[j] = ArDraw((C.c_float * 12)(*[float(x) for x in np.asarray(model).ravel()]), vertices.data_ptr(),
+                               triangles.data_ptr(), None if rgb is None else rgb.data_ptr(), vertices.numel() // 3,
+                               triangles.numel() // 3, int(rgb_all), 0)
+            keep.append(ds)
+            arr[i] = ArSrc(Image(data.data_ptr() if isinstance(data, torch.Tensor) else int(data), int(w), int(h), int(stride)),
+                           C.cast(ds, C.c_void_p), len(draws), 0)
+        offs = (C.c_int64 * max(n, 1))(*[int(o) for o in offsets])
+        return n, arr, cams, offs, keep
+
+    def render_ar_packed(self, packed, style, pixels):
+        """svo_render_ar of the arrays of pack_ar"""
+        n, arr, cams, offs, _ = packed
+        p = pixels.data_ptr() if isinstance(pixels, torch.Tensor) else int(pixels)
+        _check(lib().svo_render_ar(self._h, n, arr, cams, offs, C.byref(style), C.c_void_p(p)))
 
     def copy_segments(self, segs):
         """svo_copy_segments: 2-D byte segments, device to device. segs: (src address, dst address, row_bytes,

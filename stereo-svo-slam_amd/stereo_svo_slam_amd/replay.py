@@ -15,6 +15,7 @@ Host bookkeeping only; every frame goes through StereoSlam.new_image (libsvo_hip
     python -m stereo_svo_slam_amd.replay --settings EuRoC.yaml --pairs 'seq/%06d_left.png,seq/%06d_right.png'
     python -m stereo_svo_slam_amd.replay --synthetic tiny --frames 20 --dump-views views/
     python -m stereo_svo_slam_amd.replay --synthetic tiny --frames 20 --dump-scene scene/
+    python -m stereo_svo_slam_amd.replay --synthetic tiny --frames 20 --dump-ar ar/ --ar-box 0.2 --ar-at 0,0,0.5
 
 Inputs follow the reference's conventions (the library's `left` is the physically RIGHT camera):
 EurocInput (src/app/euroc_input.cpp:48-70,100-105), VideoInput (src/app/video_input.cpp:29-36), EconInput
@@ -27,6 +28,9 @@ current frame): the gray image the tracker worked on, which with --gpu-rectify /
 The text overlay and the x2 resize of the window are not drawn.
 --dump-scene DIR writes per frame DIR/000000_scene.ppm: the 3-D viewer's picture of the map so far
 (src/qt-viewer/PointCloudViewer.qml: points, trajectory, frusta) through its front camera.
+--dump-ar DIR writes per frame DIR/000000_ar.ppm: the AR demo's picture (src/ar-app/), a lit box of edge --ar-box
+fixed at the world point --ar-at over the frame's left image, seen from the tracked pose; the default placement is the
+demo's, half a metre in front of the first camera (AnimatedEntity.qml:56). If the pose is right the box stands still.
 With $SVO_DATA set (a EuRoC `mav0/` directory, or a directory of side-by-side frames) and no
 explicit input that data is used; otherwise the seeded synthetic sequence.
 """
@@ -38,7 +42,7 @@ import time
 
 import numpy as np
 
-from . import synth
+from . import hip_lib, synth
 from .stereo_slam import StereoSlam
 
 # key in the YAML -> CameraSettings field (src/app/image_input.cpp:16-36)
@@ -356,11 +360,20 @@ def read_ppm(path):
     return np.frombuffer(body, np.uint8).reshape(h, w, 3)
 
 
+AR_BOX, AR_RGB = 0.2, 0xc08040
+
+
+def ar_objects(size=AR_BOX, at=hip_lib.AR_AT, rgb=AR_RGB):
+    """the objects of --dump-ar for StereoSlam.get_ar: one box of edge `size` at the world point `at`"""
+    return [(*hip_lib.ar_box(size), hip_lib.ar_model(at), rgb)]
+
+
 class Replay:
     """process_image loop: only the time inside new_image is accumulated (slam_app.cpp:186-190)."""
 
     def __init__(self, settings, device=0, time_trace=False, fast=False, rectify_maps=None, input_format=None,
-                 gpu_imu=False, dump_views=None, dump_scene=None, calibration=None, keyframe_window=None):
+                 gpu_imu=False, dump_views=None, dump_scene=None, calibration=None, keyframe_window=None, dump_ar=None,
+                 ar_box=AR_BOX, ar_at=hip_lib.AR_AT):
         """fast=False keeps the library default: the reference-order Gauss-Newton (bit-exact traces).
         rectify_maps = (left maps, right maps): the frames fed are raw and are rectified on the GPU.
         calibration = (left, right) CameraCalibrations: the same, with the maps built on the GPU as well.
@@ -370,10 +383,14 @@ class Replay:
         dump_views: a directory that receives, per frame, the last keyframe and the current frame with a marker per
         keypoint as the reference app's window shows them (write_ppm), outside the timed region.
         dump_scene: a directory that receives, per frame, the 3-D viewer's picture of the map (get_scene), likewise.
+        dump_ar: a directory that receives, per frame, the AR demo's picture (get_ar): a lit box of edge ar_box at the
+        world point ar_at over the frame's left image, likewise. The default is the demo's placement, half a metre in
+        front of the first camera.
         keyframe_window: the retired keyframes the tracker keeps (StereoSlamBatch.set_keyframe_window); None: all."""
         self.settings = settings
-        self.dump_views, self.dump_scene = dump_views, dump_scene
-        for d in (dump_views, dump_scene):
+        self.dump_views, self.dump_scene, self.dump_ar = dump_views, dump_scene, dump_ar
+        self.ar_objects = ar_objects(ar_box, ar_at)
+        for d in (dump_views, dump_scene, dump_ar):
             if d:
                 os.makedirs(d, exist_ok=True)
         self.gpu_imu = gpu_imu
@@ -436,6 +453,10 @@ class Replay:
             img = self.slam.get_scene("front", pixel="rgb8")
             if img is not None:
                 write_ppm(os.path.join(self.dump_scene, f"{len(self.cumulative) - 1:06d}_scene.ppm"), img)
+        if self.dump_ar:
+            img = self.slam.get_ar(self.ar_objects, pixel="rgb8")
+            if img is not None:
+                write_ppm(os.path.join(self.dump_ar, f"{len(self.cumulative) - 1:06d}_ar.ppm"), img)
         if self.time_trace:                       # like PRINT_TIME_TRACE of the reference
             print("\n".join(time_trace_lines(self.slam.stats())))
 
@@ -488,6 +509,12 @@ def build_parser():
     ap.add_argument("--dump-scene", metavar="DIR",
                     help="write per frame DIR/NNNNNN_scene.ppm: the 3-D viewer's picture of the map so far (keyframe points, "
                          "trajectory, a frustum per keyframe and at the current pose) through its front camera")
+    ap.add_argument("--dump-ar", metavar="DIR",
+                    help="write per frame DIR/NNNNNN_ar.ppm: the AR demo's picture, a lit box standing in the world over the "
+                         "frame's left image, seen from the tracked pose")
+    ap.add_argument("--ar-box", metavar="SIZE", type=float, default=AR_BOX, help="edge of the box of --dump-ar, metres")
+    ap.add_argument("--ar-at", metavar="X,Y,Z", default=",".join(str(x) for x in hip_lib.AR_AT),
+                    help="world point of the box's centre (default: half a metre in front of the first camera, as the demo)")
     ap.add_argument("--frames", type=int, default=100)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--rate", type=float, default=20.0, help="frames per second of the time stamps")
@@ -550,7 +577,8 @@ def main(argv=None):
         ap.error("--gpu-imu needs --gyro")
     gyro = np.loadtxt(args.gyro, ndmin=2) if args.gyro else None
     rp = Replay(settings, args.device, args.time_trace, args.fast, rectify_maps=rect, input_format=fmt, gpu_imu=args.gpu_imu,
-                dump_views=args.dump_views, dump_scene=args.dump_scene, calibration=cal,
+                dump_views=args.dump_views, dump_scene=args.dump_scene, calibration=cal, dump_ar=args.dump_ar,
+                ar_box=args.ar_box, ar_at=tuple(float(x) for x in args.ar_at.split(",")),
                 keyframe_window=args.keyframe_window)
     for k, (left, right, t) in enumerate(frames):
         rp.feed(left, right, t, None if gyro is None else gyro[gyro[:, 0] == k, 1:4])

@@ -377,6 +377,74 @@ class Scenes:
         return self.pixels[lo:lo + self.rows * self.pitch].reshape(self.rows, self.cols, self.channels)
 
 
+class ArPictures:
+    """One svo_submit_export_ar: owns the buffers the library writes. After wait(): `segments`
+    (hip_lib.AR_SEGMENT_DTYPE, one per named slot) and image(i); `pixels` is the whole buffer, a numpy uint8 view of
+    pinned memory in host mode, a torch uint8 tensor on the ctx's device in device mode. cols, rows, pitch,
+    image_bytes: the shape of every image of the job (svo_ar_size); channels: 3 or 4. meshes: (vertices [V, 3],
+    triangles [T, 3][, rgb [T] or None]) each; instances: hip_lib.ArInstance, or (model of 12 floats, mesh index,
+    rgb) each; first: None (every slot shows every instance) or n + 1 ascending offsets into the instances."""
+
+    def __init__(self, slam, seqs, style, meshes, instances, first, device):
+        self._slam = slam
+        self.style, self.device_mode = style, bool(device)
+        self.seqs = None if seqs is None else [int(s) for s in seqs]
+        n = self._n = slam.n if seqs is None else len(self.seqs)
+        self.cols, self.rows = slam.width, slam.height
+        self.pitch, self.image_bytes = hip_lib.ar_size(slam.cam, slam.width, slam.height, style)
+        self.channels = hip_lib.PIXEL_BYTES[style.pixel]
+        self.capacity = n * self.image_bytes
+        self._keep = []
+        self._meshes = (hip_lib.ArMesh * max(len(meshes), 1))()
+        for i, m in enumerate(meshes):
+            v = np.ascontiguousarray(m[0], np.float32).reshape(-1, 3)
+            t = np.ascontiguousarray(m[1], np.int32).reshape(-1, 3)
+            rgb = None if len(m) < 3 or m[2] is None else np.ascontiguousarray(m[2], np.uint32).reshape(-1)
+            if rgb is not None and len(rgb) != len(t):
+                raise ValueError(f"mesh {i}: {len(rgb)} colours for {len(t)} triangles")
+            self._keep += [v, t, rgb]
+            self._meshes[i] = hip_lib.ArMesh(v.ctypes.data if len(v) else None, t.ctypes.data if len(t) else None,
+                                             None if rgb is None else rgb.ctypes.data, len(v), len(t), 0)
+        self._n_meshes = len(meshes)
+        inst = [x if isinstance(x, hip_lib.ArInstance) else hip_lib.ar_instance(*x) for x in instances]
+        self._inst = (hip_lib.ArInstance * max(len(inst), 1))(*inst)
+        self._n_inst = len(inst)
+        self._first = None if first is None else (C.c_int * (n + 1))(*[int(f) for f in first])
+        self._seg = np.zeros(max(n, 1), hip_lib.AR_SEGMENT_DTYPE)
+        self.segments = self._seg[:n]
+        self._buf = (torch.zeros(max(self.capacity, 4), dtype=torch.uint8, device=slam.device) if device
+                     else torch.zeros(max(self.capacity, 4), dtype=torch.uint8, pin_memory=True))
+        self._dst = hip_lib.ArDst(self._seg.ctypes.data, self._buf.data_ptr(), self.capacity)
+        self._seq_arr = None if seqs is None else (C.c_int * max(n, 1))(*self.seqs)
+
+    @property
+    def pixels(self):
+        return self._buf if self.device_mode else self._buf.numpy()
+
+    def submit(self):
+        """queue the job (again: the same slots into the same buffers, once the previous one is delivered)"""
+        slam = self._slam
+        if self.device_mode:
+            torch.cuda.current_stream(slam.device).synchronize()     # (nothing of the caller's is still using the tensor)
+        _check(lib().svo_submit_export_ar(slam._ctx, self._seq_arr, self._n, C.byref(self.style), self._meshes, self._n_meshes,
+                                          self._inst, self._first, self._n_inst, C.byref(self._dst),
+                                          hip_lib.MEM_DEVICE if self.device_mode else hip_lib.MEM_HOST))
+        return self
+
+    def wait(self):
+        self._slam.wait()
+        return self
+
+    def image(self, i):
+        """the image of named slot i: [rows, cols, 3 | 4], a view of `pixels` (numpy in host mode, a torch tensor in
+        device mode); None for a slot whose status is AR_NONE"""
+        e = self.segments[i]
+        if int(e["status"]) != hip_lib.AR_OK:
+            return None
+        lo = int(e["offset"])
+        return self.pixels[lo:lo + self.rows * self.pitch].reshape(self.rows, self.cols, self.channels)
+
+
 class Snapshot:
     """The sequence state of one slot (svo_submit_save / svo_submit_load): `host` (numpy uint8, the host part) and
     `data` (the data part: numpy uint8, or a torch uint8 tensor on the ctx's device in device mode). Valid after
@@ -711,6 +779,20 @@ class StereoSlamBatch:
     def export_scenes(self, seqs=None, **kw):
         """submit_scenes + wait"""
         return self.submit_scenes(seqs, **kw).wait()
+
+    def submit_ar(self, meshes, instances, seqs=None, first=None, device=False, style=None, **kw):
+        """svo_submit_export_ar: queue the AR demo's picture (the instanced meshes, lit and depth tested, over the
+        left image of each named slot's current frame, seen from its pose through its rig's intrinsics) of the named
+        slots (None: all), ordered with the frame sets; nothing is waited for. meshes, instances, first: see
+        ArPictures; style: a hip_lib.ArStyle, or its fields as keywords (hip_lib.ar_style: pixel, light, ambient,
+        near). Returns an ArPictures, valid after wait()."""
+        if style is None:
+            style = hip_lib.ar_style(**kw)
+        return ArPictures(self, seqs, style, meshes, instances, first, device).submit()
+
+    def export_ar(self, meshes, instances, seqs=None, **kw):
+        """submit_ar + wait"""
+        return self.submit_ar(meshes, instances, seqs, **kw).wait()
 
     def snapshot_size(self, seq):
         """svo_snapshot_size: (host_bytes, data_bytes) a save of the slot needs right now (waits)."""
@@ -1115,4 +1197,16 @@ class StereoSlam(StereoSlamBatch):
             return None
         kw["device"] = False
         img = self.export_scenes(None, camera=camera, **kw).image(0)
+        return None if img is None else img.copy()
+
+    def get_ar(self, objects, **kw):
+        """the AR demo's picture of the current frame as a numpy array [height, width, 3 | 4] (export_ar of the one
+        slot: pixel, light, ambient, near). objects: (vertices, triangles, model of 12 floats, rgb) each, e.g.
+        (*hip_lib.ar_box(0.2), hip_lib.ar_model(hip_lib.AR_AT), 0xc08040). None before the first frame"""
+        if self._ctx is None:
+            return None
+        kw["device"] = False
+        meshes = [(v, t) for v, t, _, _ in objects]
+        instances = [(model, i, rgb) for i, (_, _, model, rgb) in enumerate(objects)]
+        img = self.export_ar(meshes, instances, None, **kw).image(0)
         return None if img is None else img.copy()

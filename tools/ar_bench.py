@@ -1,0 +1,244 @@
+"""What the AR demo's picture costs on the MI355X: the two kernels through the stage entry, the ctx's job in device and
+host mode, and pictures queued between the steps of bench.py's workload.
+
+bench.py's workload (C2 `euroc`, borrowed device frames from bench.py's rendered loops, pipelined submits), in one
+process:
+
+  kernel     256 slots in one group after `--warmup` steps. Every slot shows one box (12 triangles, each face tens of
+             tiles) and one tessellated sphere (`--sphere` x 2 `--sphere` bands: a few thousand small triangles), both
+             placed a metre in front of the slot's own current pose, so that every image has them in view. The stage
+             entry svo_render_ar on the slots' level-0 planes (through a device-mode view job), 752 x 480 RGBA; median
+             of `--repeats` calls between two device events. A call is the upload of its tables, both kernels and a
+             stream synchronise. The kernels' own times come from a `rocprofv3 --kernel-trace --stats` run of this
+             tool with --kernel-only, in a run of its own: this tool cannot record them.
+  job        the ctx's own job of every slot (submit + wait, host clock) in device and in host mode: the host's table
+             building, one upload, the kernels and a stream synchronise (host mode: and the copies out). Beside it, on
+             the same output bytes: the device-mode RGBA view job of §4.11 (in this run).
+  pipelined  frames/s over `--steps` queued steps without pictures and with a device-mode picture of every slot queued
+             behind every 10th frame set; legs alternate, median of `--pipelined-repeats` each.
+Prints one JSON line.
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+os.environ.setdefault("GPU_MAX_HW_QUEUES", "20")         # (bench.py's setting: 14 groups of 256)
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, "stereo-svo-slam_amd"), os.path.join(ROOT, "oracle")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+import numpy as np
+import torch
+
+import bench
+from stereo_svo_slam_amd import hip_lib
+from stereo_svo_slam_amd.stereo_slam import ArPictures, StereoSlamBatch
+
+HBM_PEAK = 8.0e12
+BOX_RGB, SPHERE_RGB = 0xc08040, 0x4080c0
+
+
+def timed(device, fn):
+    torch.cuda.synchronize(device)
+    t0 = time.perf_counter()
+    fn()
+    torch.cuda.synchronize(device)
+    return time.perf_counter() - t0
+
+
+def median_ms(device, fn, repeats):
+    fn()
+    all_ms = [timed(device, fn) * 1e3 for _ in range(repeats)]
+    return statistics.median(all_ms), all_ms
+
+
+def event_ms(fn, repeats):
+    """median of the device time between two events around fn(), on the current stream"""
+    out = []
+    for _ in range(repeats):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        out.append(a.elapsed_time(b))
+    return statistics.median(out), out
+
+
+def sphere(radius, bands):
+    """a UV sphere: (vertices float32 [V, 3], triangles int32 [T, 3]), 2 * bands * (bands - 1) * 2 triangles"""
+    lat = np.linspace(0, np.pi, bands + 1)
+    lon = np.linspace(0, 2 * np.pi, 2 * bands, endpoint=False)
+    v = np.array([[np.sin(a) * np.cos(b), np.cos(a), np.sin(a) * np.sin(b)] for a in lat for b in lon], np.float32) * np.float32(radius)
+    n = 2 * bands
+    t = []
+    for i in range(bands):
+        for j in range(n):
+            a, b, c, d = i * n + j, i * n + (j + 1) % n, (i + 1) * n + j, (i + 1) * n + (j + 1) % n
+            if i > 0:
+                t.append((a, b, c))
+            if i < bands - 1:
+                t.append((b, d, c))
+    return v, np.array(t, np.int32)
+
+
+def rodrigues(r):
+    r = np.asarray(r, np.float64)
+    th = np.sqrt(r @ r)
+    if th < 1e-12:
+        return np.eye(3)
+    k = r / th
+    K = np.array([[0, -k[2], k[1]], [k[2], 0, -k[0]], [-k[1], k[0], 0]])
+    return np.eye(3) + np.sin(th) * K + (1 - np.cos(th)) * (K @ K)
+
+
+def placed(slam, slots):
+    """two instances per slot, a metre in front of its current pose: (instances, first)"""
+    inst = []
+    for s in range(slots):
+        p = slam.pose(s)
+        R = rodrigues(p[3:6])
+        inst.append((hip_lib.ar_model(p[:3] + R @ np.array([-0.25, 0.0, 1.0]), 1.0, R @ rodrigues([0.4, 0.6, 0.0])), 0, BOX_RGB))
+        inst.append((hip_lib.ar_model(p[:3] + R @ np.array([0.3, 0.0, 1.2])), 1, SPHERE_RGB))
+    return inst, [2 * s for s in range(slots + 1)]
+
+
+def start(cfg, lefts, rights, slots, groups, device, steps):
+    if groups:
+        os.environ["SVO_GROUPS"] = str(groups)
+    else:
+        os.environ.pop("SVO_GROUPS", None)
+    slam = StereoSlamBatch(cfg, cfg["width"], cfg["height"], slots, device.index)
+    packed = bench.step_packer(lefts, rights, bench.loop_plan(slots, len(lefts), lefts[0].shape[0]), True)(slam, steps)
+    return slam, packed
+
+
+def job_leg(args, device, cfg, lefts, rights, meshes):
+    slots = args.slots
+    n = min(slots, len(lefts))
+    slam, packed = start(cfg, lefts[:n], rights[:n], slots, 1, device, args.warmup)
+    for pk in packed:
+        slam.submit_packed(pk)
+    slam.wait()
+    W, H = cfg["width"], cfg["height"]
+    inst, first = placed(slam, slots)
+    style = hip_lib.ar_style(pixel="rgba8")
+    tri = sum(len(meshes[k][1]) for _, k, _ in inst[:2])
+    out = {"slots": slots, "warmup_steps": args.warmup, "cols": W, "rows": H, "triangles_per_slot": tri,
+           "box_triangles": len(meshes[0][1]), "sphere_triangles": len(meshes[1][1])}
+    job = ArPictures(slam, None, style, meshes, inst, first, True).submit().wait()
+    px = job.pixels.view(slots, -1)[:, :H * W * 4].view(slots, H, W, 4)
+    out["covered_fraction"] = float(((px[..., 0] != px[..., 1]) | (px[..., 1] != px[..., 2])).float().mean())
+    out["bytes_written"] = written = slots * H * job.pitch
+    # the stage entry on the same planes
+    views = slam.submit_views("frames", pixel="gray8", device=True).wait()
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
+    dm = [(dev(m[0]), dev(m[1])) for m in meshes]
+    h = hip_lib.Handle(device.index, 1024)
+    srcs = [((views.pixels.data_ptr() + s * views.image_bytes, W, H, W),
+             [(m, dm[k][0], dm[k][1], None, rgb) for m, k, rgb in inst[2 * s:2 * s + 2]]) for s in range(slots)]
+    _, cam = slam.slot_rig(0)
+    cams = [hip_lib.ar_camera_of_pose(slam.pose(s), cam) for s in range(slots)]
+    dst = torch.empty(slots * job.image_bytes, dtype=torch.uint8, device=device)
+    packed_ar = h.pack_ar(srcs, cams, [s * job.image_bytes for s in range(slots)])
+    call = lambda: h.render_ar_packed(packed_ar, style, dst)
+    call()
+    out["stage_entry_equals_job"] = bool(torch.equal(dst, job.pixels))
+    if not args.kernel_only:
+        ms, all_ms = event_ms(call, args.repeats)
+        out["stage_entry"] = {"call_ms": ms, "call_ms_all": all_ms, "bytes_per_s": written / (ms * 1e-3),
+                              "tiles": slots * ((W + 63) // 64) * ((H + 15) // 16), "records": slots * tri}
+        ms, all_ms = median_ms(device, lambda: job.submit().wait(), args.repeats)
+        out["device_mode_job"] = {"job_ms": ms, "job_ms_all": all_ms, "bytes_per_s": written / (ms * 1e-3),
+                                  "fraction_of_hbm_peak": written / (ms * 1e-3) / HBM_PEAK}
+        host = ArPictures(slam, None, style, meshes, inst, first, False).submit().wait()
+        ms, all_ms = median_ms(device, lambda: host.submit().wait(), args.repeats)
+        out["host_mode_job"] = {"job_ms": ms, "job_ms_all": all_ms, "bytes_per_s": written / (ms * 1e-3)}
+        del host
+        box_only = ArPictures(slam, None, style, meshes, inst[0::2], list(range(slots + 1)), True).submit().wait()
+        ms, all_ms = median_ms(device, lambda: box_only.submit().wait(), args.repeats)
+        out["device_mode_job_box_only"] = {"job_ms": ms, "job_ms_all": all_ms}
+        del box_only
+        v = slam.submit_views("frames", pixel="rgba8", device=True).wait()
+        ms, all_ms = median_ms(device, lambda: v.submit().wait(), args.repeats)
+        out["view_rgba8_job"] = {"job_ms": ms, "job_ms_all": all_ms, "bytes_written": v.capacity, "bytes_per_s": v.capacity / (ms * 1e-3)}
+    out["device_GB"] = slam.memory().device_bytes / 1e9
+    h.close()
+    slam.close()
+    return out
+
+
+def pipelined_leg(args, device, cfg, lefts, rights, slots, groups, meshes):
+    K, W, every = args.steps, args.warmup, 10
+    n = min(slots, len(lefts))
+    runs_n = 2 * args.pipelined_repeats
+    slam, packed = start(cfg, lefts[:n], rights[:n], slots, groups, device, W + runs_n * K)
+    for pk in packed[:W]:
+        slam.submit_packed(pk)
+    slam.wait()
+    out = {"slots": slots, "groups": slam.groups(), "steps": K, "ar_every": every}
+    inst, first = placed(slam, slots)
+    style = hip_lib.ar_style(pixel="rgba8")
+    ring = [ArPictures(slam, None, style, meshes, inst, first, True).submit().wait() for _ in range(2)]
+    runs = {"plain": [], "ar": []}
+    for r in range(runs_n):
+        kind = ("plain", "ar")[r % 2]
+        steps = packed[W + r * K:W + (r + 1) * K]
+
+        def run():
+            for k, pk in enumerate(steps):
+                slam.submit_packed(pk)
+                if kind == "ar" and k % every == every - 1:
+                    ring[(k // every) % 2].submit()
+            slam.wait()
+        runs[kind].append(slots * K / timed(device, run))
+    for kind in runs:
+        out[f"frames_per_s_{kind}"] = statistics.median(runs[kind])
+        out[f"frames_per_s_{kind}_all"] = runs[kind]
+    out["ar_vs_plain"] = out["frames_per_s_ar"] / out["frames_per_s_plain"]
+    out["ar_bytes_per_job"] = ring[0].capacity
+    out["device_GB"] = slam.memory().device_bytes / 1e9
+    slam.close()
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--slots", type=int, default=256)
+    ap.add_argument("--sphere", type=int, default=32, help="bands of the sphere: 4 * bands * (bands - 1) triangles")
+    ap.add_argument("--kernel-only", action="store_true", help="one job and one stage-entry call, nothing timed: for a kernel trace")
+    ap.add_argument("--legs", default="256:1", help="slots:groups per pipelined leg (groups 0: the ctx's default); '' for none")
+    ap.add_argument("--loops", type=int, default=64)
+    ap.add_argument("--loop-frames", type=int, default=bench.LOOP_FRAMES)
+    ap.add_argument("--steps", type=int, default=40, help="steps of one timed pipelined run")
+    ap.add_argument("--warmup", type=int, default=60, help="steps before anything is timed")
+    ap.add_argument("--repeats", type=int, default=9)
+    ap.add_argument("--pipelined-repeats", type=int, default=5, help="timed runs per kind of a pipelined leg")
+    ap.add_argument("--out", default=None, help="also write the JSON result to this file")
+    args = ap.parse_args()
+    device = torch.device("cuda", 0)
+    legs = [tuple(int(x) for x in l.split(":")) for l in args.legs.split(",") if l] if not args.kernel_only else []
+    n_loops = min(max([s for s, _ in legs] + [args.slots]), args.loops)
+    cfg, lefts, rights = bench.render_loops("euroc", list(range(n_loops)), args.loop_frames, device)
+    meshes = [hip_lib.ar_box(0.3), sphere(0.15, args.sphere)]
+    out = {"metric": "ar_bench", "config": "euroc", "hbm_peak_bytes_per_s": HBM_PEAK, "hw_queues": int(os.environ["GPU_MAX_HW_QUEUES"]),
+           "job": job_leg(args, device, cfg, lefts, rights, meshes), "legs": []}
+    print(json.dumps(out["job"]), file=sys.stderr, flush=True)        # (progress)
+    for slots, groups in legs:
+        out["legs"].append(pipelined_leg(args, device, cfg, lefts, rights, slots, groups, meshes))
+        print(json.dumps(out["legs"][-1]), file=sys.stderr, flush=True)
+    text = json.dumps(out)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(text + "\n")
+    print(text, flush=True)
+
+
+if __name__ == "__main__":
+    main()
