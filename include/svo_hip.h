@@ -1068,6 +1068,114 @@ typedef struct svo_ar_src {
 int svo_render_ar(svo_handle *h, int n, const svo_ar_src *src, const svo_ar_camera *cameras, const int64_t *offset,
                   const svo_ar_style *style, uint8_t *pixels);
 
+/* ---- dense: disparity and depth maps of many slots in one queued job ------------
+ * The tracker computes stereo disparity at its keypoints only. A dense map is the reference's disparity search
+ * (DepthFilter::calculate_disparities, src/lib/depth_filter.cpp:259-327, i.e. svo_ssd_disparity with clamp_half = 1)
+ * evaluated at every point of a lattice over the rectified, converted left and right planes of a slot, which exist in
+ * device memory only. A disparity job is the batched reader: the groups that own a named slot compute one map per
+ * slot with one kernel launch each (dense.hip) and deliver it into host or device memory; the host writes one
+ * svo_disparity_segment per named slot.
+ *
+ * Lattice: cols = W / step, rows = H / step (integer division); lattice point (ix, iy) is the pixel
+ * x = ix * step + step / 2, y = iy * step + step / 2, and its value is exactly what
+ * svo_ssd_disparity(left, right, {(x, y)}, 1, win, search_x, search_y, 1, .) gives for that point.
+ *
+ * Point rule: with wb = win / 2, wa = (win + 1) / 2,
+ *   template box  x11 = max(0, x - wb), x12 = min(W - 1, x + wa), y11 = max(0, y - wb), y12 = min(H, y + wa)
+ *   region box    x21 = x11, x22 = min(W - 1, x + wa + search_x), y21 = max(0, y - wb - search_y),
+ *                 y22 = min(H - 1, y + wa + search_y)
+ *   invalid (-1)  x12 <= 0, y12 <= 0, x11 >= W - 1 or y11 >= H - 1; the same four tests on the region box; or any of
+ *                 tw = x12 - x11, th = y12 - y11, mw = (x22 - x21) - tw + 1, mh = (y22 - y21) - th + 1 is <= 0
+ *   candidate     (k, j), 0 <= k < mh, 0 <= j < mw, has the exact integer
+ *                 SSD(k, j) = sum over r < th, c < tw of (R[y21 + k + r][x21 + j + c] - L[y11 + r][x11 + c])^2,
+ *                 rounded once to float
+ * The clipping is the reference's own: the template never holds the last column, a template clipped at the bottom
+ * leaves mh = y11 - y21, and near the right edge mw shrinks to 1.
+ *
+ * Argmin and ties, as one pass over the candidates in row-major order (k outer, j inner): a float value strictly
+ * below the best so far sets best, minx = j, sum = j, count = 1; a value equal to the best with j >= minx adds j to
+ * sum and 1 to count. d = (float)sum / (float)count, and the disparity is d < 0.5f ? 0.5f : d. (This equals the
+ * reference's two loops: the first minimum of the float map, then the mean column over j >= minx, k >= miny.)
+ *
+ * Planes: the value plane is cols x rows float32, dense. SVO_DENSE_DISPARITY: the disparity as above.
+ * SVO_DENSE_DEPTH: z = baseline / disparity of a valid point in float (outlier_check's _z; a valid disparity is
+ * already >= 0.5) and 0 at an invalid point; baseline is that of the slot's rig. With style.cost = 1 a second plane
+ * follows the first at + cols * rows * 4 bytes: best, the float-rounded minimum SSD, and -1 at an invalid point.
+ *
+ * Layout: image_bytes = planes * cols * rows * 4 rounded up to a multiple of 256; named slot i of a job goes to
+ * offset = i * image_bytes of dst->values, whatever group owns it. Of a slot exactly the planes' bytes are written; a
+ * slot whose status is SVO_DISPARITY_NONE writes only its segment. */
+enum { SVO_DENSE_DISPARITY = 0, SVO_DENSE_DEPTH = 1 };
+enum { SVO_DISPARITY_OK = 0,
+       SVO_DISPARITY_NONE = 1 };    /* an empty slot, no keyframe yet, or the keyframe has given its image set back */
+
+typedef struct svo_disparity_style {   /* 32 bytes; what one job computes; copied at submit                 */
+    int32_t value;                  /* SVO_DENSE_*                                                          */
+    int32_t step;                   /* 1 .. 16                                                              */
+    int32_t win, search_x, search_y;/* 0: the ctx's window_size_depth_calculator / search_x / search_y; else within
+                                       what svo_ssd_disparity accepts (win <= 35, search_x <= 64, search_y <= 8) */
+    int32_t cost;                   /* 0 / 1: the second plane                                              */
+    int32_t _reserved[2];           /* 0                                                                    */
+} svo_disparity_style;
+
+typedef struct svo_disparity_segment { /* 64 bytes, host, one per named slot                                */
+    int32_t seq, run;               /* slot and ordinal of its run (svo_run_info.run)                       */
+    int32_t frame_id;               /* of the slot's current frame; -1: empty slot                          */
+    int32_t keyframe_id;            /* LAST_KEYFRAMES: the keyframe used (-1: the slot has none); FRAMES: -1 */
+    int32_t status;                 /* SVO_DISPARITY_*                                                      */
+    int32_t _pad;
+    int64_t offset;                 /* the planes are bytes [offset, offset + planes * cols * rows * 4) of dst->values */
+    float   pose[6];                /* FRAMES: svo_get_pose; LAST_KEYFRAMES: the keyframe's pose            */
+    float   time_stamp;             /* of the slot's current frame                                          */
+    float   baseline;               /* of the slot's rig                                                    */
+} svo_disparity_segment;
+
+typedef struct svo_disparity_dst {
+    svo_disparity_segment *segments;/* HOST memory always, >= n entries                                     */
+    float  *values;                 /* host or device (mem); 16-byte aligned                                */
+    int64_t capacity;               /* bytes `values` holds                                                 */
+} svo_disparity_dst;
+
+/* the shape of one slot's planes of a job with that style in a ctx of these settings, without a GPU (any out pointer
+ * may be NULL); planes is 1 or 2. Settings svo_ctx_create rejects, or a style a job rejects: SVO_ERR_INVALID */
+int svo_disparity_size(const svo_camera_settings *cam, int width, int height, const svo_disparity_style *style,
+                       int *cols, int *rows, int *planes, int64_t *image_bytes);
+/* what: SVO_EXPORT_FRAMES (level 0 of the left pyramid and the right image of the slot's current frame; a slot that
+ * sat steps out uses its last frame) or SVO_EXPORT_LAST_KEYFRAMES (the image set of the newest keyframe; once it has
+ * given its images back the status is SVO_DISPARITY_NONE). These are the planes a view job shows for plane = LEFT,
+ * level = 0 and plane = RIGHT: after rectification and colour conversion, and under SVO_MEM_DEVICE_BORROW the
+ * caller's buffers, which the validity rule above keeps alive. Queued exactly as svo_submit_export_views is (seqs ==
+ * NULL names every slot in order, n is ignored): the job sees every frame set, restart, load and pose update
+ * submitted before it and none submitted after, only groups that own a named slot get work, no group waits for
+ * another, the slot is not changed (its deferred pose-filter update is flushed first). style and dst are copied;
+ * segments and values stay valid until svo_wait, after which everything is delivered. mem: SVO_MEM_HOST or
+ * SVO_MEM_DEVICE, of `values`.
+ * Rejected with SVO_ERR_INVALID and nothing queued: a slot out of range or named twice; a bad what, mem, value, cost
+ * or step; a window or search value outside the limits; cols or rows of 0; a _reserved != 0; NULL segments; values
+ * NULL or not 16-byte aligned; a failed ctx, as in svo_submit_images. SVO_ERR_CAPACITY: dst->capacity < named slots *
+ * image_bytes (the bound, so it is checked here).
+ * Host mode: a group computes its named slots densely into a device staging block, made by the group's first
+ * host-mode disparity job and replaced when outgrown (svo_memory.device_bytes), and copies each run of consecutive
+ * named slots out in one piece. Device mode writes in place and allocates nothing. A ctx that never asks for a
+ * disparity map allocates, launches and copies nothing more. */
+int svo_submit_export_disparity(svo_ctx *ctx, int what, const int *seqs, int n, const svo_disparity_style *style,
+                                const svo_disparity_dst *dst, int mem);
+int svo_export_disparity(svo_ctx *ctx, int what, const int *seqs, int n, const svo_disparity_style *style,
+                         const svo_disparity_dst *dst, int mem);   /* submit + wait */
+/* stage entry of the kernel: n image pairs in the job's launch (chunked when the diagnostic SVO_DENSE_TABLE_IMAGES
+ * bounds the image table). src[i].left / right: gray planes of one size (device memory, any base address, stride >=
+ * width, 1 .. 32768 pixels a side); the pairs of one call may differ in size. style->win, search_x and search_y must
+ * be given (1 .. 35, 0 .. 64, 0 .. 8); cols or rows of 0 for an image is rejected. The planes of pair i go to
+ * (char *)values + offset[i] (host array, >= 0, multiples of 16; values: device, 16-byte aligned). Exactly the
+ * planes' bytes are written. Complete on return. */
+typedef struct svo_dense_src {
+    svo_image left, right;
+    float     baseline;               /* SVO_DENSE_DEPTH: z = baseline / disparity                           */
+    int32_t   _reserved;              /* 0                                                                   */
+} svo_dense_src;
+int svo_dense_disparity(svo_handle *h, int n, const svo_dense_src *src, const int64_t *offset,
+                        const svo_disparity_style *style, float *values);
+
 /* ---- snapshots: the sequence state of a slot saved, loaded, moved between ctxs ------------
  * The reference has no checkpoint or resume (a StereoSlam lives and dies with its process). A snapshot is
  * everything the next frame of a slot depends on and everything its getters return, so that a sequence saved

@@ -1,6 +1,6 @@
 // svo_capi_tables.hip — the stage-level entries that take many images, sets or segments and build a table for one
-// launch: rectification and remap, frame ingest, keypoint and map export, the viewer's images and scenes, the AR picture, segment
-// copies, the pose filter. Every entry keeps a grow-only workspace of its own in the handle (svo_handle.hpp).
+// launch: rectification and remap, frame ingest, keypoint and map export, the viewer's images and scenes, the AR picture,
+// dense disparity maps, segment copies, the pose filter. Every entry keeps a grow-only workspace of its own in the handle (svo_handle.hpp).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -430,6 +430,54 @@ extern "C" int svo_render_ar(svo_handle* h, int n, const svo_ar_src* src, const 
     }
     return launch_tiles(h, tiles, reinterpret_cast<ArTile*>(base + draws_bytes + images_bytes + setup_bytes + records_bytes), chunk,
                         [&](const ArTile* d, int m, hipStream_t s) { launch_ar(d, m, d_images, params, s); });
+}
+
+extern "C" int svo_dense_disparity(svo_handle* h, int n, const svo_dense_src* src, const int64_t* offset,
+                                   const svo_disparity_style* style, float* values) {
+    CHECK_H(h);
+    if (n < 0 || (n > 0 && (!src || !offset))) return svo_set_error(SVO_ERR_INVALID, "svo_dense_disparity: bad arguments");
+    DenseParams params;
+    if (const int rc = dense_check_style(style, nullptr, "svo_dense_disparity", &params)) return rc;
+    if (!values || ((uintptr_t)values & 15)) return svo_set_error(SVO_ERR_INVALID, "svo_dense_disparity: values is NULL or not 16-byte aligned");
+    std::vector<DenseImage> images((size_t)n);
+    std::vector<int> tiles((size_t)n);
+    for (int i = 0; i < n; i++) {
+        const svo_image& l = src[i].left;
+        const svo_image& r = src[i].right;
+        if (!l.data || !r.data || l.width < 1 || l.height < 1 || l.width > (1 << 15) || l.height > (1 << 15) || r.width != l.width ||
+            r.height != l.height || l.stride < l.width || r.stride < r.width || src[i]._reserved != 0)
+            return svo_set_error(SVO_ERR_INVALID, "svo_dense_disparity: image %d: two device planes of one size, 1 .. 32768 pixels a side, stride >= width, _reserved 0", i);
+        if (l.width / params.step < 1 || l.height / params.step < 1)
+            return svo_set_error(SVO_ERR_INVALID, "svo_dense_disparity: image %d: %d x %d has no lattice point at step %d", i, l.width, l.height, params.step);
+        if (offset[i] < 0 || (offset[i] & 15)) return svo_set_error(SVO_ERR_INVALID, "svo_dense_disparity: image %d: offset must be >= 0 and a multiple of 16", i);
+        images[(size_t)i] = DenseImage{l.data, r.data, reinterpret_cast<float*>(reinterpret_cast<uint8_t*>(values) + offset[i]),
+                                       l.stride, r.stride, l.width, l.height, src[i].baseline, 0};
+        tiles[(size_t)i] = dense_tiles(params, l.width, l.height);
+    }
+    if (n == 0) return SVO_OK;
+    long long workgroups = 0;
+    for (int t : tiles) workgroups += t;
+    dense_plan(params, workgroups);
+    for (int i = 0; i < n; i++) tiles[(size_t)i] = dense_tiles(params, images[(size_t)i].w, images[(size_t)i].h);
+    // (SVO_DENSE_TABLE_IMAGES: a smaller table, so that tests reach the chunked launches)
+    const size_t chunk = table_tiles("SVO_DENSE_TABLE_IMAGES", std::min<size_t>((size_t)n, DENSE_MAX_IMAGES));
+    if (const int rc = h->dense_ws.reserve(sizeof(DenseImage) * chunk, h->stream)) return rc;
+    DenseImage* d_images = reinterpret_cast<DenseImage*>(h->dense_ws.ptr.get());
+    int rc = SVO_OK;
+    for (size_t i0 = 0; i0 < (size_t)n && rc == SVO_OK; i0 += chunk) {
+        const size_t m = std::min(chunk, (size_t)n - i0);
+        if (i0 > 0 && hipStreamSynchronize(h->stream) != hipSuccess) { rc = svo_set_error(SVO_ERR_HIP, "svo_dense_disparity: a launch failed"); break; }
+        if (hipMemcpyAsync(d_images, images.data() + i0, sizeof(DenseImage) * m, hipMemcpyHostToDevice, h->stream) != hipSuccess) {
+            rc = svo_set_error(SVO_ERR_HIP, "svo_dense_disparity: an upload failed");
+            break;
+        }
+        launch_dense(d_images, (int)m, *std::max_element(tiles.begin() + (ptrdiff_t)i0, tiles.begin() + (ptrdiff_t)(i0 + m)), params, h->stream);
+        if (hipGetLastError() != hipSuccess) rc = svo_set_error(SVO_ERR_HIP, "svo_dense_disparity: a launch failed");
+    }
+    const hipError_t e = hipStreamSynchronize(h->stream);    // (the uploads read host memory of this call)
+    if (rc) return rc;
+    HIP_TRY(e);
+    return SVO_OK;
 }
 
 extern "C" int svo_copy_segments(svo_handle* h, int n, const svo_copy_segment* segs) {

@@ -338,6 +338,9 @@ struct svo_group {
     svo::PinnedPtr<uint8_t> ar_in_host;
     uint8_t* d_ar_rec = nullptr; size_t ar_rec_bytes = 0;
     uint8_t* d_ar = nullptr; size_t ar_bytes = 0;
+    // disparity maps (grp_export_disparity) in host mode: the planes of one job, made by the first such job and
+    // replaced when outgrown
+    uint8_t* d_dense = nullptr; size_t dense_bytes = 0;
     // batched pose-filter updates (grp_pose_updates): the upload block (samples | filter states | start poses |
     // sample offsets) and behind it the download block (filter states | filtered poses) of one job, device and pinned,
     // made by the first such job and replaced when outgrown

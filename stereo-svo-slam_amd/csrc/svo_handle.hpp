@@ -46,6 +46,7 @@ struct svo_handle {
     svo_workspace view_ws;          // svo_render_views: the tile table
     svo_workspace scene_ws;         // svo_render_scene: the sets and image records of a call, then the tile table
     svo_workspace ar_ws;            // svo_render_ar: the draws, image records, work list and screen records of a call, then the tile table
+    svo_workspace dense_ws;         // svo_dense_disparity: the image table
 };
 
 #define CHECK_H(h)                                                   \

@@ -312,6 +312,36 @@ int ar_work(int image, int w, int h, const svo_ar_draw* draws, int n_draws, std:
 void launch_ar_setup(const ArSetup* d_setup, int n_setup, const ArImage* d_images, const ArParams& p, hipStream_t stream);
 void launch_ar(const ArTile* d_tiles, int n_tiles, const ArImage* d_images, const ArParams& p, hipStream_t stream);
 
+// ------------------------------------------------------------ dense disparity (dense.hip)
+// One image pair of a launch: the two gray planes (any base, strides >= w; both w x h), the planes at out (cols x rows
+// floats each, dense; 4-byte aligned) and the baseline of SVO_DENSE_DEPTH. One table entry per image: a workgroup
+// takes its image from blockIdx.y and computes its tile from blockIdx.x.
+struct DenseImage {
+    const uint8_t* left;
+    const uint8_t* right;
+    float* out;
+    int left_stride, right_stride, w, h;
+    float baseline;
+    int _pad;
+};
+// what a launch computes, from a checked svo_disparity_style whose win / search_x / search_y are resolved
+struct DenseParams {
+    int value, step, win, search_x, search_y, cost;
+    int band;          // lattice rows of a workgroup at most (dense_plan; the values do not depend on it)
+};
+// what a disparity job, svo_disparity_size and the stage entry check alike; win / search_x / search_y of 0 are taken
+// from cam (null: a 0 is rejected) before the limits are checked, into *out
+int dense_check_style(const svo_disparity_style* style, const svo_camera_settings* cam, const char* who, DenseParams* out);
+// cols, rows, planes and image_bytes of a w x h image pair (any out pointer may be null)
+void dense_shape(const DenseParams& p, int w, int h, int* cols, int* rows, int* planes, int64_t* image_bytes);
+// the workgroups of one w x h image: every launch's grid.x is the largest of its images'
+int dense_tiles(const DenseParams& p, int w, int h);
+// the band of a launch that would have so many workgroups with the full band (call before dense_tiles)
+void dense_plan(DenseParams& p, long long workgroups_at_full_band);
+// n images (<= DENSE_MAX_IMAGES), grid (tiles, n)
+constexpr size_t DENSE_MAX_IMAGES = 65535;
+void launch_dense(const DenseImage* d_images, int n, int tiles, const DenseParams& p, hipStream_t stream);
+
 // ------------------------------------------------------------ batched pose filter (pose_filter.hip)
 // n_states filter states, one lane each, POSE_FILTER_LANES per workgroup. State b runs samples
 // [first[b], first[b + 1]) (clamped to [0, n_samples)) in order; a state without samples is neither read nor written.

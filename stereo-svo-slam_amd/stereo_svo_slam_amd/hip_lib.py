@@ -41,6 +41,7 @@ SYMBOLS = (
     "svo_submit_pose_updates", "svo_update_poses", "svo_pose_filter_batch",
     "svo_map_size", "svo_submit_export_map", "svo_export_map", "svo_pack_map_points",
     "svo_view_size", "svo_submit_export_views", "svo_export_views", "svo_render_views",
+    "svo_disparity_size", "svo_submit_export_disparity", "svo_export_disparity", "svo_dense_disparity",
     "svo_scene_size", "svo_scene_look_at", "svo_scene_frustum", "svo_submit_export_scenes", "svo_export_scenes",
     "svo_render_scene",
     "svo_ar_size", "svo_ar_camera_of_pose", "svo_submit_export_ar", "svo_export_ar", "svo_render_ar",
@@ -373,6 +374,58 @@ class Keypoints(C.Structure):
 class ViewSrc(C.Structure):
     """svo_view_src (include/svo_hip.h): one image of svo_render_views."""
     _fields_ = [("image", Image), ("kps", Keypoints)]
+
+
+# dense disparity and depth maps (svo_submit_export_disparity, include/svo_hip.h): the value, a segment (one per named
+# slot)
+DENSE_DISPARITY, DENSE_DEPTH = 0, 1
+DENSE_VALUES = ("disparity", "depth")
+DISPARITY_OK, DISPARITY_NONE = 0, 1
+DISPARITY_SEGMENT_DTYPE = np.dtype([("seq", "<i4"), ("run", "<i4"), ("frame_id", "<i4"), ("keyframe_id", "<i4"),
+                                    ("status", "<i4"), ("_pad", "<i4"), ("offset", "<i8"), ("pose", "<f4", (6,)),
+                                    ("time_stamp", "<f4"), ("baseline", "<f4")])
+assert DISPARITY_SEGMENT_DTYPE.itemsize == 64
+
+
+class DisparityStyle(C.Structure):
+    """svo_disparity_style (include/svo_hip.h): what one disparity job computes."""
+    _fields_ = [("value", C.c_int32), ("step", C.c_int32), ("win", C.c_int32), ("search_x", C.c_int32),
+                ("search_y", C.c_int32), ("cost", C.c_int32), ("_reserved", C.c_int32 * 2)]
+
+
+class DisparitySegment(C.Structure):
+    """svo_disparity_segment (include/svo_hip.h); DISPARITY_SEGMENT_DTYPE is the same layout for numpy."""
+    _fields_ = [("seq", C.c_int32), ("run", C.c_int32), ("frame_id", C.c_int32), ("keyframe_id", C.c_int32),
+                ("status", C.c_int32), ("_pad", C.c_int32), ("offset", C.c_int64), ("pose", C.c_float * 6),
+                ("time_stamp", C.c_float), ("baseline", C.c_float)]
+
+
+class DisparityDst(C.Structure):
+    """svo_disparity_dst (include/svo_hip.h)."""
+    _fields_ = [("segments", C.c_void_p), ("values", C.c_void_p), ("capacity", C.c_int64)]
+
+
+class DenseSrc(C.Structure):
+    """svo_dense_src (include/svo_hip.h): one image pair of svo_dense_disparity."""
+    _fields_ = [("left", Image), ("right", Image), ("baseline", C.c_float), ("_reserved", C.c_int32)]
+
+
+assert (C.sizeof(DisparityStyle), C.sizeof(DisparitySegment), C.sizeof(DisparityDst), C.sizeof(DenseSrc)) == (32, 64, 24, 56)
+
+
+def disparity_style(value=DENSE_DISPARITY, step=1, win=0, search_x=0, search_y=0, cost=False):
+    """a DisparityStyle; value may be a name (DENSE_VALUES); win / search_x / search_y of 0: the ctx's settings"""
+    if isinstance(value, str):
+        value = DENSE_VALUES.index(value)
+    return DisparityStyle(int(value), int(step), int(win), int(search_x), int(search_y), int(bool(cost)))
+
+
+def disparity_size(cam, width, height, style):
+    """svo_disparity_size (host only): (cols, rows, planes, image_bytes) of one slot of a disparity job with `style`."""
+    cols, rows, planes, nbytes = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int64(0)
+    _check(lib().svo_disparity_size(C.byref(cam), int(width), int(height), C.byref(style), C.byref(cols), C.byref(rows),
+                                    C.byref(planes), C.byref(nbytes)))
+    return cols.value, rows.value, planes.value, nbytes.value
 
 
 # scenes (svo_submit_export_scenes, include/svo_hip.h): what is shown, the classes of the key, a line of the stage
@@ -923,6 +976,26 @@ class Handle:
         offs = (C.c_int64 * max(len(srcs), 1))(*[int(o) for o in offsets])
         p = pixels.data_ptr() if isinstance(pixels, torch.Tensor) else int(pixels)
         _check(lib().svo_render_views(self._h, len(srcs), arr, offs, C.byref(style), C.c_void_p(p)))
+
+    def pack_dense(self, srcs, offsets):
+        """the argument arrays of dense_disparity, built once (keeps Python out of a timed loop)"""
+        arr = (DenseSrc * max(len(srcs), 1))()
+        for i, (left, right, baseline) in enumerate(srcs):
+            for name, (data, w, h, stride) in (("left", left), ("right", right)):
+                setattr(arr[i], name, Image(data.data_ptr() if isinstance(data, torch.Tensor) else int(data), int(w), int(h), int(stride)))
+            arr[i].baseline = float(baseline)
+        return len(srcs), arr, (C.c_int64 * max(len(srcs), 1))(*[int(o) for o in offsets]), srcs
+
+    def dense_disparity_packed(self, packed, style, values):
+        p = values.data_ptr() if isinstance(values, torch.Tensor) else int(values)
+        _check(lib().svo_dense_disparity(self._h, packed[0], packed[1], packed[2], C.byref(style), C.c_void_p(p)))
+
+    def dense_disparity(self, srcs, offsets, style, values):
+        """svo_dense_disparity: dense disparity or depth planes of `style` (a DisparityStyle with win, search_x and
+        search_y given). srcs: per image pair (left, right, baseline) with left / right ((data address or uint8
+        device tensor [H, W]), width, height, stride); offsets[i]: the byte of `values` (a float32 device tensor, or
+        a raw device address) the planes of pair i start at. Complete on return."""
+        self.dense_disparity_packed(self.pack_dense(srcs, offsets), style, values)
 
     def render_scene(self, srcs, cameras, offsets, style, pixels):
         """svo_render_scene: the viewer's scene of keyframe sets and lines as images of `style` (a SceneStyle). srcs:

@@ -26,6 +26,8 @@ frames that are gray already give the CSV they gave before colour frames were co
 as binary PPM files, DIR/000000_keyframe.ppm (the last keyframe, a marker per keypoint) and DIR/000000_frame.ppm (the
 current frame): the gray image the tracker worked on, which with --gpu-rectify / --gpu-ingest only the GPU has seen.
 The text overlay and the x2 resize of the window are not drawn.
+--dump-disparity DIR [--disparity-step S] [--disparity-depth] writes per frame DIR/000000_disparity.npy: the dense
+disparity (or depth) map of the frame's rectified pair at every S-th pixel.
 --dump-scene DIR writes per frame DIR/000000_scene.ppm: the 3-D viewer's picture of the map so far
 (src/qt-viewer/PointCloudViewer.qml: points, trajectory, frusta) through its front camera.
 --dump-ar DIR writes per frame DIR/000000_ar.ppm: the AR demo's picture (src/ar-app/), a lit box of edge --ar-box
@@ -373,7 +375,7 @@ class Replay:
 
     def __init__(self, settings, device=0, time_trace=False, fast=False, rectify_maps=None, input_format=None,
                  gpu_imu=False, dump_views=None, dump_scene=None, calibration=None, keyframe_window=None, dump_ar=None,
-                 ar_box=AR_BOX, ar_at=hip_lib.AR_AT):
+                 ar_box=AR_BOX, ar_at=hip_lib.AR_AT, dump_disparity=None, disparity_step=4, disparity_depth=False):
         """fast=False keeps the library default: the reference-order Gauss-Newton (bit-exact traces).
         rectify_maps = (left maps, right maps): the frames fed are raw and are rectified on the GPU.
         calibration = (left, right) CameraCalibrations: the same, with the maps built on the GPU as well.
@@ -386,11 +388,14 @@ class Replay:
         dump_ar: a directory that receives, per frame, the AR demo's picture (get_ar): a lit box of edge ar_box at the
         world point ar_at over the frame's left image, likewise. The default is the demo's placement, half a metre in
         front of the first camera.
+        dump_disparity: a directory that receives, per frame, the dense disparity map of the frame (get_disparity at
+        the lattice disparity_step; the depth map with disparity_depth) as NNNNNN_disparity.npy [rows, cols], likewise.
         keyframe_window: the retired keyframes the tracker keeps (StereoSlamBatch.set_keyframe_window); None: all."""
         self.settings = settings
         self.dump_views, self.dump_scene, self.dump_ar = dump_views, dump_scene, dump_ar
         self.ar_objects = ar_objects(ar_box, ar_at)
-        for d in (dump_views, dump_scene, dump_ar):
+        self.dump_disparity, self.disparity_step, self.disparity_depth = dump_disparity, int(disparity_step), bool(disparity_depth)
+        for d in (dump_views, dump_scene, dump_ar, dump_disparity):
             if d:
                 os.makedirs(d, exist_ok=True)
         self.gpu_imu = gpu_imu
@@ -457,6 +462,10 @@ class Replay:
             img = self.slam.get_ar(self.ar_objects, pixel="rgb8")
             if img is not None:
                 write_ppm(os.path.join(self.dump_ar, f"{len(self.cumulative) - 1:06d}_ar.ppm"), img)
+        if self.dump_disparity:
+            planes = self.slam.get_disparity(value="depth" if self.disparity_depth else "disparity", step=self.disparity_step)
+            if planes is not None:
+                np.save(os.path.join(self.dump_disparity, f"{len(self.cumulative) - 1:06d}_disparity.npy"), planes[0])
         if self.time_trace:                       # like PRINT_TIME_TRACE of the reference
             print("\n".join(time_trace_lines(self.slam.stats())))
 
@@ -515,6 +524,11 @@ def build_parser():
     ap.add_argument("--ar-box", metavar="SIZE", type=float, default=AR_BOX, help="edge of the box of --dump-ar, metres")
     ap.add_argument("--ar-at", metavar="X,Y,Z", default=",".join(str(x) for x in hip_lib.AR_AT),
                     help="world point of the box's centre (default: half a metre in front of the first camera, as the demo)")
+    ap.add_argument("--dump-disparity", metavar="DIR",
+                    help="write per frame DIR/NNNNNN_disparity.npy: the dense disparity map of the frame's rectified pair "
+                         "(float32 [rows, cols]; -1 where the search window leaves the image)")
+    ap.add_argument("--disparity-step", metavar="S", type=int, default=4, help="lattice of --dump-disparity: every S-th pixel, 1 .. 16")
+    ap.add_argument("--disparity-depth", action="store_true", help="--dump-disparity writes depth, baseline / disparity (0: none)")
     ap.add_argument("--frames", type=int, default=100)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--rate", type=float, default=20.0, help="frames per second of the time stamps")
@@ -579,7 +593,8 @@ def main(argv=None):
     rp = Replay(settings, args.device, args.time_trace, args.fast, rectify_maps=rect, input_format=fmt, gpu_imu=args.gpu_imu,
                 dump_views=args.dump_views, dump_scene=args.dump_scene, calibration=cal, dump_ar=args.dump_ar,
                 ar_box=args.ar_box, ar_at=tuple(float(x) for x in args.ar_at.split(",")),
-                keyframe_window=args.keyframe_window)
+                keyframe_window=args.keyframe_window, dump_disparity=args.dump_disparity, disparity_step=args.disparity_step,
+                disparity_depth=args.disparity_depth)
     for k, (left, right, t) in enumerate(frames):
         rp.feed(left, right, t, None if gyro is None else gyro[gyro[:, 0] == k, 1:4])
     rows = rp.rows()

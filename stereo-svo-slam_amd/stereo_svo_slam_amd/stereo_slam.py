@@ -323,6 +323,55 @@ class Views:
         return a.reshape(shape)
 
 
+class Disparities:
+    """One svo_submit_export_disparity: owns the buffers the library writes. After wait(): `segments`
+    (hip_lib.DISPARITY_SEGMENT_DTYPE, one per named slot), `values` [slots, planes, rows, cols] float32 (a strided view
+    of the buffer: numpy over pinned memory in host mode, a torch tensor on the ctx's device in device mode; a slot
+    whose status is DISPARITY_NONE keeps what the buffer held) and planes(i). cols, rows, planes, image_bytes: the shape
+    of every slot of the job (svo_disparity_size)."""
+
+    def __init__(self, slam, what, seqs, style, device):
+        self._slam = slam
+        self.what, self.style, self.device_mode = int(what), style, bool(device)
+        self.seqs = None if seqs is None else [int(s) for s in seqs]
+        n = self._n = slam.n if seqs is None else len(self.seqs)
+        self.cols, self.rows, self.n_planes, self.image_bytes = slam.disparity_size(style)
+        self.capacity = n * self.image_bytes
+        self._seg = np.zeros(max(n, 1), hip_lib.DISPARITY_SEGMENT_DTYPE)
+        self.segments = self._seg[:n]
+        floats = max(self.capacity // 4, 4)
+        self._buf = (torch.zeros(floats, dtype=torch.float32, device=slam.device) if device
+                     else torch.zeros(floats, dtype=torch.float32, pin_memory=True))
+        self._dst = hip_lib.DisparityDst(self._seg.ctypes.data, self._buf.data_ptr(), self.capacity)
+        self._seq_arr = None if seqs is None else (C.c_int * max(n, 1))(*self.seqs)
+
+    @property
+    def values(self):
+        plane = self.rows * self.cols
+        v = torch.as_strided(self._buf, (self._n, self.n_planes, self.rows, self.cols), (self.image_bytes // 4, plane, self.cols, 1))
+        return v if self.device_mode else v.numpy()
+
+    def submit(self):
+        """queue the job (again: the same slots into the same buffers, once the previous one is delivered)"""
+        slam = self._slam
+        if self.device_mode:
+            torch.cuda.current_stream(slam.device).synchronize()     # (nothing of the caller's is still using the tensor)
+        _check(lib().svo_submit_export_disparity(slam._ctx, self.what, self._seq_arr, self._n, C.byref(self.style),
+                                                 C.byref(self._dst), hip_lib.MEM_DEVICE if self.device_mode else hip_lib.MEM_HOST))
+        return self
+
+    def wait(self):
+        self._slam.wait()
+        return self
+
+    def planes(self, i):
+        """the planes of named slot i: [planes, rows, cols], a view of `values`; None for a slot whose status is
+        DISPARITY_NONE"""
+        if int(self.segments[i]["status"]) != hip_lib.DISPARITY_OK:
+            return None
+        return self.values[i]
+
+
 class Scenes:
     """One svo_submit_export_scenes: owns the buffers the library writes. After wait(): `segments`
     (hip_lib.SCENE_SEGMENT_DTYPE, one per named slot) and image(i); `pixels` is the whole buffer, a numpy uint8 view
@@ -763,6 +812,28 @@ class StereoSlamBatch:
         """submit_views + wait"""
         return self.submit_views(what, seqs, **kw).wait()
 
+    def disparity_size(self, style):
+        """svo_disparity_size: (cols, rows, planes, image_bytes) of one slot of a disparity job with `style` in this ctx"""
+        return hip_lib.disparity_size(self.cam, self.width, self.height, style)
+
+    def submit_disparity(self, what="frames", seqs=None, value="disparity", step=1, win=0, search_x=0, search_y=0,
+                         cost=False, device=False, style=None):
+        """svo_submit_export_disparity: queue a dense disparity (value="disparity") or depth ("depth") map of the
+        current frames (what="frames") or newest keyframes ("last_keyframes") of the slots `seqs` (None: all, in
+        order) behind what was submitted so far; nothing is waited for. step: the lattice (1 .. 16); win, search_x,
+        search_y: 0 takes the ctx's settings; cost: a second plane with the minimum SSD; style: a
+        hip_lib.DisparityStyle instead of all these. Returns a Disparities, valid after its wait() (or the ctx's);
+        its submit() queues the same job again into the same buffers."""
+        if isinstance(what, str):
+            what = hip_lib.EXPORT_WHAT.index(what)
+        if style is None:
+            style = hip_lib.disparity_style(value, step, win, search_x, search_y, cost)
+        return Disparities(self, what, seqs, style, device).submit()
+
+    def export_disparity(self, what="frames", seqs=None, **kw):
+        """submit_disparity + wait"""
+        return self.submit_disparity(what, seqs, **kw).wait()
+
     def submit_scenes(self, seqs=None, camera="front", device=False, style=None, **kw):
         """svo_submit_export_scenes: queue the viewer's 3-D picture (keyframe points, trajectory, a frustum per
         keyframe and at the current pose) of the slots `seqs` (None: all, in order) behind what was submitted so far;
@@ -1189,6 +1260,16 @@ class StereoSlam(StereoSlamBatch):
         kw["device"] = False
         img = self.export_views(what, None, **kw).image(0)
         return None if img is None else img.copy()
+
+    def get_disparity(self, what="frames", **kw):
+        """the dense disparity (or, value="depth", depth) map of the current frame (or, what="last_keyframes", of the
+        newest keyframe) as a numpy array [planes, rows, cols] (export_disparity of the one slot: value, step, win,
+        search_x, search_y, cost); None when there is none"""
+        if self._ctx is None:
+            return None
+        kw["device"] = False
+        planes = self.export_disparity(what, None, **kw).planes(0)
+        return None if planes is None else planes.copy()
 
     def get_scene(self, camera="front", **kw):
         """the viewer's 3-D picture of the map as a numpy array [rows, cols, 3 | 4] (export_scenes of the one slot:
