@@ -1176,6 +1176,114 @@ typedef struct svo_dense_src {
 int svo_dense_disparity(svo_handle *h, int n, const svo_dense_src *src, const int64_t *offset,
                         const svo_disparity_style *style, float *values);
 
+/* ---- clouds: dense coloured point clouds of many slots in one queued job ------------
+ * A dense map ("dense" above) lives in image space; every consumer of this library's maps (the viewer reply, the
+ * scene, svo_export_map) carries svo_map_point records in the world frame. A cloud job is the 3-D form of the dense
+ * map: every lattice point becomes the kps3d the reference would give a new keypoint at that pixel
+ * (DepthCalculator::calculate_depth, src/lib/depth_calculator.cpp:241-256; kf_init_kernel), bit for bit, is filtered,
+ * coloured from the left plane and delivered as an svo_map_point, into host or device memory. Everything it needs
+ * (the rectified, converted planes, the slot's rig, the tracked pose) is on the device and nowhere else.
+ *
+ * Lattice: cols = W / step, rows = H / step, pixel x = ix * step + step / 2, y = iy * step + step / 2. For a lattice
+ * point, disp and best are exactly the two planes that a disparity job with value = SVO_DENSE_DISPARITY, cost = 1 and
+ * the same step, win, search_x, search_y gives (-1: an invalid point). The window and search defaults, the point rule
+ * and the argmin are those of "dense".
+ *
+ * Triangulation, in float32, every operation rounded once (no fused multiply-add), with the slot's rig fx, fy, cx, cy,
+ * baseline and a pose (x, y, z, rx, ry, rz):
+ *   _z = baseline / fmaxf(0.5f, disp);  _x = ((float)x - cx) / fx * _z;  _y = ((float)y - cy) / fy * _z
+ *   SVO_CLOUD_WORLD:  p = R * (_x, _y, _z) + t, with R = (float)Rodrigues(rx, ry, rz) computed in double and each row
+ *                     summed as s = 0; s += R[i][k] * v[k], k = 0, 1, 2 (PoseManager's float rotation matrix)
+ *   SVO_CLOUD_CAMERA: p = (_x, _y, _z)
+ *
+ * Filter: an invalid point is always dropped. A valid point is dropped if any of
+ *   disp < min_disparity;   _z > max_depth;   best > max_mean_cost * (float)(tw * th)
+ * holds, each one float32 comparison (the product rounded once); a filter value of 0 is off. tw, th: the clipped
+ * template box of the point rule (x12 - x11, y12 - y11).
+ *
+ * Record: one svo_map_point, 16 bytes: x, y, z = p's bits; color[0 .. 2] = L[y][x], the gray of the left plane;
+ * flags = 0.
+ *
+ * Layouts. points_per_slot = cols * rows; named slot i of a job owns records [i * points_per_slot, (i + 1) *
+ * points_per_slot) of dst->points, whatever group owns it.
+ *   SVO_CLOUD_COMPACT:   the kept points of a slot lie densely in row-major lattice order (iy outer, ix inner) from
+ *                        the slot's first record on: n_points records. The order is stable (two runs give the same
+ *                        bytes) and nothing beyond record n_points is written.
+ *   SVO_CLOUD_ORGANIZED: every lattice point has its record at iy * cols + ix. A dropped or invalid point gets
+ *                        x = y = z = +0.0f, the gray and flags = SVO_CLOUD_DROPPED (no SVO_IGNORE_* bit); n_points is
+ *                        still the kept count. */
+enum { SVO_CLOUD_WORLD = 0, SVO_CLOUD_CAMERA = 1 };
+enum { SVO_CLOUD_COMPACT = 0, SVO_CLOUD_ORGANIZED = 1 };
+enum { SVO_CLOUD_OK = 0,
+       SVO_CLOUD_NONE = 1 };        /* as SVO_DISPARITY_NONE: only the segment is written                   */
+enum { SVO_CLOUD_DROPPED = 0x80 };  /* svo_map_point.flags of a dropped point in the organized layout       */
+
+typedef struct svo_cloud_style {    /* 48 bytes; what one job computes; copied at submit                    */
+    int32_t step;                   /* 1 .. 16                                                              */
+    int32_t win, search_x, search_y;/* as in svo_disparity_style; 0: the ctx's settings                     */
+    int32_t frame;                  /* SVO_CLOUD_WORLD / SVO_CLOUD_CAMERA                                   */
+    int32_t layout;                 /* SVO_CLOUD_COMPACT / SVO_CLOUD_ORGANIZED                              */
+    float   min_disparity;          /* the three filter values: finite, >= 0; 0: off                        */
+    float   max_depth;
+    float   max_mean_cost;
+    int32_t _reserved[3];           /* 0                                                                    */
+} svo_cloud_style;
+
+typedef struct svo_cloud_segment {  /* 64 bytes, host, one per named slot                                   */
+    int32_t seq, run;               /* slot and ordinal of its run (svo_run_info.run)                       */
+    int32_t frame_id;               /* of the slot's current frame; -1: empty slot                          */
+    int32_t keyframe_id;            /* LAST_KEYFRAMES: the keyframe used (-1: the slot has none); FRAMES: -1 */
+    int32_t status;                 /* SVO_CLOUD_*                                                          */
+    int32_t n_points;               /* kept points (0 with SVO_CLOUD_NONE)                                  */
+    int64_t first_point;            /* the slot's records start at dst->points[first_point]                 */
+    float   pose[6];                /* the pose used. FRAMES: svo_get_pose; LAST_KEYFRAMES: the keyframe's  */
+    float   time_stamp;             /* of the slot's current frame                                          */
+    float   baseline;               /* of the slot's rig                                                    */
+} svo_cloud_segment;
+
+typedef struct svo_cloud_dst {
+    svo_cloud_segment *segments;    /* HOST memory always, >= n entries                                     */
+    svo_map_point     *points;      /* host or device (mem); 16-byte aligned                                */
+    int64_t            capacity;    /* records `points` holds                                               */
+} svo_cloud_dst;
+
+/* the lattice of one slot of a job with that style in a ctx of these settings, without a GPU (any out pointer may be
+ * NULL). Settings svo_ctx_create rejects, or a style a job rejects: SVO_ERR_INVALID */
+int svo_cloud_size(const svo_camera_settings *cam, int width, int height, const svo_cloud_style *style, int *cols,
+                   int *rows, int64_t *points_per_slot);
+/* what, seqs, n, mem, the planes read, the queueing and the lifetime of style, dst, segments and points: exactly as
+ * svo_submit_export_disparity. The job sees every frame set, restart, load and pose update submitted before it and
+ * none submitted after; only groups that own a named slot get work; the slot is not changed.
+ * Rejected with SVO_ERR_INVALID and nothing queued: everything svo_submit_export_disparity rejects (points in the
+ * place of values); a bad frame or layout; a filter value that is negative or not finite. SVO_ERR_CAPACITY:
+ * dst->capacity < named slots * points_per_slot (the bound, so it is checked here).
+ * Memory: a group searches into a staging block of its own (not the disparity job's), made by the group's first cloud
+ * job and replaced when outgrown (svo_memory.device_bytes). Per named slot of the group it holds the disparity and
+ * cost planes, the tile counts, the pose's matrices and the kept count, and in host mode the slot's records:
+ *   slot_bytes = up256(2 * 4 * points_per_slot) + up256(4 * ceil(points_per_slot / 256)) + 256 + (host ? 16 * points_per_slot : 0)
+ *   block      = min(named slots of the group, chunk) * slot_bytes + up256(4 * min(named slots of the group, chunk))
+ * with up256 rounding up to a multiple of 256 and chunk = max(1, 256 MiB / slot_bytes) (the diagnostic
+ * SVO_CLOUD_CHUNK_SLOTS lowers it): a job with more slots runs in chunks of so many. Host mode copies out each
+ * slot's kept prefix (compact) or runs of consecutive slots (organized); the kept counts of a chunk come back in one
+ * copy. A ctx that never asks for a cloud allocates, launches and copies nothing more. */
+int svo_submit_export_cloud(svo_ctx *ctx, int what, const int *seqs, int n, const svo_cloud_style *style,
+                            const svo_cloud_dst *dst, int mem);
+int svo_export_cloud(svo_ctx *ctx, int what, const int *seqs, int n, const svo_cloud_style *style,
+                     const svo_cloud_dst *dst, int mem);   /* submit + wait */
+/* stage entry of the kernels: n image pairs (chunked when the diagnostic SVO_CLOUD_TABLE_IMAGES bounds the image
+ * table). src[i].left / right as in svo_dense_src; the pairs of one call may differ in size. style->win, search_x and
+ * search_y must be given. The records of pair i start at points[first[i]] (host array, >= 0; points: device, 16-byte
+ * aligned): n_points of them in the compact layout, cols * rows in the organized one; nothing else is written.
+ * counts: device int32[n], the kept count of every pair, or NULL. Complete on return. */
+typedef struct svo_cloud_src {       /* 96 bytes */
+    svo_image left, right;
+    float     baseline, fx, fy, cx, cy;
+    float     pose[6];                /* SVO_CLOUD_WORLD: x, y, z, rx, ry, rz                                 */
+    int32_t   _reserved;              /* 0                                                                   */
+} svo_cloud_src;
+int svo_cloud_points(svo_handle *h, int n, const svo_cloud_src *src, const int64_t *first, const svo_cloud_style *style,
+                     svo_map_point *points, int32_t *counts);
+
 /* ---- snapshots: the sequence state of a slot saved, loaded, moved between ctxs ------------
  * The reference has no checkpoint or resume (a StereoSlam lives and dies with its process). A snapshot is
  * everything the next frame of a slot depends on and everything its getters return, so that a sequence saved

@@ -475,12 +475,10 @@ __global__ __launch_bounds__(256) void kf_init_kernel(const KfInitArgs* __restri
     for (int i = old_count + tid; i < n; i += 256) {
         const svo_kp2d kp = G(a.kps.kps2d)[i];
         const float disparity = G(a.disparity)[i];
-        const float _z = baseline / fmaxf(0.5f, disparity);
-        const float _x = (kp.x - cx) / fx * _z;
-        const float _y = (kp.y - cy) / fy * _z;
-        float loc[3] = {_x, _y, _z};
-        mat33f_vec(pm.R, loc, loc);
-        G(a.kps.kps3d)[i] = svo_kp3d{loc[0] + pm.t[0], loc[1] + pm.t[1], loc[2] + pm.t[2]};
+        float loc[3];
+        kp_triangulate(kp.x, kp.y, disparity, fx, fy, cx, cy, baseline, loc);
+        const float _z = loc[2];
+        G(a.kps.kps3d)[i] = kp_to_world(pm, loc);
         uint32_t st = lcg0;
         for (int q = old_count; q <= i; q++) st = st * 1664525u + 1013904223u;
         G(a.kps.color)[i] = (st >> 8) & 0xFFFFFFu;

@@ -1,6 +1,6 @@
 // svo_capi_tables.hip — the stage-level entries that take many images, sets or segments and build a table for one
 // launch: rectification and remap, frame ingest, keypoint and map export, the viewer's images and scenes, the AR picture,
-// dense disparity maps, segment copies, the pose filter. Every entry keeps a grow-only workspace of its own in the handle (svo_handle.hpp).
+// dense disparity maps and point clouds, segment copies, the pose filter. Every entry keeps a grow-only workspace of its own in the handle (svo_handle.hpp).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -473,6 +473,89 @@ extern "C" int svo_dense_disparity(svo_handle* h, int n, const svo_dense_src* sr
         }
         launch_dense(d_images, (int)m, *std::max_element(tiles.begin() + (ptrdiff_t)i0, tiles.begin() + (ptrdiff_t)(i0 + m)), params, h->stream);
         if (hipGetLastError() != hipSuccess) rc = svo_set_error(SVO_ERR_HIP, "svo_dense_disparity: a launch failed");
+    }
+    const hipError_t e = hipStreamSynchronize(h->stream);    // (the uploads read host memory of this call)
+    if (rc) return rc;
+    HIP_TRY(e);
+    return SVO_OK;
+}
+
+extern "C" int svo_cloud_points(svo_handle* h, int n, const svo_cloud_src* src, const int64_t* first, const svo_cloud_style* style,
+                                svo_map_point* points, int32_t* counts) {
+    CHECK_H(h);
+    if (n < 0 || (n > 0 && (!src || !first))) return svo_set_error(SVO_ERR_INVALID, "svo_cloud_points: bad arguments");
+    DenseParams search;
+    CloudParams params;
+    if (const int rc = cloud_check_style(style, nullptr, "svo_cloud_points", &search, &params)) return rc;
+    if (!points || ((uintptr_t)points & 15)) return svo_set_error(SVO_ERR_INVALID, "svo_cloud_points: points is NULL or not 16-byte aligned");
+    if ((uintptr_t)counts & 3) return svo_set_error(SVO_ERR_INVALID, "svo_cloud_points: counts is not 4-byte aligned");
+    // per image of a chunk: its two planes, its tile counts and its pose matrices, each rounded up to 256 bytes
+    std::vector<size_t> image_block((size_t)n + 1, 0);
+    for (int i = 0; i < n; i++) {
+        const svo_image& l = src[i].left;
+        const svo_image& r = src[i].right;
+        if (!l.data || !r.data || l.width < 1 || l.height < 1 || l.width > (1 << 15) || l.height > (1 << 15) || r.width != l.width ||
+            r.height != l.height || l.stride < l.width || r.stride < r.width || src[i]._reserved != 0)
+            return svo_set_error(SVO_ERR_INVALID, "svo_cloud_points: image %d: two device planes of one size, 1 .. 32768 pixels a side, stride >= width, _reserved 0", i);
+        if (l.width / params.step < 1 || l.height / params.step < 1)
+            return svo_set_error(SVO_ERR_INVALID, "svo_cloud_points: image %d: %d x %d has no lattice point at step %d", i, l.width, l.height, params.step);
+        if (first[i] < 0) return svo_set_error(SVO_ERR_INVALID, "svo_cloud_points: image %d: first must be >= 0", i);
+        const size_t pts = (size_t)(l.width / params.step) * (size_t)(l.height / params.step);
+        image_block[(size_t)i + 1] = (pts * 8 + 255) / 256 * 256 + ((size_t)cloud_tiles((int64_t)pts) * 4 + 255) / 256 * 256 + 256;
+    }
+    if (n == 0) return SVO_OK;
+    // (SVO_CLOUD_TABLE_IMAGES: a smaller table, so that tests reach the chunked launches. SVO_CLOUD_SKIP_SEARCH=1: a
+    // measurement's switch, tools/cloud_bench.py: the search is not launched and the count and write launches run on the
+    // planes the workspace holds from the call before, so that their time can be taken alone)
+    const size_t chunk = table_tiles("SVO_CLOUD_TABLE_IMAGES", std::min<size_t>((size_t)n, DENSE_MAX_IMAGES));
+    const char* skip_env = std::getenv("SVO_CLOUD_SKIP_SEARCH");
+    const bool skip_search = skip_env && std::atoi(skip_env) == 1;
+    const size_t tables = ((sizeof(CloudImage) + sizeof(DenseImage)) * chunk + 255) / 256 * 256;
+    size_t block = 0;
+    for (size_t i0 = 0; i0 < (size_t)n; i0 += chunk) {
+        size_t b = 0;
+        for (size_t i = i0; i < std::min(i0 + chunk, (size_t)n); i++) b += image_block[i + 1];
+        block = std::max(block, b);
+    }
+    if (const int rc = h->cloud_ws.reserve(tables + block, h->stream)) return rc;
+    CloudImage* d_cloud = reinterpret_cast<CloudImage*>(h->cloud_ws.ptr.get());
+    DenseImage* d_dense = reinterpret_cast<DenseImage*>(d_cloud + chunk);
+    std::vector<CloudImage> cloud(chunk);
+    std::vector<DenseImage> dense(chunk);
+    int rc = SVO_OK;
+    for (size_t i0 = 0; i0 < (size_t)n && rc == SVO_OK; i0 += chunk) {
+        const size_t m = std::min(chunk, (size_t)n - i0);
+        if (i0 > 0 && hipStreamSynchronize(h->stream) != hipSuccess) { rc = svo_set_error(SVO_ERR_HIP, "svo_cloud_points: a launch failed"); break; }
+        uint8_t* at = h->cloud_ws.ptr.get() + tables;
+        long long workgroups = 0;
+        int cloud_grid = 0;
+        for (size_t j = 0; j < m; j++) {
+            const svo_cloud_src& s = src[i0 + j];
+            const size_t pts = (size_t)(s.left.width / params.step) * (size_t)(s.left.height / params.step);
+            float* planes = reinterpret_cast<float*>(at);
+            int* tile_counts = reinterpret_cast<int*>(at + (pts * 8 + 255) / 256 * 256);
+            float* mats = reinterpret_cast<float*>(at + image_block[i0 + j + 1] - 256);
+            at += image_block[i0 + j + 1];
+            dense[j] = DenseImage{s.left.data, s.right.data, planes, s.left.stride, s.right.stride, s.left.width, s.left.height, s.baseline, 0};
+            CloudImage& c = cloud[j];
+            c = CloudImage{s.left.data, planes, planes + pts, points + first[i0 + j], tile_counts, counts ? counts + (i0 + j) : nullptr,
+                           s.left.stride, s.left.width, s.left.height, s.baseline, s.fx, s.fy, s.cx, s.cy, {}, mats};
+            std::memcpy(c.pose, s.pose, sizeof(c.pose));
+            workgroups += dense_tiles(search, s.left.width, s.left.height);
+            cloud_grid = std::max(cloud_grid, cloud_tiles((int64_t)pts));
+        }
+        DenseParams sp = search;
+        dense_plan(sp, workgroups);
+        int dense_grid = 0;
+        for (size_t j = 0; j < m; j++) dense_grid = std::max(dense_grid, dense_tiles(sp, dense[j].w, dense[j].h));
+        if (hipMemcpyAsync(d_cloud, cloud.data(), sizeof(CloudImage) * m, hipMemcpyHostToDevice, h->stream) != hipSuccess ||
+            hipMemcpyAsync(d_dense, dense.data(), sizeof(DenseImage) * m, hipMemcpyHostToDevice, h->stream) != hipSuccess) {
+            rc = svo_set_error(SVO_ERR_HIP, "svo_cloud_points: an upload failed");
+            break;
+        }
+        if (!skip_search) launch_dense(d_dense, (int)m, dense_grid, sp, h->stream);
+        launch_cloud(d_cloud, (int)m, cloud_grid, params, h->stream);
+        if (hipGetLastError() != hipSuccess) rc = svo_set_error(SVO_ERR_HIP, "svo_cloud_points: a launch failed");
     }
     const hipError_t e = hipStreamSynchronize(h->stream);    // (the uploads read host memory of this call)
     if (rc) return rc;

@@ -31,7 +31,7 @@
 // single-workgroup-per-sequence alignment kernel of one group overlaps the window kernels of
 // the other. svo_submit_images() queues a frame set on every group and returns;
 // svo_wait() drains the queues. svo_new_images() = submit + wait. Restarts (svo_ctx_restart_sequences),
-// exports (svo_submit_export, svo_submit_export_map, svo_submit_export_views, svo_submit_export_disparity, svo_submit_export_scenes, svo_submit_export_ar), saves and loads (svo_submit_save / svo_submit_load) and pose-filter updates
+// exports (svo_submit_export, svo_submit_export_map, svo_submit_export_views, svo_submit_export_disparity, svo_submit_export_cloud, svo_submit_export_scenes, svo_submit_export_ar), saves and loads (svo_submit_save / svo_submit_load) and pose-filter updates
 // (svo_submit_pose_updates) are entries of the same queues, so they are ordered with the frame sets.
 struct svo_ctx {
     // the group's share of an svo_submit_export: its named slots (indices in the group) in named order, the
@@ -66,6 +66,13 @@ struct svo_ctx {
         std::vector<int> seqs, seg;
         svo_disparity_style style{};
         svo_disparity_dst dst{};
+    };
+    // the group's share of an svo_submit_export_cloud: as DisparityExport, records in the place of planes
+    struct CloudExport {
+        int what = 0, mem = 0;
+        std::vector<int> seqs, seg;
+        svo_cloud_style style{};
+        svo_cloud_dst dst{};
     };
     // the group's share of an svo_submit_export_scenes: its named slots (indices in the group) in named order, the
     // camera of each and the segment (and image) of the job each one fills
@@ -102,7 +109,7 @@ struct svo_ctx {
     // one entry of a group's queue: a frame set, or (restart non-empty) the end of some of its sequences, or
     // (exp.seqs non-empty) an export, or (snap.seqs / snap.loads non-empty) a save / a load, or (pose.seqs non-empty)
     // pose-filter updates, or (map.seqs non-empty) a map export, or (view.seqs non-empty) a view job, or (scene.seqs
-    // non-empty) a scene job, or (ar.seqs non-empty) an ar job, or (disp.seqs non-empty) a disparity job, or (assign non-empty) a rig assignment, or (trim non-empty) a trim of keyframes
+    // non-empty) a scene job, or (ar.seqs non-empty) an ar job, or (disp.seqs non-empty) a disparity job, or (cloud.seqs non-empty) a cloud job, or (assign non-empty) a rig assignment, or (trim non-empty) a trim of keyframes
     struct Job {
         std::vector<const uint8_t*> left, right;
         std::vector<float> ts;
@@ -117,6 +124,7 @@ struct svo_ctx {
         MapExport map;
         ViewExport view;
         DisparityExport disp;
+        CloudExport cloud;
         SceneExport scene;
         ArExport ar;
     };
@@ -175,7 +183,10 @@ void worker_run_job(svo_ctx::Worker& w, const svo_ctx::Job& job) {
     const svo_ctx::SceneExport& sc = job.scene;
     const svo_ctx::ArExport& ar = job.ar;
     const svo_ctx::DisparityExport& dp = job.disp;
-    const int rc = !dp.seqs.empty()
+    const svo_ctx::CloudExport& cl = job.cloud;
+    const int rc = !cl.seqs.empty()
+                       ? grp_export_cloud(w.g.get(), cl.what, cl.mem, cl.seqs.data(), cl.seg.data(), (int)cl.seqs.size(), w.first, &cl.style, &cl.dst)
+                   : !dp.seqs.empty()
                        ? grp_export_disparity(w.g.get(), dp.what, dp.mem, dp.seqs.data(), dp.seg.data(), (int)dp.seqs.size(), w.first, &dp.style, &dp.dst)
                    : !ar.seqs.empty()
                        ? grp_export_ar(w.g.get(), ar.mem, ar.seqs.data(), ar.seg.data(), ar.inst0.data(), ar.inst1.data(), (int)ar.seqs.size(), w.first, ar.job.get(), &ar.dst)
@@ -624,6 +635,49 @@ extern "C" int svo_submit_export_disparity(svo_ctx* c, int what, const int* seqs
 extern "C" int svo_export_disparity(svo_ctx* c, int what, const int* seqs, int n, const svo_disparity_style* style,
                                     const svo_disparity_dst* dst, int mem) {
     const int rc = svo_submit_export_disparity(c, what, seqs, n, style, dst, mem);
+    return rc ? rc : svo_wait(c);
+}
+
+extern "C" int svo_submit_export_cloud(svo_ctx* c, int what, const int* seqs, int n, const svo_cloud_style* style,
+                                       const svo_cloud_dst* dst, int mem) {
+    if (!c || !dst || !dst->segments || (what != SVO_EXPORT_FRAMES && what != SVO_EXPORT_LAST_KEYFRAMES) ||
+        (mem != SVO_MEM_HOST && mem != SVO_MEM_DEVICE) || (seqs && n < 0))
+        return svo_set_error(SVO_ERR_INVALID, "svo_submit_export_cloud: bad arguments (what %d, mem %d)", what, mem);
+    const svo_group* g0 = c->workers[0]->g.get();                    // (every group has the same settings)
+    if (const int rc = grp_check_cloud_style(g0, style)) return rc;
+    if (!dst->points || ((uintptr_t)dst->points & 15))
+        return svo_set_error(SVO_ERR_INVALID, "svo_submit_export_cloud: points is NULL or not 16-byte aligned");
+    if (!seqs) n = c->B;
+    std::vector<char> named(c->B, 0);
+    for (int i = 0; i < n; i++) {
+        const int s = seqs ? seqs[i] : i;
+        if (s < 0 || s >= c->B || named[s])
+            return svo_set_error(SVO_ERR_INVALID, "svo_submit_export_cloud: sequence %d is out of range or named twice", s);
+        named[s] = 1;
+    }
+    const int64_t per_slot = grp_cloud_points(g0, style);
+    if (dst->capacity < n * per_slot)
+        return svo_set_error(SVO_ERR_CAPACITY, "svo_submit_export_cloud: %d slots need %lld records, capacity %lld", n,
+                             (long long)(n * per_slot), (long long)dst->capacity);
+    if (c->failed.load()) return reject_failed(c, "svo_submit_export_cloud");
+    for (auto& wp : c->workers) {
+        svo_ctx::Worker& w = *wp;
+        svo_ctx::Job job;
+        svo_ctx::CloudExport& e = job.cloud;
+        for (int i = 0; i < n; i++) {
+            const int s = seqs ? seqs[i] : i;
+            if (s >= w.first && s < w.first + w.count) { e.seqs.push_back(s - w.first); e.seg.push_back(i); }
+        }
+        if (e.seqs.empty()) continue;
+        e.what = what; e.mem = mem; e.style = *style; e.dst = *dst;
+        worker_submit(w, std::move(job));
+    }
+    return SVO_OK;
+}
+
+extern "C" int svo_export_cloud(svo_ctx* c, int what, const int* seqs, int n, const svo_cloud_style* style,
+                                const svo_cloud_dst* dst, int mem) {
+    const int rc = svo_submit_export_cloud(c, what, seqs, n, style, dst, mem);
     return rc ? rc : svo_wait(c);
 }
 

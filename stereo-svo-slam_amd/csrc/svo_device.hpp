@@ -226,6 +226,23 @@ __device__ inline void mat33f_vec(const float* a, const float v[3], float out[3]
     out[0] = t[0]; out[1] = t[1]; out[2] = t[2];
 }
 
+// The kps3d a new keypoint gets (DepthCalculator::calculate_depth, src/lib/depth_calculator.cpp:241-256): the camera
+// frame point of the pixel (x, y) with that disparity into loc (loc[2] is the reference's _z), and loc in the world
+// frame of a pose. kf_init_kernel (keyframe.hip) and the cloud kernels (cloud.hip) both call these, so the two cannot
+// drift.
+__device__ inline void kp_triangulate(float x, float y, float disparity, float fx, float fy, float cx, float cy, float baseline,
+                                      float loc[3]) {
+    const float _z = baseline / fmaxf(0.5f, disparity);
+    const float _x = (x - cx) / fx * _z;
+    const float _y = (y - cy) / fy * _z;
+    loc[0] = _x; loc[1] = _y; loc[2] = _z;
+}
+__device__ inline svo_kp3d kp_to_world(const PoseMats& pm, const float loc[3]) {
+    float w[3];
+    mat33f_vec(pm.R, loc, w);
+    return svo_kp3d{w[0] + pm.t[0], w[1] + pm.t[1], w[2] + pm.t[2]};
+}
+
 // project_keypoints, src/lib/transform_keypoints.cpp:11-48: translate by -t in
 // float, then cv::projectPoints(rvec = -r, tvec = 0) in double, float store.
 struct CamD {

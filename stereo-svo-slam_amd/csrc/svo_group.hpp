@@ -1,7 +1,7 @@
 // svo_group.hpp — one group of sequences as svo_ctx.hip drives it: the opaque interface of svo_group.hip (creation,
 // settings, restarts), svo_group_step.hip (grp_new_images), svo_group_export.hip (grp_export, grp_capacity),
 // svo_group_map.hip (grp_export_map, grp_map_size), svo_group_view.hip (grp_export_views, grp_view_bytes),
-// svo_group_scene.hip (grp_export_scenes, grp_scene_bytes), svo_group_ar.hip (grp_export_ar, grp_ar_bytes), svo_group_dense.hip (grp_export_disparity, grp_disparity_bytes),
+// svo_group_scene.hip (grp_export_scenes, grp_scene_bytes), svo_group_ar.hip (grp_export_ar, grp_ar_bytes), svo_group_dense.hip (grp_export_disparity, grp_disparity_bytes), svo_group_cloud.hip (grp_export_cloud, grp_cloud_points),
 // svo_group_snapshot.hip (grp_check_snapshot, grp_save, grp_load, grp_snapshot_size) and svo_group_pose.hip
 // (grp_pose_updates).
 #pragma once
@@ -97,6 +97,14 @@ int grp_export_disparity(svo_group* g, int what, int mem, const int* seqs, const
 // changes in a group)
 int grp_check_disparity_style(const svo_group* g, const svo_disparity_style* style);
 int64_t grp_disparity_bytes(const svo_group* g, const svo_disparity_style* style);
+// One group's share of svo_submit_export_cloud (svo_group_cloud.hip), as grp_export_disparity: slot seqs[i] fills
+// dst->segments[seg[i]] and its records start at record seg[i] * points_per_slot of dst->points. style: checked
+// (grp_check_cloud_style). Delivered on return. A failed group rejects it.
+int grp_export_cloud(svo_group* g, int what, int mem, const int* seqs, const int* seg, int n, int seq0, const svo_cloud_style* style,
+                     const svo_cloud_dst* dst);
+// what svo_submit_export_cloud checks of a style, and the points_per_slot of a checked one
+int grp_check_cloud_style(const svo_group* g, const svo_cloud_style* style);
+int64_t grp_cloud_points(const svo_group* g, const svo_cloud_style* style);
 // what svo_map_size reports of a slot (the queues have drained)
 void grp_map_size(const svo_group* g, int seq, int from_keyframe, int* keyframes, int64_t* points_bound, int* from = nullptr);
 // Snapshots (svo_submit_save / svo_submit_load). grp_check_snapshot: everything svo_submit_load checks of one

@@ -341,6 +341,11 @@ struct svo_group {
     // disparity maps (grp_export_disparity) in host mode: the planes of one job, made by the first such job and
     // replaced when outgrown
     uint8_t* d_dense = nullptr; size_t dense_bytes = 0;
+    // point clouds (grp_export_cloud): the staging block of one chunk of a job (planes | tile counts and pose matrices |
+    // in host mode records | kept counts) and the pinned mirror of the kept counts, made by the first such job and
+    // replaced when outgrown
+    uint8_t* d_cloud = nullptr; size_t cloud_bytes = 0;
+    svo::PinnedPtr<int> cloud_counts_host; size_t cloud_counts_cap = 0;
     // batched pose-filter updates (grp_pose_updates): the upload block (samples | filter states | start poses |
     // sample offsets) and behind it the download block (filter states | filtered poses) of one job, device and pinned,
     // made by the first such job and replaced when outgrown

@@ -342,6 +342,37 @@ void dense_plan(DenseParams& p, long long workgroups_at_full_band);
 constexpr size_t DENSE_MAX_IMAGES = 65535;
 void launch_dense(const DenseImage* d_images, int n, int tiles, const DenseParams& p, hipStream_t stream);
 
+// ------------------------------------------------------------ dense point clouds (cloud.hip)
+// One image of a launch: the left plane (the gray of a record), the disparity and cost planes of a search over its
+// lattice (cols x rows floats each, dense: dense_disparity_kernel's with cost), where its records start, its tile
+// counts (one int per tile of CLOUD_TILE lattice points; written by the count launch, read by the write launch), its
+// kept count (null: not reported), the rig, the pose and 48 bytes for the pose's matrices. One table entry per image: a workgroup takes its image
+// from blockIdx.y and its tile from blockIdx.x.
+constexpr int CLOUD_TILE = 256;
+struct CloudImage {
+    const uint8_t* left;
+    const float* disp;
+    const float* best;
+    svo_map_point* points;
+    int* tile_counts;
+    int* n_points;
+    int left_stride, w, h;
+    float baseline, fx, fy, cx, cy;
+    float pose[6];
+    float* mats;       // 12 floats of the image's own: the pose's float rotation matrix and translation (the count launch writes them, the write launch reads them)
+};
+// what a launch computes, from a checked svo_cloud_style whose win is resolved
+struct CloudParams {
+    int step, win, frame, layout;
+    float min_disparity, max_depth, max_mean_cost;
+};
+// what a cloud job, svo_cloud_size and the stage entry check alike (win / search_x / search_y as dense_check_style):
+// the search of the job into *search (a disparity plane and a cost plane), the rest into *out
+int cloud_check_style(const svo_cloud_style* style, const svo_camera_settings* cam, const char* who, DenseParams* search, CloudParams* out);
+constexpr int cloud_tiles(int64_t points) { return (int)((points + CLOUD_TILE - 1) / CLOUD_TILE); }
+// n images (<= DENSE_MAX_IMAGES), grid (tiles, n) twice: the count launch, then the write launch
+void launch_cloud(const CloudImage* d_images, int n, int tiles, const CloudParams& p, hipStream_t stream);
+
 // ------------------------------------------------------------ batched pose filter (pose_filter.hip)
 // n_states filter states, one lane each, POSE_FILTER_LANES per workgroup. State b runs samples
 // [first[b], first[b + 1]) (clamped to [0, n_samples)) in order; a state without samples is neither read nor written.

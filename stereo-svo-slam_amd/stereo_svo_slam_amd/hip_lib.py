@@ -42,6 +42,7 @@ SYMBOLS = (
     "svo_map_size", "svo_submit_export_map", "svo_export_map", "svo_pack_map_points",
     "svo_view_size", "svo_submit_export_views", "svo_export_views", "svo_render_views",
     "svo_disparity_size", "svo_submit_export_disparity", "svo_export_disparity", "svo_dense_disparity",
+    "svo_cloud_size", "svo_submit_export_cloud", "svo_export_cloud", "svo_cloud_points",
     "svo_scene_size", "svo_scene_look_at", "svo_scene_frustum", "svo_submit_export_scenes", "svo_export_scenes",
     "svo_render_scene",
     "svo_ar_size", "svo_ar_camera_of_pose", "svo_submit_export_ar", "svo_export_ar", "svo_render_ar",
@@ -426,6 +427,68 @@ def disparity_size(cam, width, height, style):
     _check(lib().svo_disparity_size(C.byref(cam), int(width), int(height), C.byref(style), C.byref(cols), C.byref(rows),
                                     C.byref(planes), C.byref(nbytes)))
     return cols.value, rows.value, planes.value, nbytes.value
+
+
+# dense point clouds (svo_submit_export_cloud, include/svo_hip.h): the frame, the layout, a segment (one per named
+# slot); the records are MAP_POINT_DTYPE
+CLOUD_WORLD, CLOUD_CAMERA = 0, 1
+CLOUD_FRAMES = ("world", "camera")
+CLOUD_COMPACT, CLOUD_ORGANIZED = 0, 1
+CLOUD_LAYOUTS = ("compact", "organized")
+CLOUD_OK, CLOUD_NONE = 0, 1
+CLOUD_DROPPED = 0x80
+CLOUD_SEGMENT_DTYPE = np.dtype([("seq", "<i4"), ("run", "<i4"), ("frame_id", "<i4"), ("keyframe_id", "<i4"),
+                                ("status", "<i4"), ("n_points", "<i4"), ("first_point", "<i8"), ("pose", "<f4", (6,)),
+                                ("time_stamp", "<f4"), ("baseline", "<f4")])
+assert CLOUD_SEGMENT_DTYPE.itemsize == 64
+
+
+class CloudStyle(C.Structure):
+    """svo_cloud_style (include/svo_hip.h): what one cloud job computes."""
+    _fields_ = [("step", C.c_int32), ("win", C.c_int32), ("search_x", C.c_int32), ("search_y", C.c_int32),
+                ("frame", C.c_int32), ("layout", C.c_int32), ("min_disparity", C.c_float), ("max_depth", C.c_float),
+                ("max_mean_cost", C.c_float), ("_reserved", C.c_int32 * 3)]
+
+
+class CloudSegment(C.Structure):
+    """svo_cloud_segment (include/svo_hip.h); CLOUD_SEGMENT_DTYPE is the same layout for numpy."""
+    _fields_ = [("seq", C.c_int32), ("run", C.c_int32), ("frame_id", C.c_int32), ("keyframe_id", C.c_int32),
+                ("status", C.c_int32), ("n_points", C.c_int32), ("first_point", C.c_int64), ("pose", C.c_float * 6),
+                ("time_stamp", C.c_float), ("baseline", C.c_float)]
+
+
+class CloudDst(C.Structure):
+    """svo_cloud_dst (include/svo_hip.h)."""
+    _fields_ = [("segments", C.c_void_p), ("points", C.c_void_p), ("capacity", C.c_int64)]
+
+
+class CloudSrc(C.Structure):
+    """svo_cloud_src (include/svo_hip.h): one image pair of svo_cloud_points."""
+    _fields_ = [("left", Image), ("right", Image), ("baseline", C.c_float), ("fx", C.c_float), ("fy", C.c_float),
+                ("cx", C.c_float), ("cy", C.c_float), ("pose", C.c_float * 6), ("_reserved", C.c_int32)]
+
+
+assert (C.sizeof(CloudStyle), C.sizeof(CloudSegment), C.sizeof(CloudDst), C.sizeof(CloudSrc)) == (48, 64, 24, 96)
+
+
+def cloud_style(step=1, win=0, search_x=0, search_y=0, frame=CLOUD_WORLD, layout=CLOUD_COMPACT, min_disparity=0.0,
+                max_depth=0.0, max_mean_cost=0.0):
+    """a CloudStyle; frame and layout may be names (CLOUD_FRAMES, CLOUD_LAYOUTS); win / search_x / search_y of 0: the
+    ctx's settings; a filter value of 0: off"""
+    if isinstance(frame, str):
+        frame = CLOUD_FRAMES.index(frame)
+    if isinstance(layout, str):
+        layout = CLOUD_LAYOUTS.index(layout)
+    return CloudStyle(int(step), int(win), int(search_x), int(search_y), int(frame), int(layout), float(min_disparity),
+                      float(max_depth), float(max_mean_cost))
+
+
+def cloud_size(cam, width, height, style):
+    """svo_cloud_size (host only): (cols, rows, points_per_slot) of one slot of a cloud job with `style`."""
+    cols, rows, points = C.c_int(0), C.c_int(0), C.c_int64(0)
+    _check(lib().svo_cloud_size(C.byref(cam), int(width), int(height), C.byref(style), C.byref(cols), C.byref(rows),
+                                C.byref(points)))
+    return cols.value, rows.value, points.value
 
 
 # scenes (svo_submit_export_scenes, include/svo_hip.h): what is shown, the classes of the key, a line of the stage
@@ -996,6 +1059,30 @@ class Handle:
         device tensor [H, W]), width, height, stride); offsets[i]: the byte of `values` (a float32 device tensor, or
         a raw device address) the planes of pair i start at. Complete on return."""
         self.dense_disparity_packed(self.pack_dense(srcs, offsets), style, values)
+
+    def pack_cloud(self, srcs, first):
+        """the argument arrays of cloud_points, built once (keeps Python out of a timed loop)"""
+        arr = (CloudSrc * max(len(srcs), 1))()
+        for i, (left, right, rig, pose) in enumerate(srcs):
+            for name, (data, w, h, stride) in (("left", left), ("right", right)):
+                setattr(arr[i], name, Image(data.data_ptr() if isinstance(data, torch.Tensor) else int(data), int(w), int(h), int(stride)))
+            for k in ("baseline", "fx", "fy", "cx", "cy"):
+                setattr(arr[i], k, float(rig[k]))
+            arr[i].pose = (C.c_float * 6)(*[float(v) for v in pose])
+        return len(srcs), arr, (C.c_int64 * max(len(srcs), 1))(*[int(o) for o in first]), srcs
+
+    def cloud_points_packed(self, packed, style, points, counts=None):
+        p = points.data_ptr() if isinstance(points, torch.Tensor) else int(points)
+        c = None if counts is None else C.c_void_p(counts.data_ptr() if isinstance(counts, torch.Tensor) else int(counts))
+        _check(lib().svo_cloud_points(self._h, packed[0], packed[1], packed[2], C.byref(style), C.c_void_p(p), c))
+
+    def cloud_points(self, srcs, first, style, points, counts=None):
+        """svo_cloud_points: the coloured 3-D points of `style` (a CloudStyle with win, search_x and search_y given).
+        srcs: per image pair (left, right, rig, pose) with left / right ((data address or uint8 device tensor [H, W]),
+        width, height, stride), rig a mapping with baseline, fx, fy, cx, cy and pose six floats; first[i]: the record
+        of `points` (a device tensor of 16-byte records, or a raw device address) the records of pair i start at;
+        counts: an int32 device tensor [n] (or address) for the kept counts, or None. Complete on return."""
+        self.cloud_points_packed(self.pack_cloud(srcs, first), style, points, counts)
 
     def render_scene(self, srcs, cameras, offsets, style, pixels):
         """svo_render_scene: the viewer's scene of keyframe sets and lines as images of `style` (a SceneStyle). srcs:

@@ -28,6 +28,9 @@ current frame): the gray image the tracker worked on, which with --gpu-rectify /
 The text overlay and the x2 resize of the window are not drawn.
 --dump-disparity DIR [--disparity-step S] [--disparity-depth] writes per frame DIR/000000_disparity.npy: the dense
 disparity (or depth) map of the frame's rectified pair at every S-th pixel.
+--dump-cloud DIR [--cloud-step S] [--cloud-max-depth Z] writes, whenever the newest keyframe changes,
+DIR/kf000000_cloud.ply: the dense coloured point cloud of that keyframe in the world frame at every S-th pixel (binary
+little-endian PLY, x y z float and red green blue uchar), so that the files of a run together are a dense map of it.
 --dump-scene DIR writes per frame DIR/000000_scene.ppm: the 3-D viewer's picture of the map so far
 (src/qt-viewer/PointCloudViewer.qml: points, trajectory, frusta) through its front camera.
 --dump-ar DIR writes per frame DIR/000000_ar.ppm: the AR demo's picture (src/ar-app/), a lit box of edge --ar-box
@@ -362,6 +365,35 @@ def read_ppm(path):
     return np.frombuffer(body, np.uint8).reshape(h, w, 3)
 
 
+PLY_VERTEX = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("red", "u1"), ("green", "u1"), ("blue", "u1")])
+
+
+def write_ply(path, points):
+    """map points (hip_lib.MAP_POINT_DTYPE) as a binary little-endian PLY: x y z float, red green blue uchar"""
+    v = np.empty(len(points), PLY_VERTEX)
+    for k in ("x", "y", "z"):
+        v[k] = points[k]
+    for i, k in enumerate(("red", "green", "blue")):
+        v[k] = points["color"][:, i]
+    header = ("ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n"
+              "property uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n" % len(v))
+    with open(path, "wb") as fh:
+        fh.write(header.encode("ascii"))
+        fh.write(v.tobytes())
+
+
+def read_ply(path):
+    """a PLY as write_ply writes it, as an array of PLY_VERTEX"""
+    with open(path, "rb") as fh:
+        raw = fh.read()
+    head, body = raw.split(b"end_header\n", 1)
+    lines = head.decode("ascii").split("\n")
+    assert lines[0] == "ply" and lines[1] == "format binary_little_endian 1.0"
+    n = int(lines[2].split()[2])
+    assert len(body) == n * PLY_VERTEX.itemsize
+    return np.frombuffer(body, PLY_VERTEX)
+
+
 AR_BOX, AR_RGB = 0.2, 0xc08040
 
 
@@ -375,7 +407,8 @@ class Replay:
 
     def __init__(self, settings, device=0, time_trace=False, fast=False, rectify_maps=None, input_format=None,
                  gpu_imu=False, dump_views=None, dump_scene=None, calibration=None, keyframe_window=None, dump_ar=None,
-                 ar_box=AR_BOX, ar_at=hip_lib.AR_AT, dump_disparity=None, disparity_step=4, disparity_depth=False):
+                 ar_box=AR_BOX, ar_at=hip_lib.AR_AT, dump_disparity=None, disparity_step=4, disparity_depth=False,
+                 dump_cloud=None, cloud_step=4, cloud_max_depth=0.0):
         """fast=False keeps the library default: the reference-order Gauss-Newton (bit-exact traces).
         rectify_maps = (left maps, right maps): the frames fed are raw and are rectified on the GPU.
         calibration = (left, right) CameraCalibrations: the same, with the maps built on the GPU as well.
@@ -390,12 +423,16 @@ class Replay:
         front of the first camera.
         dump_disparity: a directory that receives, per frame, the dense disparity map of the frame (get_disparity at
         the lattice disparity_step; the depth map with disparity_depth) as NNNNNN_disparity.npy [rows, cols], likewise.
+        dump_cloud: a directory that receives, whenever the newest keyframe id changes, that keyframe's dense point cloud
+        in the world frame (get_cloud of "last_keyframes" at the lattice cloud_step, points deeper than cloud_max_depth
+        dropped; 0: none dropped) as kfNNNNNN_cloud.ply (write_ply), likewise.
         keyframe_window: the retired keyframes the tracker keeps (StereoSlamBatch.set_keyframe_window); None: all."""
         self.settings = settings
         self.dump_views, self.dump_scene, self.dump_ar = dump_views, dump_scene, dump_ar
         self.ar_objects = ar_objects(ar_box, ar_at)
         self.dump_disparity, self.disparity_step, self.disparity_depth = dump_disparity, int(disparity_step), bool(disparity_depth)
-        for d in (dump_views, dump_scene, dump_ar, dump_disparity):
+        self.dump_cloud, self.cloud_step, self.cloud_max_depth, self._cloud_kf = dump_cloud, int(cloud_step), float(cloud_max_depth), -1
+        for d in (dump_views, dump_scene, dump_ar, dump_disparity, dump_cloud):
             if d:
                 os.makedirs(d, exist_ok=True)
         self.gpu_imu = gpu_imu
@@ -466,6 +503,13 @@ class Replay:
             planes = self.slam.get_disparity(value="depth" if self.disparity_depth else "disparity", step=self.disparity_step)
             if planes is not None:
                 np.save(os.path.join(self.dump_disparity, f"{len(self.cumulative) - 1:06d}_disparity.npy"), planes[0])
+        if self.dump_cloud:
+            kf = int(self.slam.stats().n_keyframes) - 1
+            if kf != self._cloud_kf:
+                self._cloud_kf = kf
+                points = self.slam.get_cloud("last_keyframes", step=self.cloud_step, max_depth=self.cloud_max_depth)
+                if points is not None:
+                    write_ply(os.path.join(self.dump_cloud, f"kf{kf:06d}_cloud.ply"), points)
         if self.time_trace:                       # like PRINT_TIME_TRACE of the reference
             print("\n".join(time_trace_lines(self.slam.stats())))
 
@@ -529,6 +573,12 @@ def build_parser():
                          "(float32 [rows, cols]; -1 where the search window leaves the image)")
     ap.add_argument("--disparity-step", metavar="S", type=int, default=4, help="lattice of --dump-disparity: every S-th pixel, 1 .. 16")
     ap.add_argument("--disparity-depth", action="store_true", help="--dump-disparity writes depth, baseline / disparity (0: none)")
+    ap.add_argument("--dump-cloud", metavar="DIR",
+                    help="write DIR/kfNNNNNN_cloud.ply whenever the newest keyframe changes: its dense coloured point cloud in "
+                         "the world frame (binary little-endian PLY: x y z float, red green blue uchar)")
+    ap.add_argument("--cloud-step", metavar="S", type=int, default=4, help="lattice of --dump-cloud: every S-th pixel, 1 .. 16")
+    ap.add_argument("--cloud-max-depth", metavar="Z", type=float, default=0.0,
+                    help="--dump-cloud drops points deeper than Z in the camera frame (0: none)")
     ap.add_argument("--frames", type=int, default=100)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--rate", type=float, default=20.0, help="frames per second of the time stamps")
@@ -594,7 +644,8 @@ def main(argv=None):
                 dump_views=args.dump_views, dump_scene=args.dump_scene, calibration=cal, dump_ar=args.dump_ar,
                 ar_box=args.ar_box, ar_at=tuple(float(x) for x in args.ar_at.split(",")),
                 keyframe_window=args.keyframe_window, dump_disparity=args.dump_disparity, disparity_step=args.disparity_step,
-                disparity_depth=args.disparity_depth)
+                disparity_depth=args.disparity_depth, dump_cloud=args.dump_cloud, cloud_step=args.cloud_step,
+                cloud_max_depth=args.cloud_max_depth)
     for k, (left, right, t) in enumerate(frames):
         rp.feed(left, right, t, None if gyro is None else gyro[gyro[:, 0] == k, 1:4])
     rows = rp.rows()

@@ -372,6 +372,68 @@ class Disparities:
         return self.values[i]
 
 
+class Clouds:
+    """One svo_submit_export_cloud: owns the buffers the library writes. After wait(): `segments`
+    (hip_lib.CLOUD_SEGMENT_DTYPE, one per named slot), points(i) and, in the organized layout, organized(i).
+    `points_buffer` is a uint8 [capacity, 16] tensor: pinned memory in host mode, on the ctx's device in device mode
+    (points(i) / organized(i) then copy the slot's records to the host). cols, rows, points_per_slot: the lattice of
+    every slot of the job (svo_cloud_size)."""
+
+    def __init__(self, slam, what, seqs, style, device):
+        self._slam = slam
+        self.what, self.style, self.device_mode = int(what), style, bool(device)
+        self.seqs = None if seqs is None else [int(s) for s in seqs]
+        n = self._n = slam.n if seqs is None else len(self.seqs)
+        self.cols, self.rows, self.points_per_slot = slam.cloud_size(style)
+        self.capacity = n * self.points_per_slot
+        self._seg = np.zeros(max(n, 1), hip_lib.CLOUD_SEGMENT_DTYPE)
+        self.segments = self._seg[:n]
+        shape = (max(self.capacity, 1), hip_lib.MAP_POINT_DTYPE.itemsize)
+        self.points_buffer = (torch.zeros(shape, dtype=torch.uint8, device=slam.device) if device
+                              else torch.zeros(shape, dtype=torch.uint8, pin_memory=True))
+        self._dst = hip_lib.CloudDst(self._seg.ctypes.data, self.points_buffer.data_ptr(), self.capacity)
+        self._seq_arr = None if seqs is None else (C.c_int * max(n, 1))(*self.seqs)
+
+    def submit(self):
+        """queue the job (again: the same slots into the same buffers, once the previous one is delivered)"""
+        slam = self._slam
+        if self.device_mode:
+            torch.cuda.current_stream(slam.device).synchronize()     # (nothing of the caller's is still using the tensor)
+        _check(lib().svo_submit_export_cloud(slam._ctx, self.what, self._seq_arr, self._n, C.byref(self.style),
+                                             C.byref(self._dst), hip_lib.MEM_DEVICE if self.device_mode else hip_lib.MEM_HOST))
+        return self
+
+    def wait(self):
+        self._slam.wait()
+        return self
+
+    def _records(self, lo, n):
+        a = self.points_buffer[lo:lo + n]
+        a = a.cpu().numpy() if self.device_mode else a.numpy()
+        return a.view(hip_lib.MAP_POINT_DTYPE)[:, 0]
+
+    def points(self, i):
+        """the kept points of named slot i (hip_lib.MAP_POINT_DTYPE) in row-major lattice order; None for a slot whose
+        status is CLOUD_NONE. In the organized layout: the records without CLOUD_DROPPED, a copy."""
+        e = self.segments[i]
+        if int(e["status"]) != hip_lib.CLOUD_OK:
+            return None
+        if self.style.layout == hip_lib.CLOUD_ORGANIZED:
+            r = self._records(int(e["first_point"]), self.points_per_slot)
+            return r[(r["flags"] & hip_lib.CLOUD_DROPPED) == 0]
+        return self._records(int(e["first_point"]), int(e["n_points"]))
+
+    def organized(self, i):
+        """the records of named slot i as [rows, cols] (organized layout only); None for a slot whose status is
+        CLOUD_NONE"""
+        if self.style.layout != hip_lib.CLOUD_ORGANIZED:
+            raise ValueError("organized(): the job's layout is compact")
+        e = self.segments[i]
+        if int(e["status"]) != hip_lib.CLOUD_OK:
+            return None
+        return self._records(int(e["first_point"]), self.points_per_slot).reshape(self.rows, self.cols)
+
+
 class Scenes:
     """One svo_submit_export_scenes: owns the buffers the library writes. After wait(): `segments`
     (hip_lib.SCENE_SEGMENT_DTYPE, one per named slot) and image(i); `pixels` is the whole buffer, a numpy uint8 view
@@ -834,6 +896,28 @@ class StereoSlamBatch:
         """submit_disparity + wait"""
         return self.submit_disparity(what, seqs, **kw).wait()
 
+    def cloud_size(self, style):
+        """svo_cloud_size: (cols, rows, points_per_slot) of one slot of a cloud job with `style` in this ctx"""
+        return hip_lib.cloud_size(self.cam, self.width, self.height, style)
+
+    def submit_cloud(self, what="frames", seqs=None, step=1, win=0, search_x=0, search_y=0, frame="world", layout="compact",
+                     min_disparity=0.0, max_depth=0.0, max_mean_cost=0.0, device=False, style=None):
+        """svo_submit_export_cloud: queue a dense coloured point cloud of the current frames (what="frames") or newest
+        keyframes ("last_keyframes") of the slots `seqs` (None: all, in order) behind what was submitted so far;
+        nothing is waited for. step, win, search_x, search_y: as submit_disparity; frame: "world" or "camera";
+        layout: "compact" or "organized"; min_disparity, max_depth, max_mean_cost: the filter (0: off); style: a
+        hip_lib.CloudStyle instead of all these. Returns a Clouds, valid after its wait() (or the ctx's); its submit()
+        queues the same job again into the same buffers."""
+        if isinstance(what, str):
+            what = hip_lib.EXPORT_WHAT.index(what)
+        if style is None:
+            style = hip_lib.cloud_style(step, win, search_x, search_y, frame, layout, min_disparity, max_depth, max_mean_cost)
+        return Clouds(self, what, seqs, style, device).submit()
+
+    def export_cloud(self, what="frames", seqs=None, **kw):
+        """submit_cloud + wait"""
+        return self.submit_cloud(what, seqs, **kw).wait()
+
     def submit_scenes(self, seqs=None, camera="front", device=False, style=None, **kw):
         """svo_submit_export_scenes: queue the viewer's 3-D picture (keyframe points, trajectory, a frustum per
         keyframe and at the current pose) of the slots `seqs` (None: all, in order) behind what was submitted so far;
@@ -1270,6 +1354,17 @@ class StereoSlam(StereoSlamBatch):
         kw["device"] = False
         planes = self.export_disparity(what, None, **kw).planes(0)
         return None if planes is None else planes.copy()
+
+    def get_cloud(self, what="frames", **kw):
+        """the dense coloured point cloud of the current frame (or, what="last_keyframes", of the newest keyframe) as
+        a numpy array of hip_lib.MAP_POINT_DTYPE (export_cloud of the one slot: step, frame, layout, the filter, ...;
+        layout="organized": [rows, cols]); None when there is none"""
+        if self._ctx is None:
+            return None
+        kw["device"] = False
+        job = self.export_cloud(what, None, **kw)
+        pts = job.organized(0) if job.style.layout == hip_lib.CLOUD_ORGANIZED else job.points(0)
+        return None if pts is None else pts.copy()
 
     def get_scene(self, camera="front", **kw):
         """the viewer's 3-D picture of the map as a numpy array [rows, cols, 3 | 4] (export_scenes of the one slot:
