@@ -1487,6 +1487,20 @@ int svo_pinv6_check(svo_handle *h, const float *H_dev, int n, float *out_dev, in
  * Vt[36], U^T[36] and delta[6]; sweeps_dev[n] the Jacobi sweeps run. Both impls give the same bits. */
 int svo_solve6_check(svo_handle *h, const float *H_dev, const float *b_dev, int n, float *out_dev,
                      int32_t *sweeps_dev, int impl);
+/* Diagnostic: the alignment records (the per-level workspace svo_sparse_align's first kernel fills from the previous
+ * frame: per patch pixel the reference half of the cost, the reference patch sum and the image gradient, per keypoint
+ * sum g g^T) of `batch` sequences, computed by that kernel and by the one-lane-per-pixel kernel it replaced, on the
+ * same inputs. kps2d / flags (NULL: none) hold the sequences `stride` entries apart, n_dev[batch] (device) the counts,
+ * each 0..n_bound, n_bound <= stride; prev_pyr[batch][max_pyramid_levels] the level images (device; any base
+ * alignment, stride >= width, at least 3 x 3; levels below min_pyramid_level_pose_estimation are not read). Each
+ * kernel fills a workspace of its own, [batch][levels used][68][rec_cap] floats (rec_cap a multiple of 4, >= n_bound),
+ * preset to ws_fill. *n_diff receives the number of 32-bit words in which the two differ, *first_diff the index of
+ * the first (-1: none); rec_out (device, NULL: not wanted) the kernel's workspace, ref_out (likewise) the
+ * replaced kernel's. */
+int svo_sia_records_check(svo_handle *h, int batch, int stride, const int32_t *n_dev, int n_bound,
+                          const svo_kp2d *kps2d, const uint32_t *flags, const svo_image *prev_pyr,
+                          const svo_camera_settings *cam, int rec_cap, uint32_t ws_fill, float *rec_out,
+                          float *ref_out, int64_t *n_diff, int64_t *first_diff);
 /* Diagnostic: the reprojection refinement (svo_reproj_gn) of `batch` sequences in one launch, the way the
  * tracker launches it. Every keypoint array holds the sequences `stride` entries apart (sequence b starts at
  * b * stride); n_dev[batch] (device) the counts, each 0..n_bound, n_bound <= stride; pose_in / pose_out

@@ -33,6 +33,7 @@
 //     (svo_*_set_fast_solver) builds sum_kp J^T (sum_px g g^T) J with a wave reduction and solves
 //     by LDL^T.
 #include "svo_kernels.hpp"
+#include "sia_block.hpp"
 #include <mutex>
 #include <algorithm>
 #include <cstdlib>
@@ -92,7 +93,6 @@ __host__ __device__ constexpr int sia_stg(int T, int mode) { return T == 64 && m
 #endif
 __host__ __device__ constexpr int sia_acc_u(int T, int mode) { return T == 64 && mode == 2 ? SVO_SIA_ACC_U : 4; }
 enum { KF_PX = 0, KF_PY, KF_PZ, KF_QX, KF_QY, KF_GXX, KF_GXY, KF_GYY, KF_ACT, KF_COUNT };
-enum { REC_I1 = 0, REC_PS = 1, REC_G0 = 2, REC_G1 = 3 };
 struct SiaLds {
     size_t img, tbuf, kpf, rec, sums, stage, pipe, total;
 };
@@ -125,49 +125,145 @@ __constant__ int8_t c_tri_c[21] = {0, 1, 2, 3, 4, 5, 1, 2, 3, 4, 5, 2, 3, 4, 5, 
 // Everything the alignment needs from the PREVIOUS frame is independent of the pose: per patch
 // pixel the reference half of the cost (image_comparison.cpp:20-88), the reference patch sum of
 // the residual (:449-460) and the image gradient of calculate_hessian (:351-388), per keypoint
-// sum g g^T. sia_prep_kernel computes them for every level in one launch, one lane per
-// (keypoint, patch pixel), into a struct-of-arrays workspace: rec_ws[level - min][row][rec_cap]
-// with row = field * 16 + pixel (fields REC_*), rows 64..66 = sum gxgx, gxgy, gygy.
-constexpr int SIA_REC_ROWS = 68;
+// sum g g^T. sia_prep_kernel computes them for every level in one launch into a struct-of-arrays
+// workspace: rec_ws[level - min][row][rec_cap] with row = field * 16 + pixel (fields REC_*), rows
+// 64..66 = sum gxgx, gxgy, gygy.
+//
+// A wave takes SIA_PREP_KPS = 16 keypoints, a lane one patch row (four pixels) of one keypoint: lane =
+// patch row * 16 + keypoint. The 49 byte taps of a pixel (five 3x3 patch sums and the 2x2 cost taps) lie
+// in five rows of eight bytes (sia_block.hpp), which the lane loads once, 8 bytes at a time, and shifts
+// per pixel; the arithmetic on the taps is the reference's, expression for expression. A patch sum
+// whose taps are not where the block has them (a float increment of the walk rounded across an integer,
+// a pixel in the outermost columns, an image narrower than a block row) reads the image directly.
+// No LDS: the four lanes of a keypoint load overlapping rows (20 loads of 8 bytes for 8 different rows)
+// from the same cache lines; sharing them through LDS would trade 3 of a lane's 5 loads for 2 LDS writes,
+// 5 LDS reads and the wait between them.
+constexpr int SIA_PREP_KPS = 16;
+
+// byte k (0..4) of a shifted block row as a float (v_cvt_f32_ubyte<k>)
+__device__ inline float prep_byte(uint64_t s, int k) {
+    return k < 4 ? (float)(((uint32_t)s >> (8 * k)) & 0xffu) : (float)((uint32_t)(s >> 32) & 0xffu);
+}
+
+// a + b as v_add_f32 a, b. The same sum for every pair of numbers. Of two NaNs the instruction returns its first
+// operand's, as the reference's addss does; the compiler swaps the operands of an add at will, and with them the sign
+// of the NaN that a keypoint with a NaN coordinate leaves in its records (1 - x2 negates x2's NaN, so a patch sum adds
+// NaNs of both signs). Written this way the running sum's NaN wins in every add, the first term's in the end, as in
+// the one-lane-per-pixel kernel.
+__device__ inline float prep_add(float a, float b) {
+    float r;
+    asm("v_add_f32_e32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+
+// the taps of one patch pixel: block row j shifted right by sh bytes has column e - 1 in byte 0 (sh < 0: not all there)
+struct PrepTaps {
+    const ImgView& im;
+    const SiaBlock& blk;
+    int pr, e, sh;
+    const uint64_t (&rows)[SIA_BLK_ROWS];
+    // get_patch_sum (svo_device.hpp patch_sum, the same expression) at (cx, cy), whose taps are expected at
+    // bytes D .. D + 2 of the shifted block rows J .. J + 2
+    template <int D, int J>
+    __device__ inline float sum(float cx, float cy) const {
+        const float sx = cx - 0.5f, sy = cy - 0.5f;
+        const float fx_ = floorf(sx), fy_ = floorf(sy);
+        const int ipx = (int)fx_, ipy = (int)fy_;
+        const float x2 = sx - (float)ipx, y2 = sy - (float)ipy;
+        // 1 - x2 and 1 - y2 as one packed subtract, the instruction the one-lane-per-pixel kernel has here
+        // (v_pk_add_f32 with a negated operand). The same value for every number; for a NaN coordinate, which passes
+        // the bounds tests, it negates the NaN's sign where v_sub_f32 keeps it, and that sign is what the records of
+        // such a keypoint have always carried.
+        const v2f w1 = v2f{1.0f, 1.0f} - v2f{x2, y2};
+        const float x1 = w1.x, y1 = w1.y;
+        float t[3][3];
+        if (sia_block_has_sum(blk, pr, sh, e, D, J, ipx, ipy, im.h)) {
+#pragma unroll
+            for (int r = 0; r < 3; r++) {
+                const uint64_t s = rows[J + r] >> (8 * sh);      // (shifted where it is used: five kept rows cost a wave per SIMD)
+#pragma unroll
+                for (int c = 0; c < 3; c++) t[r][c] = prep_byte(s, D + c);
+            }
+        } else {
+            // (the rare path forms its addresses where it runs: hoisted out of the pixel loop they would hold
+            // registers through the common one)
+            int iy = ipy;
+            asm volatile("" : "+v"(iy));
+            const uint8_t* s1 = im.g() + (long)iy * im.stride + ipx;
+#pragma unroll
+            for (int r = 0; r < 3; r++)
+#pragma unroll
+                for (int c = 0; c < 3; c++) t[r][c] = (float)s1[r * im.stride + c];
+        }
+        // the sum of the nine terms, left to right as the expression of patch_sum has them (prep_add)
+        float intensity = x1 * y1 * t[0][0];
+        intensity = prep_add(intensity, y1 * t[0][1]);
+        intensity = prep_add(intensity, x2 * y1 * t[0][2]);
+        intensity = prep_add(intensity, x1 * t[1][0]);
+        intensity = prep_add(intensity, t[1][1]);
+        intensity = prep_add(intensity, x2 * t[1][2]);
+        intensity = prep_add(intensity, x1 * y2 * t[2][0]);
+        intensity = prep_add(intensity, y2 * t[2][1]);
+        intensity = prep_add(intensity, x2 * y2 * t[2][2]);
+        // the sum is formed here, one patch sum after the other: left to sink to where the sums are subtracted, the
+        // taps and weights of a pixel's four gradient sums side by side take the registers of three more waves per SIMD
+        asm volatile("" : "+v"(intensity));
+        return intensity;
+    }
+};
 
 __global__ __launch_bounds__(64) void sia_prep_kernel(const SiaArgs* __restrict__ args) {
     const SiaArgs& a = args[blockIdx.z];
-    const int n = min(*G(a.n_ptr), a.rec_cap);
     const int level = a.cam.min_pyramid_level_pose_estimation + blockIdx.y;
     if (level >= a.cam.max_pyramid_levels) return;
-    const int idx = blockIdx.x * 64 + threadIdx.x;      // single-wave workgroups: they fit any free slot
-    const int kp = idx >> 4, px = idx & 15;
+    const int lane = threadIdx.x;                        // single-wave workgroups: they fit any free slot
+    const int kp0 = blockIdx.x * SIA_PREP_KPS, kp = kp0 + (lane & 15), pr = lane >> 4;
+    // One round trip before the taps: the count, the keypoint's flags and its position leave together, with no
+    // branch between them (behind a branch the compiler sinks the count's load to its use, a second round trip).
+    // An index below SiaArgs::cap, the readable length of the keypoint arrays, is theirs whatever n turns out to
+    // be; a lane past it asks for the last slot and drops what arrives. Without arrays (cap == 0) the loads read
+    // the argument block itself, without flags the position once more, and the result is dropped.
+    // (& not &&: the block's fields are read together, not one behind the test of the other)
+    const bool have = (a.cap > 0) & (a.kps2d != nullptr), have_flags = have & (a.flags != nullptr);
+    const int kl = max(min(kp, a.cap - 1), 0);
+    const svo_kp2d* const kp_src = have ? a.kps2d + kl : reinterpret_cast<const svo_kp2d*>(&a);
+    const uint32_t* const fl_src = have_flags ? a.flags + kl : reinterpret_cast<const uint32_t*>(kp_src);
+    const int n_raw = *G(a.n_ptr);
+    svo_kp2d kref = *G(kp_src);
+    uint32_t flg = *G(fl_src);
+    asm volatile("" ::: "memory");                       // (keeps the loads above the branches below, as in compute_kp)
+    if (!have) kref = svo_kp2d{0.f, 0.f};
+    if (!have_flags) flg = 0;
+    const int n = min(n_raw, a.rec_cap);
     const int span = (n + 3) & ~3;                       // the consumer copies float4 columns
-    if (kp >= span) return;                              // (whole 16-lane rows leave together)
+    if (kp0 >= span) return;
     const ImgView prev = a.prev[level];
     const int divider = 1 << level;
-    float g0 = 0, g1 = 0, psr = __builtin_nanf(""), i1 = __builtin_nanf("");
-    const bool active = kp < n && !(a.flags && (G(a.flags)[kp] & SVO_IGNORE_TEMPORARY));
+    if (level != 0) { kref.x /= divider; kref.y /= divider; }      // setLevel
+    // the block rows of this patch row: SIA_BLK_ROWS loads of 8 bytes (any alignment), all of them pixels of the
+    // image whatever the position holds, so they do not wait for the active flag either
+    const SiaBlock blk = sia_block(kref.x, kref.y, prev.w, prev.h);
+    uint64_t rows[SIA_BLK_ROWS] = {};
+    if (blk.ok) {
+#pragma unroll
+        for (int j = 0; j < SIA_BLK_ROWS; j++)
+            __builtin_memcpy(&rows[j], (const void*)(prev.g() + (size_t)sia_block_row(blk, pr, j, prev.h) * prev.stride + blk.cx0), 8);
+        asm volatile("" ::: "memory");
+    }
+    const bool active = kp < n && !(flg & SVO_IGNORE_TEMPORARY);
+    // the reference's walk over the patch: x++ per column, x -= 4 and y++ per row (float arithmetic)
+    float kx = kref.x - 2.f, ky = kref.y - 2.f;
+    for (int rr = 0; rr < pr; rr++) {
+        kx += 1.f; kx += 1.f; kx += 1.f; kx += 1.f;
+        kx -= 4.f;
+        ky += 1.f;
+    }
+    // reference half of the cost (image_comparison.cpp:20-88): one window test per keypoint
+    bool cost_in = false;
+    int wsh = -1;                               // bytes the window's two rows of this patch row are shifted by, < 0: read from the image
+    float x12 = 0, y12 = 0;                     // (the four weights are formed per pixel: two registers instead of four)
+    SVO_GP(const uint8_t) wp = nullptr;         // ... or where they lie in the image
     if (active) {
-        svo_kp2d kref = G(a.kps2d)[kp];
-        if (level != 0) { kref.x /= divider; kref.y /= divider; }      // setLevel
-        // the reference's walk over the patch: x++ per column, x -= 4 and y++ per row (float arithmetic)
-        float kx = kref.x - 2.f, ky = kref.y - 2.f;
-        for (int rr = 0; rr < (px >> 2); rr++) {
-            kx += 1.f; kx += 1.f; kx += 1.f; kx += 1.f;
-            kx -= 4.f;
-            ky += 1.f;
-        }
-        for (int cc = 0; cc < (px & 3); cc++) kx += 1.f;
-        // calculate_hessian bounds (:351-352)
-        if (!(((double)kx - 2.0) < 0 || ((double)ky - 2.0) < 0 ||
-              ((double)kx + 3.0) >= prev.w || ((double)ky + 3.0) >= prev.h)) {
-            const float int1 = patch_sum(prev.g(), prev.stride, kx + 1, ky);
-            const float int2 = patch_sum(prev.g(), prev.stride, kx - 1, ky);
-            const float int3 = patch_sum(prev.g(), prev.stride, kx, ky + 1);
-            const float int4 = patch_sum(prev.g(), prev.stride, kx, ky - 1);
-            g0 = int1 - int2; g1 = int3 - int4;
-        }
-        // reference half of the residual test (:449-453)
-        if (!(((double)kx - 1.0) < 0 || ((double)ky - 1.0) < 0 ||
-              ((double)kx + 2.0) > prev.w || ((double)ky + 2.0) > prev.h))
-            psr = patch_sum(prev.g(), prev.stride, kx, ky);
-        // reference half of the cost (image_comparison.cpp:20-88): one window test per keypoint
         const int ps = a.cam.window_size_pose_estimator;
         const float half_size = ((float)ps - 1.0f) / 2.0f;
         const float s1x = kref.x - half_size, s1y = kref.y - half_size;
@@ -175,29 +271,95 @@ __global__ __launch_bounds__(64) void sia_prep_kernel(const SiaArgs* __restrict_
         if (f1x >= 0.f && f1y >= 0.f && f1x < 65536.f && f1y < 65536.f) {
             const int ip1x = (int)f1x, ip1y = (int)f1y;
             if (ip1y + ps < prev.h && ip1x + ps < prev.w) {
-                const float x12 = s1x - (float)ip1x, y12 = s1y - (float)ip1y;
-                const float x11 = 1.0f - x12, y11 = 1.0f - y12;
-                const float m0 = x11 * y11, m1 = x12 * y11, m2 = x11 * y12, m3 = x12 * y12;
-                const uint8_t* p = prev.g() + (size_t)((px >> 2) + ip1y) * prev.stride + (px & 3) + ip1x;
-                float t = 0;
-                t += m0 * (float)p[0];
-                t += m1 * (float)p[1];
-                t += m2 * (float)p[prev.stride];
-                t += m3 * (float)p[prev.stride + 1];
-                i1 = t;
+                cost_in = true;
+                x12 = s1x - (float)ip1x; y12 = s1y - (float)ip1y;
+                // (a window smaller than the 4 x 4 patch is not tested for the rows below it: read from the image, as ever)
+                wsh = ps >= 4 ? sia_block_window_shift(blk, ip1x, ip1y, prev.h) : -1;
+                wp = prev.g() + (size_t)(pr + ip1y) * prev.stride + ip1x;
             }
         }
     }
-    float* out = G(a.rec_ws) + (size_t)blockIdx.y * SIA_REC_ROWS * a.rec_cap;
-    out[(size_t)(REC_I1 * 16 + px) * a.rec_cap + kp] = i1;
-    out[(size_t)(REC_PS * 16 + px) * a.rec_cap + kp] = psr;
-    out[(size_t)(REC_G0 * 16 + px) * a.rec_cap + kp] = g0;
-    out[(size_t)(REC_G1 * 16 + px) * a.rec_cap + kp] = g1;
-    const float gxx = row16_sum_dpp(g0 * g0), gxy = row16_sum_dpp(g0 * g1), gyy = row16_sum_dpp(g1 * g1);
-    if (px == 0) {
-        out[(size_t)64 * a.rec_cap + kp] = gxx;
-        out[(size_t)65 * a.rec_cap + kp] = gxy;
-        out[(size_t)66 * a.rec_cap + kp] = gyy;
+    // Pixel after pixel (not unrolled: four pixels' taps and weights side by side would take the registers of two
+    // more waves per SIMD). A store instruction writes, of four rows, 16 consecutive keypoints each: whole 64-byte
+    // sectors.
+    //
+    // sum g g^T over the 16 pixels keeps the association order that row16_sum_dpp over 16 lanes px = 0..15 leaves in
+    // lane px == 0 (what rows 64..66 have always held): pairs px ^ 1, then px ^ 2 — a patch row, (v0 + v1) + (v2 + v3),
+    // in this lane — then the half mirror — patch rows 0 + 1 and 2 + 3: the lanes 16 apart — then the row mirror —
+    // (0 + 1) + (2 + 3): the lanes 32 apart. A float add of numbers, or of NaNs of one sign and payload (all a keypoint with a NaN coordinate has), gives the same bits with its operands swapped, so every lane
+    // of a keypoint ends with that sum.
+    float lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};         // v0 + v1 and v2 + v3 of gx gx, gx gy, gy gy
+    // (one wave-uniform base per field and a 32-bit offset per lane: a level's records stay far below 4 GB)
+    SVO_GP(float) const lvl = G(a.rec_ws) + (size_t)blockIdx.y * SIA_REC_ROWS * a.rec_cap;
+    unsigned off = (unsigned)(pr * 4) * (unsigned)a.rec_cap + (unsigned)kp;
+#pragma unroll 1
+    for (int c = 0; c < 4; c++) {
+        float g0 = 0, g1 = 0, psr = __builtin_nanf(""), i1 = __builtin_nanf("");
+        if (active) {
+            // this pixel's columns e - 1 .. e + 3 of the block rows in bytes 0 .. 4
+            const int e = sia_block_floor(kx - 0.5f);
+            const PrepTaps tp{prev, blk, pr, e, sia_block_shift(blk, e), rows};
+            // calculate_hessian bounds (:351-352)
+            if (!(((double)kx - 2.0) < 0 || ((double)ky - 2.0) < 0 ||
+                  ((double)kx + 3.0) >= prev.w || ((double)ky + 3.0) >= prev.h)) {
+                const float int1 = tp.sum<2, 1>(kx + 1, ky);
+                const float int2 = tp.sum<0, 1>(kx - 1, ky);
+                const float int3 = tp.sum<1, 2>(kx, ky + 1);
+                const float int4 = tp.sum<1, 0>(kx, ky - 1);
+                g0 = int1 - int2; g1 = int3 - int4;
+            }
+            // reference half of the residual test (:449-453)
+            if (!(((double)kx - 1.0) < 0 || ((double)ky - 1.0) < 0 ||
+                  ((double)kx + 2.0) > prev.w || ((double)ky + 2.0) > prev.h))
+                psr = tp.sum<1, 1>(kx, ky);
+            if (cost_in) {
+                float p00, p01, p10, p11;
+                if (wsh >= 0) {
+                    const uint64_t w0 = rows[2] >> (8 * (wsh + c)), w1 = rows[3] >> (8 * (wsh + c));
+                    p00 = prep_byte(w0, 0); p01 = prep_byte(w0, 1);
+                    p10 = prep_byte(w1, 0); p11 = prep_byte(w1, 1);
+                } else {
+                    SVO_GP(const uint8_t) p = wp + c;
+                    p00 = (float)p[0]; p01 = (float)p[1];
+                    p10 = (float)p[prev.stride]; p11 = (float)p[prev.stride + 1];
+                }
+                const float x11 = 1.0f - x12, y11 = 1.0f - y12;
+                const float m0 = x11 * y11, m1 = x12 * y11, m2 = x11 * y12, m3 = x12 * y12;
+                float t = 0;
+                t += m0 * p00;
+                t += m1 * p01;
+                t += m2 * p10;
+                t += m3 * p11;
+                i1 = t;
+            }
+            kx += 1.f;
+        }
+        const float gg[3] = {g0 * g0, g0 * g1, g1 * g1};
+#pragma unroll
+        for (int k = 0; k < 3; k++) {          // (c is wave-uniform)
+            if (c == 0) lo[k] = gg[k];
+            else if (c == 1) lo[k] = lo[k] + gg[k];
+            else if (c == 2) hi[k] = gg[k];
+            else hi[k] = hi[k] + gg[k];
+        }
+        if (kp < span) {
+            (lvl + (size_t)(REC_I1 * 16) * a.rec_cap)[off] = i1;
+            (lvl + (size_t)(REC_PS * 16) * a.rec_cap)[off] = psr;
+            (lvl + (size_t)(REC_G0 * 16) * a.rec_cap)[off] = g0;
+            (lvl + (size_t)(REC_G1 * 16) * a.rec_cap)[off] = g1;
+        }
+        off += (unsigned)a.rec_cap;
+    }
+    float sums[3];
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        float q = lo[k] + hi[k];
+        q += __shfl_xor(q, 16, 64);
+        q += __shfl_xor(q, 32, 64);
+        sums[k] = q;
+    }
+    if (kp < span && pr < 3) {
+        lvl[(unsigned)(64 + pr) * (unsigned)a.rec_cap + (unsigned)kp] = pr == 0 ? sums[0] : pr == 1 ? sums[1] : sums[2];
     }
 }
 
@@ -1077,14 +1239,19 @@ LaunchShape sia_pick_shape(int batch, const svo_camera_settings& cam, int width,
     return {lds <= SIA_LDS_BUDGET && cap <= rec_cap, waves, mode, cap, lds};
 }
 
+void launch_sia_prep(const SiaArgs* d_args, int batch, const svo_camera_settings& cam, int n_bound, hipStream_t stream) {
+    const int nb = std::max(n_bound, 1);
+    const int n_lv = cam.max_pyramid_levels - cam.min_pyramid_level_pose_estimation;
+    // (the bound rounded up as the kernel rounds a count: waves of SIA_PREP_KPS keypoints)
+    hipLaunchKernelGGL(sia_prep_kernel, dim3((((nb + 3) & ~3) + SIA_PREP_KPS - 1) / SIA_PREP_KPS, n_lv, batch), dim3(64), 0, stream, d_args);
+}
+
 LaunchStatus launch_sia(const SiaArgs* d_args, int batch, const svo_camera_settings& cam, int width,
                         int height, int n_bound, int rec_cap, int exact, hipStream_t stream) {
     const LaunchShape sh = sia_pick_shape(batch, cam, width, height, n_bound, rec_cap, exact);
     if (!sh.fits) return {sh, hipSuccess};
-    const int nb = std::max(n_bound, 1);
-    const int n_lv = cam.max_pyramid_levels - cam.min_pyramid_level_pose_estimation;
     const int img = sia_img_bytes(cam, width, height);
-    hipLaunchKernelGGL(sia_prep_kernel, dim3((((nb + 3) & ~3) * 16 + 63) / 64, n_lv, batch), dim3(64), 0, stream, d_args);
+    launch_sia_prep(d_args, batch, cam, n_bound, stream);
 #define SIA_CASE(W, M) if (sh.waves == W && sh.mode == M) return sia_launch_shape<W, M>(d_args, batch, img, sh, stream);
     SIA_CASE(1, 0) SIA_CASE(2, 0) SIA_CASE(4, 0)
     SIA_CASE(1, 1) SIA_CASE(2, 1) SIA_CASE(4, 1)

@@ -192,7 +192,7 @@ extern "C" int svo_sparse_align(svo_handle* h, const svo_image* prev_pyr, const 
     sa.kp_ws = h->sia_kpws.get();
     sa.rec_ws = h->sia_rec.get(); sa.rec_cap = h->rec_cap;
     sa.dbg_H = dbg; sa.dbg_level = dbg_level;
-    sa.cap = h->max_kps;
+    sa.cap = n;              // the caller's arrays hold n entries: nothing past them is read
     sa.exact_pinv = h->exact_pinv;
     SiaArgs* d;
     rc = stage(h, sa, &d);

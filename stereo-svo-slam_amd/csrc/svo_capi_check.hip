@@ -3,6 +3,7 @@
 // and the queries of the layouts and launch shapes those entries work with.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <climits>
 #include <cstring>
 #include <vector>
@@ -227,6 +228,163 @@ extern "C" int svo_sparse_align_batch_mats(svo_handle* h, int batch, int stride,
                              alignof(PoseMats));
     return sparse_align_batch(h, batch, stride, n_dev, n_bound, kps2d, kps3d, flags, prev_pyr, cur_pyr, cam, pose_guess,
                               dbg_level, ws_fill, pose_out, cost, trace, dbg, waves, mode, cap, static_cast<PoseMats*>(mats_out));
+}
+
+// svo_sia_records_check: the alignment records of sia_prep_kernel (sia.hip) against the kernel it replaced.
+// sia_prep_ref_kernel is that kernel as it was, one lane per (keypoint, patch pixel) and every tap a byte load of its
+// own: 49 loads per lane behind three bounds branches, stores of sixteen 16-byte pieces per instruction. It runs only
+// here, as the definition of every word of rec_ws (values, NaN payloads, and which words are written at all).
+__global__ __launch_bounds__(64) void sia_prep_ref_kernel(const SiaArgs* __restrict__ args) {
+    const SiaArgs& a = args[blockIdx.z];
+    const int n = min(*G(a.n_ptr), a.rec_cap);
+    const int level = a.cam.min_pyramid_level_pose_estimation + blockIdx.y;
+    if (level >= a.cam.max_pyramid_levels) return;
+    const int idx = blockIdx.x * 64 + threadIdx.x;
+    const int kp = idx >> 4, px = idx & 15;
+    const int span = (n + 3) & ~3;                       // the consumer copies float4 columns
+    if (kp >= span) return;                              // (whole 16-lane rows leave together)
+    const ImgView prev = a.prev[level];
+    const int divider = 1 << level;
+    float g0 = 0, g1 = 0, psr = __builtin_nanf(""), i1 = __builtin_nanf("");
+    const bool active = kp < n && !(a.flags && (G(a.flags)[kp] & SVO_IGNORE_TEMPORARY));
+    if (active) {
+        svo_kp2d kref = G(a.kps2d)[kp];
+        if (level != 0) { kref.x /= divider; kref.y /= divider; }      // setLevel
+        // the reference's walk over the patch: x++ per column, x -= 4 and y++ per row (float arithmetic)
+        float kx = kref.x - 2.f, ky = kref.y - 2.f;
+        for (int rr = 0; rr < (px >> 2); rr++) {
+            kx += 1.f; kx += 1.f; kx += 1.f; kx += 1.f;
+            kx -= 4.f;
+            ky += 1.f;
+        }
+        for (int cc = 0; cc < (px & 3); cc++) kx += 1.f;
+        // calculate_hessian bounds (:351-352)
+        if (!(((double)kx - 2.0) < 0 || ((double)ky - 2.0) < 0 ||
+              ((double)kx + 3.0) >= prev.w || ((double)ky + 3.0) >= prev.h)) {
+            const float int1 = patch_sum(prev.g(), prev.stride, kx + 1, ky);
+            const float int2 = patch_sum(prev.g(), prev.stride, kx - 1, ky);
+            const float int3 = patch_sum(prev.g(), prev.stride, kx, ky + 1);
+            const float int4 = patch_sum(prev.g(), prev.stride, kx, ky - 1);
+            g0 = int1 - int2; g1 = int3 - int4;
+        }
+        // reference half of the residual test (:449-453)
+        if (!(((double)kx - 1.0) < 0 || ((double)ky - 1.0) < 0 ||
+              ((double)kx + 2.0) > prev.w || ((double)ky + 2.0) > prev.h))
+            psr = patch_sum(prev.g(), prev.stride, kx, ky);
+        // reference half of the cost (image_comparison.cpp:20-88): one window test per keypoint
+        const int ps = a.cam.window_size_pose_estimator;
+        const float half_size = ((float)ps - 1.0f) / 2.0f;
+        const float s1x = kref.x - half_size, s1y = kref.y - half_size;
+        const float f1x = floorf(s1x), f1y = floorf(s1y);
+        if (f1x >= 0.f && f1y >= 0.f && f1x < 65536.f && f1y < 65536.f) {
+            const int ip1x = (int)f1x, ip1y = (int)f1y;
+            if (ip1y + ps < prev.h && ip1x + ps < prev.w) {
+                const float x12 = s1x - (float)ip1x, y12 = s1y - (float)ip1y;
+                const float x11 = 1.0f - x12, y11 = 1.0f - y12;
+                const float m0 = x11 * y11, m1 = x12 * y11, m2 = x11 * y12, m3 = x12 * y12;
+                const uint8_t* p = prev.g() + (size_t)((px >> 2) + ip1y) * prev.stride + (px & 3) + ip1x;
+                float t = 0;
+                t += m0 * (float)p[0];
+                t += m1 * (float)p[1];
+                t += m2 * (float)p[prev.stride];
+                t += m3 * (float)p[prev.stride + 1];
+                i1 = t;
+            }
+        }
+    }
+    float* out = G(a.rec_ws) + (size_t)blockIdx.y * SIA_REC_ROWS * a.rec_cap;
+    out[(size_t)(REC_I1 * 16 + px) * a.rec_cap + kp] = i1;
+    out[(size_t)(REC_PS * 16 + px) * a.rec_cap + kp] = psr;
+    out[(size_t)(REC_G0 * 16 + px) * a.rec_cap + kp] = g0;
+    out[(size_t)(REC_G1 * 16 + px) * a.rec_cap + kp] = g1;
+    const float gxx = row16_sum_dpp(g0 * g0), gxy = row16_sum_dpp(g0 * g1), gyy = row16_sum_dpp(g1 * g1);
+    if (px == 0) {
+        out[(size_t)64 * a.rec_cap + kp] = gxx;
+        out[(size_t)65 * a.rec_cap + kp] = gxy;
+        out[(size_t)66 * a.rec_cap + kp] = gyy;
+    }
+}
+
+// words that differ between a[0..n) and b[0..n): out[0] += their number, out[1] = min(out[1], the first one's index)
+__global__ void __launch_bounds__(256) words_diff_kernel(const uint32_t* a, const uint32_t* b, size_t n, unsigned long long* out) {
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256)
+        if (a[i] != b[i]) {
+            atomicAdd(&out[0], 1ull);
+            atomicMin(&out[1], (unsigned long long)i);
+        }
+}
+
+// Both kernels on the same batch of SiaArgs: `batch` sequences with keypoint arrays of `stride` slots each (kps2d,
+// flags — null: no flags), n_dev[b] <= n_bound keypoints, prev_pyr[b * max_pyramid_levels + level] the previous
+// frame's level images (any base alignment, any stride >= width, at least 3 x 3; the levels below
+// min_pyramid_level_pose_estimation are not read). Each kernel writes a workspace of its own, [batch][levels
+// used][68][rec_cap] floats filled with ws_fill first, so a word only one of them writes differs too. n_diff: the
+// number of differing 32-bit words, first_diff: the index of the first (-1: none); rec_out: null, or device memory that
+// receives the new kernel's workspace; ref_out: the same for the reference kernel's.
+extern "C" int svo_sia_records_check(svo_handle* h, int batch, int stride, const int32_t* n_dev, int n_bound,
+                                     const svo_kp2d* kps2d, const uint32_t* flags, const svo_image* prev_pyr,
+                                     const svo_camera_settings* cam, int rec_cap, uint32_t ws_fill, float* rec_out,
+                                     float* ref_out, int64_t* n_diff, int64_t* first_diff) {
+    CHECK_H(h);
+    if (!cam || !prev_pyr || !n_diff || !first_diff || (n_bound > 0 && !kps2d))
+        return svo_set_error(SVO_ERR_INVALID, "svo_sia_records_check: bad arguments");
+    if (cam->max_pyramid_levels < 1 || cam->max_pyramid_levels > 7 || cam->min_pyramid_level_pose_estimation < 0 ||
+        cam->min_pyramid_level_pose_estimation >= cam->max_pyramid_levels)
+        return svo_set_error(SVO_ERR_INVALID, "svo_sia_records_check: max_pyramid_levels must be 1..7, min below it");
+    if (rec_cap < 4 || (rec_cap & 3) || rec_cap < n_bound || rec_cap > (1 << 20))
+        return svo_set_error(SVO_ERR_INVALID, "svo_sia_records_check: rec_cap must be a multiple of 4 in n_bound..2^20");
+    int rc = check_batch_counts("svo_sia_records_check", batch, stride, n_dev, n_bound);
+    if (rc) return rc;
+    const int levels = cam->max_pyramid_levels;
+    for (int b = 0; b < batch; b++)
+        for (int l = cam->min_pyramid_level_pose_estimation; l < levels; l++) {
+            const svo_image& p = prev_pyr[(size_t)b * levels + l];
+            if (!p.data || p.width < 3 || p.height < 3 || p.stride < p.width)
+                return svo_set_error(SVO_ERR_INVALID, "svo_sia_records_check: sequence %d level %d: no image of at least 3 x 3", b, l);
+        }
+    const size_t rec_floats = sia_rec_ws_floats(*cam, rec_cap), words = rec_floats * (size_t)batch;
+    DevPtr<float> ws;
+    DevPtr<unsigned long long> res;
+    HIP_TRY(dev_malloc(ws, sizeof(float) * 2 * words));
+    HIP_TRY(dev_malloc(res, 2 * sizeof(unsigned long long)));
+    HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(ws.get()), (int)ws_fill, 2 * words, h->stream));
+    const unsigned long long init[2] = {0ull, ~0ull};
+    HIP_TRY(hipMemcpyAsync(res.get(), init, sizeof(init), hipMemcpyHostToDevice, h->stream));
+    std::vector<SiaArgs> blocks((size_t)2 * batch);          // [0, batch): the kernel's, [batch, 2 batch): the reference's
+    for (int k = 0; k < 2 * batch; k++) {
+        SiaArgs& sa = blocks[(size_t)k];
+        const int b = k % batch;
+        memset(&sa, 0, sizeof(sa));
+        for (int l = cam->min_pyramid_level_pose_estimation; l < levels; l++) sa.prev[l] = make_view(prev_pyr[(size_t)b * levels + l]);
+        sa.cam = *cam;
+        sa.n_ptr = n_dev + b;
+        sa.kps2d = kps2d ? kps2d + (size_t)b * (size_t)stride : nullptr;
+        sa.flags = flags ? flags + (size_t)b * (size_t)stride : nullptr;
+        sa.rec_ws = ws.get() + (size_t)k * rec_floats;
+        sa.rec_cap = rec_cap;
+        sa.dbg_level = -1;
+        sa.cap = stride;
+    }
+    SiaArgs* d;
+    rc = stage(h, blocks, &d);
+    if (rc) return rc;
+    launch_sia_prep(d, batch, *cam, n_bound, h->stream);
+    HIP_TRY(hipGetLastError());
+    const int nb = n_bound > 1 ? n_bound : 1;
+    sia_prep_ref_kernel<<<dim3((((nb + 3) & ~3) * 16 + 63) / 64, levels - cam->min_pyramid_level_pose_estimation, batch), 64, 0,
+                          h->stream>>>(d + batch);
+    HIP_TRY(hipGetLastError());
+    words_diff_kernel<<<(unsigned)std::min<size_t>((words + 255) / 256, 1024), 256, 0, h->stream>>>(
+        reinterpret_cast<const uint32_t*>(ws.get()), reinterpret_cast<const uint32_t*>(ws.get() + words), words, res.get());
+    HIP_TRY(hipGetLastError());
+    if (rec_out) HIP_TRY(hipMemcpyAsync(rec_out, ws.get(), sizeof(float) * words, hipMemcpyDeviceToDevice, h->stream));
+    if (ref_out) HIP_TRY(hipMemcpyAsync(ref_out, ws.get() + words, sizeof(float) * words, hipMemcpyDeviceToDevice, h->stream));
+    unsigned long long got[2];
+    HIP_TRY(hipMemcpyAsync(got, res.get(), sizeof(got), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    *n_diff = (int64_t)got[0];
+    *first_diff = got[0] ? (int64_t)got[1] : -1;
+    return SVO_OK;            // (the workspaces are freed here: the launches are complete)
 }
 
 extern "C" int svo_pose_mats_layout(int64_t* block_bytes, int64_t* rd_offset, int64_t* r_offset, int64_t* ri_offset,

@@ -173,7 +173,8 @@ struct SiaArgs {
     float* kp_ws;                 // workspace [9][rec_cap] floats: per-keypoint values of sets that do not fit LDS
     float* dbg_H;                 // optional [36+6+6]: H, b, step of the first get_gradient of `dbg_level`
     int dbg_level;
-    int cap;
+    int cap;                      // entries of kps2d / flags that may be read (>= *n_ptr): sia_prep_kernel asks for a slot
+                                  // before it knows the count and never for one at or past cap
     int exact_pinv;               // 1: reference-order normal equations + the reference's SVD pseudo-inverse (parity mode)
     PoseMats* mats_out;           // optional: rotation matrices of pose_out, for the kernels that project with it
 };
@@ -199,6 +200,11 @@ LaunchShape sia_pick_shape(int batch, const svo_camera_settings& cam, int width,
 LaunchStatus launch_sia(const SiaArgs* d_args, int batch, const svo_camera_settings& cam, int width,
                         int height, int n_bound, int rec_cap, int exact, hipStream_t stream);
 size_t sia_rec_ws_floats(const svo_camera_settings& cam, int rec_cap);   // size of SiaArgs::rec_ws
+// SiaArgs::rec_ws: [levels used][SIA_REC_ROWS][rec_cap] floats, row = field * 16 + patch pixel (fields REC_*), rows
+// 64..66 = sum over the patch of gx gx, gx gy, gy gy; sia_prep_kernel alone (launch_sia runs it first)
+constexpr int SIA_REC_ROWS = 68;
+enum { REC_I1 = 0, REC_PS = 1, REC_G0 = 2, REC_G1 = 3 };
+void launch_sia_prep(const SiaArgs* d_args, int batch, const svo_camera_settings& cam, int n_bound, hipStream_t stream);
 
 // --------------------------------------------------------------------- KLT
 struct KfDev {                    // one keyframe as the device sees it

@@ -54,6 +54,7 @@ SYMBOLS = (
     "svo_keyframe_launch_info", "svo_compact_batch", "svo_keyframe_merge_batch", "svo_keyframe_init_batch",
     "svo_keyframe_record_layout", "svo_ssd_disparity_batch",
     "svo_sparse_align_batch_mats", "svo_pose_mats_layout", "svo_filter_update_table_batch",
+    "svo_sia_records_check",
 )
 
 # svo_ctx_set_input_format / svo_convert_frames: how the buffers of a sequence become its two gray images
@@ -1237,6 +1238,30 @@ class Handle:
             assert mats_out.numel() * mats_out.element_size() >= batch * pose_mats_layout()["bytes"]
             _check(lib().svo_sparse_align_batch_mats(*args, _ptr(mats_out)))
         return pose_out, cost, trace, dbg, (waves.value, mode.value, cap.value)
+
+    def sia_records_check(self, n, n_bound, kps2d, flags, prev_pyrs, cam, rec_cap=None, ws_fill=0, want_records=False, want_ref=False):
+        """Diagnostic: the alignment records of len(n) sequences by the records kernel and by the one-lane-per-pixel
+        kernel it replaced (svo_sia_records_check). n: int32 [batch] device; kps2d [batch, stride, 2] float32, flags
+        [batch, stride] int32 / uint32 or None, device; prev_pyrs: per sequence the list of its max_pyramid_levels
+        level images (uint8 device tensors or views with unit column stride). Returns (number of differing 32-bit
+        words, index of the first or -1, the kernel's records [batch, levels used, 68, rec_cap] float32 or None); with
+        want_ref a fourth value: the replaced kernel's records."""
+        batch, stride = kps2d.shape[0], kps2d.shape[1]
+        levels = cam.max_pyramid_levels
+        if rec_cap is None:
+            rec_cap = (max(int(n_bound), 1) + 255) // 256 * 256
+        used = levels - cam.min_pyramid_level_pose_estimation
+        rec = torch.empty((batch, used, 68, rec_cap), dtype=torch.float32, device=kps2d.device) if want_records else None
+        ref = torch.empty((batch, used, 68, rec_cap), dtype=torch.float32, device=kps2d.device) if want_ref else None
+        pp = (Image * (batch * levels))()
+        for b in range(batch):
+            for l in range(levels):
+                pp[b * levels + l] = _img(prev_pyrs[b][l])
+        n_diff, first = C.c_int64(0), C.c_int64(0)
+        _check(lib().svo_sia_records_check(self._h, batch, stride, _ptr(n), int(n_bound), _ptr(kps2d), _ptr(flags), pp,
+                                           C.byref(cam), int(rec_cap), C.c_uint32(ws_fill), _ptr(rec), _ptr(ref), C.byref(n_diff),
+                                           C.byref(first)))
+        return (n_diff.value, first.value, rec, ref) if want_ref else (n_diff.value, first.value, rec)
 
     # -- A3 ---------------------------------------------------------------
     def project_keypoints(self, pose, kps3d, cam):
