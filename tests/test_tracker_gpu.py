@@ -24,15 +24,16 @@ def _free_port():
 pytestmark = pytest.mark.gpu
 
 def _run(config, n_frames, seed, on_device=False, motion_scale=1.0, exact=True, tol=None,
-         render_device="cpu"):
+         render_device="cpu", overrides=None):
     """Both trackers frame by frame. exact=True (the default here and of the product: the
     reference-order mode): every GN trace must equal the oracle's and the pose is the oracle's bit for
     bit; exact=False (svo_ctx_set_fast_solver): pose within 1e-4. Returns the fraction of
-    tracked frames whose GN traces equal the oracle's as the third value."""
+    tracked frames whose GN traces equal the oracle's as the third value. overrides: camera settings (the image
+    size among them) that replace the preset's."""
     if tol is None:
         tol = 0.0 if exact else 1e-4
     cfg, L, R, poses, ts = synth.make_sequence(config, n_frames, seed, device=render_device,
-                                               motion_scale=motion_scale)
+                                               motion_scale=motion_scale, overrides=overrides)
     L = [x.cpu() for x in L]
     R = [x.cpu() for x in R]
     cam = util.oracle_camera(cfg)
