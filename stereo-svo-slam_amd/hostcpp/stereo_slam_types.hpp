@@ -106,14 +106,27 @@ private:
             R[k] = t + s * r_x[k];
         }
     }
-    // cv::Rodrigues (matrix -> vector) for a proper rotation, away from theta = pi
+    // cv::Rodrigues (matrix -> vector) without its SVD re-orthonormalisation of the input: below
+    // s = 1e-5 the rotation is 0 (c > 0) or pi (c <= 0: axis from the diagonal, signs of y and z from
+    // R(0,1) and R(0,2), R(1,2) breaking the tie when x is the smallest component)
     static Vec3f matrix_to_vector(const double R[9]) {
-        const double rx = R[7] - R[5], ry = R[2] - R[6], rz = R[3] - R[1];
+        double rx = R[7] - R[5], ry = R[2] - R[6], rz = R[3] - R[1];
         const double s = std::sqrt((rx * rx + ry * ry + rz * rz) * 0.25);
         double c = (R[0] + R[4] + R[8] - 1) * 0.5;
         c = c > 1. ? 1. : (c < -1. ? -1. : c);
-        const double theta = std::acos(c);
-        if (s < 1e-5) return {0.f, 0.f, 0.f};
+        double theta = std::acos(c);
+        if (s < 1e-5) {
+            if (c > 0) return {0.f, 0.f, 0.f};
+            double t = (R[0] + 1) * 0.5;
+            rx = std::sqrt(t > 0. ? t : 0.);
+            t = (R[4] + 1) * 0.5;
+            ry = std::sqrt(t > 0. ? t : 0.) * (R[1] < 0 ? -1. : 1.);
+            t = (R[8] + 1) * 0.5;
+            rz = std::sqrt(t > 0. ? t : 0.) * (R[2] < 0 ? -1. : 1.);
+            if (std::fabs(rx) < std::fabs(ry) && std::fabs(rx) < std::fabs(rz) && (R[5] > 0) != (ry * rz > 0)) rz = -rz;
+            theta /= std::sqrt(rx * rx + ry * ry + rz * rz);
+            return {(float)(rx * theta), (float)(ry * theta), (float)(rz * theta)};
+        }
         const double vth = 1 / (2 * s) * theta;
         return {(float)(rx * vth), (float)(ry * vth), (float)(rz * vth)};
     }

@@ -301,16 +301,18 @@ def _rodrigues_inv(R):
     th = math.acos(c)
     v = np.array([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]])
     s = np.linalg.norm(v) / 2
-    if s < 1e-10:
+    if s < 1e-5:                     # OpenCV's threshold (hostcpp/stereo_slam_types.hpp has the same arms)
         if c > 0:
             return np.zeros(3)
-        # theta = pi: axis from the diagonal
+        # theta = pi: axis from the diagonal, signs from R(0,1), R(0,2) and the R(1,2) tie-break
         a = np.sqrt(np.maximum((np.diag(R) + 1) / 2, 0))
         if R[0, 1] < 0:
             a[1] = -a[1]
         if R[0, 2] < 0:
             a[2] = -a[2]
-        return a / max(np.linalg.norm(a), 1e-30) * th
+        if abs(a[0]) < abs(a[1]) and abs(a[0]) < abs(a[2]) and (R[1, 2] > 0) != (a[1] * a[2] > 0):
+            a[2] = -a[2]
+        return a * (th / math.sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]))
     return v / (2 * s) * th
 
 

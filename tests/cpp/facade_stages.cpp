@@ -4,7 +4,9 @@
 // steps through the ctypes binding and compares bit for bit.
 //   facade_stages <dir> <width> <height> [fast]
 //   <dir>/{l0,r0,l1,r1}.raw  width*height bytes each, <dir>/cam.bin = svo_camera_settings
-//   -> <dir>/out.bin: int32 n, then float32 records (see below)
+//   -> <dir>/out.bin: int32 n, then float32 records (see below), then int32: the levels of StereoImage::left and their
+//      (cols, rows), the levels of StereoImage::opt_flow and theirs
+// The images are handed over in rows of width + 13 bytes (Image8::step != cols).
 #include <cstdio>
 #include <cstring>
 #include <string>
@@ -25,6 +27,13 @@ static std::vector<uint8_t> read_file(const std::string& path, size_t bytes) {
     return v;
 }
 
+// a packed image copied into rows of `step` bytes; the padding holds 0xA5
+static std::vector<uint8_t> with_step(const std::vector<uint8_t>& src, int w, int h, int step) {
+    std::vector<uint8_t> v((size_t)step * h, 0xA5);
+    for (int y = 0; y < h; y++) std::memcpy(v.data() + (size_t)y * step, src.data() + (size_t)y * w, w);
+    return v;
+}
+
 int main(int argc, char** argv) {
     if (argc < 4) return 2;
     const std::string dir = argv[1];
@@ -36,7 +45,10 @@ int main(int argc, char** argv) {
         std::memcpy(&cam, cb.data(), sizeof(cam));
         const auto l0 = read_file(dir + "/l0.raw", (size_t)w * hgt), r0 = read_file(dir + "/r0.raw", (size_t)w * hgt);
         const auto l1 = read_file(dir + "/l1.raw", (size_t)w * hgt), r1 = read_file(dir + "/r1.raw", (size_t)w * hgt);
-        const Image8 L0{l0.data(), w, hgt, w}, R0{r0.data(), w, hgt, w}, L1{l1.data(), w, hgt, w}, R1{r1.data(), w, hgt, w};
+        const int step = w + 13;
+        const auto sl0 = with_step(l0, w, hgt, step), sr0 = with_step(r0, w, hgt, step);
+        const auto sl1 = with_step(l1, w, hgt, step), sr1 = with_step(r1, w, hgt, step);
+        const Image8 L0{sl0.data(), w, hgt, step}, R0{sr0.data(), w, hgt, step}, L1{sl1.data(), w, hgt, step}, R1{sr1.data(), w, hgt, step};
 
         // first frame through the tracker: keyframe 0 with its keypoints
         StereoSlam slam(cam);
@@ -84,6 +96,14 @@ int main(int argc, char** argv) {
             const KeyPointInformation& k = frame.kps.info[i];
             const float rec[5] = {(float)flags_of(k), (float)k.outlier_count, (float)k.inlier_count, k.kf_inv_depth, k.kf_variance};
             std::fwrite(rec, 4, 5, f);
+        }
+        for (const std::vector<DeviceImage>* pyr : {&frame.stereo_image.left, &frame.stereo_image.opt_flow}) {
+            const int32_t levels = (int32_t)pyr->size();
+            std::fwrite(&levels, 4, 1, f);
+            for (const DeviceImage& im : *pyr) {
+                const int32_t dims[2] = {im.cols(), im.rows()};
+                std::fwrite(dims, 4, 2, f);
+            }
         }
         std::fclose(f);
         std::printf("keypoints %d sia_cost %.3f refine_cost %.4f\n", n, sia_cost, refine_cost);

@@ -35,6 +35,33 @@ def test_robot_angles_is_rodrigues_of_rz_rx_ry():
     assert np.allclose(wire.robot_angles(np.zeros(6)), 0)
 
 
+def test_robot_angles_at_half_turns_equal_the_float64_twin():
+    """cv::Rodrigues' theta = pi arm (s < 1e-5, c <= 0: axis from the diagonal and its sign rules) against the float64
+    twin of tests/facade_ref.py. The twin takes its single-axis matrices from the oracle, wire.py from numpy: entries
+    agree to about 1e-15, and the axis is a square root of (Rii + 1) / 2, so components agree to sqrt(1e-15) = 3e-8
+    where the diagonal entry is near -1 and far better elsewhere; 1e-6 covers that."""
+    import facade_ref as FR
+    pi = float(np.float32(np.pi))
+    cases = [(pi, 0, 0), (0, pi, 0), (0, 0, -pi), (-pi, 0, 0), (0, -pi, 0), (0, 0, pi), (pi, pi, 0),
+             (np.pi, 0, 0), (0, 0, -np.pi), (np.pi - 5e-6, 0, 0), (0, -np.pi + 5e-6, 0)]
+    cases += [c for b in (-2.5, -1.0, 0.3, 1.0) for c in ((pi, b, 0), (pi, 0, b), (b, 0, pi), (b, 0, -pi), (0, pi, b), (-pi, b, 0))]
+    labels = set()
+    for angles in cases:
+        a32 = np.array(angles, np.float32)                  # (the twin takes float angles: give wire.py the same ones)
+        want, label, rotation = FR.robot_angles64(a32)
+        labels.add(label)
+        got = wire.robot_angles(np.concatenate([np.zeros(3), a32.astype(np.float64)]))
+        assert label.startswith(FR.PI) and abs(rotation - np.pi) < 2e-5, (angles, label, rotation)
+        assert np.allclose(got, want, rtol=0, atol=1e-6), (angles, label, got, want)
+    assert FR.robot_angles64(np.array([pi, pi, pi], np.float32))[1] == FR.ZERO          # three half turns: the identity
+    assert np.array_equal(wire.robot_angles([0, 0, 0, pi, pi, pi]), np.zeros(3))
+    assert wire.robot_angles([0, 0, 0, pi, 0, 0])[0] > 3.14             # a half turn, not (0, 0, 0) and not -pi
+    assert {FR.PI, FR.PI + "+y", FR.PI + "+z"} <= labels and any("+tie" in l for l in labels), labels
+    # s on both sides of OpenCV's threshold near a half turn: the generic arm above it
+    want, label, _ = FR.robot_angles64(np.array([np.pi - 2e-5, 0, 0], np.float32))
+    assert label == FR.GENERIC and np.allclose(wire.robot_angles([0, 0, 0, float(np.float32(np.pi - 2e-5)), 0, 0]), want, rtol=0, atol=1e-9)
+
+
 def test_messages_have_the_reference_layout():
     s = _FakeSlam()
     kfs = json.loads(wire.handle("ws://host:1234/keyframes", "get", s))
