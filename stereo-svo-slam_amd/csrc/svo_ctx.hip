@@ -17,12 +17,14 @@
 #include <new>
 #include <string>
 #include <thread>
+#include <variant>
 #include <vector>
 
 #include "svo_group.hpp"
 #include "svo_group_state.hpp"
 #include "svo_host.hpp"
 #include "svo_kernels.hpp"
+#include "svo_named_slots.hpp"
 
 // svo_ctx: the public object. Its sequences are split over 1..G groups; a group owns a
 // HIP stream, its argument blocks and (G > 1) a host thread that drives it, so the groups
@@ -30,10 +32,28 @@
 // its argument blocks, the other group's kernels keep the GPU busy, and the latency-bound
 // single-workgroup-per-sequence alignment kernel of one group overlaps the window kernels of
 // the other. svo_submit_images() queues a frame set on every group and returns;
-// svo_wait() drains the queues. svo_new_images() = submit + wait. Restarts (svo_ctx_restart_sequences),
-// exports (svo_submit_export, svo_submit_export_map, svo_submit_export_views, svo_submit_export_disparity, svo_submit_export_cloud, svo_submit_export_scenes, svo_submit_export_ar), saves and loads (svo_submit_save / svo_submit_load) and pose-filter updates
-// (svo_submit_pose_updates) are entries of the same queues, so they are ordered with the frame sets.
+// svo_wait() drains the queues. svo_new_images() = submit + wait. Everything else a ctx can submit (the kinds of
+// svo_ctx::Job) is an entry of the same queues, so it is ordered with the frame sets.
 struct svo_ctx {
+    // a frame set: the group's share of an svo_submit_images
+    struct Frames {
+        std::vector<const uint8_t*> left, right;
+        std::vector<float> ts;
+        int stride = 0, mem = 0;
+    };
+    // the end of some of the group's sequences (svo_ctx_restart_sequences): indices in the group
+    struct Restart {
+        std::vector<int> seqs;
+    };
+    // a trim of keyframes (svo_submit_trim_keyframes): indices in the group, and the id each one's keyframes go below
+    struct Trim {
+        std::vector<int> seqs, below;
+    };
+    // a rig assignment (svo_ctx_assign_rigs): indices in the group, and what each is bound to
+    struct RigAssign {
+        std::vector<int> seqs;
+        std::vector<RigBinding> bindings;
+    };
     // the group's share of an svo_submit_export: its named slots (indices in the group) in named order, the
     // segment each one fills, and the record of the caller's arrays the group packs from
     struct Export {
@@ -51,29 +71,18 @@ struct svo_ctx {
         svo_map_filter filter{};
         svo_map_dst dst{};
     };
-    // the group's share of an svo_submit_export_views: its named slots (indices in the group) in named order and the
-    // segment (and image) of the job each one fills
-    struct ViewExport {
+    // the group's share of an svo_submit_export_views, _disparity or _cloud: its named slots (indices in the group) in
+    // named order and the segment (and image, planes or records) of the job each one fills
+    template <typename Style, typename Dst>
+    struct ImageExport {
         int what = 0, mem = 0;
         std::vector<int> seqs, seg;
-        svo_view_style style{};
-        svo_view_dst dst{};
+        Style style{};
+        Dst dst{};
     };
-    // the group's share of an svo_submit_export_disparity: its named slots (indices in the group) in named order and
-    // the segment (and planes) of the job each one fills
-    struct DisparityExport {
-        int what = 0, mem = 0;
-        std::vector<int> seqs, seg;
-        svo_disparity_style style{};
-        svo_disparity_dst dst{};
-    };
-    // the group's share of an svo_submit_export_cloud: as DisparityExport, records in the place of planes
-    struct CloudExport {
-        int what = 0, mem = 0;
-        std::vector<int> seqs, seg;
-        svo_cloud_style style{};
-        svo_cloud_dst dst{};
-    };
+    using ViewExport = ImageExport<svo_view_style, svo_view_dst>;
+    using DisparityExport = ImageExport<svo_disparity_style, svo_disparity_dst>;
+    using CloudExport = ImageExport<svo_cloud_style, svo_cloud_dst>;
     // the group's share of an svo_submit_export_scenes: its named slots (indices in the group) in named order, the
     // camera of each and the segment (and image) of the job each one fills
     struct SceneExport {
@@ -92,11 +101,15 @@ struct svo_ctx {
         std::shared_ptr<const ArJob> job;
         svo_ar_dst dst{};
     };
-    // the group's share of an svo_submit_save (snaps) or svo_submit_load (loads): its named slots, indices in the group
-    struct Snapshots {
+    // the group's share of an svo_submit_save: its named slots, indices in the group, and where each one goes
+    struct Save {
         int mem = 0;
         std::vector<int> seqs;
         std::vector<svo_snapshot> snaps;
+    };
+    // the group's share of an svo_submit_load: the checked snapshots of its named slots (seq: index in the group)
+    struct Load {
+        int mem = 0;
         std::vector<SnapshotLoad> loads;
     };
     // the group's share of an svo_submit_pose_updates: its named slots with a positive count (indices in the group),
@@ -106,28 +119,9 @@ struct svo_ctx {
         std::vector<svo_pose_sample> samples;
         std::vector<float*> filtered;
     };
-    // one entry of a group's queue: a frame set, or (restart non-empty) the end of some of its sequences, or
-    // (exp.seqs non-empty) an export, or (snap.seqs / snap.loads non-empty) a save / a load, or (pose.seqs non-empty)
-    // pose-filter updates, or (map.seqs non-empty) a map export, or (view.seqs non-empty) a view job, or (scene.seqs
-    // non-empty) a scene job, or (ar.seqs non-empty) an ar job, or (disp.seqs non-empty) a disparity job, or (cloud.seqs non-empty) a cloud job, or (assign non-empty) a rig assignment, or (trim non-empty) a trim of keyframes
-    struct Job {
-        std::vector<const uint8_t*> left, right;
-        std::vector<float> ts;
-        int stride = 0, mem = 0;
-        std::vector<int> restart;        // indices in the group
-        std::vector<int> trim, trim_below;   // indices in the group, and the id each one's keyframes go below
-        std::vector<int> assign;         // indices in the group, and what each is bound to
-        std::vector<RigBinding> bindings;
-        Export exp;
-        Snapshots snap;
-        PoseUpdates pose;
-        MapExport map;
-        ViewExport view;
-        DisparityExport disp;
-        CloudExport cloud;
-        SceneExport scene;
-        ArExport ar;
-    };
+    // one entry of a group's queue (the frame set first: a Job{} is one, with nothing allocated)
+    using Job = std::variant<Frames, Restart, Trim, RigAssign, Export, MapExport, ViewExport, DisparityExport, CloudExport,
+                             SceneExport, ArExport, Save, Load, PoseUpdates>;
     struct Worker {
         Group g;
         int first = 0, count = 0;
@@ -173,45 +167,43 @@ namespace {
 // the job joins the group's queue (one group: it runs here, on the caller's thread)
 void worker_submit(svo_ctx::Worker& w, svo_ctx::Job&& job);
 
+// what a group runs for each kind of entry (seq0: the ctx slot of the group's first)
+int run_job(svo_group* g, int, const svo_ctx::Frames& j) {
+    return grp_new_images(g, j.left.data(), j.right.empty() ? nullptr : j.right.data(), j.stride, j.ts.data(), j.mem);
+}
+int run_job(svo_group* g, int, const svo_ctx::Restart& j) { return grp_restart_sequences(g, j.seqs.data(), (int)j.seqs.size()); }
+int run_job(svo_group* g, int, const svo_ctx::Trim& j) { return grp_trim_keyframes(g, j.seqs.data(), j.below.data(), (int)j.seqs.size()); }
+int run_job(svo_group* g, int, const svo_ctx::RigAssign& j) { return grp_assign_rigs(g, j.seqs.data(), j.bindings.data(), (int)j.seqs.size()); }
+int run_job(svo_group* g, int seq0, const svo_ctx::Export& j) {
+    return grp_export(g, j.what, j.mem, j.seqs.data(), j.seg.data(), (int)j.seqs.size(), seq0, j.base, &j.dst);
+}
+int run_job(svo_group* g, int seq0, const svo_ctx::MapExport& j) {
+    return grp_export_map(g, j.mem, j.seqs.data(), j.seg.data(), j.regions.data(), (int)j.seqs.size(), seq0, &j.filter, &j.dst);
+}
+int run_job(svo_group* g, int seq0, const svo_ctx::ViewExport& j) {
+    return grp_export_views(g, j.what, j.mem, j.seqs.data(), j.seg.data(), (int)j.seqs.size(), seq0, &j.style, &j.dst);
+}
+int run_job(svo_group* g, int seq0, const svo_ctx::DisparityExport& j) {
+    return grp_export_disparity(g, j.what, j.mem, j.seqs.data(), j.seg.data(), (int)j.seqs.size(), seq0, &j.style, &j.dst);
+}
+int run_job(svo_group* g, int seq0, const svo_ctx::CloudExport& j) {
+    return grp_export_cloud(g, j.what, j.mem, j.seqs.data(), j.seg.data(), (int)j.seqs.size(), seq0, &j.style, &j.dst);
+}
+int run_job(svo_group* g, int seq0, const svo_ctx::SceneExport& j) {
+    return grp_export_scenes(g, j.mem, j.seqs.data(), j.seg.data(), (int)j.seqs.size(), seq0, &j.style, j.cameras.data(), &j.dst);
+}
+int run_job(svo_group* g, int seq0, const svo_ctx::ArExport& j) {
+    return grp_export_ar(g, j.mem, j.seqs.data(), j.seg.data(), j.inst0.data(), j.inst1.data(), (int)j.seqs.size(), seq0, j.job.get(), &j.dst);
+}
+int run_job(svo_group* g, int, const svo_ctx::Save& j) { return grp_save(g, j.seqs.data(), (int)j.seqs.size(), j.snaps.data(), j.mem); }
+int run_job(svo_group* g, int, const svo_ctx::Load& j) { return grp_load(g, j.loads.data(), (int)j.loads.size(), j.mem); }
+int run_job(svo_group* g, int, const svo_ctx::PoseUpdates& j) {
+    return grp_pose_updates(g, j.seqs.data(), j.counts.data(), (int)j.seqs.size(), j.samples.data(), j.filtered.data());
+}
+
 void worker_run_job(svo_ctx::Worker& w, const svo_ctx::Job& job) {
     if (w.err != SVO_OK || w.ctx_failed->load()) return;   // after a failure (any group) the queues are dropped
-    const svo_ctx::Export& e = job.exp;
-    const svo_ctx::Snapshots& sn = job.snap;
-    const svo_ctx::PoseUpdates& pu = job.pose;
-    const svo_ctx::MapExport& mp = job.map;
-    const svo_ctx::ViewExport& vw = job.view;
-    const svo_ctx::SceneExport& sc = job.scene;
-    const svo_ctx::ArExport& ar = job.ar;
-    const svo_ctx::DisparityExport& dp = job.disp;
-    const svo_ctx::CloudExport& cl = job.cloud;
-    const int rc = !cl.seqs.empty()
-                       ? grp_export_cloud(w.g.get(), cl.what, cl.mem, cl.seqs.data(), cl.seg.data(), (int)cl.seqs.size(), w.first, &cl.style, &cl.dst)
-                   : !dp.seqs.empty()
-                       ? grp_export_disparity(w.g.get(), dp.what, dp.mem, dp.seqs.data(), dp.seg.data(), (int)dp.seqs.size(), w.first, &dp.style, &dp.dst)
-                   : !ar.seqs.empty()
-                       ? grp_export_ar(w.g.get(), ar.mem, ar.seqs.data(), ar.seg.data(), ar.inst0.data(), ar.inst1.data(), (int)ar.seqs.size(), w.first, ar.job.get(), &ar.dst)
-                   : !sc.seqs.empty()
-                       ? grp_export_scenes(w.g.get(), sc.mem, sc.seqs.data(), sc.seg.data(), (int)sc.seqs.size(), w.first, &sc.style, sc.cameras.data(), &sc.dst)
-                   : !vw.seqs.empty()
-                       ? grp_export_views(w.g.get(), vw.what, vw.mem, vw.seqs.data(), vw.seg.data(), (int)vw.seqs.size(), w.first, &vw.style, &vw.dst)
-                   : !mp.seqs.empty()
-                       ? grp_export_map(w.g.get(), mp.mem, mp.seqs.data(), mp.seg.data(), mp.regions.data(), (int)mp.seqs.size(), w.first, &mp.filter, &mp.dst)
-                   : !pu.seqs.empty()
-                       ? grp_pose_updates(w.g.get(), pu.seqs.data(), pu.counts.data(), (int)pu.seqs.size(), pu.samples.data(), pu.filtered.data())
-                   : !sn.loads.empty()
-                       ? grp_load(w.g.get(), sn.loads.data(), (int)sn.loads.size(), sn.mem)
-                   : !sn.seqs.empty()
-                       ? grp_save(w.g.get(), sn.seqs.data(), (int)sn.seqs.size(), sn.snaps.data(), sn.mem)
-                   : !e.seqs.empty()
-                       ? grp_export(w.g.get(), e.what, e.mem, e.seqs.data(), e.seg.data(), (int)e.seqs.size(), w.first, e.base, &e.dst)
-                   : !job.assign.empty()
-                       ? grp_assign_rigs(w.g.get(), job.assign.data(), job.bindings.data(), (int)job.assign.size())
-                   : !job.trim.empty()
-                       ? grp_trim_keyframes(w.g.get(), job.trim.data(), job.trim_below.data(), (int)job.trim.size())
-                   : !job.restart.empty()
-                       ? grp_restart_sequences(w.g.get(), job.restart.data(), (int)job.restart.size())
-                       : grp_new_images(w.g.get(), job.left.data(), job.right.empty() ? nullptr : job.right.data(), job.stride,
-                                        job.ts.data(), job.mem);
+    const int rc = std::visit([&w](const auto& j) { return run_job(w.g.get(), w.first, j); }, job);
     if (rc != SVO_OK) {
         w.err = rc;
         w.msg = svo_last_error();
@@ -282,6 +274,12 @@ int ctx_seq(svo_ctx* c, int seq, svo_group** g, int* local) {
         }
     HIP_TRY(hipSetDevice(c->device));
     return SVO_OK;
+}
+
+// nothing is queued on any group once one of them has failed (the first call after the failure reports its cause)
+int reject_failed(svo_ctx* c, const char* name) {
+    const int rc = ctx_drain(c);
+    return rc ? rc : svo_set_error(SVO_ERR_INVALID, "%s: an earlier frame of this ctx failed; create a new ctx", name);
 }
 
 }  // namespace
@@ -359,13 +357,10 @@ extern "C" int svo_submit_images(svo_ctx* c, const uint8_t* const* left, const u
     const svo::IngestFormat& f = *svo::ingest_format(c->input_format);
     if ((long long)stride < (long long)svo::ingest_row_pixels(f, c->width) * f.channels)   // (nothing is queued: the ctx stays usable)
         return svo_set_error(SVO_ERR_INVALID, "svo_submit_images: stride %d is below the row's bytes", stride);
-    if (c->failed.load()) {                      // nothing is queued on any group once one of them has failed
-        const int rc = ctx_drain(c);             // (the first call after the failure reports its cause)
-        return rc ? rc : svo_set_error(SVO_ERR_INVALID, "svo_submit_images: an earlier frame of this ctx failed; create a new ctx");
-    }
+    if (c->failed.load()) return reject_failed(c, "svo_submit_images");
     for (auto& wp : c->workers) {
         svo_ctx::Worker& w = *wp;
-        svo_ctx::Job job;
+        svo_ctx::Frames job;
         job.left.assign(left + w.first, left + w.first + w.count);
         if (right && !c->one_buffer()) job.right.assign(right + w.first, right + w.first + w.count);   // (else: ignored)
         job.ts.assign(time_stamps + w.first, time_stamps + w.first + w.count);
@@ -377,19 +372,15 @@ extern "C" int svo_submit_images(svo_ctx* c, const uint8_t* const* left, const u
 
 extern "C" int svo_ctx_restart_sequences(svo_ctx* c, const int* seqs, int n) {
     if (!c || n < 0 || (n > 0 && !seqs)) return svo_set_error(SVO_ERR_INVALID, "svo_ctx_restart_sequences: bad arguments");
-    for (int i = 0; i < n; i++)
-        if (seqs[i] < 0 || seqs[i] >= c->B)
-            return svo_set_error(SVO_ERR_INVALID, "svo_ctx_restart_sequences: sequence %d out of range", seqs[i]);
-    if (c->failed.load()) {                      // (as svo_submit_images)
-        const int rc = ctx_drain(c);
-        return rc ? rc : svo_set_error(SVO_ERR_INVALID, "svo_ctx_restart_sequences: an earlier frame of this ctx failed; create a new ctx");
-    }
+    const NamedSlots slots{seqs, n};
+    if (const int bad = slots.first_bad(c->B, false); bad >= 0)
+        return svo_set_error(SVO_ERR_INVALID, "svo_ctx_restart_sequences: sequence %d out of range", slots.at(bad));
+    if (c->failed.load()) return reject_failed(c, "svo_ctx_restart_sequences");
     for (auto& wp : c->workers) {
         svo_ctx::Worker& w = *wp;
-        svo_ctx::Job job;
-        for (int i = 0; i < n; i++)
-            if (seqs[i] >= w.first && seqs[i] < w.first + w.count) job.restart.push_back(seqs[i] - w.first);
-        if (!job.restart.empty()) worker_submit(w, std::move(job));
+        svo_ctx::Restart job;
+        slots.each_in(w.first, w.count, [&](int, int local) { job.seqs.push_back(local); });
+        if (!job.seqs.empty()) worker_submit(w, std::move(job));
     }
     return SVO_OK;
 }
@@ -397,27 +388,18 @@ extern "C" int svo_ctx_restart_sequences(svo_ctx* c, const int* seqs, int n) {
 extern "C" int svo_submit_trim_keyframes(svo_ctx* c, const int* seqs, const int* below, int n) {
     if (!c || (seqs && n < 0)) return svo_set_error(SVO_ERR_INVALID, "svo_submit_trim_keyframes: bad arguments");
     if (!seqs) n = c->B;
-    std::vector<char> named(c->B, 0);
-    for (int i = 0; i < n; i++) {
-        const int s = seqs ? seqs[i] : i;
-        if (s < 0 || s >= c->B || named[s])
-            return svo_set_error(SVO_ERR_INVALID, "svo_submit_trim_keyframes: sequence %d is out of range or named twice", s);
-        named[s] = 1;
-    }
-    if (c->failed.load()) {                      // (as svo_submit_images)
-        const int rc = ctx_drain(c);
-        return rc ? rc : svo_set_error(SVO_ERR_INVALID, "svo_submit_trim_keyframes: an earlier frame of this ctx failed; create a new ctx");
-    }
+    const NamedSlots slots{seqs, n};
+    if (const int bad = slots.first_bad(c->B, true); bad >= 0)
+        return svo_set_error(SVO_ERR_INVALID, "svo_submit_trim_keyframes: sequence %d is out of range or named twice", slots.at(bad));
+    if (c->failed.load()) return reject_failed(c, "svo_submit_trim_keyframes");
     for (auto& wp : c->workers) {
         svo_ctx::Worker& w = *wp;
-        svo_ctx::Job job;
-        for (int i = 0; i < n; i++) {
-            const int s = seqs ? seqs[i] : i;
-            if (s < w.first || s >= w.first + w.count) continue;
-            job.trim.push_back(s - w.first);
-            job.trim_below.push_back(below ? below[i] : INT_MAX);     // (NULL: everything retired)
-        }
-        if (!job.trim.empty()) worker_submit(w, std::move(job));
+        svo_ctx::Trim job;
+        slots.each_in(w.first, w.count, [&](int i, int local) {
+            job.seqs.push_back(local);
+            job.below.push_back(below ? below[i] : INT_MAX);     // (NULL: everything retired)
+        });
+        if (!job.seqs.empty()) worker_submit(w, std::move(job));
     }
     return SVO_OK;
 }
@@ -447,36 +429,25 @@ extern "C" int svo_submit_export(svo_ctx* c, int what, const int* seqs, int n, c
         (mem != SVO_MEM_HOST && mem != SVO_MEM_DEVICE) || (seqs && n < 0))
         return svo_set_error(SVO_ERR_INVALID, "svo_submit_export: bad arguments (what %d, mem %d)", what, mem);
     if (!seqs) n = c->B;
-    std::vector<char> named(c->B, 0);
-    for (int i = 0; i < n; i++) {
-        const int s = seqs ? seqs[i] : i;
-        if (s < 0 || s >= c->B || named[s])
-            return svo_set_error(SVO_ERR_INVALID, "svo_submit_export: sequence %d is out of range or named twice", s);
-        named[s] = 1;
-    }
+    const NamedSlots slots{seqs, n};
+    if (const int bad = slots.first_bad(c->B, true); bad >= 0)
+        return svo_set_error(SVO_ERR_INVALID, "svo_submit_export: sequence %d is out of range or named twice", slots.at(bad));
     for (const void* p : {(const void*)dst->kps2d, (const void*)dst->kps3d, (const void*)dst->info})
         if ((uintptr_t)p & 3) return svo_set_error(SVO_ERR_INVALID, "svo_submit_export: an array is not 4-byte aligned");
     const int64_t per_seq = grp_capacity(c->workers[0]->g.get());     // (the same in every group)
     if ((dst->kps2d || dst->kps3d || dst->info) && dst->capacity < n * per_seq)
         return svo_set_error(SVO_ERR_CAPACITY, "svo_submit_export: %d slots need arrays of %lld records, capacity %lld", n,
                              (long long)(n * per_seq), (long long)dst->capacity);
-    if (c->failed.load()) {                      // (as svo_submit_images)
-        const int rc = ctx_drain(c);
-        return rc ? rc : svo_set_error(SVO_ERR_INVALID, "svo_submit_export: an earlier frame of this ctx failed; create a new ctx");
-    }
+    if (c->failed.load()) return reject_failed(c, "svo_submit_export");
     int64_t before = 0;                          // named slots of the groups so far
     for (auto& wp : c->workers) {
         svo_ctx::Worker& w = *wp;
-        svo_ctx::Job job;
-        svo_ctx::Export& e = job.exp;
-        for (int i = 0; i < n; i++) {
-            const int s = seqs ? seqs[i] : i;
-            if (s >= w.first && s < w.first + w.count) { e.seqs.push_back(s - w.first); e.seg.push_back(i); }
-        }
+        svo_ctx::Export e;
+        slots.each_in(w.first, w.count, [&](int i, int local) { e.seqs.push_back(local); e.seg.push_back(i); });
         if (e.seqs.empty()) continue;
         e.what = what; e.mem = mem; e.dst = *dst; e.base = before * per_seq;
         before += (int64_t)e.seqs.size();
-        worker_submit(w, std::move(job));
+        worker_submit(w, std::move(e));
     }
     return SVO_OK;
 }
@@ -492,18 +463,10 @@ namespace {
 int check_snapshot_call(svo_ctx* c, const char* name, const int* seqs, int n, const svo_snapshot* snaps, int mem) {
     if (!c || n < 0 || (n > 0 && (!seqs || !snaps)) || (mem != SVO_MEM_HOST && mem != SVO_MEM_DEVICE))
         return svo_set_error(SVO_ERR_INVALID, "%s: bad arguments (mem %d)", name, mem);
-    std::vector<char> named(c->B, 0);
-    for (int i = 0; i < n; i++) {
-        if (seqs[i] < 0 || seqs[i] >= c->B || named[seqs[i]])
-            return svo_set_error(SVO_ERR_INVALID, "%s: sequence %d is out of range or named twice", name, seqs[i]);
-        named[seqs[i]] = 1;
-    }
+    const NamedSlots slots{seqs, n};
+    if (const int bad = slots.first_bad(c->B, true); bad >= 0)
+        return svo_set_error(SVO_ERR_INVALID, "%s: sequence %d is out of range or named twice", name, slots.at(bad));
     return SVO_OK;
-}
-
-int reject_failed(svo_ctx* c, const char* name) {      // (as svo_submit_images)
-    const int rc = ctx_drain(c);
-    return rc ? rc : svo_set_error(SVO_ERR_INVALID, "%s: an earlier frame of this ctx failed; create a new ctx", name);
 }
 
 }  // namespace
@@ -518,12 +481,11 @@ extern "C" int svo_submit_export_map(svo_ctx* c, const int* seqs, int n, const s
     if ((f.drop_flags & ~(uint32_t)(SVO_IGNORE_DURING_REFINEMENT | SVO_IGNORE_COMPLETELY | SVO_IGNORE_TEMPORARY)) || f._reserved != 0)
         return svo_set_error(SVO_ERR_INVALID, "svo_submit_export_map: drop_flags 0x%x has unknown bits, or _reserved is not 0", f.drop_flags);
     if ((uintptr_t)dst->points & 15) return svo_set_error(SVO_ERR_INVALID, "svo_submit_export_map: points is not 16-byte aligned");
-    std::vector<char> named(c->B, 0);
-    for (int i = 0; i < n; i++) {
-        const int s = seqs ? seqs[i] : i;
-        if (s < 0 || s >= c->B || named[s])
-            return svo_set_error(SVO_ERR_INVALID, "svo_submit_export_map: sequence %d is out of range or named twice", s);
-        named[s] = 1;
+    const NamedSlots slots{seqs, n};
+    const int bad = slots.first_bad(c->B, true);
+    for (int i = 0; i < n; i++) {                // (a slot's name is checked before its region)
+        if (i == bad)
+            return svo_set_error(SVO_ERR_INVALID, "svo_submit_export_map: sequence %d is out of range or named twice", slots.at(i));
         const svo_map_region& r = regions[i];
         if (r.first_point < 0 || r.point_capacity < 0 || r.first_keyframe_entry < 0 || r.keyframe_capacity < 0 || r.from_keyframe < 0)
             return svo_set_error(SVO_ERR_INVALID, "svo_submit_export_map: region %d has a negative field", i);
@@ -533,15 +495,11 @@ extern "C" int svo_submit_export_map(svo_ctx* c, const int* seqs, int n, const s
     if (c->failed.load()) return reject_failed(c, "svo_submit_export_map");
     for (auto& wp : c->workers) {
         svo_ctx::Worker& w = *wp;
-        svo_ctx::Job job;
-        svo_ctx::MapExport& e = job.map;
-        for (int i = 0; i < n; i++) {
-            const int s = seqs ? seqs[i] : i;
-            if (s >= w.first && s < w.first + w.count) { e.seqs.push_back(s - w.first); e.seg.push_back(i); e.regions.push_back(regions[i]); }
-        }
+        svo_ctx::MapExport e;
+        slots.each_in(w.first, w.count, [&](int i, int local) { e.seqs.push_back(local); e.seg.push_back(i); e.regions.push_back(regions[i]); });
         if (e.seqs.empty()) continue;
         e.mem = mem; e.filter = f; e.dst = *dst;
-        worker_submit(w, std::move(job));
+        worker_submit(w, std::move(e));
     }
     return SVO_OK;
 }
@@ -562,13 +520,9 @@ extern "C" int svo_submit_export_views(svo_ctx* c, int what, const int* seqs, in
     if (!dst->pixels || ((uintptr_t)dst->pixels & 3))
         return svo_set_error(SVO_ERR_INVALID, "svo_submit_export_views: pixels is NULL or not 4-byte aligned");
     if (!seqs) n = c->B;
-    std::vector<char> named(c->B, 0);
-    for (int i = 0; i < n; i++) {
-        const int s = seqs ? seqs[i] : i;
-        if (s < 0 || s >= c->B || named[s])
-            return svo_set_error(SVO_ERR_INVALID, "svo_submit_export_views: sequence %d is out of range or named twice", s);
-        named[s] = 1;
-    }
+    const NamedSlots slots{seqs, n};
+    if (const int bad = slots.first_bad(c->B, true); bad >= 0)
+        return svo_set_error(SVO_ERR_INVALID, "svo_submit_export_views: sequence %d is out of range or named twice", slots.at(bad));
     const int64_t image_bytes = grp_view_bytes(g0, style);
     if (dst->capacity < n * image_bytes)
         return svo_set_error(SVO_ERR_CAPACITY, "svo_submit_export_views: %d slots need %lld bytes, capacity %lld", n,
@@ -576,15 +530,11 @@ extern "C" int svo_submit_export_views(svo_ctx* c, int what, const int* seqs, in
     if (c->failed.load()) return reject_failed(c, "svo_submit_export_views");
     for (auto& wp : c->workers) {
         svo_ctx::Worker& w = *wp;
-        svo_ctx::Job job;
-        svo_ctx::ViewExport& e = job.view;
-        for (int i = 0; i < n; i++) {
-            const int s = seqs ? seqs[i] : i;
-            if (s >= w.first && s < w.first + w.count) { e.seqs.push_back(s - w.first); e.seg.push_back(i); }
-        }
+        svo_ctx::ViewExport e;
+        slots.each_in(w.first, w.count, [&](int i, int local) { e.seqs.push_back(local); e.seg.push_back(i); });
         if (e.seqs.empty()) continue;
         e.what = what; e.mem = mem; e.style = *style; e.dst = *dst;
-        worker_submit(w, std::move(job));
+        worker_submit(w, std::move(e));
     }
     return SVO_OK;
 }
@@ -605,13 +555,9 @@ extern "C" int svo_submit_export_disparity(svo_ctx* c, int what, const int* seqs
     if (!dst->values || ((uintptr_t)dst->values & 15))
         return svo_set_error(SVO_ERR_INVALID, "svo_submit_export_disparity: values is NULL or not 16-byte aligned");
     if (!seqs) n = c->B;
-    std::vector<char> named(c->B, 0);
-    for (int i = 0; i < n; i++) {
-        const int s = seqs ? seqs[i] : i;
-        if (s < 0 || s >= c->B || named[s])
-            return svo_set_error(SVO_ERR_INVALID, "svo_submit_export_disparity: sequence %d is out of range or named twice", s);
-        named[s] = 1;
-    }
+    const NamedSlots slots{seqs, n};
+    if (const int bad = slots.first_bad(c->B, true); bad >= 0)
+        return svo_set_error(SVO_ERR_INVALID, "svo_submit_export_disparity: sequence %d is out of range or named twice", slots.at(bad));
     const int64_t image_bytes = grp_disparity_bytes(g0, style);
     if (dst->capacity < n * image_bytes)
         return svo_set_error(SVO_ERR_CAPACITY, "svo_submit_export_disparity: %d slots need %lld bytes, capacity %lld", n,
@@ -619,15 +565,11 @@ extern "C" int svo_submit_export_disparity(svo_ctx* c, int what, const int* seqs
     if (c->failed.load()) return reject_failed(c, "svo_submit_export_disparity");
     for (auto& wp : c->workers) {
         svo_ctx::Worker& w = *wp;
-        svo_ctx::Job job;
-        svo_ctx::DisparityExport& e = job.disp;
-        for (int i = 0; i < n; i++) {
-            const int s = seqs ? seqs[i] : i;
-            if (s >= w.first && s < w.first + w.count) { e.seqs.push_back(s - w.first); e.seg.push_back(i); }
-        }
+        svo_ctx::DisparityExport e;
+        slots.each_in(w.first, w.count, [&](int i, int local) { e.seqs.push_back(local); e.seg.push_back(i); });
         if (e.seqs.empty()) continue;
         e.what = what; e.mem = mem; e.style = *style; e.dst = *dst;
-        worker_submit(w, std::move(job));
+        worker_submit(w, std::move(e));
     }
     return SVO_OK;
 }
@@ -648,13 +590,9 @@ extern "C" int svo_submit_export_cloud(svo_ctx* c, int what, const int* seqs, in
     if (!dst->points || ((uintptr_t)dst->points & 15))
         return svo_set_error(SVO_ERR_INVALID, "svo_submit_export_cloud: points is NULL or not 16-byte aligned");
     if (!seqs) n = c->B;
-    std::vector<char> named(c->B, 0);
-    for (int i = 0; i < n; i++) {
-        const int s = seqs ? seqs[i] : i;
-        if (s < 0 || s >= c->B || named[s])
-            return svo_set_error(SVO_ERR_INVALID, "svo_submit_export_cloud: sequence %d is out of range or named twice", s);
-        named[s] = 1;
-    }
+    const NamedSlots slots{seqs, n};
+    if (const int bad = slots.first_bad(c->B, true); bad >= 0)
+        return svo_set_error(SVO_ERR_INVALID, "svo_submit_export_cloud: sequence %d is out of range or named twice", slots.at(bad));
     const int64_t per_slot = grp_cloud_points(g0, style);
     if (dst->capacity < n * per_slot)
         return svo_set_error(SVO_ERR_CAPACITY, "svo_submit_export_cloud: %d slots need %lld records, capacity %lld", n,
@@ -662,15 +600,11 @@ extern "C" int svo_submit_export_cloud(svo_ctx* c, int what, const int* seqs, in
     if (c->failed.load()) return reject_failed(c, "svo_submit_export_cloud");
     for (auto& wp : c->workers) {
         svo_ctx::Worker& w = *wp;
-        svo_ctx::Job job;
-        svo_ctx::CloudExport& e = job.cloud;
-        for (int i = 0; i < n; i++) {
-            const int s = seqs ? seqs[i] : i;
-            if (s >= w.first && s < w.first + w.count) { e.seqs.push_back(s - w.first); e.seg.push_back(i); }
-        }
+        svo_ctx::CloudExport e;
+        slots.each_in(w.first, w.count, [&](int i, int local) { e.seqs.push_back(local); e.seg.push_back(i); });
         if (e.seqs.empty()) continue;
         e.what = what; e.mem = mem; e.style = *style; e.dst = *dst;
-        worker_submit(w, std::move(job));
+        worker_submit(w, std::move(e));
     }
     return SVO_OK;
 }
@@ -689,12 +623,11 @@ extern "C" int svo_submit_export_scenes(svo_ctx* c, const int* seqs, int n, cons
     if (!dst->pixels || ((uintptr_t)dst->pixels & 3))
         return svo_set_error(SVO_ERR_INVALID, "svo_submit_export_scenes: pixels is NULL or not 4-byte aligned");
     if (!seqs) n = c->B;
-    std::vector<char> named(c->B, 0);
-    for (int i = 0; i < n; i++) {
-        const int s = seqs ? seqs[i] : i;
-        if (s < 0 || s >= c->B || named[s])
-            return svo_set_error(SVO_ERR_INVALID, "svo_submit_export_scenes: sequence %d is out of range or named twice", s);
-        named[s] = 1;
+    const NamedSlots slots{seqs, n};
+    const int bad = slots.first_bad(c->B, true);
+    for (int i = 0; i < n; i++) {                // (a slot's name is checked before its camera)
+        if (i == bad)
+            return svo_set_error(SVO_ERR_INVALID, "svo_submit_export_scenes: sequence %d is out of range or named twice", slots.at(i));
         if (const int rc = svo::scene_check_camera(&cameras[i], "svo_submit_export_scenes", i)) return rc;
     }
     const int64_t image_bytes = grp_scene_bytes(style);
@@ -704,15 +637,11 @@ extern "C" int svo_submit_export_scenes(svo_ctx* c, const int* seqs, int n, cons
     if (c->failed.load()) return reject_failed(c, "svo_submit_export_scenes");
     for (auto& wp : c->workers) {
         svo_ctx::Worker& w = *wp;
-        svo_ctx::Job job;
-        svo_ctx::SceneExport& e = job.scene;
-        for (int i = 0; i < n; i++) {
-            const int s = seqs ? seqs[i] : i;
-            if (s >= w.first && s < w.first + w.count) { e.seqs.push_back(s - w.first); e.seg.push_back(i); e.cameras.push_back(cameras[i]); }
-        }
+        svo_ctx::SceneExport e;
+        slots.each_in(w.first, w.count, [&](int i, int local) { e.seqs.push_back(local); e.seg.push_back(i); e.cameras.push_back(cameras[i]); });
         if (e.seqs.empty()) continue;
         e.mem = mem; e.style = *style; e.dst = *dst;
-        worker_submit(w, std::move(job));
+        worker_submit(w, std::move(e));
     }
     return SVO_OK;
 }
@@ -733,12 +662,9 @@ extern "C" int svo_submit_export_ar(svo_ctx* c, const int* seqs, int n, const sv
     if (const int rc = svo::ar_check_style(style, who)) return rc;
     if (!dst->pixels || ((uintptr_t)dst->pixels & 3)) return svo_set_error(SVO_ERR_INVALID, "%s: pixels is NULL or not 4-byte aligned", who);
     if (!seqs) n = c->B;
-    std::vector<char> named(c->B, 0);
-    for (int i = 0; i < n; i++) {
-        const int s = seqs ? seqs[i] : i;
-        if (s < 0 || s >= c->B || named[s]) return svo_set_error(SVO_ERR_INVALID, "%s: sequence %d is out of range or named twice", who, s);
-        named[s] = 1;
-    }
+    const NamedSlots slots{seqs, n};
+    if (const int bad = slots.first_bad(c->B, true); bad >= 0)
+        return svo_set_error(SVO_ERR_INVALID, "%s: sequence %d is out of range or named twice", who, slots.at(bad));
     if (first) {
         if (first[0] < 0 || first[n] != n_instances)
             return svo_set_error(SVO_ERR_INVALID, "%s: first starts at %d and ends at %d, not at >= 0 and %d", who, first[0], first[n], n_instances);
@@ -782,17 +708,14 @@ extern "C" int svo_submit_export_ar(svo_ctx* c, const int* seqs, int n, const sv
     if (c->failed.load()) return reject_failed(c, who);
     for (auto& wp : c->workers) {
         svo_ctx::Worker& w = *wp;
-        svo_ctx::Job jb;
-        svo_ctx::ArExport& e = jb.ar;
-        for (int i = 0; i < n; i++) {
-            const int s = seqs ? seqs[i] : i;
-            if (s < w.first || s >= w.first + w.count) continue;
-            e.seqs.push_back(s - w.first); e.seg.push_back(i);
+        svo_ctx::ArExport e;
+        slots.each_in(w.first, w.count, [&](int i, int local) {
+            e.seqs.push_back(local); e.seg.push_back(i);
             e.inst0.push_back(first ? first[i] : 0); e.inst1.push_back(first ? first[i + 1] : n_instances);
-        }
+        });
         if (e.seqs.empty()) continue;
         e.mem = mem; e.job = job; e.dst = *dst;
-        worker_submit(w, std::move(jb));
+        worker_submit(w, std::move(e));
     }
     return SVO_OK;
 }
@@ -818,16 +741,13 @@ extern "C" int svo_submit_save(svo_ctx* c, const int* seqs, int n, svo_snapshot*
             (!snaps[i].data && snaps[i].data_capacity > 0))
             return svo_set_error(SVO_ERR_INVALID, "svo_submit_save: snapshot %d: the host part needs room for its header, the data part its memory", i);
     if (c->failed.load()) return reject_failed(c, "svo_submit_save");
+    const NamedSlots slots{seqs, n};
     for (auto& wp : c->workers) {
         svo_ctx::Worker& w = *wp;
-        svo_ctx::Job job;
-        for (int i = 0; i < n; i++)
-            if (seqs[i] >= w.first && seqs[i] < w.first + w.count) {
-                job.snap.seqs.push_back(seqs[i] - w.first);
-                job.snap.snaps.push_back(snaps[i]);
-            }
-        if (job.snap.seqs.empty()) continue;
-        job.snap.mem = mem;
+        svo_ctx::Save job;
+        slots.each_in(w.first, w.count, [&](int i, int local) { job.seqs.push_back(local); job.snaps.push_back(snaps[i]); });
+        if (job.seqs.empty()) continue;
+        job.mem = mem;
         worker_submit(w, std::move(job));
     }
     return SVO_OK;
@@ -849,16 +769,16 @@ extern "C" int svo_submit_load(svo_ctx* c, const int* seqs, int n, const svo_sna
             return rc;                           // (every group has the same size and capacity; the settings: the slot's rig's)
     }
     if (c->failed.load()) return reject_failed(c, "svo_submit_load");
+    const NamedSlots slots{seqs, n};
     for (auto& wp : c->workers) {
         svo_ctx::Worker& w = *wp;
-        svo_ctx::Job job;
-        for (int i = 0; i < n; i++)
-            if (seqs[i] >= w.first && seqs[i] < w.first + w.count) {
-                loads[i].seq -= w.first;
-                job.snap.loads.push_back(std::move(loads[i]));
-            }
-        if (job.snap.loads.empty()) continue;
-        job.snap.mem = mem;
+        svo_ctx::Load job;
+        slots.each_in(w.first, w.count, [&](int i, int local) {
+            loads[i].seq = local;
+            job.loads.push_back(std::move(loads[i]));
+        });
+        if (job.loads.empty()) continue;
+        job.mem = mem;
         worker_submit(w, std::move(job));
     }
     return SVO_OK;
@@ -873,14 +793,13 @@ extern "C" int svo_submit_pose_updates(svo_ctx* c, const int* seqs, const int* c
                                        float* filtered) {
     if (!c || !counts || (seqs && n < 0)) return svo_set_error(SVO_ERR_INVALID, "svo_submit_pose_updates: bad arguments");
     if (!seqs) n = c->B;
-    std::vector<char> named(c->B, 0);
+    const NamedSlots slots{seqs, n};
+    const int bad = slots.first_bad(c->B, true);
     std::vector<int64_t> first((size_t)n + 1, 0);     // sample offsets of the named slots
-    for (int i = 0; i < n; i++) {
-        const int s = seqs ? seqs[i] : i;
-        if (s < 0 || s >= c->B || named[s])
-            return svo_set_error(SVO_ERR_INVALID, "svo_submit_pose_updates: sequence %d is out of range or named twice", s);
-        named[s] = 1;
-        if (counts[i] < 0) return svo_set_error(SVO_ERR_INVALID, "svo_submit_pose_updates: sequence %d: negative count", s);
+    for (int i = 0; i < n; i++) {                // (a slot's name is checked before its count)
+        if (i == bad)
+            return svo_set_error(SVO_ERR_INVALID, "svo_submit_pose_updates: sequence %d is out of range or named twice", slots.at(i));
+        if (counts[i] < 0) return svo_set_error(SVO_ERR_INVALID, "svo_submit_pose_updates: sequence %d: negative count", slots.at(i));
         first[i + 1] = first[i] + counts[i];
     }
     const int64_t total = first[n];
@@ -892,17 +811,15 @@ extern "C" int svo_submit_pose_updates(svo_ctx* c, const int* seqs, const int* c
     if (c->failed.load()) return reject_failed(c, "svo_submit_pose_updates");
     for (auto& wp : c->workers) {
         svo_ctx::Worker& w = *wp;
-        svo_ctx::Job job;
-        svo_ctx::PoseUpdates& u = job.pose;
-        for (int i = 0; i < n; i++) {
-            const int s = seqs ? seqs[i] : i;
-            if (counts[i] == 0 || s < w.first || s >= w.first + w.count) continue;
-            u.seqs.push_back(s - w.first);
+        svo_ctx::PoseUpdates u;
+        slots.each_in(w.first, w.count, [&](int i, int local) {
+            if (counts[i] == 0) return;
+            u.seqs.push_back(local);
             u.counts.push_back(counts[i]);
             u.samples.insert(u.samples.end(), samples + first[i], samples + first[i + 1]);
             u.filtered.push_back(filtered ? filtered + first[i] * 6 : nullptr);
-        }
-        if (!u.seqs.empty()) worker_submit(w, std::move(job));
+        });
+        if (!u.seqs.empty()) worker_submit(w, std::move(u));
     }
     return SVO_OK;
 }
@@ -1217,8 +1134,10 @@ extern "C" int svo_ctx_remove_rigs(svo_ctx* c, const int* ids, int n) {
 
 extern "C" int svo_ctx_assign_rigs(svo_ctx* c, const int* seqs, const int* rigs, int n) {
     if (!c || n < 0 || (n > 0 && (!seqs || !rigs))) return svo_set_error(SVO_ERR_INVALID, "svo_ctx_assign_rigs: bad arguments");
-    for (int i = 0; i < n; i++) {
-        if (seqs[i] < 0 || seqs[i] >= c->B)
+    const NamedSlots slots{seqs, n};
+    const int bad = slots.first_bad(c->B, false);
+    for (int i = 0; i < n; i++) {                // (a slot's name is checked before its rig)
+        if (i == bad)
             return svo_set_error(SVO_ERR_INVALID, "svo_ctx_assign_rigs: sequence %d out of range", seqs[i]);
         if (!rig_exists(c, rigs[i])) return svo_set_error(SVO_ERR_INVALID, "svo_ctx_assign_rigs: rig %d does not exist", rigs[i]);
     }
@@ -1226,15 +1145,14 @@ extern "C" int svo_ctx_assign_rigs(svo_ctx* c, const int* seqs, const int* rigs,
     const size_t map_bytes = svo::remap_map_bytes(c->width, c->height);
     for (auto& wp : c->workers) {
         svo_ctx::Worker& w = *wp;
-        svo_ctx::Job job;
-        for (int i = 0; i < n; i++) {
-            if (seqs[i] < w.first || seqs[i] >= w.first + w.count) continue;
+        svo_ctx::RigAssign job;
+        slots.each_in(w.first, w.count, [&](int i, int local) {
             const svo_ctx::Rig& r = c->rigs[rigs[i]];
             const uint8_t* base = r.maps.get();
-            job.assign.push_back(seqs[i] - w.first);
+            job.seqs.push_back(local);
             job.bindings.push_back(RigBinding{rigs[i], r.cam, {base, base ? base + map_bytes : nullptr}});
-        }
-        if (!job.assign.empty()) worker_submit(w, std::move(job));
+        });
+        if (!job.seqs.empty()) worker_submit(w, std::move(job));
     }
     for (int i = 0; i < n; i++) c->slot_rig[seqs[i]] = rigs[i];
     return SVO_OK;

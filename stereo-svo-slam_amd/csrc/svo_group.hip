@@ -45,6 +45,37 @@ void dev_release(svo_group* c, void* p, size_t bytes) {
         }
 }
 
+// a plain copy where a slot fills its image_bytes, a short one for a lone slot, else a 2-D one of `used` bytes per slot
+int copy_out_slots(hipStream_t st, uint8_t* to, const uint8_t* from, const int* seg, const char* shown, int n, int64_t image_bytes,
+                   int64_t used) {
+    for (int i = 0; i < n;) {
+        if (!shown[i]) { i++; continue; }
+        int j = i + 1;
+        while (j < n && shown[j] && seg[j] == seg[j - 1] + 1) j++;
+        uint8_t* dst = to + (int64_t)seg[i] * image_bytes;
+        const uint8_t* src = from + (int64_t)i * image_bytes;
+        if (used == image_bytes)
+            HIP_TRY(hipMemcpyAsync(dst, src, (size_t)((j - i) * image_bytes), hipMemcpyDeviceToHost, st));
+        else if (j - i == 1)
+            HIP_TRY(hipMemcpyAsync(dst, src, (size_t)used, hipMemcpyDeviceToHost, st));
+        else
+            HIP_TRY(hipMemcpy2DAsync(dst, (size_t)image_bytes, src, (size_t)image_bytes, (size_t)used, (size_t)(j - i), hipMemcpyDeviceToHost, st));
+        i = j;
+    }
+    return SVO_OK;
+}
+
+int reject_if_failed(const svo_group* c, const char* who) {
+    return c->failed ? svo_set_error(SVO_ERR_INVALID, "%s: an earlier frame of this ctx failed; create a new ctx", who) : SVO_OK;
+}
+
+int job_begin(svo_group* c, const char* who) {
+    if (const int rc = reject_if_failed(c, who)) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    flush_pending(c);
+    return SVO_OK;
+}
+
 // ------------------------------------------------------------------------------------ storage
 
 // Image-set storage comes from slabs allocated in chunks: one hipMalloc (a device-wide
@@ -501,8 +532,7 @@ void trim_keyframes(svo_group* c, Seq& q, int below) {
 }  // namespace svo
 
 int grp_trim_keyframes(svo_group* c, const int* seqs, const int* below, int n) {
-    if (c->failed)
-        return svo_set_error(SVO_ERR_INVALID, "svo_submit_trim_keyframes: an earlier frame of this ctx failed; create a new ctx");
+    if (const int rc = reject_if_failed(c, "svo_submit_trim_keyframes")) return rc;
     for (int i = 0; i < n; i++) trim_keyframes(c, c->seqs[seqs[i]], below[i]);
     return SVO_OK;
 }
@@ -515,15 +545,13 @@ svo_keyframe_range grp_keyframe_range(const svo_group* c, int seq) {
 }
 
 int grp_restart_sequences(svo_group* c, const int* seqs, int n) {
-    if (c->failed)
-        return svo_set_error(SVO_ERR_INVALID, "svo_ctx_restart_sequences: an earlier frame of this ctx failed; create a new ctx");
+    if (const int rc = reject_if_failed(c, "svo_ctx_restart_sequences")) return rc;
     for (int i = 0; i < n; i++) end_sequence(c, seqs[i]);
     return SVO_OK;
 }
 
 int grp_assign_rigs(svo_group* c, const int* seqs, const RigBinding* b, int n) {
-    if (c->failed)
-        return svo_set_error(SVO_ERR_INVALID, "svo_ctx_assign_rigs: an earlier frame of this ctx failed; create a new ctx");
+    if (const int rc = reject_if_failed(c, "svo_ctx_assign_rigs")) return rc;
     for (int i = 0; i < n; i++) {
         end_sequence(c, seqs[i]);
         Seq& q = c->seqs[seqs[i]];

@@ -14,31 +14,6 @@ using namespace svo;
 
 namespace {
 
-// the input block (device and its pinned mirror) holds `bytes`; a grown one replaces the old
-int reserve_ar_in(svo_group* c, size_t bytes) {
-    if (bytes <= c->ar_in_bytes) return SVO_OK;
-    HIP_TRY(hipStreamSynchronize(c->stream.get()));
-    bytes = align_up(bytes, 4096);
-    if (c->d_ar_in) dev_release(c, c->d_ar_in, c->ar_in_bytes);
-    c->d_ar_in = nullptr; c->ar_in_bytes = 0;
-    c->ar_in_host.reset();
-    HIP_TRY(pinned_malloc(c->ar_in_host, bytes));
-    if (const int rc = dev_alloc(c, &c->d_ar_in, bytes, false)) return rc;
-    c->ar_in_bytes = bytes;
-    return SVO_OK;
-}
-
-// *block (of *have bytes) holds `bytes`: the screen records, or the host-mode staging block
-int reserve_ar_block(svo_group* c, uint8_t** block, size_t* have, size_t bytes) {
-    if (bytes <= *have) return SVO_OK;
-    HIP_TRY(hipStreamSynchronize(c->stream.get()));
-    if (*block) dev_release(c, *block, *have);
-    *block = nullptr; *have = 0;
-    if (const int rc = dev_alloc(c, block, bytes, false)) return rc;
-    *have = bytes;
-    return SVO_OK;
-}
-
 size_t pad16(size_t b) { return (b + 15) / 16 * 16; }
 
 }  // namespace
@@ -80,10 +55,7 @@ int64_t grp_ar_bytes(const svo_group* c, const svo_ar_style* style) {
 // (group_tile_table), one launch unless it outgrows them.
 int grp_export_ar(svo_group* c, int mem, const int* seqs, const int* seg, const int* inst0, const int* inst1, int n, int seq0,
                   const ArJob* job, const svo_ar_dst* dst) {
-    if (c->failed)
-        return svo_set_error(SVO_ERR_INVALID, "svo_submit_export_ar: an earlier frame of this ctx failed; create a new ctx");
-    HIP_TRY(hipSetDevice(c->device));
-    flush_pending(c);
+    if (const int rc = job_begin(c, "svo_submit_export_ar")) return rc;
     hipStream_t st = c->stream.get();
     const bool host = mem == SVO_MEM_HOST;
     const int cols = c->width, rows = c->height;
@@ -136,15 +108,15 @@ int grp_export_ar(svo_group* c, int mem, const int* seqs, const int* seg, const 
     }
     if (!images.empty()) {
         if (host)
-            if (const int rc = reserve_ar_block(c, &c->d_ar, &c->ar_bytes, (size_t)n * (size_t)image_bytes)) return rc;
-        if (const int rc = reserve_ar_block(c, &c->d_ar_rec, &c->ar_rec_bytes, sizeof(ArRecord) * records)) return rc;
+            if (const int rc = c->d_ar.reserve(c, (size_t)n * (size_t)image_bytes)) return rc;
+        if (const int rc = c->d_ar_rec.reserve(c, sizeof(ArRecord) * records)) return rc;
         // the input block: vertices | triangles | colours | draws | images | work list
         const size_t v_bytes = pad16(sizeof(float) * job->vertices.size()), t_bytes = pad16(sizeof(int32_t) * job->triangles.size());
         const size_t c_bytes = pad16(sizeof(uint32_t) * job->rgb.size()), d_bytes = pad16(sizeof(svo_ar_draw) * draws.size());
         const size_t i_bytes = pad16(sizeof(ArImage) * images.size()), s_bytes = sizeof(ArSetup) * setup.size();
         const size_t in_bytes = v_bytes + t_bytes + c_bytes + d_bytes + i_bytes + s_bytes;
-        if (const int rc = reserve_ar_in(c, in_bytes)) return rc;
-        uint8_t* dev = c->d_ar_in;
+        if (const int rc = c->d_ar_in.reserve(c, align_up(in_bytes, 4096))) return rc;
+        uint8_t* dev = c->d_ar_in.p;
         const float* d_vertices = reinterpret_cast<const float*>(dev);
         const int32_t* d_triangles = reinterpret_cast<const int32_t*>(dev + v_bytes);
         const uint32_t* d_rgb = reinterpret_cast<const uint32_t*>(dev + v_bytes + t_bytes);
@@ -159,11 +131,11 @@ int grp_export_ar(svo_group* c, int mem, const int* seqs, const int* seg, const 
         }
         for (size_t k = 0; k < placed.size(); k++) {
             const Placed& pl = placed[k];
-            images[k].dst = host ? c->d_ar + (int64_t)pl.i * image_bytes : dst->pixels + (int64_t)seg[pl.i] * image_bytes;
+            images[k].dst = host ? c->d_ar.p + (int64_t)pl.i * image_bytes : dst->pixels + (int64_t)seg[pl.i] * image_bytes;
             images[k].draws = d_draws + pl.draw0;
-            images[k].records = reinterpret_cast<ArRecord*>(c->d_ar_rec) + pl.rec0;
+            images[k].records = reinterpret_cast<ArRecord*>(c->d_ar_rec.p) + pl.rec0;
         }
-        uint8_t* h = c->ar_in_host.get();
+        uint8_t* h = c->d_ar_in.host.get();
         auto put = [&](size_t at, const void* from, size_t b) { if (b) std::memcpy(h + at, from, b); };
         put(0, job->vertices.data(), sizeof(float) * job->vertices.size());
         put(v_bytes, job->triangles.data(), sizeof(int32_t) * job->triangles.size());
@@ -183,20 +155,8 @@ int grp_export_ar(svo_group* c, int mem, const int* seqs, const int* seg, const 
             if (const int rc = table.add(t)) return rc;
         if (const int rc = table.launch(false)) return rc;
     }
-    for (int i = 0; host && i < n;) {
-        if (!shown[i]) { i++; continue; }
-        int j = i + 1;
-        while (j < n && shown[j] && seg[j] == seg[j - 1] + 1) j++;
-        uint8_t* to = dst->pixels + (int64_t)seg[i] * image_bytes;
-        const uint8_t* from = c->d_ar + (int64_t)i * image_bytes;
-        if (used == image_bytes)
-            HIP_TRY(hipMemcpyAsync(to, from, (size_t)((j - i) * image_bytes), hipMemcpyDeviceToHost, st));
-        else if (j - i == 1)
-            HIP_TRY(hipMemcpyAsync(to, from, (size_t)used, hipMemcpyDeviceToHost, st));
-        else
-            HIP_TRY(hipMemcpy2DAsync(to, (size_t)image_bytes, from, (size_t)image_bytes, (size_t)used, (size_t)(j - i), hipMemcpyDeviceToHost, st));
-        i = j;
-    }
+    if (host)
+        if (const int rc = copy_out_slots(st, dst->pixels, c->d_ar.p, seg, shown.data(), n, image_bytes, used)) return rc;
     HIP_TRY(hipStreamSynchronize(st));       // delivered: svo_wait means that
     return SVO_OK;
 }

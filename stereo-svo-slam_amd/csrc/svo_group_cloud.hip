@@ -33,13 +33,7 @@ int reserve_cloud(svo_group* c, size_t bytes, size_t slots) {
         HIP_TRY(pinned_malloc(c->cloud_counts_host, sizeof(int) * slots));
         c->cloud_counts_cap = slots;
     }
-    if (bytes <= c->cloud_bytes) return SVO_OK;
-    HIP_TRY(hipStreamSynchronize(c->stream.get()));
-    if (c->d_cloud) dev_release(c, c->d_cloud, c->cloud_bytes);
-    c->d_cloud = nullptr; c->cloud_bytes = 0;
-    if (const int rc = dev_alloc(c, &c->d_cloud, bytes, false)) return rc;
-    c->cloud_bytes = bytes;
-    return SVO_OK;
+    return c->d_cloud.reserve(c, bytes);
 }
 
 // the style is checked and the ctx's size has a lattice point at its step
@@ -84,10 +78,7 @@ int64_t grp_cloud_points(const svo_group* c, const svo_cloud_style* style) {
 // are consecutive in both (organized). The two image tables share the group's argument blocks, half each.
 int grp_export_cloud(svo_group* c, int what, int mem, const int* seqs, const int* seg, int n, int seq0, const svo_cloud_style* style,
                      const svo_cloud_dst* dst) {
-    if (c->failed)
-        return svo_set_error(SVO_ERR_INVALID, "svo_submit_export_cloud: an earlier frame of this ctx failed; create a new ctx");
-    HIP_TRY(hipSetDevice(c->device));
-    flush_pending(c);
+    if (const int rc = job_begin(c, "svo_submit_export_cloud")) return rc;
     hipStream_t st = c->stream.get();
     const bool host = mem == SVO_MEM_HOST;
     DenseParams search;
@@ -100,10 +91,10 @@ int grp_export_cloud(svo_group* c, int what, int mem, const int* seqs, const int
     const size_t m_max = std::min<size_t>((size_t)n, chunk);
     const Staging sg((size_t)points, host, m_max);
     if (const int rc = reserve_cloud(c, sg.total, m_max)) return rc;
-    uint8_t* const d_planes = c->d_cloud;
+    uint8_t* const d_planes = c->d_cloud.p;
     uint8_t* const d_counts = d_planes + m_max * sg.planes;
     uint8_t* const d_records = d_counts + m_max * sg.counts;
-    int* const d_kept = reinterpret_cast<int*>(c->d_cloud + m_max * sg.slot);
+    int* const d_kept = reinterpret_cast<int*>(c->d_cloud.p + m_max * sg.slot);
     int* const kept = c->cloud_counts_host.get();
     const int cloud_grid = cloud_tiles(points);
     for (int i0 = 0; i0 < n; i0 += (int)m_max) {

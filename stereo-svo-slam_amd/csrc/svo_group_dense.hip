@@ -13,17 +13,6 @@ using namespace svo;
 
 namespace {
 
-// the host-mode staging block holds `bytes`
-int reserve_dense(svo_group* c, size_t bytes) {
-    if (bytes <= c->dense_bytes) return SVO_OK;
-    HIP_TRY(hipStreamSynchronize(c->stream.get()));
-    if (c->d_dense) dev_release(c, c->d_dense, c->dense_bytes);
-    c->d_dense = nullptr; c->dense_bytes = 0;
-    if (const int rc = dev_alloc(c, &c->d_dense, bytes, false)) return rc;
-    c->dense_bytes = bytes;
-    return SVO_OK;
-}
-
 // the style is checked and the ctx's size has a lattice point at its step
 int check_style(const svo_camera_settings* cam, int width, int height, const svo_disparity_style* style, const char* who, DenseParams* out) {
     DenseParams p;
@@ -64,10 +53,7 @@ int64_t grp_disparity_bytes(const svo_group* c, const svo_disparity_style* style
 // group's argument blocks, one launch unless it outgrows them.
 int grp_export_disparity(svo_group* c, int what, int mem, const int* seqs, const int* seg, int n, int seq0,
                          const svo_disparity_style* style, const svo_disparity_dst* dst) {
-    if (c->failed)
-        return svo_set_error(SVO_ERR_INVALID, "svo_submit_export_disparity: an earlier frame of this ctx failed; create a new ctx");
-    HIP_TRY(hipSetDevice(c->device));
-    flush_pending(c);
+    if (const int rc = job_begin(c, "svo_submit_export_disparity")) return rc;
     hipStream_t st = c->stream.get();
     const bool host = mem == SVO_MEM_HOST;
     DenseParams params;
@@ -77,7 +63,7 @@ int grp_export_disparity(svo_group* c, int what, int mem, const int* seqs, const
     const int64_t used = (int64_t)planes * cols * rows * 4;   // bytes of a slot's planes
     int tiles = dense_tiles(params, c->width, c->height);
     if (host)
-        if (const int rc = reserve_dense(c, (size_t)n * (size_t)image_bytes)) return rc;
+        if (const int rc = c->d_dense.reserve(c, (size_t)n * (size_t)image_bytes)) return rc;
     // (SVO_DENSE_TABLE_IMAGES: a smaller table, so that tests reach the chunked launches)
     auto table = group_tile_table<DenseImage>(c, "SVO_DENSE_TABLE_IMAGES",
                                               [&](const DenseImage* d, int m, hipStream_t s) { launch_dense(d, m, tiles, params, s); });
@@ -107,7 +93,7 @@ int grp_export_disparity(svo_group* c, int what, int mem, const int* seqs, const
                                  c->width, c->height);
         e.status = SVO_DISPARITY_OK;
         shown[i] = 1;
-        uint8_t* out = host ? c->d_dense + (int64_t)i * image_bytes : reinterpret_cast<uint8_t*>(dst->values) + e.offset;
+        uint8_t* out = host ? c->d_dense.p + (int64_t)i * image_bytes : reinterpret_cast<uint8_t*>(dst->values) + e.offset;
         if (const int rc = table.add(DenseImage{l.data, r.data, reinterpret_cast<float*>(out), l.stride, r.stride, l.w, l.h, q.cam.baseline, 0}))
             return rc;
     }
@@ -116,20 +102,8 @@ int grp_export_disparity(svo_group* c, int what, int mem, const int* seqs, const
         tiles = dense_tiles(params, c->width, c->height);
     }
     if (const int rc = table.launch(false)) return rc;
-    for (int i = 0; host && i < n;) {
-        if (!shown[i]) { i++; continue; }
-        int j = i + 1;
-        while (j < n && shown[j] && seg[j] == seg[j - 1] + 1) j++;
-        uint8_t* to = reinterpret_cast<uint8_t*>(dst->values) + (int64_t)seg[i] * image_bytes;
-        const uint8_t* from = c->d_dense + (int64_t)i * image_bytes;
-        if (used == image_bytes)
-            HIP_TRY(hipMemcpyAsync(to, from, (size_t)((j - i) * image_bytes), hipMemcpyDeviceToHost, st));
-        else if (j - i == 1)
-            HIP_TRY(hipMemcpyAsync(to, from, (size_t)used, hipMemcpyDeviceToHost, st));
-        else
-            HIP_TRY(hipMemcpy2DAsync(to, (size_t)image_bytes, from, (size_t)image_bytes, (size_t)used, (size_t)(j - i), hipMemcpyDeviceToHost, st));
-        i = j;
-    }
+    if (host)
+        if (const int rc = copy_out_slots(st, reinterpret_cast<uint8_t*>(dst->values), c->d_dense.p, seg, shown.data(), n, image_bytes, used)) return rc;
     HIP_TRY(hipStreamSynchronize(st));       // delivered: svo_wait means that
     return SVO_OK;
 }

@@ -10,35 +10,6 @@
 
 using namespace svo;
 
-namespace {
-
-// the counts block (device and its pinned mirror) holds `ints`; a grown one replaces the old
-int reserve_map_counts(svo_group* c, size_t ints) {
-    if (ints <= c->map_counts) return SVO_OK;
-    HIP_TRY(hipStreamSynchronize(c->stream.get()));
-    ints = align_up(ints, 1024);
-    if (c->d_map_counts) dev_release(c, c->d_map_counts, sizeof(int) * c->map_counts);
-    c->d_map_counts = nullptr; c->map_counts = 0;
-    c->map_counts_host.reset();
-    HIP_TRY(pinned_malloc(c->map_counts_host, sizeof(int) * ints));
-    if (const int rc = dev_alloc(c, &c->d_map_counts, ints, false)) return rc;
-    c->map_counts = ints;
-    return SVO_OK;
-}
-
-// the host-mode staging block holds `points`
-int reserve_map_points(svo_group* c, size_t points) {
-    if (points <= c->map_points) return SVO_OK;
-    HIP_TRY(hipStreamSynchronize(c->stream.get()));
-    if (c->d_map_points) dev_release(c, c->d_map_points, sizeof(svo_map_point) * c->map_points);
-    c->d_map_points = nullptr; c->map_points = 0;
-    if (const int rc = dev_alloc(c, &c->d_map_points, points, false)) return rc;
-    c->map_points = points;
-    return SVO_OK;
-}
-
-}  // namespace
-
 // (a trimmed slot: from its first resident keyframe on, if that is later; *from receives the effective start)
 void grp_map_size(const svo_group* c, int seq, int from_keyframe, int* keyframes, int64_t* points_bound, int* from) {
     const Seq& q = c->seqs[seq];
@@ -57,10 +28,7 @@ void grp_map_size(const svo_group* c, int seq, int from_keyframe, int* keyframes
 // the staging block.
 int grp_export_map(svo_group* c, int mem, const int* seqs, const int* seg, const svo_map_region* regions, int n, int seq0,
                    const svo_map_filter* filter, const svo_map_dst* dst) {
-    if (c->failed)
-        return svo_set_error(SVO_ERR_INVALID, "svo_submit_export_map: an earlier frame of this ctx failed; create a new ctx");
-    HIP_TRY(hipSetDevice(c->device));
-    flush_pending(c);
+    if (const int rc = job_begin(c, "svo_submit_export_map")) return rc;
     hipStream_t st = c->stream.get();
     const bool host = mem == SVO_MEM_HOST;
     struct Placed { int i, set0; int64_t stage; };   // a delivered slot: its first set and its first record of the staging block
@@ -88,11 +56,11 @@ int grp_export_map(svo_group* c, int mem, const int* seqs, const int* seg, const
     }
     const int* kept = nullptr;               // per exported keyframe (set)
     if (!tiles.empty()) {
-        if (const int rc = reserve_map_counts(c, (size_t)sets + tiles.size())) return rc;
+        if (const int rc = c->d_map_counts.reserve(c, sizeof(int) * align_up((size_t)sets + tiles.size(), 1024))) return rc;
         if (host && staged > 0)
-            if (const int rc = reserve_map_points(c, (size_t)staged)) return rc;
-        svo_map_point* out = host ? c->d_map_points : dst->points;
-        int* set_counts = c->d_map_counts;
+            if (const int rc = c->d_map_points.reserve(c, sizeof(svo_map_point) * (size_t)staged)) return rc;
+        svo_map_point* out = host ? c->d_map_points.p : dst->points;
+        int* set_counts = c->d_map_counts.p;
         int* tile_counts = set_counts + sets;
         // (SVO_MAP_TABLE_TILES: a smaller table, so that tests reach the chunked launches)
         auto table = group_tile_table<MapTile>(c, "SVO_MAP_TABLE_TILES", [&](const MapTile* d, int m, hipStream_t s) {
@@ -101,8 +69,8 @@ int grp_export_map(svo_group* c, int mem, const int* seqs, const int* seg, const
         for (const MapTile& t : tiles)
             if (const int rc = table.add(t)) return rc;
         if (const int rc = table.launch(false)) return rc;
-        kept = c->map_counts_host.get();
-        HIP_TRY(hipMemcpyAsync(c->map_counts_host.get(), set_counts, sizeof(int) * (size_t)sets, hipMemcpyDeviceToHost, st));
+        kept = c->d_map_counts.host.get();
+        HIP_TRY(hipMemcpyAsync(c->d_map_counts.host.get(), set_counts, sizeof(int) * (size_t)sets, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
     }
     for (const Placed& p : placed) {
@@ -120,7 +88,7 @@ int grp_export_map(svo_group* c, int mem, const int* seqs, const int* seg, const
         }
         e.n_points = at;
         if (host && at > 0)
-            HIP_TRY(hipMemcpyAsync(dst->points + r.first_point, c->d_map_points + p.stage, sizeof(svo_map_point) * (size_t)at,
+            HIP_TRY(hipMemcpyAsync(dst->points + r.first_point, c->d_map_points.p + p.stage, sizeof(svo_map_point) * (size_t)at,
                                    hipMemcpyDeviceToHost, st));
     }
     HIP_TRY(hipStreamSynchronize(st));       // delivered: svo_wait means that

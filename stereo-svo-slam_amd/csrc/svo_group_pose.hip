@@ -63,8 +63,7 @@ bool has_ctor_pattern(const PoseFilter& kf) {
 // launch, one download; delivered on return.
 int grp_pose_updates(svo_group* c, const int* seqs, const int* counts, int n, const svo_pose_sample* samples,
                      float* const* filtered) {
-    if (c->failed)
-        return svo_set_error(SVO_ERR_INVALID, "svo_submit_pose_updates: an earlier frame of this ctx failed; create a new ctx");
+    if (const int rc = reject_if_failed(c, "svo_submit_pose_updates")) return rc;
     if (n <= 0) return SVO_OK;
     HIP_TRY(hipSetDevice(c->device));
     flush_pending(c);

@@ -14,31 +14,6 @@ using namespace svo;
 
 namespace {
 
-// the input block (device and its pinned mirror) holds `bytes`; a grown one replaces the old
-int reserve_scene_in(svo_group* c, size_t bytes) {
-    if (bytes <= c->scene_in_bytes) return SVO_OK;
-    HIP_TRY(hipStreamSynchronize(c->stream.get()));
-    bytes = align_up(bytes, 4096);
-    if (c->d_scene_in) dev_release(c, c->d_scene_in, c->scene_in_bytes);
-    c->d_scene_in = nullptr; c->scene_in_bytes = 0;
-    c->scene_in_host.reset();
-    HIP_TRY(pinned_malloc(c->scene_in_host, bytes));
-    if (const int rc = dev_alloc(c, &c->d_scene_in, bytes, false)) return rc;
-    c->scene_in_bytes = bytes;
-    return SVO_OK;
-}
-
-// the host-mode staging block holds `bytes`
-int reserve_scene(svo_group* c, size_t bytes) {
-    if (bytes <= c->scene_bytes) return SVO_OK;
-    HIP_TRY(hipStreamSynchronize(c->stream.get()));
-    if (c->d_scene) dev_release(c, c->d_scene, c->scene_bytes);
-    c->d_scene = nullptr; c->scene_bytes = 0;
-    if (const int rc = dev_alloc(c, &c->d_scene, bytes, false)) return rc;
-    c->scene_bytes = bytes;
-    return SVO_OK;
-}
-
 bool finite3(const float v[3]) { return std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]); }
 
 void cross(const double a[3], const double b[3], double o[3]) {
@@ -141,10 +116,7 @@ int64_t grp_scene_bytes(const svo_scene_style* style) {
 // outgrows them.
 int grp_export_scenes(svo_group* c, int mem, const int* seqs, const int* seg, int n, int seq0, const svo_scene_style* style,
                       const svo_scene_camera* cameras, const svo_scene_dst* dst) {
-    if (c->failed)
-        return svo_set_error(SVO_ERR_INVALID, "svo_submit_export_scenes: an earlier frame of this ctx failed; create a new ctx");
-    HIP_TRY(hipSetDevice(c->device));
-    flush_pending(c);
+    if (const int rc = job_begin(c, "svo_submit_export_scenes")) return rc;
     hipStream_t st = c->stream.get();
     const bool host = mem == SVO_MEM_HOST;
     const int cols = style->cols, rows = style->rows;
@@ -202,25 +174,25 @@ int grp_export_scenes(svo_group* c, int mem, const int* seqs, const int* seg, in
     }
     if (!images.empty()) {
         if (host)
-            if (const int rc = reserve_scene(c, (size_t)n * (size_t)image_bytes)) return rc;
+            if (const int rc = c->d_scene.reserve(c, (size_t)n * (size_t)image_bytes)) return rc;
         // the input block: lines | sets | images
         const size_t lines_bytes = sizeof(svo_scene_line) * lines.size(), sets_bytes = sizeof(SceneSet) * sets.size();
         const size_t in_bytes = lines_bytes + sets_bytes + sizeof(SceneImage) * images.size();
-        if (const int rc = reserve_scene_in(c, in_bytes)) return rc;
-        const svo_scene_line* d_lines = reinterpret_cast<const svo_scene_line*>(c->d_scene_in);
-        const SceneSet* d_sets = reinterpret_cast<const SceneSet*>(c->d_scene_in + lines_bytes);
-        const SceneImage* d_images = reinterpret_cast<const SceneImage*>(c->d_scene_in + lines_bytes + sets_bytes);
+        if (const int rc = c->d_scene_in.reserve(c, align_up(in_bytes, 4096))) return rc;
+        const svo_scene_line* d_lines = reinterpret_cast<const svo_scene_line*>(c->d_scene_in.p);
+        const SceneSet* d_sets = reinterpret_cast<const SceneSet*>(c->d_scene_in.p + lines_bytes);
+        const SceneImage* d_images = reinterpret_cast<const SceneImage*>(c->d_scene_in.p + lines_bytes + sets_bytes);
         for (size_t k = 0; k < placed.size(); k++) {
             const Placed& pl = placed[k];
-            images[k].dst = host ? c->d_scene + (int64_t)pl.i * image_bytes : dst->pixels + (int64_t)seg[pl.i] * image_bytes;
+            images[k].dst = host ? c->d_scene.p + (int64_t)pl.i * image_bytes : dst->pixels + (int64_t)seg[pl.i] * image_bytes;
             images[k].sets = d_sets + pl.set0;
             images[k].lines = d_lines + pl.line0;
         }
-        uint8_t* h = c->scene_in_host.get();
+        uint8_t* h = c->d_scene_in.host.get();
         if (lines_bytes) std::memcpy(h, lines.data(), lines_bytes);
         if (sets_bytes) std::memcpy(h + lines_bytes, sets.data(), sets_bytes);
         std::memcpy(h + lines_bytes + sets_bytes, images.data(), sizeof(SceneImage) * images.size());
-        HIP_TRY(hipMemcpyAsync(c->d_scene_in, h, in_bytes, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(c->d_scene_in.p, h, in_bytes, hipMemcpyHostToDevice, st));
         const SceneParams params = scene_params(*style);
         // (SVO_SCENE_TABLE_TILES: a smaller table, so that tests reach the chunked launches)
         auto table = group_tile_table<SceneTile>(c, "SVO_SCENE_TABLE_TILES", [&](const SceneTile* d, int m, hipStream_t s) {
@@ -230,20 +202,8 @@ int grp_export_scenes(svo_group* c, int mem, const int* seqs, const int* seg, in
             if (const int rc = table.add(t)) return rc;
         if (const int rc = table.launch(false)) return rc;
     }
-    for (int i = 0; host && i < n;) {
-        if (!shown[i]) { i++; continue; }
-        int j = i + 1;
-        while (j < n && shown[j] && seg[j] == seg[j - 1] + 1) j++;
-        uint8_t* to = dst->pixels + (int64_t)seg[i] * image_bytes;
-        const uint8_t* from = c->d_scene + (int64_t)i * image_bytes;
-        if (used == image_bytes)
-            HIP_TRY(hipMemcpyAsync(to, from, (size_t)((j - i) * image_bytes), hipMemcpyDeviceToHost, st));
-        else if (j - i == 1)
-            HIP_TRY(hipMemcpyAsync(to, from, (size_t)used, hipMemcpyDeviceToHost, st));
-        else
-            HIP_TRY(hipMemcpy2DAsync(to, (size_t)image_bytes, from, (size_t)image_bytes, (size_t)used, (size_t)(j - i), hipMemcpyDeviceToHost, st));
-        i = j;
-    }
+    if (host)
+        if (const int rc = copy_out_slots(st, dst->pixels, c->d_scene.p, seg, shown.data(), n, image_bytes, used)) return rc;
     HIP_TRY(hipStreamSynchronize(st));       // delivered: svo_wait means that
     return SVO_OK;
 }

@@ -221,17 +221,6 @@ struct PlaneTable {
     }
 };
 
-// the host-mode staging block holds `bytes`
-int reserve_snap_stage(svo_group* c, size_t bytes) {
-    if (bytes <= c->snap_bytes) return SVO_OK;
-    HIP_TRY(hipStreamSynchronize(c->stream.get()));
-    if (c->d_snap) dev_release(c, c->d_snap, c->snap_bytes);
-    c->d_snap = nullptr; c->snap_bytes = 0;
-    if (const int rc = dev_alloc(c, &c->d_snap, bytes, false)) return rc;
-    c->snap_bytes = bytes;
-    return SVO_OK;
-}
-
 }  // namespace
 
 int grp_snapshot_size(svo_group* c, int s, int64_t* host_bytes, int64_t* data_bytes) {
@@ -259,8 +248,7 @@ int grp_check_snapshot(const svo_group* c, const svo_camera_settings* slot_cam, 
 
 // One group's share of svo_submit_save, between two steps of the group: slot seqs[i] into snaps[i].
 int grp_save(svo_group* c, const int* seqs, int n, const svo_snapshot* snaps, int mem) {
-    if (c->failed)
-        return svo_set_error(SVO_ERR_INVALID, "svo_submit_save: an earlier frame of this ctx failed; create a new ctx");
+    if (const int rc = reject_if_failed(c, "svo_submit_save")) return rc;
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t st = c->stream.get();
     const bool host = mem == SVO_MEM_HOST;
@@ -294,15 +282,15 @@ int grp_save(svo_group* c, const int* seqs, int n, const svo_snapshot* snaps, in
         stage += align_up((size_t)p.h.data_bytes, 256);
     }
     if (host && stage > 0) {
-        if (const int rc = reserve_snap_stage(c, stage)) return rc;
-        HIP_TRY(hipMemsetAsync(c->d_snap, 0, stage, st));     // (the bytes between planes: a host-mode snapshot is all defined)
+        if (const int rc = c->d_snap.reserve(c, stage)) return rc;
+        HIP_TRY(hipMemsetAsync(c->d_snap.p, 0, stage, st));     // (the bytes between planes: a host-mode snapshot is all defined)
     }
     PlaneTable table(c);
     for (int i = 0; i < n; i++) {
         const SavePlan& p = plans[i];
         if (p.h.status != SVO_SNAPSHOT_COMPLETE) continue;
         const Seq& q = c->seqs[seqs[i]];
-        uint8_t* base = host ? c->d_snap + stage_off[i] : static_cast<uint8_t*>(snaps[i].data);
+        uint8_t* base = host ? c->d_snap.p + stage_off[i] : static_cast<uint8_t*>(snaps[i].data);
         const std::vector<DevPlane> dev = device_planes(c, q, p.sets);
         for (size_t j = 0; j < dev.size(); j++) {
             const svo_snapshot_plane& e = p.dir[j];
@@ -313,7 +301,7 @@ int grp_save(svo_group* c, const int* seqs, int n, const svo_snapshot* snaps, in
     if (host)
         for (int i = 0; i < n; i++)
             if (plans[i].h.status == SVO_SNAPSHOT_COMPLETE && plans[i].h.data_bytes > 0)
-                HIP_TRY(hipMemcpyAsync(snaps[i].data, c->d_snap + stage_off[i], (size_t)plans[i].h.data_bytes, hipMemcpyDeviceToHost, st));
+                HIP_TRY(hipMemcpyAsync(snaps[i].data, c->d_snap.p + stage_off[i], (size_t)plans[i].h.data_bytes, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));       // delivered: svo_wait means that
     return SVO_OK;
 }
@@ -321,8 +309,7 @@ int grp_save(svo_group* c, const int* seqs, int n, const svo_snapshot* snaps, in
 // One group's share of svo_submit_load, between two steps of the group. The host parts are checked copies
 // (grp_check_snapshot); the data parts are trusted.
 int grp_load(svo_group* c, const SnapshotLoad* loads, int n, int mem) {
-    if (c->failed)
-        return svo_set_error(SVO_ERR_INVALID, "svo_submit_load: an earlier frame of this ctx failed; create a new ctx");
+    if (const int rc = reject_if_failed(c, "svo_submit_load")) return rc;
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t st = c->stream.get();
     const bool host = mem == SVO_MEM_HOST;
@@ -333,7 +320,7 @@ int grp_load(svo_group* c, const SnapshotLoad* loads, int n, int mem) {
         stage += align_up((size_t)reinterpret_cast<const SnapHeader*>(loads[i].host.data())->data_bytes, 256);
     }
     if (host && stage > 0)
-        if (const int rc = reserve_snap_stage(c, stage)) return rc;
+        if (const int rc = c->d_snap.reserve(c, stage)) return rc;
     PlaneTable table(c);
     std::vector<std::vector<KfDev>> records((size_t)n);      // (read by their uploads until the stream is idle)
     for (int i = 0; i < n; i++) {
@@ -399,8 +386,8 @@ int grp_load(svo_group* c, const SnapshotLoad* loads, int n, int mem) {
         // the data part -> device
         const uint8_t* base = static_cast<const uint8_t*>(loads[i].data);
         if (host && h.data_bytes > 0) {
-            HIP_TRY(hipMemcpyAsync(c->d_snap + stage_off[i], loads[i].data, (size_t)h.data_bytes, hipMemcpyHostToDevice, st));
-            base = c->d_snap + stage_off[i];
+            HIP_TRY(hipMemcpyAsync(c->d_snap.p + stage_off[i], loads[i].data, (size_t)h.data_bytes, hipMemcpyHostToDevice, st));
+            base = c->d_snap.p + stage_off[i];
         }
         const std::vector<DevPlane> dev = device_planes(c, q, sets);
         for (size_t j = 0; j < dev.size(); j++) {

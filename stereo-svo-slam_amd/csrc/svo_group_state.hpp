@@ -275,6 +275,16 @@ struct ArgBlocks {
     size_t frame_bytes = 0, frame_rig_bytes = 0, bytes = 0;
 };
 
+// A device block of the group that is made by the first job that needs it and replaced when outgrown: `bytes` is
+// what dev_alloc booked and what dev_release gives back. Mirror: a pinned block of the same size goes with it.
+template <typename T, bool Mirror = false>
+struct GrowBlock {
+    T* p = nullptr;
+    size_t bytes = 0;
+    PinnedPtr<T> host;               // (Mirror only)
+    int reserve(svo_group* c, size_t want);   // the block holds `want` bytes; a grown one replaces the old
+};
+
 }  // namespace svo
 
 struct svo_group {
@@ -315,36 +325,33 @@ struct svo_group {
     uint8_t* d_export = nullptr;
     // snapshots (grp_save / grp_load) in host mode: the data parts of one call, made by the first such call and
     // replaced when outgrown
-    uint8_t* d_snap = nullptr; size_t snap_bytes = 0;
-    // map export (grp_export_map): the kept counts of one job (map_counts ints: per exported keyframe, then per tile)
-    // and the pinned mirror that its per-keyframe part comes back into, made by the group's first map export; in host
-    // mode the staging block of map_points points, made by the first host-mode one. Replaced when outgrown.
-    int* d_map_counts = nullptr; size_t map_counts = 0;
-    svo::PinnedPtr<int> map_counts_host;
-    svo_map_point* d_map_points = nullptr; size_t map_points = 0;
+    svo::GrowBlock<uint8_t> d_snap;
+    // map export (grp_export_map): the kept counts of one job (per exported keyframe, then per tile) and the pinned
+    // mirror that its per-keyframe part comes back into, made by the group's first map export; in host mode the
+    // staging block of points, made by the first host-mode one. Replaced when outgrown.
+    svo::GrowBlock<int, true> d_map_counts;
+    svo::GrowBlock<svo_map_point> d_map_points;
     // views (grp_export_views) in host mode: the images of one job, made by the first such job and replaced when
     // outgrown
-    uint8_t* d_view = nullptr; size_t view_bytes = 0;
+    svo::GrowBlock<uint8_t> d_view;
     // scenes (grp_export_scenes): the input block of one job (lines | keyframe sets | image records) and its pinned
     // mirror, made by the group's first scene job; in host mode the images of one job, made by the first host-mode
     // one. Replaced when outgrown.
-    uint8_t* d_scene_in = nullptr; size_t scene_in_bytes = 0;
-    svo::PinnedPtr<uint8_t> scene_in_host;
-    uint8_t* d_scene = nullptr; size_t scene_bytes = 0;
+    svo::GrowBlock<uint8_t, true> d_scene_in;
+    svo::GrowBlock<uint8_t> d_scene;
     // ar pictures (grp_export_ar): the input block of one job (meshes | draws | image records | work list) and its
     // pinned mirror and the screen records of one job, made by the group's first ar job; in host mode the images of
     // one job, made by the first host-mode one. Replaced when outgrown.
-    uint8_t* d_ar_in = nullptr; size_t ar_in_bytes = 0;
-    svo::PinnedPtr<uint8_t> ar_in_host;
-    uint8_t* d_ar_rec = nullptr; size_t ar_rec_bytes = 0;
-    uint8_t* d_ar = nullptr; size_t ar_bytes = 0;
+    svo::GrowBlock<uint8_t, true> d_ar_in;
+    svo::GrowBlock<uint8_t> d_ar_rec;
+    svo::GrowBlock<uint8_t> d_ar;
     // disparity maps (grp_export_disparity) in host mode: the planes of one job, made by the first such job and
     // replaced when outgrown
-    uint8_t* d_dense = nullptr; size_t dense_bytes = 0;
+    svo::GrowBlock<uint8_t> d_dense;
     // point clouds (grp_export_cloud): the staging block of one chunk of a job (planes | tile counts and pose matrices |
     // in host mode records | kept counts) and the pinned mirror of the kept counts, made by the first such job and
     // replaced when outgrown
-    uint8_t* d_cloud = nullptr; size_t cloud_bytes = 0;
+    svo::GrowBlock<uint8_t> d_cloud;
     svo::PinnedPtr<int> cloud_counts_host; size_t cloud_counts_cap = 0;
     // batched pose-filter updates (grp_pose_updates): the upload block (samples | filter states | start poses |
     // sample offsets) and behind it the download block (filter states | filtered poses) of one job, device and pinned,
@@ -419,6 +426,16 @@ TileTable<Tile, Launch> group_tile_table(svo_group* c, const char* env, Launch r
 // what one unit of the group implements for the others (svo_group.hip all of it)
 size_t align_up(size_t v, size_t a);
 void dev_release(svo_group* c, void* p, size_t bytes);                 // gives an allocation of dev_alloc back
+// Host-mode delivery of a job whose named slot seg[i] owns image_bytes at seg[i] * image_bytes of the caller's `to` and
+// whose i-th slot was staged at i * image_bytes of `from`, `used` bytes of it: every run of delivered slots (shown[i])
+// that are consecutive in both goes out with one copy, so that the bytes between two slots stay untouched. Enqueued
+// on `st`; the caller synchronises.
+int copy_out_slots(hipStream_t st, uint8_t* to, const uint8_t* from, const int* seg, const char* shown, int n, int64_t image_bytes,
+                   int64_t used);
+// a failed group rejects the job of entry point `who` (SVO_OK: it has not failed)
+int reject_if_failed(const svo_group* c, const char* who);
+// how a job that reads the slots' poses begins: reject_if_failed, the group's device, the deferred pose-filter updates
+int job_begin(svo_group* c, const char* who);
 int acquire_set(svo_group* c, Seq& q, ImageSet** out);
 void release_set(Seq& q, ImageSet*& s);
 int take_kf_slab(svo_group* c, KpsDev* out);
@@ -430,4 +447,21 @@ void trim_keyframes(svo_group* c, Seq& q, int below);                  // drops 
 int check_settings(const svo_camera_settings* cam, int width, int height, int n_sequences);
 int keypoint_capacity(const svo_camera_settings& cam, int width, int height);
 int usable_lk_levels(const svo_camera_settings& cam, int width, int height);
+
+template <typename T, bool Mirror>
+int GrowBlock<T, Mirror>::reserve(svo_group* c, size_t want) {
+    if (want <= bytes) return SVO_OK;
+    HIP_TRY(hipStreamSynchronize(c->stream.get()));
+    if (p) dev_release(c, p, bytes);
+    p = nullptr; bytes = 0;
+    if (Mirror) {
+        host.reset();
+        HIP_TRY(pinned_malloc(host, want));
+    }
+    uint8_t* q = nullptr;
+    if (const int rc = dev_alloc(c, &q, want, false)) return rc;
+    p = reinterpret_cast<T*>(q);
+    bytes = want;
+    return SVO_OK;
+}
 }  // namespace svo

@@ -599,8 +599,7 @@ int grp_new_images(svo_group* c, const uint8_t* const* left, const uint8_t* cons
     if (!c || !left || (!right && c->fmt->buffers == 2) || !time_stamps ||
         (long long)stride < (long long)ingest_row_pixels(*c->fmt, c->width) * c->fmt->channels)
         return svo_set_error(SVO_ERR_INVALID, "svo_new_images: bad arguments");
-    if (c->failed)
-        return svo_set_error(SVO_ERR_INVALID, "svo_new_images: an earlier frame of this ctx failed; create a new ctx");
+    if (const int rc = reject_if_failed(c, "svo_new_images")) return rc;
     Step s;
     s.left = left; s.right = right; s.stride = stride; s.mem = mem; s.time_stamps = time_stamps;
     const int rc = step(c, s);

@@ -23,17 +23,6 @@ void view_shape(int width, int height, const svo_view_style& s, int* cols, int* 
     if (image_bytes) *image_bytes = (int64_t)align_up((size_t)(p * h), 256);
 }
 
-// the host-mode staging block holds `bytes`
-int reserve_view(svo_group* c, size_t bytes) {
-    if (bytes <= c->view_bytes) return SVO_OK;
-    HIP_TRY(hipStreamSynchronize(c->stream.get()));
-    if (c->d_view) dev_release(c, c->d_view, c->view_bytes);
-    c->d_view = nullptr; c->view_bytes = 0;
-    if (const int rc = dev_alloc(c, &c->d_view, bytes, false)) return rc;
-    c->view_bytes = bytes;
-    return SVO_OK;
-}
-
 }  // namespace
 
 extern "C" int svo_view_size(const svo_camera_settings* cam, int width, int height, const svo_view_style* style, int* cols,
@@ -62,17 +51,14 @@ int grp_check_view_style(const svo_group* c, const svo_view_style* style) {
 // (group_tile_table), one launch unless it outgrows them.
 int grp_export_views(svo_group* c, int what, int mem, const int* seqs, const int* seg, int n, int seq0,
                      const svo_view_style* style, const svo_view_dst* dst) {
-    if (c->failed)
-        return svo_set_error(SVO_ERR_INVALID, "svo_submit_export_views: an earlier frame of this ctx failed; create a new ctx");
-    HIP_TRY(hipSetDevice(c->device));
-    flush_pending(c);
+    if (const int rc = job_begin(c, "svo_submit_export_views")) return rc;
     hipStream_t st = c->stream.get();
     const bool host = mem == SVO_MEM_HOST;
     int cols, rows; int64_t pitch, image_bytes;
     view_shape(c->width, c->height, *style, &cols, &rows, &pitch, &image_bytes);
     const int64_t used = (int64_t)rows * pitch;          // bytes of an image
     if (host)
-        if (const int rc = reserve_view(c, (size_t)n * (size_t)image_bytes)) return rc;
+        if (const int rc = c->d_view.reserve(c, (size_t)n * (size_t)image_bytes)) return rc;
     const ViewParams params = view_params(*style);
     // (SVO_VIEW_TABLE_TILES: a smaller table, so that tests reach the chunked launches)
     auto table = group_tile_table<ViewTile>(c, "SVO_VIEW_TABLE_TILES",
@@ -103,27 +89,15 @@ int grp_export_views(svo_group* c, int what, int mem, const int* seqs, const int
             return svo_set_error(SVO_ERR_INVALID, "svo_submit_export_views: level %d is %d x %d, not %d x %d", style->level, src.w, src.h, cols, rows);
         e.status = SVO_VIEW_OK;
         shown[i] = 1;
-        uint8_t* out = host ? c->d_view + (int64_t)i * image_bytes : dst->pixels + e.offset;
+        uint8_t* out = host ? c->d_view.p + (int64_t)i * image_bytes : dst->pixels + e.offset;
         tiles.clear();
         view_tiles(src, out, style->markers ? kps : nullptr, e.n, tiles);
         for (const ViewTile& t : tiles)
             if (const int rc = table.add(t)) return rc;
     }
     if (const int rc = table.launch(false)) return rc;
-    for (int i = 0; host && i < n;) {
-        if (!shown[i]) { i++; continue; }
-        int j = i + 1;
-        while (j < n && shown[j] && seg[j] == seg[j - 1] + 1) j++;
-        uint8_t* to = dst->pixels + (int64_t)seg[i] * image_bytes;
-        const uint8_t* from = c->d_view + (int64_t)i * image_bytes;
-        if (used == image_bytes)
-            HIP_TRY(hipMemcpyAsync(to, from, (size_t)((j - i) * image_bytes), hipMemcpyDeviceToHost, st));
-        else if (j - i == 1)
-            HIP_TRY(hipMemcpyAsync(to, from, (size_t)used, hipMemcpyDeviceToHost, st));
-        else
-            HIP_TRY(hipMemcpy2DAsync(to, (size_t)image_bytes, from, (size_t)image_bytes, (size_t)used, (size_t)(j - i), hipMemcpyDeviceToHost, st));
-        i = j;
-    }
+    if (host)
+        if (const int rc = copy_out_slots(st, dst->pixels, c->d_view.p, seg, shown.data(), n, image_bytes, used)) return rc;
     HIP_TRY(hipStreamSynchronize(st));       // delivered: svo_wait means that
     return SVO_OK;
 }
