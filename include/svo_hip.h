@@ -1284,6 +1284,74 @@ typedef struct svo_cloud_src {       /* 96 bytes */
 int svo_cloud_points(svo_handle *h, int n, const svo_cloud_src *src, const int64_t *first, const svo_cloud_style *style,
                      svo_map_point *points, int32_t *counts);
 
+/* ---- cross-check: which values of a dense map or cloud to trust ------------
+ * "dense" and "clouds" deliver the one-directional search at every lattice point, so they hold a confident-looking
+ * value where the stereo pair has none: half-occluded bands beside depth edges, repeated texture, flat walls. A wrong
+ * match in texture has a low cost, so neither the cost plane nor max_mean_cost sees it. The left-right consistency
+ * check keeps a disparity only if the search from the matched right pixel back into the left image comes home. The
+ * reverse search is the point rule of "dense" on the mirrored, swapped planes, which exist on the device only.
+ *
+ * Statement. point(L, R, x, y) is svo_ssd_disparity(L, R, {(x, y)}, 1, win, search_x, search_y, 1, .): the disparity
+ * of "dense" (-1: invalid). With W the width, Lm[y][u] = R[y][W - 1 - u] and Rm[y][u] = L[y][W - 1 - u]. For the
+ * lattice point at pixel (x, y) with disp its forward disparity (before any conversion to depth):
+ *   lr = -1                      the point is invalid in the forward search; otherwise
+ *   xr = x + (int)(disp + 0.5f)  (a float add rounded once, then truncation; disp >= 0.5)
+ *   lr = -2                      xr > W - 1; otherwise
+ *   rd = point(Lm, Rm, W - 1 - xr, y) with the same win, search_x, search_y
+ *   lr = -2                      rd is invalid; else lr = fabsf(disp - rd)
+ * A point FAILS at a tolerance max_lr_diff > 0 iff lr < 0.0f || lr > max_lr_diff (float32 comparisons).
+ *
+ * The setting rides beside the style in the "checked" form of each entry, which takes the unchecked entry's arguments
+ * plus a check. With check == NULL or check->lr == 0 a checked entry is the unchecked one: the same launches, bytes,
+ * memory, segments and rejections. Rejected with SVO_ERR_INVALID and nothing queued (a non-NULL check is checked
+ * whatever its lr): lr other than 0 or 1, a negative or non-finite max_lr_diff, a non-zero _reserved; for a cloud
+ * lr = 1 with max_lr_diff == 0. Everything else is rejected exactly as the unchecked entry rejects it.
+ *
+ * Disparity job and stage with lr = 1: a plane lr is appended, so the plane order is value, [cost], lr, planes is 2
+ * or 3 and image_bytes = up256(planes * cols * rows * 4). With max_lr_diff > 0 the value plane of a failing point
+ * gets the invalid value (-1 for SVO_DENSE_DISPARITY, 0 for SVO_DENSE_DEPTH); with max_lr_diff == 0 the check only
+ * reports. The cost plane is never changed. SVO_DENSE_DEPTH is baseline / disp of the surviving disparity, the bits
+ * of the unchecked job.
+ * Cloud job and stage with lr = 1: a failing point is dropped, in addition to the three filters of "clouds"; order
+ * and layouts are unchanged.
+ *
+ * Queueing: no new job kind. A checked job is a disparity or cloud job, so queue order, segments and the "slot is not
+ * changed" rule are theirs.
+ * Memory: the reverse search writes one float per column of every lattice row, reverse_bytes = up256(rows * W * 4) per
+ * slot, into a staging block of the group (not the disparity or cloud job's), made by the group's first checked job
+ * and replaced when outgrown (svo_memory.device_bytes):
+ *   block = min(named slots of the group, chunk) * reverse_bytes
+ * Disparity job: chunk = max(1, 256 MiB / reverse_bytes) (the diagnostic SVO_LR_CHUNK_SLOTS lowers it); the forward
+ * search of all named slots runs as in the unchecked job, then the reverse search and the check run in chunks of so
+ * many slots. The forward disparity is converted in place (a lane reads and writes only its own lattice point), so a
+ * device-mode job with value = SVO_DENSE_DEPTH needs no copy of it. Cloud job: the chunk of "clouds" with slot_bytes +
+ * reverse_bytes in the place of slot_bytes; the check masks the staged disparity plane before the count and write
+ * launches, which therefore agree as before. An unchecked job allocates what it did; a ctx that never asks for a check
+ * allocates, launches and copies nothing more. */
+typedef struct svo_stereo_check {   /* 32 bytes; copied at submit */
+    int32_t lr;            /* 0: off (the same as a NULL check), 1: on                       */
+    float   max_lr_diff;   /* finite, >= 0; 0: report only (a cloud job requires > 0)        */
+    int32_t _reserved[6];  /* 0 */
+} svo_stereo_check;
+
+/* svo_disparity_size of a checked job: planes is 1 .. 3 */
+int svo_disparity_size_checked(const svo_camera_settings *cam, int width, int height, const svo_disparity_style *style,
+                               const svo_stereo_check *check, int *cols, int *rows, int *planes, int64_t *image_bytes);
+int svo_submit_export_disparity_checked(svo_ctx *ctx, int what, const int *seqs, int n, const svo_disparity_style *style,
+                                        const svo_stereo_check *check, const svo_disparity_dst *dst, int mem);
+int svo_export_disparity_checked(svo_ctx *ctx, int what, const int *seqs, int n, const svo_disparity_style *style,
+                                 const svo_stereo_check *check, const svo_disparity_dst *dst, int mem);   /* submit + wait */
+/* stage entry: svo_dense_disparity with the check; the reverse planes of a table chunk live in the handle's workspace */
+int svo_dense_disparity_checked(svo_handle *h, int n, const svo_dense_src *src, const int64_t *offset,
+                                const svo_disparity_style *style, const svo_stereo_check *check, float *values);
+int svo_submit_export_cloud_checked(svo_ctx *ctx, int what, const int *seqs, int n, const svo_cloud_style *style,
+                                    const svo_stereo_check *check, const svo_cloud_dst *dst, int mem);
+int svo_export_cloud_checked(svo_ctx *ctx, int what, const int *seqs, int n, const svo_cloud_style *style,
+                             const svo_stereo_check *check, const svo_cloud_dst *dst, int mem);   /* submit + wait */
+/* stage entry: svo_cloud_points with the check */
+int svo_cloud_points_checked(svo_handle *h, int n, const svo_cloud_src *src, const int64_t *first, const svo_cloud_style *style,
+                             const svo_stereo_check *check, svo_map_point *points, int32_t *counts);
+
 /* ---- snapshots: the sequence state of a slot saved, loaded, moved between ctxs ------------
  * The reference has no checkpoint or resume (a StereoSlam lives and dies with its process). A snapshot is
  * everything the next frame of a slot depends on and everything its getters return, so that a sequence saved

@@ -74,8 +74,8 @@ int dense_check_style(const svo_disparity_style* s, const svo_camera_settings* c
     return SVO_OK;
 }
 
-void dense_shape(const DenseParams& p, int w, int h, int* cols, int* rows, int* planes, int64_t* image_bytes) {
-    const int c = w / p.step, r = h / p.step, n = 1 + p.cost;
+void dense_shape(const DenseParams& p, int w, int h, int* cols, int* rows, int* planes, int64_t* image_bytes, int lr) {
+    const int c = w / p.step, r = h / p.step, n = 1 + p.cost + lr;
     if (cols) *cols = c;
     if (rows) *rows = r;
     if (planes) *planes = n;
@@ -108,14 +108,26 @@ __device__ __forceinline__ int dense_wave_prefix(int v) {
     return v;
 }
 
-__global__ __launch_bounds__(DENSE_THREADS) void dense_disparity_kernel(const DenseImage* __restrict__ images, const DenseParams p) {
+// MIRROR: the reverse search of the cross-check (include/svo_hip.h, "cross-check"; lr.hip has the rest). The point rule
+// runs on the mirrored, swapped planes Lm[y][u] = R[y][W - 1 - u], Rm[y][u] = L[y][W - 1 - u]: the two staging loops
+// read column W - 1 - xx of the other plane (byte loads: a wave reads 64 consecutive bytes in descending order, at any
+// base and stride), the lattice has every column (column step 1) and the rows of the forward lattice, and the disparity
+// of mirrored column u goes to out[iy][W - 1 - u], a plane of rows x W floats indexed by the right image's own column.
+// Nothing after the staging differs. MIRROR = false is the kernel as it was.
+template <bool MIRROR>
+__global__ __launch_bounds__(DENSE_THREADS) void dense_disparity_kernel(const std::conditional_t<MIRROR, LrImage, DenseImage>* __restrict__ images,
+                                                                        const DenseParams p) {
     __shared__ __attribute__((aligned(16))) uint8_t s_l[DENSE_L_ROWS * DENSE_THREADS];
     __shared__ __attribute__((aligned(16))) uint8_t s_r[DENSE_R_ROWS * DENSE_R_COLS];
     __shared__ int s_p[2][DENSE_BAND][DENSE_THREADS];
     __shared__ int s_t[2][DENSE_BAND][DENSE_THREADS / 64];
-    const DenseImage im = G(images)[blockIdx.y];
+    const auto im = G(images)[blockIdx.y];
     const int W = im.w, H = im.h, step = p.step, win = p.win, sx = p.search_x, sy = p.search_y;
-    const int cols = W / step, rows = H / step;
+    const int cstep = MIRROR ? 1 : step;                   // the lattice's column step
+    const int cols = W / cstep, rows = H / step;
+    const uint8_t* const src_l = MIRROR ? im.right : im.left;
+    const uint8_t* const src_r = MIRROR ? im.left : im.right;
+    const int stride_l = MIRROR ? im.right_stride : im.left_stride, stride_r = MIRROR ? im.left_stride : im.right_stride;
     const int wb = win / 2, wa = (win + 1) / 2;
     const int span = dense_span(win), band = dense_band(step, win, p.band);
     const int ntx = (W + span - 1) / span, nty = (rows + band - 1) / band;
@@ -130,17 +142,17 @@ __global__ __launch_bounds__(DENSE_THREADS) void dense_disparity_kernel(const De
     // the band's planes, zero outside the images
     for (int i = tid; i < DENSE_L_ROWS * DENSE_THREADS; i += DENSE_THREADS) {
         const int yy = yl0 + i / DENSE_THREADS, xx = X0 + i % DENSE_THREADS;
-        s_l[i] = (yy < H && xx >= 0 && xx < W) ? G(im.left)[(int64_t)yy * im.left_stride + xx] : (uint8_t)0;
+        s_l[i] = (yy < H && xx >= 0 && xx < W) ? G(src_l)[(int64_t)yy * stride_l + (MIRROR ? W - 1 - xx : xx)] : (uint8_t)0;
     }
     for (int i = tid; i < DENSE_R_ROWS * DENSE_R_COLS; i += DENSE_THREADS) {
         const int yy = yl0 - sy + i / DENSE_R_COLS, xx = X0 + i % DENSE_R_COLS;
-        s_r[i] = (yy >= 0 && yy < H && xx >= 0 && xx < W) ? G(im.right)[(int64_t)yy * im.right_stride + xx] : (uint8_t)0;
+        s_r[i] = (yy >= 0 && yy < H && xx >= 0 && xx < W) ? G(src_r)[(int64_t)yy * stride_r + (MIRROR ? W - 1 - xx : xx)] : (uint8_t)0;
     }
 
     // this lane's lattice point, if it has one: column x of the tile's span
-    const int x = X0 + tid, xl = x - step / 2;
-    const bool in_span = tid >= wb && tid < wb + span && xl >= 0 && xl % step == 0 && xl / step < cols;
-    const int ix = in_span ? xl / step : 0;
+    const int x = X0 + tid, xl = x - cstep / 2;
+    const bool in_span = tid >= wb && tid < wb + span && xl >= 0 && xl % cstep == 0 && xl / cstep < cols;
+    const int ix = in_span ? xl / cstep : 0;
     const int x11 = max(0, x - wb), x12 = min(W - 1, x + wa), x22 = min(W - 1, x + wa + sx);
     const int tw = x12 - x11, mw = (x22 - x11) - tw + 1;
     const bool xok = !(x12 <= 0 || x11 >= W - 1 || x22 <= 0) && tw > 0 && mw > 0;
@@ -221,6 +233,15 @@ __global__ __launch_bounds__(DENSE_THREADS) void dense_disparity_kernel(const De
 
     if (!in_span) return;
     SVO_GP(float) out = G(im.out);
+    if (MIRROR) {                                          // the disparity alone, at the unmirrored column
+#pragma unroll
+        for (int r = 0; r < DENSE_BAND; r++) {
+            if (r >= nrow) continue;
+            const float d = (float)sum[r] / (float)cnt[r];
+            out[(int64_t)(iy0 + r) * W + (W - 1 - ix)] = xok && cnt[r] > 0 ? (d < 0.5f ? 0.5f : d) : -1.f;
+        }
+        return;
+    }
     const int64_t plane = (int64_t)cols * rows;
 #pragma unroll
     for (int r = 0; r < DENSE_BAND; r++) {
@@ -240,7 +261,12 @@ __global__ __launch_bounds__(DENSE_THREADS) void dense_disparity_kernel(const De
 
 void launch_dense(const DenseImage* d_images, int n, int tiles, const DenseParams& p, hipStream_t stream) {
     if (n <= 0 || tiles <= 0) return;
-    hipLaunchKernelGGL(dense_disparity_kernel, dim3(tiles, n), dim3(DENSE_THREADS), 0, stream, d_images, p);
+    hipLaunchKernelGGL(dense_disparity_kernel<false>, dim3(tiles, n), dim3(DENSE_THREADS), 0, stream, d_images, p);
+}
+
+void launch_dense_reverse(const LrImage* d_images, int n, int tiles, const DenseParams& p, hipStream_t stream) {
+    if (n <= 0 || tiles <= 0) return;
+    hipLaunchKernelGGL(dense_disparity_kernel<true>, dim3(tiles, n), dim3(DENSE_THREADS), 0, stream, d_images, p);
 }
 
 }  // namespace svo

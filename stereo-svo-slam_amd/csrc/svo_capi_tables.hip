@@ -432,12 +432,21 @@ extern "C" int svo_render_ar(svo_handle* h, int n, const svo_ar_src* src, const 
                         [&](const ArTile* d, int m, hipStream_t s) { launch_ar(d, m, d_images, params, s); });
 }
 
-extern "C" int svo_dense_disparity(svo_handle* h, int n, const svo_dense_src* src, const int64_t* offset,
-                                   const svo_disparity_style* style, float* values) {
+// With a check that is on, a chunk of the image table is followed by its LrImage table and the reverse planes of its
+// images (each a multiple of 256 bytes) in the workspace: the search writes disparities whatever the style's value, the
+// reverse search and the check follow it in the stream.
+extern "C" int svo_dense_disparity_checked(svo_handle* h, int n, const svo_dense_src* src, const int64_t* offset,
+                                           const svo_disparity_style* style, const svo_stereo_check* check, float* values) {
     CHECK_H(h);
     if (n < 0 || (n > 0 && (!src || !offset))) return svo_set_error(SVO_ERR_INVALID, "svo_dense_disparity: bad arguments");
     DenseParams params;
     if (const int rc = dense_check_style(style, nullptr, "svo_dense_disparity", &params)) return rc;
+    LrCheck lr;
+    if (const int rc = lr_check_parse(check, false, "svo_dense_disparity_checked", &lr)) return rc;
+    const LrParams lr_params{params.value, params.step, lr.max_lr_diff};
+    if (lr.on) params.value = SVO_DENSE_DISPARITY;
+    std::vector<LrImage> checks(lr.on ? (size_t)n : 0);
+    std::vector<size_t> reverse(lr.on ? (size_t)n : 0);
     if (!values || ((uintptr_t)values & 15)) return svo_set_error(SVO_ERR_INVALID, "svo_dense_disparity: values is NULL or not 16-byte aligned");
     std::vector<DenseImage> images((size_t)n);
     std::vector<int> tiles((size_t)n);
@@ -453,6 +462,13 @@ extern "C" int svo_dense_disparity(svo_handle* h, int n, const svo_dense_src* sr
         images[(size_t)i] = DenseImage{l.data, r.data, reinterpret_cast<float*>(reinterpret_cast<uint8_t*>(values) + offset[i]),
                                        l.stride, r.stride, l.width, l.height, src[i].baseline, 0};
         tiles[(size_t)i] = dense_tiles(params, l.width, l.height);
+        if (lr.on) {
+            float* value = images[(size_t)i].out;
+            const int64_t plane = (int64_t)(l.width / params.step) * (l.height / params.step);
+            checks[(size_t)i] = LrImage{l.data, r.data, nullptr, value, value + (1 + params.cost) * plane, l.stride, r.stride, l.width, l.height,
+                                        src[i].baseline, 0};
+            reverse[(size_t)i] = lr_reverse_bytes(l.width, l.height, params.step);
+        }
     }
     if (n == 0) return SVO_OK;
     long long workgroups = 0;
@@ -461,8 +477,16 @@ extern "C" int svo_dense_disparity(svo_handle* h, int n, const svo_dense_src* sr
     for (int i = 0; i < n; i++) tiles[(size_t)i] = dense_tiles(params, images[(size_t)i].w, images[(size_t)i].h);
     // (SVO_DENSE_TABLE_IMAGES: a smaller table, so that tests reach the chunked launches)
     const size_t chunk = table_tiles("SVO_DENSE_TABLE_IMAGES", std::min<size_t>((size_t)n, DENSE_MAX_IMAGES));
-    if (const int rc = h->dense_ws.reserve(sizeof(DenseImage) * chunk, h->stream)) return rc;
+    const size_t tables = lr.on ? ((sizeof(DenseImage) + sizeof(LrImage)) * chunk + 255) / 256 * 256 : sizeof(DenseImage) * chunk;
+    size_t block = 0;
+    for (size_t i0 = 0; lr.on && i0 < (size_t)n; i0 += chunk) {
+        size_t b = 0;
+        for (size_t i = i0; i < std::min(i0 + chunk, (size_t)n); i++) b += reverse[i];
+        block = std::max(block, b);
+    }
+    if (const int rc = h->dense_ws.reserve(tables + block, h->stream)) return rc;
     DenseImage* d_images = reinterpret_cast<DenseImage*>(h->dense_ws.ptr.get());
+    LrImage* d_checks = reinterpret_cast<LrImage*>(d_images + chunk);
     int rc = SVO_OK;
     for (size_t i0 = 0; i0 < (size_t)n && rc == SVO_OK; i0 += chunk) {
         const size_t m = std::min(chunk, (size_t)n - i0);
@@ -471,7 +495,23 @@ extern "C" int svo_dense_disparity(svo_handle* h, int n, const svo_dense_src* sr
             rc = svo_set_error(SVO_ERR_HIP, "svo_dense_disparity: an upload failed");
             break;
         }
-        launch_dense(d_images, (int)m, *std::max_element(tiles.begin() + (ptrdiff_t)i0, tiles.begin() + (ptrdiff_t)(i0 + m)), params, h->stream);
+        const int grid = *std::max_element(tiles.begin() + (ptrdiff_t)i0, tiles.begin() + (ptrdiff_t)(i0 + m));
+        launch_dense(d_images, (int)m, grid, params, h->stream);
+        if (lr.on) {
+            uint8_t* at = h->dense_ws.ptr.get() + tables;
+            int lr_grid = 0;
+            for (size_t i = i0; i < i0 + m; i++) {
+                checks[i].out = reinterpret_cast<float*>(at);
+                at += reverse[i];
+                lr_grid = std::max(lr_grid, lr_tiles((int64_t)(checks[i].w / params.step) * (checks[i].h / params.step)));
+            }
+            if (hipMemcpyAsync(d_checks, checks.data() + i0, sizeof(LrImage) * m, hipMemcpyHostToDevice, h->stream) != hipSuccess) {
+                rc = svo_set_error(SVO_ERR_HIP, "svo_dense_disparity: an upload failed");
+                break;
+            }
+            launch_dense_reverse(d_checks, (int)m, grid, params, h->stream);
+            launch_lr_check(d_checks, (int)m, lr_grid, lr_params, h->stream);
+        }
         if (hipGetLastError() != hipSuccess) rc = svo_set_error(SVO_ERR_HIP, "svo_dense_disparity: a launch failed");
     }
     const hipError_t e = hipStreamSynchronize(h->stream);    // (the uploads read host memory of this call)
@@ -480,13 +520,24 @@ extern "C" int svo_dense_disparity(svo_handle* h, int n, const svo_dense_src* sr
     return SVO_OK;
 }
 
-extern "C" int svo_cloud_points(svo_handle* h, int n, const svo_cloud_src* src, const int64_t* first, const svo_cloud_style* style,
-                                svo_map_point* points, int32_t* counts) {
+extern "C" int svo_dense_disparity(svo_handle* h, int n, const svo_dense_src* src, const int64_t* offset,
+                                   const svo_disparity_style* style, float* values) {
+    return svo_dense_disparity_checked(h, n, src, offset, style, nullptr, values);
+}
+
+// With a check that is on, an image's block of the workspace ends with its reverse plane, the LrImage table follows
+// the other two, and the reverse search and the check (a mask on the staged disparity plane) run between the search
+// and the count launch.
+extern "C" int svo_cloud_points_checked(svo_handle* h, int n, const svo_cloud_src* src, const int64_t* first, const svo_cloud_style* style,
+                                        const svo_stereo_check* check, svo_map_point* points, int32_t* counts) {
     CHECK_H(h);
     if (n < 0 || (n > 0 && (!src || !first))) return svo_set_error(SVO_ERR_INVALID, "svo_cloud_points: bad arguments");
     DenseParams search;
     CloudParams params;
     if (const int rc = cloud_check_style(style, nullptr, "svo_cloud_points", &search, &params)) return rc;
+    LrCheck lr;
+    if (const int rc = lr_check_parse(check, true, "svo_cloud_points_checked", &lr)) return rc;
+    const LrParams lr_params{SVO_DENSE_DISPARITY, search.step, lr.max_lr_diff};
     if (!points || ((uintptr_t)points & 15)) return svo_set_error(SVO_ERR_INVALID, "svo_cloud_points: points is NULL or not 16-byte aligned");
     if ((uintptr_t)counts & 3) return svo_set_error(SVO_ERR_INVALID, "svo_cloud_points: counts is not 4-byte aligned");
     // per image of a chunk: its two planes, its tile counts and its pose matrices, each rounded up to 256 bytes
@@ -501,7 +552,8 @@ extern "C" int svo_cloud_points(svo_handle* h, int n, const svo_cloud_src* src, 
             return svo_set_error(SVO_ERR_INVALID, "svo_cloud_points: image %d: %d x %d has no lattice point at step %d", i, l.width, l.height, params.step);
         if (first[i] < 0) return svo_set_error(SVO_ERR_INVALID, "svo_cloud_points: image %d: first must be >= 0", i);
         const size_t pts = (size_t)(l.width / params.step) * (size_t)(l.height / params.step);
-        image_block[(size_t)i + 1] = (pts * 8 + 255) / 256 * 256 + ((size_t)cloud_tiles((int64_t)pts) * 4 + 255) / 256 * 256 + 256;
+        image_block[(size_t)i + 1] = (pts * 8 + 255) / 256 * 256 + ((size_t)cloud_tiles((int64_t)pts) * 4 + 255) / 256 * 256 + 256 +
+                                     (lr.on ? lr_reverse_bytes(l.width, l.height, params.step) : 0);
     }
     if (n == 0) return SVO_OK;
     // (SVO_CLOUD_TABLE_IMAGES: a smaller table, so that tests reach the chunked launches. SVO_CLOUD_SKIP_SEARCH=1: a
@@ -510,7 +562,7 @@ extern "C" int svo_cloud_points(svo_handle* h, int n, const svo_cloud_src* src, 
     const size_t chunk = table_tiles("SVO_CLOUD_TABLE_IMAGES", std::min<size_t>((size_t)n, DENSE_MAX_IMAGES));
     const char* skip_env = std::getenv("SVO_CLOUD_SKIP_SEARCH");
     const bool skip_search = skip_env && std::atoi(skip_env) == 1;
-    const size_t tables = ((sizeof(CloudImage) + sizeof(DenseImage)) * chunk + 255) / 256 * 256;
+    const size_t tables = ((sizeof(CloudImage) + sizeof(DenseImage) + (lr.on ? sizeof(LrImage) : 0)) * chunk + 255) / 256 * 256;
     size_t block = 0;
     for (size_t i0 = 0; i0 < (size_t)n; i0 += chunk) {
         size_t b = 0;
@@ -520,8 +572,10 @@ extern "C" int svo_cloud_points(svo_handle* h, int n, const svo_cloud_src* src, 
     if (const int rc = h->cloud_ws.reserve(tables + block, h->stream)) return rc;
     CloudImage* d_cloud = reinterpret_cast<CloudImage*>(h->cloud_ws.ptr.get());
     DenseImage* d_dense = reinterpret_cast<DenseImage*>(d_cloud + chunk);
+    LrImage* d_checks = reinterpret_cast<LrImage*>(d_dense + chunk);
     std::vector<CloudImage> cloud(chunk);
     std::vector<DenseImage> dense(chunk);
+    std::vector<LrImage> checks(lr.on ? chunk : 0);
     int rc = SVO_OK;
     for (size_t i0 = 0; i0 < (size_t)n && rc == SVO_OK; i0 += chunk) {
         const size_t m = std::min(chunk, (size_t)n - i0);
@@ -534,7 +588,11 @@ extern "C" int svo_cloud_points(svo_handle* h, int n, const svo_cloud_src* src, 
             const size_t pts = (size_t)(s.left.width / params.step) * (size_t)(s.left.height / params.step);
             float* planes = reinterpret_cast<float*>(at);
             int* tile_counts = reinterpret_cast<int*>(at + (pts * 8 + 255) / 256 * 256);
-            float* mats = reinterpret_cast<float*>(at + image_block[i0 + j + 1] - 256);
+            const size_t reverse = lr.on ? lr_reverse_bytes(s.left.width, s.left.height, params.step) : 0;
+            float* mats = reinterpret_cast<float*>(at + image_block[i0 + j + 1] - reverse - 256);
+            if (lr.on)
+                checks[j] = LrImage{s.left.data, s.right.data, reinterpret_cast<float*>(at + image_block[i0 + j + 1] - reverse), planes, nullptr,
+                                    s.left.stride, s.right.stride, s.left.width, s.left.height, s.baseline, 0};
             at += image_block[i0 + j + 1];
             dense[j] = DenseImage{s.left.data, s.right.data, planes, s.left.stride, s.right.stride, s.left.width, s.left.height, s.baseline, 0};
             CloudImage& c = cloud[j];
@@ -554,6 +612,14 @@ extern "C" int svo_cloud_points(svo_handle* h, int n, const svo_cloud_src* src, 
             break;
         }
         if (!skip_search) launch_dense(d_dense, (int)m, dense_grid, sp, h->stream);
+        if (lr.on) {
+            if (hipMemcpyAsync(d_checks, checks.data(), sizeof(LrImage) * m, hipMemcpyHostToDevice, h->stream) != hipSuccess) {
+                rc = svo_set_error(SVO_ERR_HIP, "svo_cloud_points: an upload failed");
+                break;
+            }
+            launch_dense_reverse(d_checks, (int)m, dense_grid, sp, h->stream);
+            launch_lr_check(d_checks, (int)m, lr_tiles((int64_t)cloud_grid * CLOUD_TILE), lr_params, h->stream);
+        }
         launch_cloud(d_cloud, (int)m, cloud_grid, params, h->stream);
         if (hipGetLastError() != hipSuccess) rc = svo_set_error(SVO_ERR_HIP, "svo_cloud_points: a launch failed");
     }
@@ -561,6 +627,11 @@ extern "C" int svo_cloud_points(svo_handle* h, int n, const svo_cloud_src* src, 
     if (rc) return rc;
     HIP_TRY(e);
     return SVO_OK;
+}
+
+extern "C" int svo_cloud_points(svo_handle* h, int n, const svo_cloud_src* src, const int64_t* first, const svo_cloud_style* style,
+                                svo_map_point* points, int32_t* counts) {
+    return svo_cloud_points_checked(h, n, src, first, style, nullptr, points, counts);
 }
 
 extern "C" int svo_copy_segments(svo_handle* h, int n, const svo_copy_segment* segs) {

@@ -81,8 +81,15 @@ struct svo_ctx {
         Dst dst{};
     };
     using ViewExport = ImageExport<svo_view_style, svo_view_dst>;
-    using DisparityExport = ImageExport<svo_disparity_style, svo_disparity_dst>;
-    using CloudExport = ImageExport<svo_cloud_style, svo_cloud_dst>;
+    // (a checked job carries its cross-check beside the style: has_check)
+    template <typename Style, typename Dst>
+    struct CheckedExport : ImageExport<Style, Dst> {
+        bool has_check = false;
+        svo_stereo_check check{};
+        const svo_stereo_check* check_ptr() const { return has_check ? &check : nullptr; }
+    };
+    using DisparityExport = CheckedExport<svo_disparity_style, svo_disparity_dst>;
+    using CloudExport = CheckedExport<svo_cloud_style, svo_cloud_dst>;
     // the group's share of an svo_submit_export_scenes: its named slots (indices in the group) in named order, the
     // camera of each and the segment (and image) of the job each one fills
     struct SceneExport {
@@ -184,10 +191,10 @@ int run_job(svo_group* g, int seq0, const svo_ctx::ViewExport& j) {
     return grp_export_views(g, j.what, j.mem, j.seqs.data(), j.seg.data(), (int)j.seqs.size(), seq0, &j.style, &j.dst);
 }
 int run_job(svo_group* g, int seq0, const svo_ctx::DisparityExport& j) {
-    return grp_export_disparity(g, j.what, j.mem, j.seqs.data(), j.seg.data(), (int)j.seqs.size(), seq0, &j.style, &j.dst);
+    return grp_export_disparity(g, j.what, j.mem, j.seqs.data(), j.seg.data(), (int)j.seqs.size(), seq0, &j.style, j.check_ptr(), &j.dst);
 }
 int run_job(svo_group* g, int seq0, const svo_ctx::CloudExport& j) {
-    return grp_export_cloud(g, j.what, j.mem, j.seqs.data(), j.seg.data(), (int)j.seqs.size(), seq0, &j.style, &j.dst);
+    return grp_export_cloud(g, j.what, j.mem, j.seqs.data(), j.seg.data(), (int)j.seqs.size(), seq0, &j.style, j.check_ptr(), &j.dst);
 }
 int run_job(svo_group* g, int seq0, const svo_ctx::SceneExport& j) {
     return grp_export_scenes(g, j.mem, j.seqs.data(), j.seg.data(), (int)j.seqs.size(), seq0, &j.style, j.cameras.data(), &j.dst);
@@ -545,20 +552,24 @@ extern "C" int svo_export_views(svo_ctx* c, int what, const int* seqs, int n, co
     return rc ? rc : svo_wait(c);
 }
 
-extern "C" int svo_submit_export_disparity(svo_ctx* c, int what, const int* seqs, int n, const svo_disparity_style* style,
-                                           const svo_disparity_dst* dst, int mem) {
+extern "C" int svo_submit_export_disparity_checked(svo_ctx* c, int what, const int* seqs, int n, const svo_disparity_style* style,
+                                                   const svo_stereo_check* check, const svo_disparity_dst* dst, int mem) {
+    if (check && check->lr == 0) {                                   // (off: the unchecked job, once the check itself is checked)
+        if (const int rc = svo::lr_check_parse(check, false, "svo_submit_export_disparity_checked", nullptr)) return rc;
+        check = nullptr;
+    }
     if (!c || !dst || !dst->segments || (what != SVO_EXPORT_FRAMES && what != SVO_EXPORT_LAST_KEYFRAMES) ||
         (mem != SVO_MEM_HOST && mem != SVO_MEM_DEVICE) || (seqs && n < 0))
         return svo_set_error(SVO_ERR_INVALID, "svo_submit_export_disparity: bad arguments (what %d, mem %d)", what, mem);
     const svo_group* g0 = c->workers[0]->g.get();                    // (every group has the same settings)
-    if (const int rc = grp_check_disparity_style(g0, style)) return rc;
+    if (const int rc = grp_check_disparity_style(g0, style, check)) return rc;
     if (!dst->values || ((uintptr_t)dst->values & 15))
         return svo_set_error(SVO_ERR_INVALID, "svo_submit_export_disparity: values is NULL or not 16-byte aligned");
     if (!seqs) n = c->B;
     const NamedSlots slots{seqs, n};
     if (const int bad = slots.first_bad(c->B, true); bad >= 0)
         return svo_set_error(SVO_ERR_INVALID, "svo_submit_export_disparity: sequence %d is out of range or named twice", slots.at(bad));
-    const int64_t image_bytes = grp_disparity_bytes(g0, style);
+    const int64_t image_bytes = grp_disparity_bytes(g0, style, check);
     if (dst->capacity < n * image_bytes)
         return svo_set_error(SVO_ERR_CAPACITY, "svo_submit_export_disparity: %d slots need %lld bytes, capacity %lld", n,
                              (long long)(n * image_bytes), (long long)dst->capacity);
@@ -569,9 +580,15 @@ extern "C" int svo_submit_export_disparity(svo_ctx* c, int what, const int* seqs
         slots.each_in(w.first, w.count, [&](int i, int local) { e.seqs.push_back(local); e.seg.push_back(i); });
         if (e.seqs.empty()) continue;
         e.what = what; e.mem = mem; e.style = *style; e.dst = *dst;
+        if (check) { e.has_check = true; e.check = *check; }
         worker_submit(w, std::move(e));
     }
     return SVO_OK;
+}
+
+extern "C" int svo_submit_export_disparity(svo_ctx* c, int what, const int* seqs, int n, const svo_disparity_style* style,
+                                           const svo_disparity_dst* dst, int mem) {
+    return svo_submit_export_disparity_checked(c, what, seqs, n, style, nullptr, dst, mem);
 }
 
 extern "C" int svo_export_disparity(svo_ctx* c, int what, const int* seqs, int n, const svo_disparity_style* style,
@@ -580,13 +597,23 @@ extern "C" int svo_export_disparity(svo_ctx* c, int what, const int* seqs, int n
     return rc ? rc : svo_wait(c);
 }
 
-extern "C" int svo_submit_export_cloud(svo_ctx* c, int what, const int* seqs, int n, const svo_cloud_style* style,
-                                       const svo_cloud_dst* dst, int mem) {
+extern "C" int svo_export_disparity_checked(svo_ctx* c, int what, const int* seqs, int n, const svo_disparity_style* style,
+                                            const svo_stereo_check* check, const svo_disparity_dst* dst, int mem) {
+    const int rc = svo_submit_export_disparity_checked(c, what, seqs, n, style, check, dst, mem);
+    return rc ? rc : svo_wait(c);
+}
+
+extern "C" int svo_submit_export_cloud_checked(svo_ctx* c, int what, const int* seqs, int n, const svo_cloud_style* style,
+                                               const svo_stereo_check* check, const svo_cloud_dst* dst, int mem) {
+    if (check && check->lr == 0) {                                   // (off: the unchecked job, once the check itself is checked)
+        if (const int rc = svo::lr_check_parse(check, true, "svo_submit_export_cloud_checked", nullptr)) return rc;
+        check = nullptr;
+    }
     if (!c || !dst || !dst->segments || (what != SVO_EXPORT_FRAMES && what != SVO_EXPORT_LAST_KEYFRAMES) ||
         (mem != SVO_MEM_HOST && mem != SVO_MEM_DEVICE) || (seqs && n < 0))
         return svo_set_error(SVO_ERR_INVALID, "svo_submit_export_cloud: bad arguments (what %d, mem %d)", what, mem);
     const svo_group* g0 = c->workers[0]->g.get();                    // (every group has the same settings)
-    if (const int rc = grp_check_cloud_style(g0, style)) return rc;
+    if (const int rc = grp_check_cloud_style(g0, style, check)) return rc;
     if (!dst->points || ((uintptr_t)dst->points & 15))
         return svo_set_error(SVO_ERR_INVALID, "svo_submit_export_cloud: points is NULL or not 16-byte aligned");
     if (!seqs) n = c->B;
@@ -604,14 +631,26 @@ extern "C" int svo_submit_export_cloud(svo_ctx* c, int what, const int* seqs, in
         slots.each_in(w.first, w.count, [&](int i, int local) { e.seqs.push_back(local); e.seg.push_back(i); });
         if (e.seqs.empty()) continue;
         e.what = what; e.mem = mem; e.style = *style; e.dst = *dst;
+        if (check) { e.has_check = true; e.check = *check; }
         worker_submit(w, std::move(e));
     }
     return SVO_OK;
 }
 
+extern "C" int svo_submit_export_cloud(svo_ctx* c, int what, const int* seqs, int n, const svo_cloud_style* style,
+                                       const svo_cloud_dst* dst, int mem) {
+    return svo_submit_export_cloud_checked(c, what, seqs, n, style, nullptr, dst, mem);
+}
+
 extern "C" int svo_export_cloud(svo_ctx* c, int what, const int* seqs, int n, const svo_cloud_style* style,
                                 const svo_cloud_dst* dst, int mem) {
     const int rc = svo_submit_export_cloud(c, what, seqs, n, style, dst, mem);
+    return rc ? rc : svo_wait(c);
+}
+
+extern "C" int svo_export_cloud_checked(svo_ctx* c, int what, const int* seqs, int n, const svo_cloud_style* style,
+                                        const svo_stereo_check* check, const svo_cloud_dst* dst, int mem) {
+    const int rc = svo_submit_export_cloud_checked(c, what, seqs, n, style, check, dst, mem);
     return rc ? rc : svo_wait(c);
 }
 

@@ -90,20 +90,21 @@ int64_t grp_ar_bytes(const svo_group* g, const svo_ar_style* style);   // the im
 // One group's share of svo_submit_export_disparity (svo_group_dense.hip), between two steps of the group, on the thread
 // that drives it: slot seqs[i] (index in the group; ctx slot seq0 + seqs[i]) fills dst->segments[seg[i]] and its planes
 // go to byte seg[i] * image_bytes of dst->values (host or device memory: mem). style: checked
-// (grp_check_disparity_style). Delivered on return. A failed group rejects it.
+// (grp_check_disparity_style). check: the cross-check of a checked job (checked too), or null. Delivered on return. A
+// failed group rejects it.
 int grp_export_disparity(svo_group* g, int what, int mem, const int* seqs, const int* seg, int n, int seq0,
-                         const svo_disparity_style* style, const svo_disparity_dst* dst);
+                         const svo_disparity_style* style, const svo_stereo_check* check, const svo_disparity_dst* dst);
 // what svo_submit_export_disparity checks of a style, and the image_bytes of a checked one (they read only what never
 // changes in a group)
-int grp_check_disparity_style(const svo_group* g, const svo_disparity_style* style);
-int64_t grp_disparity_bytes(const svo_group* g, const svo_disparity_style* style);
+int grp_check_disparity_style(const svo_group* g, const svo_disparity_style* style, const svo_stereo_check* check);
+int64_t grp_disparity_bytes(const svo_group* g, const svo_disparity_style* style, const svo_stereo_check* check);
 // One group's share of svo_submit_export_cloud (svo_group_cloud.hip), as grp_export_disparity: slot seqs[i] fills
 // dst->segments[seg[i]] and its records start at record seg[i] * points_per_slot of dst->points. style: checked
-// (grp_check_cloud_style). Delivered on return. A failed group rejects it.
+// (grp_check_cloud_style). check: as in grp_export_disparity. Delivered on return. A failed group rejects it.
 int grp_export_cloud(svo_group* g, int what, int mem, const int* seqs, const int* seg, int n, int seq0, const svo_cloud_style* style,
-                     const svo_cloud_dst* dst);
+                     const svo_stereo_check* check, const svo_cloud_dst* dst);
 // what svo_submit_export_cloud checks of a style, and the points_per_slot of a checked one
-int grp_check_cloud_style(const svo_group* g, const svo_cloud_style* style);
+int grp_check_cloud_style(const svo_group* g, const svo_cloud_style* style, const svo_stereo_check* check);
 int64_t grp_cloud_points(const svo_group* g, const svo_cloud_style* style);
 // what svo_map_size reports of a slot (the queues have drained)
 void grp_map_size(const svo_group* g, int seq, int from_keyframe, int* keyframes, int64_t* points_bound, int* from = nullptr);

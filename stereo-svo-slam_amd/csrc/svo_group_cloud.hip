@@ -60,8 +60,10 @@ extern "C" int svo_cloud_size(const svo_camera_settings* cam, int width, int hei
     return SVO_OK;
 }
 
-int grp_check_cloud_style(const svo_group* c, const svo_cloud_style* style) {
-    return check_style(&c->cam, c->width, c->height, style, "svo_submit_export_cloud", nullptr, nullptr);
+int grp_check_cloud_style(const svo_group* c, const svo_cloud_style* style, const svo_stereo_check* check) {
+    const char* who = check ? "svo_submit_export_cloud_checked" : "svo_submit_export_cloud";
+    if (const int rc = check_style(&c->cam, c->width, c->height, style, who, nullptr, nullptr)) return rc;
+    return lr_check_parse(check, true, who, nullptr);
 }
 
 int64_t grp_cloud_points(const svo_group* c, const svo_cloud_style* style) {
@@ -76,21 +78,30 @@ int64_t grp_cloud_points(const svo_group* c, const svo_cloud_style* style) {
 // count and write launches over them (device mode: into the caller's records; host mode: into the block's), one copy
 // of the kept counts, and in host mode the copies out: each slot's kept prefix (compact) or every run of slots that
 // are consecutive in both (organized). The two image tables share the group's argument blocks, half each.
+// A checked job (include/svo_hip.h, "cross-check") has a third table, a third of the blocks each: between the search
+// and the count launch the reverse search fills the chunk's reverse planes (the group's d_lr block) and the check
+// sets the staged disparity of a failing point to -1, which the count and write launches drop as an invalid point.
 int grp_export_cloud(svo_group* c, int what, int mem, const int* seqs, const int* seg, int n, int seq0, const svo_cloud_style* style,
-                     const svo_cloud_dst* dst) {
+                     const svo_stereo_check* check, const svo_cloud_dst* dst) {
     if (const int rc = job_begin(c, "svo_submit_export_cloud")) return rc;
     hipStream_t st = c->stream.get();
     const bool host = mem == SVO_MEM_HOST;
     DenseParams search;
     CloudParams params;
     if (const int rc = cloud_check_style(style, &c->cam, "svo_submit_export_cloud", &search, &params)) return rc;
+    LrCheck lr;
+    if (const int rc = lr_check_parse(check, true, "svo_submit_export_cloud", &lr)) return rc;
+    const size_t reverse = lr.on ? lr_reverse_bytes(c->width, c->height, search.step) : 0;
+    const LrParams lr_params{SVO_DENSE_DISPARITY, search.step, lr.max_lr_diff};
     const int64_t points = (int64_t)(c->width / search.step) * (c->height / search.step);
     const bool organized = params.layout == SVO_CLOUD_ORGANIZED;
     // (SVO_CLOUD_CHUNK_SLOTS: fewer slots per chunk, so that tests reach the chunked path)
-    const size_t chunk = table_tiles("SVO_CLOUD_CHUNK_SLOTS", std::max<size_t>(1, CLOUD_STAGING_BYTES / Staging((size_t)points, host, 1).slot));
+    const size_t chunk = table_tiles("SVO_CLOUD_CHUNK_SLOTS", std::max<size_t>(1, CLOUD_STAGING_BYTES / (Staging((size_t)points, host, 1).slot + reverse)));
     const size_t m_max = std::min<size_t>((size_t)n, chunk);
     const Staging sg((size_t)points, host, m_max);
     if (const int rc = reserve_cloud(c, sg.total, m_max)) return rc;
+    if (lr.on)
+        if (const int rc = c->d_lr.reserve(c, m_max * reverse)) return rc;
     uint8_t* const d_planes = c->d_cloud.p;
     uint8_t* const d_counts = d_planes + m_max * sg.planes;
     uint8_t* const d_records = d_counts + m_max * sg.counts;
@@ -136,12 +147,20 @@ int grp_export_cloud(svo_group* c, int what, int mem, const int* seqs, const int
                                                   [&](const DenseImage* d, int k, hipStream_t s) { launch_dense(d, k, dense_grid, sp, s); });
         auto cloud = group_tile_table<CloudImage>(c, "SVO_CLOUD_TABLE_IMAGES",
                                                   [&](const CloudImage* d, int k, hipStream_t s) { launch_cloud(d, k, cloud_grid, params, s); });
-        const size_t half = c->args.bytes / 2 / 256 * 256;
+        auto checks = group_tile_table<LrImage>(c, "SVO_CLOUD_TABLE_IMAGES", [&](const LrImage* d, int k, hipStream_t s) {
+            launch_dense_reverse(d, k, dense_grid, sp, s);
+            launch_lr_check(d, k, lr_tiles(points), lr_params, s);
+        });
+        const size_t half = c->args.bytes / (lr.on ? 3 : 2) / 256 * 256;   // (a third each of a checked job's three tables)
         dense.cap = std::min({dense.cap, half / sizeof(DenseImage), DENSE_MAX_IMAGES});
         cloud.cap = std::min({cloud.cap, half / sizeof(CloudImage), DENSE_MAX_IMAGES});
         cloud.h = reinterpret_cast<CloudImage*>(reinterpret_cast<uint8_t*>(cloud.h) + half);
         cloud.d = reinterpret_cast<CloudImage*>(reinterpret_cast<uint8_t*>(cloud.d) + half);
+        checks.h = reinterpret_cast<LrImage*>(reinterpret_cast<uint8_t*>(checks.h) + 2 * half);
+        checks.d = reinterpret_cast<LrImage*>(reinterpret_cast<uint8_t*>(checks.d) + 2 * half);
         if (dense.cap < 1 || cloud.cap < 1) return svo_set_error(SVO_ERR_CAPACITY, "svo_submit_export_cloud: the argument blocks hold no image table");
+        // (checked: one cap for all three, so that the tables fill and launch in step: search, check, count and write)
+        if (lr.on) dense.cap = cloud.cap = checks.cap = std::min(dense.cap, cloud.cap);
         dense_plan(sp, (long long)dense_tiles(search, c->width, c->height) * (long long)std::min<size_t>((size_t)shown, dense.cap));
         dense_grid = dense_tiles(sp, c->width, c->height);
         for (int j = 0; j < m; j++) {
@@ -154,12 +173,17 @@ int grp_export_cloud(svo_group* c, int what, int mem, const int* seqs, const int
             uint8_t* counts = d_counts + (size_t)j * sg.counts;
             svo_map_point* out = host ? reinterpret_cast<svo_map_point*>(d_records + (size_t)j * sg.records) : dst->points + e.first_point;
             if (const int rc = dense.add(DenseImage{l.data, r.data, planes, l.stride, r.stride, l.w, l.h, q.cam.baseline, 0})) return rc;
+            if (lr.on)
+                if (const int rc = checks.add(LrImage{l.data, r.data, reinterpret_cast<float*>(c->d_lr.p + (size_t)j * reverse), planes, nullptr,
+                                                      l.stride, r.stride, l.w, l.h, q.cam.baseline, 0}))
+                    return rc;
             CloudImage ci{l.data, planes, planes + points, out, reinterpret_cast<int*>(counts), d_kept + j, l.stride, l.w, l.h,
                           q.cam.baseline, q.cam.fx, q.cam.fy, q.cam.cx, q.cam.cy, {}, reinterpret_cast<float*>(counts + sg.counts - 256)};
             std::memcpy(ci.pose, e.pose, sizeof(ci.pose));
             if (const int rc = cloud.add(ci)) return rc;
         }
         if (const int rc = dense.launch(false)) return rc;
+        if (const int rc = checks.launch(false)) return rc;
         if (const int rc = cloud.launch(false)) return rc;
         HIP_TRY(hipMemcpyAsync(kept, d_kept, sizeof(int) * (size_t)m, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));

@@ -13,6 +13,8 @@ using namespace svo;
 
 namespace {
 
+constexpr size_t LR_STAGING_BYTES = (size_t)256 << 20;   // the reverse planes of one chunk of a checked job at most (one slot always fits)
+
 // the style is checked and the ctx's size has a lattice point at its step
 int check_style(const svo_camera_settings* cam, int width, int height, const svo_disparity_style* style, const char* who, DenseParams* out) {
     DenseParams p;
@@ -25,23 +27,34 @@ int check_style(const svo_camera_settings* cam, int width, int height, const svo
 
 }  // namespace
 
-extern "C" int svo_disparity_size(const svo_camera_settings* cam, int width, int height, const svo_disparity_style* style,
-                                  int* cols, int* rows, int* planes, int64_t* image_bytes) {
+extern "C" int svo_disparity_size_checked(const svo_camera_settings* cam, int width, int height, const svo_disparity_style* style,
+                                          const svo_stereo_check* check, int* cols, int* rows, int* planes, int64_t* image_bytes) {
+    const char* who = check ? "svo_disparity_size_checked" : "svo_disparity_size";
     if (const int rc = check_settings(cam, width, height, 1)) return rc;
     DenseParams p;
-    if (const int rc = check_style(cam, width, height, style, "svo_disparity_size", &p)) return rc;
-    dense_shape(p, width, height, cols, rows, planes, image_bytes);
+    if (const int rc = check_style(cam, width, height, style, who, &p)) return rc;
+    LrCheck lr;
+    if (const int rc = lr_check_parse(check, false, who, &lr)) return rc;
+    dense_shape(p, width, height, cols, rows, planes, image_bytes, lr.on);
     return SVO_OK;
 }
 
-int grp_check_disparity_style(const svo_group* c, const svo_disparity_style* style) {
-    return check_style(&c->cam, c->width, c->height, style, "svo_submit_export_disparity", nullptr);
+extern "C" int svo_disparity_size(const svo_camera_settings* cam, int width, int height, const svo_disparity_style* style,
+                                  int* cols, int* rows, int* planes, int64_t* image_bytes) {
+    return svo_disparity_size_checked(cam, width, height, style, nullptr, cols, rows, planes, image_bytes);
 }
 
-int64_t grp_disparity_bytes(const svo_group* c, const svo_disparity_style* style) {
+int grp_check_disparity_style(const svo_group* c, const svo_disparity_style* style, const svo_stereo_check* check) {
+    const char* who = check ? "svo_submit_export_disparity_checked" : "svo_submit_export_disparity";
+    if (const int rc = check_style(&c->cam, c->width, c->height, style, who, nullptr)) return rc;
+    return lr_check_parse(check, false, who, nullptr);
+}
+
+int64_t grp_disparity_bytes(const svo_group* c, const svo_disparity_style* style, const svo_stereo_check* check) {
     DenseParams p;
     int64_t bytes = 0;
-    if (dense_check_style(style, &c->cam, "svo_submit_export_disparity", &p) == SVO_OK) dense_shape(p, c->width, c->height, nullptr, nullptr, nullptr, &bytes);
+    if (dense_check_style(style, &c->cam, "svo_submit_export_disparity", &p) == SVO_OK)
+        dense_shape(p, c->width, c->height, nullptr, nullptr, nullptr, &bytes, check && check->lr == 1);
     return bytes;
 }
 
@@ -51,15 +64,23 @@ int64_t grp_disparity_bytes(const svo_group* c, const svo_disparity_style* style
 // with one copy: a plain one where the planes fill their image_bytes, else a 2-D one of the planes' bytes per slot, so
 // that the bytes between two slots stay untouched. The image table (one entry per delivered slot) goes through the
 // group's argument blocks, one launch unless it outgrows them.
+// A checked job (include/svo_hip.h, "cross-check") searches disparities whatever the style's value, and then, per
+// chunk of delivered slots whose reverse planes fit the group's d_lr block, runs the reverse search and the check,
+// which appends the lr plane and masks and converts the value plane in place. The stream orders a chunk's check before
+// the next chunk's reverse search, so the chunks share the block without a wait of the host.
 int grp_export_disparity(svo_group* c, int what, int mem, const int* seqs, const int* seg, int n, int seq0,
-                         const svo_disparity_style* style, const svo_disparity_dst* dst) {
+                         const svo_disparity_style* style, const svo_stereo_check* check, const svo_disparity_dst* dst) {
     if (const int rc = job_begin(c, "svo_submit_export_disparity")) return rc;
     hipStream_t st = c->stream.get();
     const bool host = mem == SVO_MEM_HOST;
     DenseParams params;
     if (const int rc = dense_check_style(style, &c->cam, "svo_submit_export_disparity", &params)) return rc;
+    LrCheck lr;
+    if (const int rc = lr_check_parse(check, false, "svo_submit_export_disparity", &lr)) return rc;
+    const LrParams lr_params{params.value, params.step, lr.max_lr_diff};
+    if (lr.on) params.value = SVO_DENSE_DISPARITY;
     int cols, rows, planes; int64_t image_bytes;
-    dense_shape(params, c->width, c->height, &cols, &rows, &planes, &image_bytes);
+    dense_shape(params, c->width, c->height, &cols, &rows, &planes, &image_bytes, lr.on);
     const int64_t used = (int64_t)planes * cols * rows * 4;   // bytes of a slot's planes
     int tiles = dense_tiles(params, c->width, c->height);
     if (host)
@@ -101,7 +122,36 @@ int grp_export_disparity(svo_group* c, int what, int mem, const int* seqs, const
         dense_plan(params, (long long)tiles * (long long)table.m);
         tiles = dense_tiles(params, c->width, c->height);
     }
-    if (const int rc = table.launch(false)) return rc;
+    if (const int rc = table.launch(lr.on)) return rc;    // (checked: the argument blocks are filled again)
+    if (lr.on) {
+        const size_t reverse = lr_reverse_bytes(c->width, c->height, params.step);
+        // (SVO_LR_CHUNK_SLOTS: fewer slots per chunk, so that tests reach the chunked path)
+        const size_t chunk = std::min<size_t>((size_t)n, table_tiles("SVO_LR_CHUNK_SLOTS", std::max<size_t>(1, LR_STAGING_BYTES / reverse)));
+        if (const int rc = c->d_lr.reserve(c, chunk * reverse)) return rc;
+        const DenseParams rp = params;
+        const int lr_grid = lr_tiles((int64_t)cols * rows);
+        auto checks = group_tile_table<LrImage>(c, "SVO_DENSE_TABLE_IMAGES", [&](const LrImage* d, int m, hipStream_t s) {
+            launch_dense_reverse(d, m, tiles, rp, s);
+            launch_lr_check(d, m, lr_grid, lr_params, s);
+        });
+        checks.cap = std::min({checks.cap, DENSE_MAX_IMAGES, chunk});
+        for (int i = 0; i < n; i++) {
+            if (!shown[i]) continue;
+            const Seq& q = c->seqs[seqs[i]];
+            const ImageSet* set = what == SVO_EXPORT_FRAMES ? q.cur_set : q.kfs.back().set;
+            const ImgView& l = set->left[0];
+            const ImgView& r = set->right;
+            float* out = reinterpret_cast<float*>(host ? c->d_dense.p + (int64_t)i * image_bytes
+                                                       : reinterpret_cast<uint8_t*>(dst->values) + dst->segments[seg[i]].offset);
+            if (checks.m == checks.cap)                    // (a chunk is full: its launches go first)
+                if (const int rc = checks.launch(true)) return rc;
+            float* rev = reinterpret_cast<float*>(c->d_lr.p + checks.m * reverse);
+            if (const int rc = checks.add(LrImage{l.data, r.data, rev, out, out + (int64_t)(planes - 1) * cols * rows, l.stride, r.stride, l.w, l.h,
+                                                  q.cam.baseline, 0}))
+                return rc;
+        }
+        if (const int rc = checks.launch(false)) return rc;
+    }
     if (host)
         if (const int rc = copy_out_slots(st, reinterpret_cast<uint8_t*>(dst->values), c->d_dense.p, seg, shown.data(), n, image_bytes, used)) return rc;
     HIP_TRY(hipStreamSynchronize(st));       // delivered: svo_wait means that

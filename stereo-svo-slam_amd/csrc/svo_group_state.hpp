@@ -353,6 +353,9 @@ struct svo_group {
     // replaced when outgrown
     svo::GrowBlock<uint8_t> d_cloud;
     svo::PinnedPtr<int> cloud_counts_host; size_t cloud_counts_cap = 0;
+    // cross-check (a checked grp_export_disparity or grp_export_cloud): the reverse planes of one chunk of a job, made
+    // by the first checked job and replaced when outgrown
+    svo::GrowBlock<uint8_t> d_lr;
     // batched pose-filter updates (grp_pose_updates): the upload block (samples | filter states | start poses |
     // sample offsets) and behind it the download block (filter states | filtered poses) of one job, device and pinned,
     // made by the first such job and replaced when outgrown

@@ -332,8 +332,8 @@ struct DenseParams {
 // what a disparity job, svo_disparity_size and the stage entry check alike; win / search_x / search_y of 0 are taken
 // from cam (null: a 0 is rejected) before the limits are checked, into *out
 int dense_check_style(const svo_disparity_style* style, const svo_camera_settings* cam, const char* who, DenseParams* out);
-// cols, rows, planes and image_bytes of a w x h image pair (any out pointer may be null)
-void dense_shape(const DenseParams& p, int w, int h, int* cols, int* rows, int* planes, int64_t* image_bytes);
+// cols, rows, planes and image_bytes of a w x h image pair (any out pointer may be null); lr = 1: with the lr plane
+void dense_shape(const DenseParams& p, int w, int h, int* cols, int* rows, int* planes, int64_t* image_bytes, int lr = 0);
 // the workgroups of one w x h image: every launch's grid.x is the largest of its images'
 int dense_tiles(const DenseParams& p, int w, int h);
 // the band of a launch that would have so many workgroups with the full band (call before dense_tiles)
@@ -341,6 +341,42 @@ void dense_plan(DenseParams& p, long long workgroups_at_full_band);
 // n images (<= DENSE_MAX_IMAGES), grid (tiles, n)
 constexpr size_t DENSE_MAX_IMAGES = 65535;
 void launch_dense(const DenseImage* d_images, int n, int tiles, const DenseParams& p, hipStream_t stream);
+
+// ------------------------------------------------------------ left-right cross-check (dense.hip's mirrored kernel, lr.hip)
+// One image pair of a checked launch: the two gray planes as in DenseImage; out: the reverse plane, rows x w floats
+// (the disparity of the search from right column xr back into the left image, at [iy][xr]; -1: invalid), written by
+// the reverse launch and read by the check launch; value: cols x rows floats, the forward disparity before the check
+// launch and the value plane after it; lr: the lr plane (cols x rows floats), or null; the baseline of SVO_DENSE_DEPTH.
+struct LrImage {
+    const uint8_t* left;
+    const uint8_t* right;
+    float* out;
+    float* value;
+    float* lr;
+    int left_stride, right_stride, w, h;
+    float baseline;
+    int _pad;
+};
+// what a check launch computes: value SVO_DENSE_DEPTH converts the surviving disparities; max_lr_diff 0: report only
+struct LrParams {
+    int value, step;
+    float max_lr_diff;
+};
+// a checked svo_stereo_check (null: off): on, and the tolerance. cloud: max_lr_diff 0 with lr = 1 is rejected
+struct LrCheck {
+    int on = 0;
+    float max_lr_diff = 0.f;
+};
+int lr_check_parse(const svo_stereo_check* check, bool cloud, const char* who, LrCheck* out);
+// the bytes of one image's reverse plane (a multiple of 256)
+inline size_t lr_reverse_bytes(int w, int h, int step) { return ((size_t)(h / step) * (size_t)w * 4 + 255) / 256 * 256; }
+// the reverse search of n images (<= DENSE_MAX_IMAGES): the grid of launch_dense over the same images and params
+// (value and cost of p are not read: the plane holds disparities)
+void launch_dense_reverse(const LrImage* d_images, int n, int tiles, const DenseParams& p, hipStream_t stream);
+// the check of n images, grid (lr_tiles of the largest lattice, n)
+constexpr int LR_TILE = 1024;
+constexpr int lr_tiles(int64_t points) { return (int)((points + LR_TILE - 1) / LR_TILE); }
+void launch_lr_check(const LrImage* d_images, int n, int tiles, const LrParams& p, hipStream_t stream);
 
 // ------------------------------------------------------------ dense point clouds (cloud.hip)
 // One image of a launch: the left plane (the gray of a record), the disparity and cost planes of a search over its

@@ -43,6 +43,9 @@ SYMBOLS = (
     "svo_view_size", "svo_submit_export_views", "svo_export_views", "svo_render_views",
     "svo_disparity_size", "svo_submit_export_disparity", "svo_export_disparity", "svo_dense_disparity",
     "svo_cloud_size", "svo_submit_export_cloud", "svo_export_cloud", "svo_cloud_points",
+    "svo_disparity_size_checked", "svo_submit_export_disparity_checked", "svo_export_disparity_checked",
+    "svo_dense_disparity_checked", "svo_submit_export_cloud_checked", "svo_export_cloud_checked",
+    "svo_cloud_points_checked",
     "svo_scene_size", "svo_scene_look_at", "svo_scene_frustum", "svo_submit_export_scenes", "svo_export_scenes",
     "svo_render_scene",
     "svo_ar_size", "svo_ar_camera_of_pose", "svo_submit_export_ar", "svo_export_ar", "svo_render_ar",
@@ -422,11 +425,29 @@ def disparity_style(value=DENSE_DISPARITY, step=1, win=0, search_x=0, search_y=0
     return DisparityStyle(int(value), int(step), int(win), int(search_x), int(search_y), int(bool(cost)))
 
 
-def disparity_size(cam, width, height, style):
-    """svo_disparity_size (host only): (cols, rows, planes, image_bytes) of one slot of a disparity job with `style`."""
+class StereoCheck(C.Structure):
+    """svo_stereo_check (include/svo_hip.h, "cross-check"): the left-right check of a checked disparity or cloud job."""
+    _fields_ = [("lr", C.c_int32), ("max_lr_diff", C.c_float), ("_reserved", C.c_int32 * 6)]
+
+
+assert C.sizeof(StereoCheck) == 32
+
+
+def stereo_check(lr=True, max_lr_diff=0.0):
+    """a StereoCheck; max_lr_diff of 0: report only (the lr plane; a cloud needs a tolerance > 0)"""
+    return StereoCheck(int(bool(lr)), float(max_lr_diff))
+
+
+def disparity_size(cam, width, height, style, check=None):
+    """svo_disparity_size (host only): (cols, rows, planes, image_bytes) of one slot of a disparity job with `style`;
+    check: a StereoCheck (svo_disparity_size_checked), or None."""
     cols, rows, planes, nbytes = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int64(0)
-    _check(lib().svo_disparity_size(C.byref(cam), int(width), int(height), C.byref(style), C.byref(cols), C.byref(rows),
-                                    C.byref(planes), C.byref(nbytes)))
+    if check is None:
+        _check(lib().svo_disparity_size(C.byref(cam), int(width), int(height), C.byref(style), C.byref(cols),
+                                        C.byref(rows), C.byref(planes), C.byref(nbytes)))
+    else:
+        _check(lib().svo_disparity_size_checked(C.byref(cam), int(width), int(height), C.byref(style), C.byref(check),
+                                                C.byref(cols), C.byref(rows), C.byref(planes), C.byref(nbytes)))
     return cols.value, rows.value, planes.value, nbytes.value
 
 
@@ -1050,16 +1071,21 @@ class Handle:
             arr[i].baseline = float(baseline)
         return len(srcs), arr, (C.c_int64 * max(len(srcs), 1))(*[int(o) for o in offsets]), srcs
 
-    def dense_disparity_packed(self, packed, style, values):
+    def dense_disparity_packed(self, packed, style, values, check=None):
         p = values.data_ptr() if isinstance(values, torch.Tensor) else int(values)
-        _check(lib().svo_dense_disparity(self._h, packed[0], packed[1], packed[2], C.byref(style), C.c_void_p(p)))
+        if check is None:
+            _check(lib().svo_dense_disparity(self._h, packed[0], packed[1], packed[2], C.byref(style), C.c_void_p(p)))
+        else:
+            _check(lib().svo_dense_disparity_checked(self._h, packed[0], packed[1], packed[2], C.byref(style),
+                                                     C.byref(check), C.c_void_p(p)))
 
-    def dense_disparity(self, srcs, offsets, style, values):
+    def dense_disparity(self, srcs, offsets, style, values, check=None):
         """svo_dense_disparity: dense disparity or depth planes of `style` (a DisparityStyle with win, search_x and
         search_y given). srcs: per image pair (left, right, baseline) with left / right ((data address or uint8
         device tensor [H, W]), width, height, stride); offsets[i]: the byte of `values` (a float32 device tensor, or
-        a raw device address) the planes of pair i start at. Complete on return."""
-        self.dense_disparity_packed(self.pack_dense(srcs, offsets), style, values)
+        a raw device address) the planes of pair i start at. check: a StereoCheck (svo_dense_disparity_checked: the
+        lr plane follows the others), or None. Complete on return."""
+        self.dense_disparity_packed(self.pack_dense(srcs, offsets), style, values, check)
 
     def pack_cloud(self, srcs, first):
         """the argument arrays of cloud_points, built once (keeps Python out of a timed loop)"""
@@ -1072,18 +1098,23 @@ class Handle:
             arr[i].pose = (C.c_float * 6)(*[float(v) for v in pose])
         return len(srcs), arr, (C.c_int64 * max(len(srcs), 1))(*[int(o) for o in first]), srcs
 
-    def cloud_points_packed(self, packed, style, points, counts=None):
+    def cloud_points_packed(self, packed, style, points, counts=None, check=None):
         p = points.data_ptr() if isinstance(points, torch.Tensor) else int(points)
         c = None if counts is None else C.c_void_p(counts.data_ptr() if isinstance(counts, torch.Tensor) else int(counts))
-        _check(lib().svo_cloud_points(self._h, packed[0], packed[1], packed[2], C.byref(style), C.c_void_p(p), c))
+        if check is None:
+            _check(lib().svo_cloud_points(self._h, packed[0], packed[1], packed[2], C.byref(style), C.c_void_p(p), c))
+        else:
+            _check(lib().svo_cloud_points_checked(self._h, packed[0], packed[1], packed[2], C.byref(style), C.byref(check),
+                                                  C.c_void_p(p), c))
 
-    def cloud_points(self, srcs, first, style, points, counts=None):
+    def cloud_points(self, srcs, first, style, points, counts=None, check=None):
         """svo_cloud_points: the coloured 3-D points of `style` (a CloudStyle with win, search_x and search_y given).
         srcs: per image pair (left, right, rig, pose) with left / right ((data address or uint8 device tensor [H, W]),
         width, height, stride), rig a mapping with baseline, fx, fy, cx, cy and pose six floats; first[i]: the record
         of `points` (a device tensor of 16-byte records, or a raw device address) the records of pair i start at;
-        counts: an int32 device tensor [n] (or address) for the kept counts, or None. Complete on return."""
-        self.cloud_points_packed(self.pack_cloud(srcs, first), style, points, counts)
+        counts: an int32 device tensor [n] (or address) for the kept counts, or None. check: a StereoCheck
+        (svo_cloud_points_checked: failing points are dropped), or None. Complete on return."""
+        self.cloud_points_packed(self.pack_cloud(srcs, first), style, points, counts, check)
 
     def render_scene(self, srcs, cameras, offsets, style, pixels):
         """svo_render_scene: the viewer's scene of keyframe sets and lines as images of `style` (a SceneStyle). srcs:

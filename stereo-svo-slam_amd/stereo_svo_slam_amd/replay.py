@@ -27,7 +27,9 @@ as binary PPM files, DIR/000000_keyframe.ppm (the last keyframe, a marker per ke
 current frame): the gray image the tracker worked on, which with --gpu-rectify / --gpu-ingest only the GPU has seen.
 The text overlay and the x2 resize of the window are not drawn.
 --dump-disparity DIR [--disparity-step S] [--disparity-depth] writes per frame DIR/000000_disparity.npy: the dense
-disparity (or depth) map of the frame's rectified pair at every S-th pixel.
+disparity (or depth) map of the frame's rectified pair at every S-th pixel. With --disparity-lr D the map is
+cross-checked left-right and the file is [3, rows, cols]: the value (invalid where the two searches differ by more than
+D; D = 0 only reports), the cost and the lr plane. --cloud-lr D drops such points from the clouds of --dump-cloud.
 --dump-cloud DIR [--cloud-step S] [--cloud-max-depth Z] writes, whenever the newest keyframe changes,
 DIR/kf000000_cloud.ply: the dense coloured point cloud of that keyframe in the world frame at every S-th pixel (binary
 little-endian PLY, x y z float and red green blue uchar), so that the files of a run together are a dense map of it.
@@ -410,7 +412,7 @@ class Replay:
     def __init__(self, settings, device=0, time_trace=False, fast=False, rectify_maps=None, input_format=None,
                  gpu_imu=False, dump_views=None, dump_scene=None, calibration=None, keyframe_window=None, dump_ar=None,
                  ar_box=AR_BOX, ar_at=hip_lib.AR_AT, dump_disparity=None, disparity_step=4, disparity_depth=False,
-                 dump_cloud=None, cloud_step=4, cloud_max_depth=0.0):
+                 dump_cloud=None, cloud_step=4, cloud_max_depth=0.0, disparity_lr=None, cloud_lr=None):
         """fast=False keeps the library default: the reference-order Gauss-Newton (bit-exact traces).
         rectify_maps = (left maps, right maps): the frames fed are raw and are rectified on the GPU.
         calibration = (left, right) CameraCalibrations: the same, with the maps built on the GPU as well.
@@ -428,12 +430,16 @@ class Replay:
         dump_cloud: a directory that receives, whenever the newest keyframe id changes, that keyframe's dense point cloud
         in the world frame (get_cloud of "last_keyframes" at the lattice cloud_step, points deeper than cloud_max_depth
         dropped; 0: none dropped) as kfNNNNNN_cloud.ply (write_ply), likewise.
+        disparity_lr: None, or the tolerance of the left-right cross-check of dump_disparity (0: report only); the file
+        is then [3, rows, cols]: value, cost, lr. cloud_lr: None, or the tolerance (> 0) of the cross-check of dump_cloud.
         keyframe_window: the retired keyframes the tracker keeps (StereoSlamBatch.set_keyframe_window); None: all."""
         self.settings = settings
         self.dump_views, self.dump_scene, self.dump_ar = dump_views, dump_scene, dump_ar
         self.ar_objects = ar_objects(ar_box, ar_at)
         self.dump_disparity, self.disparity_step, self.disparity_depth = dump_disparity, int(disparity_step), bool(disparity_depth)
         self.dump_cloud, self.cloud_step, self.cloud_max_depth, self._cloud_kf = dump_cloud, int(cloud_step), float(cloud_max_depth), -1
+        self.disparity_lr = None if disparity_lr is None else float(disparity_lr)
+        self.cloud_lr = None if cloud_lr is None else float(cloud_lr)
         for d in (dump_views, dump_scene, dump_ar, dump_disparity, dump_cloud):
             if d:
                 os.makedirs(d, exist_ok=True)
@@ -502,14 +508,21 @@ class Replay:
             if img is not None:
                 write_ppm(os.path.join(self.dump_ar, f"{len(self.cumulative) - 1:06d}_ar.ppm"), img)
         if self.dump_disparity:
-            planes = self.slam.get_disparity(value="depth" if self.disparity_depth else "disparity", step=self.disparity_step)
+            value = "depth" if self.disparity_depth else "disparity"
+            if self.disparity_lr is None:
+                planes = self.slam.get_disparity(value=value, step=self.disparity_step)
+            else:
+                planes = self.slam.get_disparity(value=value, step=self.disparity_step, cost=True,
+                                                 lr_check=self.disparity_lr if self.disparity_lr > 0 else True)
             if planes is not None:
-                np.save(os.path.join(self.dump_disparity, f"{len(self.cumulative) - 1:06d}_disparity.npy"), planes[0])
+                np.save(os.path.join(self.dump_disparity, f"{len(self.cumulative) - 1:06d}_disparity.npy"),
+                        planes[0] if self.disparity_lr is None else planes)
         if self.dump_cloud:
             kf = int(self.slam.stats().n_keyframes) - 1
             if kf != self._cloud_kf:
                 self._cloud_kf = kf
-                points = self.slam.get_cloud("last_keyframes", step=self.cloud_step, max_depth=self.cloud_max_depth)
+                points = self.slam.get_cloud("last_keyframes", step=self.cloud_step, max_depth=self.cloud_max_depth,
+                                             lr_check=self.cloud_lr)
                 if points is not None:
                     write_ply(os.path.join(self.dump_cloud, f"kf{kf:06d}_cloud.ply"), points)
         if self.time_trace:                       # like PRINT_TIME_TRACE of the reference
@@ -575,10 +588,15 @@ def build_parser():
                          "(float32 [rows, cols]; -1 where the search window leaves the image)")
     ap.add_argument("--disparity-step", metavar="S", type=int, default=4, help="lattice of --dump-disparity: every S-th pixel, 1 .. 16")
     ap.add_argument("--disparity-depth", action="store_true", help="--dump-disparity writes depth, baseline / disparity (0: none)")
+    ap.add_argument("--disparity-lr", metavar="D", type=float, default=None,
+                    help="--dump-disparity cross-checks left-right and writes [3, rows, cols]: the value (invalid where the "
+                         "two searches differ by more than D; 0: report only), the cost and the lr plane")
     ap.add_argument("--dump-cloud", metavar="DIR",
                     help="write DIR/kfNNNNNN_cloud.ply whenever the newest keyframe changes: its dense coloured point cloud in "
                          "the world frame (binary little-endian PLY: x y z float, red green blue uchar)")
     ap.add_argument("--cloud-step", metavar="S", type=int, default=4, help="lattice of --dump-cloud: every S-th pixel, 1 .. 16")
+    ap.add_argument("--cloud-lr", metavar="D", type=float, default=None,
+                    help="--dump-cloud drops points whose left-right cross-check differs by more than D (> 0)")
     ap.add_argument("--cloud-max-depth", metavar="Z", type=float, default=0.0,
                     help="--dump-cloud drops points deeper than Z in the camera frame (0: none)")
     ap.add_argument("--frames", type=int, default=100)
@@ -647,7 +665,7 @@ def main(argv=None):
                 ar_box=args.ar_box, ar_at=tuple(float(x) for x in args.ar_at.split(",")),
                 keyframe_window=args.keyframe_window, dump_disparity=args.dump_disparity, disparity_step=args.disparity_step,
                 disparity_depth=args.disparity_depth, dump_cloud=args.dump_cloud, cloud_step=args.cloud_step,
-                cloud_max_depth=args.cloud_max_depth)
+                cloud_max_depth=args.cloud_max_depth, disparity_lr=args.disparity_lr, cloud_lr=args.cloud_lr)
     for k, (left, right, t) in enumerate(frames):
         rp.feed(left, right, t, None if gyro is None else gyro[gyro[:, 0] == k, 1:4])
     rows = rp.rows()

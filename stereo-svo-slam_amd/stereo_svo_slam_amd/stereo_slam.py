@@ -328,14 +328,16 @@ class Disparities:
     (hip_lib.DISPARITY_SEGMENT_DTYPE, one per named slot), `values` [slots, planes, rows, cols] float32 (a strided view
     of the buffer: numpy over pinned memory in host mode, a torch tensor on the ctx's device in device mode; a slot
     whose status is DISPARITY_NONE keeps what the buffer held) and planes(i). cols, rows, planes, image_bytes: the shape
-    of every slot of the job (svo_disparity_size)."""
+    of every slot of the job (svo_disparity_size). A checked job (check: a hip_lib.StereoCheck that is on) goes through
+    svo_submit_export_disparity_checked; its last plane is the lr plane, lr(i)."""
 
-    def __init__(self, slam, what, seqs, style, device):
+    def __init__(self, slam, what, seqs, style, device, check=None):
         self._slam = slam
         self.what, self.style, self.device_mode = int(what), style, bool(device)
+        self.check = check if check is not None and check.lr else None
         self.seqs = None if seqs is None else [int(s) for s in seqs]
         n = self._n = slam.n if seqs is None else len(self.seqs)
-        self.cols, self.rows, self.n_planes, self.image_bytes = slam.disparity_size(style)
+        self.cols, self.rows, self.n_planes, self.image_bytes = slam.disparity_size(style, self.check)
         self.capacity = n * self.image_bytes
         self._seg = np.zeros(max(n, 1), hip_lib.DISPARITY_SEGMENT_DTYPE)
         self.segments = self._seg[:n]
@@ -356,8 +358,13 @@ class Disparities:
         slam = self._slam
         if self.device_mode:
             torch.cuda.current_stream(slam.device).synchronize()     # (nothing of the caller's is still using the tensor)
-        _check(lib().svo_submit_export_disparity(slam._ctx, self.what, self._seq_arr, self._n, C.byref(self.style),
-                                                 C.byref(self._dst), hip_lib.MEM_DEVICE if self.device_mode else hip_lib.MEM_HOST))
+        mem = hip_lib.MEM_DEVICE if self.device_mode else hip_lib.MEM_HOST
+        if self.check is None:
+            _check(lib().svo_submit_export_disparity(slam._ctx, self.what, self._seq_arr, self._n, C.byref(self.style),
+                                                     C.byref(self._dst), mem))
+        else:
+            _check(lib().svo_submit_export_disparity_checked(slam._ctx, self.what, self._seq_arr, self._n, C.byref(self.style),
+                                                             C.byref(self.check), C.byref(self._dst), mem))
         return self
 
     def wait(self):
@@ -371,17 +378,25 @@ class Disparities:
             return None
         return self.values[i]
 
+    def lr(self, i):
+        """the lr plane of named slot i of a checked job ([rows, cols]: -1 invalid, -2 no way back, else the
+        left-right difference); None for an unchecked job or a slot whose status is DISPARITY_NONE"""
+        planes = self.planes(i)
+        return None if planes is None or self.check is None else planes[-1]
+
 
 class Clouds:
     """One svo_submit_export_cloud: owns the buffers the library writes. After wait(): `segments`
     (hip_lib.CLOUD_SEGMENT_DTYPE, one per named slot), points(i) and, in the organized layout, organized(i).
     `points_buffer` is a uint8 [capacity, 16] tensor: pinned memory in host mode, on the ctx's device in device mode
     (points(i) / organized(i) then copy the slot's records to the host). cols, rows, points_per_slot: the lattice of
-    every slot of the job (svo_cloud_size)."""
+    every slot of the job (svo_cloud_size). A checked job (check: a hip_lib.StereoCheck that is on) goes through
+    svo_submit_export_cloud_checked."""
 
-    def __init__(self, slam, what, seqs, style, device):
+    def __init__(self, slam, what, seqs, style, device, check=None):
         self._slam = slam
         self.what, self.style, self.device_mode = int(what), style, bool(device)
+        self.check = check if check is not None and check.lr else None
         self.seqs = None if seqs is None else [int(s) for s in seqs]
         n = self._n = slam.n if seqs is None else len(self.seqs)
         self.cols, self.rows, self.points_per_slot = slam.cloud_size(style)
@@ -399,8 +414,13 @@ class Clouds:
         slam = self._slam
         if self.device_mode:
             torch.cuda.current_stream(slam.device).synchronize()     # (nothing of the caller's is still using the tensor)
-        _check(lib().svo_submit_export_cloud(slam._ctx, self.what, self._seq_arr, self._n, C.byref(self.style),
-                                             C.byref(self._dst), hip_lib.MEM_DEVICE if self.device_mode else hip_lib.MEM_HOST))
+        mem = hip_lib.MEM_DEVICE if self.device_mode else hip_lib.MEM_HOST
+        if self.check is None:
+            _check(lib().svo_submit_export_cloud(slam._ctx, self.what, self._seq_arr, self._n, C.byref(self.style),
+                                                 C.byref(self._dst), mem))
+        else:
+            _check(lib().svo_submit_export_cloud_checked(slam._ctx, self.what, self._seq_arr, self._n, C.byref(self.style),
+                                                         C.byref(self.check), C.byref(self._dst), mem))
         return self
 
     def wait(self):
@@ -874,23 +894,33 @@ class StereoSlamBatch:
         """submit_views + wait"""
         return self.submit_views(what, seqs, **kw).wait()
 
-    def disparity_size(self, style):
-        """svo_disparity_size: (cols, rows, planes, image_bytes) of one slot of a disparity job with `style` in this ctx"""
-        return hip_lib.disparity_size(self.cam, self.width, self.height, style)
+    def disparity_size(self, style, check=None):
+        """svo_disparity_size: (cols, rows, planes, image_bytes) of one slot of a disparity job with `style` (and
+        `check`, a hip_lib.StereoCheck or None) in this ctx"""
+        return hip_lib.disparity_size(self.cam, self.width, self.height, style, check)
+
+    @staticmethod
+    def _stereo_check(lr_check):
+        """lr_check of submit_disparity / submit_cloud as a hip_lib.StereoCheck: None or False: off (the unchecked
+        entry); True: report only; a number: the tolerance max_lr_diff"""
+        if lr_check is None or lr_check is False:
+            return None
+        return hip_lib.stereo_check(True, 0.0 if lr_check is True else float(lr_check))
 
     def submit_disparity(self, what="frames", seqs=None, value="disparity", step=1, win=0, search_x=0, search_y=0,
-                         cost=False, device=False, style=None):
+                         cost=False, device=False, style=None, lr_check=None):
         """svo_submit_export_disparity: queue a dense disparity (value="disparity") or depth ("depth") map of the
         current frames (what="frames") or newest keyframes ("last_keyframes") of the slots `seqs` (None: all, in
         order) behind what was submitted so far; nothing is waited for. step: the lattice (1 .. 16); win, search_x,
         search_y: 0 takes the ctx's settings; cost: a second plane with the minimum SSD; style: a
-        hip_lib.DisparityStyle instead of all these. Returns a Disparities, valid after its wait() (or the ctx's);
+        hip_lib.DisparityStyle instead of all these; lr_check: the left-right cross-check (True: the lr plane is
+        appended; a tolerance: values that differ by more are set invalid as well; default off). Returns a Disparities, valid after its wait() (or the ctx's);
         its submit() queues the same job again into the same buffers."""
         if isinstance(what, str):
             what = hip_lib.EXPORT_WHAT.index(what)
         if style is None:
             style = hip_lib.disparity_style(value, step, win, search_x, search_y, cost)
-        return Disparities(self, what, seqs, style, device).submit()
+        return Disparities(self, what, seqs, style, device, self._stereo_check(lr_check)).submit()
 
     def export_disparity(self, what="frames", seqs=None, **kw):
         """submit_disparity + wait"""
@@ -901,18 +931,19 @@ class StereoSlamBatch:
         return hip_lib.cloud_size(self.cam, self.width, self.height, style)
 
     def submit_cloud(self, what="frames", seqs=None, step=1, win=0, search_x=0, search_y=0, frame="world", layout="compact",
-                     min_disparity=0.0, max_depth=0.0, max_mean_cost=0.0, device=False, style=None):
+                     min_disparity=0.0, max_depth=0.0, max_mean_cost=0.0, device=False, style=None, lr_check=None):
         """svo_submit_export_cloud: queue a dense coloured point cloud of the current frames (what="frames") or newest
         keyframes ("last_keyframes") of the slots `seqs` (None: all, in order) behind what was submitted so far;
         nothing is waited for. step, win, search_x, search_y: as submit_disparity; frame: "world" or "camera";
         layout: "compact" or "organized"; min_disparity, max_depth, max_mean_cost: the filter (0: off); style: a
-        hip_lib.CloudStyle instead of all these. Returns a Clouds, valid after its wait() (or the ctx's); its submit()
+        hip_lib.CloudStyle instead of all these; lr_check: a tolerance > 0 drops the points that fail the left-right
+        cross-check (default off). Returns a Clouds, valid after its wait() (or the ctx's); its submit()
         queues the same job again into the same buffers."""
         if isinstance(what, str):
             what = hip_lib.EXPORT_WHAT.index(what)
         if style is None:
             style = hip_lib.cloud_style(step, win, search_x, search_y, frame, layout, min_disparity, max_depth, max_mean_cost)
-        return Clouds(self, what, seqs, style, device).submit()
+        return Clouds(self, what, seqs, style, device, self._stereo_check(lr_check)).submit()
 
     def export_cloud(self, what="frames", seqs=None, **kw):
         """submit_cloud + wait"""

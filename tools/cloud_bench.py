@@ -92,14 +92,23 @@ def kernel_leg(args, device, cfg, lefts, rights):
                     cloud()
                 finally:
                     del os.environ["SVO_CLOUD_SKIP_SEARCH"]
+            checked, kept_checked = None, None
+            if args.checked is not None:                     # (the left-right cross-check of DESIGN 4.19 at that tolerance)
+                check = hip_lib.stereo_check(True, args.checked)
+                checked = lambda: h.cloud_points_packed(packed, style, points, counts, check)
+                checked()
+                torch.cuda.synchronize(device)
+                kept_checked = int(counts.sum().item())
             cloud(); dense(); kernels()                      # warm-up of the legs
             torch.cuda.synchronize(device)
             kept = int(counts.sum().item())
-            t_cloud, t_dense, t_kernels = [], [], []
+            t_cloud, t_dense, t_kernels, t_checked = [], [], [], []
             for _ in range(args.repeats):                   # the legs alternate
                 t_cloud.append(event_ms(cloud))
                 t_dense.append(event_ms(dense))
                 t_kernels.append(event_ms(kernels))
+                if checked:
+                    t_checked.append(event_ms(checked))
             c_ms, d_ms, k_ms = (statistics.median(t) / n for t in (t_cloud, t_dense, t_kernels))
             moved = 17 * P + 16 * kept / n                   # per image: both launches read the two planes, one reads the gray
             out["shapes"].append({"step": step, "images": n, "cols": cols, "rows": rows, "kept_fraction": kept / (n * P),
@@ -109,6 +118,10 @@ def kernel_leg(args, device, cfg, lefts, rights):
                                   "cloud_minus_search_ms_per_image": c_ms - d_ms,
                                   "kernels_bytes_per_image": moved, "kernels_bytes_per_s": moved / (k_ms * 1e-3),
                                   "kernels_fraction_of_8TBps": moved / (k_ms * 1e-3) / PEAK_BYTES_PER_S})
+            if checked:
+                out["shapes"][-1].update({"checked_cloud_ms_per_image": statistics.median(t_checked) / n, "checked_cloud_call_ms_all": t_checked,
+                                          "checked_over_cloud": statistics.median(t_checked) / n / c_ms, "max_lr_diff": args.checked,
+                                          "checked_kept_fraction": kept_checked / (n * P)})
             print(json.dumps(out["shapes"][-1]), file=sys.stderr, flush=True)      # (progress)
             del points, planes
     h.close()
@@ -215,6 +228,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--host-repeats", type=int, default=1, help="timed runs of the host path (seconds each at step 1)")
     ap.add_argument("--no-job", action="store_true", help="the kernel leg only")
+    ap.add_argument("--checked", type=float, default=None, metavar="D", help="also time svo_cloud_points_checked at the tolerance D")
     ap.add_argument("--out", default=None, help="also write the JSON result to this file")
     args = ap.parse_args()
     device = torch.device("cuda", 0)

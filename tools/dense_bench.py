@@ -11,7 +11,11 @@ One process, bench.py's rendered `euroc` stereo pairs (752 x 480), the EuRoC set
              pair), on min(images, `--baseline-images`) images. At steps 1 and 2 only every `--baseline-rows`-th
              lattice row is run and the time scaled up by the rows left out: `baseline_rows_run` / `lattice_rows` in
              the JSON say so. The first image's rows are compared with the dense map, bit for bit.
-             Every shape is warmed up first; the two legs alternate, median of `--repeats` each.
+             Every shape is warmed up first; the two legs alternate, median of `--repeats` each. `--no-baseline`
+             leaves it out.
+  checked    with `--checked D`: svo_dense_disparity_checked (the left-right cross-check of DESIGN §4.19 at the tolerance
+             D, two planes) on the same pairs, a third leg alternating with the others. The unchecked figure of the
+             parent commit comes from this tool run with SVO_HIP_LIB set to the parent's library, without --checked.
   job        frames/s over `--steps` queued steps of bench.py's workload without any job and with a device-mode
              step-4 disparity job of every slot queued behind every frame set; legs alternate, median of
              `--pipelined-repeats` each.
@@ -104,13 +108,26 @@ def kernel_leg(args, device, cfg, lefts, rights):
                     rc = lib.svo_ssd_disparity(h._h, C.byref(a), C.byref(b), C.c_void_p(d_kps.data_ptr()), len(kps), win, sx, sy, 1,
                                                C.c_void_p(b_out.data_ptr() + i * len(kps) * 4))
                     assert rc == 0
-            dense(); baseline()                              # warm-up of both legs
+            if args.no_baseline:
+                baseline = lambda: None
+            checked = None
+            if args.checked is not None:
+                check = hip_lib.stereo_check(True, args.checked)
+                dst_c = torch.empty(n * 2 * cols * rows, dtype=torch.float32, device=device)
+                packed_c = h.pack_dense([((l, W, H, l.stride(0)), (r, W, H, r.stride(0)), cfg["baseline"]) for l, r in pairs],
+                                        [i * 2 * cols * rows * 4 for i in range(n)])
+                checked = lambda: h.dense_disparity_packed(packed_c, style, dst_c, check)
+                checked()
+            dense(); baseline()                              # warm-up of the legs
             torch.cuda.synchronize(device)
-            same = bool(torch.equal(dst[:cols * rows].view(rows, cols)[::every], b_out[:len(kps)].view(len(run_rows), cols)))
-            t_dense, t_base = [], []
+            same = None if args.no_baseline else bool(torch.equal(dst[:cols * rows].view(rows, cols)[::every],
+                                                                  b_out[:len(kps)].view(len(run_rows), cols)))
+            t_dense, t_base, t_checked = [], [], []
             for _ in range(args.repeats):                   # the legs alternate
                 t_dense.append(event_ms(dense))
                 t_base.append(event_ms(baseline))
+                if checked:
+                    t_checked.append(event_ms(checked))
             d_ms = statistics.median(t_dense) / n
             b_ms = statistics.median(t_base) / nb * (rows / len(run_rows))
             out["shapes"].append({"step": step, "images": n, "cols": cols, "rows": rows, "candidate_points_per_image": cand,
@@ -120,6 +137,13 @@ def kernel_leg(args, device, cfg, lefts, rights):
                                   "baseline_rows_run": len(run_rows), "lattice_rows": rows,
                                   "baseline_scaled_up": every > 1, "baseline_over_dense": b_ms / d_ms,
                                   "baseline_rows_equal_dense": same})
+            if checked:
+                c_ms = statistics.median(t_checked) / n
+                lr = dst_c.view(n, 2, rows, cols)[:, 1]
+                out["shapes"][-1].update({"checked_ms_per_image": c_ms, "checked_call_ms_all": t_checked, "checked_over_dense": c_ms / d_ms,
+                                          "max_lr_diff": args.checked,
+                                          "failing_fraction": float(((lr < 0) | (lr > args.checked)).float().mean().item())})
+                del dst_c
             print(json.dumps(out["shapes"][-1]), file=sys.stderr, flush=True)      # (progress)
     h.close()
     return out
@@ -175,6 +199,8 @@ def main():
     ap.add_argument("--images", type=lambda t: [int(x) for x in t.split(",")], default=[1, 16, 256])
     ap.add_argument("--baseline-images", type=int, default=4, help="images the per-keypoint baseline runs on at most")
     ap.add_argument("--baseline-rows", type=int, default=8, help="at steps 1 and 2 the baseline runs every n-th lattice row, scaled up")
+    ap.add_argument("--no-baseline", action="store_true", help="leave the per-keypoint baseline out (its fields are then of no use)")
+    ap.add_argument("--checked", type=float, default=None, metavar="D", help="also time svo_dense_disparity_checked at the tolerance D")
     ap.add_argument("--legs", default="256:1,1024:3", help="slots:groups per job leg (groups 0: the ctx's default); '' for none")
     ap.add_argument("--job-step", type=int, default=4)
     ap.add_argument("--loops", type=int, default=64)
