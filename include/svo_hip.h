@@ -1352,6 +1352,99 @@ int svo_export_cloud_checked(svo_ctx *ctx, int what, const int *seqs, int n, con
 int svo_cloud_points_checked(svo_handle *h, int n, const svo_cloud_src *src, const int64_t *first, const svo_cloud_style *style,
                              const svo_stereo_check *check, svo_map_point *points, int32_t *counts);
 
+/* ---- scene clouds: dense clouds ("clouds", "cross-check") drawn in the scene picture ------------
+ * A scene job can draw, beside the elements above, svo_map_point records: the dense cloud of each named slot's frame
+ * or newest keyframe (the LIVE LAYER), records of the caller's in device memory (the EXTRA SPAN), or both.
+ *
+ * The picture. A CLOUD POINT is a svo_map_point record (x, y, z, color[3], flags). It is drawn unless
+ * flags & SVO_CLOUD_DROPPED or flags & style->filter.drop_flags (own_only and min_inliers do not apply: a record has
+ * neither). It follows the `point` rule of "scene" word for word with s = clouds->point_size (the stage entry: its
+ * point_size argument): c = T(x, y, z); dropped unless every c_k is finite and c_2 >= near; u = (f * c_0) / c_2 + cx,
+ * v = (f * c_1) / c_2 + cy; dropped unless |u| < 2^15 and |v| < 2^15; px = floor(u), py = floor(v); it covers the
+ * s x s pixels [px - (s-1)/2, px - (s-1)/2 + s - 1] x [py - (s-1)/2, py - (s-1)/2 + s - 1]. Its depth is c_2, its
+ * colour color[0], color[1], color[2] as r, g, b, its class SVO_SCENE_CLASS_CLOUD = 4:
+ *   key = bits(c_2) << 32 | 4 << 24 | r << 16 | g << 8 | b
+ * so at equal depth a keypoint (class 3) and every line beat a cloud point, and between two cloud points the smaller
+ * colour word wins. No key of "scene" changes: a picture without cloud points is byte for byte the picture of "scene".
+ *
+ * How it is drawn (scene.hip): a splat pass visits every record once, one lane per record, and offers its key with a
+ * 64-bit atomic min to a key plane uint64[rows][cols] of its image in device memory, cleared to all ones before; the
+ * tile kernel then starts from that plane instead of from all ones. The min is an integer min, so the bytes depend on
+ * no order and two runs agree.
+ *
+ * The job. svo_submit_export_scenes_clouds is svo_submit_export_scenes with a svo_scene_clouds. No new job kind: queue
+ * order, segments, "the slot is not changed", the SVO_SCENE_NONE rule (such a slot draws nothing; its info is status =
+ * SVO_CLOUD_NONE, keyframe_id = -1, live_points = 0 and the span's n) and the copy-out are the scene job's. clouds == NULL, or live == 0
+ * with extra == NULL, IS svo_submit_export_scenes: the same launches, bytes, memory and rejections.
+ *   live layer  per named slot exactly the records that svo_submit_export_cloud_checked(what, ..., `cloud` with
+ *               layout = SVO_CLOUD_ORGANIZED, check, ...) delivers for that slot at the same queue position: the same
+ *               planes, rig and pose, the same launches, bit for bit. They go into a staging block of the group and
+ *               are never copied out. A slot the cloud job gives SVO_CLOUD_NONE (LAST_KEYFRAMES without a keyframe)
+ *               shows the picture without a live layer.
+ *   extra span  extra[i] belongs to seqs[i]: n records in device memory, read when the job runs (they stay valid and
+ *               unchanged until svo_wait). A caller shows an accumulated map this way: it keeps compact clouds of
+ *               earlier keyframes, or a svo_export_map result, in one device array and passes it with every job.
+ *   info[i]     of seqs[i]: status mirrors SVO_CLOUD_OK / SVO_CLOUD_NONE of the live layer (NONE with live == 0),
+ *               keyframe_id is the cloud segment's (-1 without a live layer), live_points its kept count,
+ *               extra_points the span's n.
+ * Rejected with SVO_ERR_INVALID and nothing queued: everything svo_submit_export_scenes rejects; with live == 1
+ * everything svo_submit_export_cloud_checked rejects of `cloud` and `check`, cloud.frame != SVO_CLOUD_WORLD,
+ * cloud.layout != 0, a bad `what`; live other than 0 or 1; point_size outside 1 .. 16; a non-zero _reserved; a span
+ * with n < 0, or with n > 0 and a NULL or not 16-byte aligned pointer.
+ * Memory, per group, in blocks of its own made by the first such job, replaced when outgrown and counted in
+ * svo_memory.device_bytes:
+ *   key planes   key_bytes = up256(8 * cols * rows) per slot of a chunk
+ *   live layer   16 * points_per_slot per slot of a chunk, beside what the cloud job itself stages in device mode:
+ *                its slot_bytes ("clouds") and, checked, reverse_bytes ("cross-check"), in the cloud job's blocks
+ *   block        min(named slots of the group, chunk) * (key_bytes + 16 * points_per_slot [live])
+ *   chunk        max(1, 256 MiB / (key_bytes + [live: slot_bytes + 16 * points_per_slot + reverse_bytes])); the
+ *                diagnostic SVO_SCENE_CHUNK_SLOTS lowers it
+ * Per chunk the order on the group's stream is: search, check, cloud write, clear, splat, tile render. The span table
+ * (pieces of 1024 records, one workgroup each) goes through the group's argument blocks like the tile table; the
+ * diagnostic SVO_SCENE_TABLE_SPANS makes it smaller. A job without clouds allocates what it did. */
+enum { SVO_SCENE_CLASS_CLOUD = 4 };
+
+typedef struct svo_scene_span {       /* 16 bytes */
+    const svo_map_point *points;      /* device, 16-byte aligned                                             */
+    int64_t n;                        /* >= 0 records                                                        */
+} svo_scene_span;
+
+typedef struct svo_scene_cloud_info { /* 32 bytes, host, one per named slot                                  */
+    int32_t status;                   /* SVO_CLOUD_OK: a live cloud was drawn; SVO_CLOUD_NONE                */
+    int32_t keyframe_id;              /* LAST_KEYFRAMES: the keyframe used; else -1                          */
+    int32_t live_points;              /* the live layer's kept count                                         */
+    int32_t _pad;
+    int64_t extra_points;             /* the extra span's n                                                  */
+    int64_t _pad2;
+} svo_scene_cloud_info;
+
+typedef struct svo_scene_clouds {     /* copied at submit (the spans too; not the records)                   */
+    int32_t live;                     /* 0: no live layer, 1: the dense cloud of `what` of each named slot   */
+    int32_t what;                     /* SVO_EXPORT_FRAMES / SVO_EXPORT_LAST_KEYFRAMES                       */
+    svo_cloud_style  cloud;           /* frame SVO_CLOUD_WORLD, layout 0; step, window, search, the filters  */
+    svo_stereo_check check;           /* as in svo_submit_export_cloud_checked                               */
+    int32_t point_size;               /* 1 .. 16                                                             */
+    int32_t _reserved[3];             /* 0                                                                   */
+    const svo_scene_span *extra;      /* NULL, or ONE PER NAMED SLOT (n = 0: none)                           */
+    svo_scene_cloud_info *info;       /* NULL, or host, one per named slot; valid until svo_wait             */
+} svo_scene_clouds;
+
+int svo_submit_export_scenes_clouds(svo_ctx *ctx, const int *seqs, int n, const svo_scene_style *style,
+                                    const svo_scene_clouds *clouds, const svo_scene_camera *cameras,
+                                    const svo_scene_dst *dst, int mem);
+int svo_export_scenes_clouds(svo_ctx *ctx, const int *seqs, int n, const svo_scene_style *style,
+                             const svo_scene_clouds *clouds, const svo_scene_camera *cameras,
+                             const svo_scene_dst *dst, int mem);   /* submit + wait */
+/* stage entry: svo_render_scene with cloud points. Image i also shows the n_spans[i] spans that follow those of image
+ * i - 1 in `spans` (host arrays; n_spans[i] >= 0; spans may be NULL if every count is 0), as cloud points of
+ * `point_size`. The key planes of the images that have a record live in the handle's workspace; the span table is
+ * chunked when the diagnostic SVO_SCENE_TABLE_SPANS bounds it. With no record anywhere it is svo_render_scene: the
+ * same launches and bytes. Rejected as svo_render_scene rejects, and: point_size outside 1 .. 16, a negative count, a
+ * span with n < 0 or with n > 0 and a NULL or not 16-byte aligned pointer. Complete on return. */
+int svo_render_scene_clouds(svo_handle *h, int n, const svo_scene_src *src, const svo_scene_span *spans,
+                            const int32_t *n_spans, const svo_scene_camera *cameras, const int64_t *offset,
+                            const svo_scene_style *style, int32_t point_size, uint8_t *pixels);
+
 /* ---- snapshots: the sequence state of a slot saved, loaded, moved between ctxs ------------
  * The reference has no checkpoint or resume (a StereoSlam lives and dies with its process). A snapshot is
  * everything the next frame of a slot depends on and everything its getters return, so that a sequence saved

@@ -21,9 +21,21 @@
 //     as one 16-byte store, RGB as three dwords where the address allows, else pixel by pixel / byte by byte.
 //
 // The min makes the bytes independent of the order the lanes arrive in: two runs give the same image. Every tile
-// re-projects every element of its image, which is most of the kernel's time (DESIGN 4.12 has the figures). A
-// projection pass into a per-image buffer would trade that for a second launch and a buffer per job; it has not been
-// built or measured, so the simpler form stands on reasoning only.
+// re-projects every element of its image, which is most of the kernel's time (DESIGN 4.12 has the figures). That is
+// fine for the few thousand keypoints of a map and not for a dense cloud of 10^5 records per image.
+//
+// Cloud points (include/svo_hip.h, "scene clouds") therefore take a projection pass of their own, scene_splat_kernel:
+// the host cuts every span of svo_map_point records into pieces of SCENE_SPLAT_PIECE records (SceneSpan), one
+// workgroup each. A lane loads its 16-byte record in one load, tests the flags, transforms and projects it with the
+// device functions of step 2 (the arithmetic is the same by construction), clips its square to the image and offers
+// its key with a 64-bit global atomic min, result unused, to the image's key plane uint64[h][w], which the host
+// clears to all ones on the same stream beforehand. scene_render_kernel<true> then seeds its LDS plane in step 1
+// from that plane (all ones for the tile's pixels outside the image and for an image without a plane) and goes on
+// unchanged; scene_render_kernel<false> is the kernel as it was and runs whenever no image of a launch has a plane.
+// Every record is visited once per image, not once per tile.
+//
+// Bounds of the splat pass: a plane address is y * w + x with x, y already clipped to [0, w) x [0, h); of a piece
+// exactly records [0, n) are read; no float becomes an integer before scene_project's 2^15 rule has passed.
 //
 // Bounds: every LDS index and every global address follows from integers already clipped to the tile, which the
 // host clamps to the image. A projected coordinate only becomes an integer after |u|, |v| < 2^15 is known, so
@@ -39,6 +51,7 @@ namespace svo {
 
 constexpr int SCENE_THREADS = 256;
 static_assert(SCENE_TILE_W == 64 && SCENE_TILE_H * 16 == SCENE_THREADS, "4 pixels of a 64-pixel row per lane");
+static_assert(sizeof(svo_map_point) == 16 && sizeof(SceneSpan) == 16 && SCENE_SPLAT_PIECE % SCENE_THREADS == 0, "a record is one 16-byte load");
 static_assert(sizeof(svo_scene_line) == 32 && sizeof(svo_scene_camera) == 64 && sizeof(svo_scene_segment) == 64, "record sizes of the C ABI");
 constexpr uint32_t SCENE_FLAG_BITS = SVO_IGNORE_DURING_REFINEMENT | SVO_IGNORE_COMPLETELY | SVO_IGNORE_TEMPORARY;
 constexpr int SCENE_MAX_SIDE = 4096;
@@ -125,8 +138,44 @@ __device__ __forceinline__ void scene_offer(unsigned long long* keys, int x, int
     atomicMin(&keys[y * SCENE_TILE_W + x], (unsigned long long)__float_as_uint(depth) << 32 | low);
 }
 
+// One lane per record of a piece; SCENE_SPLAT_PIECE / SCENE_THREADS records per lane, a wave's 64 records adjacent.
+__global__ __launch_bounds__(SCENE_THREADS) void scene_splat_kernel(const SceneSpan* __restrict__ spans,
+                                                                    const SceneImage* __restrict__ images,
+                                                                    unsigned long long* const* __restrict__ planes, const SceneParams p) {
+    const SceneSpan sp = G(spans)[blockIdx.x];
+    const SceneImage im = G(images)[sp.image];
+    SVO_GP(unsigned long long) plane = G(G(planes)[sp.image]);
+    SVO_GP(const uint4) rec = (SVO_GP(const uint4))G(sp.points);
+    const int s = p.point_size, w = im.w, h = im.h;
+    for (int k = threadIdx.x; k < sp.n; k += SCENE_THREADS) {
+        const uint4 q = rec[k];                            // x, y, z, r | g << 8 | b << 16 | flags << 24
+        const uint32_t flags = q.w >> 24;
+        // (the transform comes before the flags test so that all four words are needed at once: one 16-byte load,
+        // not a dword for the flags and three more behind the branch)
+        float c[3];
+        const bool finite = scene_transform(im.cam, __uint_as_float(q.x), __uint_as_float(q.y), __uint_as_float(q.z), c);
+        if ((flags & (SVO_CLOUD_DROPPED | p.filter.drop_flags)) || !finite) continue;
+        if (!(c[2] >= im.cam.near)) continue;
+        int X, Y;
+        if (!scene_project(im.cam, c, X, Y)) continue;
+        // the square, clipped to the image
+        int xa = X - (s - 1) / 2, ya = Y - (s - 1) / 2;
+        int xb = xa + s - 1, yb = ya + s - 1;
+        xa = max(xa, 0); xb = min(xb, w - 1);
+        ya = max(ya, 0); yb = min(yb, h - 1);
+        if (xa > xb || ya > yb) continue;
+        const uint32_t low = (uint32_t)SVO_SCENE_CLASS_CLOUD << 24 | (q.w & 0xffu) << 16 | (q.w & 0xff00u) | ((q.w >> 16) & 0xffu);
+        const unsigned long long key = (unsigned long long)__float_as_uint(c[2]) << 32 | low;
+        for (int y = ya; y <= yb; y++)
+            for (int x = xa; x <= xb; x++) atomicMin((unsigned long long*)(plane + ((size_t)y * w + x)), key);
+    }
+}
+
+template <bool CLOUDS>
 __global__ __launch_bounds__(SCENE_THREADS) void scene_render_kernel(const SceneTile* __restrict__ tiles,
-                                                                     const SceneImage* __restrict__ images, const SceneParams p) {
+                                                                     const SceneImage* __restrict__ images,
+                                                                     const unsigned long long* const* __restrict__ planes,
+                                                                     const SceneParams p) {
     __shared__ unsigned long long keys[SCENE_TILE_W * SCENE_TILE_H];
     const SceneTile t = G(tiles)[blockIdx.x];
     const SceneImage im = G(images)[t.image];
@@ -134,7 +183,15 @@ __global__ __launch_bounds__(SCENE_THREADS) void scene_render_kernel(const Scene
     const int tw = min(SCENE_TILE_W, im.w - t.x0), th = min(SCENE_TILE_H, im.h - t.y0);   // the tile's pixels inside the image
 
     // 1. the key plane
-    for (int i = tid; i < SCENE_TILE_W * SCENE_TILE_H; i += SCENE_THREADS) keys[i] = ~0ull;
+    if (CLOUDS) {
+        SVO_GP(const unsigned long long) plane = G(G(planes)[t.image]);   // (null: an image without cloud points)
+        for (int i = tid; i < SCENE_TILE_W * SCENE_TILE_H; i += SCENE_THREADS) {
+            const int x = i % SCENE_TILE_W, y = i / SCENE_TILE_W;
+            keys[i] = plane && x < tw && y < th ? plane[(size_t)(t.y0 + y) * im.w + (t.x0 + x)] : ~0ull;
+        }
+    } else {
+        for (int i = tid; i < SCENE_TILE_W * SCENE_TILE_H; i += SCENE_THREADS) keys[i] = ~0ull;
+    }
     __syncthreads();
 
     // 2. the points
@@ -264,7 +321,21 @@ __global__ __launch_bounds__(SCENE_THREADS) void scene_render_kernel(const Scene
 
 void launch_scene(const SceneTile* d_tiles, int n_tiles, const SceneImage* d_images, const SceneParams& p, hipStream_t stream) {
     if (n_tiles <= 0) return;
-    hipLaunchKernelGGL(scene_render_kernel, dim3(n_tiles), dim3(SCENE_THREADS), 0, stream, d_tiles, d_images, p);
+    hipLaunchKernelGGL(scene_render_kernel<false>, dim3(n_tiles), dim3(SCENE_THREADS), 0, stream, d_tiles, d_images, nullptr, p);
+}
+
+void launch_scene_clouds(const SceneTile* d_tiles, int n_tiles, const SceneImage* d_images, unsigned long long* const* d_planes,
+                         const SceneParams& p, hipStream_t stream) {
+    if (n_tiles <= 0) return;
+    hipLaunchKernelGGL(scene_render_kernel<true>, dim3(n_tiles), dim3(SCENE_THREADS), 0, stream, d_tiles, d_images, d_planes, p);
+}
+
+void launch_scene_splat(const SceneSpan* d_spans, int n_spans, const SceneImage* d_images, unsigned long long* const* d_planes,
+                        const SceneParams& p, int point_size, hipStream_t stream) {
+    if (n_spans <= 0) return;
+    SceneParams q = p;
+    q.point_size = point_size;
+    hipLaunchKernelGGL(scene_splat_kernel, dim3(n_spans), dim3(SCENE_THREADS), 0, stream, d_spans, d_images, d_planes, q);
 }
 
 }  // namespace svo

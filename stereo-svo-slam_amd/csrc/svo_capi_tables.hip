@@ -352,6 +352,102 @@ extern "C" int svo_render_scene(svo_handle* h, int n, const svo_scene_src* src, 
                         [&](const SceneTile* d, int m, hipStream_t s) { launch_scene(d, m, d_images, params, s); });
 }
 
+// svo_render_scene with cloud points: the key planes of the images that have a record are cleared, the pieces of
+// every span go through the splat pass (a table of its own, chunked like the tile table), then the tile kernel starts
+// from the planes. Without a record it is svo_render_scene itself.
+extern "C" int svo_render_scene_clouds(svo_handle* h, int n, const svo_scene_src* src, const svo_scene_span* spans, const int32_t* n_spans,
+                                       const svo_scene_camera* cameras, const int64_t* offset, const svo_scene_style* style,
+                                       int32_t point_size, uint8_t* pixels) {
+    const char* who = "svo_render_scene_clouds";
+    CHECK_H(h);
+    if (n < 0 || (n > 0 && (!src || !cameras || !offset || !n_spans))) return svo_set_error(SVO_ERR_INVALID, "%s: bad arguments", who);
+    if (point_size < 1 || point_size > 16) return svo_set_error(SVO_ERR_INVALID, "%s: point_size %d is not within 1 .. 16", who, point_size);
+    int64_t records = 0, pieces = 0;
+    size_t n_all = 0;
+    for (int i = 0; i < n; i++) {
+        if (n_spans[i] < 0 || (n_spans[i] > 0 && !spans)) return svo_set_error(SVO_ERR_INVALID, "%s: image %d: %d spans, or no span array", who, i, n_spans[i]);
+        for (int j = 0; j < n_spans[i]; j++, n_all++) {
+            const svo_scene_span& sp = spans[n_all];
+            if (!scene_span_ok((uintptr_t)sp.points, sp.n))
+                return svo_set_error(SVO_ERR_INVALID, "%s: image %d: span %d: n %lld must be >= 0 and its records device memory, 16-byte aligned", who, i, j,
+                                     (long long)sp.n);
+            records += sp.n;
+            pieces += scene_span_pieces(sp.n);
+        }
+    }
+    if (records == 0) return svo_render_scene(h, n, src, cameras, offset, style, pixels);
+    if (pieces > INT_MAX) return svo_set_error(SVO_ERR_INVALID, "%s: %lld records are too many for one call", who, (long long)records);
+    if (const int rc = scene_check_style(style, who)) return rc;
+    if (!pixels || ((uintptr_t)pixels & 3)) return svo_set_error(SVO_ERR_INVALID, "%s: pixels is NULL or not 4-byte aligned", who);
+    std::vector<SceneSet> sets;
+    std::vector<SceneImage> images;
+    std::vector<size_t> set0, plane_at((size_t)n, SIZE_MAX);
+    std::vector<SceneTile> tiles;
+    std::vector<SceneSpan> table;
+    size_t planes_bytes = 0;
+    n_all = 0;
+    for (int i = 0; i < n; i++) {
+        const svo_scene_src& s = src[i];
+        if (s.cols < 1 || s.cols > 4096 || s.rows < 1 || s.rows > 4096)
+            return svo_set_error(SVO_ERR_INVALID, "%s: image %d: %d x %d is not within 1 .. 4096 a side", who, i, s.cols, s.rows);
+        if (offset[i] < 0 || (offset[i] & 3)) return svo_set_error(SVO_ERR_INVALID, "%s: image %d: offset must be >= 0 and a multiple of 4", who, i);
+        if (const int rc = scene_check_camera(&cameras[i], who, i)) return rc;
+        if (s.n_sets < 0 || s.n_lines < 0 || (s.n_sets > 0 && (!s.sets || !s.own_id)) || (s.n_lines > 0 && !s.lines) || ((uintptr_t)s.lines & 15))
+            return svo_set_error(SVO_ERR_INVALID, "%s: image %d: sets, own_id or lines missing, or lines not 16-byte aligned", who, i);
+        set0.push_back(sets.size());
+        for (int j = 0; j < s.n_sets; j++) {
+            const svo_keypoints& k = s.sets[j];
+            if (k.n < 0) return svo_set_error(SVO_ERR_INVALID, "%s: image %d: set %d: n must be >= 0", who, i, j);
+            KpsDev d;
+            if (!take_planes(k, KP_MAP, k.n > 0, d))
+                return svo_set_error(SVO_ERR_INVALID, "%s: image %d: set %d: kps3d, flags, keyframe_id, inlier_count and color are device memory, 4-byte aligned", who, i, j);
+            sets.push_back(scene_set(d, k.n, s.own_id[j]));
+        }
+        for (int j = 0; j < n_spans[i]; j++, n_all++) {
+            const svo_scene_span& sp = spans[n_all];
+            if (sp.n > 0 && plane_at[(size_t)i] == SIZE_MAX) {
+                plane_at[(size_t)i] = planes_bytes;
+                planes_bytes += scene_key_bytes(s.cols, s.rows);
+            }
+            scene_each_piece(sp.n, [&](int64_t first, int count) { table.push_back(SceneSpan{sp.points + first, i, count}); });
+        }
+        SceneImage im;
+        im.cam = cameras[i];
+        im.dst = pixels + offset[i];
+        im.sets = nullptr; im.lines = s.lines;             // (the sets are placed below, once the block is there)
+        im.n_sets = s.n_sets; im.n_lines = s.n_lines;
+        im.w = s.cols; im.h = s.rows;
+        scene_tiles(i, s.cols, s.rows, tiles);
+        images.push_back(im);
+    }
+    const size_t chunk = table_tiles("SVO_SCENE_TABLE_TILES", std::min<size_t>(tiles.size(), (size_t)INT_MAX));
+    const size_t sets_bytes = (sizeof(SceneSet) * sets.size() + 15) / 16 * 16;
+    const size_t images_bytes = (sizeof(SceneImage) * images.size() + 15) / 16 * 16;
+    if (const int rc = h->scene_ws.reserve(sets_bytes + images_bytes + sizeof(SceneTile) * chunk, h->stream)) return rc;
+    // (SVO_SCENE_TABLE_SPANS: a smaller span table, so that tests reach the chunked splat launches)
+    const size_t span_chunk = table_tiles("SVO_SCENE_TABLE_SPANS", table.size());
+    const size_t ptrs_bytes = (sizeof(unsigned long long*) * (size_t)n + 255) / 256 * 256;
+    if (const int rc = h->scene_cloud_ws.reserve(planes_bytes + ptrs_bytes + sizeof(SceneSpan) * span_chunk, h->stream)) return rc;
+    uint8_t* const d_planes = h->scene_cloud_ws.ptr.get();
+    unsigned long long** const d_ptrs = reinterpret_cast<unsigned long long**>(d_planes + planes_bytes);
+    std::vector<unsigned long long*> ptrs((size_t)n, nullptr);
+    for (int i = 0; i < n; i++)
+        if (plane_at[(size_t)i] != SIZE_MAX) ptrs[(size_t)i] = reinterpret_cast<unsigned long long*>(d_planes + plane_at[(size_t)i]);
+    const SceneSet* d_sets = reinterpret_cast<const SceneSet*>(h->scene_ws.ptr.get());
+    const SceneImage* d_images = reinterpret_cast<const SceneImage*>(h->scene_ws.ptr.get() + sets_bytes);
+    for (size_t i = 0; i < images.size(); i++) images[i].sets = d_sets + set0[i];
+    if (!sets.empty()) HIP_TRY(hipMemcpyAsync(h->scene_ws.ptr.get(), sets.data(), sizeof(SceneSet) * sets.size(), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->scene_ws.ptr.get() + sets_bytes, images.data(), sizeof(SceneImage) * images.size(), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(d_ptrs, ptrs.data(), sizeof(unsigned long long*) * (size_t)n, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemsetAsync(d_planes, 0xff, planes_bytes, h->stream));
+    const SceneParams params = scene_params(*style);
+    if (const int rc = launch_tiles(h, table, reinterpret_cast<SceneSpan*>(d_planes + planes_bytes + ptrs_bytes), span_chunk,
+                                    [&](const SceneSpan* d, int m, hipStream_t s) { launch_scene_splat(d, m, d_images, d_ptrs, params, point_size, s); }))
+        return rc;
+    return launch_tiles(h, tiles, reinterpret_cast<SceneTile*>(h->scene_ws.ptr.get() + sets_bytes + images_bytes), chunk,
+                        [&](const SceneTile* d, int m, hipStream_t s) { launch_scene_clouds(d, m, d_images, d_ptrs, params, s); });
+}
+
 extern "C" int svo_render_ar(svo_handle* h, int n, const svo_ar_src* src, const svo_ar_camera* cameras, const int64_t* offset,
                              const svo_ar_style* style, uint8_t* pixels) {
     CHECK_H(h);

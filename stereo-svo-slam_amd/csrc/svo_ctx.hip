@@ -98,6 +98,10 @@ struct svo_ctx {
         std::vector<svo_scene_camera> cameras;
         svo_scene_style style{};
         svo_scene_dst dst{};
+        // (svo_submit_export_scenes_clouds: the clouds and the span of each named slot of the group, or none)
+        bool has_clouds = false;
+        svo_scene_clouds clouds{};
+        std::vector<svo_scene_span> extra;
     };
     // the group's share of an svo_submit_export_ar: its named slots (indices in the group) in named order, the
     // instances [inst0, inst1) of the job each one shows, the segment (and image) of the job each one fills, and
@@ -197,7 +201,8 @@ int run_job(svo_group* g, int seq0, const svo_ctx::CloudExport& j) {
     return grp_export_cloud(g, j.what, j.mem, j.seqs.data(), j.seg.data(), (int)j.seqs.size(), seq0, &j.style, j.check_ptr(), &j.dst);
 }
 int run_job(svo_group* g, int seq0, const svo_ctx::SceneExport& j) {
-    return grp_export_scenes(g, j.mem, j.seqs.data(), j.seg.data(), (int)j.seqs.size(), seq0, &j.style, j.cameras.data(), &j.dst);
+    return grp_export_scenes_clouds(g, j.mem, j.seqs.data(), j.seg.data(), (int)j.seqs.size(), seq0, &j.style, j.cameras.data(), &j.dst,
+                                    j.has_clouds ? &j.clouds : nullptr, j.extra.empty() ? nullptr : j.extra.data());
 }
 int run_job(svo_group* g, int seq0, const svo_ctx::ArExport& j) {
     return grp_export_ar(g, j.mem, j.seqs.data(), j.seg.data(), j.inst0.data(), j.inst1.data(), (int)j.seqs.size(), seq0, j.job.get(), &j.dst);
@@ -656,6 +661,17 @@ extern "C" int svo_export_cloud_checked(svo_ctx* c, int what, const int* seqs, i
 
 extern "C" int svo_submit_export_scenes(svo_ctx* c, const int* seqs, int n, const svo_scene_style* style,
                                         const svo_scene_camera* cameras, const svo_scene_dst* dst, int mem) {
+    return svo_submit_export_scenes_clouds(c, seqs, n, style, nullptr, cameras, dst, mem);
+}
+
+extern "C" int svo_submit_export_scenes_clouds(svo_ctx* c, const int* seqs, int n, const svo_scene_style* style,
+                                               const svo_scene_clouds* clouds, const svo_scene_camera* cameras, const svo_scene_dst* dst,
+                                               int mem) {
+    if (clouds && clouds->live == 0 && !clouds->extra) {             // (nothing to draw: the plain job, once the clouds are checked)
+        if (c)
+            if (const int rc = grp_check_scene_clouds(c->workers[0]->g.get(), clouds)) return rc;
+        clouds = nullptr;
+    }
     if (!c || !dst || !dst->segments || !cameras || (mem != SVO_MEM_HOST && mem != SVO_MEM_DEVICE) || (seqs && n < 0))
         return svo_set_error(SVO_ERR_INVALID, "svo_submit_export_scenes: bad arguments (mem %d)", mem);
     if (const int rc = svo::scene_check_style(style, "svo_submit_export_scenes")) return rc;
@@ -669,6 +685,13 @@ extern "C" int svo_submit_export_scenes(svo_ctx* c, const int* seqs, int n, cons
             return svo_set_error(SVO_ERR_INVALID, "svo_submit_export_scenes: sequence %d is out of range or named twice", slots.at(i));
         if (const int rc = svo::scene_check_camera(&cameras[i], "svo_submit_export_scenes", i)) return rc;
     }
+    if (clouds) {
+        if (const int rc = grp_check_scene_clouds(c->workers[0]->g.get(), clouds)) return rc;   // (every group has the same settings)
+        for (int i = 0; clouds->extra && i < n; i++)
+            if (!svo::scene_span_ok((uintptr_t)clouds->extra[i].points, clouds->extra[i].n))
+                return svo_set_error(SVO_ERR_INVALID, "svo_submit_export_scenes_clouds: span %d: n %lld must be >= 0 and its records device memory, 16-byte aligned",
+                                     i, (long long)clouds->extra[i].n);
+    }
     const int64_t image_bytes = grp_scene_bytes(style);
     if (dst->capacity < n * image_bytes)
         return svo_set_error(SVO_ERR_CAPACITY, "svo_submit_export_scenes: %d slots need %lld bytes, capacity %lld", n,
@@ -677,9 +700,13 @@ extern "C" int svo_submit_export_scenes(svo_ctx* c, const int* seqs, int n, cons
     for (auto& wp : c->workers) {
         svo_ctx::Worker& w = *wp;
         svo_ctx::SceneExport e;
-        slots.each_in(w.first, w.count, [&](int i, int local) { e.seqs.push_back(local); e.seg.push_back(i); e.cameras.push_back(cameras[i]); });
+        slots.each_in(w.first, w.count, [&](int i, int local) {
+            e.seqs.push_back(local); e.seg.push_back(i); e.cameras.push_back(cameras[i]);
+            if (clouds && clouds->extra) e.extra.push_back(clouds->extra[i]);
+        });
         if (e.seqs.empty()) continue;
         e.mem = mem; e.style = *style; e.dst = *dst;
+        if (clouds) { e.has_clouds = true; e.clouds = *clouds; }
         worker_submit(w, std::move(e));
     }
     return SVO_OK;
@@ -688,6 +715,12 @@ extern "C" int svo_submit_export_scenes(svo_ctx* c, const int* seqs, int n, cons
 extern "C" int svo_export_scenes(svo_ctx* c, const int* seqs, int n, const svo_scene_style* style,
                                  const svo_scene_camera* cameras, const svo_scene_dst* dst, int mem) {
     const int rc = svo_submit_export_scenes(c, seqs, n, style, cameras, dst, mem);
+    return rc ? rc : svo_wait(c);
+}
+
+extern "C" int svo_export_scenes_clouds(svo_ctx* c, const int* seqs, int n, const svo_scene_style* style, const svo_scene_clouds* clouds,
+                                        const svo_scene_camera* cameras, const svo_scene_dst* dst, int mem) {
+    const int rc = svo_submit_export_scenes_clouds(c, seqs, n, style, clouds, cameras, dst, mem);
     return rc ? rc : svo_wait(c);
 }
 

@@ -68,6 +68,14 @@ int64_t grp_view_bytes(const svo_group* g, const svo_view_style* style);
 int grp_export_scenes(svo_group* g, int mem, const int* seqs, const int* seg, int n, int seq0, const svo_scene_style* style,
                       const svo_scene_camera* cameras, const svo_scene_dst* dst);
 int64_t grp_scene_bytes(const svo_scene_style* style);   // the image_bytes of a checked style
+// grp_export_scenes with cloud points (svo_submit_export_scenes_clouds). clouds: checked (grp_check_scene_clouds), its
+// extra is not read; extra: null, or the span of every seqs[i], checked; clouds->info[seg[i]] is filled if there is one.
+// clouds == null is grp_export_scenes.
+int grp_export_scenes_clouds(svo_group* g, int mem, const int* seqs, const int* seg, int n, int seq0, const svo_scene_style* style,
+                             const svo_scene_camera* cameras, const svo_scene_dst* dst, const svo_scene_clouds* clouds,
+                             const svo_scene_span* extra);
+// what svo_submit_export_scenes_clouds checks of a clouds but for its spans
+int grp_check_scene_clouds(const svo_group* g, const svo_scene_clouds* clouds);
 // What svo_submit_export_ar copied of its caller's arrays, checked; the jobs of all groups share one (read only).
 // The meshes lie back to back: mesh m has vertices [v0, v0 + n_vertices) (3 floats each), triangles [t0, t0 +
 // n_triangles) (3 indices each) and, with has_rgb, the colours [c0, c0 + n_triangles).
@@ -106,6 +114,8 @@ int grp_export_cloud(svo_group* g, int what, int mem, const int* seqs, const int
 // what svo_submit_export_cloud checks of a style, and the points_per_slot of a checked one
 int grp_check_cloud_style(const svo_group* g, const svo_cloud_style* style, const svo_stereo_check* check);
 int64_t grp_cloud_points(const svo_group* g, const svo_cloud_style* style);
+// what one slot of a device-mode job with that checked style and check stages: slot_bytes [+ reverse_bytes]
+int64_t grp_cloud_slot_bytes(const svo_group* g, const svo_cloud_style* style, const svo_stereo_check* check);
 // what svo_map_size reports of a slot (the queues have drained)
 void grp_map_size(const svo_group* g, int seq, int from_keyframe, int* keyframes, int64_t* points_bound, int* from = nullptr);
 // Snapshots (svo_submit_save / svo_submit_load). grp_check_snapshot: everything svo_submit_load checks of one

@@ -72,6 +72,15 @@ int64_t grp_cloud_points(const svo_group* c, const svo_cloud_style* style) {
     return (int64_t)(c->width / s.step) * (c->height / s.step);
 }
 
+int64_t grp_cloud_slot_bytes(const svo_group* c, const svo_cloud_style* style, const svo_stereo_check* check) {
+    DenseParams s;
+    if (cloud_check_style(style, &c->cam, "svo_submit_export_cloud", &s, nullptr) != SVO_OK) return 0;
+    LrCheck lr;
+    if (lr_check_parse(check, true, "svo_submit_export_cloud", &lr) != SVO_OK) return 0;
+    const size_t points = (size_t)(c->width / s.step) * (size_t)(c->height / s.step);
+    return (int64_t)(Staging(points, false, 1).slot + (lr.on ? lr_reverse_bytes(c->width, c->height, s.step) : 0));
+}
+
 // The named slots of the group as segments and records (svo_submit_export_cloud). Named slot seg[i] of the job owns
 // the records from seg[i] * points on. The slots run in chunks of at most `chunk` (one chunk unless the job stages
 // more than CLOUD_STAGING_BYTES): per chunk the search of its delivered slots into the staging block's planes, the

@@ -339,6 +339,9 @@ struct svo_group {
     // one. Replaced when outgrown.
     svo::GrowBlock<uint8_t, true> d_scene_in;
     svo::GrowBlock<uint8_t> d_scene;
+    // scene clouds (grp_export_scenes_clouds): the key planes of one chunk of a job, then the records of its live layer,
+    // made by the first such job and replaced when outgrown
+    svo::GrowBlock<uint8_t> d_scene_cloud;
     // ar pictures (grp_export_ar): the input block of one job (meshes | draws | image records | work list) and its
     // pinned mirror and the screen records of one job, made by the group's first ar job; in host mode the images of
     // one job, made by the first host-mode one. Replaced when outgrown.

@@ -45,6 +45,7 @@ struct svo_handle {
     svo_workspace map_ws;           // svo_pack_map_points: the tile counts of a call, then the tile table
     svo_workspace view_ws;          // svo_render_views: the tile table
     svo_workspace scene_ws;         // svo_render_scene: the sets and image records of a call, then the tile table
+    svo_workspace scene_cloud_ws;   // svo_render_scene_clouds: the key planes of a call, the plane table, then the span table
     svo_workspace ar_ws;            // svo_render_ar: the draws, image records, work list and screen records of a call, then the tile table
     svo_workspace dense_ws;         // svo_dense_disparity: the image table
     svo_workspace cloud_ws;         // svo_cloud_points: the two image tables of a chunk, then its planes, tile counts and pose matrices

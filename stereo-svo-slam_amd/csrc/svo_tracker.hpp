@@ -6,6 +6,7 @@
 
 #include "../../include/svo_hip.h"
 #include "svo_kernels.hpp"
+#include "svo_scene_plan.hpp"
 
 namespace svo {
 
@@ -261,6 +262,19 @@ void scene_tiles(int image, int w, int h, std::vector<SceneTile>& out);
 // the 8 world lines of a frustum (svo_scene_frustum) as records of class cls and colour rgb, appended to `out`
 void scene_frustum_lines(const float pose[6], const float dims[3], uint32_t cls_rgb, std::vector<svo_scene_line>& out);
 void launch_scene(const SceneTile* d_tiles, int n_tiles, const SceneImage* d_images, const SceneParams& p, hipStream_t stream);
+// Cloud points ("scene clouds"). One piece of a span of records: at most SCENE_SPLAT_PIECE of them, shown in `image`,
+// one workgroup of the splat pass (svo_scene_plan.hpp cuts the spans)
+constexpr int SCENE_SPLAT_PIECE = SCENE_PLAN_PIECE;
+struct SceneSpan {
+    const svo_map_point* points;
+    int image, n;
+};
+// d_planes[image]: the image's key plane uint64[h][w], all ones before the splat pass; null: an image without cloud
+// points (no piece may name it). The splat pass, then the tile kernel that starts from the planes.
+void launch_scene_splat(const SceneSpan* d_spans, int n_spans, const SceneImage* d_images, unsigned long long* const* d_planes,
+                        const SceneParams& p, int point_size, hipStream_t stream);
+void launch_scene_clouds(const SceneTile* d_tiles, int n_tiles, const SceneImage* d_images, unsigned long long* const* d_planes,
+                         const SceneParams& p, hipStream_t stream);
 
 // ------------------------------------------------------------ ar (ar.hip)
 // The screen record of one (image, triangle), written by the first launch and walked by the second: the snapped

@@ -48,6 +48,7 @@ SYMBOLS = (
     "svo_cloud_points_checked",
     "svo_scene_size", "svo_scene_look_at", "svo_scene_frustum", "svo_submit_export_scenes", "svo_export_scenes",
     "svo_render_scene",
+    "svo_submit_export_scenes_clouds", "svo_export_scenes_clouds", "svo_render_scene_clouds",
     "svo_ar_size", "svo_ar_camera_of_pose", "svo_submit_export_ar", "svo_export_ar", "svo_render_ar",
     "svo_remap_linear_multi", "svo_ctx_add_rigs", "svo_ctx_remove_rigs", "svo_ctx_assign_rigs", "svo_ctx_get_slot_rig",
     "svo_ctx_get_rigs",
@@ -601,6 +602,61 @@ def scene_frustum(pose, dims=(0.1, 0.08, 0.07)):
     return out
 
 
+# scene clouds (svo_submit_export_scenes_clouds, include/svo_hip.h): dense clouds drawn in the scene picture
+SCENE_CLASS_CLOUD = 4
+SCENE_CLOUD_INFO_DTYPE = np.dtype([("status", "<i4"), ("keyframe_id", "<i4"), ("live_points", "<i4"), ("_pad", "<i4"),
+                                   ("extra_points", "<i8"), ("_pad2", "<i8")])
+
+
+class SceneSpan(C.Structure):
+    """svo_scene_span (include/svo_hip.h): n svo_map_point records in device memory."""
+    _fields_ = [("points", C.c_void_p), ("n", C.c_int64)]
+
+
+class SceneCloudInfo(C.Structure):
+    """svo_scene_cloud_info (include/svo_hip.h); SCENE_CLOUD_INFO_DTYPE is the same layout for numpy."""
+    _fields_ = [("status", C.c_int32), ("keyframe_id", C.c_int32), ("live_points", C.c_int32), ("_pad", C.c_int32),
+                ("extra_points", C.c_int64), ("_pad2", C.c_int64)]
+
+
+class SceneClouds(C.Structure):
+    """svo_scene_clouds (include/svo_hip.h): the live layer and the extra spans of a scene job."""
+    _fields_ = [("live", C.c_int32), ("what", C.c_int32), ("cloud", CloudStyle), ("check", StereoCheck),
+                ("point_size", C.c_int32), ("_reserved", C.c_int32 * 3), ("extra", C.c_void_p), ("info", C.c_void_p)]
+
+
+assert (C.sizeof(SceneSpan), C.sizeof(SceneCloudInfo), C.sizeof(SceneClouds), SCENE_CLOUD_INFO_DTYPE.itemsize) == (16, 32, 120, 32)
+
+
+def scene_span(records):
+    """a SceneSpan of `records`: None, a device tensor holding MAP_POINT_DTYPE records, or (address, n)"""
+    if records is None:
+        return SceneSpan(None, 0)
+    if isinstance(records, torch.Tensor):
+        n = records.numel() * records.element_size() // MAP_POINT_DTYPE.itemsize
+        return SceneSpan(records.data_ptr() if n else None, n)
+    ptr, n = records
+    return SceneSpan(int(ptr) if ptr else None, int(n))
+
+
+def scene_clouds(live=False, what=0, step=1, win=0, search_x=0, search_y=0, min_disparity=0.0, max_depth=0.0,
+                 max_mean_cost=0.0, lr_check=0.0, point_size=1, extra=None, info=None):
+    """a SceneClouds and what it points to, as (clouds, keep): keep the second alive until the job is delivered.
+    live: draw the dense cloud of `what` (0: frames, 1: newest keyframes) of every named slot, searched with step, win,
+    search_x, search_y (0: the ctx's), filtered by min_disparity, max_depth, max_mean_cost (0: off) and, with
+    lr_check > 0, by the left-right check at that tolerance. extra: None, or per named slot what scene_span takes.
+    info: None, or a numpy array of SCENE_CLOUD_INFO_DTYPE, one per named slot."""
+    check = stereo_check(lr_check > 0, lr_check) if live else StereoCheck()
+    spans = None
+    if extra is not None:
+        spans = (SceneSpan * max(len(extra), 1))(*[scene_span(e) for e in extra])
+    c = SceneClouds(int(bool(live)), int(what), cloud_style(step, win, search_x, search_y, CLOUD_WORLD, CLOUD_COMPACT,
+                                                           min_disparity, max_depth, max_mean_cost),
+                    check, int(point_size), (C.c_int32 * 3)(), C.cast(spans, C.c_void_p) if spans is not None else None,
+                    info.ctypes.data if info is not None else None)
+    return c, (spans, extra, info)
+
+
 # ar pictures (svo_submit_export_ar, include/svo_hip.h): lit meshes over each slot's camera image
 AR_OK, AR_NONE = 0, 1
 AR_MAX_TRIANGLES = 65536
@@ -1150,6 +1206,26 @@ class Handle:
         n, arr, cams, offs, _ = packed
         p = pixels.data_ptr() if isinstance(pixels, torch.Tensor) else int(pixels)
         _check(lib().svo_render_scene(self._h, n, arr, cams, offs, C.byref(style), C.c_void_p(p)))
+
+    def render_scene_clouds(self, srcs, spans, cameras, offsets, style, point_size, pixels):
+        """svo_render_scene_clouds: render_scene with cloud points. spans: per image a list of what scene_span takes
+        (device tensors of MAP_POINT_DTYPE records, or (address, n)); point_size: the cloud points' square."""
+        packed = self.pack_scene(srcs, cameras, offsets)
+        self.render_scene_clouds_packed(packed, self.pack_scene_spans(spans), style, point_size, pixels)
+
+    def pack_scene_spans(self, spans):
+        """the span arrays of render_scene_clouds, built once; the device tensors must stay alive"""
+        flat = [scene_span(e) for per_image in spans for e in per_image]
+        arr = (SceneSpan * max(len(flat), 1))(*flat)
+        counts = (C.c_int32 * max(len(spans), 1))(*[len(per_image) for per_image in spans])
+        return arr, counts, spans
+
+    def render_scene_clouds_packed(self, packed, packed_spans, style, point_size, pixels):
+        """svo_render_scene_clouds of the arrays of pack_scene and pack_scene_spans"""
+        n, arr, cams, offs, _ = packed
+        p = pixels.data_ptr() if isinstance(pixels, torch.Tensor) else int(pixels)
+        _check(lib().svo_render_scene_clouds(self._h, n, arr, packed_spans[0], packed_spans[1], cams, offs, C.byref(style),
+                                             C.c_int32(int(point_size)), C.c_void_p(p)))
 
     def render_ar(self, srcs, cameras, offsets, style, pixels):
         """svo_render_ar: lit meshes over gray planes as images of `style` (an ArStyle). srcs: per image

@@ -34,7 +34,9 @@ D; D = 0 only reports), the cost and the lr plane. --cloud-lr D drops such point
 DIR/kf000000_cloud.ply: the dense coloured point cloud of that keyframe in the world frame at every S-th pixel (binary
 little-endian PLY, x y z float and red green blue uchar), so that the files of a run together are a dense map of it.
 --dump-scene DIR writes per frame DIR/000000_scene.ppm: the 3-D viewer's picture of the map so far
-(src/qt-viewer/PointCloudViewer.qml: points, trajectory, frusta) through its front camera.
+(src/qt-viewer/PointCloudViewer.qml: points, trajectory, frusta) through its front camera. --scene-dense STEP
+[--scene-dense-lr D] [--scene-dense-max-depth Z] draws the frame's dense cloud into it, --scene-accumulate N the dense
+clouds of the keyframes so far (one device array of at most N records): the dense map growing.
 --dump-ar DIR writes per frame DIR/000000_ar.ppm: the AR demo's picture (src/ar-app/), a lit box of edge --ar-box
 fixed at the world point --ar-at over the frame's left image, seen from the tracked pose; the default placement is the
 demo's, half a metre in front of the first camera (AnimatedEntity.qml:56). If the pose is right the box stands still.
@@ -48,6 +50,7 @@ import re
 import time
 
 import numpy as np
+import torch
 
 from . import hip_lib, synth
 from .stereo_slam import StereoSlam
@@ -412,7 +415,8 @@ class Replay:
     def __init__(self, settings, device=0, time_trace=False, fast=False, rectify_maps=None, input_format=None,
                  gpu_imu=False, dump_views=None, dump_scene=None, calibration=None, keyframe_window=None, dump_ar=None,
                  ar_box=AR_BOX, ar_at=hip_lib.AR_AT, dump_disparity=None, disparity_step=4, disparity_depth=False,
-                 dump_cloud=None, cloud_step=4, cloud_max_depth=0.0, disparity_lr=None, cloud_lr=None):
+                 dump_cloud=None, cloud_step=4, cloud_max_depth=0.0, disparity_lr=None, cloud_lr=None, scene_dense=None,
+                 scene_dense_lr=None, scene_dense_max_depth=0.0, scene_accumulate=0):
         """fast=False keeps the library default: the reference-order Gauss-Newton (bit-exact traces).
         rectify_maps = (left maps, right maps): the frames fed are raw and are rectified on the GPU.
         calibration = (left, right) CameraCalibrations: the same, with the maps built on the GPU as well.
@@ -422,6 +426,12 @@ class Replay:
         dump_views: a directory that receives, per frame, the last keyframe and the current frame with a marker per
         keypoint as the reference app's window shows them (write_ppm), outside the timed region.
         dump_scene: a directory that receives, per frame, the 3-D viewer's picture of the map (get_scene), likewise.
+        scene_dense: None, or the lattice step (1 .. 16) of the dense cloud of the current frame that dump_scene draws into
+        its picture (get_scene(dense=...)); scene_dense_lr: None, or the tolerance (> 0) of its left-right cross-check;
+        scene_dense_max_depth: points deeper than this are dropped (0: none). scene_accumulate = N > 0: whenever the newest
+        keyframe id changes, that keyframe's compact device cloud (the same step, check and depth; step 4 without
+        scene_dense) is appended to one device tensor of at most N records, oldest dropped first, which dump_scene
+        draws as the extra span: the pictures show the dense map growing.
         dump_ar: a directory that receives, per frame, the AR demo's picture (get_ar): a lit box of edge ar_box at the
         world point ar_at over the frame's left image, likewise. The default is the demo's placement, half a metre in
         front of the first camera.
@@ -440,6 +450,10 @@ class Replay:
         self.dump_cloud, self.cloud_step, self.cloud_max_depth, self._cloud_kf = dump_cloud, int(cloud_step), float(cloud_max_depth), -1
         self.disparity_lr = None if disparity_lr is None else float(disparity_lr)
         self.cloud_lr = None if cloud_lr is None else float(cloud_lr)
+        self.scene_dense = None if scene_dense is None else int(scene_dense)
+        self.scene_dense_lr = None if scene_dense_lr is None else float(scene_dense_lr)
+        self.scene_dense_max_depth, self.scene_accumulate = float(scene_dense_max_depth), int(scene_accumulate)
+        self._scene_kf, self._scene_map = -1, None
         for d in (dump_views, dump_scene, dump_ar, dump_disparity, dump_cloud):
             if d:
                 os.makedirs(d, exist_ok=True)
@@ -500,7 +514,7 @@ class Replay:
                 if img is not None:
                     write_ppm(os.path.join(self.dump_views, f"{k:06d}_{name}.ppm"), img)
         if self.dump_scene:
-            img = self.slam.get_scene("front", pixel="rgb8")
+            img = self.slam.get_scene("front", pixel="rgb8", **self._scene_clouds())
             if img is not None:
                 write_ppm(os.path.join(self.dump_scene, f"{len(self.cumulative) - 1:06d}_scene.ppm"), img)
         if self.dump_ar:
@@ -527,6 +541,26 @@ class Replay:
                     write_ply(os.path.join(self.dump_cloud, f"kf{kf:06d}_cloud.ply"), points)
         if self.time_trace:                       # like PRINT_TIME_TRACE of the reference
             print("\n".join(time_trace_lines(self.slam.stats())))
+
+    def _scene_clouds(self):
+        """the dense and clouds arguments of dump_scene's get_scene ({}: the sparse picture)"""
+        kw = {}
+        step = self.scene_dense if self.scene_dense is not None else 4
+        if self.scene_dense is not None:
+            kw["dense"] = dict(what="frames", step=step, max_depth=self.scene_dense_max_depth, lr_check=self.scene_dense_lr or 0.0)
+        if self.scene_accumulate > 0:
+            kf = int(self.slam.stats().n_keyframes) - 1
+            if kf != self._scene_kf:
+                self._scene_kf = kf
+                job = self.slam.export_cloud("last_keyframes", None, step=step, layout="compact", device=True,
+                                             max_depth=self.scene_dense_max_depth, lr_check=self.scene_dense_lr)
+                if int(job.segments[0]["status"]) == hip_lib.CLOUD_OK:
+                    new = job.points_buffer[:int(job.segments[0]["n_points"])]
+                    both = new if self._scene_map is None else torch.cat([self._scene_map, new])
+                    self._scene_map = both[max(0, both.shape[0] - self.scene_accumulate):].contiguous()
+            if self._scene_map is not None and self._scene_map.shape[0] > 0:
+                kw["clouds"] = [self._scene_map]
+        return kw
 
     def rows(self):
         traj = self.slam.get_trajectory()
@@ -577,6 +611,15 @@ def build_parser():
     ap.add_argument("--dump-scene", metavar="DIR",
                     help="write per frame DIR/NNNNNN_scene.ppm: the 3-D viewer's picture of the map so far (keyframe points, "
                          "trajectory, a frustum per keyframe and at the current pose) through its front camera")
+    ap.add_argument("--scene-dense", metavar="STEP", type=int, default=None,
+                    help="--dump-scene also draws the dense cloud of the current frame, every STEP-th pixel (1 .. 16)")
+    ap.add_argument("--scene-dense-lr", metavar="D", type=float, default=None,
+                    help="--scene-dense / --scene-accumulate drop points whose left-right cross-check differs by more than D (> 0)")
+    ap.add_argument("--scene-dense-max-depth", metavar="Z", type=float, default=0.0,
+                    help="--scene-dense / --scene-accumulate drop points deeper than Z in the camera frame (0: none)")
+    ap.add_argument("--scene-accumulate", metavar="N", type=int, default=0,
+                    help="--dump-scene also draws the dense clouds of the keyframes so far, kept on the device in one array of "
+                         "at most N records (oldest dropped first): the dense map growing")
     ap.add_argument("--dump-ar", metavar="DIR",
                     help="write per frame DIR/NNNNNN_ar.ppm: the AR demo's picture, a lit box standing in the world over the "
                          "frame's left image, seen from the tracked pose")
@@ -665,7 +708,9 @@ def main(argv=None):
                 ar_box=args.ar_box, ar_at=tuple(float(x) for x in args.ar_at.split(",")),
                 keyframe_window=args.keyframe_window, dump_disparity=args.dump_disparity, disparity_step=args.disparity_step,
                 disparity_depth=args.disparity_depth, dump_cloud=args.dump_cloud, cloud_step=args.cloud_step,
-                cloud_max_depth=args.cloud_max_depth, disparity_lr=args.disparity_lr, cloud_lr=args.cloud_lr)
+                cloud_max_depth=args.cloud_max_depth, disparity_lr=args.disparity_lr, cloud_lr=args.cloud_lr,
+                scene_dense=args.scene_dense, scene_dense_lr=args.scene_dense_lr, scene_dense_max_depth=args.scene_dense_max_depth,
+                scene_accumulate=args.scene_accumulate)
     for k, (left, right, t) in enumerate(frames):
         rp.feed(left, right, t, None if gyro is None else gyro[gyro[:, 0] == k, 1:4])
     rows = rp.rows()

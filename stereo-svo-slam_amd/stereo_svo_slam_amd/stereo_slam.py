@@ -458,9 +458,14 @@ class Scenes:
     """One svo_submit_export_scenes: owns the buffers the library writes. After wait(): `segments`
     (hip_lib.SCENE_SEGMENT_DTYPE, one per named slot) and image(i); `pixels` is the whole buffer, a numpy uint8 view
     of pinned memory in host mode, a torch uint8 tensor on the ctx's device in device mode. cols, rows, pitch,
-    image_bytes: the shape of every image of the job (svo_scene_size); channels: 3 or 4."""
+    image_bytes: the shape of every image of the job (svo_scene_size); channels: 3 or 4. With dense or clouds
+    (StereoSlamBatch.submit_scenes) the job is svo_submit_export_scenes_clouds and `cloud_info`
+    (hip_lib.SCENE_CLOUD_INFO_DTYPE, one per named slot) says what was drawn; without them cloud_info is None."""
 
-    def __init__(self, slam, seqs, style, cameras, device):
+    DENSE_DEFAULTS = dict(live=True, what="frames", step=2, win=0, search_x=0, search_y=0, min_disparity=0.0, max_depth=0.0,
+                          max_mean_cost=0.0, lr_check=0.0, point_size=1)
+
+    def __init__(self, slam, seqs, style, cameras, device, dense=None, clouds=None):
         self._slam = slam
         self.style, self.device_mode = style, bool(device)
         self.seqs = None if seqs is None else [int(s) for s in seqs]
@@ -480,6 +485,23 @@ class Scenes:
                      else torch.zeros(max(self.capacity, 4), dtype=torch.uint8, pin_memory=True))
         self._dst = hip_lib.SceneDst(self._seg.ctypes.data, self._buf.data_ptr(), self.capacity)
         self._seq_arr = None if seqs is None else (C.c_int * max(n, 1))(*self.seqs)
+        self.cloud_info = self._clouds = None
+        if dense is not None or clouds is not None:
+            d = dict(self.DENSE_DEFAULTS)
+            unknown = set(dense or {}) - set(d)
+            if unknown:
+                raise ValueError(f"dense: unknown keys {sorted(unknown)}")
+            d.update(dense or {})
+            if isinstance(d["what"], str):
+                d["what"] = hip_lib.EXPORT_WHAT.index(d["what"])
+            d["lr_check"] = float(d["lr_check"] or 0.0)
+            if clouds is not None and len(clouds) != n:
+                raise ValueError(f"{len(clouds)} clouds for {n} named slots: one per named slot")
+            self._info = np.zeros(max(n, 1), hip_lib.SCENE_CLOUD_INFO_DTYPE)
+            self.cloud_info = self._info[:n]
+            live = dense is not None and bool(d.pop("live"))
+            d.pop("live", None)
+            self._clouds = hip_lib.scene_clouds(live=live, extra=clouds, info=self._info, **d)
 
     @property
     def pixels(self):
@@ -490,8 +512,13 @@ class Scenes:
         slam = self._slam
         if self.device_mode:
             torch.cuda.current_stream(slam.device).synchronize()     # (nothing of the caller's is still using the tensor)
-        _check(lib().svo_submit_export_scenes(slam._ctx, self._seq_arr, self._n, C.byref(self.style), self._cams,
-                                              C.byref(self._dst), hip_lib.MEM_DEVICE if self.device_mode else hip_lib.MEM_HOST))
+        mem = hip_lib.MEM_DEVICE if self.device_mode else hip_lib.MEM_HOST
+        if self._clouds is None:
+            _check(lib().svo_submit_export_scenes(slam._ctx, self._seq_arr, self._n, C.byref(self.style), self._cams,
+                                                  C.byref(self._dst), mem))
+        else:
+            _check(lib().svo_submit_export_scenes_clouds(slam._ctx, self._seq_arr, self._n, C.byref(self.style),
+                                                         C.byref(self._clouds[0]), self._cams, C.byref(self._dst), mem))
         return self
 
     def wait(self):
@@ -949,18 +976,23 @@ class StereoSlamBatch:
         """submit_cloud + wait"""
         return self.submit_cloud(what, seqs, **kw).wait()
 
-    def submit_scenes(self, seqs=None, camera="front", device=False, style=None, **kw):
+    def submit_scenes(self, seqs=None, camera="front", device=False, style=None, dense=None, clouds=None, **kw):
         """svo_submit_export_scenes: queue the viewer's 3-D picture (keyframe points, trajectory, a frustum per
         keyframe and at the current pose) of the slots `seqs` (None: all, in order) behind what was submitted so far;
         nothing is waited for. camera: a preset name ("front", "top", "side"), one hip_lib.SceneCamera for all, or a
         list with one per named slot; style: a hip_lib.SceneStyle, or its fields as keywords (hip_lib.scene_style:
-        cols, rows, pixel, point_size, colours, show, from_keyframe, trajectory_tail, filter). Returns a Scenes,
-        valid after its wait() (or the ctx's); its submit() queues the same job again into the same buffers."""
+        cols, rows, pixel, point_size, colours, show, from_keyframe, trajectory_tail, filter). dense: None, or a dict
+        (any of what, step, win, search_x, search_y, min_disparity, max_depth, max_mean_cost, lr_check, point_size;
+        live=False: only point_size counts, for `clouds`) that draws the dense cloud of every named slot's frame (what="frames") or newest keyframe ("last_keyframes")
+        into its picture, the cloud submit_cloud(layout="organized") with these values would deliver; clouds: None,
+        or per named slot a device tensor of hip_lib.MAP_POINT_DTYPE bytes, (address, n) or None: records of the
+        caller's drawn as well (they stay alive and unchanged until the job is delivered). Returns a Scenes, valid
+        after its wait() (or the ctx's); its submit() queues the same job again into the same buffers."""
         if style is None:
             style = hip_lib.scene_style(**kw)
         if isinstance(camera, str):
             camera = hip_lib.scene_preset(camera, style.cols, style.rows)
-        return Scenes(self, seqs, style, camera, device).submit()
+        return Scenes(self, seqs, style, camera, device, dense, clouds).submit()
 
     def export_scenes(self, seqs=None, **kw):
         """submit_scenes + wait"""
@@ -1399,7 +1431,8 @@ class StereoSlam(StereoSlamBatch):
 
     def get_scene(self, camera="front", **kw):
         """the viewer's 3-D picture of the map as a numpy array [rows, cols, 3 | 4] (export_scenes of the one slot:
-        camera, cols, rows, pixel, show, ...); None before the first frame"""
+        camera, cols, rows, pixel, show, ...; dense=dict(...) draws the current frame's dense cloud into it); None before
+        the first frame"""
         if self._ctx is None:
             return None
         kw["device"] = False

@@ -19,6 +19,18 @@ process:
   pipelined  frames/s over `--steps` queued steps without scenes and with a device-mode 256 x 256 scene of every slot
              queued behind every 10th frame set; legs alternate, median of `--repeats` each.
 Prints one JSON line.
+
+--clouds STEPS (e.g. 1,2,4) measures the cloud points of DESIGN §4.20 instead and writes profiles/scene_cloud_bench.json:
+`--cloud-slots` slots in one group at the ctx's 752 x 480, their dense clouds (device mode, organized) at every step,
+drawn into 640 x 480 RGBA pictures from behind each slot's pose.
+  stage      svo_render_scene_clouds on the clouds alone (no keypoints, no lines), device events around a call: the
+             clear of the key planes, the splat pass and the CLOUDS tile kernel; records/s and the keys offered
+             (8 bytes each) per second beside the guide's chip-wide atomic rate. `tiles_only`: the same images without
+             spans (the CLOUDS = false kernel alone). `walked_by_every_tile`: the kept records as one keyframe set per
+             image through svo_render_scene, the form the splat pass replaces. `pile`: one slot's record count on one
+             pixel, distinct depths.
+  job        the device-mode scene job without and with the live layer (submit + wait, host clock), and the cloud job
+             that the layer runs first.
 """
 import argparse
 import json
@@ -217,8 +229,118 @@ def pipelined_leg(args, device, cfg, lefts, rights, slots, groups):
     return out
 
 
+ATOMIC_RATE = 1.3e12        # chip-wide rate of global float atomic adds, bytes/s (the microarchitecture guide)
+CLOUD_SIZE = (640, 480)
+
+
+def behind(pose, cols, rows, back=1.0):
+    """a camera `back` behind a pose, looking along its viewing direction"""
+    r = np.asarray(pose[3:6], np.float64)
+    angle = np.sqrt(r @ r)
+    k = r / angle if angle > 0 else np.zeros(3)
+    K = np.array([[0, -k[2], k[1]], [k[2], 0, -k[0]], [-k[1], k[0], 0]])
+    R = np.eye(3) + np.sin(angle) * K + (1 - np.cos(angle)) * (K @ K)            # Rodrigues
+    t = np.asarray(pose[:3], np.float64)
+    return hip_lib.scene_look_at(t - back * R[:, 2], t + R[:, 2], -R[:, 1], 60.0, cols, rows, 0.05)
+
+
+def offered_keys(rec, cam, cols, rows, size):
+    """how many keys the splat pass offers for the records [n, 4] int32 (float64 on the device: a count, not the picture)"""
+    v = torch.tensor(list(cam.view), dtype=torch.float64, device=rec.device).reshape(3, 4)
+    xyz = rec[:, :3].contiguous().view(torch.float32).double()
+    c = xyz @ v[:, :3].T + v[:, 3]
+    ok = (((rec[:, 3] >> 24) & 0x80) == 0) & torch.isfinite(c).all(dim=1) & (c[:, 2] >= cam.near)
+    z = torch.where(ok, c[:, 2], torch.ones_like(c[:, 2]))
+    u, w = cam.f * c[:, 0] / z + cam.cx, cam.f * c[:, 1] / z + cam.cy
+    ok &= (u.abs() < 32768) & (w.abs() < 32768)
+    x0, y0 = torch.floor(u) - (size - 1) // 2, torch.floor(w) - (size - 1) // 2
+    nx = (torch.clamp(x0 + size - 1, max=cols - 1) - torch.clamp(x0, min=0) + 1).clamp(min=0)
+    ny = (torch.clamp(y0 + size - 1, max=rows - 1) - torch.clamp(y0, min=0) + 1).clamp(min=0)
+    return int((nx * ny)[ok].sum().item()), int(ok.sum().item())
+
+
+def clouds_leg(args, device, cfg, lefts, rights, steps):
+    slots, (cols, rows) = args.cloud_slots, CLOUD_SIZE
+    n = min(slots, len(lefts))
+    slam, packed = start(cfg, lefts[:n], rights[:n], slots, 1, device, args.warmup)
+    for pk in packed:
+        slam.submit_packed(pk)
+    slam.wait()
+    cams = [behind(slam.pose(s), cols, rows) for s in range(slots)]
+    style = hip_lib.scene_style(cols=cols, rows=rows, pixel="rgba8")
+    pitch, image_bytes = hip_lib.scene_size(style)
+    dst = torch.empty(slots * image_bytes, dtype=torch.uint8, device=device)
+    offsets = [i * image_bytes for i in range(slots)]
+    h = hip_lib.Handle(device.index, 1024)
+    empty = h.pack_scene([(cols, rows, [], None)] * slots, cams, offsets)
+    out = {"slots": slots, "picture": [cols, rows], "point_size": args.cloud_point_size, "atomic_rate_bytes_per_s": ATOMIC_RATE,
+           "warmup_steps": args.warmup, "steps": {}}
+    no_spans = h.pack_scene_spans([[] for _ in range(slots)])
+    ms, all_ms = event_ms(lambda: h.render_scene_clouds_packed(empty, no_spans, style, args.cloud_point_size, dst), args.repeats)
+    out["tiles_only"] = {"call_ms": ms, "call_ms_all": all_ms}
+    plain = slam.submit_scenes(camera=cams, device=True, style=style).wait()
+    out["job_without_layer"] = dict(zip(("job_ms", "job_ms_all"), median_ms(device, lambda: plain.submit().wait(), args.repeats)))
+    for step in steps:
+        cloud = slam.export_cloud("frames", None, step=step, layout="organized", device=True)
+        per = cloud.points_per_slot
+        rec = cloud.points_buffer.view(torch.int32).reshape(-1, 4)
+        spans = h.pack_scene_spans([[(cloud.points_buffer[i * per:].data_ptr(), per)] for i in range(slots)])
+        call = lambda: h.render_scene_clouds_packed(empty, spans, style, args.cloud_point_size, dst)
+        call()
+        ms, all_ms = event_ms(call, args.repeats)
+        keys = drawn = 0
+        for i in range(slots):
+            k, d = offered_keys(rec[i * per:(i + 1) * per], cams[i], cols, rows, args.cloud_point_size)
+            keys, drawn = keys + k, drawn + d
+        leg = {"records": slots * per, "records_per_slot": per, "kept": int(cloud.segments["n_points"].sum()), "drawn": drawn, "keys_offered": keys,
+               "call_ms": ms, "call_ms_all": all_ms, "records_per_s": slots * per / (ms * 1e-3), "atomic_bytes_per_s": 8 * keys / (ms * 1e-3),
+               "fraction_of_atomic_rate": 8 * keys / (ms * 1e-3) / ATOMIC_RATE, "pieces": slots * ((per + 1023) // 1024),
+               "tiles": slots * ((cols + 63) // 64) * ((rows + 15) // 16)}
+        # the form the splat pass replaces: every tile walks the kept records as one keyframe set of its image
+        sets, keep = [], []
+        for i in range(slots):
+            r = rec[i * per:(i + 1) * per]
+            r = r[((r[:, 3] >> 24) & 0x80) == 0]
+            z = torch.zeros(len(r), dtype=torch.int32, device=device)
+            planes = {"kps3d": r[:, :3].contiguous(), "flags": z, "keyframe_id": z, "inlier_count": z, "color": (r[:, 3] & 0xffffff).contiguous()}
+            keep.append(planes)
+            sets.append((cols, rows, [(len(r), 0, planes)], None))
+        walked = h.pack_scene(sets, cams, offsets)
+        wstyle = hip_lib.scene_style(cols=cols, rows=rows, pixel="rgba8", point_size=args.cloud_point_size)
+        h.render_scene_packed(walked, wstyle, dst)
+        wms, wall = event_ms(lambda: h.render_scene_packed(walked, wstyle, dst), max(3, args.repeats // 3))
+        leg["walked_by_every_tile"] = {"call_ms": wms, "call_ms_all": wall, "projections": leg["kept"] * ((cols + 63) // 64) * ((rows + 15) // 16)}
+        # the pile: one slot's record count on one pixel of one image, distinct depths
+        pile = torch.zeros((per, 4), dtype=torch.float32, device=device)
+        pile[:, 2] = 1.0 + torch.arange(per, device=device, dtype=torch.float32) / (2.0 * per)
+        pile = pile[torch.randperm(per, device=device)].contiguous()
+        eye = hip_lib.scene_look_at((0, 0, 0), (0, 0, 1), (0, -1, 0), 60.0, cols, rows, 0.05)
+        one = h.pack_scene([(cols, rows, [], None)], [eye], [0])
+        pile_spans = h.pack_scene_spans([[(pile.data_ptr(), per)]])
+        pcall = lambda: h.render_scene_clouds_packed(one, pile_spans, style, 1, dst)
+        pcall()
+        pms, pall = event_ms(pcall, args.repeats)
+        ems, eall = event_ms(lambda: h.render_scene_clouds_packed(one, h.pack_scene_spans([[]]), style, 1, dst), args.repeats)
+        leg["pile"] = {"records": per, "call_ms": pms, "call_ms_all": pall, "one_image_without_spans_ms": ems}
+        # the job: the cloud job alone, and the scene job with the layer
+        leg["cloud_job"] = dict(zip(("job_ms", "job_ms_all"), median_ms(device, lambda: cloud.submit().wait(), args.repeats)))
+        sc = slam.submit_scenes(camera=cams, device=True, style=style, dense=dict(what="frames", step=step, point_size=args.cloud_point_size)).wait()
+        leg["job_with_layer"] = dict(zip(("job_ms", "job_ms_all"), median_ms(device, lambda: sc.submit().wait(), args.repeats)))
+        leg["live_points"] = int(sc.cloud_info["live_points"].sum())
+        out["steps"][str(step)] = leg
+        print(json.dumps({str(step): leg}), file=sys.stderr, flush=True)
+        del cloud, sc, keep, walked
+    h.close()
+    out["device_GB"] = slam.memory().device_bytes / 1e9
+    slam.close()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--clouds", default=None, metavar="STEPS", help="measure the cloud points at these lattice steps (e.g. 1,2,4) and nothing else")
+    ap.add_argument("--cloud-slots", type=int, default=16)
+    ap.add_argument("--cloud-point-size", type=int, default=2)
     ap.add_argument("--slots", type=int, default=256)
     ap.add_argument("--kernel-only", action="store_true", help="one job per size and nothing timed: for a kernel trace")
     ap.add_argument("--legs", default="256:1", help="slots:groups per pipelined leg (groups 0: the ctx's default); '' for none")
@@ -233,7 +355,19 @@ def main():
     device = torch.device("cuda", 0)
     legs = [tuple(int(x) for x in l.split(":")) for l in args.legs.split(",") if l] if not args.kernel_only else []
     n_loops = min(max([s for s, _ in legs] + [args.slots]), args.loops)
+    if args.clouds:
+        n_loops = min(args.cloud_slots, args.loops)
     cfg, lefts, rights = bench.render_loops("euroc", list(range(n_loops)), args.loop_frames, device)
+    if args.clouds:
+        out = {"metric": "scene_cloud_bench", "config": "euroc", "hw_queues": int(os.environ["GPU_MAX_HW_QUEUES"]),
+               "clouds": clouds_leg(args, device, cfg, lefts, rights, [int(x) for x in args.clouds.split(",")])}
+        text = json.dumps(out)
+        path = args.out or os.path.join(ROOT, "profiles", "scene_cloud_bench.json")
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        with open(path, "w") as f:
+            f.write(text + "\n")
+        print(text, flush=True)
+        return
     out = {"metric": "scene_bench", "config": "euroc", "hbm_peak_bytes_per_s": HBM_PEAK,
            "hw_queues": int(os.environ["GPU_MAX_HW_QUEUES"]), "job": job_leg(args, device, cfg, lefts, rights), "legs": []}
     print(json.dumps(out["job"]), file=sys.stderr, flush=True)        # (progress)
