@@ -1445,6 +1445,212 @@ int svo_render_scene_clouds(svo_handle *h, int n, const svo_scene_src *src, cons
                             const int32_t *n_spans, const svo_scene_camera *cameras, const int64_t *offset,
                             const svo_scene_style *style, int32_t point_size, uint8_t *pixels);
 
+/* ---- voxel maps: svo_map_point records fused into a sparse voxel grid ------------
+ * "clouds" gives one cloud per frame or keyframe. A voxel map is what they add up to: a hash table in device memory,
+ * bounded in size, that holds every surface once and averages the records that fell into the same voxel. It takes
+ * svo_map_point records from anywhere (clouds, svo_export_map, a caller's own) and gives svo_map_point records back,
+ * so every consumer of those reads it. The fusion is stated in integer arithmetic: integer adds, a max and the claim
+ * of a key commute, so a map's content does not depend on the order of arrival and an extraction, which sorts by
+ * key, gives the same bytes in every run. No float atomic is used.
+ *
+ * A map has a voxel edge `voxel` (float32, finite, > 0), capacity = 1 << log2_capacity entries (6 .. 26 here) and
+ * drop_flags (SVO_IGNORE_* bits only). It is svo_voxel_map_bytes(log2_capacity) = 256 + 40 * capacity bytes of device
+ * memory, 16-byte aligned: a header, and per entry
+ *   key u64;  count, sx, sy, sz, sr, sg, sb, last u32          an empty entry: key = ~0, everything else 0
+ * The header holds a magic word, the params and the counters of svo_voxel_map_info. A map is valid from its
+ * svo_voxel_clear on; every other entry rejects a map whose header does not hold exactly the params it is given.
+ *
+ * Key of a record (x, y, z, color, flags). Per coordinate c, in float32, each operation rounded once:
+ *   t = c / voxel;  q = floorf(t)
+ * The record is OUTSIDE unless fabsf(q) < 1048576.0f holds for all three coordinates (so a NaN or an infinity is
+ * outside). Otherwise
+ *   i = (int)q + 1048576                       1 <= i < 2^21
+ *   o = min(255u, (uint32_t)((t - q) * 256.0f))  the sub-voxel offset
+ *   key = ix << 42 | iy << 21 | iz
+ *
+ * Skipped records. A record with flags & SVO_CLOUD_DROPPED or flags & drop_flags is never offered: it changes
+ * nothing and counts nowhere.
+ *
+ * Fusing an offered record with stamp s (a u32 of the span it comes from). An outside record only counts in
+ * n_outside. Otherwise the entry of its key is found or claimed (n_voxels += 1 when claimed) and
+ *   count += 1;  sx += ox, sy += oy, sz += oz;  sr += color[0], sg += color[1], sb += color[2];  last = max(last, s)
+ * and n_fused += 1. Every sum is modulo 2^32: a voxel is meaningful up to 2^32 / 255 = 16843009 records; a wrapped
+ * sum is still the same in every run.
+ *
+ * Placement (a diagnostic fact, so that tests can craft probe chains; callers may not rely on where an entry lies):
+ *   home = (key * 0x9E3779B97F4A7C15) >> (64 - log2_capacity)   (the product modulo 2^64)
+ * and linear probing, step +1 modulo capacity.
+ *
+ * Load bound. A fuse is admitted only if, for every map it names,
+ *   n_voxels + (records of all spans of this call into that map) <= capacity - capacity / 4
+ * with n_voxels the header's. The check is on the bound (every record might claim an entry; skipped and outside
+ * records count) and is made on the host before any launch: the rule of SVO_MAP_TOO_SMALL. A probe therefore always
+ * ends and no record is lost to a full table; `overflow` counts records whose probe visited every entry, and stays 0.
+ *
+ * Extraction with a filter (min_count, min_stamp): an entry is kept iff count >= max(1, min_count) and
+ * last >= min_stamp. The kept entries leave in ascending key order (lexicographic in ix, iy, iz), each as one
+ * svo_map_point:
+ *   x = (float)(((double)(ix - 1048576) + ((double)sx / (double)count + 0.5) / 256.0) * (double)voxel)
+ * in double, each operation rounded once (no fused multiply-add), one rounding to float32; y, z alike;
+ *   color[k] = min(255, (sum_k + count / 2) / count)  in 64-bit integers;  flags = 0.
+ *
+ * How it runs (voxel.hip): the fuse is one launch for many spans into many maps, one lane per record; the lanes of a
+ * wavefront that hold the same key elect a leader, which alone probes (the claim is a 64-bit compare-and-swap of ~0)
+ * and adds the group's sums. Probe and election loops are bounded (capacity and 64 rounds); nothing spins or waits.
+ * The extraction counts, scans, writes (key, entry) pairs, sorts them by key and gathers. */
+typedef struct svo_voxel_params {   /* 16 bytes */
+    float    voxel;                 /* the voxel edge: finite, > 0                                          */
+    int32_t  log2_capacity;         /* stage entries: 6 .. 26                                               */
+    uint32_t drop_flags;            /* records with (flags & drop_flags) != 0 are skipped; SVO_IGNORE_* bits only */
+    int32_t  _reserved;             /* 0                                                                    */
+} svo_voxel_params;
+
+typedef struct svo_voxel_map {      /* 24 bytes: a map and the params it was cleared with                   */
+    void            *data;          /* device, 16-byte aligned, svo_voxel_map_bytes(params.log2_capacity)   */
+    svo_voxel_params params;
+} svo_voxel_map;
+
+typedef struct svo_voxel_span {     /* 24 bytes */
+    const svo_map_point *points;    /* device, 16-byte aligned (n = 0: not read)                            */
+    int64_t  n;                     /* >= 0 records                                                         */
+    int32_t  map;                   /* index into the call's maps                                           */
+    uint32_t stamp;                 /* what `last` of the entries it reaches is raised to                   */
+} svo_voxel_span;
+
+typedef struct svo_voxel_map_info { /* 48 bytes */
+    float    voxel;
+    int32_t  log2_capacity;
+    uint32_t drop_flags;
+    int32_t  _pad;
+    int64_t  n_voxels;              /* claimed entries                                                      */
+    int64_t  n_fused;               /* records added to an entry                                            */
+    int64_t  n_outside;             /* offered records that were outside                                    */
+    int64_t  overflow;              /* records whose probe visited every entry (0: see the load bound)      */
+} svo_voxel_map_info;
+
+typedef struct svo_voxel_filter {   /* 16 bytes */
+    uint32_t min_count;             /* kept: count >= max(1, min_count)                                     */
+    uint32_t min_stamp;             /* kept: last >= min_stamp                                              */
+    int32_t  _reserved[2];          /* 0                                                                    */
+} svo_voxel_filter;
+
+/* the bytes of a map, without a GPU; 0 for a log2_capacity outside 6 .. 26 */
+int64_t svo_voxel_map_bytes(int log2_capacity);
+/* Stage entries, complete on return. SVO_ERR_INVALID with nothing written: bad params (voxel not finite or <= 0,
+ * log2_capacity outside 6 .. 26, drop_flags bits that are no SVO_IGNORE_* bit, _reserved != 0), a NULL or not 16-byte
+ * aligned map or records, a negative n, a span that names no map of the call, a map named twice in one call, and (all
+ * but svo_voxel_clear) a map that was not cleared with the same params.
+ * svo_voxel_clear: every entry empty, the counters 0, the header holds the params. */
+int svo_voxel_clear(svo_handle *h, void *map, const svo_voxel_params *params);
+/* n_spans spans into n_maps maps in one launch (host arrays). SVO_ERR_CAPACITY with nothing written if the load bound
+ * of any named map fails. */
+int svo_voxel_fuse(svo_handle *h, int n_spans, const svo_voxel_span *spans, int n_maps, const svo_voxel_map *maps);
+/* the params and counters the map's header holds */
+int svo_voxel_info(svo_handle *h, const void *map, svo_voxel_map_info *info);
+/* the kept entries as records points[0, *n_points) (device, 16-byte aligned); nothing else is written. filter == NULL
+ * keeps every entry. points == NULL only counts. SVO_ERR_CAPACITY if the kept count exceeds `capacity`: *n_points is
+ * set and nothing is written. The (key, entry) pairs and the sort's temporary storage live in the handle's
+ * workspace: 24 bytes per kept entry and what the sort asks for. */
+int svo_voxel_extract(svo_handle *h, const svo_voxel_map *map, const svo_voxel_filter *filter, svo_map_point *points,
+                      int64_t capacity, int64_t *n_points);
+
+/* Voxel maps inside a ctx: every slot can own one, and three queued jobs fuse the slots' dense clouds into them, read
+ * them out and clear them.
+ *
+ * What a map is not. A map is an accumulator of the SLOT, not state of the sequence that runs in it: only fuse and
+ * clear jobs change it. svo_ctx_restart_sequences, svo_submit_load, a trim, a rig assignment and the end of a
+ * sequence leave it alone; snapshots do not carry it. A caller that wants a map per run clears it at the restart.
+ *
+ * svo_ctx_set_voxel_maps gives each named slot (seqs == NULL: every slot) a cleared map of its own with these params
+ * (log2_capacity 10 .. 26), replacing one it had; params == NULL takes the maps away. It is a setter: it waits for the
+ * queues, like svo_ctx_set_keyframe_window. A map's svo_voxel_map_bytes count in svo_memory.device_bytes; a ctx that
+ * never sets maps allocates, launches and copies nothing more. svo_get_voxel_map_info waits too; SVO_ERR_INVALID for a
+ * slot without a map. */
+int svo_ctx_set_voxel_maps(svo_ctx *ctx, const int *seqs, int n, const svo_voxel_params *params);
+int svo_get_voxel_map_info(svo_ctx *ctx, int seq, svo_voxel_map_info *info);
+
+/* svo_submit_fuse_clouds is queued like a cloud job: it sees what was submitted before it and nothing after, only the
+ * groups that own a named slot get work, and the slots' sequences are not changed. Per named slot it computes exactly
+ * the records that svo_submit_export_cloud_checked(what, ..., style with layout = SVO_CLOUD_ORGANIZED and frame =
+ * SVO_CLOUD_WORLD, check) delivers for that slot at that queue position (the same launches, in device mode, into a
+ * block of the group; they never leave the device) and fuses them with `stamp` into the slot's map: one fuse launch
+ * per chunk of slots (the chunk of "clouds", with 16 * points_per_slot more per slot; SVO_CLOUD_CHUNK_SLOTS lowers it).
+ * info[i] belongs to seqs[i], is host memory and is valid at svo_wait:
+ *   SVO_FUSE_OK      fused. n_offered: the cloud's kept count (its records without SVO_CLOUD_DROPPED); n_fused,
+ *                    n_outside: what this job added to the map's counters; n_voxels: the map's entries afterwards
+ *   SVO_FUSE_NONE    the cloud job would give SVO_CLOUD_NONE (no frame, or no keyframe): nothing is fused
+ *   SVO_FUSE_NO_MAP  the slot has no map (this comes first)
+ *   SVO_FUSE_FULL    n_voxels + points_per_slot > capacity - capacity / 4 (the load bound, on the bound, checked before
+ *                    any launch with the ctx's host mirror of n_voxels): nothing is fused, the ctx does not fail. The
+ *                    caller exports the map and sets a larger one.
+ * The mirror of a map's counters is refreshed from the headers the job copies back anyway.
+ * Rejected with SVO_ERR_INVALID and nothing queued: everything svo_submit_export_cloud_checked rejects of what, seqs,
+ * style and check; style->frame != SVO_CLOUD_WORLD; style->layout != 0; a NULL info.
+ * Memory, per group, made by the first fuse job and replaced when outgrown (svo_memory.device_bytes): the records of
+ * a chunk, 16 * points_per_slot per slot, and the chunk's tables (up256(24 m) + up256(64 m) + up256(32 m) bytes for m
+ * slots, device and pinned), beside the cloud job's own blocks. */
+enum { SVO_FUSE_OK = 0, SVO_FUSE_NONE = 1, SVO_FUSE_NO_MAP = 2, SVO_FUSE_FULL = 3 };
+
+typedef struct svo_fuse_info {      /* 64 bytes, host, one per named slot */
+    int32_t seq, run;               /* slot and ordinal of its run                                          */
+    int32_t frame_id;               /* of the slot's current frame; -1: empty slot                          */
+    int32_t keyframe_id;            /* LAST_KEYFRAMES: the keyframe used (-1: none); FRAMES: -1             */
+    int32_t status;                 /* SVO_FUSE_*                                                           */
+    int32_t n_offered;              /* the cloud's kept count                                               */
+    int32_t n_fused, n_outside;     /* added by this job                                                    */
+    int64_t n_voxels;               /* of the map after the job (NO_MAP: 0)                                 */
+    float   pose[6];                /* the pose used, as svo_cloud_segment.pose                             */
+} svo_fuse_info;
+
+int svo_submit_fuse_clouds(svo_ctx *ctx, int what, const int *seqs, int n, const svo_cloud_style *style,
+                           const svo_stereo_check *check, uint32_t stamp, svo_fuse_info *info);
+int svo_fuse_clouds(svo_ctx *ctx, int what, const int *seqs, int n, const svo_cloud_style *style,
+                    const svo_stereo_check *check, uint32_t stamp, svo_fuse_info *info);   /* submit + wait */
+
+/* svo_submit_export_voxel_maps follows svo_submit_export_map: a region per named slot, a shared filter, a 64-byte
+ * segment per slot in host memory, records in host or device memory (mem). A slot's entries are kept iff
+ * count >= max(1, filter->min_count) and last >= max(filter->min_stamp, region.min_stamp), and leave in key order into
+ * points[first_point, first_point + n_points): exactly those records are written. A slot whose n_voxels (the host
+ * mirror: the bound, checked before any launch) exceeds its point_capacity comes back SVO_VOXEL_TOO_SMALL with
+ * n_voxels the capacity needed and nothing else written; a slot without a map SVO_VOXEL_NO_MAP. Host mode stages the
+ * records in a block of the group and copies the kept prefix out. Rejected with SVO_ERR_INVALID: a bad mem, a slot
+ * out of range or named twice, a negative region field or a non-zero _reserved, points not 16-byte aligned, a region
+ * with a capacity and NULL points. Memory (svo_memory.device_bytes), per group: 4 bytes per tile of 256 entries of the
+ * largest map, 24 bytes per kept entry and what the sort asks for, and in host mode 16 bytes per kept entry. */
+enum { SVO_VOXEL_OK = 0, SVO_VOXEL_NO_MAP = 1, SVO_VOXEL_TOO_SMALL = 2 };
+
+typedef struct svo_voxel_region {   /* 32 bytes */
+    int64_t  first_point;           /* the slot's records start at dst->points[first_point]                 */
+    int64_t  point_capacity;        /* records the region holds                                             */
+    uint32_t min_stamp;             /* this slot's entries with last < min_stamp are not kept               */
+    int32_t  _reserved[3];          /* 0                                                                    */
+} svo_voxel_region;
+
+typedef struct svo_voxel_segment {  /* 64 bytes, host, one per named slot */
+    int32_t seq, run;
+    int32_t frame_id;
+    int32_t status;                 /* SVO_VOXEL_*                                                          */
+    int64_t first_point;            /* the region's                                                         */
+    int64_t n_points;               /* records written (0 unless SVO_VOXEL_OK)                              */
+    int64_t n_voxels;               /* the map's entries: the point_capacity that is always enough          */
+    int64_t n_fused;                /* the map's counter                                                    */
+    float   voxel;
+    int32_t log2_capacity;
+    int64_t _pad;
+} svo_voxel_segment;
+
+typedef struct svo_voxel_dst {
+    svo_voxel_segment *segments;    /* HOST memory always, >= n entries                                     */
+    svo_map_point     *points;      /* host or device (mem), 16-byte aligned; NULL: every point_capacity is 0 */
+} svo_voxel_dst;
+
+int svo_submit_export_voxel_maps(svo_ctx *ctx, const int *seqs, int n, const svo_voxel_region *regions,
+                                 const svo_voxel_filter *filter, const svo_voxel_dst *dst, int mem);
+int svo_export_voxel_maps(svo_ctx *ctx, const int *seqs, int n, const svo_voxel_region *regions,
+                          const svo_voxel_filter *filter, const svo_voxel_dst *dst, int mem);   /* submit + wait */
+/* queued: the maps of the named slots become empty (a slot without a map is skipped) */
+int svo_submit_clear_voxel_maps(svo_ctx *ctx, const int *seqs, int n);
+
 /* ---- snapshots: the sequence state of a slot saved, loaded, moved between ctxs ------------
  * The reference has no checkpoint or resume (a StereoSlam lives and dies with its process). A snapshot is
  * everything the next frame of a slot depends on and everything its getters return, so that a sequence saved

@@ -1,0 +1,162 @@
+// svo_capi_voxel.hip — the stage entries of the voxel maps (include/svo_hip.h, "voxel maps"): clear, fuse, info and
+// extract on maps in the caller's device memory, complete on return. Every check is made on the host before any
+// launch (the params, the alignment, the header of each named map, the load bound), with the arithmetic of
+// svo_voxel_plan.hpp; the kernels are voxel.hip's.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "svo_handle.hpp"
+#include "svo_voxel_plan.hpp"
+
+using namespace svo;
+
+namespace svo {
+
+int voxel_check_params(const svo_voxel_params* p, bool ctx, const char* who) {
+    if (!p) return svo_set_error(SVO_ERR_INVALID, "%s: no params", who);
+    if (!(p->voxel > 0.f) || !(p->voxel <= FLT_MAX)) return svo_set_error(SVO_ERR_INVALID, "%s: voxel must be finite and > 0", who);
+    if (!voxel_log2_ok(p->log2_capacity, ctx))
+        return svo_set_error(SVO_ERR_INVALID, "%s: log2_capacity %d outside %d .. %d", who, p->log2_capacity,
+                             ctx ? VOXEL_LOG2_MIN_CTX : VOXEL_LOG2_MIN, VOXEL_LOG2_MAX);
+    if ((p->drop_flags & ~(uint32_t)(SVO_IGNORE_DURING_REFINEMENT | SVO_IGNORE_COMPLETELY | SVO_IGNORE_TEMPORARY)) || p->_reserved != 0)
+        return svo_set_error(SVO_ERR_INVALID, "%s: drop_flags 0x%x has unknown bits, or _reserved is not 0", who, p->drop_flags);
+    return SVO_OK;
+}
+
+// the header of a map that was cleared with exactly these params
+bool voxel_header_matches(const VoxelHeader& hd, const svo_voxel_params& p) {
+    return hd.magic == VOXEL_MAGIC && hd.log2_capacity == p.log2_capacity && memcmp(&hd.voxel, &p.voxel, 4) == 0 && hd.drop_flags == p.drop_flags;
+}
+
+}  // namespace svo
+
+static VoxelMapDev map_dev(void* data, const svo_voxel_params& p) {
+    return VoxelMapDev{static_cast<uint8_t*>(data), p.voxel, p.log2_capacity, p.drop_flags, 0};
+}
+
+static int check_map(const svo_voxel_map* m, const char* who, int i) {
+    if (!m) return svo_set_error(SVO_ERR_INVALID, "%s: no map", who);
+    if (const int rc = voxel_check_params(&m->params, false, who)) return rc;
+    if (!m->data || ((uintptr_t)m->data & 15)) return svo_set_error(SVO_ERR_INVALID, "%s: map %d is NULL or not 16-byte aligned", who, i);
+    return SVO_OK;
+}
+
+extern "C" int64_t svo_voxel_map_bytes(int log2_capacity) { return (int64_t)voxel_map_bytes(log2_capacity); }
+
+extern "C" int svo_voxel_clear(svo_handle* h, void* map, const svo_voxel_params* params) {
+    CHECK_H(h);
+    const svo_voxel_map m{map, params ? *params : svo_voxel_params{}};
+    if (!params) return svo_set_error(SVO_ERR_INVALID, "svo_voxel_clear: no params");
+    if (const int rc = check_map(&m, "svo_voxel_clear", 0)) return rc;
+    launch_voxel_clear(map_dev(map, *params), h->stream);
+    return finish_launch(h);
+}
+
+extern "C" int svo_voxel_info(svo_handle* h, const void* map, svo_voxel_map_info* info) {
+    CHECK_H(h);
+    if (!map || ((uintptr_t)map & 15) || !info) return svo_set_error(SVO_ERR_INVALID, "svo_voxel_info: map is NULL or not 16-byte aligned, or no info");
+    VoxelHeader hd;
+    HIP_TRY(hipMemcpyAsync(&hd, map, sizeof(hd), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    const svo_voxel_params p{hd.voxel, hd.log2_capacity, hd.drop_flags, 0};
+    if (hd.magic != VOXEL_MAGIC || voxel_check_params(&p, false, "svo_voxel_info") != SVO_OK)
+        return svo_set_error(SVO_ERR_INVALID, "svo_voxel_info: the map was never cleared");
+    *info = svo_voxel_map_info{hd.voxel, hd.log2_capacity, hd.drop_flags, 0, (int64_t)hd.n_voxels, (int64_t)hd.n_fused, (int64_t)hd.n_outside,
+                               (int64_t)hd.overflow};
+    return SVO_OK;
+}
+
+extern "C" int svo_voxel_fuse(svo_handle* h, int n_spans, const svo_voxel_span* spans, int n_maps, const svo_voxel_map* maps) {
+    CHECK_H(h);
+    if (n_spans < 0 || n_maps < 0 || (n_spans > 0 && !spans) || (n_maps > 0 && !maps))
+        return svo_set_error(SVO_ERR_INVALID, "svo_voxel_fuse: bad arguments");
+    std::vector<VoxelMapDev> dmaps((size_t)n_maps);
+    std::vector<const void*> seen;
+    for (int i = 0; i < n_maps; i++) {
+        if (const int rc = check_map(&maps[i], "svo_voxel_fuse", i)) return rc;
+        dmaps[(size_t)i] = map_dev(maps[i].data, maps[i].params);
+        seen.push_back(maps[i].data);
+    }
+    std::sort(seen.begin(), seen.end());
+    if (std::adjacent_find(seen.begin(), seen.end()) != seen.end()) return svo_set_error(SVO_ERR_INVALID, "svo_voxel_fuse: a map is named twice");
+    std::vector<VoxelSpanDev> dspans;
+    std::vector<uint64_t> records((size_t)n_maps, 0);
+    int64_t tiles = 0;
+    for (int i = 0; i < n_spans; i++) {
+        const svo_voxel_span& s = spans[i];
+        if (!voxel_span_ok((uintptr_t)s.points, s.n)) return svo_set_error(SVO_ERR_INVALID, "svo_voxel_fuse: span %d: n < 0, or records NULL or not 16-byte aligned", i);
+        if (s.map < 0 || s.map >= n_maps) return svo_set_error(SVO_ERR_INVALID, "svo_voxel_fuse: span %d names map %d of %d", i, s.map, n_maps);
+        if (!voxel_add_records(records[(size_t)s.map], s.n)) return svo_set_error(SVO_ERR_CAPACITY, "svo_voxel_fuse: span %d: too many records", i);
+        if (s.n == 0) continue;
+        dspans.push_back(VoxelSpanDev{s.points, s.n, tiles, s.map, s.stamp});
+        tiles += voxel_span_tiles(s.n);
+        if (tiles > INT32_MAX) return svo_set_error(SVO_ERR_CAPACITY, "svo_voxel_fuse: too many records for one call");
+    }
+    if (n_maps == 0) return SVO_OK;
+    // the tables of the call: the maps, their headers as the device holds them now, the spans
+    const size_t maps_bytes = voxel_up256(sizeof(VoxelMapDev) * dmaps.size()), heads_bytes = voxel_up256(sizeof(VoxelHeader) * dmaps.size());
+    if (const int rc = h->voxel_ws.reserve(maps_bytes + heads_bytes + voxel_up256(sizeof(VoxelSpanDev) * dspans.size()), h->stream)) return rc;
+    VoxelMapDev* d_maps = reinterpret_cast<VoxelMapDev*>(h->voxel_ws.ptr.get());
+    VoxelHeader* d_heads = reinterpret_cast<VoxelHeader*>(h->voxel_ws.ptr.get() + maps_bytes);
+    VoxelSpanDev* d_spans = reinterpret_cast<VoxelSpanDev*>(h->voxel_ws.ptr.get() + maps_bytes + heads_bytes);
+    std::vector<VoxelHeader> heads(dmaps.size());
+    HIP_TRY(hipMemcpyAsync(d_maps, dmaps.data(), sizeof(VoxelMapDev) * dmaps.size(), hipMemcpyHostToDevice, h->stream));
+    launch_voxel_headers(d_maps, n_maps, d_heads, h->stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(heads.data(), d_heads, sizeof(VoxelHeader) * heads.size(), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    for (int i = 0; i < n_maps; i++)
+        if (!voxel_header_matches(heads[(size_t)i], maps[i].params))
+            return svo_set_error(SVO_ERR_INVALID, "svo_voxel_fuse: map %d was not cleared with these params", i);
+    for (int i = 0; i < n_maps; i++)
+        if (!voxel_load_ok(heads[(size_t)i].n_voxels, records[(size_t)i], maps[i].params.log2_capacity))
+            return svo_set_error(SVO_ERR_CAPACITY, "svo_voxel_fuse: map %d: %llu voxels + %llu records exceed %llu (SVO_MAP_TOO_SMALL's rule: the bound)", i,
+                                 heads[(size_t)i].n_voxels, (unsigned long long)records[(size_t)i],
+                                 (unsigned long long)voxel_load_limit(maps[i].params.log2_capacity));
+    if (dspans.empty()) return SVO_OK;
+    HIP_TRY(hipMemcpyAsync(d_spans, dspans.data(), sizeof(VoxelSpanDev) * dspans.size(), hipMemcpyHostToDevice, h->stream));
+    // (SVO_VOXEL_LANE_ATOMICS: the other form of the kernel, for tools/voxel_bench.py and the tests of its equality)
+    const char* form = std::getenv("SVO_VOXEL_LANE_ATOMICS");
+    launch_voxel_fuse(d_spans, (int)dspans.size(), tiles, d_maps, form && std::atoi(form) != 0, h->stream);
+    return finish_launch(h);
+}
+
+extern "C" int svo_voxel_extract(svo_handle* h, const svo_voxel_map* map, const svo_voxel_filter* filter, svo_map_point* points,
+                                 int64_t capacity, int64_t* n_points) {
+    CHECK_H(h);
+    if (const int rc = check_map(map, "svo_voxel_extract", 0)) return rc;
+    if (!n_points) return svo_set_error(SVO_ERR_INVALID, "svo_voxel_extract: no n_points");
+    if (filter && (filter->_reserved[0] != 0 || filter->_reserved[1] != 0)) return svo_set_error(SVO_ERR_INVALID, "svo_voxel_extract: a _reserved is not 0");
+    if (points && (((uintptr_t)points & 15) || capacity < 0)) return svo_set_error(SVO_ERR_INVALID, "svo_voxel_extract: points not 16-byte aligned, or capacity < 0");
+    const VoxelFilterDev f{filter ? std::max<uint32_t>(1u, filter->min_count) : 1u, filter ? filter->min_stamp : 0u};
+    const VoxelMapDev mp = map_dev(map->data, map->params);
+    VoxelHeader hd;
+    HIP_TRY(hipMemcpyAsync(&hd, map->data, sizeof(hd), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (!voxel_header_matches(hd, map->params)) return svo_set_error(SVO_ERR_INVALID, "svo_voxel_extract: the map was not cleared with these params");
+    if (const int rc = h->voxel_ws.reserve(voxel_offsets_bytes(mp.log2_capacity), h->stream)) return rc;
+    int32_t* tile_offsets = reinterpret_cast<int32_t*>(h->voxel_ws.ptr.get());
+    launch_voxel_count(mp, f, tile_offsets, h->stream);
+    HIP_TRY(hipGetLastError());
+    int32_t kept = 0;
+    HIP_TRY(hipMemcpyAsync(&kept, tile_offsets + voxel_map_tiles(mp.log2_capacity), sizeof(kept), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    *n_points = kept;
+    if (!points) return SVO_OK;
+    if (!voxel_extract_fits(kept, capacity)) return svo_set_error(SVO_ERR_CAPACITY, "svo_voxel_extract: %d voxels kept, capacity %lld", kept, (long long)capacity);
+    if (kept == 0) return SVO_OK;
+    size_t temp_bytes = 0;
+    if (const int rc = voxel_sort_temp_bytes((size_t)kept, &temp_bytes)) return rc;
+    const VoxelExtractPlan plan = voxel_extract_plan((uint64_t)kept, temp_bytes);
+    if (const int rc = h->voxel_sort_ws.reserve(plan.bytes, h->stream)) return rc;
+    uint8_t* ws = h->voxel_sort_ws.ptr.get();
+    if (const int rc = launch_voxel_extract(mp, f, tile_offsets, (size_t)kept, reinterpret_cast<uint64_t*>(ws + plan.keys_in),
+                                            reinterpret_cast<uint64_t*>(ws + plan.keys_out), reinterpret_cast<uint32_t*>(ws + plan.index_in),
+                                            reinterpret_cast<uint32_t*>(ws + plan.index_out), ws + plan.sort_temp, temp_bytes, points, h->stream))
+        return rc;
+    return finish_launch(h);
+}

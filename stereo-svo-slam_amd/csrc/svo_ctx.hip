@@ -130,9 +130,32 @@ struct svo_ctx {
         std::vector<svo_pose_sample> samples;
         std::vector<float*> filtered;
     };
+    // the group's share of an svo_submit_fuse_clouds: its named slots (indices in the group) in named order and the
+    // info of the job each one fills
+    struct FuseClouds {
+        int what = 0;
+        std::vector<int> seqs, seg;
+        svo_cloud_style style{};
+        bool has_check = false;
+        svo_stereo_check check{};
+        uint32_t stamp = 0;
+        svo_fuse_info* info = nullptr;
+    };
+    // the group's share of an svo_submit_export_voxel_maps, as MapExport
+    struct VoxelExport {
+        int mem = 0;
+        std::vector<int> seqs, seg;
+        std::vector<svo_voxel_region> regions;
+        svo_voxel_filter filter{};
+        svo_voxel_dst dst{};
+    };
+    // the group's share of an svo_submit_clear_voxel_maps: indices in the group
+    struct VoxelClear {
+        std::vector<int> seqs;
+    };
     // one entry of a group's queue (the frame set first: a Job{} is one, with nothing allocated)
     using Job = std::variant<Frames, Restart, Trim, RigAssign, Export, MapExport, ViewExport, DisparityExport, CloudExport,
-                             SceneExport, ArExport, Save, Load, PoseUpdates>;
+                             SceneExport, ArExport, Save, Load, PoseUpdates, FuseClouds, VoxelExport, VoxelClear>;
     struct Worker {
         Group g;
         int first = 0, count = 0;
@@ -212,6 +235,15 @@ int run_job(svo_group* g, int, const svo_ctx::Load& j) { return grp_load(g, j.lo
 int run_job(svo_group* g, int, const svo_ctx::PoseUpdates& j) {
     return grp_pose_updates(g, j.seqs.data(), j.counts.data(), (int)j.seqs.size(), j.samples.data(), j.filtered.data());
 }
+
+int run_job(svo_group* g, int seq0, const svo_ctx::FuseClouds& j) {
+    return grp_fuse_clouds(g, j.what, j.seqs.data(), j.seg.data(), (int)j.seqs.size(), seq0, &j.style, j.has_check ? &j.check : nullptr, j.stamp,
+                           j.info);
+}
+int run_job(svo_group* g, int seq0, const svo_ctx::VoxelExport& j) {
+    return grp_export_voxel_maps(g, j.mem, j.seqs.data(), j.seg.data(), j.regions.data(), (int)j.seqs.size(), seq0, &j.filter, &j.dst);
+}
+int run_job(svo_group* g, int, const svo_ctx::VoxelClear& j) { return grp_clear_voxel_maps(g, j.seqs.data(), (int)j.seqs.size()); }
 
 void worker_run_job(svo_ctx::Worker& w, const svo_ctx::Job& job) {
     if (w.err != SVO_OK || w.ctx_failed->load()) return;   // after a failure (any group) the queues are dropped
@@ -637,6 +669,123 @@ extern "C" int svo_submit_export_cloud_checked(svo_ctx* c, int what, const int* 
         if (e.seqs.empty()) continue;
         e.what = what; e.mem = mem; e.style = *style; e.dst = *dst;
         if (check) { e.has_check = true; e.check = *check; }
+        worker_submit(w, std::move(e));
+    }
+    return SVO_OK;
+}
+
+namespace svo { int voxel_check_params(const svo_voxel_params* p, bool ctx, const char* who); }
+
+extern "C" int svo_ctx_set_voxel_maps(svo_ctx* c, const int* seqs, int n, const svo_voxel_params* params) {
+    if (!c || (seqs && n < 0)) return svo_set_error(SVO_ERR_INVALID, "svo_ctx_set_voxel_maps: bad arguments");
+    if (params)
+        if (const int rc = svo::voxel_check_params(params, true, "svo_ctx_set_voxel_maps")) return rc;
+    if (!seqs) n = c->B;
+    const NamedSlots slots{seqs, n};
+    if (const int bad = slots.first_bad(c->B, true); bad >= 0)
+        return svo_set_error(SVO_ERR_INVALID, "svo_ctx_set_voxel_maps: sequence %d is out of range or named twice", slots.at(bad));
+    if (const int rc = ctx_drain(c)) return rc;
+    for (auto& wp : c->workers) {
+        std::vector<int> local;
+        slots.each_in(wp->first, wp->count, [&](int, int l) { local.push_back(l); });
+        if (local.empty()) continue;
+        if (const int rc = grp_set_voxel_maps(wp->g.get(), local.data(), (int)local.size(), params)) return rc;
+    }
+    return SVO_OK;
+}
+
+extern "C" int svo_get_voxel_map_info(svo_ctx* ctx, int seq, svo_voxel_map_info* info) {
+    svo_group* g; int s;
+    if (const int rc = ctx_seq(ctx, seq, &g, &s)) return rc;
+    if (!grp_voxel_map_info(g, s, info)) return svo_set_error(SVO_ERR_INVALID, "svo_get_voxel_map_info: slot %d has no voxel map", seq);
+    return SVO_OK;
+}
+
+extern "C" int svo_submit_fuse_clouds(svo_ctx* c, int what, const int* seqs, int n, const svo_cloud_style* style,
+                                      const svo_stereo_check* check, uint32_t stamp, svo_fuse_info* info) {
+    if (check && check->lr == 0) {                                   // (off: the unchecked job, once the check itself is checked)
+        if (const int rc = svo::lr_check_parse(check, true, "svo_submit_fuse_clouds", nullptr)) return rc;
+        check = nullptr;
+    }
+    if (!c || !info || (what != SVO_EXPORT_FRAMES && what != SVO_EXPORT_LAST_KEYFRAMES) || (seqs && n < 0))
+        return svo_set_error(SVO_ERR_INVALID, "svo_submit_fuse_clouds: bad arguments (what %d)", what);
+    const svo_group* g0 = c->workers[0]->g.get();                    // (every group has the same settings)
+    if (const int rc = grp_check_cloud_style(g0, style, check)) return rc;
+    if (style->frame != SVO_CLOUD_WORLD || style->layout != 0)
+        return svo_set_error(SVO_ERR_INVALID, "svo_submit_fuse_clouds: frame must be SVO_CLOUD_WORLD and layout 0");
+    if (!seqs) n = c->B;
+    const NamedSlots slots{seqs, n};
+    if (const int bad = slots.first_bad(c->B, true); bad >= 0)
+        return svo_set_error(SVO_ERR_INVALID, "svo_submit_fuse_clouds: sequence %d is out of range or named twice", slots.at(bad));
+    if (c->failed.load()) return reject_failed(c, "svo_submit_fuse_clouds");
+    for (auto& wp : c->workers) {
+        svo_ctx::Worker& w = *wp;
+        svo_ctx::FuseClouds e;
+        slots.each_in(w.first, w.count, [&](int i, int local) { e.seqs.push_back(local); e.seg.push_back(i); });
+        if (e.seqs.empty()) continue;
+        e.what = what; e.style = *style; e.stamp = stamp; e.info = info;
+        if (check) { e.has_check = true; e.check = *check; }
+        worker_submit(w, std::move(e));
+    }
+    return SVO_OK;
+}
+
+extern "C" int svo_fuse_clouds(svo_ctx* c, int what, const int* seqs, int n, const svo_cloud_style* style, const svo_stereo_check* check,
+                               uint32_t stamp, svo_fuse_info* info) {
+    const int rc = svo_submit_fuse_clouds(c, what, seqs, n, style, check, stamp, info);
+    return rc ? rc : svo_wait(c);
+}
+
+extern "C" int svo_submit_export_voxel_maps(svo_ctx* c, const int* seqs, int n, const svo_voxel_region* regions,
+                                            const svo_voxel_filter* filter, const svo_voxel_dst* dst, int mem) {
+    if (!c || !dst || !dst->segments || (mem != SVO_MEM_HOST && mem != SVO_MEM_DEVICE) || (seqs && n < 0))
+        return svo_set_error(SVO_ERR_INVALID, "svo_submit_export_voxel_maps: bad arguments (mem %d)", mem);
+    if (!seqs) n = c->B;
+    if (n > 0 && !regions) return svo_set_error(SVO_ERR_INVALID, "svo_submit_export_voxel_maps: no regions");
+    const svo_voxel_filter f = filter ? *filter : svo_voxel_filter{0, 0, {0, 0}};
+    if (f._reserved[0] != 0 || f._reserved[1] != 0) return svo_set_error(SVO_ERR_INVALID, "svo_submit_export_voxel_maps: a _reserved is not 0");
+    if ((uintptr_t)dst->points & 15) return svo_set_error(SVO_ERR_INVALID, "svo_submit_export_voxel_maps: points is not 16-byte aligned");
+    const NamedSlots slots{seqs, n};
+    const int bad = slots.first_bad(c->B, true);
+    for (int i = 0; i < n; i++) {                // (a slot's name is checked before its region)
+        if (i == bad)
+            return svo_set_error(SVO_ERR_INVALID, "svo_submit_export_voxel_maps: sequence %d is out of range or named twice", slots.at(i));
+        const svo_voxel_region& r = regions[i];
+        if (r.first_point < 0 || r.point_capacity < 0 || r._reserved[0] != 0 || r._reserved[1] != 0 || r._reserved[2] != 0)
+            return svo_set_error(SVO_ERR_INVALID, "svo_submit_export_voxel_maps: region %d has a negative field or a non-zero _reserved", i);
+        if (r.point_capacity > 0 && !dst->points)
+            return svo_set_error(SVO_ERR_INVALID, "svo_submit_export_voxel_maps: region %d has a capacity, but points is NULL", i);
+    }
+    if (c->failed.load()) return reject_failed(c, "svo_submit_export_voxel_maps");
+    for (auto& wp : c->workers) {
+        svo_ctx::Worker& w = *wp;
+        svo_ctx::VoxelExport e;
+        slots.each_in(w.first, w.count, [&](int i, int local) { e.seqs.push_back(local); e.seg.push_back(i); e.regions.push_back(regions[i]); });
+        if (e.seqs.empty()) continue;
+        e.mem = mem; e.filter = f; e.dst = *dst;
+        worker_submit(w, std::move(e));
+    }
+    return SVO_OK;
+}
+
+extern "C" int svo_export_voxel_maps(svo_ctx* c, const int* seqs, int n, const svo_voxel_region* regions, const svo_voxel_filter* filter,
+                                     const svo_voxel_dst* dst, int mem) {
+    const int rc = svo_submit_export_voxel_maps(c, seqs, n, regions, filter, dst, mem);
+    return rc ? rc : svo_wait(c);
+}
+
+extern "C" int svo_submit_clear_voxel_maps(svo_ctx* c, const int* seqs, int n) {
+    if (!c || (seqs && n < 0)) return svo_set_error(SVO_ERR_INVALID, "svo_submit_clear_voxel_maps: bad arguments");
+    if (!seqs) n = c->B;
+    const NamedSlots slots{seqs, n};
+    if (const int bad = slots.first_bad(c->B, true); bad >= 0)
+        return svo_set_error(SVO_ERR_INVALID, "svo_submit_clear_voxel_maps: sequence %d is out of range or named twice", slots.at(bad));
+    if (c->failed.load()) return reject_failed(c, "svo_submit_clear_voxel_maps");
+    for (auto& wp : c->workers) {
+        svo_ctx::Worker& w = *wp;
+        svo_ctx::VoxelClear e;
+        slots.each_in(w.first, w.count, [&](int, int local) { e.seqs.push_back(local); });
+        if (e.seqs.empty()) continue;
         worker_submit(w, std::move(e));
     }
     return SVO_OK;

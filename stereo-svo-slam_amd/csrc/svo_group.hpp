@@ -1,7 +1,7 @@
 // svo_group.hpp — one group of sequences as svo_ctx.hip drives it: the opaque interface of svo_group.hip (creation,
 // settings, restarts), svo_group_step.hip (grp_new_images), svo_group_export.hip (grp_export, grp_capacity),
 // svo_group_map.hip (grp_export_map, grp_map_size), svo_group_view.hip (grp_export_views, grp_view_bytes),
-// svo_group_scene.hip (grp_export_scenes, grp_scene_bytes), svo_group_ar.hip (grp_export_ar, grp_ar_bytes), svo_group_dense.hip (grp_export_disparity, grp_disparity_bytes), svo_group_cloud.hip (grp_export_cloud, grp_cloud_points),
+// svo_group_scene.hip (grp_export_scenes, grp_scene_bytes), svo_group_ar.hip (grp_export_ar, grp_ar_bytes), svo_group_dense.hip (grp_export_disparity, grp_disparity_bytes), svo_group_cloud.hip (grp_export_cloud, grp_cloud_points), svo_group_voxel.hip (the voxel maps),
 // svo_group_snapshot.hip (grp_check_snapshot, grp_save, grp_load, grp_snapshot_size) and svo_group_pose.hip
 // (grp_pose_updates).
 #pragma once
@@ -116,6 +116,18 @@ int grp_check_cloud_style(const svo_group* g, const svo_cloud_style* style, cons
 int64_t grp_cloud_points(const svo_group* g, const svo_cloud_style* style);
 // what one slot of a device-mode job with that checked style and check stages: slot_bytes [+ reverse_bytes]
 int64_t grp_cloud_slot_bytes(const svo_group* g, const svo_cloud_style* style, const svo_stereo_check* check);
+// Voxel maps (svo_group_voxel.hip). grp_set_voxel_maps: the named slots (indices in the group) get a cleared map of
+// `params` (checked), or with params == null lose theirs; grp_voxel_map_info: false for a slot without a map (both:
+// the queues have drained). The three jobs run between two steps of the group, on the thread that drives it, and are
+// delivered on return; a failed group rejects them. grp_fuse_clouds: slot seqs[i] fills info[seg[i]];
+// grp_export_voxel_maps: slot seqs[i] fills dst->segments[seg[i]] and goes where regions[i] says.
+int grp_set_voxel_maps(svo_group* g, const int* seqs, int n, const svo_voxel_params* params);
+bool grp_voxel_map_info(svo_group* g, int seq, svo_voxel_map_info* info);
+int grp_fuse_clouds(svo_group* g, int what, const int* seqs, const int* seg, int n, int seq0, const svo_cloud_style* style,
+                    const svo_stereo_check* check, uint32_t stamp, svo_fuse_info* info);
+int grp_export_voxel_maps(svo_group* g, int mem, const int* seqs, const int* seg, const svo_voxel_region* regions, int n, int seq0,
+                          const svo_voxel_filter* filter, const svo_voxel_dst* dst);
+int grp_clear_voxel_maps(svo_group* g, const int* seqs, int n);
 // what svo_map_size reports of a slot (the queues have drained)
 void grp_map_size(const svo_group* g, int seq, int from_keyframe, int* keyframes, int64_t* points_bound, int* from = nullptr);
 // Snapshots (svo_submit_save / svo_submit_load). grp_check_snapshot: everything svo_submit_load checks of one

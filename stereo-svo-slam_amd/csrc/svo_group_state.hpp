@@ -359,6 +359,19 @@ struct svo_group {
     // cross-check (a checked grp_export_disparity or grp_export_cloud): the reverse planes of one chunk of a job, made
     // by the first checked job and replaced when outgrown
     svo::GrowBlock<uint8_t> d_lr;
+    // voxel maps (svo_group_voxel.hip): a map per slot that has one (svo_ctx_set_voxel_maps; empty until then) with
+    // the host mirror of its header; the records of one chunk of a fuse job and its tables (maps | headers | spans,
+    // mirrored); the tile offsets, the sort staging and in host mode the records of an export. Each block is made by
+    // the first job that needs it and replaced when outgrown.
+    struct VoxelSlot {
+        uint8_t* p = nullptr;
+        svo_voxel_params params{};
+        svo::VoxelHeader head{};         // as of the last job that changed the map
+    };
+    std::vector<VoxelSlot> voxel_maps;
+    svo::GrowBlock<uint8_t> d_voxel_records;
+    svo::GrowBlock<uint8_t, true> d_voxel_tables;
+    svo::GrowBlock<uint8_t> d_voxel_offsets, d_voxel_sort, d_voxel_out;
     // batched pose-filter updates (grp_pose_updates): the upload block (samples | filter states | start poses |
     // sample offsets) and behind it the download block (filter states | filtered poses) of one job, device and pinned,
     // made by the first such job and replaced when outgrown

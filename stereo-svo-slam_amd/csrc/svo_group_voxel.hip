@@ -1,0 +1,214 @@
+// svo_group_voxel.hip — the voxel maps of a sequence group (include/svo_hip.h, "voxel maps"): a map per slot that has
+// one, the fuse job (the organized world-frame clouds of the named slots, computed by grp_export_cloud in device mode
+// into a block of the group, then one fuse launch per chunk), the export job (voxel.hip's count, scan, pairs, sort
+// and gather per slot) and the clear job. A map belongs to the slot: nothing else in the group touches it. The host
+// arithmetic is svo_voxel_plan.hpp's, the state svo_group_state.hpp's.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstring>
+
+#include "svo_group_state.hpp"
+#include "svo_voxel_plan.hpp"
+
+using namespace svo;
+
+namespace {
+
+constexpr size_t FUSE_STAGING_BYTES = (size_t)256 << 20;   // the slots of one chunk stage at most so much (one slot always fits)
+
+VoxelMapDev map_dev(const svo_group::VoxelSlot& v) { return VoxelMapDev{v.p, v.params.voxel, v.params.log2_capacity, v.params.drop_flags, 0}; }
+
+void drop_map(svo_group* c, svo_group::VoxelSlot& v) {
+    if (v.p) dev_release(c, v.p, voxel_map_bytes(v.params.log2_capacity));
+    v = svo_group::VoxelSlot{};
+}
+
+// the mirror of an empty map
+VoxelHeader empty_head(const svo_voxel_params& p) {
+    VoxelHeader h{};
+    h.magic = VOXEL_MAGIC; h.log2_capacity = p.log2_capacity; h.voxel = p.voxel; h.drop_flags = p.drop_flags;
+    return h;
+}
+
+}  // namespace
+
+int grp_set_voxel_maps(svo_group* c, const int* seqs, int n, const svo_voxel_params* params) {
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t st = c->stream.get();
+    HIP_TRY(hipStreamSynchronize(st));
+    if (c->voxel_maps.empty()) {
+        if (!params) return SVO_OK;
+        c->voxel_maps.resize((size_t)c->B);
+    }
+    for (int i = 0; i < n; i++) {
+        svo_group::VoxelSlot& v = c->voxel_maps[(size_t)seqs[i]];
+        drop_map(c, v);
+        if (!params) continue;
+        if (const int rc = dev_alloc(c, &v.p, voxel_map_bytes(params->log2_capacity), false)) return rc;
+        v.params = *params;
+        v.head = empty_head(*params);
+        launch_voxel_clear(map_dev(v), st);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    return SVO_OK;
+}
+
+bool grp_voxel_map_info(svo_group* c, int seq, svo_voxel_map_info* info) {
+    if (c->voxel_maps.empty() || !c->voxel_maps[(size_t)seq].p) return false;
+    const VoxelHeader& h = c->voxel_maps[(size_t)seq].head;
+    if (info)
+        *info = svo_voxel_map_info{h.voxel, h.log2_capacity, h.drop_flags, 0, (int64_t)h.n_voxels, (int64_t)h.n_fused, (int64_t)h.n_outside,
+                                   (int64_t)h.overflow};
+    return true;
+}
+
+int grp_clear_voxel_maps(svo_group* c, const int* seqs, int n) {
+    if (const int rc = job_begin(c, "svo_submit_clear_voxel_maps")) return rc;
+    if (c->voxel_maps.empty()) return SVO_OK;
+    hipStream_t st = c->stream.get();
+    for (int i = 0; i < n; i++) {
+        svo_group::VoxelSlot& v = c->voxel_maps[(size_t)seqs[i]];
+        if (!v.p) continue;
+        launch_voxel_clear(map_dev(v), st);
+        HIP_TRY(hipGetLastError());
+        v.head = empty_head(v.params);
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    return SVO_OK;
+}
+
+// The statuses are settled on the host first (no map, no frame or keyframe, the load bound with the mirror's
+// n_voxels); the slots that are left run in chunks: grp_export_cloud in device mode writes the chunk's organized
+// records into d_voxel_records, one fuse launch puts them into the slots' maps, one launch gathers the maps' headers
+// and one copy brings them back: the new mirrors, and what the job added to the counters.
+int grp_fuse_clouds(svo_group* c, int what, const int* seqs, const int* seg, int n, int seq0, const svo_cloud_style* style,
+                    const svo_stereo_check* check, uint32_t stamp, svo_fuse_info* info) {
+    if (const int rc = job_begin(c, "svo_submit_fuse_clouds")) return rc;
+    hipStream_t st = c->stream.get();
+    svo_cloud_style organized = *style;
+    organized.layout = SVO_CLOUD_ORGANIZED;
+    const int64_t points = grp_cloud_points(c, &organized);
+    std::vector<int> todo, todo_at;                          // the slots to fuse (indices in the group) and their position in the job
+    for (int i = 0; i < n; i++) {
+        const Seq& q = c->seqs[seqs[i]];
+        svo_fuse_info& f = clear(info[seg[i]]);
+        f.seq = seq0 + seqs[i]; f.run = q.run; f.frame_id = q.frame_id; f.keyframe_id = -1;
+        const svo_group::VoxelSlot* v = c->voxel_maps.empty() ? nullptr : &c->voxel_maps[(size_t)seqs[i]];
+        if (!v || !v->p) { f.status = SVO_FUSE_NO_MAP; continue; }
+        f.n_voxels = (int64_t)v->head.n_voxels;
+        if (what == SVO_EXPORT_FRAMES ? q.frame_id < 0 : q.kfs.empty()) { f.status = SVO_FUSE_NONE; continue; }
+        if (!voxel_load_ok(v->head.n_voxels, (uint64_t)points, v->params.log2_capacity)) { f.status = SVO_FUSE_FULL; continue; }
+        f.status = SVO_FUSE_OK;
+        todo.push_back(seqs[i]);
+        todo_at.push_back(seg[i]);
+    }
+    if (todo.empty()) return SVO_OK;
+    const size_t rec_bytes = sizeof(svo_map_point) * (size_t)points;
+    // (SVO_CLOUD_CHUNK_SLOTS: fewer slots per chunk, so that tests reach the chunked path)
+    const size_t per_slot = (size_t)grp_cloud_slot_bytes(c, &organized, check) + rec_bytes;
+    const size_t m_max = std::min(todo.size(), table_tiles("SVO_CLOUD_CHUNK_SLOTS", std::max<size_t>(1, FUSE_STAGING_BYTES / std::max<size_t>(per_slot, 1))));
+    if (const int rc = c->d_voxel_records.reserve(c, m_max * rec_bytes)) return rc;
+    svo_map_point* const d_records = reinterpret_cast<svo_map_point*>(c->d_voxel_records.p);
+    // the tables of a chunk: maps | headers | spans, m_max of each
+    const size_t maps_off = 0, heads_off = voxel_up256(sizeof(VoxelMapDev) * m_max), spans_off = heads_off + voxel_up256(sizeof(VoxelHeader) * m_max);
+    if (const int rc = c->d_voxel_tables.reserve(c, spans_off + voxel_up256(sizeof(VoxelSpanDev) * m_max))) return rc;
+    uint8_t* const h_tab = c->d_voxel_tables.host.get();
+    uint8_t* const d_tab = c->d_voxel_tables.p;
+    std::vector<svo_cloud_segment> csegs(m_max);
+    std::vector<int> local(m_max);
+    for (size_t j = 0; j < m_max; j++) local[j] = (int)j;
+    for (size_t i0 = 0; i0 < todo.size(); i0 += m_max) {
+        const int m = (int)std::min(m_max, todo.size() - i0);
+        const svo_cloud_dst cloud_dst{csegs.data(), d_records, (int64_t)m * points};
+        if (const int rc = grp_export_cloud(c, what, SVO_MEM_DEVICE, todo.data() + i0, local.data(), m, seq0, &organized, check, &cloud_dst)) return rc;
+        VoxelMapDev* h_maps = reinterpret_cast<VoxelMapDev*>(h_tab + maps_off);
+        VoxelSpanDev* h_spans = reinterpret_cast<VoxelSpanDev*>(h_tab + spans_off);
+        int n_spans = 0;
+        int64_t tiles = 0;
+        for (int j = 0; j < m; j++) {
+            const svo_group::VoxelSlot& v = c->voxel_maps[(size_t)todo[i0 + (size_t)j]];
+            svo_fuse_info& f = info[todo_at[i0 + (size_t)j]];
+            const svo_cloud_segment& e = csegs[(size_t)j];
+            h_maps[j] = map_dev(v);
+            f.keyframe_id = e.keyframe_id;
+            std::memcpy(f.pose, e.pose, sizeof(f.pose));
+            if (e.status != SVO_CLOUD_OK) { f.status = SVO_FUSE_NONE; continue; }
+            f.n_offered = e.n_points;
+            h_spans[n_spans++] = VoxelSpanDev{d_records + (int64_t)j * points, points, tiles, j, stamp};
+            tiles += voxel_span_tiles(points);
+        }
+        HIP_TRY(hipMemcpyAsync(d_tab + maps_off, h_maps, sizeof(VoxelMapDev) * (size_t)m, hipMemcpyHostToDevice, st));
+        if (n_spans > 0) {
+            HIP_TRY(hipMemcpyAsync(d_tab + spans_off, h_spans, sizeof(VoxelSpanDev) * (size_t)n_spans, hipMemcpyHostToDevice, st));
+            launch_voxel_fuse(reinterpret_cast<const VoxelSpanDev*>(d_tab + spans_off), n_spans, tiles,
+                              reinterpret_cast<const VoxelMapDev*>(d_tab + maps_off), false, st);
+            HIP_TRY(hipGetLastError());
+        }
+        launch_voxel_headers(reinterpret_cast<const VoxelMapDev*>(d_tab + maps_off), m, reinterpret_cast<VoxelHeader*>(d_tab + heads_off), st);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(h_tab + heads_off, d_tab + heads_off, sizeof(VoxelHeader) * (size_t)m, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));   // fused; the blocks are free for the next chunk
+        const VoxelHeader* heads = reinterpret_cast<const VoxelHeader*>(h_tab + heads_off);
+        for (int j = 0; j < m; j++) {
+            svo_group::VoxelSlot& v = c->voxel_maps[(size_t)todo[i0 + (size_t)j]];
+            svo_fuse_info& f = info[todo_at[i0 + (size_t)j]];
+            f.n_fused = (int32_t)(heads[j].n_fused - v.head.n_fused);
+            f.n_outside = (int32_t)(heads[j].n_outside - v.head.n_outside);
+            f.n_voxels = (int64_t)heads[j].n_voxels;
+            v.head = heads[j];
+        }
+    }
+    return SVO_OK;
+}
+
+int grp_export_voxel_maps(svo_group* c, int mem, const int* seqs, const int* seg, const svo_voxel_region* regions, int n, int seq0,
+                          const svo_voxel_filter* filter, const svo_voxel_dst* dst) {
+    if (const int rc = job_begin(c, "svo_submit_export_voxel_maps")) return rc;
+    hipStream_t st = c->stream.get();
+    const bool host = mem == SVO_MEM_HOST;
+    for (int i = 0; i < n; i++) {
+        const Seq& q = c->seqs[seqs[i]];
+        const svo_voxel_region& r = regions[i];
+        svo_voxel_segment& e = clear(dst->segments[seg[i]]);
+        e.seq = seq0 + seqs[i]; e.run = q.run; e.frame_id = q.frame_id; e.first_point = r.first_point; e.status = SVO_VOXEL_NO_MAP;
+        const svo_group::VoxelSlot* v = c->voxel_maps.empty() ? nullptr : &c->voxel_maps[(size_t)seqs[i]];
+        if (!v || !v->p) continue;
+        e.n_voxels = (int64_t)v->head.n_voxels; e.n_fused = (int64_t)v->head.n_fused;
+        e.voxel = v->params.voxel; e.log2_capacity = v->params.log2_capacity;
+        if (!voxel_extract_fits(e.n_voxels, r.point_capacity)) { e.status = SVO_VOXEL_TOO_SMALL; continue; }
+        e.status = SVO_VOXEL_OK;
+        if (e.n_voxels == 0) continue;
+        const VoxelMapDev mp = map_dev(*v);
+        const VoxelFilterDev f{std::max<uint32_t>(1u, filter->min_count), std::max(filter->min_stamp, r.min_stamp)};
+        if (const int rc = c->d_voxel_offsets.reserve(c, voxel_offsets_bytes(mp.log2_capacity))) return rc;
+        int32_t* offsets = reinterpret_cast<int32_t*>(c->d_voxel_offsets.p);
+        launch_voxel_count(mp, f, offsets, st);
+        HIP_TRY(hipGetLastError());
+        int32_t kept = 0;
+        HIP_TRY(hipMemcpyAsync(&kept, offsets + voxel_map_tiles(mp.log2_capacity), sizeof(kept), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (kept < 0 || !voxel_extract_fits(kept, r.point_capacity))
+            return svo_set_error(SVO_ERR_INVALID, "svo_submit_export_voxel_maps: slot %d keeps %d entries, its mirror counts %lld", e.seq, kept,
+                                 (long long)e.n_voxels);
+        e.n_points = kept;
+        if (kept == 0) continue;
+        size_t temp_bytes = 0;
+        if (const int rc = voxel_sort_temp_bytes((size_t)kept, &temp_bytes)) return rc;
+        const VoxelExtractPlan plan = voxel_extract_plan((uint64_t)kept, temp_bytes);
+        if (const int rc = c->d_voxel_sort.reserve(c, plan.bytes)) return rc;
+        if (host)
+            if (const int rc = c->d_voxel_out.reserve(c, sizeof(svo_map_point) * (size_t)kept)) return rc;
+        uint8_t* ws = c->d_voxel_sort.p;
+        svo_map_point* out = host ? reinterpret_cast<svo_map_point*>(c->d_voxel_out.p) : dst->points + r.first_point;
+        if (const int rc = launch_voxel_extract(mp, f, offsets, (size_t)kept, reinterpret_cast<uint64_t*>(ws + plan.keys_in),
+                                                reinterpret_cast<uint64_t*>(ws + plan.keys_out), reinterpret_cast<uint32_t*>(ws + plan.index_in),
+                                                reinterpret_cast<uint32_t*>(ws + plan.index_out), ws + plan.sort_temp, temp_bytes, out, st))
+            return rc;
+        HIP_TRY(hipGetLastError());
+        if (host) HIP_TRY(hipMemcpyAsync(dst->points + r.first_point, out, sizeof(svo_map_point) * (size_t)kept, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));   // delivered, and the blocks are free for the next slot
+    }
+    return SVO_OK;
+}

@@ -443,4 +443,51 @@ struct PoseFilterArgs {
 };
 void launch_pose_filter(const PoseFilterArgs& a, hipStream_t stream);
 
+// ------------------------------------------------------------ voxel maps (voxel.hip)
+// A map in device memory, 16-byte aligned: the header (256 bytes), the key plane (uint64[capacity], ~0: empty) and
+// one 32-byte accumulator record per entry (count, sx, sy, sz, sr, sg, sb, last). The sizes and the host arithmetic
+// are svo_voxel_plan.hpp's.
+struct VoxelHeader {              // the first 64 of the header's 256 bytes; the rest is 0
+    uint32_t magic;
+    int32_t log2_capacity;
+    float voxel;
+    uint32_t drop_flags;
+    unsigned long long n_voxels, n_fused, n_outside, overflow;
+    uint32_t _pad[4];
+};
+static_assert(sizeof(VoxelHeader) == 64, "one 64-byte block");
+struct VoxelMapDev {              // a map of a launch
+    uint8_t* base;
+    float voxel;
+    int32_t log2_capacity;
+    uint32_t drop_flags;
+    int32_t _pad;
+};
+struct VoxelSpanDev {             // n > 0 records for maps[map]; tile0: the workgroups of the spans before it
+    const svo_map_point* points;
+    int64_t n;
+    int64_t tile0;
+    int32_t map;
+    uint32_t stamp;
+};
+struct VoxelFilterDev { uint32_t min_count, min_stamp; };   // min_count >= 1
+// empty entries and a header with zero counters
+void launch_voxel_clear(const VoxelMapDev& map, hipStream_t stream);
+// headers[i] = the header block of maps[i] (one launch, so that the host reads them with one copy)
+void launch_voxel_headers(const VoxelMapDev* d_maps, int n, VoxelHeader* d_headers, hipStream_t stream);
+// n_spans >= 1 spans of `tiles` workgroups in all into the maps they name. lane_atomics: every lane adds its own
+// record to the entry its key's leader found, instead of one summed add per distinct key of a wavefront (the same
+// table content; a diagnostic that the bench tool times).
+void launch_voxel_fuse(const VoxelSpanDev* d_spans, int n_spans, int64_t tiles, const VoxelMapDev* d_maps, bool lane_atomics,
+                       hipStream_t stream);
+// tile_offsets[t] = kept entries of the tiles before t, tile_offsets[tiles] = all kept entries (two launches)
+void launch_voxel_count(const VoxelMapDev& map, VoxelFilterDev f, int32_t* tile_offsets, hipStream_t stream);
+// the temporary storage of the sort of n pairs
+int voxel_sort_temp_bytes(size_t n, size_t* bytes);
+// after launch_voxel_count with the same filter: the (key, entry) pairs of the n kept entries, sorted by key, as
+// records points[0, n). keys_* / index_*: n values each.
+int launch_voxel_extract(const VoxelMapDev& map, VoxelFilterDev f, const int32_t* tile_offsets, size_t n, uint64_t* keys_in,
+                         uint64_t* keys_out, uint32_t* index_in, uint32_t* index_out, void* sort_temp, size_t sort_temp_bytes,
+                         svo_map_point* points, hipStream_t stream);
+
 }  // namespace svo

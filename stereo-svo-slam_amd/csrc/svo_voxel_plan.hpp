@@ -1,0 +1,92 @@
+// svo_voxel_plan.hpp — the host arithmetic of the voxel maps (include/svo_hip.h, "voxel maps"): the bytes of a map,
+// the placement hash, the load bound a fuse is admitted by, what a span and a region must look like, the tiles a span
+// is cut into and the staging of an extraction. Plain C++: no HIP, no error text; svo_capi_voxel.hip formats its own
+// messages. tests/cpp/voxel_plan_check.cpp exercises it on the CPU, plain and under the sanitizers.
+#pragma once
+
+#include <cstddef>
+#include <cstdint>
+
+namespace svo {
+
+constexpr uint32_t VOXEL_MAGIC = 0x31585653u;       // "SVX1"
+constexpr size_t VOXEL_HEADER_BYTES = 256;
+constexpr size_t VOXEL_ENTRY_BYTES = 40;            // key u64 + eight u32 accumulators
+constexpr int VOXEL_TILE = 256;                     // records of a fuse workgroup, entries of an extraction tile
+constexpr int VOXEL_LOG2_MIN = 6, VOXEL_LOG2_MIN_CTX = 10, VOXEL_LOG2_MAX = 26;
+constexpr uint64_t VOXEL_EMPTY = ~(uint64_t)0;
+constexpr uint64_t VOXEL_HASH = 0x9E3779B97F4A7C15ull;
+
+inline bool voxel_log2_ok(int log2_capacity, bool ctx) {
+    return log2_capacity >= (ctx ? VOXEL_LOG2_MIN_CTX : VOXEL_LOG2_MIN) && log2_capacity <= VOXEL_LOG2_MAX;
+}
+
+// header, key plane, accumulator records (0 for a log2_capacity no entry accepts)
+inline size_t voxel_map_bytes(int log2_capacity) {
+    if (!voxel_log2_ok(log2_capacity, false)) return 0;
+    return VOXEL_HEADER_BYTES + (VOXEL_ENTRY_BYTES << log2_capacity);
+}
+
+// where a key's probe chain starts
+inline uint64_t voxel_home(uint64_t key, int log2_capacity) { return (key * VOXEL_HASH) >> (64 - log2_capacity); }
+
+// the entries a map may hold at most: capacity - capacity / 4
+inline uint64_t voxel_load_limit(int log2_capacity) {
+    const uint64_t cap = (uint64_t)1 << log2_capacity;
+    return cap - cap / 4;
+}
+
+// records += n without wrapping (n >= 0): false when the sum does not fit
+inline bool voxel_add_records(uint64_t& records, int64_t n) {
+    if (n < 0 || (uint64_t)n > UINT64_MAX - records) return false;
+    records += (uint64_t)n;
+    return true;
+}
+
+// the load bound: n_voxels + records <= capacity - capacity / 4, on the bound (every record may claim an entry)
+inline bool voxel_load_ok(uint64_t n_voxels, uint64_t records, int log2_capacity) {
+    const uint64_t limit = voxel_load_limit(log2_capacity);
+    return n_voxels <= limit && records <= limit - n_voxels;
+}
+
+// a span the entries accept: n >= 0, and with n > 0 a 16-byte aligned, non-null address
+inline bool voxel_span_ok(uintptr_t points, int64_t n) { return n >= 0 && (n == 0 || (points != 0 && (points & 15) == 0)); }
+
+// the workgroups of a span of n records (n <= 0: none)
+inline int64_t voxel_span_tiles(int64_t n) { return n <= 0 ? 0 : n / VOXEL_TILE + (n % VOXEL_TILE != 0); }
+
+// the tiles of an extraction pass over a map
+inline int64_t voxel_map_tiles(int log2_capacity) { return (((int64_t)1 << log2_capacity) + VOXEL_TILE - 1) / VOXEL_TILE; }
+
+// a region [first, first + capacity) of an array of `total` records
+inline bool voxel_region_ok(int64_t first, int64_t capacity, int64_t total) {
+    return first >= 0 && capacity >= 0 && total >= 0 && first <= total && capacity <= total - first;
+}
+
+inline size_t voxel_up256(size_t v) { return (v + 255) / 256 * 256; }
+
+// the tile offsets of an extraction: one int per tile and the total
+inline size_t voxel_offsets_bytes(int log2_capacity) { return voxel_up256(sizeof(int32_t) * ((size_t)voxel_map_tiles(log2_capacity) + 1)); }
+
+// The staging of an extraction that keeps `kept` entries (known after the count pass): the (key, entry index) pairs
+// before and after the sort, and the sort's own temporary storage. Offsets into one block, multiples of 256.
+struct VoxelExtractPlan {
+    size_t keys_in, keys_out, index_in, index_out, sort_temp, bytes;
+};
+inline VoxelExtractPlan voxel_extract_plan(uint64_t kept, size_t sort_temp_bytes) {
+    VoxelExtractPlan p{};
+    size_t at = 0;
+    auto take = [&](size_t bytes) { const size_t off = at; at += voxel_up256(bytes); return off; };
+    p.keys_in = take(sizeof(uint64_t) * (size_t)kept);
+    p.keys_out = take(sizeof(uint64_t) * (size_t)kept);
+    p.index_in = take(sizeof(uint32_t) * (size_t)kept);
+    p.index_out = take(sizeof(uint32_t) * (size_t)kept);
+    p.sort_temp = take(sort_temp_bytes);
+    p.bytes = at;
+    return p;
+}
+
+// does an extraction of `kept` entries fit `capacity` records?
+inline bool voxel_extract_fits(int64_t kept, int64_t capacity) { return kept >= 0 && capacity >= 0 && kept <= capacity; }
+
+}  // namespace svo

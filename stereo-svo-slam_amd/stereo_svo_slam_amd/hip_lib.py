@@ -49,6 +49,9 @@ SYMBOLS = (
     "svo_scene_size", "svo_scene_look_at", "svo_scene_frustum", "svo_submit_export_scenes", "svo_export_scenes",
     "svo_render_scene",
     "svo_submit_export_scenes_clouds", "svo_export_scenes_clouds", "svo_render_scene_clouds",
+    "svo_voxel_map_bytes", "svo_voxel_clear", "svo_voxel_fuse", "svo_voxel_info", "svo_voxel_extract",
+    "svo_ctx_set_voxel_maps", "svo_get_voxel_map_info", "svo_submit_fuse_clouds", "svo_fuse_clouds",
+    "svo_submit_export_voxel_maps", "svo_export_voxel_maps", "svo_submit_clear_voxel_maps",
     "svo_ar_size", "svo_ar_camera_of_pose", "svo_submit_export_ar", "svo_export_ar", "svo_render_ar",
     "svo_remap_linear_multi", "svo_ctx_add_rigs", "svo_ctx_remove_rigs", "svo_ctx_assign_rigs", "svo_ctx_get_slot_rig",
     "svo_ctx_get_rigs",
@@ -657,6 +660,76 @@ def scene_clouds(live=False, what=0, step=1, win=0, search_x=0, search_y=0, min_
     return c, (spans, extra, info)
 
 
+# voxel maps (include/svo_hip.h): svo_map_point records fused into a sparse voxel grid in device memory
+VOXEL_LOG2_MIN, VOXEL_LOG2_MAX = 6, 26
+
+
+class VoxelParams(C.Structure):
+    """svo_voxel_params (include/svo_hip.h): what a map is cleared with."""
+    _fields_ = [("voxel", C.c_float), ("log2_capacity", C.c_int32), ("drop_flags", C.c_uint32), ("_reserved", C.c_int32)]
+
+
+class VoxelMap(C.Structure):
+    """svo_voxel_map (include/svo_hip.h): a map in device memory and its params."""
+    _fields_ = [("data", C.c_void_p), ("params", VoxelParams)]
+
+
+class VoxelSpan(C.Structure):
+    """svo_voxel_span (include/svo_hip.h): n records for map `map` of a call, fused with `stamp`."""
+    _fields_ = [("points", C.c_void_p), ("n", C.c_int64), ("map", C.c_int32), ("stamp", C.c_uint32)]
+
+
+class VoxelMapInfo(C.Structure):
+    """svo_voxel_map_info (include/svo_hip.h): the params and counters of a map's header."""
+    _fields_ = [("voxel", C.c_float), ("log2_capacity", C.c_int32), ("drop_flags", C.c_uint32), ("_pad", C.c_int32),
+                ("n_voxels", C.c_int64), ("n_fused", C.c_int64), ("n_outside", C.c_int64), ("overflow", C.c_int64)]
+
+
+class VoxelFilter(C.Structure):
+    """svo_voxel_filter (include/svo_hip.h): which entries an extraction keeps."""
+    _fields_ = [("min_count", C.c_uint32), ("min_stamp", C.c_uint32), ("_reserved", C.c_int32 * 2)]
+
+
+assert (C.sizeof(VoxelParams), C.sizeof(VoxelMap), C.sizeof(VoxelSpan), C.sizeof(VoxelMapInfo), C.sizeof(VoxelFilter)) == (16, 24, 24, 48, 16)
+
+
+# the ctx's voxel maps: svo_submit_fuse_clouds, svo_submit_export_voxel_maps
+FUSE_OK, FUSE_NONE, FUSE_NO_MAP, FUSE_FULL = range(4)
+VOXEL_OK, VOXEL_NO_MAP, VOXEL_TOO_SMALL = range(3)
+FUSE_INFO_DTYPE = np.dtype([("seq", "<i4"), ("run", "<i4"), ("frame_id", "<i4"), ("keyframe_id", "<i4"), ("status", "<i4"),
+                            ("n_offered", "<i4"), ("n_fused", "<i4"), ("n_outside", "<i4"), ("n_voxels", "<i8"), ("pose", "<f4", (6,))])
+VOXEL_REGION_DTYPE = np.dtype([("first_point", "<i8"), ("point_capacity", "<i8"), ("min_stamp", "<u4"), ("_reserved", "<i4", (3,))])
+VOXEL_SEGMENT_DTYPE = np.dtype([("seq", "<i4"), ("run", "<i4"), ("frame_id", "<i4"), ("status", "<i4"), ("first_point", "<i8"),
+                                ("n_points", "<i8"), ("n_voxels", "<i8"), ("n_fused", "<i8"), ("voxel", "<f4"),
+                                ("log2_capacity", "<i4"), ("_pad", "<i8")])
+
+
+class VoxelDst(C.Structure):
+    """svo_voxel_dst (include/svo_hip.h)"""
+    _fields_ = [("segments", C.c_void_p), ("points", C.c_void_p)]
+
+
+assert (FUSE_INFO_DTYPE.itemsize, VOXEL_REGION_DTYPE.itemsize, VOXEL_SEGMENT_DTYPE.itemsize, C.sizeof(VoxelDst)) == (64, 32, 64, 16)
+
+
+def voxel_map_bytes(log2_capacity):
+    """svo_voxel_map_bytes: the device bytes of a map of 1 << log2_capacity entries (needs no GPU)"""
+    n = lib().svo_voxel_map_bytes(int(log2_capacity))
+    if n <= 0:
+        raise SvoError(f"log2_capacity {log2_capacity} is outside {VOXEL_LOG2_MIN} .. {VOXEL_LOG2_MAX}")
+    return n
+
+
+def voxel_params(voxel, log2_capacity, drop_flags=0):
+    return VoxelParams(float(voxel), int(log2_capacity), int(drop_flags), 0)
+
+
+def _voxel_map(m):
+    """a VoxelMap of (device tensor or address, VoxelParams)"""
+    data, params = m
+    return VoxelMap(data.data_ptr() if isinstance(data, torch.Tensor) else int(data), params)
+
+
 # ar pictures (svo_submit_export_ar, include/svo_hip.h): lit meshes over each slot's camera image
 AR_OK, AR_NONE = 0, 1
 AR_MAX_TRIANGLES = 65536
@@ -818,6 +891,14 @@ def lib():
                 "g.build()'` (hipcc --offload-arch=gfx950). There is no CPU fallback.")
         _LIB = C.CDLL(LIB_PATH)
         _LIB.svo_last_error.restype = C.c_char_p
+        _LIB.svo_voxel_map_bytes.restype = C.c_int64
+        for name in ("svo_submit_fuse_clouds", "svo_fuse_clouds"):
+            getattr(_LIB, name).argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+        for name in ("svo_submit_export_voxel_maps", "svo_export_voxel_maps"):     # (regions: a numpy array's address)
+            getattr(_LIB, name).argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        _LIB.svo_ctx_set_voxel_maps.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        _LIB.svo_submit_clear_voxel_maps.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        _LIB.svo_get_voxel_map_info.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         for name in ("svo_submit_pose_updates", "svo_update_poses"):
             getattr(_LIB, name).argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         _LIB.svo_scene_look_at.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_int, C.c_float,
@@ -1171,6 +1252,60 @@ class Handle:
         counts: an int32 device tensor [n] (or address) for the kept counts, or None. check: a StereoCheck
         (svo_cloud_points_checked: failing points are dropped), or None. Complete on return."""
         self.cloud_points_packed(self.pack_cloud(srcs, first), style, points, counts, check)
+
+    # -- voxel maps ---------------------------------------------------------
+    def voxel_new(self, params, device="cuda"):
+        """a cleared map of `params` (a VoxelParams) in a device tensor of its own, as the (tensor, params) pair the
+        other voxel_* methods take"""
+        data = torch.empty(voxel_map_bytes(params.log2_capacity), dtype=torch.uint8, device=device)
+        self.voxel_clear((data, params))
+        return data, params
+
+    def voxel_clear(self, m):
+        """svo_voxel_clear: m = (uint8 device tensor or address of svo_voxel_map_bytes bytes, VoxelParams)"""
+        vm = _voxel_map(m)
+        _check(lib().svo_voxel_clear(self._h, C.c_void_p(vm.data), C.byref(vm.params)))
+
+    def voxel_fuse(self, spans, maps):
+        """svo_voxel_fuse: spans = [(records, map index, stamp)] with records a device tensor of 16-byte
+        MAP_POINT_DTYPE records, (address, n) or None; maps = [(tensor or address, VoxelParams)]. One launch; raises
+        (SVO_ERR_CAPACITY, nothing written) when a load bound fails. Complete on return."""
+        arr = (VoxelSpan * max(len(spans), 1))()
+        for i, (records, mi, stamp) in enumerate(spans):
+            sp = scene_span(records)
+            arr[i] = VoxelSpan(sp.points, sp.n, int(mi), int(stamp))
+        marr = (VoxelMap * max(len(maps), 1))(*[_voxel_map(m) for m in maps])
+        _check(lib().svo_voxel_fuse(self._h, len(spans), arr, len(maps), marr))
+
+    def voxel_info(self, m):
+        """svo_voxel_info: the header of a map as a dict (voxel, log2_capacity, drop_flags, n_voxels, n_fused,
+        n_outside, overflow). m: (tensor or address, params), a tensor or an address."""
+        data = m[0] if isinstance(m, tuple) else m
+        info = VoxelMapInfo()
+        _check(lib().svo_voxel_info(self._h, C.c_void_p(data.data_ptr() if isinstance(data, torch.Tensor) else int(data)), C.byref(info)))
+        return {n: getattr(info, n) for n, _ in VoxelMapInfo._fields_ if n != "_pad"}
+
+    def voxel_count(self, m, min_count=0, min_stamp=0):
+        """svo_voxel_extract with points == NULL: how many entries the filter keeps"""
+        n = C.c_int64(-1)
+        _check(lib().svo_voxel_extract(self._h, C.byref(_voxel_map(m)), C.byref(VoxelFilter(int(min_count), int(min_stamp))), None,
+                                       C.c_int64(0), C.byref(n)))
+        return n.value
+
+    def voxel_extract(self, m, min_count=0, min_stamp=0, points=None, capacity=None):
+        """svo_voxel_extract: the kept entries in ascending key order as MAP_POINT_DTYPE records. points: a device
+        tensor (or address, with `capacity` records) that receives them, or None: one of exactly the kept count is
+        made. Returns (points, n)."""
+        if points is None:
+            capacity = self.voxel_count(m, min_count, min_stamp)
+            points = torch.empty((max(capacity, 1), 16), dtype=torch.uint8, device="cuda")
+        elif capacity is None:
+            capacity = points.numel() * points.element_size() // MAP_POINT_DTYPE.itemsize
+        n = C.c_int64(-1)
+        p = points.data_ptr() if isinstance(points, torch.Tensor) else int(points)
+        _check(lib().svo_voxel_extract(self._h, C.byref(_voxel_map(m)), C.byref(VoxelFilter(int(min_count), int(min_stamp))),
+                                       C.c_void_p(p), C.c_int64(int(capacity)), C.byref(n)))
+        return points, n.value
 
     def render_scene(self, srcs, cameras, offsets, style, pixels):
         """svo_render_scene: the viewer's scene of keyframe sets and lines as images of `style` (a SceneStyle). srcs:

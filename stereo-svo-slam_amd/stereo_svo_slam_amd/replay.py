@@ -37,6 +37,10 @@ little-endian PLY, x y z float and red green blue uchar), so that the files of a
 (src/qt-viewer/PointCloudViewer.qml: points, trajectory, frusta) through its front camera. --scene-dense STEP
 [--scene-dense-lr D] [--scene-dense-max-depth Z] draws the frame's dense cloud into it, --scene-accumulate N the dense
 clouds of the keyframes so far (one device array of at most N records): the dense map growing.
+--dump-dense-map FILE.ply --dense-map-voxel V [--dense-map-log2 N] [--dense-map-min-count K] fuses every new keyframe's
+dense cloud (--cloud-step, --cloud-lr, --cloud-max-depth) into a voxel map of edge V kept inside the ctx (bounded,
+every surface once, the keyframes that saw a voxel averaged) and writes it as one PLY at the end; --scene-fused V draws
+that map in the pictures of --dump-scene.
 --dump-ar DIR writes per frame DIR/000000_ar.ppm: the AR demo's picture (src/ar-app/), a lit box of edge --ar-box
 fixed at the world point --ar-at over the frame's left image, seen from the tracked pose; the default placement is the
 demo's, half a metre in front of the first camera (AnimatedEntity.qml:56). If the pose is right the box stands still.
@@ -416,7 +420,8 @@ class Replay:
                  gpu_imu=False, dump_views=None, dump_scene=None, calibration=None, keyframe_window=None, dump_ar=None,
                  ar_box=AR_BOX, ar_at=hip_lib.AR_AT, dump_disparity=None, disparity_step=4, disparity_depth=False,
                  dump_cloud=None, cloud_step=4, cloud_max_depth=0.0, disparity_lr=None, cloud_lr=None, scene_dense=None,
-                 scene_dense_lr=None, scene_dense_max_depth=0.0, scene_accumulate=0):
+                 scene_dense_lr=None, scene_dense_max_depth=0.0, scene_accumulate=0, dump_dense_map=None, dense_map_voxel=None,
+                 dense_map_log2=20, dense_map_min_count=0, scene_fused=None):
         """fast=False keeps the library default: the reference-order Gauss-Newton (bit-exact traces).
         rectify_maps = (left maps, right maps): the frames fed are raw and are rectified on the GPU.
         calibration = (left, right) CameraCalibrations: the same, with the maps built on the GPU as well.
@@ -442,6 +447,10 @@ class Replay:
         dropped; 0: none dropped) as kfNNNNNN_cloud.ply (write_ply), likewise.
         disparity_lr: None, or the tolerance of the left-right cross-check of dump_disparity (0: report only); the file
         is then [3, rows, cols]: value, cost, lr. cloud_lr: None, or the tolerance (> 0) of the cross-check of dump_cloud.
+        dump_dense_map: a PLY file that receives, at finish(), the slot's voxel map (get_voxel_map with
+        dense_map_min_count): every new keyframe's dense cloud (cloud_step, cloud_lr, cloud_max_depth) is fused into a map
+        of edge dense_map_voxel and 1 << dense_map_log2 entries kept inside the ctx. scene_fused = V: dump_scene draws
+        that fused map (edge V; the same map when both are given) as the extra span, exported to device memory.
         keyframe_window: the retired keyframes the tracker keeps (StereoSlamBatch.set_keyframe_window); None: all."""
         self.settings = settings
         self.dump_views, self.dump_scene, self.dump_ar = dump_views, dump_scene, dump_ar
@@ -454,6 +463,14 @@ class Replay:
         self.scene_dense_lr = None if scene_dense_lr is None else float(scene_dense_lr)
         self.scene_dense_max_depth, self.scene_accumulate = float(scene_dense_max_depth), int(scene_accumulate)
         self._scene_kf, self._scene_map = -1, None
+        self.dump_dense_map, self.dense_map_log2, self.dense_map_min_count = dump_dense_map, int(dense_map_log2), int(dense_map_min_count)
+        self.scene_fused = None if scene_fused is None else float(scene_fused)
+        self.dense_map_voxel = float(dense_map_voxel) if dense_map_voxel is not None else self.scene_fused
+        if dump_dense_map and self.dense_map_voxel is None:
+            raise ValueError("dump_dense_map needs dense_map_voxel")
+        if self.scene_fused is not None and self.scene_fused != self.dense_map_voxel:
+            raise ValueError("scene_fused and dense_map_voxel name one map: give the same edge")
+        self._dense_map_set, self._fused_job = False, None
         for d in (dump_views, dump_scene, dump_ar, dump_disparity, dump_cloud):
             if d:
                 os.makedirs(d, exist_ok=True)
@@ -539,8 +556,26 @@ class Replay:
                                              lr_check=self.cloud_lr)
                 if points is not None:
                     write_ply(os.path.join(self.dump_cloud, f"kf{kf:06d}_cloud.ply"), points)
+        if self.dense_map_voxel is not None and not self.dump_scene:
+            self._fuse_dense_map()
         if self.time_trace:                       # like PRINT_TIME_TRACE of the reference
             print("\n".join(time_trace_lines(self.slam.stats())))
+
+    def _fuse_dense_map(self):
+        """the newest keyframe's dense cloud into the ctx's voxel map, once per keyframe (the map is set after the first
+        frame: the ctx exists from then on). True: the map changed."""
+        if self.slam._ctx is None:
+            return False
+        if not self._dense_map_set:
+            self.slam.set_voxel_maps(self.dense_map_voxel, self.dense_map_log2)
+            self._dense_map_set = True
+        return self.slam.fuse_new_keyframes(step=self.cloud_step, max_depth=self.cloud_max_depth, lr_check=self.cloud_lr) is not None
+
+    def finish(self):
+        """what is written once, after the last frame: the dense map of dump_dense_map"""
+        if self.dump_dense_map:
+            points = self.slam.get_voxel_map(min_count=self.dense_map_min_count) if self._dense_map_set else None
+            write_ply(self.dump_dense_map, points if points is not None else np.zeros(0, hip_lib.MAP_POINT_DTYPE))
 
     def _scene_clouds(self):
         """the dense and clouds arguments of dump_scene's get_scene ({}: the sparse picture)"""
@@ -560,6 +595,14 @@ class Replay:
                     self._scene_map = both[max(0, both.shape[0] - self.scene_accumulate):].contiguous()
             if self._scene_map is not None and self._scene_map.shape[0] > 0:
                 kw["clouds"] = [self._scene_map]
+        if self.dense_map_voxel is not None:
+            changed = self._fuse_dense_map()
+            if self.scene_fused is not None and self._dense_map_set:
+                if changed or self._fused_job is None:          # (the export stays on the device; the job owns the records)
+                    self._fused_job = self.slam.export_voxel_maps(None, min_count=self.dense_map_min_count, device=True)
+                span = self._fused_job.span(0)
+                if span[1] > 0:
+                    kw["clouds"] = [span]
         return kw
 
     def rows(self):
@@ -642,6 +685,16 @@ def build_parser():
                     help="--dump-cloud drops points whose left-right cross-check differs by more than D (> 0)")
     ap.add_argument("--cloud-max-depth", metavar="Z", type=float, default=0.0,
                     help="--dump-cloud drops points deeper than Z in the camera frame (0: none)")
+    ap.add_argument("--dump-dense-map", metavar="FILE.ply",
+                    help="fuse every new keyframe's dense cloud (--cloud-step, --cloud-lr, --cloud-max-depth) into a voxel map "
+                         "kept inside the ctx and write it as one binary PLY at the end; needs --dense-map-voxel")
+    ap.add_argument("--dense-map-voxel", metavar="V", type=float, default=None, help="voxel edge of --dump-dense-map, metres (> 0)")
+    ap.add_argument("--dense-map-log2", metavar="N", type=int, default=20, help="the map holds 1 << N entries (10 .. 26)")
+    ap.add_argument("--dense-map-min-count", metavar="K", type=int, default=0,
+                    help="--dump-dense-map / --scene-fused keep only voxels that at least K records fell into")
+    ap.add_argument("--scene-fused", metavar="V", type=float, default=None,
+                    help="--dump-scene also draws the fused dense map of voxel edge V (the map of --dump-dense-map), exported to "
+                         "device memory whenever a keyframe was fused")
     ap.add_argument("--frames", type=int, default=100)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--rate", type=float, default=20.0, help="frames per second of the time stamps")
@@ -653,9 +706,29 @@ def build_parser():
     return ap
 
 
+def check_dense_map_args(ap, args):
+    """what --dump-dense-map and --scene-fused need of each other and of their values (ap.error: exits with status 2)"""
+    if args.dump_dense_map and args.dense_map_voxel is None:
+        ap.error("--dump-dense-map needs --dense-map-voxel")
+    if args.dense_map_voxel is not None and not (args.dump_dense_map or args.scene_fused is not None):
+        ap.error("--dense-map-voxel needs --dump-dense-map")
+    for name, v in (("--dense-map-voxel", args.dense_map_voxel), ("--scene-fused", args.scene_fused)):
+        if v is not None and not (v > 0 and v < float("inf")):
+            ap.error(f"{name} must be a finite edge > 0")
+    if args.scene_fused is not None and not args.dump_scene:
+        ap.error("--scene-fused needs --dump-scene")
+    if args.scene_fused is not None and args.dense_map_voxel is not None and args.scene_fused != args.dense_map_voxel:
+        ap.error("--scene-fused and --dense-map-voxel name one map: give the same edge")
+    if not 10 <= args.dense_map_log2 <= 26:
+        ap.error("--dense-map-log2 must be 10 .. 26")
+    if args.dense_map_min_count < 0:
+        ap.error("--dense-map-min-count must be >= 0")
+
+
 def main(argv=None):
     ap = build_parser()
     args = ap.parse_args(argv)
+    check_dense_map_args(ap, args)
 
     gt = None
     rect = cal = None
@@ -710,9 +783,11 @@ def main(argv=None):
                 disparity_depth=args.disparity_depth, dump_cloud=args.dump_cloud, cloud_step=args.cloud_step,
                 cloud_max_depth=args.cloud_max_depth, disparity_lr=args.disparity_lr, cloud_lr=args.cloud_lr,
                 scene_dense=args.scene_dense, scene_dense_lr=args.scene_dense_lr, scene_dense_max_depth=args.scene_dense_max_depth,
-                scene_accumulate=args.scene_accumulate)
+                scene_accumulate=args.scene_accumulate, dump_dense_map=args.dump_dense_map, dense_map_voxel=args.dense_map_voxel,
+                dense_map_log2=args.dense_map_log2, dense_map_min_count=args.dense_map_min_count, scene_fused=args.scene_fused)
     for k, (left, right, t) in enumerate(frames):
         rp.feed(left, right, t, None if gyro is None else gyro[gyro[:, 0] == k, 1:4])
+    rp.finish()
     rows = rp.rows()
     print(f"frames {rows.shape[0]}  Average FPS: {fps_from_csv_rows(rows):.2f}  "
           f"keyframes {rp.slam.num_keyframes()}")

@@ -454,6 +454,85 @@ class Clouds:
         return self._records(int(e["first_point"]), self.points_per_slot).reshape(self.rows, self.cols)
 
 
+class Fusion:
+    """One svo_submit_fuse_clouds: owns the info the library writes. After wait(): `info` (hip_lib.FUSE_INFO_DTYPE, one
+    per named slot). Its submit() queues the same job again (the same slots, style and stamp)."""
+
+    def __init__(self, slam, what, seqs, style, check, stamp):
+        self._slam = slam
+        self.what, self.style, self.stamp = int(what), style, int(stamp)
+        self.check = check if check is not None and check.lr else None
+        self.seqs = None if seqs is None else [int(s) for s in seqs]
+        n = self._n = slam.n if seqs is None else len(self.seqs)
+        self._info = np.zeros(max(n, 1), hip_lib.FUSE_INFO_DTYPE)
+        self.info = self._info[:n]
+        self._seq_arr = None if seqs is None else (C.c_int * max(n, 1))(*self.seqs)
+
+    def submit(self):
+        _check(lib().svo_submit_fuse_clouds(self._slam._ctx, self.what, self._seq_arr, self._n, C.byref(self.style),
+                                            None if self.check is None else C.byref(self.check), self.stamp, self._info.ctypes.data))
+        return self
+
+    def wait(self):
+        self._slam.wait()
+        return self
+
+
+class VoxelMaps:
+    """One svo_submit_export_voxel_maps: owns the buffers the library writes. After wait(): `segments`
+    (hip_lib.VOXEL_SEGMENT_DTYPE, one per named slot) and points(i); `points_buffer` is a uint8 [capacity, 16] tensor,
+    pinned memory in host mode, on the ctx's device in device mode. capacities: the records each named slot's region
+    holds, back to back."""
+
+    def __init__(self, slam, seqs, capacities, min_count, min_stamp, device):
+        self._slam = slam
+        self.device_mode = bool(device)
+        self.seqs = None if seqs is None else [int(s) for s in seqs]
+        n = self._n = slam.n if seqs is None else len(self.seqs)
+        caps = [int(c) for c in np.broadcast_to(capacities, (n,))]
+        self.regions = np.zeros(max(n, 1), hip_lib.VOXEL_REGION_DTYPE)
+        self.regions["point_capacity"][:n] = caps
+        self.regions["first_point"][:n] = np.cumsum([0] + caps[:-1]) if n else []
+        self.regions["min_stamp"][:n] = np.broadcast_to(min_stamp, (n,))
+        self.capacity = sum(caps)
+        self._filter = hip_lib.VoxelFilter(int(min_count), 0)
+        self._seg = np.zeros(max(n, 1), hip_lib.VOXEL_SEGMENT_DTYPE)
+        self.segments = self._seg[:n]
+        shape = (max(self.capacity, 1), hip_lib.MAP_POINT_DTYPE.itemsize)
+        self.points_buffer = (torch.zeros(shape, dtype=torch.uint8, device=slam.device) if device
+                              else torch.zeros(shape, dtype=torch.uint8, pin_memory=True))
+        self._dst = hip_lib.VoxelDst(self._seg.ctypes.data, self.points_buffer.data_ptr())
+        self._seq_arr = None if seqs is None else (C.c_int * max(n, 1))(*self.seqs)
+
+    def submit(self):
+        slam = self._slam
+        if self.device_mode:
+            torch.cuda.current_stream(slam.device).synchronize()     # (nothing of the caller's is still using the tensor)
+        _check(lib().svo_submit_export_voxel_maps(slam._ctx, self._seq_arr, self._n, self.regions.ctypes.data_as(C.c_void_p), C.byref(self._filter),
+                                                  C.byref(self._dst), hip_lib.MEM_DEVICE if self.device_mode else hip_lib.MEM_HOST))
+        return self
+
+    def wait(self):
+        self._slam.wait()
+        return self
+
+    def span(self, i):
+        """(device address, n) of named slot i's records (device mode): what a scene job's extra span takes"""
+        e = self.segments[i]
+        n = int(e["n_points"]) if int(e["status"]) == hip_lib.VOXEL_OK else 0
+        return (self.points_buffer.data_ptr() + 16 * int(e["first_point"]) if n else None, n)
+
+    def points(self, i):
+        """the records of named slot i (hip_lib.MAP_POINT_DTYPE) in key order; None unless its status is VOXEL_OK"""
+        e = self.segments[i]
+        if int(e["status"]) != hip_lib.VOXEL_OK:
+            return None
+        lo = int(e["first_point"])
+        a = self.points_buffer[lo:lo + int(e["n_points"])]
+        a = a.cpu().numpy() if self.device_mode else a.numpy()
+        return a.view(hip_lib.MAP_POINT_DTYPE)[:, 0]
+
+
 class Scenes:
     """One svo_submit_export_scenes: owns the buffers the library writes. After wait(): `segments`
     (hip_lib.SCENE_SEGMENT_DTYPE, one per named slot) and image(i); `pixels` is the whole buffer, a numpy uint8 view
@@ -661,6 +740,8 @@ class StereoSlamBatch:
         self.cam = camera_settings
         self.width, self.height, self.n = width, height, n_sequences
         self.device = torch.device("cuda", device)
+        self._fuse_stamp = 0             # submit_fuse: the automatic stamp
+        self._fused_keyframe = {}        # fuse_new_keyframes: slot -> newest keyframe id it fused
         self._ctx = C.c_void_p()
         _check(lib().svo_ctx_create(C.byref(self.cam), width, height, n_sequences, device,
                                     C.byref(self._ctx)))
@@ -1070,6 +1151,8 @@ class StereoSlamBatch:
         seqs = [int(s) for s in ([seqs] if np.isscalar(seqs) else seqs)]
         arr = (C.c_int * max(len(seqs), 1))(*seqs)
         _check(lib().svo_ctx_restart_sequences(self._ctx, arr, len(seqs)))
+        for q in seqs:
+            self._fused_keyframe.pop(q, None)   # (fuse_new_keyframes: the new run's keyframes are new)
 
     # -- trimming retired keyframes ------------------------------------------------------------------------
     def trim_keyframes(self, seqs=None, below=None, wait=True):
@@ -1217,6 +1300,88 @@ class StereoSlamBatch:
 
     def drop_finished_runs(self, seq=-1):
         _check(lib().svo_drop_finished_runs(self._ctx, seq))
+
+    # -- voxel maps: the slots' dense clouds fused into one bounded map per slot -----------------------------------
+    def set_voxel_maps(self, voxel, log2_capacity=20, seqs=None, drop_flags=0):
+        """svo_ctx_set_voxel_maps: every slot of `seqs` (None: all) gets an empty voxel map of edge `voxel` and
+        1 << log2_capacity entries (10 .. 26); voxel=None takes the maps away. Waits for the queues."""
+        n = self.n if seqs is None else len(seqs)
+        arr = None if seqs is None else (C.c_int * max(n, 1))(*[int(s) for s in seqs])
+        params = None if voxel is None else C.byref(hip_lib.voxel_params(voxel, log2_capacity, drop_flags))
+        _check(lib().svo_ctx_set_voxel_maps(self._ctx, arr, n, params))
+        named = range(self.n) if seqs is None else [int(s) for s in seqs]
+        for s in named:
+            self._fused_keyframe.pop(s, None)
+
+    def voxel_map_info(self, seq=0):
+        """svo_get_voxel_map_info as a dict (waits); None for a slot without a map"""
+        info = hip_lib.VoxelMapInfo()
+        if lib().svo_get_voxel_map_info(self._ctx, int(seq), C.byref(info)) != 0:
+            return None
+        return {n: getattr(info, n) for n, _ in hip_lib.VoxelMapInfo._fields_ if n != "_pad"}
+
+    def submit_fuse(self, what="last_keyframes", seqs=None, stamp=None, lr_check=None, step=4, win=0, search_x=0, search_y=0,
+                    min_disparity=0.0, max_depth=0.0, max_mean_cost=0.0):
+        """svo_submit_fuse_clouds: queue the fusion of the dense world-frame cloud of the newest keyframes (or,
+        what="frames", the current frames) of the slots `seqs` (None: all) into their voxel maps, behind what was
+        submitted so far; nothing is waited for. The cloud is submit_cloud's (step, win, search_x, search_y, the
+        filter, lr_check); stamp: a u32 the reached voxels are raised to (None: a counter of this object, one more
+        per job). Returns a Fusion, valid after its wait() (or the ctx's)."""
+        if isinstance(what, str):
+            what = hip_lib.EXPORT_WHAT.index(what)
+        if stamp is None:
+            self._fuse_stamp += 1
+            stamp = self._fuse_stamp
+        style = hip_lib.cloud_style(step, win, search_x, search_y, "world", "compact", min_disparity, max_depth, max_mean_cost)
+        return Fusion(self, what, seqs, style, self._stereo_check(lr_check), stamp).submit()
+
+    def fuse_clouds(self, what="last_keyframes", seqs=None, **kw):
+        """submit_fuse + wait"""
+        return self.submit_fuse(what, seqs, **kw).wait()
+
+    def fuse_new_keyframes(self, seqs=None, **kw):
+        """fuse_clouds("last_keyframes") of only those slots whose newest keyframe changed since this method last fused
+        them (the bookkeeping is here, on the host: it waits for the queues to read the keyframe counts). Returns the
+        Fusion, or None when no slot has a new keyframe."""
+        named = list(range(self.n)) if seqs is None else [int(s) for s in seqs]
+        self.wait()
+        fresh = []
+        for s in named:
+            r = self.keyframe_range(s)
+            newest = r.count - 1
+            if r.count > 0 and self._fused_keyframe.get(s) != newest:
+                fresh.append((s, newest))
+        if not fresh:
+            return None
+        job = self.fuse_clouds("last_keyframes", [s for s, _ in fresh], **kw)
+        for (s, newest), f in zip(fresh, job.info):
+            if int(f["status"]) == hip_lib.FUSE_OK:
+                self._fused_keyframe[s] = newest
+        return job
+
+    def submit_voxel_maps(self, seqs=None, min_count=0, min_stamp=0, device=False, capacities=None):
+        """svo_submit_export_voxel_maps: queue the export of the voxel maps of the slots `seqs` (None: all) as
+        MAP_POINT_DTYPE records in key order. capacities: the records each slot's region holds (an int or one per
+        slot; nothing is waited for then, and a slot that outgrew it comes back VOXEL_TOO_SMALL); default: what the
+        maps hold right now (waits for the queues). Returns a VoxelMaps, valid after its wait()."""
+        if capacities is None:
+            named = range(self.n) if seqs is None else [int(s) for s in seqs]
+            capacities = [(self.voxel_map_info(s) or {"n_voxels": 0})["n_voxels"] for s in named]
+        return VoxelMaps(self, seqs, capacities, min_count, min_stamp, device).submit()
+
+    def export_voxel_maps(self, seqs=None, **kw):
+        """submit_voxel_maps + wait"""
+        return self.submit_voxel_maps(seqs, **kw).wait()
+
+    def clear_voxel_maps(self, seqs=None, wait=True):
+        """svo_submit_clear_voxel_maps: queued; the maps of the slots `seqs` (None: all) become empty"""
+        n = self.n if seqs is None else len(seqs)
+        arr = None if seqs is None else (C.c_int * max(n, 1))(*[int(s) for s in seqs])
+        _check(lib().svo_submit_clear_voxel_maps(self._ctx, arr, n))
+        for s in (range(self.n) if seqs is None else [int(x) for x in seqs]):
+            self._fused_keyframe.pop(s, None)
+        if wait:
+            self.wait()
 
     def memory(self):
         m = Memory()
@@ -1427,6 +1592,15 @@ class StereoSlam(StereoSlamBatch):
         kw["device"] = False
         job = self.export_cloud(what, None, **kw)
         pts = job.organized(0) if job.style.layout == hip_lib.CLOUD_ORGANIZED else job.points(0)
+        return None if pts is None else pts.copy()
+
+    def get_voxel_map(self, **kw):
+        """the slot's voxel map as a numpy array of hip_lib.MAP_POINT_DTYPE in key order (export_voxel_maps of the one
+        slot: min_count, min_stamp); None without a map"""
+        if self._ctx is None:
+            return None
+        kw["device"] = False
+        pts = self.export_voxel_maps(None, **kw).points(0)
         return None if pts is None else pts.copy()
 
     def get_scene(self, camera="front", **kw):

@@ -1,0 +1,197 @@
+"""What fusing dense clouds into voxel maps costs on the MI355X. Writes profiles/voxel_bench.json.
+
+  fuse       svo_voxel_fuse on organized world-frame clouds of bench.py's workload (C2 `euroc`, `--slots` slots after a
+             warm-up, lattice step `--step`): fused records/s of the two forms of the kernel (one summed set of
+             atomics per distinct key of a wavefront; every lane its own atomics: SVO_VOXEL_LANE_ATOMICS=1), with all
+             spans into ONE map and with one map per slot (`--slots` maps per launch). Device events around a call:
+             the header gather and its copy, the table uploads, the kernel and a stream synchronise. Every repeat
+             starts from cleared maps.
+  pile       one slot's record count on one voxel, both forms.
+  extract    svo_voxel_extract of one map by occupancy (the map filled to 1/16, 1/4 and 3/4 of its entries with
+             distinct voxels): count, scan, pairs, sort, gather and the two small copies.
+  host path  what the job replaces: the organized clouds downloaded (a host-mode cloud job) and fused on the host
+             with numpy (the vectorised statement of tests/voxel_ref.py).
+  pipelined  frames/s over `--steps` queued steps of bench.py's workload without fusion and with a fuse job of every
+             slot's newest keyframe queued behind every frame set; legs alternate, median of `--repeats` each.
+Prints one JSON line.
+"""
+import argparse
+import datetime
+import json
+import os
+import statistics
+import sys
+import time
+
+os.environ.setdefault("GPU_MAX_HW_QUEUES", "20")         # (bench.py's setting)
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, "stereo-svo-slam_amd"), os.path.join(ROOT, "tests")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+import numpy as np
+import torch
+
+import bench
+import voxel_ref as VR
+from stereo_svo_slam_amd import hip_lib
+from stereo_svo_slam_amd.stereo_slam import StereoSlamBatch
+
+
+def event_ms(fn, repeats, before=None):
+    """median of the device time between two events around fn(); before() runs untimed ahead of every repeat"""
+    out = []
+    for _ in range(repeats + 1):
+        if before:
+            before()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        torch.cuda.synchronize()
+        out.append(a.elapsed_time(b))
+    return statistics.median(out[1:]), out[1:]
+
+
+def start(cfg, lefts, rights, slots, groups, device, steps):
+    os.environ["SVO_GROUPS"] = str(groups)
+    slam = StereoSlamBatch(cfg, cfg["width"], cfg["height"], slots, device.index)
+    packed = bench.step_packer(lefts, rights, bench.loop_plan(slots, len(lefts), lefts[0].shape[0]), True)(slam, steps)
+    return slam, packed
+
+
+def fuse_leg(args, h, clouds, points, log2_one, log2_each):
+    n = len(clouds)
+    out = {}
+    for maps_name, n_maps, log2 in (("one_map", 1, log2_one), ("map_per_slot", n, log2_each)):
+        params = hip_lib.voxel_params(args.voxel, log2)
+        maps = [h.voxel_new(params) for _ in range(n_maps)]
+        spans = [(c, i % n_maps, 1) for i, c in enumerate(clouds)]
+        for form in (0, 1):
+            os.environ["SVO_VOXEL_LANE_ATOMICS"] = str(form)
+            ms, all_ms = event_ms(lambda: h.voxel_fuse(spans, maps), args.repeats, before=lambda: [h.voxel_clear(m) for m in maps])
+            fused = sum(h.voxel_info(m)["n_fused"] for m in maps)
+            voxels = sum(h.voxel_info(m)["n_voxels"] for m in maps)
+            out[f"{maps_name}_{'lane_atomics' if form else 'group_sums'}"] = {
+                "maps": n_maps, "log2_capacity": log2, "records": n * points, "fused": fused, "voxels": voxels, "ms": ms, "all_ms": all_ms,
+                "fused_records_per_s": fused / (ms * 1e-3)}
+        os.environ.pop("SVO_VOXEL_LANE_ATOMICS")
+    return out
+
+
+def pile_leg(args, h, points):
+    rec = VR.records(np.tile(np.array([[0.5, 0.5, 0.5]], np.float32) * args.voxel, (points, 1)), (200, 100, 50))
+    dev = torch.from_numpy(rec.view(np.uint8).reshape(-1, 16)).cuda()
+    log2 = max(10, int(np.ceil(np.log2(points * 4 / 3 + 2))))
+    m = h.voxel_new(hip_lib.voxel_params(args.voxel, log2))
+    out = {"records": points}
+    for form in (0, 1):
+        os.environ["SVO_VOXEL_LANE_ATOMICS"] = str(form)
+        ms, all_ms = event_ms(lambda: h.voxel_fuse([(dev, 0, 1)], [m]), args.repeats, before=lambda: h.voxel_clear(m))
+        out["lane_atomics" if form else "group_sums"] = {"ms": ms, "all_ms": all_ms, "records_per_s": points / (ms * 1e-3)}
+    os.environ.pop("SVO_VOXEL_LANE_ATOMICS")
+    return out
+
+
+def extract_leg(args, h, log2):
+    out = []
+    cap = 1 << log2
+    for frac in (1 / 16, 1 / 4, 3 / 4):
+        n = int(cap * frac)
+        idx = np.arange(n)
+        xyz = (np.stack([idx % 512, idx // 512 % 512, idx // (512 * 512)], 1) + 0.5) * args.voxel
+        dev = torch.from_numpy(VR.records(xyz, (1, 2, 3)).view(np.uint8).reshape(-1, 16)).cuda()
+        m = h.voxel_new(hip_lib.voxel_params(args.voxel, log2))
+        h.voxel_fuse([(dev, 0, 1)], [m])
+        assert h.voxel_info(m)["n_voxels"] == n
+        pts = torch.empty((n, 16), dtype=torch.uint8, device="cuda")
+        ms, all_ms = event_ms(lambda: h.voxel_extract(m, points=pts, capacity=n), args.repeats)
+        out.append({"log2_capacity": log2, "voxels": n, "ms": ms, "all_ms": all_ms, "voxels_per_s": n / (ms * 1e-3)})
+    return out
+
+
+def host_leg(args, slam, slots):
+    t0 = time.perf_counter()
+    job = slam.export_cloud("last_keyframes", list(range(slots)), step=args.step, layout="organized")
+    t1 = time.perf_counter()
+    fused = 0
+    for i in range(slots):
+        org = job.organized(i)
+        if org is None:
+            continue
+        m = VR.Map(args.voxel, 26)
+        m.fuse(org.ravel(), 1)
+        fused += m.n_fused
+    t2 = time.perf_counter()
+    return {"slots": slots, "download_ms": (t1 - t0) * 1e3, "numpy_fuse_ms": (t2 - t1) * 1e3, "fused": fused,
+            "fused_records_per_s": fused / (t2 - t0)}
+
+
+def pipelined_leg(args, device, cfg, lefts, rights):
+    slam, packed = start(cfg, lefts, rights, args.pipe_slots, args.groups, device, args.steps + args.warmup)
+    slam.set_voxel_maps(args.voxel, args.pipe_log2)
+    for k in range(args.warmup):
+        slam.submit_packed(packed[k])
+    slam.wait()
+    fps = {"plain": [], "fused": []}
+    for _ in range(args.repeats):
+        for leg in ("plain", "fused"):
+            slam.clear_voxel_maps()
+            keep = []
+            torch.cuda.synchronize(device)
+            t0 = time.perf_counter()
+            for k in range(args.warmup, args.warmup + args.steps):
+                slam.submit_packed(packed[k])
+                if leg == "fused":
+                    keep.append(slam.submit_fuse("last_keyframes", None, step=args.step))
+            slam.wait()
+            fps[leg].append(args.steps * args.pipe_slots / (time.perf_counter() - t0))
+    statuses = np.bincount(np.concatenate([j.info["status"] for j in keep]), minlength=4).tolist() if keep else []
+    out = {"slots": args.pipe_slots, "groups": args.groups, "steps": args.steps, "log2_capacity": args.pipe_log2,
+           "frames_per_s": {k: statistics.median(v) for k, v in fps.items()}, "all": fps, "fuse_statuses_last_leg": statuses}
+    slam.close()
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--slots", type=int, default=256)
+    ap.add_argument("--step", type=int, default=4)
+    ap.add_argument("--voxel", type=float, default=0.05)
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=6)
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--pipe-slots", type=int, default=1024)
+    ap.add_argument("--pipe-log2", type=int, default=18)
+    ap.add_argument("--groups", type=int, default=4)
+    ap.add_argument("--loop-frames", type=int, default=bench.LOOP_FRAMES)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    device = torch.device("cuda", 0)
+    cfg, lefts, rights = bench.render_loops("euroc", list(range(min(8, args.slots))), args.loop_frames, device)
+    slam, packed = start(cfg, lefts, rights, args.slots, 1, device, args.warmup)
+    for k in range(args.warmup):
+        slam.submit_packed(packed[k])
+    slam.wait()
+    job = slam.export_cloud("last_keyframes", None, step=args.step, layout="organized", device=True)
+    points = job.points_per_slot
+    clouds = [job.points_buffer[i * points:(i + 1) * points] for i in range(args.slots) if int(job.segments[i]["status"]) == hip_lib.CLOUD_OK]
+    h = hip_lib.Handle(0, 1024)
+    total = len(clouds) * points
+    log2_one = min(26, int(np.ceil(np.log2(total * 4 / 3 + 2))))
+    log2_each = max(10, int(np.ceil(np.log2(points * 4 / 3 + 2))))
+    out = {"tool": "tools/voxel_bench.py", "date": datetime.date.today().isoformat(), "command": " ".join(sys.argv),
+           "device": torch.cuda.get_device_name(0), "step": args.step, "voxel": args.voxel, "points_per_slot": points,
+           "fuse": fuse_leg(args, h, clouds, points, log2_one, log2_each), "pile": pile_leg(args, h, points),
+           "extract": extract_leg(args, h, 22), "host_path": host_leg(args, slam, min(args.slots, 16))}
+    slam.close()
+    out["pipelined"] = pipelined_leg(args, device, cfg, lefts, rights)
+    path = args.out or os.path.join(ROOT, "profiles", "voxel_bench.json")
+    with open(path, "w") as fh:
+        json.dump(out, fh, indent=1)
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
