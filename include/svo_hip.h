@@ -2078,6 +2078,17 @@ typedef struct svo_ssd_sequence {
 } svo_ssd_sequence;
 int svo_ssd_disparity_batch(svo_handle *h, int batch, const svo_ssd_sequence *seqs, int n_bound, int win, int search_y,
                             int *max_win);
+/* Diagnostic: ssd_disparity_kernel (one wavefront per keypoint) against the four-wave kernel it replaced, which the
+ * library keeps for this entry only. Both run on the same batch in svo_ssd_disparity_batch's launch form, with the
+ * same checks; neither writes the sequences' own disparity arrays (which may be NULL). Each kernel writes into
+ * [batch][stride] floats of its own, every word set to `fill` first, sequence b's entry i at b * stride + i
+ * (stride >= every cap): an entry only one kernel writes differs, an entry neither wrote holds `fill`. *n_diff: the
+ * number of 32-bit words that differ, *first_diff the index of the first (-1: none). disp_out / ref_out: NULL, or
+ * device memory of batch * stride floats that receives the kernel's / the reference kernel's array. Complete on
+ * return. */
+int svo_ssd_disparity_check(svo_handle *h, int batch, const svo_ssd_sequence *seqs, int n_bound, int win, int search_y,
+                            int stride, uint32_t fill, float *disp_out, float *ref_out, int64_t *n_diff,
+                            int64_t *first_diff);
 
 /* Diagnostic: the depth filter update as the tracker launches it for a tracked frame (svo_filter_update_batch is the
  * stage form: explicit references, nothing written outside the frame's arrays). Keypoint i of sequence b comes from

@@ -3,7 +3,7 @@
 //
 //  * ssd_disparity_kernel (C1): calculate_disparities (depth_filter.cpp:259-327)
 //    and the identical loop of DepthCalculator::calculate_depth
-//    (depth_calculator.cpp:200-240). One workgroup per keypoint; template and
+//    (depth_calculator.cpp:200-240). One wavefront per keypoint; template and
 //    search region live in LDS; exact int32 SSD (cv::matchTemplate TM_SQDIFF),
 //    first minimum of the float map in row-major order (cv::minMaxLoc) and
 //    the tie-averaged column of :313-323.
@@ -11,63 +11,102 @@
 //    update_kps3d (:130-257), the flag/write-back loop of
 //    StereoSlam::new_image (src/lib/stereo_slam.cpp:205-229) and the counter
 //    of KeyFrameManager::keyframe_needed (keyframe_manager.cpp:47-74).
-#include "svo_kernels.hpp"
+#include "ssd_common.hpp"
 
 namespace svo {
 
-// 4 consecutive pixels of row y starting at column x as one (possibly unaligned)
-// dword load, cut to `valid` bytes; byte loads only where the dword would run
-// past the end of the image row
-typedef uint32_t __attribute__((aligned(1))) u32_unaligned;
-__device__ inline uint32_t load_u8x4(const ImgView& im, int y, int x, int valid) {
-    const uint8_t* src = im.g() + (size_t)y * im.stride + x;
-    uint32_t v;
-    if (x + 4 <= im.w) {
-        v = *reinterpret_cast<const u32_unaligned*>(src);
-    } else {
-        v = 0;
-#pragma unroll
-        for (int b = 0; b < 4; b++)
-            if (x + b < im.w) v |= (uint32_t)src[b] << (8 * b);
-    }
-    if (valid < 4) v &= (1u << (8 * valid)) - 1u;
+constexpr int SSD_P_STRIDE = 100;               // ints per row of the column-sum prefixes: >= region width + 1, and = 4 mod 16, so
+                                                // the rows 4 * (lane >> 4) of a gather start 16 banks apart
+
+// what a barrier is to a workgroup of one wavefront: LDS operations of a wave complete in program order, so the
+// compiler keeping that order is all there is to do
+__device__ __forceinline__ void ssd_wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// inclusive prefix sum over the 64 lanes: four shifts inside the 16-lane rows, then row_bcast:15 / row_bcast:31
+// carry a row's last lane into the rows after it (wave_sum_bcast_i, svo_device.hpp)
+__device__ __forceinline__ int ssd_wave_scan_i(int v) {
+    v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xF, 0xF, false);   // row_shr:1 (a lane without a source adds 0)
+    v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xF, 0xF, false);   // row_shr:2
+    v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xF, 0xF, false);   // row_shr:4
+    v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xF, 0xF, false);   // row_shr:8
+    v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xA, 0xF, false);   // row_bcast:15 into rows 1 and 3
+    v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xC, 0xF, false);   // row_bcast:31 into rows 2 and 3
     return v;
 }
 
-// 16 consecutive pixels of row y starting at column x (any alignment), every valid byte ^ (flip & 0xff),
-// bytes from `valid` on = (pad & 0xff): one 16-byte load when the row has them, dwords otherwise
-__device__ inline uint4 load_u8x16(const ImgView& im, int y, int x, int valid, uint32_t flip, uint32_t pad) {
-    uint32_t w[4];
-    if (x + 16 <= im.w) {
-        const uint8_t* src = im.g() + (size_t)y * im.stride + x;
-        __builtin_memcpy(w, src, 16);                     // (one global_load_dwordx4: any byte alignment)
+// The cross term of NMB x NJB blocks of the match map: per template row one Toeplitz B fragment (5 dwords +
+// v_alignbyte), then per block one ds_read_b128 A fragment and one v_mfma_i32_16x16x64_i8. The block counts are
+// template parameters so that a row's reads stand in one basic block, ahead of its matrix instructions.
+template <int R_ROWS, int N_MB, int N_JB, int NMB, int NJB>
+__device__ __forceinline__ void ssd_cross(const uint8_t* s_t, const uint8_t* s_r, int th, int lane, ssd_v4i (&acc)[N_MB][N_JB]) {
+    const int fm = lane & 15, fh = lane >> 4;        // fragment row / column and 16-byte k slice
+    // B: bytes [16 + 16 fh - fm, +16) of the padded template row
+    const int o = 16 + 16 * fh - fm;
+    const uint32_t* tb = reinterpret_cast<const uint32_t*>(s_t) + (o >> 2);
+    const unsigned sh = (unsigned)(o & 3);
+    const uint8_t* ab = s_r + 16 * fh;
+    // the operands of a template row: five dwords of the template and a 16-byte piece of the region per block
+    struct Row { uint32_t t[5]; ssd_v4i af[NMB][NJB]; };
+    auto read_row = [&](int r, Row& w) {
+        const uint32_t* t = tb + r * (SSD_T_STRIDE / 4);
+#pragma unroll
+        for (int d = 0; d < 5; d++) w.t[d] = t[d];
+#pragma unroll
+        for (int mb = 0; mb < NMB; mb++)
+#pragma unroll
+            for (int jb = 0; jb < NJB; jb++)
+                w.af[mb][jb] = *reinterpret_cast<const ssd_v4i*>(ab + 16 * jb + min(16 * mb + fm + r, R_ROWS - 1) * SSD_R_STRIDE);
+    };
+    auto use_row = [&](const Row& w) {
+        ssd_v4i bf;
+        bf.x = (int)__builtin_amdgcn_alignbyte(w.t[1], w.t[0], sh);
+        bf.y = (int)__builtin_amdgcn_alignbyte(w.t[2], w.t[1], sh);
+        bf.z = (int)__builtin_amdgcn_alignbyte(w.t[3], w.t[2], sh);
+        bf.w = (int)__builtin_amdgcn_alignbyte(w.t[4], w.t[3], sh);
+#pragma unroll
+        for (int mb = 0; mb < NMB; mb++)
+#pragma unroll
+            for (int jb = 0; jb < NJB; jb++)
+                acc[mb][jb] = __builtin_amdgcn_mfma_i32_16x16x64_i8(w.af[mb][jb], bf, acc[mb][jb], 0, 0, 0);
+    };
+    if constexpr (NMB * NJB <= 5) {
+        // one wave has nobody to hide its LDS round trip behind: two rows per trip, all their reads issued first.
+        // Template row th is staged as zeros (th <= SSD_MAX_WIN, and s_t has one row more), so an odd th adds 0.
+        for (int r = 0; r < th; r += 2) {
+            Row r0, r1;
+            read_row(r, r0);
+            read_row(r + 1, r1);
+            use_row(r0);
+            use_row(r1);
+        }
     } else {
-#pragma unroll
-        for (int k = 0; k < 4; k++) w[k] = load_u8x4(im, y, x + 4 * k, 4);
+        for (int r = 0; r < th; r++) {     // (ten blocks: two rows' operands do not fit 128 registers)
+            Row cur;
+            read_row(r, cur);
+            use_row(cur);
+        }
     }
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        const int nv = valid - 4 * k;                     // valid bytes of this dword
-        const uint32_t vm = nv >= 4 ? 0xFFFFFFFFu : (nv <= 0 ? 0u : ((1u << (8 * nv)) - 1u));
-        w[k] = ((w[k] ^ flip) & vm) | (pad & ~vm);
+}
+template <int R_ROWS, int N_MB, int N_JB, int NMB>
+__device__ __forceinline__ void ssd_cross_jb(const uint8_t* s_t, const uint8_t* s_r, int th, int lane, int n_jb,
+                                             ssd_v4i (&acc)[N_MB][N_JB]) {
+    static_assert(N_JB == 5, "one case per column block count");
+    switch (n_jb) {
+        case 1: ssd_cross<R_ROWS, N_MB, N_JB, NMB, 1>(s_t, s_r, th, lane, acc); break;
+        case 2: ssd_cross<R_ROWS, N_MB, N_JB, NMB, 2>(s_t, s_r, th, lane, acc); break;
+        case 3: ssd_cross<R_ROWS, N_MB, N_JB, NMB, 3>(s_t, s_r, th, lane, acc); break;
+        case 4: ssd_cross<R_ROWS, N_MB, N_JB, NMB, 4>(s_t, s_r, th, lane, acc); break;
+        default: ssd_cross<R_ROWS, N_MB, N_JB, NMB, 5>(s_t, s_r, th, lane, acc); break;
     }
-    return make_uint4(w[0], w[1], w[2], w[3]);
 }
 
-constexpr int SSD_WIN_ALL = 35, SSD_MH_ALL = 17; // template edge and match-map rows (2*search_y+1) the entry points accept
-constexpr int SSD_MAX_MW = 65;                  // match-map columns (search_x+1)
-constexpr int SSD_T_STRIDE = 96;                // bytes per padded template row: 16 zeros | row | zeros
-constexpr int SSD_R_STRIDE = 144;               // bytes per search-region row (36 dwords: conflict-free b128 rows)
-constexpr int SSD_W_STRIDE = 105;               // ints per row of the column sums (= 1 mod 8: the 8 rows x 8 segments of 8 columns
-                                                // that a wave reads in the row pass hit 64 different banks; 100 was a 4-way conflict)
-#ifndef SVO_SSD_THREADS
-#define SVO_SSD_THREADS 256
-#endif
-constexpr int SSD_THREADS = SVO_SSD_THREADS;
-
-typedef int ssd_v4i __attribute__((ext_vector_type(4)));
-
-// C1. One workgroup (4 waves) per keypoint. cv::matchTemplate(TM_SQDIFF) is
+// C1. One wavefront per keypoint (single-wave workgroups: a keypoint starts as soon as one wave slot and 9.4 KB of
+// LDS are free anywhere, where the four-wave workgroup this replaced waited for four slots and 15 KB on one CU).
+// cv::matchTemplate(TM_SQDIFF) is
 //   SSD[k][j] = sum_w R^2 - 2 sum_w R*T + sum T^2   over the window w at offset (k, j),
 // exact in integers, and it is invariant to subtracting 128 from every pixel, so both images
 // are staged as signed bytes (x ^ 0x80).
@@ -77,33 +116,33 @@ typedef int ssd_v4i __attribute__((ext_vector_type(4)));
 //        D[k][n] += sum_x A[k][x] * B[x][n],  A[k][x] = R[k + r][j0 + x]  (aligned 16 B / lane),
 //                                             B[x][n] = T[r][x - n]       (0 outside the row),
 //    so D[k][n] accumulates sum_{r,c} R[k+r][j0+n+c] T[r][c] over the th rows. Rows k >= mh and
-//    columns j >= mw of D are computed and dropped. A wave owns a (16-row, 16-column) block of
-//    the match map; B is rebuilt per row from the zero-padded template (5 dwords + v_alignbyte).
-//    Any k-order inside the instruction is fine as long as A and B agree: lane l holds bytes
-//    16*(l>>4) .. +15 of its row / column for both operands.
-//  * sum_w R^2: sliding window sums, columns first (one thread per region column), then rows.
+//    columns j >= mw of D are computed and dropped. B depends on the template row and the lane only: it is built
+//    once per row (zero-padded template, 5 dwords + v_alignbyte) and serves every block of the map, whose
+//    accumulators all stay in registers. Any k-order inside the instruction is fine as long as A and B agree:
+//    lane l holds bytes 16*(l>>4) .. +15 of its row / column for both operands.
+//  * sum_w R^2: a lane owns region columns lane and lane + 64 and keeps their sliding column sums W[k][x] =
+//    sum_{r<th} R[k+r][x]^2 of all map rows in registers. Once the matrix loop is done with the region tile, the
+//    prefix sums of W along x (a wave scan) take its place, and a window sum is P[k][j + tw] - P[k][j], gathered
+//    in the accumulators' layout. The match map itself is never stored.
 //  * argmin: cv::minMaxLoc runs on matchTemplate's CV_32F result, so it is the first minimum in row-major
 //    order of the map ROUNDED TO FLOAT (two integers above 2^24 that round to one float tie, and the earlier
 //    wins); the key is (bits of (float)SSD, index). Then the tie-averaged column of :313-323.
 // SSD_MAX_WIN / SSD_MAX_MH: what the LDS is sized for. The window kernels of a step share each CU's 160 KB with
 // the alignment kernel's 38 KB per wavefront, and what fits is what runs: the shape for windows up to 31 and
-// search_y up to 6 (every configuration of the reference) takes 14.9 KB instead of 18.2.
+// search_y up to 6 (every configuration of the reference) takes 9.4 KB, the other 11.0.
 template <int SSD_MAX_WIN, int SSD_MAX_MH>
-__global__ __launch_bounds__(SSD_THREADS) void ssd_disparity_kernel(const SsdArgs* __restrict__ args) {
-    constexpr int SSD_R_ROWS = SSD_MAX_WIN + SSD_MAX_MH, SSD_MAX_MATCH = SSD_MAX_MW * SSD_MAX_MH;
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void ssd_disparity_kernel(const SsdArgs* __restrict__ args) {
+    constexpr int SSD_R_ROWS = SSD_MAX_WIN + SSD_MAX_MH, SSD_T_ROWS = SSD_MAX_WIN + 1;
+    constexpr int N_MB = (SSD_MAX_MH + 15) / 16, N_JB = (SSD_MAX_MW + 15) / 16;
     const SsdArgs& a = args[blockIdx.y];
     if (a.enable && !*G(a.enable)) return;
     const int n = *G(a.n_ptr);
     const int kp = a.first + (a.first_ptr ? *G(a.first_ptr) : 0) + (int)blockIdx.x;
     if (kp >= n) return;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int lane = threadIdx.x;
 
-    __shared__ __attribute__((aligned(16))) uint8_t s_t[(SSD_MAX_WIN + 1) * SSD_T_STRIDE];
+    __shared__ __attribute__((aligned(16))) uint8_t s_t[SSD_T_ROWS * SSD_T_STRIDE];
     __shared__ __attribute__((aligned(16))) uint8_t s_r[SSD_R_ROWS * SSD_R_STRIDE];
-    __shared__ int s_w[SSD_MAX_MH * SSD_W_STRIDE];
-    __shared__ int s_tt[4];
-    __shared__ unsigned long long s_key[SSD_THREADS / 64];
-    __shared__ int s_sum[SSD_THREADS / 64], s_cnt[SSD_THREADS / 64];
 
     const int window_before = a.win / 2, window_after = (a.win + 1) / 2;
     const int cols = a.left.w, rows = a.left.h;
@@ -123,173 +162,195 @@ __global__ __launch_bounds__(SSD_THREADS) void ssd_disparity_kernel(const SsdArg
     if (a.clamp_half && (x12 <= 0 || y12 <= 0 || x11 >= cols - 1 || y11 >= rows - 1)) skip = true;
     if (a.clamp_half && (x22 <= 0 || y22 <= 0 || x21 >= cols - 1 || y21 >= rows - 1)) skip = true;
     if (tw <= 0 || th <= 0 || mw <= 0 || mh <= 0) skip = true;
-    if (tw > SSD_MAX_WIN || th > SSD_MAX_WIN || mw > SSD_MAX_MW || mh > SSD_MAX_MH || rw > SSD_W_STRIDE ||
+    if (tw > SSD_MAX_WIN || th > SSD_MAX_WIN || mw > SSD_MAX_MW || mh > SSD_MAX_MH || rw >= SSD_P_STRIDE ||
         rh > SSD_R_ROWS)
         skip = true;  // the host validates window sizes; never taken with valid settings
     if (skip) {
-        if (tid == 0) G(a.disparity)[kp] = -1.0f;
+        if (lane == 0) G(a.disparity)[kp] = -1.0f;
         return;
     }
 
     // ---- stage: template rows as [16 zero bytes | row ^ 0x80 | zeros], search region ^ 0x80 (bytes past
-    // the region's width: 0x80), 16 bytes per lane and step: a template row is three chunks, a region row
-    // up to six (round 2 staged dwords: 7 + 3 trips of ~22 instructions per thread against 2 + 1 here)
+    // the region's width: 0x80), 16 bytes per lane and chunk: a template row is three chunks, a region row
+    // up to six. A lane has 3 + 7 chunks (4 + 8 in the large shape): the 16-byte loads of all of them are issued
+    // first, then the dword and byte loads of chunks that cross the image's right edge, and only then is anything
+    // used.
     static_assert(SSD_T_STRIDE % 16 == 0 && SSD_R_STRIDE % 16 == 0, "rows are whole 16-byte chunks");
-    for (int i = tid; i < (SSD_MAX_WIN + 1) * (SSD_T_STRIDE / 16); i += SSD_THREADS) {
-        const int r = i / (SSD_T_STRIDE / 16), ch = i % (SSD_T_STRIDE / 16);
-        const int c = 16 * (ch - 1);                      // template column of the chunk's first byte
-        uint4 v = make_uint4(0, 0, 0, 0);
-        if (r < th && c >= 0 && c < tw) v = load_u8x16(a.left, y11 + r, x11 + c, tw - c, 0x80808080u, 0u);
-        reinterpret_cast<uint4*>(s_t)[i] = v;
-    }
-    for (int i = tid; i < SSD_R_ROWS * (SSD_R_STRIDE / 16); i += SSD_THREADS) {
-        const int r = i / (SSD_R_STRIDE / 16), ch = i % (SSD_R_STRIDE / 16);
-        uint4 v = make_uint4(0, 0, 0, 0);
-        if (r < rh && 16 * ch < rw) v = load_u8x16(a.right, y21 + r, x21 + 16 * ch, rw - 16 * ch, 0x80808080u, 0x80808080u);
-        reinterpret_cast<uint4*>(s_r)[i] = v;
-    }
-    __syncthreads();
-
-    // ---- sum T^2 (wave 3) and the column sums W[k][x] = sum_{r<th} R[k+r][x]^2 (one thread per column)
-    if (wave == SSD_THREADS / 64 - 1) {
-        int tt = 0;
-        if (lane < th) {
-            const uint32_t* trow = reinterpret_cast<const uint32_t*>(s_t + lane * SSD_T_STRIDE) + 4;
-#pragma unroll
-            for (int d = 0; d < 9; d++) tt = __builtin_amdgcn_sdot4((int)trow[d], (int)trow[d], tt, false);
-        }
-        tt = wave_sum_dpp_i(tt);
-        if (lane == 0) s_tt[0] = tt;
-    }
-    if (tid < rw) {
-        const int8_t* col = reinterpret_cast<const int8_t*>(s_r) + tid;
-        int sq = 0;
-        for (int r = 0; r < th; r++) {
-            const int v = col[r * SSD_R_STRIDE];
-            sq += __mul24(v, v);
-        }
-        s_w[tid] = sq;
-        for (int k = 1; k < mh; k++) {
-            const int vn = col[(k + th - 1) * SSD_R_STRIDE], vo = col[(k - 1) * SSD_R_STRIDE];
-            sq += __mul24(vn, vn) - __mul24(vo, vo);
-            s_w[k * SSD_W_STRIDE + tid] = sq;
-        }
-    }
-
-    // ---- cross term on the matrix cores: wave -> (row block, column block) of the match map
-    const int n_jb = (mw + 15) >> 4, n_mb = (mh + 15) >> 4;
-    const int fm = lane & 15, fh = lane >> 4;        // fragment row / column and 16-byte k slice
-    constexpr int SSD_SLOTS = (10 + SSD_THREADS / 64 - 1) / (SSD_THREADS / 64);   // <= 2 x 5 blocks over the waves
-    ssd_v4i acc[SSD_SLOTS];
-    int task_of[SSD_SLOTS];
-#pragma unroll
-    for (int t = 0; t < SSD_SLOTS; t++) { acc[t] = ssd_v4i{0, 0, 0, 0}; task_of[t] = -1; }
     {
-        int slot = 0;
-        for (int task = wave; task < n_jb * n_mb && slot < SSD_SLOTS; task += SSD_THREADS / 64, slot++) {
-            task_of[slot] = task;
-            const int mb = task >= n_jb ? 1 : 0, jb = task - mb * n_jb;      // (at most two row blocks: the map has <= 17 rows)
-            // B: bytes [16 + 16 fh - fm, +16) of the padded template row
-            const int o = 16 + 16 * fh - fm;
-            const uint32_t* tb = reinterpret_cast<const uint32_t*>(s_t) + (o >> 2);
-            const unsigned sh = (unsigned)(o & 3);
-            const uint8_t* ab = s_r + (16 * jb + 16 * fh);
-            const int arow = 16 * mb + fm;
-            ssd_v4i c = {0, 0, 0, 0};
-            for (int r = 0; r < th; r++) {
-                const uint32_t* t = tb + r * (SSD_T_STRIDE / 4);
-                const uint32_t t0 = t[0], t1 = t[1], t2 = t[2], t3 = t[3], t4 = t[4];
-                ssd_v4i bf;
-                bf.x = (int)__builtin_amdgcn_alignbyte(t1, t0, sh);
-                bf.y = (int)__builtin_amdgcn_alignbyte(t2, t1, sh);
-                bf.z = (int)__builtin_amdgcn_alignbyte(t3, t2, sh);
-                bf.w = (int)__builtin_amdgcn_alignbyte(t4, t3, sh);
-                const ssd_v4i af = *reinterpret_cast<const ssd_v4i*>(ab + min(arow + r, SSD_R_ROWS - 1) * SSD_R_STRIDE);
-                c = __builtin_amdgcn_mfma_i32_16x16x64_i8(af, bf, c, 0, 0, 0);
+        constexpr int T_CH = SSD_T_STRIDE / 16, R_CH = SSD_R_STRIDE / 16;
+        constexpr int NT = SSD_T_ROWS * T_CH, NR = SSD_R_ROWS * R_CH, T_TRIPS = (NT + 63) / 64, R_TRIPS = (NR + 63) / 64;
+        uint4 tv[T_TRIPS], rv[R_TRIPS];
+        const int lw = a.left.w, rwid = a.right.w;
+#pragma unroll
+        for (int t = 0; t < T_TRIPS; t++) {
+            const int i = lane + 64 * t, r = i / T_CH, c = 16 * (i % T_CH - 1);    // c: template column of the chunk's first byte
+            tv[t] = make_uint4(0, 0, 0, 0);
+            if (r < th && c >= 0 && c < tw && x11 + c + 16 <= lw) tv[t] = load_u8x16_whole(a.left, y11 + r, x11 + c);
+        }
+#pragma unroll
+        for (int t = 0; t < R_TRIPS; t++) {
+            const int i = lane + 64 * t, r = i / R_CH, c = 16 * (i % R_CH);
+            rv[t] = make_uint4(0, 0, 0, 0);
+            if (r < rh && c < rw && x21 + c + 16 <= rwid) rv[t] = load_u8x16_whole(a.right, y21 + r, x21 + c);
+        }
+#pragma unroll
+        for (int t = 0; t < T_TRIPS; t++) {
+            const int i = lane + 64 * t, r = i / T_CH, c = 16 * (i % T_CH - 1);
+            if (r < th && c >= 0 && c < tw && x11 + c + 16 > lw) tv[t] = load_u8x16_edge(a.left, y11 + r, x11 + c);
+        }
+#pragma unroll
+        for (int t = 0; t < R_TRIPS; t++) {
+            const int i = lane + 64 * t, r = i / R_CH, c = 16 * (i % R_CH);
+            if (r < rh && c < rw && x21 + c + 16 > rwid) rv[t] = load_u8x16_edge(a.right, y21 + r, x21 + c);
+        }
+#pragma unroll
+        for (int t = 0; t < T_TRIPS; t++) {
+            const int i = lane + 64 * t, r = i / T_CH, c = 16 * (i % T_CH - 1);
+            uint4 v = make_uint4(0, 0, 0, 0);
+            if (r < th && c >= 0 && c < tw) v = finish_u8x16(tv[t], tw - c, 0x80808080u, 0u);
+            if (NT % 64 == 0 || i < NT) reinterpret_cast<uint4*>(s_t)[i] = v;
+        }
+#pragma unroll
+        for (int t = 0; t < R_TRIPS; t++) {
+            const int i = lane + 64 * t, r = i / R_CH, c = 16 * (i % R_CH);
+            uint4 v = make_uint4(0, 0, 0, 0);
+            if (r < rh && c < rw) v = finish_u8x16(rv[t], rw - c, 0x80808080u, 0x80808080u);
+            if (NR % 64 == 0 || i < NR) reinterpret_cast<uint4*>(s_r)[i] = v;
+        }
+    }
+    ssd_wave_sync();
+
+    // ---- sum T^2: a lane per template row
+    int stt = 0;
+    if (lane < th) {
+        const uint32_t* trow = reinterpret_cast<const uint32_t*>(s_t + lane * SSD_T_STRIDE) + 4;
+#pragma unroll
+        for (int d = 0; d < 9; d++) stt = __builtin_amdgcn_sdot4((int)trow[d], (int)trow[d], stt, false);
+    }
+    stt = wave_sum_dpp_i(stt);
+
+    // ---- cross term on the matrix cores: every block of the match map in this wave
+    const int n_jb = (mw + 15) >> 4;
+    const int fm = lane & 15, fh = lane >> 4;
+    ssd_v4i acc[N_MB][N_JB];
+#pragma unroll
+    for (int mb = 0; mb < N_MB; mb++)
+#pragma unroll
+        for (int jb = 0; jb < N_JB; jb++) acc[mb][jb] = ssd_v4i{0, 0, 0, 0};
+    static_assert(N_MB <= 2, "two row blocks of 16 at most");
+    if (N_MB == 2 && mh > 16) ssd_cross_jb<SSD_R_ROWS, N_MB, N_JB, N_MB>(s_t, s_r, th, lane, n_jb, acc);
+    else ssd_cross_jb<SSD_R_ROWS, N_MB, N_JB, 1>(s_t, s_r, th, lane, n_jb, acc);
+    // ---- column sums W[k][x] = sum_{r<th} R[k+r][x]^2 of region columns lane and lane + 64 (both inside the tile's
+    // 144 bytes; what columns >= rw give is never used), the reads of a sweep issued together: eight rows of the
+    // first window at a time, then the rows entering and leaving for all other map rows at once. Rows up to
+    // SSD_R_ROWS - 2 are read, all staged.
+    int w0[SSD_MAX_MH], w1[SSD_MAX_MH];
+    {
+        const int8_t* col = reinterpret_cast<const int8_t*>(s_r) + lane;
+        int sq0 = 0, sq1 = 0;
+        for (int r0 = 0; r0 < th; r0 += 8) {
+            int v0[8], v1[8];
+#pragma unroll
+            for (int i = 0; i < 8; i++) {
+                const int rr = min(r0 + i, SSD_R_ROWS - 1);
+                v0[i] = col[rr * SSD_R_STRIDE];
+                v1[i] = col[rr * SSD_R_STRIDE + 64];
             }
-            acc[slot] = c;
-        }
-    }
-    __syncthreads();
-
-    // ---- window sums of R^2: rows of W, 8 sliding segments per map row -> s_m. The match map takes
-    // the place of the search region, which nobody reads after the barrier above (17.4 KB of LDS per
-    // workgroup instead of 21.7: one more workgroup fits beside the alignment kernel's on a CU)
-    static_assert(sizeof(int) * SSD_MAX_MATCH <= SSD_R_ROWS * SSD_R_STRIDE, "match map must fit the region tile");
-    static_assert(SSD_MAX_MH <= 32, "two row blocks of 16 at most");
-    int* const s_m = reinterpret_cast<int*>(s_r);
-    {
-        const int seg_len = (mw + 7) >> 3;
-        for (int item = tid; item < mh * 8; item += SSD_THREADS) {
-            const int k = item >> 3, j0 = (item & 7) * seg_len, j1 = min(mw, j0 + seg_len);
-            if (j0 < j1) {
-                const int* wrow = &s_w[k * SSD_W_STRIDE];
-                int sq = 0;
-                for (int c = 0; c < tw; c++) sq += wrow[j0 + c];
-                s_m[k * mw + j0] = sq;
-                for (int j = j0 + 1; j < j1; j++) {
-                    sq += wrow[j + tw - 1] - wrow[j - 1];
-                    s_m[k * mw + j] = sq;
-                }
+#pragma unroll
+            for (int i = 0; i < 8; i++) {
+                const bool in = r0 + i < th;
+                sq0 += in ? __mul24(v0[i], v0[i]) : 0;
+                sq1 += in ? __mul24(v1[i], v1[i]) : 0;
             }
         }
-    }
-    __syncthreads();
-    {
-        const int stt = s_tt[0];
+        w0[0] = sq0; w1[0] = sq1;
+        const int8_t* coln = col + (th - 1) * SSD_R_STRIDE;
+        int n0[SSD_MAX_MH], n1[SSD_MAX_MH], o0[SSD_MAX_MH], o1[SSD_MAX_MH];
 #pragma unroll
-        for (int slot = 0; slot < SSD_SLOTS; slot++) {
-            const int task = task_of[slot];
-            if (task < 0) continue;
-            const int mb = task >= n_jb ? 1 : 0, jb = task - mb * n_jb;      // (at most two row blocks: the map has <= 17 rows)
-            const int j = 16 * jb + fm;                     // C/D: col = lane & 15, row = 4 (lane >> 4) + reg
+        for (int k = 1; k < SSD_MAX_MH; k++) {
+            n0[k] = coln[k * SSD_R_STRIDE]; n1[k] = coln[k * SSD_R_STRIDE + 64];
+            o0[k] = col[(k - 1) * SSD_R_STRIDE]; o1[k] = col[(k - 1) * SSD_R_STRIDE + 64];
+        }
 #pragma unroll
-            for (int i = 0; i < 4; i++) {
-                const int k = 16 * mb + 4 * fh + i;
-                if (k < mh && j < mw) s_m[k * mw + j] += stt - 2 * acc[slot][i];
-            }
+        for (int k = 1; k < SSD_MAX_MH; k++) {
+            sq0 += __mul24(n0[k], n0[k]) - __mul24(o0[k], o0[k]);
+            sq1 += __mul24(n1[k], n1[k]) - __mul24(o1[k], o1[k]);
+            w0[k] = sq0; w1[k] = sq1;
         }
     }
-    __syncthreads();
+    ssd_wave_sync();
 
-    const int nm = mw * mh;
-    unsigned long long best = ~0ull;
-    for (int o = tid; o < nm; o += SSD_THREADS) {
-        const unsigned long long key = ((unsigned long long)__float_as_uint((float)s_m[o]) << 32) | (unsigned)o;
-        best = key < best ? key : best;
+    // ---- prefix sums of W along the columns take the place of the region tile, which nobody reads any more:
+    // P[k][0] = 0, P[k][x + 1] = W[k][0] + .. + W[k][x] for x < rw
+    static_assert(sizeof(int) * SSD_MAX_MH * SSD_P_STRIDE <= SSD_R_ROWS * SSD_R_STRIDE, "the prefix rows must fit the region tile");
+    static_assert(SSD_MAX_WIN + SSD_MAX_MW <= SSD_P_STRIDE && SSD_P_STRIDE <= 128 + 1, "a row holds rw + 1 prefixes of two columns per lane");
+    int* const s_p = reinterpret_cast<int*>(s_r);
+#pragma unroll
+    for (int k = 0; k < SSD_MAX_MH; k++) {
+        if (k < mh) {
+            const int p0 = ssd_wave_scan_i(w0[k]);
+            const int p1 = ssd_wave_scan_i(w1[k]) + __builtin_amdgcn_readlane(p0, 63);
+            if (lane == 0) s_p[k * SSD_P_STRIDE] = 0;
+            if (lane < rw) s_p[k * SSD_P_STRIDE + lane + 1] = p0;
+            if (lane + 64 < rw) s_p[k * SSD_P_STRIDE + lane + 65] = p1;
+        }
     }
+    ssd_wave_sync();
+
+    // ---- the map in the accumulators' layout (C/D: col = lane & 15, row = 4 (lane >> 4) + reg) and its argmin.
     // first minimum of the FLOAT map in row-major order == smallest (float bits, index) key: an SSD is not
     // negative, and non-negative floats order like their bit patterns. Above 2^24 different integers round to
     // one float, and cv::minMaxLoc sees the floats: the earlier position wins, not the smaller integer.
+    // An accumulator register then holds the float's bits for the tie pass.
+    unsigned long long best = ~0ull;
+#pragma unroll
+    for (int mb = 0; mb < N_MB; mb++)
+#pragma unroll
+        for (int jb = 0; jb < N_JB; jb++) {
+            if (jb < n_jb && 16 * mb < mh) {
+                const int j = 16 * jb + fm, jc = min(j, mw - 1);     // (clamped: a dropped entry reads inside the rows too)
+#pragma unroll
+                for (int i = 0; i < 4; i++) {
+                    const int k = 16 * mb + 4 * fh + i, kc = min(k, SSD_MAX_MH - 1);
+                    const int* prow = &s_p[kc * SSD_P_STRIDE + jc];
+                    const int ssd = prow[tw] - prow[0] + stt - 2 * acc[mb][jb][i];
+                    const float f = (float)ssd;
+                    acc[mb][jb][i] = (int)__float_as_uint(f);
+                    if (k < mh && j < mw) {
+                        const unsigned long long key = ((unsigned long long)__float_as_uint(f) << 32) | (unsigned)(k * mw + j);
+                        best = key < best ? key : best;
+                    }
+                }
+            }
+        }
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) {
         const unsigned long long other = __shfl_xor(best, o, 64);
         best = other < best ? other : best;
     }
-    if ((tid & 63) == 0) s_key[tid >> 6] = best;
-    __syncthreads();
-    best = s_key[0];
-    for (int w = 1; w < SSD_THREADS / 64; w++) best = s_key[w] < best ? s_key[w] : best;
-    const int min_o = (int)(best & 0xffffffffu);
+    // (every lane holds the same key now: taken as wave-uniform values)
+    const int min_o = __builtin_amdgcn_readfirstlane((int)(best & 0xffffffffu));
     const int minx = min_o % mw, miny = min_o / mw;
-    const float minVal = __uint_as_float((unsigned)(best >> 32));
+    const float minVal = __uint_as_float((unsigned)__builtin_amdgcn_readfirstlane((int)(best >> 32)));
 
     int sumj = 0, cnt = 0;
-    // o / mw without an integer division: exact for o * mw < 2^20 (the map has at most 65 x 17 entries)
-    const unsigned magic = ((1u << 20) + (unsigned)mw - 1u) / (unsigned)mw;
-    for (int o = tid; o < nm; o += SSD_THREADS) {
-        const int k = (int)(((unsigned)o * magic) >> 20), j = o - k * mw;
-        if (j >= minx && k >= miny && (double)(float)s_m[o] <= (double)minVal) { sumj += j; cnt++; }
-    }
+#pragma unroll
+    for (int mb = 0; mb < N_MB; mb++)
+#pragma unroll
+        for (int jb = 0; jb < N_JB; jb++) {
+            const int j = 16 * jb + fm;
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                const int k = 16 * mb + 4 * fh + i;
+                // (a block that was not computed has j >= mw or k >= mh)
+                if (k < mh && j < mw && j >= minx && k >= miny && (double)__uint_as_float((unsigned)acc[mb][jb][i]) <= (double)minVal) { sumj += j; cnt++; }
+            }
+        }
     sumj = wave_sum_dpp_i(sumj);
     cnt = wave_sum_dpp_i(cnt);
-    if ((tid & 63) == 0) { s_sum[tid >> 6] = sumj; s_cnt[tid >> 6] = cnt; }
-    __syncthreads();
-    if (tid == 0) {
-        int ts = 0, tc = 0;
-        for (int w = 0; w < SSD_THREADS / 64; w++) { ts += s_sum[w]; tc += s_cnt[w]; }
-        float minPos = (float)ts;      // sum of small ints: exact in float in any order
-        minPos = minPos / tc;
+    if (lane == 0) {
+        float minPos = (float)sumj;    // sum of small ints: exact in float in any order
+        minPos = minPos / cnt;
         G(a.disparity)[kp] = a.clamp_half ? fmaxf(0.5f, minPos) : minPos;
     }
 }
@@ -298,10 +359,14 @@ int ssd_pick_max_win(int win, int search_y) { return win <= 31 && 2 * search_y +
 
 void launch_ssd(const SsdArgs* d_args, int batch, int max_n, int win, int search_y, hipStream_t stream) {
     if (max_n <= 0) return;
+#ifdef SVO_SSD_FOUR_WAVES     // diagnostic builds (tools/build_variants.sh): the replaced kernel on the product path, for A/B runs
+    launch_ssd_ref(d_args, batch, max_n, win, search_y, stream);
+    return;
+#endif
     if (ssd_pick_max_win(win, search_y) == 31)
-        hipLaunchKernelGGL((ssd_disparity_kernel<31, 13>), dim3(max_n, batch), dim3(SSD_THREADS), 0, stream, d_args);
+        hipLaunchKernelGGL((ssd_disparity_kernel<31, 13>), dim3(max_n, batch), dim3(64), 0, stream, d_args);
     else
-        hipLaunchKernelGGL((ssd_disparity_kernel<SSD_WIN_ALL, SSD_MH_ALL>), dim3(max_n, batch), dim3(SSD_THREADS), 0, stream, d_args);
+        hipLaunchKernelGGL((ssd_disparity_kernel<SSD_WIN_ALL, SSD_MH_ALL>), dim3(max_n, batch), dim3(64), 0, stream, d_args);
 }
 
 // -------------------------------------------------------------------------

@@ -8,6 +8,7 @@
 #include <cstring>
 #include <vector>
 
+#include "ssd_common.hpp"
 #include "svo_handle.hpp"
 
 using namespace svo;
@@ -811,31 +812,32 @@ extern "C" int svo_keyframe_init_batch(svo_handle* h, int batch, const svo_kf_in
     return finish_launch(h);
 }
 
-extern "C" int svo_ssd_disparity_batch(svo_handle* h, int batch, const svo_ssd_sequence* seqs, int n_bound, int win,
-                                       int search_y, int* max_win) {
-    CHECK_H(h);
+// the checks of the two SSD entries and the argument blocks as pack_ssd fills them. own_disparity: the sequences'
+// disparity arrays are the output (svo_ssd_disparity_batch) and must exist; otherwise the caller sets the blocks' own.
+static int ssd_fill_blocks(const char* who, svo_handle* h, int batch, const svo_ssd_sequence* seqs, int n_bound, int win,
+                           int search_y, bool own_disparity, std::vector<SsdArgs>& blocks) {
     constexpr int kMaxIndex = 1 << 29;             // first, *first_ptr and n_bound: their sum stays an int
     if (bad_batch(batch, seqs) || n_bound < 0 || n_bound > kMaxIndex)
-        return svo_set_error(SVO_ERR_INVALID, "svo_ssd_disparity_batch: need 1 <= batch <= 4096, seqs and 0 <= n_bound <= 2^29");
+        return svo_set_error(SVO_ERR_INVALID, "%s: need 1 <= batch <= 4096, seqs and 0 <= n_bound <= 2^29", who);
     if (win < 1 || win > 35 || search_y < 0 || search_y > 8)
-        return svo_set_error(SVO_ERR_INVALID, "svo_ssd_disparity_batch: win<=35, search_y<=8 supported");
+        return svo_set_error(SVO_ERR_INVALID, "%s: win<=35, search_y<=8 supported", who);
     HIP_TRY(hipStreamSynchronize(h->stream));
-    std::vector<SsdArgs> blocks((size_t)batch);
+    blocks.resize((size_t)batch);
     for (int b = 0; b < batch; b++) {
         const svo_ssd_sequence& s = seqs[b];
-        if (klt_bad_view(s.left) || klt_bad_view(s.right) || !s.n || s.cap < 0 || (s.cap > 0 && (!s.kps2d || !s.disparity)) ||
-            s.first < 0 || s.first > kMaxIndex)
-            return svo_set_error(SVO_ERR_INVALID, "svo_ssd_disparity_batch: sequence %d: bad arguments", b);
+        if (klt_bad_view(s.left) || klt_bad_view(s.right) || !s.n || s.cap < 0 ||
+            (s.cap > 0 && (!s.kps2d || (own_disparity && !s.disparity))) || s.first < 0 || s.first > kMaxIndex)
+            return svo_set_error(SVO_ERR_INVALID, "%s: sequence %d: bad arguments", who, b);
         if (s.win < 1 || s.win > win || s.search_x < 0 || s.search_x > 64 || s.search_y < 0 || s.search_y > search_y)
-            return svo_set_error(SVO_ERR_INVALID, "svo_ssd_disparity_batch: sequence %d: win %d, search_x %d, search_y %d exceed "
-                                 "the launch's %d, 64, %d", b, s.win, s.search_x, s.search_y, win, search_y);
+            return svo_set_error(SVO_ERR_INVALID, "%s: sequence %d: win %d, search_x %d, search_y %d exceed "
+                                 "the launch's %d, 64, %d", who, b, s.win, s.search_x, s.search_y, win, search_y);
         int32_t n = 0, first = 0;
         if (const int rc = read_i32(s.n, 1, &n)) return rc;
         if (s.first_ptr)
             if (const int rc = read_i32(s.first_ptr, 1, &first)) return rc;
         if (n < 0 || n > s.cap || first < 0 || first > kMaxIndex)
-            return svo_set_error(SVO_ERR_INVALID, "svo_ssd_disparity_batch: sequence %d: n = %d is outside 0..cap = %d, or "
-                                 "*first_ptr = %d is outside 0..2^29", b, n, s.cap, first);
+            return svo_set_error(SVO_ERR_INVALID, "%s: sequence %d: n = %d is outside 0..cap = %d, or "
+                                 "*first_ptr = %d is outside 0..2^29", who, b, n, s.cap, first);
         SsdArgs& sa = blocks[(size_t)b];
         memset(&sa, 0, sizeof(sa));
         sa.left = make_view(s.left); sa.right = make_view(s.right);
@@ -844,12 +846,295 @@ extern "C" int svo_ssd_disparity_batch(svo_handle* h, int batch, const svo_ssd_s
         sa.first = s.first; sa.first_ptr = s.first_ptr;
         sa.enable = s.enable;
     }
+    return SVO_OK;
+}
+
+extern "C" int svo_ssd_disparity_batch(svo_handle* h, int batch, const svo_ssd_sequence* seqs, int n_bound, int win,
+                                       int search_y, int* max_win) {
+    CHECK_H(h);
+    std::vector<SsdArgs> blocks;
+    int rc = ssd_fill_blocks("svo_ssd_disparity_batch", h, batch, seqs, n_bound, win, search_y, true, blocks);
+    if (rc) return rc;
     SsdArgs* d;
-    const int rc = stage(h, blocks, &d);
+    rc = stage(h, blocks, &d);
     if (rc) return rc;
     if (max_win) *max_win = ssd_pick_max_win(win, search_y);
     launch_ssd(d, batch, n_bound, win, search_y, h->stream);
     return finish_launch(h);
+}
+
+// svo_ssd_disparity_check: ssd_disparity_kernel (depth.hip) against the kernel it replaced. ssd_disparity_ref_kernel is
+// that kernel as it was: one workgroup of four waves per keypoint, a wave per (16-row, 16-column) block of the match map
+// with a Toeplitz fragment of its own, the column sums in a plane of LDS, five barriers. It runs only here, as the
+// definition of every disparity word (values, -1 for a skipped keypoint, and which entries are written at all).
+constexpr int SSD_W_STRIDE = 105;               // ints per row of the column sums (= 1 mod 8: the 8 rows x 8 segments of 8 columns
+                                                // that a wave reads in the row pass hit 64 different banks; 100 was a 4-way conflict)
+constexpr int SSD_REF_THREADS = 256;
+
+template <int SSD_MAX_WIN, int SSD_MAX_MH>
+__global__ __launch_bounds__(SSD_REF_THREADS) void ssd_disparity_ref_kernel(const SsdArgs* __restrict__ args) {
+    constexpr int SSD_THREADS = SSD_REF_THREADS;
+    constexpr int SSD_R_ROWS = SSD_MAX_WIN + SSD_MAX_MH, SSD_MAX_MATCH = SSD_MAX_MW * SSD_MAX_MH;
+    const SsdArgs& a = args[blockIdx.y];
+    if (a.enable && !*G(a.enable)) return;
+    const int n = *G(a.n_ptr);
+    const int kp = a.first + (a.first_ptr ? *G(a.first_ptr) : 0) + (int)blockIdx.x;
+    if (kp >= n) return;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+
+    __shared__ __attribute__((aligned(16))) uint8_t s_t[(SSD_MAX_WIN + 1) * SSD_T_STRIDE];
+    __shared__ __attribute__((aligned(16))) uint8_t s_r[SSD_R_ROWS * SSD_R_STRIDE];
+    __shared__ int s_w[SSD_MAX_MH * SSD_W_STRIDE];
+    __shared__ int s_tt[4];
+    __shared__ unsigned long long s_key[SSD_THREADS / 64];
+    __shared__ int s_sum[SSD_THREADS / 64], s_cnt[SSD_THREADS / 64];
+
+    const int window_before = a.win / 2, window_after = (a.win + 1) / 2;
+    const int cols = a.left.w, rows = a.left.h;
+    const svo_kp2d p = G(a.kps2d)[kp];
+    const int x = (int)p.x, y = (int)p.y;
+    const int x11 = max(0, x - window_before);
+    const int x12 = min(cols - 1, x + window_after);
+    const int y11 = max(0, y - window_before);
+    const int y12 = min(rows, y + window_after);
+    const int x21 = x11;
+    const int x22 = min(cols - 1, x + window_after + a.search_x);
+    const int y21 = max(0, y - window_before - a.search_y);
+    const int y22 = min(rows - 1, y + window_after + a.search_y);
+    const int tw = x12 - x11, th = y12 - y11, rw = x22 - x21, rh = y22 - y21;
+    const int mw = rw - tw + 1, mh = rh - th + 1;
+    bool skip = false;
+    if (a.clamp_half && (x12 <= 0 || y12 <= 0 || x11 >= cols - 1 || y11 >= rows - 1)) skip = true;
+    if (a.clamp_half && (x22 <= 0 || y22 <= 0 || x21 >= cols - 1 || y21 >= rows - 1)) skip = true;
+    if (tw <= 0 || th <= 0 || mw <= 0 || mh <= 0) skip = true;
+    if (tw > SSD_MAX_WIN || th > SSD_MAX_WIN || mw > SSD_MAX_MW || mh > SSD_MAX_MH || rw > SSD_W_STRIDE ||
+        rh > SSD_R_ROWS)
+        skip = true;  // the host validates window sizes; never taken with valid settings
+    if (skip) {
+        if (tid == 0) G(a.disparity)[kp] = -1.0f;
+        return;
+    }
+
+    // ---- stage: template rows as [16 zero bytes | row ^ 0x80 | zeros], search region ^ 0x80 (bytes past
+    // the region's width: 0x80), 16 bytes per lane and step: a template row is three chunks, a region row
+    // up to six
+    static_assert(SSD_T_STRIDE % 16 == 0 && SSD_R_STRIDE % 16 == 0, "rows are whole 16-byte chunks");
+    for (int i = tid; i < (SSD_MAX_WIN + 1) * (SSD_T_STRIDE / 16); i += SSD_THREADS) {
+        const int r = i / (SSD_T_STRIDE / 16), ch = i % (SSD_T_STRIDE / 16);
+        const int c = 16 * (ch - 1);                      // template column of the chunk's first byte
+        uint4 v = make_uint4(0, 0, 0, 0);
+        if (r < th && c >= 0 && c < tw) v = load_u8x16(a.left, y11 + r, x11 + c, tw - c, 0x80808080u, 0u);
+        reinterpret_cast<uint4*>(s_t)[i] = v;
+    }
+    for (int i = tid; i < SSD_R_ROWS * (SSD_R_STRIDE / 16); i += SSD_THREADS) {
+        const int r = i / (SSD_R_STRIDE / 16), ch = i % (SSD_R_STRIDE / 16);
+        uint4 v = make_uint4(0, 0, 0, 0);
+        if (r < rh && 16 * ch < rw) v = load_u8x16(a.right, y21 + r, x21 + 16 * ch, rw - 16 * ch, 0x80808080u, 0x80808080u);
+        reinterpret_cast<uint4*>(s_r)[i] = v;
+    }
+    __syncthreads();
+
+    // ---- sum T^2 (wave 3) and the column sums W[k][x] = sum_{r<th} R[k+r][x]^2 (one thread per column)
+    if (wave == SSD_THREADS / 64 - 1) {
+        int tt = 0;
+        if (lane < th) {
+            const uint32_t* trow = reinterpret_cast<const uint32_t*>(s_t + lane * SSD_T_STRIDE) + 4;
+#pragma unroll
+            for (int d = 0; d < 9; d++) tt = __builtin_amdgcn_sdot4((int)trow[d], (int)trow[d], tt, false);
+        }
+        tt = wave_sum_dpp_i(tt);
+        if (lane == 0) s_tt[0] = tt;
+    }
+    if (tid < rw) {
+        const int8_t* col = reinterpret_cast<const int8_t*>(s_r) + tid;
+        int sq = 0;
+        for (int r = 0; r < th; r++) {
+            const int v = col[r * SSD_R_STRIDE];
+            sq += __mul24(v, v);
+        }
+        s_w[tid] = sq;
+        for (int k = 1; k < mh; k++) {
+            const int vn = col[(k + th - 1) * SSD_R_STRIDE], vo = col[(k - 1) * SSD_R_STRIDE];
+            sq += __mul24(vn, vn) - __mul24(vo, vo);
+            s_w[k * SSD_W_STRIDE + tid] = sq;
+        }
+    }
+
+    // ---- cross term on the matrix cores: wave -> (row block, column block) of the match map
+    const int n_jb = (mw + 15) >> 4, n_mb = (mh + 15) >> 4;
+    const int fm = lane & 15, fh = lane >> 4;        // fragment row / column and 16-byte k slice
+    constexpr int SSD_SLOTS = (10 + SSD_THREADS / 64 - 1) / (SSD_THREADS / 64);   // <= 2 x 5 blocks over the waves
+    ssd_v4i acc[SSD_SLOTS];
+    int task_of[SSD_SLOTS];
+#pragma unroll
+    for (int t = 0; t < SSD_SLOTS; t++) { acc[t] = ssd_v4i{0, 0, 0, 0}; task_of[t] = -1; }
+    {
+        int slot = 0;
+        for (int task = wave; task < n_jb * n_mb && slot < SSD_SLOTS; task += SSD_THREADS / 64, slot++) {
+            task_of[slot] = task;
+            const int mb = task >= n_jb ? 1 : 0, jb = task - mb * n_jb;      // (at most two row blocks: the map has <= 17 rows)
+            // B: bytes [16 + 16 fh - fm, +16) of the padded template row
+            const int o = 16 + 16 * fh - fm;
+            const uint32_t* tb = reinterpret_cast<const uint32_t*>(s_t) + (o >> 2);
+            const unsigned sh = (unsigned)(o & 3);
+            const uint8_t* ab = s_r + (16 * jb + 16 * fh);
+            const int arow = 16 * mb + fm;
+            ssd_v4i c = {0, 0, 0, 0};
+            for (int r = 0; r < th; r++) {
+                const uint32_t* t = tb + r * (SSD_T_STRIDE / 4);
+                const uint32_t t0 = t[0], t1 = t[1], t2 = t[2], t3 = t[3], t4 = t[4];
+                ssd_v4i bf;
+                bf.x = (int)__builtin_amdgcn_alignbyte(t1, t0, sh);
+                bf.y = (int)__builtin_amdgcn_alignbyte(t2, t1, sh);
+                bf.z = (int)__builtin_amdgcn_alignbyte(t3, t2, sh);
+                bf.w = (int)__builtin_amdgcn_alignbyte(t4, t3, sh);
+                const ssd_v4i af = *reinterpret_cast<const ssd_v4i*>(ab + min(arow + r, SSD_R_ROWS - 1) * SSD_R_STRIDE);
+                c = __builtin_amdgcn_mfma_i32_16x16x64_i8(af, bf, c, 0, 0, 0);
+            }
+            acc[slot] = c;
+        }
+    }
+    __syncthreads();
+
+    // ---- window sums of R^2: rows of W, 8 sliding segments per map row -> s_m. The match map takes
+    // the place of the search region, which nobody reads after the barrier above
+    static_assert(sizeof(int) * SSD_MAX_MATCH <= SSD_R_ROWS * SSD_R_STRIDE, "match map must fit the region tile");
+    static_assert(SSD_MAX_MH <= 32, "two row blocks of 16 at most");
+    int* const s_m = reinterpret_cast<int*>(s_r);
+    {
+        const int seg_len = (mw + 7) >> 3;
+        for (int item = tid; item < mh * 8; item += SSD_THREADS) {
+            const int k = item >> 3, j0 = (item & 7) * seg_len, j1 = min(mw, j0 + seg_len);
+            if (j0 < j1) {
+                const int* wrow = &s_w[k * SSD_W_STRIDE];
+                int sq = 0;
+                for (int c = 0; c < tw; c++) sq += wrow[j0 + c];
+                s_m[k * mw + j0] = sq;
+                for (int j = j0 + 1; j < j1; j++) {
+                    sq += wrow[j + tw - 1] - wrow[j - 1];
+                    s_m[k * mw + j] = sq;
+                }
+            }
+        }
+    }
+    __syncthreads();
+    {
+        const int stt = s_tt[0];
+#pragma unroll
+        for (int slot = 0; slot < SSD_SLOTS; slot++) {
+            const int task = task_of[slot];
+            if (task < 0) continue;
+            const int mb = task >= n_jb ? 1 : 0, jb = task - mb * n_jb;      // (at most two row blocks: the map has <= 17 rows)
+            const int j = 16 * jb + fm;                     // C/D: col = lane & 15, row = 4 (lane >> 4) + reg
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                const int k = 16 * mb + 4 * fh + i;
+                if (k < mh && j < mw) s_m[k * mw + j] += stt - 2 * acc[slot][i];
+            }
+        }
+    }
+    __syncthreads();
+
+    const int nm = mw * mh;
+    unsigned long long best = ~0ull;
+    for (int o = tid; o < nm; o += SSD_THREADS) {
+        const unsigned long long key = ((unsigned long long)__float_as_uint((float)s_m[o]) << 32) | (unsigned)o;
+        best = key < best ? key : best;
+    }
+    // first minimum of the FLOAT map in row-major order == smallest (float bits, index) key: an SSD is not
+    // negative, and non-negative floats order like their bit patterns. Above 2^24 different integers round to
+    // one float, and cv::minMaxLoc sees the floats: the earlier position wins, not the smaller integer.
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        const unsigned long long other = __shfl_xor(best, o, 64);
+        best = other < best ? other : best;
+    }
+    if ((tid & 63) == 0) s_key[tid >> 6] = best;
+    __syncthreads();
+    best = s_key[0];
+    for (int w = 1; w < SSD_THREADS / 64; w++) best = s_key[w] < best ? s_key[w] : best;
+    const int min_o = (int)(best & 0xffffffffu);
+    const int minx = min_o % mw, miny = min_o / mw;
+    const float minVal = __uint_as_float((unsigned)(best >> 32));
+
+    int sumj = 0, cnt = 0;
+    // o / mw without an integer division: exact for o * mw < 2^20 (the map has at most 65 x 17 entries)
+    const unsigned magic = ((1u << 20) + (unsigned)mw - 1u) / (unsigned)mw;
+    for (int o = tid; o < nm; o += SSD_THREADS) {
+        const int k = (int)(((unsigned)o * magic) >> 20), j = o - k * mw;
+        if (j >= minx && k >= miny && (double)(float)s_m[o] <= (double)minVal) { sumj += j; cnt++; }
+    }
+    sumj = wave_sum_dpp_i(sumj);
+    cnt = wave_sum_dpp_i(cnt);
+    if ((tid & 63) == 0) { s_sum[tid >> 6] = sumj; s_cnt[tid >> 6] = cnt; }
+    __syncthreads();
+    if (tid == 0) {
+        int ts = 0, tc = 0;
+        for (int w = 0; w < SSD_THREADS / 64; w++) { ts += s_sum[w]; tc += s_cnt[w]; }
+        float minPos = (float)ts;      // sum of small ints: exact in float in any order
+        minPos = minPos / tc;
+        G(a.disparity)[kp] = a.clamp_half ? fmaxf(0.5f, minPos) : minPos;
+    }
+}
+
+void svo::launch_ssd_ref(const SsdArgs* d_args, int batch, int max_n, int win, int search_y, hipStream_t stream) {
+    if (max_n <= 0) return;
+    if (ssd_pick_max_win(win, search_y) == 31)
+        hipLaunchKernelGGL((ssd_disparity_ref_kernel<31, 13>), dim3(max_n, batch), dim3(SSD_REF_THREADS), 0, stream, d_args);
+    else
+        hipLaunchKernelGGL((ssd_disparity_ref_kernel<SSD_WIN_ALL, SSD_MH_ALL>), dim3(max_n, batch), dim3(SSD_REF_THREADS), 0, stream, d_args);
+}
+
+// Both kernels on the same batch of svo_ssd_sequence, through launch_ssd's form (grid (n_bound, batch), the shape
+// that win and search_y choose). Neither writes the sequences' own disparity arrays (they may be NULL): each kernel
+// gets [batch][stride] floats of its own, every word set to `fill` first, sequence b's entries at b * stride, so an
+// entry that only one kernel writes differs too, and an entry nobody wrote still holds `fill`. stride >= every cap.
+// n_diff: the number of differing 32-bit words, first_diff: the index of the first (-1: none); disp_out / ref_out: null,
+// or device memory of [batch][stride] floats that receives the kernel's / the reference kernel's array.
+extern "C" int svo_ssd_disparity_check(svo_handle* h, int batch, const svo_ssd_sequence* seqs, int n_bound, int win,
+                                       int search_y, int stride, uint32_t fill, float* disp_out, float* ref_out,
+                                       int64_t* n_diff, int64_t* first_diff) {
+    CHECK_H(h);
+    if (!n_diff || !first_diff || stride < 1)
+        return svo_set_error(SVO_ERR_INVALID, "svo_ssd_disparity_check: need n_diff, first_diff and stride >= 1");
+    std::vector<SsdArgs> blocks;
+    int rc = ssd_fill_blocks("svo_ssd_disparity_check", h, batch, seqs, n_bound, win, search_y, false, blocks);
+    if (rc) return rc;
+    for (int b = 0; b < batch; b++)
+        if (seqs[b].cap > stride)
+            return svo_set_error(SVO_ERR_INVALID, "svo_ssd_disparity_check: sequence %d: cap %d exceeds stride %d", b, seqs[b].cap, stride);
+    const size_t words = (size_t)batch * (size_t)stride;
+    DevPtr<float> ws;
+    DevPtr<unsigned long long> res;
+    HIP_TRY(dev_malloc(ws, sizeof(float) * 2 * words));
+    HIP_TRY(dev_malloc(res, 2 * sizeof(unsigned long long)));
+    HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(ws.get()), (int)fill, 2 * words, h->stream));
+    const unsigned long long init[2] = {0ull, ~0ull};
+    HIP_TRY(hipMemcpyAsync(res.get(), init, sizeof(init), hipMemcpyHostToDevice, h->stream));
+    blocks.resize((size_t)2 * batch);                        // [0, batch): the kernel's, [batch, 2 batch): the reference's
+    for (int b = 0; b < batch; b++) {
+        blocks[(size_t)b].disparity = ws.get() + (size_t)b * stride;
+        blocks[(size_t)(batch + b)] = blocks[(size_t)b];
+        blocks[(size_t)(batch + b)].disparity = ws.get() + words + (size_t)b * stride;
+    }
+    SsdArgs* d;
+    rc = stage(h, blocks, &d);
+    if (rc) return rc;
+    launch_ssd(d, batch, n_bound, win, search_y, h->stream);
+    HIP_TRY(hipGetLastError());
+    launch_ssd_ref(d + batch, batch, n_bound, win, search_y, h->stream);
+    HIP_TRY(hipGetLastError());
+    words_diff_kernel<<<(unsigned)std::min<size_t>((words + 255) / 256, 1024), 256, 0, h->stream>>>(
+        reinterpret_cast<const uint32_t*>(ws.get()), reinterpret_cast<const uint32_t*>(ws.get() + words), words, res.get());
+    HIP_TRY(hipGetLastError());
+    if (disp_out) HIP_TRY(hipMemcpyAsync(disp_out, ws.get(), sizeof(float) * words, hipMemcpyDeviceToDevice, h->stream));
+    if (ref_out) HIP_TRY(hipMemcpyAsync(ref_out, ws.get() + words, sizeof(float) * words, hipMemcpyDeviceToDevice, h->stream));
+    unsigned long long got[2];
+    HIP_TRY(hipMemcpyAsync(got, res.get(), sizeof(got), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    *n_diff = (int64_t)got[0];
+    *first_diff = got[0] ? (int64_t)got[1] : -1;
+    return SVO_OK;            // (the workspaces are freed here: the launches are complete)
 }
 
 // svo_filter_update_table_batch: launch_filter in the form the tracker makes it (FilterArgs::kfs set: references

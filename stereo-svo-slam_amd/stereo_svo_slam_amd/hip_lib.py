@@ -61,7 +61,7 @@ SYMBOLS = (
     "svo_keyframe_launch_info", "svo_compact_batch", "svo_keyframe_merge_batch", "svo_keyframe_init_batch",
     "svo_keyframe_record_layout", "svo_ssd_disparity_batch",
     "svo_sparse_align_batch_mats", "svo_pose_mats_layout", "svo_filter_update_table_batch",
-    "svo_sia_records_check",
+    "svo_sia_records_check", "svo_ssd_disparity_check",
 )
 
 # svo_ctx_set_input_format / svo_convert_frames: how the buffers of a sequence become its two gray images
@@ -1698,6 +1698,22 @@ class Handle:
         _check(lib().svo_ssd_disparity_batch(self._h, len(seqs), arr, int(n_bound), int(win), int(search_y),
                                              C.byref(max_win)))
         return max_win.value
+
+    def ssd_disparity_check(self, seqs, n_bound, win, search_y, stride, fill=0):
+        """Diagnostic: svo_ssd_disparity_check, the one-wave SSD kernel against the four-wave kernel it replaced on
+        the sequences of ssd_disparity_batch (their `disparity` is not written and may be missing). Returns (number
+        of differing 32-bit words, index of the first or -1, the kernel's array [batch, stride] float32 whose
+        unwritten words hold `fill`, the replaced kernel's array)."""
+        arr = (SsdSequence * len(seqs))()
+        for a, s in zip(arr, seqs):
+            _fill(a, s, skip=("left", "right"))
+            a.left, a.right = _img(s["left"]), _img(s["right"])
+        out = torch.empty((len(seqs), int(stride)), dtype=torch.float32, device=self.device)
+        ref = torch.empty_like(out)
+        n_diff, first = C.c_int64(0), C.c_int64(0)
+        _check(lib().svo_ssd_disparity_check(self._h, len(seqs), arr, int(n_bound), int(win), int(search_y), int(stride),
+                                             C.c_uint32(fill), _ptr(out), _ptr(ref), C.byref(n_diff), C.byref(first)))
+        return n_diff.value, first.value, out, ref
 
 
 def detect_to_numpy(cells, counts):

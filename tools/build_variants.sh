@@ -7,6 +7,8 @@
 #   -DSVO_SIA_ACC_U=4 adds four keypoints per trip (over 256 registers), -DSVO_SIA_OCC=n caps the registers,
 #   -DSVO_SIA_PRELOAD=0 loads MODE 2's operands where they are used, one behind the other (the kernels of round 6, instruction
 #   for instruction), -DSVO_SIA_QREG=0 hands the projections from cost() to get_gradient through kp_ws.
+# ssd_disparity_kernel (depth.hip): build_variants.sh ssd4 -DSVO_SSD_FOUR_WAVES launches the four-wave kernel that the one-wave
+#   kernel replaced (kept in svo_capi_check.hip) on the product path: the parent's SSD shape without a parent checkout.
 # Run it in a checkout of the commit to compare against for that commit's library; never while a source is being edited.
 set -e
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
