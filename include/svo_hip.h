@@ -1445,6 +1445,103 @@ int svo_render_scene_clouds(svo_handle *h, int n, const svo_scene_src *src, cons
                             const int32_t *n_spans, const svo_scene_camera *cameras, const int64_t *offset,
                             const svo_scene_style *style, int32_t point_size, uint8_t *pixels);
 
+/* ---- ar occlusion: meshes of the AR picture hidden behind the scene's dense stereo depth ------------
+ * "ar" draws its meshes over the camera image as if the room were empty: a box placed behind a table leg is painted
+ * over the leg. The checked cloud of the very frame the picture shows ("clouds", "cross-check"; frame =
+ * SVO_CLOUD_CAMERA) is a depth of the left rectified plane in the camera frame of the picture's depth c_2, so one
+ * comparison per pixel decides whether the scene is in front of the mesh.
+ *
+ * An OCCLUDER of an image is a lattice of svo_map_point records in the SVO_CLOUD_ORGANIZED layout: cols, rows, step,
+ * the record of lattice point (ix, iy) at iy * cols + ix. Only z and flags of a record are read.
+ *   occluder of a pixel   pixel (px, py) of the picture belongs to cell ix = px / step, iy = py / step (integer
+ *              division). The pixel HAS AN OCCLUDER DEPTH zo = record.z iff ix < cols and iy < rows, the record's
+ *              flags carry neither SVO_CLOUD_DROPPED nor any bit of drop_flags, and zo is finite and > 0. Otherwise
+ *              nothing occludes the pixel: so also in the columns and rows beyond cols * step, rows * step when step
+ *              does not divide the size, and everywhere in an image without an occluder (records == NULL).
+ *   pixel      the rule of "ar" extended, not changed: the keys, the coverage and the smallest-key winner are those of
+ *              "ar". Let z be the winner's depth, the float whose bits are key >> 32. The winner is HIDDEN iff the
+ *              pixel has an occluder depth and z > zo + margin: one float32 add rounded once, one float32 comparison
+ *              (zo + margin = +inf hides nothing). A pixel without a winner shows the background as before. Testing
+ *              only the winner is the same as testing every fragment: every other covering triangle of the pixel has
+ *              z' >= z (the key orders by depth first), so it is hidden whenever the winner is, and when the winner is
+ *              visible it wins whatever becomes of the others.
+ *   hidden     SVO_AR_HIDDEN_DROP: a hidden pixel shows the background (g, g, g).
+ *              SVO_AR_HIDDEN_DIM:  every channel becomes (c' * (256 - a) + g * a + 128) >> 8 in integers, with a =
+ *              alpha (0 .. 256), c' the winner's shaded channel and g the background gray: a = 0 shows the mesh
+ *              unchanged, a = 256 the background.
+ *   visibility per image, exact integers: covered = the pixels that have a winner, hidden = those of them whose winner
+ *              is hidden. They are summed on the device with 64-bit integer atomic adds, one pair per workgroup after a
+ *              reduction inside it, so the order of arrival cannot matter.
+ *
+ * The job. svo_submit_export_ar_occluded is svo_submit_export_ar with a svo_ar_occlusion. No new job kind: queue
+ * order, segments, the SVO_AR_NONE rule (such a slot writes only its segment; its info is status = SVO_CLOUD_NONE and
+ * zeros), the copy-out and "the slot is not changed" are the AR job's. occlusion == NULL or on == 0 IS
+ * svo_submit_export_ar: the same launches, bytes and memory (of a non-NULL occlusion the scalar fields are checked
+ * whatever its on; cloud, check and info are read with on == 1 only). With on == 1 named slot i's occluder is exactly the records that svo_submit_export_cloud_checked(
+ * SVO_EXPORT_FRAMES, ..., `cloud` with frame = SVO_CLOUD_CAMERA and layout = SVO_CLOUD_ORGANIZED, check, ...) delivers
+ * for that slot at the same queue position: the same planes, rig and launches, bit for bit, with cols = W / step,
+ * rows = H / step. They go into a staging block of the group and never leave the device. The frame is always the
+ * current frame: that is the image the picture shows. info[i] of named slot i: status = SVO_CLOUD_OK and
+ * occluder_points = the cloud's kept count where a picture was drawn, covered and hidden as above.
+ * Rejected with SVO_ERR_INVALID and nothing queued: everything svo_submit_export_ar rejects; of a non-NULL occlusion
+ * on or hidden outside their values, alpha outside 0 .. 256, a margin that is negative or not finite, a non-zero
+ * _reserved; with on == 1 everything svo_submit_export_cloud_checked rejects of `cloud` and `check`, cloud.frame !=
+ * SVO_CLOUD_CAMERA, cloud.layout != 0; in the stage entry also an occluder with step outside 1 .. 16, with cols or rows <= 0, with a pointer that
+ * is not 16-byte aligned or with a non-zero _reserved.
+ * Memory, per group: the live layer has a block of its own, 16 * points_per_slot per slot of a chunk, made by the
+ * group's first occluded job, replaced when outgrown and counted in svo_memory.device_bytes. It sits beside what the
+ * cloud job itself stages in device mode in its own blocks (slot_bytes of "clouds" and, checked, reverse_bytes of
+ * "cross-check"). chunk = max(1, 256 MiB / (slot_bytes + 16 * points_per_slot + reverse_bytes)); the diagnostic
+ * SVO_AR_CHUNK_SLOTS lowers it. The input block of the AR job also carries one occluder entry (32 bytes) and one pair
+ * of counters (16 bytes) per delivered slot. Per chunk the order on the group's stream is: search, check, cloud write,
+ * set-up, tile render. The counters of all slots come back in the job's one copy, after the last chunk. An unoccluded
+ * job allocates what it did; a ctx that never asks allocates, launches and copies nothing more. */
+enum { SVO_AR_HIDDEN_DROP = 0, SVO_AR_HIDDEN_DIM = 1 };
+
+typedef struct svo_ar_visibility {    /* 32 bytes, host, one per named slot / image                          */
+    int32_t status;                   /* SVO_CLOUD_OK: the image had an occluder; SVO_CLOUD_NONE             */
+    int32_t occluder_points;          /* the job: the cloud's kept count; the stage entry: 0                 */
+    int64_t covered;                  /* pixels that have a winner                                           */
+    int64_t hidden;                   /* those whose winner is hidden                                        */
+    int64_t _pad;
+} svo_ar_visibility;
+
+typedef struct svo_ar_occlusion {     /* 128 bytes; copied at submit                                         */
+    int32_t on;                       /* 0: the job IS svo_submit_export_ar; 1: occluded                     */
+    int32_t hidden;                   /* SVO_AR_HIDDEN_DROP / SVO_AR_HIDDEN_DIM                              */
+    int32_t alpha;                    /* 0 .. 256 (read by DIM only; checked always)                         */
+    float   margin;                   /* finite, >= 0, in the unit of the depths                             */
+    uint32_t drop_flags;              /* records with any of these flag bits occlude nothing                 */
+    int32_t _reserved[3];             /* 0                                                                   */
+    svo_cloud_style  cloud;           /* frame SVO_CLOUD_CAMERA, layout 0; step, window, search, the filters */
+    svo_stereo_check check;           /* as in svo_submit_export_cloud_checked                               */
+    svo_ar_visibility *info;          /* NULL, or host, one per named slot; valid until svo_wait             */
+    int64_t _reserved2;               /* 0                                                                   */
+} svo_ar_occlusion;
+
+typedef struct svo_ar_occluder {      /* 24 bytes; one image of the stage entry                              */
+    const svo_map_point *records;     /* device, 16-byte aligned, cols * rows records; NULL: no occluder     */
+    int32_t cols, rows, step;         /* > 0, > 0, 1 .. 16 (not read with records == NULL)                   */
+    int32_t _reserved;                /* 0                                                                   */
+} svo_ar_occluder;
+
+int svo_submit_export_ar_occluded(svo_ctx *ctx, const int *seqs, int n, const svo_ar_style *style,
+                                  const svo_ar_occlusion *occlusion, const svo_ar_mesh *meshes, int n_meshes,
+                                  const svo_ar_instance *instances, const int *first, int n_instances,
+                                  const svo_ar_dst *dst, int mem);
+int svo_export_ar_occluded(svo_ctx *ctx, const int *seqs, int n, const svo_ar_style *style,
+                           const svo_ar_occlusion *occlusion, const svo_ar_mesh *meshes, int n_meshes,
+                           const svo_ar_instance *instances, const int *first, int n_instances,
+                           const svo_ar_dst *dst, int mem);   /* submit + wait */
+/* stage entry: svo_render_ar plus one svo_ar_occluder per image (host array) and a host array of n visibilities, or
+ * NULL. Only on, hidden, alpha, margin, drop_flags and the reserved words of the occlusion are read. With occlusion ==
+ * NULL or on == 0 it is svo_render_ar: the same launches and bytes (occluders is not read; a visibility gets status =
+ * SVO_CLOUD_NONE and zeros). The occluder table and the counters live in the handle's workspace, behind the tables of
+ * svo_render_ar. Complete on return. */
+int svo_render_ar_occluded(svo_handle *h, int n, const svo_ar_src *src, const svo_ar_camera *cameras,
+                           const int64_t *offset, const svo_ar_style *style, const svo_ar_occlusion *occlusion,
+                           const svo_ar_occluder *occluders, uint8_t *pixels, svo_ar_visibility *visibility);
+
 /* ---- voxel maps: svo_map_point records fused into a sparse voxel grid ------------
  * "clouds" gives one cloud per frame or keyframe. A voxel map is what they add up to: a hash table in device memory,
  * bounded in size, that holds every surface once and averages the records that fell into the same voxel. It takes

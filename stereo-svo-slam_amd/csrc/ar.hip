@@ -33,6 +33,32 @@
 // pixel address follows from those integers. Of an image exactly the bytes [dst + y * w * bpp, + w * bpp) of rows
 // 0 .. h-1 are written and the bytes [src + y * stride, + w) read; of a draw triangles [0, n_triangles), its rgb
 // likewise, and vertices [0, n_vertices); of the records [0, n_records).
+//
+// Occlusion (include/svo_hip.h, "ar occlusion"): ar_render_kernel<true> is the same kernel with an occluder per image,
+// an organized lattice of svo_map_point records. ar_render_kernel<false> is the kernel above, argument for argument.
+//  - before the record walk every lane asks for the records of up to four cells of its tile, 16 bytes each (one
+//    global_load_dwordx4), consecutive lanes consecutive cells of a lattice row, so that they are in flight during the
+//    walk; after it the lane reduces each to one float (z, or +inf where nothing occludes) in an LDS plane of at most
+//    1024 floats; one barrier;
+//  - in 4. a lane looks up the cell of each of its four pixels (one division for the first, then carried), compares
+//    the winner's depth with zo + margin, and drops or dims; the lanes' covered / hidden counts (0 .. 4) are summed per
+//    wavefront with three ballots and popcounts each, per workgroup with one LDS atomic add per wavefront, and the
+//    workgroup adds its pair to the image's two 64-bit counters with integer atomics: no order can change the sums.
+// Bounds of the occluded part: with the tile [bx0, bx1] x [by0, by1] inside the image and step >= 1, the tile's cells
+// are cx0 = bx0 / step .. min(bx1 / step, cols - 1) and likewise in y: ncx x ncy of them, both <= 0 made 0 (the tile
+// lies beyond the lattice; no record is read). bx1 - bx0 <= 63 and by1 - by0 <= 15 give ncx <= 63 / step + 2 and
+// ncy <= 15 / step + 2, and since tiles start at multiples of 64 and 16, ncx * ncy <= 1024 = AR_OCC_CELLS, reached at
+// step 1 (n_cells is clipped to it all the same, and a lookup beyond n_cells occludes nothing). A record address is
+// (cy0 + q) * cols + cx0 + r with q < ncy, r < ncx, so row <= rows - 1 and column <= cols - 1: inside the cols x rows
+// records the host checked. A pixel x >= bx0, y >= by0 has ix = x / step - cx0 >= 0, iy >= 0, and is looked up only
+// when ix < ncx and iy < ncy. The counters are words 0 and 1 of the image's ArOccluder::counts.
+// LDS banks of the plane (ds_read_b32: bank = word % 32, conflicts within a 32-lane half, which holds two tile rows
+// of 16 lanes): lane l of a row reads word (4 l + i) / step of its cell row. step >= 4: the four pixels of a lane share
+// a cell and 16 lanes read 16 / (step / 4) consecutive or equal words: no conflict, equal addresses broadcast; the
+// second row of the half reads the same words (same cell row) or words ncx further on. step 2: words 2 l + i / 2, 32
+// distinct words a row: no conflict within a row, two-way against the other row when it is another cell row. step 1:
+// words 4 l + i, stride 4: two-way within a row, four-way with the other row (+64 words). step 3: stride 4 / 3, at
+// most two-way. These are four reads per lane per tile; they were not measured apart from the kernel's time.
 #include <cmath>
 
 #include "svo_host.hpp"
@@ -43,6 +69,8 @@ namespace svo {
 static_assert(AR_TILE_W == 64 && AR_TILE_H * 16 == AR_THREADS, "4 pixels of a 64-pixel row per lane");
 static_assert(sizeof(ArRecord) == 64 && sizeof(svo_ar_camera) == 64 && sizeof(svo_ar_segment) == 64 && sizeof(svo_ar_instance) == 64 &&
               sizeof(svo_ar_draw) == 88 && sizeof(svo_ar_style) == 32 && sizeof(svo_ar_mesh) == 40, "record sizes of the C ABI");
+static_assert(sizeof(svo_ar_visibility) == 32 && sizeof(svo_ar_occlusion) == 128 && sizeof(svo_ar_occluder) == 24 && sizeof(ArOccluder) == 32 &&
+              sizeof(svo_map_point) == 16, "record sizes of ar occlusion");
 #ifndef SVO_AR_SMALL_PIXELS
 #define SVO_AR_SMALL_PIXELS 64                             // (-DSVO_AR_SMALL_PIXELS=n: the variants tools/ar_bench.py compared)
 #endif
@@ -67,6 +95,19 @@ int ar_check_camera(const svo_ar_camera* c, const char* who, int i) {
         return svo_set_error(SVO_ERR_INVALID, "%s: camera %d: an entry is not finite, or fx or fy is not > 0", who, i);
     return SVO_OK;
 }
+
+int ar_check_occlusion(const svo_ar_occlusion* o, const char* who) {
+    if (!o) return SVO_OK;
+    if (o->on != 0 && o->on != 1) return svo_set_error(SVO_ERR_INVALID, "%s: occlusion: on %d is neither 0 nor 1", who, o->on);
+    if (o->hidden != SVO_AR_HIDDEN_DROP && o->hidden != SVO_AR_HIDDEN_DIM) return svo_set_error(SVO_ERR_INVALID, "%s: occlusion: hidden %d", who, o->hidden);
+    if (o->alpha < 0 || o->alpha > 256) return svo_set_error(SVO_ERR_INVALID, "%s: occlusion: alpha %d is not within 0 .. 256", who, o->alpha);
+    if (!(o->margin >= 0) || !std::isfinite(o->margin)) return svo_set_error(SVO_ERR_INVALID, "%s: occlusion: margin is negative or not finite", who);
+    if (o->_reserved[0] != 0 || o->_reserved[1] != 0 || o->_reserved[2] != 0 || o->_reserved2 != 0)
+        return svo_set_error(SVO_ERR_INVALID, "%s: occlusion: a _reserved is not 0", who);
+    return SVO_OK;
+}
+
+ArOcclusion ar_occlusion(const svo_ar_occlusion& o) { return ArOcclusion{o.hidden, o.alpha, o.margin, o.drop_flags}; }
 
 ArParams ar_params(const svo_ar_style& s) {
     return ArParams{s.pixel == SVO_PIXEL_RGB8 ? 3 : 4, {s.light[0], s.light[1], s.light[2]}, s.ambient, s.near};
@@ -188,7 +229,41 @@ __device__ __forceinline__ unsigned long long ar_key(const ArTri& t, long long e
     return (unsigned long long)__float_as_uint(z) << 32 | t.rgb;
 }
 
-__global__ __launch_bounds__(AR_THREADS) void ar_render_kernel(const ArTile* __restrict__ tiles, const ArImage* __restrict__ images, const ArParams p) {
+// What the occluded kernel gets beyond the three arguments of ar_render_kernel<false>
+struct ArOcclArgs {
+    const ArOccluder* occluders;
+    ArOcclusion o;
+};
+constexpr int AR_OCC_CELLS = AR_TILE_W * AR_TILE_H;        // cells a tile can touch: most at step 1 (see the header comment)
+
+// the staged occluder plane and the workgroup's two counters: LDS of ar_render_kernel<true> only
+__device__ __forceinline__ float* ar_occ_plane() {
+    __shared__ float occ[AR_OCC_CELLS];
+    return occ;
+}
+__device__ __forceinline__ unsigned int* ar_occ_counts() {
+    __shared__ unsigned int vis[2];
+    return vis;
+}
+
+// a record as one float: its z where it occludes, +inf where nothing does (dropped, a drop_flags bit, z not finite or <= 0)
+__device__ __forceinline__ float ar_occluder_depth(const uint4 r, uint32_t drop_flags) {
+    const float z = __uint_as_float(r.z);
+    const uint32_t flags = r.w >> 24;
+    return ((flags & ((uint32_t)SVO_CLOUD_DROPPED | drop_flags)) == 0 && z > 0.f && ar_finite(z)) ? z : INFINITY;
+}
+
+// the lanes' counts (0 .. 4 each) summed over the wavefront: one ballot and popcount per bit
+__device__ __forceinline__ unsigned int ar_wave_sum(int v) {
+    return (unsigned int)(__popcll(__ballot(v & 1)) + 2 * __popcll(__ballot(v & 2)) + 4 * __popcll(__ballot(v & 4)));
+}
+
+// OCCLUDE = false: the kernel of "ar", three arguments. OCCLUDE = true: "ar occlusion", one ArOcclArgs more.
+template <bool OCCLUDE, typename... Occl>
+__global__ __launch_bounds__(AR_THREADS) void ar_render_kernel(const ArTile* __restrict__ tiles, const ArImage* __restrict__ images, const ArParams p,
+                                                              const Occl... occl) {
+    static_assert(sizeof...(Occl) == (OCCLUDE ? 1 : 0), "the occluded kernel takes one ArOcclArgs");
+    const ArOcclArgs oa{occl...};                           // (OCCLUDE = false: all zero and never read)
     __shared__ unsigned long long keys[AR_TILE_W * AR_TILE_H];
     __shared__ int queue[AR_THREADS];
     __shared__ int n_queue;
@@ -202,6 +277,32 @@ __global__ __launch_bounds__(AR_THREADS) void ar_render_kernel(const ArTile* __r
     // 1. the key plane
     for (int i = tid; i < AR_TILE_W * AR_TILE_H; i += AR_THREADS) keys[i] = ~0ull;
     if (tid == 0) n_queue = 0;
+    // (occluded) the tile's cells [cx0, cx0 + ncx) x [cy0, cy0 + ncy) of the lattice, clipped to it; their records
+    // are asked for here, 16 bytes a lane and consecutive lanes consecutive cells of a lattice row, and first used
+    // after the record walk
+    int cx0 = 0, cy0 = 0, ncx = 0, ncy = 0, n_cells = 0, step = 1;
+    uint4 staged[AR_OCC_CELLS / AR_THREADS];
+    if constexpr (OCCLUDE) {
+        const ArOccluder oc = G(oa.occluders)[t.image];
+        if (tid == 0) { ar_occ_counts()[0] = 0; ar_occ_counts()[1] = 0; }
+        if (oc.records) {
+            step = oc.step;
+            cx0 = bx0 / step; cy0 = by0 / step;
+            ncx = min(bx1 / step, oc.cols - 1) - cx0 + 1; ncy = min(by1 / step, oc.rows - 1) - cy0 + 1;
+            if (ncx <= 0 || ncy <= 0) ncx = ncy = 0;             // the tile lies beyond the lattice
+            n_cells = min(ncx * ncy, AR_OCC_CELLS);
+        }
+        SVO_GP(const uint4) cells = (SVO_GP(const uint4))G(oc.records);
+        // cell c = tid + j * AR_THREADS is (c % ncx, c / ncx) of the tile's cells: one division, then carried
+        const int div = max(ncx, 1), dq = AR_THREADS / div, dr = AR_THREADS % div;
+        int cq = tid / div, cr = tid % div;
+#pragma unroll
+        for (int j = 0; j < AR_OCC_CELLS / AR_THREADS; j++) {
+            if (tid + j * AR_THREADS < n_cells) staged[j] = cells[(int64_t)(cy0 + cq) * oc.cols + (cx0 + cr)];
+            cq += dq; cr += dr;
+            if (cr >= div) { cr -= div; cq++; }
+        }
+    }
     __syncthreads();
 
     // 2. and 3. the records
@@ -258,40 +359,98 @@ __global__ __launch_bounds__(AR_THREADS) void ar_render_kernel(const ArTile* __r
     }
     // (every round ends with a barrier, so the keys are final here)
 
-    // 4. decode and store
+    // 4. decode and store; (occluded) the staged records become the plane of occluder depths first
+    if constexpr (OCCLUDE) {
+        float* occ = ar_occ_plane();
+#pragma unroll
+        for (int j = 0; j < AR_OCC_CELLS / AR_THREADS; j++) {
+            const int c = tid + j * AR_THREADS;
+            if (c < n_cells) occ[c] = ar_occluder_depth(staged[j], oa.o.drop_flags);
+        }
+        __syncthreads();
+    }
     const int px = ly < th ? max(0, min(4, tw - lx)) : 0;                            // pixels of this lane: 0 .. 4
-    if (px == 0) return;
-    const int x = t.x0 + lx, y = t.y0 + ly;
-    SVO_GP(const uint8_t) g = G(im.src) + (int64_t)y * im.src_stride + x;
-    uint32_t rgb[4];                                                                 // r | g << 8 | b << 16 | 255 << 24
-    for (int i = 0; i < 4; i++) {
-        const unsigned long long key = keys[ly * AR_TILE_W + lx + i];
-        if (key == ~0ull) {
-            const uint32_t v = i < px ? g[i] : 0;
-            rgb[i] = v | v << 8 | v << 16 | 0xff000000u;
+    if constexpr (!OCCLUDE)
+        if (px == 0) return;
+    int n_covered = 0, n_hidden = 0;                                                 // (occluded) of this lane's pixels
+    if (px > 0) {
+        const int x = t.x0 + lx, y = t.y0 + ly;
+        SVO_GP(const uint8_t) g = G(im.src) + (int64_t)y * im.src_stride + x;
+        uint32_t rgb[4];                                                             // r | g << 8 | b << 16 | 255 << 24
+        // (occluded) the cell of pixel x + i, relative to the tile's first: x / step once, then carried with x % step.
+        // x >= bx0 and y >= by0, so ix, iy >= 0
+        int ix = 0, xr = 0, iy = 0;
+        if constexpr (OCCLUDE) {
+            ix = x / step - cx0; xr = x % step; iy = y / step - cy0;
+        }
+        for (int i = 0; i < 4; i++) {
+            const unsigned long long key = keys[ly * AR_TILE_W + lx + i];
+            bool hide = false;
+            if constexpr (OCCLUDE) {
+                const int at = iy * ncx + ix;
+                const bool has_cell = ix < ncx && iy < ncy && at < n_cells;          // a cell outside the staged ones occludes nothing
+                if (++xr == step) { xr = 0; ix++; }
+                if (key != ~0ull && i < px) {
+                    const float zo = has_cell ? ar_occ_plane()[at] : INFINITY;
+                    hide = __uint_as_float((uint32_t)(key >> 32)) > zo + oa.o.margin;
+                    n_covered++;
+                    n_hidden += hide;
+                }
+            }
+            bool background = key == ~0ull;
+            if constexpr (OCCLUDE) {
+                background = background || (hide && oa.o.hidden == SVO_AR_HIDDEN_DROP);
+            }
+            if (background) {
+                const uint32_t v = i < px ? g[i] : 0;
+                rgb[i] = v | v << 8 | v << 16 | 0xff000000u;
+            } else {
+                uint32_t c = (uint32_t)key;
+                if constexpr (OCCLUDE) {
+                    if (hide) {                                                      // dim: (c' (256 - a) + g a + 128) >> 8 per channel
+                        const uint32_t a = (uint32_t)oa.o.alpha, ga = (uint32_t)g[i] * a + 128u;
+                        c = ((((c >> 16) & 0xffu) * (256u - a) + ga) >> 8) << 16 | ((((c >> 8) & 0xffu) * (256u - a) + ga) >> 8) << 8 |
+                            (((c & 0xffu) * (256u - a) + ga) >> 8);
+                    }
+                }
+                rgb[i] = ((c >> 16) & 0xffu) | (c & 0xff00u) | ((c & 0xffu) << 16) | 0xff000000u;
+            }
+        }
+        SVO_GP(uint8_t) d = G(im.dst) + ((int64_t)y * im.w + x) * p.bpp;
+        if (p.bpp == 4) {
+            if (px == 4 && ((uintptr_t)d & 15) == 0) {
+                *(SVO_GP(uint4))d = make_uint4(rgb[0], rgb[1], rgb[2], rgb[3]);
+            } else {
+                for (int i = 0; i < px; i++) ((SVO_GP(uint32_t))d)[i] = rgb[i];      // (an RGBA image is 4-byte aligned)
+            }
         } else {
-            const uint32_t c = (uint32_t)key;
-            rgb[i] = ((c >> 16) & 0xffu) | (c & 0xff00u) | ((c & 0xffu) << 16) | 0xff000000u;
+            if (px == 4 && ((uintptr_t)d & 3) == 0) {
+                const uint32_t a = rgb[0] & 0xffffffu, b = rgb[1] & 0xffffffu, c = rgb[2] & 0xffffffu, e = rgb[3] & 0xffffffu;
+                SVO_GP(uint32_t) d4 = (SVO_GP(uint32_t))d;
+                d4[0] = a | b << 24;
+                d4[1] = b >> 8 | c << 16;
+                d4[2] = c >> 16 | e << 8;
+            } else {
+                for (int i = 0; i < px; i++) {
+                    d[3 * i] = (uint8_t)rgb[i]; d[3 * i + 1] = (uint8_t)(rgb[i] >> 8); d[3 * i + 2] = (uint8_t)(rgb[i] >> 16);
+                }
+            }
         }
     }
-    SVO_GP(uint8_t) d = G(im.dst) + ((int64_t)y * im.w + x) * p.bpp;
-    if (p.bpp == 4) {
-        if (px == 4 && ((uintptr_t)d & 15) == 0) {
-            *(SVO_GP(uint4))d = make_uint4(rgb[0], rgb[1], rgb[2], rgb[3]);
-        } else {
-            for (int i = 0; i < px; i++) ((SVO_GP(uint32_t))d)[i] = rgb[i];          // (an RGBA image is 4-byte aligned)
+    // (occluded) the counts: per wavefront by ballot and popcount, per workgroup in LDS, then one pair of 64-bit
+    // integer adds to the image's counters. Every lane of the workgroup arrives here.
+    if constexpr (OCCLUDE) {
+        unsigned int* vis = ar_occ_counts();
+        const unsigned int wave_covered = ar_wave_sum(n_covered), wave_hidden = ar_wave_sum(n_hidden);
+        if ((tid & (warpSize - 1)) == 0) {
+            if (wave_covered) atomicAdd(&vis[0], wave_covered);
+            if (wave_hidden) atomicAdd(&vis[1], wave_hidden);
         }
-    } else {
-        if (px == 4 && ((uintptr_t)d & 3) == 0) {
-            const uint32_t a = rgb[0] & 0xffffffu, b = rgb[1] & 0xffffffu, c = rgb[2] & 0xffffffu, e = rgb[3] & 0xffffffu;
-            SVO_GP(uint32_t) d4 = (SVO_GP(uint32_t))d;
-            d4[0] = a | b << 24;
-            d4[1] = b >> 8 | c << 16;
-            d4[2] = c >> 16 | e << 8;
-        } else {
-            for (int i = 0; i < px; i++) {
-                d[3 * i] = (uint8_t)rgb[i]; d[3 * i + 1] = (uint8_t)(rgb[i] >> 8); d[3 * i + 2] = (uint8_t)(rgb[i] >> 16);
-            }
+        __syncthreads();
+        if (tid == 0) {
+            unsigned long long* counts = G(oa.occluders)[t.image].counts;
+            if (vis[0]) atomicAdd(&counts[0], (unsigned long long)vis[0]);
+            if (vis[1]) atomicAdd(&counts[1], (unsigned long long)vis[1]);
         }
     }
 }
@@ -303,7 +462,14 @@ void launch_ar_setup(const ArSetup* d_setup, int n_setup, const ArImage* d_image
 
 void launch_ar(const ArTile* d_tiles, int n_tiles, const ArImage* d_images, const ArParams& p, hipStream_t stream) {
     if (n_tiles <= 0) return;
-    hipLaunchKernelGGL(ar_render_kernel, dim3(n_tiles), dim3(AR_THREADS), 0, stream, d_tiles, d_images, p);
+    hipLaunchKernelGGL((ar_render_kernel<false>), dim3(n_tiles), dim3(AR_THREADS), 0, stream, d_tiles, d_images, p);
+}
+
+void launch_ar_occluded(const ArTile* d_tiles, int n_tiles, const ArImage* d_images, const ArOccluder* d_occluders, const ArParams& p,
+                        const ArOcclusion& o, hipStream_t stream) {
+    if (n_tiles <= 0) return;
+    hipLaunchKernelGGL((ar_render_kernel<true, ArOcclArgs>), dim3(n_tiles), dim3(AR_THREADS), 0, stream, d_tiles, d_images, p,
+                       ArOcclArgs{d_occluders, o});
 }
 
 }  // namespace svo

@@ -448,9 +448,14 @@ extern "C" int svo_render_scene_clouds(svo_handle* h, int n, const svo_scene_src
                         [&](const SceneTile* d, int m, hipStream_t s) { launch_scene_clouds(d, m, d_images, d_ptrs, params, s); });
 }
 
-extern "C" int svo_render_ar(svo_handle* h, int n, const svo_ar_src* src, const svo_ar_camera* cameras, const int64_t* offset,
-                             const svo_ar_style* style, uint8_t* pixels) {
+// svo_render_ar (occlusion == null) and svo_render_ar_occluded. `occluded` (occlusion->on == 1): the occluder table and
+// the images' counters follow the records in the workspace, the tile table comes last as before; the counters come
+// back in one copy after the last tile launch.
+static int render_ar(svo_handle* h, int n, const svo_ar_src* src, const svo_ar_camera* cameras, const int64_t* offset, const svo_ar_style* style,
+                     const svo_ar_occlusion* occlusion, const svo_ar_occluder* occluders, uint8_t* pixels, svo_ar_visibility* visibility) {
     CHECK_H(h);
+    const bool occluded = occlusion && occlusion->on == 1;
+    if (occluded && n > 0 && !occluders) return svo_set_error(SVO_ERR_INVALID, "svo_render_ar_occluded: no occluders");
     if (n < 0 || (n > 0 && (!src || !cameras || !offset))) return svo_set_error(SVO_ERR_INVALID, "svo_render_ar: bad arguments");
     if (const int rc = ar_check_style(style, "svo_render_ar")) return rc;
     if (!pixels || ((uintptr_t)pixels & 3)) return svo_set_error(SVO_ERR_INVALID, "svo_render_ar: pixels is NULL or not 4-byte aligned");
@@ -481,6 +486,11 @@ extern "C" int svo_render_ar(svo_handle* h, int n, const svo_ar_src* src, const 
         }
         if (tri > SVO_AR_MAX_TRIANGLES)
             return svo_set_error(SVO_ERR_CAPACITY, "svo_render_ar: image %d: %lld triangles, at most %d", i, (long long)tri, (int)SVO_AR_MAX_TRIANGLES);
+        if (occluded) {
+            const svo_ar_occluder& o = occluders[i];
+            if (o._reserved != 0 || (o.records && (o.step < 1 || o.step > 16 || o.cols <= 0 || o.rows <= 0 || ((uintptr_t)o.records & 15))))
+                return svo_set_error(SVO_ERR_INVALID, "svo_render_ar_occluded: image %d: an occluder of step 1 .. 16, cols and rows > 0, records 16-byte aligned, _reserved 0", i);
+        }
         draw0.push_back(draws.size());
         rec0.push_back(records);
         draws.insert(draws.end(), s.draws, s.draws + s.n_draws);
@@ -493,13 +503,19 @@ extern "C" int svo_render_ar(svo_handle* h, int n, const svo_ar_src* src, const 
         records += (size_t)a.n_records;
         images.push_back(a);
     }
+    for (int i = 0; visibility && i < n; i++) {
+        visibility[i] = svo_ar_visibility{};
+        visibility[i].status = occluded && occluders[i].records ? SVO_CLOUD_OK : SVO_CLOUD_NONE;
+    }
     if (tiles.empty()) return SVO_OK;
     // (SVO_AR_TABLE_TILES: a smaller table, so that tests reach the chunked launches)
     const size_t chunk = table_tiles("SVO_AR_TABLE_TILES", std::min<size_t>(tiles.size(), (size_t)INT_MAX));
     auto pad = [](size_t b) { return (b + 15) / 16 * 16; };
     const size_t draws_bytes = pad(sizeof(svo_ar_draw) * draws.size()), images_bytes = pad(sizeof(ArImage) * images.size());
     const size_t setup_bytes = pad(sizeof(ArSetup) * setup.size()), records_bytes = sizeof(ArRecord) * records;
-    const size_t bytes = draws_bytes + images_bytes + setup_bytes + records_bytes + sizeof(ArTile) * chunk;
+    const size_t occl_bytes = occluded ? sizeof(ArOccluder) * (size_t)n : 0, counts_bytes = occluded ? 16 * (size_t)n : 0;
+    const size_t tiles_at = draws_bytes + images_bytes + setup_bytes + records_bytes + occl_bytes + counts_bytes;
+    const size_t bytes = tiles_at + sizeof(ArTile) * chunk;
     if (const int rc = h->ar_ws.reserve(bytes, h->stream)) return rc;
     uint8_t* base = h->ar_ws.ptr.get();
     const svo_ar_draw* d_draws = reinterpret_cast<const svo_ar_draw*>(base);
@@ -507,6 +523,13 @@ extern "C" int svo_render_ar(svo_handle* h, int n, const svo_ar_src* src, const 
     const ArSetup* d_setup = reinterpret_cast<const ArSetup*>(base + draws_bytes + images_bytes);
     ArRecord* d_records = reinterpret_cast<ArRecord*>(base + draws_bytes + images_bytes + setup_bytes);
     for (size_t i = 0; i < images.size(); i++) { images[i].draws = d_draws + draw0[i]; images[i].records = d_records + rec0[i]; }
+    const ArOccluder* d_occluders = reinterpret_cast<const ArOccluder*>(base + draws_bytes + images_bytes + setup_bytes + records_bytes);
+    unsigned long long* d_counts = reinterpret_cast<unsigned long long*>(base + draws_bytes + images_bytes + setup_bytes + records_bytes + occl_bytes);
+    std::vector<ArOccluder> occl;
+    for (int i = 0; occluded && i < n; i++) {
+        const svo_ar_occluder& o = occluders[i];
+        occl.push_back(ArOccluder{o.records, d_counts + 2 * (size_t)i, o.records ? o.cols : 0, o.records ? o.rows : 0, o.records ? o.step : 1, 0});
+    }
     const ArParams params = ar_params(*style);
     int rc = SVO_OK;
     auto up = [&](const void* dst, const void* from, size_t b) {
@@ -516,6 +539,9 @@ extern "C" int svo_render_ar(svo_handle* h, int n, const svo_ar_src* src, const 
     up(d_draws, draws.data(), sizeof(svo_ar_draw) * draws.size());
     up(d_images, images.data(), sizeof(ArImage) * images.size());
     up(d_setup, setup.data(), sizeof(ArSetup) * setup.size());
+    up(d_occluders, occl.data(), sizeof(ArOccluder) * occl.size());
+    if (rc == SVO_OK && occluded && hipMemsetAsync(d_counts, 0, counts_bytes, h->stream) != hipSuccess)
+        rc = svo_set_error(SVO_ERR_HIP, "svo_render_ar_occluded: clearing the counters failed");
     if (rc == SVO_OK) {
         launch_ar_setup(d_setup, (int)setup.size(), d_images, params, h->stream);
         if (hipGetLastError() != hipSuccess) rc = svo_set_error(SVO_ERR_HIP, "svo_render_ar: the first launch failed");
@@ -524,9 +550,38 @@ extern "C" int svo_render_ar(svo_handle* h, int n, const svo_ar_src* src, const 
         (void)hipStreamSynchronize(h->stream);
         return rc;
     }
-    return launch_tiles(h, tiles, reinterpret_cast<ArTile*>(base + draws_bytes + images_bytes + setup_bytes + records_bytes), chunk,
-                        [&](const ArTile* d, int m, hipStream_t s) { launch_ar(d, m, d_images, params, s); });
+    if (!occluded)
+        return launch_tiles(h, tiles, reinterpret_cast<ArTile*>(base + tiles_at), chunk,
+                            [&](const ArTile* d, int m, hipStream_t s) { launch_ar(d, m, d_images, params, s); });
+    const ArOcclusion occlusion_params = ar_occlusion(*occlusion);
+    if (const int rc2 = launch_tiles(h, tiles, reinterpret_cast<ArTile*>(base + tiles_at), chunk, [&](const ArTile* d, int m, hipStream_t s) {
+            launch_ar_occluded(d, m, d_images, d_occluders, params, occlusion_params, s);
+        }))
+        return rc2;
+    if (visibility) {
+        std::vector<unsigned long long> counts(2 * (size_t)n);
+        HIP_TRY(hipMemcpyAsync(counts.data(), d_counts, counts_bytes, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        for (int i = 0; i < n; i++) {
+            visibility[i].covered = (int64_t)counts[2 * (size_t)i];
+            visibility[i].hidden = (int64_t)counts[2 * (size_t)i + 1];
+        }
+    }
+    return SVO_OK;
 }
+
+extern "C" int svo_render_ar(svo_handle* h, int n, const svo_ar_src* src, const svo_ar_camera* cameras, const int64_t* offset,
+                             const svo_ar_style* style, uint8_t* pixels) {
+    return render_ar(h, n, src, cameras, offset, style, nullptr, nullptr, pixels, nullptr);
+}
+
+extern "C" int svo_render_ar_occluded(svo_handle* h, int n, const svo_ar_src* src, const svo_ar_camera* cameras, const int64_t* offset,
+                                      const svo_ar_style* style, const svo_ar_occlusion* occlusion, const svo_ar_occluder* occluders,
+                                      uint8_t* pixels, svo_ar_visibility* visibility) {
+    if (const int rc = ar_check_occlusion(occlusion, "svo_render_ar_occluded")) return rc;
+    return render_ar(h, n, src, cameras, offset, style, occlusion, occluders, pixels, visibility);
+}
+
 
 // With a check that is on, a chunk of the image table is followed by its LrImage table and the reverse planes of its
 // images (each a multiple of 256 bytes) in the workspace: the search writes disparities whatever the style's value, the

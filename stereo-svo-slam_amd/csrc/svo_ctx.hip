@@ -111,6 +111,9 @@ struct svo_ctx {
         std::vector<int> seqs, seg, inst0, inst1;
         std::shared_ptr<const ArJob> job;
         svo_ar_dst dst{};
+        // (svo_submit_export_ar_occluded with on == 1: the occlusion)
+        bool occluded = false;
+        svo_ar_occlusion occlusion{};
     };
     // the group's share of an svo_submit_save: its named slots, indices in the group, and where each one goes
     struct Save {
@@ -228,7 +231,8 @@ int run_job(svo_group* g, int seq0, const svo_ctx::SceneExport& j) {
                                     j.has_clouds ? &j.clouds : nullptr, j.extra.empty() ? nullptr : j.extra.data());
 }
 int run_job(svo_group* g, int seq0, const svo_ctx::ArExport& j) {
-    return grp_export_ar(g, j.mem, j.seqs.data(), j.seg.data(), j.inst0.data(), j.inst1.data(), (int)j.seqs.size(), seq0, j.job.get(), &j.dst);
+    return grp_export_ar_occluded(g, j.mem, j.seqs.data(), j.seg.data(), j.inst0.data(), j.inst1.data(), (int)j.seqs.size(), seq0, j.job.get(), &j.dst,
+                                  j.occluded ? &j.occlusion : nullptr);
 }
 int run_job(svo_group* g, int, const svo_ctx::Save& j) { return grp_save(g, j.seqs.data(), (int)j.seqs.size(), j.snaps.data(), j.mem); }
 int run_job(svo_group* g, int, const svo_ctx::Load& j) { return grp_load(g, j.loads.data(), (int)j.loads.size(), j.mem); }
@@ -873,14 +877,15 @@ extern "C" int svo_export_scenes_clouds(svo_ctx* c, const int* seqs, int n, cons
     return rc ? rc : svo_wait(c);
 }
 
-extern "C" int svo_submit_export_ar(svo_ctx* c, const int* seqs, int n, const svo_ar_style* style, const svo_ar_mesh* meshes,
-                                    int n_meshes, const svo_ar_instance* instances, const int* first, int n_instances,
-                                    const svo_ar_dst* dst, int mem) {
-    const char* who = "svo_submit_export_ar";
+// svo_submit_export_ar (occlusion == null) and svo_submit_export_ar_occluded
+static int submit_export_ar(svo_ctx* c, const char* who, const int* seqs, int n, const svo_ar_style* style, const svo_ar_occlusion* occlusion,
+                            const svo_ar_mesh* meshes, int n_meshes, const svo_ar_instance* instances, const int* first, int n_instances,
+                            const svo_ar_dst* dst, int mem) {
     if (!c || !dst || !dst->segments || (mem != SVO_MEM_HOST && mem != SVO_MEM_DEVICE) || (seqs && n < 0) || n_meshes < 0 ||
         n_instances < 0 || (n_meshes > 0 && !meshes) || (n_instances > 0 && !instances))
         return svo_set_error(SVO_ERR_INVALID, "%s: bad arguments (mem %d, %d meshes, %d instances)", who, mem, n_meshes, n_instances);
     if (const int rc = svo::ar_check_style(style, who)) return rc;
+    if (const int rc = grp_check_ar_occlusion(c->workers[0]->g.get(), occlusion)) return rc;   // (every group has the same size and settings)
     if (!dst->pixels || ((uintptr_t)dst->pixels & 3)) return svo_set_error(SVO_ERR_INVALID, "%s: pixels is NULL or not 4-byte aligned", who);
     if (!seqs) n = c->B;
     const NamedSlots slots{seqs, n};
@@ -936,9 +941,29 @@ extern "C" int svo_submit_export_ar(svo_ctx* c, const int* seqs, int n, const sv
         });
         if (e.seqs.empty()) continue;
         e.mem = mem; e.job = job; e.dst = *dst;
+        if (occlusion && occlusion->on == 1) { e.occluded = true; e.occlusion = *occlusion; }
         worker_submit(w, std::move(e));
     }
     return SVO_OK;
+}
+
+extern "C" int svo_submit_export_ar(svo_ctx* c, const int* seqs, int n, const svo_ar_style* style, const svo_ar_mesh* meshes,
+                                    int n_meshes, const svo_ar_instance* instances, const int* first, int n_instances,
+                                    const svo_ar_dst* dst, int mem) {
+    return submit_export_ar(c, "svo_submit_export_ar", seqs, n, style, nullptr, meshes, n_meshes, instances, first, n_instances, dst, mem);
+}
+
+extern "C" int svo_submit_export_ar_occluded(svo_ctx* c, const int* seqs, int n, const svo_ar_style* style, const svo_ar_occlusion* occlusion,
+                                             const svo_ar_mesh* meshes, int n_meshes, const svo_ar_instance* instances, const int* first,
+                                             int n_instances, const svo_ar_dst* dst, int mem) {
+    return submit_export_ar(c, "svo_submit_export_ar_occluded", seqs, n, style, occlusion, meshes, n_meshes, instances, first, n_instances, dst, mem);
+}
+
+extern "C" int svo_export_ar_occluded(svo_ctx* c, const int* seqs, int n, const svo_ar_style* style, const svo_ar_occlusion* occlusion,
+                                      const svo_ar_mesh* meshes, int n_meshes, const svo_ar_instance* instances, const int* first, int n_instances,
+                                      const svo_ar_dst* dst, int mem) {
+    const int rc = svo_submit_export_ar_occluded(c, seqs, n, style, occlusion, meshes, n_meshes, instances, first, n_instances, dst, mem);
+    return rc ? rc : svo_wait(c);
 }
 
 extern "C" int svo_export_ar(svo_ctx* c, const int* seqs, int n, const svo_ar_style* style, const svo_ar_mesh* meshes, int n_meshes,

@@ -95,6 +95,13 @@ struct ArJob {
 int grp_export_ar(svo_group* g, int mem, const int* seqs, const int* seg, const int* inst0, const int* inst1, int n, int seq0,
                   const ArJob* job, const svo_ar_dst* dst);
 int64_t grp_ar_bytes(const svo_group* g, const svo_ar_style* style);   // the image_bytes of a checked style
+// grp_export_ar hidden behind the slots' dense stereo depth (svo_submit_export_ar_occluded). occlusion: checked
+// (grp_check_ar_occlusion) with on == 1; occlusion->info[seg[i]] is filled if there is one. occlusion == null is
+// grp_export_ar.
+int grp_export_ar_occluded(svo_group* g, int mem, const int* seqs, const int* seg, const int* inst0, const int* inst1, int n, int seq0,
+                           const ArJob* job, const svo_ar_dst* dst, const svo_ar_occlusion* occlusion);
+// what svo_submit_export_ar_occluded checks of an occlusion (null: nothing)
+int grp_check_ar_occlusion(const svo_group* g, const svo_ar_occlusion* occlusion);
 // One group's share of svo_submit_export_disparity (svo_group_dense.hip), between two steps of the group, on the thread
 // that drives it: slot seqs[i] (index in the group; ctx slot seq0 + seqs[i]) fills dst->segments[seg[i]] and its planes
 // go to byte seg[i] * image_bytes of dst->values (host or device memory: mem). style: checked

@@ -348,6 +348,9 @@ struct svo_group {
     svo::GrowBlock<uint8_t, true> d_ar_in;
     svo::GrowBlock<uint8_t> d_ar_rec;
     svo::GrowBlock<uint8_t> d_ar;
+    // ar occlusion (grp_export_ar_occluded): the organized records of one chunk of a job, made by the first occluded
+    // job and replaced when outgrown
+    svo::GrowBlock<uint8_t> d_ar_occ;
     // disparity maps (grp_export_disparity) in host mode: the planes of one job, made by the first such job and
     // replaced when outgrown
     svo::GrowBlock<uint8_t> d_dense;

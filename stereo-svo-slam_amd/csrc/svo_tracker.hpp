@@ -325,6 +325,26 @@ void ar_shape(const svo_ar_style& style, int cols, int rows, int64_t* pitch, int
 int ar_work(int image, int w, int h, const svo_ar_draw* draws, int n_draws, std::vector<ArSetup>& setup, std::vector<ArTile>& tiles);
 void launch_ar_setup(const ArSetup* d_setup, int n_setup, const ArImage* d_images, const ArParams& p, hipStream_t stream);
 void launch_ar(const ArTile* d_tiles, int n_tiles, const ArImage* d_images, const ArParams& p, hipStream_t stream);
+// ar occlusion (include/svo_hip.h, "ar occlusion"). The occluder of one image, beside its ArImage (same index): the
+// organized lattice (null: the image has none; cols, rows > 0 and step 1 .. 16 otherwise) and the image's two
+// counters {covered, hidden}, zero before the launch, which the tile kernel adds to. 32 bytes.
+struct ArOccluder {
+    const svo_map_point* records;
+    unsigned long long* counts;
+    int cols, rows, step, _pad;
+};
+// what the occluded launch reads of a checked svo_ar_occlusion
+struct ArOcclusion {
+    int hidden, alpha;
+    float margin;
+    uint32_t drop_flags;
+};
+// the scalar fields of an occlusion (on, hidden, alpha, margin, the reserved words)
+int ar_check_occlusion(const svo_ar_occlusion* o, const char* who);
+ArOcclusion ar_occlusion(const svo_ar_occlusion& o);
+// launch_ar with occluders: d_occluders[image] belongs to d_images[image]
+void launch_ar_occluded(const ArTile* d_tiles, int n_tiles, const ArImage* d_images, const ArOccluder* d_occluders, const ArParams& p,
+                        const ArOcclusion& o, hipStream_t stream);
 
 // ------------------------------------------------------------ dense disparity (dense.hip)
 // One image pair of a launch: the two gray planes (any base, strides >= w; both w x h), the planes at out (cols x rows

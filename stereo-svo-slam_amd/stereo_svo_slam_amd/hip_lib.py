@@ -53,6 +53,7 @@ SYMBOLS = (
     "svo_ctx_set_voxel_maps", "svo_get_voxel_map_info", "svo_submit_fuse_clouds", "svo_fuse_clouds",
     "svo_submit_export_voxel_maps", "svo_export_voxel_maps", "svo_submit_clear_voxel_maps",
     "svo_ar_size", "svo_ar_camera_of_pose", "svo_submit_export_ar", "svo_export_ar", "svo_render_ar",
+    "svo_submit_export_ar_occluded", "svo_export_ar_occluded", "svo_render_ar_occluded",
     "svo_remap_linear_multi", "svo_ctx_add_rigs", "svo_ctx_remove_rigs", "svo_ctx_assign_rigs", "svo_ctx_get_slot_rig",
     "svo_ctx_get_rigs",
     "svo_klt_track_batch", "svo_klt_cache_layout",
@@ -829,6 +830,53 @@ def ar_instance(model, mesh=0, rgb=0xc08040):
     return ArInstance((C.c_float * 12)(*[float(x) for x in np.asarray(model).ravel()]), int(mesh), int(rgb))
 
 
+# ar occlusion (svo_submit_export_ar_occluded, include/svo_hip.h): meshes hidden behind the dense stereo depth
+AR_HIDDEN_DROP, AR_HIDDEN_DIM = 0, 1
+AR_HIDDEN = ("drop", "dim")
+AR_VISIBILITY_DTYPE = np.dtype([("status", "<i4"), ("occluder_points", "<i4"), ("covered", "<i8"), ("hidden", "<i8"),
+                                ("_pad", "<i8")])
+
+
+class ArOcclusion(C.Structure):
+    """svo_ar_occlusion (include/svo_hip.h): how an ar job hides its meshes behind the slots' dense stereo depth."""
+    _fields_ = [("on", C.c_int32), ("hidden", C.c_int32), ("alpha", C.c_int32), ("margin", C.c_float),
+                ("drop_flags", C.c_uint32), ("_reserved", C.c_int32 * 3), ("cloud", CloudStyle), ("check", StereoCheck),
+                ("info", C.c_void_p), ("_reserved2", C.c_int64)]
+
+
+class ArOccluder(C.Structure):
+    """svo_ar_occluder (include/svo_hip.h): the organized lattice of one image of svo_render_ar_occluded."""
+    _fields_ = [("records", C.c_void_p), ("cols", C.c_int32), ("rows", C.c_int32), ("step", C.c_int32),
+                ("_reserved", C.c_int32)]
+
+
+assert (C.sizeof(ArOcclusion), C.sizeof(ArOccluder), AR_VISIBILITY_DTYPE.itemsize) == (128, 24, 32)
+
+
+def ar_occlusion(on=True, step=4, hidden=AR_HIDDEN_DROP, alpha=128, margin=0.0, drop_flags=0, win=0, search_x=0, search_y=0,
+                 min_disparity=0.0, max_depth=0.0, max_mean_cost=0.0, lr_check=0.0, info=None):
+    """an ArOcclusion. hidden may be a name (AR_HIDDEN); step, win, search_x, search_y, min_disparity, max_depth,
+    max_mean_cost: the cloud that occludes (cloud_style; 0: the ctx's settings / off); lr_check > 0: the left-right
+    check at that tolerance; info: None, or a numpy array of AR_VISIBILITY_DTYPE, one per named slot, that must stay
+    alive until the job is delivered."""
+    if isinstance(hidden, str):
+        hidden = AR_HIDDEN.index(hidden)
+    lr_check = float(lr_check or 0.0)
+    return ArOcclusion(int(bool(on)), int(hidden), int(alpha), float(margin), int(drop_flags), (C.c_int32 * 3)(),
+                       cloud_style(step, win, search_x, search_y, CLOUD_CAMERA, CLOUD_COMPACT, min_disparity, max_depth,
+                                   max_mean_cost),
+                       stereo_check(lr_check > 0, lr_check), info.ctypes.data if info is not None else None, 0)
+
+
+def ar_occluder(records, cols=0, rows=0, step=1):
+    """an ArOccluder of `records`: None (the image has none), a device tensor holding cols * rows MAP_POINT_DTYPE
+    records, or a raw device address"""
+    if records is None:
+        return ArOccluder(None, 0, 0, 0, 0)
+    ptr = records.data_ptr() if isinstance(records, torch.Tensor) else int(records)
+    return ArOccluder(ptr, int(cols), int(rows), int(step), 0)
+
+
 class SnapshotInfo(C.Structure):
     """struct svo_snapshot_info (include/svo_hip.h): the header of a snapshot's host part."""
     _fields_ = [("magic", C.c_uint32), ("version", C.c_uint32), ("byte_order", C.c_uint32), ("status", C.c_uint32),
@@ -1362,13 +1410,16 @@ class Handle:
         _check(lib().svo_render_scene_clouds(self._h, n, arr, packed_spans[0], packed_spans[1], cams, offs, C.byref(style),
                                              C.c_int32(int(point_size)), C.c_void_p(p)))
 
-    def render_ar(self, srcs, cameras, offsets, style, pixels):
+    def render_ar(self, srcs, cameras, offsets, style, pixels, occluders=None, occlusion=None):
         """svo_render_ar: lit meshes over gray planes as images of `style` (an ArStyle). srcs: per image
         ((data address or uint8 device tensor, width, height, stride), draws) with draws a list of (model of 12
         floats, vertices float32 device tensor [V, 3], triangles int32 device tensor [T, 3], rgb uint32 / int32 device
         tensor [T] or None, the instance's colour); cameras: an ArCamera per image; offsets[i]: the byte of `pixels`
-        (a uint8 device tensor, or a raw device address) image i starts at. Complete on return."""
-        self.render_ar_packed(self.pack_ar(srcs, cameras, offsets), style, pixels)
+        (a uint8 device tensor, or a raw device address) image i starts at. Complete on return.
+        With occlusion (an ArOcclusion; only its scalar fields are read) the call is svo_render_ar_occluded: occluders
+        is one ArOccluder, or what ar_occluder takes as a tuple, per image, and the visibility of every image is
+        returned (AR_VISIBILITY_DTYPE [n]); without it None is returned."""
+        return self.render_ar_packed(self.pack_ar(srcs, cameras, offsets), style, pixels, occluders, occlusion)
 
     def pack_ar(self, srcs, cameras, offsets):
         """the argument arrays of render_ar, built once (keeps Python out of a timed call); pass the result to
@@ -1390,11 +1441,26 @@ class Handle:
         offs = (C.c_int64 * max(n, 1))(*[int(o) for o in offsets])
         return n, arr, cams, offs, keep
 
-    def render_ar_packed(self, packed, style, pixels):
-        """svo_render_ar of the arrays of pack_ar"""
+    def pack_ar_occluders(self, occluders):
+        """the occluder array of render_ar_packed, built once; the device tensors must stay alive"""
+        occ = [o if isinstance(o, ArOccluder) else ar_occluder(*(o if isinstance(o, (tuple, list)) else (o,)))
+               for o in occluders]
+        return (ArOccluder * max(len(occ), 1))(*occ)
+
+    def render_ar_packed(self, packed, style, pixels, occluders=None, occlusion=None):
+        """svo_render_ar of the arrays of pack_ar; with occlusion svo_render_ar_occluded (occluders: as in render_ar,
+        or the array of pack_ar_occluders), which returns the visibilities"""
         n, arr, cams, offs, _ = packed
         p = pixels.data_ptr() if isinstance(pixels, torch.Tensor) else int(pixels)
-        _check(lib().svo_render_ar(self._h, n, arr, cams, offs, C.byref(style), C.c_void_p(p)))
+        if occlusion is None:
+            _check(lib().svo_render_ar(self._h, n, arr, cams, offs, C.byref(style), C.c_void_p(p)))
+            return None
+        if occluders is not None and not isinstance(occluders, C.Array):
+            occluders = self.pack_ar_occluders(occluders)
+        vis = np.zeros(max(n, 1), AR_VISIBILITY_DTYPE)
+        _check(lib().svo_render_ar_occluded(self._h, n, arr, cams, offs, C.byref(style), C.byref(occlusion), occluders,
+                                            C.c_void_p(p), C.c_void_p(vis.ctypes.data)))
+        return vis[:n]
 
     def copy_segments(self, segs):
         """svo_copy_segments: 2-D byte segments, device to device. segs: (src address, dst address, row_bytes,

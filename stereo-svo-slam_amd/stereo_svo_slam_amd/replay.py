@@ -44,6 +44,9 @@ that map in the pictures of --dump-scene.
 --dump-ar DIR writes per frame DIR/000000_ar.ppm: the AR demo's picture (src/ar-app/), a lit box of edge --ar-box
 fixed at the world point --ar-at over the frame's left image, seen from the tracked pose; the default placement is the
 demo's, half a metre in front of the first camera (AnimatedEntity.qml:56). If the pose is right the box stands still.
+--ar-occlude STEP [--ar-hidden drop|dim] [--ar-alpha A] [--ar-margin M] [--ar-lr D] hides the box where the frame's
+dense stereo depth (searched at every STEP-th pixel, left-right checked at tolerance D) lies in front of it, and prints
+a line "ar NNNNNN covered C hidden H occluder_points P" per frame.
 With $SVO_DATA set (a EuRoC `mav0/` directory, or a directory of side-by-side frames) and no
 explicit input that data is used; otherwise the seeded synthetic sequence.
 """
@@ -421,7 +424,7 @@ class Replay:
                  ar_box=AR_BOX, ar_at=hip_lib.AR_AT, dump_disparity=None, disparity_step=4, disparity_depth=False,
                  dump_cloud=None, cloud_step=4, cloud_max_depth=0.0, disparity_lr=None, cloud_lr=None, scene_dense=None,
                  scene_dense_lr=None, scene_dense_max_depth=0.0, scene_accumulate=0, dump_dense_map=None, dense_map_voxel=None,
-                 dense_map_log2=20, dense_map_min_count=0, scene_fused=None):
+                 dense_map_log2=20, dense_map_min_count=0, scene_fused=None, ar_occlusion=None):
         """fast=False keeps the library default: the reference-order Gauss-Newton (bit-exact traces).
         rectify_maps = (left maps, right maps): the frames fed are raw and are rectified on the GPU.
         calibration = (left, right) CameraCalibrations: the same, with the maps built on the GPU as well.
@@ -439,7 +442,9 @@ class Replay:
         draws as the extra span: the pictures show the dense map growing.
         dump_ar: a directory that receives, per frame, the AR demo's picture (get_ar): a lit box of edge ar_box at the
         world point ar_at over the frame's left image, likewise. The default is the demo's placement, half a metre in
-        front of the first camera.
+        front of the first camera. ar_occlusion: None, or the occlusion of StereoSlamBatch.submit_ar as a dict: the box
+        is hidden behind the frame's dense stereo depth, and a line "ar NNNNNN covered C hidden H occluder_points P" per
+        frame goes to the log (ar_log keeps the three numbers per frame).
         dump_disparity: a directory that receives, per frame, the dense disparity map of the frame (get_disparity at
         the lattice disparity_step; the depth map with disparity_depth) as NNNNNN_disparity.npy [rows, cols], likewise.
         dump_cloud: a directory that receives, whenever the newest keyframe id changes, that keyframe's dense point cloud
@@ -455,6 +460,7 @@ class Replay:
         self.settings = settings
         self.dump_views, self.dump_scene, self.dump_ar = dump_views, dump_scene, dump_ar
         self.ar_objects = ar_objects(ar_box, ar_at)
+        self.ar_occlusion, self.ar_log = ar_occlusion, []
         self.dump_disparity, self.disparity_step, self.disparity_depth = dump_disparity, int(disparity_step), bool(disparity_depth)
         self.dump_cloud, self.cloud_step, self.cloud_max_depth, self._cloud_kf = dump_cloud, int(cloud_step), float(cloud_max_depth), -1
         self.disparity_lr = None if disparity_lr is None else float(disparity_lr)
@@ -535,9 +541,14 @@ class Replay:
             if img is not None:
                 write_ppm(os.path.join(self.dump_scene, f"{len(self.cumulative) - 1:06d}_scene.ppm"), img)
         if self.dump_ar:
-            img = self.slam.get_ar(self.ar_objects, pixel="rgb8")
+            img = self.slam.get_ar(self.ar_objects, pixel="rgb8", occlusion=self.ar_occlusion)
             if img is not None:
                 write_ppm(os.path.join(self.dump_ar, f"{len(self.cumulative) - 1:06d}_ar.ppm"), img)
+                if self.ar_occlusion is not None:
+                    v = self.slam.ar_visibility
+                    self.ar_log.append((int(v["covered"]), int(v["hidden"]), int(v["occluder_points"])))
+                    print(f"ar {len(self.cumulative) - 1:06d} covered {self.ar_log[-1][0]} hidden {self.ar_log[-1][1]} "
+                          f"occluder_points {self.ar_log[-1][2]}")
         if self.dump_disparity:
             value = "depth" if self.disparity_depth else "disparity"
             if self.disparity_lr is None:
@@ -667,6 +678,16 @@ def build_parser():
                     help="write per frame DIR/NNNNNN_ar.ppm: the AR demo's picture, a lit box standing in the world over the "
                          "frame's left image, seen from the tracked pose")
     ap.add_argument("--ar-box", metavar="SIZE", type=float, default=AR_BOX, help="edge of the box of --dump-ar, metres")
+    ap.add_argument("--ar-occlude", metavar="STEP", type=int, default=None,
+                    help="--dump-ar hides the box behind the frame's dense stereo depth, searched at every STEP-th pixel (1 .. 16), "
+                         "and prints the covered and hidden pixels of every frame")
+    ap.add_argument("--ar-hidden", choices=hip_lib.AR_HIDDEN, default="drop",
+                    help="hidden pixels of --ar-occlude show the image (drop) or the box blended into it (dim)")
+    ap.add_argument("--ar-alpha", metavar="A", type=int, default=128, help="--ar-hidden dim: the image's weight, 0 .. 256")
+    ap.add_argument("--ar-margin", metavar="M", type=float, default=0.0,
+                    help="--ar-occlude hides what lies more than M behind the scene's depth (the unit of the baseline)")
+    ap.add_argument("--ar-lr", metavar="D", type=float, default=None,
+                    help="--ar-occlude trusts only depths that pass the left-right check at tolerance D pixels")
     ap.add_argument("--ar-at", metavar="X,Y,Z", default=",".join(str(x) for x in hip_lib.AR_AT),
                     help="world point of the box's centre (default: half a metre in front of the first camera, as the demo)")
     ap.add_argument("--dump-disparity", metavar="DIR",
@@ -776,6 +797,15 @@ def main(argv=None):
     if args.gpu_imu and not args.gyro:
         ap.error("--gpu-imu needs --gyro")
     gyro = np.loadtxt(args.gyro, ndmin=2) if args.gyro else None
+    occlusion = None
+    if args.ar_occlude is not None:
+        if not args.dump_ar:
+            ap.error("--ar-occlude needs --dump-ar")
+        if not 1 <= args.ar_occlude <= 16 or not 0 <= args.ar_alpha <= 256 or not 0 <= args.ar_margin < float("inf"):
+            ap.error("--ar-occlude must be 1 .. 16, --ar-alpha 0 .. 256 and --ar-margin finite and >= 0")
+        if args.ar_lr is not None and not 0 < args.ar_lr < float("inf"):
+            ap.error("--ar-lr must be a finite tolerance > 0")
+        occlusion = dict(step=args.ar_occlude, hidden=args.ar_hidden, alpha=args.ar_alpha, margin=args.ar_margin, lr_check=args.ar_lr or 0.0)
     rp = Replay(settings, args.device, args.time_trace, args.fast, rectify_maps=rect, input_format=fmt, gpu_imu=args.gpu_imu,
                 dump_views=args.dump_views, dump_scene=args.dump_scene, calibration=cal, dump_ar=args.dump_ar,
                 ar_box=args.ar_box, ar_at=tuple(float(x) for x in args.ar_at.split(",")),
@@ -784,7 +814,8 @@ def main(argv=None):
                 cloud_max_depth=args.cloud_max_depth, disparity_lr=args.disparity_lr, cloud_lr=args.cloud_lr,
                 scene_dense=args.scene_dense, scene_dense_lr=args.scene_dense_lr, scene_dense_max_depth=args.scene_dense_max_depth,
                 scene_accumulate=args.scene_accumulate, dump_dense_map=args.dump_dense_map, dense_map_voxel=args.dense_map_voxel,
-                dense_map_log2=args.dense_map_log2, dense_map_min_count=args.dense_map_min_count, scene_fused=args.scene_fused)
+                dense_map_log2=args.dense_map_log2, dense_map_min_count=args.dense_map_min_count, scene_fused=args.scene_fused,
+                ar_occlusion=occlusion)
     for k, (left, right, t) in enumerate(frames):
         rp.feed(left, right, t, None if gyro is None else gyro[gyro[:, 0] == k, 1:4])
     rp.finish()

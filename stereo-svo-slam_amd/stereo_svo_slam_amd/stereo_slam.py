@@ -620,9 +620,15 @@ class ArPictures:
     pinned memory in host mode, a torch uint8 tensor on the ctx's device in device mode. cols, rows, pitch,
     image_bytes: the shape of every image of the job (svo_ar_size); channels: 3 or 4. meshes: (vertices [V, 3],
     triangles [T, 3][, rgb [T] or None]) each; instances: hip_lib.ArInstance, or (model of 12 floats, mesh index,
-    rgb) each; first: None (every slot shows every instance) or n + 1 ascending offsets into the instances."""
+    rgb) each; first: None (every slot shows every instance) or n + 1 ascending offsets into the instances.
+    With occlusion (StereoSlamBatch.submit_ar) the job is svo_submit_export_ar_occluded and `visibility`
+    (hip_lib.AR_VISIBILITY_DTYPE, one per named slot) says how much of the meshes is hidden; without it visibility
+    is None."""
 
-    def __init__(self, slam, seqs, style, meshes, instances, first, device):
+    OCCLUSION_DEFAULTS = dict(step=4, hidden="drop", alpha=128, margin=0.0, drop_flags=0, win=0, search_x=0, search_y=0,
+                              min_disparity=0.0, max_depth=0.0, max_mean_cost=0.0, lr_check=0.0)
+
+    def __init__(self, slam, seqs, style, meshes, instances, first, device, occlusion=None):
         self._slam = slam
         self.style, self.device_mode = style, bool(device)
         self.seqs = None if seqs is None else [int(s) for s in seqs]
@@ -653,6 +659,20 @@ class ArPictures:
                      else torch.zeros(max(self.capacity, 4), dtype=torch.uint8, pin_memory=True))
         self._dst = hip_lib.ArDst(self._seg.ctypes.data, self._buf.data_ptr(), self.capacity)
         self._seq_arr = None if seqs is None else (C.c_int * max(n, 1))(*self.seqs)
+        self.visibility = self._occlusion = None
+        if occlusion is not None:
+            if isinstance(occlusion, hip_lib.ArOcclusion):
+                self._occlusion = hip_lib.ArOcclusion.from_buffer_copy(occlusion)
+            else:
+                d = dict(self.OCCLUSION_DEFAULTS)
+                unknown = set(occlusion) - set(d)
+                if unknown:
+                    raise ValueError(f"occlusion: unknown keys {sorted(unknown)}")
+                d.update(occlusion)
+                self._occlusion = hip_lib.ar_occlusion(True, **d)
+            self._vis = np.zeros(max(n, 1), hip_lib.AR_VISIBILITY_DTYPE)
+            self._occlusion.info = self._vis.ctypes.data
+            self.visibility = self._vis[:n]
 
     @property
     def pixels(self):
@@ -663,9 +683,14 @@ class ArPictures:
         slam = self._slam
         if self.device_mode:
             torch.cuda.current_stream(slam.device).synchronize()     # (nothing of the caller's is still using the tensor)
-        _check(lib().svo_submit_export_ar(slam._ctx, self._seq_arr, self._n, C.byref(self.style), self._meshes, self._n_meshes,
-                                          self._inst, self._first, self._n_inst, C.byref(self._dst),
-                                          hip_lib.MEM_DEVICE if self.device_mode else hip_lib.MEM_HOST))
+        mem = hip_lib.MEM_DEVICE if self.device_mode else hip_lib.MEM_HOST
+        if self._occlusion is None:
+            _check(lib().svo_submit_export_ar(slam._ctx, self._seq_arr, self._n, C.byref(self.style), self._meshes, self._n_meshes,
+                                              self._inst, self._first, self._n_inst, C.byref(self._dst), mem))
+        else:
+            _check(lib().svo_submit_export_ar_occluded(slam._ctx, self._seq_arr, self._n, C.byref(self.style),
+                                                       C.byref(self._occlusion), self._meshes, self._n_meshes, self._inst,
+                                                       self._first, self._n_inst, C.byref(self._dst), mem))
         return self
 
     def wait(self):
@@ -1079,15 +1104,18 @@ class StereoSlamBatch:
         """submit_scenes + wait"""
         return self.submit_scenes(seqs, **kw).wait()
 
-    def submit_ar(self, meshes, instances, seqs=None, first=None, device=False, style=None, **kw):
+    def submit_ar(self, meshes, instances, seqs=None, first=None, device=False, style=None, occlusion=None, **kw):
         """svo_submit_export_ar: queue the AR demo's picture (the instanced meshes, lit and depth tested, over the
         left image of each named slot's current frame, seen from its pose through its rig's intrinsics) of the named
         slots (None: all), ordered with the frame sets; nothing is waited for. meshes, instances, first: see
         ArPictures; style: a hip_lib.ArStyle, or its fields as keywords (hip_lib.ar_style: pixel, light, ambient,
-        near). Returns an ArPictures, valid after wait()."""
+        near). occlusion: None, a hip_lib.ArOcclusion, or a dict (step, hidden = "drop" | "dim", alpha, margin,
+        drop_flags, win, search_x, search_y, min_disparity, max_depth, max_mean_cost, lr_check): the job is
+        svo_submit_export_ar_occluded, the meshes are hidden behind the dense, checked stereo depth of the frame and
+        ArPictures.visibility counts the covered and hidden pixels. Returns an ArPictures, valid after wait()."""
         if style is None:
             style = hip_lib.ar_style(**kw)
-        return ArPictures(self, seqs, style, meshes, instances, first, device).submit()
+        return ArPictures(self, seqs, style, meshes, instances, first, device, occlusion).submit()
 
     def export_ar(self, meshes, instances, seqs=None, **kw):
         """submit_ar + wait"""
@@ -1528,6 +1556,7 @@ class StereoSlam(StereoSlamBatch):
     def __init__(self, camera_settings, width=None, height=None, device=0):
         self._pending = (camera_settings, device)
         self._ctx = None
+        self.ar_visibility = None          # get_ar with occlusion: the last picture's counts
         if width is not None:
             super().__init__(camera_settings, width, height, 1, device)
 
@@ -1616,11 +1645,15 @@ class StereoSlam(StereoSlamBatch):
     def get_ar(self, objects, **kw):
         """the AR demo's picture of the current frame as a numpy array [height, width, 3 | 4] (export_ar of the one
         slot: pixel, light, ambient, near). objects: (vertices, triangles, model of 12 floats, rgb) each, e.g.
-        (*hip_lib.ar_box(0.2), hip_lib.ar_model(hip_lib.AR_AT), 0xc08040). None before the first frame"""
+        (*hip_lib.ar_box(0.2), hip_lib.ar_model(hip_lib.AR_AT), 0xc08040). occlusion = dict(...) (submit_ar) hides
+        the objects behind the frame's dense stereo depth. None before the first frame"""
         if self._ctx is None:
             return None
         kw["device"] = False
         meshes = [(v, t) for v, t, _, _ in objects]
         instances = [(model, i, rgb) for i, (_, _, model, rgb) in enumerate(objects)]
-        img = self.export_ar(meshes, instances, None, **kw).image(0)
+        job = self.export_ar(meshes, instances, None, **kw)
+        # (with occlusion: the picture's hip_lib.AR_VISIBILITY_DTYPE record, for whoever wants the counts)
+        self.ar_visibility = None if job.visibility is None else job.visibility[0].copy()
+        img = job.image(0)
         return None if img is None else img.copy()

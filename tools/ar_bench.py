@@ -17,6 +17,20 @@ process:
   pipelined  frames/s over `--steps` queued steps without pictures and with a device-mode picture of every slot queued
              behind every 10th frame set; legs alternate, median of `--pipelined-repeats` each.
 Prints one JSON line.
+
+--occluded STEP[,STEP...] measures the occluded picture instead, per lattice step, on the same workload
+and meshes, and writes profiles/ar_occlusion_bench.json unless --out names another file:
+
+  kernel     the stage entry with an occluder (ar_render_kernel<true>; the lattices are the slots' checked camera-frame
+             clouds, computed once by a device-mode cloud job) against the stage entry without (ar_render_kernel<false>),
+             alternating, median of `--repeats` calls each between two device events.
+  job        the occluded job of every slot (submit + wait, host clock, device mode) against the unoccluded job plus a
+             checked device-mode cloud job of the same style, which it replaces; medians and every repeat, so that the
+             spread can be read.
+  host path  what a caller did before, for `--host-slots` slots: the cloud to the host, the picture to the host, a numpy
+             rasteriser for the meshes' depths, the composition; seconds per slot beside the job's.
+  pipelined  frames/s with nothing, with a plain picture and with an occluded picture of every slot behind every 10th
+             frame set.
 """
 import argparse
 import json
@@ -207,6 +221,161 @@ def pipelined_leg(args, device, cfg, lefts, rights, slots, groups, meshes):
     return out
 
 
+def host_depths(H, W, camera, draws, near):
+    """float32 [H, W]: the smallest depth of the meshes per pixel (+inf: none), rasterised on the host in numpy with the
+    arithmetic of include/svo_hip.h, "ar": what a caller needed before the job could occlude"""
+    cam = np.frombuffer(bytes(camera), np.float32)
+    V, fx, fy, cx, cy = cam[:12].reshape(3, 4).astype(np.float64), cam[12], cam[13], cam[14], cam[15]
+    depth = np.full((H, W), np.inf, np.float32)
+    for model, vertices, triangles in draws:
+        M = np.asarray(model, np.float64).reshape(3, 4)
+        w = vertices.astype(np.float64) @ M[:, :3].T + M[:, 3]
+        c = w @ V[:, :3].T + V[:, 3]
+        ok = c[:, 2] >= near
+        z = np.where(ok, c[:, 2], 1.0)
+        X = np.floor((fx * c[:, 0] / z + cx) * 16).astype(np.int64)
+        Y = np.floor((fy * c[:, 1] / z + cy) * 16).astype(np.int64)
+        for t in triangles:
+            if not ok[t].all():
+                continue
+            x, y, d = X[t], Y[t], c[t, 2]
+            A = (x[1] - x[0]) * (y[2] - y[0]) - (y[1] - y[0]) * (x[2] - x[0])
+            x0, x1 = max((x.min() + 7) >> 4, 0), min((x.max() - 8) >> 4, W - 1)
+            y0, y1 = max((y.min() + 7) >> 4, 0), min((y.max() - 8) >> 4, H - 1)
+            if A == 0 or x0 > x1 or y0 > y1:
+                continue
+            px, py = np.meshgrid(16 * np.arange(x0, x1 + 1) + 8, 16 * np.arange(y0, y1 + 1) + 8)
+            E = [((x[b] - x[a]) * (py - y[a]) - (y[b] - y[a]) * (px - x[a])) * (1 if A > 0 else -1) for a, b in ((1, 2), (2, 0), (0, 1))]
+            inside = (E[0] >= 0) & (E[1] >= 0) & (E[2] >= 0)
+            zz = ((E[0] * d[0] + E[1] * d[1] + E[2] * d[2]) / abs(A)).astype(np.float32)
+            sub = depth[y0:y1 + 1, x0:x1 + 1]
+            sub[inside & (zz < sub)] = zz[inside & (zz < sub)]
+    return depth
+
+
+def spread(all_ms):
+    return {"min_ms": min(all_ms), "max_ms": max(all_ms), "spread_ms": max(all_ms) - min(all_ms)}
+
+
+def occluded_leg(args, device, cfg, lefts, rights, meshes, step):
+    slots = args.slots
+    n = min(slots, len(lefts))
+    K, every = args.steps, 10
+    runs_n = 3 * args.pipelined_repeats
+    slam, packed = start(cfg, lefts[:n], rights[:n], slots, 1, device, args.warmup + (0 if args.kernel_only else runs_n * K))
+    for pk in packed[:args.warmup]:
+        slam.submit_packed(pk)
+    slam.wait()
+    W, H = cfg["width"], cfg["height"]
+    progress = lambda what: print(f"step {step}: {what}", file=sys.stderr, flush=True)
+    progress("warmed up")
+    inst, first = placed(slam, slots)
+    style = hip_lib.ar_style(pixel="rgba8")
+    occ = dict(step=step, margin=args.margin, max_depth=args.max_depth, lr_check=args.lr)
+    out = {"step": step, "slots": slots, "warmup_steps": args.warmup, "cols": W, "rows": H, "occlusion": occ,
+           "triangles_per_slot": sum(len(meshes[k][1]) for _, k, _ in inst[:2])}
+    plain = ArPictures(slam, None, style, meshes, inst, first, True).submit().wait()
+    job = ArPictures(slam, None, style, meshes, inst, first, True, occ).submit().wait()
+    cloud = slam.submit_cloud("frames", None, step=step, frame="camera", layout="organized", max_depth=args.max_depth, lr_check=args.lr or None,
+                              device=True).wait()
+    vis = job.visibility
+    out["covered"], out["hidden"] = int(vis["covered"].sum()), int(vis["hidden"].sum())
+    out["hidden_fraction"] = out["hidden"] / max(out["covered"], 1)
+    out["occluder_points_per_slot"] = float(vis["occluder_points"].mean())
+    out["lattice_bytes_per_slot"] = 16 * cloud.points_per_slot
+    # the stage entry on the same planes, with the clouds as occluders
+    views = slam.submit_views("frames", pixel="gray8", device=True).wait()
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
+    dm = [(dev(m[0]), dev(m[1])) for m in meshes]
+    h = hip_lib.Handle(device.index, 1024)
+    srcs = [((views.pixels.data_ptr() + s * views.image_bytes, W, H, W),
+             [(m, dm[k][0], dm[k][1], None, rgb) for m, k, rgb in inst[2 * s:2 * s + 2]]) for s in range(slots)]
+    _, cam = slam.slot_rig(0)
+    cams = [hip_lib.ar_camera_of_pose(slam.pose(s), cam) for s in range(slots)]
+    dst = torch.empty(slots * job.image_bytes, dtype=torch.uint8, device=device)
+    packed_ar = h.pack_ar(srcs, cams, [s * job.image_bytes for s in range(slots)])
+    occluders = h.pack_ar_occluders([(cloud.points_buffer.data_ptr() + 16 * int(e["first_point"]), cloud.cols, cloud.rows, step)
+                                     for e in cloud.segments])
+    occlusion = hip_lib.ar_occlusion(step=step, margin=args.margin)
+    with_occ = lambda: h.render_ar_packed(packed_ar, style, dst, occluders, occlusion)
+    without = lambda: h.render_ar_packed(packed_ar, style, dst)
+    v2 = with_occ()
+    out["stage_entry_equals_job"] = bool(torch.equal(dst, job.pixels)) and bool((v2["covered"] == vis["covered"]).all() and (v2["hidden"] == vis["hidden"]).all())
+    without()
+    out["stage_entry_plain_equals_job"] = bool(torch.equal(dst, plain.pixels))
+    if not args.kernel_only:
+        a_all, b_all = [], []
+        for _ in range(args.repeats):                                  # alternating
+            b_all += event_ms(without, 1)[1]
+            a_all += event_ms(with_occ, 1)[1]
+        a, b = statistics.median(a_all), statistics.median(b_all)
+        progress("stage entry timed")
+        out["stage_entry"] = {"occluded_call_ms": a, "plain_call_ms": b, "ratio": a / b, "occluded_call_ms_all": a_all, "plain_call_ms_all": b_all}
+        legs = {"occluded_job": lambda: job.submit().wait(), "plain_job": lambda: plain.submit().wait(), "cloud_job": lambda: cloud.submit().wait()}
+        all_ms = {k: [] for k in legs}
+        for k in legs:
+            legs[k]()
+        for _ in range(args.repeats):                                  # alternating
+            for k in legs:
+                all_ms[k].append(timed(device, legs[k]) * 1e3)
+        med = {k: statistics.median(v) for k, v in all_ms.items()}
+        out["job"] = {f"{k}_ms": med[k] for k in legs}
+        out["job"].update({f"{k}_ms_all": all_ms[k] for k in legs})
+        out["job"]["plain_plus_cloud_ms"] = med["plain_job"] + med["cloud_job"]
+        out["job"]["occluded_vs_plain_plus_cloud"] = med["occluded_job"] / (med["plain_job"] + med["cloud_job"])
+        out["job"]["spread"] = {k: spread(all_ms[k]) for k in legs}
+        progress("jobs timed")
+        # the host path it replaces, for a few slots
+        hs = list(range(min(args.host_slots, slots)))
+        t0 = time.perf_counter()
+        hc = slam.export_cloud("frames", hs, step=step, frame="camera", layout="organized", max_depth=args.max_depth, lr_check=args.lr or None)
+        hp = ArPictures(slam, hs, style, meshes, [x for s in hs for x in inst[2 * s:2 * s + 2]], [2 * i for i in range(len(hs) + 1)], False).submit().wait()
+        t1 = time.perf_counter()
+        gray = slam.export_views("frames", hs, plane="left", level=0, pixel="gray8")
+        differ = 0
+        for i, s in enumerate(hs):
+            z = host_depths(H, W, cams[s], [(m, meshes[k][0], meshes[k][1]) for m, k, _ in inst[2 * s:2 * s + 2]], style.near)
+            rec = hc.organized(i)
+            zo = np.where(((rec["flags"] & 0x80) == 0) & np.isfinite(rec["z"]) & (rec["z"] > 0), rec["z"], np.inf).astype(np.float32)
+            full = np.full((H, W), np.inf, np.float32)
+            full[:hc.rows * step, :hc.cols * step] = zo.repeat(step, 0).repeat(step, 1)
+            hide = np.isfinite(z) & (z > full + np.float32(args.margin))
+            img = hp.image(i).copy()
+            img[hide, :3] = gray.image(i)[hide][:, None]
+            got = job.image(s).cpu().numpy()
+            differ += int((img != got).any(axis=2).sum())
+        t2 = time.perf_counter()
+        out["host_path"] = {"slots": len(hs), "exports_s_per_slot": (t1 - t0) / len(hs), "rasterise_compose_s_per_slot": (t2 - t1) / len(hs),
+                            "total_s_per_slot": (t2 - t0) / len(hs), "occluded_job_s_per_slot": med["occluded_job"] * 1e-3 / slots,
+                            "pixels_differing_from_the_job": differ,
+                            "note": "the host rasteriser computes in float64: a few pixels at depth ties may differ from the job"}
+        progress("host path timed")
+        # pictures behind every 10th frame set
+        rings = {"plain": None, "ar": [plain, ArPictures(slam, None, style, meshes, inst, first, True).submit().wait()],
+                 "occluded": [job, ArPictures(slam, None, style, meshes, inst, first, True, occ).submit().wait()]}
+        runs = {k: [] for k in rings}
+        for r in range(runs_n):
+            kind = ("plain", "ar", "occluded")[r % 3]
+            steps = packed[args.warmup + r * K:args.warmup + (r + 1) * K]
+
+            def run():
+                for k, pk in enumerate(steps):
+                    slam.submit_packed(pk)
+                    if rings[kind] and k % every == every - 1:
+                        rings[kind][(k // every) % 2].submit()
+                slam.wait()
+            runs[kind].append(slots * K / timed(device, run))
+        out["pipelined"] = {"steps": K, "every": every, "groups": slam.groups()}
+        for kind in runs:
+            out["pipelined"][f"frames_per_s_{kind}"] = statistics.median(runs[kind])
+            out["pipelined"][f"frames_per_s_{kind}_all"] = runs[kind]
+        out["pipelined"]["occluded_vs_plain"] = out["pipelined"]["frames_per_s_occluded"] / out["pipelined"]["frames_per_s_plain"]
+    out["device_GB"] = slam.memory().device_bytes / 1e9
+    h.close()
+    slam.close()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--slots", type=int, default=256)
@@ -220,12 +389,31 @@ def main():
     ap.add_argument("--repeats", type=int, default=9)
     ap.add_argument("--pipelined-repeats", type=int, default=5, help="timed runs per kind of a pipelined leg")
     ap.add_argument("--out", default=None, help="also write the JSON result to this file")
+    ap.add_argument("--occluded", metavar="STEP[,STEP...]", default=None,
+                    help="measure the occluded picture at these lattice steps instead (writes profiles/ar_occlusion_bench.json unless --out)")
+    ap.add_argument("--margin", type=float, default=0.05, help="--occluded: the margin")
+    ap.add_argument("--max-depth", type=float, default=20.0, help="--occluded: the cloud's max_depth filter")
+    ap.add_argument("--lr", type=float, default=1.5, help="--occluded: the left-right tolerance (0: unchecked)")
+    ap.add_argument("--host-slots", type=int, default=2, help="--occluded: slots the host path is timed on")
     args = ap.parse_args()
     device = torch.device("cuda", 0)
     legs = [tuple(int(x) for x in l.split(":")) for l in args.legs.split(",") if l] if not args.kernel_only else []
     n_loops = min(max([s for s, _ in legs] + [args.slots]), args.loops)
     cfg, lefts, rights = bench.render_loops("euroc", list(range(n_loops)), args.loop_frames, device)
     meshes = [hip_lib.ar_box(0.3), sphere(0.15, args.sphere)]
+    if args.occluded:
+        n_loops = min(args.slots, args.loops)
+        out = {"metric": "ar_occlusion_bench", "config": "euroc", "hw_queues": int(os.environ["GPU_MAX_HW_QUEUES"]), "steps": []}
+        for step in (int(x) for x in args.occluded.split(",")):
+            out["steps"].append(occluded_leg(args, device, cfg, lefts[:n_loops], rights[:n_loops], meshes, step))
+            print(json.dumps(out["steps"][-1]), file=sys.stderr, flush=True)
+        text = json.dumps(out)
+        path = args.out or os.path.join(ROOT, "profiles", "ar_occlusion_bench.json")
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        with open(path, "w") as f:
+            f.write(text + "\n")
+        print(text, flush=True)
+        return
     out = {"metric": "ar_bench", "config": "euroc", "hbm_peak_bytes_per_s": HBM_PEAK, "hw_queues": int(os.environ["GPU_MAX_HW_QUEUES"]),
            "job": job_leg(args, device, cfg, lefts, rights, meshes), "legs": []}
     print(json.dumps(out["job"]), file=sys.stderr, flush=True)        # (progress)
