@@ -1,0 +1,86 @@
+// svo_ctx_voxel.hip — the voxel maps of the ctx's slots (svo_ctx_state.hpp): giving slots a map, its info, and the
+// queued jobs that fuse dense clouds into the maps, export them and clear them.
+#include "svo_ctx_state.hpp"
+
+extern "C" int svo_ctx_set_voxel_maps(svo_ctx* c, const int* seqs, int n, const svo_voxel_params* params) {
+    if (!c || !naming_ok(seqs, n)) return svo_set_error(SVO_ERR_INVALID, "svo_ctx_set_voxel_maps: bad arguments");
+    if (params)
+        if (const int rc = svo::voxel_check_params(params, true, "svo_ctx_set_voxel_maps")) return rc;
+    const NamedSlots slots = ctx_slots(c, seqs, n);
+    if (const int rc = check_slots(c, "svo_ctx_set_voxel_maps", slots)) return rc;
+    if (const int rc = ctx_drain(c)) return rc;
+    for (auto& wp : c->workers) {
+        SlotList local;
+        if (!slots.share(wp->first, wp->count, local, every_slot)) continue;
+        if (const int rc = grp_set_voxel_maps(wp->g.get(), local.seqs.data(), (int)local.seqs.size(), params)) return rc;
+    }
+    return SVO_OK;
+}
+
+extern "C" int svo_get_voxel_map_info(svo_ctx* ctx, int seq, svo_voxel_map_info* info) {
+    svo_group* g; int s;
+    if (const int rc = ctx_seq(ctx, seq, &g, &s)) return rc;
+    if (!grp_voxel_map_info(g, s, info)) return svo_set_error(SVO_ERR_INVALID, "svo_get_voxel_map_info: slot %d has no voxel map", seq);
+    return SVO_OK;
+}
+
+extern "C" int svo_submit_fuse_clouds(svo_ctx* c, int what, const int* seqs, int n, const svo_cloud_style* style,
+                                      const svo_stereo_check* check, uint32_t stamp, svo_fuse_info* info) {
+    if (const int rc = drop_check_that_is_off(&check, true, "svo_submit_fuse_clouds")) return rc;
+    if (!c || !info || !what_ok(what) || !naming_ok(seqs, n))
+        return svo_set_error(SVO_ERR_INVALID, "svo_submit_fuse_clouds: bad arguments (what %d)", what);
+    if (const int rc = grp_check_cloud_style(c->g0(), style, check)) return rc;
+    if (style->frame != SVO_CLOUD_WORLD || style->layout != 0)
+        return svo_set_error(SVO_ERR_INVALID, "svo_submit_fuse_clouds: frame must be SVO_CLOUD_WORLD and layout 0");
+    const NamedSlots slots = ctx_slots(c, seqs, n);
+    if (const int rc = check_slots(c, "svo_submit_fuse_clouds", slots)) return rc;
+    if (c->failed.load()) return reject_failed(c, "svo_submit_fuse_clouds");
+    submit_shares<svo_ctx::FuseClouds>(c, slots, every_slot, [&](svo_ctx::FuseClouds& e) {
+        e.what = what; e.style = *style; e.stamp = stamp; e.info = info;
+        e.set_check(check);
+    });
+    return SVO_OK;
+}
+
+extern "C" int svo_fuse_clouds(svo_ctx* c, int what, const int* seqs, int n, const svo_cloud_style* style, const svo_stereo_check* check,
+                               uint32_t stamp, svo_fuse_info* info) {
+    return then_wait(c, svo_submit_fuse_clouds(c, what, seqs, n, style, check, stamp, info));
+}
+
+extern "C" int svo_submit_export_voxel_maps(svo_ctx* c, const int* seqs, int n, const svo_voxel_region* regions,
+                                            const svo_voxel_filter* filter, const svo_voxel_dst* dst, int mem) {
+    if (!c || !dst || !dst->segments || !mem_ok(mem) || !naming_ok(seqs, n))
+        return svo_set_error(SVO_ERR_INVALID, "svo_submit_export_voxel_maps: bad arguments (mem %d)", mem);
+    const NamedSlots slots = ctx_slots(c, seqs, n);
+    if (slots.n > 0 && !regions) return svo_set_error(SVO_ERR_INVALID, "svo_submit_export_voxel_maps: no regions");
+    const svo_voxel_filter f = filter ? *filter : svo_voxel_filter{0, 0, {0, 0}};
+    if (f._reserved[0] != 0 || f._reserved[1] != 0) return svo_set_error(SVO_ERR_INVALID, "svo_submit_export_voxel_maps: a _reserved is not 0");
+    if ((uintptr_t)dst->points & 15) return svo_set_error(SVO_ERR_INVALID, "svo_submit_export_voxel_maps: points is not 16-byte aligned");
+    const int rc = check_slots_and_items(c, "svo_submit_export_voxel_maps", slots, [&](int i) {
+        const svo_voxel_region& r = regions[i];
+        if (r.first_point < 0 || r.point_capacity < 0 || r._reserved[0] != 0 || r._reserved[1] != 0 || r._reserved[2] != 0)
+            return svo_set_error(SVO_ERR_INVALID, "svo_submit_export_voxel_maps: region %d has a negative field or a non-zero _reserved", i);
+        if (r.point_capacity > 0 && !dst->points)
+            return svo_set_error(SVO_ERR_INVALID, "svo_submit_export_voxel_maps: region %d has a capacity, but points is NULL", i);
+        return (int)SVO_OK;
+    });
+    if (rc) return rc;
+    if (c->failed.load()) return reject_failed(c, "svo_submit_export_voxel_maps");
+    submit_shares<svo_ctx::VoxelExport>(c, slots, [&](svo_ctx::VoxelExport& e, int i, int) { e.regions.push_back(regions[i]); return true; },
+                                        [&](svo_ctx::VoxelExport& e) { e.mem = mem; e.filter = f; e.dst = *dst; });
+    return SVO_OK;
+}
+
+extern "C" int svo_export_voxel_maps(svo_ctx* c, const int* seqs, int n, const svo_voxel_region* regions, const svo_voxel_filter* filter,
+                                     const svo_voxel_dst* dst, int mem) {
+    return then_wait(c, svo_submit_export_voxel_maps(c, seqs, n, regions, filter, dst, mem));
+}
+
+extern "C" int svo_submit_clear_voxel_maps(svo_ctx* c, const int* seqs, int n) {
+    if (!c || !naming_ok(seqs, n)) return svo_set_error(SVO_ERR_INVALID, "svo_submit_clear_voxel_maps: bad arguments");
+    const NamedSlots slots = ctx_slots(c, seqs, n);
+    if (const int rc = check_slots(c, "svo_submit_clear_voxel_maps", slots)) return rc;
+    if (c->failed.load()) return reject_failed(c, "svo_submit_clear_voxel_maps");
+    submit_shares<svo_ctx::VoxelClear>(c, slots, every_slot, nothing_more);
+    return SVO_OK;
+}

@@ -1,9 +1,10 @@
-// svo_group.hpp — one group of sequences as svo_ctx.hip drives it: the opaque interface of svo_group.hip (creation,
-// settings, restarts), svo_group_step.hip (grp_new_images), svo_group_export.hip (grp_export, grp_capacity),
+// svo_group.hpp — one group of sequences as the ctx drives it (svo_ctx*.hip): the opaque interface of svo_group.hip
+// (creation, settings, restarts), svo_group_step.hip (grp_new_images), svo_group_export.hip (grp_export, grp_capacity),
 // svo_group_map.hip (grp_export_map, grp_map_size), svo_group_view.hip (grp_export_views, grp_view_bytes),
-// svo_group_scene.hip (grp_export_scenes, grp_scene_bytes), svo_group_ar.hip (grp_export_ar, grp_ar_bytes), svo_group_dense.hip (grp_export_disparity, grp_disparity_bytes), svo_group_cloud.hip (grp_export_cloud, grp_cloud_points), svo_group_voxel.hip (the voxel maps),
-// svo_group_snapshot.hip (grp_check_snapshot, grp_save, grp_load, grp_snapshot_size) and svo_group_pose.hip
-// (grp_pose_updates).
+// svo_group_scene.hip (grp_export_scenes, grp_scene_bytes), svo_group_ar.hip (grp_export_ar, grp_ar_bytes),
+// svo_group_dense.hip (grp_export_disparity, grp_disparity_bytes), svo_group_cloud.hip (grp_export_cloud,
+// grp_cloud_points), svo_group_voxel.hip (the voxel maps), svo_group_snapshot.hip (grp_check_snapshot, grp_save,
+// grp_load, grp_snapshot_size) and svo_group_pose.hip (grp_pose_updates).
 #pragma once
 
 #include <cstdint>

@@ -4,7 +4,7 @@
 // svo_group_scene.hip: the scenes; svo_group_ar.hip: the ar pictures;
 // svo_group_snapshot.hip: save and load;
 // svo_group_pose.hip: the batched pose-filter updates) and the per-sequence getters of
-// svo_ctx.hip include it. Everyone else drives a group through the opaque interface of svo_group.hpp.
+// svo_ctx_get.hip include it. Everyone else drives a group through the opaque interface of svo_group.hpp.
 //
 // Host side = bookkeeping only: image-set pool, argument blocks, the 12-state
 // pose Kalman filter (stereo_slam.cpp:296-359) and the keyframe decision. All

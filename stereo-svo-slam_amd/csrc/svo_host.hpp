@@ -1,4 +1,4 @@
-// svo_host.hpp — what the host files of the C ABI share (svo_capi*.hip, svo_ctx.hip, svo_group*.hip):
+// svo_host.hpp — what the host files of the C ABI share (svo_capi*.hip, svo_ctx*.hip, svo_group*.hip):
 // the thread-local error text, HIP_TRY, owners of HIP resources, so that every early return of
 // a creation path frees what was made before it, and the chunked upload of a tile table.
 #pragma once
