@@ -1,0 +1,589 @@
+"""The objects behind the ctx's queued jobs (svo_submit_*, include/svo_hip.h): each owns the buffers the library writes
+until the job is delivered, and queues the same job again with submit(). `Job` is what they share, the way
+csrc/svo_ctx_state.hpp is for the entries they call: the named slots, the per-slot records, the destination in pinned or
+device memory, submit() and wait(). `Frame` and `Snapshot` are the plain values of the getters and of save / load.
+StereoSlamBatch (stereo_slam.py) makes all of them. No compute happens in Python.
+"""
+import ctypes as C
+
+import numpy as np
+import torch
+
+from . import hip_lib
+from .hip_lib import SvoError, _check, lib
+
+KP_INFO_DTYPE = np.dtype([
+    ("score", "<f4"), ("level", "<i4"), ("type", "<i4"), ("keyframe_id", "<i4"),
+    ("keypoint_index", "<i4"), ("color", "u1", (3,)), ("ignore_during_refinement", "u1"),
+    ("ignore_completely", "u1"), ("ignore_temporary", "u1"), ("_pad", "u1", (2,)),
+    ("outlier_count", "<i4"), ("inlier_count", "<i4"), ("kf_inv_depth", "<f4"),
+    ("kf_variance", "<f4")], align=False)
+assert KP_INFO_DTYPE.itemsize == 44
+
+
+def int_array(values):
+    """a C int array of `values` (one element at least, so that an empty list still has an address)"""
+    return (C.c_int * max(len(values), 1))(*values)
+
+
+def named_slots(slam, seqs, explicit=False):
+    """(seqs, n, array) of a call that names slots of `slam`: seqs as a list of ints, their number and the C int array the
+    entry takes. seqs=None stands for every slot in order: (None, slam.n, None), or with explicit=True the list
+    0 .. slam.n - 1 spelled out."""
+    if seqs is None:
+        if not explicit:
+            return None, slam.n, None
+        seqs = range(slam.n)
+    seqs = [int(s) for s in seqs]
+    return seqs, len(seqs), int_array(seqs)
+
+
+def caller_memory(device, on_device):
+    """the SVO_MEM_* constant for buffers of the caller's in device (on_device) or host memory; for device memory the
+    caller's current stream is synchronised first, so that nothing of theirs is still using the tensors"""
+    if on_device:
+        torch.cuda.current_stream(device).synchronize()
+        return hip_lib.MEM_DEVICE
+    return hip_lib.MEM_HOST
+
+
+class Frame:
+    """Frame / KeyFrame (src/include/stereo_slam_types.hpp:117-131) without images."""
+
+    def __init__(self, pose, kps2d, kps3d, info):
+        self.pose = pose
+        self.kps2d = kps2d
+        self.kps3d = kps3d
+        self.info = info
+
+
+class Job:
+    """What the queued jobs share. A subclass names its slots with _name(), makes its buffers and gives _call(ctx, mem):
+    the one library call of the job."""
+
+    EXPLICIT_SLOTS = False             # seqs=None travels as NULL, not as the list 0 .. n - 1
+
+    def _name(self, slam, seqs, device=False):
+        """_slam, device_mode and the named slots (seqs, _n, _seq_arr); returns their number"""
+        self._slam, self.device_mode = slam, bool(device)
+        self.seqs, self._n, self._seq_arr = named_slots(slam, seqs, self.EXPLICIT_SLOTS)
+        return self._n
+
+    def _per_slot(self, dtype):
+        """(array, view) of one zeroed record per named slot: the array has one record at least (its address goes to
+        the library), the view exactly the named ones"""
+        a = np.zeros(max(self._n, 1), dtype)
+        return a, a[:self._n]
+
+    def _segments(self, dtype):
+        self._seg, self.segments = self._per_slot(dtype)
+
+    def _alloc(self, shape, dtype, make=torch.zeros):
+        """the destination: on the ctx's device in device mode, pinned host memory otherwise"""
+        if self.device_mode:
+            return make(shape, dtype=dtype, device=self._slam.device)
+        return make(shape, dtype=dtype, pin_memory=True)
+
+    def submit(self):
+        """queue the job (again: the same slots into the same buffers, once the previous one is delivered)"""
+        _check(self._call(self._slam._ctx, caller_memory(self._slam.device, self.device_mode)))
+        return self
+
+    def wait(self):
+        self._slam.wait()
+        return self
+
+
+class PictureJob(Job):
+    """A job of one picture per named slot: `pixels` is the whole buffer, a numpy uint8 view of pinned memory in host
+    mode, a torch uint8 tensor on the ctx's device in device mode. A subclass sets cols, rows, pitch, image_bytes and
+    channels before _pictures(), and OK: the status of a slot that has a picture."""
+
+    GRAY_IS_2D = False                 # one channel: [rows, cols, 1] (True: [rows, cols])
+
+    def _pictures(self, seg_dtype, dst_type):
+        self.capacity = self._n * self.image_bytes
+        self._segments(seg_dtype)
+        self._buf = self._alloc(max(self.capacity, 4), torch.uint8)
+        self._dst = dst_type(self._seg.ctypes.data, self._buf.data_ptr(), self.capacity)
+
+    @property
+    def pixels(self):
+        return self._buf if self.device_mode else self._buf.numpy()
+
+    def image(self, i):
+        """the image of named slot i: [rows, cols, channels] (a Views' gray8: [rows, cols]), a view of `pixels` (numpy in
+        host mode, a torch tensor in device mode); None for a slot whose status is not OK (it has no picture)"""
+        e = self.segments[i]
+        if int(e["status"]) != self.OK:
+            return None
+        lo = int(e["offset"])
+        shape = (self.rows, self.cols) + (() if self.channels == 1 and self.GRAY_IS_2D else (self.channels,))
+        return self.pixels[lo:lo + self.rows * self.pitch].reshape(shape)
+
+
+class PointJob(Job):
+    """A job that delivers hip_lib.MAP_POINT_DTYPE records: `points_buffer` is a uint8 [capacity, 16] tensor, pinned
+    memory in host mode, on the ctx's device in device mode."""
+
+    def _points(self, make=torch.zeros):
+        self.points_buffer = self._alloc((max(self.capacity, 1), hip_lib.MAP_POINT_DTYPE.itemsize), torch.uint8, make)
+
+    def _records(self, lo, n):
+        """records [lo, lo + n) as numpy (device mode copies them to the host)"""
+        a = self.points_buffer[lo:lo + n]
+        a = a.cpu().numpy() if self.device_mode else a.numpy()
+        return a.view(hip_lib.MAP_POINT_DTYPE)[:, 0]
+
+
+class Export(Job):
+    """One svo_submit_export: keeps the buffers the library writes alive. After wait(): `segments`
+    (hip_lib.EXPORT_SEGMENT_DTYPE, one per named slot) and the record arrays kps2d [capacity, 2] float32,
+    kps3d [capacity, 3] float32 and info — numpy views of pinned memory (info: KP_INFO_DTYPE [capacity]) in host
+    mode, torch tensors on the ctx's device (info: uint8 [capacity, 44]) in device mode; None for a field that
+    was not asked for. Slot i's keypoints are records [segments[i].first, + segments[i].n) of every array.
+    Unlike the other jobs' its segments live in a torch tensor, and its record arrays start uninitialised."""
+
+    def __init__(self, slam, what, seqs, device, fields):
+        n = self._name(slam, seqs, device)
+        self.what = what
+        self.capacity = n * slam.export_capacity()
+        self._seg = torch.zeros(max(n, 1) * hip_lib.EXPORT_SEGMENT_DTYPE.itemsize, dtype=torch.uint8)
+        self.segments = self._seg.numpy().view(hip_lib.EXPORT_SEGMENT_DTYPE)[:n]
+        shapes = {"kps2d": ((self.capacity, 2), torch.float32), "kps3d": ((self.capacity, 3), torch.float32),
+                  "info": ((self.capacity, KP_INFO_DTYPE.itemsize), torch.uint8)}
+        assert set(fields) <= set(shapes), fields
+        self._bufs = {name: self._alloc(*shapes[name], make=torch.empty) for name in fields}
+        self._dst = hip_lib.ExportDst(self._seg.data_ptr(), *[
+            self._bufs[name].data_ptr() if name in self._bufs else None for name in ("kps2d", "kps3d", "info")],
+            self.capacity)
+
+    def _field(self, name):
+        t = self._bufs.get(name)
+        if t is None or self.device_mode:
+            return t
+        a = t.numpy()
+        return a.view(KP_INFO_DTYPE)[:, 0] if name == "info" else a
+
+    kps2d = property(lambda self: self._field("kps2d"))
+    kps3d = property(lambda self: self._field("kps3d"))
+    info = property(lambda self: self._field("info"))
+
+    def _call(self, ctx, mem):
+        return lib().svo_submit_export(ctx, self.what, self._seq_arr, self._n, C.byref(self._dst), mem)
+
+    def frame(self, i):
+        """segment i as a Frame (what get_frame / get_keyframe return); a field that was not exported is None.
+        Device mode copies the segment's records to the host."""
+        e = self.segments[i]
+        lo, hi = int(e["first"]), int(e["first"]) + int(e["n"])
+        out = []
+        for name in ("kps2d", "kps3d", "info"):
+            a = self._field(name)
+            if a is not None:
+                a = a[lo:hi]
+                if self.device_mode:
+                    a = a.cpu().numpy()
+                    if name == "info":
+                        a = a.view(KP_INFO_DTYPE)[:, 0]
+                a = a.copy()
+            out.append(a)
+        return Frame(np.array(e["pose"], np.float32), *out)
+
+
+class MapExport(PointJob):
+    """One svo_submit_export_map: owns the buffers the library writes. `regions` (hip_lib.MAP_REGION_DTYPE, one per
+    named slot: where the slot goes and from which keyframe on) are laid out here, densely in named order, from the
+    capacities given, unless an array of them is passed. After wait(): `segments` (hip_lib.MAP_SEGMENT_DTYPE, one
+    per named slot), keyframes(i), points(i) and points_of_keyframe(i, k). The points are a numpy view
+    (hip_lib.MAP_POINT_DTYPE) of pinned memory in host mode, `points_buffer` a uint8 [capacity, 16] tensor on the
+    ctx's device in device mode (points(i) then copies the slot's records to the host). The points start
+    uninitialised, like an Export's records."""
+
+    EXPLICIT_SLOTS = True              # (`seqs` is always the list: the regions go with it, one by one)
+
+    def __init__(self, slam, seqs=None, from_keyframe=None, filter=None, device=False, point_capacity=0,
+                 keyframe_capacity=0, regions=None):
+        self._name(slam, seqs, device)
+        self.filter = hip_lib.map_filter(filter)
+        self.regions = self._per_slot(hip_lib.MAP_REGION_DTYPE)[1]
+        if regions is not None:
+            self.regions[:] = regions
+        else:
+            self.regions["from_keyframe"] = 0 if from_keyframe is None else from_keyframe
+            self.regions["point_capacity"] = point_capacity
+            self.regions["keyframe_capacity"] = keyframe_capacity
+            self._place()
+        self._segments(hip_lib.MAP_SEGMENT_DTYPE)
+        self._allocate()
+
+    def _place(self):
+        """every slot behind the one named before it"""
+        r = self.regions
+        r["first_point"] = np.cumsum(r["point_capacity"]) - r["point_capacity"]
+        r["first_keyframe_entry"] = np.cumsum(r["keyframe_capacity"]) - r["keyframe_capacity"]
+
+    def _allocate(self):
+        r = self.regions
+        self.capacity = int((r["first_point"] + r["point_capacity"]).max()) if self._n else 0
+        entries = int((r["first_keyframe_entry"] + r["keyframe_capacity"]).max()) if self._n else 0
+        self._kfs = np.zeros(max(entries, 1), hip_lib.MAP_KEYFRAME_DTYPE)
+        self._points(torch.empty)
+        self._dst = hip_lib.MapDst(self._seg.ctypes.data, self._kfs.ctypes.data if entries else None,
+                                   self.points_buffer.data_ptr() if self.capacity else None)
+
+    def _call(self, ctx, mem):
+        return lib().svo_submit_export_map(ctx, self._seq_arr, self._n, self.regions.ctypes.data_as(C.c_void_p),
+                                           C.byref(self.filter), C.byref(self._dst), mem)
+
+    def grow(self):
+        """after wait(): every slot that came back MAP_TOO_SMALL gets the capacities its segment asks for, the regions
+        are laid out again and new buffers made. False: every slot was delivered and nothing changed."""
+        small = self.segments["status"] == hip_lib.MAP_TOO_SMALL
+        if not small.any():
+            return False
+        r = self.regions
+        r["point_capacity"] = np.where(small, np.maximum(r["point_capacity"], self.segments["points_bound"]), r["point_capacity"])
+        r["keyframe_capacity"] = np.where(small, np.maximum(r["keyframe_capacity"], self.segments["n_exported"]), r["keyframe_capacity"])
+        self._place()
+        self._allocate()
+        return True
+
+    def keyframes(self, i):
+        """the svo_map_keyframe entries (hip_lib.MAP_KEYFRAME_DTYPE) of named slot i; none for a slot that was not delivered"""
+        e, r = self.segments[i], self.regions[i]
+        n = int(e["n_exported"]) if e["status"] == hip_lib.MAP_COMPLETE else 0
+        return self._kfs[int(r["first_keyframe_entry"]):int(r["first_keyframe_entry"]) + n]
+
+    def first_keyframe(self, i):
+        """svo_map_segment.first_keyframe of named slot i: its oldest resident keyframe when the job ran"""
+        return hip_lib.map_first_keyframe(self.segments[i])
+
+    def points(self, i):
+        """the kept points of named slot i (hip_lib.MAP_POINT_DTYPE), keyframe after keyframe"""
+        return self._records(int(self.regions[i]["first_point"]), int(self.segments[i]["n_points"]))
+
+    def points_of_keyframe(self, i, k):
+        """the kept points of the k-th exported keyframe of named slot i"""
+        kf = self.keyframes(i)[k]
+        return self._records(int(kf["first"]), int(kf["n"]))
+
+
+class Views(PictureJob):
+    """One svo_submit_export_views: owns the buffers the library writes. After wait(): `segments`
+    (hip_lib.VIEW_SEGMENT_DTYPE, one per named slot), image(i) and `pixels` (PictureJob). cols, rows, pitch,
+    image_bytes: the shape of every image of the job (svo_view_size); channels: 1, 3 or 4."""
+
+    OK, GRAY_IS_2D = hip_lib.VIEW_OK, True
+
+    def __init__(self, slam, what, seqs, style, device):
+        self._name(slam, seqs, device)
+        self.what, self.style = int(what), style
+        self.cols, self.rows, self.pitch, self.image_bytes = slam.view_size(style)
+        self.channels = hip_lib.PIXEL_BYTES[style.pixel]
+        self._pictures(hip_lib.VIEW_SEGMENT_DTYPE, hip_lib.ViewDst)
+
+    def _call(self, ctx, mem):
+        return lib().svo_submit_export_views(ctx, self.what, self._seq_arr, self._n, C.byref(self.style), C.byref(self._dst), mem)
+
+
+def _check_that_is_on(check):
+    """a hip_lib.StereoCheck that is on, or None: a job without one goes through the unchecked entry"""
+    return check if check is not None and check.lr else None
+
+
+class Disparities(Job):
+    """One svo_submit_export_disparity: owns the buffers the library writes. After wait(): `segments`
+    (hip_lib.DISPARITY_SEGMENT_DTYPE, one per named slot), `values` [slots, planes, rows, cols] float32 (a strided view
+    of the buffer: numpy over pinned memory in host mode, a torch tensor on the ctx's device in device mode; a slot
+    whose status is DISPARITY_NONE keeps what the buffer held) and planes(i). cols, rows, planes, image_bytes: the shape
+    of every slot of the job (svo_disparity_size). A checked job (check: a hip_lib.StereoCheck that is on) goes through
+    svo_submit_export_disparity_checked; its last plane is the lr plane, lr(i)."""
+
+    def __init__(self, slam, what, seqs, style, device, check=None):
+        n = self._name(slam, seqs, device)
+        self.what, self.style, self.check = int(what), style, _check_that_is_on(check)
+        self.cols, self.rows, self.n_planes, self.image_bytes = slam.disparity_size(style, self.check)
+        self.capacity = n * self.image_bytes
+        self._segments(hip_lib.DISPARITY_SEGMENT_DTYPE)
+        self._buf = self._alloc(max(self.capacity // 4, 4), torch.float32)
+        self._dst = hip_lib.DisparityDst(self._seg.ctypes.data, self._buf.data_ptr(), self.capacity)
+
+    @property
+    def values(self):
+        plane = self.rows * self.cols
+        v = torch.as_strided(self._buf, (self._n, self.n_planes, self.rows, self.cols), (self.image_bytes // 4, plane, self.cols, 1))
+        return v if self.device_mode else v.numpy()
+
+    def _call(self, ctx, mem):
+        if self.check is None:
+            return lib().svo_submit_export_disparity(ctx, self.what, self._seq_arr, self._n, C.byref(self.style),
+                                                     C.byref(self._dst), mem)
+        return lib().svo_submit_export_disparity_checked(ctx, self.what, self._seq_arr, self._n, C.byref(self.style),
+                                                         C.byref(self.check), C.byref(self._dst), mem)
+
+    def planes(self, i):
+        """the planes of named slot i: [planes, rows, cols], a view of `values`; None for a slot whose status is
+        DISPARITY_NONE"""
+        if int(self.segments[i]["status"]) != hip_lib.DISPARITY_OK:
+            return None
+        return self.values[i]
+
+    def lr(self, i):
+        """the lr plane of named slot i of a checked job ([rows, cols]: -1 invalid, -2 no way back, else the
+        left-right difference); None for an unchecked job or a slot whose status is DISPARITY_NONE"""
+        planes = self.planes(i)
+        return None if planes is None or self.check is None else planes[-1]
+
+
+class Clouds(PointJob):
+    """One svo_submit_export_cloud: owns the buffers the library writes. After wait(): `segments`
+    (hip_lib.CLOUD_SEGMENT_DTYPE, one per named slot), points(i) and, in the organized layout, organized(i).
+    `points_buffer`: PointJob (points(i) / organized(i) copy a device-mode slot's records to the host). cols, rows,
+    points_per_slot: the lattice of every slot of the job (svo_cloud_size). A checked job (check: a hip_lib.StereoCheck
+    that is on) goes through svo_submit_export_cloud_checked."""
+
+    def __init__(self, slam, what, seqs, style, device, check=None):
+        n = self._name(slam, seqs, device)
+        self.what, self.style, self.check = int(what), style, _check_that_is_on(check)
+        self.cols, self.rows, self.points_per_slot = slam.cloud_size(style)
+        self.capacity = n * self.points_per_slot
+        self._segments(hip_lib.CLOUD_SEGMENT_DTYPE)
+        self._points()
+        self._dst = hip_lib.CloudDst(self._seg.ctypes.data, self.points_buffer.data_ptr(), self.capacity)
+
+    def _call(self, ctx, mem):
+        if self.check is None:
+            return lib().svo_submit_export_cloud(ctx, self.what, self._seq_arr, self._n, C.byref(self.style),
+                                                 C.byref(self._dst), mem)
+        return lib().svo_submit_export_cloud_checked(ctx, self.what, self._seq_arr, self._n, C.byref(self.style),
+                                                     C.byref(self.check), C.byref(self._dst), mem)
+
+    def points(self, i):
+        """the kept points of named slot i (hip_lib.MAP_POINT_DTYPE) in row-major lattice order; None for a slot whose
+        status is CLOUD_NONE. In the organized layout: the records without CLOUD_DROPPED, a copy."""
+        e = self.segments[i]
+        if int(e["status"]) != hip_lib.CLOUD_OK:
+            return None
+        if self.style.layout == hip_lib.CLOUD_ORGANIZED:
+            r = self._records(int(e["first_point"]), self.points_per_slot)
+            return r[(r["flags"] & hip_lib.CLOUD_DROPPED) == 0]
+        return self._records(int(e["first_point"]), int(e["n_points"]))
+
+    def organized(self, i):
+        """the records of named slot i as [rows, cols] (organized layout only); None for a slot whose status is
+        CLOUD_NONE"""
+        if self.style.layout != hip_lib.CLOUD_ORGANIZED:
+            raise ValueError("organized(): the job's layout is compact")
+        e = self.segments[i]
+        if int(e["status"]) != hip_lib.CLOUD_OK:
+            return None
+        return self._records(int(e["first_point"]), self.points_per_slot).reshape(self.rows, self.cols)
+
+
+class Fusion(Job):
+    """One svo_submit_fuse_clouds: owns the info the library writes. After wait(): `info` (hip_lib.FUSE_INFO_DTYPE, one
+    per named slot). Its submit() queues the same job again (the same slots, style and stamp). Nothing of the caller's
+    goes in or out on the device: it is a host-mode job, and its submit() never synchronises a stream."""
+
+    def __init__(self, slam, what, seqs, style, check, stamp):
+        self._name(slam, seqs)
+        self.what, self.style, self.stamp, self.check = int(what), style, int(stamp), _check_that_is_on(check)
+        self._info, self.info = self._per_slot(hip_lib.FUSE_INFO_DTYPE)
+
+    def _call(self, ctx, mem):
+        return lib().svo_submit_fuse_clouds(ctx, self.what, self._seq_arr, self._n, C.byref(self.style),
+                                            None if self.check is None else C.byref(self.check), self.stamp, self._info.ctypes.data)
+
+
+class VoxelMaps(PointJob):
+    """One svo_submit_export_voxel_maps: owns the buffers the library writes. After wait(): `segments`
+    (hip_lib.VOXEL_SEGMENT_DTYPE, one per named slot) and points(i); `points_buffer`: PointJob. capacities: the records
+    each named slot's region holds, back to back."""
+
+    def __init__(self, slam, seqs, capacities, min_count, min_stamp, device):
+        n = self._name(slam, seqs, device)
+        caps = [int(c) for c in np.broadcast_to(capacities, (n,))]
+        self.regions = self._per_slot(hip_lib.VOXEL_REGION_DTYPE)[0]
+        self.regions["point_capacity"][:n] = caps
+        self.regions["first_point"][:n] = np.cumsum([0] + caps[:-1]) if n else []
+        self.regions["min_stamp"][:n] = np.broadcast_to(min_stamp, (n,))
+        self.capacity = sum(caps)
+        self._filter = hip_lib.VoxelFilter(int(min_count), 0)
+        self._segments(hip_lib.VOXEL_SEGMENT_DTYPE)
+        self._points()
+        self._dst = hip_lib.VoxelDst(self._seg.ctypes.data, self.points_buffer.data_ptr())
+
+    def _call(self, ctx, mem):
+        return lib().svo_submit_export_voxel_maps(ctx, self._seq_arr, self._n, self.regions.ctypes.data_as(C.c_void_p),
+                                                  C.byref(self._filter), C.byref(self._dst), mem)
+
+    def span(self, i):
+        """(device address, n) of named slot i's records (device mode): what a scene job's extra span takes"""
+        e = self.segments[i]
+        n = int(e["n_points"]) if int(e["status"]) == hip_lib.VOXEL_OK else 0
+        return (self.points_buffer.data_ptr() + 16 * int(e["first_point"]) if n else None, n)
+
+    def points(self, i):
+        """the records of named slot i (hip_lib.MAP_POINT_DTYPE) in key order; None unless its status is VOXEL_OK"""
+        e = self.segments[i]
+        if int(e["status"]) != hip_lib.VOXEL_OK:
+            return None
+        return self._records(int(e["first_point"]), int(e["n_points"]))
+
+
+class Scenes(PictureJob):
+    """One svo_submit_export_scenes: owns the buffers the library writes. After wait(): `segments`
+    (hip_lib.SCENE_SEGMENT_DTYPE, one per named slot), image(i) and `pixels` (PictureJob). cols, rows, pitch,
+    image_bytes: the shape of every image of the job (svo_scene_size); channels: 3 or 4. With dense or clouds
+    (StereoSlamBatch.submit_scenes) the job is svo_submit_export_scenes_clouds and `cloud_info`
+    (hip_lib.SCENE_CLOUD_INFO_DTYPE, one per named slot) says what was drawn; without them cloud_info is None."""
+
+    OK = hip_lib.SCENE_OK
+    DENSE_DEFAULTS = dict(live=True, what="frames", step=2, win=0, search_x=0, search_y=0, min_disparity=0.0, max_depth=0.0,
+                          max_mean_cost=0.0, lr_check=0.0, point_size=1)
+
+    def __init__(self, slam, seqs, style, cameras, device, dense=None, clouds=None):
+        n = self._name(slam, seqs, device)
+        self.style = style
+        self.cols, self.rows = style.cols, style.rows
+        self.pitch, self.image_bytes = hip_lib.scene_size(style)
+        self.channels = hip_lib.PIXEL_BYTES[style.pixel]
+        if isinstance(cameras, hip_lib.SceneCamera):
+            cameras = [cameras] * n                       # one view of all
+        if len(cameras) != n:
+            raise ValueError(f"{len(cameras)} cameras for {n} named slots: one per named slot, or a single one for all")
+        self._cams = (hip_lib.SceneCamera * max(n, 1))(*cameras)
+        self._pictures(hip_lib.SCENE_SEGMENT_DTYPE, hip_lib.SceneDst)
+        self.cloud_info = self._clouds = None
+        if dense is not None or clouds is not None:
+            d = dict(self.DENSE_DEFAULTS)
+            unknown = set(dense or {}) - set(d)
+            if unknown:
+                raise ValueError(f"dense: unknown keys {sorted(unknown)}")
+            d.update(dense or {})
+            if isinstance(d["what"], str):
+                d["what"] = hip_lib.EXPORT_WHAT.index(d["what"])
+            d["lr_check"] = float(d["lr_check"] or 0.0)
+            if clouds is not None and len(clouds) != n:
+                raise ValueError(f"{len(clouds)} clouds for {n} named slots: one per named slot")
+            self._info, self.cloud_info = self._per_slot(hip_lib.SCENE_CLOUD_INFO_DTYPE)
+            live = dense is not None and bool(d.pop("live"))
+            d.pop("live", None)
+            self._clouds = hip_lib.scene_clouds(live=live, extra=clouds, info=self._info, **d)
+
+    def _call(self, ctx, mem):
+        if self._clouds is None:
+            return lib().svo_submit_export_scenes(ctx, self._seq_arr, self._n, C.byref(self.style), self._cams,
+                                                  C.byref(self._dst), mem)
+        return lib().svo_submit_export_scenes_clouds(ctx, self._seq_arr, self._n, C.byref(self.style),
+                                                     C.byref(self._clouds[0]), self._cams, C.byref(self._dst), mem)
+
+
+class ArPictures(PictureJob):
+    """One svo_submit_export_ar: owns the buffers the library writes. After wait(): `segments`
+    (hip_lib.AR_SEGMENT_DTYPE, one per named slot), image(i) and `pixels` (PictureJob). cols, rows, pitch,
+    image_bytes: the shape of every image of the job (svo_ar_size); channels: 3 or 4. meshes: (vertices [V, 3],
+    triangles [T, 3][, rgb [T] or None]) each; instances: hip_lib.ArInstance, or (model of 12 floats, mesh index,
+    rgb) each; first: None (every slot shows every instance) or n + 1 ascending offsets into the instances.
+    With occlusion (StereoSlamBatch.submit_ar) the job is svo_submit_export_ar_occluded and `visibility`
+    (hip_lib.AR_VISIBILITY_DTYPE, one per named slot) says how much of the meshes is hidden; without it visibility
+    is None."""
+
+    OK = hip_lib.AR_OK
+    OCCLUSION_DEFAULTS = dict(step=4, hidden="drop", alpha=128, margin=0.0, drop_flags=0, win=0, search_x=0, search_y=0,
+                              min_disparity=0.0, max_depth=0.0, max_mean_cost=0.0, lr_check=0.0)
+
+    def __init__(self, slam, seqs, style, meshes, instances, first, device, occlusion=None):
+        n = self._name(slam, seqs, device)
+        self.style = style
+        self.cols, self.rows = slam.width, slam.height
+        self.pitch, self.image_bytes = hip_lib.ar_size(slam.cam, slam.width, slam.height, style)
+        self.channels = hip_lib.PIXEL_BYTES[style.pixel]
+        self._keep = []
+        self._meshes = (hip_lib.ArMesh * max(len(meshes), 1))()
+        for i, m in enumerate(meshes):
+            v = np.ascontiguousarray(m[0], np.float32).reshape(-1, 3)
+            t = np.ascontiguousarray(m[1], np.int32).reshape(-1, 3)
+            rgb = None if len(m) < 3 or m[2] is None else np.ascontiguousarray(m[2], np.uint32).reshape(-1)
+            if rgb is not None and len(rgb) != len(t):
+                raise ValueError(f"mesh {i}: {len(rgb)} colours for {len(t)} triangles")
+            self._keep += [v, t, rgb]
+            self._meshes[i] = hip_lib.ArMesh(v.ctypes.data if len(v) else None, t.ctypes.data if len(t) else None,
+                                             None if rgb is None else rgb.ctypes.data, len(v), len(t), 0)
+        self._n_meshes = len(meshes)
+        inst = [x if isinstance(x, hip_lib.ArInstance) else hip_lib.ar_instance(*x) for x in instances]
+        self._inst = (hip_lib.ArInstance * max(len(inst), 1))(*inst)
+        self._n_inst = len(inst)
+        self._first = None if first is None else (C.c_int * (n + 1))(*[int(f) for f in first])
+        self._pictures(hip_lib.AR_SEGMENT_DTYPE, hip_lib.ArDst)
+        self.visibility = self._occlusion = None
+        if occlusion is not None:
+            if isinstance(occlusion, hip_lib.ArOcclusion):
+                self._occlusion = hip_lib.ArOcclusion.from_buffer_copy(occlusion)
+            else:
+                d = dict(self.OCCLUSION_DEFAULTS)
+                unknown = set(occlusion) - set(d)
+                if unknown:
+                    raise ValueError(f"occlusion: unknown keys {sorted(unknown)}")
+                d.update(occlusion)
+                self._occlusion = hip_lib.ar_occlusion(True, **d)
+            self._vis, self.visibility = self._per_slot(hip_lib.AR_VISIBILITY_DTYPE)
+            self._occlusion.info = self._vis.ctypes.data
+
+    def _call(self, ctx, mem):
+        if self._occlusion is None:
+            return lib().svo_submit_export_ar(ctx, self._seq_arr, self._n, C.byref(self.style), self._meshes, self._n_meshes,
+                                              self._inst, self._first, self._n_inst, C.byref(self._dst), mem)
+        return lib().svo_submit_export_ar_occluded(ctx, self._seq_arr, self._n, C.byref(self.style),
+                                                   C.byref(self._occlusion), self._meshes, self._n_meshes, self._inst,
+                                                   self._first, self._n_inst, C.byref(self._dst), mem)
+
+
+class Snapshot:
+    """The sequence state of one slot (svo_submit_save / svo_submit_load): `host` (numpy uint8, the host part) and
+    `data` (the data part: numpy uint8, or a torch uint8 tensor on the ctx's device in device mode). Valid after
+    the wait() that follows its save. `info`: the checked header (hip_lib.SnapshotInfo). tobytes() / frombytes():
+    one self-contained blob for a file."""
+
+    def __init__(self, host, data):
+        self.host, self.data = host, data
+
+    @property
+    def device_mode(self):
+        return isinstance(self.data, torch.Tensor)
+
+    @property
+    def info(self):
+        return hip_lib.snapshot_info(self.host)
+
+    def trimmed(self):
+        """the two parts cut to the sizes the header states (a save is given capacities)"""
+        i = self.info
+        return Snapshot(self.host[:i.host_bytes], self.data[:i.data_bytes])
+
+    def tobytes(self):
+        """host part, then data part (their sizes are in the header)"""
+        t = self.trimmed()
+        data = t.data.cpu().numpy() if t.device_mode else t.data
+        return t.host.tobytes() + data.tobytes()
+
+    @classmethod
+    def frombytes(cls, blob, device=None):
+        """from tobytes(); device: a torch device for a device-mode snapshot (default: host mode)"""
+        i = hip_lib.snapshot_info(blob)
+        if i.status != hip_lib.SNAPSHOT_COMPLETE or len(blob) < i.host_bytes + i.data_bytes:
+            raise SvoError("snapshot: incomplete")
+        a = np.frombuffer(blob, np.uint8)
+        host, data = a[:i.host_bytes].copy(), a[i.host_bytes:i.host_bytes + i.data_bytes].copy()
+        return cls(host, torch.from_numpy(data).to(device) if device is not None else data)
+
+    def _buffers(self):
+        if self.device_mode:
+            assert self.data.is_cuda and self.data.dtype == torch.uint8 and self.data.is_contiguous()
+            data, n = self.data.data_ptr(), self.data.numel()
+        else:
+            assert self.data.dtype == np.uint8 and self.data.flags.c_contiguous
+            data, n = self.data.ctypes.data, self.data.size
+        assert self.host.dtype == np.uint8 and self.host.flags.c_contiguous
+        return hip_lib.SnapshotBuffers(self.host.ctypes.data, self.host.size, data if n else None, n)

@@ -5,7 +5,8 @@
 new_image(left, right, time_stamp), get_frame(), get_keyframe(), get_keyframes())
 and of the C++ class (src/include/stereo_slam.hpp:35-62: + get_trajectory,
 update_pose).  `StereoSlamBatch` drives B independent sequences through the same
-kernel launches (one svo_ctx).  No compute happens in Python.
+kernel launches (one svo_ctx).  No compute happens in Python.  The objects its
+submit_* methods return live in jobs.py and are importable from here as well.
 """
 import ctypes as C
 
@@ -14,14 +15,8 @@ import torch
 
 from . import hip_lib
 from .hip_lib import POSE_SAMPLE_CHAIN, POSE_SAMPLE_DTYPE, CameraSettings, SvoError, _check, lib
-
-KP_INFO_DTYPE = np.dtype([
-    ("score", "<f4"), ("level", "<i4"), ("type", "<i4"), ("keyframe_id", "<i4"),
-    ("keypoint_index", "<i4"), ("color", "u1", (3,)), ("ignore_during_refinement", "u1"),
-    ("ignore_completely", "u1"), ("ignore_temporary", "u1"), ("_pad", "u1", (2,)),
-    ("outlier_count", "<i4"), ("inlier_count", "<i4"), ("kf_inv_depth", "<f4"),
-    ("kf_variance", "<f4")], align=False)
-assert KP_INFO_DTYPE.itemsize == 44
+from .jobs import (KP_INFO_DTYPE, ArPictures, Clouds, Disparities, Export, Frame, Fusion, MapExport,  # noqa: F401
+                   Scenes, Snapshot, Views, VoxelMaps, caller_memory, int_array, named_slots)
 
 
 class GnTrace(C.Structure):
@@ -94,668 +89,6 @@ def pick_sia_lds_bytes(cfg, batch, n_bound, rec_cap=1 << 20, exact=True):
     return out.value
 
 
-class Frame:
-    """Frame / KeyFrame (src/include/stereo_slam_types.hpp:117-131) without images."""
-
-    def __init__(self, pose, kps2d, kps3d, info):
-        self.pose = pose
-        self.kps2d = kps2d
-        self.kps3d = kps3d
-        self.info = info
-
-
-class Export:
-    """One svo_submit_export: keeps the buffers the library writes alive. After wait(): `segments`
-    (hip_lib.EXPORT_SEGMENT_DTYPE, one per named slot) and the record arrays kps2d [capacity, 2] float32,
-    kps3d [capacity, 3] float32 and info — numpy views of pinned memory (info: KP_INFO_DTYPE [capacity]) in host
-    mode, torch tensors on the ctx's device (info: uint8 [capacity, 44]) in device mode; None for a field that
-    was not asked for. Slot i's keypoints are records [segments[i].first, + segments[i].n) of every array."""
-
-    def __init__(self, slam, what, seqs, device, fields):
-        self._slam = slam
-        self.what, self.device_mode = what, bool(device)
-        self.seqs = None if seqs is None else [int(s) for s in seqs]
-        n = slam.n if seqs is None else len(self.seqs)
-        self.capacity = n * slam.export_capacity()
-        self._seg = torch.zeros(max(n, 1) * hip_lib.EXPORT_SEGMENT_DTYPE.itemsize, dtype=torch.uint8)
-        self.segments = self._seg.numpy().view(hip_lib.EXPORT_SEGMENT_DTYPE)[:n]
-        shapes = {"kps2d": ((self.capacity, 2), torch.float32), "kps3d": ((self.capacity, 3), torch.float32),
-                  "info": ((self.capacity, KP_INFO_DTYPE.itemsize), torch.uint8)}
-        assert set(fields) <= set(shapes), fields
-        self._bufs = {}
-        for name in fields:
-            shape, dtype = shapes[name]
-            self._bufs[name] = (torch.empty(shape, dtype=dtype, device=slam.device) if device
-                                else torch.empty(shape, dtype=dtype, pin_memory=True))
-        self._dst = hip_lib.ExportDst(self._seg.data_ptr(), *[
-            self._bufs[name].data_ptr() if name in self._bufs else None for name in ("kps2d", "kps3d", "info")],
-            self.capacity)
-        self._seq_arr = None if seqs is None else (C.c_int * max(n, 1))(*self.seqs)
-        self._n = n
-
-    def _field(self, name):
-        t = self._bufs.get(name)
-        if t is None or self.device_mode:
-            return t
-        a = t.numpy()
-        return a.view(KP_INFO_DTYPE)[:, 0] if name == "info" else a
-
-    kps2d = property(lambda self: self._field("kps2d"))
-    kps3d = property(lambda self: self._field("kps3d"))
-    info = property(lambda self: self._field("info"))
-
-    def submit(self):
-        """queue the export (again: the same slots into the same buffers, once the previous one is delivered)"""
-        slam = self._slam
-        if self.device_mode:
-            torch.cuda.current_stream(slam.device).synchronize()     # (nothing of the caller's is still using the tensors)
-        _check(lib().svo_submit_export(slam._ctx, self.what, self._seq_arr, self._n, C.byref(self._dst),
-                                       hip_lib.MEM_DEVICE if self.device_mode else hip_lib.MEM_HOST))
-        return self
-
-    def wait(self):
-        self._slam.wait()
-        return self
-
-    def frame(self, i):
-        """segment i as a Frame (what get_frame / get_keyframe return); a field that was not exported is None.
-        Device mode copies the segment's records to the host."""
-        e = self.segments[i]
-        lo, hi = int(e["first"]), int(e["first"]) + int(e["n"])
-        out = []
-        for name in ("kps2d", "kps3d", "info"):
-            a = self._field(name)
-            if a is not None:
-                a = a[lo:hi]
-                if self.device_mode:
-                    a = a.cpu().numpy()
-                    if name == "info":
-                        a = a.view(KP_INFO_DTYPE)[:, 0]
-                a = a.copy()
-            out.append(a)
-        return Frame(np.array(e["pose"], np.float32), *out)
-
-
-class MapExport:
-    """One svo_submit_export_map: owns the buffers the library writes. `regions` (hip_lib.MAP_REGION_DTYPE, one per
-    named slot: where the slot goes and from which keyframe on) are laid out here, densely in named order, from the
-    capacities given, unless an array of them is passed. After wait(): `segments` (hip_lib.MAP_SEGMENT_DTYPE, one
-    per named slot), keyframes(i), points(i) and points_of_keyframe(i, k). The points are a numpy view
-    (hip_lib.MAP_POINT_DTYPE) of pinned memory in host mode, `points_buffer` a uint8 [capacity, 16] tensor on the
-    ctx's device in device mode (points(i) then copies the slot's records to the host)."""
-
-    def __init__(self, slam, seqs=None, from_keyframe=None, filter=None, device=False, point_capacity=0,
-                 keyframe_capacity=0, regions=None):
-        self._slam = slam
-        self.device_mode = bool(device)
-        self.seqs = list(range(slam.n)) if seqs is None else [int(s) for s in seqs]
-        n = self._n = len(self.seqs)
-        self.filter = hip_lib.map_filter(filter)
-        self.regions = np.zeros(max(n, 1), hip_lib.MAP_REGION_DTYPE)[:n]
-        if regions is not None:
-            self.regions[:] = regions
-        else:
-            self.regions["from_keyframe"] = 0 if from_keyframe is None else from_keyframe
-            self.regions["point_capacity"] = point_capacity
-            self.regions["keyframe_capacity"] = keyframe_capacity
-            self._place()
-        self._seq_arr = (C.c_int * max(n, 1))(*self.seqs)
-        self._seg = np.zeros(max(n, 1), hip_lib.MAP_SEGMENT_DTYPE)
-        self.segments = self._seg[:n]
-        self._allocate()
-
-    def _place(self):
-        """every slot behind the one named before it"""
-        r = self.regions
-        r["first_point"] = np.cumsum(r["point_capacity"]) - r["point_capacity"]
-        r["first_keyframe_entry"] = np.cumsum(r["keyframe_capacity"]) - r["keyframe_capacity"]
-
-    def _allocate(self):
-        r = self.regions
-        self.capacity = int((r["first_point"] + r["point_capacity"]).max()) if self._n else 0
-        entries = int((r["first_keyframe_entry"] + r["keyframe_capacity"]).max()) if self._n else 0
-        self._kfs = np.zeros(max(entries, 1), hip_lib.MAP_KEYFRAME_DTYPE)
-        shape = (max(self.capacity, 1), hip_lib.MAP_POINT_DTYPE.itemsize)
-        self.points_buffer = (torch.empty(shape, dtype=torch.uint8, device=self._slam.device) if self.device_mode
-                              else torch.empty(shape, dtype=torch.uint8, pin_memory=True))
-        self._dst = hip_lib.MapDst(self._seg.ctypes.data, self._kfs.ctypes.data if entries else None,
-                                   self.points_buffer.data_ptr() if self.capacity else None)
-
-    def submit(self):
-        """queue the export (again: the same slots into the same buffers, once the previous one is delivered)"""
-        slam = self._slam
-        if self.device_mode:
-            torch.cuda.current_stream(slam.device).synchronize()     # (nothing of the caller's is still using the tensor)
-        _check(lib().svo_submit_export_map(slam._ctx, self._seq_arr, self._n, self.regions.ctypes.data_as(C.c_void_p),
-                                           C.byref(self.filter), C.byref(self._dst),
-                                           hip_lib.MEM_DEVICE if self.device_mode else hip_lib.MEM_HOST))
-        return self
-
-    def wait(self):
-        self._slam.wait()
-        return self
-
-    def grow(self):
-        """after wait(): every slot that came back MAP_TOO_SMALL gets the capacities its segment asks for, the regions
-        are laid out again and new buffers made. False: every slot was delivered and nothing changed."""
-        small = self.segments["status"] == hip_lib.MAP_TOO_SMALL
-        if not small.any():
-            return False
-        r = self.regions
-        r["point_capacity"] = np.where(small, np.maximum(r["point_capacity"], self.segments["points_bound"]), r["point_capacity"])
-        r["keyframe_capacity"] = np.where(small, np.maximum(r["keyframe_capacity"], self.segments["n_exported"]), r["keyframe_capacity"])
-        self._place()
-        self._allocate()
-        return True
-
-    def keyframes(self, i):
-        """the svo_map_keyframe entries (hip_lib.MAP_KEYFRAME_DTYPE) of named slot i; none for a slot that was not delivered"""
-        e, r = self.segments[i], self.regions[i]
-        n = int(e["n_exported"]) if e["status"] == hip_lib.MAP_COMPLETE else 0
-        return self._kfs[int(r["first_keyframe_entry"]):int(r["first_keyframe_entry"]) + n]
-
-    def first_keyframe(self, i):
-        """svo_map_segment.first_keyframe of named slot i: its oldest resident keyframe when the job ran"""
-        return hip_lib.map_first_keyframe(self.segments[i])
-
-    def _records(self, lo, n):
-        a = self.points_buffer[lo:lo + n]
-        a = a.cpu().numpy() if self.device_mode else a.numpy()
-        return a.view(hip_lib.MAP_POINT_DTYPE)[:, 0]
-
-    def points(self, i):
-        """the kept points of named slot i (hip_lib.MAP_POINT_DTYPE), keyframe after keyframe"""
-        return self._records(int(self.regions[i]["first_point"]), int(self.segments[i]["n_points"]))
-
-    def points_of_keyframe(self, i, k):
-        """the kept points of the k-th exported keyframe of named slot i"""
-        kf = self.keyframes(i)[k]
-        return self._records(int(kf["first"]), int(kf["n"]))
-
-
-class Views:
-    """One svo_submit_export_views: owns the buffers the library writes. After wait(): `segments`
-    (hip_lib.VIEW_SEGMENT_DTYPE, one per named slot) and image(i); `pixels` is the whole buffer, a numpy uint8 view of
-    pinned memory in host mode, a torch uint8 tensor on the ctx's device in device mode. cols, rows, pitch,
-    image_bytes: the shape of every image of the job (svo_view_size); channels: 1, 3 or 4."""
-
-    def __init__(self, slam, what, seqs, style, device):
-        self._slam = slam
-        self.what, self.style, self.device_mode = int(what), style, bool(device)
-        self.seqs = None if seqs is None else [int(s) for s in seqs]
-        n = self._n = slam.n if seqs is None else len(self.seqs)
-        self.cols, self.rows, self.pitch, self.image_bytes = slam.view_size(style)
-        self.channels = hip_lib.PIXEL_BYTES[style.pixel]
-        self.capacity = n * self.image_bytes
-        self._seg = np.zeros(max(n, 1), hip_lib.VIEW_SEGMENT_DTYPE)
-        self.segments = self._seg[:n]
-        self._buf = (torch.zeros(max(self.capacity, 4), dtype=torch.uint8, device=slam.device) if device
-                     else torch.zeros(max(self.capacity, 4), dtype=torch.uint8, pin_memory=True))
-        self._dst = hip_lib.ViewDst(self._seg.ctypes.data, self._buf.data_ptr(), self.capacity)
-        self._seq_arr = None if seqs is None else (C.c_int * max(n, 1))(*self.seqs)
-
-    @property
-    def pixels(self):
-        return self._buf if self.device_mode else self._buf.numpy()
-
-    def submit(self):
-        """queue the job (again: the same slots into the same buffers, once the previous one is delivered)"""
-        slam = self._slam
-        if self.device_mode:
-            torch.cuda.current_stream(slam.device).synchronize()     # (nothing of the caller's is still using the tensor)
-        _check(lib().svo_submit_export_views(slam._ctx, self.what, self._seq_arr, self._n, C.byref(self.style),
-                                             C.byref(self._dst), hip_lib.MEM_DEVICE if self.device_mode else hip_lib.MEM_HOST))
-        return self
-
-    def wait(self):
-        self._slam.wait()
-        return self
-
-    def image(self, i):
-        """the image of named slot i: [rows, cols] (gray8) or [rows, cols, 3 | 4], a view of `pixels` (numpy in host
-        mode, a torch tensor in device mode); None for a slot whose status is VIEW_NONE"""
-        e = self.segments[i]
-        if int(e["status"]) != hip_lib.VIEW_OK:
-            return None
-        lo = int(e["offset"])
-        a = self.pixels[lo:lo + self.rows * self.pitch]
-        shape = (self.rows, self.cols) + ((self.channels,) if self.channels > 1 else ())
-        return a.reshape(shape)
-
-
-class Disparities:
-    """One svo_submit_export_disparity: owns the buffers the library writes. After wait(): `segments`
-    (hip_lib.DISPARITY_SEGMENT_DTYPE, one per named slot), `values` [slots, planes, rows, cols] float32 (a strided view
-    of the buffer: numpy over pinned memory in host mode, a torch tensor on the ctx's device in device mode; a slot
-    whose status is DISPARITY_NONE keeps what the buffer held) and planes(i). cols, rows, planes, image_bytes: the shape
-    of every slot of the job (svo_disparity_size). A checked job (check: a hip_lib.StereoCheck that is on) goes through
-    svo_submit_export_disparity_checked; its last plane is the lr plane, lr(i)."""
-
-    def __init__(self, slam, what, seqs, style, device, check=None):
-        self._slam = slam
-        self.what, self.style, self.device_mode = int(what), style, bool(device)
-        self.check = check if check is not None and check.lr else None
-        self.seqs = None if seqs is None else [int(s) for s in seqs]
-        n = self._n = slam.n if seqs is None else len(self.seqs)
-        self.cols, self.rows, self.n_planes, self.image_bytes = slam.disparity_size(style, self.check)
-        self.capacity = n * self.image_bytes
-        self._seg = np.zeros(max(n, 1), hip_lib.DISPARITY_SEGMENT_DTYPE)
-        self.segments = self._seg[:n]
-        floats = max(self.capacity // 4, 4)
-        self._buf = (torch.zeros(floats, dtype=torch.float32, device=slam.device) if device
-                     else torch.zeros(floats, dtype=torch.float32, pin_memory=True))
-        self._dst = hip_lib.DisparityDst(self._seg.ctypes.data, self._buf.data_ptr(), self.capacity)
-        self._seq_arr = None if seqs is None else (C.c_int * max(n, 1))(*self.seqs)
-
-    @property
-    def values(self):
-        plane = self.rows * self.cols
-        v = torch.as_strided(self._buf, (self._n, self.n_planes, self.rows, self.cols), (self.image_bytes // 4, plane, self.cols, 1))
-        return v if self.device_mode else v.numpy()
-
-    def submit(self):
-        """queue the job (again: the same slots into the same buffers, once the previous one is delivered)"""
-        slam = self._slam
-        if self.device_mode:
-            torch.cuda.current_stream(slam.device).synchronize()     # (nothing of the caller's is still using the tensor)
-        mem = hip_lib.MEM_DEVICE if self.device_mode else hip_lib.MEM_HOST
-        if self.check is None:
-            _check(lib().svo_submit_export_disparity(slam._ctx, self.what, self._seq_arr, self._n, C.byref(self.style),
-                                                     C.byref(self._dst), mem))
-        else:
-            _check(lib().svo_submit_export_disparity_checked(slam._ctx, self.what, self._seq_arr, self._n, C.byref(self.style),
-                                                             C.byref(self.check), C.byref(self._dst), mem))
-        return self
-
-    def wait(self):
-        self._slam.wait()
-        return self
-
-    def planes(self, i):
-        """the planes of named slot i: [planes, rows, cols], a view of `values`; None for a slot whose status is
-        DISPARITY_NONE"""
-        if int(self.segments[i]["status"]) != hip_lib.DISPARITY_OK:
-            return None
-        return self.values[i]
-
-    def lr(self, i):
-        """the lr plane of named slot i of a checked job ([rows, cols]: -1 invalid, -2 no way back, else the
-        left-right difference); None for an unchecked job or a slot whose status is DISPARITY_NONE"""
-        planes = self.planes(i)
-        return None if planes is None or self.check is None else planes[-1]
-
-
-class Clouds:
-    """One svo_submit_export_cloud: owns the buffers the library writes. After wait(): `segments`
-    (hip_lib.CLOUD_SEGMENT_DTYPE, one per named slot), points(i) and, in the organized layout, organized(i).
-    `points_buffer` is a uint8 [capacity, 16] tensor: pinned memory in host mode, on the ctx's device in device mode
-    (points(i) / organized(i) then copy the slot's records to the host). cols, rows, points_per_slot: the lattice of
-    every slot of the job (svo_cloud_size). A checked job (check: a hip_lib.StereoCheck that is on) goes through
-    svo_submit_export_cloud_checked."""
-
-    def __init__(self, slam, what, seqs, style, device, check=None):
-        self._slam = slam
-        self.what, self.style, self.device_mode = int(what), style, bool(device)
-        self.check = check if check is not None and check.lr else None
-        self.seqs = None if seqs is None else [int(s) for s in seqs]
-        n = self._n = slam.n if seqs is None else len(self.seqs)
-        self.cols, self.rows, self.points_per_slot = slam.cloud_size(style)
-        self.capacity = n * self.points_per_slot
-        self._seg = np.zeros(max(n, 1), hip_lib.CLOUD_SEGMENT_DTYPE)
-        self.segments = self._seg[:n]
-        shape = (max(self.capacity, 1), hip_lib.MAP_POINT_DTYPE.itemsize)
-        self.points_buffer = (torch.zeros(shape, dtype=torch.uint8, device=slam.device) if device
-                              else torch.zeros(shape, dtype=torch.uint8, pin_memory=True))
-        self._dst = hip_lib.CloudDst(self._seg.ctypes.data, self.points_buffer.data_ptr(), self.capacity)
-        self._seq_arr = None if seqs is None else (C.c_int * max(n, 1))(*self.seqs)
-
-    def submit(self):
-        """queue the job (again: the same slots into the same buffers, once the previous one is delivered)"""
-        slam = self._slam
-        if self.device_mode:
-            torch.cuda.current_stream(slam.device).synchronize()     # (nothing of the caller's is still using the tensor)
-        mem = hip_lib.MEM_DEVICE if self.device_mode else hip_lib.MEM_HOST
-        if self.check is None:
-            _check(lib().svo_submit_export_cloud(slam._ctx, self.what, self._seq_arr, self._n, C.byref(self.style),
-                                                 C.byref(self._dst), mem))
-        else:
-            _check(lib().svo_submit_export_cloud_checked(slam._ctx, self.what, self._seq_arr, self._n, C.byref(self.style),
-                                                         C.byref(self.check), C.byref(self._dst), mem))
-        return self
-
-    def wait(self):
-        self._slam.wait()
-        return self
-
-    def _records(self, lo, n):
-        a = self.points_buffer[lo:lo + n]
-        a = a.cpu().numpy() if self.device_mode else a.numpy()
-        return a.view(hip_lib.MAP_POINT_DTYPE)[:, 0]
-
-    def points(self, i):
-        """the kept points of named slot i (hip_lib.MAP_POINT_DTYPE) in row-major lattice order; None for a slot whose
-        status is CLOUD_NONE. In the organized layout: the records without CLOUD_DROPPED, a copy."""
-        e = self.segments[i]
-        if int(e["status"]) != hip_lib.CLOUD_OK:
-            return None
-        if self.style.layout == hip_lib.CLOUD_ORGANIZED:
-            r = self._records(int(e["first_point"]), self.points_per_slot)
-            return r[(r["flags"] & hip_lib.CLOUD_DROPPED) == 0]
-        return self._records(int(e["first_point"]), int(e["n_points"]))
-
-    def organized(self, i):
-        """the records of named slot i as [rows, cols] (organized layout only); None for a slot whose status is
-        CLOUD_NONE"""
-        if self.style.layout != hip_lib.CLOUD_ORGANIZED:
-            raise ValueError("organized(): the job's layout is compact")
-        e = self.segments[i]
-        if int(e["status"]) != hip_lib.CLOUD_OK:
-            return None
-        return self._records(int(e["first_point"]), self.points_per_slot).reshape(self.rows, self.cols)
-
-
-class Fusion:
-    """One svo_submit_fuse_clouds: owns the info the library writes. After wait(): `info` (hip_lib.FUSE_INFO_DTYPE, one
-    per named slot). Its submit() queues the same job again (the same slots, style and stamp)."""
-
-    def __init__(self, slam, what, seqs, style, check, stamp):
-        self._slam = slam
-        self.what, self.style, self.stamp = int(what), style, int(stamp)
-        self.check = check if check is not None and check.lr else None
-        self.seqs = None if seqs is None else [int(s) for s in seqs]
-        n = self._n = slam.n if seqs is None else len(self.seqs)
-        self._info = np.zeros(max(n, 1), hip_lib.FUSE_INFO_DTYPE)
-        self.info = self._info[:n]
-        self._seq_arr = None if seqs is None else (C.c_int * max(n, 1))(*self.seqs)
-
-    def submit(self):
-        _check(lib().svo_submit_fuse_clouds(self._slam._ctx, self.what, self._seq_arr, self._n, C.byref(self.style),
-                                            None if self.check is None else C.byref(self.check), self.stamp, self._info.ctypes.data))
-        return self
-
-    def wait(self):
-        self._slam.wait()
-        return self
-
-
-class VoxelMaps:
-    """One svo_submit_export_voxel_maps: owns the buffers the library writes. After wait(): `segments`
-    (hip_lib.VOXEL_SEGMENT_DTYPE, one per named slot) and points(i); `points_buffer` is a uint8 [capacity, 16] tensor,
-    pinned memory in host mode, on the ctx's device in device mode. capacities: the records each named slot's region
-    holds, back to back."""
-
-    def __init__(self, slam, seqs, capacities, min_count, min_stamp, device):
-        self._slam = slam
-        self.device_mode = bool(device)
-        self.seqs = None if seqs is None else [int(s) for s in seqs]
-        n = self._n = slam.n if seqs is None else len(self.seqs)
-        caps = [int(c) for c in np.broadcast_to(capacities, (n,))]
-        self.regions = np.zeros(max(n, 1), hip_lib.VOXEL_REGION_DTYPE)
-        self.regions["point_capacity"][:n] = caps
-        self.regions["first_point"][:n] = np.cumsum([0] + caps[:-1]) if n else []
-        self.regions["min_stamp"][:n] = np.broadcast_to(min_stamp, (n,))
-        self.capacity = sum(caps)
-        self._filter = hip_lib.VoxelFilter(int(min_count), 0)
-        self._seg = np.zeros(max(n, 1), hip_lib.VOXEL_SEGMENT_DTYPE)
-        self.segments = self._seg[:n]
-        shape = (max(self.capacity, 1), hip_lib.MAP_POINT_DTYPE.itemsize)
-        self.points_buffer = (torch.zeros(shape, dtype=torch.uint8, device=slam.device) if device
-                              else torch.zeros(shape, dtype=torch.uint8, pin_memory=True))
-        self._dst = hip_lib.VoxelDst(self._seg.ctypes.data, self.points_buffer.data_ptr())
-        self._seq_arr = None if seqs is None else (C.c_int * max(n, 1))(*self.seqs)
-
-    def submit(self):
-        slam = self._slam
-        if self.device_mode:
-            torch.cuda.current_stream(slam.device).synchronize()     # (nothing of the caller's is still using the tensor)
-        _check(lib().svo_submit_export_voxel_maps(slam._ctx, self._seq_arr, self._n, self.regions.ctypes.data_as(C.c_void_p), C.byref(self._filter),
-                                                  C.byref(self._dst), hip_lib.MEM_DEVICE if self.device_mode else hip_lib.MEM_HOST))
-        return self
-
-    def wait(self):
-        self._slam.wait()
-        return self
-
-    def span(self, i):
-        """(device address, n) of named slot i's records (device mode): what a scene job's extra span takes"""
-        e = self.segments[i]
-        n = int(e["n_points"]) if int(e["status"]) == hip_lib.VOXEL_OK else 0
-        return (self.points_buffer.data_ptr() + 16 * int(e["first_point"]) if n else None, n)
-
-    def points(self, i):
-        """the records of named slot i (hip_lib.MAP_POINT_DTYPE) in key order; None unless its status is VOXEL_OK"""
-        e = self.segments[i]
-        if int(e["status"]) != hip_lib.VOXEL_OK:
-            return None
-        lo = int(e["first_point"])
-        a = self.points_buffer[lo:lo + int(e["n_points"])]
-        a = a.cpu().numpy() if self.device_mode else a.numpy()
-        return a.view(hip_lib.MAP_POINT_DTYPE)[:, 0]
-
-
-class Scenes:
-    """One svo_submit_export_scenes: owns the buffers the library writes. After wait(): `segments`
-    (hip_lib.SCENE_SEGMENT_DTYPE, one per named slot) and image(i); `pixels` is the whole buffer, a numpy uint8 view
-    of pinned memory in host mode, a torch uint8 tensor on the ctx's device in device mode. cols, rows, pitch,
-    image_bytes: the shape of every image of the job (svo_scene_size); channels: 3 or 4. With dense or clouds
-    (StereoSlamBatch.submit_scenes) the job is svo_submit_export_scenes_clouds and `cloud_info`
-    (hip_lib.SCENE_CLOUD_INFO_DTYPE, one per named slot) says what was drawn; without them cloud_info is None."""
-
-    DENSE_DEFAULTS = dict(live=True, what="frames", step=2, win=0, search_x=0, search_y=0, min_disparity=0.0, max_depth=0.0,
-                          max_mean_cost=0.0, lr_check=0.0, point_size=1)
-
-    def __init__(self, slam, seqs, style, cameras, device, dense=None, clouds=None):
-        self._slam = slam
-        self.style, self.device_mode = style, bool(device)
-        self.seqs = None if seqs is None else [int(s) for s in seqs]
-        n = self._n = slam.n if seqs is None else len(self.seqs)
-        self.cols, self.rows = style.cols, style.rows
-        self.pitch, self.image_bytes = hip_lib.scene_size(style)
-        self.channels = hip_lib.PIXEL_BYTES[style.pixel]
-        self.capacity = n * self.image_bytes
-        if isinstance(cameras, hip_lib.SceneCamera):
-            cameras = [cameras] * n                       # one view of all
-        if len(cameras) != n:
-            raise ValueError(f"{len(cameras)} cameras for {n} named slots: one per named slot, or a single one for all")
-        self._cams = (hip_lib.SceneCamera * max(n, 1))(*cameras)
-        self._seg = np.zeros(max(n, 1), hip_lib.SCENE_SEGMENT_DTYPE)
-        self.segments = self._seg[:n]
-        self._buf = (torch.zeros(max(self.capacity, 4), dtype=torch.uint8, device=slam.device) if device
-                     else torch.zeros(max(self.capacity, 4), dtype=torch.uint8, pin_memory=True))
-        self._dst = hip_lib.SceneDst(self._seg.ctypes.data, self._buf.data_ptr(), self.capacity)
-        self._seq_arr = None if seqs is None else (C.c_int * max(n, 1))(*self.seqs)
-        self.cloud_info = self._clouds = None
-        if dense is not None or clouds is not None:
-            d = dict(self.DENSE_DEFAULTS)
-            unknown = set(dense or {}) - set(d)
-            if unknown:
-                raise ValueError(f"dense: unknown keys {sorted(unknown)}")
-            d.update(dense or {})
-            if isinstance(d["what"], str):
-                d["what"] = hip_lib.EXPORT_WHAT.index(d["what"])
-            d["lr_check"] = float(d["lr_check"] or 0.0)
-            if clouds is not None and len(clouds) != n:
-                raise ValueError(f"{len(clouds)} clouds for {n} named slots: one per named slot")
-            self._info = np.zeros(max(n, 1), hip_lib.SCENE_CLOUD_INFO_DTYPE)
-            self.cloud_info = self._info[:n]
-            live = dense is not None and bool(d.pop("live"))
-            d.pop("live", None)
-            self._clouds = hip_lib.scene_clouds(live=live, extra=clouds, info=self._info, **d)
-
-    @property
-    def pixels(self):
-        return self._buf if self.device_mode else self._buf.numpy()
-
-    def submit(self):
-        """queue the job (again: the same slots into the same buffers, once the previous one is delivered)"""
-        slam = self._slam
-        if self.device_mode:
-            torch.cuda.current_stream(slam.device).synchronize()     # (nothing of the caller's is still using the tensor)
-        mem = hip_lib.MEM_DEVICE if self.device_mode else hip_lib.MEM_HOST
-        if self._clouds is None:
-            _check(lib().svo_submit_export_scenes(slam._ctx, self._seq_arr, self._n, C.byref(self.style), self._cams,
-                                                  C.byref(self._dst), mem))
-        else:
-            _check(lib().svo_submit_export_scenes_clouds(slam._ctx, self._seq_arr, self._n, C.byref(self.style),
-                                                         C.byref(self._clouds[0]), self._cams, C.byref(self._dst), mem))
-        return self
-
-    def wait(self):
-        self._slam.wait()
-        return self
-
-    def image(self, i):
-        """the image of named slot i: [rows, cols, 3 | 4], a view of `pixels` (numpy in host mode, a torch tensor in
-        device mode); None for a slot whose status is SCENE_NONE"""
-        e = self.segments[i]
-        if int(e["status"]) != hip_lib.SCENE_OK:
-            return None
-        lo = int(e["offset"])
-        return self.pixels[lo:lo + self.rows * self.pitch].reshape(self.rows, self.cols, self.channels)
-
-
-class ArPictures:
-    """One svo_submit_export_ar: owns the buffers the library writes. After wait(): `segments`
-    (hip_lib.AR_SEGMENT_DTYPE, one per named slot) and image(i); `pixels` is the whole buffer, a numpy uint8 view of
-    pinned memory in host mode, a torch uint8 tensor on the ctx's device in device mode. cols, rows, pitch,
-    image_bytes: the shape of every image of the job (svo_ar_size); channels: 3 or 4. meshes: (vertices [V, 3],
-    triangles [T, 3][, rgb [T] or None]) each; instances: hip_lib.ArInstance, or (model of 12 floats, mesh index,
-    rgb) each; first: None (every slot shows every instance) or n + 1 ascending offsets into the instances.
-    With occlusion (StereoSlamBatch.submit_ar) the job is svo_submit_export_ar_occluded and `visibility`
-    (hip_lib.AR_VISIBILITY_DTYPE, one per named slot) says how much of the meshes is hidden; without it visibility
-    is None."""
-
-    OCCLUSION_DEFAULTS = dict(step=4, hidden="drop", alpha=128, margin=0.0, drop_flags=0, win=0, search_x=0, search_y=0,
-                              min_disparity=0.0, max_depth=0.0, max_mean_cost=0.0, lr_check=0.0)
-
-    def __init__(self, slam, seqs, style, meshes, instances, first, device, occlusion=None):
-        self._slam = slam
-        self.style, self.device_mode = style, bool(device)
-        self.seqs = None if seqs is None else [int(s) for s in seqs]
-        n = self._n = slam.n if seqs is None else len(self.seqs)
-        self.cols, self.rows = slam.width, slam.height
-        self.pitch, self.image_bytes = hip_lib.ar_size(slam.cam, slam.width, slam.height, style)
-        self.channels = hip_lib.PIXEL_BYTES[style.pixel]
-        self.capacity = n * self.image_bytes
-        self._keep = []
-        self._meshes = (hip_lib.ArMesh * max(len(meshes), 1))()
-        for i, m in enumerate(meshes):
-            v = np.ascontiguousarray(m[0], np.float32).reshape(-1, 3)
-            t = np.ascontiguousarray(m[1], np.int32).reshape(-1, 3)
-            rgb = None if len(m) < 3 or m[2] is None else np.ascontiguousarray(m[2], np.uint32).reshape(-1)
-            if rgb is not None and len(rgb) != len(t):
-                raise ValueError(f"mesh {i}: {len(rgb)} colours for {len(t)} triangles")
-            self._keep += [v, t, rgb]
-            self._meshes[i] = hip_lib.ArMesh(v.ctypes.data if len(v) else None, t.ctypes.data if len(t) else None,
-                                             None if rgb is None else rgb.ctypes.data, len(v), len(t), 0)
-        self._n_meshes = len(meshes)
-        inst = [x if isinstance(x, hip_lib.ArInstance) else hip_lib.ar_instance(*x) for x in instances]
-        self._inst = (hip_lib.ArInstance * max(len(inst), 1))(*inst)
-        self._n_inst = len(inst)
-        self._first = None if first is None else (C.c_int * (n + 1))(*[int(f) for f in first])
-        self._seg = np.zeros(max(n, 1), hip_lib.AR_SEGMENT_DTYPE)
-        self.segments = self._seg[:n]
-        self._buf = (torch.zeros(max(self.capacity, 4), dtype=torch.uint8, device=slam.device) if device
-                     else torch.zeros(max(self.capacity, 4), dtype=torch.uint8, pin_memory=True))
-        self._dst = hip_lib.ArDst(self._seg.ctypes.data, self._buf.data_ptr(), self.capacity)
-        self._seq_arr = None if seqs is None else (C.c_int * max(n, 1))(*self.seqs)
-        self.visibility = self._occlusion = None
-        if occlusion is not None:
-            if isinstance(occlusion, hip_lib.ArOcclusion):
-                self._occlusion = hip_lib.ArOcclusion.from_buffer_copy(occlusion)
-            else:
-                d = dict(self.OCCLUSION_DEFAULTS)
-                unknown = set(occlusion) - set(d)
-                if unknown:
-                    raise ValueError(f"occlusion: unknown keys {sorted(unknown)}")
-                d.update(occlusion)
-                self._occlusion = hip_lib.ar_occlusion(True, **d)
-            self._vis = np.zeros(max(n, 1), hip_lib.AR_VISIBILITY_DTYPE)
-            self._occlusion.info = self._vis.ctypes.data
-            self.visibility = self._vis[:n]
-
-    @property
-    def pixels(self):
-        return self._buf if self.device_mode else self._buf.numpy()
-
-    def submit(self):
-        """queue the job (again: the same slots into the same buffers, once the previous one is delivered)"""
-        slam = self._slam
-        if self.device_mode:
-            torch.cuda.current_stream(slam.device).synchronize()     # (nothing of the caller's is still using the tensor)
-        mem = hip_lib.MEM_DEVICE if self.device_mode else hip_lib.MEM_HOST
-        if self._occlusion is None:
-            _check(lib().svo_submit_export_ar(slam._ctx, self._seq_arr, self._n, C.byref(self.style), self._meshes, self._n_meshes,
-                                              self._inst, self._first, self._n_inst, C.byref(self._dst), mem))
-        else:
-            _check(lib().svo_submit_export_ar_occluded(slam._ctx, self._seq_arr, self._n, C.byref(self.style),
-                                                       C.byref(self._occlusion), self._meshes, self._n_meshes, self._inst,
-                                                       self._first, self._n_inst, C.byref(self._dst), mem))
-        return self
-
-    def wait(self):
-        self._slam.wait()
-        return self
-
-    def image(self, i):
-        """the image of named slot i: [rows, cols, 3 | 4], a view of `pixels` (numpy in host mode, a torch tensor in
-        device mode); None for a slot whose status is AR_NONE"""
-        e = self.segments[i]
-        if int(e["status"]) != hip_lib.AR_OK:
-            return None
-        lo = int(e["offset"])
-        return self.pixels[lo:lo + self.rows * self.pitch].reshape(self.rows, self.cols, self.channels)
-
-
-class Snapshot:
-    """The sequence state of one slot (svo_submit_save / svo_submit_load): `host` (numpy uint8, the host part) and
-    `data` (the data part: numpy uint8, or a torch uint8 tensor on the ctx's device in device mode). Valid after
-    the wait() that follows its save. `info`: the checked header (hip_lib.SnapshotInfo). tobytes() / frombytes():
-    one self-contained blob for a file."""
-
-    def __init__(self, host, data):
-        self.host, self.data = host, data
-
-    @property
-    def device_mode(self):
-        return isinstance(self.data, torch.Tensor)
-
-    @property
-    def info(self):
-        return hip_lib.snapshot_info(self.host)
-
-    def trimmed(self):
-        """the two parts cut to the sizes the header states (a save is given capacities)"""
-        i = self.info
-        return Snapshot(self.host[:i.host_bytes], self.data[:i.data_bytes])
-
-    def tobytes(self):
-        """host part, then data part (their sizes are in the header)"""
-        t = self.trimmed()
-        data = t.data.cpu().numpy() if t.device_mode else t.data
-        return t.host.tobytes() + data.tobytes()
-
-    @classmethod
-    def frombytes(cls, blob, device=None):
-        """from tobytes(); device: a torch device for a device-mode snapshot (default: host mode)"""
-        i = hip_lib.snapshot_info(blob)
-        if i.status != hip_lib.SNAPSHOT_COMPLETE or len(blob) < i.host_bytes + i.data_bytes:
-            raise SvoError("snapshot: incomplete")
-        a = np.frombuffer(blob, np.uint8)
-        host, data = a[:i.host_bytes].copy(), a[i.host_bytes:i.host_bytes + i.data_bytes].copy()
-        return cls(host, torch.from_numpy(data).to(device) if device is not None else data)
-
-    def _buffers(self):
-        if self.device_mode:
-            assert self.data.is_cuda and self.data.dtype == torch.uint8 and self.data.is_contiguous()
-            data, n = self.data.data_ptr(), self.data.numel()
-        else:
-            assert self.data.dtype == np.uint8 and self.data.flags.c_contiguous
-            data, n = self.data.ctypes.data, self.data.size
-        assert self.host.dtype == np.uint8 and self.host.flags.c_contiguous
-        return hip_lib.SnapshotBuffers(self.host.ctypes.data, self.host.size, data if n else None, n)
-
-
 class StereoSlamBatch:
     def __init__(self, camera_settings, width, height, n_sequences=1, device=0):
         if isinstance(camera_settings, dict):
@@ -823,11 +156,10 @@ class StereoSlamBatch:
             assert tuple(m.shape) == (self.height, self.width), "a rectification map has the ctx size"
         if on_dev:
             assert all(m.is_cuda and m.device == self.device for m in maps), "maps on the ctx's GPU"
-            torch.cuda.current_stream(self.device).synchronize()
             ptrs = [C.c_void_p(m.data_ptr()) for m in maps]
         else:
             ptrs = [m.ctypes.data_as(C.c_void_p) for m in maps]
-        _check(lib().svo_ctx_set_rectification(self._ctx, *ptrs, 1 if on_dev else 0))
+        _check(lib().svo_ctx_set_rectification(self._ctx, *ptrs, caller_memory(self.device, on_dev)))
 
     def set_calibration(self, left, right):
         """svo_ctx_set_calibration: set_rectification with the maps of two CameraCalibrations (the cameras behind the
@@ -914,10 +246,8 @@ class StereoSlamBatch:
                 stride = st
                 keep.append(arr)
                 dst[s] = p
-        if on_dev:
-            torch.cuda.current_stream(self.device).synchronize()
         ts = (C.c_float * self.n)(*[float(t) for t in time_stamps])
-        _check(lib().svo_new_images(self._ctx, ptrs_l, ptrs_r, stride, ts, 1 if on_dev else 0))
+        _check(lib().svo_new_images(self._ctx, ptrs_l, ptrs_r, stride, ts, caller_memory(self.device, on_dev)))
 
     def pack_images(self, lefts, rights, time_stamps, borrow=False):
         """Pre-build the argument arrays of one step (keeps Python out of a timed loop); pass the
@@ -988,7 +318,7 @@ class StereoSlamBatch:
         default: what the slots need right now (map_size: waits for the queues). regions: a
         hip_lib.MAP_REGION_DTYPE array that places every slot itself."""
         if regions is None and (point_capacity is None or keyframe_capacity is None):
-            named = list(range(self.n)) if seqs is None else [int(s) for s in seqs]
+            named = named_slots(self, seqs, explicit=True)[0]
             frm = np.broadcast_to(0 if from_keyframe is None else from_keyframe, (len(named),))
             sizes = [self.map_size(s, f) for s, f in zip(named, frm)]
             if keyframe_capacity is None:
@@ -1128,15 +458,12 @@ class StereoSlamBatch:
         return hb.value, db.value
 
     def _snapshot_call(self, fn, seqs, snaps):
-        seqs = [int(s) for s in seqs]
-        assert len(seqs) == len(snaps)
+        seqs, n, seq_arr = named_slots(self, seqs)
+        assert n == len(snaps)
         device = [s.device_mode for s in snaps]
         assert all(device) or not any(device), "snapshots of one call are all in host or all in device memory"
-        if any(device):
-            torch.cuda.current_stream(self.device).synchronize()     # (nothing of the caller's is still using the tensors)
-        arr = (hip_lib.SnapshotBuffers * max(len(seqs), 1))(*[s._buffers() for s in snaps])
-        _check(fn(self._ctx, (C.c_int * max(len(seqs), 1))(*seqs), len(seqs), arr,
-                  hip_lib.MEM_DEVICE if any(device) else hip_lib.MEM_HOST))
+        arr = (hip_lib.SnapshotBuffers * max(n, 1))(*[s._buffers() for s in snaps])
+        _check(fn(self._ctx, seq_arr, n, arr, caller_memory(self.device, any(device))))
 
     def new_snapshot(self, host_bytes, data_bytes, device=False):
         """zeroed buffers for a save (zeroed: the bytes between the planes of a device-mode data part are not
@@ -1151,7 +478,7 @@ class StereoSlamBatch:
         what the frames still queued may add; nothing is waited for then, and a save whose capacity turns out too
         small gives a header-only snapshot (info.status == SNAPSHOT_TOO_SMALL, with the sizes needed). Default:
         made here with the sizes the slots need, after a wait for the queues."""
-        seqs = list(range(self.n)) if seqs is None else [int(s) for s in seqs]
+        seqs = named_slots(self, seqs, explicit=True)[0]
         if snapshots is None:
             snapshots = [self.new_snapshot(*self.snapshot_size(s), device) for s in seqs]
         self._snapshot_call(lib().svo_submit_save, seqs, snapshots)
@@ -1176,24 +503,17 @@ class StereoSlamBatch:
     def restart(self, seqs):
         """svo_ctx_restart_sequences: the named slots end their sequences (ordered with the submitted frame
         sets, does not wait); the next frame a slot gets is frame 0 of a new sequence."""
-        seqs = [int(s) for s in ([seqs] if np.isscalar(seqs) else seqs)]
-        arr = (C.c_int * max(len(seqs), 1))(*seqs)
-        _check(lib().svo_ctx_restart_sequences(self._ctx, arr, len(seqs)))
-        for q in seqs:
-            self._fused_keyframe.pop(q, None)   # (fuse_new_keyframes: the new run's keyframes are new)
+        seqs, n, arr = named_slots(self, [seqs] if np.isscalar(seqs) else seqs)
+        _check(lib().svo_ctx_restart_sequences(self._ctx, arr, n))
+        self._forget_fused(seqs)                # (the new run's keyframes are new)
 
     # -- trimming retired keyframes ------------------------------------------------------------------------
     def trim_keyframes(self, seqs=None, below=None, wait=True):
         """svo_submit_trim_keyframes: the slots `seqs` (None: all, in order) drop their keyframes with an id below
         min(below, retired) (below: None = everything retired, an int, or one per slot), ordered with the submitted
         frame sets like restart(). wait=False: queued only. Ids never move; the storage returns to the ctx."""
-        if seqs is not None:
-            seqs = [int(s) for s in ([seqs] if np.isscalar(seqs) else seqs)]
-        n = self.n if seqs is None else len(seqs)
-        arr = None if seqs is None else (C.c_int * max(n, 1))(*seqs)
-        lim = None
-        if below is not None:
-            lim = (C.c_int * max(n, 1))(*[int(b) for b in np.broadcast_to(below, (n,))])
+        _, n, arr = named_slots(self, [seqs] if np.isscalar(seqs) else seqs)
+        lim = None if below is None else int_array([int(b) for b in np.broadcast_to(below, (n,))])
         fn = lib().svo_trim_keyframes if wait else lib().svo_submit_trim_keyframes
         _check(fn(self._ctx, arr, lim, n))
 
@@ -1240,9 +560,7 @@ class StereoSlamBatch:
             keep.append(maps)
             ptrs = [m.data_ptr() if on_dev else m.ctypes.data for m in maps]
             arr[i].left_map_x, arr[i].left_map_y, arr[i].right_map_x, arr[i].right_map_y = ptrs
-            arr[i].mem = hip_lib.MEM_DEVICE if on_dev else hip_lib.MEM_HOST
-        if any(isinstance(m[0], torch.Tensor) for m in keep):
-            torch.cuda.current_stream(self.device).synchronize()
+            arr[i].mem = caller_memory(self.device, on_dev)
         plain = [i for i in range(len(rigs)) if i not in cals]
         out = [None] * len(rigs)
         added = []
@@ -1264,7 +582,7 @@ class StereoSlamBatch:
                 added += list(ids[:n])
         except SvoError:
             if added:                             # (a mixed list is all or nothing, like each entry)
-                _check(lib().svo_ctx_remove_rigs(self._ctx, (C.c_int * len(added))(*added), len(added)))
+                _check(lib().svo_ctx_remove_rigs(self._ctx, int_array(added), len(added)))
             raise
         for i in range(len(rigs)):                # (find_rig: the full settings of every rig added here)
             cam = CameraSettings.from_buffer_copy(self.cam)
@@ -1281,17 +599,16 @@ class StereoSlamBatch:
     def remove_rigs(self, ids):
         """svo_ctx_remove_rigs: waits; SvoError (nothing removed) for rig 0 or while a slot is bound to one of them"""
         ids = [int(i) for i in ([ids] if np.isscalar(ids) else ids)]
-        _check(lib().svo_ctx_remove_rigs(self._ctx, (C.c_int * max(len(ids), 1))(*ids), len(ids)))
+        _check(lib().svo_ctx_remove_rigs(self._ctx, int_array(ids), len(ids)))
         for i in ids:
             self._rig_settings().pop(i, None)
 
     def assign_rigs(self, seqs, rigs):
         """svo_ctx_assign_rigs: slot seqs[i] ends its sequence like restart() and is bound to rig rigs[i] (ordered with
         the submitted frame sets, does not wait); its next frame is frame 0 of a new sequence under that rig."""
-        seqs, rigs = [int(s) for s in seqs], [int(r) for r in rigs]
-        assert len(seqs) == len(rigs)
-        n = len(seqs)
-        _check(lib().svo_ctx_assign_rigs(self._ctx, (C.c_int * max(n, 1))(*seqs), (C.c_int * max(n, 1))(*rigs), n))
+        (_, n, seq_arr), rigs = named_slots(self, seqs), [int(r) for r in rigs]
+        assert n == len(rigs)
+        _check(lib().svo_ctx_assign_rigs(self._ctx, seq_arr, int_array(rigs), n))
 
     def slot_rig(self, seq):
         """svo_ctx_get_slot_rig: (rig id, CameraSettings the slot tracks with)"""
@@ -1330,16 +647,18 @@ class StereoSlamBatch:
         _check(lib().svo_drop_finished_runs(self._ctx, seq))
 
     # -- voxel maps: the slots' dense clouds fused into one bounded map per slot -----------------------------------
+    def _forget_fused(self, seqs):
+        """fuse_new_keyframes fuses the newest keyframe of these slots (None: all) again"""
+        for s in (range(self.n) if seqs is None else seqs):
+            self._fused_keyframe.pop(s, None)
+
     def set_voxel_maps(self, voxel, log2_capacity=20, seqs=None, drop_flags=0):
         """svo_ctx_set_voxel_maps: every slot of `seqs` (None: all) gets an empty voxel map of edge `voxel` and
         1 << log2_capacity entries (10 .. 26); voxel=None takes the maps away. Waits for the queues."""
-        n = self.n if seqs is None else len(seqs)
-        arr = None if seqs is None else (C.c_int * max(n, 1))(*[int(s) for s in seqs])
+        seqs, n, arr = named_slots(self, seqs)
         params = None if voxel is None else C.byref(hip_lib.voxel_params(voxel, log2_capacity, drop_flags))
         _check(lib().svo_ctx_set_voxel_maps(self._ctx, arr, n, params))
-        named = range(self.n) if seqs is None else [int(s) for s in seqs]
-        for s in named:
-            self._fused_keyframe.pop(s, None)
+        self._forget_fused(seqs)
 
     def voxel_map_info(self, seq=0):
         """svo_get_voxel_map_info as a dict (waits); None for a slot without a map"""
@@ -1371,7 +690,7 @@ class StereoSlamBatch:
         """fuse_clouds("last_keyframes") of only those slots whose newest keyframe changed since this method last fused
         them (the bookkeeping is here, on the host: it waits for the queues to read the keyframe counts). Returns the
         Fusion, or None when no slot has a new keyframe."""
-        named = list(range(self.n)) if seqs is None else [int(s) for s in seqs]
+        named = named_slots(self, seqs, explicit=True)[0]
         self.wait()
         fresh = []
         for s in named:
@@ -1393,7 +712,7 @@ class StereoSlamBatch:
         slot; nothing is waited for then, and a slot that outgrew it comes back VOXEL_TOO_SMALL); default: what the
         maps hold right now (waits for the queues). Returns a VoxelMaps, valid after its wait()."""
         if capacities is None:
-            named = range(self.n) if seqs is None else [int(s) for s in seqs]
+            named = named_slots(self, seqs, explicit=True)[0]
             capacities = [(self.voxel_map_info(s) or {"n_voxels": 0})["n_voxels"] for s in named]
         return VoxelMaps(self, seqs, capacities, min_count, min_stamp, device).submit()
 
@@ -1403,11 +722,9 @@ class StereoSlamBatch:
 
     def clear_voxel_maps(self, seqs=None, wait=True):
         """svo_submit_clear_voxel_maps: queued; the maps of the slots `seqs` (None: all) become empty"""
-        n = self.n if seqs is None else len(seqs)
-        arr = None if seqs is None else (C.c_int * max(n, 1))(*[int(s) for s in seqs])
+        seqs, n, arr = named_slots(self, seqs)
         _check(lib().svo_submit_clear_voxel_maps(self._ctx, arr, n))
-        for s in (range(self.n) if seqs is None else [int(x) for x in seqs]):
-            self._fused_keyframe.pop(s, None)
+        self._forget_fused(seqs)
         if wait:
             self.wait()
 
@@ -1504,15 +821,13 @@ class StereoSlamBatch:
         what was submitted so far; nothing is waited for. samples_per_seq[i]: the POSE_SAMPLE_DTYPE records of slot
         seqs[i] in the order they are applied (an empty array or None: the slot is left alone). Returns the filtered
         poses, float32 [total, 6] in sample order, valid after wait()."""
-        seqs = None if seqs is None else [int(s) for s in seqs]
-        n = self.n if seqs is None else len(seqs)
+        _, n, seq_arr = named_slots(self, seqs)
         assert len(samples_per_seq) == n
         per = [np.zeros(0, POSE_SAMPLE_DTYPE) if a is None else np.ascontiguousarray(a, POSE_SAMPLE_DTYPE).reshape(-1)
                for a in samples_per_seq]
-        counts = (C.c_int * max(n, 1))(*[len(a) for a in per])
+        counts = int_array([len(a) for a in per])
         samples = np.concatenate(per) if per else np.zeros(0, POSE_SAMPLE_DTYPE)
         filtered = np.zeros((len(samples), 6), np.float32)
-        seq_arr = None if seqs is None else (C.c_int * max(n, 1))(*seqs)
         _check(lib().svo_submit_pose_updates(self._ctx, seq_arr, counts, n, samples.ctypes.data if len(samples) else None,
                                              filtered.ctypes.data if len(samples) else None))
         return filtered                            # (the worker writes into it: the caller keeps it until wait())
@@ -1593,67 +908,55 @@ class StereoSlam(StereoSlamBatch):
                 super().set_keyframe_window(self._window)
         self.new_images([left], [right], [time_stamp])
 
-    def get_image(self, what="frames", **kw):
-        """the image of the current frame (or, what="last_keyframes", of the newest keyframe) as a numpy array
-        (export_views of the one slot: plane, level, pixel, markers, ...); None when there is none"""
+    def _get(self, export, pick, *args, **kw):
+        """what the get_* share: None without a ctx; else the host-mode job `export` of the one slot, and a copy of what
+        `pick` takes from it (None when there is none)"""
         if self._ctx is None:
             return None
         kw["device"] = False
-        img = self.export_views(what, None, **kw).image(0)
-        return None if img is None else img.copy()
+        out = pick(export(*args, **kw))
+        return None if out is None else out.copy()
+
+    def get_image(self, what="frames", **kw):
+        """the image of the current frame (or, what="last_keyframes", of the newest keyframe) as a numpy array
+        (export_views of the one slot: plane, level, pixel, markers, ...); None when there is none"""
+        return self._get(self.export_views, lambda job: job.image(0), what, None, **kw)
 
     def get_disparity(self, what="frames", **kw):
         """the dense disparity (or, value="depth", depth) map of the current frame (or, what="last_keyframes", of the
         newest keyframe) as a numpy array [planes, rows, cols] (export_disparity of the one slot: value, step, win,
         search_x, search_y, cost); None when there is none"""
-        if self._ctx is None:
-            return None
-        kw["device"] = False
-        planes = self.export_disparity(what, None, **kw).planes(0)
-        return None if planes is None else planes.copy()
+        return self._get(self.export_disparity, lambda job: job.planes(0), what, None, **kw)
 
     def get_cloud(self, what="frames", **kw):
         """the dense coloured point cloud of the current frame (or, what="last_keyframes", of the newest keyframe) as
         a numpy array of hip_lib.MAP_POINT_DTYPE (export_cloud of the one slot: step, frame, layout, the filter, ...;
         layout="organized": [rows, cols]); None when there is none"""
-        if self._ctx is None:
-            return None
-        kw["device"] = False
-        job = self.export_cloud(what, None, **kw)
-        pts = job.organized(0) if job.style.layout == hip_lib.CLOUD_ORGANIZED else job.points(0)
-        return None if pts is None else pts.copy()
+        def pick(job):
+            return job.organized(0) if job.style.layout == hip_lib.CLOUD_ORGANIZED else job.points(0)
+        return self._get(self.export_cloud, pick, what, None, **kw)
 
     def get_voxel_map(self, **kw):
         """the slot's voxel map as a numpy array of hip_lib.MAP_POINT_DTYPE in key order (export_voxel_maps of the one
         slot: min_count, min_stamp); None without a map"""
-        if self._ctx is None:
-            return None
-        kw["device"] = False
-        pts = self.export_voxel_maps(None, **kw).points(0)
-        return None if pts is None else pts.copy()
+        return self._get(self.export_voxel_maps, lambda job: job.points(0), None, **kw)
 
     def get_scene(self, camera="front", **kw):
         """the viewer's 3-D picture of the map as a numpy array [rows, cols, 3 | 4] (export_scenes of the one slot:
         camera, cols, rows, pixel, show, ...; dense=dict(...) draws the current frame's dense cloud into it); None before
         the first frame"""
-        if self._ctx is None:
-            return None
-        kw["device"] = False
-        img = self.export_scenes(None, camera=camera, **kw).image(0)
-        return None if img is None else img.copy()
+        return self._get(self.export_scenes, lambda job: job.image(0), None, camera=camera, **kw)
 
     def get_ar(self, objects, **kw):
         """the AR demo's picture of the current frame as a numpy array [height, width, 3 | 4] (export_ar of the one
         slot: pixel, light, ambient, near). objects: (vertices, triangles, model of 12 floats, rgb) each, e.g.
         (*hip_lib.ar_box(0.2), hip_lib.ar_model(hip_lib.AR_AT), 0xc08040). occlusion = dict(...) (submit_ar) hides
         the objects behind the frame's dense stereo depth. None before the first frame"""
-        if self._ctx is None:
-            return None
-        kw["device"] = False
         meshes = [(v, t) for v, t, _, _ in objects]
         instances = [(model, i, rgb) for i, (_, _, model, rgb) in enumerate(objects)]
-        job = self.export_ar(meshes, instances, None, **kw)
-        # (with occlusion: the picture's hip_lib.AR_VISIBILITY_DTYPE record, for whoever wants the counts)
-        self.ar_visibility = None if job.visibility is None else job.visibility[0].copy()
-        img = job.image(0)
-        return None if img is None else img.copy()
+
+        def pick(job):
+            # (with occlusion: the picture's hip_lib.AR_VISIBILITY_DTYPE record, for whoever wants the counts)
+            self.ar_visibility = None if job.visibility is None else job.visibility[0].copy()
+            return job.image(0)
+        return self._get(self.export_ar, pick, meshes, instances, None, **kw)
