@@ -1352,6 +1352,87 @@ int svo_export_cloud_checked(svo_ctx *ctx, int what, const int *seqs, int n, con
 int svo_cloud_points_checked(svo_handle *h, int n, const svo_cloud_src *src, const int64_t *first, const svo_cloud_style *style,
                              const svo_stereo_check *check, svo_map_point *points, int32_t *counts);
 
+/* ---- sgm: semi-global aggregation and sub-pixel values for dense maps ------------
+ * In "dense" a lattice point decides alone (winner takes all), so a flat wall gives noise, and its disparities are
+ * whole numbers but for the tie mean. Semi-global matching cures both: the costs of "dense" are kept as a volume,
+ * penalties for disparity changes are aggregated along four scanline paths over the lattice, the winner is taken from
+ * the sum over the paths, and a parabola through the winner's neighbours gives the fraction. All of it is integer
+ * arithmetic up to the last four float operations, and it is held to the bit like everything else here.
+ *
+ * Statement. The lattice, the boxes and the candidates (k, j) are those of "dense". D = search_x + 1 <= 64. For a
+ * valid point count = mw and area = tw * th; for an invalid point count = 0.
+ *   Cost volume  j < count:        C(p, j) = min(cost_cap, (min over k < mh of SSD(k, j)) / area), the exact integer
+ *                                  SSD and the exact floor division
+ *                count <= j < D:   C(p, j) = cost_cap
+ *                invalid point:    C(p, j) = 0 for every j
+ *   Paths        four directions r over the lattice: (+1, 0), (-1, 0), (0, +1), (0, -1) in (ix, iy).
+ *                p - r outside the lattice:  L_r(p, j) = C(p, j)
+ *                otherwise, with P = L_r(p - r, .) over all D entries and m = min over j of P(j):
+ *                  L_r(p, j) = C(p, j) + min(P(j), P(j - 1) + p1 [j > 0], P(j + 1) + p1 [j < D - 1], m + p2) - m
+ *                S(p, j) = sum over r of L_r(p, j). L_r <= cost_cap + p2, so S <= 4 * (cost_cap + p2) fits 16 bits.
+ *   Value        an invalid point (count = 0) is -1, with SVO_DENSE_DEPTH 0.
+ *                j0 = the smallest j < count with the least S(p, j);  d = (float)j0.
+ *                With subpixel = 1 and 0 < j0 < count - 1, with the ints a = S(j0 - 1), b = S(j0), c = S(j0 + 1):
+ *                  d = (float)j0 + (float)(a - c) / (float)(2 * (a - 2 * b + c))
+ *                (the denominator is >= 2 because j0 is the first minimum; two exact conversions, one division and
+ *                one addition, each rounded once to float).
+ *                disparity = d < 0.5f ? 0.5f : d;  depth = baseline / disparity.
+ *                With cost = 1 the second plane holds (float)S(p, j0), or -1 at an invalid point.
+ * There are no defaults for p1, p2 and cost_cap in this ABI. */
+typedef struct svo_sgm_params {     /* 32 bytes; copied at submit */
+    int32_t paths;                  /* 4 (8 is reserved for the diagonals and rejected for now) */
+    int32_t p1, p2;                 /* 1 <= p1 <= p2 */
+    int32_t cost_cap;               /* >= 1; 4 * (cost_cap + p2) <= 65535 */
+    int32_t subpixel;               /* 0 / 1 */
+    int32_t _reserved[3];           /* 0 */
+} svo_sgm_params;
+
+/* The SGM mode of the disparity job: queued exactly as svo_submit_export_disparity is, and it rejects what that
+ * rejects; also (SVO_ERR_INVALID, nothing queued) a NULL sgm, a bad field of it, and an effective search_x > 63. The
+ * segments, the shape of a slot's planes and image_bytes are those of svo_disparity_size for the style; the value and
+ * cost planes hold the values of the statement above. Inside the ctx it is the disparity job carrying the params, not
+ * another kind of queue entry. There is no cross-check of an SGM job yet.
+ * Memory: the sums, the volume and the count plane of a slot (2 * cols * rows * D * 2 bytes and cols * rows * 2, each
+ * rounded up to 256) live in a block of the group, made by the group's first SGM job and replaced when outgrown
+ * (svo_memory.device_bytes). The slots of a job go through it in chunks of max(1, 512 MiB / slot bytes) slots (the
+ * diagnostic SVO_SGM_CHUNK_SLOTS lowers it); one slot always fits. A 752 x 480 slot at step 1 with D = 61 needs 44 MB
+ * for the volume and as much for the sums, at step 4 2.75 MB each. */
+int svo_submit_export_disparity_sgm(svo_ctx *ctx, int what, const int *seqs, int n, const svo_disparity_style *style,
+                                    const svo_sgm_params *sgm, const svo_disparity_dst *dst, int mem);
+int svo_export_disparity_sgm(svo_ctx *ctx, int what, const int *seqs, int n, const svo_disparity_style *style,
+                             const svo_sgm_params *sgm, const svo_disparity_dst *dst, int mem);   /* submit + wait */
+
+/* Stage entries, over the handle's workspace; each complete on return. src, style and the lattice as in
+ * svo_dense_disparity, but style->search_x <= 63 (SVO_ERR_INVALID beyond it).
+ *
+ * svo_dense_cost_volume: the cost volume alone. Pair i writes its volume, uint16 [rows][cols][D] (j fastest, dense), at
+ * (char *)volumes + volume_offset[i] and its count plane, uint16 [rows][cols], at (char *)volumes + count_offset[i]
+ * (host arrays, >= 0, multiples of 2; volumes: device, 2-byte aligned). This layout is part of the ABI. Exactly these
+ * bytes are written. cost_cap: 1 .. 65535. style->value and cost are checked and not used. */
+int svo_dense_cost_volume(svo_handle *h, int n, const svo_dense_src *src, const svo_disparity_style *style, int cost_cap,
+                          const int64_t *volume_offset, const int64_t *count_offset, uint16_t *volumes);
+/* svo_sgm_aggregate: paths and value rule over the caller's volumes in that layout (costs of any kind, census for
+ * one). volumes[i] (host array of device pointers, 2-byte aligned): volume i; an entry above sgm->cost_cap is read as
+ * cost_cap. counts: NULL, or a host array of device pointers to the count planes (a NULL entry, or counts == NULL:
+ * every point has D candidates; a count above D is read as D). value: SVO_DENSE_*, cost: 0 / 1. The planes of volume i
+ * go to (char *)values + offset[i] as in svo_dense_disparity. cols, rows >= 1, 1 <= D <= 64. The sums S of a chunk of
+ * volumes live in the handle's workspace; a call is chunked so that a chunk's S stays within 256 MiB (the diagnostic
+ * SVO_SGM_CHUNK_SLOTS lowers the volumes per chunk), one volume always fits, and a single volume whose S needs more
+ * than 1 GiB is answered with SVO_ERR_CAPACITY. */
+typedef struct svo_sgm_shape {      /* 16 bytes */
+    int32_t cols, rows, D;
+    float   baseline;               /* SVO_DENSE_DEPTH: z = baseline / disparity */
+} svo_sgm_shape;
+int svo_sgm_aggregate(svo_handle *h, int n, const svo_sgm_shape *shapes, const uint16_t *const *volumes,
+                      const uint16_t *const *counts, int value, int cost, const svo_sgm_params *sgm, const int64_t *offset,
+                      float *values);
+/* svo_dense_disparity_sgm: the two together for pairs of any sizes: svo_dense_disparity's arguments and planes (shape
+ * and bytes per pair as svo_disparity_size gives them for the style), the values those of the statement. The volume,
+ * the count plane and S of a chunk of pairs live in the handle's workspace, chunked as above (volume, counts and S of a
+ * chunk within 512 MiB); a single pair whose volume needs more than 1 GiB is answered with SVO_ERR_CAPACITY. */
+int svo_dense_disparity_sgm(svo_handle *h, int n, const svo_dense_src *src, const int64_t *offset,
+                            const svo_disparity_style *style, const svo_sgm_params *sgm, float *values);
+
 /* ---- scene clouds: dense clouds ("clouds", "cross-check") drawn in the scene picture ------------
  * A scene job can draw, beside the elements above, svo_map_point records: the dense cloud of each named slot's frame
  * or newest keyframe (the LIVE LAYER), records of the caller's in device memory (the EXTRA SPAN), or both.

@@ -259,6 +259,131 @@ __global__ __launch_bounds__(DENSE_THREADS) void dense_disparity_kernel(const st
     }
 }
 
+// The cost volume of include/svo_hip.h ("sgm"): dense_disparity_kernel's tile, staging, sliding column sums and prefix,
+// with the candidates walked j outer, dy inner, so that the state of a lattice row is one running minimum over dy (the
+// exact int32 SSD, never a float). After the dy loop the point's lane divides by its area, caps and stores one uint16
+// per row at [iy][ix][j]; after the last j it stores the count plane. Of an image exactly vol[0 .. rows * cols * D) and
+// count[0 .. rows * cols) are written.
+__global__ __launch_bounds__(DENSE_THREADS) void dense_cost_volume_kernel(const CostImage* __restrict__ images, const DenseParams p,
+                                                                          const int cost_cap) {
+    __shared__ __attribute__((aligned(16))) uint8_t s_l[DENSE_L_ROWS * DENSE_THREADS];
+    __shared__ __attribute__((aligned(16))) uint8_t s_r[DENSE_R_ROWS * DENSE_R_COLS];
+    __shared__ int s_p[2][DENSE_BAND][DENSE_THREADS];
+    __shared__ int s_t[2][DENSE_BAND][DENSE_THREADS / 64];
+    const auto im = G(images)[blockIdx.y];
+    const int W = im.w, H = im.h, step = p.step, win = p.win, sx = p.search_x, sy = p.search_y;
+    const int cols = W / step, rows = H / step, D = sx + 1;
+    const int wb = win / 2, wa = (win + 1) / 2;
+    const int span = dense_span(win), band = dense_band(step, win, p.band);
+    const int ntx = (W + span - 1) / span, nty = (rows + band - 1) / band;
+    if ((int)blockIdx.x >= ntx * nty) return;
+    const int tx = (int)blockIdx.x % ntx, ty = (int)blockIdx.x / ntx;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int X0 = tx * span - wb;
+    const int iy0 = ty * band, nrow = min(band, rows - iy0);
+    const int yc0 = iy0 * step + step / 2;
+    const int yl0 = max(0, yc0 - wb);
+
+    for (int i = tid; i < DENSE_L_ROWS * DENSE_THREADS; i += DENSE_THREADS) {
+        const int yy = yl0 + i / DENSE_THREADS, xx = X0 + i % DENSE_THREADS;
+        s_l[i] = (yy < H && xx >= 0 && xx < W) ? G(im.left)[(int64_t)yy * im.left_stride + xx] : (uint8_t)0;
+    }
+    for (int i = tid; i < DENSE_R_ROWS * DENSE_R_COLS; i += DENSE_THREADS) {
+        const int yy = yl0 - sy + i / DENSE_R_COLS, xx = X0 + i % DENSE_R_COLS;
+        s_r[i] = (yy >= 0 && yy < H && xx >= 0 && xx < W) ? G(im.right)[(int64_t)yy * im.right_stride + xx] : (uint8_t)0;
+    }
+
+    const int x = X0 + tid, xl = x - step / 2;
+    const bool in_span = tid >= wb && tid < wb + span && xl >= 0 && xl % step == 0 && xl / step < cols;
+    const int ix = in_span ? xl / step : 0;
+    const int x11 = max(0, x - wb), x12 = min(W - 1, x + wa), x22 = min(W - 1, x + wa + sx);
+    const int tw = x12 - x11, mw = (x22 - x11) - tw + 1;
+    const bool xok = !(x12 <= 0 || x11 >= W - 1 || x22 <= 0) && tw > 0 && mw > 0;
+    const int pa = in_span ? min(max(x11 - X0, 0), DENSE_THREADS) : 0;
+    const int pb = in_span ? min(max(x12 - X0, 0), DENSE_THREADS) : 0;
+
+    int row_lo[DENSE_BAND], row_hi[DENSE_BAND], dy_lo[DENSE_BAND], dy_hi[DENSE_BAND];
+#pragma unroll
+    for (int r = 0; r < DENSE_BAND; r++) {
+        const int y = yc0 + min(r, nrow - 1) * step;
+        const int y11 = max(0, y - wb), y12 = min(H, y + wa);
+        const int y21 = max(0, y - wb - sy), y22 = min(H - 1, y + wa + sy);
+        const int th = y12 - y11, mh = (y22 - y21) - th + 1;
+        const bool yok = r < nrow && !(y12 <= 0 || y11 >= H - 1 || y22 <= 0 || y21 >= H - 1) && th > 0 && mh > 0;
+        row_lo[r] = y11 - yl0; row_hi[r] = y12 - yl0;
+        dy_lo[r] = y21 - y11; dy_hi[r] = yok ? dy_lo[r] + mh - 1 : dy_lo[r] - 1;
+    }
+    __syncthreads();
+
+    SVO_GP(uint16_t) vol = G(im.vol);
+    const int ia = max(pa - 1, 0), ib = max(pb - 1, 0), wva = ia >> 6, wvb = ib >> 6;
+    int buf = 0;
+    for (int j = 0; j <= sx; j++) {
+        int best[DENSE_BAND];
+#pragma unroll
+        for (int r = 0; r < DENSE_BAND; r++) best[r] = 0x7fffffff;
+        for (int dy = -sy; dy <= sy; dy++) {
+            const uint8_t* lp = s_l + tid;
+            const uint8_t* rp = s_r + (dy + sy) * DENSE_R_COLS + tid + j;
+            int Cr[DENSE_BAND];
+            int C = 0, lo = 0, hi = 0;
+#pragma unroll
+            for (int r = 0; r < DENSE_BAND; r++) {
+#pragma unroll 8
+                for (const int to = row_hi[r]; hi < to; hi++) {
+                    const int d = (int)rp[hi * DENSE_R_COLS] - (int)lp[hi * DENSE_THREADS];
+                    C += d * d;
+                }
+#pragma unroll 4
+                for (const int to = row_lo[r]; lo < to; lo++) {
+                    const int d = (int)rp[lo * DENSE_R_COLS] - (int)lp[lo * DENSE_THREADS];
+                    C -= d * d;
+                }
+                Cr[r] = C;
+            }
+#pragma unroll
+            for (int r = 0; r < DENSE_BAND; r++) Cr[r] = dense_wave_prefix(Cr[r]);
+#pragma unroll
+            for (int r = 0; r < DENSE_BAND; r++) {
+                s_p[buf][r][tid] = Cr[r];
+                if (lane == 63) s_t[buf][r][wave] = Cr[r];
+            }
+            __syncthreads();
+#pragma unroll
+            for (int r = 0; r < DENSE_BAND; r++) {
+                if (dy < dy_lo[r] || dy > dy_hi[r]) continue;   // (the same for every lane)
+                const int t0 = s_t[buf][r][0], t1 = s_t[buf][r][1], t2 = s_t[buf][r][2];
+                const int fa = pa > 0 ? s_p[buf][r][ia] + (wva > 0 ? t0 : 0) + (wva > 1 ? t1 : 0) + (wva > 2 ? t2 : 0) : 0;
+                const int fb = pb > 0 ? s_p[buf][r][ib] + (wvb > 0 ? t0 : 0) + (wvb > 1 ? t1 : 0) + (wvb > 2 ? t2 : 0) : 0;
+                best[r] = min(best[r], fb - fa);
+            }
+            buf ^= 1;
+        }
+        if (in_span) {
+#pragma unroll
+            for (int r = 0; r < DENSE_BAND; r++) {
+                if (r >= nrow) continue;
+                const bool valid = xok && dy_hi[r] >= dy_lo[r];
+                const int area = max(tw * (row_hi[r] - row_lo[r]), 1);
+                const int c = valid ? (j < mw ? min(cost_cap, best[r] / area) : cost_cap) : 0;
+                vol[((int64_t)(iy0 + r) * cols + ix) * D + j] = (uint16_t)c;
+            }
+        }
+    }
+    if (!in_span) return;
+    SVO_GP(uint16_t) count = G(im.count);
+#pragma unroll
+    for (int r = 0; r < DENSE_BAND; r++) {
+        if (r >= nrow) continue;
+        count[(int64_t)(iy0 + r) * cols + ix] = (uint16_t)(xok && dy_hi[r] >= dy_lo[r] ? mw : 0);
+    }
+}
+
+void launch_dense_cost_volume(const CostImage* d_images, int n, int tiles, const DenseParams& p, int cost_cap, hipStream_t stream) {
+    if (n <= 0 || tiles <= 0) return;
+    hipLaunchKernelGGL(dense_cost_volume_kernel, dim3(tiles, n), dim3(DENSE_THREADS), 0, stream, d_images, p, cost_cap);
+}
+
 void launch_dense(const DenseImage* d_images, int n, int tiles, const DenseParams& p, hipStream_t stream) {
     if (n <= 0 || tiles <= 0) return;
     hipLaunchKernelGGL(dense_disparity_kernel<false>, dim3(tiles, n), dim3(DENSE_THREADS), 0, stream, d_images, p);

@@ -136,6 +136,32 @@ extern "C" int svo_export_disparity_checked(svo_ctx* c, int what, const int* seq
     return then_wait(c, svo_submit_export_disparity_checked(c, what, seqs, n, style, check, dst, mem));
 }
 
+// the disparity job in its SGM mode (include/svo_hip.h, "sgm"): the same queue entry carrying the params
+extern "C" int svo_submit_export_disparity_sgm(svo_ctx* c, int what, const int* seqs, int n, const svo_disparity_style* style,
+                                               const svo_sgm_params* sgm, const svo_disparity_dst* dst, int mem) {
+    if (!c || !dst || !dst->segments || !what_ok(what) || !mem_ok(mem) || !naming_ok(seqs, n))
+        return svo_set_error(SVO_ERR_INVALID, "svo_submit_export_disparity_sgm: bad arguments (what %d, mem %d)", what, mem);
+    if (const int rc = grp_check_disparity_style(c->g0(), style, nullptr)) return rc;
+    if (const int rc = grp_check_disparity_sgm(c->g0(), style, sgm)) return rc;
+    if (!dst->values || ((uintptr_t)dst->values & 15))
+        return svo_set_error(SVO_ERR_INVALID, "svo_submit_export_disparity_sgm: values is NULL or not 16-byte aligned");
+    const NamedSlots slots = ctx_slots(c, seqs, n);
+    if (const int rc = check_slots(c, "svo_submit_export_disparity_sgm", slots)) return rc;
+    if (const int rc = check_capacity("svo_submit_export_disparity_sgm", slots.n, grp_disparity_bytes(c->g0(), style, nullptr), dst->capacity, "bytes"))
+        return rc;
+    if (c->failed.load()) return reject_failed(c, "svo_submit_export_disparity_sgm");
+    submit_shares<svo_ctx::DisparityExport>(c, slots, every_slot, [&](svo_ctx::DisparityExport& e) {
+        e.what = what; e.mem = mem; e.style = *style; e.dst = *dst;
+        e.has_sgm = true; e.sgm = *sgm;
+    });
+    return SVO_OK;
+}
+
+extern "C" int svo_export_disparity_sgm(svo_ctx* c, int what, const int* seqs, int n, const svo_disparity_style* style,
+                                        const svo_sgm_params* sgm, const svo_disparity_dst* dst, int mem) {
+    return then_wait(c, svo_submit_export_disparity_sgm(c, what, seqs, n, style, sgm, dst, mem));
+}
+
 extern "C" int svo_submit_export_cloud_checked(svo_ctx* c, int what, const int* seqs, int n, const svo_cloud_style* style,
                                                const svo_stereo_check* check, const svo_cloud_dst* dst, int mem) {
     if (const int rc = drop_check_that_is_off(&check, true, "svo_submit_export_cloud_checked")) return rc;

@@ -85,7 +85,12 @@ struct svo_ctx {
     };
     template <typename Style, typename Dst>
     struct CheckedExport : ImageExport<Style, Dst>, StereoCheck {};
-    using DisparityExport = CheckedExport<svo_disparity_style, svo_disparity_dst>;
+    // (svo_submit_export_disparity_sgm: the same job carrying the SGM params)
+    struct DisparityExport : CheckedExport<svo_disparity_style, svo_disparity_dst> {
+        bool has_sgm = false;
+        svo_sgm_params sgm{};
+        const svo_sgm_params* sgm_ptr() const { return has_sgm ? &sgm : nullptr; }
+    };
     using CloudExport = CheckedExport<svo_cloud_style, svo_cloud_dst>;
     // the group's share of an svo_submit_export_scenes: the camera of each slot
     struct SceneExport : SlotShare {

@@ -109,7 +109,10 @@ int grp_check_ar_occlusion(const svo_group* g, const svo_ar_occlusion* occlusion
 // (grp_check_disparity_style). check: the cross-check of a checked job (checked too), or null. Delivered on return. A
 // failed group rejects it.
 int grp_export_disparity(svo_group* g, int what, int mem, const int* seqs, const int* seg, int n, int seq0,
-                         const svo_disparity_style* style, const svo_stereo_check* check, const svo_disparity_dst* dst);
+                         const svo_disparity_style* style, const svo_stereo_check* check, const svo_sgm_params* sgm,
+                         const svo_disparity_dst* dst);
+// what svo_submit_export_disparity_sgm checks beside the style: the params, and an effective search_x <= 63
+int grp_check_disparity_sgm(const svo_group* g, const svo_disparity_style* style, const svo_sgm_params* sgm);
 // what svo_submit_export_disparity checks of a style, and the image_bytes of a checked one (they read only what never
 // changes in a group)
 int grp_check_disparity_style(const svo_group* g, const svo_disparity_style* style, const svo_stereo_check* check);

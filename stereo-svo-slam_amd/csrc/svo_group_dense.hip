@@ -14,6 +14,7 @@ using namespace svo;
 namespace {
 
 constexpr size_t LR_STAGING_BYTES = (size_t)256 << 20;   // the reverse planes of one chunk of a checked job at most (one slot always fits)
+constexpr size_t SGM_STAGING_BYTES = (size_t)512 << 20;  // the sums, volumes and count planes of one chunk of an SGM job at most (likewise)
 
 // the style is checked and the ctx's size has a lattice point at its step
 int check_style(const svo_camera_settings* cam, int width, int height, const svo_disparity_style* style, const char* who, DenseParams* out) {
@@ -25,7 +26,54 @@ int check_style(const svo_camera_settings* cam, int width, int height, const svo
     return SVO_OK;
 }
 
+// The SGM mode of the job (include/svo_hip.h, "sgm"): per chunk of delivered slots whose sums, volumes and count planes
+// fit the group's d_sgm block, the cost-volume launch and the two launches of the paths, which write the slots' planes.
+// The two image tables share the group's argument blocks, half each, and fill and launch in step. The stream orders a
+// chunk's launches before the next chunk's, so the chunks share the block.
+int export_sgm(svo_group* c, const std::vector<DenseImage>& images, const DenseParams& params, const SgmParams& sp, int cols, int rows) {
+    if (images.empty()) return SVO_OK;
+    const int D = params.search_x + 1;
+    const size_t volume = sgm_volume_bytes(cols, rows, D), slot = 2 * volume + sgm_count_bytes(cols, rows);
+    // (SVO_SGM_CHUNK_SLOTS: fewer slots per chunk, so that tests reach the chunked path)
+    const size_t chunk = std::min(images.size(), table_tiles("SVO_SGM_CHUNK_SLOTS", std::max<size_t>(1, SGM_STAGING_BYTES / slot)));
+    if (const int rc = c->d_sgm.reserve(c, chunk * slot)) return rc;
+    DenseParams dp = params;
+    int grid = 0;
+    auto costs = group_tile_table<CostImage>(c, "SVO_DENSE_TABLE_IMAGES", [&](const CostImage* d, int m, hipStream_t s) {
+        launch_dense_cost_volume(d, m, grid, dp, sp.cost_cap, s);
+    });
+    auto sums = group_tile_table<SgmImage>(c, "SVO_DENSE_TABLE_IMAGES", [&](const SgmImage* d, int m, hipStream_t s) { launch_sgm(d, m, cols, rows, sp, s); });
+    const size_t half = c->args.bytes / 2 / 256 * 256;
+    costs.cap = sums.cap = std::min({costs.cap, half / sizeof(CostImage), half / sizeof(SgmImage), DENSE_MAX_IMAGES, chunk});
+    sums.h = reinterpret_cast<SgmImage*>(reinterpret_cast<uint8_t*>(sums.h) + half);
+    sums.d = reinterpret_cast<SgmImage*>(reinterpret_cast<uint8_t*>(sums.d) + half);
+    if (costs.cap < 1) return svo_set_error(SVO_ERR_CAPACITY, "svo_submit_export_disparity_sgm: the argument blocks hold no image table");
+    dense_plan(dp, (long long)dense_tiles(params, c->width, c->height) * (long long)std::min(images.size(), costs.cap));
+    grid = dense_tiles(dp, c->width, c->height);
+    for (const DenseImage& im : images) {
+        if (costs.m == costs.cap) {                        // (a chunk is full: its launches go first)
+            if (const int rc = costs.launch(true)) return rc;
+            if (const int rc = sums.launch(true)) return rc;
+        }
+        uint8_t* const at = c->d_sgm.p + costs.m * slot;   // sums | volume | count plane
+        uint16_t* const vol = reinterpret_cast<uint16_t*>(at + volume);
+        uint16_t* const count = reinterpret_cast<uint16_t*>(at + 2 * volume);
+        if (const int rc = costs.add(CostImage{im.left, im.right, vol, count, im.left_stride, im.right_stride, im.w, im.h})) return rc;
+        if (const int rc = sums.add(SgmImage{vol, count, reinterpret_cast<uint16_t*>(at), im.out, cols, rows, D, im.baseline})) return rc;
+    }
+    if (const int rc = costs.launch(false)) return rc;
+    return sums.launch(false);
+}
+
 }  // namespace
+
+int grp_check_disparity_sgm(const svo_group* c, const svo_disparity_style* style, const svo_sgm_params* sgm) {
+    const char* who = "svo_submit_export_disparity_sgm";
+    DenseParams p;
+    if (const int rc = check_style(&c->cam, c->width, c->height, style, who, &p)) return rc;
+    if (p.search_x + 1 > SGM_MAX_D) return svo_set_error(SVO_ERR_INVALID, "%s: search_x %d: at most %d with a cost volume", who, p.search_x, SGM_MAX_D - 1);
+    return sgm_check_params(sgm, who, nullptr);
+}
 
 extern "C" int svo_disparity_size_checked(const svo_camera_settings* cam, int width, int height, const svo_disparity_style* style,
                                           const svo_stereo_check* check, int* cols, int* rows, int* planes, int64_t* image_bytes) {
@@ -68,8 +116,10 @@ int64_t grp_disparity_bytes(const svo_group* c, const svo_disparity_style* style
 // chunk of delivered slots whose reverse planes fit the group's d_lr block, runs the reverse search and the check,
 // which appends the lr plane and masks and converts the value plane in place. The stream orders a chunk's check before
 // the next chunk's reverse search, so the chunks share the block without a wait of the host.
+// An SGM job (sgm != null; never checked) leaves the image table empty and delivers through export_sgm.
 int grp_export_disparity(svo_group* c, int what, int mem, const int* seqs, const int* seg, int n, int seq0,
-                         const svo_disparity_style* style, const svo_stereo_check* check, const svo_disparity_dst* dst) {
+                         const svo_disparity_style* style, const svo_stereo_check* check, const svo_sgm_params* sgm,
+                         const svo_disparity_dst* dst) {
     if (const int rc = job_begin(c, "svo_submit_export_disparity")) return rc;
     hipStream_t st = c->stream.get();
     const bool host = mem == SVO_MEM_HOST;
@@ -79,6 +129,13 @@ int grp_export_disparity(svo_group* c, int what, int mem, const int* seqs, const
     if (const int rc = lr_check_parse(check, false, "svo_submit_export_disparity", &lr)) return rc;
     const LrParams lr_params{params.value, params.step, lr.max_lr_diff};
     if (lr.on) params.value = SVO_DENSE_DISPARITY;
+    SgmParams sgm_params{};
+    if (sgm) {
+        if (const int rc = sgm_check_params(sgm, "svo_submit_export_disparity_sgm", &sgm_params)) return rc;
+        sgm_params.value = params.value;
+        sgm_params.cost = params.cost;
+    }
+    std::vector<DenseImage> sgm_images;                    // (an SGM job: the delivered slots, for export_sgm)
     int cols, rows, planes; int64_t image_bytes;
     dense_shape(params, c->width, c->height, &cols, &rows, &planes, &image_bytes, lr.on);
     const int64_t used = (int64_t)planes * cols * rows * 4;   // bytes of a slot's planes
@@ -115,9 +172,15 @@ int grp_export_disparity(svo_group* c, int what, int mem, const int* seqs, const
         e.status = SVO_DISPARITY_OK;
         shown[i] = 1;
         uint8_t* out = host ? c->d_dense.p + (int64_t)i * image_bytes : reinterpret_cast<uint8_t*>(dst->values) + e.offset;
-        if (const int rc = table.add(DenseImage{l.data, r.data, reinterpret_cast<float*>(out), l.stride, r.stride, l.w, l.h, q.cam.baseline, 0}))
-            return rc;
+        const DenseImage image{l.data, r.data, reinterpret_cast<float*>(out), l.stride, r.stride, l.w, l.h, q.cam.baseline, 0};
+        if (sgm) {
+            sgm_images.push_back(image);
+            continue;
+        }
+        if (const int rc = table.add(image)) return rc;
     }
+    if (sgm)
+        if (const int rc = export_sgm(c, sgm_images, params, sgm_params, cols, rows)) return rc;
     if (table.m == (size_t)std::count(shown.begin(), shown.end(), 1)) {   // (one launch: sized by what it holds)
         dense_plan(params, (long long)tiles * (long long)table.m);
         tiles = dense_tiles(params, c->width, c->height);

@@ -362,6 +362,9 @@ struct svo_group {
     // cross-check (a checked grp_export_disparity or grp_export_cloud): the reverse planes of one chunk of a job, made
     // by the first checked job and replaced when outgrown
     svo::GrowBlock<uint8_t> d_lr;
+    // semi-global aggregation (an SGM grp_export_disparity): the sums, volumes and count planes of one chunk of a job,
+    // made by the first SGM job and replaced when outgrown
+    svo::GrowBlock<uint8_t> d_sgm;
     // voxel maps (svo_group_voxel.hip): a map per slot that has one (svo_ctx_set_voxel_maps; empty until then) with
     // the host mirror of its header; the records of one chunk of a fuse job and its tables (maps | headers | spans,
     // mirrored); the tile offsets, the sort staging and in host mode the records of an export. Each block is made by

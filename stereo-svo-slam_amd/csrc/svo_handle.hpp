@@ -1,5 +1,5 @@
-// svo_handle.hpp — what the four files of the stage-level C API share (svo_capi.hip, svo_capi_tables.hip,
-// svo_capi_check.hip, svo_capi_voxel.hip; nothing else includes it): the handle, its device ring for argument blocks, its grow-only
+// svo_handle.hpp — what the five files of the stage-level C API share (svo_capi.hip, svo_capi_tables.hip,
+// svo_capi_check.hip, svo_capi_voxel.hip, svo_capi_sgm.hip; nothing else includes it): the handle, its device ring for argument blocks, its grow-only
 // workspaces and the check of a caller's keypoint planes.
 #pragma once
 
@@ -48,6 +48,7 @@ struct svo_handle {
     svo_workspace scene_cloud_ws;   // svo_render_scene_clouds: the key planes of a call, the plane table, then the span table
     svo_workspace ar_ws;            // svo_render_ar: the draws, image records, work list and screen records of a call, then the tile table
     svo_workspace dense_ws;         // svo_dense_disparity: the image table
+    svo_workspace sgm_ws;           // svo_sgm_aggregate, svo_dense_disparity_sgm: the two image tables of a chunk, then its sums, volumes and count planes
     svo_workspace cloud_ws;         // svo_cloud_points: the two image tables of a chunk, then its planes, tile counts and pose matrices
     svo_workspace voxel_ws;         // svo_voxel_fuse: the map table, the maps' headers, the span table; svo_voxel_extract: the tile offsets
     svo_workspace voxel_sort_ws;    // svo_voxel_extract: the (key, entry) pairs before and after the sort and the sort's temporary storage

@@ -412,6 +412,43 @@ constexpr int LR_TILE = 1024;
 constexpr int lr_tiles(int64_t points) { return (int)((points + LR_TILE - 1) / LR_TILE); }
 void launch_lr_check(const LrImage* d_images, int n, int tiles, const LrParams& p, hipStream_t stream);
 
+// ------------------------------------------------------------ semi-global aggregation (dense.hip's cost-volume kernel, sgm.hip)
+// One image pair of a cost-volume launch: the two gray planes as in DenseImage; vol: uint16 [rows][cols][D] with
+// D = search_x + 1 (j fastest, dense); count: uint16 [rows][cols]. Both 2-byte aligned.
+struct CostImage {
+    const uint8_t* left;
+    const uint8_t* right;
+    uint16_t* vol;
+    uint16_t* count;
+    int left_stride, right_stride, w, h;
+};
+// the cost volumes of n images (<= DENSE_MAX_IMAGES): launch_dense's grid over the same images and params (value and
+// cost of p are not read), search_x <= 63
+void launch_dense_cost_volume(const CostImage* d_images, int n, int tiles, const DenseParams& p, int cost_cap, hipStream_t stream);
+// One volume of an aggregation: vol and count as above (count null: every point has D candidates), sum: the block of
+// S, uint16 [rows][cols][D], written by the first launch and read by the second; out: the value plane and, with cost,
+// the cost plane behind it (cols x rows floats each); the baseline of SVO_DENSE_DEPTH.
+struct SgmImage {
+    const uint16_t* vol;
+    const uint16_t* count;
+    uint16_t* sum;
+    float* out;
+    int cols, rows, D;
+    float baseline;
+};
+// a checked svo_sgm_params with the value and cost of the style
+struct SgmParams {
+    int p1, p2, cost_cap, subpixel, value, cost;
+};
+int sgm_check_params(const svo_sgm_params* sgm, const char* who, SgmParams* out);
+constexpr int SGM_MAX_D = 64;
+// the bytes of one volume or one block of S (a multiple of 256), and of one count plane
+inline size_t sgm_volume_bytes(int cols, int rows, int D) { return ((size_t)cols * (size_t)rows * (size_t)D * 2 + 255) / 256 * 256; }
+inline size_t sgm_count_bytes(int cols, int rows) { return ((size_t)cols * (size_t)rows * 2 + 255) / 256 * 256; }
+// the four paths and the value rule of n volumes (<= DENSE_MAX_IMAGES): two launches, rows then columns, ordered by
+// the stream; max_cols / max_rows: the largest lattice of the table
+void launch_sgm(const SgmImage* d_images, int n, int max_cols, int max_rows, const SgmParams& p, hipStream_t stream);
+
 // ------------------------------------------------------------ dense point clouds (cloud.hip)
 // One image of a launch: the left plane (the gray of a record), the disparity and cost planes of a search over its
 // lattice (cols x rows floats each, dense: dense_disparity_kernel's with cost), where its records start, its tile

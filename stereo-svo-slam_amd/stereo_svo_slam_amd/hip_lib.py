@@ -46,6 +46,8 @@ SYMBOLS = (
     "svo_disparity_size_checked", "svo_submit_export_disparity_checked", "svo_export_disparity_checked",
     "svo_dense_disparity_checked", "svo_submit_export_cloud_checked", "svo_export_cloud_checked",
     "svo_cloud_points_checked",
+    "svo_submit_export_disparity_sgm", "svo_export_disparity_sgm",
+    "svo_dense_cost_volume", "svo_sgm_aggregate", "svo_dense_disparity_sgm",
     "svo_scene_size", "svo_scene_look_at", "svo_scene_frustum", "svo_submit_export_scenes", "svo_export_scenes",
     "svo_render_scene",
     "svo_submit_export_scenes_clouds", "svo_export_scenes_clouds", "svo_render_scene_clouds",
@@ -441,6 +443,28 @@ assert C.sizeof(StereoCheck) == 32
 def stereo_check(lr=True, max_lr_diff=0.0):
     """a StereoCheck; max_lr_diff of 0: report only (the lr plane; a cloud needs a tolerance > 0)"""
     return StereoCheck(int(bool(lr)), float(max_lr_diff))
+
+
+class SgmParams(C.Structure):
+    """svo_sgm_params (include/svo_hip.h, "sgm"): the penalties, the cost cap and the sub-pixel switch of an SGM search."""
+    _fields_ = [("paths", C.c_int32), ("p1", C.c_int32), ("p2", C.c_int32), ("cost_cap", C.c_int32), ("subpixel", C.c_int32),
+                ("_reserved", C.c_int32 * 3)]
+
+
+class SgmShape(C.Structure):
+    """svo_sgm_shape (include/svo_hip.h): the lattice and candidates of one volume of svo_sgm_aggregate."""
+    _fields_ = [("cols", C.c_int32), ("rows", C.c_int32), ("D", C.c_int32), ("baseline", C.c_float)]
+
+
+assert (C.sizeof(SgmParams), C.sizeof(SgmShape)) == (32, 16)
+# what sgm=True stands for in the Python layers (the C ABI has no defaults): chosen by tools/sgm_sweep.py over the
+# numpy statement, profiles/sgm_defaults.json
+SGM_DEFAULTS = dict(p1=64, p2=256, cost_cap=4095, subpixel=True)
+
+
+def sgm_params(p1, p2, cost_cap, subpixel=True):
+    """an SgmParams of four paths"""
+    return SgmParams(4, int(p1), int(p2), int(cost_cap), int(bool(subpixel)))
 
 
 def disparity_size(cam, width, height, style, check=None):
@@ -1271,6 +1295,38 @@ class Handle:
         a raw device address) the planes of pair i start at. check: a StereoCheck (svo_dense_disparity_checked: the
         lr plane follows the others), or None. Complete on return."""
         self.dense_disparity_packed(self.pack_dense(srcs, offsets), style, values, check)
+
+    def dense_cost_volume(self, srcs, style, cost_cap, volume_offsets, count_offsets, volumes):
+        """svo_dense_cost_volume: the uint16 cost volume [rows, cols, search_x + 1] and count plane [rows, cols] of every
+        pair of srcs (as in dense_disparity) at the bytes volume_offsets[i] / count_offsets[i] of `volumes` (a uint16
+        or int16 device tensor, or a raw device address). Complete on return."""
+        n, arr, _, _ = self.pack_dense(srcs, volume_offsets)
+        vo = (C.c_int64 * max(n, 1))(*[int(o) for o in volume_offsets])
+        co = (C.c_int64 * max(n, 1))(*[int(o) for o in count_offsets])
+        p = volumes.data_ptr() if isinstance(volumes, torch.Tensor) else int(volumes)
+        _check(lib().svo_dense_cost_volume(self._h, n, arr, C.byref(style), int(cost_cap), vo, co, C.c_void_p(p)))
+
+    def sgm_aggregate(self, shapes, volumes, counts, value, cost, sgm, offsets, values):
+        """svo_sgm_aggregate: the four paths and the value rule over the caller's volumes. shapes: per volume (cols,
+        rows, D, baseline); volumes: per volume a device tensor or raw device address of uint16 [rows, cols, D];
+        counts: None, or per volume a device tensor / address of uint16 [rows, cols] or None; value: DENSE_*; cost:
+        the second plane; sgm: an SgmParams; offsets[i]: the byte of `values` (a float32 device tensor or raw device
+        address) the planes of volume i start at. Complete on return."""
+        n = len(shapes)
+        addr = lambda v: 0 if v is None else (v.data_ptr() if isinstance(v, torch.Tensor) else int(v))
+        sh = (SgmShape * max(n, 1))(*[SgmShape(int(c), int(r), int(d), float(b)) for c, r, d, b in shapes])
+        vols = (C.c_void_p * max(n, 1))(*[addr(v) for v in volumes])
+        cnts = None if counts is None else (C.c_void_p * max(n, 1))(*[addr(v) for v in counts])
+        offs = (C.c_int64 * max(n, 1))(*[int(o) for o in offsets])
+        _check(lib().svo_sgm_aggregate(self._h, n, sh, vols, cnts, int(value), int(bool(cost)), C.byref(sgm), offs,
+                                       C.c_void_p(addr(values))))
+
+    def dense_disparity_sgm(self, srcs, offsets, style, sgm, values):
+        """svo_dense_disparity_sgm: dense_disparity with semi-global aggregation and sub-pixel values (sgm: an
+        SgmParams; style.search_x <= 63). Complete on return."""
+        packed = self.pack_dense(srcs, offsets)
+        p = values.data_ptr() if isinstance(values, torch.Tensor) else int(values)
+        _check(lib().svo_dense_disparity_sgm(self._h, packed[0], packed[1], packed[2], C.byref(style), C.byref(sgm), C.c_void_p(p)))
 
     def pack_cloud(self, srcs, first):
         """the argument arrays of cloud_points, built once (keeps Python out of a timed loop)"""

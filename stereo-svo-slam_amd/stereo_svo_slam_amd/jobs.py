@@ -298,11 +298,15 @@ class Disparities(Job):
     of the buffer: numpy over pinned memory in host mode, a torch tensor on the ctx's device in device mode; a slot
     whose status is DISPARITY_NONE keeps what the buffer held) and planes(i). cols, rows, planes, image_bytes: the shape
     of every slot of the job (svo_disparity_size). A checked job (check: a hip_lib.StereoCheck that is on) goes through
-    svo_submit_export_disparity_checked; its last plane is the lr plane, lr(i)."""
+    svo_submit_export_disparity_checked; its last plane is the lr plane, lr(i). An SGM job (sgm: a hip_lib.SgmParams)
+    goes through svo_submit_export_disparity_sgm: the same planes with semi-global aggregation and sub-pixel values;
+    together with a check that is on it raises ValueError."""
 
-    def __init__(self, slam, what, seqs, style, device, check=None):
+    def __init__(self, slam, what, seqs, style, device, check=None, sgm=None):
         n = self._name(slam, seqs, device)
-        self.what, self.style, self.check = int(what), style, _check_that_is_on(check)
+        self.what, self.style, self.check, self.sgm = int(what), style, _check_that_is_on(check), sgm
+        if self.check is not None and sgm is not None:
+            raise ValueError("a disparity job is checked or SGM, not both")
         self.cols, self.rows, self.n_planes, self.image_bytes = slam.disparity_size(style, self.check)
         self.capacity = n * self.image_bytes
         self._segments(hip_lib.DISPARITY_SEGMENT_DTYPE)
@@ -316,6 +320,9 @@ class Disparities(Job):
         return v if self.device_mode else v.numpy()
 
     def _call(self, ctx, mem):
+        if self.sgm is not None:
+            return lib().svo_submit_export_disparity_sgm(ctx, self.what, self._seq_arr, self._n, C.byref(self.style),
+                                                         C.byref(self.sgm), C.byref(self._dst), mem)
         if self.check is None:
             return lib().svo_submit_export_disparity(ctx, self.what, self._seq_arr, self._n, C.byref(self.style),
                                                      C.byref(self._dst), mem)

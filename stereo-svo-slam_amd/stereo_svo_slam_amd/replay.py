@@ -27,7 +27,8 @@ as binary PPM files, DIR/000000_keyframe.ppm (the last keyframe, a marker per ke
 current frame): the gray image the tracker worked on, which with --gpu-rectify / --gpu-ingest only the GPU has seen.
 The text overlay and the x2 resize of the window are not drawn.
 --dump-disparity DIR [--disparity-step S] [--disparity-depth] writes per frame DIR/000000_disparity.npy: the dense
-disparity (or depth) map of the frame's rectified pair at every S-th pixel. With --disparity-lr D the map is
+disparity (or depth) map of the frame's rectified pair at every S-th pixel. With --disparity-sgm P1,P2[,CAP] the map is
+aggregated semi-globally and the file stacks value and aggregated cost. With --disparity-lr D the map is
 cross-checked left-right and the file is [3, rows, cols]: the value (invalid where the two searches differ by more than
 D; D = 0 only reports), the cost and the lr plane. --cloud-lr D drops such points from the clouds of --dump-cloud.
 --dump-cloud DIR [--cloud-step S] [--cloud-max-depth Z] writes, whenever the newest keyframe changes,
@@ -424,7 +425,7 @@ class Replay:
                  ar_box=AR_BOX, ar_at=hip_lib.AR_AT, dump_disparity=None, disparity_step=4, disparity_depth=False,
                  dump_cloud=None, cloud_step=4, cloud_max_depth=0.0, disparity_lr=None, cloud_lr=None, scene_dense=None,
                  scene_dense_lr=None, scene_dense_max_depth=0.0, scene_accumulate=0, dump_dense_map=None, dense_map_voxel=None,
-                 dense_map_log2=20, dense_map_min_count=0, scene_fused=None, ar_occlusion=None):
+                 dense_map_log2=20, dense_map_min_count=0, scene_fused=None, ar_occlusion=None, disparity_sgm=None):
         """fast=False keeps the library default: the reference-order Gauss-Newton (bit-exact traces).
         rectify_maps = (left maps, right maps): the frames fed are raw and are rectified on the GPU.
         calibration = (left, right) CameraCalibrations: the same, with the maps built on the GPU as well.
@@ -451,7 +452,9 @@ class Replay:
         in the world frame (get_cloud of "last_keyframes" at the lattice cloud_step, points deeper than cloud_max_depth
         dropped; 0: none dropped) as kfNNNNNN_cloud.ply (write_ply), likewise.
         disparity_lr: None, or the tolerance of the left-right cross-check of dump_disparity (0: report only); the file
-        is then [3, rows, cols]: value, cost, lr. cloud_lr: None, or the tolerance (> 0) of the cross-check of dump_cloud.
+        is then [3, rows, cols]: value, cost, lr. disparity_sgm: None, or (p1, p2[, cost_cap]) of semi-global aggregation
+        for dump_disparity (cost_cap: hip_lib.SGM_DEFAULTS'); the file is then [2, rows, cols]: value, aggregated cost;
+        not together with disparity_lr. cloud_lr: None, or the tolerance (> 0) of the cross-check of dump_cloud.
         dump_dense_map: a PLY file that receives, at finish(), the slot's voxel map (get_voxel_map with
         dense_map_min_count): every new keyframe's dense cloud (cloud_step, cloud_lr, cloud_max_depth) is fused into a map
         of edge dense_map_voxel and 1 << dense_map_log2 entries kept inside the ctx. scene_fused = V: dump_scene draws
@@ -464,6 +467,12 @@ class Replay:
         self.dump_disparity, self.disparity_step, self.disparity_depth = dump_disparity, int(disparity_step), bool(disparity_depth)
         self.dump_cloud, self.cloud_step, self.cloud_max_depth, self._cloud_kf = dump_cloud, int(cloud_step), float(cloud_max_depth), -1
         self.disparity_lr = None if disparity_lr is None else float(disparity_lr)
+        self.disparity_sgm = None
+        if disparity_sgm is not None:
+            if disparity_lr is not None:
+                raise ValueError("disparity_sgm and disparity_lr exclude each other")
+            p = [int(v) for v in disparity_sgm]
+            self.disparity_sgm = dict(p1=p[0], p2=p[1], cost_cap=p[2] if len(p) > 2 else hip_lib.SGM_DEFAULTS["cost_cap"])
         self.cloud_lr = None if cloud_lr is None else float(cloud_lr)
         self.scene_dense = None if scene_dense is None else int(scene_dense)
         self.scene_dense_lr = None if scene_dense_lr is None else float(scene_dense_lr)
@@ -551,14 +560,16 @@ class Replay:
                           f"occluder_points {self.ar_log[-1][2]}")
         if self.dump_disparity:
             value = "depth" if self.disparity_depth else "disparity"
-            if self.disparity_lr is None:
+            if self.disparity_sgm is not None:
+                planes = self.slam.get_disparity(value=value, step=self.disparity_step, cost=True, sgm=self.disparity_sgm)
+            elif self.disparity_lr is None:
                 planes = self.slam.get_disparity(value=value, step=self.disparity_step)
             else:
                 planes = self.slam.get_disparity(value=value, step=self.disparity_step, cost=True,
                                                  lr_check=self.disparity_lr if self.disparity_lr > 0 else True)
             if planes is not None:
                 np.save(os.path.join(self.dump_disparity, f"{len(self.cumulative) - 1:06d}_disparity.npy"),
-                        planes[0] if self.disparity_lr is None else planes)
+                        planes[0] if self.disparity_lr is None and self.disparity_sgm is None else planes)
         if self.dump_cloud:
             kf = int(self.slam.stats().n_keyframes) - 1
             if kf != self._cloud_kf:
@@ -695,6 +706,9 @@ def build_parser():
                          "(float32 [rows, cols]; -1 where the search window leaves the image)")
     ap.add_argument("--disparity-step", metavar="S", type=int, default=4, help="lattice of --dump-disparity: every S-th pixel, 1 .. 16")
     ap.add_argument("--disparity-depth", action="store_true", help="--dump-disparity writes depth, baseline / disparity (0: none)")
+    ap.add_argument("--disparity-sgm", metavar="P1,P2[,CAP]", default=None,
+                    help="--dump-disparity aggregates semi-globally with these penalties (and cost cap) and writes "
+                         "[2, rows, cols]: the sub-pixel value and the aggregated cost; needs a search_x <= 63")
     ap.add_argument("--disparity-lr", metavar="D", type=float, default=None,
                     help="--dump-disparity cross-checks left-right and writes [3, rows, cols]: the value (invalid where the "
                          "two searches differ by more than D; 0: report only), the cost and the lr plane")
@@ -812,6 +826,7 @@ def main(argv=None):
                 keyframe_window=args.keyframe_window, dump_disparity=args.dump_disparity, disparity_step=args.disparity_step,
                 disparity_depth=args.disparity_depth, dump_cloud=args.dump_cloud, cloud_step=args.cloud_step,
                 cloud_max_depth=args.cloud_max_depth, disparity_lr=args.disparity_lr, cloud_lr=args.cloud_lr,
+                disparity_sgm=None if args.disparity_sgm is None else args.disparity_sgm.split(","),
                 scene_dense=args.scene_dense, scene_dense_lr=args.scene_dense_lr, scene_dense_max_depth=args.scene_dense_max_depth,
                 scene_accumulate=args.scene_accumulate, dump_dense_map=args.dump_dense_map, dense_map_voxel=args.dense_map_voxel,
                 dense_map_log2=args.dense_map_log2, dense_map_min_count=args.dense_map_min_count, scene_fused=args.scene_fused,

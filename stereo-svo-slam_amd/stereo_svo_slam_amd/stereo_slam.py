@@ -370,20 +370,33 @@ class StereoSlamBatch:
             return None
         return hip_lib.stereo_check(True, 0.0 if lr_check is True else float(lr_check))
 
+    @staticmethod
+    def _sgm_params(sgm):
+        """sgm of submit_disparity as a hip_lib.SgmParams: None or False: off; True: hip_lib.SGM_DEFAULTS; a dict with
+        p1, p2, cost_cap and, if wanted, subpixel; or an SgmParams"""
+        if sgm is None or sgm is False:
+            return None
+        if isinstance(sgm, hip_lib.SgmParams):
+            return sgm
+        return hip_lib.sgm_params(**(hip_lib.SGM_DEFAULTS if sgm is True else dict(sgm)))
+
     def submit_disparity(self, what="frames", seqs=None, value="disparity", step=1, win=0, search_x=0, search_y=0,
-                         cost=False, device=False, style=None, lr_check=None):
+                         cost=False, device=False, style=None, lr_check=None, sgm=None):
         """svo_submit_export_disparity: queue a dense disparity (value="disparity") or depth ("depth") map of the
         current frames (what="frames") or newest keyframes ("last_keyframes") of the slots `seqs` (None: all, in
         order) behind what was submitted so far; nothing is waited for. step: the lattice (1 .. 16); win, search_x,
         search_y: 0 takes the ctx's settings; cost: a second plane with the minimum SSD; style: a
         hip_lib.DisparityStyle instead of all these; lr_check: the left-right cross-check (True: the lr plane is
-        appended; a tolerance: values that differ by more are set invalid as well; default off). Returns a Disparities, valid after its wait() (or the ctx's);
-        its submit() queues the same job again into the same buffers."""
+        appended; a tolerance: values that differ by more are set invalid as well; default off); sgm: semi-global
+        aggregation and sub-pixel values (True: hip_lib.SGM_DEFAULTS; or dict(p1=, p2=, cost_cap=, subpixel=); search_x
+        <= 63; the cost plane then holds the aggregated cost; not together with lr_check: ValueError; default off).
+        Returns a Disparities, valid after its wait() (or the ctx's); its submit() queues the same job again into the
+        same buffers."""
         if isinstance(what, str):
             what = hip_lib.EXPORT_WHAT.index(what)
         if style is None:
             style = hip_lib.disparity_style(value, step, win, search_x, search_y, cost)
-        return Disparities(self, what, seqs, style, device, self._stereo_check(lr_check)).submit()
+        return Disparities(self, what, seqs, style, device, self._stereo_check(lr_check), self._sgm_params(sgm)).submit()
 
     def export_disparity(self, what="frames", seqs=None, **kw):
         """submit_disparity + wait"""

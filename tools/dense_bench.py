@@ -16,6 +16,10 @@ One process, bench.py's rendered `euroc` stereo pairs (752 x 480), the EuRoC set
   checked    with `--checked D`: svo_dense_disparity_checked (the left-right cross-check of DESIGN §4.19 at the tolerance
              D, two planes) on the same pairs, a third leg alternating with the others. The unchecked figure of the
              parent commit comes from this tool run with SVO_HIP_LIB set to the parent's library, without --checked.
+  sgm        with `--sgm P1,P2[,CAP]`: semi-global aggregation on the same pairs, three more legs
+             alternating with the others: svo_dense_cost_volume (the cost-volume kernel), svo_sgm_aggregate on those
+             volumes (the paths and the value rule; with the achieved bytes/s over 2 B of C and 4 B of S per entry and
+             direction pair) and svo_dense_disparity_sgm (the whole stage entry). The baseline is dense_ms_per_image.
   job        frames/s over `--steps` queued steps of bench.py's workload without any job and with a device-mode
              step-4 disparity job of every slot queued behind every frame set; legs alternate, median of
              `--pipelined-repeats` each.
@@ -118,16 +122,19 @@ def kernel_leg(args, device, cfg, lefts, rights):
                                         [i * 2 * cols * rows * 4 for i in range(n)])
                 checked = lambda: h.dense_disparity_packed(packed_c, style, dst_c, check)
                 checked()
+            sgm = sgm_legs(args, h, device, cfg, pairs, style, cols, rows) if args.sgm else None
             dense(); baseline()                              # warm-up of the legs
             torch.cuda.synchronize(device)
             same = None if args.no_baseline else bool(torch.equal(dst[:cols * rows].view(rows, cols)[::every],
                                                                   b_out[:len(kps)].view(len(run_rows), cols)))
-            t_dense, t_base, t_checked = [], [], []
+            t_dense, t_base, t_checked, t_sgm = [], [], [], {k: [] for k in (sgm or {})}
             for _ in range(args.repeats):                   # the legs alternate
                 t_dense.append(event_ms(dense))
                 t_base.append(event_ms(baseline))
                 if checked:
                     t_checked.append(event_ms(checked))
+                for k in t_sgm:
+                    t_sgm[k].append(event_ms(sgm[k]))
             d_ms = statistics.median(t_dense) / n
             b_ms = statistics.median(t_base) / nb * (rows / len(run_rows))
             out["shapes"].append({"step": step, "images": n, "cols": cols, "rows": rows, "candidate_points_per_image": cand,
@@ -144,9 +151,52 @@ def kernel_leg(args, device, cfg, lefts, rights):
                                           "max_lr_diff": args.checked,
                                           "failing_fraction": float(((lr < 0) | (lr > args.checked)).float().mean().item())})
                 del dst_c
+            if sgm:
+                entries = cols * rows * (sx + 1)
+                ms = {k: statistics.median(v) / n for k, v in t_sgm.items()}
+                out["shapes"][-1].update({"sgm": args.sgm, "candidates": sx + 1, "volume_entries_per_image": entries,
+                                          "cost_volume_ms_per_image": ms["cost_volume"], "paths_ms_per_image": ms["paths"],
+                                          "sgm_ms_per_image": ms["whole"], "sgm_call_ms_all": t_sgm,
+                                          "paths_bytes_per_s": 2 * 6 * entries / (ms["paths"] * 1e-3),
+                                          "cost_volume_over_dense": ms["cost_volume"] / d_ms, "sgm_over_dense": ms["whole"] / d_ms})
+                del sgm
             print(json.dumps(out["shapes"][-1]), file=sys.stderr, flush=True)      # (progress)
     h.close()
     return out
+
+
+def sgm_legs(args, h, device, cfg, pairs, style, cols, rows):
+    """the three SGM legs over `pairs` with their arguments built once: {name: callable}. The volumes of all pairs live
+    in one tensor (volume | count plane per pair)"""
+    W, H, lib, n = cfg["width"], cfg["height"], hip_lib.lib(), len(pairs)
+    D = style.search_x + 1
+    cap = args.sgm[2] if len(args.sgm) > 2 else hip_lib.SGM_DEFAULTS["cost_cap"]
+    sp = hip_lib.sgm_params(args.sgm[0], args.sgm[1], cap)
+    per = cols * rows * (D + 1)                            # uint16 words of a pair
+    vols = torch.empty(n * per, dtype=torch.int16, device=device)
+    dst = torch.empty(n * cols * rows, dtype=torch.float32, device=device)
+    packed = h.pack_dense([((l, W, H, l.stride(0)), (r, W, H, r.stride(0)), cfg["baseline"]) for l, r in pairs],
+                          [i * cols * rows * 4 for i in range(n)])
+    vo = (C.c_int64 * n)(*[i * per * 2 for i in range(n)])
+    co = (C.c_int64 * n)(*[(i * per + cols * rows * D) * 2 for i in range(n)])
+    shapes = (hip_lib.SgmShape * n)(*[hip_lib.SgmShape(cols, rows, D, cfg["baseline"]) for _ in range(n)])
+    vp = (C.c_void_p * n)(*[vols.data_ptr() + vo[i] for i in range(n)])
+    cp = (C.c_void_p * n)(*[vols.data_ptr() + co[i] for i in range(n)])
+
+    def cost_volume():
+        assert lib.svo_dense_cost_volume(h._h, n, packed[1], C.byref(style), cap, vo, co, C.c_void_p(vols.data_ptr())) == 0
+
+    def paths():
+        assert lib.svo_sgm_aggregate(h._h, n, shapes, vp, cp, 0, 0, C.byref(sp), packed[2], C.c_void_p(dst.data_ptr())) == 0
+
+    def whole():
+        assert lib.svo_dense_disparity_sgm(h._h, n, packed[1], packed[2], C.byref(style), C.byref(sp), C.c_void_p(dst.data_ptr())) == 0
+    legs = {"cost_volume": cost_volume, "paths": paths, "whole": whole}
+    legs["cost_volume"](); legs["paths"]()
+    mine = dst.clone()
+    legs["whole"]()                                        # (and the warm-up: the two-step result is the whole's)
+    assert torch.equal(mine, dst)
+    return legs                                            # (the closures keep the tensors and arrays alive)
 
 
 def start(cfg, lefts, rights, slots, groups, device, steps):
@@ -201,6 +251,8 @@ def main():
     ap.add_argument("--baseline-rows", type=int, default=8, help="at steps 1 and 2 the baseline runs every n-th lattice row, scaled up")
     ap.add_argument("--no-baseline", action="store_true", help="leave the per-keypoint baseline out (its fields are then of no use)")
     ap.add_argument("--checked", type=float, default=None, metavar="D", help="also time svo_dense_disparity_checked at the tolerance D")
+    ap.add_argument("--sgm", type=lambda t: [int(x) for x in t.split(",")], default=None, metavar="P1,P2[,CAP]",
+                    help="also time the cost-volume kernel, the paths and svo_dense_disparity_sgm with these penalties")
     ap.add_argument("--legs", default="256:1,1024:3", help="slots:groups per job leg (groups 0: the ctx's default); '' for none")
     ap.add_argument("--job-step", type=int, default=4)
     ap.add_argument("--loops", type=int, default=64)
