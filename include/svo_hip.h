@@ -1391,7 +1391,7 @@ typedef struct svo_sgm_params {     /* 32 bytes; copied at submit */
  * rejects; also (SVO_ERR_INVALID, nothing queued) a NULL sgm, a bad field of it, and an effective search_x > 63. The
  * segments, the shape of a slot's planes and image_bytes are those of svo_disparity_size for the style; the value and
  * cost planes hold the values of the statement above. Inside the ctx it is the disparity job carrying the params, not
- * another kind of queue entry. There is no cross-check of an SGM job yet.
+ * another kind of queue entry. Its cross-check is a rule of its own, "sgm cross-check" below.
  * Memory: the sums, the volume and the count plane of a slot (2 * cols * rows * D * 2 bytes and cols * rows * 2, each
  * rounded up to 256) live in a block of the group, made by the group's first SGM job and replaced when outgrown
  * (svo_memory.device_bytes). The slots of a job go through it in chunks of max(1, 512 MiB / slot bytes) slots (the
@@ -1432,6 +1432,75 @@ int svo_sgm_aggregate(svo_handle *h, int n, const svo_sgm_shape *shapes, const u
  * chunk within 512 MiB); a single pair whose volume needs more than 1 GiB is answered with SVO_ERR_CAPACITY. */
 int svo_dense_disparity_sgm(svo_handle *h, int n, const svo_dense_src *src, const int64_t *offset,
                             const svo_disparity_style *style, const svo_sgm_params *sgm, float *values);
+
+/* ---- sgm cross-check: the left-right check of an SGM map, and clouds of SGM maps ------------
+ * SGM fills a half-occluded band with smooth, confident, wrong values: the aggregated cost is low there and
+ * max_mean_cost cannot see it. The check of "cross-check" asks a second, mirrored search; for an SGM map that second
+ * search is a second SGM map, the same arithmetic run on the mirrored, swapped planes over their own lattice.
+ *
+ * Statement. With W the width, step, cols, rows and x = ix * step + step / 2 of "dense":
+ *   fwd = the SGM disparity plane of (L, R) by the statement of "sgm" (always the disparity, before any conversion to
+ *         depth);
+ *   rev = the SGM disparity plane of (Lm, Rm), Lm[y][u] = R[y][W - 1 - u], Rm[y][u] = L[y][W - 1 - u], with the same
+ *         style and params, over the lattice "dense" gives the mirrored planes: the same cols, rows and x.
+ * For the lattice point (ix, iy) at pixel x with disp = fwd[iy][ix]:
+ *   lr = -1                      disp is invalid; otherwise
+ *   xr = x + (int)(disp + 0.5f)  (a float add rounded once, then truncation; disp >= 0.5)
+ *   lr = -2                      xr > W - 1; otherwise
+ *   ixm = min((W - 1 - xr) / step, cols - 1)  (integer division: the lattice cell of the mirrored pair that holds the
+ *         matched column W - 1 - xr; the clamp bites only for step >= 5 with W % step >= 2 + step / 2)
+ *   rd = rev[iy][ixm]
+ *   lr = -2                      rd is invalid; else lr = fabsf(disp - rd)
+ * Failing (lr < 0.0f || lr > max_lr_diff at max_lr_diff > 0), the lr plane, the invalid value of a failing point, the
+ * untouched cost plane and SVO_DENSE_DEPTH = baseline / disp of a survivor are exactly as in "cross-check". With a
+ * check the forward SGM run writes disparities and the check does the division, the float operation of the unchecked
+ * SGM map: a point of a depth job that does not fail has the unchecked SGM job's bits.
+ *
+ * Entries: the SGM entry's arguments plus a svo_stereo_check. check == NULL or check->lr == 0 is the unchecked SGM
+ * entry, launch for launch. Rejected (SVO_ERR_INVALID, nothing queued) is what the SGM entry rejects and what
+ * "cross-check" rejects of a check, together; the shape of a slot's planes is that of svo_disparity_size_checked. No
+ * new kind of queue entry: these are disparity and cloud jobs. The top-level check of "cross-check" stays what it is:
+ * svo_submit_export_disparity_checked and svo_submit_export_cloud_checked run winner takes all.
+ *
+ * Clouds of SGM maps (svo_submit_export_cloud_sgm; check NULL or lr == 0: no check; a check needs max_lr_diff > 0):
+ * the cloud job of "clouds" with the SGM value plane (the disparity, cost = 1) as its staged disparity plane and
+ * best = (float)S(p, j0) as its cost plane. Triangulation, layouts, min_disparity and max_depth are unchanged;
+ * max_mean_cost != 0 drops a point iff best > max_mean_cost * 4.0f (one float product, one comparison): S is the sum
+ * over four paths of a cost that is per pixel already, so the factor is the number of paths where "clouds" has the
+ * template's area. With a check the check masks the staged disparity plane before the count and write launches.
+ * Shapes are those of svo_cloud_size. Also rejected: an effective search_x > 63, a NULL or bad sgm.
+ *
+ * Memory. A checked SGM slot stages two volumes, two blocks of sums, two count planes and the reverse plane:
+ *   slot_bytes = 2 * (2 * up256(cols * rows * D * 2) + up256(cols * rows * 2)) + up256(cols * rows * 4)
+ * in the block of "sgm" (svo_memory.device_bytes), with the same chunk rule: chunks of max(1, 512 MiB / slot_bytes) slots
+ * (SVO_SGM_CHUNK_SLOTS lowers it), block = min(delivered slots of the group, chunk) * slot_bytes; one slot always
+ * fits. An unchecked SGM slot is 2 * up256(cols * rows * D * 2) + up256(cols * rows * 2) as before. A checked SGM job
+ * does not use the reverse block of "cross-check". An SGM cloud job stages what a cloud job stages (slot_bytes of
+ * "clouds", no reverse_bytes) plus this block for the slots of one of its chunks. An unchecked SGM job, a checked or
+ * unchecked winner-takes-all job and a ctx that uses none of this allocate, launch and copy what they did.
+ *
+ * Launches of a chunk of m checked slots: the cost volumes of the m pairs, those of the m mirrored pairs, the two
+ * launches of the paths over one table of 2 m volumes (the mirrored ones behind the forward ones, writing their
+ * disparity alone), and the lattice form of the check kernel. */
+int svo_submit_export_disparity_sgm_checked(svo_ctx *ctx, int what, const int *seqs, int n, const svo_disparity_style *style,
+                                            const svo_sgm_params *sgm, const svo_stereo_check *check,
+                                            const svo_disparity_dst *dst, int mem);
+int svo_export_disparity_sgm_checked(svo_ctx *ctx, int what, const int *seqs, int n, const svo_disparity_style *style,
+                                     const svo_sgm_params *sgm, const svo_stereo_check *check, const svo_disparity_dst *dst,
+                                     int mem);   /* submit + wait */
+/* stage entry: svo_dense_disparity_sgm with the check; per pair the workspace also holds the mirrored pair's volume,
+ * count plane, S and disparity plane (chunked as there, within 512 MiB) */
+int svo_dense_disparity_sgm_checked(svo_handle *h, int n, const svo_dense_src *src, const int64_t *offset,
+                                    const svo_disparity_style *style, const svo_sgm_params *sgm,
+                                    const svo_stereo_check *check, float *values);
+int svo_submit_export_cloud_sgm(svo_ctx *ctx, int what, const int *seqs, int n, const svo_cloud_style *style,
+                                const svo_sgm_params *sgm, const svo_stereo_check *check, const svo_cloud_dst *dst, int mem);
+int svo_export_cloud_sgm(svo_ctx *ctx, int what, const int *seqs, int n, const svo_cloud_style *style,
+                         const svo_sgm_params *sgm, const svo_stereo_check *check, const svo_cloud_dst *dst,
+                         int mem);   /* submit + wait */
+/* stage entry: svo_cloud_points over SGM maps (style->win, search_x, search_y given; search_x <= 63) */
+int svo_cloud_points_sgm(svo_handle *h, int n, const svo_cloud_src *src, const int64_t *first, const svo_cloud_style *style,
+                         const svo_sgm_params *sgm, const svo_stereo_check *check, svo_map_point *points, int32_t *counts);
 
 /* ---- scene clouds: dense clouds ("clouds", "cross-check") drawn in the scene picture ------------
  * A scene job can draw, beside the elements above, svo_map_point records: the dense cloud of each named slot's frame

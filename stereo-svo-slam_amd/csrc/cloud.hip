@@ -49,7 +49,7 @@ int cloud_check_style(const svo_cloud_style* s, const svo_camera_settings* cam, 
         if (!(v >= 0.f) || !(v <= FLT_MAX)) return svo_set_error(SVO_ERR_INVALID, "%s: a filter value is negative or not finite", who);
     if (s->_reserved[0] != 0 || s->_reserved[1] != 0 || s->_reserved[2] != 0) return svo_set_error(SVO_ERR_INVALID, "%s: a _reserved is not 0", who);
     if (search) *search = dp;
-    if (out) *out = CloudParams{dp.step, dp.win, s->frame, s->layout, s->min_disparity, s->max_depth, s->max_mean_cost};
+    if (out) *out = CloudParams{dp.step, dp.win, s->frame, s->layout, s->min_disparity, s->max_depth, s->max_mean_cost, 0};
     return SVO_OK;
 }
 
@@ -67,7 +67,9 @@ __device__ __forceinline__ bool cloud_keep(const CloudImage& im, const CloudPara
     bool keep = true;
     if (p.min_disparity != 0.f && disp < p.min_disparity) keep = false;
     if (p.max_depth != 0.f && loc[2] > p.max_depth) keep = false;
-    if (p.max_mean_cost != 0.f) {
+    if (p.max_mean_cost != 0.f && p.sgm_cost) {            // (an SGM map: best is the sum of four paths of a cost per pixel)
+        if (best > p.max_mean_cost * 4.0f) keep = false;
+    } else if (p.max_mean_cost != 0.f) {
         const int wb = p.win / 2, wa = (p.win + 1) / 2;
         const int tw = min(im.w - 1, x + wa) - max(0, x - wb), th = min(im.h, y + wa) - max(0, y - wb);
         if (best > p.max_mean_cost * (float)(tw * th)) keep = false;

@@ -264,6 +264,11 @@ __global__ __launch_bounds__(DENSE_THREADS) void dense_disparity_kernel(const st
 // exact int32 SSD, never a float). After the dy loop the point's lane divides by its area, caps and stores one uint16
 // per row at [iy][ix][j]; after the last j it stores the count plane. Of an image exactly vol[0 .. rows * cols * D) and
 // count[0 .. rows * cols) are written.
+// MIRROR: the reverse volume of a checked SGM map (include/svo_hip.h, "sgm cross-check"). As in
+// dense_disparity_kernel<true> the two staging loops read column W - 1 - xx of the other plane; unlike there the lattice
+// keeps its column step, so cols, ix and every index after the staging are those of MIRROR = false, in the mirrored
+// pair's own coordinates. MIRROR = false is the kernel as it was.
+template <bool MIRROR>
 __global__ __launch_bounds__(DENSE_THREADS) void dense_cost_volume_kernel(const CostImage* __restrict__ images, const DenseParams p,
                                                                           const int cost_cap) {
     __shared__ __attribute__((aligned(16))) uint8_t s_l[DENSE_L_ROWS * DENSE_THREADS];
@@ -284,13 +289,16 @@ __global__ __launch_bounds__(DENSE_THREADS) void dense_cost_volume_kernel(const 
     const int yc0 = iy0 * step + step / 2;
     const int yl0 = max(0, yc0 - wb);
 
+    const uint8_t* const src_l = MIRROR ? im.right : im.left;
+    const uint8_t* const src_r = MIRROR ? im.left : im.right;
+    const int stride_l = MIRROR ? im.right_stride : im.left_stride, stride_r = MIRROR ? im.left_stride : im.right_stride;
     for (int i = tid; i < DENSE_L_ROWS * DENSE_THREADS; i += DENSE_THREADS) {
         const int yy = yl0 + i / DENSE_THREADS, xx = X0 + i % DENSE_THREADS;
-        s_l[i] = (yy < H && xx >= 0 && xx < W) ? G(im.left)[(int64_t)yy * im.left_stride + xx] : (uint8_t)0;
+        s_l[i] = (yy < H && xx >= 0 && xx < W) ? G(src_l)[(int64_t)yy * stride_l + (MIRROR ? W - 1 - xx : xx)] : (uint8_t)0;
     }
     for (int i = tid; i < DENSE_R_ROWS * DENSE_R_COLS; i += DENSE_THREADS) {
         const int yy = yl0 - sy + i / DENSE_R_COLS, xx = X0 + i % DENSE_R_COLS;
-        s_r[i] = (yy >= 0 && yy < H && xx >= 0 && xx < W) ? G(im.right)[(int64_t)yy * im.right_stride + xx] : (uint8_t)0;
+        s_r[i] = (yy >= 0 && yy < H && xx >= 0 && xx < W) ? G(src_r)[(int64_t)yy * stride_r + (MIRROR ? W - 1 - xx : xx)] : (uint8_t)0;
     }
 
     const int x = X0 + tid, xl = x - step / 2;
@@ -381,7 +389,12 @@ __global__ __launch_bounds__(DENSE_THREADS) void dense_cost_volume_kernel(const 
 
 void launch_dense_cost_volume(const CostImage* d_images, int n, int tiles, const DenseParams& p, int cost_cap, hipStream_t stream) {
     if (n <= 0 || tiles <= 0) return;
-    hipLaunchKernelGGL(dense_cost_volume_kernel, dim3(tiles, n), dim3(DENSE_THREADS), 0, stream, d_images, p, cost_cap);
+    hipLaunchKernelGGL(dense_cost_volume_kernel<false>, dim3(tiles, n), dim3(DENSE_THREADS), 0, stream, d_images, p, cost_cap);
+}
+
+void launch_dense_cost_volume_mirrored(const CostImage* d_images, int n, int tiles, const DenseParams& p, int cost_cap, hipStream_t stream) {
+    if (n <= 0 || tiles <= 0) return;
+    hipLaunchKernelGGL(dense_cost_volume_kernel<true>, dim3(tiles, n), dim3(DENSE_THREADS), 0, stream, d_images, p, cost_cap);
 }
 
 void launch_dense(const DenseImage* d_images, int n, int tiles, const DenseParams& p, hipStream_t stream) {

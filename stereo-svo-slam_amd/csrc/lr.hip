@@ -12,8 +12,14 @@
 // only its own points of the value plane, so the plane is converted in place; the reverse plane is only read. About
 // 8 B in and 4 to 8 B out per lattice point; no LDS, no atomics; the roof is HBM.
 //
+// LATTICE: the check of an SGM map (include/svo_hip.h, "sgm cross-check"). The reverse plane is the SGM disparity of
+// the mirrored pair over its own lattice, cols x rows floats, and the point gathers the cell that holds its matched
+// column: ixm = min((W - 1 - xr) / step, cols - 1). Nothing else differs.
+//
 // Bounds: of an image, floats [0, cols * rows) of value and lr are read / written (k < total), and floats
 // [iy * w + xr] of the reverse plane with iy < rows, x <= xr <= w - 1 (xr > w - 1 is tested before the read).
+// LATTICE: floats [iy * cols + ixm] with iy < rows and, as 0 <= W - 1 - xr under the same test, 0 <= ixm <= cols - 1
+// by the clamp (which bites only where W % step >= 2 + step / 2 leaves columns beyond the last cell).
 #include <cmath>
 
 #include "svo_host.hpp"
@@ -39,6 +45,7 @@ int lr_check_parse(const svo_stereo_check* s, bool cloud, const char* who, LrChe
     return SVO_OK;
 }
 
+template <bool LATTICE>
 __global__ __launch_bounds__(LR_THREADS) void lr_check_kernel(const LrImage* __restrict__ images, const LrParams p) {
     const LrImage im = G(images)[blockIdx.y];
     const int W = im.w, cols = W / p.step, total = cols * (im.h / p.step);
@@ -55,7 +62,8 @@ __global__ __launch_bounds__(LR_THREADS) void lr_check_kernel(const LrImage* __r
         const int k = k0 + q, iy = k / cols, ix = k - iy * cols;
         const int x = ix * p.step + p.step / 2;
         xr[q] = x + (int)(disp[q] + 0.5f);
-        rd[q] = (disp[q] >= 0.f && xr[q] <= W - 1) ? rev[(int64_t)iy * W + xr[q]] : -1.f;
+        const int64_t at = LATTICE ? (int64_t)iy * cols + min((W - 1 - xr[q]) / p.step, cols - 1) : (int64_t)iy * W + xr[q];
+        rd[q] = (disp[q] >= 0.f && xr[q] <= W - 1) ? rev[at] : -1.f;
     }
     const float inv = p.value == SVO_DENSE_DEPTH ? 0.f : -1.f;
 #pragma unroll
@@ -72,7 +80,12 @@ __global__ __launch_bounds__(LR_THREADS) void lr_check_kernel(const LrImage* __r
 
 void launch_lr_check(const LrImage* d_images, int n, int tiles, const LrParams& p, hipStream_t stream) {
     if (n <= 0 || tiles <= 0) return;
-    hipLaunchKernelGGL(lr_check_kernel, dim3(tiles, n), dim3(LR_THREADS), 0, stream, d_images, p);
+    hipLaunchKernelGGL(lr_check_kernel<false>, dim3(tiles, n), dim3(LR_THREADS), 0, stream, d_images, p);
+}
+
+void launch_lr_check_lattice(const LrImage* d_images, int n, int tiles, const LrParams& p, hipStream_t stream) {
+    if (n <= 0 || tiles <= 0) return;
+    hipLaunchKernelGGL(lr_check_kernel<true>, dim3(tiles, n), dim3(LR_THREADS), 0, stream, d_images, p);
 }
 
 }  // namespace svo

@@ -21,7 +21,12 @@
 // its uint16.
 //
 // Bounds: a wavefront owns line `line` < lines of its image and touches vol / sum at (point * D + lane) for lane < D
-// and point < cols * rows only; count and out at point < cols * rows (out + plane with cost). No LDS.
+// and point < cols * rows only; count and out at point < cols * rows (out + plane with cost; never for a reverse
+// volume of a checked job, whose out is one plane). No LDS.
+//
+// A checked job (include/svo_hip.h, "sgm cross-check") puts the volumes of the mirrored pairs behind the forward ones
+// in the same table, so the same two launches carry both: the kernel is latency bound with few images,
+// and twice the entries of a launch cost less than a second pair of launches.
 #include "svo_host.hpp"
 #include "svo_tracker.hpp"
 
@@ -40,7 +45,7 @@ int sgm_check_params(const svo_sgm_params* s, const char* who, SgmParams* out) {
         return svo_set_error(SVO_ERR_INVALID, "%s: cost_cap %d, p2 %d: cost_cap >= 1 and 4 * (cost_cap + p2) <= 65535", who, s->cost_cap, s->p2);
     if (s->subpixel != 0 && s->subpixel != 1) return svo_set_error(SVO_ERR_INVALID, "%s: subpixel %d", who, s->subpixel);
     if (s->_reserved[0] != 0 || s->_reserved[1] != 0 || s->_reserved[2] != 0) return svo_set_error(SVO_ERR_INVALID, "%s: a _reserved is not 0", who);
-    if (out) *out = SgmParams{s->p1, s->p2, s->cost_cap, s->subpixel, 0, 0};
+    if (out) *out = SgmParams{s->p1, s->p2, s->cost_cap, s->subpixel, 0, 0, 0};
     return SVO_OK;
 }
 
@@ -66,9 +71,9 @@ __device__ __forceinline__ int sgm_step(int P, int c, int p1, int p2, bool live)
 }
 
 // the value and cost of one point from its complete S (every lane its own), in every lane
-__device__ __forceinline__ void sgm_value(int S, int lane, int count, const SgmParams& p, float baseline, float* value, float* cost) {
+__device__ __forceinline__ void sgm_value(int S, int lane, int count, const SgmParams& p, bool depth, float baseline, float* value, float* cost) {
     const int key = sgm_wave_min(lane < count ? (S << 6 | lane) : 0x7fffffff);
-    *value = p.value == SVO_DENSE_DEPTH ? 0.f : -1.f;
+    *value = depth ? 0.f : -1.f;
     *cost = -1.f;
     if (count <= 0) return;                                // (the same for every lane)
     const int j0 = key & 63, b = key >> 6;
@@ -78,7 +83,7 @@ __device__ __forceinline__ void sgm_value(int S, int lane, int count, const SgmP
         d = d + (float)(a - c) / (float)(2 * (a - 2 * b + c));
     }
     const float disp = d < 0.5f ? 0.5f : d;
-    *value = p.value == SVO_DENSE_DEPTH ? baseline / disp : disp;
+    *value = depth ? baseline / disp : disp;
     *cost = (float)b;
 }
 
@@ -120,6 +125,9 @@ __global__ __launch_bounds__(SGM_THREADS) void sgm_paths_kernel(const SgmImage* 
     SVO_GP(const uint16_t) count = G(im.count);
     SVO_GP(float) out = G(im.out);
     const int64_t plane = (int64_t)im.cols * im.rows;
+    // (a reverse volume of a checked job, the same for the whole workgroup: its disparity alone)
+    const bool reverse = p.reverse_from > 0 && (int)blockIdx.y >= p.reverse_from;
+    const bool depth = !reverse && p.value == SVO_DENSE_DEPTH, with_cost = !reverse && p.cost;
     P = SGM_BIG;
     for (int i0 = len - 1; i0 >= 0; i0 -= SGM_AHEAD) {
         int c[SGM_AHEAD], s[SGM_AHEAD], n[SGM_AHEAD];
@@ -139,10 +147,10 @@ __global__ __launch_bounds__(SGM_THREADS) void sgm_paths_kernel(const SgmImage* 
                 if (live) sum[pt * D + lane] = (uint16_t)(s[k] + P);
             } else {
                 float value, cost;
-                sgm_value(live ? s[k] + P : 0, lane, min(n[k], D), p, im.baseline, &value, &cost);
+                sgm_value(live ? s[k] + P : 0, lane, min(n[k], D), p, depth, im.baseline, &value, &cost);
                 if (lane == 0) {
                     out[pt] = value;
-                    if (p.cost) out[plane + pt] = cost;
+                    if (with_cost) out[plane + pt] = cost;
                 }
             }
         }

@@ -33,7 +33,7 @@ int run_job(svo_group* g, int seq0, const svo_ctx::DisparityExport& j) {
     return grp_export_disparity(g, j.what, j.mem, j.seqs.data(), j.seg.data(), (int)j.seqs.size(), seq0, &j.style, j.check_ptr(), j.sgm_ptr(), &j.dst);
 }
 int run_job(svo_group* g, int seq0, const svo_ctx::CloudExport& j) {
-    return grp_export_cloud(g, j.what, j.mem, j.seqs.data(), j.seg.data(), (int)j.seqs.size(), seq0, &j.style, j.check_ptr(), &j.dst);
+    return grp_export_cloud(g, j.what, j.mem, j.seqs.data(), j.seg.data(), (int)j.seqs.size(), seq0, &j.style, j.check_ptr(), &j.dst, j.sgm_ptr());
 }
 int run_job(svo_group* g, int seq0, const svo_ctx::SceneExport& j) {
     return grp_export_scenes_clouds(g, j.mem, j.seqs.data(), j.seg.data(), (int)j.seqs.size(), seq0, &j.style, j.cameras.data(), &j.dst,

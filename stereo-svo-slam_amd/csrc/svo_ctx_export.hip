@@ -136,30 +136,80 @@ extern "C" int svo_export_disparity_checked(svo_ctx* c, int what, const int* seq
     return then_wait(c, svo_submit_export_disparity_checked(c, what, seqs, n, style, check, dst, mem));
 }
 
-// the disparity job in its SGM mode (include/svo_hip.h, "sgm"): the same queue entry carrying the params
-extern "C" int svo_submit_export_disparity_sgm(svo_ctx* c, int what, const int* seqs, int n, const svo_disparity_style* style,
-                                               const svo_sgm_params* sgm, const svo_disparity_dst* dst, int mem) {
+// the disparity job in its SGM mode (include/svo_hip.h, "sgm"): the same queue entry carrying the params, and with a
+// check that is on ("sgm cross-check") the check beside them
+namespace {
+
+int submit_disparity_sgm(svo_ctx* c, int what, const int* seqs, int n, const svo_disparity_style* style, const svo_sgm_params* sgm,
+                         const svo_stereo_check* check, const svo_disparity_dst* dst, int mem, const char* who) {
     if (!c || !dst || !dst->segments || !what_ok(what) || !mem_ok(mem) || !naming_ok(seqs, n))
-        return svo_set_error(SVO_ERR_INVALID, "svo_submit_export_disparity_sgm: bad arguments (what %d, mem %d)", what, mem);
-    if (const int rc = grp_check_disparity_style(c->g0(), style, nullptr)) return rc;
-    if (const int rc = grp_check_disparity_sgm(c->g0(), style, sgm)) return rc;
-    if (!dst->values || ((uintptr_t)dst->values & 15))
-        return svo_set_error(SVO_ERR_INVALID, "svo_submit_export_disparity_sgm: values is NULL or not 16-byte aligned");
+        return svo_set_error(SVO_ERR_INVALID, "%s: bad arguments (what %d, mem %d)", who, what, mem);
+    if (const int rc = grp_check_disparity_style(c->g0(), style, check)) return rc;
+    if (const int rc = grp_check_disparity_sgm(c->g0(), style, sgm, who)) return rc;
+    if (!dst->values || ((uintptr_t)dst->values & 15)) return svo_set_error(SVO_ERR_INVALID, "%s: values is NULL or not 16-byte aligned", who);
     const NamedSlots slots = ctx_slots(c, seqs, n);
-    if (const int rc = check_slots(c, "svo_submit_export_disparity_sgm", slots)) return rc;
-    if (const int rc = check_capacity("svo_submit_export_disparity_sgm", slots.n, grp_disparity_bytes(c->g0(), style, nullptr), dst->capacity, "bytes"))
-        return rc;
-    if (c->failed.load()) return reject_failed(c, "svo_submit_export_disparity_sgm");
+    if (const int rc = check_slots(c, who, slots)) return rc;
+    if (const int rc = check_capacity(who, slots.n, grp_disparity_bytes(c->g0(), style, check), dst->capacity, "bytes")) return rc;
+    if (c->failed.load()) return reject_failed(c, who);
     submit_shares<svo_ctx::DisparityExport>(c, slots, every_slot, [&](svo_ctx::DisparityExport& e) {
         e.what = what; e.mem = mem; e.style = *style; e.dst = *dst;
         e.has_sgm = true; e.sgm = *sgm;
+        e.set_check(check);
     });
     return SVO_OK;
+}
+
+}  // namespace
+
+extern "C" int svo_submit_export_disparity_sgm(svo_ctx* c, int what, const int* seqs, int n, const svo_disparity_style* style,
+                                               const svo_sgm_params* sgm, const svo_disparity_dst* dst, int mem) {
+    return submit_disparity_sgm(c, what, seqs, n, style, sgm, nullptr, dst, mem, "svo_submit_export_disparity_sgm");
 }
 
 extern "C" int svo_export_disparity_sgm(svo_ctx* c, int what, const int* seqs, int n, const svo_disparity_style* style,
                                         const svo_sgm_params* sgm, const svo_disparity_dst* dst, int mem) {
     return then_wait(c, svo_submit_export_disparity_sgm(c, what, seqs, n, style, sgm, dst, mem));
+}
+
+extern "C" int svo_submit_export_disparity_sgm_checked(svo_ctx* c, int what, const int* seqs, int n, const svo_disparity_style* style,
+                                                       const svo_sgm_params* sgm, const svo_stereo_check* check,
+                                                       const svo_disparity_dst* dst, int mem) {
+    if (const int rc = drop_check_that_is_off(&check, false, "svo_submit_export_disparity_sgm_checked")) return rc;
+    if (!check) return svo_submit_export_disparity_sgm(c, what, seqs, n, style, sgm, dst, mem);
+    return submit_disparity_sgm(c, what, seqs, n, style, sgm, check, dst, mem, "svo_submit_export_disparity_sgm_checked");
+}
+
+extern "C" int svo_export_disparity_sgm_checked(svo_ctx* c, int what, const int* seqs, int n, const svo_disparity_style* style,
+                                                const svo_sgm_params* sgm, const svo_stereo_check* check, const svo_disparity_dst* dst,
+                                                int mem) {
+    return then_wait(c, svo_submit_export_disparity_sgm_checked(c, what, seqs, n, style, sgm, check, dst, mem));
+}
+
+// the cloud job over an SGM map ("sgm cross-check"): the cloud job's queue entry carrying the params and the check
+extern "C" int svo_submit_export_cloud_sgm(svo_ctx* c, int what, const int* seqs, int n, const svo_cloud_style* style,
+                                           const svo_sgm_params* sgm, const svo_stereo_check* check, const svo_cloud_dst* dst, int mem) {
+    const char* const who = "svo_submit_export_cloud_sgm";
+    if (const int rc = drop_check_that_is_off(&check, true, who)) return rc;
+    if (!c || !dst || !dst->segments || !what_ok(what) || !mem_ok(mem) || !naming_ok(seqs, n))
+        return svo_set_error(SVO_ERR_INVALID, "%s: bad arguments (what %d, mem %d)", who, what, mem);
+    if (const int rc = grp_check_cloud_style(c->g0(), style, check)) return rc;
+    if (const int rc = grp_check_cloud_sgm(c->g0(), style, sgm, who)) return rc;
+    if (!dst->points || ((uintptr_t)dst->points & 15)) return svo_set_error(SVO_ERR_INVALID, "%s: points is NULL or not 16-byte aligned", who);
+    const NamedSlots slots = ctx_slots(c, seqs, n);
+    if (const int rc = check_slots(c, who, slots)) return rc;
+    if (const int rc = check_capacity(who, slots.n, grp_cloud_points(c->g0(), style), dst->capacity, "records")) return rc;
+    if (c->failed.load()) return reject_failed(c, who);
+    submit_shares<svo_ctx::CloudExport>(c, slots, every_slot, [&](svo_ctx::CloudExport& e) {
+        e.what = what; e.mem = mem; e.style = *style; e.dst = *dst;
+        e.has_sgm = true; e.sgm = *sgm;
+        e.set_check(check);
+    });
+    return SVO_OK;
+}
+
+extern "C" int svo_export_cloud_sgm(svo_ctx* c, int what, const int* seqs, int n, const svo_cloud_style* style, const svo_sgm_params* sgm,
+                                    const svo_stereo_check* check, const svo_cloud_dst* dst, int mem) {
+    return then_wait(c, svo_submit_export_cloud_sgm(c, what, seqs, n, style, sgm, check, dst, mem));
 }
 
 extern "C" int svo_submit_export_cloud_checked(svo_ctx* c, int what, const int* seqs, int n, const svo_cloud_style* style,

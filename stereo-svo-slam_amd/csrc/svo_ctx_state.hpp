@@ -85,13 +85,15 @@ struct svo_ctx {
     };
     template <typename Style, typename Dst>
     struct CheckedExport : ImageExport<Style, Dst>, StereoCheck {};
-    // (svo_submit_export_disparity_sgm: the same job carrying the SGM params)
-    struct DisparityExport : CheckedExport<svo_disparity_style, svo_disparity_dst> {
+    // (svo_submit_export_disparity_sgm, svo_submit_export_cloud_sgm: the same job carrying the SGM params)
+    template <typename Style, typename Dst>
+    struct SgmExport : CheckedExport<Style, Dst> {
         bool has_sgm = false;
         svo_sgm_params sgm{};
         const svo_sgm_params* sgm_ptr() const { return has_sgm ? &sgm : nullptr; }
     };
-    using CloudExport = CheckedExport<svo_cloud_style, svo_cloud_dst>;
+    using DisparityExport = SgmExport<svo_disparity_style, svo_disparity_dst>;
+    using CloudExport = SgmExport<svo_cloud_style, svo_cloud_dst>;
     // the group's share of an svo_submit_export_scenes: the camera of each slot
     struct SceneExport : SlotShare {
         int mem = 0;

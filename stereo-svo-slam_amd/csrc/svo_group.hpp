@@ -112,7 +112,8 @@ int grp_export_disparity(svo_group* g, int what, int mem, const int* seqs, const
                          const svo_disparity_style* style, const svo_stereo_check* check, const svo_sgm_params* sgm,
                          const svo_disparity_dst* dst);
 // what svo_submit_export_disparity_sgm checks beside the style: the params, and an effective search_x <= 63
-int grp_check_disparity_sgm(const svo_group* g, const svo_disparity_style* style, const svo_sgm_params* sgm);
+int grp_check_disparity_sgm(const svo_group* g, const svo_disparity_style* style, const svo_sgm_params* sgm,
+                            const char* who = "svo_submit_export_disparity_sgm");
 // what svo_submit_export_disparity checks of a style, and the image_bytes of a checked one (they read only what never
 // changes in a group)
 int grp_check_disparity_style(const svo_group* g, const svo_disparity_style* style, const svo_stereo_check* check);
@@ -121,10 +122,12 @@ int64_t grp_disparity_bytes(const svo_group* g, const svo_disparity_style* style
 // dst->segments[seg[i]] and its records start at record seg[i] * points_per_slot of dst->points. style: checked
 // (grp_check_cloud_style). check: as in grp_export_disparity. Delivered on return. A failed group rejects it.
 int grp_export_cloud(svo_group* g, int what, int mem, const int* seqs, const int* seg, int n, int seq0, const svo_cloud_style* style,
-                     const svo_stereo_check* check, const svo_cloud_dst* dst);
+                     const svo_stereo_check* check, const svo_cloud_dst* dst, const svo_sgm_params* sgm = nullptr);
 // what svo_submit_export_cloud checks of a style, and the points_per_slot of a checked one
 int grp_check_cloud_style(const svo_group* g, const svo_cloud_style* style, const svo_stereo_check* check);
 int64_t grp_cloud_points(const svo_group* g, const svo_cloud_style* style);
+// what svo_submit_export_cloud_sgm checks beside the style: the params, and an effective search_x <= 63
+int grp_check_cloud_sgm(const svo_group* g, const svo_cloud_style* style, const svo_sgm_params* sgm, const char* who);
 // what one slot of a device-mode job with that checked style and check stages: slot_bytes [+ reverse_bytes]
 int64_t grp_cloud_slot_bytes(const svo_group* g, const svo_cloud_style* style, const svo_stereo_check* check);
 // Voxel maps (svo_group_voxel.hip). grp_set_voxel_maps: the named slots (indices in the group) get a cleared map of

@@ -66,6 +66,13 @@ int grp_check_cloud_style(const svo_group* c, const svo_cloud_style* style, cons
     return lr_check_parse(check, true, who, nullptr);
 }
 
+int grp_check_cloud_sgm(const svo_group* c, const svo_cloud_style* style, const svo_sgm_params* sgm, const char* who) {
+    DenseParams s;
+    if (const int rc = check_style(&c->cam, c->width, c->height, style, who, &s, nullptr)) return rc;
+    if (s.search_x + 1 > SGM_MAX_D) return svo_set_error(SVO_ERR_INVALID, "%s: search_x %d: at most %d with a cost volume", who, s.search_x, SGM_MAX_D - 1);
+    return sgm_check_params(sgm, who, nullptr);
+}
+
 int64_t grp_cloud_points(const svo_group* c, const svo_cloud_style* style) {
     DenseParams s;
     if (cloud_check_style(style, &c->cam, "svo_submit_export_cloud", &s, nullptr) != SVO_OK) return 0;
@@ -90,8 +97,11 @@ int64_t grp_cloud_slot_bytes(const svo_group* c, const svo_cloud_style* style, c
 // A checked job (include/svo_hip.h, "cross-check") has a third table, a third of the blocks each: between the search
 // and the count launch the reverse search fills the chunk's reverse planes (the group's d_lr block) and the check
 // sets the staged disparity of a failing point to -1, which the count and write launches drop as an invalid point.
+// An SGM job (sgm != null; include/svo_hip.h, "sgm cross-check") fills the staged planes with grp_sgm_planes in the
+// place of the search, its check in the place of the reverse search and the check (no d_lr block), and the count and
+// write launches read the cost plane as the sum of four paths.
 int grp_export_cloud(svo_group* c, int what, int mem, const int* seqs, const int* seg, int n, int seq0, const svo_cloud_style* style,
-                     const svo_stereo_check* check, const svo_cloud_dst* dst) {
+                     const svo_stereo_check* check, const svo_cloud_dst* dst, const svo_sgm_params* sgm) {
     if (const int rc = job_begin(c, "svo_submit_export_cloud")) return rc;
     hipStream_t st = c->stream.get();
     const bool host = mem == SVO_MEM_HOST;
@@ -100,7 +110,14 @@ int grp_export_cloud(svo_group* c, int what, int mem, const int* seqs, const int
     if (const int rc = cloud_check_style(style, &c->cam, "svo_submit_export_cloud", &search, &params)) return rc;
     LrCheck lr;
     if (const int rc = lr_check_parse(check, true, "svo_submit_export_cloud", &lr)) return rc;
-    const size_t reverse = lr.on ? lr_reverse_bytes(c->width, c->height, search.step) : 0;
+    SgmParams sgm_params{};
+    if (sgm) {
+        if (const int rc = sgm_check_params(sgm, "svo_submit_export_cloud_sgm", &sgm_params)) return rc;
+        sgm_params.value = SVO_DENSE_DISPARITY;
+        sgm_params.cost = 1;
+        params.sgm_cost = 1;
+    }
+    const size_t reverse = lr.on && !sgm ? lr_reverse_bytes(c->width, c->height, search.step) : 0;
     const LrParams lr_params{SVO_DENSE_DISPARITY, search.step, lr.max_lr_diff};
     const int64_t points = (int64_t)(c->width / search.step) * (c->height / search.step);
     const bool organized = params.layout == SVO_CLOUD_ORGANIZED;
@@ -109,7 +126,7 @@ int grp_export_cloud(svo_group* c, int what, int mem, const int* seqs, const int
     const size_t m_max = std::min<size_t>((size_t)n, chunk);
     const Staging sg((size_t)points, host, m_max);
     if (const int rc = reserve_cloud(c, sg.total, m_max)) return rc;
-    if (lr.on)
+    if (lr.on && !sgm)
         if (const int rc = c->d_lr.reserve(c, m_max * reverse)) return rc;
     uint8_t* const d_planes = c->d_cloud.p;
     uint8_t* const d_counts = d_planes + m_max * sg.planes;
@@ -149,6 +166,20 @@ int grp_export_cloud(svo_group* c, int what, int mem, const int* seqs, const int
             shown++;
         }
         if (shown == 0) continue;
+        if (sgm) {                                         // (the planes first: it uses the argument blocks itself)
+            std::vector<DenseImage> images;
+            for (int j = 0; j < m; j++) {
+                if (!sets[(size_t)j]) continue;
+                const ImgView& l = sets[(size_t)j]->left[0];
+                const ImgView& r = sets[(size_t)j]->right;
+                images.push_back(DenseImage{l.data, r.data, reinterpret_cast<float*>(d_planes + (size_t)j * sg.planes), l.stride, r.stride, l.w, l.h,
+                                            c->seqs[seqs[i0 + j]].cam.baseline, 0});
+            }
+            if (const int rc = grp_sgm_planes(c, images, search, sgm_params, c->width / search.step, c->height / search.step,
+                                              lr.on ? &lr_params : nullptr, -1, true))
+                return rc;
+        }
+        const bool wta_check = lr.on && !sgm;
         // (SVO_CLOUD_TABLE_IMAGES: smaller tables, so that tests reach the chunked launches)
         DenseParams sp = search;
         int dense_grid = 0;
@@ -160,7 +191,7 @@ int grp_export_cloud(svo_group* c, int what, int mem, const int* seqs, const int
             launch_dense_reverse(d, k, dense_grid, sp, s);
             launch_lr_check(d, k, lr_tiles(points), lr_params, s);
         });
-        const size_t half = c->args.bytes / (lr.on ? 3 : 2) / 256 * 256;   // (a third each of a checked job's three tables)
+        const size_t half = c->args.bytes / (wta_check ? 3 : 2) / 256 * 256;   // (a third each of a checked job's three tables)
         dense.cap = std::min({dense.cap, half / sizeof(DenseImage), DENSE_MAX_IMAGES});
         cloud.cap = std::min({cloud.cap, half / sizeof(CloudImage), DENSE_MAX_IMAGES});
         cloud.h = reinterpret_cast<CloudImage*>(reinterpret_cast<uint8_t*>(cloud.h) + half);
@@ -169,7 +200,7 @@ int grp_export_cloud(svo_group* c, int what, int mem, const int* seqs, const int
         checks.d = reinterpret_cast<LrImage*>(reinterpret_cast<uint8_t*>(checks.d) + 2 * half);
         if (dense.cap < 1 || cloud.cap < 1) return svo_set_error(SVO_ERR_CAPACITY, "svo_submit_export_cloud: the argument blocks hold no image table");
         // (checked: one cap for all three, so that the tables fill and launch in step: search, check, count and write)
-        if (lr.on) dense.cap = cloud.cap = checks.cap = std::min(dense.cap, cloud.cap);
+        if (wta_check) dense.cap = cloud.cap = checks.cap = std::min(dense.cap, cloud.cap);
         dense_plan(sp, (long long)dense_tiles(search, c->width, c->height) * (long long)std::min<size_t>((size_t)shown, dense.cap));
         dense_grid = dense_tiles(sp, c->width, c->height);
         for (int j = 0; j < m; j++) {
@@ -181,8 +212,9 @@ int grp_export_cloud(svo_group* c, int what, int mem, const int* seqs, const int
             float* planes = reinterpret_cast<float*>(d_planes + (size_t)j * sg.planes);
             uint8_t* counts = d_counts + (size_t)j * sg.counts;
             svo_map_point* out = host ? reinterpret_cast<svo_map_point*>(d_records + (size_t)j * sg.records) : dst->points + e.first_point;
-            if (const int rc = dense.add(DenseImage{l.data, r.data, planes, l.stride, r.stride, l.w, l.h, q.cam.baseline, 0})) return rc;
-            if (lr.on)
+            if (!sgm)
+                if (const int rc = dense.add(DenseImage{l.data, r.data, planes, l.stride, r.stride, l.w, l.h, q.cam.baseline, 0})) return rc;
+            if (wta_check)
                 if (const int rc = checks.add(LrImage{l.data, r.data, reinterpret_cast<float*>(c->d_lr.p + (size_t)j * reverse), planes, nullptr,
                                                       l.stride, r.stride, l.w, l.h, q.cam.baseline, 0}))
                     return rc;

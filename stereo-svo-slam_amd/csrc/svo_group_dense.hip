@@ -26,49 +26,81 @@ int check_style(const svo_camera_settings* cam, int width, int height, const svo
     return SVO_OK;
 }
 
+}  // namespace
+
 // The SGM mode of the job (include/svo_hip.h, "sgm"): per chunk of delivered slots whose sums, volumes and count planes
 // fit the group's d_sgm block, the cost-volume launch and the two launches of the paths, which write the slots' planes.
 // The two image tables share the group's argument blocks, half each, and fill and launch in step. The stream orders a
 // chunk's launches before the next chunk's, so the chunks share the block.
-int export_sgm(svo_group* c, const std::vector<DenseImage>& images, const DenseParams& params, const SgmParams& sp, int cols, int rows) {
+// check ("sgm cross-check"): a slot of the block also holds the sums, volume, count plane and disparity plane of the
+// mirrored pair; a chunk of m slots has 2 m entries in the two tables, the mirrored pairs behind the forward ones (the
+// mirrored cost-volume launch takes the second half, the launches of the paths all of them), and a third table, a
+// third of the blocks each, carries the lattice check, which writes the lr plane (value + lr_plane floats) and masks and
+// converts the value plane in place (lr_plane < 0: no lr plane, a cloud job's mask). args_reused: the caller fills the
+// argument blocks again, so the last upload must be over on return.
+int svo::grp_sgm_planes(svo_group* c, const std::vector<DenseImage>& images, const DenseParams& params, SgmParams sp, int cols, int rows,
+                        const LrParams* check, int64_t lr_plane, bool args_reused) {
     if (images.empty()) return SVO_OK;
     const int D = params.search_x + 1;
-    const size_t volume = sgm_volume_bytes(cols, rows, D), slot = 2 * volume + sgm_count_bytes(cols, rows);
+    const size_t per = check ? 2 : 1;
+    const size_t volume = sgm_volume_bytes(cols, rows, D), one = 2 * volume + sgm_count_bytes(cols, rows);
+    const size_t slot = sgm_slot_bytes(cols, rows, D, check != nullptr);
     // (SVO_SGM_CHUNK_SLOTS: fewer slots per chunk, so that tests reach the chunked path)
     const size_t chunk = std::min(images.size(), table_tiles("SVO_SGM_CHUNK_SLOTS", std::max<size_t>(1, SGM_STAGING_BYTES / slot)));
     if (const int rc = c->d_sgm.reserve(c, chunk * slot)) return rc;
     DenseParams dp = params;
     int grid = 0;
     auto costs = group_tile_table<CostImage>(c, "SVO_DENSE_TABLE_IMAGES", [&](const CostImage* d, int m, hipStream_t s) {
-        launch_dense_cost_volume(d, m, grid, dp, sp.cost_cap, s);
+        launch_dense_cost_volume(d, m / (int)per, grid, dp, sp.cost_cap, s);
+        if (check) launch_dense_cost_volume_mirrored(d + m / 2, m / 2, grid, dp, sp.cost_cap, s);
     });
-    auto sums = group_tile_table<SgmImage>(c, "SVO_DENSE_TABLE_IMAGES", [&](const SgmImage* d, int m, hipStream_t s) { launch_sgm(d, m, cols, rows, sp, s); });
-    const size_t half = c->args.bytes / 2 / 256 * 256;
-    costs.cap = sums.cap = std::min({costs.cap, half / sizeof(CostImage), half / sizeof(SgmImage), DENSE_MAX_IMAGES, chunk});
-    sums.h = reinterpret_cast<SgmImage*>(reinterpret_cast<uint8_t*>(sums.h) + half);
-    sums.d = reinterpret_cast<SgmImage*>(reinterpret_cast<uint8_t*>(sums.d) + half);
-    if (costs.cap < 1) return svo_set_error(SVO_ERR_CAPACITY, "svo_submit_export_disparity_sgm: the argument blocks hold no image table");
-    dense_plan(dp, (long long)dense_tiles(params, c->width, c->height) * (long long)std::min(images.size(), costs.cap));
+    auto sums = group_tile_table<SgmImage>(c, "SVO_DENSE_TABLE_IMAGES", [&](const SgmImage* d, int m, hipStream_t s) {
+        sp.reverse_from = check ? m / 2 : 0;
+        launch_sgm(d, m, cols, rows, sp, s);
+    });
+    auto checks = group_tile_table<LrImage>(c, "SVO_DENSE_TABLE_IMAGES", [&](const LrImage* d, int m, hipStream_t s) {
+        launch_lr_check_lattice(d, m, lr_tiles((int64_t)cols * rows), *check, s);
+    });
+    const size_t part = c->args.bytes / (check ? 3 : 2) / 256 * 256;
+    const size_t cap = std::min({costs.cap, part / sizeof(CostImage) / per, part / sizeof(SgmImage) / per, DENSE_MAX_IMAGES / per, chunk,
+                                 check ? part / sizeof(LrImage) : chunk});
+    sums.h = reinterpret_cast<SgmImage*>(reinterpret_cast<uint8_t*>(sums.h) + part);
+    sums.d = reinterpret_cast<SgmImage*>(reinterpret_cast<uint8_t*>(sums.d) + part);
+    checks.h = reinterpret_cast<LrImage*>(reinterpret_cast<uint8_t*>(checks.h) + 2 * part);
+    checks.d = reinterpret_cast<LrImage*>(reinterpret_cast<uint8_t*>(checks.d) + 2 * part);
+    if (cap < 1) return svo_set_error(SVO_ERR_CAPACITY, "svo_submit_export_disparity_sgm: the argument blocks hold no image table");
+    dense_plan(dp, (long long)dense_tiles(params, c->width, c->height) * (long long)std::min(images.size(), cap));
     grid = dense_tiles(dp, c->width, c->height);
-    for (const DenseImage& im : images) {
-        if (costs.m == costs.cap) {                        // (a chunk is full: its launches go first)
-            if (const int rc = costs.launch(true)) return rc;
-            if (const int rc = sums.launch(true)) return rc;
+    for (size_t i0 = 0; i0 < images.size(); i0 += cap) {
+        const size_t m = std::min(cap, images.size() - i0);
+        for (size_t k = 0; k < m; k++) {
+            const DenseImage& im = images[i0 + k];
+            uint8_t* const at = c->d_sgm.p + k * slot;     // sums | volume | count plane [| the same of the mirrored pair | its disparity plane]
+            uint16_t* const vol = reinterpret_cast<uint16_t*>(at + volume);
+            uint16_t* const count = reinterpret_cast<uint16_t*>(at + 2 * volume);
+            costs.h[k] = CostImage{im.left, im.right, vol, count, im.left_stride, im.right_stride, im.w, im.h};
+            sums.h[k] = SgmImage{vol, count, reinterpret_cast<uint16_t*>(at), im.out, cols, rows, D, im.baseline};
+            if (!check) continue;
+            uint16_t* const rvol = reinterpret_cast<uint16_t*>(at + one + volume);
+            uint16_t* const rcount = reinterpret_cast<uint16_t*>(at + one + 2 * volume);
+            float* const rev = reinterpret_cast<float*>(at + 2 * one);
+            costs.h[m + k] = CostImage{im.left, im.right, rvol, rcount, im.left_stride, im.right_stride, im.w, im.h};
+            sums.h[m + k] = SgmImage{rvol, rcount, reinterpret_cast<uint16_t*>(at + one), rev, cols, rows, D, im.baseline};
+            checks.h[k] = LrImage{im.left, im.right, rev, im.out, lr_plane < 0 ? nullptr : im.out + lr_plane, im.left_stride, im.right_stride, im.w, im.h, im.baseline, 0};
         }
-        uint8_t* const at = c->d_sgm.p + costs.m * slot;   // sums | volume | count plane
-        uint16_t* const vol = reinterpret_cast<uint16_t*>(at + volume);
-        uint16_t* const count = reinterpret_cast<uint16_t*>(at + 2 * volume);
-        if (const int rc = costs.add(CostImage{im.left, im.right, vol, count, im.left_stride, im.right_stride, im.w, im.h})) return rc;
-        if (const int rc = sums.add(SgmImage{vol, count, reinterpret_cast<uint16_t*>(at), im.out, cols, rows, D, im.baseline})) return rc;
+        const bool more = args_reused || i0 + m < images.size();   // (a chunk is full: its launches go first)
+        costs.m = sums.m = per * m;
+        if (const int rc = costs.launch(more)) return rc;
+        if (const int rc = sums.launch(more)) return rc;
+        if (check) {
+            checks.m = m;
+            if (const int rc = checks.launch(more)) return rc;
+        }
     }
-    if (const int rc = costs.launch(false)) return rc;
-    return sums.launch(false);
+    return SVO_OK;
 }
 
-}  // namespace
-
-int grp_check_disparity_sgm(const svo_group* c, const svo_disparity_style* style, const svo_sgm_params* sgm) {
-    const char* who = "svo_submit_export_disparity_sgm";
+int grp_check_disparity_sgm(const svo_group* c, const svo_disparity_style* style, const svo_sgm_params* sgm, const char* who) {
     DenseParams p;
     if (const int rc = check_style(&c->cam, c->width, c->height, style, who, &p)) return rc;
     if (p.search_x + 1 > SGM_MAX_D) return svo_set_error(SVO_ERR_INVALID, "%s: search_x %d: at most %d with a cost volume", who, p.search_x, SGM_MAX_D - 1);
@@ -116,7 +148,8 @@ int64_t grp_disparity_bytes(const svo_group* c, const svo_disparity_style* style
 // chunk of delivered slots whose reverse planes fit the group's d_lr block, runs the reverse search and the check,
 // which appends the lr plane and masks and converts the value plane in place. The stream orders a chunk's check before
 // the next chunk's reverse search, so the chunks share the block without a wait of the host.
-// An SGM job (sgm != null; never checked) leaves the image table empty and delivers through export_sgm.
+// An SGM job (sgm != null) leaves the image table empty and delivers through grp_sgm_planes, its check included (another
+// rule, "sgm cross-check": no reverse search of this function and no d_lr block).
 int grp_export_disparity(svo_group* c, int what, int mem, const int* seqs, const int* seg, int n, int seq0,
                          const svo_disparity_style* style, const svo_stereo_check* check, const svo_sgm_params* sgm,
                          const svo_disparity_dst* dst) {
@@ -135,7 +168,7 @@ int grp_export_disparity(svo_group* c, int what, int mem, const int* seqs, const
         sgm_params.value = params.value;
         sgm_params.cost = params.cost;
     }
-    std::vector<DenseImage> sgm_images;                    // (an SGM job: the delivered slots, for export_sgm)
+    std::vector<DenseImage> sgm_images;                    // (an SGM job: the delivered slots, for grp_sgm_planes)
     int cols, rows, planes; int64_t image_bytes;
     dense_shape(params, c->width, c->height, &cols, &rows, &planes, &image_bytes, lr.on);
     const int64_t used = (int64_t)planes * cols * rows * 4;   // bytes of a slot's planes
@@ -180,13 +213,14 @@ int grp_export_disparity(svo_group* c, int what, int mem, const int* seqs, const
         if (const int rc = table.add(image)) return rc;
     }
     if (sgm)
-        if (const int rc = export_sgm(c, sgm_images, params, sgm_params, cols, rows)) return rc;
+        if (const int rc = grp_sgm_planes(c, sgm_images, params, sgm_params, cols, rows, lr.on ? &lr_params : nullptr, (int64_t)(planes - 1) * cols * rows, false))
+            return rc;
     if (table.m == (size_t)std::count(shown.begin(), shown.end(), 1)) {   // (one launch: sized by what it holds)
         dense_plan(params, (long long)tiles * (long long)table.m);
         tiles = dense_tiles(params, c->width, c->height);
     }
     if (const int rc = table.launch(lr.on)) return rc;    // (checked: the argument blocks are filled again)
-    if (lr.on) {
+    if (lr.on && !sgm) {
         const size_t reverse = lr_reverse_bytes(c->width, c->height, params.step);
         // (SVO_LR_CHUNK_SLOTS: fewer slots per chunk, so that tests reach the chunked path)
         const size_t chunk = std::min<size_t>((size_t)n, table_tiles("SVO_LR_CHUNK_SLOTS", std::max<size_t>(1, LR_STAGING_BYTES / reverse)));

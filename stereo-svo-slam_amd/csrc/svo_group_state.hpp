@@ -362,8 +362,9 @@ struct svo_group {
     // cross-check (a checked grp_export_disparity or grp_export_cloud): the reverse planes of one chunk of a job, made
     // by the first checked job and replaced when outgrown
     svo::GrowBlock<uint8_t> d_lr;
-    // semi-global aggregation (an SGM grp_export_disparity): the sums, volumes and count planes of one chunk of a job,
-    // made by the first SGM job and replaced when outgrown
+    // semi-global aggregation (an SGM grp_export_disparity or grp_export_cloud): the sums, volumes and count planes of
+    // one chunk of a job, with a check also those of the mirrored pairs and their disparity planes, made by the first
+    // SGM job and replaced when outgrown
     svo::GrowBlock<uint8_t> d_sgm;
     // voxel maps (svo_group_voxel.hip): a map per slot that has one (svo_ctx_set_voxel_maps; empty until then) with
     // the host mirror of its header; the records of one chunk of a fuse job and its tables (maps | headers | spans,
@@ -448,7 +449,7 @@ TileTable<Tile, Launch> group_tile_table(svo_group* c, const char* env, Launch r
             table_tiles(env, c->args.bytes / sizeof(Tile)), c->stream.get(), run};
 }
 
-// what one unit of the group implements for the others (svo_group.hip all of it)
+// what one unit of the group implements for the others (svo_group.hip all of it but the last)
 size_t align_up(size_t v, size_t a);
 void dev_release(svo_group* c, void* p, size_t bytes);                 // gives an allocation of dev_alloc back
 // Host-mode delivery of a job whose named slot seg[i] owns image_bytes at seg[i] * image_bytes of the caller's `to` and
@@ -462,6 +463,13 @@ int reject_if_failed(const svo_group* c, const char* who);
 // how a job that reads the slots' poses begins: reject_if_failed, the group's device, the deferred pose-filter updates
 int job_begin(svo_group* c, const char* who);
 int acquire_set(svo_group* c, Seq& q, ImageSet** out);
+// The SGM planes of `images` (svo_group_dense.hip): value [, cost] at each image's out, computed through the group's
+// d_sgm block and argument blocks, enqueued on the group's stream. sp: the checked params with the value and cost of
+// the planes. check: the lattice check of "sgm cross-check" behind them (sp.value is SVO_DENSE_DISPARITY then), which
+// writes the lr plane at out + lr_plane floats (< 0: none) and masks and converts the value plane; null: none.
+// args_reused: the caller fills the argument blocks again, so the uploads are over on return.
+int grp_sgm_planes(svo_group* c, const std::vector<DenseImage>& images, const DenseParams& params, SgmParams sp, int cols, int rows,
+                   const LrParams* check, int64_t lr_plane, bool args_reused);
 void release_set(Seq& q, ImageSet*& s);
 int take_kf_slab(svo_group* c, KpsDev* out);
 void fill_kf_record(const svo_group* c, const Seq& q, int id, const KfHost& k, KfDev& d);

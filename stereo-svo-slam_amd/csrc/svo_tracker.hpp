@@ -411,6 +411,10 @@ void launch_dense_reverse(const LrImage* d_images, int n, int tiles, const Dense
 constexpr int LR_TILE = 1024;
 constexpr int lr_tiles(int64_t points) { return (int)((points + LR_TILE - 1) / LR_TILE); }
 void launch_lr_check(const LrImage* d_images, int n, int tiles, const LrParams& p, hipStream_t stream);
+// the lattice form (include/svo_hip.h, "sgm cross-check"): out is cols x rows floats, the disparity of the mirrored
+// pair's lattice point at [iy][ixm], and the check gathers ixm = min((w - 1 - xr) / step, cols - 1); left and right
+// are not read
+void launch_lr_check_lattice(const LrImage* d_images, int n, int tiles, const LrParams& p, hipStream_t stream);
 
 // ------------------------------------------------------------ semi-global aggregation (dense.hip's cost-volume kernel, sgm.hip)
 // One image pair of a cost-volume launch: the two gray planes as in DenseImage; vol: uint16 [rows][cols][D] with
@@ -425,6 +429,9 @@ struct CostImage {
 // the cost volumes of n images (<= DENSE_MAX_IMAGES): launch_dense's grid over the same images and params (value and
 // cost of p are not read), search_x <= 63
 void launch_dense_cost_volume(const CostImage* d_images, int n, int tiles, const DenseParams& p, int cost_cap, hipStream_t stream);
+// the same over the mirrored, swapped planes Lm[y][u] = R[y][w - 1 - u], Rm[y][u] = L[y][w - 1 - u] of every image:
+// the volume and count plane of the mirrored pair's lattice, which is the lattice "dense" gives it
+void launch_dense_cost_volume_mirrored(const CostImage* d_images, int n, int tiles, const DenseParams& p, int cost_cap, hipStream_t stream);
 // One volume of an aggregation: vol and count as above (count null: every point has D candidates), sum: the block of
 // S, uint16 [rows][cols][D], written by the first launch and read by the second; out: the value plane and, with cost,
 // the cost plane behind it (cols x rows floats each); the baseline of SVO_DENSE_DEPTH.
@@ -436,15 +443,24 @@ struct SgmImage {
     int cols, rows, D;
     float baseline;
 };
-// a checked svo_sgm_params with the value and cost of the style
+// a checked svo_sgm_params with the value and cost of the style. reverse_from > 0: the table entries from that index
+// on are the reverse volumes of a checked job: they write their disparity alone whatever value and cost say
 struct SgmParams {
     int p1, p2, cost_cap, subpixel, value, cost;
+    int reverse_from;
 };
 int sgm_check_params(const svo_sgm_params* sgm, const char* who, SgmParams* out);
 constexpr int SGM_MAX_D = 64;
 // the bytes of one volume or one block of S (a multiple of 256), and of one count plane
 inline size_t sgm_volume_bytes(int cols, int rows, int D) { return ((size_t)cols * (size_t)rows * (size_t)D * 2 + 255) / 256 * 256; }
 inline size_t sgm_count_bytes(int cols, int rows) { return ((size_t)cols * (size_t)rows * 2 + 255) / 256 * 256; }
+// the bytes of the reverse disparity plane of a checked SGM map, and what one image of an SGM map stages in all:
+// sums, volume and count plane, and with a check those of the mirrored pair and its disparity plane
+inline size_t sgm_reverse_bytes(int cols, int rows) { return ((size_t)cols * (size_t)rows * 4 + 255) / 256 * 256; }
+inline size_t sgm_slot_bytes(int cols, int rows, int D, bool checked) {
+    const size_t one = 2 * sgm_volume_bytes(cols, rows, D) + sgm_count_bytes(cols, rows);
+    return checked ? 2 * one + sgm_reverse_bytes(cols, rows) : one;
+}
 // the four paths and the value rule of n volumes (<= DENSE_MAX_IMAGES): two launches, rows then columns, ordered by
 // the stream; max_cols / max_rows: the largest lattice of the table
 void launch_sgm(const SgmImage* d_images, int n, int max_cols, int max_rows, const SgmParams& p, hipStream_t stream);
@@ -469,9 +485,11 @@ struct CloudImage {
     float* mats;       // 12 floats of the image's own: the pose's float rotation matrix and translation (the count launch writes them, the write launch reads them)
 };
 // what a launch computes, from a checked svo_cloud_style whose win is resolved
+// (sgm_cost = 1: the planes are an SGM map's, whose cost is per pixel already: max_mean_cost drops best > max_mean_cost * 4.0f)
 struct CloudParams {
     int step, win, frame, layout;
     float min_disparity, max_depth, max_mean_cost;
+    int sgm_cost;
 };
 // what a cloud job, svo_cloud_size and the stage entry check alike (win / search_x / search_y as dense_check_style):
 // the search of the job into *search (a disparity plane and a cost plane), the rest into *out

@@ -48,6 +48,8 @@ SYMBOLS = (
     "svo_cloud_points_checked",
     "svo_submit_export_disparity_sgm", "svo_export_disparity_sgm",
     "svo_dense_cost_volume", "svo_sgm_aggregate", "svo_dense_disparity_sgm",
+    "svo_submit_export_disparity_sgm_checked", "svo_export_disparity_sgm_checked", "svo_dense_disparity_sgm_checked",
+    "svo_submit_export_cloud_sgm", "svo_export_cloud_sgm", "svo_cloud_points_sgm",
     "svo_scene_size", "svo_scene_look_at", "svo_scene_frustum", "svo_submit_export_scenes", "svo_export_scenes",
     "svo_render_scene",
     "svo_submit_export_scenes_clouds", "svo_export_scenes_clouds", "svo_render_scene_clouds",
@@ -465,6 +467,21 @@ SGM_DEFAULTS = dict(p1=64, p2=256, cost_cap=4095, subpixel=True)
 def sgm_params(p1, p2, cost_cap, subpixel=True):
     """an SgmParams of four paths"""
     return SgmParams(4, int(p1), int(p2), int(cost_cap), int(bool(subpixel)))
+
+
+def sgm_job(sgm):
+    """sgm of submit_disparity / submit_cloud as (SgmParams, StereoCheck or None). None or False: (None, None); True:
+    SGM_DEFAULTS; an SgmParams: itself, unchecked; a dict with p1, p2, cost_cap and, if wanted, subpixel and lr_check.
+    lr_check is the cross-check of the SGM map (include/svo_hip.h, "sgm cross-check": a second SGM map of the mirrored
+    pair, another rule than the top-level lr_check=): None or False: off; True: report only; a number: the tolerance"""
+    if sgm is None or sgm is False:
+        return None, None
+    if isinstance(sgm, SgmParams):
+        return sgm, None
+    fields = dict(SGM_DEFAULTS if sgm is True else sgm)
+    lr = fields.pop("lr_check", None)
+    check = None if lr is None or lr is False else stereo_check(True, 0.0 if lr is True else float(lr))
+    return sgm_params(**fields), check
 
 
 def disparity_size(cam, width, height, style, check=None):
@@ -1321,12 +1338,19 @@ class Handle:
         _check(lib().svo_sgm_aggregate(self._h, n, sh, vols, cnts, int(value), int(bool(cost)), C.byref(sgm), offs,
                                        C.c_void_p(addr(values))))
 
-    def dense_disparity_sgm(self, srcs, offsets, style, sgm, values):
-        """svo_dense_disparity_sgm: dense_disparity with semi-global aggregation and sub-pixel values (sgm: an
-        SgmParams; style.search_x <= 63). Complete on return."""
-        packed = self.pack_dense(srcs, offsets)
+    def dense_disparity_sgm_packed(self, packed, style, sgm, values, check=None):
         p = values.data_ptr() if isinstance(values, torch.Tensor) else int(values)
-        _check(lib().svo_dense_disparity_sgm(self._h, packed[0], packed[1], packed[2], C.byref(style), C.byref(sgm), C.c_void_p(p)))
+        if check is None:
+            _check(lib().svo_dense_disparity_sgm(self._h, packed[0], packed[1], packed[2], C.byref(style), C.byref(sgm), C.c_void_p(p)))
+        else:
+            _check(lib().svo_dense_disparity_sgm_checked(self._h, packed[0], packed[1], packed[2], C.byref(style), C.byref(sgm),
+                                                         C.byref(check), C.c_void_p(p)))
+
+    def dense_disparity_sgm(self, srcs, offsets, style, sgm, values, check=None):
+        """svo_dense_disparity_sgm: dense_disparity with semi-global aggregation and sub-pixel values (sgm: an
+        SgmParams; style.search_x <= 63). check: a StereoCheck (svo_dense_disparity_sgm_checked: the cross-check of
+        the SGM map, the lr plane appended), or None. Complete on return."""
+        self.dense_disparity_sgm_packed(self.pack_dense(srcs, offsets), style, sgm, values, check)
 
     def pack_cloud(self, srcs, first):
         """the argument arrays of cloud_points, built once (keeps Python out of a timed loop)"""
@@ -1356,6 +1380,18 @@ class Handle:
         counts: an int32 device tensor [n] (or address) for the kept counts, or None. check: a StereoCheck
         (svo_cloud_points_checked: failing points are dropped), or None. Complete on return."""
         self.cloud_points_packed(self.pack_cloud(srcs, first), style, points, counts, check)
+
+    def cloud_points_sgm_packed(self, packed, style, sgm, points, counts=None, check=None):
+        p = points.data_ptr() if isinstance(points, torch.Tensor) else int(points)
+        c = None if counts is None else C.c_void_p(counts.data_ptr() if isinstance(counts, torch.Tensor) else int(counts))
+        _check(lib().svo_cloud_points_sgm(self._h, packed[0], packed[1], packed[2], C.byref(style), C.byref(sgm),
+                                          None if check is None else C.byref(check), C.c_void_p(p), c))
+
+    def cloud_points_sgm(self, srcs, first, style, sgm, points, counts=None, check=None):
+        """svo_cloud_points_sgm: cloud_points over SGM maps (sgm: an SgmParams; style.search_x <= 63; max_mean_cost
+        bounds the aggregated cost over its four paths). check: a StereoCheck with a tolerance (the cross-check of the
+        SGM map: failing points are dropped), or None. Complete on return."""
+        self.cloud_points_sgm_packed(self.pack_cloud(srcs, first), style, sgm, points, counts, check)
 
     # -- voxel maps ---------------------------------------------------------
     def voxel_new(self, params, device="cuda"):

@@ -287,6 +287,10 @@ class Views(PictureJob):
         return lib().svo_submit_export_views(ctx, self.what, self._seq_arr, self._n, C.byref(self.style), C.byref(self._dst), mem)
 
 
+SGM_AND_LR_CHECK = ("lr_check= is the cross-check of the winner-takes-all search; the cross-check of an SGM job is the "
+                    "lr_check key of its sgm dict, e.g. sgm=dict(hip_lib.SGM_DEFAULTS, lr_check=1.0)")
+
+
 def _check_that_is_on(check):
     """a hip_lib.StereoCheck that is on, or None: a job without one goes through the unchecked entry"""
     return check if check is not None and check.lr else None
@@ -300,13 +304,17 @@ class Disparities(Job):
     of every slot of the job (svo_disparity_size). A checked job (check: a hip_lib.StereoCheck that is on) goes through
     svo_submit_export_disparity_checked; its last plane is the lr plane, lr(i). An SGM job (sgm: a hip_lib.SgmParams)
     goes through svo_submit_export_disparity_sgm: the same planes with semi-global aggregation and sub-pixel values;
-    together with a check that is on it raises ValueError."""
+    with sgm_check (a StereoCheck that is on: the cross-check of the SGM map, the lr_check key of the sgm dict) through
+    svo_submit_export_disparity_sgm_checked, and lr(i) is its lr plane. sgm together with a top-level check that is
+    on raises ValueError: the two checks are different rules."""
 
-    def __init__(self, slam, what, seqs, style, device, check=None, sgm=None):
+    def __init__(self, slam, what, seqs, style, device, check=None, sgm=None, sgm_check=None):
         n = self._name(slam, seqs, device)
         self.what, self.style, self.check, self.sgm = int(what), style, _check_that_is_on(check), sgm
         if self.check is not None and sgm is not None:
-            raise ValueError("a disparity job is checked or SGM, not both")
+            raise ValueError(SGM_AND_LR_CHECK)
+        if sgm is not None:
+            self.check = _check_that_is_on(sgm_check)
         self.cols, self.rows, self.n_planes, self.image_bytes = slam.disparity_size(style, self.check)
         self.capacity = n * self.image_bytes
         self._segments(hip_lib.DISPARITY_SEGMENT_DTYPE)
@@ -320,6 +328,9 @@ class Disparities(Job):
         return v if self.device_mode else v.numpy()
 
     def _call(self, ctx, mem):
+        if self.sgm is not None and self.check is not None:
+            return lib().svo_submit_export_disparity_sgm_checked(ctx, self.what, self._seq_arr, self._n, C.byref(self.style),
+                                                                 C.byref(self.sgm), C.byref(self.check), C.byref(self._dst), mem)
         if self.sgm is not None:
             return lib().svo_submit_export_disparity_sgm(ctx, self.what, self._seq_arr, self._n, C.byref(self.style),
                                                          C.byref(self.sgm), C.byref(self._dst), mem)
@@ -348,11 +359,17 @@ class Clouds(PointJob):
     (hip_lib.CLOUD_SEGMENT_DTYPE, one per named slot), points(i) and, in the organized layout, organized(i).
     `points_buffer`: PointJob (points(i) / organized(i) copy a device-mode slot's records to the host). cols, rows,
     points_per_slot: the lattice of every slot of the job (svo_cloud_size). A checked job (check: a hip_lib.StereoCheck
-    that is on) goes through svo_submit_export_cloud_checked."""
+    that is on) goes through svo_submit_export_cloud_checked. An SGM job (sgm: a hip_lib.SgmParams; sgm_check: the
+    cross-check of the SGM map, or None) goes through svo_submit_export_cloud_sgm; sgm together with a top-level check
+    that is on raises ValueError."""
 
-    def __init__(self, slam, what, seqs, style, device, check=None):
+    def __init__(self, slam, what, seqs, style, device, check=None, sgm=None, sgm_check=None):
         n = self._name(slam, seqs, device)
-        self.what, self.style, self.check = int(what), style, _check_that_is_on(check)
+        self.what, self.style, self.check, self.sgm = int(what), style, _check_that_is_on(check), sgm
+        if self.check is not None and sgm is not None:
+            raise ValueError(SGM_AND_LR_CHECK)
+        if sgm is not None:
+            self.check = _check_that_is_on(sgm_check)
         self.cols, self.rows, self.points_per_slot = slam.cloud_size(style)
         self.capacity = n * self.points_per_slot
         self._segments(hip_lib.CLOUD_SEGMENT_DTYPE)
@@ -360,6 +377,9 @@ class Clouds(PointJob):
         self._dst = hip_lib.CloudDst(self._seg.ctypes.data, self.points_buffer.data_ptr(), self.capacity)
 
     def _call(self, ctx, mem):
+        if self.sgm is not None:
+            return lib().svo_submit_export_cloud_sgm(ctx, self.what, self._seq_arr, self._n, C.byref(self.style), C.byref(self.sgm),
+                                                     None if self.check is None else C.byref(self.check), C.byref(self._dst), mem)
         if self.check is None:
             return lib().svo_submit_export_cloud(ctx, self.what, self._seq_arr, self._n, C.byref(self.style),
                                                  C.byref(self._dst), mem)

@@ -30,7 +30,9 @@ The text overlay and the x2 resize of the window are not drawn.
 disparity (or depth) map of the frame's rectified pair at every S-th pixel. With --disparity-sgm P1,P2[,CAP] the map is
 aggregated semi-globally and the file stacks value and aggregated cost. With --disparity-lr D the map is
 cross-checked left-right and the file is [3, rows, cols]: the value (invalid where the two searches differ by more than
-D; D = 0 only reports), the cost and the lr plane. --cloud-lr D drops such points from the clouds of --dump-cloud.
+D; D = 0 only reports), the cost and the lr plane; together with --disparity-sgm the check is the SGM map's own (a
+second SGM map of the mirrored pair) and the file stacks value, aggregated cost and lr. --cloud-lr D drops such points
+from the clouds of --dump-cloud; --cloud-sgm P1,P2[,CAP] makes those the clouds of the SGM map (and --cloud-lr its check).
 --dump-cloud DIR [--cloud-step S] [--cloud-max-depth Z] writes, whenever the newest keyframe changes,
 DIR/kf000000_cloud.ply: the dense coloured point cloud of that keyframe in the world frame at every S-th pixel (binary
 little-endian PLY, x y z float and red green blue uchar), so that the files of a run together are a dense map of it.
@@ -425,7 +427,7 @@ class Replay:
                  ar_box=AR_BOX, ar_at=hip_lib.AR_AT, dump_disparity=None, disparity_step=4, disparity_depth=False,
                  dump_cloud=None, cloud_step=4, cloud_max_depth=0.0, disparity_lr=None, cloud_lr=None, scene_dense=None,
                  scene_dense_lr=None, scene_dense_max_depth=0.0, scene_accumulate=0, dump_dense_map=None, dense_map_voxel=None,
-                 dense_map_log2=20, dense_map_min_count=0, scene_fused=None, ar_occlusion=None, disparity_sgm=None):
+                 dense_map_log2=20, dense_map_min_count=0, scene_fused=None, ar_occlusion=None, disparity_sgm=None, cloud_sgm=None):
         """fast=False keeps the library default: the reference-order Gauss-Newton (bit-exact traces).
         rectify_maps = (left maps, right maps): the frames fed are raw and are rectified on the GPU.
         calibration = (left, right) CameraCalibrations: the same, with the maps built on the GPU as well.
@@ -454,7 +456,9 @@ class Replay:
         disparity_lr: None, or the tolerance of the left-right cross-check of dump_disparity (0: report only); the file
         is then [3, rows, cols]: value, cost, lr. disparity_sgm: None, or (p1, p2[, cost_cap]) of semi-global aggregation
         for dump_disparity (cost_cap: hip_lib.SGM_DEFAULTS'); the file is then [2, rows, cols]: value, aggregated cost;
-        not together with disparity_lr. cloud_lr: None, or the tolerance (> 0) of the cross-check of dump_cloud.
+        together with disparity_lr the SGM map is cross-checked by its own rule and the file is [3, rows, cols]: value,
+        aggregated cost, lr. cloud_lr: None, or the tolerance (> 0) of the cross-check of dump_cloud. cloud_sgm: None, or
+        (p1, p2[, cost_cap]): dump_cloud writes the clouds of the SGM map, cloud_lr then being the SGM map's own check.
         dump_dense_map: a PLY file that receives, at finish(), the slot's voxel map (get_voxel_map with
         dense_map_min_count): every new keyframe's dense cloud (cloud_step, cloud_lr, cloud_max_depth) is fused into a map
         of edge dense_map_voxel and 1 << dense_map_log2 entries kept inside the ctx. scene_fused = V: dump_scene draws
@@ -467,13 +471,16 @@ class Replay:
         self.dump_disparity, self.disparity_step, self.disparity_depth = dump_disparity, int(disparity_step), bool(disparity_depth)
         self.dump_cloud, self.cloud_step, self.cloud_max_depth, self._cloud_kf = dump_cloud, int(cloud_step), float(cloud_max_depth), -1
         self.disparity_lr = None if disparity_lr is None else float(disparity_lr)
-        self.disparity_sgm = None
-        if disparity_sgm is not None:
-            if disparity_lr is not None:
-                raise ValueError("disparity_sgm and disparity_lr exclude each other")
-            p = [int(v) for v in disparity_sgm]
-            self.disparity_sgm = dict(p1=p[0], p2=p[1], cost_cap=p[2] if len(p) > 2 else hip_lib.SGM_DEFAULTS["cost_cap"])
+
+        def sgm_dict(spec, lr):
+            """(p1, p2[, cost_cap]) and the tolerance of the SGM map's own check (None: off; 0: report only) as sgm="""
+            p = [int(v) for v in spec]
+            return dict(p1=p[0], p2=p[1], cost_cap=p[2] if len(p) > 2 else hip_lib.SGM_DEFAULTS["cost_cap"],
+                        lr_check=None if lr is None else (lr if lr > 0 else True))
+
+        self.disparity_sgm = None if disparity_sgm is None else sgm_dict(disparity_sgm, self.disparity_lr)
         self.cloud_lr = None if cloud_lr is None else float(cloud_lr)
+        self.cloud_sgm = None if cloud_sgm is None else sgm_dict(cloud_sgm, self.cloud_lr)
         self.scene_dense = None if scene_dense is None else int(scene_dense)
         self.scene_dense_lr = None if scene_dense_lr is None else float(scene_dense_lr)
         self.scene_dense_max_depth, self.scene_accumulate = float(scene_dense_max_depth), int(scene_accumulate)
@@ -575,7 +582,7 @@ class Replay:
             if kf != self._cloud_kf:
                 self._cloud_kf = kf
                 points = self.slam.get_cloud("last_keyframes", step=self.cloud_step, max_depth=self.cloud_max_depth,
-                                             lr_check=self.cloud_lr)
+                                             **(dict(lr_check=self.cloud_lr) if self.cloud_sgm is None else dict(sgm=self.cloud_sgm)))
                 if points is not None:
                     write_ply(os.path.join(self.dump_cloud, f"kf{kf:06d}_cloud.ply"), points)
         if self.dense_map_voxel is not None and not self.dump_scene:
@@ -708,7 +715,8 @@ def build_parser():
     ap.add_argument("--disparity-depth", action="store_true", help="--dump-disparity writes depth, baseline / disparity (0: none)")
     ap.add_argument("--disparity-sgm", metavar="P1,P2[,CAP]", default=None,
                     help="--dump-disparity aggregates semi-globally with these penalties (and cost cap) and writes "
-                         "[2, rows, cols]: the sub-pixel value and the aggregated cost; needs a search_x <= 63")
+                         "[2, rows, cols]: the sub-pixel value and the aggregated cost; needs a search_x <= 63; with "
+                         "--disparity-lr D the SGM map is cross-checked by its own rule and the lr plane is stacked behind them")
     ap.add_argument("--disparity-lr", metavar="D", type=float, default=None,
                     help="--dump-disparity cross-checks left-right and writes [3, rows, cols]: the value (invalid where the "
                          "two searches differ by more than D; 0: report only), the cost and the lr plane")
@@ -718,6 +726,9 @@ def build_parser():
     ap.add_argument("--cloud-step", metavar="S", type=int, default=4, help="lattice of --dump-cloud: every S-th pixel, 1 .. 16")
     ap.add_argument("--cloud-lr", metavar="D", type=float, default=None,
                     help="--dump-cloud drops points whose left-right cross-check differs by more than D (> 0)")
+    ap.add_argument("--cloud-sgm", metavar="P1,P2[,CAP]", default=None,
+                    help="--dump-cloud writes the clouds of the semi-globally aggregated map with these penalties (and cost cap); "
+                         "--cloud-lr D is then the SGM map's own cross-check; needs a search_x <= 63")
     ap.add_argument("--cloud-max-depth", metavar="Z", type=float, default=0.0,
                     help="--dump-cloud drops points deeper than Z in the camera frame (0: none)")
     ap.add_argument("--dump-dense-map", metavar="FILE.ply",
@@ -827,6 +838,7 @@ def main(argv=None):
                 disparity_depth=args.disparity_depth, dump_cloud=args.dump_cloud, cloud_step=args.cloud_step,
                 cloud_max_depth=args.cloud_max_depth, disparity_lr=args.disparity_lr, cloud_lr=args.cloud_lr,
                 disparity_sgm=None if args.disparity_sgm is None else args.disparity_sgm.split(","),
+                cloud_sgm=None if args.cloud_sgm is None else args.cloud_sgm.split(","),
                 scene_dense=args.scene_dense, scene_dense_lr=args.scene_dense_lr, scene_dense_max_depth=args.scene_dense_max_depth,
                 scene_accumulate=args.scene_accumulate, dump_dense_map=args.dump_dense_map, dense_map_voxel=args.dense_map_voxel,
                 dense_map_log2=args.dense_map_log2, dense_map_min_count=args.dense_map_min_count, scene_fused=args.scene_fused,

@@ -372,13 +372,8 @@ class StereoSlamBatch:
 
     @staticmethod
     def _sgm_params(sgm):
-        """sgm of submit_disparity as a hip_lib.SgmParams: None or False: off; True: hip_lib.SGM_DEFAULTS; a dict with
-        p1, p2, cost_cap and, if wanted, subpixel; or an SgmParams"""
-        if sgm is None or sgm is False:
-            return None
-        if isinstance(sgm, hip_lib.SgmParams):
-            return sgm
-        return hip_lib.sgm_params(**(hip_lib.SGM_DEFAULTS if sgm is True else dict(sgm)))
+        """sgm of submit_disparity / submit_cloud as (hip_lib.SgmParams, hip_lib.StereoCheck or None): hip_lib.sgm_job"""
+        return hip_lib.sgm_job(sgm)
 
     def submit_disparity(self, what="frames", seqs=None, value="disparity", step=1, win=0, search_x=0, search_y=0,
                          cost=False, device=False, style=None, lr_check=None, sgm=None):
@@ -388,15 +383,17 @@ class StereoSlamBatch:
         search_y: 0 takes the ctx's settings; cost: a second plane with the minimum SSD; style: a
         hip_lib.DisparityStyle instead of all these; lr_check: the left-right cross-check (True: the lr plane is
         appended; a tolerance: values that differ by more are set invalid as well; default off); sgm: semi-global
-        aggregation and sub-pixel values (True: hip_lib.SGM_DEFAULTS; or dict(p1=, p2=, cost_cap=, subpixel=); search_x
-        <= 63; the cost plane then holds the aggregated cost; not together with lr_check: ValueError; default off).
+        aggregation and sub-pixel values (True: hip_lib.SGM_DEFAULTS; or dict(p1=, p2=, cost_cap=, subpixel=,
+        lr_check=); search_x <= 63; the cost plane then holds the aggregated cost; the dict's lr_check (None, True or a
+        tolerance, as the top-level one) is the cross-check of the SGM map, a second SGM map of the mirrored pair, e.g.
+        sgm=dict(hip_lib.SGM_DEFAULTS, lr_check=1.0); the top-level lr_check together with sgm: ValueError; default off).
         Returns a Disparities, valid after its wait() (or the ctx's); its submit() queues the same job again into the
         same buffers."""
         if isinstance(what, str):
             what = hip_lib.EXPORT_WHAT.index(what)
         if style is None:
             style = hip_lib.disparity_style(value, step, win, search_x, search_y, cost)
-        return Disparities(self, what, seqs, style, device, self._stereo_check(lr_check), self._sgm_params(sgm)).submit()
+        return Disparities(self, what, seqs, style, device, self._stereo_check(lr_check), *self._sgm_params(sgm)).submit()
 
     def export_disparity(self, what="frames", seqs=None, **kw):
         """submit_disparity + wait"""
@@ -407,19 +404,21 @@ class StereoSlamBatch:
         return hip_lib.cloud_size(self.cam, self.width, self.height, style)
 
     def submit_cloud(self, what="frames", seqs=None, step=1, win=0, search_x=0, search_y=0, frame="world", layout="compact",
-                     min_disparity=0.0, max_depth=0.0, max_mean_cost=0.0, device=False, style=None, lr_check=None):
+                     min_disparity=0.0, max_depth=0.0, max_mean_cost=0.0, device=False, style=None, lr_check=None, sgm=None):
         """svo_submit_export_cloud: queue a dense coloured point cloud of the current frames (what="frames") or newest
         keyframes ("last_keyframes") of the slots `seqs` (None: all, in order) behind what was submitted so far;
         nothing is waited for. step, win, search_x, search_y: as submit_disparity; frame: "world" or "camera";
         layout: "compact" or "organized"; min_disparity, max_depth, max_mean_cost: the filter (0: off); style: a
         hip_lib.CloudStyle instead of all these; lr_check: a tolerance > 0 drops the points that fail the left-right
-        cross-check (default off). Returns a Clouds, valid after its wait() (or the ctx's); its submit()
+        cross-check (default off); sgm: as submit_disparity: the cloud of the SGM map (max_mean_cost then bounds the
+        aggregated cost over its four paths; the dict's lr_check, a tolerance > 0, drops the points that fail the SGM
+        map's cross-check; the top-level lr_check together with sgm: ValueError; default off). Returns a Clouds, valid after its wait() (or the ctx's); its submit()
         queues the same job again into the same buffers."""
         if isinstance(what, str):
             what = hip_lib.EXPORT_WHAT.index(what)
         if style is None:
             style = hip_lib.cloud_style(step, win, search_x, search_y, frame, layout, min_disparity, max_depth, max_mean_cost)
-        return Clouds(self, what, seqs, style, device, self._stereo_check(lr_check)).submit()
+        return Clouds(self, what, seqs, style, device, self._stereo_check(lr_check), *self._sgm_params(sgm)).submit()
 
     def export_cloud(self, what="frames", seqs=None, **kw):
         """submit_cloud + wait"""

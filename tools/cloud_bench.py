@@ -10,6 +10,8 @@ and 4, 1, 16 and 256 images:
            and svo_dense_disparity with the cost plane on the same pairs (what the cloud adds is the difference). The
            bytes the two kernels move per image are counted from the statement (17 B per lattice point in, 16 B per kept
            point out) and set against 8 TB/s. Every shape is warmed up first; the legs alternate, median of `--repeats`.
+           With `--sgm P1,P2[,CAP]` a further leg: svo_cloud_points_sgm (the cloud of the SGM map) on the
+           same pairs, with `--checked D` under the SGM map's own cross-check as well.
   job      in a ctx of 256 slots after `--warmup` steps of bench.py's workload, for the first 1, 16 and 256 slots:
            a cloud job into device and into host memory, (a) a disparity job with the cost plane into device memory, and
            (b) the host path the cloud job replaces: export_disparity(value="disparity", cost=True) into host memory
@@ -99,6 +101,17 @@ def kernel_leg(args, device, cfg, lefts, rights):
                 checked()
                 torch.cuda.synchronize(device)
                 kept_checked = int(counts.sum().item())
+            sgm_legs, sgm_kept = {}, {}
+            if args.sgm:                                     # (the cloud of the SGM map, and under its own cross-check)
+                sp = hip_lib.sgm_params(args.sgm[0], args.sgm[1], args.sgm[2] if len(args.sgm) > 2 else hip_lib.SGM_DEFAULTS["cost_cap"])
+                sgm_legs["sgm_cloud"] = lambda: h.cloud_points_sgm_packed(packed, style, sp, points, counts)
+                if args.checked is not None:
+                    sgm_legs["sgm_checked_cloud"] = lambda: h.cloud_points_sgm_packed(packed, style, sp, points, counts, check)
+                for k, leg in sgm_legs.items():
+                    leg()
+                    torch.cuda.synchronize(device)
+                    sgm_kept[k] = int(counts.sum().item())
+            t_sgm = {k: [] for k in sgm_legs}
             cloud(); dense(); kernels()                      # warm-up of the legs
             torch.cuda.synchronize(device)
             kept = int(counts.sum().item())
@@ -109,6 +122,8 @@ def kernel_leg(args, device, cfg, lefts, rights):
                 t_kernels.append(event_ms(kernels))
                 if checked:
                     t_checked.append(event_ms(checked))
+                for k, leg in sgm_legs.items():
+                    t_sgm[k].append(event_ms(leg))
             c_ms, d_ms, k_ms = (statistics.median(t) / n for t in (t_cloud, t_dense, t_kernels))
             moved = 17 * P + 16 * kept / n                   # per image: both launches read the two planes, one reads the gray
             out["shapes"].append({"step": step, "images": n, "cols": cols, "rows": rows, "kept_fraction": kept / (n * P),
@@ -122,6 +137,12 @@ def kernel_leg(args, device, cfg, lefts, rights):
                 out["shapes"][-1].update({"checked_cloud_ms_per_image": statistics.median(t_checked) / n, "checked_cloud_call_ms_all": t_checked,
                                           "checked_over_cloud": statistics.median(t_checked) / n / c_ms, "max_lr_diff": args.checked,
                                           "checked_kept_fraction": kept_checked / (n * P)})
+            for k in sgm_legs:
+                ms = statistics.median(t_sgm[k]) / n
+                out["shapes"][-1].update({"sgm": args.sgm, f"{k}_ms_per_image": ms, f"{k}_call_ms_all": t_sgm[k], f"{k}_over_cloud": ms / c_ms,
+                                          f"{k}_kept_fraction": sgm_kept[k] / (n * P)})
+            if len(sgm_legs) == 2:
+                out["shapes"][-1]["sgm_checked_over_sgm_cloud"] = statistics.median(t_sgm["sgm_checked_cloud"]) / statistics.median(t_sgm["sgm_cloud"])
             print(json.dumps(out["shapes"][-1]), file=sys.stderr, flush=True)      # (progress)
             del points, planes
     h.close()
@@ -229,6 +250,8 @@ def main():
     ap.add_argument("--host-repeats", type=int, default=1, help="timed runs of the host path (seconds each at step 1)")
     ap.add_argument("--no-job", action="store_true", help="the kernel leg only")
     ap.add_argument("--checked", type=float, default=None, metavar="D", help="also time svo_cloud_points_checked at the tolerance D")
+    ap.add_argument("--sgm", type=lambda t: [int(x) for x in t.split(",")], default=None, metavar="P1,P2[,CAP]",
+                    help="also time svo_cloud_points_sgm with these penalties (with --checked D: under the SGM map's own cross-check too)")
     ap.add_argument("--out", default=None, help="also write the JSON result to this file")
     args = ap.parse_args()
     device = torch.device("cuda", 0)

@@ -20,6 +20,8 @@ One process, bench.py's rendered `euroc` stereo pairs (752 x 480), the EuRoC set
              alternating with the others: svo_dense_cost_volume (the cost-volume kernel), svo_sgm_aggregate on those
              volumes (the paths and the value rule; with the achieved bytes/s over 2 B of C and 4 B of S per entry and
              direction pair) and svo_dense_disparity_sgm (the whole stage entry). The baseline is dense_ms_per_image.
+             Together with `--checked D` a fourth leg: svo_dense_disparity_sgm_checked (the SGM map's own cross-check,
+             DESIGN §4.24, at the tolerance D), to be read against the unchecked whole (sgm_checked_over_sgm).
   job        frames/s over `--steps` queued steps of bench.py's workload without any job and with a device-mode
              step-4 disparity job of every slot queued behind every frame set; legs alternate, median of
              `--pipelined-repeats` each.
@@ -159,6 +161,11 @@ def kernel_leg(args, device, cfg, lefts, rights):
                                           "sgm_ms_per_image": ms["whole"], "sgm_call_ms_all": t_sgm,
                                           "paths_bytes_per_s": 2 * 6 * entries / (ms["paths"] * 1e-3),
                                           "cost_volume_over_dense": ms["cost_volume"] / d_ms, "sgm_over_dense": ms["whole"] / d_ms})
+                if "checked" in ms:
+                    lr = sgm["checked"].dst.view(n, 2, rows, cols)[:, 1]
+                    out["shapes"][-1].update({"sgm_checked_ms_per_image": ms["checked"], "sgm_checked_over_sgm": ms["checked"] / ms["whole"],
+                                              "sgm_checked_over_dense": ms["checked"] / d_ms, "max_lr_diff": args.checked,
+                                              "sgm_failing_fraction": float(((lr < 0) | (lr > args.checked)).float().mean().item())})
                 del sgm
             print(json.dumps(out["shapes"][-1]), file=sys.stderr, flush=True)      # (progress)
     h.close()
@@ -196,6 +203,19 @@ def sgm_legs(args, h, device, cfg, pairs, style, cols, rows):
     mine = dst.clone()
     legs["whole"]()                                        # (and the warm-up: the two-step result is the whole's)
     assert torch.equal(mine, dst)
+    if args.checked is not None:                           # value and lr planes per pair
+        check = hip_lib.stereo_check(True, args.checked)
+        dst_c = torch.empty(n * 2 * cols * rows, dtype=torch.float32, device=device)
+        packed_c = h.pack_dense([((l, W, H, l.stride(0)), (r, W, H, r.stride(0)), cfg["baseline"]) for l, r in pairs],
+                                [i * 2 * cols * rows * 4 for i in range(n)])
+
+        def checked():
+            h.dense_disparity_sgm_packed(packed_c, style, sp, dst_c, check)
+        checked.dst = dst_c
+        checked()
+        kept = dst_c.view(n, 2, rows, cols)[:, 0] >= 0     # a point that does not fail has the unchecked map's bits
+        assert torch.equal(dst_c.view(n, 2, rows, cols)[:, 0][kept], dst.view(n, rows, cols)[kept])
+        legs["checked"] = checked
     return legs                                            # (the closures keep the tensors and arrays alive)
 
 
