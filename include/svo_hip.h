@@ -1898,6 +1898,107 @@ int svo_export_voxel_maps(svo_ctx *ctx, const int *seqs, int n, const svo_voxel_
 /* queued: the maps of the named slots become empty (a slot without a map is skipped) */
 int svo_submit_clear_voxel_maps(svo_ctx *ctx, const int *seqs, int n);
 
+/* ---- voxel prune: a voxel map reduced in place to the entries a keep rule names ------------
+ * A map of "voxel maps" only grows. A prune gives entries back without a trip through the host: the map follows the
+ * camera (a box around a centre), forgets what was not seen lately (`last`) and sheds entries that never gathered
+ * evidence (`count`), so that a fused map can run without end.
+ *
+ * The keep rule (svo_voxel_keep). Centre voxel: per coordinate, ci is the index i that the key rule of "voxel maps"
+ * gives center (t = c / voxel; q = floorf(t); i = (int)q + 1048576, in float32); a centre that the key rule calls
+ * outside (a NaN and an infinity too) is rejected. An entry with key parts (ix, iy, iz) is INSIDE THE BOX iff
+ *   |ix - cix| <= radius && |iy - ciy| <= radius && |iz - ciz| <= radius
+ * in integers (a Chebyshev box of 2 radius + 1 voxels per axis: membership is exact). radius < 0: there is no box and
+ * center is not read. An entry is KEPT iff count >= max(1, min_count) and last >= min_stamp and, with radius >= 0,
+ * it is inside the box.
+ *
+ * After a prune the map holds exactly the kept entries, each with its eight accumulators unchanged, and n_voxels is
+ * the kept count. n_fused, n_outside and overflow keep their values: they are cumulative over the map's life (from
+ * its last clear), not a description of the entries it holds now. Placement follows the rule of "voxel maps" (home by
+ * the multiplicative hash, linear probing): every kept entry is reachable from its home without crossing an empty
+ * entry, so a later fuse of a record with a kept key finds the entry and claims no second one. Where an entry lies
+ * stays a diagnostic fact: a prune may move kept entries.
+ *
+ * What follows, and what the tests hold:
+ *   - an extraction after prune(K) with filter F equals, byte for byte, an extraction before it with "F and K";
+ *   - prune(K) twice equals prune(K) once;
+ *   - a prune that removes nothing writes no byte of the map;
+ *   - a prune that keeps nothing leaves what svo_voxel_clear leaves, but for the three cumulative counters;
+ *   - fusing further spans after a prune gives what the statement gives from the pruned content;
+ *   - the load bound of the next fuse uses the new n_voxels.
+ *
+ * How it runs (voxel.hip): blanking keys would cut the probe chains behind them, so the map is rebuilt in place:
+ * count and scan with the keep rule, the kept entries (40 bytes each) to a staging block, the table cleared (the
+ * header stays), one lane per staged entry reinserts (the fuse's probe and claim, bounded by the capacity), and
+ * n_voxels is set. Six launches ordered by the stream; nothing spins or waits for another workgroup, and nothing is
+ * read back in between: each rebuild kernel compares the scan's total with the header's n_voxels and returns at once
+ * when they are equal. */
+typedef struct svo_voxel_keep {     /* 32 bytes */
+    uint32_t min_count;             /* kept: count >= max(1, min_count)                                     */
+    uint32_t min_stamp;             /* kept: last >= min_stamp                                              */
+    float    center[3];             /* the box's centre, in the map's coordinates                           */
+    int32_t  radius;                /* in voxels; < 0: no box (center is not read)                          */
+    int32_t  _reserved[2];          /* 0                                                                    */
+} svo_voxel_keep;
+
+typedef struct svo_voxel_prune_result { /* 32 bytes */
+    int64_t n_before;               /* the map's n_voxels before the prune                                  */
+    int64_t n_kept;                 /* and after it                                                         */
+    int32_t center_voxel[3];        /* (cix, ciy, ciz); radius < 0: 0                                       */
+    int32_t _pad;
+} svo_voxel_prune_result;
+
+/* Stage entry, complete on return; `out` may be NULL. The staging block lives in the handle's workspace:
+ * up256(40 * n_voxels) bytes, sized on the header's n_voxels (the bound of what is kept: no count is read back before
+ * the launches), beside the tile offsets (4 bytes per tile of 256 entries). SVO_ERR_CAPACITY with nothing written if
+ * that block would exceed 1 GiB. SVO_ERR_INVALID with nothing written: what svo_voxel_extract rejects of the map, a
+ * NULL keep, a non-zero _reserved and, with radius >= 0, a centre that is not finite or lies outside by the key rule. */
+int svo_voxel_prune(svo_handle *h, const svo_voxel_map *map, const svo_voxel_keep *keep, svo_voxel_prune_result *out);
+
+/* svo_submit_prune_voxel_maps prunes the maps of the named slots inside a ctx. It is queued like a fuse job: it sees
+ * what was submitted before it and nothing after, only the groups that own a named slot get work, no other group is
+ * drained and the slots' sequences are not changed. keep's min_count, min_stamp and radius hold for every named slot;
+ * the centre of slot seqs[i] (not read with radius < 0) comes by center_mode:
+ *   SVO_PRUNE_CENTER_GIVEN  centers[3 i .. 3 i + 2] (host, copied at the call); centers == NULL: keep->center for all.
+ *                           Checked at the call against the voxel edge of the slot's map as the ctx knows it then.
+ *   SVO_PRUNE_CENTER_POSE   the slot's camera centre at that queue position: the world-frame point that the cloud
+ *                           job's camera-to-world transform (w = R loc + t of the slot's current pose, "clouds") gives
+ *                           the camera-frame origin, which is the pose's translation pose[0 .. 2]. It is taken by the
+ *                           group's worker when the job runs, so a map that follows the camera needs no wait.
+ * info[i] belongs to seqs[i], is host memory and is valid at svo_wait:
+ *   SVO_PRUNE_OK         pruned: n_before and n_kept are the map's n_voxels before and after, center and center_voxel
+ *                        the centre used and its voxel (radius < 0: 0)
+ *   SVO_PRUNE_NO_MAP     the slot has no map (this comes first)
+ *   SVO_PRUNE_NO_POSE    pose mode on an empty slot (no frame yet), or with a camera centre that is not finite or
+ *                        lies outside by the key rule: nothing is pruned
+ *   SVO_PRUNE_TOO_LARGE  staging the map's n_voxels entries would exceed 1 GiB (svo_voxel_prune's bound, with the ctx's
+ *                        host mirror of n_voxels): the map is unchanged and the ctx does not fail
+ * The job copies the headers back and refreshes the ctx's mirror of the maps' counters in queue order: a fuse job
+ * queued behind a prune job settles its SVO_FUSE_FULL on the pruned count, with no wait between them.
+ * Rejected with SVO_ERR_INVALID and nothing queued: a NULL keep or info, a non-zero _reserved, a center_mode that is
+ * neither, a slot out of range or named twice and, in given mode with radius >= 0, a centre that is not finite or
+ * lies outside by the key rule for its slot's map.
+ * Memory, per group, made by the first prune job and replaced when outgrown (svo_memory.device_bytes): one block of
+ *   up256(4 * (capacity / 256 + 1)) + up256(40 * n_voxels)
+ * bytes (capacity / 256 at least 1), the largest that a slot of a job has needed: the tile offsets and the staging. */
+enum { SVO_PRUNE_OK = 0, SVO_PRUNE_NO_MAP = 1, SVO_PRUNE_NO_POSE = 2, SVO_PRUNE_TOO_LARGE = 3 };
+enum { SVO_PRUNE_CENTER_GIVEN = 0, SVO_PRUNE_CENTER_POSE = 1 };
+
+typedef struct svo_prune_info {     /* 64 bytes, host, one per named slot */
+    int32_t seq, run;               /* slot and ordinal of its run                                          */
+    int32_t frame_id;               /* of the slot's current frame; -1: empty slot                          */
+    int32_t status;                 /* SVO_PRUNE_*                                                          */
+    int64_t n_before;               /* the map's n_voxels before the job (NO_MAP: 0)                        */
+    int64_t n_kept;                 /* and after it (not pruned: n_before)                                  */
+    float   center[3];              /* the centre used (radius < 0, NO_MAP, NO_POSE on an empty slot: 0)    */
+    int32_t center_voxel[3];        /* its voxel by the key rule (not OK: 0)                                */
+    int32_t _pad[2];
+} svo_prune_info;
+
+int svo_submit_prune_voxel_maps(svo_ctx *ctx, const int *seqs, int n, const svo_voxel_keep *keep, int center_mode,
+                                const float *centers, svo_prune_info *info);
+int svo_prune_voxel_maps(svo_ctx *ctx, const int *seqs, int n, const svo_voxel_keep *keep, int center_mode,
+                         const float *centers, svo_prune_info *info);   /* submit + wait */
+
 /* ---- snapshots: the sequence state of a slot saved, loaded, moved between ctxs ------------
  * The reference has no checkpoint or resume (a StereoSlam lives and dies with its process). A snapshot is
  * everything the next frame of a slot depends on and everything its getters return, so that a sequence saved

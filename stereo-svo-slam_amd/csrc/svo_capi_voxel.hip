@@ -1,5 +1,5 @@
-// svo_capi_voxel.hip — the stage entries of the voxel maps (include/svo_hip.h, "voxel maps"): clear, fuse, info and
-// extract on maps in the caller's device memory, complete on return. Every check is made on the host before any
+// svo_capi_voxel.hip — the stage entries of the voxel maps (include/svo_hip.h, "voxel maps", "voxel prune"): clear, fuse,
+// info, extract and prune on maps in the caller's device memory, complete on return. Every check is made on the host before any
 // launch (the params, the alignment, the header of each named map, the load bound), with the arithmetic of
 // svo_voxel_plan.hpp; the kernels are voxel.hip's.
 #include <hip/hip_runtime.h>
@@ -159,4 +159,47 @@ extern "C" int svo_voxel_extract(svo_handle* h, const svo_voxel_map* map, const 
                                             reinterpret_cast<uint32_t*>(ws + plan.index_out), ws + plan.sort_temp, temp_bytes, points, h->stream))
         return rc;
     return finish_launch(h);
+}
+
+namespace svo {
+
+// the keep rule as the kernels take it, or why it is rejected; center_voxel: the three indices (0 without a box)
+int voxel_check_keep(const svo_voxel_keep* keep, const float* center, float voxel, const char* who, VoxelKeepDev* out) {
+    if (!keep) return svo_set_error(SVO_ERR_INVALID, "%s: no keep rule", who);
+    if (keep->_reserved[0] != 0 || keep->_reserved[1] != 0) return svo_set_error(SVO_ERR_INVALID, "%s: a _reserved of the keep rule is not 0", who);
+    *out = VoxelKeepDev{std::max<uint32_t>(1u, keep->min_count), keep->min_stamp, {0, 0, 0}, keep->radius < 0 ? -1 : keep->radius};
+    if (keep->radius < 0) return SVO_OK;
+    for (int j = 0; j < 3; j++)
+        if (!voxel_center_index(center[j], voxel, out->c[j]))
+            return svo_set_error(SVO_ERR_INVALID, "%s: the centre's coordinate %d (%g) is not finite or lies outside the map's key range", who, j,
+                                 (double)center[j]);
+    return SVO_OK;
+}
+
+}  // namespace svo
+
+extern "C" int svo_voxel_prune(svo_handle* h, const svo_voxel_map* map, const svo_voxel_keep* keep, svo_voxel_prune_result* out) {
+    CHECK_H(h);
+    if (const int rc = check_map(map, "svo_voxel_prune", 0)) return rc;
+    VoxelKeepDev f;
+    if (const int rc = voxel_check_keep(keep, keep ? keep->center : nullptr, map->params.voxel, "svo_voxel_prune", &f)) return rc;
+    const VoxelMapDev mp = map_dev(map->data, map->params);
+    VoxelHeader hd;
+    HIP_TRY(hipMemcpyAsync(&hd, map->data, sizeof(hd), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (!voxel_header_matches(hd, map->params)) return svo_set_error(SVO_ERR_INVALID, "svo_voxel_prune: the map was not cleared with these params");
+    VoxelPrunePlan plan;
+    if (hd.n_voxels > ((uint64_t)1 << mp.log2_capacity) || !voxel_prune_plan(hd.n_voxels, plan))
+        return svo_set_error(SVO_ERR_CAPACITY, "svo_voxel_prune: staging %llu entries exceeds %zu bytes", hd.n_voxels, VOXEL_PRUNE_STAGING_MAX);
+    // the tile offsets, then the staging block
+    const size_t offsets_bytes = voxel_offsets_bytes(mp.log2_capacity);
+    if (const int rc = h->voxel_ws.reserve(offsets_bytes + plan.bytes, h->stream)) return rc;
+    int32_t* tile_offsets = reinterpret_cast<int32_t*>(h->voxel_ws.ptr.get());
+    launch_voxel_prune(mp, f, tile_offsets, h->voxel_ws.ptr.get() + offsets_bytes, hd.n_voxels, h->stream);
+    HIP_TRY(hipGetLastError());
+    int32_t kept = 0;
+    HIP_TRY(hipMemcpyAsync(&kept, tile_offsets + voxel_map_tiles(mp.log2_capacity), sizeof(kept), hipMemcpyDeviceToHost, h->stream));
+    if (const int rc = finish_launch(h)) return rc;
+    if (out) *out = svo_voxel_prune_result{(int64_t)hd.n_voxels, (int64_t)kept, {f.c[0], f.c[1], f.c[2]}, 0};
+    return SVO_OK;
 }

@@ -55,6 +55,9 @@ int run_job(svo_group* g, int seq0, const svo_ctx::VoxelExport& j) {
     return grp_export_voxel_maps(g, j.mem, j.seqs.data(), j.seg.data(), j.regions.data(), (int)j.seqs.size(), seq0, &j.filter, &j.dst);
 }
 int run_job(svo_group* g, int, const svo_ctx::VoxelClear& j) { return grp_clear_voxel_maps(g, j.seqs.data(), (int)j.seqs.size()); }
+int run_job(svo_group* g, int seq0, const svo_ctx::VoxelPrune& j) {
+    return grp_prune_voxel_maps(g, j.seqs.data(), j.seg.data(), (int)j.seqs.size(), seq0, &j.keep, j.center_mode, j.centers.data(), j.info);
+}
 
 void worker_run_job(svo_ctx::Worker& w, const svo_ctx::Job& job) {
     if (w.err != SVO_OK || w.ctx_failed->load()) return;   // after a failure (any group) the queues are dropped

@@ -149,9 +149,17 @@ struct svo_ctx {
     };
     // the group's share of an svo_submit_clear_voxel_maps
     struct VoxelClear : SlotList {};
+    // the group's share of an svo_submit_prune_voxel_maps: a slot fills the info of its named position; in given
+    // mode three floats per slot of the share
+    struct VoxelPrune : SlotShare {
+        svo_voxel_keep keep{};
+        int center_mode = 0;
+        std::vector<float> centers;
+        svo_prune_info* info = nullptr;
+    };
     // one entry of a group's queue (the frame set first: a Job{} is one, with nothing allocated)
     using Job = std::variant<Frames, Restart, Trim, RigAssign, Export, MapExport, ViewExport, DisparityExport, CloudExport,
-                             SceneExport, ArExport, Save, Load, PoseUpdates, FuseClouds, VoxelExport, VoxelClear>;
+                             SceneExport, ArExport, Save, Load, PoseUpdates, FuseClouds, VoxelExport, VoxelClear, VoxelPrune>;
     struct Worker {
         Group g;
         int first = 0, count = 0;

@@ -1,6 +1,7 @@
 // svo_ctx_voxel.hip — the voxel maps of the ctx's slots (svo_ctx_state.hpp): giving slots a map, its info, and the
-// queued jobs that fuse dense clouds into the maps, export them and clear them.
+// queued jobs that fuse dense clouds into the maps, export them, clear them and prune them.
 #include "svo_ctx_state.hpp"
+#include "svo_voxel_plan.hpp"
 
 extern "C" int svo_ctx_set_voxel_maps(svo_ctx* c, const int* seqs, int n, const svo_voxel_params* params) {
     if (!c || !naming_ok(seqs, n)) return svo_set_error(SVO_ERR_INVALID, "svo_ctx_set_voxel_maps: bad arguments");
@@ -83,4 +84,43 @@ extern "C" int svo_submit_clear_voxel_maps(svo_ctx* c, const int* seqs, int n) {
     if (c->failed.load()) return reject_failed(c, "svo_submit_clear_voxel_maps");
     submit_shares<svo_ctx::VoxelClear>(c, slots, every_slot, nothing_more);
     return SVO_OK;
+}
+
+extern "C" int svo_submit_prune_voxel_maps(svo_ctx* c, const int* seqs, int n, const svo_voxel_keep* keep, int center_mode, const float* centers,
+                                           svo_prune_info* info) {
+    if (!c || !keep || !info || !naming_ok(seqs, n) || (center_mode != SVO_PRUNE_CENTER_GIVEN && center_mode != SVO_PRUNE_CENTER_POSE))
+        return svo_set_error(SVO_ERR_INVALID, "svo_submit_prune_voxel_maps: bad arguments (center_mode %d)", center_mode);
+    if (keep->_reserved[0] != 0 || keep->_reserved[1] != 0) return svo_set_error(SVO_ERR_INVALID, "svo_submit_prune_voxel_maps: a _reserved is not 0");
+    const NamedSlots slots = ctx_slots(c, seqs, n);
+    const bool given = center_mode == SVO_PRUNE_CENTER_GIVEN && keep->radius >= 0;
+    auto center_of = [&](int i) { return centers && center_mode == SVO_PRUNE_CENTER_GIVEN ? centers + 3 * (size_t)i : keep->center; };
+    const int rc = check_slots_and_items(c, "svo_submit_prune_voxel_maps", slots, [&](int i) {
+        if (!given) return (int)SVO_OK;
+        const int s = slots.at(i);
+        for (auto& wp : c->workers) {
+            if (s < wp->first || s >= wp->first + wp->count) continue;
+            const float voxel = grp_voxel_edge(wp->g.get(), s - wp->first);
+            int32_t ci;
+            for (int j = 0; j < 3 && voxel > 0.f; j++)
+                if (!svo::voxel_center_index(center_of(i)[j], voxel, ci))
+                    return svo_set_error(SVO_ERR_INVALID, "svo_submit_prune_voxel_maps: slot %d: the centre's coordinate %d (%g) is not finite or lies outside the map's key range",
+                                         s, j, (double)center_of(i)[j]);
+        }
+        return (int)SVO_OK;
+    });
+    if (rc) return rc;
+    if (c->failed.load()) return reject_failed(c, "svo_submit_prune_voxel_maps");
+    submit_shares<svo_ctx::VoxelPrune>(c, slots,
+                                       [&](svo_ctx::VoxelPrune& e, int i, int) {
+                                           const float* at = center_of(i);
+                                           e.centers.insert(e.centers.end(), at, at + 3);
+                                           return true;
+                                       },
+                                       [&](svo_ctx::VoxelPrune& e) { e.keep = *keep; e.center_mode = center_mode; e.info = info; });
+    return SVO_OK;
+}
+
+extern "C" int svo_prune_voxel_maps(svo_ctx* c, const int* seqs, int n, const svo_voxel_keep* keep, int center_mode, const float* centers,
+                                    svo_prune_info* info) {
+    return then_wait(c, svo_submit_prune_voxel_maps(c, seqs, n, keep, center_mode, centers, info));
 }

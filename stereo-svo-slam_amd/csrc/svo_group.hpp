@@ -142,6 +142,12 @@ int grp_fuse_clouds(svo_group* g, int what, const int* seqs, const int* seg, int
 int grp_export_voxel_maps(svo_group* g, int mem, const int* seqs, const int* seg, const svo_voxel_region* regions, int n, int seq0,
                           const svo_voxel_filter* filter, const svo_voxel_dst* dst);
 int grp_clear_voxel_maps(svo_group* g, const int* seqs, int n);
+// the prune job: the maps of the named slots rebuilt from their kept entries. centers: three floats per named slot
+// (given mode), not read in pose mode. grp_voxel_edge: the voxel edge of a slot's map (0: no map); it changes only in
+// grp_set_voxel_maps, so the submitting thread may read it.
+int grp_prune_voxel_maps(svo_group* g, const int* seqs, const int* seg, int n, int seq0, const svo_voxel_keep* keep, int center_mode,
+                         const float* centers, svo_prune_info* info);
+float grp_voxel_edge(const svo_group* g, int seq);
 // what svo_map_size reports of a slot (the queues have drained)
 void grp_map_size(const svo_group* g, int seq, int from_keyframe, int* keyframes, int64_t* points_bound, int* from = nullptr);
 // Snapshots (svo_submit_save / svo_submit_load). grp_check_snapshot: everything svo_submit_load checks of one

@@ -379,6 +379,7 @@ struct svo_group {
     svo::GrowBlock<uint8_t> d_voxel_records;
     svo::GrowBlock<uint8_t, true> d_voxel_tables;
     svo::GrowBlock<uint8_t> d_voxel_offsets, d_voxel_sort, d_voxel_out;
+    svo::GrowBlock<uint8_t> d_voxel_prune;   // a prune job: the tile offsets and the staging of one slot at a time
     // batched pose-filter updates (grp_pose_updates): the upload block (samples | filter states | start poses |
     // sample offsets) and behind it the download block (filter states | filtered poses) of one job, device and pinned,
     // made by the first such job and replaced when outgrown

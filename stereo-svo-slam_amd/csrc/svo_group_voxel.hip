@@ -1,7 +1,7 @@
 // svo_group_voxel.hip — the voxel maps of a sequence group (include/svo_hip.h, "voxel maps"): a map per slot that has
 // one, the fuse job (the organized world-frame clouds of the named slots, computed by grp_export_cloud in device mode
 // into a block of the group, then one fuse launch per chunk), the export job (voxel.hip's count, scan, pairs, sort
-// and gather per slot) and the clear job. A map belongs to the slot: nothing else in the group touches it. The host
+// and gather per slot), the clear job and the prune job (voxel.hip's rebuild in place per slot; "voxel prune"). A map belongs to the slot: nothing else in the group touches it. The host
 // arithmetic is svo_voxel_plan.hpp's, the state svo_group_state.hpp's.
 #include <hip/hip_runtime.h>
 
@@ -209,6 +209,68 @@ int grp_export_voxel_maps(svo_group* c, int mem, const int* seqs, const int* seg
         HIP_TRY(hipGetLastError());
         if (host) HIP_TRY(hipMemcpyAsync(dst->points + r.first_point, out, sizeof(svo_map_point) * (size_t)kept, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));   // delivered, and the blocks are free for the next slot
+    }
+    return SVO_OK;
+}
+
+float grp_voxel_edge(const svo_group* c, int seq) {
+    return c->voxel_maps.empty() || !c->voxel_maps[(size_t)seq].p ? 0.f : c->voxel_maps[(size_t)seq].params.voxel;
+}
+
+// The statuses are settled on the host first (no map, no pose, the staging bound with the mirror's n_voxels); one
+// block holds the tile offsets and the staging of the largest slot, and the slots that are left use it one after the
+// other in stream order: the six launches of launch_voxel_prune and a copy of the map's header, which is the new
+// mirror. One wait at the end.
+int grp_prune_voxel_maps(svo_group* c, const int* seqs, const int* seg, int n, int seq0, const svo_voxel_keep* keep, int center_mode,
+                         const float* centers, svo_prune_info* info) {
+    if (const int rc = job_begin(c, "svo_submit_prune_voxel_maps")) return rc;
+    hipStream_t st = c->stream.get();
+    struct Todo { int seq, at; VoxelKeepDev f; VoxelPrunePlan plan; size_t offsets; };
+    std::vector<Todo> todo;
+    size_t need = 0;
+    for (int i = 0; i < n; i++) {
+        const Seq& q = c->seqs[seqs[i]];
+        svo_prune_info& e = clear(info[seg[i]]);
+        e.seq = seq0 + seqs[i]; e.run = q.run; e.frame_id = q.frame_id; e.status = SVO_PRUNE_NO_MAP;
+        const svo_group::VoxelSlot* v = c->voxel_maps.empty() ? nullptr : &c->voxel_maps[(size_t)seqs[i]];
+        if (!v || !v->p) continue;
+        e.n_before = e.n_kept = (int64_t)v->head.n_voxels;
+        Todo t{seqs[i], seg[i], VoxelKeepDev{std::max<uint32_t>(1u, keep->min_count), keep->min_stamp, {0, 0, 0}, keep->radius < 0 ? -1 : keep->radius}, {}, 0};
+        e.status = SVO_PRUNE_NO_POSE;
+        if (center_mode == SVO_PRUNE_CENTER_POSE && q.frame_id < 0) continue;
+        if (keep->radius >= 0) {
+            const float* at = center_mode == SVO_PRUNE_CENTER_POSE ? q.pose : centers + 3 * (size_t)i;
+            std::memcpy(e.center, at, sizeof(e.center));
+            // (a given centre was checked at the call, and the slot's map cannot have changed since: setters wait)
+            if (!voxel_center_index(at[0], v->params.voxel, t.f.c[0]) || !voxel_center_index(at[1], v->params.voxel, t.f.c[1]) ||
+                !voxel_center_index(at[2], v->params.voxel, t.f.c[2]))
+                continue;
+        }
+        if (v->head.n_voxels > ((uint64_t)1 << v->params.log2_capacity) || !voxel_prune_plan(v->head.n_voxels, t.plan)) {
+            e.status = SVO_PRUNE_TOO_LARGE;
+            continue;
+        }
+        e.status = SVO_PRUNE_OK;
+        for (int j = 0; j < 3; j++) e.center_voxel[j] = t.f.c[j];
+        t.offsets = voxel_offsets_bytes(v->params.log2_capacity);
+        need = std::max(need, t.offsets + t.plan.bytes);
+        todo.push_back(t);
+    }
+    if (todo.empty()) return SVO_OK;
+    if (const int rc = c->d_voxel_prune.reserve(c, need)) return rc;
+    std::vector<VoxelHeader> heads(todo.size());
+    for (size_t j = 0; j < todo.size(); j++) {
+        const svo_group::VoxelSlot& v = c->voxel_maps[(size_t)todo[j].seq];
+        launch_voxel_prune(map_dev(v), todo[j].f, reinterpret_cast<int32_t*>(c->d_voxel_prune.p), c->d_voxel_prune.p + todo[j].offsets,
+                           v.head.n_voxels, st);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(&heads[j], v.p, sizeof(VoxelHeader), hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    for (size_t j = 0; j < todo.size(); j++) {
+        svo_group::VoxelSlot& v = c->voxel_maps[(size_t)todo[j].seq];
+        info[todo[j].at].n_kept = (int64_t)heads[j].n_voxels;
+        v.head = heads[j];
     }
     return SVO_OK;
 }

@@ -564,5 +564,18 @@ int voxel_sort_temp_bytes(size_t n, size_t* bytes);
 int launch_voxel_extract(const VoxelMapDev& map, VoxelFilterDev f, const int32_t* tile_offsets, size_t n, uint64_t* keys_in,
                          uint64_t* keys_out, uint32_t* index_in, uint32_t* index_out, void* sort_temp, size_t sort_temp_bytes,
                          svo_map_point* points, hipStream_t stream);
+// The keep rule of a prune (include/svo_hip.h, "voxel prune"): min_count >= 1; c: the centre voxel's three key parts;
+// radius < 0: no box.
+struct VoxelKeepDev {
+    uint32_t min_count, min_stamp;
+    int32_t c[3];
+    int32_t radius;
+};
+// The map rebuilt in place from its kept entries, with no host read-back: count and scan (tile_offsets as
+// launch_voxel_count's), stage, clear, reinsert and the header's n_voxels, six launches ordered by the stream.
+// n_bound: an upper bound of the kept count (the header's n_voxels as the host knows it); staging: the
+// voxel_prune_plan block of n_bound entries. When nothing leaves, only tile_offsets is written.
+void launch_voxel_prune(const VoxelMapDev& map, VoxelKeepDev keep, int32_t* tile_offsets, uint8_t* staging, uint64_t n_bound,
+                        hipStream_t stream);
 
 }  // namespace svo

@@ -89,4 +89,36 @@ inline VoxelExtractPlan voxel_extract_plan(uint64_t kept, size_t sort_temp_bytes
 // does an extraction of `kept` entries fit `capacity` records?
 inline bool voxel_extract_fits(int64_t kept, int64_t capacity) { return kept >= 0 && capacity >= 0 && kept <= capacity; }
 
+// ---- voxel prune (include/svo_hip.h, "voxel prune"; tests/cpp/voxel_prune_plan_check.cpp)
+constexpr size_t VOXEL_PRUNE_STAGING_MAX = (size_t)1 << 30;
+
+// The index the key rule gives one coordinate of a centre (t = c / voxel; q = floorf(t); i = (int)q + 2^20), in
+// float32 as the fuse kernel computes it; false: outside (a NaN and an infinity too), and i is left alone. One division
+// and one floor, each rounded once on the host as on the device: there is nothing a compiler could contract.
+inline bool voxel_center_index(float c, float voxel, int32_t& i) {
+    const float t = c / voxel;
+    const float q = __builtin_floorf(t);
+    if (!(__builtin_fabsf(q) < 1048576.0f)) return false;
+    i = (int32_t)q + 1048576;
+    return true;
+}
+
+// The staging of a prune of a map whose header counts n_voxels entries (the bound of what is kept; nothing is read
+// back before the launches): the accumulator records (32 bytes each, 16-byte aligned) and behind them the keys, in one
+// block of up256(40 * n_voxels) bytes. false: the block would exceed VOXEL_PRUNE_STAGING_MAX (or n_voxels a table).
+struct VoxelPrunePlan {
+    size_t acc, keys, bytes;
+};
+inline bool voxel_prune_plan(uint64_t n_voxels, VoxelPrunePlan& p) {
+    p = VoxelPrunePlan{};
+    if (n_voxels > VOXEL_PRUNE_STAGING_MAX / VOXEL_ENTRY_BYTES) return false;
+    p.acc = 0;
+    p.keys = 32 * (size_t)n_voxels;
+    p.bytes = voxel_up256(VOXEL_ENTRY_BYTES * (size_t)n_voxels);
+    return p.bytes <= VOXEL_PRUNE_STAGING_MAX;
+}
+
+// the workgroups of the reinsert pass over at most n_voxels staged entries
+inline int64_t voxel_prune_tiles(uint64_t n_voxels) { return (int64_t)((n_voxels + VOXEL_TILE - 1) / VOXEL_TILE); }
+
 }  // namespace svo

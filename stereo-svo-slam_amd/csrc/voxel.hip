@@ -30,8 +30,20 @@
 // the means in double and 64-bit integers, one 16-byte store). Keys are unique, so the sorted order and every byte
 // are the same in every run.
 //
+// Prune ("voxel prune"): blanking the keys of the entries that leave would cut the probe chains behind them, so the
+// map is rebuilt in place, in six launches that the stream orders (no workgroup waits for another): voxel_prune_count_kernel
+// and voxel_scan_kernel as above with the keep rule (count, stamp, the box over the key's three 21-bit parts),
+// voxel_prune_stage_kernel (every kept entry to the staging block at tile offset + rank: two 16-byte loads and stores
+// and the key), voxel_prune_clear_kernel (keys and accumulators; the header stays), voxel_prune_reinsert_kernel (one
+// lane per staged entry: the fuse's probe and claim, then plain stores) and voxel_prune_finish_kernel (n_voxels = the
+// total). Nothing is read back between them: every kernel after the scan compares the scan's total with the header's
+// n_voxels and returns when they are equal, so a prune that removes nothing writes no byte of the map; n_voxels
+// changes only in the last launch, so all of them see the same answer.
+//
 // Bounds: of a span, records [0, n) are read. Of a map, keys and acc entries [0, capacity) (slot = (slot + 1) &
-// (capacity - 1)) and the header. tile_offsets [0, tiles]; pairs and records [0, n) with n the scan's total.
+// (capacity - 1)) and the header. tile_offsets [0, tiles]; pairs and records [0, n) with n the scan's total. Of a
+// prune's staging block, records and keys [0, min(total, n_bound)) with n_bound the n_voxels the block was sized by;
+// the clear writes the 16-byte units [0, (40 << log2_capacity) / 16) behind the header.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -298,6 +310,131 @@ __global__ __launch_bounds__(VOXEL_THREADS) void voxel_gather_kernel(const Voxel
     r.x = xyz[0]; r.y = xyz[1]; r.z = xyz[2];
     r.w = rgb[0] | rgb[1] << 8 | rgb[2] << 16;
     ((SVO_GP(uint4))points)[i] = r;
+}
+
+// ---- prune: the map rebuilt in place from its kept entries (include/svo_hip.h, "voxel prune")
+
+// the keep rule of a prune on entry e: count, stamp, and the Chebyshev box over the key's three 21-bit parts
+__device__ __forceinline__ bool voxel_prune_keep(const VoxelMapDev& mp, const VoxelKeepDev& f, uint32_t e, unsigned long long& key) {
+    key = VOXEL_EMPTY;
+    if (e >= (1u << mp.log2_capacity)) return false;
+    key = voxel_keys(mp)[e];
+    if (key == VOXEL_EMPTY) return false;
+    const SVO_GP(uint32_t) a = voxel_acc(mp) + (size_t)e * 8;
+    if (!(a[0] >= f.min_count && a[7] >= f.min_stamp)) return false;
+    if (f.radius < 0) return true;
+    const int d[3] = {(int)(uint32_t)(key >> 42) - f.c[0], (int)(uint32_t)((key >> 21) & 0x1fffffu) - f.c[1], (int)(uint32_t)(key & 0x1fffffu) - f.c[2]};
+    return abs(d[0]) <= f.radius && abs(d[1]) <= f.radius && abs(d[2]) <= f.radius;
+}
+
+// nothing leaves the map: the scan's total is the header's n_voxels (both final before any rebuild kernel starts; the
+// header's count is written again only by voxel_prune_finish_kernel, the last launch)
+__device__ __forceinline__ bool voxel_prune_nothing_leaves(const VoxelMapDev& mp, const int32_t* __restrict__ tile_offsets, int tiles) {
+    return (unsigned long long)G(tile_offsets)[tiles] == ((SVO_GP(const VoxelHeader))mp.base)->n_voxels;
+}
+
+__global__ __launch_bounds__(VOXEL_THREADS) void voxel_prune_count_kernel(const VoxelMapDev mp, const VoxelKeepDev f, int32_t* __restrict__ tile_counts) {
+    __shared__ int wave_n[VOXEL_WAVES];
+    unsigned long long key;
+    const bool keep = voxel_prune_keep(mp, f, blockIdx.x * VOXEL_TILE + threadIdx.x, key);
+    const unsigned long long m = __ballot(keep);
+    if ((threadIdx.x & 63) == 0) wave_n[threadIdx.x >> 6] = __popcll(m);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int n = 0;
+        for (int w = 0; w < VOXEL_WAVES; w++) n += wave_n[w];
+        G(tile_counts)[blockIdx.x] = n;
+    }
+}
+
+// the kept entry of rank r leaves as acc_out[2 r], acc_out[2 r + 1] (two 16-byte stores) and keys_out[r]
+__global__ __launch_bounds__(VOXEL_THREADS) void voxel_prune_stage_kernel(const VoxelMapDev mp, const VoxelKeepDev f,
+                                                                          const int32_t* __restrict__ tile_offsets, const int tiles, const size_t n_bound,
+                                                                          uint4* __restrict__ acc_out, unsigned long long* __restrict__ keys_out) {
+    __shared__ int wave_n[VOXEL_WAVES];
+    if (voxel_prune_nothing_leaves(mp, tile_offsets, tiles)) return;   // (uniform over the grid)
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t e = blockIdx.x * VOXEL_TILE + threadIdx.x;
+    unsigned long long key;
+    const bool keep = voxel_prune_keep(mp, f, e, key);
+    const unsigned long long m = __ballot(keep);
+    const int rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+    if (lane == 0) wave_n[wave] = __popcll(m);
+    __syncthreads();
+    size_t at = (size_t)G(tile_offsets)[blockIdx.x] + rank;
+    for (int w = 0; w < wave; w++) at += wave_n[w];
+    if (keep && at < n_bound) {                            // (at < n_bound always: the kept are among the header's n_voxels)
+        const SVO_GP(uint4) a = (SVO_GP(uint4))(voxel_acc(mp) + (size_t)e * 8);
+        const uint4 lo = a[0], hi = a[1];
+        ((SVO_GP(uint4))acc_out)[2 * at] = lo;
+        ((SVO_GP(uint4))acc_out)[2 * at + 1] = hi;
+        G(keys_out)[at] = key;
+    }
+}
+
+// 16-byte unit u behind the header block: all ones over the keys, zeros over the accumulators; the header stays
+__global__ __launch_bounds__(VOXEL_THREADS) void voxel_prune_clear_kernel(const VoxelMapDev mp, const size_t units,
+                                                                          const int32_t* __restrict__ tile_offsets, const int tiles) {
+    if (voxel_prune_nothing_leaves(mp, tile_offsets, tiles)) return;
+    const size_t u = (size_t)blockIdx.x * VOXEL_THREADS + threadIdx.x;
+    if (u >= units) return;
+    const size_t key_units = ((size_t)8 << mp.log2_capacity) / 16;
+    const uint32_t w = u < key_units ? ~0u : 0u;
+    ((SVO_GP(uint4))(mp.base + VOXEL_HEADER_BYTES))[u] = make_uint4(w, w, w, w);
+}
+
+// One lane per staged entry: the probe of the fuse from the key's home, the claim ~0 -> key (keys are unique: a lane
+// never meets its own key, and an entry another lane claimed holds another key for good), then the eight
+// accumulators as two plain 16-byte stores: nobody else writes the entry this lane claimed.
+__global__ __launch_bounds__(VOXEL_THREADS) void voxel_prune_reinsert_kernel(const VoxelMapDev mp, const int32_t* __restrict__ tile_offsets, const int tiles,
+                                                                             const size_t n_bound, const uint4* __restrict__ acc_in,
+                                                                             const unsigned long long* __restrict__ keys_in) {
+    if (voxel_prune_nothing_leaves(mp, tile_offsets, tiles)) return;
+    const size_t i = (size_t)blockIdx.x * VOXEL_THREADS + threadIdx.x;
+    const size_t n = min((size_t)max(G(tile_offsets)[tiles], 0), n_bound);
+    if (i >= n) return;
+    const unsigned long long key = G(keys_in)[i];
+    const uint4 lo = ((SVO_GP(const uint4))acc_in)[2 * i], hi = ((SVO_GP(const uint4))acc_in)[2 * i + 1];
+    const uint32_t cap = 1u << mp.log2_capacity, mask = cap - 1;
+    SVO_GP(unsigned long long) keys = voxel_keys(mp);
+    uint32_t s = (uint32_t)((key * VOXEL_HASH) >> (64 - mp.log2_capacity));
+    for (uint32_t it = 0; it < cap; it++) {
+        if (__hip_atomic_load(keys + s, VOXEL_RELAXED) == VOXEL_EMPTY) {
+            unsigned long long expected = VOXEL_EMPTY;
+            if (__hip_atomic_compare_exchange_strong(keys + s, &expected, key, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
+                SVO_GP(uint4) a = (SVO_GP(uint4))(voxel_acc(mp) + (size_t)s * 8);
+                a[0] = lo;
+                a[1] = hi;
+                return;
+            }
+        }
+        s = (s + 1) & mask;
+    }
+    // (not reached: the cleared table has `capacity` empty entries for at most n_voxels <= capacity keys)
+}
+
+// the last launch of a prune: the header's n_voxels becomes the kept count
+__global__ __launch_bounds__(64) void voxel_prune_finish_kernel(const VoxelMapDev mp, const int32_t* __restrict__ tile_offsets, const int tiles) {
+    if (threadIdx.x != 0 || voxel_prune_nothing_leaves(mp, tile_offsets, tiles)) return;
+    ((SVO_GP(VoxelHeader))mp.base)->n_voxels = (unsigned long long)max(G(tile_offsets)[tiles], 0);
+}
+
+void launch_voxel_prune(const VoxelMapDev& map, VoxelKeepDev keep, int32_t* tile_offsets, uint8_t* staging, uint64_t n_bound,
+                        hipStream_t stream) {
+    const int tiles = (int)voxel_map_tiles(map.log2_capacity);
+    hipLaunchKernelGGL(voxel_prune_count_kernel, dim3(tiles), dim3(VOXEL_THREADS), 0, stream, map, keep, tile_offsets);
+    hipLaunchKernelGGL(voxel_scan_kernel, dim3(1), dim3(VOXEL_THREADS), 0, stream, tile_offsets, tiles);
+    VoxelPrunePlan plan;
+    if (n_bound == 0 || !voxel_prune_plan(n_bound, plan)) return;   // (an empty map keeps nothing; the callers check the plan first)
+    uint4* acc = reinterpret_cast<uint4*>(staging + plan.acc);
+    unsigned long long* keys = reinterpret_cast<unsigned long long*>(staging + plan.keys);
+    const size_t units = (voxel_map_bytes(map.log2_capacity) - VOXEL_HEADER_BYTES) / 16;
+    hipLaunchKernelGGL(voxel_prune_stage_kernel, dim3(tiles), dim3(VOXEL_THREADS), 0, stream, map, keep, tile_offsets, tiles, (size_t)n_bound, acc, keys);
+    hipLaunchKernelGGL(voxel_prune_clear_kernel, dim3((unsigned)((units + VOXEL_THREADS - 1) / VOXEL_THREADS)), dim3(VOXEL_THREADS), 0, stream, map,
+                       units, tile_offsets, tiles);
+    hipLaunchKernelGGL(voxel_prune_reinsert_kernel, dim3((unsigned)voxel_prune_tiles(n_bound)), dim3(VOXEL_THREADS), 0, stream, map, tile_offsets,
+                       tiles, (size_t)n_bound, acc, keys);
+    hipLaunchKernelGGL(voxel_prune_finish_kernel, dim3(1), dim3(64), 0, stream, map, tile_offsets, tiles);
 }
 
 void launch_voxel_clear(const VoxelMapDev& map, hipStream_t stream) {

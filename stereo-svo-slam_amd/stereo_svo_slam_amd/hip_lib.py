@@ -56,6 +56,7 @@ SYMBOLS = (
     "svo_voxel_map_bytes", "svo_voxel_clear", "svo_voxel_fuse", "svo_voxel_info", "svo_voxel_extract",
     "svo_ctx_set_voxel_maps", "svo_get_voxel_map_info", "svo_submit_fuse_clouds", "svo_fuse_clouds",
     "svo_submit_export_voxel_maps", "svo_export_voxel_maps", "svo_submit_clear_voxel_maps",
+    "svo_voxel_prune", "svo_submit_prune_voxel_maps", "svo_prune_voxel_maps",
     "svo_ar_size", "svo_ar_camera_of_pose", "svo_submit_export_ar", "svo_export_ar", "svo_render_ar",
     "svo_submit_export_ar_occluded", "svo_export_ar_occluded", "svo_render_ar_occluded",
     "svo_remap_linear_multi", "svo_ctx_add_rigs", "svo_ctx_remove_rigs", "svo_ctx_assign_rigs", "svo_ctx_get_slot_rig",
@@ -735,6 +736,26 @@ class VoxelFilter(C.Structure):
 assert (C.sizeof(VoxelParams), C.sizeof(VoxelMap), C.sizeof(VoxelSpan), C.sizeof(VoxelMapInfo), C.sizeof(VoxelFilter)) == (16, 24, 24, 48, 16)
 
 
+class VoxelKeep(C.Structure):
+    """svo_voxel_keep (include/svo_hip.h, "voxel prune"): which entries a prune keeps."""
+    _fields_ = [("min_count", C.c_uint32), ("min_stamp", C.c_uint32), ("center", C.c_float * 3), ("radius", C.c_int32),
+                ("_reserved", C.c_int32 * 2)]
+
+
+class VoxelPruneResult(C.Structure):
+    """svo_voxel_prune_result (include/svo_hip.h)."""
+    _fields_ = [("n_before", C.c_int64), ("n_kept", C.c_int64), ("center_voxel", C.c_int32 * 3), ("_pad", C.c_int32)]
+
+
+assert (C.sizeof(VoxelKeep), C.sizeof(VoxelPruneResult)) == (32, 32)
+# the ctx's prune job: svo_submit_prune_voxel_maps
+PRUNE_OK, PRUNE_NO_MAP, PRUNE_NO_POSE, PRUNE_TOO_LARGE = range(4)
+PRUNE_CENTER_GIVEN, PRUNE_CENTER_POSE = 0, 1
+PRUNE_INFO_DTYPE = np.dtype([("seq", "<i4"), ("run", "<i4"), ("frame_id", "<i4"), ("status", "<i4"), ("n_before", "<i8"), ("n_kept", "<i8"),
+                             ("center", "<f4", (3,)), ("center_voxel", "<i4", (3,)), ("_pad", "<i4", (2,))])
+assert PRUNE_INFO_DTYPE.itemsize == 64
+
+
 # the ctx's voxel maps: svo_submit_fuse_clouds, svo_submit_export_voxel_maps
 FUSE_OK, FUSE_NONE, FUSE_NO_MAP, FUSE_FULL = range(4)
 VOXEL_OK, VOXEL_NO_MAP, VOXEL_TOO_SMALL = range(3)
@@ -764,6 +785,12 @@ def voxel_map_bytes(log2_capacity):
 
 def voxel_params(voxel, log2_capacity, drop_flags=0):
     return VoxelParams(float(voxel), int(log2_capacity), int(drop_flags), 0)
+
+
+def voxel_keep(min_count=0, min_stamp=0, center=(0.0, 0.0, 0.0), radius=-1):
+    """a VoxelKeep: count >= max(1, min_count), last >= min_stamp and, with radius >= 0 (in voxels), the box of
+    2 radius + 1 voxels per axis around the voxel that holds `center`"""
+    return VoxelKeep(int(min_count), int(min_stamp), (C.c_float * 3)(*[float(c) for c in center]), int(radius), (C.c_int32 * 2)(0, 0))
 
 
 def _voxel_map(m):
@@ -986,6 +1013,13 @@ def lib():
         for name in ("svo_submit_export_voxel_maps", "svo_export_voxel_maps"):     # (regions: a numpy array's address)
             getattr(_LIB, name).argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
         _LIB.svo_ctx_set_voxel_maps.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        # (centers, info: a numpy array's address. An older diagnostic build named by SVO_HIP_LIB may lack the entries:
+        # calling one then fails by name, as every missing entry does)
+        for name in ("svo_submit_prune_voxel_maps", "svo_prune_voxel_maps"):
+            if hasattr(_LIB, name):
+                getattr(_LIB, name).argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        if hasattr(_LIB, "svo_voxel_prune"):
+            _LIB.svo_voxel_prune.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _LIB.svo_submit_clear_voxel_maps.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         _LIB.svo_get_voxel_map_info.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         for name in ("svo_submit_pose_updates", "svo_update_poses"):
@@ -1446,6 +1480,13 @@ class Handle:
         _check(lib().svo_voxel_extract(self._h, C.byref(_voxel_map(m)), C.byref(VoxelFilter(int(min_count), int(min_stamp))),
                                        C.c_void_p(p), C.c_int64(int(capacity)), C.byref(n)))
         return points, n.value
+
+    def voxel_prune(self, m, keep):
+        """svo_voxel_prune: the map reduced in place to the entries `keep` (a VoxelKeep, see voxel_keep) names. Returns
+        a dict: n_before, n_kept, center_voxel. Complete on return."""
+        out = VoxelPruneResult()
+        _check(lib().svo_voxel_prune(self._h, C.byref(_voxel_map(m)), C.byref(keep) if keep is not None else None, C.byref(out)))
+        return {"n_before": out.n_before, "n_kept": out.n_kept, "center_voxel": tuple(out.center_voxel)}
 
     def render_scene(self, srcs, cameras, offsets, style, pixels):
         """svo_render_scene: the viewer's scene of keyframe sets and lines as images of `style` (a SceneStyle). srcs:

@@ -423,6 +423,29 @@ class Fusion(Job):
                                             None if self.check is None else C.byref(self.check), self.stamp, self._info.ctypes.data)
 
 
+class Prune(Job):
+    """One svo_submit_prune_voxel_maps: owns the info the library writes and the centres it reads at the call. After
+    wait(): `info` (hip_lib.PRUNE_INFO_DTYPE, one per named slot). keep: a hip_lib.VoxelKeep (its center is used where
+    `centers` is None); centers: "pose" (each slot's camera centre when the job runs) or one xyz per named slot. Its
+    submit() queues the same job again. A host-mode job: its submit() never synchronises a stream."""
+
+    def __init__(self, slam, seqs, keep, centers):
+        n = self._name(slam, seqs)
+        self.keep = keep
+        self.center_mode = hip_lib.PRUNE_CENTER_POSE if isinstance(centers, str) else hip_lib.PRUNE_CENTER_GIVEN
+        if isinstance(centers, str) and centers != "pose":
+            raise ValueError(f"centers is 'pose' or coordinates, not {centers!r}")
+        self.centers = None
+        if self.center_mode == hip_lib.PRUNE_CENTER_GIVEN and centers is not None:
+            self.centers = np.ascontiguousarray(np.broadcast_to(np.asarray(centers, np.float32), (n, 3)))
+        self._info, self.info = self._per_slot(hip_lib.PRUNE_INFO_DTYPE)
+
+    def _call(self, ctx, mem):
+        centers = None if self.centers is None or not len(self.centers) else self.centers.ctypes.data
+        return lib().svo_submit_prune_voxel_maps(ctx, self._seq_arr, self._n, C.byref(self.keep), self.center_mode, centers,
+                                                 self._info.ctypes.data)
+
+
 class VoxelMaps(PointJob):
     """One svo_submit_export_voxel_maps: owns the buffers the library writes. After wait(): `segments`
     (hip_lib.VOXEL_SEGMENT_DTYPE, one per named slot) and points(i); `points_buffer`: PointJob. capacities: the records

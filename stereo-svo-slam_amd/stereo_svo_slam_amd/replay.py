@@ -42,7 +42,8 @@ little-endian PLY, x y z float and red green blue uchar), so that the files of a
 clouds of the keyframes so far (one device array of at most N records): the dense map growing.
 --dump-dense-map FILE.ply --dense-map-voxel V [--dense-map-log2 N] [--dense-map-min-count K] fuses every new keyframe's
 dense cloud (--cloud-step, --cloud-lr, --cloud-max-depth) into a voxel map of edge V kept inside the ctx (bounded,
-every surface once, the keyframes that saw a voxel averaged) and writes it as one PLY at the end; --scene-fused V draws
+every surface once, the keyframes that saw a voxel averaged) and writes it as one PLY at the end; --dense-map-window METRES
+and --dense-map-keep N prune it behind every fuse (a box around the camera; what the last N fuses reached); --scene-fused V draws
 that map in the pictures of --dump-scene.
 --dump-ar DIR writes per frame DIR/000000_ar.ppm: the AR demo's picture (src/ar-app/), a lit box of edge --ar-box
 fixed at the world point --ar-at over the frame's left image, seen from the tracked pose; the default placement is the
@@ -427,7 +428,7 @@ class Replay:
                  ar_box=AR_BOX, ar_at=hip_lib.AR_AT, dump_disparity=None, disparity_step=4, disparity_depth=False,
                  dump_cloud=None, cloud_step=4, cloud_max_depth=0.0, disparity_lr=None, cloud_lr=None, scene_dense=None,
                  scene_dense_lr=None, scene_dense_max_depth=0.0, scene_accumulate=0, dump_dense_map=None, dense_map_voxel=None,
-                 dense_map_log2=20, dense_map_min_count=0, scene_fused=None, ar_occlusion=None, disparity_sgm=None, cloud_sgm=None):
+                 dense_map_log2=20, dense_map_min_count=0, dense_map_window=None, dense_map_keep=None, scene_fused=None, ar_occlusion=None, disparity_sgm=None, cloud_sgm=None):
         """fast=False keeps the library default: the reference-order Gauss-Newton (bit-exact traces).
         rectify_maps = (left maps, right maps): the frames fed are raw and are rectified on the GPU.
         calibration = (left, right) CameraCalibrations: the same, with the maps built on the GPU as well.
@@ -492,6 +493,17 @@ class Replay:
             raise ValueError("dump_dense_map needs dense_map_voxel")
         if self.scene_fused is not None and self.scene_fused != self.dense_map_voxel:
             raise ValueError("scene_fused and dense_map_voxel name one map: give the same edge")
+        # (a prune behind every fuse of the map: a box of dense_map_window metres around the camera, and only what the
+        # last dense_map_keep fuses reached)
+        self.dense_map_prune = None
+        if dense_map_window is not None or dense_map_keep is not None:
+            if self.dense_map_voxel is None:
+                raise ValueError("dense_map_window and dense_map_keep need a dense map")
+            self.dense_map_prune = dict(center="pose")
+            if dense_map_window is not None:
+                self.dense_map_prune["radius"] = float(dense_map_window)
+            if dense_map_keep is not None:
+                self.dense_map_prune["keep_stamps"] = int(dense_map_keep)
         self._dense_map_set, self._fused_job = False, None
         for d in (dump_views, dump_scene, dump_ar, dump_disparity, dump_cloud):
             if d:
@@ -598,7 +610,8 @@ class Replay:
         if not self._dense_map_set:
             self.slam.set_voxel_maps(self.dense_map_voxel, self.dense_map_log2)
             self._dense_map_set = True
-        return self.slam.fuse_new_keyframes(step=self.cloud_step, max_depth=self.cloud_max_depth, lr_check=self.cloud_lr) is not None
+        return self.slam.fuse_new_keyframes(step=self.cloud_step, max_depth=self.cloud_max_depth, lr_check=self.cloud_lr,
+                                            prune=self.dense_map_prune) is not None
 
     def finish(self):
         """what is written once, after the last frame: the dense map of dump_dense_map"""
@@ -738,6 +751,11 @@ def build_parser():
     ap.add_argument("--dense-map-log2", metavar="N", type=int, default=20, help="the map holds 1 << N entries (10 .. 26)")
     ap.add_argument("--dense-map-min-count", metavar="K", type=int, default=0,
                     help="--dump-dense-map / --scene-fused keep only voxels that at least K records fell into")
+    ap.add_argument("--dense-map-window", metavar="METRES", type=float, default=None,
+                    help="prune the map of --dump-dense-map / --scene-fused behind every fuse to the voxels within METRES of the "
+                         "camera on every axis (floor(METRES / V) voxels around the camera's voxel): the map follows the camera")
+    ap.add_argument("--dense-map-keep", metavar="N", type=int, default=None,
+                    help="prune the map behind every fuse to the voxels that one of the last N fuses reached")
     ap.add_argument("--scene-fused", metavar="V", type=float, default=None,
                     help="--dump-scene also draws the fused dense map of voxel edge V (the map of --dump-dense-map), exported to "
                          "device memory whenever a keyframe was fused")
@@ -769,6 +787,12 @@ def check_dense_map_args(ap, args):
         ap.error("--dense-map-log2 must be 10 .. 26")
     if args.dense_map_min_count < 0:
         ap.error("--dense-map-min-count must be >= 0")
+    if (args.dense_map_window is not None or args.dense_map_keep is not None) and not (args.dump_dense_map or args.scene_fused is not None):
+        ap.error("--dense-map-window and --dense-map-keep need --dump-dense-map or --scene-fused")
+    if args.dense_map_window is not None and not (0 <= args.dense_map_window < float("inf")):
+        ap.error("--dense-map-window must be finite and >= 0")
+    if args.dense_map_keep is not None and args.dense_map_keep < 1:
+        ap.error("--dense-map-keep must be >= 1")
 
 
 def main(argv=None):
@@ -841,7 +865,8 @@ def main(argv=None):
                 cloud_sgm=None if args.cloud_sgm is None else args.cloud_sgm.split(","),
                 scene_dense=args.scene_dense, scene_dense_lr=args.scene_dense_lr, scene_dense_max_depth=args.scene_dense_max_depth,
                 scene_accumulate=args.scene_accumulate, dump_dense_map=args.dump_dense_map, dense_map_voxel=args.dense_map_voxel,
-                dense_map_log2=args.dense_map_log2, dense_map_min_count=args.dense_map_min_count, scene_fused=args.scene_fused,
+                dense_map_log2=args.dense_map_log2, dense_map_min_count=args.dense_map_min_count, dense_map_window=args.dense_map_window,
+                dense_map_keep=args.dense_map_keep, scene_fused=args.scene_fused,
                 ar_occlusion=occlusion)
     for k, (left, right, t) in enumerate(frames):
         rp.feed(left, right, t, None if gyro is None else gyro[gyro[:, 0] == k, 1:4])

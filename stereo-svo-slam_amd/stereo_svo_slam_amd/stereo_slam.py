@@ -15,7 +15,7 @@ import torch
 
 from . import hip_lib
 from .hip_lib import POSE_SAMPLE_CHAIN, POSE_SAMPLE_DTYPE, CameraSettings, SvoError, _check, lib
-from .jobs import (KP_INFO_DTYPE, ArPictures, Clouds, Disparities, Export, Frame, Fusion, MapExport,  # noqa: F401
+from .jobs import (KP_INFO_DTYPE, ArPictures, Clouds, Disparities, Export, Frame, Fusion, MapExport, Prune,  # noqa: F401
                    Scenes, Snapshot, Views, VoxelMaps, caller_memory, int_array, named_slots)
 
 
@@ -698,10 +698,13 @@ class StereoSlamBatch:
         """submit_fuse + wait"""
         return self.submit_fuse(what, seqs, **kw).wait()
 
-    def fuse_new_keyframes(self, seqs=None, **kw):
+    def fuse_new_keyframes(self, seqs=None, prune=None, **kw):
         """fuse_clouds("last_keyframes") of only those slots whose newest keyframe changed since this method last fused
         them (the bookkeeping is here, on the host: it waits for the queues to read the keyframe counts). Returns the
-        Fusion, or None when no slot has a new keyframe."""
+        Fusion, or None when no slot has a new keyframe. prune: a dict of submit_prune's keywords; the prune of the
+        fused slots is queued behind the fuse (and waited for with it; the Prune is the Fusion's `.prune`).
+        keep_stamps=N in it stands for min_stamp = stamp - N + 1 with `stamp` this fuse's: what the last N fuses of
+        this object reached stays."""
         named = named_slots(self, seqs, explicit=True)[0]
         self.wait()
         fresh = []
@@ -712,7 +715,15 @@ class StereoSlamBatch:
                 fresh.append((s, newest))
         if not fresh:
             return None
-        job = self.fuse_clouds("last_keyframes", [s for s, _ in fresh], **kw)
+        job = self.submit_fuse("last_keyframes", [s for s, _ in fresh], **kw)
+        job.prune = None
+        if prune is not None:
+            prune = dict(prune)
+            keep_stamps = prune.pop("keep_stamps", None)
+            if keep_stamps is not None:
+                prune["min_stamp"] = max(0, job.stamp - int(keep_stamps) + 1)
+            job.prune = self.submit_prune([s for s, _ in fresh], **prune)
+        job.wait()
         for (s, newest), f in zip(fresh, job.info):
             if int(f["status"]) == hip_lib.FUSE_OK:
                 self._fused_keyframe[s] = newest
@@ -731,6 +742,38 @@ class StereoSlamBatch:
     def export_voxel_maps(self, seqs=None, **kw):
         """submit_voxel_maps + wait"""
         return self.submit_voxel_maps(seqs, **kw).wait()
+
+    def submit_prune(self, seqs=None, min_count=0, min_stamp=0, radius=None, center="pose"):
+        """svo_submit_prune_voxel_maps: queue a prune of the voxel maps of the slots `seqs` (None: all) behind what was
+        submitted so far; nothing is waited for. An entry stays iff count >= max(1, min_count), last >= min_stamp and,
+        with a radius, it lies in the box around the centre. radius: metres (None: no box), turned into voxels per
+        slot as floor(radius / voxel) with that slot's voxel edge in double, so the box never reaches further than
+        `radius` from the centre voxel's faces; slots whose maps differ in their edge go as one job per edge (the
+        edges are read from the ctx: with a radius this waits for the queues once). center: "pose" (each slot's
+        camera centre when the job runs), one xyz for all, or an array of one xyz per named slot. Returns a Prune,
+        valid after its wait() (or the ctx's); with several edges a list of them."""
+        if radius is None:                                   # no box: no centre is read, and no pose is asked for
+            return Prune(self, seqs, hip_lib.voxel_keep(min_count, min_stamp), None).submit()
+        named = named_slots(self, seqs, explicit=True)[0]
+        by_radius, no_map = {}, []
+        for i, s in enumerate(named):
+            info = self.voxel_map_info(s)
+            if info is None:
+                no_map.append(i)                              # (PRUNE_NO_MAP whatever the radius: it goes with the first job)
+            else:
+                by_radius.setdefault(int(np.floor(float(radius) / float(np.float32(info["voxel"])))), []).append(i)
+        first = next(iter(by_radius), 0)
+        by_radius[first] = sorted(by_radius.get(first, []) + no_map)
+        per_slot = None if isinstance(center, str) else np.broadcast_to(np.asarray(center, np.float32), (len(named), 3))
+        jobs = [Prune(self, [named[i] for i in idx], hip_lib.voxel_keep(min_count, min_stamp, radius=r),
+                      center if per_slot is None else per_slot[idx]).submit() for r, idx in by_radius.items()]
+        return jobs[0] if len(jobs) == 1 else jobs
+
+    def prune_voxel_maps(self, seqs=None, **kw):
+        """submit_prune + wait"""
+        job = self.submit_prune(seqs, **kw)
+        self.wait()
+        return job
 
     def clear_voxel_maps(self, seqs=None, wait=True):
         """svo_submit_clear_voxel_maps: queued; the maps of the slots `seqs` (None: all) become empty"""
@@ -947,6 +990,11 @@ class StereoSlam(StereoSlamBatch):
         def pick(job):
             return job.organized(0) if job.style.layout == hip_lib.CLOUD_ORGANIZED else job.points(0)
         return self._get(self.export_cloud, pick, what, None, **kw)
+
+    def prune_voxel_map(self, **kw):
+        """prune_voxel_maps of the one slot (min_count, min_stamp, radius in metres, center="pose" or xyz): its record
+        of hip_lib.PRUNE_INFO_DTYPE"""
+        return self.prune_voxel_maps([0], **kw).info[0].copy()
 
     def get_voxel_map(self, **kw):
         """the slot's voxel map as a numpy array of hip_lib.MAP_POINT_DTYPE in key order (export_voxel_maps of the one

@@ -14,6 +14,14 @@
   pipelined  frames/s over `--steps` queued steps of bench.py's workload without fusion and with a fuse job of every
              slot's newest keyframe queued behind every frame set; legs alternate, median of `--repeats` each.
 Prints one JSON line.
+
+  --prune    instead of all that (writes profiles/voxel_prune_bench.json): svo_voxel_prune of a map of
+             1 << 16, 20 and 24 entries at 0.25, 0.5 and 0.75 load (distinct voxels, half of them fused with stamp 1 and
+             half with stamp 2), keeping all (min_stamp 1: the early out) and keeping the newer half (min_stamp 2; the
+             map is restored from a copy ahead of every repeat, untimed), beside what the library could do with the
+             same map before: a count pass (svo_voxel_extract with points == NULL), svo_voxel_extract of the kept half,
+             and the host path a prune replaces: that half extracted and downloaded, svo_voxel_clear, the records
+             uploaded and fused again (wall clock; it loses the counts and stamps, which a prune keeps).
 """
 import argparse
 import datetime
@@ -154,8 +162,61 @@ def pipelined_leg(args, device, cfg, lefts, rights):
     return out
 
 
+def prune_leg(args, h):
+    out = []
+    for log2 in args.prune_log2:
+        cap = 1 << log2
+        for load in (0.25, 0.5, 0.75):
+            n = int(cap * load)
+            idx = np.arange(n)
+            xyz = (np.stack([idx % 512, idx // 512 % 512, idx // (512 * 512)], 1) + 0.5) * args.voxel
+            dev = torch.from_numpy(VR.records(xyz, (1, 2, 3)).view(np.uint8).reshape(-1, 16)).cuda()
+            half = n // 2
+            m = h.voxel_new(hip_lib.voxel_params(args.voxel, log2))
+            h.voxel_fuse([(dev[:half], 0, 1), (dev[half:], 0, 2)], [m])
+            assert h.voxel_info(m)["n_voxels"] == n
+            pristine = m[0].clone()
+            restore = lambda: m[0].copy_(pristine)
+            keep_all, keep_half = hip_lib.voxel_keep(min_stamp=1), hip_lib.voxel_keep(min_stamp=2)
+            row = {"log2_capacity": log2, "load": load, "voxels": n, "kept_half": n - half}
+            row["count_ms"], row["count_all_ms"] = event_ms(lambda: h.voxel_count(m), args.repeats)
+            row["prune_keep_all_ms"], row["prune_keep_all_all_ms"] = event_ms(lambda: h.voxel_prune(m, keep_all), args.repeats)
+            assert torch.equal(m[0], pristine)                               # nothing left: nothing written
+            row["prune_keep_half_ms"], row["prune_keep_half_all_ms"] = event_ms(lambda: h.voxel_prune(m, keep_half), args.repeats, before=restore)
+            assert h.voxel_info(m)["n_voxels"] == n - half
+            restore()
+            pts = torch.empty((n, 16), dtype=torch.uint8, device="cuda")
+            row["extract_half_ms"], row["extract_half_all_ms"] = event_ms(lambda: h.voxel_extract(m, min_stamp=2, points=pts, capacity=n), args.repeats)
+
+            def host_path():
+                _, k = h.voxel_extract(m, min_stamp=2, points=pts, capacity=n)
+                rec = pts[:k].cpu()
+                h.voxel_clear(m)
+                h.voxel_fuse([(rec.cuda(), 0, 2)], [m])
+            host = []
+            for _ in range(args.repeats + 1):
+                restore()
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                host_path()
+                torch.cuda.synchronize()
+                host.append((time.perf_counter() - t0) * 1e3)
+            assert h.voxel_info(m)["n_voxels"] == n - half
+            row["host_path_ms"], row["host_path_all_ms"] = statistics.median(host[1:]), host[1:]
+            row["keep_all_over_count"] = row["prune_keep_all_ms"] / row["count_ms"]
+            row["keep_half_over_extract_half"] = row["prune_keep_half_ms"] / row["extract_half_ms"]
+            row["host_path_over_keep_half"] = row["host_path_ms"] / row["prune_keep_half_ms"]
+            out.append(row)
+            print(json.dumps({k: v for k, v in row.items() if not k.endswith("all_ms")}), file=sys.stderr, flush=True)
+            del m, pristine, pts, dev
+            torch.cuda.empty_cache()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--prune", action="store_true", help="only the prune measurement (profiles/voxel_prune_bench.json)")
+    ap.add_argument("--prune-log2", type=int, nargs="+", default=[16, 20, 24])
     ap.add_argument("--slots", type=int, default=256)
     ap.add_argument("--step", type=int, default=4)
     ap.add_argument("--voxel", type=float, default=0.05)
@@ -169,6 +230,14 @@ def main():
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     device = torch.device("cuda", 0)
+    if args.prune:
+        out = {"tool": "tools/voxel_bench.py", "date": datetime.date.today().isoformat(), "command": " ".join(sys.argv),
+               "device": torch.cuda.get_device_name(0), "voxel": args.voxel, "repeats": args.repeats,
+               "prune": prune_leg(args, hip_lib.Handle(0, 1024))}
+        with open(args.out or os.path.join(ROOT, "profiles", "voxel_prune_bench.json"), "w") as fh:
+            json.dump(out, fh, indent=1)
+        print(json.dumps(out))
+        return
     cfg, lefts, rights = bench.render_loops("euroc", list(range(min(8, args.slots))), args.loop_frames, device)
     slam, packed = start(cfg, lefts, rights, args.slots, 1, device, args.warmup)
     for k in range(args.warmup):
