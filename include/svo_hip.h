@@ -1999,6 +1999,87 @@ int svo_submit_prune_voxel_maps(svo_ctx *ctx, const int *seqs, int n, const svo_
 int svo_prune_voxel_maps(svo_ctx *ctx, const int *seqs, int n, const svo_voxel_keep *keep, int center_mode,
                          const float *centers, svo_prune_info *info);   /* submit + wait */
 
+/* ---- sgm fusion: voxel maps fed by the clouds of SGM maps ------------
+ * A voxel map averages whatever depth it is given, and it lives for the whole run; the winner-takes-all disparities of
+ * "dense" are whole numbers, so z = baseline / d is a stack of sheets. This section and the two after it give the
+ * three consumers of a slot's dense cloud inside the ctx (the fuse job, the scene job's live layer, the occluded AR
+ * job) an SGM form. None has new arithmetic, a new kernel or a new kind of queue entry: each is the consumer's own
+ * statement with svo_submit_export_cloud_sgm(what, ..., style, sgm, check, ...) in the place of
+ * svo_submit_export_cloud_checked(what, ..., style, check, ...): the same records bit for bit, at the same queue
+ * position, into the same block that never leaves the device, and then the consumer's launches as they are.
+ *
+ * svo_submit_fuse_clouds_sgm is svo_submit_fuse_clouds with the params. `check` is the check of "sgm cross-check" (the
+ * second SGM map of the mirrored pair, not the reverse search of "cross-check"); NULL or lr == 0: unchecked.
+ * sgm == NULL IS svo_submit_fuse_clouds: the same launches, bytes, memory and rejections. Statuses and svo_fuse_info
+ * are unchanged; SVO_FUSE_FULL is settled as before, ahead of any launch. max_mean_cost bounds the aggregated cost
+ * over four paths, as in "sgm cross-check".
+ * Rejected with SVO_ERR_INVALID and nothing queued: everything svo_submit_fuse_clouds rejects and everything
+ * svo_submit_export_cloud_sgm rejects of style, sgm and check: a bad param (paths != 4 among them), the 16-bit bound,
+ * an effective search_x > 63, a non-zero _reserved, a check that is on with max_lr_diff <= 0.
+ * Memory, per group: the records and tables of svo_submit_fuse_clouds and the cloud job's staging block (slot_bytes of
+ * "clouds" per slot of a chunk), no reverse block whatever the check; the SGM planes of a chunk's delivered slots go
+ * through the group's block of "sgm" under its rule (slot_bytes of "sgm cross-check", chunks of max(1, 512 MiB /
+ * slot_bytes), SVO_SGM_CHUNK_SLOTS, one slot always fits), counted in svo_memory.device_bytes. The chunk of the fuse
+ * job is max(1, 256 MiB / (slot_bytes of "clouds" + 16 * points_per_slot)). A job without sgm, and a ctx that never
+ * asks, allocate, launch and copy what they did.
+ * No stage entry: the stage form is svo_cloud_points_sgm followed by svo_voxel_fuse. */
+int svo_submit_fuse_clouds_sgm(svo_ctx *ctx, int what, const int *seqs, int n, const svo_cloud_style *style,
+                               const svo_sgm_params *sgm, const svo_stereo_check *check, uint32_t stamp,
+                               svo_fuse_info *info);
+int svo_fuse_clouds_sgm(svo_ctx *ctx, int what, const int *seqs, int n, const svo_cloud_style *style,
+                        const svo_sgm_params *sgm, const svo_stereo_check *check, uint32_t stamp,
+                        svo_fuse_info *info);   /* submit + wait */
+
+/* ---- sgm scene clouds: the scene picture's live layer from SGM maps ------------
+ * svo_submit_export_scenes_clouds_sgm is svo_submit_export_scenes_clouds with the params: with live == 1 the live
+ * layer of named slot i is exactly the records svo_submit_export_cloud_sgm(clouds->what, ..., clouds->cloud in the
+ * organized layout, sgm, &clouds->check, ...) delivers for that slot at that queue position. clouds->check is then the
+ * check of "sgm cross-check"; lr == 0: unchecked. Segments, svo_scene_cloud_info, the extra spans, the splat pass
+ * and the tile render are unchanged. sgm == NULL IS svo_submit_export_scenes_clouds. A non-NULL sgm is validated
+ * whatever clouds says (also with clouds == NULL or live == 0, where the job is otherwise the plain one and the
+ * params are not used).
+ * Rejected with SVO_ERR_INVALID and nothing queued: everything svo_submit_export_scenes_clouds rejects, a bad sgm, and
+ * with live == 1 everything svo_submit_export_cloud_sgm rejects of clouds->cloud, sgm and clouds->check (as listed
+ * under "sgm fusion").
+ * Memory, per group: the blocks of "scene clouds" with
+ *   chunk = max(1, 256 MiB / (key_bytes + [live: slot_bytes + 16 * points_per_slot]))
+ * (no reverse_bytes term, and no reverse block), and the SGM planes of a chunk's delivered slots in the group's block of
+ * "sgm" under its rule, as in "sgm fusion". Per chunk the order on the group's stream is: cost volumes, paths, check,
+ * cloud write, clear, splat, tile render. A job without sgm allocates, launches and copies what it did.
+ * No stage entry: the stage form is svo_cloud_points_sgm followed by svo_render_scene_clouds. */
+int svo_submit_export_scenes_clouds_sgm(svo_ctx *ctx, const int *seqs, int n, const svo_scene_style *style,
+                                        const svo_scene_clouds *clouds, const svo_sgm_params *sgm,
+                                        const svo_scene_camera *cameras, const svo_scene_dst *dst, int mem);
+int svo_export_scenes_clouds_sgm(svo_ctx *ctx, const int *seqs, int n, const svo_scene_style *style,
+                                 const svo_scene_clouds *clouds, const svo_sgm_params *sgm,
+                                 const svo_scene_camera *cameras, const svo_scene_dst *dst, int mem);   /* submit + wait */
+
+/* ---- sgm ar occlusion: meshes hidden behind the depth of SGM maps ------------
+ * svo_submit_export_ar_occluded_sgm is svo_submit_export_ar_occluded with the params: with on == 1 the occluder of
+ * named slot i is exactly the records svo_submit_export_cloud_sgm(SVO_EXPORT_FRAMES, ..., occlusion->cloud in the
+ * camera frame and the organized layout, sgm, &occlusion->check, ...) delivers for that slot at that queue position.
+ * occlusion->check is then the check of "sgm cross-check"; lr == 0: unchecked. The pixel rule, the pictures' layout,
+ * segments and svo_ar_visibility are unchanged. sgm == NULL IS svo_submit_export_ar_occluded. A non-NULL sgm is
+ * validated whatever occlusion->on says, like the occlusion's scalar fields; with occlusion == NULL or on == 0 the job
+ * is otherwise svo_submit_export_ar and the params are not used.
+ * Rejected with SVO_ERR_INVALID and nothing queued: everything svo_submit_export_ar_occluded rejects, a bad sgm, and
+ * with on == 1 everything svo_submit_export_cloud_sgm rejects of occlusion->cloud, sgm and occlusion->check (as listed
+ * under "sgm fusion").
+ * Memory, per group: the blocks of "ar occlusion" with
+ *   chunk = max(1, 256 MiB / (slot_bytes + 16 * points_per_slot))
+ * (no reverse_bytes term, and no reverse block), and the SGM planes of a chunk's delivered slots in the group's block of
+ * "sgm" under its rule, as in "sgm fusion". Per chunk the order on the group's stream is: cost volumes, paths, check,
+ * cloud write, set-up, tile render. A job without sgm allocates, launches and copies what it did.
+ * No stage entry: the stage form is svo_cloud_points_sgm followed by svo_render_ar_occluded. */
+int svo_submit_export_ar_occluded_sgm(svo_ctx *ctx, const int *seqs, int n, const svo_ar_style *style,
+                                      const svo_ar_occlusion *occlusion, const svo_sgm_params *sgm,
+                                      const svo_ar_mesh *meshes, int n_meshes, const svo_ar_instance *instances,
+                                      const int *first, int n_instances, const svo_ar_dst *dst, int mem);
+int svo_export_ar_occluded_sgm(svo_ctx *ctx, const int *seqs, int n, const svo_ar_style *style,
+                               const svo_ar_occlusion *occlusion, const svo_sgm_params *sgm,
+                               const svo_ar_mesh *meshes, int n_meshes, const svo_ar_instance *instances,
+                               const int *first, int n_instances, const svo_ar_dst *dst, int mem);   /* submit + wait */
+
 /* ---- snapshots: the sequence state of a slot saved, loaded, moved between ctxs ------------
  * The reference has no checkpoint or resume (a StereoSlam lives and dies with its process). A snapshot is
  * everything the next frame of a slot depends on and everything its getters return, so that a sequence saved

@@ -37,11 +37,11 @@ int run_job(svo_group* g, int seq0, const svo_ctx::CloudExport& j) {
 }
 int run_job(svo_group* g, int seq0, const svo_ctx::SceneExport& j) {
     return grp_export_scenes_clouds(g, j.mem, j.seqs.data(), j.seg.data(), (int)j.seqs.size(), seq0, &j.style, j.cameras.data(), &j.dst,
-                                    j.has_clouds ? &j.clouds : nullptr, j.extra.empty() ? nullptr : j.extra.data());
+                                    j.has_clouds ? &j.clouds : nullptr, j.extra.empty() ? nullptr : j.extra.data(), j.sgm_ptr());
 }
 int run_job(svo_group* g, int seq0, const svo_ctx::ArExport& j) {
     return grp_export_ar_occluded(g, j.mem, j.seqs.data(), j.seg.data(), j.inst0.data(), j.inst1.data(), (int)j.seqs.size(), seq0, j.job.get(), &j.dst,
-                                  j.occluded ? &j.occlusion : nullptr);
+                                  j.occluded ? &j.occlusion : nullptr, j.sgm_ptr());
 }
 int run_job(svo_group* g, int, const svo_ctx::Save& j) { return grp_save(g, j.seqs.data(), (int)j.seqs.size(), j.snaps.data(), j.mem); }
 int run_job(svo_group* g, int, const svo_ctx::Load& j) { return grp_load(g, j.loads.data(), (int)j.loads.size(), j.mem); }
@@ -49,7 +49,7 @@ int run_job(svo_group* g, int, const svo_ctx::PoseUpdates& j) {
     return grp_pose_updates(g, j.seqs.data(), j.counts.data(), (int)j.seqs.size(), j.samples.data(), j.filtered.data());
 }
 int run_job(svo_group* g, int seq0, const svo_ctx::FuseClouds& j) {
-    return grp_fuse_clouds(g, j.what, j.seqs.data(), j.seg.data(), (int)j.seqs.size(), seq0, &j.style, j.check_ptr(), j.stamp, j.info);
+    return grp_fuse_clouds(g, j.what, j.seqs.data(), j.seg.data(), (int)j.seqs.size(), seq0, &j.style, j.check_ptr(), j.stamp, j.info, j.sgm_ptr());
 }
 int run_job(svo_group* g, int seq0, const svo_ctx::VoxelExport& j) {
     return grp_export_voxel_maps(g, j.mem, j.seqs.data(), j.seg.data(), j.regions.data(), (int)j.seqs.size(), seq0, &j.filter, &j.dst);

@@ -250,9 +250,20 @@ extern "C" int svo_submit_export_scenes(svo_ctx* c, const int* seqs, int n, cons
     return svo_submit_export_scenes_clouds(c, seqs, n, style, nullptr, cameras, dst, mem);
 }
 
-extern "C" int svo_submit_export_scenes_clouds(svo_ctx* c, const int* seqs, int n, const svo_scene_style* style,
-                                               const svo_scene_clouds* clouds, const svo_scene_camera* cameras, const svo_scene_dst* dst,
-                                               int mem) {
+// svo_submit_export_scenes_clouds (sgm == null) and svo_submit_export_scenes_clouds_sgm, whose params are checked
+// whatever clouds->live says and used by the live layer only
+static int submit_scenes_clouds(svo_ctx* c, const int* seqs, int n, const svo_scene_style* style, const svo_scene_clouds* clouds,
+                                const svo_sgm_params* sgm, const svo_scene_camera* cameras, const svo_scene_dst* dst, int mem) {
+    if (sgm) {
+        const char* const who = "svo_submit_export_scenes_clouds_sgm";
+        if (const int rc = svo::sgm_check_params(sgm, who, nullptr)) return rc;
+        if (c && clouds && clouds->live == 1) {
+            if (const int rc = grp_check_scene_clouds(c->g0(), clouds)) return rc;
+            if (const int rc = grp_check_cloud_sgm(c->g0(), &clouds->cloud, sgm, who)) return rc;
+        } else {
+            sgm = nullptr;
+        }
+    }
     if (clouds && clouds->live == 0 && !clouds->extra) {             // (nothing to draw: the plain job, once the clouds are checked)
         if (c)
             if (const int rc = grp_check_scene_clouds(c->g0(), clouds)) return rc;
@@ -283,8 +294,27 @@ extern "C" int svo_submit_export_scenes_clouds(svo_ctx* c, const int* seqs, int 
     }, [&](svo_ctx::SceneExport& e) {
         e.mem = mem; e.style = *style; e.dst = *dst;
         if (clouds) { e.has_clouds = true; e.clouds = *clouds; }
+        e.set_sgm(sgm);
     });
     return SVO_OK;
+}
+
+extern "C" int svo_submit_export_scenes_clouds(svo_ctx* c, const int* seqs, int n, const svo_scene_style* style,
+                                               const svo_scene_clouds* clouds, const svo_scene_camera* cameras, const svo_scene_dst* dst,
+                                               int mem) {
+    return submit_scenes_clouds(c, seqs, n, style, clouds, nullptr, cameras, dst, mem);
+}
+
+// the scene job whose live layer is the cloud of SGM maps (include/svo_hip.h, "sgm scene clouds")
+extern "C" int svo_submit_export_scenes_clouds_sgm(svo_ctx* c, const int* seqs, int n, const svo_scene_style* style,
+                                                   const svo_scene_clouds* clouds, const svo_sgm_params* sgm,
+                                                   const svo_scene_camera* cameras, const svo_scene_dst* dst, int mem) {
+    return submit_scenes_clouds(c, seqs, n, style, clouds, sgm, cameras, dst, mem);
+}
+
+extern "C" int svo_export_scenes_clouds_sgm(svo_ctx* c, const int* seqs, int n, const svo_scene_style* style, const svo_scene_clouds* clouds,
+                                            const svo_sgm_params* sgm, const svo_scene_camera* cameras, const svo_scene_dst* dst, int mem) {
+    return then_wait(c, svo_submit_export_scenes_clouds_sgm(c, seqs, n, style, clouds, sgm, cameras, dst, mem));
 }
 
 extern "C" int svo_export_scenes(svo_ctx* c, const int* seqs, int n, const svo_scene_style* style,
@@ -299,15 +329,24 @@ extern "C" int svo_export_scenes_clouds(svo_ctx* c, const int* seqs, int n, cons
 
 // ------------------------------------------------------------------ AR pictures
 
-// svo_submit_export_ar (occlusion == null) and svo_submit_export_ar_occluded
+// svo_submit_export_ar (occlusion == null), svo_submit_export_ar_occluded (sgm == null) and
+// svo_submit_export_ar_occluded_sgm, whose params are checked whatever occlusion->on says and used with on == 1 only
 static int submit_export_ar(svo_ctx* c, const char* who, const int* seqs, int n, const svo_ar_style* style, const svo_ar_occlusion* occlusion,
-                            const svo_ar_mesh* meshes, int n_meshes, const svo_ar_instance* instances, const int* first, int n_instances,
+                            const svo_sgm_params* sgm, const svo_ar_mesh* meshes, int n_meshes, const svo_ar_instance* instances, const int* first, int n_instances,
                             const svo_ar_dst* dst, int mem) {
     if (!c || !dst || !dst->segments || !mem_ok(mem) || !naming_ok(seqs, n) || n_meshes < 0 ||
         n_instances < 0 || (n_meshes > 0 && !meshes) || (n_instances > 0 && !instances))
         return svo_set_error(SVO_ERR_INVALID, "%s: bad arguments (mem %d, %d meshes, %d instances)", who, mem, n_meshes, n_instances);
     if (const int rc = svo::ar_check_style(style, who)) return rc;
     if (const int rc = grp_check_ar_occlusion(c->g0(), occlusion)) return rc;
+    if (sgm) {
+        if (const int rc = svo::sgm_check_params(sgm, who, nullptr)) return rc;
+        if (occlusion && occlusion->on == 1) {
+            if (const int rc = grp_check_cloud_sgm(c->g0(), &occlusion->cloud, sgm, who)) return rc;
+        } else {
+            sgm = nullptr;
+        }
+    }
     if (!dst->pixels || ((uintptr_t)dst->pixels & 3)) return svo_set_error(SVO_ERR_INVALID, "%s: pixels is NULL or not 4-byte aligned", who);
     const NamedSlots slots = ctx_slots(c, seqs, n);
     n = slots.n;
@@ -357,6 +396,7 @@ static int submit_export_ar(svo_ctx* c, const char* who, const int* seqs, int n,
     }, [&](svo_ctx::ArExport& e) {
         e.mem = mem; e.job = job; e.dst = *dst;
         if (occlusion && occlusion->on == 1) { e.occluded = true; e.occlusion = *occlusion; }
+        e.set_sgm(sgm);
     });
     return SVO_OK;
 }
@@ -364,13 +404,29 @@ static int submit_export_ar(svo_ctx* c, const char* who, const int* seqs, int n,
 extern "C" int svo_submit_export_ar(svo_ctx* c, const int* seqs, int n, const svo_ar_style* style, const svo_ar_mesh* meshes,
                                     int n_meshes, const svo_ar_instance* instances, const int* first, int n_instances,
                                     const svo_ar_dst* dst, int mem) {
-    return submit_export_ar(c, "svo_submit_export_ar", seqs, n, style, nullptr, meshes, n_meshes, instances, first, n_instances, dst, mem);
+    return submit_export_ar(c, "svo_submit_export_ar", seqs, n, style, nullptr, nullptr, meshes, n_meshes, instances, first, n_instances, dst, mem);
 }
 
 extern "C" int svo_submit_export_ar_occluded(svo_ctx* c, const int* seqs, int n, const svo_ar_style* style, const svo_ar_occlusion* occlusion,
                                              const svo_ar_mesh* meshes, int n_meshes, const svo_ar_instance* instances, const int* first,
                                              int n_instances, const svo_ar_dst* dst, int mem) {
-    return submit_export_ar(c, "svo_submit_export_ar_occluded", seqs, n, style, occlusion, meshes, n_meshes, instances, first, n_instances, dst, mem);
+    return submit_export_ar(c, "svo_submit_export_ar_occluded", seqs, n, style, occlusion, nullptr, meshes, n_meshes, instances, first, n_instances, dst, mem);
+}
+
+// the occluded job behind the depth of SGM maps (include/svo_hip.h, "sgm ar occlusion")
+extern "C" int svo_submit_export_ar_occluded_sgm(svo_ctx* c, const int* seqs, int n, const svo_ar_style* style, const svo_ar_occlusion* occlusion,
+                                                 const svo_sgm_params* sgm, const svo_ar_mesh* meshes, int n_meshes,
+                                                 const svo_ar_instance* instances, const int* first, int n_instances, const svo_ar_dst* dst,
+                                                 int mem) {
+    if (!sgm) return svo_submit_export_ar_occluded(c, seqs, n, style, occlusion, meshes, n_meshes, instances, first, n_instances, dst, mem);
+    return submit_export_ar(c, "svo_submit_export_ar_occluded_sgm", seqs, n, style, occlusion, sgm, meshes, n_meshes, instances, first, n_instances,
+                            dst, mem);
+}
+
+extern "C" int svo_export_ar_occluded_sgm(svo_ctx* c, const int* seqs, int n, const svo_ar_style* style, const svo_ar_occlusion* occlusion,
+                                          const svo_sgm_params* sgm, const svo_ar_mesh* meshes, int n_meshes, const svo_ar_instance* instances,
+                                          const int* first, int n_instances, const svo_ar_dst* dst, int mem) {
+    return then_wait(c, svo_submit_export_ar_occluded_sgm(c, seqs, n, style, occlusion, sgm, meshes, n_meshes, instances, first, n_instances, dst, mem));
 }
 
 extern "C" int svo_export_ar_occluded(svo_ctx* c, const int* seqs, int n, const svo_ar_style* style, const svo_ar_occlusion* occlusion,

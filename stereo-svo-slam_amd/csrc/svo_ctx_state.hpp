@@ -85,17 +85,22 @@ struct svo_ctx {
     };
     template <typename Style, typename Dst>
     struct CheckedExport : ImageExport<Style, Dst>, StereoCheck {};
-    // (svo_submit_export_disparity_sgm, svo_submit_export_cloud_sgm: the same job carrying the SGM params)
-    template <typename Style, typename Dst>
-    struct SgmExport : CheckedExport<Style, Dst> {
+    // the SGM params a job carries beside its style, or none (the entries with _sgm in their names: the same job in
+    // its SGM mode)
+    struct SgmMode {
         bool has_sgm = false;
         svo_sgm_params sgm{};
         const svo_sgm_params* sgm_ptr() const { return has_sgm ? &sgm : nullptr; }
+        void set_sgm(const svo_sgm_params* p) {
+            if (p) { has_sgm = true; sgm = *p; }
+        }
     };
+    template <typename Style, typename Dst>
+    struct SgmExport : CheckedExport<Style, Dst>, SgmMode {};
     using DisparityExport = SgmExport<svo_disparity_style, svo_disparity_dst>;
     using CloudExport = SgmExport<svo_cloud_style, svo_cloud_dst>;
     // the group's share of an svo_submit_export_scenes: the camera of each slot
-    struct SceneExport : SlotShare {
+    struct SceneExport : SlotShare, SgmMode {
         int mem = 0;
         std::vector<svo_scene_camera> cameras;
         svo_scene_style style{};
@@ -107,7 +112,7 @@ struct svo_ctx {
     };
     // the group's share of an svo_submit_export_ar: the instances [inst0, inst1) of the job each slot shows, and the
     // job's copied arrays, which the groups share
-    struct ArExport : SlotShare {
+    struct ArExport : SlotShare, SgmMode {
         int mem = 0;
         std::vector<int> inst0, inst1;
         std::shared_ptr<const ArJob> job;
@@ -134,7 +139,7 @@ struct svo_ctx {
         std::vector<float*> filtered;
     };
     // the group's share of an svo_submit_fuse_clouds: a slot fills the info of its named position
-    struct FuseClouds : SlotShare, StereoCheck {
+    struct FuseClouds : SlotShare, StereoCheck, SgmMode {
         int what = 0;
         svo_cloud_style style{};
         uint32_t stamp = 0;

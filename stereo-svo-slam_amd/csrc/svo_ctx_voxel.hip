@@ -25,22 +25,42 @@ extern "C" int svo_get_voxel_map_info(svo_ctx* ctx, int seq, svo_voxel_map_info*
     return SVO_OK;
 }
 
-extern "C" int svo_submit_fuse_clouds(svo_ctx* c, int what, const int* seqs, int n, const svo_cloud_style* style,
-                                      const svo_stereo_check* check, uint32_t stamp, svo_fuse_info* info) {
-    if (const int rc = drop_check_that_is_off(&check, true, "svo_submit_fuse_clouds")) return rc;
-    if (!c || !info || !what_ok(what) || !naming_ok(seqs, n))
-        return svo_set_error(SVO_ERR_INVALID, "svo_submit_fuse_clouds: bad arguments (what %d)", what);
+// svo_submit_fuse_clouds (sgm == null) and svo_submit_fuse_clouds_sgm
+static int submit_fuse_clouds(svo_ctx* c, const char* who, int what, const int* seqs, int n, const svo_cloud_style* style,
+                              const svo_sgm_params* sgm, const svo_stereo_check* check, uint32_t stamp, svo_fuse_info* info) {
+    if (const int rc = drop_check_that_is_off(&check, true, who)) return rc;
+    if (!c || !info || !what_ok(what) || !naming_ok(seqs, n)) return svo_set_error(SVO_ERR_INVALID, "%s: bad arguments (what %d)", who, what);
     if (const int rc = grp_check_cloud_style(c->g0(), style, check)) return rc;
+    if (sgm)
+        if (const int rc = grp_check_cloud_sgm(c->g0(), style, sgm, who)) return rc;
     if (style->frame != SVO_CLOUD_WORLD || style->layout != 0)
-        return svo_set_error(SVO_ERR_INVALID, "svo_submit_fuse_clouds: frame must be SVO_CLOUD_WORLD and layout 0");
+        return svo_set_error(SVO_ERR_INVALID, "%s: frame must be SVO_CLOUD_WORLD and layout 0", who);
     const NamedSlots slots = ctx_slots(c, seqs, n);
-    if (const int rc = check_slots(c, "svo_submit_fuse_clouds", slots)) return rc;
-    if (c->failed.load()) return reject_failed(c, "svo_submit_fuse_clouds");
+    if (const int rc = check_slots(c, who, slots)) return rc;
+    if (c->failed.load()) return reject_failed(c, who);
     submit_shares<svo_ctx::FuseClouds>(c, slots, every_slot, [&](svo_ctx::FuseClouds& e) {
         e.what = what; e.style = *style; e.stamp = stamp; e.info = info;
         e.set_check(check);
+        e.set_sgm(sgm);
     });
     return SVO_OK;
+}
+
+extern "C" int svo_submit_fuse_clouds(svo_ctx* c, int what, const int* seqs, int n, const svo_cloud_style* style,
+                                      const svo_stereo_check* check, uint32_t stamp, svo_fuse_info* info) {
+    return submit_fuse_clouds(c, "svo_submit_fuse_clouds", what, seqs, n, style, nullptr, check, stamp, info);
+}
+
+// the fuse job over SGM maps (include/svo_hip.h, "sgm fusion"): the same queue entry carrying the params
+extern "C" int svo_submit_fuse_clouds_sgm(svo_ctx* c, int what, const int* seqs, int n, const svo_cloud_style* style,
+                                          const svo_sgm_params* sgm, const svo_stereo_check* check, uint32_t stamp, svo_fuse_info* info) {
+    if (!sgm) return svo_submit_fuse_clouds(c, what, seqs, n, style, check, stamp, info);
+    return submit_fuse_clouds(c, "svo_submit_fuse_clouds_sgm", what, seqs, n, style, sgm, check, stamp, info);
+}
+
+extern "C" int svo_fuse_clouds_sgm(svo_ctx* c, int what, const int* seqs, int n, const svo_cloud_style* style, const svo_sgm_params* sgm,
+                                   const svo_stereo_check* check, uint32_t stamp, svo_fuse_info* info) {
+    return then_wait(c, svo_submit_fuse_clouds_sgm(c, what, seqs, n, style, sgm, check, stamp, info));
 }
 
 extern "C" int svo_fuse_clouds(svo_ctx* c, int what, const int* seqs, int n, const svo_cloud_style* style, const svo_stereo_check* check,

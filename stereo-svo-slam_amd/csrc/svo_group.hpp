@@ -71,10 +71,10 @@ int grp_export_scenes(svo_group* g, int mem, const int* seqs, const int* seg, in
 int64_t grp_scene_bytes(const svo_scene_style* style);   // the image_bytes of a checked style
 // grp_export_scenes with cloud points (svo_submit_export_scenes_clouds). clouds: checked (grp_check_scene_clouds), its
 // extra is not read; extra: null, or the span of every seqs[i], checked; clouds->info[seg[i]] is filled if there is one.
-// clouds == null is grp_export_scenes.
+// clouds == null is grp_export_scenes. sgm: checked (grp_check_cloud_sgm); the live layer is then the SGM cloud job's.
 int grp_export_scenes_clouds(svo_group* g, int mem, const int* seqs, const int* seg, int n, int seq0, const svo_scene_style* style,
                              const svo_scene_camera* cameras, const svo_scene_dst* dst, const svo_scene_clouds* clouds,
-                             const svo_scene_span* extra);
+                             const svo_scene_span* extra, const svo_sgm_params* sgm = nullptr);
 // what svo_submit_export_scenes_clouds checks of a clouds but for its spans
 int grp_check_scene_clouds(const svo_group* g, const svo_scene_clouds* clouds);
 // What svo_submit_export_ar copied of its caller's arrays, checked; the jobs of all groups share one (read only).
@@ -98,9 +98,9 @@ int grp_export_ar(svo_group* g, int mem, const int* seqs, const int* seg, const 
 int64_t grp_ar_bytes(const svo_group* g, const svo_ar_style* style);   // the image_bytes of a checked style
 // grp_export_ar hidden behind the slots' dense stereo depth (svo_submit_export_ar_occluded). occlusion: checked
 // (grp_check_ar_occlusion) with on == 1; occlusion->info[seg[i]] is filled if there is one. occlusion == null is
-// grp_export_ar.
+// grp_export_ar. sgm: checked (grp_check_cloud_sgm); the occluder is then the SGM cloud job's.
 int grp_export_ar_occluded(svo_group* g, int mem, const int* seqs, const int* seg, const int* inst0, const int* inst1, int n, int seq0,
-                           const ArJob* job, const svo_ar_dst* dst, const svo_ar_occlusion* occlusion);
+                           const ArJob* job, const svo_ar_dst* dst, const svo_ar_occlusion* occlusion, const svo_sgm_params* sgm = nullptr);
 // what svo_submit_export_ar_occluded checks of an occlusion (null: nothing)
 int grp_check_ar_occlusion(const svo_group* g, const svo_ar_occlusion* occlusion);
 // One group's share of svo_submit_export_disparity (svo_group_dense.hip), between two steps of the group, on the thread
@@ -128,17 +128,20 @@ int grp_check_cloud_style(const svo_group* g, const svo_cloud_style* style, cons
 int64_t grp_cloud_points(const svo_group* g, const svo_cloud_style* style);
 // what svo_submit_export_cloud_sgm checks beside the style: the params, and an effective search_x <= 63
 int grp_check_cloud_sgm(const svo_group* g, const svo_cloud_style* style, const svo_sgm_params* sgm, const char* who);
-// what one slot of a device-mode job with that checked style and check stages: slot_bytes [+ reverse_bytes]
-int64_t grp_cloud_slot_bytes(const svo_group* g, const svo_cloud_style* style, const svo_stereo_check* check);
+// what one slot of a device-mode job with that checked style and check stages in the cloud job's blocks: slot_bytes
+// [+ reverse_bytes]; an SGM job (sgm != null) has no reverse block
+int64_t grp_cloud_slot_bytes(const svo_group* g, const svo_cloud_style* style, const svo_stereo_check* check,
+                             const svo_sgm_params* sgm = nullptr);
 // Voxel maps (svo_group_voxel.hip). grp_set_voxel_maps: the named slots (indices in the group) get a cleared map of
 // `params` (checked), or with params == null lose theirs; grp_voxel_map_info: false for a slot without a map (both:
 // the queues have drained). The three jobs run between two steps of the group, on the thread that drives it, and are
 // delivered on return; a failed group rejects them. grp_fuse_clouds: slot seqs[i] fills info[seg[i]];
-// grp_export_voxel_maps: slot seqs[i] fills dst->segments[seg[i]] and goes where regions[i] says.
+// grp_export_voxel_maps: slot seqs[i] fills dst->segments[seg[i]] and goes where regions[i] says. grp_fuse_clouds with
+// sgm (checked: grp_check_cloud_sgm) fuses the records of the SGM cloud job.
 int grp_set_voxel_maps(svo_group* g, const int* seqs, int n, const svo_voxel_params* params);
 bool grp_voxel_map_info(svo_group* g, int seq, svo_voxel_map_info* info);
 int grp_fuse_clouds(svo_group* g, int what, const int* seqs, const int* seg, int n, int seq0, const svo_cloud_style* style,
-                    const svo_stereo_check* check, uint32_t stamp, svo_fuse_info* info);
+                    const svo_stereo_check* check, uint32_t stamp, svo_fuse_info* info, const svo_sgm_params* sgm = nullptr);
 int grp_export_voxel_maps(svo_group* g, int mem, const int* seqs, const int* seg, const svo_voxel_region* regions, int n, int seq0,
                           const svo_voxel_filter* filter, const svo_voxel_dst* dst);
 int grp_clear_voxel_maps(svo_group* g, const int* seqs, int n);

@@ -78,9 +78,11 @@ int grp_check_ar_occlusion(const svo_group* c, const svo_ar_occlusion* occlusion
 // of its slots is grp_export_cloud itself, in device mode, the camera frame and the organized layout, into the group's
 // d_ar_occ block (search, check, cloud write: its launches, its blocks); then the first launch over the chunk's
 // triangles and the tile kernel over its tiles. Slot i of the job has records i % chunk of the block. The counters of
-// every slot come back in one copy after the last chunk.
+// every slot come back in one copy after the last chunk. With sgm the occluder is the SGM cloud job's
+// (svo_submit_export_ar_occluded_sgm): it fills the argument blocks itself and has left them when it returns, before
+// this job's tile table is built.
 int grp_export_ar_occluded(svo_group* c, int mem, const int* seqs, const int* seg, const int* inst0, const int* inst1, int n, int seq0,
-                           const ArJob* job, const svo_ar_dst* dst, const svo_ar_occlusion* occl) {
+                           const ArJob* job, const svo_ar_dst* dst, const svo_ar_occlusion* occl, const svo_sgm_params* sgm) {
     if (const int rc = job_begin(c, "svo_submit_export_ar")) return rc;
     hipStream_t st = c->stream.get();
     const bool host = mem == SVO_MEM_HOST;
@@ -178,7 +180,7 @@ int grp_export_ar_occluded(svo_group* c, int mem, const int* seqs, const int* se
             points = grp_cloud_points(c, &cloud_style);
             const size_t rec_bytes = sizeof(svo_map_point) * (size_t)points;
             // (SVO_AR_CHUNK_SLOTS: fewer slots per chunk, so that tests reach the chunked path)
-            const size_t per_slot = (size_t)grp_cloud_slot_bytes(c, &cloud_style, check) + rec_bytes;
+            const size_t per_slot = (size_t)grp_cloud_slot_bytes(c, &cloud_style, check, sgm) + rec_bytes;
             m_max = std::min<size_t>((size_t)n, table_tiles("SVO_AR_CHUNK_SLOTS", std::max<size_t>(1, AR_STAGING_BYTES / std::max<size_t>(per_slot, 1))));
             if (const int rc = c->d_ar_occ.reserve(c, m_max * rec_bytes)) return rc;
             for (size_t k = 0; k < placed.size(); k++)
@@ -225,7 +227,7 @@ int grp_export_ar_occluded(svo_group* c, int mem, const int* seqs, const int* se
                 if (ran) HIP_TRY(hipStreamSynchronize(st));  // the records and the argument blocks are free for this chunk
                 ran = true;
                 const svo_cloud_dst cloud_dst{csegs.data(), reinterpret_cast<svo_map_point*>(c->d_ar_occ.p), (int64_t)m * points};
-                if (const int rc = grp_export_cloud(c, SVO_EXPORT_FRAMES, SVO_MEM_DEVICE, seqs + i0, local.data(), m, seq0, &cloud_style, check, &cloud_dst))
+                if (const int rc = grp_export_cloud(c, SVO_EXPORT_FRAMES, SVO_MEM_DEVICE, seqs + i0, local.data(), m, seq0, &cloud_style, check, &cloud_dst, sgm))
                     return rc;
                 for (size_t kk = k0; kk < k; kk++) {
                     const svo_cloud_segment& e = csegs[(size_t)(placed[kk].i - i0)];

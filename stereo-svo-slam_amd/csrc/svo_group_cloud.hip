@@ -79,13 +79,13 @@ int64_t grp_cloud_points(const svo_group* c, const svo_cloud_style* style) {
     return (int64_t)(c->width / s.step) * (c->height / s.step);
 }
 
-int64_t grp_cloud_slot_bytes(const svo_group* c, const svo_cloud_style* style, const svo_stereo_check* check) {
+int64_t grp_cloud_slot_bytes(const svo_group* c, const svo_cloud_style* style, const svo_stereo_check* check, const svo_sgm_params* sgm) {
     DenseParams s;
     if (cloud_check_style(style, &c->cam, "svo_submit_export_cloud", &s, nullptr) != SVO_OK) return 0;
     LrCheck lr;
     if (lr_check_parse(check, true, "svo_submit_export_cloud", &lr) != SVO_OK) return 0;
     const size_t points = (size_t)(c->width / s.step) * (size_t)(c->height / s.step);
-    return (int64_t)(Staging(points, false, 1).slot + (lr.on ? lr_reverse_bytes(c->width, c->height, s.step) : 0));
+    return (int64_t)(Staging(points, false, 1).slot + (lr.on && !sgm ? lr_reverse_bytes(c->width, c->height, s.step) : 0));
 }
 
 // The named slots of the group as segments and records (svo_submit_export_cloud). Named slot seg[i] of the job owns

@@ -144,10 +144,12 @@ int grp_export_scenes(svo_group* c, int mem, const int* seqs, const int* seg, in
 // the chunk's key planes, the other part of that block, are cleared to all ones; the pieces of every slot's extra span
 // and live records go through the splat pass; then the tile kernel that starts from the planes. The span table takes
 // the first half of the group's argument blocks, the tile table the second. Every delivered slot has a plane: one that
-// nobody offers to stays all ones, which is the picture without cloud points.
+// nobody offers to stays all ones, which is the picture without cloud points. With sgm the live layer is the SGM cloud
+// job's (svo_submit_export_scenes_clouds_sgm): it fills the argument blocks itself and has left them when it returns,
+// before this job's span and tile tables are built.
 int grp_export_scenes_clouds(svo_group* c, int mem, const int* seqs, const int* seg, int n, int seq0, const svo_scene_style* style,
                              const svo_scene_camera* cameras, const svo_scene_dst* dst, const svo_scene_clouds* clouds,
-                             const svo_scene_span* extra) {
+                             const svo_scene_span* extra, const svo_sgm_params* sgm) {
     if (const int rc = job_begin(c, "svo_submit_export_scenes")) return rc;
     hipStream_t st = c->stream.get();
     const bool host = mem == SVO_MEM_HOST;
@@ -229,6 +231,7 @@ int grp_export_scenes_clouds(svo_group* c, int mem, const int* seqs, const int* 
         }
         // the chunks of a job with clouds: slot i of the job has plane and records i % m_max of the block
         const bool live = clouds && clouds->live == 1;
+        if (!live) sgm = nullptr;
         const svo_stereo_check* check = live && clouds->check.lr ? &clouds->check : nullptr;
         const int64_t points = live ? grp_cloud_points(c, &clouds->cloud) : 0;
         const size_t key_bytes = scene_key_bytes(cols, rows), rec_bytes = sizeof(svo_map_point) * (size_t)points;
@@ -238,7 +241,7 @@ int grp_export_scenes_clouds(svo_group* c, int mem, const int* seqs, const int* 
         if (clouds) {
             // (SVO_SCENE_CHUNK_SLOTS: fewer slots per chunk, so that tests reach the chunked path)
             const char* lower = std::getenv("SVO_SCENE_CHUNK_SLOTS");
-            m_max = scene_chunk_slots(key_bytes + (live ? grp_cloud_slot_bytes(c, &clouds->cloud, check) + rec_bytes : 0), (size_t)n,
+            m_max = scene_chunk_slots(key_bytes + (live ? grp_cloud_slot_bytes(c, &clouds->cloud, check, sgm) + rec_bytes : 0), (size_t)n,
                                       lower ? std::atoll(lower) : 0);
             if (const int rc = c->d_scene_cloud.reserve(c, m_max * (key_bytes + rec_bytes))) return rc;
             d_records = c->d_scene_cloud.p + m_max * key_bytes;
@@ -277,7 +280,7 @@ int grp_export_scenes_clouds(svo_group* c, int mem, const int* seqs, const int* 
                 if (i0 > 0) HIP_TRY(hipStreamSynchronize(st));   // the block is free for this chunk
                 if (live) {
                     const svo_cloud_dst cloud_dst{csegs.data(), reinterpret_cast<svo_map_point*>(d_records), (int64_t)m * points};
-                    if (const int rc = grp_export_cloud(c, clouds->what, SVO_MEM_DEVICE, seqs + i0, local.data(), m, seq0, &cloud_style, check, &cloud_dst))
+                    if (const int rc = grp_export_cloud(c, clouds->what, SVO_MEM_DEVICE, seqs + i0, local.data(), m, seq0, &cloud_style, check, &cloud_dst, sgm))
                         return rc;
                 }
                 HIP_TRY(hipMemsetAsync(c->d_scene_cloud.p, 0xff, (size_t)m * key_bytes, st));

@@ -82,9 +82,10 @@ int grp_clear_voxel_maps(svo_group* c, const int* seqs, int n) {
 // The statuses are settled on the host first (no map, no frame or keyframe, the load bound with the mirror's
 // n_voxels); the slots that are left run in chunks: grp_export_cloud in device mode writes the chunk's organized
 // records into d_voxel_records, one fuse launch puts them into the slots' maps, one launch gathers the maps' headers
-// and one copy brings them back: the new mirrors, and what the job added to the counters.
+// and one copy brings them back: the new mirrors, and what the job added to the counters. With sgm the records are the
+// SGM cloud job's (svo_submit_fuse_clouds_sgm): its planes and check in the group's d_sgm block, no reverse block.
 int grp_fuse_clouds(svo_group* c, int what, const int* seqs, const int* seg, int n, int seq0, const svo_cloud_style* style,
-                    const svo_stereo_check* check, uint32_t stamp, svo_fuse_info* info) {
+                    const svo_stereo_check* check, uint32_t stamp, svo_fuse_info* info, const svo_sgm_params* sgm) {
     if (const int rc = job_begin(c, "svo_submit_fuse_clouds")) return rc;
     hipStream_t st = c->stream.get();
     svo_cloud_style organized = *style;
@@ -107,7 +108,7 @@ int grp_fuse_clouds(svo_group* c, int what, const int* seqs, const int* seg, int
     if (todo.empty()) return SVO_OK;
     const size_t rec_bytes = sizeof(svo_map_point) * (size_t)points;
     // (SVO_CLOUD_CHUNK_SLOTS: fewer slots per chunk, so that tests reach the chunked path)
-    const size_t per_slot = (size_t)grp_cloud_slot_bytes(c, &organized, check) + rec_bytes;
+    const size_t per_slot = (size_t)grp_cloud_slot_bytes(c, &organized, check, sgm) + rec_bytes;
     const size_t m_max = std::min(todo.size(), table_tiles("SVO_CLOUD_CHUNK_SLOTS", std::max<size_t>(1, FUSE_STAGING_BYTES / std::max<size_t>(per_slot, 1))));
     if (const int rc = c->d_voxel_records.reserve(c, m_max * rec_bytes)) return rc;
     svo_map_point* const d_records = reinterpret_cast<svo_map_point*>(c->d_voxel_records.p);
@@ -122,7 +123,7 @@ int grp_fuse_clouds(svo_group* c, int what, const int* seqs, const int* seg, int
     for (size_t i0 = 0; i0 < todo.size(); i0 += m_max) {
         const int m = (int)std::min(m_max, todo.size() - i0);
         const svo_cloud_dst cloud_dst{csegs.data(), d_records, (int64_t)m * points};
-        if (const int rc = grp_export_cloud(c, what, SVO_MEM_DEVICE, todo.data() + i0, local.data(), m, seq0, &organized, check, &cloud_dst)) return rc;
+        if (const int rc = grp_export_cloud(c, what, SVO_MEM_DEVICE, todo.data() + i0, local.data(), m, seq0, &organized, check, &cloud_dst, sgm)) return rc;
         VoxelMapDev* h_maps = reinterpret_cast<VoxelMapDev*>(h_tab + maps_off);
         VoxelSpanDev* h_spans = reinterpret_cast<VoxelSpanDev*>(h_tab + spans_off);
         int n_spans = 0;

@@ -50,6 +50,8 @@ SYMBOLS = (
     "svo_dense_cost_volume", "svo_sgm_aggregate", "svo_dense_disparity_sgm",
     "svo_submit_export_disparity_sgm_checked", "svo_export_disparity_sgm_checked", "svo_dense_disparity_sgm_checked",
     "svo_submit_export_cloud_sgm", "svo_export_cloud_sgm", "svo_cloud_points_sgm",
+    "svo_submit_fuse_clouds_sgm", "svo_fuse_clouds_sgm", "svo_submit_export_scenes_clouds_sgm", "svo_export_scenes_clouds_sgm",
+    "svo_submit_export_ar_occluded_sgm", "svo_export_ar_occluded_sgm",
     "svo_scene_size", "svo_scene_look_at", "svo_scene_frustum", "svo_submit_export_scenes", "svo_export_scenes",
     "svo_render_scene",
     "svo_submit_export_scenes_clouds", "svo_export_scenes_clouds", "svo_render_scene_clouds",
@@ -485,6 +487,17 @@ def sgm_job(sgm):
     return sgm_params(**fields), check
 
 
+def sgm_consumer(sgm, lr_check, where):
+    """sgm_job for a consumer of the cloud job (submit_fuse, the dense= dict of submit_scenes, the occlusion= dict of
+    submit_ar) whose own lr_check sits beside sgm: the two checks are different rules, so lr_check together with sgm
+    raises ValueError; `where` names the place for the message ("dense", "occlusion", "submit_fuse")."""
+    params, check = sgm_job(sgm)
+    if params is not None and lr_check:
+        raise ValueError(f"{where}: lr_check is the cross-check of the winner-takes-all search; with sgm the cross-check is "
+                         f"the lr_check key of the sgm dict, e.g. sgm=dict(hip_lib.SGM_DEFAULTS, lr_check=1.0)")
+    return params, check
+
+
 def disparity_size(cam, width, height, style, check=None):
     """svo_disparity_size (host only): (cols, rows, planes, image_bytes) of one slot of a disparity job with `style`;
     check: a StereoCheck (svo_disparity_size_checked), or None."""
@@ -666,7 +679,9 @@ class SceneCloudInfo(C.Structure):
 
 
 class SceneClouds(C.Structure):
-    """svo_scene_clouds (include/svo_hip.h): the live layer and the extra spans of a scene job."""
+    """svo_scene_clouds (include/svo_hip.h): the live layer and the extra spans of a scene job. sgm (Python only): None,
+    or the SgmParams the job goes through svo_submit_export_scenes_clouds_sgm with; `check` is then the SGM map's own."""
+    sgm = None
     _fields_ = [("live", C.c_int32), ("what", C.c_int32), ("cloud", CloudStyle), ("check", StereoCheck),
                 ("point_size", C.c_int32), ("_reserved", C.c_int32 * 3), ("extra", C.c_void_p), ("info", C.c_void_p)]
 
@@ -686,13 +701,19 @@ def scene_span(records):
 
 
 def scene_clouds(live=False, what=0, step=1, win=0, search_x=0, search_y=0, min_disparity=0.0, max_depth=0.0,
-                 max_mean_cost=0.0, lr_check=0.0, point_size=1, extra=None, info=None):
+                 max_mean_cost=0.0, lr_check=0.0, point_size=1, extra=None, info=None, sgm=None):
     """a SceneClouds and what it points to, as (clouds, keep): keep the second alive until the job is delivered.
     live: draw the dense cloud of `what` (0: frames, 1: newest keyframes) of every named slot, searched with step, win,
     search_x, search_y (0: the ctx's), filtered by min_disparity, max_depth, max_mean_cost (0: off) and, with
     lr_check > 0, by the left-right check at that tolerance. extra: None, or per named slot what scene_span takes.
-    info: None, or a numpy array of SCENE_CLOUD_INFO_DTYPE, one per named slot."""
+    info: None, or a numpy array of SCENE_CLOUD_INFO_DTYPE, one per named slot. sgm: what sgm_job takes: the live layer
+    is the cloud of the SGM map (clouds.sgm holds the params, clouds.check the SGM map's own check, the lr_check key of
+    the sgm dict; lr_check beside sgm: ValueError)."""
+    lr_check = float(lr_check or 0.0)
+    sgm, sgm_check = sgm_consumer(sgm, lr_check, "dense")
     check = stereo_check(lr_check > 0, lr_check) if live else StereoCheck()
+    if sgm is not None and live:
+        check = sgm_check if sgm_check is not None else StereoCheck()
     spans = None
     if extra is not None:
         spans = (SceneSpan * max(len(extra), 1))(*[scene_span(e) for e in extra])
@@ -700,6 +721,7 @@ def scene_clouds(live=False, what=0, step=1, win=0, search_x=0, search_y=0, min_
                                                            min_disparity, max_depth, max_mean_cost),
                     check, int(point_size), (C.c_int32 * 3)(), C.cast(spans, C.c_void_p) if spans is not None else None,
                     info.ctypes.data if info is not None else None)
+    c.sgm = sgm
     return c, (spans, extra, info)
 
 
@@ -906,7 +928,10 @@ AR_VISIBILITY_DTYPE = np.dtype([("status", "<i4"), ("occluder_points", "<i4"), (
 
 
 class ArOcclusion(C.Structure):
-    """svo_ar_occlusion (include/svo_hip.h): how an ar job hides its meshes behind the slots' dense stereo depth."""
+    """svo_ar_occlusion (include/svo_hip.h): how an ar job hides its meshes behind the slots' dense stereo depth. sgm
+    (Python only): None, or the SgmParams the job goes through svo_submit_export_ar_occluded_sgm with; `check` is then
+    the SGM map's own."""
+    sgm = None
     _fields_ = [("on", C.c_int32), ("hidden", C.c_int32), ("alpha", C.c_int32), ("margin", C.c_float),
                 ("drop_flags", C.c_uint32), ("_reserved", C.c_int32 * 3), ("cloud", CloudStyle), ("check", StereoCheck),
                 ("info", C.c_void_p), ("_reserved2", C.c_int64)]
@@ -922,18 +947,26 @@ assert (C.sizeof(ArOcclusion), C.sizeof(ArOccluder), AR_VISIBILITY_DTYPE.itemsiz
 
 
 def ar_occlusion(on=True, step=4, hidden=AR_HIDDEN_DROP, alpha=128, margin=0.0, drop_flags=0, win=0, search_x=0, search_y=0,
-                 min_disparity=0.0, max_depth=0.0, max_mean_cost=0.0, lr_check=0.0, info=None):
+                 min_disparity=0.0, max_depth=0.0, max_mean_cost=0.0, lr_check=0.0, info=None, sgm=None):
     """an ArOcclusion. hidden may be a name (AR_HIDDEN); step, win, search_x, search_y, min_disparity, max_depth,
     max_mean_cost: the cloud that occludes (cloud_style; 0: the ctx's settings / off); lr_check > 0: the left-right
     check at that tolerance; info: None, or a numpy array of AR_VISIBILITY_DTYPE, one per named slot, that must stay
-    alive until the job is delivered."""
+    alive until the job is delivered. sgm: what sgm_job takes: the occluder is the cloud of the SGM map (the result's
+    sgm holds the params, its check the SGM map's own check, the lr_check key of the sgm dict; lr_check beside sgm:
+    ValueError)."""
     if isinstance(hidden, str):
         hidden = AR_HIDDEN.index(hidden)
     lr_check = float(lr_check or 0.0)
-    return ArOcclusion(int(bool(on)), int(hidden), int(alpha), float(margin), int(drop_flags), (C.c_int32 * 3)(),
-                       cloud_style(step, win, search_x, search_y, CLOUD_CAMERA, CLOUD_COMPACT, min_disparity, max_depth,
-                                   max_mean_cost),
-                       stereo_check(lr_check > 0, lr_check), info.ctypes.data if info is not None else None, 0)
+    sgm, sgm_check = sgm_consumer(sgm, lr_check, "occlusion")
+    check = stereo_check(lr_check > 0, lr_check)
+    if sgm is not None:
+        check = sgm_check if sgm_check is not None else StereoCheck()
+    o = ArOcclusion(int(bool(on)), int(hidden), int(alpha), float(margin), int(drop_flags), (C.c_int32 * 3)(),
+                    cloud_style(step, win, search_x, search_y, CLOUD_CAMERA, CLOUD_COMPACT, min_disparity, max_depth,
+                                max_mean_cost),
+                    check, info.ctypes.data if info is not None else None, 0)
+    o.sgm = sgm
+    return o
 
 
 def ar_occluder(records, cols=0, rows=0, step=1):
@@ -1010,6 +1043,14 @@ def lib():
         _LIB.svo_voxel_map_bytes.restype = C.c_int64
         for name in ("svo_submit_fuse_clouds", "svo_fuse_clouds"):
             getattr(_LIB, name).argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+        # (the SGM forms of the cloud's consumers; an older diagnostic build may lack them, as below)
+        p, i = C.c_void_p, C.c_int
+        for names, argtypes in ((("svo_submit_fuse_clouds_sgm", "svo_fuse_clouds_sgm"), [p, i, p, i, p, p, p, C.c_uint32, p]),
+                                (("svo_submit_export_scenes_clouds_sgm", "svo_export_scenes_clouds_sgm"), [p, p, i, p, p, p, p, p, i]),
+                                (("svo_submit_export_ar_occluded_sgm", "svo_export_ar_occluded_sgm"), [p, p, i, p, p, p, p, i, p, p, i, p, i])):
+            for name in names:
+                if hasattr(_LIB, name):
+                    getattr(_LIB, name).argtypes = argtypes
         for name in ("svo_submit_export_voxel_maps", "svo_export_voxel_maps"):     # (regions: a numpy array's address)
             getattr(_LIB, name).argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
         _LIB.svo_ctx_set_voxel_maps.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]

@@ -411,14 +411,24 @@ class Clouds(PointJob):
 class Fusion(Job):
     """One svo_submit_fuse_clouds: owns the info the library writes. After wait(): `info` (hip_lib.FUSE_INFO_DTYPE, one
     per named slot). Its submit() queues the same job again (the same slots, style and stamp). Nothing of the caller's
-    goes in or out on the device: it is a host-mode job, and its submit() never synchronises a stream."""
+    goes in or out on the device: it is a host-mode job, and its submit() never synchronises a stream. An SGM job (sgm:
+    a hip_lib.SgmParams; sgm_check: the cross-check of the SGM map, or None) goes through svo_submit_fuse_clouds_sgm;
+    sgm together with a top-level check that is on raises ValueError."""
 
-    def __init__(self, slam, what, seqs, style, check, stamp):
+    def __init__(self, slam, what, seqs, style, check, stamp, sgm=None, sgm_check=None):
         self._name(slam, seqs)
-        self.what, self.style, self.stamp, self.check = int(what), style, int(stamp), _check_that_is_on(check)
+        self.what, self.style, self.stamp, self.check, self.sgm = int(what), style, int(stamp), _check_that_is_on(check), sgm
+        if self.check is not None and sgm is not None:
+            raise ValueError(SGM_AND_LR_CHECK)
+        if sgm is not None:
+            self.check = _check_that_is_on(sgm_check)
         self._info, self.info = self._per_slot(hip_lib.FUSE_INFO_DTYPE)
 
     def _call(self, ctx, mem):
+        if self.sgm is not None:
+            return lib().svo_submit_fuse_clouds_sgm(ctx, self.what, self._seq_arr, self._n, C.byref(self.style), C.byref(self.sgm),
+                                                    None if self.check is None else C.byref(self.check), self.stamp,
+                                                    self._info.ctypes.data)
         return lib().svo_submit_fuse_clouds(ctx, self.what, self._seq_arr, self._n, C.byref(self.style),
                                             None if self.check is None else C.byref(self.check), self.stamp, self._info.ctypes.data)
 
@@ -487,11 +497,13 @@ class Scenes(PictureJob):
     (hip_lib.SCENE_SEGMENT_DTYPE, one per named slot), image(i) and `pixels` (PictureJob). cols, rows, pitch,
     image_bytes: the shape of every image of the job (svo_scene_size); channels: 3 or 4. With dense or clouds
     (StereoSlamBatch.submit_scenes) the job is svo_submit_export_scenes_clouds and `cloud_info`
-    (hip_lib.SCENE_CLOUD_INFO_DTYPE, one per named slot) says what was drawn; without them cloud_info is None."""
+    (hip_lib.SCENE_CLOUD_INFO_DTYPE, one per named slot) says what was drawn; without them cloud_info is None. With the
+    key sgm in dense (what hip_lib.sgm_job takes) the job is svo_submit_export_scenes_clouds_sgm: the live layer is the
+    cloud of the SGM map, `sgm` its params, and the lr_check key of the sgm dict its check."""
 
     OK = hip_lib.SCENE_OK
     DENSE_DEFAULTS = dict(live=True, what="frames", step=2, win=0, search_x=0, search_y=0, min_disparity=0.0, max_depth=0.0,
-                          max_mean_cost=0.0, lr_check=0.0, point_size=1)
+                          max_mean_cost=0.0, lr_check=0.0, point_size=1, sgm=None)
 
     def __init__(self, slam, seqs, style, cameras, device, dense=None, clouds=None):
         n = self._name(slam, seqs, device)
@@ -505,7 +517,7 @@ class Scenes(PictureJob):
             raise ValueError(f"{len(cameras)} cameras for {n} named slots: one per named slot, or a single one for all")
         self._cams = (hip_lib.SceneCamera * max(n, 1))(*cameras)
         self._pictures(hip_lib.SCENE_SEGMENT_DTYPE, hip_lib.SceneDst)
-        self.cloud_info = self._clouds = None
+        self.cloud_info = self._clouds = self.sgm = None
         if dense is not None or clouds is not None:
             d = dict(self.DENSE_DEFAULTS)
             unknown = set(dense or {}) - set(d)
@@ -521,8 +533,13 @@ class Scenes(PictureJob):
             live = dense is not None and bool(d.pop("live"))
             d.pop("live", None)
             self._clouds = hip_lib.scene_clouds(live=live, extra=clouds, info=self._info, **d)
+            self.sgm = self._clouds[0].sgm
 
     def _call(self, ctx, mem):
+        if self.sgm is not None:
+            return lib().svo_submit_export_scenes_clouds_sgm(ctx, self._seq_arr, self._n, C.byref(self.style),
+                                                             C.byref(self._clouds[0]), C.byref(self.sgm), self._cams,
+                                                             C.byref(self._dst), mem)
         if self._clouds is None:
             return lib().svo_submit_export_scenes(ctx, self._seq_arr, self._n, C.byref(self.style), self._cams,
                                                   C.byref(self._dst), mem)
@@ -538,11 +555,13 @@ class ArPictures(PictureJob):
     rgb) each; first: None (every slot shows every instance) or n + 1 ascending offsets into the instances.
     With occlusion (StereoSlamBatch.submit_ar) the job is svo_submit_export_ar_occluded and `visibility`
     (hip_lib.AR_VISIBILITY_DTYPE, one per named slot) says how much of the meshes is hidden; without it visibility
-    is None."""
+    is None. With the key sgm in occlusion (what hip_lib.sgm_job takes; or an ArOcclusion whose sgm is set) the job is
+    svo_submit_export_ar_occluded_sgm: the occluder is the cloud of the SGM map, `sgm` its params, and the lr_check key
+    of the sgm dict its check."""
 
     OK = hip_lib.AR_OK
     OCCLUSION_DEFAULTS = dict(step=4, hidden="drop", alpha=128, margin=0.0, drop_flags=0, win=0, search_x=0, search_y=0,
-                              min_disparity=0.0, max_depth=0.0, max_mean_cost=0.0, lr_check=0.0)
+                              min_disparity=0.0, max_depth=0.0, max_mean_cost=0.0, lr_check=0.0, sgm=None)
 
     def __init__(self, slam, seqs, style, meshes, instances, first, device, occlusion=None):
         n = self._name(slam, seqs, device)
@@ -567,10 +586,11 @@ class ArPictures(PictureJob):
         self._n_inst = len(inst)
         self._first = None if first is None else (C.c_int * (n + 1))(*[int(f) for f in first])
         self._pictures(hip_lib.AR_SEGMENT_DTYPE, hip_lib.ArDst)
-        self.visibility = self._occlusion = None
+        self.visibility = self._occlusion = self.sgm = None
         if occlusion is not None:
             if isinstance(occlusion, hip_lib.ArOcclusion):
                 self._occlusion = hip_lib.ArOcclusion.from_buffer_copy(occlusion)
+                self._occlusion.sgm = occlusion.sgm
             else:
                 d = dict(self.OCCLUSION_DEFAULTS)
                 unknown = set(occlusion) - set(d)
@@ -580,8 +600,14 @@ class ArPictures(PictureJob):
                 self._occlusion = hip_lib.ar_occlusion(True, **d)
             self._vis, self.visibility = self._per_slot(hip_lib.AR_VISIBILITY_DTYPE)
             self._occlusion.info = self._vis.ctypes.data
+            self.sgm = self._occlusion.sgm
 
     def _call(self, ctx, mem):
+        if self.sgm is not None:
+            return lib().svo_submit_export_ar_occluded_sgm(ctx, self._seq_arr, self._n, C.byref(self.style),
+                                                           C.byref(self._occlusion), C.byref(self.sgm), self._meshes,
+                                                           self._n_meshes, self._inst, self._first, self._n_inst,
+                                                           C.byref(self._dst), mem)
         if self._occlusion is None:
             return lib().svo_submit_export_ar(ctx, self._seq_arr, self._n, C.byref(self.style), self._meshes, self._n_meshes,
                                               self._inst, self._first, self._n_inst, C.byref(self._dst), mem)

@@ -33,6 +33,9 @@ cross-checked left-right and the file is [3, rows, cols]: the value (invalid whe
 D; D = 0 only reports), the cost and the lr plane; together with --disparity-sgm the check is the SGM map's own (a
 second SGM map of the mirrored pair) and the file stacks value, aggregated cost and lr. --cloud-lr D drops such points
 from the clouds of --dump-cloud; --cloud-sgm P1,P2[,CAP] makes those the clouds of the SGM map (and --cloud-lr its check).
+The consumers of the clouds have the same switch: --dense-map-sgm (the map of --dump-dense-map / --scene-fused, with
+--cloud-lr), --scene-dense-sgm (--scene-dense / --scene-accumulate, with --scene-dense-lr) and --ar-sgm (--ar-occlude,
+with --ar-lr); each takes P1,P2[,CAP] and needs a search_x <= 63.
 --dump-cloud DIR [--cloud-step S] [--cloud-max-depth Z] writes, whenever the newest keyframe changes,
 DIR/kf000000_cloud.ply: the dense coloured point cloud of that keyframe in the world frame at every S-th pixel (binary
 little-endian PLY, x y z float and red green blue uchar), so that the files of a run together are a dense map of it.
@@ -428,7 +431,8 @@ class Replay:
                  ar_box=AR_BOX, ar_at=hip_lib.AR_AT, dump_disparity=None, disparity_step=4, disparity_depth=False,
                  dump_cloud=None, cloud_step=4, cloud_max_depth=0.0, disparity_lr=None, cloud_lr=None, scene_dense=None,
                  scene_dense_lr=None, scene_dense_max_depth=0.0, scene_accumulate=0, dump_dense_map=None, dense_map_voxel=None,
-                 dense_map_log2=20, dense_map_min_count=0, dense_map_window=None, dense_map_keep=None, scene_fused=None, ar_occlusion=None, disparity_sgm=None, cloud_sgm=None):
+                 dense_map_log2=20, dense_map_min_count=0, dense_map_window=None, dense_map_keep=None, scene_fused=None, ar_occlusion=None, disparity_sgm=None, cloud_sgm=None,
+                 dense_map_sgm=None, scene_dense_sgm=None, ar_sgm=None):
         """fast=False keeps the library default: the reference-order Gauss-Newton (bit-exact traces).
         rectify_maps = (left maps, right maps): the frames fed are raw and are rectified on the GPU.
         calibration = (left, right) CameraCalibrations: the same, with the maps built on the GPU as well.
@@ -484,6 +488,19 @@ class Replay:
         self.cloud_sgm = None if cloud_sgm is None else sgm_dict(cloud_sgm, self.cloud_lr)
         self.scene_dense = None if scene_dense is None else int(scene_dense)
         self.scene_dense_lr = None if scene_dense_lr is None else float(scene_dense_lr)
+        # (the SGM forms of the cloud's consumers: the same flags' clouds from the SGM map, the flag's lr then being the SGM
+        # map's own check)
+        for flag, spec in (("dense_map_sgm", dense_map_sgm), ("scene_dense_sgm", scene_dense_sgm), ("ar_sgm", ar_sgm)):
+            if spec is not None and int(settings["search_x"]) > 63:
+                raise ValueError(f"--{flag.replace('_', '-')} needs a search_x <= 63 (the settings have {int(settings['search_x'])}): "
+                                 "the cost volume of the semi-global search holds at most 64 candidates")
+        self.dense_map_sgm = None if dense_map_sgm is None else sgm_dict(dense_map_sgm, self.cloud_lr)
+        self.scene_dense_sgm = None if scene_dense_sgm is None else sgm_dict(scene_dense_sgm, self.scene_dense_lr)
+        if ar_sgm is not None:
+            if self.ar_occlusion is None:
+                raise ValueError("--ar-sgm needs --ar-occlude")
+            lr = self.ar_occlusion.get("lr_check") or None
+            self.ar_occlusion = dict(self.ar_occlusion, lr_check=0.0, sgm=sgm_dict(ar_sgm, lr))
         self.scene_dense_max_depth, self.scene_accumulate = float(scene_dense_max_depth), int(scene_accumulate)
         self._scene_kf, self._scene_map = -1, None
         self.dump_dense_map, self.dense_map_log2, self.dense_map_min_count = dump_dense_map, int(dense_map_log2), int(dense_map_min_count)
@@ -610,8 +627,8 @@ class Replay:
         if not self._dense_map_set:
             self.slam.set_voxel_maps(self.dense_map_voxel, self.dense_map_log2)
             self._dense_map_set = True
-        return self.slam.fuse_new_keyframes(step=self.cloud_step, max_depth=self.cloud_max_depth, lr_check=self.cloud_lr,
-                                            prune=self.dense_map_prune) is not None
+        how = dict(lr_check=self.cloud_lr) if self.dense_map_sgm is None else dict(sgm=self.dense_map_sgm)
+        return self.slam.fuse_new_keyframes(step=self.cloud_step, max_depth=self.cloud_max_depth, prune=self.dense_map_prune, **how) is not None
 
     def finish(self):
         """what is written once, after the last frame: the dense map of dump_dense_map"""
@@ -623,14 +640,17 @@ class Replay:
         """the dense and clouds arguments of dump_scene's get_scene ({}: the sparse picture)"""
         kw = {}
         step = self.scene_dense if self.scene_dense is not None else 4
+        sgm = self.scene_dense_sgm
         if self.scene_dense is not None:
-            kw["dense"] = dict(what="frames", step=step, max_depth=self.scene_dense_max_depth, lr_check=self.scene_dense_lr or 0.0)
+            kw["dense"] = dict(what="frames", step=step, max_depth=self.scene_dense_max_depth,
+                               **(dict(lr_check=self.scene_dense_lr or 0.0) if sgm is None else dict(sgm=sgm)))
         if self.scene_accumulate > 0:
             kf = int(self.slam.stats().n_keyframes) - 1
             if kf != self._scene_kf:
                 self._scene_kf = kf
                 job = self.slam.export_cloud("last_keyframes", None, step=step, layout="compact", device=True,
-                                             max_depth=self.scene_dense_max_depth, lr_check=self.scene_dense_lr)
+                                             max_depth=self.scene_dense_max_depth,
+                                             **(dict(lr_check=self.scene_dense_lr) if sgm is None else dict(sgm=sgm)))
                 if int(job.segments[0]["status"]) == hip_lib.CLOUD_OK:
                     new = job.points_buffer[:int(job.segments[0]["n_points"])]
                     both = new if self._scene_map is None else torch.cat([self._scene_map, new])
@@ -702,6 +722,9 @@ def build_parser():
                     help="--scene-dense / --scene-accumulate drop points whose left-right cross-check differs by more than D (> 0)")
     ap.add_argument("--scene-dense-max-depth", metavar="Z", type=float, default=0.0,
                     help="--scene-dense / --scene-accumulate drop points deeper than Z in the camera frame (0: none)")
+    ap.add_argument("--scene-dense-sgm", metavar="P1,P2[,CAP]", default=None,
+                    help="--scene-dense / --scene-accumulate draw the clouds of the semi-globally aggregated map with these "
+                         "penalties (and cost cap); --scene-dense-lr D is then the SGM map's own cross-check; needs a search_x <= 63")
     ap.add_argument("--scene-accumulate", metavar="N", type=int, default=0,
                     help="--dump-scene also draws the dense clouds of the keyframes so far, kept on the device in one array of "
                          "at most N records (oldest dropped first): the dense map growing")
@@ -719,6 +742,9 @@ def build_parser():
                     help="--ar-occlude hides what lies more than M behind the scene's depth (the unit of the baseline)")
     ap.add_argument("--ar-lr", metavar="D", type=float, default=None,
                     help="--ar-occlude trusts only depths that pass the left-right check at tolerance D pixels")
+    ap.add_argument("--ar-sgm", metavar="P1,P2[,CAP]", default=None,
+                    help="--ar-occlude hides the box behind the depth of the semi-globally aggregated map with these penalties "
+                         "(and cost cap); --ar-lr D is then the SGM map's own cross-check; needs a search_x <= 63")
     ap.add_argument("--ar-at", metavar="X,Y,Z", default=",".join(str(x) for x in hip_lib.AR_AT),
                     help="world point of the box's centre (default: half a metre in front of the first camera, as the demo)")
     ap.add_argument("--dump-disparity", metavar="DIR",
@@ -747,6 +773,9 @@ def build_parser():
     ap.add_argument("--dump-dense-map", metavar="FILE.ply",
                     help="fuse every new keyframe's dense cloud (--cloud-step, --cloud-lr, --cloud-max-depth) into a voxel map "
                          "kept inside the ctx and write it as one binary PLY at the end; needs --dense-map-voxel")
+    ap.add_argument("--dense-map-sgm", metavar="P1,P2[,CAP]", default=None,
+                    help="--dump-dense-map / --scene-fused fuse the clouds of the semi-globally aggregated map with these penalties "
+                         "(and cost cap): sub-pixel depth; --cloud-lr D is then the SGM map's own cross-check; needs a search_x <= 63")
     ap.add_argument("--dense-map-voxel", metavar="V", type=float, default=None, help="voxel edge of --dump-dense-map, metres (> 0)")
     ap.add_argument("--dense-map-log2", metavar="N", type=int, default=20, help="the map holds 1 << N entries (10 .. 26)")
     ap.add_argument("--dense-map-min-count", metavar="K", type=int, default=0,
@@ -793,6 +822,12 @@ def check_dense_map_args(ap, args):
         ap.error("--dense-map-window must be finite and >= 0")
     if args.dense_map_keep is not None and args.dense_map_keep < 1:
         ap.error("--dense-map-keep must be >= 1")
+    if args.dense_map_sgm is not None and not (args.dump_dense_map or args.scene_fused is not None):
+        ap.error("--dense-map-sgm needs --dump-dense-map or --scene-fused")
+    if args.scene_dense_sgm is not None and args.scene_dense is None and args.scene_accumulate <= 0:
+        ap.error("--scene-dense-sgm needs --scene-dense or --scene-accumulate")
+    if args.ar_sgm is not None and args.ar_occlude is None:
+        ap.error("--ar-sgm needs --ar-occlude")
 
 
 def main(argv=None):
@@ -855,6 +890,10 @@ def main(argv=None):
         if args.ar_lr is not None and not 0 < args.ar_lr < float("inf"):
             ap.error("--ar-lr must be a finite tolerance > 0")
         occlusion = dict(step=args.ar_occlude, hidden=args.ar_hidden, alpha=args.ar_alpha, margin=args.ar_margin, lr_check=args.ar_lr or 0.0)
+    split = lambda spec: None if spec is None else spec.split(",")
+    for flag, spec in (("--dense-map-sgm", args.dense_map_sgm), ("--scene-dense-sgm", args.scene_dense_sgm), ("--ar-sgm", args.ar_sgm)):
+        if spec is not None and int(settings["search_x"]) > 63:
+            ap.error(f"{flag} needs a search_x <= 63 (the settings have {int(settings['search_x'])})")
     rp = Replay(settings, args.device, args.time_trace, args.fast, rectify_maps=rect, input_format=fmt, gpu_imu=args.gpu_imu,
                 dump_views=args.dump_views, dump_scene=args.dump_scene, calibration=cal, dump_ar=args.dump_ar,
                 ar_box=args.ar_box, ar_at=tuple(float(x) for x in args.ar_at.split(",")),
@@ -867,7 +906,8 @@ def main(argv=None):
                 scene_accumulate=args.scene_accumulate, dump_dense_map=args.dump_dense_map, dense_map_voxel=args.dense_map_voxel,
                 dense_map_log2=args.dense_map_log2, dense_map_min_count=args.dense_map_min_count, dense_map_window=args.dense_map_window,
                 dense_map_keep=args.dense_map_keep, scene_fused=args.scene_fused,
-                ar_occlusion=occlusion)
+                ar_occlusion=occlusion, dense_map_sgm=split(args.dense_map_sgm), scene_dense_sgm=split(args.scene_dense_sgm),
+                ar_sgm=split(args.ar_sgm))
     for k, (left, right, t) in enumerate(frames):
         rp.feed(left, right, t, None if gyro is None else gyro[gyro[:, 0] == k, 1:4])
     rp.finish()

@@ -430,8 +430,9 @@ class StereoSlamBatch:
         nothing is waited for. camera: a preset name ("front", "top", "side"), one hip_lib.SceneCamera for all, or a
         list with one per named slot; style: a hip_lib.SceneStyle, or its fields as keywords (hip_lib.scene_style:
         cols, rows, pixel, point_size, colours, show, from_keyframe, trajectory_tail, filter). dense: None, or a dict
-        (any of what, step, win, search_x, search_y, min_disparity, max_depth, max_mean_cost, lr_check, point_size;
-        live=False: only point_size counts, for `clouds`) that draws the dense cloud of every named slot's frame (what="frames") or newest keyframe ("last_keyframes")
+        (any of what, step, win, search_x, search_y, min_disparity, max_depth, max_mean_cost, lr_check, point_size, sgm;
+        live=False: only point_size counts, for `clouds`; sgm: as submit_cloud's: the live layer is the cloud of the SGM
+        map, its check the lr_check key of the sgm dict, and lr_check beside sgm is a ValueError) that draws the dense cloud of every named slot's frame (what="frames") or newest keyframe ("last_keyframes")
         into its picture, the cloud submit_cloud(layout="organized") with these values would deliver; clouds: None,
         or per named slot a device tensor of hip_lib.MAP_POINT_DTYPE bytes, (address, n) or None: records of the
         caller's drawn as well (they stay alive and unchanged until the job is delivered). Returns a Scenes, valid
@@ -452,9 +453,11 @@ class StereoSlamBatch:
         slots (None: all), ordered with the frame sets; nothing is waited for. meshes, instances, first: see
         ArPictures; style: a hip_lib.ArStyle, or its fields as keywords (hip_lib.ar_style: pixel, light, ambient,
         near). occlusion: None, a hip_lib.ArOcclusion, or a dict (step, hidden = "drop" | "dim", alpha, margin,
-        drop_flags, win, search_x, search_y, min_disparity, max_depth, max_mean_cost, lr_check): the job is
+        drop_flags, win, search_x, search_y, min_disparity, max_depth, max_mean_cost, lr_check, sgm): the job is
         svo_submit_export_ar_occluded, the meshes are hidden behind the dense, checked stereo depth of the frame and
-        ArPictures.visibility counts the covered and hidden pixels. Returns an ArPictures, valid after wait()."""
+        ArPictures.visibility counts the covered and hidden pixels. sgm in the dict (as submit_cloud's): the depth is
+        the SGM map's (svo_submit_export_ar_occluded_sgm), its check the lr_check key of the sgm dict, and lr_check
+        beside sgm is a ValueError. Returns an ArPictures, valid after wait()."""
         if style is None:
             style = hip_lib.ar_style(**kw)
         return ArPictures(self, seqs, style, meshes, instances, first, device, occlusion).submit()
@@ -680,19 +683,22 @@ class StereoSlamBatch:
         return {n: getattr(info, n) for n, _ in hip_lib.VoxelMapInfo._fields_ if n != "_pad"}
 
     def submit_fuse(self, what="last_keyframes", seqs=None, stamp=None, lr_check=None, step=4, win=0, search_x=0, search_y=0,
-                    min_disparity=0.0, max_depth=0.0, max_mean_cost=0.0):
+                    min_disparity=0.0, max_depth=0.0, max_mean_cost=0.0, sgm=None):
         """svo_submit_fuse_clouds: queue the fusion of the dense world-frame cloud of the newest keyframes (or,
         what="frames", the current frames) of the slots `seqs` (None: all) into their voxel maps, behind what was
         submitted so far; nothing is waited for. The cloud is submit_cloud's (step, win, search_x, search_y, the
-        filter, lr_check); stamp: a u32 the reached voxels are raised to (None: a counter of this object, one more
-        per job). Returns a Fusion, valid after its wait() (or the ctx's)."""
+        filter, lr_check, sgm: with sgm the job is svo_submit_fuse_clouds_sgm and fuses the cloud of the SGM map, whose
+        check is the lr_check key of the sgm dict; the top-level lr_check together with sgm: ValueError); stamp: a u32
+        the reached voxels are raised to (None: a counter of this object, one more per job). Returns a Fusion, valid
+        after its wait() (or the ctx's)."""
         if isinstance(what, str):
             what = hip_lib.EXPORT_WHAT.index(what)
+        sgm = hip_lib.sgm_consumer(sgm, lr_check, "submit_fuse")
         if stamp is None:
             self._fuse_stamp += 1
             stamp = self._fuse_stamp
         style = hip_lib.cloud_style(step, win, search_x, search_y, "world", "compact", min_disparity, max_depth, max_mean_cost)
-        return Fusion(self, what, seqs, style, self._stereo_check(lr_check), stamp).submit()
+        return Fusion(self, what, seqs, style, self._stereo_check(lr_check), stamp, *sgm).submit()
 
     def fuse_clouds(self, what="last_keyframes", seqs=None, **kw):
         """submit_fuse + wait"""

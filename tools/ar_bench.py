@@ -31,6 +31,11 @@ and meshes, and writes profiles/ar_occlusion_bench.json unless --out names anoth
              rasteriser for the meshes' depths, the composition; seconds per slot beside the job's.
   pipelined  frames/s with nothing, with a plain picture and with an occluded picture of every slot behind every 10th
              frame set.
+
+--occluded STEPS --sgm P1,P2[,CAP] measures only the occluded job (sets the key "ar" of
+profiles/sgm_consumers_bench.json): at every step the job through svo_submit_export_ar_occluded and through
+svo_submit_export_ar_occluded_sgm, unchecked and checked at tolerance `--lr`; the legs alternate in one process, median of
+`--repeats` each.
 """
 import argparse
 import json
@@ -42,7 +47,7 @@ import time
 os.environ.setdefault("GPU_MAX_HW_QUEUES", "20")         # (bench.py's setting: 14 groups of 256)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (ROOT, os.path.join(ROOT, "stereo-svo-slam_amd"), os.path.join(ROOT, "oracle")):
+for p in (ROOT, os.path.join(ROOT, "stereo-svo-slam_amd"), os.path.join(ROOT, "oracle"), os.path.join(ROOT, "tools")):
     if p not in sys.path:
         sys.path.insert(0, p)
 
@@ -50,6 +55,7 @@ import numpy as np
 import torch
 
 import bench
+import job_ab
 from stereo_svo_slam_amd import hip_lib
 from stereo_svo_slam_amd.stereo_slam import ArPictures, StereoSlamBatch
 
@@ -376,8 +382,38 @@ def occluded_leg(args, device, cfg, lefts, rights, meshes, step):
     return out
 
 
+def sgm_leg(args, device, cfg, lefts, rights, meshes, steps):
+    slots = args.slots
+    n = min(slots, len(lefts))
+    slam, packed = start(cfg, lefts[:n], rights[:n], slots, 1, device, args.warmup)
+    for pk in packed:
+        slam.submit_packed(pk)
+    slam.wait()
+    inst, first = placed(slam, slots)
+    style = hip_lib.ar_style(pixel="rgba8")
+    out = {"slots": slots, "margin": args.margin, "max_depth": args.max_depth, "lr": args.lr, "sgm": args.sgm, "steps": {}}
+    for step in steps:
+        jobs = {}
+        for name, how in (("wta", dict()), ("wta_checked", dict(lr_check=args.lr)), ("sgm", dict(sgm=job_ab.sgm_dict(args.sgm, None))),
+                          ("sgm_checked", dict(sgm=job_ab.sgm_dict(args.sgm, args.lr)))):
+            occ = dict(step=step, margin=args.margin, max_depth=args.max_depth, **how)
+            jobs[name] = ArPictures(slam, None, style, meshes, inst, first, True, occ).submit().wait()
+        timed = job_ab.alternate_jobs(device, jobs, args.repeats)
+        out["steps"][str(step)] = {"hidden": {k: int(j.visibility["hidden"].sum()) for k, j in jobs.items()},
+                                   "covered": int(jobs["wta"].visibility["covered"].sum()),
+                                   "occluder_points": {k: int(j.visibility["occluder_points"].sum()) for k, j in jobs.items()}, "jobs": timed,
+                                   "ratios": job_ab.ratios(timed, [("sgm", "wta"), ("sgm_checked", "wta_checked")])}
+        print(json.dumps({str(step): out["steps"][str(step)]}), file=sys.stderr, flush=True)
+        del jobs
+    out["device_GB"] = slam.memory().device_bytes / 1e9
+    slam.close()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--sgm", metavar="P1,P2[,CAP]", default=None,
+                    help="--occluded: only the occluded job under SGM against winner-takes-all (profiles/sgm_consumers_bench.json)")
     ap.add_argument("--slots", type=int, default=256)
     ap.add_argument("--sphere", type=int, default=32, help="bands of the sphere: 4 * bands * (bands - 1) triangles")
     ap.add_argument("--kernel-only", action="store_true", help="one job and one stage-entry call, nothing timed: for a kernel trace")
@@ -401,6 +437,15 @@ def main():
     n_loops = min(max([s for s, _ in legs] + [args.slots]), args.loops)
     cfg, lefts, rights = bench.render_loops("euroc", list(range(n_loops)), args.loop_frames, device)
     meshes = [hip_lib.ar_box(0.3), sphere(0.15, args.sphere)]
+    if args.sgm and not args.occluded:
+        ap.error("--sgm needs --occluded STEPS")
+    if args.occluded and args.sgm:
+        n_loops = min(args.slots, args.loops)
+        leg = dict(sgm_leg(args, device, cfg, lefts[:n_loops], rights[:n_loops], meshes, [int(x) for x in args.occluded.split(",")]),
+                   tool="tools/ar_bench.py", command=" ".join(sys.argv), device=torch.cuda.get_device_name(0))
+        job_ab.merge_result(args.out or os.path.join(ROOT, "profiles", "sgm_consumers_bench.json"), "ar", leg)
+        print(json.dumps(leg), flush=True)
+        return
     if args.occluded:
         n_loops = min(args.slots, args.loops)
         out = {"metric": "ar_occlusion_bench", "config": "euroc", "hw_queues": int(os.environ["GPU_MAX_HW_QUEUES"]), "steps": []}

@@ -31,6 +31,11 @@ drawn into 640 x 480 RGBA pictures from behind each slot's pose.
              pixel, distinct depths.
   job        the device-mode scene job without and with the live layer (submit + wait, host clock), and the cloud job
              that the layer runs first.
+
+--clouds STEPS --sgm P1,P2[,CAP] measures only the job with the live layer (sets the key "scene" of
+profiles/sgm_consumers_bench.json): at every step the scene job through svo_submit_export_scenes_clouds and through
+svo_submit_export_scenes_clouds_sgm, unchecked and checked at tolerance `--lr`; the legs alternate in one process, median
+of `--repeats` each.
 """
 import argparse
 import json
@@ -42,7 +47,7 @@ import time
 os.environ.setdefault("GPU_MAX_HW_QUEUES", "20")         # (bench.py's setting: 14 groups of 256)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (ROOT, os.path.join(ROOT, "stereo-svo-slam_amd")):
+for p in (ROOT, os.path.join(ROOT, "stereo-svo-slam_amd"), os.path.join(ROOT, "tools")):
     if p not in sys.path:
         sys.path.insert(0, p)
 
@@ -50,6 +55,7 @@ import numpy as np
 import torch
 
 import bench
+import job_ab
 from stereo_svo_slam_amd import hip_lib
 from stereo_svo_slam_amd.stereo_slam import StereoSlamBatch
 
@@ -336,8 +342,37 @@ def clouds_leg(args, device, cfg, lefts, rights, steps):
     return out
 
 
+def sgm_leg(args, device, cfg, lefts, rights, steps):
+    slots, (cols, rows) = args.cloud_slots, CLOUD_SIZE
+    n = min(slots, len(lefts))
+    slam, packed = start(cfg, lefts[:n], rights[:n], slots, 1, device, args.warmup)
+    for pk in packed:
+        slam.submit_packed(pk)
+    slam.wait()
+    cams = [behind(slam.pose(s), cols, rows) for s in range(slots)]
+    style = hip_lib.scene_style(cols=cols, rows=rows, pixel="rgba8")
+    out = {"slots": slots, "picture": [cols, rows], "point_size": args.cloud_point_size, "lr": args.lr, "sgm": args.sgm, "steps": {}}
+    for step in steps:
+        jobs = {}
+        for name, how in (("wta", dict()), ("wta_checked", dict(lr_check=args.lr)), ("sgm", dict(sgm=job_ab.sgm_dict(args.sgm, None))),
+                          ("sgm_checked", dict(sgm=job_ab.sgm_dict(args.sgm, args.lr)))):
+            jobs[name] = slam.submit_scenes(camera=cams, device=True, style=style,
+                                            dense=dict(what="frames", step=step, point_size=args.cloud_point_size, **how)).wait()
+        timed = job_ab.alternate_jobs(device, jobs, args.repeats)
+        out["steps"][str(step)] = {"live_points": {k: int(j.cloud_info["live_points"].sum()) for k, j in jobs.items()}, "jobs": timed,
+                                   "ratios": job_ab.ratios(timed, [("sgm", "wta"), ("sgm_checked", "wta_checked")])}
+        print(json.dumps({str(step): out["steps"][str(step)]}), file=sys.stderr, flush=True)
+        del jobs
+    out["device_GB"] = slam.memory().device_bytes / 1e9
+    slam.close()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--sgm", metavar="P1,P2[,CAP]", default=None,
+                    help="--clouds: only the job with the live layer under SGM against winner-takes-all (profiles/sgm_consumers_bench.json)")
+    ap.add_argument("--lr", type=float, default=1.0, help="--sgm: the tolerance of the checked legs")
     ap.add_argument("--clouds", default=None, metavar="STEPS", help="measure the cloud points at these lattice steps (e.g. 1,2,4) and nothing else")
     ap.add_argument("--cloud-slots", type=int, default=16)
     ap.add_argument("--cloud-point-size", type=int, default=2)
@@ -358,6 +393,14 @@ def main():
     if args.clouds:
         n_loops = min(args.cloud_slots, args.loops)
     cfg, lefts, rights = bench.render_loops("euroc", list(range(n_loops)), args.loop_frames, device)
+    if args.sgm and not args.clouds:
+        ap.error("--sgm needs --clouds STEPS")
+    if args.clouds and args.sgm:
+        leg = dict(sgm_leg(args, device, cfg, lefts, rights, [int(x) for x in args.clouds.split(",")]), tool="tools/scene_bench.py",
+                   command=" ".join(sys.argv), device=torch.cuda.get_device_name(0))
+        job_ab.merge_result(args.out or os.path.join(ROOT, "profiles", "sgm_consumers_bench.json"), "scene", leg)
+        print(json.dumps(leg), flush=True)
+        return
     if args.clouds:
         out = {"metric": "scene_cloud_bench", "config": "euroc", "hw_queues": int(os.environ["GPU_MAX_HW_QUEUES"]),
                "clouds": clouds_leg(args, device, cfg, lefts, rights, [int(x) for x in args.clouds.split(",")])}

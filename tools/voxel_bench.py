@@ -15,6 +15,10 @@
              slot's newest keyframe queued behind every frame set; legs alternate, median of `--repeats` each.
 Prints one JSON line.
 
+  --sgm P1,P2[,CAP]  instead of all that (sets the key "fuse" of profiles/sgm_consumers_bench.json): the fuse
+             job of `--slots` slots' newest keyframes at lattice step `--step` through svo_submit_fuse_clouds and through
+             svo_submit_fuse_clouds_sgm, unchecked and checked at tolerance `--lr`, beside the cloud jobs alone; the legs
+             alternate in one process, median of `--repeats` each.
   --prune    instead of all that (writes profiles/voxel_prune_bench.json): svo_voxel_prune of a map of
              1 << 16, 20 and 24 entries at 0.25, 0.5 and 0.75 load (distinct voxels, half of them fused with stamp 1 and
              half with stamp 2), keeping all (min_stamp 1: the early out) and keeping the newer half (min_stamp 2; the
@@ -34,7 +38,7 @@ import time
 os.environ.setdefault("GPU_MAX_HW_QUEUES", "20")         # (bench.py's setting)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (ROOT, os.path.join(ROOT, "stereo-svo-slam_amd"), os.path.join(ROOT, "tests")):
+for p in (ROOT, os.path.join(ROOT, "stereo-svo-slam_amd"), os.path.join(ROOT, "tests"), os.path.join(ROOT, "tools")):
     if p not in sys.path:
         sys.path.insert(0, p)
 
@@ -42,6 +46,7 @@ import numpy as np
 import torch
 
 import bench
+import job_ab
 import voxel_ref as VR
 from stereo_svo_slam_amd import hip_lib
 from stereo_svo_slam_amd.stereo_slam import StereoSlamBatch
@@ -162,6 +167,29 @@ def pipelined_leg(args, device, cfg, lefts, rights):
     return out
 
 
+def sgm_leg(args, device, cfg, lefts, rights):
+    slam, packed = start(cfg, lefts, rights, args.slots, 1, device, args.warmup)
+    slam.set_voxel_maps(args.voxel, args.pipe_log2)
+    for pk in packed:
+        slam.submit_packed(pk)
+    slam.wait()
+    jobs = {}
+    for name, how in (("wta", dict()), ("wta_checked", dict(lr_check=args.lr)), ("sgm", dict(sgm=job_ab.sgm_dict(args.sgm, None))),
+                      ("sgm_checked", dict(sgm=job_ab.sgm_dict(args.sgm, args.lr)))):
+        jobs[f"fuse_{name}"] = slam.submit_fuse("last_keyframes", None, stamp=1, step=args.step, **how).wait()
+        jobs[f"cloud_{name}"] = slam.submit_cloud("last_keyframes", None, step=args.step, layout="organized", device=True, **how).wait()
+    offered = {name: int(job.info["n_offered"].sum()) for name, job in jobs.items() if name.startswith("fuse")}
+    statuses = {name: np.bincount(job.info["status"], minlength=4).tolist() for name, job in jobs.items() if name.startswith("fuse")}
+    timed = job_ab.alternate_jobs(device, jobs, args.repeats)
+    out = {"slots": args.slots, "step": args.step, "lr": args.lr, "sgm": args.sgm, "voxel": args.voxel, "log2_capacity": args.pipe_log2,
+           "points_per_slot": jobs["cloud_wta"].points_per_slot, "offered": offered, "fuse_statuses": statuses, "jobs": timed,
+           "ratios": job_ab.ratios(timed, [("fuse_sgm", "fuse_wta"), ("fuse_sgm_checked", "fuse_wta_checked"),
+                                           ("cloud_sgm", "cloud_wta"), ("cloud_sgm_checked", "cloud_wta_checked")]),
+           "device_GB": slam.memory().device_bytes / 1e9}
+    slam.close()
+    return out
+
+
 def prune_leg(args, h):
     out = []
     for log2 in args.prune_log2:
@@ -217,6 +245,8 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--prune", action="store_true", help="only the prune measurement (profiles/voxel_prune_bench.json)")
     ap.add_argument("--prune-log2", type=int, nargs="+", default=[16, 20, 24])
+    ap.add_argument("--sgm", metavar="P1,P2[,CAP]", default=None, help="only the fuse job under SGM against winner-takes-all (profiles/sgm_consumers_bench.json)")
+    ap.add_argument("--lr", type=float, default=1.0, help="--sgm: the tolerance of the checked legs")
     ap.add_argument("--slots", type=int, default=256)
     ap.add_argument("--step", type=int, default=4)
     ap.add_argument("--voxel", type=float, default=0.05)
@@ -239,6 +269,11 @@ def main():
         print(json.dumps(out))
         return
     cfg, lefts, rights = bench.render_loops("euroc", list(range(min(8, args.slots))), args.loop_frames, device)
+    if args.sgm:
+        leg = dict(sgm_leg(args, device, cfg, lefts, rights), tool="tools/voxel_bench.py", command=" ".join(sys.argv), device=torch.cuda.get_device_name(0))
+        job_ab.merge_result(args.out or os.path.join(ROOT, "profiles", "sgm_consumers_bench.json"), "fuse", leg)
+        print(json.dumps(leg))
+        return
     slam, packed = start(cfg, lefts, rights, args.slots, 1, device, args.warmup)
     for k in range(args.warmup):
         slam.submit_packed(packed[k])
