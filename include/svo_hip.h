@@ -2080,6 +2080,114 @@ int svo_export_ar_occluded_sgm(svo_ctx *ctx, const int *seqs, int n, const svo_a
                                const svo_ar_mesh *meshes, int n_meshes, const svo_ar_instance *instances,
                                const int *first, int n_instances, const svo_ar_dst *dst, int mem);   /* submit + wait */
 
+/* ---- voxel carve: entries of a voxel map removed where the current frame's dense depth sees through them ------------
+ * A voxel map averages whatever it is given for the whole run, and "voxel prune" forgets entries by count, stamp and a
+ * box. Neither removes an entry that the camera now sees to be wrong: a wrong disparity that survived its check and
+ * claimed a voxel in front of the wall, or the ghost of an object that has moved. A carve removes the entries that lie
+ * in FRONT of what the camera measures along their ray: the occluder of "ar occlusion" (the organized, camera-frame cloud
+ * of the very frame the camera shows) read the other way round.
+ *
+ * Inputs: a map (svo_voxel_map), a camera (svo_ar_camera), the image size W x H, an occluder (svo_ar_occluder: records,
+ * cols, rows, step) and a svo_voxel_carve_rule. Per non-empty entry; all arithmetic float32, each operation rounded once,
+ * without contraction, but for step 1:
+ *   1 point     w = the point the entry extracts to by the formula of "voxel maps": per coordinate computed in double and
+ *               rounded once to float. An entry with last > max_last is no candidate: it is kept.
+ *   2 camera    c_k = ((V[4k] * w_0 + V[4k+1] * w_1) + V[4k+2] * w_2) + V[4k+3], the c_k of "ar". Any c_k not finite, or
+ *               c_2 < near: the entry is kept.
+ *   3 pixel     u = (fx * c_0) / c_2 + cx, v = (fy * c_1) / c_2 + cy. The entry is kept unless
+ *               u >= 0.0f && u < (float)W && v >= 0.0f && v < (float)H (a NaN keeps it). px = (int)u, py = (int)v; the
+ *               cell is ix = px / step, iy = py / step.
+ *   4 evidence  a cell HAS AN OCCLUDER DEPTH zo by the rule of "ar occlusion", with this struct's drop_flags. ring = 0:
+ *               the evidence is the cell's zo. ring = 1: zmin = the minimum of zo over the cells (ix + dx, iy + dy), dx,
+ *               dy in {-1, 0, 1}, that lie inside the lattice. If the cell itself lies outside the lattice (ix >= cols
+ *               or iy >= rows), or any cell consulted has no occluder depth, or records == NULL, the evidence is
+ *               incomplete: the entry is kept. The ring keeps the rim of a foreground object from being carved by a
+ *               background cell beside it when step > 1.
+ *   5 verdict   the entry is CARVED iff c_2 + margin < zmin: one add, one comparison. The camera measured a surface more
+ *               than margin behind the entry.
+ * One contradiction removes an entry (no votes: that would need a ninth accumulator); ring, margin and max_last are
+ * the guards.
+ *
+ * With an optional svo_voxel_keep an entry STAYS iff the keep rule of "voxel prune" keeps it and it is not carved
+ * (keep == NULL: every entry is kept by the keep rule). The map is rebuilt exactly as a prune rebuilds it: the same
+ * placement guarantees, the eight accumulators unchanged, n_voxels = the entries that stay, the three cumulative
+ * counters untouched, and a call that removes nothing writes no byte of the map.
+ *
+ * Result, exact integers summed on the device (one 64-bit atomic add per count and workgroup after a reduction inside
+ * it, so arrival order cannot matter): n_before, n_kept = the map's n_voxels before and after; n_tested = the entries
+ * that reached step 5; n_carved = those step 5 carves, whether or not the keep rule rejects them too.
+ *
+ * How it runs (voxel.hip): the prune's six launches with its count and stage kernels instantiated on the joined rule.
+ * The carve is evaluated once, in the count pass, which leaves one 64-bit ballot word per wavefront in the workspace;
+ * the stage pass reads the words. */
+typedef struct svo_voxel_carve_rule {    /* 32 bytes */
+    float    margin;                /* finite, >= 0, in the unit of the depths                              */
+    float    near;                  /* finite, > 0                                                          */
+    uint32_t max_last;              /* an entry with last > max_last is kept                                */
+    uint32_t drop_flags;            /* occluder records with any of these flag bits give no depth           */
+    int32_t  ring;                  /* 0: the entry's cell; 1: the cell and its neighbours                  */
+    int32_t  _reserved[3];          /* 0                                                                    */
+} svo_voxel_carve_rule;
+
+typedef struct svo_voxel_carve_result { /* 32 bytes */
+    int64_t n_before;               /* the map's n_voxels before the call                                   */
+    int64_t n_kept;                 /* and after it                                                         */
+    int64_t n_tested;               /* entries that reached step 5                                          */
+    int64_t n_carved;               /* entries that step 5 carves                                           */
+} svo_voxel_carve_result;
+
+/* Stage entry, complete on return; keep and result may be NULL. The workspace is svo_voxel_prune's (the tile offsets and
+ * the staging block, with its 1 GiB bound and SVO_ERR_CAPACITY), followed by the ballot words (8 bytes per 64 entries)
+ * and the counters. SVO_ERR_INVALID with nothing written: what svo_voxel_prune rejects of the map and of a non-NULL
+ * keep; what svo_render_ar_occluded rejects of a camera and an occluder (a NULL pointer to either too); a NULL carve, a
+ * margin that is negative or not finite, a near that is not finite or <= 0, a ring that is neither 0 nor 1, a non-zero
+ * _reserved; width or height outside 1 .. 32768. An occluder with records == NULL gives no evidence anywhere: the call
+ * is a plain prune by keep and n_tested = n_carved = 0. */
+int svo_voxel_carve(svo_handle *h, const svo_voxel_map *map, const svo_ar_camera *camera, int width, int height,
+                    const svo_ar_occluder *occluder, const svo_voxel_carve_rule *carve, const svo_voxel_keep *keep,
+                    svo_voxel_carve_result *result);
+
+/* svo_submit_carve_voxel_maps carves the maps of the named slots inside a ctx with the frame each slot holds at that
+ * queue position. It is queued like a prune job and is no new kind of queue entry: it is the prune entry carrying a
+ * carve, as the SGM jobs carry their params. keep (NULL: every entry is kept by the keep rule), center_mode and centers
+ * are the prune job's. Per named slot:
+ *   occluder   exactly the records that svo_submit_export_ar_occluded would use at that queue position with `cloud` and
+ *              `check`, or svo_submit_export_ar_occluded_sgm with `sgm`: the current frame, frame = SVO_CLOUD_CAMERA,
+ *              organized, cols = W / step, rows = H / step, computed by the cloud job's own launches into the occluded AR
+ *              job's block of the group; they never leave the device
+ *   camera     svo_ar_camera_of_pose of the slot's current pose and rig (its deferred pose-filter update is flushed
+ *              first, as for the AR job); the image size is the ctx's W x H
+ * info[i] belongs to seqs[i], is host memory and is valid at svo_wait:
+ *   SVO_CARVE_OK         carved: the four counts of svo_voxel_carve_result, and the pose the camera was made of
+ *   SVO_CARVE_NO_MAP     the slot has no map (this comes first)
+ *   SVO_CARVE_NONE       an empty slot (no frame yet, as SVO_CLOUD_NONE): nothing changes
+ *   SVO_CARVE_NO_POSE, SVO_CARVE_TOO_LARGE   as SVO_PRUNE_NO_POSE and SVO_PRUNE_TOO_LARGE: nothing changes
+ * The ctx's mirror of the maps' counters is refreshed in queue order: a fuse job queued behind a carve is admitted on
+ * the carved count. Rejected with SVO_ERR_INVALID and nothing queued: everything svo_submit_export_ar_occluded(_sgm)
+ * rejects of cloud, sgm and check (cloud.frame != SVO_CLOUD_CAMERA and cloud.layout != 0 too), everything
+ * svo_submit_prune_voxel_maps rejects (of a non-NULL keep), everything svo_voxel_carve rejects of the carve, a NULL info.
+ * Memory, per group, made on first use: the occluded AR job's cloud blocks and the prune job's block, which here also
+ * holds the ballot words of the largest map and 256 bytes of counters per carved slot. A ctx that never carves
+ * allocates, launches and copies nothing more; a prune job launches what it launched before. */
+enum { SVO_CARVE_OK = 0, SVO_CARVE_NO_MAP = 1, SVO_CARVE_NO_POSE = 2, SVO_CARVE_TOO_LARGE = 3, SVO_CARVE_NONE = 4 };
+
+typedef struct svo_carve_info {     /* 64 bytes, host, one per named slot */
+    int32_t seq, run;               /* slot and ordinal of its run                                          */
+    int32_t frame_id;               /* of the slot's current frame; -1: empty slot                          */
+    int32_t status;                 /* SVO_CARVE_*                                                          */
+    int64_t n_before;               /* the map's n_voxels before the job (NO_MAP: 0)                        */
+    int64_t n_kept;                 /* and after it (not carved: n_before)                                  */
+    int32_t n_tested, n_carved;     /* the stage result's counts; a map has at most 1 << 26 entries      */
+    float   pose[6];                /* svo_get_pose at that queue position                                  */
+} svo_carve_info;
+
+int svo_submit_carve_voxel_maps(svo_ctx *ctx, const int *seqs, int n, const svo_cloud_style *cloud, const svo_sgm_params *sgm,
+                                const svo_stereo_check *check, const svo_voxel_carve_rule *carve, const svo_voxel_keep *keep,
+                                int center_mode, const float *centers, svo_carve_info *info);
+int svo_carve_voxel_maps(svo_ctx *ctx, const int *seqs, int n, const svo_cloud_style *cloud, const svo_sgm_params *sgm,
+                         const svo_stereo_check *check, const svo_voxel_carve_rule *carve, const svo_voxel_keep *keep,
+                         int center_mode, const float *centers, svo_carve_info *info);   /* submit + wait */
+
 /* ---- snapshots: the sequence state of a slot saved, loaded, moved between ctxs ------------
  * The reference has no checkpoint or resume (a StereoSlam lives and dies with its process). A snapshot is
  * everything the next frame of a slot depends on and everything its getters return, so that a sequence saved

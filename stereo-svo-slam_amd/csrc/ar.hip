@@ -87,6 +87,13 @@ int ar_check_style(const svo_ar_style* s, const char* who) {
     return SVO_OK;
 }
 
+int ar_check_occluder(const svo_ar_occluder* o, const char* who, int i) {
+    if (!o) return svo_set_error(SVO_ERR_INVALID, "%s: no occluders", who);
+    if (o->_reserved != 0 || (o->records && (o->step < 1 || o->step > 16 || o->cols <= 0 || o->rows <= 0 || ((uintptr_t)o->records & 15))))
+        return svo_set_error(SVO_ERR_INVALID, "%s: image %d: an occluder of step 1 .. 16, cols and rows > 0, records 16-byte aligned, _reserved 0", who, i);
+    return SVO_OK;
+}
+
 int ar_check_camera(const svo_ar_camera* c, const char* who, int i) {
     if (!c) return svo_set_error(SVO_ERR_INVALID, "%s: no cameras", who);
     bool finite = std::isfinite(c->fx) && std::isfinite(c->fy) && std::isfinite(c->cx) && std::isfinite(c->cy);

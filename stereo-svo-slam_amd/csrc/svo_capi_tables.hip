@@ -487,9 +487,7 @@ static int render_ar(svo_handle* h, int n, const svo_ar_src* src, const svo_ar_c
         if (tri > SVO_AR_MAX_TRIANGLES)
             return svo_set_error(SVO_ERR_CAPACITY, "svo_render_ar: image %d: %lld triangles, at most %d", i, (long long)tri, (int)SVO_AR_MAX_TRIANGLES);
         if (occluded) {
-            const svo_ar_occluder& o = occluders[i];
-            if (o._reserved != 0 || (o.records && (o.step < 1 || o.step > 16 || o.cols <= 0 || o.rows <= 0 || ((uintptr_t)o.records & 15))))
-                return svo_set_error(SVO_ERR_INVALID, "svo_render_ar_occluded: image %d: an occluder of step 1 .. 16, cols and rows > 0, records 16-byte aligned, _reserved 0", i);
+            if (const int rc = ar_check_occluder(&occluders[i], "svo_render_ar_occluded", i)) return rc;
         }
         draw0.push_back(draws.size());
         rec0.push_back(records);

@@ -1,5 +1,5 @@
-// svo_capi_voxel.hip — the stage entries of the voxel maps (include/svo_hip.h, "voxel maps", "voxel prune"): clear, fuse,
-// info, extract and prune on maps in the caller's device memory, complete on return. Every check is made on the host before any
+// svo_capi_voxel.hip — the stage entries of the voxel maps (include/svo_hip.h, "voxel maps", "voxel prune", "voxel carve"): clear, fuse,
+// info, extract, prune and carve on maps in the caller's device memory, complete on return. Every check is made on the host before any
 // launch (the params, the alignment, the header of each named map, the load bound), with the arithmetic of
 // svo_voxel_plan.hpp; the kernels are voxel.hip's.
 #include <hip/hip_runtime.h>
@@ -201,5 +201,87 @@ extern "C" int svo_voxel_prune(svo_handle* h, const svo_voxel_map* map, const sv
     HIP_TRY(hipMemcpyAsync(&kept, tile_offsets + voxel_map_tiles(mp.log2_capacity), sizeof(kept), hipMemcpyDeviceToHost, h->stream));
     if (const int rc = finish_launch(h)) return rc;
     if (out) *out = svo_voxel_prune_result{(int64_t)hd.n_voxels, (int64_t)kept, {f.c[0], f.c[1], f.c[2]}, 0};
+    return SVO_OK;
+}
+
+namespace svo {
+
+// the scalar fields of a carve and the image size, or why they are rejected
+int voxel_check_carve_rule(const svo_voxel_carve_rule* carve, int width, int height, const char* who) {
+    if (!carve) return svo_set_error(SVO_ERR_INVALID, "%s: no carve", who);
+    if (!voxel_carve_scalars_ok(carve->margin, carve->near, carve->ring, width, height))
+        return svo_set_error(SVO_ERR_INVALID, "%s: margin must be finite and >= 0, near finite and > 0, ring 0 or 1, the image 1 .. 32768 pixels a side", who);
+    if (carve->_reserved[0] != 0 || carve->_reserved[1] != 0 || carve->_reserved[2] != 0)
+        return svo_set_error(SVO_ERR_INVALID, "%s: a _reserved of the carve is not 0", who);
+    return SVO_OK;
+}
+
+// the carve as the kernels take it, or why it is rejected; the camera and the occluder are checked by the AR entry's
+// own functions
+int voxel_check_carve(const svo_voxel_carve_rule* carve, const svo_ar_camera* camera, int width, int height, const svo_ar_occluder* occluder,
+                      const char* who, VoxelCarveDev* out) {
+    if (const int rc = voxel_check_carve_rule(carve, width, height, who)) return rc;
+    if (const int rc = ar_check_camera(camera, who, 0)) return rc;
+    if (const int rc = ar_check_occluder(occluder, who, 0)) return rc;
+    const svo_ar_occluder& o = *occluder;
+    *out = voxel_carve_dev(*carve, *camera, width, height, o.records, o.cols, o.rows, o.step);
+    return SVO_OK;
+}
+
+// records == nullptr: no evidence anywhere (cols, rows and step are not used then)
+VoxelCarveDev voxel_carve_dev(const svo_voxel_carve_rule& carve, const svo_ar_camera& camera, int width, int height, const svo_map_point* records,
+                              int cols, int rows, int step) {
+    VoxelCarveDev d{};
+    memcpy(d.view, camera.view, sizeof(d.view));
+    d.fx = camera.fx; d.fy = camera.fy; d.cx = camera.cx; d.cy = camera.cy;
+    d.w = (float)width; d.h = (float)height;
+    d.margin = carve.margin; d.near = carve.near;
+    d.records = records;
+    d.cols = records ? cols : 0; d.rows = records ? rows : 0; d.step = records ? step : 1;
+    d.drop_flags = ((uint32_t)SVO_CLOUD_DROPPED | carve.drop_flags) & 0xffu;
+    d.max_last = carve.max_last;
+    d.ring = carve.ring;
+    return d;
+}
+
+}  // namespace svo
+
+extern "C" int svo_voxel_carve(svo_handle* h, const svo_voxel_map* map, const svo_ar_camera* camera, int width, int height,
+                               const svo_ar_occluder* occluder, const svo_voxel_carve_rule* carve, const svo_voxel_keep* keep,
+                               svo_voxel_carve_result* result) {
+    CHECK_H(h);
+    if (const int rc = check_map(map, "svo_voxel_carve", 0)) return rc;
+    const svo_voxel_keep all{0u, 0u, {0.f, 0.f, 0.f}, -1, {0, 0}};   // keep == NULL: every entry is kept by the keep rule
+    VoxelCarveRule rule{};
+    if (const int rc = voxel_check_keep(keep ? keep : &all, keep ? keep->center : all.center, map->params.voxel, "svo_voxel_carve", &rule.keep)) return rc;
+    if (const int rc = voxel_check_carve(carve, camera, width, height, occluder, "svo_voxel_carve", &rule.carve)) return rc;
+    const VoxelMapDev mp = map_dev(map->data, map->params);
+    VoxelHeader hd;
+    HIP_TRY(hipMemcpyAsync(&hd, map->data, sizeof(hd), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (!voxel_header_matches(hd, map->params)) return svo_set_error(SVO_ERR_INVALID, "svo_voxel_carve: the map was not cleared with these params");
+    VoxelPrunePlan plan;
+    if (hd.n_voxels > ((uint64_t)1 << mp.log2_capacity) || !voxel_prune_plan(hd.n_voxels, plan))
+        return svo_set_error(SVO_ERR_CAPACITY, "svo_voxel_carve: staging %llu entries exceeds %zu bytes", hd.n_voxels, VOXEL_PRUNE_STAGING_MAX);
+    // the prune's block (tile offsets, staging), then the ballot words and the counters
+    const size_t offsets_bytes = voxel_offsets_bytes(mp.log2_capacity);
+    const VoxelCarvePlan extra = voxel_carve_plan(mp.log2_capacity);
+    if (const int rc = h->voxel_ws.reserve(offsets_bytes + plan.bytes + extra.bytes, h->stream)) return rc;
+    uint8_t* ws = h->voxel_ws.ptr.get();
+    int32_t* tile_offsets = reinterpret_cast<int32_t*>(ws);
+    rule.ballots = reinterpret_cast<unsigned long long*>(ws + offsets_bytes + plan.bytes + extra.ballots);
+    rule.counters = reinterpret_cast<unsigned long long*>(ws + offsets_bytes + plan.bytes + extra.counters);
+    // (SVO_VOXEL_CARVE_REEVALUATE: the other form of the kernels, for tools/voxel_bench.py and the test of its equality:
+    // no ballot words, the stage pass evaluates the carve again)
+    const char* form = std::getenv("SVO_VOXEL_CARVE_REEVALUATE");
+    if (form && std::atoi(form) != 0) rule.ballots = nullptr;
+    launch_voxel_carve(mp, rule, tile_offsets, ws + offsets_bytes, hd.n_voxels, h->stream);
+    HIP_TRY(hipGetLastError());
+    int32_t kept = 0;
+    unsigned long long counts[2] = {0, 0};
+    HIP_TRY(hipMemcpyAsync(&kept, tile_offsets + voxel_map_tiles(mp.log2_capacity), sizeof(kept), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(counts, rule.counters, sizeof(counts), hipMemcpyDeviceToHost, h->stream));
+    if (const int rc = finish_launch(h)) return rc;
+    if (result) *result = svo_voxel_carve_result{(int64_t)hd.n_voxels, (int64_t)kept, (int64_t)counts[0], (int64_t)counts[1]};
     return SVO_OK;
 }

@@ -56,6 +56,9 @@ int run_job(svo_group* g, int seq0, const svo_ctx::VoxelExport& j) {
 }
 int run_job(svo_group* g, int, const svo_ctx::VoxelClear& j) { return grp_clear_voxel_maps(g, j.seqs.data(), (int)j.seqs.size()); }
 int run_job(svo_group* g, int seq0, const svo_ctx::VoxelPrune& j) {
+    if (j.has_carve)
+        return grp_carve_voxel_maps(g, j.seqs.data(), j.seg.data(), (int)j.seqs.size(), seq0, &j.cloud, j.sgm_ptr(), j.check_ptr(), &j.carve, &j.keep,
+                                    j.center_mode, j.centers.data(), j.carve_info);
     return grp_prune_voxel_maps(g, j.seqs.data(), j.seg.data(), (int)j.seqs.size(), seq0, &j.keep, j.center_mode, j.centers.data(), j.info);
 }
 

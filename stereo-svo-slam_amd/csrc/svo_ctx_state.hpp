@@ -156,11 +156,17 @@ struct svo_ctx {
     struct VoxelClear : SlotList {};
     // the group's share of an svo_submit_prune_voxel_maps: a slot fills the info of its named position; in given
     // mode three floats per slot of the share
-    struct VoxelPrune : SlotShare {
+    // (svo_submit_carve_voxel_maps: the same entry carrying a carve, the cloud style of its occluder with the check
+    // and the SGM params beside it, and the carve's own info records)
+    struct VoxelPrune : SlotShare, StereoCheck, SgmMode {
         svo_voxel_keep keep{};
         int center_mode = 0;
         std::vector<float> centers;
         svo_prune_info* info = nullptr;
+        bool has_carve = false;
+        svo_voxel_carve_rule carve{};
+        svo_cloud_style cloud{};
+        svo_carve_info* carve_info = nullptr;
     };
     // one entry of a group's queue (the frame set first: a Job{} is one, with nothing allocated)
     using Job = std::variant<Frames, Restart, Trim, RigAssign, Export, MapExport, ViewExport, DisparityExport, CloudExport,
@@ -206,7 +212,8 @@ struct svo_ctx {
     const svo_group* g0() const { return workers[0]->g.get(); }   // (every group has the same size and settings)
 };
 
-namespace svo { int voxel_check_params(const svo_voxel_params* p, bool ctx, const char* who); }   // svo_capi_voxel.hip
+namespace svo { int voxel_check_params(const svo_voxel_params* p, bool ctx, const char* who); }
+namespace svo { int voxel_check_carve_rule(const svo_voxel_carve_rule* carve, int width, int height, const char* who); }   // svo_capi_voxel.hip
 extern "C" int svo_ctx_set_exact_pinv(svo_ctx* c, int on);
 
 // ------------------------------------------------------------------ the queue (svo_ctx.hip)

@@ -1,5 +1,7 @@
 // svo_ctx_voxel.hip — the voxel maps of the ctx's slots (svo_ctx_state.hpp): giving slots a map, its info, and the
 // queued jobs that fuse dense clouds into the maps, export them, clear them and prune them.
+#include <functional>
+
 #include "svo_ctx_state.hpp"
 #include "svo_voxel_plan.hpp"
 
@@ -106,15 +108,14 @@ extern "C" int svo_submit_clear_voxel_maps(svo_ctx* c, const int* seqs, int n) {
     return SVO_OK;
 }
 
-extern "C" int svo_submit_prune_voxel_maps(svo_ctx* c, const int* seqs, int n, const svo_voxel_keep* keep, int center_mode, const float* centers,
-                                           svo_prune_info* info) {
-    if (!c || !keep || !info || !naming_ok(seqs, n) || (center_mode != SVO_PRUNE_CENTER_GIVEN && center_mode != SVO_PRUNE_CENTER_POSE))
-        return svo_set_error(SVO_ERR_INVALID, "svo_submit_prune_voxel_maps: bad arguments (center_mode %d)", center_mode);
-    if (keep->_reserved[0] != 0 || keep->_reserved[1] != 0) return svo_set_error(SVO_ERR_INVALID, "svo_submit_prune_voxel_maps: a _reserved is not 0");
+// svo_submit_prune_voxel_maps, and svo_submit_carve_voxel_maps through `more`, which fills what the entry carries besides
+static int submit_prune(svo_ctx* c, const char* who, const int* seqs, int n, const svo_voxel_keep* keep, int center_mode, const float* centers,
+                        const std::function<void(svo_ctx::VoxelPrune&)>& more) {
+    if (keep->_reserved[0] != 0 || keep->_reserved[1] != 0) return svo_set_error(SVO_ERR_INVALID, "%s: a _reserved is not 0", who);
     const NamedSlots slots = ctx_slots(c, seqs, n);
     const bool given = center_mode == SVO_PRUNE_CENTER_GIVEN && keep->radius >= 0;
     auto center_of = [&](int i) { return centers && center_mode == SVO_PRUNE_CENTER_GIVEN ? centers + 3 * (size_t)i : keep->center; };
-    const int rc = check_slots_and_items(c, "svo_submit_prune_voxel_maps", slots, [&](int i) {
+    const int rc = check_slots_and_items(c, who, slots, [&](int i) {
         if (!given) return (int)SVO_OK;
         const int s = slots.at(i);
         for (auto& wp : c->workers) {
@@ -123,21 +124,56 @@ extern "C" int svo_submit_prune_voxel_maps(svo_ctx* c, const int* seqs, int n, c
             int32_t ci;
             for (int j = 0; j < 3 && voxel > 0.f; j++)
                 if (!svo::voxel_center_index(center_of(i)[j], voxel, ci))
-                    return svo_set_error(SVO_ERR_INVALID, "svo_submit_prune_voxel_maps: slot %d: the centre's coordinate %d (%g) is not finite or lies outside the map's key range",
-                                         s, j, (double)center_of(i)[j]);
+                    return svo_set_error(SVO_ERR_INVALID, "%s: slot %d: the centre's coordinate %d (%g) is not finite or lies outside the map's key range",
+                                         who, s, j, (double)center_of(i)[j]);
         }
         return (int)SVO_OK;
     });
     if (rc) return rc;
-    if (c->failed.load()) return reject_failed(c, "svo_submit_prune_voxel_maps");
+    if (c->failed.load()) return reject_failed(c, who);
     submit_shares<svo_ctx::VoxelPrune>(c, slots,
                                        [&](svo_ctx::VoxelPrune& e, int i, int) {
                                            const float* at = center_of(i);
                                            e.centers.insert(e.centers.end(), at, at + 3);
                                            return true;
                                        },
-                                       [&](svo_ctx::VoxelPrune& e) { e.keep = *keep; e.center_mode = center_mode; e.info = info; });
+                                       [&](svo_ctx::VoxelPrune& e) { e.keep = *keep; e.center_mode = center_mode; more(e); });
     return SVO_OK;
+}
+
+extern "C" int svo_submit_prune_voxel_maps(svo_ctx* c, const int* seqs, int n, const svo_voxel_keep* keep, int center_mode, const float* centers,
+                                           svo_prune_info* info) {
+    if (!c || !keep || !info || !naming_ok(seqs, n) || (center_mode != SVO_PRUNE_CENTER_GIVEN && center_mode != SVO_PRUNE_CENTER_POSE))
+        return svo_set_error(SVO_ERR_INVALID, "svo_submit_prune_voxel_maps: bad arguments (center_mode %d)", center_mode);
+    return submit_prune(c, "svo_submit_prune_voxel_maps", seqs, n, keep, center_mode, centers, [&](svo_ctx::VoxelPrune& e) { e.info = info; });
+}
+
+// the carve job (include/svo_hip.h, "voxel carve"): the prune entry carrying a carve
+extern "C" int svo_submit_carve_voxel_maps(svo_ctx* c, const int* seqs, int n, const svo_cloud_style* cloud, const svo_sgm_params* sgm,
+                                           const svo_stereo_check* check, const svo_voxel_carve_rule* carve, const svo_voxel_keep* keep,
+                                           int center_mode, const float* centers, svo_carve_info* info) {
+    const char* who = "svo_submit_carve_voxel_maps";
+    if (const int rc = drop_check_that_is_off(&check, true, who)) return rc;
+    if (!c || !info || !naming_ok(seqs, n) || (center_mode != SVO_PRUNE_CENTER_GIVEN && center_mode != SVO_PRUNE_CENTER_POSE))
+        return svo_set_error(SVO_ERR_INVALID, "%s: bad arguments (center_mode %d)", who, center_mode);
+    if (const int rc = grp_check_cloud_style(c->g0(), cloud, check)) return rc;
+    if (sgm)
+        if (const int rc = grp_check_cloud_sgm(c->g0(), cloud, sgm, who)) return rc;
+    if (cloud->frame != SVO_CLOUD_CAMERA || cloud->layout != 0)
+        return svo_set_error(SVO_ERR_INVALID, "%s: cloud.frame %d must be SVO_CLOUD_CAMERA and cloud.layout %d must be 0", who, cloud->frame, cloud->layout);
+    if (const int rc = svo::voxel_check_carve_rule(carve, 1, 1, who)) return rc;
+    const svo_voxel_keep all{0u, 0u, {0.f, 0.f, 0.f}, -1, {0, 0}};
+    return submit_prune(c, who, seqs, n, keep ? keep : &all, center_mode, centers, [&](svo_ctx::VoxelPrune& e) {
+        e.has_carve = true; e.carve = *carve; e.cloud = *cloud; e.carve_info = info;
+        e.set_check(check);
+        e.set_sgm(sgm);
+    });
+}
+
+extern "C" int svo_carve_voxel_maps(svo_ctx* c, const int* seqs, int n, const svo_cloud_style* cloud, const svo_sgm_params* sgm,
+                                    const svo_stereo_check* check, const svo_voxel_carve_rule* carve, const svo_voxel_keep* keep, int center_mode,
+                                    const float* centers, svo_carve_info* info) {
+    return then_wait(c, svo_submit_carve_voxel_maps(c, seqs, n, cloud, sgm, check, carve, keep, center_mode, centers, info));
 }
 
 extern "C" int svo_prune_voxel_maps(svo_ctx* c, const int* seqs, int n, const svo_voxel_keep* keep, int center_mode, const float* centers,

@@ -150,6 +150,12 @@ int grp_clear_voxel_maps(svo_group* g, const int* seqs, int n);
 // grp_set_voxel_maps, so the submitting thread may read it.
 int grp_prune_voxel_maps(svo_group* g, const int* seqs, const int* seg, int n, int seq0, const svo_voxel_keep* keep, int center_mode,
                          const float* centers, svo_prune_info* info);
+// the carve job ("voxel carve"): grp_prune_voxel_maps with a carve. The occluder of a slot is grp_export_cloud itself, in
+// device mode, the camera frame and the organized layout of the current frame, into the block of the occluded AR job;
+// the camera is svo_ar_camera_of_pose of the slot's pose and rig. cloud, sgm and check: checked as for the AR job.
+int grp_carve_voxel_maps(svo_group* g, const int* seqs, const int* seg, int n, int seq0, const svo_cloud_style* cloud, const svo_sgm_params* sgm,
+                         const svo_stereo_check* check, const svo_voxel_carve_rule* carve, const svo_voxel_keep* keep, int center_mode,
+                         const float* centers, svo_carve_info* info);
 float grp_voxel_edge(const svo_group* g, int seq);
 // what svo_map_size reports of a slot (the queues have drained)
 void grp_map_size(const svo_group* g, int seq, int from_keyframe, int* keyframes, int64_t* points_bound, int* from = nullptr);

@@ -275,3 +275,100 @@ int grp_prune_voxel_maps(svo_group* c, const int* seqs, const int* seg, int n, i
     }
     return SVO_OK;
 }
+
+// grp_prune_voxel_maps with a carve ("voxel carve"). The statuses are settled on the host first (no map, an empty slot, no
+// pose, the staging bound); the slots that are left run in chunks: grp_export_cloud in device mode writes the chunk's
+// organized camera-frame records into the occluded AR job's block, then per slot the six launches of
+// launch_voxel_carve in the prune job's block (tile offsets | staging | ballot words; the counters of every slot of the
+// job lie behind them) and a copy of the map's header, the new mirror. One wait per chunk, one copy of all counters.
+int grp_carve_voxel_maps(svo_group* c, const int* seqs, const int* seg, int n, int seq0, const svo_cloud_style* cloud, const svo_sgm_params* sgm,
+                         const svo_stereo_check* check, const svo_voxel_carve_rule* carve, const svo_voxel_keep* keep, int center_mode,
+                         const float* centers, svo_carve_info* info) {
+    if (const int rc = job_begin(c, "svo_submit_carve_voxel_maps")) return rc;
+    hipStream_t st = c->stream.get();
+    struct Todo { int seq, at; VoxelKeepDev f; VoxelPrunePlan plan; size_t offsets; VoxelCarvePlan extra; };
+    std::vector<Todo> todo;
+    size_t need = 0;
+    for (int i = 0; i < n; i++) {
+        const Seq& q = c->seqs[seqs[i]];
+        svo_carve_info& e = clear(info[seg[i]]);
+        e.seq = seq0 + seqs[i]; e.run = q.run; e.frame_id = q.frame_id; e.status = SVO_CARVE_NO_MAP;
+        std::memcpy(e.pose, q.pose, sizeof(e.pose));
+        const svo_group::VoxelSlot* v = c->voxel_maps.empty() ? nullptr : &c->voxel_maps[(size_t)seqs[i]];
+        if (!v || !v->p) continue;
+        e.n_before = e.n_kept = (int64_t)v->head.n_voxels;
+        e.status = SVO_CARVE_NONE;
+        if (q.frame_id < 0 || !q.cur_set) continue;
+        Todo t{seqs[i], seg[i], VoxelKeepDev{std::max<uint32_t>(1u, keep->min_count), keep->min_stamp, {0, 0, 0}, keep->radius < 0 ? -1 : keep->radius}, {}, 0, {}};
+        e.status = SVO_CARVE_NO_POSE;
+        if (keep->radius >= 0) {
+            const float* at = center_mode == SVO_PRUNE_CENTER_POSE ? q.pose : centers + 3 * (size_t)i;
+            if (!voxel_center_index(at[0], v->params.voxel, t.f.c[0]) || !voxel_center_index(at[1], v->params.voxel, t.f.c[1]) ||
+                !voxel_center_index(at[2], v->params.voxel, t.f.c[2]))
+                continue;
+        }
+        if (v->head.n_voxels > ((uint64_t)1 << v->params.log2_capacity) || !voxel_prune_plan(v->head.n_voxels, t.plan)) {
+            e.status = SVO_CARVE_TOO_LARGE;
+            continue;
+        }
+        e.status = SVO_CARVE_OK;
+        t.offsets = voxel_offsets_bytes(v->params.log2_capacity);
+        t.extra = voxel_carve_plan(v->params.log2_capacity);
+        need = std::max(need, t.offsets + t.plan.bytes + t.extra.counters);   // (the ballot words; the counters follow for all slots)
+        todo.push_back(t);
+    }
+    if (todo.empty()) return SVO_OK;
+    svo_cloud_style organized = *cloud;
+    organized.layout = SVO_CLOUD_ORGANIZED;
+    const int64_t points = grp_cloud_points(c, &organized);
+    const size_t rec_bytes = sizeof(svo_map_point) * (size_t)points;
+    // (SVO_AR_CHUNK_SLOTS: fewer slots per chunk, as in the occluded AR job)
+    const size_t per_slot = (size_t)grp_cloud_slot_bytes(c, &organized, check, sgm) + rec_bytes;
+    const size_t m_max = std::min(todo.size(), table_tiles("SVO_AR_CHUNK_SLOTS", std::max<size_t>(1, FUSE_STAGING_BYTES / std::max<size_t>(per_slot, 1))));
+    if (const int rc = c->d_ar_occ.reserve(c, m_max * rec_bytes)) return rc;
+    if (const int rc = c->d_voxel_prune.reserve(c, need + 256 * todo.size())) return rc;
+    svo_map_point* const d_records = reinterpret_cast<svo_map_point*>(c->d_ar_occ.p);
+    uint8_t* const block = c->d_voxel_prune.p;
+    std::vector<VoxelHeader> heads(todo.size());
+    std::vector<unsigned long long> counts(32 * todo.size(), 0);
+    std::vector<svo_cloud_segment> csegs(m_max);
+    std::vector<int> local(m_max), chunk_seqs(m_max);
+    for (size_t j = 0; j < m_max; j++) local[j] = (int)j;
+    const int cols = c->width / organized.step, rows = c->height / organized.step;
+    for (size_t i0 = 0; i0 < todo.size(); i0 += m_max) {
+        const int m = (int)std::min(m_max, todo.size() - i0);
+        for (int j = 0; j < m; j++) chunk_seqs[(size_t)j] = todo[i0 + (size_t)j].seq;
+        const svo_cloud_dst cloud_dst{csegs.data(), d_records, (int64_t)m * points};
+        if (const int rc = grp_export_cloud(c, SVO_EXPORT_FRAMES, SVO_MEM_DEVICE, chunk_seqs.data(), local.data(), m, seq0, &organized, check, &cloud_dst, sgm))
+            return rc;
+        for (int j = 0; j < m; j++) {
+            const Todo& t = todo[i0 + (size_t)j];
+            const svo_group::VoxelSlot& v = c->voxel_maps[(size_t)t.seq];
+            const Seq& q = c->seqs[t.seq];
+            if (csegs[(size_t)j].status != SVO_CLOUD_OK)
+                return svo_set_error(SVO_ERR_INVALID, "svo_submit_carve_voxel_maps: slot %d has a frame and no cloud", seq0 + t.seq);
+            svo_ar_camera cam;
+            svo_ar_camera_of_pose(q.pose, &q.cam, &cam);
+            VoxelCarveRule rule{};
+            rule.keep = t.f;
+            rule.carve = voxel_carve_dev(*carve, cam, c->width, c->height, d_records + (int64_t)j * points, cols, rows, organized.step);
+            rule.ballots = reinterpret_cast<unsigned long long*>(block + t.offsets + t.plan.bytes);
+            rule.counters = reinterpret_cast<unsigned long long*>(block + need + 256 * (i0 + (size_t)j));
+            launch_voxel_carve(map_dev(v), rule, reinterpret_cast<int32_t*>(block), block + t.offsets, v.head.n_voxels, st);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpyAsync(&heads[i0 + (size_t)j], v.p, sizeof(VoxelHeader), hipMemcpyDeviceToHost, st));
+        }
+        HIP_TRY(hipStreamSynchronize(st));   // carved; the records are free for the next chunk
+    }
+    HIP_TRY(hipMemcpyAsync(counts.data(), block + need, 256 * todo.size(), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    for (size_t j = 0; j < todo.size(); j++) {
+        svo_group::VoxelSlot& v = c->voxel_maps[(size_t)todo[j].seq];
+        svo_carve_info& e = info[todo[j].at];
+        e.n_kept = (int64_t)heads[j].n_voxels;
+        e.n_tested = (int32_t)counts[32 * j];
+        e.n_carved = (int32_t)counts[32 * j + 1];
+        v.head = heads[j];
+    }
+    return SVO_OK;
+}

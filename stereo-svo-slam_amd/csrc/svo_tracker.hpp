@@ -317,6 +317,9 @@ struct ArParams {
 // what an ar job, svo_ar_size and the stage entry check alike
 int ar_check_style(const svo_ar_style* style, const char* who);
 int ar_check_camera(const svo_ar_camera* cam, const char* who, int i);
+// an occluder of the stage entries (svo_render_ar_occluded, svo_voxel_carve): records == NULL (nothing else is read but _reserved), or
+// step 1 .. 16, cols and rows > 0 and 16-byte aligned records
+int ar_check_occluder(const svo_ar_occluder* o, const char* who, int i);
 ArParams ar_params(const svo_ar_style& style);
 // pitch and image_bytes of a cols x rows image of a checked style
 void ar_shape(const svo_ar_style& style, int cols, int rows, int64_t* pitch, int64_t* image_bytes);
@@ -570,12 +573,41 @@ struct VoxelKeepDev {
     uint32_t min_count, min_stamp;
     int32_t c[3];
     int32_t radius;
+    static constexpr bool carves = false;
 };
 // The map rebuilt in place from its kept entries, with no host read-back: count and scan (tile_offsets as
 // launch_voxel_count's), stage, clear, reinsert and the header's n_voxels, six launches ordered by the stream.
 // n_bound: an upper bound of the kept count (the header's n_voxels as the host knows it); staging: the
 // voxel_prune_plan block of n_bound entries. When nothing leaves, only tile_offsets is written.
 void launch_voxel_prune(const VoxelMapDev& map, VoxelKeepDev keep, int32_t* tile_offsets, uint8_t* staging, uint64_t n_bound,
+                        hipStream_t stream);
+// The carve of a checked call (include/svo_hip.h, "voxel carve"): the camera, the image size as floats, the occluder
+// lattice (records == nullptr: no evidence anywhere) and the guards. drop_flags holds SVO_CLOUD_DROPPED too.
+struct VoxelCarveDev {
+    float view[12];
+    float fx, fy, cx, cy;
+    float w, h;
+    float margin, near;
+    const svo_map_point* records;
+    int32_t cols, rows, step;
+    uint32_t drop_flags;
+    uint32_t max_last;
+    int32_t ring;
+};
+// The rule of a carving rebuild: an entry stays iff `keep` keeps it and `carve` does not carve it. ballots: one word
+// per wavefront of the count pass (VOXEL_TILE / 64 per tile), read by the stage pass (nullptr: a diagnostic form without
+// them, whose stage pass evaluates the rule again); counters: n_tested, n_carved.
+struct VoxelCarveRule {
+    VoxelKeepDev keep;
+    VoxelCarveDev carve;
+    unsigned long long* ballots;
+    unsigned long long* counters;
+    static constexpr bool carves = true;
+};
+// launch_voxel_prune under a VoxelCarveRule: the counters are zeroed on the stream first, then the same six launches.
+VoxelCarveDev voxel_carve_dev(const svo_voxel_carve_rule& carve, const svo_ar_camera& camera, int width, int height, const svo_map_point* records,
+                              int cols, int rows, int step);
+void launch_voxel_carve(const VoxelMapDev& map, const VoxelCarveRule& rule, int32_t* tile_offsets, uint8_t* staging, uint64_t n_bound,
                         hipStream_t stream);
 
 }  // namespace svo

@@ -121,4 +121,24 @@ inline bool voxel_prune_plan(uint64_t n_voxels, VoxelPrunePlan& p) {
 // the workgroups of the reinsert pass over at most n_voxels staged entries
 inline int64_t voxel_prune_tiles(uint64_t n_voxels) { return (int64_t)((n_voxels + VOXEL_TILE - 1) / VOXEL_TILE); }
 
+// ---- voxel carve (include/svo_hip.h, "voxel carve"): what a carving rebuild needs behind the prune's block: one
+// 64-bit ballot word per wavefront of the count pass (VOXEL_TILE / 64 per tile) and a 256-byte block for the two counters
+struct VoxelCarvePlan {
+    size_t ballots, counters, bytes;      // offsets from the end of the prune's staging, and the bytes added
+};
+inline VoxelCarvePlan voxel_carve_plan(int log2_capacity) {
+    VoxelCarvePlan p{};
+    p.ballots = 0;
+    p.counters = voxel_up256(sizeof(uint64_t) * (VOXEL_TILE / 64) * (size_t)voxel_map_tiles(log2_capacity));
+    p.bytes = p.counters + 256;
+    return p;
+}
+
+// the carve's scalar arguments: margin finite and >= 0, near finite and > 0, ring 0 or 1, the image 1 .. 32768 a side
+inline bool voxel_carve_scalars_ok(float margin, float near, int ring, int width, int height) {
+    const float big = 3.40282347e+38f;
+    return margin >= 0.f && margin <= big && near > 0.f && near <= big && (ring == 0 || ring == 1) && width >= 1 && width <= 32768 &&
+           height >= 1 && height <= 32768;
+}
+
 }  // namespace svo

@@ -40,12 +40,20 @@
 // n_voxels and returns when they are equal, so a prune that removes nothing writes no byte of the map; n_voxels
 // changes only in the last launch, so all of them see the same answer.
 //
+// Carve ("voxel carve"): the prune's rebuild with a second predicate. The count and stage kernels are templates on the
+// rule: VoxelKeepDev is the plain prune, unchanged; VoxelCarveRule adds, per non-empty entry, the entry's point (the
+// gather's three double divisions), the projection and up to nine gathers of 16-byte occluder records. It is evaluated
+// once, in the count pass, which leaves one 64-bit ballot word per wavefront; the stage pass reads the words. The two
+// counts are summed inside the workgroup and leave as one 64-bit atomic add each.
+//
 // Bounds: of a span, records [0, n) are read. Of a map, keys and acc entries [0, capacity) (slot = (slot + 1) &
 // (capacity - 1)) and the header. tile_offsets [0, tiles]; pairs and records [0, n) with n the scan's total. Of a
 // prune's staging block, records and keys [0, min(total, n_bound)) with n_bound the n_voxels the block was sized by;
-// the clear writes the 16-byte units [0, (40 << log2_capacity) / 16) behind the header.
+// the clear writes the 16-byte units [0, (40 << log2_capacity) / 16) behind the header. Of a carve: occluder records
+// [0, cols * rows) (every cell index is checked against cols and rows), ballot words [0, VOXEL_WAVES * tiles), two counters.
 #include <hip/hip_runtime.h>
 
+#include <cfloat>
 #include <cstring>
 
 #include <rocprim/rocprim.hpp>
@@ -333,13 +341,85 @@ __device__ __forceinline__ bool voxel_prune_nothing_leaves(const VoxelMapDev& mp
     return (unsigned long long)G(tile_offsets)[tiles] == ((SVO_GP(const VoxelHeader))mp.base)->n_voxels;
 }
 
-__global__ __launch_bounds__(VOXEL_THREADS) void voxel_prune_count_kernel(const VoxelMapDev mp, const VoxelKeepDev f, int32_t* __restrict__ tile_counts) {
+// ---- carve (include/svo_hip.h, "voxel carve"): is the non-empty entry e contradicted by the occluder? tested: it reached step 5
+__device__ __forceinline__ bool voxel_carved(const VoxelMapDev& mp, const VoxelCarveDev& c, uint32_t e, unsigned long long key, bool& tested) {
+    tested = false;
+    if (c.records == nullptr) return false;                // (uniform) no evidence anywhere
+    const SVO_GP(uint4) a = (SVO_GP(uint4))(voxel_acc(mp) + (size_t)e * 8);
+    const uint4 lo = a[0];                                 // count sx sy sz
+    const uint32_t last = voxel_acc(mp)[(size_t)e * 8 + 7];
+    if (last > c.max_last) return false;
+    const uint32_t count = max(lo.x, 1u);
+    const int cell[3] = {(int)(uint32_t)(key >> 42) - 1048576, (int)(uint32_t)((key >> 21) & 0x1fffffu) - 1048576,
+                         (int)(uint32_t)(key & 0x1fffffu) - 1048576};
+    const uint32_t off[3] = {lo.y, lo.z, lo.w};
+    float w[3], cam[3];
+    for (int j = 0; j < 3; j++) {                          // the gather's point
+        const double mean = (double)off[j] / (double)count;
+        w[j] = (float)(((double)cell[j] + (mean + 0.5) / 256.0) * (double)mp.voxel);
+    }
+    for (int k = 0; k < 3; k++) cam[k] = ((c.view[4 * k] * w[0] + c.view[4 * k + 1] * w[1]) + c.view[4 * k + 2] * w[2]) + c.view[4 * k + 3];
+    if (!(fabsf(cam[0]) <= FLT_MAX && fabsf(cam[1]) <= FLT_MAX && fabsf(cam[2]) <= FLT_MAX) || cam[2] < c.near) return false;
+    const float u = (c.fx * cam[0]) / cam[2] + c.cx, v = (c.fy * cam[1]) / cam[2] + c.cy;
+    if (!(u >= 0.0f && u < c.w && v >= 0.0f && v < c.h)) return false;
+    const int ix = (int)u / c.step, iy = (int)v / c.step;
+    if (ix >= c.cols || iy >= c.rows) return false;
+    float zmin = 0.f;
+    bool first = true;
+    for (int dy = -c.ring; dy <= c.ring; dy++) {           // (ring is 0 or 1: at most nine cells)
+        for (int dx = -c.ring; dx <= c.ring; dx++) {
+            const int x = ix + dx, y = iy + dy;
+            if (x < 0 || y < 0 || x >= c.cols || y >= c.rows) continue;
+            const uint4 r = ((SVO_GP(const uint4))c.records)[(size_t)y * c.cols + x];
+            const float zo = __uint_as_float(r.z);
+            if (((r.w >> 24) & c.drop_flags) || !(zo > 0.f && zo <= FLT_MAX)) return false;   // incomplete evidence
+            zmin = first ? zo : fminf(zmin, zo);
+            first = false;
+        }
+    }
+    tested = true;
+    return cam[2] + c.margin < zmin;
+}
+
+// does entry e stay, by the rule of the launch? key: the entry's, VOXEL_EMPTY past the table. The plain prune:
+__device__ __forceinline__ bool voxel_rule_stays(const VoxelMapDev& mp, const VoxelKeepDev& f, uint32_t e, unsigned long long& key, bool&, bool&) {
+    return voxel_prune_keep(mp, f, e, key);
+}
+// the carve: kept by the keep rule and not carved; the carve is evaluated on every non-empty entry
+__device__ __forceinline__ bool voxel_rule_stays(const VoxelMapDev& mp, const VoxelCarveRule& f, uint32_t e, unsigned long long& key, bool& tested,
+                                                 bool& carved) {
+    const bool keep = voxel_prune_keep(mp, f.keep, e, key);
+    if (key == VOXEL_EMPTY) return false;
+    carved = voxel_carved(mp, f.carve, e, key, tested);
+    return keep && !carved;
+}
+
+template <class Rule>
+__global__ __launch_bounds__(VOXEL_THREADS) void voxel_prune_count_kernel(const VoxelMapDev mp, const Rule f, int32_t* __restrict__ tile_counts) {
     __shared__ int wave_n[VOXEL_WAVES];
     unsigned long long key;
-    const bool keep = voxel_prune_keep(mp, f, blockIdx.x * VOXEL_TILE + threadIdx.x, key);
+    bool tested = false, carved = false;
+    const bool keep = voxel_rule_stays(mp, f, blockIdx.x * VOXEL_TILE + threadIdx.x, key, tested, carved);
     const unsigned long long m = __ballot(keep);
     if ((threadIdx.x & 63) == 0) wave_n[threadIdx.x >> 6] = __popcll(m);
-    __syncthreads();
+    if constexpr (Rule::carves) {                          // the wavefront's verdicts for the stage pass, and the two counts
+        __shared__ int wave_t[VOXEL_WAVES], wave_c[VOXEL_WAVES];
+        const unsigned long long mt = __ballot(tested), mc = __ballot(carved);
+        if ((threadIdx.x & 63) == 0) {
+            if (f.ballots) G(f.ballots)[(size_t)blockIdx.x * VOXEL_WAVES + (threadIdx.x >> 6)] = m;
+            wave_t[threadIdx.x >> 6] = __popcll(mt);
+            wave_c[threadIdx.x >> 6] = __popcll(mc);
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            unsigned long long t = 0, c = 0;
+            for (int w = 0; w < VOXEL_WAVES; w++) { t += wave_t[w]; c += wave_c[w]; }
+            if (t) __hip_atomic_fetch_add(f.counters + 0, t, VOXEL_RELAXED);
+            if (c) __hip_atomic_fetch_add(f.counters + 1, c, VOXEL_RELAXED);
+        }
+    } else {
+        __syncthreads();
+    }
     if (threadIdx.x == 0) {
         int n = 0;
         for (int w = 0; w < VOXEL_WAVES; w++) n += wave_n[w];
@@ -348,16 +428,30 @@ __global__ __launch_bounds__(VOXEL_THREADS) void voxel_prune_count_kernel(const 
 }
 
 // the kept entry of rank r leaves as acc_out[2 r], acc_out[2 r + 1] (two 16-byte stores) and keys_out[r]
-__global__ __launch_bounds__(VOXEL_THREADS) void voxel_prune_stage_kernel(const VoxelMapDev mp, const VoxelKeepDev f,
+template <class Rule>
+__global__ __launch_bounds__(VOXEL_THREADS) void voxel_prune_stage_kernel(const VoxelMapDev mp, const Rule f,
                                                                           const int32_t* __restrict__ tile_offsets, const int tiles, const size_t n_bound,
                                                                           uint4* __restrict__ acc_out, unsigned long long* __restrict__ keys_out) {
     __shared__ int wave_n[VOXEL_WAVES];
     if (voxel_prune_nothing_leaves(mp, tile_offsets, tiles)) return;   // (uniform over the grid)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const uint32_t e = blockIdx.x * VOXEL_TILE + threadIdx.x;
-    unsigned long long key;
-    const bool keep = voxel_prune_keep(mp, f, e, key);
-    const unsigned long long m = __ballot(keep);
+    unsigned long long key, m;
+    bool keep;
+    if constexpr (Rule::carves) {                          // the count pass's verdicts; a set bit names a non-empty entry of the table
+        if (f.ballots) {                                   // (uniform)
+            m = G(f.ballots)[(size_t)blockIdx.x * VOXEL_WAVES + wave];
+            keep = (m >> lane) & 1;
+            key = keep ? voxel_keys(mp)[e] : VOXEL_EMPTY;
+        } else {                                           // (the diagnostic form: no words, the rule evaluated again)
+            bool tested = false, carved = false;
+            keep = voxel_rule_stays(mp, f, e, key, tested, carved);
+            m = __ballot(keep);
+        }
+    } else {
+        keep = voxel_prune_keep(mp, f, e, key);
+        m = __ballot(keep);
+    }
     const int rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
     if (lane == 0) wave_n[wave] = __popcll(m);
     __syncthreads();
@@ -419,22 +513,33 @@ __global__ __launch_bounds__(64) void voxel_prune_finish_kernel(const VoxelMapDe
     ((SVO_GP(VoxelHeader))mp.base)->n_voxels = (unsigned long long)max(G(tile_offsets)[tiles], 0);
 }
 
-void launch_voxel_prune(const VoxelMapDev& map, VoxelKeepDev keep, int32_t* tile_offsets, uint8_t* staging, uint64_t n_bound,
-                        hipStream_t stream) {
+template <class Rule>
+static void launch_voxel_rebuild(const VoxelMapDev& map, const Rule& rule, int32_t* tile_offsets, uint8_t* staging, uint64_t n_bound, hipStream_t stream) {
     const int tiles = (int)voxel_map_tiles(map.log2_capacity);
-    hipLaunchKernelGGL(voxel_prune_count_kernel, dim3(tiles), dim3(VOXEL_THREADS), 0, stream, map, keep, tile_offsets);
+    hipLaunchKernelGGL(voxel_prune_count_kernel<Rule>, dim3(tiles), dim3(VOXEL_THREADS), 0, stream, map, rule, tile_offsets);
     hipLaunchKernelGGL(voxel_scan_kernel, dim3(1), dim3(VOXEL_THREADS), 0, stream, tile_offsets, tiles);
     VoxelPrunePlan plan;
     if (n_bound == 0 || !voxel_prune_plan(n_bound, plan)) return;   // (an empty map keeps nothing; the callers check the plan first)
     uint4* acc = reinterpret_cast<uint4*>(staging + plan.acc);
     unsigned long long* keys = reinterpret_cast<unsigned long long*>(staging + plan.keys);
     const size_t units = (voxel_map_bytes(map.log2_capacity) - VOXEL_HEADER_BYTES) / 16;
-    hipLaunchKernelGGL(voxel_prune_stage_kernel, dim3(tiles), dim3(VOXEL_THREADS), 0, stream, map, keep, tile_offsets, tiles, (size_t)n_bound, acc, keys);
+    hipLaunchKernelGGL(voxel_prune_stage_kernel<Rule>, dim3(tiles), dim3(VOXEL_THREADS), 0, stream, map, rule, tile_offsets, tiles, (size_t)n_bound, acc, keys);
     hipLaunchKernelGGL(voxel_prune_clear_kernel, dim3((unsigned)((units + VOXEL_THREADS - 1) / VOXEL_THREADS)), dim3(VOXEL_THREADS), 0, stream, map,
                        units, tile_offsets, tiles);
     hipLaunchKernelGGL(voxel_prune_reinsert_kernel, dim3((unsigned)voxel_prune_tiles(n_bound)), dim3(VOXEL_THREADS), 0, stream, map, tile_offsets,
                        tiles, (size_t)n_bound, acc, keys);
     hipLaunchKernelGGL(voxel_prune_finish_kernel, dim3(1), dim3(64), 0, stream, map, tile_offsets, tiles);
+}
+
+void launch_voxel_prune(const VoxelMapDev& map, VoxelKeepDev keep, int32_t* tile_offsets, uint8_t* staging, uint64_t n_bound,
+                        hipStream_t stream) {
+    launch_voxel_rebuild(map, keep, tile_offsets, staging, n_bound, stream);
+}
+
+void launch_voxel_carve(const VoxelMapDev& map, const VoxelCarveRule& rule, int32_t* tile_offsets, uint8_t* staging, uint64_t n_bound,
+                        hipStream_t stream) {
+    (void)hipMemsetAsync(rule.counters, 0, 2 * sizeof(unsigned long long), stream);   // (a failure is sticky: the caller's hipGetLastError sees it)
+    launch_voxel_rebuild(map, rule, tile_offsets, staging, n_bound, stream);
 }
 
 void launch_voxel_clear(const VoxelMapDev& map, hipStream_t stream) {

@@ -58,7 +58,8 @@ SYMBOLS = (
     "svo_voxel_map_bytes", "svo_voxel_clear", "svo_voxel_fuse", "svo_voxel_info", "svo_voxel_extract",
     "svo_ctx_set_voxel_maps", "svo_get_voxel_map_info", "svo_submit_fuse_clouds", "svo_fuse_clouds",
     "svo_submit_export_voxel_maps", "svo_export_voxel_maps", "svo_submit_clear_voxel_maps",
-    "svo_voxel_prune", "svo_submit_prune_voxel_maps", "svo_prune_voxel_maps",
+    "svo_voxel_prune", "svo_submit_prune_voxel_maps", "svo_prune_voxel_maps", "svo_voxel_carve",
+    "svo_submit_carve_voxel_maps", "svo_carve_voxel_maps",
     "svo_ar_size", "svo_ar_camera_of_pose", "svo_submit_export_ar", "svo_export_ar", "svo_render_ar",
     "svo_submit_export_ar_occluded", "svo_export_ar_occluded", "svo_render_ar_occluded",
     "svo_remap_linear_multi", "svo_ctx_add_rigs", "svo_ctx_remove_rigs", "svo_ctx_assign_rigs", "svo_ctx_get_slot_rig",
@@ -770,6 +771,25 @@ class VoxelPruneResult(C.Structure):
 
 
 assert (C.sizeof(VoxelKeep), C.sizeof(VoxelPruneResult)) == (32, 32)
+
+
+class VoxelCarve(C.Structure):
+    """svo_voxel_carve_rule (include/svo_hip.h, "voxel carve"): the guards of a carve."""
+    _fields_ = [("margin", C.c_float), ("near", C.c_float), ("max_last", C.c_uint32), ("drop_flags", C.c_uint32), ("ring", C.c_int32),
+                ("_reserved", C.c_int32 * 3)]
+
+
+class VoxelCarveResult(C.Structure):
+    """svo_voxel_carve_result (include/svo_hip.h)."""
+    _fields_ = [("n_before", C.c_int64), ("n_kept", C.c_int64), ("n_tested", C.c_int64), ("n_carved", C.c_int64)]
+
+
+assert (C.sizeof(VoxelCarve), C.sizeof(VoxelCarveResult)) == (32, 32)
+# the ctx's carve job: svo_submit_carve_voxel_maps (the centre modes are the prune job's)
+CARVE_OK, CARVE_NO_MAP, CARVE_NO_POSE, CARVE_TOO_LARGE, CARVE_NONE = range(5)
+CARVE_INFO_DTYPE = np.dtype([("seq", "<i4"), ("run", "<i4"), ("frame_id", "<i4"), ("status", "<i4"), ("n_before", "<i8"), ("n_kept", "<i8"),
+                             ("n_tested", "<i4"), ("n_carved", "<i4"), ("pose", "<f4", (6,))])
+assert CARVE_INFO_DTYPE.itemsize == 64
 # the ctx's prune job: svo_submit_prune_voxel_maps
 PRUNE_OK, PRUNE_NO_MAP, PRUNE_NO_POSE, PRUNE_TOO_LARGE = range(4)
 PRUNE_CENTER_GIVEN, PRUNE_CENTER_POSE = 0, 1
@@ -813,6 +833,13 @@ def voxel_keep(min_count=0, min_stamp=0, center=(0.0, 0.0, 0.0), radius=-1):
     """a VoxelKeep: count >= max(1, min_count), last >= min_stamp and, with radius >= 0 (in voxels), the box of
     2 radius + 1 voxels per axis around the voxel that holds `center`"""
     return VoxelKeep(int(min_count), int(min_stamp), (C.c_float * 3)(*[float(c) for c in center]), int(radius), (C.c_int32 * 2)(0, 0))
+
+
+def voxel_carve(margin, near=0.01, ring=1, max_last=0xFFFFFFFF, drop_flags=0):
+    """a VoxelCarve: an entry is carved when the occluder measures a surface more than `margin` behind it along its
+    ray; entries nearer than `near` or fused after stamp `max_last` are kept; ring = 1 asks the entry's lattice cell
+    and its neighbours, ring = 0 the cell alone"""
+    return VoxelCarve(float(margin), float(near), int(max_last), int(drop_flags), int(ring), (C.c_int32 * 3)(0, 0, 0))
 
 
 def _voxel_map(m):
@@ -1061,6 +1088,11 @@ def lib():
                 getattr(_LIB, name).argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         if hasattr(_LIB, "svo_voxel_prune"):
             _LIB.svo_voxel_prune.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        for name in ("svo_submit_carve_voxel_maps", "svo_carve_voxel_maps"):
+            if hasattr(_LIB, name):
+                getattr(_LIB, name).argtypes = [p, p, i, p, p, p, p, p, i, p, p]
+        if hasattr(_LIB, "svo_voxel_carve"):
+            _LIB.svo_voxel_carve.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _LIB.svo_submit_clear_voxel_maps.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         _LIB.svo_get_voxel_map_info.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         for name in ("svo_submit_pose_updates", "svo_update_poses"):
@@ -1528,6 +1560,18 @@ class Handle:
         out = VoxelPruneResult()
         _check(lib().svo_voxel_prune(self._h, C.byref(_voxel_map(m)), C.byref(keep) if keep is not None else None, C.byref(out)))
         return {"n_before": out.n_before, "n_kept": out.n_kept, "center_voxel": tuple(out.center_voxel)}
+
+    def voxel_carve(self, m, camera, width, height, occluder, carve, keep=None):
+        """svo_voxel_carve: the map reduced in place to the entries that `keep` (a VoxelKeep, or None: all) keeps and
+        that the occluder does not contradict. camera: an ArCamera; occluder: an ArOccluder, or what ar_occluder takes
+        as a tuple (None: no evidence, a plain prune); carve: a VoxelCarve (see voxel_carve). Returns a dict: n_before,
+        n_kept, n_tested, n_carved. Complete on return."""
+        occ = occluder if isinstance(occluder, ArOccluder) else ar_occluder(*(occluder if isinstance(occluder, (tuple, list)) else (occluder,)))
+        out = VoxelCarveResult()
+        _check(lib().svo_voxel_carve(self._h, C.byref(_voxel_map(m)), C.byref(camera) if camera is not None else None, int(width), int(height),
+                                     C.byref(occ), C.byref(carve) if carve is not None else None,
+                                     C.byref(keep) if keep is not None else None, C.byref(out)))
+        return {n: getattr(out, n) for n, _ in VoxelCarveResult._fields_}
 
     def render_scene(self, srcs, cameras, offsets, style, pixels):
         """svo_render_scene: the viewer's scene of keyframe sets and lines as images of `style` (a SceneStyle). srcs:

@@ -456,6 +456,24 @@ class Prune(Job):
                                                  self._info.ctypes.data)
 
 
+class Carve(Prune):
+    """One svo_submit_carve_voxel_maps: a Prune carrying a carve. The occluder of every named slot is the organized
+    camera-frame cloud of its current frame under `style` (a hip_lib.CloudStyle), `check` (a StereoCheck or None) and
+    `sgm` (an SgmParams or None: winner-takes-all); carve: a hip_lib.VoxelCarve; keep: a VoxelKeep or None (every entry
+    is kept by the keep rule). After wait(): `info` (hip_lib.CARVE_INFO_DTYPE, one per named slot)."""
+
+    def __init__(self, slam, seqs, style, check, sgm, carve, keep, centers):
+        super().__init__(slam, seqs, keep, centers)
+        self.style, self.check, self.sgm, self.carve = style, check, sgm, carve
+        self._info, self.info = self._per_slot(hip_lib.CARVE_INFO_DTYPE)
+
+    def _call(self, ctx, mem):
+        centers = None if self.centers is None or not len(self.centers) else self.centers.ctypes.data
+        ref = lambda x: None if x is None else C.byref(x)
+        return lib().svo_submit_carve_voxel_maps(ctx, self._seq_arr, self._n, C.byref(self.style), ref(self.sgm), ref(self.check),
+                                                 ref(self.carve), ref(self.keep), self.center_mode, centers, self._info.ctypes.data)
+
+
 class VoxelMaps(PointJob):
     """One svo_submit_export_voxel_maps: owns the buffers the library writes. After wait(): `segments`
     (hip_lib.VOXEL_SEGMENT_DTYPE, one per named slot) and points(i); `points_buffer`: PointJob. capacities: the records

@@ -46,7 +46,8 @@ clouds of the keyframes so far (one device array of at most N records): the dens
 --dump-dense-map FILE.ply --dense-map-voxel V [--dense-map-log2 N] [--dense-map-min-count K] fuses every new keyframe's
 dense cloud (--cloud-step, --cloud-lr, --cloud-max-depth) into a voxel map of edge V kept inside the ctx (bounded,
 every surface once, the keyframes that saw a voxel averaged) and writes it as one PLY at the end; --dense-map-window METRES
-and --dense-map-keep N prune it behind every fuse (a box around the camera; what the last N fuses reached); --scene-fused V draws
+and --dense-map-keep N prune it behind every fuse (a box around the camera; what the last N fuses reached), --dense-map-carve
+MARGIN carves it in front of every fuse (what the current frame's dense depth sees through leaves); --scene-fused V draws
 that map in the pictures of --dump-scene.
 --dump-ar DIR writes per frame DIR/000000_ar.ppm: the AR demo's picture (src/ar-app/), a lit box of edge --ar-box
 fixed at the world point --ar-at over the frame's left image, seen from the tracked pose; the default placement is the
@@ -431,7 +432,7 @@ class Replay:
                  ar_box=AR_BOX, ar_at=hip_lib.AR_AT, dump_disparity=None, disparity_step=4, disparity_depth=False,
                  dump_cloud=None, cloud_step=4, cloud_max_depth=0.0, disparity_lr=None, cloud_lr=None, scene_dense=None,
                  scene_dense_lr=None, scene_dense_max_depth=0.0, scene_accumulate=0, dump_dense_map=None, dense_map_voxel=None,
-                 dense_map_log2=20, dense_map_min_count=0, dense_map_window=None, dense_map_keep=None, scene_fused=None, ar_occlusion=None, disparity_sgm=None, cloud_sgm=None,
+                 dense_map_log2=20, dense_map_min_count=0, dense_map_window=None, dense_map_keep=None, dense_map_carve=None, scene_fused=None, ar_occlusion=None, disparity_sgm=None, cloud_sgm=None,
                  dense_map_sgm=None, scene_dense_sgm=None, ar_sgm=None):
         """fast=False keeps the library default: the reference-order Gauss-Newton (bit-exact traces).
         rectify_maps = (left maps, right maps): the frames fed are raw and are rectified on the GPU.
@@ -521,6 +522,15 @@ class Replay:
                 self.dense_map_prune["radius"] = float(dense_map_window)
             if dense_map_keep is not None:
                 self.dense_map_prune["keep_stamps"] = int(dense_map_keep)
+        # (a carve in front of every fuse of the map: what the current frame's dense depth sees through by more than
+        # dense_map_carve metres leaves; the occluder is the fuse's own kind of cloud)
+        self.dense_map_carve = None
+        if dense_map_carve is not None:
+            if self.dense_map_voxel is None:
+                raise ValueError("dense_map_carve needs a dense map")
+            if not 0 <= float(dense_map_carve) < float("inf"):
+                raise ValueError("dense_map_carve must be finite and >= 0")
+            self.dense_map_carve = float(dense_map_carve)
         self._dense_map_set, self._fused_job = False, None
         for d in (dump_views, dump_scene, dump_ar, dump_disparity, dump_cloud):
             if d:
@@ -628,7 +638,9 @@ class Replay:
             self.slam.set_voxel_maps(self.dense_map_voxel, self.dense_map_log2)
             self._dense_map_set = True
         how = dict(lr_check=self.cloud_lr) if self.dense_map_sgm is None else dict(sgm=self.dense_map_sgm)
-        return self.slam.fuse_new_keyframes(step=self.cloud_step, max_depth=self.cloud_max_depth, prune=self.dense_map_prune, **how) is not None
+        carve = None if self.dense_map_carve is None else dict(margin=self.dense_map_carve, step=self.cloud_step, max_depth=self.cloud_max_depth, **how)
+        return self.slam.fuse_new_keyframes(step=self.cloud_step, max_depth=self.cloud_max_depth, prune=self.dense_map_prune, carve=carve,
+                                            **how) is not None
 
     def finish(self):
         """what is written once, after the last frame: the dense map of dump_dense_map"""
@@ -785,6 +797,9 @@ def build_parser():
                          "camera on every axis (floor(METRES / V) voxels around the camera's voxel): the map follows the camera")
     ap.add_argument("--dense-map-keep", metavar="N", type=int, default=None,
                     help="prune the map behind every fuse to the voxels that one of the last N fuses reached")
+    ap.add_argument("--dense-map-carve", metavar="MARGIN", type=float, default=None,
+                    help="carve the map of --dump-dense-map / --scene-fused in front of every fuse: a voxel leaves when the current "
+                         "frame's dense depth (that of --dense-map-sgm, if given) measures a surface more than MARGIN metres behind it")
     ap.add_argument("--scene-fused", metavar="V", type=float, default=None,
                     help="--dump-scene also draws the fused dense map of voxel edge V (the map of --dump-dense-map), exported to "
                          "device memory whenever a keyframe was fused")
@@ -818,6 +833,10 @@ def check_dense_map_args(ap, args):
         ap.error("--dense-map-min-count must be >= 0")
     if (args.dense_map_window is not None or args.dense_map_keep is not None) and not (args.dump_dense_map or args.scene_fused is not None):
         ap.error("--dense-map-window and --dense-map-keep need --dump-dense-map or --scene-fused")
+    if args.dense_map_carve is not None and not (args.dump_dense_map or args.scene_fused is not None):
+        ap.error("--dense-map-carve needs --dump-dense-map or --scene-fused")
+    if args.dense_map_carve is not None and not (0 <= args.dense_map_carve < float("inf")):
+        ap.error("--dense-map-carve must be finite and >= 0")
     if args.dense_map_window is not None and not (0 <= args.dense_map_window < float("inf")):
         ap.error("--dense-map-window must be finite and >= 0")
     if args.dense_map_keep is not None and args.dense_map_keep < 1:
@@ -905,7 +924,7 @@ def main(argv=None):
                 scene_dense=args.scene_dense, scene_dense_lr=args.scene_dense_lr, scene_dense_max_depth=args.scene_dense_max_depth,
                 scene_accumulate=args.scene_accumulate, dump_dense_map=args.dump_dense_map, dense_map_voxel=args.dense_map_voxel,
                 dense_map_log2=args.dense_map_log2, dense_map_min_count=args.dense_map_min_count, dense_map_window=args.dense_map_window,
-                dense_map_keep=args.dense_map_keep, scene_fused=args.scene_fused,
+                dense_map_keep=args.dense_map_keep, dense_map_carve=args.dense_map_carve, scene_fused=args.scene_fused,
                 ar_occlusion=occlusion, dense_map_sgm=split(args.dense_map_sgm), scene_dense_sgm=split(args.scene_dense_sgm),
                 ar_sgm=split(args.ar_sgm))
     for k, (left, right, t) in enumerate(frames):

@@ -15,7 +15,7 @@ import torch
 
 from . import hip_lib
 from .hip_lib import POSE_SAMPLE_CHAIN, POSE_SAMPLE_DTYPE, CameraSettings, SvoError, _check, lib
-from .jobs import (KP_INFO_DTYPE, ArPictures, Clouds, Disparities, Export, Frame, Fusion, MapExport, Prune,  # noqa: F401
+from .jobs import (KP_INFO_DTYPE, ArPictures, Clouds, Disparities, Export, Carve, Frame, Fusion, MapExport, Prune,  # noqa: F401
                    Scenes, Snapshot, Views, VoxelMaps, caller_memory, int_array, named_slots)
 
 
@@ -704,13 +704,15 @@ class StereoSlamBatch:
         """submit_fuse + wait"""
         return self.submit_fuse(what, seqs, **kw).wait()
 
-    def fuse_new_keyframes(self, seqs=None, prune=None, **kw):
+    def fuse_new_keyframes(self, seqs=None, prune=None, carve=None, **kw):
         """fuse_clouds("last_keyframes") of only those slots whose newest keyframe changed since this method last fused
         them (the bookkeeping is here, on the host: it waits for the queues to read the keyframe counts). Returns the
         Fusion, or None when no slot has a new keyframe. prune: a dict of submit_prune's keywords; the prune of the
         fused slots is queued behind the fuse (and waited for with it; the Prune is the Fusion's `.prune`).
         keep_stamps=N in it stands for min_stamp = stamp - N + 1 with `stamp` this fuse's: what the last N fuses of
-        this object reached stays."""
+        this object reached stays. carve: a dict of submit_carve's keywords (margin at least); the carve of the fused
+        slots by their current frames is queued in FRONT of the fuse, so that what the camera sees through leaves before
+        the new cloud arrives (the Carve is the Fusion's `.carve`)."""
         named = named_slots(self, seqs, explicit=True)[0]
         self.wait()
         fresh = []
@@ -721,8 +723,9 @@ class StereoSlamBatch:
                 fresh.append((s, newest))
         if not fresh:
             return None
+        carved = None if carve is None else self.submit_carve(seqs=[s for s, _ in fresh], **dict(carve))
         job = self.submit_fuse("last_keyframes", [s for s, _ in fresh], **kw)
-        job.prune = None
+        job.prune, job.carve = None, carved
         if prune is not None:
             prune = dict(prune)
             keep_stamps = prune.pop("keep_stamps", None)
@@ -778,6 +781,32 @@ class StereoSlamBatch:
     def prune_voxel_maps(self, seqs=None, **kw):
         """submit_prune + wait"""
         job = self.submit_prune(seqs, **kw)
+        self.wait()
+        return job
+
+    def submit_carve(self, margin, seqs=None, near=0.01, ring=1, max_last=0xFFFFFFFF, drop_flags=0, keep=None, lr_check=None, step=4, win=0,
+                     search_x=0, search_y=0, min_disparity=0.0, max_depth=0.0, max_mean_cost=0.0, sgm=None):
+        """svo_submit_carve_voxel_maps: queue a carve of the voxel maps of the slots `seqs` (None: all) behind what was
+        submitted so far; nothing is waited for. An entry leaves when the dense depth of the slot's current frame (the
+        occluder of export_ar's occlusion: submit_cloud's step, win, search_x, search_y, the filter, lr_check, sgm, in the
+        camera frame) measures a surface more than `margin` behind it along its ray, in its lattice cell and, with
+        ring = 1, in every neighbour of the cell; entries nearer than `near`, fused after stamp `max_last` or without
+        complete evidence stay. keep: a dict of min_count, min_stamp, radius (in voxels) and center ("pose" or xyz)
+        for a keep rule of the prune applied with it; None: none. Returns a Carve, valid after its wait() (or the
+        ctx's)."""
+        sgm = hip_lib.sgm_consumer(sgm, lr_check, "submit_carve")
+        style = hip_lib.cloud_style(step, win, search_x, search_y, "camera", "compact", min_disparity, max_depth, max_mean_cost)
+        keep = dict(keep or {})
+        center = keep.pop("center", "pose")
+        radius = keep.pop("radius", None)
+        rule = None if not keep and radius is None else hip_lib.voxel_keep(radius=-1 if radius is None else int(radius), **keep)
+        params, check = sgm if sgm[0] is not None else (None, self._stereo_check(lr_check))
+        return Carve(self, seqs, style, check, params, hip_lib.voxel_carve(margin, near, ring, max_last, drop_flags), rule,
+                     center if radius is not None else None).submit()
+
+    def carve_voxel_maps(self, margin, seqs=None, **kw):
+        """submit_carve + wait"""
+        job = self.submit_carve(margin, seqs, **kw)
         self.wait()
         return job
 
@@ -1001,6 +1030,11 @@ class StereoSlam(StereoSlamBatch):
         """prune_voxel_maps of the one slot (min_count, min_stamp, radius in metres, center="pose" or xyz): its record
         of hip_lib.PRUNE_INFO_DTYPE"""
         return self.prune_voxel_maps([0], **kw).info[0].copy()
+
+    def carve_voxel_map(self, margin, **kw):
+        """carve_voxel_maps of the one slot (margin, near, ring, max_last, keep, step, sgm, lr_check, ...): its record of
+        hip_lib.CARVE_INFO_DTYPE"""
+        return self.carve_voxel_maps(margin, [0], **kw).info[0].copy()
 
     def get_voxel_map(self, **kw):
         """the slot's voxel map as a numpy array of hip_lib.MAP_POINT_DTYPE in key order (export_voxel_maps of the one

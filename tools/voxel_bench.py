@@ -26,6 +26,15 @@ Prints one JSON line.
              same map before: a count pass (svo_voxel_extract with points == NULL), svo_voxel_extract of the kept half,
              and the host path a prune replaces: that half extracted and downloaded, svo_voxel_clear, the records
              uploaded and fused again (wall clock; it loses the counts and stamps, which a prune keeps).
+  --carve    instead of all that (writes profiles/voxel_carve_bench.json): svo_voxel_carve of a map of
+             1 << 20 and 1 << 24 entries at 0.75 load (distinct voxels on a slab that a 752 x 480 camera sees whole) under
+             occluder lattices of step 1 and 4: a carve that removes nothing (the occluder stands in front of every
+             entry), a carve that removes about half (the right half of the lattice stands behind every entry), and
+             beside them svo_voxel_prune of the same map keeping all and keeping half (by stamp), and svo_voxel_extract
+             of the whole map, and the two carves again in the other form of the kernels (SVO_VOXEL_CARVE_REEVALUATE=1: no ballot
+             words, the stage pass evaluates the rule again). The prune legs are this library's: its plain prune kernels have the
+             parent's registers, LDS and occupancy (profiles/voxel_carve_registers.txt). The map is restored from a copy ahead of every timed call, untimed; the legs alternate in
+             one process, median of `--repeats` each.
 """
 import argparse
 import datetime
@@ -241,8 +250,80 @@ def prune_leg(args, h):
     return out
 
 
+def reeval(fn):
+    """fn() under the other form of the carve's kernels: no ballot words, the stage pass evaluates the rule again"""
+    os.environ["SVO_VOXEL_CARVE_REEVALUATE"] = "1"
+    try:
+        return fn()
+    finally:
+        del os.environ["SVO_VOXEL_CARVE_REEVALUATE"]
+
+
+def carve_leg(args, h):
+    import ctypes as C
+    W, H, depth = 752, 480, 20.0
+    out = []
+    for log2 in args.carve_log2:
+        n = int((1 << log2) * 0.75)
+        idx = np.arange(n)
+        xyz = (np.stack([idx % 512, idx // 512 % 512, idx // (512 * 512)], 1) + 0.5) * args.voxel
+        dev = torch.from_numpy(VR.records(xyz, (1, 2, 3)).view(np.uint8).reshape(-1, 16)).cuda()
+        half = n // 2
+        m = h.voxel_new(hip_lib.voxel_params(args.voxel, log2))
+        h.voxel_fuse([(dev[:half], 0, 1), (dev[half:], 0, 2)], [m])
+        assert h.voxel_info(m)["n_voxels"] == n
+        pristine = m[0].clone()
+        restore = lambda: m[0].copy_(pristine)
+        side = 512 * args.voxel                                   # the slab is side x side, `depth` in front of the eye
+        view = (C.c_float * 12)(1, 0, 0, -side / 2, 0, 1, 0, -side / 2, 0, 0, 1, depth)
+        cam = hip_lib.ArCamera(view, W * depth / side, H * depth / side, W / 2, H / 2)
+        rule = hip_lib.voxel_carve(args.voxel, near=0.01, ring=1)
+        pts = torch.empty((n, 16), dtype=torch.uint8, device="cuda")
+        for step in (1, 4):
+            cols, rows = W // step, H // step
+            z = np.ones((rows, cols), np.float32)
+            occ_none = torch.from_numpy(VR.records(np.stack([np.zeros_like(z), np.zeros_like(z), z], -1).reshape(-1, 3)).view(np.uint8).reshape(-1, 16)).cuda()
+            z[:, cols // 2:] = 1000.0
+            occ_half = torch.from_numpy(VR.records(np.stack([np.zeros_like(z), np.zeros_like(z), z], -1).reshape(-1, 3)).view(np.uint8).reshape(-1, 16)).cuda()
+            seen = {}
+            legs = {"carve_none": lambda: seen.__setitem__("none", h.voxel_carve(m, cam, W, H, (occ_none, cols, rows, step), rule)),
+                    "carve_half": lambda: seen.__setitem__("half", h.voxel_carve(m, cam, W, H, (occ_half, cols, rows, step), rule)),
+                    "carve_none_reeval": lambda: reeval(lambda: h.voxel_carve(m, cam, W, H, (occ_none, cols, rows, step), rule)),
+                    "carve_half_reeval": lambda: seen.__setitem__("half_reeval", reeval(lambda: h.voxel_carve(m, cam, W, H, (occ_half, cols, rows, step), rule))),
+                    "prune_all": lambda: h.voxel_prune(m, hip_lib.voxel_keep(min_stamp=1)),
+                    "prune_half": lambda: h.voxel_prune(m, hip_lib.voxel_keep(min_stamp=2)),
+                    "extract_all": lambda: h.voxel_extract(m, points=pts, capacity=n)}
+            ms = {k: [] for k in legs}
+            for _ in range(args.repeats + 1):                     # the first round warms up
+                for name, fn in legs.items():
+                    restore()
+                    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    a.record()
+                    fn()
+                    b.record()
+                    torch.cuda.synchronize()
+                    ms[name].append(a.elapsed_time(b))
+            assert seen["none"]["n_carved"] == 0 and seen["none"]["n_tested"] == n and seen["none"]["n_kept"] == n, seen
+            assert seen["half_reeval"] == seen["half"], seen
+            row = {"log2_capacity": log2, "voxels": n, "step": step, "lattice": [cols, rows], "carve_half_result": seen["half"]}
+            for name in legs:
+                row[name + "_ms"], row[name + "_all_ms"] = statistics.median(ms[name][1:]), ms[name][1:]
+            row["reeval_over_ballot_none"] = row["carve_none_reeval_ms"] / row["carve_none_ms"]
+            row["reeval_over_ballot_half"] = row["carve_half_reeval_ms"] / row["carve_half_ms"]
+            row["carve_none_over_prune_all"] = row["carve_none_ms"] / row["prune_all_ms"]
+            row["carve_half_over_prune_half"] = row["carve_half_ms"] / row["prune_half_ms"]
+            row["carve_half_over_prune_half_plus_extract"] = row["carve_half_ms"] / (row["prune_half_ms"] + row["extract_all_ms"])
+            out.append(row)
+            print(json.dumps({k: v for k, v in row.items() if not k.endswith("all_ms")}), file=sys.stderr, flush=True)
+        del m, pristine, pts, dev
+        torch.cuda.empty_cache()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--carve", action="store_true", help="only the carve measurement (profiles/voxel_carve_bench.json)")
+    ap.add_argument("--carve-log2", type=int, nargs="+", default=[20, 24])
     ap.add_argument("--prune", action="store_true", help="only the prune measurement (profiles/voxel_prune_bench.json)")
     ap.add_argument("--prune-log2", type=int, nargs="+", default=[16, 20, 24])
     ap.add_argument("--sgm", metavar="P1,P2[,CAP]", default=None, help="only the fuse job under SGM against winner-takes-all (profiles/sgm_consumers_bench.json)")
@@ -260,6 +341,14 @@ def main():
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     device = torch.device("cuda", 0)
+    if args.carve:
+        out = {"tool": "tools/voxel_bench.py", "date": datetime.date.today().isoformat(), "command": " ".join(sys.argv),
+               "device": torch.cuda.get_device_name(0), "voxel": args.voxel, "repeats": args.repeats, "view": [752, 480],
+               "carve": carve_leg(args, hip_lib.Handle(0, 1024))}
+        with open(args.out or os.path.join(ROOT, "profiles", "voxel_carve_bench.json"), "w") as fh:
+            json.dump(out, fh, indent=1)
+        print(json.dumps(out))
+        return
     if args.prune:
         out = {"tool": "tools/voxel_bench.py", "date": datetime.date.today().isoformat(), "command": " ".join(sys.argv),
                "device": torch.cuda.get_device_name(0), "voxel": args.voxel, "repeats": args.repeats,
