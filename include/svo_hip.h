@@ -1829,7 +1829,7 @@ int svo_get_voxel_map_info(svo_ctx *ctx, int seq, svo_voxel_map_info *info);
  *   SVO_FUSE_NO_MAP  the slot has no map (this comes first)
  *   SVO_FUSE_FULL    n_voxels + points_per_slot > capacity - capacity / 4 (the load bound, on the bound, checked before
  *                    any launch with the ctx's host mirror of n_voxels): nothing is fused, the ctx does not fail. The
- *                    caller exports the map and sets a larger one.
+ *                    caller moves the map into a larger table (svo_ctx_resize_voxel_maps, "voxel entries").
  * The mirror of a map's counters is refreshed from the headers the job copies back anyway.
  * Rejected with SVO_ERR_INVALID and nothing queued: everything svo_submit_export_cloud_checked rejects of what, seqs,
  * style and check; style->frame != SVO_CLOUD_WORLD; style->layout != 0; a NULL info.
@@ -2187,6 +2187,150 @@ int svo_submit_carve_voxel_maps(svo_ctx *ctx, const int *seqs, int n, const svo_
 int svo_carve_voxel_maps(svo_ctx *ctx, const int *seqs, int n, const svo_cloud_style *cloud, const svo_sgm_params *sgm,
                          const svo_stereo_check *check, const svo_voxel_carve_rule *carve, const svo_voxel_keep *keep,
                          int center_mode, const float *centers, svo_carve_info *info);   /* submit + wait */
+
+/* ---- voxel entries: the raw entries of a voxel map packed out, merged in, moved to a table of another size ------------
+ * An entry of "voxel maps" is a key and eight integer accumulators that only ever take commutative updates (add modulo
+ * 2^32, max), so the accumulators are a complete, exact and order-free description of everything that was fused.
+ * svo_voxel_extract gives the means and throws the counts, the sums and the stamps away; re-fusing the means gives
+ * every voxel count 1. Here the entries themselves leave and enter a map: merging two maps entry by entry gives, to
+ * the bit, the map that fusing the union of their records would have given, so a map can be saved, loaded, joined
+ * with another and moved into a larger or smaller table without losing anything.
+ *
+ * Record. svo_voxel_entry: 40 bytes, 8-byte aligned: the key and acc[8] = count, sx, sy, sz, sr, sg, sb, last, exactly
+ * the key and the accumulators of "voxel maps".
+ *
+ * Pack. A map and a svo_voxel_filter, by the kept rule of the extraction: count >= max(1, min_count) and
+ * last >= min_stamp. The kept entries leave in ascending key order, each as one record with its eight accumulators
+ * verbatim. Keys are unique, so the bytes are the same in every run, wherever the entries lay in their probe chains.
+ *
+ * Merge. A span of n records is offered to a map. A record is SKIPPED if bit 63 of its key is set (the empty key ~0
+ * is one such), or its count is 0: it counts in n_skipped and nowhere else. Otherwise the entry of its key is found
+ * or claimed (n_voxels += 1 when claimed) and, with ' for the record's values,
+ *   count += count';  sx += sx', sy += sy', sz += sz', sr += sr', sg += sg', sb += sb'  (modulo 2^32);
+ *   last = max(last, last')
+ * and the header's n_fused += count' (a 64-bit sum); n_outside and overflow are untouched (overflow counts, as for a
+ * fuse, records whose probe visited every entry, and the load bound keeps it 0). Keys may repeat inside a span and
+ * across the spans of a call: the result is the same as if every underlying record had been fused.
+ *
+ * Voxel edge. A span carries the voxel edge its keys were made with. It must equal the map's `voxel` bit for bit,
+ * otherwise the call is SVO_ERR_INVALID and nothing is written. Re-voxelising is not exact and is not offered.
+ *
+ * Load bound: that of the fuse, on the bound, checked on the host before any launch:
+ *   n_voxels + (records of all spans of the call into that map) <= capacity - capacity / 4
+ * (skipped records count). On failure the call is SVO_ERR_CAPACITY with nothing written.
+ *
+ * Rehash (resize). The entries of one map go into a cleared map with another log2_capacity and the same voxel and
+ * drop_flags. Afterwards the new map holds exactly the old entries with their accumulators, the old n_voxels and the
+ * three cumulative counters (n_fused, n_outside, overflow) of the old header. Placement follows the rule of "voxel
+ * maps" (home by the new capacity, linear probing), so a fuse that follows finds every entry. The rehash is admitted
+ * only if n_voxels <= capacity' - capacity' / 4. The old map is only read.
+ *
+ * How it runs (voxel.hip): the pack is the extraction's count, scan, pairs and sort with another gather (one lane per
+ * kept entry, two 16-byte loads, one 40-byte record). The merge is one launch for many spans into many maps, cut into
+ * tiles of 256 records like the fuse, one lane per record: the probe from the key's home, the claim by a 64-bit
+ * compare-and-swap of ~0, then eight integer atomics, always atomics (another lane with the same key may find a
+ * claimed key before the claimer's first add). The rehash is one lane per entry of the old table with the prune's
+ * reinsert (keys are unique and the new table is private until the call returns: plain stores), and a one-lane launch
+ * that copies the counters. Probe loops are bounded by the capacity; nothing spins or waits. */
+typedef struct svo_voxel_entry {    /* 40 bytes */
+    uint64_t key;                   /* ix << 42 | iy << 21 | iz                                             */
+    uint32_t acc[8];                /* count, sx, sy, sz, sr, sg, sb, last                                  */
+} svo_voxel_entry;
+
+typedef struct svo_voxel_entry_span {   /* 24 bytes */
+    const svo_voxel_entry *entries; /* device, 8-byte aligned (n = 0: not read)                             */
+    int64_t  n;                     /* >= 0 records                                                         */
+    int32_t  map;                   /* index into the call's maps                                           */
+    float    voxel;                 /* the voxel edge the keys were made with: the map's, bit for bit       */
+} svo_voxel_entry_span;
+
+typedef struct svo_voxel_merge_result { /* 32 bytes, one per map of the call; exact integers summed on the device */
+    int64_t n_offered;              /* records of the call's spans into this map                            */
+    int64_t n_merged;               /* of them added to an entry                                            */
+    int64_t n_skipped;              /* of them skipped                                                      */
+    int64_t n_claimed;              /* entries claimed: what n_voxels grew by                               */
+} svo_voxel_merge_result;
+
+/* Stage entries, complete on return.
+ * svo_voxel_pack follows svo_voxel_extract exactly: entries[0, *n) (device, 8-byte aligned) receive the kept entries
+ * and nothing else is written; filter == NULL keeps every entry; entries == NULL only counts; SVO_ERR_CAPACITY if the
+ * kept count exceeds `capacity`: *n is set and nothing is written. It rejects what svo_voxel_extract rejects, and the
+ * workspace is the extraction's. */
+int svo_voxel_pack(svo_handle *h, const svo_voxel_map *map, const svo_voxel_filter *filter, svo_voxel_entry *entries,
+                   int64_t capacity, int64_t *n);
+/* n_spans spans into n_maps maps in one launch (host arrays). SVO_ERR_INVALID with nothing written: what
+ * svo_voxel_fuse rejects (entries need 8-byte alignment only), and a span whose voxel is not its map's bit for bit.
+ * SVO_ERR_CAPACITY with nothing written if the load bound of any named map fails. results: n_maps records, host
+ * memory, may be NULL. */
+int svo_voxel_merge(svo_handle *h, int n_spans, const svo_voxel_entry_span *spans, int n_maps, const svo_voxel_map *maps,
+                    svo_voxel_merge_result *results);
+/* dst (device, 16-byte aligned, svo_voxel_map_bytes(dst_log2_capacity) bytes, need not be cleared) becomes the map of
+ * src's entries with params (src's voxel, dst_log2_capacity, src's drop_flags). SVO_ERR_INVALID with nothing written:
+ * what svo_voxel_extract rejects of src, a dst that is NULL, not 16-byte aligned or overlaps src's bytes (dst ==
+ * src->data among them), a dst_log2_capacity outside 6 .. 26. SVO_ERR_CAPACITY by the admission rule: dst is then
+ * untouched. */
+int svo_voxel_rehash(svo_handle *h, const svo_voxel_map *src, void *dst, int dst_log2_capacity);
+
+/* Voxel entries inside a ctx: the maps of the slots saved, loaded and resized. svo_submit_save, svo_submit_load and
+ * snapshots still leave maps alone ("What a map is not"): a map travels by the three entries below.
+ *
+ * svo_submit_save_voxel_maps is svo_submit_export_voxel_maps with svo_voxel_entry records in place of points: the
+ * same svo_voxel_region per named slot (first_point and point_capacity count entry records), the same shared filter
+ * and region.min_stamp, the same 64-byte svo_voxel_segment per slot in host memory (n_points counts entries), the
+ * same statuses SVO_VOXEL_OK / NO_MAP / TOO_SMALL decided on the mirror before any launch, records in host or device
+ * memory (mem): exactly entries[first_point, first_point + n_points) are written, in key order. It is queued behind
+ * what was submitted so far and only the groups that own a named slot get work. Rejected with SVO_ERR_INVALID as the
+ * export, with `entries` 8-byte aligned. Memory: the export's blocks, in host mode 40 bytes per kept entry. */
+typedef struct svo_voxel_entry_dst {
+    svo_voxel_segment *segments;    /* HOST memory always, >= n entries                                     */
+    svo_voxel_entry   *entries;     /* host or device (mem), 8-byte aligned; NULL: every point_capacity is 0 */
+} svo_voxel_entry_dst;
+
+int svo_submit_save_voxel_maps(svo_ctx *ctx, const int *seqs, int n, const svo_voxel_region *regions,
+                               const svo_voxel_filter *filter, const svo_voxel_entry_dst *dst, int mem);
+int svo_save_voxel_maps(svo_ctx *ctx, const int *seqs, int n, const svo_voxel_region *regions,
+                        const svo_voxel_filter *filter, const svo_voxel_entry_dst *dst, int mem);   /* submit + wait */
+
+/* svo_submit_load_voxel_maps offers spans[i] (entries, n and voxel; `map` is not read) to the map of slot seqs[i]. The
+ * entries lie in host or device memory (mem) and stay alive and unchanged until the wait; host entries are staged
+ * through a block of the group. mode: SVO_VOXEL_LOAD_REPLACE clears the map first, counters to 0; SVO_VOXEL_LOAD_MERGE
+ * does not. One merge launch per group. info[i] belongs to seqs[i], is host memory and is valid at svo_wait:
+ *   SVO_VOXEL_LOADED       merged: the four counts of svo_voxel_merge_result; n_voxels: the map's entries afterwards,
+ *                          from the header the job copies back, which is the new mirror
+ *   SVO_VOXEL_LOAD_NO_MAP  the slot has no map (this comes first)
+ *   SVO_VOXEL_LOAD_FULL    the load bound fails on the mirror (n_voxels taken as 0 for a replace): nothing changes, a
+ *                          replace does not clear, the ctx does not fail; n_voxels: the mirror's
+ * A fuse, prune or carve queued right behind a load is admitted on the loaded count. Rejected with SVO_ERR_INVALID
+ * and nothing queued: a span svo_voxel_merge rejects, an unknown mode or mem, a NULL info, and a span whose voxel is
+ * not bit for bit the edge of the slot's map as the ctx knows it then (maps change only through setters that wait
+ * for the queues; a slot without a map is not checked). Memory, per group, made on first use: the fuse job's table
+ * block (with 32 bytes more per slot) and in host mode 40 bytes per record of the job. */
+enum { SVO_VOXEL_LOAD_REPLACE = 0, SVO_VOXEL_LOAD_MERGE = 1 };
+enum { SVO_VOXEL_LOADED = 0, SVO_VOXEL_LOAD_NO_MAP = 1, SVO_VOXEL_LOAD_FULL = 2 };
+
+typedef struct svo_voxel_load_info { /* 64 bytes, host, one per named slot */
+    int32_t seq, run;               /* slot and ordinal of its run                                          */
+    int32_t status;                 /* SVO_VOXEL_LOAD*                                                      */
+    int32_t _pad;
+    int64_t n_offered, n_merged, n_skipped, n_claimed;   /* as svo_voxel_merge_result; not loaded: 0        */
+    int64_t n_voxels;               /* of the map after the job (NO_MAP: 0)                                 */
+    int64_t _pad2;
+} svo_voxel_load_info;
+
+int svo_submit_load_voxel_maps(svo_ctx *ctx, const int *seqs, int n, const svo_voxel_entry_span *spans, int mode, int mem,
+                               svo_voxel_load_info *info);
+int svo_load_voxel_maps(svo_ctx *ctx, const int *seqs, int n, const svo_voxel_entry_span *spans, int mode, int mem,
+                        svo_voxel_load_info *info);   /* submit + wait */
+
+/* svo_ctx_resize_voxel_maps is a setter like svo_ctx_set_voxel_maps: it waits for the queues. Every named slot with a
+ * map (seqs == NULL: every slot; slots without a map are skipped) gets a map of 1 << log2_capacity entries (10 .. 26)
+ * with the same voxel and drop_flags that holds the old map's entries and counters (the rehash above); the old map
+ * is released and svo_memory.device_bytes follows. Shrinking is allowed where it fits. If the entries of any named
+ * slot do not fit the new capacity (the mirror's n_voxels > capacity' - capacity' / 4) the call is SVO_ERR_CAPACITY
+ * before anything is allocated or changed. Then the new map of every slot that moves is allocated before any map is
+ * moved: an allocation that fails gives the others back and leaves every map as it was too. Until the moves are done
+ * the old and the new maps of the named slots exist side by side. */
+int svo_ctx_resize_voxel_maps(svo_ctx *ctx, const int *seqs, int n, int log2_capacity);
 
 /* ---- snapshots: the sequence state of a slot saved, loaded, moved between ctxs ------------
  * The reference has no checkpoint or resume (a StereoSlam lives and dies with its process). A snapshot is

@@ -1,5 +1,5 @@
-// svo_capi_voxel.hip — the stage entries of the voxel maps (include/svo_hip.h, "voxel maps", "voxel prune", "voxel carve"): clear, fuse,
-// info, extract, prune and carve on maps in the caller's device memory, complete on return. Every check is made on the host before any
+// svo_capi_voxel.hip — the stage entries of the voxel maps (include/svo_hip.h, "voxel maps", "voxel prune", "voxel carve", "voxel
+// entries"): clear, fuse, info, extract, prune, carve, pack, merge and rehash on maps in the caller's device memory, complete on return. Every check is made on the host before any
 // launch (the params, the alignment, the header of each named map, the load bound), with the arithmetic of
 // svo_voxel_plan.hpp; the kernels are voxel.hip's.
 #include <hip/hip_runtime.h>
@@ -125,19 +125,24 @@ extern "C" int svo_voxel_fuse(svo_handle* h, int n_spans, const svo_voxel_span* 
     return finish_launch(h);
 }
 
-extern "C" int svo_voxel_extract(svo_handle* h, const svo_voxel_map* map, const svo_voxel_filter* filter, svo_map_point* points,
-                                 int64_t capacity, int64_t* n_points) {
-    CHECK_H(h);
-    if (const int rc = check_map(map, "svo_voxel_extract", 0)) return rc;
-    if (!n_points) return svo_set_error(SVO_ERR_INVALID, "svo_voxel_extract: no n_points");
-    if (filter && (filter->_reserved[0] != 0 || filter->_reserved[1] != 0)) return svo_set_error(SVO_ERR_INVALID, "svo_voxel_extract: a _reserved is not 0");
-    if (points && (((uintptr_t)points & 15) || capacity < 0)) return svo_set_error(SVO_ERR_INVALID, "svo_voxel_extract: points not 16-byte aligned, or capacity < 0");
+// svo_voxel_extract and svo_voxel_pack: the kept entries of a map in key order as records out[0, *n_out), by the
+// launcher that writes that kind of record (launch_voxel_extract, launch_voxel_pack). The checks, the count pass, the
+// answer on a capacity too small and the staging are one code; `records`, `align` and `count`: what the entry calls its
+// records and its count, and the alignment the records need.
+template <class Record, class Launch>
+static int voxel_read_out(svo_handle* h, const char* who, const svo_voxel_map* map, const svo_voxel_filter* filter, Record* out, const char* records,
+                          uintptr_t align, const char* count, int64_t capacity, int64_t* n_out, Launch launch) {
+    if (const int rc = check_map(map, who, 0)) return rc;
+    if (!n_out) return svo_set_error(SVO_ERR_INVALID, "%s: no %s", who, count);
+    if (filter && (filter->_reserved[0] != 0 || filter->_reserved[1] != 0)) return svo_set_error(SVO_ERR_INVALID, "%s: a _reserved is not 0", who);
+    if (out && (((uintptr_t)out & (align - 1)) || capacity < 0))
+        return svo_set_error(SVO_ERR_INVALID, "%s: %s not %d-byte aligned, or capacity < 0", who, records, (int)align);
     const VoxelFilterDev f{filter ? std::max<uint32_t>(1u, filter->min_count) : 1u, filter ? filter->min_stamp : 0u};
     const VoxelMapDev mp = map_dev(map->data, map->params);
     VoxelHeader hd;
     HIP_TRY(hipMemcpyAsync(&hd, map->data, sizeof(hd), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
-    if (!voxel_header_matches(hd, map->params)) return svo_set_error(SVO_ERR_INVALID, "svo_voxel_extract: the map was not cleared with these params");
+    if (!voxel_header_matches(hd, map->params)) return svo_set_error(SVO_ERR_INVALID, "%s: the map was not cleared with these params", who);
     if (const int rc = h->voxel_ws.reserve(voxel_offsets_bytes(mp.log2_capacity), h->stream)) return rc;
     int32_t* tile_offsets = reinterpret_cast<int32_t*>(h->voxel_ws.ptr.get());
     launch_voxel_count(mp, f, tile_offsets, h->stream);
@@ -145,19 +150,125 @@ extern "C" int svo_voxel_extract(svo_handle* h, const svo_voxel_map* map, const 
     int32_t kept = 0;
     HIP_TRY(hipMemcpyAsync(&kept, tile_offsets + voxel_map_tiles(mp.log2_capacity), sizeof(kept), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
-    *n_points = kept;
-    if (!points) return SVO_OK;
-    if (!voxel_extract_fits(kept, capacity)) return svo_set_error(SVO_ERR_CAPACITY, "svo_voxel_extract: %d voxels kept, capacity %lld", kept, (long long)capacity);
+    *n_out = kept;
+    if (!out) return SVO_OK;
+    if (!voxel_extract_fits(kept, capacity)) return svo_set_error(SVO_ERR_CAPACITY, "%s: %d voxels kept, capacity %lld", who, kept, (long long)capacity);
     if (kept == 0) return SVO_OK;
     size_t temp_bytes = 0;
     if (const int rc = voxel_sort_temp_bytes((size_t)kept, &temp_bytes)) return rc;
     const VoxelExtractPlan plan = voxel_extract_plan((uint64_t)kept, temp_bytes);
     if (const int rc = h->voxel_sort_ws.reserve(plan.bytes, h->stream)) return rc;
     uint8_t* ws = h->voxel_sort_ws.ptr.get();
-    if (const int rc = launch_voxel_extract(mp, f, tile_offsets, (size_t)kept, reinterpret_cast<uint64_t*>(ws + plan.keys_in),
-                                            reinterpret_cast<uint64_t*>(ws + plan.keys_out), reinterpret_cast<uint32_t*>(ws + plan.index_in),
-                                            reinterpret_cast<uint32_t*>(ws + plan.index_out), ws + plan.sort_temp, temp_bytes, points, h->stream))
+    if (const int rc = launch(mp, f, tile_offsets, (size_t)kept, reinterpret_cast<uint64_t*>(ws + plan.keys_in),
+                              reinterpret_cast<uint64_t*>(ws + plan.keys_out), reinterpret_cast<uint32_t*>(ws + plan.index_in),
+                              reinterpret_cast<uint32_t*>(ws + plan.index_out), ws + plan.sort_temp, temp_bytes, out, h->stream))
         return rc;
+    return finish_launch(h);
+}
+
+extern "C" int svo_voxel_extract(svo_handle* h, const svo_voxel_map* map, const svo_voxel_filter* filter, svo_map_point* points,
+                                 int64_t capacity, int64_t* n_points) {
+    CHECK_H(h);
+    return voxel_read_out(h, "svo_voxel_extract", map, filter, points, "points", 16, "n_points", capacity, n_points, launch_voxel_extract);
+}
+
+extern "C" int svo_voxel_pack(svo_handle* h, const svo_voxel_map* map, const svo_voxel_filter* filter, svo_voxel_entry* entries,
+                              int64_t capacity, int64_t* n) {
+    CHECK_H(h);
+    return voxel_read_out(h, "svo_voxel_pack", map, filter, entries, "entries", 8, "n", capacity, n, launch_voxel_pack);
+}
+
+extern "C" int svo_voxel_merge(svo_handle* h, int n_spans, const svo_voxel_entry_span* spans, int n_maps, const svo_voxel_map* maps,
+                               svo_voxel_merge_result* results) {
+    CHECK_H(h);
+    if (n_spans < 0 || n_maps < 0 || (n_spans > 0 && !spans) || (n_maps > 0 && !maps))
+        return svo_set_error(SVO_ERR_INVALID, "svo_voxel_merge: bad arguments");
+    std::vector<VoxelMapDev> dmaps((size_t)n_maps);
+    std::vector<const void*> seen;
+    for (int i = 0; i < n_maps; i++) {
+        if (const int rc = check_map(&maps[i], "svo_voxel_merge", i)) return rc;
+        dmaps[(size_t)i] = map_dev(maps[i].data, maps[i].params);
+        seen.push_back(maps[i].data);
+    }
+    std::sort(seen.begin(), seen.end());
+    if (std::adjacent_find(seen.begin(), seen.end()) != seen.end()) return svo_set_error(SVO_ERR_INVALID, "svo_voxel_merge: a map is named twice");
+    std::vector<VoxelEntrySpanDev> dspans;
+    std::vector<std::vector<int64_t>> counts((size_t)n_maps);   // the spans' record counts per map, for the load bound
+    int64_t tiles = 0;
+    for (int i = 0; i < n_spans; i++) {
+        const svo_voxel_entry_span& s = spans[i];
+        if (!voxel_entry_span_ok((uintptr_t)s.entries, s.n))
+            return svo_set_error(SVO_ERR_INVALID, "svo_voxel_merge: span %d: n < 0, or entries NULL or not 8-byte aligned", i);
+        if (s.map < 0 || s.map >= n_maps) return svo_set_error(SVO_ERR_INVALID, "svo_voxel_merge: span %d names map %d of %d", i, s.map, n_maps);
+        if (!voxel_edge_same(s.voxel, maps[s.map].params.voxel))
+            return svo_set_error(SVO_ERR_INVALID, "svo_voxel_merge: span %d: its keys were made with voxel %.9g, map %d has %.9g", i, (double)s.voxel, s.map,
+                                 (double)maps[s.map].params.voxel);
+        counts[(size_t)s.map].push_back(s.n);
+        if (s.n == 0) continue;
+        dspans.push_back(VoxelEntrySpanDev{s.entries, s.n, tiles, s.map, 0});
+        tiles += voxel_entry_span_tiles(s.n);
+        if (tiles > INT32_MAX) return svo_set_error(SVO_ERR_CAPACITY, "svo_voxel_merge: too many records for one call");
+    }
+    if (n_maps == 0) return SVO_OK;
+    // the tables of the call: the maps, their headers as the device holds them now, the counts, the spans
+    const size_t maps_bytes = voxel_up256(sizeof(VoxelMapDev) * dmaps.size()), heads_bytes = voxel_up256(sizeof(VoxelHeader) * dmaps.size());
+    const size_t counts_bytes = voxel_up256(sizeof(VoxelMergeCounts) * dmaps.size());
+    if (const int rc = h->voxel_ws.reserve(maps_bytes + heads_bytes + counts_bytes + voxel_up256(sizeof(VoxelEntrySpanDev) * dspans.size()), h->stream))
+        return rc;
+    uint8_t* ws = h->voxel_ws.ptr.get();
+    VoxelMapDev* d_maps = reinterpret_cast<VoxelMapDev*>(ws);
+    VoxelHeader* d_heads = reinterpret_cast<VoxelHeader*>(ws + maps_bytes);
+    VoxelMergeCounts* d_counts = reinterpret_cast<VoxelMergeCounts*>(ws + maps_bytes + heads_bytes);
+    VoxelEntrySpanDev* d_spans = reinterpret_cast<VoxelEntrySpanDev*>(ws + maps_bytes + heads_bytes + counts_bytes);
+    std::vector<VoxelHeader> heads(dmaps.size());
+    HIP_TRY(hipMemcpyAsync(d_maps, dmaps.data(), sizeof(VoxelMapDev) * dmaps.size(), hipMemcpyHostToDevice, h->stream));
+    launch_voxel_headers(d_maps, n_maps, d_heads, h->stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(heads.data(), d_heads, sizeof(VoxelHeader) * heads.size(), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    for (int i = 0; i < n_maps; i++)
+        if (!voxel_header_matches(heads[(size_t)i], maps[i].params))
+            return svo_set_error(SVO_ERR_INVALID, "svo_voxel_merge: map %d was not cleared with these params", i);
+    for (int i = 0; i < n_maps; i++)
+        if (!voxel_merge_load_ok(heads[(size_t)i].n_voxels, counts[(size_t)i].data(), (int)counts[(size_t)i].size(), maps[i].params.log2_capacity))
+            return svo_set_error(SVO_ERR_CAPACITY, "svo_voxel_merge: map %d: %llu voxels and the call's records exceed %llu (the load bound)", i,
+                                 heads[(size_t)i].n_voxels, (unsigned long long)voxel_load_limit(maps[i].params.log2_capacity));
+    if (dspans.empty()) {
+        if (results) std::fill(results, results + n_maps, svo_voxel_merge_result{0, 0, 0, 0});
+        return SVO_OK;
+    }
+    HIP_TRY(hipMemcpyAsync(d_spans, dspans.data(), sizeof(VoxelEntrySpanDev) * dspans.size(), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemsetAsync(d_counts, 0, sizeof(VoxelMergeCounts) * dmaps.size(), h->stream));
+    launch_voxel_merge(d_spans, (int)dspans.size(), tiles, d_maps, d_counts, h->stream);
+    HIP_TRY(hipGetLastError());
+    std::vector<VoxelMergeCounts> got(dmaps.size());
+    HIP_TRY(hipMemcpyAsync(got.data(), d_counts, sizeof(VoxelMergeCounts) * got.size(), hipMemcpyDeviceToHost, h->stream));
+    if (const int rc = finish_launch(h)) return rc;
+    if (results)
+        for (int i = 0; i < n_maps; i++)
+            results[i] = svo_voxel_merge_result{(int64_t)got[(size_t)i].n_offered, (int64_t)got[(size_t)i].n_merged, (int64_t)got[(size_t)i].n_skipped,
+                                                (int64_t)got[(size_t)i].n_claimed};
+    return SVO_OK;
+}
+
+extern "C" int svo_voxel_rehash(svo_handle* h, const svo_voxel_map* src, void* dst, int dst_log2_capacity) {
+    CHECK_H(h);
+    if (const int rc = check_map(src, "svo_voxel_rehash", 0)) return rc;
+    if (!voxel_log2_ok(dst_log2_capacity, false))
+        return svo_set_error(SVO_ERR_INVALID, "svo_voxel_rehash: dst_log2_capacity %d outside %d .. %d", dst_log2_capacity, VOXEL_LOG2_MIN, VOXEL_LOG2_MAX);
+    if (!dst || ((uintptr_t)dst & 15)) return svo_set_error(SVO_ERR_INVALID, "svo_voxel_rehash: dst is NULL or not 16-byte aligned");
+    if (voxel_ranges_overlap((uintptr_t)src->data, voxel_map_bytes(src->params.log2_capacity), (uintptr_t)dst, voxel_map_bytes(dst_log2_capacity)))
+        return svo_set_error(SVO_ERR_INVALID, "svo_voxel_rehash: dst shares bytes with the map it is made from");
+    VoxelHeader hd;
+    HIP_TRY(hipMemcpyAsync(&hd, src->data, sizeof(hd), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (!voxel_header_matches(hd, src->params)) return svo_set_error(SVO_ERR_INVALID, "svo_voxel_rehash: the map was not cleared with these params");
+    if (!voxel_rehash_ok(hd.n_voxels, dst_log2_capacity))
+        return svo_set_error(SVO_ERR_CAPACITY, "svo_voxel_rehash: %llu voxels exceed %llu, the load limit of log2_capacity %d", hd.n_voxels,
+                             (unsigned long long)voxel_load_limit(dst_log2_capacity), dst_log2_capacity);
+    svo_voxel_params to = src->params;
+    to.log2_capacity = dst_log2_capacity;
+    launch_voxel_rehash(map_dev(src->data, src->params), map_dev(dst, to), h->stream);
     return finish_launch(h);
 }
 

@@ -62,6 +62,13 @@ int run_job(svo_group* g, int seq0, const svo_ctx::VoxelPrune& j) {
     return grp_prune_voxel_maps(g, j.seqs.data(), j.seg.data(), (int)j.seqs.size(), seq0, &j.keep, j.center_mode, j.centers.data(), j.info);
 }
 
+int run_job(svo_group* g, int seq0, const svo_ctx::VoxelSave& j) {
+    return grp_save_voxel_maps(g, j.mem, j.seqs.data(), j.seg.data(), j.regions.data(), (int)j.seqs.size(), seq0, &j.filter, &j.dst);
+}
+int run_job(svo_group* g, int seq0, const svo_ctx::VoxelLoad& j) {
+    return grp_load_voxel_maps(g, j.mode, j.mem, j.seqs.data(), j.seg.data(), j.spans.data(), (int)j.seqs.size(), seq0, j.info);
+}
+
 void worker_run_job(svo_ctx::Worker& w, const svo_ctx::Job& job) {
     if (w.err != SVO_OK || w.ctx_failed->load()) return;   // after a failure (any group) the queues are dropped
     const int rc = std::visit([&w](const auto& j) { return run_job(w.g.get(), w.first, j); }, job);

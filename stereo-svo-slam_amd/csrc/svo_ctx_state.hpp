@@ -168,9 +168,22 @@ struct svo_ctx {
         svo_cloud_style cloud{};
         svo_carve_info* carve_info = nullptr;
     };
+    // the group's share of an svo_submit_save_voxel_maps, as VoxelExport with entry records
+    struct VoxelSave : SlotShare {
+        int mem = 0;
+        std::vector<svo_voxel_region> regions;
+        svo_voxel_filter filter{};
+        svo_voxel_entry_dst dst{};
+    };
+    // the group's share of an svo_submit_load_voxel_maps: the span of each slot; a slot fills the info of its named position
+    struct VoxelLoad : SlotShare {
+        int mode = 0, mem = 0;
+        std::vector<svo_voxel_entry_span> spans;
+        svo_voxel_load_info* info = nullptr;
+    };
     // one entry of a group's queue (the frame set first: a Job{} is one, with nothing allocated)
     using Job = std::variant<Frames, Restart, Trim, RigAssign, Export, MapExport, ViewExport, DisparityExport, CloudExport,
-                             SceneExport, ArExport, Save, Load, PoseUpdates, FuseClouds, VoxelExport, VoxelClear, VoxelPrune>;
+                             SceneExport, ArExport, Save, Load, PoseUpdates, FuseClouds, VoxelExport, VoxelClear, VoxelPrune, VoxelSave, VoxelLoad>;
     struct Worker {
         Group g;
         int first = 0, count = 0;

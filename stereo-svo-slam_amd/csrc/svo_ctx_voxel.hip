@@ -1,5 +1,6 @@
 // svo_ctx_voxel.hip — the voxel maps of the ctx's slots (svo_ctx_state.hpp): giving slots a map, its info, and the
-// queued jobs that fuse dense clouds into the maps, export them, clear them and prune them.
+// queued jobs that fuse dense clouds into the maps, export them, clear them and prune them; "voxel entries": the queued
+// jobs that save and load the maps' raw entries, and the setter that moves the maps into tables of another size.
 #include <functional>
 
 #include "svo_ctx_state.hpp"
@@ -70,28 +71,106 @@ extern "C" int svo_fuse_clouds(svo_ctx* c, int what, const int* seqs, int n, con
     return then_wait(c, svo_submit_fuse_clouds(c, what, seqs, n, style, check, stamp, info));
 }
 
-extern "C" int svo_submit_export_voxel_maps(svo_ctx* c, const int* seqs, int n, const svo_voxel_region* regions,
-                                            const svo_voxel_filter* filter, const svo_voxel_dst* dst, int mem) {
-    if (!c || !dst || !dst->segments || !mem_ok(mem) || !naming_ok(seqs, n))
-        return svo_set_error(SVO_ERR_INVALID, "svo_submit_export_voxel_maps: bad arguments (mem %d)", mem);
+// svo_submit_export_voxel_maps (J = VoxelExport: points, 16-byte aligned) and svo_submit_save_voxel_maps (J = VoxelSave:
+// entry records, 8-byte aligned): the same regions, filter and segments; `records` is dst's array of them
+template <typename J, typename Dst>
+static int submit_voxel_out(svo_ctx* c, const char* who, const int* seqs, int n, const svo_voxel_region* regions, const svo_voxel_filter* filter,
+                            const Dst* dst, const void* records, const char* what, uintptr_t align, int mem) {
+    if (!c || !dst || !dst->segments || !mem_ok(mem) || !naming_ok(seqs, n)) return svo_set_error(SVO_ERR_INVALID, "%s: bad arguments (mem %d)", who, mem);
     const NamedSlots slots = ctx_slots(c, seqs, n);
-    if (slots.n > 0 && !regions) return svo_set_error(SVO_ERR_INVALID, "svo_submit_export_voxel_maps: no regions");
+    if (slots.n > 0 && !regions) return svo_set_error(SVO_ERR_INVALID, "%s: no regions", who);
     const svo_voxel_filter f = filter ? *filter : svo_voxel_filter{0, 0, {0, 0}};
-    if (f._reserved[0] != 0 || f._reserved[1] != 0) return svo_set_error(SVO_ERR_INVALID, "svo_submit_export_voxel_maps: a _reserved is not 0");
-    if ((uintptr_t)dst->points & 15) return svo_set_error(SVO_ERR_INVALID, "svo_submit_export_voxel_maps: points is not 16-byte aligned");
-    const int rc = check_slots_and_items(c, "svo_submit_export_voxel_maps", slots, [&](int i) {
+    if (f._reserved[0] != 0 || f._reserved[1] != 0) return svo_set_error(SVO_ERR_INVALID, "%s: a _reserved is not 0", who);
+    if ((uintptr_t)records & (align - 1)) return svo_set_error(SVO_ERR_INVALID, "%s: %s is not %d-byte aligned", who, what, (int)align);
+    const int rc = check_slots_and_items(c, who, slots, [&](int i) {
         const svo_voxel_region& r = regions[i];
         if (r.first_point < 0 || r.point_capacity < 0 || r._reserved[0] != 0 || r._reserved[1] != 0 || r._reserved[2] != 0)
-            return svo_set_error(SVO_ERR_INVALID, "svo_submit_export_voxel_maps: region %d has a negative field or a non-zero _reserved", i);
-        if (r.point_capacity > 0 && !dst->points)
-            return svo_set_error(SVO_ERR_INVALID, "svo_submit_export_voxel_maps: region %d has a capacity, but points is NULL", i);
+            return svo_set_error(SVO_ERR_INVALID, "%s: region %d has a negative field or a non-zero _reserved", who, i);
+        if (r.point_capacity > 0 && !records) return svo_set_error(SVO_ERR_INVALID, "%s: region %d has a capacity, but %s is NULL", who, i, what);
         return (int)SVO_OK;
     });
     if (rc) return rc;
-    if (c->failed.load()) return reject_failed(c, "svo_submit_export_voxel_maps");
-    submit_shares<svo_ctx::VoxelExport>(c, slots, [&](svo_ctx::VoxelExport& e, int i, int) { e.regions.push_back(regions[i]); return true; },
-                                        [&](svo_ctx::VoxelExport& e) { e.mem = mem; e.filter = f; e.dst = *dst; });
+    if (c->failed.load()) return reject_failed(c, who);
+    submit_shares<J>(c, slots, [&](J& e, int i, int) { e.regions.push_back(regions[i]); return true; },
+                     [&](J& e) { e.mem = mem; e.filter = f; e.dst = *dst; });
     return SVO_OK;
+}
+
+extern "C" int svo_submit_export_voxel_maps(svo_ctx* c, const int* seqs, int n, const svo_voxel_region* regions,
+                                            const svo_voxel_filter* filter, const svo_voxel_dst* dst, int mem) {
+    return submit_voxel_out<svo_ctx::VoxelExport>(c, "svo_submit_export_voxel_maps", seqs, n, regions, filter, dst, dst ? dst->points : nullptr, "points", 16, mem);
+}
+
+extern "C" int svo_submit_save_voxel_maps(svo_ctx* c, const int* seqs, int n, const svo_voxel_region* regions,
+                                          const svo_voxel_filter* filter, const svo_voxel_entry_dst* dst, int mem) {
+    return submit_voxel_out<svo_ctx::VoxelSave>(c, "svo_submit_save_voxel_maps", seqs, n, regions, filter, dst, dst ? dst->entries : nullptr, "entries", 8, mem);
+}
+
+extern "C" int svo_save_voxel_maps(svo_ctx* c, const int* seqs, int n, const svo_voxel_region* regions, const svo_voxel_filter* filter,
+                                   const svo_voxel_entry_dst* dst, int mem) {
+    return then_wait(c, svo_submit_save_voxel_maps(c, seqs, n, regions, filter, dst, mem));
+}
+
+extern "C" int svo_submit_load_voxel_maps(svo_ctx* c, const int* seqs, int n, const svo_voxel_entry_span* spans, int mode, int mem,
+                                          svo_voxel_load_info* info) {
+    const char* who = "svo_submit_load_voxel_maps";
+    if (!c || !info || !mem_ok(mem) || !naming_ok(seqs, n) || (mode != SVO_VOXEL_LOAD_REPLACE && mode != SVO_VOXEL_LOAD_MERGE))
+        return svo_set_error(SVO_ERR_INVALID, "%s: bad arguments (mode %d, mem %d)", who, mode, mem);
+    const NamedSlots slots = ctx_slots(c, seqs, n);
+    if (slots.n > 0 && !spans) return svo_set_error(SVO_ERR_INVALID, "%s: no spans", who);
+    const int rc = check_slots_and_items(c, who, slots, [&](int i) {
+        const svo_voxel_entry_span& s = spans[i];
+        if (!svo::voxel_entry_span_ok((uintptr_t)s.entries, s.n))
+            return svo_set_error(SVO_ERR_INVALID, "%s: span %d: n < 0, or entries NULL or not 8-byte aligned", who, i);
+        const int seq = slots.at(i);
+        for (auto& wp : c->workers) {
+            if (seq < wp->first || seq >= wp->first + wp->count) continue;
+            const float voxel = grp_voxel_edge(wp->g.get(), seq - wp->first);
+            if (voxel > 0.f && !svo::voxel_edge_same(s.voxel, voxel))
+                return svo_set_error(SVO_ERR_INVALID, "%s: span %d: its keys were made with voxel %.9g, the map of slot %d has %.9g", who, i, (double)s.voxel,
+                                     seq, (double)voxel);
+        }
+        return (int)SVO_OK;
+    });
+    if (rc) return rc;
+    if (c->failed.load()) return reject_failed(c, who);
+    submit_shares<svo_ctx::VoxelLoad>(c, slots, [&](svo_ctx::VoxelLoad& e, int i, int) { e.spans.push_back(spans[i]); return true; },
+                                      [&](svo_ctx::VoxelLoad& e) { e.mode = mode; e.mem = mem; e.info = info; });
+    return SVO_OK;
+}
+
+extern "C" int svo_load_voxel_maps(svo_ctx* c, const int* seqs, int n, const svo_voxel_entry_span* spans, int mode, int mem,
+                                   svo_voxel_load_info* info) {
+    return then_wait(c, svo_submit_load_voxel_maps(c, seqs, n, spans, mode, mem, info));
+}
+
+extern "C" int svo_ctx_resize_voxel_maps(svo_ctx* c, const int* seqs, int n, int log2_capacity) {
+    if (!c || !naming_ok(seqs, n)) return svo_set_error(SVO_ERR_INVALID, "svo_ctx_resize_voxel_maps: bad arguments");
+    if (!svo::voxel_log2_ok(log2_capacity, true))
+        return svo_set_error(SVO_ERR_INVALID, "svo_ctx_resize_voxel_maps: log2_capacity %d outside %d .. %d", log2_capacity, svo::VOXEL_LOG2_MIN_CTX,
+                             svo::VOXEL_LOG2_MAX);
+    const NamedSlots slots = ctx_slots(c, seqs, n);
+    if (const int rc = check_slots(c, "svo_ctx_resize_voxel_maps", slots)) return rc;
+    if (const int rc = ctx_drain(c)) return rc;
+    // every group passes a phase before any enters the next: every slot fits, then every new map exists, before a map moves
+    auto phase = [&](int ph) {
+        int first = SVO_OK;
+        for (auto& wp : c->workers) {
+            SlotList local;
+            if (!slots.share(wp->first, wp->count, local, every_slot)) continue;
+            const int rc = grp_resize_voxel_maps(wp->g.get(), local.seqs.data(), (int)local.seqs.size(), log2_capacity, ph);
+            if (rc && ph != VOXEL_RESIZE_ABORT) return rc;
+            if (rc && !first) first = rc;
+        }
+        return first;
+    };
+    if (const int rc = phase(VOXEL_RESIZE_CHECK)) return rc;
+    if (const int rc = phase(VOXEL_RESIZE_ALLOC)) {
+        const std::string why = svo_last_error();
+        phase(VOXEL_RESIZE_ABORT);
+        return svo_set_error(rc, "%s", why.c_str());
+    }
+    return phase(VOXEL_RESIZE_MOVE);
 }
 
 extern "C" int svo_export_voxel_maps(svo_ctx* c, const int* seqs, int n, const svo_voxel_region* regions, const svo_voxel_filter* filter,

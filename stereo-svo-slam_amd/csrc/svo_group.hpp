@@ -157,6 +157,18 @@ int grp_carve_voxel_maps(svo_group* g, const int* seqs, const int* seg, int n, i
                          const svo_stereo_check* check, const svo_voxel_carve_rule* carve, const svo_voxel_keep* keep, int center_mode,
                          const float* centers, svo_carve_info* info);
 float grp_voxel_edge(const svo_group* g, int seq);
+// Voxel entries ("voxel entries"). grp_save_voxel_maps: grp_export_voxel_maps with entry records. grp_load_voxel_maps:
+// spans[i] (entries in `mem`, n, voxel: checked) is offered to the map of slot seqs[i], which fills info[seg[i]]; one
+// merge launch for the group's share. grp_resize_voxel_maps (the queues have drained) runs in phases, so that the ctx can
+// take every group through one before any enters the next: CHECK changes nothing and answers SVO_ERR_CAPACITY if a named
+// slot's entries do not fit log2_capacity; ALLOC makes the new map of every slot that moves; MOVE rehashes into them
+// and releases the old maps; ABORT gives back what ALLOC made (after an ALLOC that failed, here or in another group).
+int grp_save_voxel_maps(svo_group* g, int mem, const int* seqs, const int* seg, const svo_voxel_region* regions, int n, int seq0,
+                        const svo_voxel_filter* filter, const svo_voxel_entry_dst* dst);
+int grp_load_voxel_maps(svo_group* g, int mode, int mem, const int* seqs, const int* seg, const svo_voxel_entry_span* spans, int n, int seq0,
+                        svo_voxel_load_info* info);
+enum { VOXEL_RESIZE_CHECK = 0, VOXEL_RESIZE_ALLOC = 1, VOXEL_RESIZE_MOVE = 2, VOXEL_RESIZE_ABORT = 3 };
+int grp_resize_voxel_maps(svo_group* g, const int* seqs, int n, int log2_capacity, int phase);
 // what svo_map_size reports of a slot (the queues have drained)
 void grp_map_size(const svo_group* g, int seq, int from_keyframe, int* keyframes, int64_t* points_bound, int* from = nullptr);
 // Snapshots (svo_submit_save / svo_submit_load). grp_check_snapshot: everything svo_submit_load checks of one

@@ -372,6 +372,7 @@ struct svo_group {
     // the first job that needs it and replaced when outgrown.
     struct VoxelSlot {
         uint8_t* p = nullptr;
+        uint8_t* next = nullptr;         // (inside svo_ctx_resize_voxel_maps only: the map it moves into)
         svo_voxel_params params{};
         svo::VoxelHeader head{};         // as of the last job that changed the map
     };
@@ -380,6 +381,7 @@ struct svo_group {
     svo::GrowBlock<uint8_t, true> d_voxel_tables;
     svo::GrowBlock<uint8_t> d_voxel_offsets, d_voxel_sort, d_voxel_out;
     svo::GrowBlock<uint8_t> d_voxel_prune;   // a prune job: the tile offsets and the staging of one slot at a time
+    svo::GrowBlock<uint8_t> d_voxel_in;      // a load job in host mode: the entry records of the group's share
     // batched pose-filter updates (grp_pose_updates): the upload block (samples | filter states | start poses |
     // sample offsets) and behind it the download block (filter states | filtered poses) of one job, device and pinned,
     // made by the first such job and replaced when outgrown

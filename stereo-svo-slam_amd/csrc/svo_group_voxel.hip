@@ -2,7 +2,9 @@
 // one, the fuse job (the organized world-frame clouds of the named slots, computed by grp_export_cloud in device mode
 // into a block of the group, then one fuse launch per chunk), the export job (voxel.hip's count, scan, pairs, sort
 // and gather per slot), the clear job and the prune job (voxel.hip's rebuild in place per slot; "voxel prune"). A map belongs to the slot: nothing else in the group touches it. The host
-// arithmetic is svo_voxel_plan.hpp's, the state svo_group_state.hpp's.
+// arithmetic is svo_voxel_plan.hpp's, the state svo_group_state.hpp's. "voxel entries": the save job (the export job with
+// voxel.hip's pack in place of its gather), the load job (one merge launch for the group's share) and the resize (a
+// rehash per slot into a new allocation, between jobs).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -164,15 +166,18 @@ int grp_fuse_clouds(svo_group* c, int what, const int* seqs, const int* seg, int
     return SVO_OK;
 }
 
-int grp_export_voxel_maps(svo_group* c, int mem, const int* seqs, const int* seg, const svo_voxel_region* regions, int n, int seq0,
-                          const svo_voxel_filter* filter, const svo_voxel_dst* dst) {
-    if (const int rc = job_begin(c, "svo_submit_export_voxel_maps")) return rc;
+// grp_export_voxel_maps and grp_save_voxel_maps: the kept entries of each named slot's map in key order as the records
+// `launch` writes (launch_voxel_extract: points; launch_voxel_pack: entries) into records[first_point ...].
+template <class Record, class Launch>
+static int export_records(svo_group* c, const char* who, int mem, const int* seqs, const int* seg, const svo_voxel_region* regions, int n, int seq0,
+                          const svo_voxel_filter* filter, svo_voxel_segment* segments, Record* records, Launch launch) {
+    if (const int rc = job_begin(c, who)) return rc;
     hipStream_t st = c->stream.get();
     const bool host = mem == SVO_MEM_HOST;
     for (int i = 0; i < n; i++) {
         const Seq& q = c->seqs[seqs[i]];
         const svo_voxel_region& r = regions[i];
-        svo_voxel_segment& e = clear(dst->segments[seg[i]]);
+        svo_voxel_segment& e = clear(segments[seg[i]]);
         e.seq = seq0 + seqs[i]; e.run = q.run; e.frame_id = q.frame_id; e.first_point = r.first_point; e.status = SVO_VOXEL_NO_MAP;
         const svo_group::VoxelSlot* v = c->voxel_maps.empty() ? nullptr : &c->voxel_maps[(size_t)seqs[i]];
         if (!v || !v->p) continue;
@@ -191,7 +196,7 @@ int grp_export_voxel_maps(svo_group* c, int mem, const int* seqs, const int* seg
         HIP_TRY(hipMemcpyAsync(&kept, offsets + voxel_map_tiles(mp.log2_capacity), sizeof(kept), hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         if (kept < 0 || !voxel_extract_fits(kept, r.point_capacity))
-            return svo_set_error(SVO_ERR_INVALID, "svo_submit_export_voxel_maps: slot %d keeps %d entries, its mirror counts %lld", e.seq, kept,
+            return svo_set_error(SVO_ERR_INVALID, "%s: slot %d keeps %d entries, its mirror counts %lld", who, e.seq, kept,
                                  (long long)e.n_voxels);
         e.n_points = kept;
         if (kept == 0) continue;
@@ -200,18 +205,28 @@ int grp_export_voxel_maps(svo_group* c, int mem, const int* seqs, const int* seg
         const VoxelExtractPlan plan = voxel_extract_plan((uint64_t)kept, temp_bytes);
         if (const int rc = c->d_voxel_sort.reserve(c, plan.bytes)) return rc;
         if (host)
-            if (const int rc = c->d_voxel_out.reserve(c, sizeof(svo_map_point) * (size_t)kept)) return rc;
+            if (const int rc = c->d_voxel_out.reserve(c, sizeof(Record) * (size_t)kept)) return rc;
         uint8_t* ws = c->d_voxel_sort.p;
-        svo_map_point* out = host ? reinterpret_cast<svo_map_point*>(c->d_voxel_out.p) : dst->points + r.first_point;
-        if (const int rc = launch_voxel_extract(mp, f, offsets, (size_t)kept, reinterpret_cast<uint64_t*>(ws + plan.keys_in),
-                                                reinterpret_cast<uint64_t*>(ws + plan.keys_out), reinterpret_cast<uint32_t*>(ws + plan.index_in),
-                                                reinterpret_cast<uint32_t*>(ws + plan.index_out), ws + plan.sort_temp, temp_bytes, out, st))
+        Record* out = host ? reinterpret_cast<Record*>(c->d_voxel_out.p) : records + r.first_point;
+        if (const int rc = launch(mp, f, offsets, (size_t)kept, reinterpret_cast<uint64_t*>(ws + plan.keys_in),
+                                  reinterpret_cast<uint64_t*>(ws + plan.keys_out), reinterpret_cast<uint32_t*>(ws + plan.index_in),
+                                  reinterpret_cast<uint32_t*>(ws + plan.index_out), ws + plan.sort_temp, temp_bytes, out, st))
             return rc;
         HIP_TRY(hipGetLastError());
-        if (host) HIP_TRY(hipMemcpyAsync(dst->points + r.first_point, out, sizeof(svo_map_point) * (size_t)kept, hipMemcpyDeviceToHost, st));
+        if (host) HIP_TRY(hipMemcpyAsync(records + r.first_point, out, sizeof(Record) * (size_t)kept, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));   // delivered, and the blocks are free for the next slot
     }
     return SVO_OK;
+}
+
+int grp_export_voxel_maps(svo_group* c, int mem, const int* seqs, const int* seg, const svo_voxel_region* regions, int n, int seq0,
+                          const svo_voxel_filter* filter, const svo_voxel_dst* dst) {
+    return export_records(c, "svo_submit_export_voxel_maps", mem, seqs, seg, regions, n, seq0, filter, dst->segments, dst->points, launch_voxel_extract);
+}
+
+int grp_save_voxel_maps(svo_group* c, int mem, const int* seqs, const int* seg, const svo_voxel_region* regions, int n, int seq0,
+                        const svo_voxel_filter* filter, const svo_voxel_entry_dst* dst) {
+    return export_records(c, "svo_submit_save_voxel_maps", mem, seqs, seg, regions, n, seq0, filter, dst->segments, dst->entries, launch_voxel_pack);
 }
 
 float grp_voxel_edge(const svo_group* c, int seq) {
@@ -369,6 +384,142 @@ int grp_carve_voxel_maps(svo_group* c, const int* seqs, const int* seg, int n, i
         e.n_tested = (int32_t)counts[32 * j];
         e.n_carved = (int32_t)counts[32 * j + 1];
         v.head = heads[j];
+    }
+    return SVO_OK;
+}
+
+// The statuses are settled on the host first (no map, the load bound with the mirror's n_voxels, 0 for a replace); the
+// slots that are left share one merge launch: host entries are staged in d_voxel_in, a replace clears its maps first,
+// the tables (maps | headers | counts | spans) are the fuse job's block, one launch gathers the headers and one wait
+// brings headers and counts back: the new mirrors and the infos.
+int grp_load_voxel_maps(svo_group* c, int mode, int mem, const int* seqs, const int* seg, const svo_voxel_entry_span* spans, int n, int seq0,
+                        svo_voxel_load_info* info) {
+    if (const int rc = job_begin(c, "svo_submit_load_voxel_maps")) return rc;
+    hipStream_t st = c->stream.get();
+    const bool host = mem == SVO_MEM_HOST;
+    std::vector<int> todo;                                   // positions in the group's share
+    size_t in_bytes = 0;
+    for (int i = 0; i < n; i++) {
+        const Seq& q = c->seqs[seqs[i]];
+        svo_voxel_load_info& e = clear(info[seg[i]]);
+        e.seq = seq0 + seqs[i]; e.run = q.run; e.status = SVO_VOXEL_LOAD_NO_MAP;
+        const svo_group::VoxelSlot* v = c->voxel_maps.empty() ? nullptr : &c->voxel_maps[(size_t)seqs[i]];
+        if (!v || !v->p) continue;
+        e.n_voxels = (int64_t)v->head.n_voxels;
+        e.status = SVO_VOXEL_LOAD_FULL;
+        if (!voxel_merge_load_ok(mode == SVO_VOXEL_LOAD_REPLACE ? 0 : v->head.n_voxels, &spans[i].n, 1, v->params.log2_capacity)) continue;
+        e.status = SVO_VOXEL_LOADED;
+        todo.push_back(i);
+        if (host) in_bytes += voxel_up256(sizeof(svo_voxel_entry) * (size_t)spans[i].n);
+    }
+    if (todo.empty()) return SVO_OK;
+    const size_t m = todo.size();
+    int64_t all_tiles = 0;                                   // (before any clear: a job too large for one launch changes nothing)
+    for (size_t j = 0; j < m; j++) {
+        all_tiles += voxel_entry_span_tiles(spans[todo[j]].n);
+        if (all_tiles > INT32_MAX) return svo_set_error(SVO_ERR_CAPACITY, "svo_submit_load_voxel_maps: too many records for one job");
+    }
+    if (host)
+        if (const int rc = c->d_voxel_in.reserve(c, in_bytes)) return rc;
+    const size_t maps_off = 0, heads_off = voxel_up256(sizeof(VoxelMapDev) * m), counts_off = heads_off + voxel_up256(sizeof(VoxelHeader) * m),
+                 spans_off = counts_off + voxel_up256(sizeof(VoxelMergeCounts) * m);
+    if (const int rc = c->d_voxel_tables.reserve(c, spans_off + voxel_up256(sizeof(VoxelEntrySpanDev) * m))) return rc;
+    uint8_t* const h_tab = c->d_voxel_tables.host.get();
+    uint8_t* const d_tab = c->d_voxel_tables.p;
+    VoxelMapDev* h_maps = reinterpret_cast<VoxelMapDev*>(h_tab + maps_off);
+    VoxelEntrySpanDev* h_spans = reinterpret_cast<VoxelEntrySpanDev*>(h_tab + spans_off);
+    int n_spans = 0;
+    int64_t tiles = 0;
+    size_t in_at = 0;
+    for (size_t j = 0; j < m; j++) {
+        const svo_voxel_entry_span& s = spans[todo[j]];
+        svo_group::VoxelSlot& v = c->voxel_maps[(size_t)seqs[todo[j]]];
+        h_maps[j] = map_dev(v);
+        if (mode == SVO_VOXEL_LOAD_REPLACE) {
+            launch_voxel_clear(map_dev(v), st);
+            HIP_TRY(hipGetLastError());
+            v.head = empty_head(v.params);
+        }
+        if (s.n == 0) continue;
+        const svo_voxel_entry* from = s.entries;
+        if (host) {
+            svo_voxel_entry* staged = reinterpret_cast<svo_voxel_entry*>(c->d_voxel_in.p + in_at);
+            HIP_TRY(hipMemcpyAsync(staged, s.entries, sizeof(svo_voxel_entry) * (size_t)s.n, hipMemcpyHostToDevice, st));
+            in_at += voxel_up256(sizeof(svo_voxel_entry) * (size_t)s.n);
+            from = staged;
+        }
+        h_spans[n_spans++] = VoxelEntrySpanDev{from, s.n, tiles, (int32_t)j, 0};
+        tiles += voxel_entry_span_tiles(s.n);
+    }
+    HIP_TRY(hipMemcpyAsync(d_tab + maps_off, h_maps, sizeof(VoxelMapDev) * m, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(d_tab + counts_off, 0, sizeof(VoxelMergeCounts) * m, st));
+    if (n_spans > 0) {
+        HIP_TRY(hipMemcpyAsync(d_tab + spans_off, h_spans, sizeof(VoxelEntrySpanDev) * (size_t)n_spans, hipMemcpyHostToDevice, st));
+        launch_voxel_merge(reinterpret_cast<const VoxelEntrySpanDev*>(d_tab + spans_off), n_spans, tiles, reinterpret_cast<const VoxelMapDev*>(d_tab + maps_off),
+                           reinterpret_cast<VoxelMergeCounts*>(d_tab + counts_off), st);
+        HIP_TRY(hipGetLastError());
+    }
+    launch_voxel_headers(reinterpret_cast<const VoxelMapDev*>(d_tab + maps_off), (int)m, reinterpret_cast<VoxelHeader*>(d_tab + heads_off), st);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(h_tab + heads_off, d_tab + heads_off, counts_off - heads_off + sizeof(VoxelMergeCounts) * m, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));   // loaded; the caller's entries and the blocks are free
+    const VoxelHeader* heads = reinterpret_cast<const VoxelHeader*>(h_tab + heads_off);
+    const VoxelMergeCounts* counts = reinterpret_cast<const VoxelMergeCounts*>(h_tab + counts_off);
+    for (size_t j = 0; j < m; j++) {
+        svo_voxel_load_info& e = info[seg[todo[j]]];
+        e.n_offered = (int64_t)counts[j].n_offered; e.n_merged = (int64_t)counts[j].n_merged;
+        e.n_skipped = (int64_t)counts[j].n_skipped; e.n_claimed = (int64_t)counts[j].n_claimed;
+        e.n_voxels = (int64_t)heads[j].n_voxels;
+        c->voxel_maps[(size_t)seqs[todo[j]]].head = heads[j];
+    }
+    return SVO_OK;
+}
+
+int grp_resize_voxel_maps(svo_group* c, const int* seqs, int n, int log2_capacity, int phase) {
+    if (c->voxel_maps.empty()) return SVO_OK;
+    auto moves = [&](const svo_group::VoxelSlot& v) { return v.p && v.params.log2_capacity != log2_capacity; };
+    if (phase == VOXEL_RESIZE_CHECK) {
+        for (int i = 0; i < n; i++) {
+            const svo_group::VoxelSlot& v = c->voxel_maps[(size_t)seqs[i]];
+            if (v.p && !voxel_rehash_ok(v.head.n_voxels, log2_capacity))
+                return svo_set_error(SVO_ERR_CAPACITY, "svo_ctx_resize_voxel_maps: a slot's %llu voxels exceed %llu, the load limit of log2_capacity %d",
+                                     v.head.n_voxels, (unsigned long long)voxel_load_limit(log2_capacity), log2_capacity);
+        }
+        return SVO_OK;
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    if (phase == VOXEL_RESIZE_ABORT) {                       // give back what VOXEL_RESIZE_ALLOC made
+        for (int i = 0; i < n; i++) {
+            svo_group::VoxelSlot& v = c->voxel_maps[(size_t)seqs[i]];
+            if (v.next) dev_release(c, v.next, voxel_map_bytes(log2_capacity));
+            v.next = nullptr;
+        }
+        return SVO_OK;
+    }
+    if (phase == VOXEL_RESIZE_ALLOC) {                       // every new map of the group, before any map is moved
+        for (int i = 0; i < n; i++) {
+            svo_group::VoxelSlot& v = c->voxel_maps[(size_t)seqs[i]];
+            if (!moves(v)) continue;
+            if (const int rc = dev_alloc(c, &v.next, voxel_map_bytes(log2_capacity), false)) return rc;
+        }
+        return SVO_OK;
+    }
+    hipStream_t st = c->stream.get();                        // VOXEL_RESIZE_MOVE
+    HIP_TRY(hipStreamSynchronize(st));
+    for (int i = 0; i < n; i++) {
+        svo_group::VoxelSlot& v = c->voxel_maps[(size_t)seqs[i]];
+        if (!moves(v) || !v.next) continue;
+        svo_group::VoxelSlot to = v;
+        to.p = v.next;
+        to.next = nullptr;
+        to.params.log2_capacity = log2_capacity;
+        to.head.log2_capacity = log2_capacity;
+        launch_voxel_rehash(map_dev(v), map_dev(to), st);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(st));   // moved: the old map can go
+        v.next = nullptr;
+        drop_map(c, v);
+        v = to;
     }
     return SVO_OK;
 }

@@ -609,5 +609,26 @@ VoxelCarveDev voxel_carve_dev(const svo_voxel_carve_rule& carve, const svo_ar_ca
                               int cols, int rows, int step);
 void launch_voxel_carve(const VoxelMapDev& map, const VoxelCarveRule& rule, int32_t* tile_offsets, uint8_t* staging, uint64_t n_bound,
                         hipStream_t stream);
+// ---- voxel entries (include/svo_hip.h, "voxel entries")
+struct VoxelEntrySpanDev {        // n > 0 entry records for maps[map]; tile0: the workgroups of the spans before it
+    const svo_voxel_entry* entries;
+    int64_t n;
+    int64_t tile0;
+    int32_t map;
+    int32_t _pad;
+};
+struct VoxelMergeCounts { unsigned long long n_offered, n_merged, n_skipped, n_claimed; };   // of one map: svo_voxel_merge_result
+// launch_voxel_extract with the raw entries in place of the points: the same pairs and sort launches, then one
+// 40-byte record per kept entry, entries[0, n)
+int launch_voxel_pack(const VoxelMapDev& map, VoxelFilterDev f, const int32_t* tile_offsets, size_t n, uint64_t* keys_in,
+                      uint64_t* keys_out, uint32_t* index_in, uint32_t* index_out, void* sort_temp, size_t sort_temp_bytes,
+                      svo_voxel_entry* entries, hipStream_t stream);
+// n_spans >= 1 spans of `tiles` workgroups in all merged into the maps they name; counts[map] += what the launch did
+// (the caller zeroes them)
+void launch_voxel_merge(const VoxelEntrySpanDev* d_spans, int n_spans, int64_t tiles, const VoxelMapDev* d_maps, VoxelMergeCounts* d_counts,
+                        hipStream_t stream);
+// dst (any bytes) becomes the cleared map of its params, receives every entry of src and then src's n_voxels and
+// three cumulative counters: three launches ordered by the stream. dst shares no byte with src.
+void launch_voxel_rehash(const VoxelMapDev& src, const VoxelMapDev& dst, hipStream_t stream);
 
 }  // namespace svo

@@ -1,7 +1,8 @@
 // svo_voxel_plan.hpp — the host arithmetic of the voxel maps (include/svo_hip.h, "voxel maps"): the bytes of a map,
 // the placement hash, the load bound a fuse is admitted by, what a span and a region must look like, the tiles a span
 // is cut into and the staging of an extraction. Plain C++: no HIP, no error text; svo_capi_voxel.hip formats its own
-// messages. tests/cpp/voxel_plan_check.cpp exercises it on the CPU, plain and under the sanitizers.
+// messages. tests/cpp/voxel_plan_check.cpp exercises it on the CPU, plain and under the sanitizers; the prune's, the
+// carve's and the entries' parts have a program each beside it.
 #pragma once
 
 #include <cstddef>
@@ -139,6 +140,46 @@ inline bool voxel_carve_scalars_ok(float margin, float near, int ring, int width
     const float big = 3.40282347e+38f;
     return margin >= 0.f && margin <= big && near > 0.f && near <= big && (ring == 0 || ring == 1) && width >= 1 && width <= 32768 &&
            height >= 1 && height <= 32768;
+}
+
+// ---- voxel entries (include/svo_hip.h, "voxel entries"; tests/cpp/voxel_entries_plan_check.cpp)
+
+// a span of entry records the merge accepts: n >= 0, and with n > 0 a non-null, 8-byte aligned address
+inline bool voxel_entry_span_ok(uintptr_t entries, int64_t n) { return n >= 0 && (n == 0 || (entries != 0 && (entries & 7) == 0)); }
+
+// the workgroups of a span of n entry records: the fuse's tiles
+inline int64_t voxel_entry_span_tiles(int64_t n) { return voxel_span_tiles(n); }
+
+// two voxel edges are the same edge: bit for bit (0.0 and -0.0 differ, a NaN equals itself; the params check admits neither)
+inline bool voxel_edge_same(float a, float b) {
+    uint32_t ua, ub;
+    __builtin_memcpy(&ua, &a, 4);
+    __builtin_memcpy(&ub, &b, 4);
+    return ua == ub;
+}
+
+// The merge's load bound for one map: n_voxels + (the records of the n_spans spans into it) <= capacity - capacity / 4,
+// on the bound. false too when a count is negative or the sum does not fit 64 bits.
+inline bool voxel_merge_load_ok(uint64_t n_voxels, const int64_t* span_n, int n_spans, int log2_capacity) {
+    uint64_t records = 0;
+    for (int i = 0; i < n_spans; i++)
+        if (!voxel_add_records(records, span_n[i])) return false;
+    return voxel_load_ok(n_voxels, records, log2_capacity);
+}
+
+// does a pack of `kept` entries fit `capacity` records? (the extraction's rule)
+inline bool voxel_pack_fits(int64_t kept, int64_t capacity) { return voxel_extract_fits(kept, capacity); }
+
+// a rehash into a table of 1 << dst_log2_capacity entries is admitted: the log2 is one the stage entries accept and
+// the entries fit under the load limit, on the limit
+inline bool voxel_rehash_ok(uint64_t n_voxels, int dst_log2_capacity) {
+    return voxel_log2_ok(dst_log2_capacity, false) && n_voxels <= voxel_load_limit(dst_log2_capacity);
+}
+
+// do the byte ranges [a, a + a_bytes) and [b, b + b_bytes) share a byte? (no wrap: the sums are formed as differences)
+inline bool voxel_ranges_overlap(uintptr_t a, size_t a_bytes, uintptr_t b, size_t b_bytes) {
+    if (a_bytes == 0 || b_bytes == 0) return false;
+    return a <= b ? b - a < a_bytes : a - b < b_bytes;
 }
 
 }  // namespace svo

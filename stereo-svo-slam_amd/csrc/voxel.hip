@@ -46,11 +46,25 @@
 // once, in the count pass, which leaves one 64-bit ballot word per wavefront; the stage pass reads the words. The two
 // counts are summed inside the workgroup and leave as one 64-bit atomic add each.
 //
+// Entries ("voxel entries"): voxel_pack_kernel is a second gather behind the extraction's count, scan, pairs and sort
+// (launch_voxel_sorted_pairs, shared): one lane per kept entry, two 16-byte loads, one 40-byte record out.
+// voxel_merge_kernel is the fuse's launch shape (tiles of 256 records, the binary search of tile0) with one lane per
+// 40-byte record: the probe, the claim, eight integer atomics per lane, always atomics, and no election (a pack's keys
+// are unique; repeated keys meet at the entry). The header's n_voxels, n_fused (a 64-bit sum of counts) and overflow
+// and the call's four counts per map get at most one add each per wavefront. voxel_rehash_kernel is one lane per
+// entry of the source table into a cleared table of another size by the reinsert's probe, claim and plain stores
+// (voxel_place_unique: the keys of a table are unique and the destination is private), between voxel_clear_kernel on
+// the destination and a one-lane launch that copies the four counters; no staging block, nothing read back.
+//
 // Bounds: of a span, records [0, n) are read. Of a map, keys and acc entries [0, capacity) (slot = (slot + 1) &
 // (capacity - 1)) and the header. tile_offsets [0, tiles]; pairs and records [0, n) with n the scan's total. Of a
 // prune's staging block, records and keys [0, min(total, n_bound)) with n_bound the n_voxels the block was sized by;
 // the clear writes the 16-byte units [0, (40 << log2_capacity) / 16) behind the header. Of a carve: occluder records
 // [0, cols * rows) (every cell index is checked against cols and rows), ballot words [0, VOXEL_WAVES * tiles), two counters.
+// Of a pack: pairs [0, n) and entry records [0, n) with n the scan's total, which the host compared with the capacity;
+// the entry index of a pair is masked by capacity - 1. Of a merge: entry records [0, n) of a span are read, counts[map]
+// with map < n_maps (checked on the host), map entries as for a fuse. Of a rehash: source entries [0, capacity), the
+// destination's 16-byte units [0, (256 + (40 << log2_capacity')) / 16) by the clear and entries [0, capacity') by the probe.
 #include <hip/hip_runtime.h>
 
 #include <cfloat>
@@ -68,6 +82,9 @@ constexpr int VOXEL_THREADS = 256;
 constexpr int VOXEL_WAVES = VOXEL_THREADS / 64;
 static_assert(VOXEL_TILE == VOXEL_THREADS, "one lane per record or entry of a tile");
 static_assert(sizeof(svo_map_point) == 16 && sizeof(VoxelSpanDev) == 32 && sizeof(VoxelMapDev) == 24, "record sizes");
+static_assert(sizeof(svo_voxel_entry) == 40 && alignof(svo_voxel_entry) == 8 && sizeof(VoxelEntrySpanDev) == 32 && sizeof(VoxelMergeCounts) == 32 &&
+                  sizeof(svo_voxel_merge_result) == 32,
+              "entry record sizes");
 
 #define VOXEL_RELAXED __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
 
@@ -477,18 +494,11 @@ __global__ __launch_bounds__(VOXEL_THREADS) void voxel_prune_clear_kernel(const 
     ((SVO_GP(uint4))(mp.base + VOXEL_HEADER_BYTES))[u] = make_uint4(w, w, w, w);
 }
 
-// One lane per staged entry: the probe of the fuse from the key's home, the claim ~0 -> key (keys are unique: a lane
-// never meets its own key, and an entry another lane claimed holds another key for good), then the eight
-// accumulators as two plain 16-byte stores: nobody else writes the entry this lane claimed.
-__global__ __launch_bounds__(VOXEL_THREADS) void voxel_prune_reinsert_kernel(const VoxelMapDev mp, const int32_t* __restrict__ tile_offsets, const int tiles,
-                                                                             const size_t n_bound, const uint4* __restrict__ acc_in,
-                                                                             const unsigned long long* __restrict__ keys_in) {
-    if (voxel_prune_nothing_leaves(mp, tile_offsets, tiles)) return;
-    const size_t i = (size_t)blockIdx.x * VOXEL_THREADS + threadIdx.x;
-    const size_t n = min((size_t)max(G(tile_offsets)[tiles], 0), n_bound);
-    if (i >= n) return;
-    const unsigned long long key = G(keys_in)[i];
-    const uint4 lo = ((SVO_GP(const uint4))acc_in)[2 * i], hi = ((SVO_GP(const uint4))acc_in)[2 * i + 1];
+// An entry whose key no other lane of the launch holds, into a table that held none of the launch's keys before it: the
+// probe of the fuse from the key's home, the claim ~0 -> key (keys are unique: a lane never meets its own key, and an
+// entry another lane claimed holds another key for good), then the eight accumulators as two plain 16-byte stores:
+// nobody else writes the entry this lane claimed.
+__device__ __forceinline__ void voxel_place_unique(const VoxelMapDev& mp, unsigned long long key, uint4 lo, uint4 hi) {
     const uint32_t cap = 1u << mp.log2_capacity, mask = cap - 1;
     SVO_GP(unsigned long long) keys = voxel_keys(mp);
     uint32_t s = (uint32_t)((key * VOXEL_HASH) >> (64 - mp.log2_capacity));
@@ -507,10 +517,144 @@ __global__ __launch_bounds__(VOXEL_THREADS) void voxel_prune_reinsert_kernel(con
     // (not reached: the cleared table has `capacity` empty entries for at most n_voxels <= capacity keys)
 }
 
+// One lane per staged entry, placed by voxel_place_unique.
+__global__ __launch_bounds__(VOXEL_THREADS) void voxel_prune_reinsert_kernel(const VoxelMapDev mp, const int32_t* __restrict__ tile_offsets, const int tiles,
+                                                                             const size_t n_bound, const uint4* __restrict__ acc_in,
+                                                                             const unsigned long long* __restrict__ keys_in) {
+    if (voxel_prune_nothing_leaves(mp, tile_offsets, tiles)) return;
+    const size_t i = (size_t)blockIdx.x * VOXEL_THREADS + threadIdx.x;
+    const size_t n = min((size_t)max(G(tile_offsets)[tiles], 0), n_bound);
+    if (i >= n) return;
+    const unsigned long long key = G(keys_in)[i];
+    const uint4 lo = ((SVO_GP(const uint4))acc_in)[2 * i], hi = ((SVO_GP(const uint4))acc_in)[2 * i + 1];
+    voxel_place_unique(mp, key, lo, hi);
+}
+
 // the last launch of a prune: the header's n_voxels becomes the kept count
 __global__ __launch_bounds__(64) void voxel_prune_finish_kernel(const VoxelMapDev mp, const int32_t* __restrict__ tile_offsets, const int tiles) {
     if (threadIdx.x != 0 || voxel_prune_nothing_leaves(mp, tile_offsets, tiles)) return;
     ((SVO_GP(VoxelHeader))mp.base)->n_voxels = (unsigned long long)max(G(tile_offsets)[tiles], 0);
+}
+
+// ---- entries (include/svo_hip.h, "voxel entries"): the raw entries packed out in key order, merged in, rehashed
+
+// the pack's gather: the kept entry of rank i in key order leaves as entries[i], five 8-byte stores (a record is
+// 8-byte aligned, no more)
+__global__ __launch_bounds__(VOXEL_THREADS) void voxel_pack_kernel(const VoxelMapDev mp, const size_t n, const unsigned long long* __restrict__ keys,
+                                                                   const uint32_t* __restrict__ index, svo_voxel_entry* __restrict__ entries) {
+    const size_t i = (size_t)blockIdx.x * VOXEL_THREADS + threadIdx.x;
+    if (i >= n) return;
+    const unsigned long long key = G(keys)[i];
+    const uint32_t e = G(index)[i] & ((1u << mp.log2_capacity) - 1);
+    const SVO_GP(uint4) a = (SVO_GP(uint4))(voxel_acc(mp) + (size_t)e * 8);
+    const uint4 lo = a[0], hi = a[1];                      // count sx sy sz | sr sg sb last
+    SVO_GP(uint2) out = (SVO_GP(uint2))(entries + i);
+    out[0] = make_uint2((uint32_t)key, (uint32_t)(key >> 32));
+    out[1] = make_uint2(lo.x, lo.y);
+    out[2] = make_uint2(lo.z, lo.w);
+    out[3] = make_uint2(hi.x, hi.y);
+    out[4] = make_uint2(hi.z, hi.w);
+}
+
+// A workgroup takes VOXEL_TILE consecutive records of one span (the fuse's search of tile0), a lane one record. No
+// leader is elected among equal keys: the records of a pack have unique keys, and where keys do repeat (across spans,
+// or in a span a caller made) every update below is an atomic, so the lanes simply meet at the entry. A lane that
+// claimed an entry adds like every other: a second lane with the same key can find the claimed key and add before
+// the claimer's first add lands, and plain stores would lose that.
+__global__ __launch_bounds__(VOXEL_THREADS) void voxel_merge_kernel(const VoxelEntrySpanDev* __restrict__ spans, const int n_spans,
+                                                                    const VoxelMapDev* __restrict__ maps, VoxelMergeCounts* __restrict__ counts) {
+    const int64_t tile = blockIdx.x;
+    int lo = 0, hi = n_spans - 1;                          // the last span that starts at or before this tile
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (G(spans)[mid].tile0 <= tile) lo = mid; else hi = mid - 1;
+    }
+    const VoxelEntrySpanDev sp = G(spans)[lo];
+    const VoxelMapDev mp = G(maps)[sp.map];
+    const int lane = threadIdx.x & 63;
+    const int64_t k = (tile - sp.tile0) * VOXEL_TILE + (int64_t)threadIdx.x;
+
+    const bool offered = k < sp.n;
+    unsigned long long key = VOXEL_EMPTY;
+    uint32_t v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (offered) {
+        SVO_GP(const uint2) r =(SVO_GP(const uint2))(sp.entries + k);
+        const uint2 w0 = r[0], w1 = r[1], w2 = r[2], w3 = r[3], w4 = r[4];
+        key = (unsigned long long)w0.y << 32 | w0.x;
+        v[0] = w1.x; v[1] = w1.y; v[2] = w2.x; v[3] = w2.y; v[4] = w3.x; v[5] = w3.y; v[6] = w4.x; v[7] = w4.y;
+    }
+    const bool active = offered && !(key >> 63) && v[0] != 0;
+    const unsigned long long all_offered = __ballot(offered);
+    if (all_offered == 0) return;                          // (wave-uniform)
+
+    // find or claim the key's entry: bounded by the capacity, never waiting
+    const uint32_t cap = 1u << mp.log2_capacity, mask = cap - 1;
+    int slot = -1;
+    bool claimed = false;
+    if (active) {
+        SVO_GP(unsigned long long) keys = voxel_keys(mp);
+        uint32_t s = (uint32_t)((key * VOXEL_HASH) >> (64 - mp.log2_capacity));
+        for (uint32_t it = 0; it < cap; it++) {
+            unsigned long long cur = __hip_atomic_load(keys + s, VOXEL_RELAXED);
+            if (cur == VOXEL_EMPTY) {
+                unsigned long long expected = VOXEL_EMPTY;
+                if (__hip_atomic_compare_exchange_strong(keys + s, &expected, key, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
+                    claimed = true;
+                    cur = key;
+                } else {
+                    cur = expected;
+                }
+            }
+            if (cur == key) { slot = (int)s; break; }
+            s = (s + 1) & mask;
+        }
+    }
+    const bool merged = active && slot >= 0;
+    if (merged) {
+        SVO_GP(uint32_t) a = voxel_acc(mp) + (size_t)slot * 8;
+        for (int j = 0; j < 7; j++) __hip_atomic_fetch_add(a + j, v[j], VOXEL_RELAXED);
+        __hip_atomic_fetch_max(a + 7, v[7], VOXEL_RELAXED);
+    }
+
+    // the header's counters and the call's: at most one add each per wavefront
+    unsigned long long fused = merged ? v[0] : 0u;         // the 64-bit sum of the merged counts
+    for (int o = 32; o > 0; o >>= 1) fused += __shfl_xor(fused, o);
+    const unsigned long long n_offered = __popcll(all_offered), n_merged = __popcll(__ballot(merged)), n_skipped = __popcll(__ballot(offered && !active)),
+                             n_claimed = __popcll(__ballot(claimed)), n_lost = __popcll(__ballot(active && slot < 0));
+    if (lane == 0) {
+        SVO_GP(VoxelHeader) hd = (SVO_GP(VoxelHeader))mp.base;
+        if (n_claimed) __hip_atomic_fetch_add(&hd->n_voxels, n_claimed, VOXEL_RELAXED);
+        if (fused) __hip_atomic_fetch_add(&hd->n_fused, fused, VOXEL_RELAXED);
+        if (n_lost) __hip_atomic_fetch_add(&hd->overflow, n_lost, VOXEL_RELAXED);   // (the load bound keeps it 0)
+        SVO_GP(VoxelMergeCounts) c = G(counts) + sp.map;
+        __hip_atomic_fetch_add(&c->n_offered, n_offered, VOXEL_RELAXED);
+        if (n_merged) __hip_atomic_fetch_add(&c->n_merged, n_merged, VOXEL_RELAXED);
+        if (n_skipped) __hip_atomic_fetch_add(&c->n_skipped, n_skipped, VOXEL_RELAXED);
+        if (n_claimed) __hip_atomic_fetch_add(&c->n_claimed, n_claimed, VOXEL_RELAXED);
+    }
+}
+
+// One lane per entry of the source table: a non-empty entry goes into dst by voxel_place_unique. That is right here:
+// the keys of one table are unique, and dst was cleared by the launch before this one and belongs to this call alone.
+__global__ __launch_bounds__(VOXEL_THREADS) void voxel_rehash_kernel(const VoxelMapDev src, const VoxelMapDev dst) {
+    const uint32_t e = blockIdx.x * VOXEL_TILE + threadIdx.x;
+    if (e >= (1u << src.log2_capacity)) return;
+    const unsigned long long key = voxel_keys(src)[e];
+    if (key == VOXEL_EMPTY) return;
+    const SVO_GP(uint4) a = (SVO_GP(uint4))(voxel_acc(src) + (size_t)e * 8);
+    const uint4 lo = a[0], hi = a[1];
+    voxel_place_unique(dst, key, lo, hi);
+}
+
+// the last launch of a rehash: the four counters of the source header, as they are, into the cleared header of dst
+__global__ __launch_bounds__(64) void voxel_rehash_finish_kernel(const VoxelMapDev src, const VoxelMapDev dst) {
+    if (threadIdx.x != 0) return;
+    SVO_GP(const VoxelHeader) from =(SVO_GP(const VoxelHeader))src.base;
+    SVO_GP(VoxelHeader) to = (SVO_GP(VoxelHeader))dst.base;
+    to->n_voxels = from->n_voxels;
+    to->n_fused = from->n_fused;
+    to->n_outside = from->n_outside;
+    to->overflow = from->overflow;
 }
 
 template <class Rule>
@@ -573,18 +717,50 @@ int voxel_sort_temp_bytes(size_t n, size_t* bytes) {
     return SVO_OK;
 }
 
-int launch_voxel_extract(const VoxelMapDev& map, VoxelFilterDev f, const int32_t* tile_offsets, size_t n, uint64_t* keys_in,
-                         uint64_t* keys_out, uint32_t* index_in, uint32_t* index_out, void* sort_temp, size_t sort_temp_bytes,
-                         svo_map_point* points, hipStream_t stream) {
-    if (n == 0) return SVO_OK;
+// the (key, entry) pairs of the n > 0 kept entries, sorted by key: what the extraction and the pack gather from
+static int launch_voxel_sorted_pairs(const VoxelMapDev& map, VoxelFilterDev f, const int32_t* tile_offsets, size_t n, uint64_t* keys_in,
+                                     uint64_t* keys_out, uint32_t* index_in, uint32_t* index_out, void* sort_temp, size_t sort_temp_bytes,
+                                     hipStream_t stream) {
     const int tiles = (int)voxel_map_tiles(map.log2_capacity);
     hipLaunchKernelGGL(voxel_pairs_kernel, dim3(tiles), dim3(VOXEL_THREADS), 0, stream, map, f, tile_offsets, n,
                        (unsigned long long*)keys_in, index_in);
     HIP_TRY(rocprim::radix_sort_pairs(sort_temp, sort_temp_bytes, (unsigned long long*)keys_in, (unsigned long long*)keys_out, index_in,
                                       index_out, n, 0, 63, stream));
+    return SVO_OK;
+}
+
+int launch_voxel_extract(const VoxelMapDev& map, VoxelFilterDev f, const int32_t* tile_offsets, size_t n, uint64_t* keys_in,
+                         uint64_t* keys_out, uint32_t* index_in, uint32_t* index_out, void* sort_temp, size_t sort_temp_bytes,
+                         svo_map_point* points, hipStream_t stream) {
+    if (n == 0) return SVO_OK;
+    if (const int rc = launch_voxel_sorted_pairs(map, f, tile_offsets, n, keys_in, keys_out, index_in, index_out, sort_temp, sort_temp_bytes, stream))
+        return rc;
     hipLaunchKernelGGL(voxel_gather_kernel, dim3((unsigned)((n + VOXEL_THREADS - 1) / VOXEL_THREADS)), dim3(VOXEL_THREADS), 0, stream, map, n,
                        (const unsigned long long*)keys_out, index_out, points);
     return SVO_OK;
+}
+
+int launch_voxel_pack(const VoxelMapDev& map, VoxelFilterDev f, const int32_t* tile_offsets, size_t n, uint64_t* keys_in,
+                      uint64_t* keys_out, uint32_t* index_in, uint32_t* index_out, void* sort_temp, size_t sort_temp_bytes,
+                      svo_voxel_entry* entries, hipStream_t stream) {
+    if (n == 0) return SVO_OK;
+    if (const int rc = launch_voxel_sorted_pairs(map, f, tile_offsets, n, keys_in, keys_out, index_in, index_out, sort_temp, sort_temp_bytes, stream))
+        return rc;
+    hipLaunchKernelGGL(voxel_pack_kernel, dim3((unsigned)((n + VOXEL_THREADS - 1) / VOXEL_THREADS)), dim3(VOXEL_THREADS), 0, stream, map, n,
+                       (const unsigned long long*)keys_out, index_out, entries);
+    return SVO_OK;
+}
+
+void launch_voxel_merge(const VoxelEntrySpanDev* d_spans, int n_spans, int64_t tiles, const VoxelMapDev* d_maps, VoxelMergeCounts* d_counts,
+                        hipStream_t stream) {
+    if (n_spans <= 0 || tiles <= 0) return;
+    hipLaunchKernelGGL(voxel_merge_kernel, dim3((unsigned)tiles), dim3(VOXEL_THREADS), 0, stream, d_spans, n_spans, d_maps, d_counts);
+}
+
+void launch_voxel_rehash(const VoxelMapDev& src, const VoxelMapDev& dst, hipStream_t stream) {
+    launch_voxel_clear(dst, stream);
+    hipLaunchKernelGGL(voxel_rehash_kernel, dim3((unsigned)voxel_map_tiles(src.log2_capacity)), dim3(VOXEL_THREADS), 0, stream, src, dst);
+    hipLaunchKernelGGL(voxel_rehash_finish_kernel, dim3(1), dim3(64), 0, stream, src, dst);
 }
 
 }  // namespace svo

@@ -60,6 +60,8 @@ SYMBOLS = (
     "svo_submit_export_voxel_maps", "svo_export_voxel_maps", "svo_submit_clear_voxel_maps",
     "svo_voxel_prune", "svo_submit_prune_voxel_maps", "svo_prune_voxel_maps", "svo_voxel_carve",
     "svo_submit_carve_voxel_maps", "svo_carve_voxel_maps",
+    "svo_voxel_pack", "svo_voxel_merge", "svo_voxel_rehash", "svo_submit_save_voxel_maps", "svo_save_voxel_maps",
+    "svo_submit_load_voxel_maps", "svo_load_voxel_maps", "svo_ctx_resize_voxel_maps",
     "svo_ar_size", "svo_ar_camera_of_pose", "svo_submit_export_ar", "svo_export_ar", "svo_render_ar",
     "svo_submit_export_ar_occluded", "svo_export_ar_occluded", "svo_render_ar_occluded",
     "svo_remap_linear_multi", "svo_ctx_add_rigs", "svo_ctx_remove_rigs", "svo_ctx_assign_rigs", "svo_ctx_get_slot_rig",
@@ -785,6 +787,36 @@ class VoxelCarveResult(C.Structure):
 
 
 assert (C.sizeof(VoxelCarve), C.sizeof(VoxelCarveResult)) == (32, 32)
+
+# svo_voxel_entry (include/svo_hip.h, "voxel entries"): a raw entry of a map; acc = count, sx, sy, sz, sr, sg, sb, last
+VOXEL_ENTRY_DTYPE = np.dtype([("key", "<u8"), ("acc", "<u4", (8,))])
+
+
+class VoxelEntrySpan(C.Structure):
+    """svo_voxel_entry_span (include/svo_hip.h): n entry records for map `map` of a call, keys made with `voxel`."""
+    _fields_ = [("entries", C.c_void_p), ("n", C.c_int64), ("map", C.c_int32), ("voxel", C.c_float)]
+
+
+class VoxelMergeResult(C.Structure):
+    """svo_voxel_merge_result (include/svo_hip.h): what a merge did to one map."""
+    _fields_ = [("n_offered", C.c_int64), ("n_merged", C.c_int64), ("n_skipped", C.c_int64), ("n_claimed", C.c_int64)]
+
+
+assert (VOXEL_ENTRY_DTYPE.itemsize, C.sizeof(VoxelEntrySpan), C.sizeof(VoxelMergeResult)) == (40, 24, 32)
+# the ctx's save and load jobs: svo_submit_save_voxel_maps (the export's regions and segments), svo_submit_load_voxel_maps
+VOXEL_LOAD_REPLACE, VOXEL_LOAD_MERGE = 0, 1
+VOXEL_LOADED, VOXEL_LOAD_NO_MAP, VOXEL_LOAD_FULL = 0, 1, 2
+VOXEL_ENTRY_SPAN_DTYPE = np.dtype([("entries", "<u8"), ("n", "<i8"), ("map", "<i4"), ("voxel", "<f4")])
+VOXEL_LOAD_INFO_DTYPE = np.dtype([("seq", "<i4"), ("run", "<i4"), ("status", "<i4"), ("_pad", "<i4"), ("n_offered", "<i8"), ("n_merged", "<i8"),
+                                  ("n_skipped", "<i8"), ("n_claimed", "<i8"), ("n_voxels", "<i8"), ("_pad2", "<i8")])
+
+
+class VoxelEntryDst(C.Structure):
+    """svo_voxel_entry_dst (include/svo_hip.h)"""
+    _fields_ = [("segments", C.c_void_p), ("entries", C.c_void_p)]
+
+
+assert (VOXEL_ENTRY_SPAN_DTYPE.itemsize, VOXEL_LOAD_INFO_DTYPE.itemsize, C.sizeof(VoxelEntryDst)) == (24, 64, 16)
 # the ctx's carve job: svo_submit_carve_voxel_maps (the centre modes are the prune job's)
 CARVE_OK, CARVE_NO_MAP, CARVE_NO_POSE, CARVE_TOO_LARGE, CARVE_NONE = range(5)
 CARVE_INFO_DTYPE = np.dtype([("seq", "<i4"), ("run", "<i4"), ("frame_id", "<i4"), ("status", "<i4"), ("n_before", "<i8"), ("n_kept", "<i8"),
@@ -1093,6 +1125,12 @@ def lib():
                 getattr(_LIB, name).argtypes = [p, p, i, p, p, p, p, p, i, p, p]
         if hasattr(_LIB, "svo_voxel_carve"):
             _LIB.svo_voxel_carve.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        for name, argtypes in (("svo_voxel_pack", [p, p, p, p, C.c_int64, p]), ("svo_voxel_merge", [p, i, p, i, p, p]),
+                               ("svo_voxel_rehash", [p, p, p, i]), ("svo_submit_save_voxel_maps", [p, p, i, p, p, p, i]),
+                               ("svo_save_voxel_maps", [p, p, i, p, p, p, i]), ("svo_submit_load_voxel_maps", [p, p, i, p, i, i, p]),
+                               ("svo_load_voxel_maps", [p, p, i, p, i, i, p]), ("svo_ctx_resize_voxel_maps", [p, p, i, i])):
+            if hasattr(_LIB, name):
+                getattr(_LIB, name).argtypes = argtypes
         _LIB.svo_submit_clear_voxel_maps.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         _LIB.svo_get_voxel_map_info.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         for name in ("svo_submit_pose_updates", "svo_update_poses"):
@@ -1572,6 +1610,53 @@ class Handle:
                                      C.byref(occ), C.byref(carve) if carve is not None else None,
                                      C.byref(keep) if keep is not None else None, C.byref(out)))
         return {n: getattr(out, n) for n, _ in VoxelCarveResult._fields_}
+
+    def voxel_pack(self, m, min_count=0, min_stamp=0, entries=None, capacity=None):
+        """svo_voxel_pack: the kept entries in ascending key order as VOXEL_ENTRY_DTYPE records, accumulators verbatim.
+        entries: a device tensor (or address, with `capacity` records) that receives them, or None: a uint8 tensor
+        [kept, 40] of exactly the kept count is made. Returns (entries, n)."""
+        vm, f = _voxel_map(m), VoxelFilter(int(min_count), int(min_stamp))
+        n = C.c_int64(-1)
+        if entries is None:
+            _check(lib().svo_voxel_pack(self._h, C.byref(vm), C.byref(f), None, C.c_int64(0), C.byref(n)))
+            capacity = n.value
+            entries = torch.empty((max(capacity, 1), VOXEL_ENTRY_DTYPE.itemsize), dtype=torch.uint8, device="cuda")[:capacity]
+        elif capacity is None:
+            capacity = entries.numel() * entries.element_size() // VOXEL_ENTRY_DTYPE.itemsize
+        p = entries.data_ptr() if isinstance(entries, torch.Tensor) else int(entries)
+        _check(lib().svo_voxel_pack(self._h, C.byref(vm), C.byref(f), C.c_void_p(p), C.c_int64(int(capacity)), C.byref(n)))
+        return entries, n.value
+
+    def voxel_merge(self, spans, maps):
+        """svo_voxel_merge: spans = [(entries, map index, voxel)] with entries a device tensor of 40-byte
+        VOXEL_ENTRY_DTYPE records, (address, n) or None, and voxel the edge their keys were made with; maps = [(tensor
+        or address, VoxelParams)]. One launch; raises (SVO_ERR_CAPACITY, nothing written) when a load bound fails.
+        Returns per map a dict: n_offered, n_merged, n_skipped, n_claimed. Complete on return."""
+        arr = (VoxelEntrySpan * max(len(spans), 1))()
+        for i, (entries, mi, voxel) in enumerate(spans):
+            if entries is None:
+                ptr, n = None, 0
+            elif isinstance(entries, torch.Tensor):
+                n = entries.numel() * entries.element_size() // VOXEL_ENTRY_DTYPE.itemsize
+                ptr = entries.data_ptr() if n else None
+            else:
+                ptr, n = entries
+            arr[i] = VoxelEntrySpan(int(ptr) if ptr else None, int(n), int(mi), float(voxel))
+        marr = (VoxelMap * max(len(maps), 1))(*[_voxel_map(m) for m in maps])
+        res = (VoxelMergeResult * max(len(maps), 1))()
+        _check(lib().svo_voxel_merge(self._h, len(spans), arr, len(maps), marr, res))
+        return [{n: getattr(res[i], n) for n, _ in VoxelMergeResult._fields_} for i in range(len(maps))]
+
+    def voxel_rehash(self, m, log2_capacity):
+        """svo_voxel_rehash: the entries, n_voxels and cumulative counters of map m in a new map of 1 << log2_capacity
+        entries with the same voxel and drop_flags, in a device tensor of its own; m is only read. Raises
+        (SVO_ERR_CAPACITY) when the entries exceed the new load limit. Returns the (tensor, params) pair."""
+        vm = _voxel_map(m)
+        nbytes = voxel_map_bytes(log2_capacity)
+        device = m[0].device if isinstance(m[0], torch.Tensor) else "cuda"
+        data = torch.empty(nbytes, dtype=torch.uint8, device=device)
+        _check(lib().svo_voxel_rehash(self._h, C.byref(vm), C.c_void_p(data.data_ptr()), int(log2_capacity)))
+        return data, VoxelParams(vm.params.voxel, int(log2_capacity), vm.params.drop_flags, 0)
 
     def render_scene(self, srcs, cameras, offsets, style, pixels):
         """svo_render_scene: the viewer's scene of keyframe sets and lines as images of `style` (a SceneStyle). srcs:

@@ -510,6 +510,153 @@ class VoxelMaps(PointJob):
         return self._records(int(e["first_point"]), int(e["n_points"]))
 
 
+# the 64-byte header of VoxelSaves.tobytes, little endian; the records follow
+VOXEL_SAVE_MAGIC, VOXEL_SAVE_VERSION = 0x45585653, 1       # "SVXE"
+VOXEL_SAVE_HEADER_DTYPE = np.dtype([("magic", "<u4"), ("version", "<u4"), ("voxel_bits", "<u4"), ("drop_flags", "<u4"), ("log2_capacity", "<i4"),
+                                    ("_pad", "<i4"), ("n", "<i8"), ("n_fused", "<i8"), ("n_outside", "<i8"), ("overflow", "<i8"), ("_pad2", "<i8")])
+assert VOXEL_SAVE_HEADER_DTYPE.itemsize == 64
+
+
+class VoxelSaves(Job):
+    """One svo_submit_save_voxel_maps: owns the buffers the library writes. After wait(): `segments`
+    (hip_lib.VOXEL_SEGMENT_DTYPE, one per named slot; n_points counts entries), status(i), entries(i), info(i) and
+    tobytes(i). `entries_buffer`: a uint8 [capacity, 40] tensor of hip_lib.VOXEL_ENTRY_DTYPE records, pinned memory in
+    host mode, on the ctx's device in device mode. capacities: the records each named slot's region holds, back to
+    back. `maps`: per named slot what svo_get_voxel_map_info says at this job's own wait() (None for a slot without a
+    map, and for every slot until then: the ctx's wait() does not fill it). tobytes takes from it what the segment does
+    not carry: drop_flags, and n_outside and overflow, which are the map's at that wait and not at the job's queue
+    position (n, n_fused and the records are the job's); without it tobytes raises."""
+
+    def __init__(self, slam, seqs, capacities, min_count, min_stamp, device):
+        n = self._name(slam, seqs, device)
+        caps = [int(c) for c in np.broadcast_to(capacities, (n,))]
+        self.regions = self._per_slot(hip_lib.VOXEL_REGION_DTYPE)[0]
+        self.regions["point_capacity"][:n] = caps
+        self.regions["first_point"][:n] = np.cumsum([0] + caps[:-1]) if n else []
+        self.regions["min_stamp"][:n] = np.broadcast_to(min_stamp, (n,))
+        self.capacity = sum(caps)
+        self._filter = hip_lib.VoxelFilter(int(min_count), 0)
+        self._segments(hip_lib.VOXEL_SEGMENT_DTYPE)
+        self.entries_buffer = self._alloc((max(self.capacity, 1), hip_lib.VOXEL_ENTRY_DTYPE.itemsize), torch.uint8)
+        self._dst = hip_lib.VoxelEntryDst(self._seg.ctypes.data, self.entries_buffer.data_ptr())
+        self.maps = [None] * n
+
+    def _call(self, ctx, mem):
+        return lib().svo_submit_save_voxel_maps(ctx, self._seq_arr, self._n, self.regions.ctypes.data_as(C.c_void_p),
+                                                C.byref(self._filter), C.byref(self._dst), mem)
+
+    def wait(self):
+        super().wait()
+        if self._slam is not None:
+            named = range(self._slam.n) if self.seqs is None else self.seqs
+            self.maps = [self._slam.voxel_map_info(s) for s in named]
+        return self
+
+    def status(self, i):
+        return int(self.segments[i]["status"])
+
+    def info(self, i):
+        """the segment of named slot i"""
+        return self.segments[i]
+
+    def voxel(self, i):
+        """the voxel edge the keys of named slot i were made with (float32)"""
+        return np.float32(self.segments[i]["voxel"])
+
+    def entries(self, i):
+        """the records of named slot i in key order, a view: numpy hip_lib.VOXEL_ENTRY_DTYPE in host mode, a uint8 [n, 40]
+        tensor on the device in device mode; None unless its status is VOXEL_OK"""
+        e = self.segments[i]
+        if int(e["status"]) != hip_lib.VOXEL_OK:
+            return None
+        a = self.entries_buffer[int(e["first_point"]):int(e["first_point"]) + int(e["n_points"])]
+        return a if self.device_mode else a.numpy().view(hip_lib.VOXEL_ENTRY_DTYPE)[:, 0]
+
+    def tobytes(self, i):
+        """named slot i as bytes: a VOXEL_SAVE_HEADER_DTYPE header (magic, version, the voxel edge's bits, drop_flags, the
+        source's log2_capacity, n, and the map's three cumulative counters) and the n records"""
+        ent = self.entries(i)
+        if ent is None:
+            raise ValueError(f"slot {i} of the job holds no entries (status {self.status(i)})")
+        if self.maps[i] is None:
+            raise ValueError(f"slot {i}: tobytes needs the map's drop_flags and counters, which this job's own wait() reads "
+                             "(the ctx's wait() delivers the entries only)")
+        ent = ent.cpu().numpy().view(hip_lib.VOXEL_ENTRY_DTYPE)[:, 0] if self.device_mode else ent
+        e, m = self.segments[i], self.maps[i]
+        head = np.zeros((), VOXEL_SAVE_HEADER_DTYPE)
+        head["magic"], head["version"] = VOXEL_SAVE_MAGIC, VOXEL_SAVE_VERSION
+        head["voxel_bits"] = np.float32(e["voxel"]).view(np.uint32)
+        head["drop_flags"], head["log2_capacity"], head["n"] = m["drop_flags"], e["log2_capacity"], len(ent)
+        head["n_fused"], head["n_outside"], head["overflow"] = e["n_fused"], m["n_outside"], m["overflow"]
+        return head.tobytes() + ent.tobytes()
+
+    @classmethod
+    def frombytes(cls, b):
+        """the VoxelSaves of one slot that tobytes wrote: host mode, bound to no ctx (it cannot be submitted); `header`
+        holds the file's header"""
+        if len(b) < 64:
+            raise ValueError("not a saved voxel map: shorter than its header")
+        head = np.frombuffer(b[:64], VOXEL_SAVE_HEADER_DTYPE)[0]
+        n = int(head["n"])
+        if int(head["magic"]) != VOXEL_SAVE_MAGIC or int(head["version"]) != VOXEL_SAVE_VERSION or n < 0 or len(b) != 64 + 40 * n:
+            raise ValueError("not a saved voxel map: bad magic, version or length")
+        self = cls.__new__(cls)
+        self._slam, self.device_mode, self.seqs, self._n, self._seq_arr = None, False, [0], 1, None
+        self.header = head.copy()
+        self._segments(hip_lib.VOXEL_SEGMENT_DTYPE)
+        e = self.segments[0]
+        e["status"], e["n_points"], e["n_voxels"], e["n_fused"] = hip_lib.VOXEL_OK, n, n, head["n_fused"]
+        e["voxel"], e["log2_capacity"] = np.uint32(head["voxel_bits"]).view(np.float32), head["log2_capacity"]
+        self.capacity = n
+        self.entries_buffer = torch.zeros((max(n, 1), 40), dtype=torch.uint8)
+        self.entries_buffer[:n] = torch.frombuffer(bytearray(b[64:]), dtype=torch.uint8).reshape(n, 40) if n else self.entries_buffer[:0]
+        self.maps = [{"drop_flags": int(head["drop_flags"]), "n_outside": int(head["n_outside"]), "overflow": int(head["overflow"])}]
+        return self
+
+    def submit(self):
+        if self._slam is None:
+            raise ValueError("a VoxelSaves read from bytes belongs to no ctx")
+        return super().submit()
+
+
+class VoxelLoads(Job):
+    """One svo_submit_load_voxel_maps: owns the spans and keeps the entries alive until the job is delivered. After wait():
+    `info` (hip_lib.VOXEL_LOAD_INFO_DTYPE, one per named slot). sources: per named slot entry records (a numpy array of
+    hip_lib.VOXEL_ENTRY_DTYPE, a uint8 [n, 40] tensor on the host or on the ctx's device, or None: no records); voxels:
+    the voxel edge of each. All on the host or all on the device."""
+
+    def __init__(self, slam, seqs, sources, voxels, merge):
+        n = self._name(slam, seqs)
+        if len(sources) != n:
+            raise ValueError(f"{len(sources)} sources for {n} slots")
+        on_device = {isinstance(s, torch.Tensor) and s.is_cuda for s in sources if s is not None and len(s)}
+        if len(on_device) > 1:
+            raise ValueError("the entries of one load job lie all on the host or all on the device")
+        self.device_mode = bool(on_device and on_device.pop())
+        self.mode = hip_lib.VOXEL_LOAD_MERGE if merge else hip_lib.VOXEL_LOAD_REPLACE
+        self._spans = np.zeros(max(n, 1), hip_lib.VOXEL_ENTRY_SPAN_DTYPE)
+        self._keep = []
+        for i, (src, voxel) in enumerate(zip(sources, np.broadcast_to(np.asarray(voxels, np.float32), (n,)))):
+            self._spans[i]["voxel"] = voxel
+            if src is None or not len(src):
+                continue
+            if isinstance(src, torch.Tensor):
+                src = src.contiguous()
+                count, ptr = src.numel() * src.element_size() // 40, src.data_ptr()
+            else:
+                src = np.ascontiguousarray(src, hip_lib.VOXEL_ENTRY_DTYPE)
+                count, ptr = len(src), src.ctypes.data
+            self._keep.append(src)
+            self._spans[i]["entries"], self._spans[i]["n"] = ptr, count
+        self._info, self.info = self._per_slot(hip_lib.VOXEL_LOAD_INFO_DTYPE)
+
+    def _call(self, ctx, mem):
+        return lib().svo_submit_load_voxel_maps(ctx, self._seq_arr, self._n, self._spans.ctypes.data, self.mode, mem, self._info.ctypes.data)
+
+    def status(self, i):
+        return int(self.info[i]["status"])
+
+
 class Scenes(PictureJob):
     """One svo_submit_export_scenes: owns the buffers the library writes. After wait(): `segments`
     (hip_lib.SCENE_SEGMENT_DTYPE, one per named slot), image(i) and `pixels` (PictureJob). cols, rows, pitch,

@@ -197,14 +197,42 @@ def play_queue(slam, frames_of, lengths, time_of=lambda s, k: k / 20.0, order=No
     return where, frames
 
 
-def move(src, src_slots, dst, dst_slots):
+def move(src, src_slots, dst, dst_slots, voxel_maps=False):
     """Move sequences between two ctxs (or two slots of one): a device-mode save of src's slots, their restart,
     then the load into dst's slots (any slot count, group layout or GPU of the same process: the data parts go
     through a copy to dst's device when it differs). Waits for both ctxs. Returns the Snapshots (in dst's memory).
     A slot's camera settings travel with it: a target slot that tracks with other settings is first bound to a rig
     of dst with the source slot's settings (added to dst if it has none). Rectification maps are not part of a
-    snapshot and do not travel: such a rig of dst has none."""
+    snapshot and do not travel: such a rig of dst has none.
+    voxel_maps=True: the slots' voxel maps go along. Every named slot of src and of dst must have a map, pairwise with
+    the same voxel edge (ValueError before anything moves). After the sequences have moved: a device-mode save of
+    src's maps, a copy to dst's device where it differs, a replace load into dst's maps, and src's maps are cleared.
+    Returns (Snapshots, VoxelLoads); a dst map too small for the entries comes back VOXEL_LOAD_FULL in the VoxelLoads,
+    is left unchanged, and src's map is then not cleared."""
+    from . import hip_lib
     from .stereo_slam import Snapshot
+    if voxel_maps:
+        for s_slot, d_slot in zip(src_slots, dst_slots):
+            a, b = src.voxel_map_info(s_slot), dst.voxel_map_info(d_slot)
+            if a is None or b is None:
+                raise ValueError(f"move(voxel_maps=True): slot {s_slot} of src or slot {d_slot} of dst has no voxel map")
+            if np.float32(a["voxel"]).tobytes() != np.float32(b["voxel"]).tobytes():
+                raise ValueError(f"move(voxel_maps=True): slot {d_slot} of dst has voxel edge {b['voxel']!r}, slot {s_slot} of src {a['voxel']!r}")
+    snaps = _move_sequences(src, src_slots, dst, dst_slots, Snapshot)
+    if not voxel_maps:
+        return snaps
+    saves = src.save_voxel_maps(src_slots, device=True)
+    entries = [saves.entries(i) for i in range(len(src_slots))]
+    if dst.device != src.device:
+        entries = [e.to(dst.device) for e in entries]
+    loads = dst.load_voxel_maps(dst_slots, entries, voxel=[saves.voxel(i) for i in range(len(src_slots))])
+    moved = [s for i, s in enumerate(src_slots) if loads.status(i) == hip_lib.VOXEL_LOADED]
+    if moved:
+        src.clear_voxel_maps(moved)
+    return snaps, loads
+
+
+def _move_sequences(src, src_slots, dst, dst_slots, Snapshot):
     snaps = src.save(src_slots, device=True)
     src.restart(src_slots)
     if dst.device != src.device:

@@ -48,7 +48,9 @@ dense cloud (--cloud-step, --cloud-lr, --cloud-max-depth) into a voxel map of ed
 every surface once, the keyframes that saw a voxel averaged) and writes it as one PLY at the end; --dense-map-window METRES
 and --dense-map-keep N prune it behind every fuse (a box around the camera; what the last N fuses reached), --dense-map-carve
 MARGIN carves it in front of every fuse (what the current frame's dense depth sees through leaves); --scene-fused V draws
-that map in the pictures of --dump-scene.
+that map in the pictures of --dump-scene. --save-dense-map FILE writes the map's raw entries (counts, sums, stamps) at the
+end, --load-dense-map FILE merges such a file into the empty map before the first fuse (together: a run continues
+yesterday's map), and --dense-map-grow N moves a map that is full into a larger table, up to 1 << N entries.
 --dump-ar DIR writes per frame DIR/000000_ar.ppm: the AR demo's picture (src/ar-app/), a lit box of edge --ar-box
 fixed at the world point --ar-at over the frame's left image, seen from the tracked pose; the default placement is the
 demo's, half a metre in front of the first camera (AnimatedEntity.qml:56). If the pose is right the box stands still.
@@ -68,6 +70,7 @@ import numpy as np
 import torch
 
 from . import hip_lib, synth
+from .jobs import VOXEL_SAVE_HEADER_DTYPE, VOXEL_SAVE_MAGIC, VOXEL_SAVE_VERSION, VoxelSaves
 from .stereo_slam import StereoSlam
 
 # key in the YAML -> CameraSettings field (src/app/image_input.cpp:16-36)
@@ -433,7 +436,7 @@ class Replay:
                  dump_cloud=None, cloud_step=4, cloud_max_depth=0.0, disparity_lr=None, cloud_lr=None, scene_dense=None,
                  scene_dense_lr=None, scene_dense_max_depth=0.0, scene_accumulate=0, dump_dense_map=None, dense_map_voxel=None,
                  dense_map_log2=20, dense_map_min_count=0, dense_map_window=None, dense_map_keep=None, dense_map_carve=None, scene_fused=None, ar_occlusion=None, disparity_sgm=None, cloud_sgm=None,
-                 dense_map_sgm=None, scene_dense_sgm=None, ar_sgm=None):
+                 dense_map_sgm=None, scene_dense_sgm=None, ar_sgm=None, save_dense_map=None, load_dense_map=None, dense_map_grow=None):
         """fast=False keeps the library default: the reference-order Gauss-Newton (bit-exact traces).
         rectify_maps = (left maps, right maps): the frames fed are raw and are rectified on the GPU.
         calibration = (left, right) CameraCalibrations: the same, with the maps built on the GPU as well.
@@ -531,6 +534,14 @@ class Replay:
             if not 0 <= float(dense_map_carve) < float("inf"):
                 raise ValueError("dense_map_carve must be finite and >= 0")
             self.dense_map_carve = float(dense_map_carve)
+        # (the map kept across runs: its raw entries written at finish(), merged into the empty map before the first fuse;
+        # dense_map_grow: a full map moves into a larger table, up to 1 << dense_map_grow entries)
+        self.save_dense_map, self.load_dense_map = save_dense_map, load_dense_map
+        self.dense_map_grow = None if dense_map_grow is None else int(dense_map_grow)
+        if (save_dense_map or load_dense_map or dense_map_grow is not None) and self.dense_map_voxel is None:
+            raise ValueError("save_dense_map, load_dense_map and dense_map_grow need a dense map")
+        if self.dense_map_grow is not None and not self.dense_map_log2 <= self.dense_map_grow <= 26:
+            raise ValueError("dense_map_grow must be dense_map_log2 .. 26")
         self._dense_map_set, self._fused_job = False, None
         for d in (dump_views, dump_scene, dump_ar, dump_disparity, dump_cloud):
             if d:
@@ -637,13 +648,41 @@ class Replay:
         if not self._dense_map_set:
             self.slam.set_voxel_maps(self.dense_map_voxel, self.dense_map_log2)
             self._dense_map_set = True
+            if self.load_dense_map:
+                self._load_dense_map()
         how = dict(lr_check=self.cloud_lr) if self.dense_map_sgm is None else dict(sgm=self.dense_map_sgm)
         carve = None if self.dense_map_carve is None else dict(margin=self.dense_map_carve, step=self.cloud_step, max_depth=self.cloud_max_depth, **how)
         return self.slam.fuse_new_keyframes(step=self.cloud_step, max_depth=self.cloud_max_depth, prune=self.dense_map_prune, carve=carve,
-                                            **how) is not None
+                                            grow=self.dense_map_grow, **how) is not None
+
+    def _load_dense_map(self):
+        """the entries of load_dense_map (VoxelSaves.tobytes) merged into the map that was just set: the same voxel edge,
+        bit for bit; a map too small for them is resized first where dense_map_grow allows"""
+        with open(self.load_dense_map, "rb") as f:
+            saved = VoxelSaves.frombytes(f.read())
+        if np.float32(saved.voxel(0)).tobytes() != np.float32(self.dense_map_voxel).tobytes():
+            raise ValueError(f"{self.load_dense_map} was made with voxel edge {float(saved.voxel(0))!r}, the map has {self.dense_map_voxel!r}")
+        log2 = self.dense_map_log2
+        while len(saved.entries(0)) > (1 << log2) - (1 << log2) // 4 and self.dense_map_grow is not None and log2 < self.dense_map_grow:
+            log2 += 1
+        if log2 != self.dense_map_log2:
+            self.slam.resize_voxel_maps(log2)
+        info = self.slam.load_voxel_maps(None, saved, merge=True).info[0]
+        if int(info["status"]) != hip_lib.VOXEL_LOADED:
+            raise ValueError(f"{self.load_dense_map} holds {len(saved.entries(0))} entries: too many for a map of 1 << {log2} (dense_map_log2, dense_map_grow)")
 
     def finish(self):
-        """what is written once, after the last frame: the dense map of dump_dense_map"""
+        """what is written once, after the last frame: the dense map of dump_dense_map, the entries of save_dense_map"""
+        if self.save_dense_map:
+            if self._dense_map_set:
+                blob = self.slam.save_voxel_maps([0]).tobytes(0)
+            else:                                   # (no frame ever came: an empty map of these params)
+                head = np.zeros((), VOXEL_SAVE_HEADER_DTYPE)
+                head["magic"], head["version"], head["log2_capacity"] = VOXEL_SAVE_MAGIC, VOXEL_SAVE_VERSION, self.dense_map_log2
+                head["voxel_bits"] = np.float32(self.dense_map_voxel).view(np.uint32)
+                blob = head.tobytes()
+            with open(self.save_dense_map, "wb") as f:
+                f.write(blob)
         if self.dump_dense_map:
             points = self.slam.get_voxel_map(min_count=self.dense_map_min_count) if self._dense_map_set else None
             write_ply(self.dump_dense_map, points if points is not None else np.zeros(0, hip_lib.MAP_POINT_DTYPE))
@@ -803,6 +842,14 @@ def build_parser():
     ap.add_argument("--scene-fused", metavar="V", type=float, default=None,
                     help="--dump-scene also draws the fused dense map of voxel edge V (the map of --dump-dense-map), exported to "
                          "device memory whenever a keyframe was fused")
+    ap.add_argument("--save-dense-map", metavar="FILE", default=None,
+                    help="write the raw entries of the fused dense map (counts, sums and stamps, not the means) at the end of the run: "
+                         "what --load-dense-map takes; needs --dense-map-voxel")
+    ap.add_argument("--load-dense-map", metavar="FILE", default=None,
+                    help="merge the entries of a --save-dense-map file into the empty map before the first fuse (the same voxel edge): "
+                         "together with --save-dense-map a run continues yesterday's map")
+    ap.add_argument("--dense-map-grow", metavar="N", type=int, default=None,
+                    help="a dense map that is full moves into a larger table, one step of --dense-map-log2 at a time, up to 1 << N entries")
     ap.add_argument("--frames", type=int, default=100)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--rate", type=float, default=20.0, help="frames per second of the time stamps")
@@ -818,7 +865,7 @@ def check_dense_map_args(ap, args):
     """what --dump-dense-map and --scene-fused need of each other and of their values (ap.error: exits with status 2)"""
     if args.dump_dense_map and args.dense_map_voxel is None:
         ap.error("--dump-dense-map needs --dense-map-voxel")
-    if args.dense_map_voxel is not None and not (args.dump_dense_map or args.scene_fused is not None):
+    if args.dense_map_voxel is not None and not (args.dump_dense_map or args.scene_fused is not None or args.save_dense_map):
         ap.error("--dense-map-voxel needs --dump-dense-map")
     for name, v in (("--dense-map-voxel", args.dense_map_voxel), ("--scene-fused", args.scene_fused)):
         if v is not None and not (v > 0 and v < float("inf")):
@@ -829,6 +876,10 @@ def check_dense_map_args(ap, args):
         ap.error("--scene-fused and --dense-map-voxel name one map: give the same edge")
     if not 10 <= args.dense_map_log2 <= 26:
         ap.error("--dense-map-log2 must be 10 .. 26")
+    if (args.save_dense_map or args.load_dense_map or args.dense_map_grow is not None) and args.dense_map_voxel is None and args.scene_fused is None:
+        ap.error("--save-dense-map, --load-dense-map and --dense-map-grow need --dense-map-voxel")
+    if args.dense_map_grow is not None and not args.dense_map_log2 <= args.dense_map_grow <= 26:
+        ap.error("--dense-map-grow must be --dense-map-log2 .. 26")
     if args.dense_map_min_count < 0:
         ap.error("--dense-map-min-count must be >= 0")
     if (args.dense_map_window is not None or args.dense_map_keep is not None) and not (args.dump_dense_map or args.scene_fused is not None):
@@ -925,6 +976,7 @@ def main(argv=None):
                 scene_accumulate=args.scene_accumulate, dump_dense_map=args.dump_dense_map, dense_map_voxel=args.dense_map_voxel,
                 dense_map_log2=args.dense_map_log2, dense_map_min_count=args.dense_map_min_count, dense_map_window=args.dense_map_window,
                 dense_map_keep=args.dense_map_keep, dense_map_carve=args.dense_map_carve, scene_fused=args.scene_fused,
+                save_dense_map=args.save_dense_map, load_dense_map=args.load_dense_map, dense_map_grow=args.dense_map_grow,
                 ar_occlusion=occlusion, dense_map_sgm=split(args.dense_map_sgm), scene_dense_sgm=split(args.scene_dense_sgm),
                 ar_sgm=split(args.ar_sgm))
     for k, (left, right, t) in enumerate(frames):

@@ -16,7 +16,7 @@ import torch
 from . import hip_lib
 from .hip_lib import POSE_SAMPLE_CHAIN, POSE_SAMPLE_DTYPE, CameraSettings, SvoError, _check, lib
 from .jobs import (KP_INFO_DTYPE, ArPictures, Clouds, Disparities, Export, Carve, Frame, Fusion, MapExport, Prune,  # noqa: F401
-                   Scenes, Snapshot, Views, VoxelMaps, caller_memory, int_array, named_slots)
+                   Scenes, Snapshot, Views, VoxelLoads, VoxelMaps, VoxelSaves, caller_memory, int_array, named_slots)
 
 
 class GnTrace(C.Structure):
@@ -700,11 +700,33 @@ class StereoSlamBatch:
         style = hip_lib.cloud_style(step, win, search_x, search_y, "world", "compact", min_disparity, max_depth, max_mean_cost)
         return Fusion(self, what, seqs, style, self._stereo_check(lr_check), stamp, *sgm).submit()
 
-    def fuse_clouds(self, what="last_keyframes", seqs=None, **kw):
-        """submit_fuse + wait"""
-        return self.submit_fuse(what, seqs, **kw).wait()
+    def fuse_clouds(self, what="last_keyframes", seqs=None, grow=None, **kw):
+        """submit_fuse + wait. grow=N: the maps of the slots that came back FUSE_FULL are resized (resize_voxel_maps)
+        one step of log2_capacity at a time, up to N, and each is fused once more with the same stamp at the same queue
+        position (nothing else was submitted in between); the returned Fusion holds the second answer for them. A slot
+        still FUSE_FULL at N stays so. grow=None: the one job, as ever."""
+        job = self.submit_fuse(what, seqs, **kw).wait()
+        return job if grow is None else self._grow_and_fuse_again(job, grow)
 
-    def fuse_new_keyframes(self, seqs=None, prune=None, carve=None, **kw):
+    def _grow_and_fuse_again(self, job, grow):
+        """fuse_clouds(grow=) on a delivered Fusion: resize what came back FUSE_FULL, fuse it again, keep the second answer"""
+        named = list(range(self.n)) if job.seqs is None else job.seqs
+        full = [i for i, f in enumerate(job.info) if int(f["status"]) == hip_lib.FUSE_FULL]
+        while full:
+            log2 = {i: self.voxel_map_info(named[i])["log2_capacity"] for i in full}
+            full = [i for i in full if log2[i] < int(grow)]
+            if not full:
+                break
+            for lg in sorted(set(log2[i] for i in full)):
+                self.resize_voxel_maps(lg + 1, [named[i] for i in full if log2[i] == lg])
+            again = Fusion(self, job.what, [named[i] for i in full], job.style, None if job.sgm is not None else job.check, job.stamp, job.sgm,
+                           job.check if job.sgm is not None else None).submit().wait()
+            for j, i in enumerate(full):
+                job.info[i] = again.info[j]
+            full = [i for i in full if int(job.info[i]["status"]) == hip_lib.FUSE_FULL]
+        return job
+
+    def fuse_new_keyframes(self, seqs=None, prune=None, carve=None, grow=None, **kw):
         """fuse_clouds("last_keyframes") of only those slots whose newest keyframe changed since this method last fused
         them (the bookkeeping is here, on the host: it waits for the queues to read the keyframe counts). Returns the
         Fusion, or None when no slot has a new keyframe. prune: a dict of submit_prune's keywords; the prune of the
@@ -712,7 +734,8 @@ class StereoSlamBatch:
         keep_stamps=N in it stands for min_stamp = stamp - N + 1 with `stamp` this fuse's: what the last N fuses of
         this object reached stays. carve: a dict of submit_carve's keywords (margin at least); the carve of the fused
         slots by their current frames is queued in FRONT of the fuse, so that what the camera sees through leaves before
-        the new cloud arrives (the Carve is the Fusion's `.carve`)."""
+        the new cloud arrives (the Carve is the Fusion's `.carve`). grow=N: as fuse_clouds(grow=N); the second fuse of a
+        slot that was full then runs behind this call's prune."""
         named = named_slots(self, seqs, explicit=True)[0]
         self.wait()
         fresh = []
@@ -733,6 +756,8 @@ class StereoSlamBatch:
                 prune["min_stamp"] = max(0, job.stamp - int(keep_stamps) + 1)
             job.prune = self.submit_prune([s for s, _ in fresh], **prune)
         job.wait()
+        if grow is not None:
+            self._grow_and_fuse_again(job, grow)
         for (s, newest), f in zip(fresh, job.info):
             if int(f["status"]) == hip_lib.FUSE_OK:
                 self._fused_keyframe[s] = newest
@@ -751,6 +776,53 @@ class StereoSlamBatch:
     def export_voxel_maps(self, seqs=None, **kw):
         """submit_voxel_maps + wait"""
         return self.submit_voxel_maps(seqs, **kw).wait()
+
+    def submit_save_voxel_maps(self, seqs=None, min_count=0, min_stamp=0, device=False, capacities=None):
+        """svo_submit_save_voxel_maps: queue the save of the voxel maps of the slots `seqs` (None: all) as their raw
+        entries (hip_lib.VOXEL_ENTRY_DTYPE: key, counts, sums and stamps verbatim) in key order: what load_voxel_maps
+        takes, and nothing is lost on the way. capacities, min_count, min_stamp, device: as submit_voxel_maps. Returns
+        a VoxelSaves, valid after its wait()."""
+        if capacities is None:
+            named = named_slots(self, seqs, explicit=True)[0]
+            capacities = [(self.voxel_map_info(s) or {"n_voxels": 0})["n_voxels"] for s in named]
+        return VoxelSaves(self, seqs, capacities, min_count, min_stamp, device).submit()
+
+    def save_voxel_maps(self, seqs=None, **kw):
+        """submit_save_voxel_maps + wait"""
+        return self.submit_save_voxel_maps(seqs, **kw).wait()
+
+    def submit_load_voxel_maps(self, seqs, saves, merge=False, voxel=None):
+        """svo_submit_load_voxel_maps: queue a load into the voxel maps of the slots `seqs` (None: all), behind what was
+        submitted so far. saves: a delivered VoxelSaves (its named slot i goes to seqs[i]; a slot that had no map when it
+        was saved is left out of the job, whose `seqs` then names the others), or per slot entry records
+        (numpy hip_lib.VOXEL_ENTRY_DTYPE, a uint8 [n, 40] tensor, None) with voxel= the edge their keys were made with
+        (one, or one per slot). merge=False: a map is cleared first and then holds exactly the entries; merge=True: they
+        are added to what it holds, to the bit as if their records had been fused. The edge must be the map's own, bit
+        for bit. Returns a VoxelLoads, valid after its wait(): `info` says per slot what happened (VOXEL_LOAD_FULL: the
+        map is too small and unchanged: resize_voxel_maps)."""
+        if isinstance(saves, VoxelSaves):
+            named = named_slots(self, seqs, explicit=True)[0]
+            if len(named) != len(saves.segments):
+                raise ValueError(f"a VoxelSaves of {len(saves.segments)} slots for {len(named)} slots")
+            small = [i for i in range(len(named)) if saves.status(i) == hip_lib.VOXEL_TOO_SMALL]
+            if small:
+                raise ValueError(f"slots {small} of the VoxelSaves came back VOXEL_TOO_SMALL: they hold no entries")
+            ok = [i for i in range(len(named)) if saves.status(i) == hip_lib.VOXEL_OK]     # (a slot that had no map is left out of the job)
+            seqs, voxel, saves = [named[i] for i in ok], [saves.voxel(i) for i in ok], [saves.entries(i) for i in ok]
+        elif voxel is None:
+            raise ValueError("entries without a VoxelSaves need voxel=")
+        return VoxelLoads(self, seqs, list(saves), voxel, merge).submit()
+
+    def load_voxel_maps(self, seqs, saves, **kw):
+        """submit_load_voxel_maps + wait"""
+        return self.submit_load_voxel_maps(seqs, saves, **kw).wait()
+
+    def resize_voxel_maps(self, log2_capacity, seqs=None):
+        """svo_ctx_resize_voxel_maps: the voxel maps of the slots `seqs` (None: all; slots without a map are skipped) move
+        into tables of 1 << log2_capacity entries (10 .. 26) with every entry, count, sum, stamp and counter kept. Waits
+        for the queues. Raises (SVO_ERR_CAPACITY, nothing changed) when a slot's entries do not fit."""
+        seqs, n, arr = named_slots(self, seqs)
+        _check(lib().svo_ctx_resize_voxel_maps(self._ctx, arr, n, int(log2_capacity)))
 
     def submit_prune(self, seqs=None, min_count=0, min_stamp=0, radius=None, center="pose"):
         """svo_submit_prune_voxel_maps: queue a prune of the voxel maps of the slots `seqs` (None: all) behind what was
@@ -1040,6 +1112,19 @@ class StereoSlam(StereoSlamBatch):
         """the slot's voxel map as a numpy array of hip_lib.MAP_POINT_DTYPE in key order (export_voxel_maps of the one
         slot: min_count, min_stamp); None without a map"""
         return self._get(self.export_voxel_maps, lambda job: job.points(0), None, **kw)
+
+    def save_voxel_map(self, **kw):
+        """the slot's voxel map as a VoxelSaves (save_voxel_maps of the one slot): entries(0), tobytes(0)"""
+        return self.save_voxel_maps([0], **kw)
+
+    def load_voxel_map(self, save, merge=False, **kw):
+        """load_voxel_maps of the one slot from a VoxelSaves (or entry records with voxel=): its record of
+        hip_lib.VOXEL_LOAD_INFO_DTYPE"""
+        return self.load_voxel_maps([0], save if isinstance(save, VoxelSaves) else [save], merge=merge, **kw).info[0].copy()
+
+    def resize_voxel_map(self, log2_capacity):
+        """resize_voxel_maps of the one slot"""
+        self.resize_voxel_maps(log2_capacity, [0])
 
     def get_scene(self, camera="front", **kw):
         """the viewer's 3-D picture of the map as a numpy array [rows, cols, 3 | 4] (export_scenes of the one slot:

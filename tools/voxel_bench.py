@@ -35,6 +35,17 @@ Prints one JSON line.
              words, the stage pass evaluates the rule again). The prune legs are this library's: its plain prune kernels have the
              parent's registers, LDS and occupancy (profiles/voxel_carve_registers.txt). The map is restored from a copy ahead of every timed call, untimed; the legs alternate in
              one process, median of `--repeats` each.
+  --entries  instead of all that (writes profiles/voxel_entries_bench.json): a map of 1 << 24 entries at 0.75 and at
+             0.25 load (distinct voxels, fused with two stamps). svo_voxel_pack beside svo_voxel_extract of the same map (the same
+             passes; 40 B leave per entry, not 16). svo_voxel_merge of the packed span into an empty map (of 1 << 25 entries, so
+             that the load bound admits the next leg too) and into one that holds half of its keys, beside svo_voxel_fuse of as many records in both forms of its kernel into the same two
+             maps; and the same records as `--entries-slots` spans into as many maps of a quarter of the size in one launch
+             (one map per slot). svo_voxel_rehash to log2 + 1 beside svo_voxel_prune keeping everything. And, wall clock, a
+             ctx's svo_ctx_resize_voxel_maps to log2 + 1 beside the host path it replaces: the map exported to the host, a
+             larger map set, the means uploaded and fused (svo_voxel_fuse into a map of the caller's: a ctx takes records
+             only from its own clouds), which loses the counts, sums and stamps that the resize keeps. Targets are
+             restored ahead of every timed call, untimed; the first round warms up; the legs alternate in one process,
+             median of `--repeats` each.
 """
 import argparse
 import datetime
@@ -320,8 +331,127 @@ def carve_leg(args, h):
     return out
 
 
+def alternate(legs, repeats, wall=False):
+    """{name: (fn, before)} in turn, repeats + 1 rounds (the first warms up): {name: ms of every counted round}; device
+    events around fn, or with wall the host clock between two device synchronisations"""
+    ms = {k: [] for k in legs}
+    for _ in range(repeats + 1):
+        for name, (fn, before) in legs.items():
+            if before:
+                before()
+            torch.cuda.synchronize()
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0 = time.perf_counter()
+            a.record()
+            fn()
+            b.record()
+            torch.cuda.synchronize()
+            ms[name].append((time.perf_counter() - t0) * 1e3 if wall else a.elapsed_time(b))
+    return {k: v[1:] for k, v in ms.items()}
+
+
+def lane_form(fn):
+    """fn() under the other form of the fuse kernel: every lane its own atomics"""
+    os.environ["SVO_VOXEL_LANE_ATOMICS"] = "1"
+    try:
+        return fn()
+    finally:
+        del os.environ["SVO_VOXEL_LANE_ATOMICS"]
+
+
+def entries_leg(args, h):
+    import ctypes as C
+    from stereo_svo_slam_amd import synth
+    out = []
+    log2, k = args.entries_log2, args.entries_slots
+    cfg = synth.make_sequence("tiny", 1, 0, device="cpu")[0]
+    for load in (0.75, 0.25):
+        n = int((1 << log2) * load) // k * k
+        idx = np.arange(n)
+        xyz = (np.stack([idx % 512, idx // 512 % 512, idx // (512 * 512)], 1) + 0.5) * args.voxel
+        dev = torch.from_numpy(VR.records(xyz, (1, 2, 3)).view(np.uint8).reshape(-1, 16)).cuda()
+        half = n // 2
+        params = hip_lib.voxel_params(args.voxel, log2)
+        m = h.voxel_new(params)
+        h.voxel_fuse([(dev[:half], 0, 1), (dev[half:], 0, 2)], [m])
+        assert h.voxel_info(m)["n_voxels"] == n
+        ent, got = h.voxel_pack(m)
+        assert got == n
+        pts = torch.empty((n, 16), dtype=torch.uint8, device="cuda")
+        dst = h.voxel_new(hip_lib.voxel_params(args.voxel, log2 + 1))           # (log2 + 1: the load bound admits n records on top of n / 2 entries)
+        h.voxel_fuse([(dev[:half], 0, 1)], [dst])
+        half_full = dst[0].clone()                                # a map that holds half of the span's keys
+        clear, to_half = (lambda: h.voxel_clear(dst)), (lambda: dst[0].copy_(half_full))
+        small = [h.voxel_new(hip_lib.voxel_params(args.voxel, log2 - 2)) for _ in range(k)]       # one map per slot: n / k records each
+        clear_small = lambda: [h.voxel_clear(x) for x in small]
+        per = n // k
+        ent_spans = [(ent[i * per:(i + 1) * per], i, args.voxel) for i in range(k)]
+        rec_spans = [(dev[i * per:(i + 1) * per], i, 1) for i in range(k)]
+        bigger = torch.empty(hip_lib.voxel_map_bytes(log2 + 1), dtype=torch.uint8, device="cuda")
+        vm = hip_lib._voxel_map(m)
+        seen = {}
+        legs = {"pack": (lambda: h.voxel_pack(m, entries=ent, capacity=n), None),
+                "extract": (lambda: h.voxel_extract(m, points=pts, capacity=n), None),
+                "merge_empty": (lambda: seen.__setitem__("empty", h.voxel_merge([(ent, 0, args.voxel)], [dst])), clear),
+                "fuse_empty_group_sums": (lambda: h.voxel_fuse([(dev, 0, 1)], [dst]), clear),
+                "fuse_empty_lane_atomics": (lambda: lane_form(lambda: h.voxel_fuse([(dev, 0, 1)], [dst])), clear),
+                "merge_half": (lambda: seen.__setitem__("half", h.voxel_merge([(ent, 0, args.voxel)], [dst])), to_half),
+                "fuse_half_group_sums": (lambda: h.voxel_fuse([(dev, 0, 1)], [dst]), to_half),
+                "fuse_half_lane_atomics": (lambda: lane_form(lambda: h.voxel_fuse([(dev, 0, 1)], [dst])), to_half),
+                "merge_per_slot": (lambda: h.voxel_merge(ent_spans, small), clear_small),
+                "fuse_per_slot_group_sums": (lambda: h.voxel_fuse(rec_spans, small), clear_small),
+                "fuse_per_slot_lane_atomics": (lambda: lane_form(lambda: h.voxel_fuse(rec_spans, small)), clear_small),
+                "rehash": (lambda: hip_lib._check(hip_lib.lib().svo_voxel_rehash(h._h, C.byref(vm), C.c_void_p(bigger.data_ptr()), log2 + 1)), None),
+                "prune_keep_all": (lambda: h.voxel_prune(m, hip_lib.voxel_keep(min_stamp=1)), None)}
+        ms = alternate(legs, args.repeats)
+        assert seen["empty"][0]["n_claimed"] == n and seen["half"][0]["n_claimed"] == n - half and seen["half"][0]["n_merged"] == n, seen
+        assert h.voxel_info(bigger)["n_voxels"] == n and h.voxel_info(m)["n_voxels"] == n
+        row = {"log2_capacity": log2, "load": load, "entries": n, "slots": k}
+        for name in legs:
+            row[name + "_ms"], row[name + "_all_ms"] = statistics.median(ms[name]), ms[name]
+        for a, b in (("pack", "extract"), ("merge_empty", "fuse_empty_group_sums"), ("merge_empty", "fuse_empty_lane_atomics"),
+                     ("merge_half", "fuse_half_group_sums"), ("merge_half", "fuse_half_lane_atomics"), ("merge_per_slot", "fuse_per_slot_group_sums"),
+                     ("merge_per_slot", "fuse_per_slot_lane_atomics"), ("rehash", "prune_keep_all")):
+            row[f"{a}_over_{b}"] = row[a + "_ms"] / row[b + "_ms"]
+        del dst, half_full, small, bigger
+        torch.cuda.empty_cache()
+
+        # the ctx: the resize beside the host path it replaces (wall clock)
+        os.environ["SVO_GROUPS"] = "1"
+        slam = StereoSlamBatch(cfg, cfg["width"], cfg["height"], 1, 0)
+        stage = h.voxel_new(hip_lib.voxel_params(args.voxel, log2 + 1))
+
+        def restore():
+            slam.set_voxel_maps(args.voxel, log2)
+            assert slam.load_voxel_maps([0], [ent], voxel=args.voxel).status(0) == hip_lib.VOXEL_LOADED
+
+        def host_path():
+            job = slam.export_voxel_maps([0])
+            slam.set_voxel_maps(args.voxel, log2 + 1)
+            rec = torch.from_numpy(job.points(0).view(np.uint8).reshape(-1, 16)).cuda()
+            h.voxel_clear(stage)
+            h.voxel_fuse([(rec, 0, 1)], [stage])
+        ms = alternate({"ctx_resize": (lambda: slam.resize_voxel_maps(log2 + 1), restore), "ctx_host_path": (host_path, restore)}, args.repeats, wall=True)
+        restore()
+        slam.resize_voxel_maps(log2 + 1)
+        info = slam.voxel_map_info(0)
+        assert (info["n_voxels"], info["log2_capacity"], info["n_fused"]) == (n, log2 + 1, n) and h.voxel_info(stage)["n_voxels"] == n
+        slam.close()
+        for name in ms:
+            row[name + "_wall_ms"], row[name + "_all_wall_ms"] = statistics.median(ms[name]), ms[name]
+        row["ctx_host_path_over_ctx_resize"] = row["ctx_host_path_wall_ms"] / row["ctx_resize_wall_ms"]
+        out.append(row)
+        print(json.dumps({k_: v for k_, v in row.items() if "_all_" not in k_}), file=sys.stderr, flush=True)
+        del m, ent, pts, dev, stage
+        torch.cuda.empty_cache()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--entries", action="store_true", help="only the pack, merge, rehash and resize measurement (profiles/voxel_entries_bench.json)")
+    ap.add_argument("--entries-log2", type=int, default=24)
+    ap.add_argument("--entries-slots", type=int, default=4, help="--entries: the maps of the one-map-per-slot legs")
     ap.add_argument("--carve", action="store_true", help="only the carve measurement (profiles/voxel_carve_bench.json)")
     ap.add_argument("--carve-log2", type=int, nargs="+", default=[20, 24])
     ap.add_argument("--prune", action="store_true", help="only the prune measurement (profiles/voxel_prune_bench.json)")
@@ -341,6 +471,14 @@ def main():
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     device = torch.device("cuda", 0)
+    if args.entries:
+        out = {"tool": "tools/voxel_bench.py", "date": datetime.date.today().isoformat(), "command": " ".join(sys.argv),
+               "device": torch.cuda.get_device_name(0), "voxel": args.voxel, "repeats": args.repeats,
+               "entries": entries_leg(args, hip_lib.Handle(0, 1024))}
+        with open(args.out or os.path.join(ROOT, "profiles", "voxel_entries_bench.json"), "w") as fh:
+            json.dump(out, fh, indent=1)
+        print(json.dumps(out))
+        return
     if args.carve:
         out = {"tool": "tools/voxel_bench.py", "date": datetime.date.today().isoformat(), "command": " ".join(sys.argv),
                "device": torch.cuda.get_device_name(0), "voxel": args.voxel, "repeats": args.repeats, "view": [752, 480],
